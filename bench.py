@@ -15,11 +15,18 @@ anything here touches the GPU) and relays rank 0's JSON line; every rank asserts
 configs[4] (Grad-CAM inference of one 1 x 2 x 256^3 patient: eval forward + mmnn_gradcam, s/patient) the same way; they print a JSON line
 of their own metric (the headline line is the default `--config fusion`).
 
-Extra legs (rank 0, N = 1 only): `roofline` -- after the timed region, a few more (untimed) steps with every convolution launch
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` = milliseconds of one timed step).
+`--dump-outputs DIR` then writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in
+all; a fixed, seeded sample of a larger array): the fusion / unimodal step's risk scores, loss and updated parameters and running
+statistics, Grad-CAM's risk scores and attention maps.  The inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds the extra legs below (today's complete report; off by default so that a plain run measures only its headline).
+Extra legs (`--full`, rank 0, N = 1 only): `roofline` -- after the timed region, a few more (untimed) steps with every convolution launch
 bracketed by HIP events on its own launch stream and the backward serialised on one stream (un-overlapped durations); the
 kernel class with the largest total time is reported against the fp32 MFMA peak, the other classes beside it;
 `cpu_baseline` -- the CPU restatement (oracle/, plain torch.nn.functional, parity-checked against the reference) timed on
-the host cores for a bounded sample of the same workload.
+the host cores for a bounded sample of the same workload; with `--config gradcam256`, the backbone forward's event timing and the
+sustained clock behind its `roofline` entry.  `--no-roofline` / `--no-cpu-baseline` drop a leg of `--full`.
 """
 import argparse
 import ctypes
@@ -274,6 +281,28 @@ def measure_clock(L, dev):
     return float(mhz.value) if rc == 0 else None
 
 
+DUMP_BYTES = 64 * 2 ** 20 - 2 ** 16     # --dump-outputs: 64 MB in all, .npy headers included
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  Smallest first, an array is written whole
+    (its own shape) when it fits in an equal share of the space still left, otherwise as a fixed, seeded sample of its flattened
+    elements (1-D, indices ascending; the same indices for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BYTES // 4
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        a = t.detach().to(device="cpu", dtype=torch.float32).numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.size
+
+
 def run_gradcam256(a, dev, L):
     """BASELINE configs[4]: Grad-CAM attention maps of one 1 x 2 x S^3 patient (S = 256): eval-mode HIP forward + mmnn_gradcam."""
     model = build_model(dev, blend=False).eval()
@@ -289,6 +318,18 @@ def run_gradcam256(a, dev, L):
         preds, maps = cam(x)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"risk_scores": preds, **{f"attention_map_{i}": m for i, m in enumerate(maps)}})
+    assert torch.isfinite(preds).all() and all(torch.isfinite(m).all() for m in maps)
+    res = {"metric": "Grad-CAM inference seconds/patient (1 x 2 x %d^3, configs[4])" % s, "value": dt, "unit": "s/patient",
+           "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt * 1e3, "higher_is_better": False, "scaling": "weak",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "configs[4] --inference --images --preop --survival: eval forward of MultiModalModel(DenseNet121-3D(in=2), MLP(32)) "
+                                  "+ mmnn_gradcam (closed-form gradient, pooled weighting, min-max, trilinear up-sampling of 2 maps)",
+                      "volume": [2, s, s, s], "tabular": N_CLIN, "batch": 1},
+           "reference_cpu_s_per_patient": "23-36 (BASELINE.md, reference on 8 vCPU)"}
+    if not a.full or a.no_roofline:
+        return res
     # device time of the Grad-CAM arithmetic alone (everything after the model forward): events around the C-ABI call's kernels
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     fwd_ms = []
@@ -302,20 +343,13 @@ def run_gradcam256(a, dev, L):
     fwd = sorted(fwd_ms)[1]
     out_bytes = 4.0 * len(maps) * s ** 3
     flops = 778.5e9 * (s / 256.0) ** 3                        # eval forward of one 2 x 256^3 volume
-    assert torch.isfinite(preds).all() and all(torch.isfinite(m).all() for m in maps)
-    return {"metric": "Grad-CAM inference seconds/patient (1 x 2 x %d^3, configs[4])" % s, "value": dt, "unit": "s/patient",
-            "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt * 1e3, "higher_is_better": False, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "configs[4] --inference --images --preop --survival: eval forward of MultiModalModel(DenseNet121-3D(in=2), MLP(32)) "
-                                   "+ mmnn_gradcam (closed-form gradient, pooled weighting, min-max, trilinear up-sampling of 2 maps)",
-                       "volume": [2, s, s, s], "tabular": N_CLIN, "batch": 1},
-            "roofline": {"bound": "mfma", "kernel": "eval-mode backbone forward (all convolutions)", "achieved": flops / (fwd * 1e-3) / 1e12,
-                         "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": flops / (fwd * 1e-3) / 1e12 / PEAK_FP32_TFLOPS, "traffic": None,
-                         "note": "fp32-equivalent FLOPs of the whole eval forward against the fp32 MFMA peak; the conv2 layers of the 64^3 and 32^3 blocks run "
-                                 "on the bf16 pipe with three-piece operands (csrc/conv3_bf16x3.hip), so this is a throughput figure, not one kernel's roofline",
-                         "backbone_forward_ms": fwd, "gradcam_tail_ms": dt * 1e3 - fwd,
-                         "upsample_bytes_written": out_bytes, "clock_mhz": measure_clock(L, dev)},
-            "reference_cpu_s_per_patient": "23-36 (BASELINE.md, reference on 8 vCPU)"}
+    res["roofline"] = {"bound": "mfma", "kernel": "eval-mode backbone forward (all convolutions)", "achieved": flops / (fwd * 1e-3) / 1e12,
+                       "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": flops / (fwd * 1e-3) / 1e12 / PEAK_FP32_TFLOPS, "traffic": None,
+                       "note": "fp32-equivalent FLOPs of the whole eval forward against the fp32 MFMA peak; the conv2 layers of the 64^3 and 32^3 blocks run "
+                               "on the bf16 pipe with three-piece operands (csrc/conv3_bf16x3.hip), so this is a throughput figure, not one kernel's roofline",
+                       "backbone_forward_ms": fwd, "gradcam_tail_ms": dt * 1e3 - fwd,
+                       "upsample_bytes_written": out_bytes, "clock_mhz": measure_clock(L, dev)}
+    return res
 
 
 def main():
@@ -326,10 +360,15 @@ def main():
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--micro-batch", type=int, default=2)
     ap.add_argument("--config", choices=("fusion", "unimodal", "gradcam256"), default="fusion")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the extra legs (per-class kernel roofline, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: all-reduce after the whole backward instead of per dense block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.size is None:
         a.size = 256 if a.config == "gradcam256" else 128
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -377,7 +416,9 @@ def main():
     # Initialisation (plan build, lazily created streams/events, allocator growth, clock ramp after the idle model build) takes
     # a handful of steps; they are run before the W warm-up steps when W itself is too small to cover them, and reported.
     init_steps = max(0, 8 - a.warmup)
-    total_steps = a.steps + a.warmup + init_steps + 1 + 8      # + the untimed steps of the roofline leg
+    # + the untimed steps of the roofline leg (--full); counted in every run, so that the learning-rate schedule, and with it what
+    # each step computes, does not depend on --full
+    total_steps = a.steps + a.warmup + init_steps + 1 + 8
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=1e-3, total_steps=total_steps)
     blender = GradientBlender(CoxPH, survival=True, surv_criterion=surv_criterion)
     inputs, events, durations = synth_batch(dev, rank, a.micro_batch, a.size)
@@ -400,7 +441,7 @@ def main():
         opt.step()
         sched.step()
         opt.zero_grad()
-        return loss
+        return loss, out.detach()
 
     def barrier():
         torch.cuda.synchronize()
@@ -412,11 +453,11 @@ def main():
         step()
     bb = model.backbone if unimodal else model.image_model.model.backbone
     plan = next(iter(bb._plans.values()))["plan"]
-    timed_kernel = rank == 0 and world == 1 and not a.no_roofline
+    timed_kernel = a.full and rank == 0 and world == 1 and not a.no_roofline
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        loss, out = step()
     barrier()
     dt = time.perf_counter() - t0
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -425,6 +466,12 @@ def main():
     dt = float(tmax.item())
     if not torch.isfinite(loss).item():
         raise SystemExit("non-finite loss in the timed region")
+    if a.dump_outputs and rank == 0:
+        # what a caller of the step receives from its last timed call: risk scores, loss, and the model it updated
+        dump_outputs(a.dump_outputs, {
+            "risk_scores": out, "loss": loss.reshape(1),
+            "parameters": torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+            "running_stats": torch.cat([b.detach().reshape(-1) for b in model.buffers() if b.is_floating_point()])})
 
     if rank == 0:
         vols = a.steps * a.micro_batch * world
@@ -471,7 +518,7 @@ def main():
                                "conv_ms_per_step": sum(r["ms_per_step"] for r in rows),
                                "small_extent_ms_per_step": sum(r["ms_per_step"] for r in rows if r["class"].endswith((".b3", ".b4"))),
                                "classes": [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items() if k != "kernel"} for r in rows]}
-        if world == 1 and not a.no_cpu_baseline and not unimodal:
+        if a.full and world == 1 and not a.no_cpu_baseline and not unimodal:
             res["cpu_baseline"] = cpu_baseline(a.micro_batch, a.size)
         print(json.dumps(res), flush=True)
     if world > 1:

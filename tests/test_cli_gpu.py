@@ -90,6 +90,34 @@ def test_bench_two_ranks_at_baseline_extent(tmp_path):
     assert np.isfinite(d["value"]) and d["value"] > 0 and d["steps"] == 2
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline line without the --full legs, and `--dump-outputs DIR` writes the last timed
+    step's risk scores, loss, updated parameters and running statistics as float32 .npy files (at most 64 MB in all) that agree between
+    two runs of the same command (seeded inputs)."""
+    import json
+    from bench import build_model
+    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["higher_is_better"] is True and d["dtype"] == "f32" and d["unit"].startswith("volumes/s")
+        assert np.isfinite(d["ms_per_step"]) and d["ms_per_step"] > 0 and abs(d["value"] - 2e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert "roofline" not in d and "cpu_baseline" not in d
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["loss.npy", "parameters.npy", "risk_scores.npy", "running_stats.npy"]
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 2 ** 20
+        a = {f[:-4]: np.load(out / f) for f in files}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+        assert a["parameters"].size == sum(p.numel() for p in build_model("cpu").parameters()) and a["loss"].shape == (1,)
+        dumps.append(a)
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-3, atol=1e-5, err_msg=k)
+
+
 def _run_ranks(args, out, world=2):
     """main.py under torch.distributed.run, `world` ranks sharing the one card over gloo (on an 8-GPU node the same command runs over RCCL)."""
     import socket

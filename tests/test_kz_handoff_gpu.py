@@ -61,15 +61,14 @@ def test_kz_handoff_matches_unsplit(blocks, dhw, n):
 
 def test_kz_handoff_fenced_library_variant(tmp_path):
     """The portable form of the hand-off (agent-scope release / acquire fences, csrc/fprop.hpp MMNN_KZ_FENCED=1) is what any target other
-    than gfx950 gets.  When the developer variant library has been built (`MMNN_KZ_FENCED=1 python -m mmnn_sts_amd.build`), the same
-    stress runs against it in a fresh process (MMNN_LIB_PATH); skipped otherwise."""
+    than gfx950 gets.  The variant library (built by __graft_entry__.build(), or `MMNN_KZ_FENCED=1 python -m mmnn_sts_amd.build`) runs
+    the same stress in a fresh process (MMNN_LIB_PATH)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = os.path.join(root, "mmnn_sts_amd", "libmmnn_sts_fenced.so")
-    if not os.path.exists(lib):
-        pytest.skip("libmmnn_sts_fenced.so not built")
+    assert os.path.exists(lib), "libmmnn_sts_fenced.so not built: run __graft_entry__.build()"
     env = dict(os.environ, MMNN_LIB_PATH=lib)
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k", "matches_unsplit and blocks0"], env=env, cwd=root,
                        capture_output=True, text=True, timeout=900)

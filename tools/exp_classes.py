@@ -8,7 +8,7 @@ for spec in sys.argv[1:]:
         for kv in spec.split():
             k, v = kv.split("=", 1)
             env[k] = v
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "8", "--no-cpu-baseline"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "8", "--no-cpu-baseline"], env=env,
                        capture_output=True, text=True)
     if r.returncode != 0:
         print(spec, "FAILED", r.stderr[-800:])
