@@ -264,6 +264,47 @@ typedef struct {
 int mmnn_gradcam(const mmnn_gradcam_desc* d, const float* h5, const float* act_in, const float* w_head, const float* w_feat,
                  const float* gamma5, const float* running_var5, float* act, float* grads, float* heat, float* maps, void* stream);
 
+/* ---- input transforms: upstream's train_transforms / val_transforms (main.py:64-92) on a batch of (C, D, H, W) fp32 volumes
+ * (csrc/transforms.hip).  The semantics are pinned by the table in DESIGN §11, not by monai.  `stages` lists the transforms present,
+ * in upstream's order; a random stage fires for sample i when its bit is set in per_sample[i].fire.  Every random draw is made by
+ * the caller (mmnn_sts_amd/transforms.py); the taps and zoom geometry arrive precomputed.  No host synchronisation. */
+#define MMNN_TF_NORMALIZE  (1 << 0)
+#define MMNN_TF_SCALE      (1 << 1)
+#define MMNN_TF_ROTATE     (1 << 2)
+#define MMNN_TF_FLIP       (1 << 3)
+#define MMNN_TF_ZOOM       (1 << 4)
+#define MMNN_TF_RESIZE     (1 << 5)
+#define MMNN_TF_SHIFT      (1 << 6)
+#define MMNN_TF_CONTRAST   (1 << 7)
+#define MMNN_TF_SMOOTH     (1 << 8)
+#define MMNN_TF_SHARPEN    (1 << 9)
+#define MMNN_TF_HIST       (1 << 10)
+#define MMNN_TF_NOISE      (1 << 11)
+#define MMNN_TF_MAX_TAPS   13     /* 2 * radius + 1 for sigma <= 1.5 */
+typedef struct {
+  int32_t n, c, d, h, w;          /* batch and input extent */
+  int32_t out_d, out_h, out_w;    /* Resize target (= d, h, w without MMNN_TF_RESIZE) */
+  int32_t stages;                 /* MMNN_TF_* bits */
+  float norm_mean, norm_std;      /* Normalize */
+} mmnn_transform_desc;
+typedef struct {
+  int32_t fire;                   /* MMNN_TF_* bits of the random stages that apply to this sample */
+  int32_t flip_axis;              /* 0, 1, 2 = D, H, W */
+  double theta;                   /* rotation in the (H, W) plane, radians */
+  uint64_t noise_seed;            /* noise stream of this sample (keyed further by its batch index and the voxel) */
+  int32_t zoom_m[3];              /* zoom: intermediate extent floor(n * z) per axis */
+  int32_t zoom_off[3];            /* zoom: output index o reads intermediate index clamp(o + off, 0, m - 1) */
+  float shift, gamma, alpha, noise_std;
+  float hist_fl[10];              /* histogram-shift control points (reference points: linspace(0, 1, 10)) */
+  int32_t smooth_r[3], sharp1_r[3], sharp2_r[3];          /* tap radius per axis D, H, W */
+  float smooth_k[3][MMNN_TF_MAX_TAPS];                    /* taps k[-r..r] per axis */
+  float sharp1_k[3][MMNN_TF_MAX_TAPS], sharp2_k[3][MMNN_TF_MAX_TAPS];
+} mmnn_transform_params;
+int64_t mmnn_transform_workspace_bytes(const mmnn_transform_desc* d);
+/* in [n][c][d][h][w], out [n][c][out_d][out_h][out_w]; in and out must not overlap; ws >= mmnn_transform_workspace_bytes */
+int mmnn_transform_volumes(const mmnn_transform_desc* d, const mmnn_transform_params* per_sample, const float* in, float* out, void* ws,
+                           int64_t ws_bytes, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

@@ -202,6 +202,16 @@ def to_device(x, device):
     return {k: v.to(device) for k, v in x.items()} if isinstance(x, dict) else x.to(device)
 
 
+def apply_transforms(x, tf):
+    """`--transforms`: upstream's train / val transforms (main.py:64-92) on the device batch -- the image itself for image-only runs,
+    x['image'] for multimodal ones.  None: no transforms."""
+    if tf is None:
+        return x
+    if isinstance(x, dict):
+        return dict(x, image=tf(x["image"]))
+    return tf(x)
+
+
 # ---- survival (main.py:385-601) ----------------------------------------------------------------------------------------------
 def train_survival(model, train_ds, val_ds, args, device, rank, world):
     loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, collate_fn=collate, drop_last=len(train_ds) > args.batch_size)
@@ -226,6 +236,7 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
         losses, c_pred, c_ev, c_du = [], [], [], []
         for i, (x, ev, du) in enumerate(loader):
             x, ev, du = to_device(x, device), ev.to(device), du.to(device)
+            x = apply_transforms(x, getattr(args, "train_tf", None))
             out = model(x)
             loss = blender.computeLoss(out, ev, du)[0] if args.blend else surv_criterion(CoxPH, out, ev, du, device)
             boundary = is_step_boundary(i, len(loader), interval)
@@ -248,6 +259,7 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
         with torch.no_grad():
             for x, ev, du in val_loader:
                 x, ev, du = to_device(x, device), ev.to(device), du.to(device)
+                x = apply_transforms(x, getattr(args, "val_tf", None))
                 p = model(x)
                 if args.blend:
                     _, sel = blender.computeLoss(p, ev, du)
@@ -303,6 +315,7 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
         train_preds, train_gt, val_preds, val_gt = [], [], [], []
         for x, labels, _ in loader:
             x, labels = to_device(x, device), labels.to(device)
+            x = apply_transforms(x, getattr(args, "train_tf", None))
             opt.zero_grad()
             outputs = model(x)
             loss = blender.computeLoss(outputs, labels.float()) if args.blend else criterion(train_loss_function, outputs, labels.float(), device)
@@ -326,6 +339,7 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
         with torch.no_grad():
             for x, labels, _ in val_loader:
                 x, labels = to_device(x, device), labels.to(device)
+                x = apply_transforms(x, getattr(args, "val_tf", None))
                 p = model(x)
                 l = blender.computeLoss(p, labels.float(), no_reduce=True) if args.blend else criterion(loss_function, p, labels.float(), device)
                 test_loss += float(l.sum())
@@ -367,7 +381,7 @@ def inference_survival(model, ds, args, device):
     os.makedirs(os.path.join(args.output_path, "attention_maps"), exist_ok=True)
     for i in range(len(ds)):
         x, ev, du = collate([ds[i]])
-        x = to_device(x, device)
+        x = apply_transforms(to_device(x, device), getattr(args, "val_tf", None))
         with torch.no_grad():
             if cam is not None:
                 p, maps = cam(x)
@@ -405,6 +419,8 @@ def build_arg_parser():
     ap.add_argument("--val_uid_location", type=str, default="./stratified_val_uids.txt")
     ap.add_argument("--config", type=str, default=None)
     ap.add_argument("--blend_update_interval", type=int, default=5)
+    ap.add_argument("--transforms", action="store_true",
+                    help="run upstream's train_transforms / val_transforms on every image batch on the device (resizes to 64^3)")
     # synthetic-data knobs (no counterpart upstream)
     ap.add_argument("--synthetic_patients", type=int, default=16)
     ap.add_argument("--synthetic_size", type=int, default=64)
@@ -426,6 +442,8 @@ def main(argv=None):
         raise SystemExit("--segmentation / --lr_finder / --radiomics are outside the MI355X fusion path (SURVEY 2)")
     if a.bootstrap and not (a.inference and a.survival):
         raise SystemExit("--bootstrap resamples the evaluation of `--inference --survival` (main.py:767-887); it has no meaning for training runs")
+    if a.transforms and not a.images:
+        raise SystemExit("--transforms acts on image volumes: it needs --images")
     if a.image_loc:
         raise SystemExit("image loaders (NIfTI / DICOM / S3) are host I/O outside this path; run without --image_loc for synthetic volumes")
 
@@ -438,6 +456,10 @@ def main(argv=None):
     a.momentum, a.weight_decay = float(hp.get("momentum", 0.9)), float(hp.get("weight_decay", 1e-4))
     a.class_frequencies = list(hp.get("class_frequencies", [0.4] * NUM_CLASSES))     # CLASS_FREQUENCIES is undefined upstream (Q1)
     torch.manual_seed(int(hp.get("seed", 42)))
+    a.train_tf = a.val_tf = None
+    if a.transforms:
+        from mmnn_sts_amd.transforms import train_transforms, val_transforms
+        a.train_tf, a.val_tf = train_transforms, val_transforms
     model = parser.getModel(a)
     if a.multimodal:
         model.blend = a.blend

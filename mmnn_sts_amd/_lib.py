@@ -55,6 +55,24 @@ class MlpParams(Structure):
         "num_batches_tracked")]
 
 
+TF_MAX_TAPS = 13
+
+
+class TransformDesc(Structure):
+    """mmnn_transform_desc (include/mmnn_sts.h)."""
+    _fields_ = [("n", c_int32), ("c", c_int32), ("d", c_int32), ("h", c_int32), ("w", c_int32), ("out_d", c_int32), ("out_h", c_int32),
+                ("out_w", c_int32), ("stages", c_int32), ("norm_mean", c_float), ("norm_std", c_float)]
+
+
+class TransformParams(Structure):
+    """mmnn_transform_params: one sample's draws, with the Gaussian taps and zoom geometry already derived."""
+    _fields_ = [("fire", c_int32), ("flip_axis", c_int32), ("theta", ctypes.c_double), ("noise_seed", c_uint64),
+                ("zoom_m", c_int32 * 3), ("zoom_off", c_int32 * 3), ("shift", c_float), ("gamma", c_float), ("alpha", c_float),
+                ("noise_std", c_float), ("hist_fl", c_float * 10), ("smooth_r", c_int32 * 3), ("sharp1_r", c_int32 * 3),
+                ("sharp2_r", c_int32 * 3), ("smooth_k", (c_float * TF_MAX_TAPS) * 3), ("sharp1_k", (c_float * TF_MAX_TAPS) * 3),
+                ("sharp2_k", (c_float * TF_MAX_TAPS) * 3)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -129,6 +147,10 @@ def lib():
         fn.argtypes = args
     L.mmnn_conv3d_wgrad_workspace_bytes.restype = c_int64
     L.mmnn_conv3d_wgrad_workspace_bytes.argtypes = [POINTER(Conv3dDesc)]
+    L.mmnn_transform_workspace_bytes.restype = c_int64
+    L.mmnn_transform_workspace_bytes.argtypes = [POINTER(TransformDesc)]
+    L.mmnn_transform_volumes.restype = c_int32
+    L.mmnn_transform_volumes.argtypes = [POINTER(TransformDesc), POINTER(TransformParams), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
     L.mmnn_mlp_saved_floats.restype = c_int64
     L.mmnn_mlp_saved_floats.argtypes = [POINTER(MlpDesc)]
     _lib = L

@@ -127,6 +127,23 @@ def add_gradcam(model, output_dir='attention_maps', multimodal=False):
                               "only the multimodal Grad-CAM is part of this path")
 
 
+class Normalize:
+    """utils/utils.py:348-355: (x - mean * max(x)) / (std * max(x)), max over the whole sample (all channels); the sign of max(x) is
+    kept.  A stage of mmnn_sts_amd.transforms.Compose; called on its own it runs as a one-stage pipeline on the device."""
+    bit = 1          # transforms.NORMALIZE
+    prob = None
+
+    def __init__(self, mean, std):
+        if float(std) == 0.0:
+            raise ValueError("Normalize: std must be non-zero")
+        self.mean = float(mean)
+        self.stddev = float(std)
+
+    def __call__(self, image):
+        from ..transforms import Compose
+        return Compose([self])(image)
+
+
 def remap_bhb_keys(entries):
     """Key translation of the BHB-10K pretrained DenseNet121 checkpoint (utils/utils.py:368-384): drop the DataParallel prefix and
     address a dense layer's leaves through its `layers` Sequential.  (The result still says `features.*` where this DenseNet says

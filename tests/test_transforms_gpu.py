@@ -1,0 +1,387 @@
+"""GPU tests of the input transforms (mmnn_sts_amd/transforms.py, csrc/transforms.hip) against a float64 CPU restatement of the
+semantics table: every transform alone with fixed parameters at cubic and ragged extents, the full train / val
+pipelines, per-sample parameters in a batch (including more samples than one launch group holds), the noise stream's statistics
+and determinism, edge cases, and main.py --transforms end to end."""
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from mmnn_sts_amd import transforms as T
+from mmnn_sts_amd.data.constants import IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV
+from mmnn_sts_amd.utils.utils import Normalize
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda:0"
+SHAPES = [(2, 2, 32, 32, 32), (2, 2, 37, 50, 43), (1, 1, 97, 130, 111)]
+
+
+# ---- float64 restatement of the table, one sample (C, D, H, W) at a time -------------------------------------------------------
+def r_normalize(x, mean=IMAGE_DATA_MEAN, std=IMAGE_DATA_STDDEV):
+    m = x.max()
+    return (x - mean * m) / (std * m)
+
+
+def r_scale(x):
+    lo, hi = x.min(), x.max()
+    return torch.zeros_like(x) if hi == lo else (x - lo) / (hi - lo)
+
+
+def r_rotate(x, theta):
+    """Trilinear gather at s = R(theta)(p - c) + c in the (H, W) plane, D fixed, border clamp."""
+    C, D, H, W = x.shape
+    d, h, w = torch.meshgrid(torch.arange(D, dtype=torch.float64), torch.arange(H, dtype=torch.float64),
+                             torch.arange(W, dtype=torch.float64), indexing="ij")
+    ch, cw = (H - 1) / 2, (W - 1) / 2
+    sd = d
+    sh = (math.cos(theta) * (h - ch) - math.sin(theta) * (w - cw) + ch).clamp(0, H - 1)
+    sw = (math.sin(theta) * (h - ch) + math.cos(theta) * (w - cw) + cw).clamp(0, W - 1)
+    out = torch.zeros_like(x)
+    d0, h0, w0 = sd.floor().long(), sh.floor().long(), sw.floor().long()
+    td, th, tw = sd - d0, sh - h0, sw - w0
+    for dd in (0, 1):
+        for hh in (0, 1):
+            for ww in (0, 1):
+                wgt = (td if dd else 1 - td) * (th if hh else 1 - th) * (tw if ww else 1 - tw)
+                di, hi, wi = (d0 + dd).clamp(max=D - 1), (h0 + hh).clamp(max=H - 1), (w0 + ww).clamp(max=W - 1)
+                out += wgt * x[:, di, hi, wi]
+    return out
+
+
+def r_flip(x, axis):
+    return x.flip(axis + 1)
+
+
+def r_area(x, size):
+    return F.adaptive_avg_pool3d(x[None], tuple(size))[0]
+
+
+def r_zoom(x, z):
+    n = x.shape[1:]
+    m = [int(math.floor(k * z)) for k in n]
+    y = r_area(x, m)
+    for ax in range(3):
+        nn_, mm = n[ax], m[ax]
+        if mm < nn_:
+            before = (nn_ - mm) // 2
+            idx = torch.cat([torch.zeros(before, dtype=torch.long), torch.arange(mm), torch.full((nn_ - mm - before,), mm - 1, dtype=torch.long)])
+        else:
+            s = mm // 2 - nn_ // 2
+            idx = torch.arange(s, s + nn_)
+        y = y.index_select(ax + 1, idx)
+    return y
+
+
+def r_shift(x, o):
+    return x + o
+
+
+def r_contrast(x, g):
+    lo, hi = x.min(), x.max()
+    r = hi - lo
+    return ((x - lo) / (r + 1e-7)) ** g * r + lo
+
+
+def r_taps(sigma):
+    t = int(max(4 * sigma, 0.5) + 0.5)
+    return [0.5 * (math.erf((i + 0.5) / (sigma * math.sqrt(2))) - math.erf((i - 0.5) / (sigma * math.sqrt(2)))) for i in range(-t, t + 1)]
+
+
+def r_gauss(x, sig3):
+    for ax, s in enumerate(sig3):
+        k = r_taps(s)
+        t = len(k) // 2
+        n = x.shape[ax + 1]
+        out = torch.zeros_like(x)
+        for j in range(-t, t + 1):
+            # out[i] += k[j] x[i + j], zero outside
+            lo, hi = max(0, -j), min(n, n - j)
+            if hi <= lo:
+                continue
+            out.narrow(ax + 1, lo, hi - lo).add_(k[j + t] * x.narrow(ax + 1, lo + j, hi - lo))
+        x = out
+    return x
+
+
+def r_sharpen(x, s1, s2, a):
+    b = r_gauss(x, s1)
+    bb = r_gauss(b, s2)
+    return b + a * (b - bb)
+
+
+def r_hist(x, fl):
+    lo, hi = float(x.min()), float(x.max())
+    if lo == hi:
+        return x
+    ref = np.linspace(0, 1, 10)
+    y = np.interp(x.numpy(), ref * (hi - lo) + lo, np.asarray(fl) * (hi - lo) + lo)
+    return torch.from_numpy(y)
+
+
+def restate(x, stages, p, size=T.SPATIAL_SIZE):
+    """One sample through the stages present (bits), random stages where p.fire says so; noise is left out (checked statistically)."""
+    x = x.double()
+    if stages & T.NORMALIZE:
+        x = r_normalize(x)
+    if stages & T.SCALE:
+        x = r_scale(x)
+    f = p.fire & stages
+    if f & T.ROTATE:
+        x = r_rotate(x, p.theta)
+    if f & T.FLIP:
+        x = r_flip(x, p.flip_axis)
+    if f & T.ZOOM:
+        x = r_zoom(x, p.zoom)
+    if stages & T.RESIZE and tuple(x.shape[1:]) != tuple(size):
+        x = r_area(x, size)
+    if f & T.SHIFT:
+        x = r_shift(x, p.shift)
+    if f & T.CONTRAST:
+        x = r_contrast(x, p.gamma)
+    if f & T.SMOOTH:
+        x = r_gauss(x, p.smooth_sigma)
+    if f & T.SHARPEN:
+        x = r_sharpen(x, p.sharpen_sigma1, p.sharpen_sigma2, p.alpha)
+    if f & T.HIST:
+        x = r_hist(x, p.hist_fl)
+    return x
+
+
+# ---- helpers --------------------------------------------------------------------------------------------------------------
+FL = (0.0, 0.05, 0.18, 0.3, 0.41, 0.5, 0.66, 0.8, 0.93, 1.0)
+
+
+def _params(**kw):
+    return T.SampleParams(**kw)
+
+
+def _stage(bit):
+    return {T.NORMALIZE: Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV), T.SCALE: T.ScaleIntensity(), T.ROTATE: T.RandRotate(prob=1.0),
+            T.FLIP: T.RandAxisFlip(prob=1.0), T.ZOOM: T.RandZoom(prob=1.0), T.RESIZE: T.Resize(),
+            T.SHIFT: T.RandShiftIntensity(0.1, prob=1.0), T.CONTRAST: T.RandAdjustContrast(prob=1.0), T.SMOOTH: T.RandGaussianSmooth(prob=1.0),
+            T.SHARPEN: T.RandGaussianSharpen(prob=1.0), T.HIST: T.RandHistogramShift(prob=1.0),
+            T.NOISE: T.RandGaussianNoise(prob=1.0, mean=0, std=0.05)}[bit]
+
+
+def _unit(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(shape, generator=g, dtype=torch.float64).float()
+
+
+def _raw(shape, seed):
+    """MRI-like raw intensities (positive, a few hundred)."""
+    g = torch.Generator().manual_seed(seed)
+    return (300.0 + 200.0 * torch.randn(shape, generator=g, dtype=torch.float64)).abs().float()
+
+
+def _run(stages_list, x, params):
+    out = T.Compose(stages_list).apply(x.to(DEV), params)
+    torch.cuda.synchronize()
+    return out.cpu().double()
+
+
+def _check(out, x, stages, params, tol):
+    for i, p in enumerate(params):
+        ref = restate(x[i], stages, p)
+        assert out[i].shape == ref.shape
+        err = float((out[i] - ref).abs().max())
+        assert err <= tol, (i, err, tol)
+
+
+# ---- each transform alone -----------------------------------------------------------------------------------------------------
+SINGLE = [
+    ("normalize", T.NORMALIZE, {}, "raw"),
+    ("scale", T.SCALE, {}, "raw"),
+    ("rotate_small", T.ROTATE, dict(theta=0.3), "unit"),
+    ("rotate_large", T.ROTATE, dict(theta=-11.7), "unit"),
+    ("flip_d", T.FLIP, dict(flip_axis=0), "unit"),
+    ("flip_h", T.FLIP, dict(flip_axis=1), "unit"),
+    ("flip_w", T.FLIP, dict(flip_axis=2), "unit"),
+    ("zoom_in", T.ZOOM, dict(zoom=1.1), "unit"),
+    ("zoom_out", T.ZOOM, dict(zoom=0.9), "unit"),
+    ("zoom_odd", T.ZOOM, dict(zoom=0.947), "unit"),
+    ("resize", T.RESIZE, {}, "unit"),
+    ("shift", T.SHIFT, dict(shift=-0.073), "unit"),
+    ("contrast", T.CONTRAST, dict(gamma=2.7), "unit"),
+    ("smooth", T.SMOOTH, dict(smooth_sigma=(0.3, 1.0, 1.5)), "unit"),
+    ("sharpen", T.SHARPEN, dict(sharpen_sigma1=(0.9, 0.6, 1.0), sharpen_sigma2=(0.55, 0.5, 0.8), alpha=23.0), "unit"),
+    ("hist", T.HIST, dict(hist_fl=FL), "unit"),
+]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s[2:])))
+@pytest.mark.parametrize("name,bit,kw,data", SINGLE, ids=[s[0] for s in SINGLE])
+def test_each_transform_alone(name, bit, kw, data, shape):
+    x = (_raw if data == "raw" else _unit)(shape, sum(map(ord, name)))
+    params = [_params(fire=bit, **kw) for _ in range(shape[0])]
+    out = _run([_stage(bit)], x, params)
+    tol = 1e-5 * (1 + 2 * kw.get("alpha", 0.0))
+    _check(out, x, bit, params, tol)
+
+
+def test_single_transform_call_and_4d_input():
+    x = _unit((2, 20, 21, 22), 3).to(DEV)
+    y = T.ScaleIntensity()(x)
+    assert y.shape == x.shape and y is not x
+    ref = r_scale(x.cpu().double())
+    assert float((y.cpu().double() - ref).abs().max()) < 1e-6
+    z = T.Resize()(x)
+    assert z.shape == (2, 64, 64, 64)
+    x0 = x.clone()
+    T.train_transforms(x)
+    assert torch.equal(x, x0)            # the input is not modified
+
+
+# ---- full pipelines -----------------------------------------------------------------------------------------------------------
+def _all_params(**kw):
+    base = dict(fire=(1 << 12) - 1, theta=0.21, flip_axis=1, zoom=0.93, shift=0.04, gamma=1.7, smooth_sigma=(0.5, 0.8, 1.2),
+                sharpen_sigma1=(0.8, 0.9, 0.7), sharpen_sigma2=(0.6, 0.5, 0.65), alpha=12.0, hist_fl=FL, noise_std=0.0, noise_seed=1)
+    base.update(kw)
+    return T.SampleParams(**base)
+
+
+def test_train_pipeline_all_stages_128_to_64():
+    x = _raw((2, 2, 128, 128, 128), 21)
+    params = [_all_params(), _all_params(theta=-3.0, flip_axis=2, zoom=1.08, gamma=0.8, alpha=27.0)]
+    out = _run(T.train_transforms.transforms, x, params)
+    assert out.shape == (2, 2, 64, 64, 64)
+    _check(out, x, T.train_transforms.stages, params, 4e-5 * (1 + 2 * 27.0))
+
+
+def test_val_pipeline():
+    for shape in ((2, 2, 128, 128, 128), (2, 2, 64, 64, 64), (1, 2, 37, 50, 43)):
+        x = _raw(shape, 22)
+        params = T.val_transforms.randomize(shape[0])
+        out = _run(T.val_transforms.transforms, x, params)
+        assert out.shape == (shape[0], 2, 64, 64, 64)
+        _check(out, x, T.val_transforms.stages, params, 1e-5)
+
+
+def test_unimodal_single_channel():
+    x = _raw((2, 1, 80, 72, 64), 23)
+    params = [_all_params(zoom=1.04), _all_params(fire=T.ROTATE | T.SHIFT | T.HIST, theta=1.2)]
+    out = _run(T.train_transforms.transforms, x, params)
+    assert out.shape == (2, 1, 64, 64, 64)
+    _check(out, x, T.train_transforms.stages, params, 4e-5 * (1 + 2 * 12.0))
+
+
+def test_per_sample_parameters_in_a_batch():
+    """Three samples, each with its own draws (and different stages firing): each must match its own restatement, not a neighbour's."""
+    x = _raw((3, 2, 70, 66, 60), 24)
+    params = [_all_params(fire=T.ROTATE | T.ZOOM | T.CONTRAST | T.SMOOTH, theta=0.5, zoom=0.91, gamma=3.1),
+              _all_params(fire=T.FLIP | T.SHIFT | T.SHARPEN | T.HIST, flip_axis=0, shift=-0.09, alpha=19.0),
+              _all_params(fire=0)]
+    out = _run(T.train_transforms.transforms, x, params)
+    _check(out, x, T.train_transforms.stages, params, 4e-5 * (1 + 2 * 19.0))
+    swapped = restate(x[0], T.train_transforms.stages, params[1])
+    assert float((out[0] - swapped).abs().max()) > 1e-2
+
+
+def test_batch_larger_than_one_launch_group():
+    """Ten samples travel in two launch groups (8 + 2)."""
+    x = _raw((10, 2, 24, 20, 28), 25)
+    rng = np.random.default_rng(3)
+    params = [_all_params(fire=int(rng.integers(0, 1 << 12)) & ~T.NOISE, theta=float(rng.uniform(-15, 15)), flip_axis=int(rng.integers(3)),
+                          zoom=float(rng.uniform(0.9, 1.1)), shift=float(rng.uniform(-0.1, 0.1)), gamma=float(rng.uniform(0.5, 4.5)),
+                          alpha=float(rng.uniform(10, 30))) for _ in range(10)]
+    out = _run(T.train_transforms.transforms, x, params)
+    _check(out, x, T.train_transforms.stages, params, 4e-5 * (1 + 2 * 30.0))
+
+
+# ---- noise ----------------------------------------------------------------------------------------------------------------------
+def test_noise_statistics_and_determinism():
+    x = _unit((2, 2, 48, 48, 48), 26)
+    sig = 0.037
+    mk = lambda seed: [T.SampleParams(fire=T.NOISE, noise_std=sig, noise_seed=seed) for _ in range(2)]   # both samples: same seed
+    a = _run([_stage(T.NOISE)], x, mk(99))
+    b = _run([_stage(T.NOISE)], x, mk(99))
+    c = _run([_stage(T.NOISE)], x, mk(100))
+    assert torch.equal(a, b)
+    assert not torch.equal(a, c)
+    e = (a - x.double())
+    n = e[0].numel()
+    for i in range(2):
+        m, s = float(e[i].mean()), float(e[i].std())
+        assert abs(m) < 5 * sig / math.sqrt(n)
+        assert abs(s - sig) < 5 * sig / math.sqrt(2 * n)
+    corr = lambda u, v: float(np.corrcoef(u.reshape(-1).numpy(), v.reshape(-1).numpy())[0, 1])
+    lim = 5 / math.sqrt(e[0, 0].numel())
+    assert abs(corr(e[0, 0], e[0, 1])) < lim      # channels
+    assert abs(corr(e[0, 0], e[1, 0])) < lim      # samples, even with equal seeds
+    assert abs(corr(e[0, 0], (c - x.double())[0, 0])) < lim   # seeds
+
+
+def test_noise_in_the_full_pipeline():
+    x = _raw((2, 2, 64, 64, 64), 27)
+    p0 = [_all_params(fire=T.NOISE, noise_std=0.0, noise_seed=5) for _ in range(2)]
+    p1 = [_all_params(fire=T.NOISE, noise_std=0.05, noise_seed=5) for _ in range(2)]
+    clean = _run(T.train_transforms.transforms, x, p0)
+    noisy = _run(T.train_transforms.transforms, x, p1)
+    d = noisy - clean
+    assert abs(float(d.std()) - 0.05) < 0.002 and abs(float(d.mean())) < 0.002
+
+
+# ---- edge cases -----------------------------------------------------------------------------------------------------------
+def test_constant_volume():
+    x = torch.full((2, 2, 40, 36, 44), 3.7)
+    p = [T.SampleParams() for _ in range(2)]
+    out = _run([Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV), T.ScaleIntensity()], x, p)
+    assert torch.equal(out, torch.zeros_like(out))
+    for bit, kw in ((T.CONTRAST, dict(gamma=3.3)), (T.HIST, dict(hist_fl=FL))):
+        out = _run([_stage(bit)], x, [T.SampleParams(fire=bit, **kw) for _ in range(2)])
+        assert torch.equal(out, x.double()), bit
+    out = _run(T.train_transforms.transforms, x, [_all_params(noise_std=0.01), _all_params(fire=0)])
+    assert torch.isfinite(out).all()
+
+
+def test_negative_max_keeps_normalize_sign():
+    g = torch.Generator().manual_seed(28)
+    x = (-5.0 + 4.0 * torch.rand((2, 2, 30, 31, 32), generator=g, dtype=torch.float64)).float()     # max(x) < 0
+    p = [T.SampleParams() for _ in range(2)]
+    out = _run([Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV)], x, p)
+    _check(out, x, T.NORMALIZE, p, 1e-5)
+    i = int(x[0].argmax())
+    assert float(out[0].reshape(-1)[i]) == float(out[0].min())     # std * M < 0: the order of the voxels is reversed
+    out = _run([Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV), T.ScaleIntensity()], x, p)
+    _check(out, x, T.NORMALIZE | T.SCALE, p, 1e-5)
+    assert abs(float(out[0].reshape(-1)[i])) < 1e-6
+
+
+# ---- end to end ---------------------------------------------------------------------------------------------------------------
+def _cli(args, out):
+    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return r.stdout + r.stderr
+
+
+def _tiny_config(tmp_path):
+    import yaml
+    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
+                          "in_channels": 2, "dropout_prob": 0.2},
+           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
+           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
+    p = tmp_path / "config.yaml"
+    p.write_text(yaml.safe_dump(cfg))
+    return str(p)
+
+
+def test_cli_fusion_training_and_inference_with_transforms(tmp_path):
+    cfg = _tiny_config(tmp_path)
+    log = _cli(["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1", "--synthetic_patients", "4",
+                "--synthetic_size", "48", "--config", cfg], tmp_path)
+    line = [l for l in log.splitlines() if "train loss/patient" in l][-1]
+    loss = float(line.split("train loss/patient")[1].split()[0])
+    assert math.isfinite(loss), line
+    log = _cli(["--inference", "--images", "--preop", "--survival", "--transforms", "--weights", str(tmp_path / "best_surv_model.pth"),
+                "--synthetic_patients", "8", "--synthetic_size", "48", "--config", cfg], tmp_path)
+    assert "All C-indexes" in log
+    m = np.load(tmp_path / "attention_maps" / "patient0_att_map.npy")
+    assert m.shape == (64, 64, 64) and np.isfinite(m).all()
