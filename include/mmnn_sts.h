@@ -264,6 +264,49 @@ typedef struct {
 int mmnn_gradcam(const mmnn_gradcam_desc* d, const float* h5, const float* act_in, const float* w_head, const float* w_feat,
                  const float* gamma5, const float* running_var5, float* act, float* grads, float* heat, float* maps, void* stream);
 
+/* ---- batched Grad-CAM of an image-only model (what upstream gets from medcam.inject(backend='gcam'), utils/utils.py:451-455;
+ * semantics pinned in INTEGRATION.md).  The captured layer A [n][channels][v] is the last Conv3d of the encoder; per sample b and a
+ * target t_b (a sum of, one of, or the argmax of the sample's outputs):  d t_b / d A[b][c][v] = s[b][c] * mask[b][c][v] / v  in closed form
+ * (no autograd, no weight gradients), alpha[b][c] = mean over v of that gradient, heat[b][v] = ReLU(sum_c alpha[b][c] * A[b][c][v]),
+ * min-max normalised per sample (an all-equal map, the all-zero map included, becomes 0, never NaN), trilinear up-sampling to the input
+ * extent (align_corners = False).  Samples are independent.  Head families:
+ *   MMNN_GC_HEAD_DENSENET  class_layers.out . features.feature_layer . GAP . ReLU . norm5 (eval), A = the last dense layer's conv2 =
+ *                          channels [chan_off, chan_off + channels) of the concat buffer; mask = norm5 output > 0 on those channels
+ *   MMNN_GC_HEAD_SIGMOID   sigmoid . fc . GAP . ReLU(BN(A) + residual) of r3d_18's last BasicBlock; mask = the block's output > 0 */
+#define MMNN_GC_HEAD_DENSENET 0
+#define MMNN_GC_HEAD_SIGMOID  1
+#define MMNN_GC_LABEL_SUM     (-1)      /* target = sum of the sample's outputs (medcam's default) */
+#define MMNN_GC_LABEL_BEST    (-2)      /* target = argmax of the sample's outputs, chosen on the device */
+typedef struct {
+  int32_t n;                /* samples */
+  int32_t channels;         /* channels of the captured layer (<= 64) */
+  int32_t d, h, w;          /* extent of the captured layer */
+  int32_t out_d, out_h, out_w;   /* extent of the attention maps = of the input volume */
+  int32_t classes;          /* model outputs per sample */
+  int32_t label;            /* 0 <= label < classes, MMNN_GC_LABEL_SUM or MMNN_GC_LABEL_BEST */
+  int64_t act_ns;           /* sample stride (floats) of act: channels * v for a plain tensor, c_total * v inside a concat buffer */
+  int64_t mask_ns;          /* sample stride (floats) of mask_src */
+} mmnn_gradcam_unimodal_desc;
+typedef struct {
+  int32_t kind;             /* MMNN_GC_HEAD_* */
+  int32_t features;         /* DENSENET: rows of w_feat (width of features.feature_layer); SIGMOID: unused */
+  int32_t w_feat_ld;        /* DENSENET: row stride of w_feat (= c_total); SIGMOID: unused */
+  int32_t chan_off;         /* first captured channel in w_feat's columns and in gamma / running_var (DENSENET: c_total - growth) */
+  const float* w_out;       /* DENSENET: class_layers.out.weight [classes][features]; SIGMOID: fc.weight [classes][channels] */
+  const float* w_feat;      /* DENSENET: features.feature_layer.weight [features][w_feat_ld]; SIGMOID: NULL */
+  const float* gamma;       /* weight / running_var of the BN after the captured layer (norm5; layer4[-1].conv2[1]) */
+  const float* running_var;
+  const float* outputs;     /* [n][classes] model outputs (sigmoid probabilities for SIGMOID): the argmax of LABEL_BEST, sigma' */
+  float eps;                /* eps of that BN */
+} mmnn_gradcam_head;
+/* bytes of device scratch mmnn_gradcam_unimodal needs (per-sample gradient scales, per-block partial counts and extrema) */
+int64_t mmnn_gradcam_unimodal_workspace_bytes(const mmnn_gradcam_unimodal_desc* d);
+/* act: A of sample 0, channel 0 (sample b at act + b * act_ns, channel c at + c * v); mask_src: the mask's source laid out alike.
+ * Writes grads [n][channels][v] (d t_b / d A; may be NULL), heat [n][v] (normalised low-resolution maps) and maps [n][out_d][out_h][out_w].
+ * Four launches plus the up-sampling, no host synchronisation. */
+int mmnn_gradcam_unimodal(const mmnn_gradcam_unimodal_desc* d, const mmnn_gradcam_head* head, const float* act, const float* mask_src,
+                          float* grads, float* heat, float* maps, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- input transforms: upstream's train_transforms / val_transforms (main.py:64-92) on a batch of (C, D, H, W) fp32 volumes
  * (csrc/transforms.hip).  The semantics are pinned by the table in DESIGN §11, not by monai.  `stages` lists the transforms present,
  * in upstream's order; a random stage fires for sample i when its bit is set in per_sample[i].fire.  Every random draw is made by

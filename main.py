@@ -372,11 +372,12 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
 
 
 def inference_survival(model, ds, args, device):
-    """main.py:750-887: batch-1 loop, Grad-CAM maps (saved as .npy; NIfTI export needs nibabel, host I/O), C-index."""
+    """main.py:750-887: batch-1 loop, Grad-CAM maps (saved as .npy; NIfTI export needs nibabel, host I/O) of fusion and image-only
+    models (main.py:1013-1014: add_gradcam(model, multimodal=...)), C-index."""
     model = model.to(device).eval()
     if args.bootstrap:
         args.no_gradcam = True                       # main.py:774-777: no attention maps, no prediction dump while bootstrapping
-    cam = add_gradcam(model, multimodal=True) if (args.images and args.multimodal and not args.no_gradcam) else None
+    cam = add_gradcam(model, multimodal=args.multimodal) if (args.images and not args.no_gradcam) else None
     preds, evs, dus = [], [], []
     os.makedirs(os.path.join(args.output_path, "attention_maps"), exist_ok=True)
     for i in range(len(ds)):
@@ -385,7 +386,9 @@ def inference_survival(model, ds, args, device):
         with torch.no_grad():
             if cam is not None:
                 p, maps = cam(x)
-                np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_att_map.npy"), maps[0].cpu().numpy())
+                # fusion: the list of per-class maps, the first saved; image-only: (1, 1, D, H, W), the sample's map saved
+                att = maps[0] if args.multimodal else maps[0, 0]
+                np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_att_map.npy"), att.cpu().numpy())
             else:
                 p = model(x)
         preds.append(p.cpu()); evs.append(ev); dus.append(du)

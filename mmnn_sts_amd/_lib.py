@@ -49,6 +49,22 @@ class GradcamDesc(Structure):
                 ("features", c_int32), ("head_ld", c_int32), ("out_d", c_int32), ("out_h", c_int32), ("out_w", c_int32), ("eps", c_float)]
 
 
+GC_HEAD_DENSENET, GC_HEAD_SIGMOID = 0, 1
+GC_LABEL_SUM, GC_LABEL_BEST = -1, -2
+
+
+class GradcamUnimodalDesc(Structure):
+    """mmnn_gradcam_unimodal_desc (include/mmnn_sts.h)."""
+    _fields_ = [("n", c_int32), ("channels", c_int32), ("d", c_int32), ("h", c_int32), ("w", c_int32), ("out_d", c_int32),
+                ("out_h", c_int32), ("out_w", c_int32), ("classes", c_int32), ("label", c_int32), ("act_ns", c_int64), ("mask_ns", c_int64)]
+
+
+class GradcamHead(Structure):
+    """mmnn_gradcam_head: the layers between the captured Conv3d and the outputs."""
+    _fields_ = [("kind", c_int32), ("features", c_int32), ("w_feat_ld", c_int32), ("chan_off", c_int32), ("w_out", c_void_p),
+                ("w_feat", c_void_p), ("gamma", c_void_p), ("running_var", c_void_p), ("outputs", c_void_p), ("eps", c_float)]
+
+
 class MlpParams(Structure):
     _fields_ = [(k, c_void_p * MLP_MAX_LAYERS) for k in (
         "weight", "bias", "gamma", "beta", "running_mean", "running_var", "grad_weight", "grad_bias", "grad_gamma", "grad_beta",
@@ -125,6 +141,7 @@ def lib():
         "mmnn_sgd_step_multi": [POINTER(TensorRef), I, V, F, F, F, I, V],
         "mmnn_multi_copy": [POINTER(TensorRef), I, V, I, V],
         "mmnn_gradcam": [POINTER(GradcamDesc), V, V, V, V, V, V, V, V, V, V, V],
+        "mmnn_gradcam_unimodal": [POINTER(GradcamUnimodalDesc), POINTER(GradcamHead), V, V, V, V, V, V, c_int64, V],
         "mmnn_bce_logits": [c_int64, I, V, V, V, V, V, V],
         "mmnn_conv3d_out_shape": [POINTER(Conv3dDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
         "mmnn_conv3d_forward": [POINTER(Conv3dDesc), V, V, V, V],
@@ -147,6 +164,8 @@ def lib():
         fn.argtypes = args
     L.mmnn_conv3d_wgrad_workspace_bytes.restype = c_int64
     L.mmnn_conv3d_wgrad_workspace_bytes.argtypes = [POINTER(Conv3dDesc)]
+    L.mmnn_gradcam_unimodal_workspace_bytes.restype = c_int64
+    L.mmnn_gradcam_unimodal_workspace_bytes.argtypes = [POINTER(GradcamUnimodalDesc)]
     L.mmnn_transform_workspace_bytes.restype = c_int64
     L.mmnn_transform_workspace_bytes.argtypes = [POINTER(TransformDesc)]
     L.mmnn_transform_volumes.restype = c_int32

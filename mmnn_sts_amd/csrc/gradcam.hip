@@ -4,9 +4,9 @@
 //                            -> norm5 scale), channel-pooled gradient (:308-311), IN-PLACE cumulative weighting of the activations across
 //                            classes (:313-314), channel mean, min-max normalisation (:316-323)
 //   gradcam_upsample_kernel  F.interpolate(mode='trilinear', align_corners=False) of every class map to the input extent (:339),
-//                            HBM-bound: 16-byte stores of the (D, H, W) map, source map in LDS
-#include "../../include/mmnn_sts.h"
-#include "common.hpp"
+//                            HBM-bound: 16-byte stores of the (D, H, W) map, source map in LDS.  Also launched by the batched
+//                            unimodal Grad-CAM (gradcam_unimodal.hip) through launch_gradcam_upsample, one map per sample
+#include "gradcam.hpp"
 
 namespace mmnn {
 
@@ -169,6 +169,22 @@ __global__ void __launch_bounds__(256) gradcam_upsample_kernel(const UpsampleArg
   }
 }
 
+int launch_gradcam_upsample(int d, int h, int w, int D, int H, int W, int maps, const float* heat, float* out, hipStream_t st) {
+  MMNN_REQUIRE(maps >= 1 && maps <= 65535, "gradcam: %d maps not in 1..65535", maps);
+  MMNN_REQUIRE((long)D * H < (1l << 31), "gradcam: output extent too large");
+  UpsampleArgs u;
+  u.d = d; u.h = h; u.w = w; u.D = D; u.H = H; u.W = W; u.classes = maps;
+  u.heat = heat; u.maps = out;
+  u.sd = (float)d / (float)D; u.sh = (float)h / (float)H; u.sw = (float)w / (float)W;
+  long gx = ((long)D * H + 3) / 4;
+  if (gx > 65536) gx = 65536;
+  const long gx_cap = (1l << 24) / maps;          // keeps blocks x maps (and the work-items of the grid) far below 2^32
+  if (gx > gx_cap) gx = gx_cap > 0 ? gx_cap : 1;
+  MMNN_LAUNCH(gradcam_upsample_kernel, dim3((unsigned)gx, (unsigned)maps), dim3(256), 0, st, u);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace mmnn
 
 using namespace mmnn;
@@ -190,14 +206,5 @@ extern "C" int mmnn_gradcam(const mmnn_gradcam_desc* d, const float* h5, const f
   a.act = act; a.grads = grads; a.heat = heat;
   MMNN_LAUNCH(gradcam_heat_kernel, dim3(1), dim3(GC_THREADS), 0, st, a);
   MMNN_HIP(hipGetLastError());
-  UpsampleArgs u;
-  u.d = d->d; u.h = d->h; u.w = d->w; u.D = d->out_d; u.H = d->out_h; u.W = d->out_w; u.classes = d->classes;
-  u.heat = heat; u.maps = maps;
-  u.sd = (float)d->d / (float)d->out_d; u.sh = (float)d->h / (float)d->out_h; u.sw = (float)d->w / (float)d->out_w;
-  MMNN_REQUIRE((long)d->out_d * d->out_h < (1l << 31), "gradcam: output extent too large");
-  long gx = ((long)d->out_d * d->out_h + 3) / 4;
-  if (gx > 65536) gx = 65536;
-  MMNN_LAUNCH(gradcam_upsample_kernel, dim3((unsigned)gx, (unsigned)d->classes), dim3(256), 0, st, u);
-  MMNN_HIP(hipGetLastError());
-  return 0;
+  return launch_gradcam_upsample(d->d, d->h, d->w, d->out_d, d->out_h, d->out_w, d->classes, heat, maps, st);
 }

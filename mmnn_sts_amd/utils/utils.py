@@ -2,8 +2,9 @@
 
 Kept (same names / signatures): `criterion` (:20-22), `surv_criterion` (:24-29), `save_model` (:31-35),
 `BackpropagatableFeatureExtractor` (:238-251), `MultiModalGradCAM` (:253-344), `loadWeights` (:357-390, local files),
-`add_gradcam` (:451-455), `loadUIDs` (:175-181, local files).  S3 / matplotlib / medcam helpers are host-side I/O
-outside the hot path and are not reproduced.
+`add_gradcam` (:451-455), `loadUIDs` (:175-181, local files).  S3 / matplotlib helpers are host-side I/O outside the hot path
+ and are not reproduced.  In place of the third-party `medcam.inject(backend='gcam')` that upstream's
+`add_gradcam(model, multimodal=False)` returns, `GradCAM` computes the published Grad-CAM on the HIP path.
 """
 import logging
 import os
@@ -120,11 +121,156 @@ class MultiModalGradCAM(nn.Module):
         return outputs, att_maps
 
 
+class GradCAM(nn.Module):
+    """Grad-CAM (Selvaraju et al.) of an image-only model -- DenseNet / DenseNet121 / TinyDensenet or r3d_18 -- on the last Conv3d of
+    its encoder in module-registration order, for a whole batch: what upstream obtains from medcam's `gcam` backend
+    (utils/utils.py:451-455).  Rules, and where they part from medcam, are pinned in INTEGRATION.md ("Grad-CAM of image-only models").
+
+    `label`: None targets the sum of each sample's outputs, an int k output k, "best" the argmax of each sample's outputs (chosen on the
+    device).  `cam(x)` returns `(outputs, att_maps)`: the outputs of `model.eval()(x)` and a (B, 1, D, H, W) fp32 tensor of per-sample
+    min-max normalised maps in [0, 1] (an all-equal map is all zeros).  Afterwards `.features` holds the captured activations A
+    (B, C, d, h, w; for a DenseNet a view into the backbone's workspace, valid until its next forward of that input shape), `.grads`
+    d target / d A, `.heat` the (B, 1, d, h, w) normalised low-resolution maps and `.layer_name` the captured module.
+
+    The eval forward is the model's own HIP path (for r3d_18 the wrapper runs the last BasicBlock itself with the same ops, to keep
+    the pre-BN convolution output); everything after it is ONE C-ABI call (`mmnn_gradcam_unimodal`, csrc/gradcam_unimodal.hip):
+    the gradient in closed form, the channel weights, ReLU, normalisation and up-sampling.  torch only allocates.
+    """
+
+    SUPPORTED = "DenseNet, DenseNet121, TinyDensenet (mmnn_sts_amd.models.densenet) and r3d_18 (mmnn_sts_amd.models.resnet.Resnet18)"
+
+    def __init__(self, model, label=None):
+        super().__init__()
+        from ..models.densenet import DenseNet
+        from ..models.resnet import BasicBlock, Resnet18
+        if isinstance(model, DenseNet):
+            kind = "densenet"
+            nb = len(model.backbone.cfg["block_config"])
+            expected = f"backbone.denseblock{nb}.denselayer{model.backbone.cfg['block_config'][-1]}.layers.conv2"
+        elif isinstance(model, Resnet18) and isinstance(model.layer4[-1], BasicBlock):
+            kind = "r3d_18"
+            expected = f"layer4.{len(model.layer4) - 1}.conv2.0"
+        else:
+            raise TypeError(f"GradCAM supports {self.SUPPORTED}; got {type(model).__name__}")
+        if not (label is None or label == "best" or (isinstance(label, int) and not isinstance(label, bool) and label >= 0)):
+            raise ValueError(f"GradCAM label must be None, a non-negative int or 'best', got {label!r}")
+        convs = [name for name, m in model.named_modules() if isinstance(m, nn.Conv3d)]
+        if not convs or convs[-1] != expected:
+            raise TypeError(f"GradCAM: the last Conv3d of this {type(model).__name__} is {convs[-1] if convs else None}, "
+                            f"the closed-form gradient assumes {expected}")
+        self.model = model
+        self.kind = kind
+        self.label = label
+        self.layer_name = expected
+        self.features = None
+        self.grads = None
+        self.heat = None
+
+    def _label_code(self):
+        if self.label is None:
+            return _lib.GC_LABEL_SUM
+        if self.label == "best":
+            return _lib.GC_LABEL_BEST
+        return int(self.label)
+
+    def _densenet(self, x):
+        m = self.model
+        bb = m.backbone
+        h = bb(x)                                                   # norm5 output (eval statistics)
+        outputs = m.class_layers(m.features(h))                     # = DenseNet.forward
+        ent = bb._plans[(tuple(x.shape), x.device.index)]
+        L = _lib.lib()
+        n, ctot = h.shape[0], h.shape[1]
+        g = bb.cfg["growth_rate"]
+        sp = tuple(h.shape[2:])
+        v = h[0, 0].numel()
+        # the last dense block's concat buffer is [N][c_total][v] (csrc/densenet.hip: o_x, sample stride c_total * v); its last `g`
+        # channels are the output of the last conv2 (dropout is the identity in eval)
+        off = L.mmnn_densenet_ws_offset(ent["plan"], b"x", len(bb.cfg["block_config"]) - 1, 0)
+        if off < 0:
+            raise RuntimeError("GradCAM: no concat buffer in the DenseNet plan")
+        buf = ent["ws"][off:off + 4 * n * ctot * v].view(torch.float32).view((n, ctot) + sp)
+        act = buf[:, ctot - g:]
+        n5, wfeat, wout = bb.norm5, m.features.feature_layer.weight, m.class_layers.out.weight
+        for t in (h, wfeat, wout, n5.weight, n5.running_var):
+            if not (t.is_contiguous() and t.dtype == torch.float32):
+                raise RuntimeError("GradCAM expects contiguous float32 model tensors")
+        head = _lib.GradcamHead(_lib.GC_HEAD_DENSENET, wfeat.shape[0], wfeat.shape[1], ctot - g, wout.data_ptr(), wfeat.data_ptr(),
+                                n5.weight.data_ptr(), n5.running_var.data_ptr(), outputs.data_ptr(), float(n5.eps))
+        mask = h[:, ctot - g:]
+        return outputs, act, mask, ctot * v, ctot * v, head
+
+    def _r3d(self, x):
+        from ..models.resnet import _bn, _conv
+        m = self.model
+        if not x.is_cuda:
+            raise RuntimeError("mmnn_sts_amd: r3d_18 runs on the MI355X only (no CPU path); move model and input to cuda")
+        if x.dim() != 5 or x.shape[1] != m.stem[0].in_channels:
+            raise ValueError(f"expected (N, {m.stem[0].in_channels}, D, H, W) input, got {tuple(x.shape)}")
+        h = m.stem(x)                                               # = Resnet18.forward in eval mode (no dropout) ...
+        for stage in (m.layer1, m.layer2, m.layer3, m.layer4):
+            for blk in stage:
+                if blk is not m.layer4[-1]:
+                    h = blk(h, drop_p=0.0)
+        last = m.layer4[-1]                                         # ... with BasicBlock.forward of the last block unrolled
+        out = _bn(_conv(h, last.conv1[0]), last.conv1[1], relu=True)
+        act = _conv(out, last.conv2[0])                             # the captured layer, before its BatchNorm
+        residual = h if last.downsample is None else _bn(_conv(h, last.downsample[0]), last.downsample[1], relu=False)
+        y = _bn(act, last.conv2[1], relu=True, residual=residual)
+        outputs = ops.GapFcSigmoid.apply(y, m.fc.weight, m.fc.bias)
+        bn, wfc = last.conv2[1], m.fc.weight
+        for t in (act, y, wfc, bn.weight, bn.running_var, outputs):
+            if not (t.is_contiguous() and t.dtype == torch.float32):
+                raise RuntimeError("GradCAM expects contiguous float32 model tensors")
+        head = _lib.GradcamHead(_lib.GC_HEAD_SIGMOID, 0, 0, 0, wfc.data_ptr(), None, bn.weight.data_ptr(), bn.running_var.data_ptr(),
+                                outputs.data_ptr(), float(bn.eps))
+        c, v = act.shape[1], act[0, 0].numel()
+        return outputs, act, y, c * v, c * v, head
+
+    def _attention(self, captured, extent):
+        """Everything after the encoder forward: ONE C-ABI call on the captured tensors.  Returns the (B, 1, D, H, W) maps and sets
+        .features / .grads / .heat."""
+        import ctypes
+        outputs, act, mask, act_ns, mask_ns, head = captured
+        n, c = act.shape[0], act.shape[1]
+        sp = tuple(act.shape[2:])
+        D, H, W = (int(t) for t in extent)
+        dev = act.device
+        desc = _lib.GradcamUnimodalDesc(n, c, sp[0], sp[1], sp[2], D, H, W, outputs.shape[1], self._label_code(), act_ns, mask_ns)
+        L = _lib.lib()
+        ws_bytes = L.mmnn_gradcam_unimodal_workspace_bytes(ctypes.byref(desc))
+        if ws_bytes < 0:
+            raise ValueError(f"GradCAM: bad captured layer {tuple(act.shape)}")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        grads = torch.empty((n, c) + sp, device=dev, dtype=torch.float32)
+        heat = torch.empty((n, 1) + sp, device=dev, dtype=torch.float32)
+        maps = torch.empty((n, 1, D, H, W), device=dev, dtype=torch.float32)
+        _lib.check(L.mmnn_gradcam_unimodal(ctypes.byref(desc), ctypes.byref(head), act.data_ptr(), mask.data_ptr(), grads.data_ptr(),
+                                           heat.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws_bytes,
+                                           torch.cuda.current_stream().cuda_stream), "gradcam_unimodal")
+        self.features, self.grads, self.heat = act, grads, heat
+        return maps
+
+    def forward(self, x):
+        m = self.model
+        modes = [(mod, mod.training) for mod in m.modules()]
+        m.eval()
+        try:
+            with torch.no_grad():
+                captured = self._densenet(x) if self.kind == "densenet" else self._r3d(x)
+                maps = self._attention(captured, x.shape[2:])
+        finally:
+            for mod, mode in modes:
+                mod.training = mode
+        return captured[0], maps
+
+
 def add_gradcam(model, output_dir='attention_maps', multimodal=False):
+    """utils/utils.py:451-455.  multimodal: the fusion model's MultiModalGradCAM; otherwise `GradCAM` over the image-only model in place
+    of upstream's medcam.inject(model, backend='gcam', return_attention=True) (parity unpinned against medcam)."""
     if multimodal:
         return model.add_gradcam(output_dir)
-    raise NotImplementedError("unimodal Grad-CAM in the reference is the third-party `medcam` package (utils/utils.py:455); "
-                              "only the multimodal Grad-CAM is part of this path")
+    return GradCAM(model)
 
 
 class Normalize:
