@@ -80,15 +80,13 @@ int mmnn_densenet_relu_mask(void* plan, const float* params, void* workspace, in
                             uint8_t* out, void* stream);
 /* measurement: time every launch of one kernel class (-1: of every class) with HIP events recorded on the launch stream.
  * kernel_class 0 none, 1 conv2 fwd, 2 conv2 dgrad, 3 conv2 wgrad, 4 conv1 fwd, 5 conv1 dgrad, 6 conv1 wgrad, 7 stem conv,
- * 8 stem wgrad; block >= 0 restricts to one dense block (0-based).  read_timer synchronises the recorded events and returns
- * the accumulated device time and launch count since set_timer (read_timer: all recorded classes and blocks together;
- * read_timer_class: one class (0: all) of one dense block (< 0: all)). */
+ * 8 stem wgrad, 9 reserved (accepted, but no launch records it); block >= 0 restricts to one dense block (0-based).  read_timer
+ * synchronises the recorded events and returns the accumulated device time and launch count since set_timer (read_timer: all
+ * recorded classes and blocks together; read_timer_class: one class (0: all) of one dense block (< 0: all)). */
 int mmnn_densenet_set_timer(void* plan, int32_t kernel_class, int32_t block);
 int mmnn_densenet_read_timer(void* plan, double* total_ms, int64_t* launches);
 int mmnn_densenet_read_timer_class(void* plan, int32_t kernel_class, int32_t block, double* total_ms, int64_t* launches);
-/* plan options.  "persistent_forward" (0/1, default 0; experiment): run the forward of a small-extent dense block (8^3 / 4^3 voxels) as ONE
- * resident launch with grid barriers between the layers (csrc/blockfwd.hip) instead of two kernels per layer -- same results up to summation
- * order; measured slower in round 3, kept for the record and under test.  "no_kz" (0/1): never split the channel axis of a small-extent convolution over several workgroups (the tests' reference
+/* plan options.  "no_kz" (0/1): never split the channel axis of a small-extent convolution over several workgroups (the tests' reference
  * for the cross-workgroup hand-off).  "side_streams" (0, 1 or 2; default 0): run the weight-gradient kernels of the backward on that many side streams
  * beside the data-gradient chain instead of on the caller's stream -- same results.  "single_stream" (0/1): force 0 side streams
  * (un-overlapped kernel durations for profiling).  "params_version" (any non-zero

@@ -24,7 +24,6 @@ namespace c3b {
 constexpr int KC = 16, NT = 7, MAXC = 256;
 // Tile geometry: TD x TH x TW voxels = ROWS rows of 32 voxels (voxel v = 32 row + column: w = v % TW, h = (v / TW) % TH, d = v / (TW TH)).
 //   <2, 4, 32>: 256 voxels, extents wider than 16 (one workgroup per CU at 2 x 32^3).
-//   <1, 2, 16>: 32 voxels (one row of two h-lines), extents of 9..16: 256 workgroups at 2 x 16^3 (opt-in, measured slower: see below).
 template <int TD, int TH, int TW>
 struct Geo {
   static constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2, HV = HD * HH * HW, ROWS = TD * TH * TW / 32;
@@ -447,36 +446,30 @@ int launch_conv3_dgrad_bf16x3(const FpropArgs& a, hipStream_t stream) {
 }
 
 // Shapes this kernel takes (everything else stays on fprop_kernel): 32 output channels, input channels in chunks of 16, rows wider than
-// 16 voxels.  MMNN_BF16X3=0 switches it off (A/B runs, debugging).  MMNN_BF16X3=16 also sends the 9..16-voxel extents here (the <1, 2, 16>
-// tile): parity-green but SLOWER than fprop_kernel at 2 x 16^3 (40.6 vs 28.2 us per launch, profiles/r03_ab_experiments.txt) -- 256 workgroups
-// of 32 voxels each stage a 6.75x halo and read all 442 KB of weights; those layers need a cross-workgroup K-split instead.  Off by default.
+// 16 voxels.  MMNN_BF16X3=0 switches it off (A/B runs, debugging).  (r03: a 1 x 2 x 16 tile for the 9..16-voxel extents passed parity
+// but was SLOWER than fprop_kernel at 2 x 16^3 -- 40.6 vs 28.2 us per launch, profiles/r03_ab_experiments.txt: 256 workgroups of 32
+// voxels each stage a 6.75x halo and read all 442 KB of weights; those layers need a cross-workgroup K-split instead.)
 bool conv3_fwd_bf16x3_eligible(const FpropArgs& a) {
   static const int mode = [] { const char* e = getenv("MMNN_BF16X3"); return e ? atoi(e) : 32; }();
-  return mode != 0 && a.M == 32 && a.Cin % c3b::KC == 0 && a.Cin >= c3b::KC && a.Cin <= c3b::MAXC && a.W > (mode == 16 ? 8 : 16);
+  return mode != 0 && a.M == 32 && a.Cin % c3b::KC == 0 && a.Cin >= c3b::KC && a.Cin <= c3b::MAXC && a.W > 16;
 }
 
-template <int TD, int TH, int TW>
-static int launch_geo(const FpropArgs& a, hipStream_t stream) {
-  using G = c3b::Geo<TD, TH, TW>;
-  const long tiles = (long)a.N * cdiv(a.D, TD) * cdiv(a.H, TH) * cdiv(a.W, TW);
+int launch_conv3_fwd_bf16x3(const FpropArgs& a, hipStream_t stream) {
+  using G = c3b::Geo<2, 4, 32>;
+  MMNN_REQUIRE(conv3_fwd_bf16x3_eligible(a), "conv3 bf16x3: shape not handled (M=%d, Cin=%d, W=%d)", a.M, a.Cin, a.W);
+  MMNN_REQUIRE(a.drop_in.p <= 0.f, "conv3 bf16x3: no input dropout on this path");
+  MMNN_REQUIRE((long)(a.Cin + 1) * a.D * a.H * a.W < (1l << 31), "conv3 bf16x3: volume too large for 32-bit element offsets");
+  const long tiles = (long)a.N * cdiv(a.D, 2) * cdiv(a.H, 4) * cdiv(a.W, 32);
   MMNN_REQUIRE(tiles > 0 && tiles < (1l << 31), "conv3 bf16x3: grid out of range");
   static bool configured[MAX_DEVICES] = {false};
   bool& conf = configured[current_device_slot()];
   if (!conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_fwd_bf16x3_kernel<TD, TH, TW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM));
+    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_fwd_bf16x3_kernel<2, 4, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM));
     conf = true;
   }
-  MMNN_LAUNCH((conv3_fwd_bf16x3_kernel<TD, TH, TW>), dim3((unsigned)tiles), dim3(256), G::SMEM, stream, a);
+  MMNN_LAUNCH((conv3_fwd_bf16x3_kernel<2, 4, 32>), dim3((unsigned)tiles), dim3(256), G::SMEM, stream, a);
   MMNN_HIP(hipGetLastError());
   return 0;
-}
-
-int launch_conv3_fwd_bf16x3(const FpropArgs& a, hipStream_t stream) {
-  MMNN_REQUIRE(conv3_fwd_bf16x3_eligible(a), "conv3 bf16x3: shape not handled (M=%d, Cin=%d, W=%d)", a.M, a.Cin, a.W);
-  MMNN_REQUIRE(a.drop_in.p <= 0.f, "conv3 bf16x3: no input dropout on this path");
-  MMNN_REQUIRE((long)(a.Cin + 1) * a.D * a.H * a.W < (1l << 31), "conv3 bf16x3: volume too large for 32-bit element offsets");
-  if (a.W > 16) return launch_geo<2, 4, 32>(a, stream);
-  return launch_geo<1, 2, 16>(a, stream);
 }
 
 }  // namespace mmnn

@@ -1,10 +1,8 @@
 // Launch plan of the DenseNet backbone forward / backward (see densenet.hpp).
 #include "densenet.hpp"
 
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 
@@ -18,7 +16,6 @@ static size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 // cross-block K-split scratch of the plan's workspace: <= 512 blocks x (up to 4) 32x32 partial tiles, + per-tile counters
 constexpr size_t KZ_PART_BYTES = (size_t)512 * 4 * 1024 * sizeof(float);
 constexpr unsigned KZ_CNT_ENTRIES = 4096;
-constexpr size_t BLK_SYNC_BYTES = 256;     // 2 words per dense block (MAX_BLOCKS = 8), zeroed together with the K-split counters
 
 namespace {
 struct Carver {
@@ -151,34 +148,21 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
   p.o_sl_conv0 = cv.take((size_t)p.ns_conv0 * cfg.in_channels * cfg.init_features * 352 * F);
   p.o_sl_c1.assign(nb, {}); p.o_sl_c2.assign(nb, {}); p.ns_c1.assign(nb, {}); p.ns_c2.assign(nb, {});
   p.o_sl_tr.clear(); p.ns_tr.clear();
-  // Layers per weight-gradient launch (MMNN_WGRAD_GROUP="a,b,c" for >= 32768 / >= 4096 / fewer voxels per batch; 0 = the whole
-  // dense block, the default).  With the backward on one stream the weight gradients of a block can all wait for the end of its
-  // data-gradient chain: one launch per kernel variant, and the voxel splits -- hence the partial slabs `finalize` has to read
-  // back -- shrink by the number of layers that share the launch.
-  {
-    int g[3] = {0, 0, 0};
-    if (const char* e = getenv("MMNN_WGRAD_GROUP")) sscanf(e, "%d,%d,%d", &g[0], &g[1], &g[2]);
-    for (int b = 0; b < nb; ++b) {
-      const long nvox = (long)N * p.Vb[b];
-      const int want = g[nvox >= 32768 ? 0 : nvox >= 4096 ? 1 : 2];
-      p.wg_group[b] = (want < 1 || want > cfg.block_layers[b]) ? cfg.block_layers[b] : want;
-    }
-  }
+  // The weight gradients of a dense block go out together once its data-gradient chain has ended: one launch per kernel variant,
+  // and the voxel splits -- hence the partial slabs `finalize` has to read back -- shrink by the number of layers that share it.
   for (int b = 0; b < nb; ++b) {
     for (int l = 0; l < cfg.block_layers[b]; ++l) {
       const int ci = p.layers[b][l].cin;
-      // conv1: a launch covers the layers of the group that use the same channel-group width; `pairs` = its (layer, channel
+      // conv1: a launch covers the layers of the block that use the same channel-group width; `pairs` = its (layer, channel
       // group) pairs, so that every block of the launch walks the same number of voxel chunks
       int pairs = 0;
       {
-        const int g0 = (cfg.block_layers[b] - 1 - l) / p.wg_group[b];          // groups are formed from the LAST layer downwards
         const int cw = wgrad1_channel_width(ci, p.Vb[b]);
         for (int k = 0; k < cfg.block_layers[b]; ++k)
-          if ((cfg.block_layers[b] - 1 - k) / p.wg_group[b] == g0 && wgrad1_channel_width(p.layers[b][k].cin, p.Vb[b]) == cw)
-            pairs += cdiv(p.layers[b][k].cin, cw);
+          if (wgrad1_channel_width(p.layers[b][k].cin, p.Vb[b]) == cw) pairs += cdiv(p.layers[b][k].cin, cw);
       }
       const int s1 = wgrad_pick_splits(1, N, p.Db[b], p.Hb[b], p.Wb[b], p.mid, ci, pairs);
-      const int s2 = wgrad_pick_splits(27, N, p.Db[b], p.Hb[b], p.Wb[b], cfg.growth, p.mid, p.wg_group[b]);
+      const int s2 = wgrad_pick_splits(27, N, p.Db[b], p.Hb[b], p.Wb[b], cfg.growth, p.mid, cfg.block_layers[b]);
       p.ns_c1[b].push_back(s1); p.ns_c2[b].push_back(s2);
       p.o_sl_c1[b].push_back(cv.take((size_t)s1 * p.mid * ci * F));
       p.o_sl_c2[b].push_back(cv.take((size_t)s2 * 27 * cfg.growth * p.mid * F));
@@ -194,8 +178,7 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
   for (int b = 0; b < nb; ++b) p.o_dz2[b] = cv.take((size_t)cfg.block_layers[b] * N * p.mid * p.Vb[b] * F);
   // cross-block K-split scratch: <= 256 blocks x one 32x32 (or 4 x 32x32) partial tile each, + per-tile counters
   p.o_kz_part = cv.take(KZ_PART_BYTES);
-  p.o_kz_cnt = cv.take(KZ_CNT_ENTRIES * sizeof(unsigned) + BLK_SYNC_BYTES);   // + the persistent block kernels' barrier words
-  p.o_blk_sync = p.o_kz_cnt + KZ_CNT_ENTRIES * sizeof(unsigned);
+  p.o_kz_cnt = cv.take(KZ_CNT_ENTRIES * sizeof(unsigned));
   // job tables
   int nlayers = 0;
   for (int b = 0; b < nb; ++b) nlayers += cfg.block_layers[b];
@@ -205,15 +188,6 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
   p.o_jobs_run = cv.take(sizeof(RunStatJob) * p.n_run_jobs);
   p.o_jobs_pack = cv.take(sizeof(PackJob) * p.n_pack_jobs);
   p.o_jobs_grad = cv.take(sizeof(GradJob) * p.n_grad_jobs);
-  p.o_jobs_blk = cv.take(sizeof(BlkLayer) * nlayers);
-  {
-    // r03 EXPERIMENT, off by default (plan option "persistent_forward" / MMNN_PERSISTENT=1): measured SLOWER than the per-layer
-    // kernels at 2 x 2 x 128^3 -- 31-43 us per layer against 26-28 (profiles/r03_ab_experiments.txt).
-    static const bool env_on = [] { const char* e = getenv("MMNN_PERSISTENT"); return e && e[0] == '1'; }();
-    p.persistent = env_on;
-    for (int b = 0; b < nb; ++b)
-      p.persist_b[b] = (p.cin_b[b] % 2 == 0) && block_fwd_supported(N, p.Db[b], p.Hb[b], p.Wb[b], p.ctot_b[b], p.mid, cfg.growth);
-  }
   p.n_layers = nlayers;
   p.o_wg_table = cv.take(sizeof(WgradArgs) * 2 * nlayers);     // [conv2 of every layer][conv1 of every layer], see plan_backward
   p.ws_bytes = cv.cur;
@@ -300,23 +274,6 @@ static bool build_tables(Plan& p, const float* params, float* run, char* ws) {
     j.src = s.sum; j.dst_off = db; gj[ig++] = j;    // dbeta
     p.max_grad = std::max(p.max_grad, (long)C);
   };
-  {   // per-layer table of the persistent block forward
-    BlkLayer* bl = reinterpret_cast<BlkLayer*>(hj + (p.o_jobs_blk - p.o_jobs_run));
-    int id = 0;
-    for (int b = 0; b < nb; ++b)
-      for (int l = 0; l < c.block_layers[b]; ++l, ++id) {
-        const LayerOff& lo = p.layers[b][l];
-        BlkLayer& e = bl[id];
-        memset(&e, 0, sizeof(e));
-        e.cin = lo.cin; e.layer_id = id;
-        e.w1 = fptr(ws, p.o_pk_c1[b][l]); e.w2 = fptr(ws, p.o_pk_c2f[b][l]);
-        e.g1 = params + lo.n1w; e.b1 = params + lo.n1b; e.g2 = params + lo.n2w; e.b2 = params + lo.n2b;
-        e.rm1 = run + lo.r1m; e.rv1 = run + lo.r1v; e.rm2 = run + lo.r2m; e.rv2 = run + lo.r2v;
-        e.t1 = fptr(ws, p.o_t1[b][l]);
-        const StatPtr st = statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]);
-        e.st_t1_sum = st.sum; e.st_t1_sq = st.sq;
-      }
-  }
   const double cnt0 = (double)p.N * p.D0 * p.H0 * p.W0;
   run_job(p.o_st_conv0, c.init_features, 0, c.init_features, p.r_n0m, p.r_n0v, cnt0);
   pack_job(p.p_conv0, p.o_pk_conv0, (c.in_channels % 2 == 0) ? 3 : 4, c.init_features, c.in_channels, (long)7 * stem_krows(c.in_channels) * 64);
@@ -418,7 +375,6 @@ int plan_set_option(Plan& p, const char* name, long value) {
   if (s == "trace_slots") { p.trace_slots = (int)value; return 0; }
   if (s == "params_version") { p.params_version = value; return 0; }
   if (s == "no_kz") { p.no_kz = value != 0; return 0; }
-  if (s == "persistent_forward") { p.persistent = value != 0; return 0; }
   set_error("set_option: unknown option '%s'", s.c_str());
   return 1;
 }
@@ -440,25 +396,17 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
     MMNN_HIP(hipHostMalloc(&p.host_jobs, p.host_jobs_bytes, hipHostMallocDefault));
     memset(p.host_jobs, 0, p.host_jobs_bytes);
   }
-  static const bool host_timing = [] { const char* e = getenv("MMNN_HOST_TIMING"); return e && e[0] == '1'; }();   // developer aid
-  static double ht[6] = {0, 0, 0, 0, 0, 0}; static long ht_n = 0;
-  auto now = [] { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; };
-  double t_prev = host_timing ? now() : 0.0;
-  auto lap = [&](int k) { if (host_timing) { const double t = now(); ht[k] += t - t_prev; t_prev = t; } };
   // The job tables hold pointers and counts only: they change when a buffer moves, in practice once.  Uploading them on every
   // forward cost 0.85 ms of HOST time per step (hipMemcpyAsync from the pinned staging buffer returns only when the copy has
   // been handed to the idle stream), which kept the enqueueing thread from ever running ahead of the GPU.
   if (p.tab_params != params || p.tab_run != run || p.tab_ws != ws) {
     if (p.tab_ws != nullptr) MMNN_HIP(hipStreamSynchronize(stream));   // an earlier upload from the same staging buffer may still be in flight
     build_tables(p, params, run, ws);
-    lap(0);
     MMNN_HIP(hipMemcpyAsync(ws + p.o_jobs_run, p.host_jobs, p.host_jobs_bytes, hipMemcpyHostToDevice, stream));
   }
   p.trace_seq = 0;
-  lap(1);
   if (training) MMNN_HIP(hipMemsetAsync(ws + p.o_fstat, 0, p.fstat_bytes, stream));
-  MMNN_HIP(hipMemsetAsync(ws + p.o_kz_cnt, 0, KZ_CNT_ENTRIES * sizeof(unsigned) + BLK_SYNC_BYTES, stream));
-  lap(2);
+  MMNN_HIP(hipMemsetAsync(ws + p.o_kz_cnt, 0, KZ_CNT_ENTRIES * sizeof(unsigned), stream));
   // The [k][m] weight panels only change when the parameters do.  A caller that can vouch for a version number (option
   // "params_version", non-zero) gets the repack skipped while it stays the same -- 31 of 32 forwards under the reference's
   // accumulate-to-64 rule (main.py:403-407).  Version 0 (the default) repacks on every forward.
@@ -469,7 +417,6 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
     p.packed_version = p.params_version; p.packed_params = params; p.packed_ws = ws;
     ++p.pack_launches;
   }
-  lap(3);
 
   const double cnt0 = (double)N * p.D0 * p.H0 * p.W0;
   {  // stem
@@ -490,29 +437,11 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
     if (!training) q.st_out.sum = nullptr;
     if ((rc = launch_stem_pool(q, stream))) return rc;
   }
-  lap(4);
   int layer_id = 0;
   for (int b = 0; b < nb; ++b) {
     const double cnt = (double)N * p.Vb[b];
     const long xns = (long)p.ctot_b[b] * p.Vb[b];
-    const bool persistent = p.persist_b[b] && p.persistent;
-    if (persistent) {   // every layer of the block in ONE resident launch (blockfwd.hpp)
-      BlockFwdArgs q;
-      memset(&q, 0, sizeof(q));
-      q.N = N; q.D = p.Db[b]; q.H = p.Hb[b]; q.W = p.Wb[b];
-      q.cin0 = p.cin_b[b]; q.ctot = p.ctot_b[b]; q.mid = p.mid; q.growth = c.growth; q.nlayers = c.block_layers[b];
-      q.x = fptr(ws, p.o_x[b]); q.x_ns = xns;
-      const StatPtr sx = statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]);
-      q.st_x_sum = sx.sum; q.st_x_sq = sx.sq; q.nrep = p.nrep_b[b];
-      q.layers = reinterpret_cast<const BlkLayer*>(ws + p.o_jobs_blk) + layer_id;
-      q.sync = reinterpret_cast<unsigned*>(ws + p.o_blk_sync) + 2 * b;
-      q.inv_count = 1.0 / cnt; q.eps = c.eps; q.training = training;
-      q.seed = seed; q.drop_p = training ? c.dropout_p : 0.f;
-      { ScopedTimer t(p, T_BLOCK_FWD, b, stream); rc = launch_block_fwd(q, stream); }
-      if (rc) return rc;
-      layer_id += c.block_layers[b];
-    }
-    for (int l = 0; l < c.block_layers[b] && !persistent; ++l, ++layer_id) {
+    for (int l = 0; l < c.block_layers[b]; ++l, ++layer_id) {
       const LayerOff& lo = p.layers[b][l];
       FpropArgs a;
       memset(&a, 0, sizeof(a));
@@ -582,12 +511,6 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
   if (training) {
     if ((rc = launch_running_stats(reinterpret_cast<const RunStatJob*>(ws + p.o_jobs_run), p.n_run_jobs, c.momentum,
                                    p.nbt_count == p.n_run_jobs ? p.nbt : nullptr, stream))) return rc;
-  }
-  lap(5);
-  if (host_timing && ++ht_n % 20 == 0) {
-    fprintf(stderr, "[mmnn host timing, us per forward] tables %.1f  memcpy %.1f  memsets %.1f  pack %.1f  stem %.1f  layers %.1f\n", ht[0] / 20, ht[1] / 20,
-            ht[2] / 20, ht[3] / 20, ht[4] / 20, ht[5] / 20);
-    for (double& v : ht) v = 0.0;
   }
   return 0;
 }
@@ -660,20 +583,15 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
   const bool first_call = hi == nb - 1;
   if (first_call) {
     MMNN_HIP(hipMemsetAsync(ws + p.o_bstat, 0, p.bstat_bytes, stream));
-    MMNN_HIP(hipMemsetAsync(ws + p.o_kz_cnt, 0, KZ_CNT_ENTRIES * sizeof(unsigned) + BLK_SYNC_BYTES, stream));
+    MMNN_HIP(hipMemsetAsync(ws + p.o_kz_cnt, 0, KZ_CNT_ENTRIES * sizeof(unsigned), stream));
   }
   p.bwd_next = lo - 1;
-  // Two streams: the data-gradient chain (conv2 dgrad -> conv1 dgrad -> next layer) is the critical path; the weight-gradient
-  // kernels only consume its products, so they run beside it on `side`, ordered by events.  Matters for the late dense blocks
-  // whose kernels fill a fraction of the chip.  Falls back to one stream if the side stream cannot be created.
   // Streams.  The weight-gradient kernels only consume products of the data-gradient chain, so they CAN run beside it on side
-  // streams (option "side_streams" / MMNN_SIDE_STREAMS = 1 or 2).  Default 0: since the small blocks' weight gradients go out as
-  // batched launches that fill the chip, overlapping buys nothing any more and costs event hand-offs plus contention with the
-  // chain (r02, 2x2x128^3: 10.7 ms with two side streams, 10.0 with one, 9.9 with none; same ranking at 64^3; one side stream is
+  // streams (option "side_streams" = 1 or 2; one stream if a side stream cannot be created).  Default 0: since the small blocks'
+  // weight gradients go out as batched launches that fill the chip, overlapping buys nothing any more and costs event hand-offs
+  // plus contention with the chain (r02, 2x2x128^3: 10.7 ms with two side streams, 10.0 with one, 9.9 with none; same ranking at 64^3; one side stream is
   // 2 % ahead at 96^3).  Block 1's kernels cannot share a CU anyway (two waves per SIMD each).
-  static const int env_side = [] { const char* e = getenv("MMNN_SIDE_STREAMS"); return e ? atoi(e) : -1; }();
-  static const bool env_single = [] { const char* e = getenv("MMNN_SINGLE_STREAM"); return e && e[0] == '1'; }();
-  const int want_side = (env_single || p.single_stream) ? 0 : (env_side >= 0 ? env_side : p.side_streams);
+  const int want_side = p.single_stream ? 0 : p.side_streams;
   const bool single = want_side <= 0;
   if (!single && (!p.side || (want_side >= 2 && !p.side2)) && !p.side_tried) {
     p.side_tried = true;
@@ -701,9 +619,9 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
     MMNN_HIP(hipStreamWaitEvent(to, e, 0));
     return 0;
   };
-  // Weight gradients are launched in groups of `grp` layers: one event record on the main stream per group.  Every record
-  // costs the chain ~6 us (the next kernel waits for the barrier packet's signal instead of being chained by the command
-  // processor), which is as long as a whole small-block kernel, so blocks 2-4 batch several layers per record.
+  // Weight gradients are launched once per dense block: one event record on the main stream per block.  Every record costs the
+  // chain ~6 us (the next kernel waits for the barrier packet's signal instead of being chained by the command processor), which
+  // is as long as a whole small-block kernel.
   // Device-resident argument tables of every layer's two weight-gradient launches (for the batched launches below).  Their
   // content does not depend on the step (the dropout seed travels as a kernel argument), so they are uploaded only when a
   // buffer moved -- in practice once.
@@ -731,22 +649,17 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
   struct PendingW { WgradArgs w2, w1; int b, id; };
   std::vector<PendingW> pend;        // consecutive layers in DESCENDING layer id
   static const bool no_batch = [] { const char* e = getenv("MMNN_NO_WGRAD_BATCH"); return e && e[0] == '1'; }();   // debugging aid
-  hipStream_t side_all = side, side2_all = side2;
   auto flush = [&]() -> int {
     if (pend.empty()) return 0;
     int rc2;
-    // MMNN_SIDE_FROM_BLOCK=b (with side streams on): only the weight gradients of dense blocks >= b (0-based) leave the main stream
-    static const int side_from = [] { const char* e = getenv("MMNN_SIDE_FROM_BLOCK"); return e ? atoi(e) : 0; }();
-    const bool on_side = two && pend[0].b >= side_from;
-    hipStream_t side = on_side ? side_all : stream, side2 = on_side ? side2_all : stream;
-    if (on_side) {
+    if (two) {
       hipEvent_t e = next_event();
       MMNN_REQUIRE(e != nullptr, "backward: cannot create a synchronisation event");
       MMNN_HIP(hipEventRecord(e, stream));
       MMNN_HIP(hipStreamWaitEvent(side, e, 0));
       if (side2 != side) MMNN_HIP(hipStreamWaitEvent(side2, e, 0));
     }
-    // The layers of a group are independent: ONE launch per kernel variant covers them all (blockIdx.z = layer).  pend holds
+    // The layers of a block are independent: ONE launch per kernel variant covers them all (blockIdx.z = layer).  pend holds
     // descending layer ids, so a run [i, j) of it is the ascending table range [pend[j-1].id, pend[i].id].
     const int np = (int)pend.size();
     std::vector<WgradArgs> host(np);
@@ -811,7 +724,6 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
     const double cnt = (double)N * p.Vb[b];
     const long xns = (long)p.ctot_b[b] * p.Vb[b];
     const long tns = (long)p.mid * p.Vb[b];
-    const int grp = p.wg_group[b];
     for (int l = c.block_layers[b] - 1; l >= 0; --l) {
       --layer_id;
       const LayerOff& lo = p.layers[b][l];
@@ -873,9 +785,7 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       PendingW pw;
       pw.w2 = w2; pw.w1 = w1; pw.b = b; pw.id = layer_id;
       pend.push_back(pw);
-      if ((int)pend.size() >= grp || l == 0) {
-        if ((rc = flush())) return rc;
-      }
+      if (l == 0 && (rc = flush())) return rc;
     }
     if (two) {
       // Every gradient of this block (its layers, and the transition / norm5 that consumed it) is final once the side streams
@@ -1021,7 +931,6 @@ long plan_ws_offset(const Plan& p, const char* name, int i, int j) {
   if (s == "pk_c2f" && okl(i, j)) return (long)p.o_pk_c2f[i][j];
   if (s == "pk_c2b" && okl(i, j)) return (long)p.o_pk_c2b[i][j];
   if (s == "pk_conv0") return (long)p.o_pk_conv0;
-  if (s == "blk_sync") return (long)p.o_blk_sync;
   if (s == "#pack_launches") return p.pack_launches;      // counter, not an offset (tests)
   return -1;
 }

@@ -2,8 +2,6 @@
 // every (taps, prologue, epilogue) combination is compiled in its own translation unit (csrc/fprop_inst_*.hip): the kernels
 // are heavily unrolled and one TU holding all ~25 instantiations takes a quarter of an hour to compile.
 #pragma once
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "fprop.hpp"
@@ -16,12 +14,8 @@ static int launch_cfg(const FpropArgs& a_in, hipStream_t stream) {
   constexpr bool KZ_OK = (MT * NT == 1) || (TAPS == 27 && TW <= 16);   // only the small-extent tiles are ever short of blocks
   using C = FpropCfg<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
   auto kern = fprop_kernel<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
-  size_t smem = C::smem_bytes(a.Cin);
+  const size_t smem = C::smem_bytes(a.Cin);
   MMNN_REQUIRE(smem <= 160 * 1024, "fprop: %zu bytes of LDS needed (Cin=%d) exceeds 160 KiB", smem, a.Cin);
-  {
-    static const char* env = getenv("MMNN_FPROP_MIN_SMEM");   // experiment knob: force fewer blocks per CU
-    if (env) { size_t v = (size_t)atol(env); if (v > smem && v <= 160 * 1024) smem = v; }
-  }
   static size_t configured[MAX_DEVICES] = {0};   // hipFuncSetAttribute is per device: remember the largest request of each
   size_t& conf = configured[current_device_slot()];
   if (smem > conf) {
@@ -44,8 +38,7 @@ static int launch_cfg(const FpropArgs& a_in, hipStream_t stream) {
   }
   // cross-block K-split: when the (voxel, row) tiles alone cannot fill the chip, slices of the channel axis become blocks too
   int kz = 1;
-  static const bool kz_off = []() { const char* e = getenv("MMNN_NO_KZ"); return e && e[0] == '1'; }();   // debugging aid
-  if (a.kz_part && a.kz_cnt && KZ_OK && !kz_off) {
+  if (a.kz_part && a.kz_cnt && KZ_OK) {
     const int nch = cdiv(a.Cin, KC);
     while (kz * 2 <= nch && tiles * mtiles * kz * 2 <= 256 && kz < 8) kz *= 2;
     if (kz > 1) {
@@ -92,18 +85,14 @@ int dispatch(const FpropArgs& a, hipStream_t s) {
     // r03: ONE 8-wave block of 128 rows x 256 voxels (2 x 4 x 32) per CU instead of two 4-wave blocks of 128 x 128: the 442 KB of weights
     // are staged once per 256 voxels instead of once per 128, the halo shrinks from 4.8x to 3.2x of the tile, a thread stages 4 + 1 items
     // per chunk instead of 7 + 4, and the kernel needs 163 registers instead of 228 + 64 accumulation registers.  Measured on the conv2
-    // data gradient of block 1 (A/B in one process, profiles/r03_ab_experiments.txt): 141.6 -> 137.7 us.  MMNN_DGRAD_TILE=0: the r02 tile.
-    static const int big = [] { const char* e = getenv("MMNN_DGRAD_TILE"); return e ? atoi(e) : 1; }();
-    if (big == 1) return launch_cfg<27, PRO, EPI, 2, 4, 1, 2, 2, 2, 2, 4, 32>(a, s);
-    return launch_cfg<27, PRO, EPI, 2, 2, 1, 2, 2, 2, 1, 4, 32>(a, s);
+    // data gradient of block 1 (A/B in one process, profiles/r03_ab_experiments.txt): 141.6 -> 137.7 us against the r02 tile (1 x 4 x 32).
+    return launch_cfg<27, PRO, EPI, 2, 4, 1, 2, 2, 2, 2, 4, 32>(a, s);
   }
   if (a.W > 8) {
     // r03: the 128 x 64 tile as eight one-tile waves (4 x 2) instead of 2 x 2 x 2 waves with two tiles each and an in-block K-split: no
     // in-block reduction, and slice sum and epilogue run on all eight waves instead of four (9.5k + 4.7k of the launch's 66k cycles).
-    // conv2 data gradient at 2 x 16^3: 0.407 -> 0.370 ms per step (twelve launches).  MMNN_DGRAD16=0: the r02 shape.
-    static const int alt = [] { const char* e = getenv("MMNN_DGRAD16"); return e ? atoi(e) : 1; }();
-    if (alt == 1) return launch_cfg<27, PRO, EPI, 4, 2, 1, 1, 1, 4, 1, 4, 16>(a, s);
-    return launch_cfg<27, PRO, EPI, 2, 2, 2, 2, 1, 4, 1, 4, 16>(a, s);
+    // conv2 data gradient at 2 x 16^3: 0.407 -> 0.370 ms per step (twelve launches) against the r02 shape.
+    return launch_cfg<27, PRO, EPI, 4, 2, 1, 1, 1, 4, 1, 4, 16>(a, s);
   }
   if (a.W > 4) return launch_cfg<27, PRO, EPI, 4, 1, 2, 1, 1, 4, 1, 4, 8>(a, s);
   return launch_cfg<27, PRO, EPI, 4, 1, 2, 1, 1, 4, 2, 4, 4>(a, s);

@@ -1,7 +1,5 @@
 // Stem kernels: conv0 (7x7x7, stride 2) forward on fp32 MFMA, BN+ReLU+max-pool forward/backward, conv0 weight
 // gradient on fp32 MFMA.  Reference: models/densenet.py:199-202 and their autograd adjoints (main.py:469).
-#include <stdlib.h>
-
 #include "stem.hpp"
 
 namespace mmnn {
@@ -383,8 +381,7 @@ int launch_stem_pool(const StemPoolArgs& a, hipStream_t stream) {
   MMNN_REQUIRE(a.Do == (a.Di - 1) / 2 + 1 && a.Ho == (a.Hi - 1) / 2 + 1 && a.Wo == (a.Wi - 1) / 2 + 1, "stem pool: output extent mismatch");
   const int Vo = a.Do * a.Ho * a.Wo;
   const size_t smem = sizeof(float) * PF_PLANES * PF_ROWS * (size_t)(a.Wi + 2);
-  static const bool tiled = [] { const char* e = getenv("MMNN_POOL_TILED"); return !(e && e[0] == '0'); }();   // =0: direct kernel (debugging)
-  if (tiled && smem <= 64 * 1024) {   // default dynamic-LDS limit; wider rows (W > 200) take the direct kernel
+  if (smem <= 64 * 1024) {   // default dynamic-LDS limit; wider rows (W > 200) take the direct kernel
     MMNN_LAUNCH(stem_pool_tiled_kernel, dim3(cdiv(a.Do, PF_TD) * cdiv(a.Ho, PF_TH), a.C, a.N), dim3(256), smem, stream, a);
     MMNN_HIP(hipGetLastError());
     return 0;

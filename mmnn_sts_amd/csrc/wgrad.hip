@@ -17,8 +17,7 @@ static void wg3_tile(int W, int& TD, int& TH, int& TW) {
 // pays from 97 channels on (r03, 16^3: all twelve layers of block 2 in one 8-wave launch 146 us against 159 us in two launches; at
 // 32^3 the same choice costs 340 against 281 us).
 static int wg1_wc(int Cin, long V) {
-  static const int thr_env = [] { const char* e = getenv("MMNN_WG1_WC8_FROM"); int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-  const int thr = thr_env > 0 ? thr_env : (V >= 32768 ? 256 : 97);
+  const int thr = V >= 32768 ? 256 : 97;
   return Cin >= thr ? 8 : 4;
 }
 
@@ -29,9 +28,8 @@ int wgrad_pick_splits(int taps, int N, int D, int H, int W, int M, int Cin, int 
     wg3_tile(W, TD, TH, TW);
     const long ntiles = (long)N * cdiv(D, TD) * cdiv(H, TH) * cdiv(W, TW);
     const int cgroups = cdiv(Cin, 32);
-    static const int cap = [] { const char* e = getenv("MMNN_WG3_SPLIT_CAP"); int v = e ? atoi(e) : 0; return v > 0 ? v : 64; }();
-    long s = (cap > 64 ? 1024 : 512) / ((long)cgroups * batch);
-    if (s > cap) s = cap;
+    long s = 512 / ((long)cgroups * batch);
+    if (s > 64) s = 64;
     if (s > ntiles / 2) s = ntiles / 2;
     return s < 1 ? 1 : (int)s;
   }
@@ -43,7 +41,7 @@ int wgrad_pick_splits(int taps, int N, int D, int H, int W, int M, int Cin, int 
   // matters is balance: ~2048 equal blocks per launch = four rounds of two blocks per CU measured best (r02, after the loads left
   // the FLAT path: 317 / 281 / 266 / 295 us at 1024 / 1536 / 2048 / 3072; step 8.84 / 8.81 / 8.79 / 8.85 ms including the larger
   // reduction), bounded by the slab the reduction kernel then has to read (64 MiB per layer).
-  static const int target = [] { const char* e = getenv("MMNN_WG1_BLOCKS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 2048; }();
+  constexpr long target = 2048;
   const long groups = (long)cdiv(Cin, 32 * wc) * cdiv(M, 128);
   // batch > 1: the number of (layer, channel group) pairs that share the launch -- every block of the launch then gets the same
   // number of chunks, whatever its layer's channel count

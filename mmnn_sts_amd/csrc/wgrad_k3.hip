@@ -1,7 +1,5 @@
 // 3x3x3 weight-gradient kernels: instantiations + launches (its own translation unit: the kernels are heavily unrolled and this
 // file and wgrad_k1.hip are the two longest compiles of the build).  Host-side validation and split selection: wgrad.hip.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "wgrad.hpp"
@@ -41,8 +39,7 @@ static int launch3_batched(const WgradArgs* host, const WgradArgs* dev, int coun
     gx = std::max(gx, host[i].nsplit); gy = std::max(gy, cdiv(host[i].Cin, 32));
     uniform = uniform && host[i].nsplit == host[0].nsplit && cdiv(host[i].Cin, 32) == cdiv(host[0].Cin, 32);
   }
-  static const bool no_remap = [] { const char* e = getenv("MMNN_WG3_NO_XCD"); return e && e[0] == '1'; }();   // A/B knob
-  if (uniform && gy > 1 && !no_remap) {
+  if (uniform && gy > 1) {
     const long ngroups = (long)count * gx;                       // (layer, split) pairs; each owns gy blocks on one XCD
     const long blocks = 8l * gy * ((ngroups + 7) / 8);
     MMNN_REQUIRE(blocks < (1l << 31), "wgrad batch: grid out of range");
