@@ -1,19 +1,28 @@
 // Dense-layer conv2 forward (models/densenet.py:80-85: ReLU(BN(t1)) -> 3x3x3 convolution to `growth` = 32 new channels -> channel dropout,
 // + the batch statistics of the new channels for their consumers) for extents wider than 16 voxels, on the bf16 matrix pipe with fp32 accuracy:
-// every fp32 operand is split into three bf16 pieces (x = hi + mid + lo, round to nearest at each step: 24 mantissa bits) and a product
-// becomes six v_mfma_f32_32x32x16_bf16 (mid.mid, hi.lo, lo.hi, hi.mid, mid.hi, hi.hi) into one fp32 accumulator.  Measured against fp64
-// (tools/microbench/bf16x3_gemm.hip, conv3_bf16x3.hip): 4.5e-7 rms -- the fp32 matrix instruction's own error is 1.0e-6 -- at 16x the
+// every fp32 operand is split into three bf16 pieces (x = hi + mid + lo, round to nearest at each step: 24 mantissa bits, bf16x3.hpp) and a
+// product becomes six v_mfma_f32_32x32x16_bf16 (mid.mid, hi.lo, lo.hi, hi.mid, mid.hi, hi.hi) into one fp32 accumulator.  Measured against
+// fp64 (tools/microbench/bf16x3_gemm.hip, conv3_bf16x3.hip): 4.5e-7 rms -- the fp32 matrix instruction's own error is 1.0e-6 -- at 16x the
 // rate per instruction cycle; and the bf16 instruction leaves the vector ALU free beside it, which v_mfma_f32_32x32x2_f32 does not
 // (profiles/r03_microbench_mfma_acc_file.txt).  Same arguments, same results to fp32 rounding and the same statistics protocol as
 // fprop_kernel<27, PRO_BNRELU, EPI_STORE_STATS> (fprop.hpp), which stays the kernel for every other shape.
+//   Both operands arrive pre-split.  The weights come from a panel the pack launch wrote once per parameter version (PackJob kind 5 / 6,
+//   [piece][tap][k / 8][row] 16-byte entries: a lane's fragment is three 16-byte loads).  The activations come from operand planes a split
+//   pass writes right before the convolution, in the same launch_*: conv3_split_bnrelu_kernel (forward, ReLU(BN(T1)) of all input channels)
+//   and conv3_split_bnbwd_kernel (data gradient, the BN backward operand of the layer's 32 channels), [piece][n][c / 8][voxel] 16-byte
+//   entries = one LDS operand row each.  The convolution kernels stage with 16-byte copies and do no conversion arithmetic at all; the
+//   split passes use exactly the arithmetic the kernels used to apply on operand load, so the pieces -- and the results -- are the same.
 //   MFMA mapping: i = output channel (32), j = voxel (32 consecutive w), k = input channel (16 per instruction); a tap is a row offset.
 //   Workgroup: 4 waves, a 2 x 4 x 32 voxel tile.  In-block K-split over the taps: every wave multiplies all eight 32-voxel rows with taps
 //   wv, wv + 4, ... (a weight operand serves 48 MFMAs, no two waves load the same weights); the four partial tiles are summed through LDS.
 //   LDS: the halo tile of a 16-channel chunk as three bf16 planes [piece][channel half][halo voxel] of 16-byte entries, two buffers: chunk
-//   ch + 1 is loaded at the head of chunk ch's tap loop, BN + ReLU + split between its MFMAs, written to the other buffer; one barrier per chunk.
+//   ch + 1 is loaded at the head of chunk ch's tap loop and copied to the other buffer between its MFMAs; one barrier per chunk.
+//   Occupancy: 154 KB of LDS per workgroup = one workgroup (one wave per SIMD) per CU; block 1 of the flagship (2 x 32^3) has exactly one
+//   tile per CU, so a second resident workgroup would have nothing to run -- the latency is hidden inside the wave (one chunk ahead).
 #include <stdlib.h>
 
 #include "fprop.hpp"
+#include "bf16x3.hpp"
 
 namespace mmnn {
 
@@ -29,25 +38,88 @@ struct Geo {
   static constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2, HV = HD * HH * HW, ROWS = TD * TH * TW / 32;
   static constexpr int ITEMS = (2 * HV + 255) / 256;
   static constexpr size_t OPER_BYTES = (size_t)2 * 6 * HV * 16;                            // two buffers of [3][2][HV] 16-byte entries
-  static constexpr size_t SMEM = OPER_BYTES + sizeof(float) * (2 * MAXC + 2 * 4 * 32 + 32);   // + BN coefficients, statistics scratch, dropout scales
+  static constexpr size_t SMEM = OPER_BYTES + sizeof(float) * (2 * 4 * 32 + 32);          // + statistics scratch, dropout scales
   static_assert(TD * TH * TW % 32 == 0 && (TW == 32 || TW == 16), "rows of 32 voxels");
   static_assert(ITEMS <= NT, "one staging item per tap slot");
   static_assert(4 * ROWS * 16 * 64 * sizeof(float) <= OPER_BYTES, "the partial tiles are summed in the operand buffers");
   static_assert(SMEM <= 160 * 1024, "LDS");
 };
 
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-__device__ __forceinline__ uint32_t pack2(__bf16 lo, __bf16 hi) {
-  return (uint32_t)__builtin_bit_cast(unsigned short, lo) | ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
-}
 __device__ __forceinline__ bf16x8_t as_bf16x8(uint4 v) { return __builtin_bit_cast(bf16x8_t, v); }
 }  // namespace c3b
 
+// ----------------------------------------------------------------------------------------------------------------
+// Split passes: one thread per (voxel, group of 8 channels), 16-byte entries [piece][n][c / 8][v].  A workgroup is 256 voxels of one channel
+// group of one sample; its 8 coefficients go through LDS while its operand loads are in flight.
+// ----------------------------------------------------------------------------------------------------------------
+// forward operand: ReLU(BN(T1)) of all Cin channels -- exactly fmaxf(fmaf(a_c, x, b_c), 0) with bn_fwd_coef, then split3
+__global__ void __launch_bounds__(256) conv3_split_bnrelu_kernel(const FpropArgs a) {
+  __shared__ float cf[2][8];
+  const int c8 = blockIdx.y, n = blockIdx.z, C8 = a.Cin / 8, V = a.D * a.H * a.W;
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  const float* __restrict__ x = a.in0 + (long)n * a.in0_ns + (long)(a.in0_coff + 8 * c8) * V;
+  float xv[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) xv[e] = v < V ? x[(long)e * V + v] : 0.f;
+  if (threadIdx.x < 8) {
+    float ca, cb, mu, rs;
+    bn_fwd_coef(a.bn_in, 8 * c8 + threadIdx.x, ca, cb, mu, rs);
+    cf[0][threadIdx.x] = ca; cf[1][threadIdx.x] = cb;
+  }
+  __syncthreads();
+  if (v >= V) return;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) xv[e] = fmaxf(fmaf(cf[0][e], xv[e], cf[1][e]), 0.f);
+  uint4 hi, mid, lo;
+  split3x8(xv, hi, mid, lo);
+  const long ps = (long)a.N * C8 * V;
+  uint4* __restrict__ dst = reinterpret_cast<uint4*>(a.x3) + ((long)n * C8 + c8) * V + v;
+  dst[0] = hi; dst[ps] = mid; dst[2 * ps] = lo;
+}
+
+// data-gradient operand of the layer's 32 output channels: f = fmaf(p_c s, G, fmaf(q_c s, X, r_c s)), bn_bwd_coef(gr_in), s = drop_scale(drop_in)
+__global__ void __launch_bounds__(256) conv3_split_bnbwd_kernel(const FpropArgs a) {
+  __shared__ float cf[3][8];
+  const int c8 = blockIdx.y, n = blockIdx.z, C8 = a.Cin / 8, V = a.D * a.H * a.W;
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  const float* __restrict__ gn = a.in0 + (long)n * a.in0_ns + (long)(a.in0_coff + 8 * c8) * V;
+  const float* __restrict__ xn = a.in1 + (long)n * a.in1_ns + (long)(a.in1_coff + 8 * c8) * V;
+  float gv[8], xv[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    gv[e] = v < V ? gn[(long)e * V + v] : 0.f;
+    xv[e] = v < V ? xn[(long)e * V + v] : 0.f;
+  }
+  if (threadIdx.x < 8) {
+    const int c = 8 * c8 + threadIdx.x;
+    float p_, q_, r_;
+    bn_bwd_coef(a.gr_in, c, p_, q_, r_);
+    const float sc = drop_scale(a.drop_in, n, c);
+    cf[0][threadIdx.x] = p_ * sc; cf[1][threadIdx.x] = q_ * sc; cf[2][threadIdx.x] = r_ * sc;
+  }
+  __syncthreads();
+  if (v >= V) return;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) gv[e] = fmaf(cf[0][e], gv[e], fmaf(cf[1][e], xv[e], cf[2][e]));
+  uint4 hi, mid, lo;
+  split3x8(gv, hi, mid, lo);
+  const long ps = (long)a.N * C8 * V;
+  uint4* __restrict__ dst = reinterpret_cast<uint4*>(a.x3) + ((long)n * C8 + c8) * V + v;
+  dst[0] = hi; dst[ps] = mid; dst[2 * ps] = lo;
+}
+
+static int launch_split(bool bwd, const FpropArgs& a, hipStream_t stream) {
+  const int V = a.D * a.H * a.W;
+  const dim3 grid((unsigned)cdiv(V, 256), (unsigned)(a.Cin / 8), (unsigned)a.N);
+  if (bwd) MMNN_LAUNCH(conv3_split_bnbwd_kernel, grid, dim3(256), 0, stream, a);
+  else MMNN_LAUNCH(conv3_split_bnrelu_kernel, grid, dim3(256), 0, stream, a);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// conv2 forward on the pre-split planes (a.x3) and weight panel (a.w3, pack kind 5: [piece][tap][Cin / 8][32])
+// ----------------------------------------------------------------------------------------------------------------
 template <int TD, int TH, int TW>
 __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a) {
   using namespace c3b;
@@ -55,77 +127,66 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
   constexpr int HH = G::HH, HW = G::HW, HV = G::HV, ROWS = G::ROWS, ITEMS = G::ITEMS;
   constexpr size_t OPER_BYTES = G::OPER_BYTES;
   extern __shared__ uint4 xs128[];                          // [2][3][2][HV]
-  float* const coef = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + OPER_BYTES);   // [2][MAXC]: a_c, b_c
-  float* const sred = coef + 2 * MAXC;                      // [2][4][32]
+  float* const sred = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + OPER_BYTES);   // [2][4][32]
   float* const dsc = sred + 2 * 4 * 32;                     // [32] dropout scale of the output channels
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = tid & 1;
-  const int D = a.D, H = a.H, W = a.W, V = D * H * W, Cin = a.Cin, nchunk = Cin / KC;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int D = a.D, H = a.H, W = a.W, V = D * H * W, C8 = a.Cin / 8, nchunk = a.Cin / KC;
   const int twn = (W + TW - 1) / TW, thn = (H + TH - 1) / TH, tdn = (D + TD - 1) / TD;
   int b = blockIdx.x;
   const int w0 = (b % twn) * TW; b /= twn;
   const int h0 = (b % thn) * TH; b /= thn;
   const int d0 = (b % tdn) * TD;
   const int n = b / tdn;
-  const float* __restrict__ xin = a.in0 + (long)n * a.in0_ns + (long)a.in0_coff * V;
-  const float* __restrict__ wgt = a.w;
-  for (int c = tid; c < Cin; c += 256) {
-    float ca_, cb_, mu, rs;
-    bn_fwd_coef(a.bn_in, c, ca_, cb_, mu, rs);
-    coef[c] = ca_; coef[MAXC + c] = cb_;
-  }
+  const long ps = (long)a.N * C8 * V;                       // entries per piece plane
+  const uint4* __restrict__ xin = reinterpret_cast<const uint4*>(a.x3) + (long)n * C8 * V;
+  const uint4* __restrict__ wp = reinterpret_cast<const uint4*>(a.w3);
   if (tid < 32) dsc[tid] = drop_scale(a.drop_out, n, tid);
   f32x16_t acc[ROWS];
 #pragma unroll
   for (int t = 0; t < ROWS; ++t)
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-  float xr[ITEMS][8], ca[8], cb[8];
-  auto item_pos = [&](int it, int& hv, int& o) -> bool {
+  // staging item = (channel half g, halo voxel hv), g the slow index: a wave's 64 lanes copy 64 consecutive halo entries of one plane
+  uint4 xr[ITEMS][3];
+  auto item_pos = [&](int it, int& g, int& hv, int& o) -> bool {
     const int item = tid + it * 256;
-    hv = item >> 1;
+    g = item >= HV;
+    hv = item - g * HV;
     const int hd = hv / (HH * HW), hh = (hv / HW) % HH, hw = hv % HW;
     const int d = d0 + hd - 1, h = h0 + hh - 1, w = w0 + hw - 1;
     o = (d * H + h) * W + w;
     return item < 2 * HV && (unsigned)d < (unsigned)D && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
   };
   auto issue = [&](int ch) {
-    const int c0 = ch * KC + 8 * g;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ca[e] = coef[c0 + e]; cb[e] = coef[MAXC + c0 + e]; }
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
-      int hv, o;
-      const bool ok = item_pos(it, hv, o);
+      int g, hv, o;
+      const bool ok = item_pos(it, g, hv, o);
+      const uint4* src = xin + (long)(2 * ch + g) * V + o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) xr[it][e] = ok ? xin[(long)(c0 + e) * V + o] : 0.f;
+      for (int p = 0; p < 3; ++p) xr[it][p] = ok ? src[p * ps] : make_uint4(0u, 0u, 0u, 0u);   // zero padding AFTER BN + ReLU
     }
   };
   auto commit_item = [&](int it, int buf) {
-    int hv, o;
-    const bool ok = item_pos(it, hv, o);
+    int g, hv, o;
+    item_pos(it, g, hv, o);
     if (tid + it * 256 >= 2 * HV) return;
-    __bf16 ph[8], pm[8], pl[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) split3(ok ? fmaxf(fmaf(ca[e], xr[it][e], cb[e]), 0.f) : 0.f, ph[e], pm[e], pl[e]);   // zero padding AFTER BN + ReLU
     uint4* dst = xs128 + buf * (6 * HV);
-    dst[(0 * 2 + g) * HV + hv] = make_uint4(pack2(ph[0], ph[1]), pack2(ph[2], ph[3]), pack2(ph[4], ph[5]), pack2(ph[6], ph[7]));
-    dst[(1 * 2 + g) * HV + hv] = make_uint4(pack2(pm[0], pm[1]), pack2(pm[2], pm[3]), pack2(pm[4], pm[5]), pack2(pm[6], pm[7]));
-    dst[(2 * 2 + g) * HV + hv] = make_uint4(pack2(pl[0], pl[1]), pack2(pl[2], pl[3]), pack2(pl[4], pl[5]), pack2(pl[6], pl[7]));
+#pragma unroll
+    for (int p = 0; p < 3; ++p) dst[(p * 2 + g) * HV + hv] = xr[it][p];
   };
-  // weights w[(c * 27 + tap) * w_ld + m] (fp32 panel of the library): lane = (row m, channel half); ring slot ti holds tap wv + 4 ti of the
-  // chunk ahead as eight raw fp32 values, split into the three operand pieces where they are used
-  float wr[NT][8];
+  // weights: lane = (row m, channel half); ring slot ti holds the three pieces of tap wv + 4 ti of the chunk ahead
+  bf16x8_t wr[NT][3];
   auto load_w = [&](int ti, int ch) {
     const int tap = wv + 4 * ti;
     if (tap < 27 && ch < nchunk) {
-      const int c0 = ch * KC + 8 * (lane >> 5);
+      const int c8 = 2 * ch + (lane >> 5);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) wr[ti][e] = wgt[((long)(c0 + e) * 27 + tap) * a.w_ld + (lane & 31)];
+      for (int p = 0; p < 3; ++p) wr[ti][p] = as_bf16x8(wp[((long)(p * 27 + tap) * C8 + c8) * 32 + (lane & 31)]);
     }
   };
 #pragma unroll
   for (int ti = 0; ti < NT; ++ti) load_w(ti, 0);
-  __syncthreads();                                          // coefficients
   issue(0);
 #pragma unroll
   for (int it = 0; it < ITEMS; ++it) commit_item(it, 0);
@@ -139,12 +200,9 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
       const int tap = wv + 4 * ti;
       if (tap < 27) {
         const int td = tap / 9, th = (tap / 3) % 3, tw = tap % 3;
-        __bf16 ph[8], pm[8], pl[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) split3(wr[ti][e], ph[e], pm[e], pl[e]);
         bf16x8_t aw[3];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { aw[0][e] = ph[e]; aw[1][e] = pm[e]; aw[2][e] = pl[e]; }
+        for (int p = 0; p < 3; ++p) aw[p] = wr[ti][p];
         load_w(ti, ch + 1);
 #pragma unroll
         for (int t = 0; t < ROWS; ++t) {
@@ -230,20 +288,21 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
 
 // ----------------------------------------------------------------------------------------------------------------
 // conv2 DATA GRADIENT of the wide extents (autograd adjoint of the same layer, main.py:469): 32 -> 128 channels,
-//   operand f(c, v) = p_c G[c][v] + q_c X[c][v] + r_c (BN backward of the layer's output channels on operand load, dropout scale folded in,
-//   zero padding after it), epilogue: ReLU mask of conv2's input (pre = a_m T1 + b_m > 0), store, d beta / d gamma sums of norm2 --
-// the contract of fprop_kernel<27, PRO_GRAD, EPI_MASK_STORE>.  Same tile and LDS planes as the forward; here the reduction is only 32
-// channels x 27 taps, so BOTH 16-channel chunks are staged up-front (one buffer each), wave wv owns output rows 32 wv .. 32 wv + 31 for all eight
-// voxel rows and all taps (no cross-wave sum), and its weights come through a three-tap ring of raw fp32 values split where they are used.
+//   operand f(c, v) = p_c G[c][v] + q_c X[c][v] + r_c (BN backward of the layer's output channels, dropout scale folded in, zero padding
+//   after it: conv3_split_bnbwd_kernel writes it pre-split to a.x3), epilogue: ReLU mask of conv2's input (pre = a_m T1 + b_m > 0), store,
+//   d beta / d gamma sums of norm2 -- the contract of fprop_kernel<27, PRO_GRAD, EPI_MASK_STORE>.  Same tile and LDS planes as the forward;
+//   here the reduction is only 32 channels x 27 taps, so BOTH 16-channel chunks get an LDS buffer of their own: chunk 0 is staged up front,
+//   chunk 1's copies are in flight under chunk 0's first (td, th) pair of taps and land in LDS before the second one.  Wave wv owns output
+//   rows 32 wv .. 32 wv + 31 for all eight voxel rows and all taps (no cross-wave sum); its weights come through a three-tap ring of
+//   pre-split fragments (pack kind 6: [piece][tap][32 / 8][128]).
 // ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs a) {
   using namespace c3b;
   using G = Geo<2, 4, 32>;
-  constexpr int TH = 4, TW = 32, HH = G::HH, HW = G::HW, HV = G::HV, ROWS = G::ROWS, ITEMS = G::ITEMS, PF = 3;
+  constexpr int TH = 4, TW = 32, HH = G::HH, HW = G::HW, HV = G::HV, ROWS = G::ROWS, ITEMS = G::ITEMS, PF = 3, C8 = 4;
   extern __shared__ uint4 xs128[];                          // [2 chunks][3][2][HV]
-  float* const coef = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + G::OPER_BYTES);   // [3][32]: p, q, r (x dropout scale)
-  float* const ecoef = coef + 96;                           // [4][128]: a_m, b_m, mean_m, rstd_m of norm2
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = tid & 1;
+  float* const ecoef = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + G::OPER_BYTES);   // [4][128]: a_m, b_m, mean_m, rstd_m of norm2
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int D = a.D, H = a.H, W = a.W, V = D * H * W;
   const int twn = (W + TW - 1) / TW, thn = (H + TH - 1) / TH, tdn = (D + 1) / 2;
   int b = blockIdx.x;
@@ -251,96 +310,75 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
   const int h0 = (b % thn) * TH; b /= thn;
   const int d0 = (b % tdn) * 2;
   const int n = b / tdn;
-  const float* __restrict__ in0n = a.in0 + (long)n * a.in0_ns + (long)a.in0_coff * V;
-  const float* __restrict__ in1n = a.in1 + (long)n * a.in1_ns + (long)a.in1_coff * V;
-  const float* __restrict__ wgt = a.w;
-  if (tid < 32) {
-    float p_, q_, r_;
-    bn_bwd_coef(a.gr_in, tid, p_, q_, r_);
-    const float sc = drop_scale(a.drop_in, n, tid);
-    coef[tid] = p_ * sc; coef[32 + tid] = q_ * sc; coef[64 + tid] = r_ * sc;
-  }
-  if (tid >= 128) {
-    const int m = tid - 128;
-    float ea, eb, mu, rs;
-    bn_fwd_coef(a.ebn, m, ea, eb, mu, rs);
-    ecoef[m] = ea; ecoef[128 + m] = eb; ecoef[256 + m] = mu; ecoef[384 + m] = rs;
-  }
-  float x0[2][ITEMS][8], x1[2][ITEMS][8];                  // both chunks' loads are in flight together (the accumulators are not live yet)
-  auto item_pos = [&](int it, int& hv, int& o) -> bool {
+  const long ps = (long)a.N * C8 * V;
+  const uint4* __restrict__ xin = reinterpret_cast<const uint4*>(a.x3) + (long)n * C8 * V;
+  const uint4* __restrict__ wp = reinterpret_cast<const uint4*>(a.w3);
+  uint4 xr[ITEMS][3];
+  auto item_pos = [&](int it, int& g, int& hv, int& o) -> bool {
     const int item = tid + it * 256;
-    hv = item >> 1;
+    g = item >= HV;
+    hv = item - g * HV;
     const int hd = hv / (HH * HW), hh = (hv / HW) % HH, hw = hv % HW;
     const int d = d0 + hd - 1, h = h0 + hh - 1, w = w0 + hw - 1;
     o = (d * H + h) * W + w;
     return item < 2 * HV && (unsigned)d < (unsigned)D && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
   };
   auto issue = [&](int ch) {
-    const int c0 = ch * KC + 8 * g;
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
-      int hv, o;
-      const bool ok = item_pos(it, hv, o);
+      int g, hv, o;
+      const bool ok = item_pos(it, g, hv, o);
+      const uint4* src = xin + (long)(2 * ch + g) * V + o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        x0[ch][it][e] = ok ? in0n[(long)(c0 + e) * V + o] : 0.f;
-        x1[ch][it][e] = ok ? in1n[(long)(c0 + e) * V + o] : 0.f;
+      for (int p = 0; p < 3; ++p) xr[it][p] = ok ? src[p * ps] : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  auto commit = [&](int buf) {
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      int g, hv, o;
+      item_pos(it, g, hv, o);
+      if (tid + it * 256 < 2 * HV) {
+        uint4* dst = xs128 + buf * (6 * HV);
+#pragma unroll
+        for (int p = 0; p < 3; ++p) dst[(p * 2 + g) * HV + hv] = xr[it][p];
       }
     }
   };
-  auto commit_item = [&](int it, int buf) {
-    int hv, o;
-    const bool ok = item_pos(it, hv, o);
-    if (tid + it * 256 >= 2 * HV) return;
-    const int c0 = buf * KC + 8 * g;
-    __bf16 ph[8], pm[8], pl[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      split3(ok ? fmaf(coef[c0 + e], x0[buf][it][e], fmaf(coef[32 + c0 + e], x1[buf][it][e], coef[64 + c0 + e])) : 0.f, ph[e], pm[e], pl[e]);
-    uint4* dst = xs128 + buf * (6 * HV);
-    dst[(0 * 2 + g) * HV + hv] = make_uint4(pack2(ph[0], ph[1]), pack2(ph[2], ph[3]), pack2(ph[4], ph[5]), pack2(ph[6], ph[7]));
-    dst[(1 * 2 + g) * HV + hv] = make_uint4(pack2(pm[0], pm[1]), pack2(pm[2], pm[3]), pack2(pm[4], pm[5]), pack2(pm[6], pm[7]));
-    dst[(2 * 2 + g) * HV + hv] = make_uint4(pack2(pl[0], pl[1]), pack2(pl[2], pl[3]), pack2(pl[4], pl[5]), pack2(pl[6], pl[7]));
-  };
-  // weights w[(c * 27 + tap) * w_ld + m]: lane = (row m of this wave's tile, channel half); ring slot tap % PF
-  float wr[PF][8];
+  // weights: lane = (row m of this wave's tile, channel half); ring slot tap % PF
+  bf16x8_t wr[PF][3];
   auto load_w = [&](int slot, int tap, int ch) {
     if (ch < 2) {
-      const int c0 = ch * KC + 8 * (lane >> 5);
+      const int c8 = 2 * ch + (lane >> 5);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) wr[slot][e] = wgt[((long)(c0 + e) * 27 + tap) * a.w_ld + wv * 32 + (lane & 31)];
+      for (int p = 0; p < 3; ++p) wr[slot][p] = as_bf16x8(wp[((long)(p * 27 + tap) * C8 + c8) * 128 + wv * 32 + (lane & 31)]);
     }
   };
 #pragma unroll
   for (int t = 0; t < PF; ++t) load_w(t, t, 0);
-  // both chunks are staged before the first MFMA: 112 staging registers beside 128 accumulators and the weight ring spill (a first build
-  // that loaded chunk 1 under chunk 0's MFMAs: 168 spilled registers)
   issue(0);
+  if (tid >= 128) {                                         // the statistics loads travel beside the operand loads
+    const int m = tid - 128;
+    float ea, eb, mu, rs;
+    bn_fwd_coef(a.ebn, m, ea, eb, mu, rs);
+    ecoef[m] = ea; ecoef[128 + m] = eb; ecoef[256 + m] = mu; ecoef[384 + m] = rs;
+  }
+  commit(0);
   issue(1);
-  __syncthreads();                                          // coefficients (their statistics loads travel beside the operand loads)
-#pragma unroll
-  for (int it = 0; it < ITEMS; ++it) commit_item(it, 0);
-#pragma unroll
-  for (int it = 0; it < ITEMS; ++it) commit_item(it, 1);
   __syncthreads();
   f32x16_t acc[ROWS];
 #pragma unroll
   for (int t = 0; t < ROWS; ++t)
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-  for (int ch = 0; ch < 2; ++ch) {
-#pragma unroll 1
-    for (int tq = 0; tq < 9; ++tq) {                        // (td, th) pairs; the three tw of a pair are unrolled = the ring's three slots
+  auto pair = [&](int ch, int tq) {                         // (td, th) pair tq of chunk ch; its three tw = the ring's three slots
     const int td = tq / 3, th = tq % 3;
 #pragma unroll
     for (int tw = 0; tw < 3; ++tw) {
       const int tap = tq * 3 + tw;
-      __bf16 ph[8], pm[8], pl[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) split3(wr[tw][e], ph[e], pm[e], pl[e]);
       bf16x8_t aw[3];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { aw[0][e] = ph[e]; aw[1][e] = pm[e]; aw[2][e] = pl[e]; }
+      for (int p = 0; p < 3; ++p) aw[p] = wr[tw][p];
       if (tq < 8) load_w(tw, tap + PF, ch); else load_w(tw, tw, ch + 1);
 #pragma unroll
       for (int t = 0; t < ROWS; ++t) {
@@ -356,8 +394,14 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[0], acc[t], 0, 0, 0);
       }
     }
-    }
-  }
+  };
+  pair(0, 0);
+  commit(1);                                                // chunk 1 -> its own buffer: nobody reads it before this barrier
+  __syncthreads();
+#pragma unroll 1
+  for (int tq = 1; tq < 9; ++tq) pair(0, tq);
+#pragma unroll 1
+  for (int tq = 0; tq < 9; ++tq) pair(1, tq);
   // epilogue: register q of lane l = output row 32 wv + 8 (q / 4) + 4 (l / 32) + q % 4, voxel column l % 32 of row t
   const float* __restrict__ exn = a.ex + (long)n * a.ex_ns + (long)a.ex_coff * V;
   float* __restrict__ outn = a.out + (long)n * a.out_ns + (long)a.out_coff * V;
@@ -419,6 +463,9 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
   }
 }
 
+// operand planes of one launch: three pieces x N x Cin / 8 x V entries of 16 bytes (the forward's Cin = 128, the data gradient's Cin = 32)
+size_t conv3_bf16x3_plane_bytes(const FpropArgs& a) { return (size_t)3 * a.N * (a.Cin / 8) * a.D * a.H * a.W * 16; }
+
 bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a) {
   static const int mode = [] { const char* e = getenv("MMNN_BF16X3_DGRAD"); return e ? atoi(e) : 1; }();
   static const int fmode = [] { const char* e = getenv("MMNN_BF16X3"); return e ? atoi(e) : 32; }();
@@ -427,10 +474,11 @@ bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a) {
 
 int launch_conv3_dgrad_bf16x3(const FpropArgs& a, hipStream_t stream) {
   using G = c3b::Geo<2, 4, 32>;
-  constexpr size_t SMEM = G::OPER_BYTES + sizeof(float) * (96 + 512);
+  constexpr size_t SMEM = G::OPER_BYTES + sizeof(float) * 512;
   static_assert(SMEM <= 160 * 1024, "LDS");
   MMNN_REQUIRE(conv3_dgrad_bf16x3_eligible(a), "conv3 dgrad bf16x3: shape not handled (M=%d, Cin=%d, W=%d)", a.M, a.Cin, a.W);
   MMNN_REQUIRE(a.in1 && a.ex && a.dgamma && a.dbeta, "conv3 dgrad bf16x3: operands missing");
+  MMNN_REQUIRE(a.w3 && a.x3 && a.x3_bytes >= conv3_bf16x3_plane_bytes(a), "conv3 dgrad bf16x3: pre-split weights or plane scratch missing");
   MMNN_REQUIRE((long)(a.M + 1) * a.D * a.H * a.W < (1l << 31), "conv3 dgrad bf16x3: volume too large for 32-bit element offsets");
   const long tiles = (long)a.N * cdiv(a.D, 2) * cdiv(a.H, 4) * cdiv(a.W, 32);
   MMNN_REQUIRE(tiles > 0 && tiles < (1l << 31), "conv3 dgrad bf16x3: grid out of range");
@@ -440,6 +488,7 @@ int launch_conv3_dgrad_bf16x3(const FpropArgs& a, hipStream_t stream) {
     MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_dgrad_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
     conf = true;
   }
+  if (int rc = launch_split(true, a, stream)) return rc;
   MMNN_LAUNCH(conv3_dgrad_bf16x3_kernel, dim3((unsigned)tiles), dim3(256), SMEM, stream, a);
   MMNN_HIP(hipGetLastError());
   return 0;
@@ -458,6 +507,7 @@ int launch_conv3_fwd_bf16x3(const FpropArgs& a, hipStream_t stream) {
   using G = c3b::Geo<2, 4, 32>;
   MMNN_REQUIRE(conv3_fwd_bf16x3_eligible(a), "conv3 bf16x3: shape not handled (M=%d, Cin=%d, W=%d)", a.M, a.Cin, a.W);
   MMNN_REQUIRE(a.drop_in.p <= 0.f, "conv3 bf16x3: no input dropout on this path");
+  MMNN_REQUIRE(a.w3 && a.x3 && a.x3_bytes >= conv3_bf16x3_plane_bytes(a), "conv3 bf16x3: pre-split weights or plane scratch missing");
   MMNN_REQUIRE((long)(a.Cin + 1) * a.D * a.H * a.W < (1l << 31), "conv3 bf16x3: volume too large for 32-bit element offsets");
   const long tiles = (long)a.N * cdiv(a.D, 2) * cdiv(a.H, 4) * cdiv(a.W, 32);
   MMNN_REQUIRE(tiles > 0 && tiles < (1l << 31), "conv3 bf16x3: grid out of range");
@@ -467,6 +517,7 @@ int launch_conv3_fwd_bf16x3(const FpropArgs& a, hipStream_t stream) {
     MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_fwd_bf16x3_kernel<2, 4, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM));
     conf = true;
   }
+  if (int rc = launch_split(false, a, stream)) return rc;
   MMNN_LAUNCH((conv3_fwd_bf16x3_kernel<2, 4, 32>), dim3((unsigned)tiles), dim3(256), G::SMEM, stream, a);
   MMNN_HIP(hipGetLastError());
   return 0;

@@ -135,14 +135,31 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
   // packed weights
   p.o_pk_conv0 = cv.take((size_t)7 * stem_krows(cfg.in_channels) * 64 * F);
   p.o_pk_c1.assign(nb, {}); p.o_pk_c2f.assign(nb, {}); p.o_pk_c2b.assign(nb, {}); p.o_pk_tr.clear();
+  p.o_pk_c2f3.assign(nb, {}); p.o_pk_c2b3.assign(nb, {});
+  p.x3_bytes = 0;
   for (int b = 0; b < nb; ++b) {
+    // the conv2 launches of this block that run on the three-piece bf16 kernels get their weights pre-split, and the plane scratch
+    // is sized for the largest of them
+    FpropArgs f, g;
+    memset(&f, 0, sizeof(f));
+    f.N = N; f.D = p.Db[b]; f.H = p.Hb[b]; f.W = p.Wb[b];
+    g = f;
+    f.Cin = p.mid; f.M = cfg.growth;
+    g.Cin = cfg.growth; g.M = p.mid;
+    const bool f3 = conv3_fwd_bf16x3_eligible(f), b3 = conv3_dgrad_bf16x3_eligible(g);
+    if (f3) p.x3_bytes = std::max(p.x3_bytes, conv3_bf16x3_plane_bytes(f));
+    if (b3) p.x3_bytes = std::max(p.x3_bytes, conv3_bf16x3_plane_bytes(g));
+    const size_t split_panel = (size_t)3 * cfg.growth * p.mid * 27 * sizeof(uint16_t);
     for (int l = 0; l < cfg.block_layers[b]; ++l) {
       p.o_pk_c1[b].push_back(cv.take((size_t)p.mid * p.layers[b][l].cin * F));
       p.o_pk_c2f[b].push_back(cv.take((size_t)cfg.growth * p.mid * 27 * F));
       p.o_pk_c2b[b].push_back(cv.take((size_t)cfg.growth * p.mid * 27 * F));
+      p.o_pk_c2f3[b].push_back(f3 ? cv.take(split_panel) : 0);
+      p.o_pk_c2b3[b].push_back(b3 ? cv.take(split_panel) : 0);
     }
     if (b != nb - 1) p.o_pk_tr.push_back(cv.take((size_t)p.trans[b].cin * p.trans[b].cout * F));
   }
+  p.o_x3 = p.x3_bytes ? cv.take(p.x3_bytes) : 0;
   // weight-gradient slabs
   p.ns_conv0 = stem_wgrad_pick_splits(N, p.D0, p.H0, p.W0, cfg.in_channels);
   p.o_sl_conv0 = cv.take((size_t)p.ns_conv0 * cfg.in_channels * cfg.init_features * 352 * F);
@@ -183,7 +200,7 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
   int nlayers = 0;
   for (int b = 0; b < nb; ++b) nlayers += cfg.block_layers[b];
   p.n_run_jobs = nbn;
-  p.n_pack_jobs = 1 + 3 * nlayers + (nb - 1);
+  p.n_pack_jobs = 1 + 5 * nlayers + (nb - 1);             // (an upper bound: kinds 5 / 6 only for the bf16x3 layers)
   p.n_grad_jobs = 3 + 6 * nlayers + 3 * (nb - 1) + 2;
   p.o_jobs_run = cv.take(sizeof(RunStatJob) * p.n_run_jobs);
   p.o_jobs_pack = cv.take(sizeof(PackJob) * p.n_pack_jobs);
@@ -292,6 +309,8 @@ static bool build_tables(Plan& p, const float* params, float* run, char* ws) {
       pack_job(lo.c1, p.o_pk_c1[b][l], 0, p.mid, lo.cin, (long)p.mid * lo.cin);
       pack_job(lo.c2, p.o_pk_c2f[b][l], 1, c.growth, p.mid, (long)c.growth * p.mid * 27);
       pack_job(lo.c2, p.o_pk_c2b[b][l], 2, c.growth, p.mid, (long)c.growth * p.mid * 27);
+      if (p.o_pk_c2f3[b][l]) pack_job(lo.c2, p.o_pk_c2f3[b][l], 5, c.growth, p.mid, (long)27 * (p.mid / 8) * c.growth);
+      if (p.o_pk_c2b3[b][l]) pack_job(lo.c2, p.o_pk_c2b3[b][l], 6, c.growth, p.mid, (long)27 * (c.growth / 8) * p.mid);
       grad_bn(p.o_dg_n1[b][l], lo.cin, lo.n1w, lo.n1b);
       grad_slab(0, p.o_sl_c1[b][l], (long)p.mid * lo.cin, p.ns_c1[b][l], p.mid, lo.cin, lo.c1, (long)p.mid * lo.cin);
       grad_bn(p.o_dg_n2[b][l], p.mid, lo.n2w, lo.n2b);
@@ -455,7 +474,8 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
       a.out = fptr(ws, p.o_t1[b][l]); a.out_ns = (long)p.mid * p.Vb[b]; a.out_coff = 0;
       a.st_out = statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]);
       if (!training) a.st_out.sum = nullptr;
-      a.pf_ptr = fptr(ws, p.o_pk_c2f[b][l]); a.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27);
+      if (p.o_pk_c2f3[b][l]) { a.pf_ptr = fptr(ws, p.o_pk_c2f3[b][l]); a.pf_bytes = (unsigned)(3 * sizeof(uint16_t) * c.growth * p.mid * 27); }
+      else { a.pf_ptr = fptr(ws, p.o_pk_c2f[b][l]); a.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27); }
       { ScopedTimer t(p, T_CONV1_FWD, b, stream); rc = launch_fprop(a, 1, PRO_BNRELU, EPI_STORE_STATS, stream); }
       if (rc) return rc;
       // conv2: ReLU(BN(T1)) -> growth new channels of the concat buffer (+ channel dropout)
@@ -467,6 +487,7 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
       e.in0 = fptr(ws, p.o_t1[b][l]); e.in0_ns = (long)p.mid * p.Vb[b]; e.in0_coff = 0;
       e.bn_in = bnfwd(p, statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]), params, run, lo.n2w, lo.n2b, lo.r2m, lo.r2v, cnt, training);
       e.w = fptr(ws, p.o_pk_c2f[b][l]); e.w_ld = c.growth;
+      if (p.o_pk_c2f3[b][l]) { e.w3 = ws + p.o_pk_c2f3[b][l]; e.x3 = ws + p.o_x3; e.x3_bytes = p.x3_bytes; }
       e.out = fptr(ws, p.o_x[b]); e.out_ns = xns; e.out_coff = lo.cin;
       e.drop_out = dropcfg(p, seed, layer_id, training);
       e.st_out = statptr(ws, p.o_st_x[b], p.ctot_b[b], lo.cin, p.nrep_b[b]);
@@ -743,6 +764,7 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       a.gr_in = concat_grad(b, lo.cin);
       a.drop_in = drop;
       a.w = fptr(ws, p.o_pk_c2b[b][l]); a.w_ld = p.mid;
+      if (p.o_pk_c2b3[b][l]) { a.w3 = ws + p.o_pk_c2b3[b][l]; a.x3 = ws + p.o_x3; a.x3_bytes = p.x3_bytes; }
       float* dz2 = fptr(ws, p.o_dz2[b]) + (long)l * N * tns;
       a.out = dz2; a.out_ns = tns; a.out_coff = 0;
       a.ex = fptr(ws, p.o_t1[b][l]); a.ex_ns = tns; a.ex_coff = 0;
@@ -777,7 +799,8 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       d.ebn = bn1;
       d.dbeta = dg1.sum; d.dgamma = dg1.sq;
       d.s_acc = sptr(b, 0);
-      if (l > 0) { d.pf_ptr = fptr(ws, p.o_pk_c2b[b][l - 1]); d.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27); }
+      if (l > 0 && p.o_pk_c2b3[b][l - 1]) { d.pf_ptr = fptr(ws, p.o_pk_c2b3[b][l - 1]); d.pf_bytes = (unsigned)(3 * sizeof(uint16_t) * c.growth * p.mid * 27); }
+      else if (l > 0) { d.pf_ptr = fptr(ws, p.o_pk_c2b[b][l - 1]); d.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27); }
       { ScopedTimer t(p, T_CONV1_DGRAD, b, stream); rc = launch_fprop(d, 1, PRO_GRAD, EPI_MASK_ACCUM, stream); }
       if (rc) return rc;
       // both weight gradients of this layer can run from here on (its G slice was final before conv2 dgrad, dZ2 and
@@ -930,6 +953,10 @@ long plan_ws_offset(const Plan& p, const char* name, int i, int j) {
   if (s == "pk_c1" && okl(i, j)) return (long)p.o_pk_c1[i][j];
   if (s == "pk_c2f" && okl(i, j)) return (long)p.o_pk_c2f[i][j];
   if (s == "pk_c2b" && okl(i, j)) return (long)p.o_pk_c2b[i][j];
+  if (s == "pk_c2f3" && okl(i, j)) return p.o_pk_c2f3[i][j] ? (long)p.o_pk_c2f3[i][j] : -1;
+  if (s == "pk_c2b3" && okl(i, j)) return p.o_pk_c2b3[i][j] ? (long)p.o_pk_c2b3[i][j] : -1;
+  if (s == "x3") return p.x3_bytes ? (long)p.o_x3 : -1;        // planes of the latest bf16x3 conv2 launch
+  if (s == "#x3_bytes") return (long)p.x3_bytes;
   if (s == "pk_conv0") return (long)p.o_pk_conv0;
   if (s == "#pack_launches") return p.pack_launches;      // counter, not an offset (tests)
   return -1;

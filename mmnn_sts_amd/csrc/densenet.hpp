@@ -53,6 +53,8 @@ struct Plan {
   // packed weights
   size_t o_pk_conv0;
   std::vector<std::vector<size_t>> o_pk_c1, o_pk_c2f, o_pk_c2b;
+  std::vector<std::vector<size_t>> o_pk_c2f3, o_pk_c2b3;   // pre-split bf16 panels (pack kinds 5 / 6) of the layers on the bf16x3 kernels, else 0
+  size_t o_x3 = 0, x3_bytes = 0;                           // operand planes of the bf16x3 conv2 launches, one buffer for all of them
   std::vector<size_t> o_pk_tr;
   // weight-gradient slabs
   size_t o_sl_conv0; int ns_conv0;

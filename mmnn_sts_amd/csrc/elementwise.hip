@@ -1,4 +1,5 @@
 #include "elementwise.hpp"
+#include "bf16x3.hpp"
 
 #include <algorithm>
 
@@ -219,6 +220,31 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackJob* jobs) {
         const int jj = tj * 32 + ty + 8 * r, i = ti * 32 + tx;
         if (i < I && jj < J) dst[(long)(flip ? J - 1 - jj : jj) * I + i] = tile[tx][ty + 8 * r];
       }
+    }
+    return;
+  }
+  if (j.kind >= 5) {
+    // pre-split conv2 panels of the three-piece bf16 kernels (conv3_bf16x3.hip): entry i of every piece holds 8 reduction channels of
+    // one (tap, channel group, output row); the three pieces of a value are the split3 of the fp32 weight the fp32 panels hold
+    uint4* dst = reinterpret_cast<uint4*>(j.dst);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < j.count; i += (long)gridDim.x * 256) {
+      float v[8];
+      if (j.kind == 5) {                    // [t][c/8][m] of w[m][c][t]
+        const int m = (int)(i % j.M);
+        const long k = i / j.M;
+        const int c8 = (int)(k % (j.C / 8)), t = (int)(k / (j.C / 8));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = j.src[((long)m * j.C + 8 * c8 + e) * 27 + t];
+      } else {                              // [t][m/8][c] of w[m][c][26-t]
+        const int c = (int)(i % j.C);
+        const long k = i / j.C;
+        const int m8 = (int)(k % (j.M / 8)), t = (int)(k / (j.M / 8));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = j.src[((long)(8 * m8 + e) * j.C + c) * 27 + 26 - t];
+      }
+      uint4 hi, mid, lo;
+      split3x8(v, hi, mid, lo);
+      dst[i] = hi; dst[j.count + i] = mid; dst[2 * j.count + i] = lo;
     }
     return;
   }

@@ -64,8 +64,10 @@ struct PackJob {
                  // 1: conv2 fwd  dst[(c*27+t)][m] = w[m][c][t]
                  // 2: conv2 dgrad dst[(m*27+t)][c] = w[m][c][26-t]
                  // 3: stem, even Cin: dst[kd][c*49 + kh*7+kw][64] ; 4: stem, odd Cin: dst[kd][c*56 + kh*8 + kw][64]
+                 // 5: conv2 fwd, three bf16 pieces (bf16x3.hpp): 16-byte entries dst[piece][t][c/8][m] of w[m][c..c+7][t]
+                 // 6: conv2 dgrad, three bf16 pieces: 16-byte entries dst[piece][t][m/8][c] of w[m..m+7][c][26-t]
   int M, C;      // weight is [M][C][taps]
-  long count;    // number of dst elements
+  long count;    // number of dst elements (kinds 5, 6: entries of one piece)
 };
 int launch_pack(const PackJob* jobs_dev, int njobs, long max_count, hipStream_t stream);
 

@@ -62,6 +62,9 @@ struct FpropArgs {
   // one dword per 128-byte line of [pf_ptr, pf_ptr + pf_bytes) while their own first chunk is in flight, which pulls the range
   // into that XCD's L2 before the next kernel starts.
   const float* pf_ptr; unsigned pf_bytes;
+  // Three-piece bf16 kernels only (conv3_bf16x3.hip, bf16x3.hpp): the pre-split weight panel (pack kind 5 / 6, replaces `w` there) and
+  // the scratch its split pass writes the operand planes to, [3][N][Cin/8][V] 16-byte entries, `x3_bytes` long.  Null everywhere else.
+  const void* w3; void* x3; size_t x3_bytes;
   // Filled in by launch_cfg (callers leave them zero): ceil(2^32 / d) for the divisors of the workgroup -> tile decomposition
   // (3x3x3: tiles along W, H, D; 1x1x1: tiles per sample), 0 when d == 1.  q = mulhi(b, magic) is exact for b * d < 2^32 and is two
   // scalar instructions; the compiler's sequence for a run-time divisor is ~25 dependent ones, three times over, ahead of the first load.
@@ -72,6 +75,10 @@ struct FpropArgs {
 };
 
 int launch_fprop(const FpropArgs& a, int taps, int pro, int epi, hipStream_t stream);
+// conv3_bf16x3.hip: which conv2 launches run on the three-piece bf16 kernels (they need FpropArgs::w3 / x3), and the plane scratch they need
+bool conv3_fwd_bf16x3_eligible(const FpropArgs& a);
+bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a);
+size_t conv3_bf16x3_plane_bytes(const FpropArgs& a);
 int current_device_slot();   // index of the calling thread's current HIP device, for per-device caches of kernel attributes
 constexpr int MAX_DEVICES = 32;
 
