@@ -15,8 +15,8 @@
  *     Workspace sizes come from pure query functions.  All tensors are contiguous fp32, NCDHW.
  *   - threading: the library keeps no mutable state of its own besides the thread-local error text and per-device
  *     "kernel attribute already set" flags (idempotent; written with the value every writer would write).  A PLAN, however, is
- *     a stateful object: it owns host-side job tables (one pinned staging buffer), two lazily created side streams and a pool
- *     of events for its backward, and optional timers.  One plan must therefore not be used from two threads at once, and it
+ *     a stateful object: it owns host-side job tables (pinned staging buffers) and optional timers; its forward and backward
+ *     enqueue every kernel on the caller's stream.  One plan must therefore not be used from two threads at once, and it
  *     belongs to the device that was current when its first forward ran.  Sequential use from different threads is fine
  *     (autograd calls backward from another thread than forward).  Different plans are independent of each other.
  */
@@ -87,9 +87,8 @@ int mmnn_densenet_set_timer(void* plan, int32_t kernel_class, int32_t block);
 int mmnn_densenet_read_timer(void* plan, double* total_ms, int64_t* launches);
 int mmnn_densenet_read_timer_class(void* plan, int32_t kernel_class, int32_t block, double* total_ms, int64_t* launches);
 /* plan options.  "no_kz" (0/1): never split the channel axis of a small-extent convolution over several workgroups (the tests' reference
- * for the cross-workgroup hand-off).  "side_streams" (0, 1 or 2; default 0): run the weight-gradient kernels of the backward on that many side streams
- * beside the data-gradient chain instead of on the caller's stream -- same results.  "single_stream" (0/1): force 0 side streams
- * (un-overlapped kernel durations for profiling).  "params_version" (any non-zero
+ * for the cross-workgroup hand-off).  "single_stream" (any value): accepted and ignored -- the backward always runs on the caller's
+ * stream (it once selected between that and side streams for the weight gradients).  "params_version" (any non-zero
  * number the caller changes whenever it changed a parameter; 0 = unknown, the default): the forward re-packs the weights only
  * when the version, the parameter buffer or the workspace differs from the last packed one. */
 int mmnn_densenet_set_option(void* plan, const char* name, int64_t value);

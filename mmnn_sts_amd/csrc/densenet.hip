@@ -1,7 +1,6 @@
 // Launch plan of the DenseNet backbone forward / backward (see densenet.hpp).
 #include "densenet.hpp"
 
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -190,8 +189,8 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
       p.o_sl_tr.push_back(cv.take((size_t)s * p.trans[b].cout * p.trans[b].cin * F));
     }
   }
-  // dZ2 (gradient wrt the norm2 output) of every layer has its own buffer: the conv1 weight gradients that read it run on a
-  // side stream, several layers behind the data-gradient chain, and must never make the chain wait for a buffer.
+  // dZ2 (gradient wrt the norm2 output) of every layer has its own buffer: the block's batched conv1 weight gradient reads every
+  // layer's dZ2 after the data-gradient chain has passed them all.
   for (int b = 0; b < nb; ++b) p.o_dz2[b] = cv.take((size_t)cfg.block_layers[b] * N * p.mid * p.Vb[b] * F);
   // cross-block K-split scratch: <= 256 blocks x one 32x32 (or 4 x 32x32) partial tile each, + per-tile counters
   p.o_kz_part = cv.take(KZ_PART_BYTES);
@@ -221,11 +220,6 @@ void plan_free(Plan& p) {
   p.wg_pinned = nullptr;
   for (hipEvent_t e : p.timer_ev) (void)hipEventDestroy(e);
   p.timer_ev.clear();
-  for (hipEvent_t e : p.sync_ev) (void)hipEventDestroy(e);
-  p.sync_ev.clear();
-  if (p.side) (void)hipStreamDestroy(p.side);
-  if (p.side2) (void)hipStreamDestroy(p.side2);
-  p.side = p.side2 = nullptr;
 }
 
 static StatPtr statptr(char* ws, size_t o, int C, int off, int nrep = NREP) {
@@ -240,12 +234,16 @@ static StatPtr statptr(char* ws, size_t o, int C, int off, int nrep = NREP) {
 }
 static float* fptr(char* ws, size_t o) { return reinterpret_cast<float*>(ws + o); }
 
+// developer aid: every convolution launch gets its own 64 x 16 slot of the phase-trace buffer (null when tracing is off or the slots ran out)
+static unsigned long long* trace_slot(const Plan& p) {
+  return (p.trace_base && p.trace_seq < p.trace_slots) ? p.trace_base + (size_t)(p.trace_seq++) * 64 * 16 : nullptr;
+}
+
 // capacities travel with the arguments: no process-global state
 static void set_kz(FpropArgs& a, const Plan& p, char* ws) {
   a.kz_part = p.no_kz ? nullptr : fptr(ws, p.o_kz_part); a.kz_cnt = reinterpret_cast<unsigned*>(ws + p.o_kz_cnt);
   a.kz_part_bytes = KZ_PART_BYTES; a.kz_cnt_entries = KZ_CNT_ENTRIES;
-  // developer aid: every convolution launch gets its own 64 x 16 slot of the phase-trace buffer, in launch order
-  a.trace = (p.trace_base && p.trace_seq < p.trace_slots) ? p.trace_base + (size_t)(p.trace_seq++) * 64 * 16 : nullptr;
+  a.trace = trace_slot(p);
 }
 
 static BnFwd bnfwd(const Plan& p, StatPtr st, const float* params, float* run, long w, long b, long rm, long rv, double count, int training) {
@@ -388,8 +386,7 @@ int plan_read_timer(Plan& p, int kind, int block, double* total_ms, long* count)
 
 int plan_set_option(Plan& p, const char* name, long value) {
   const std::string s(name ? name : "");
-  if (s == "single_stream") { p.single_stream = value != 0; return 0; }
-  if (s == "side_streams") { p.side_streams = value < 0 ? 0 : (value > 2 ? 2 : (int)value); p.side_tried = false; return 0; }
+  if (s == "single_stream") return 0;   // accepted, no effect: the backward always runs on the caller's stream
   if (s == "trace_buffer") { p.trace_base = reinterpret_cast<unsigned long long*>(value); p.trace_seq = 0; return 0; }   // device pointer, 0 = off
   if (s == "trace_slots") { p.trace_slots = (int)value; return 0; }
   if (s == "params_version") { p.params_version = value; return 0; }
@@ -536,9 +533,9 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
   return 0;
 }
 
-// Arguments of the two weight-gradient launches of dense layer (b, l): conv2 (3x3x3, `w2`) and conv1 (1x1x1, `w1`).
-static void layer_wgrad_args(const Plan& p, const float* params, float* run, char* ws, int b, int l, int layer_id, uint64_t seed,
-                             WgradArgs& w2, WgradArgs& w1) {
+// Arguments of the two weight-gradient launches of dense layer (b, l): conv2 (3x3x3, `w2`) and conv1 (1x1x1, `w1`).  The dropout
+// seed is left 0: the batched kernels take the step's as an argument.
+static void layer_wgrad_args(const Plan& p, const float* params, float* run, char* ws, int b, int l, int layer_id, WgradArgs& w2, WgradArgs& w1) {
   const NetCfg& c = p.cfg;
   const int N = p.N;
   const double cnt = (double)N * p.Vb[b];
@@ -556,7 +553,7 @@ static void layer_wgrad_args(const Plan& p, const float* params, float* run, cha
   w2.gr.st = statptr(ws, p.o_st_x[b], p.ctot_b[b], lo.cin, p.nrep_b[b]);       // BN-backward of the layer's concat slice (gammas folded into G)
   w2.gr.s = statptr(ws, p.o_s_x[b], p.ctot_b[b], lo.cin, p.nrep_b[b]);
   w2.gr.gamma = nullptr; w2.gr.inv_count = 1.0 / cnt; w2.gr.eps = c.eps;
-  w2.drop.seed = seed; w2.drop.layer = layer_id; w2.drop.p = c.dropout_p;
+  w2.drop.layer = layer_id; w2.drop.p = c.dropout_p;
   w2.x = fptr(ws, p.o_t1[b][l]); w2.x_ns = tns; w2.x_coff = 0;
   w2.bn = bn2;
   w2.slab = fptr(ws, p.o_sl_c2[b][l]); w2.slab_stride = (long)27 * c.growth * p.mid; w2.nsplit = p.ns_c2[b][l];
@@ -607,45 +604,9 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
     MMNN_HIP(hipMemsetAsync(ws + p.o_kz_cnt, 0, KZ_CNT_ENTRIES * sizeof(unsigned), stream));
   }
   p.bwd_next = lo - 1;
-  // Streams.  The weight-gradient kernels only consume products of the data-gradient chain, so they CAN run beside it on side
-  // streams (option "side_streams" = 1 or 2; one stream if a side stream cannot be created).  Default 0: since the small blocks'
-  // weight gradients go out as batched launches that fill the chip, overlapping buys nothing any more and costs event hand-offs
-  // plus contention with the chain (r02, 2x2x128^3: 10.7 ms with two side streams, 10.0 with one, 9.9 with none; same ranking at 64^3; one side stream is
-  // 2 % ahead at 96^3).  Block 1's kernels cannot share a CU anyway (two waves per SIMD each).
-  const int want_side = p.single_stream ? 0 : p.side_streams;
-  const bool single = want_side <= 0;
-  if (!single && (!p.side || (want_side >= 2 && !p.side2)) && !p.side_tried) {
-    p.side_tried = true;
-    if (!p.side && hipStreamCreateWithFlags(&p.side, hipStreamNonBlocking) != hipSuccess) p.side = nullptr;
-    if (want_side >= 2 && p.side && !p.side2 && hipStreamCreateWithFlags(&p.side2, hipStreamNonBlocking) != hipSuccess) p.side2 = nullptr;
-  }
-  hipStream_t side = (p.side && !single) ? p.side : stream;        // conv2 weight gradients (+ the big gradient finalise)
-  hipStream_t side2 = (p.side2 && !single && want_side >= 2) ? p.side2 : side;   // conv1 weight gradients
-  const bool two = side != stream;
-  p.sync_used = 0;
-  auto next_event = [&]() -> hipEvent_t {
-    if (p.sync_used == p.sync_ev.size()) {
-      hipEvent_t e = nullptr;
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-      p.sync_ev.push_back(e);
-    }
-    return p.sync_ev[p.sync_used++];
-  };
-  // `to` waits for everything enqueued on `from` so far
-  auto order = [&](hipStream_t from, hipStream_t to) -> int {
-    if (!two) return 0;
-    hipEvent_t e = next_event();
-    MMNN_REQUIRE(e != nullptr, "backward: cannot create a synchronisation event");
-    MMNN_HIP(hipEventRecord(e, from));
-    MMNN_HIP(hipStreamWaitEvent(to, e, 0));
-    return 0;
-  };
-  // Weight gradients are launched once per dense block: one event record on the main stream per block.  Every record costs the
-  // chain ~6 us (the next kernel waits for the barrier packet's signal instead of being chained by the command processor), which
-  // is as long as a whole small-block kernel.
-  // Device-resident argument tables of every layer's two weight-gradient launches (for the batched launches below).  Their
-  // content does not depend on the step (the dropout seed travels as a kernel argument), so they are uploaded only when a
-  // buffer moved -- in practice once.
+  // Device-resident argument tables of every layer's two weight-gradient launches; the pinned staging buffer is their host copy.
+  // Their content does not depend on the step (the dropout seed travels as a kernel argument), so they are uploaded only when a
+  // buffer moved or tracing was switched on or off -- in practice once.
   if (first_call || !p.wg_uploaded) {
     const size_t bytes = sizeof(WgradArgs) * 2 * p.n_layers;
     if (!p.wg_pinned) {
@@ -656,7 +617,11 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
     std::vector<WgradArgs> tab(2 * p.n_layers);
     int id = 0;
     for (int b = 0; b < nb; ++b)
-      for (int l = 0; l < c.block_layers[b]; ++l, ++id) layer_wgrad_args(p, params, run, ws, b, l, id, 0, tab[id], tab[p.n_layers + id]);
+      for (int l = 0; l < c.block_layers[b]; ++l, ++id) {
+        layer_wgrad_args(p, params, run, ws, b, l, id, tab[id], tab[p.n_layers + id]);
+        tab[id].trace = trace_slot(p);
+        tab[p.n_layers + id].trace = trace_slot(p);
+      }
     if (!p.wg_uploaded || memcmp(tab.data(), p.wg_shadow.data(), bytes) != 0) {
       if (p.wg_uploaded) MMNN_HIP(hipStreamSynchronize(stream));   // an earlier upload from the pinned buffer may still be in flight
       memcpy(p.wg_pinned, tab.data(), bytes);
@@ -667,53 +632,28 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
   }
   const WgradArgs* dev_w2 = reinterpret_cast<const WgradArgs*>(ws + p.o_wg_table);
   const WgradArgs* dev_w1 = dev_w2 + p.n_layers;
-  struct PendingW { WgradArgs w2, w1; int b, id; };
-  std::vector<PendingW> pend;        // consecutive layers in DESCENDING layer id
-  static const bool no_batch = [] { const char* e = getenv("MMNN_NO_WGRAD_BATCH"); return e && e[0] == '1'; }();   // debugging aid
-  auto flush = [&]() -> int {
-    if (pend.empty()) return 0;
+  const WgradArgs* host_w2 = static_cast<const WgradArgs*>(p.wg_pinned);
+  const WgradArgs* host_w1 = host_w2 + p.n_layers;
+  // The weight gradients of dense block b (layer ids [id0, id0 + its layer count)) go out once the data-gradient chain has passed all
+  // of its layers.  The layers are independent: ONE launch per kernel variant covers them all (blockIdx.z = layer).
+  auto block_wgrads = [&](int b, int id0) -> int {
+    const int np = c.block_layers[b];
     int rc2;
-    if (two) {
-      hipEvent_t e = next_event();
-      MMNN_REQUIRE(e != nullptr, "backward: cannot create a synchronisation event");
-      MMNN_HIP(hipEventRecord(e, stream));
-      MMNN_HIP(hipStreamWaitEvent(side, e, 0));
-      if (side2 != side) MMNN_HIP(hipStreamWaitEvent(side2, e, 0));
-    }
-    // The layers of a block are independent: ONE launch per kernel variant covers them all (blockIdx.z = layer).  pend holds
-    // descending layer ids, so a run [i, j) of it is the ascending table range [pend[j-1].id, pend[i].id].
-    const int np = (int)pend.size();
-    std::vector<WgradArgs> host(np);
-    if (np > 1 && !no_batch) {
-      for (int i = 0; i < np; ++i) host[np - 1 - i] = pend[i].w2;
-      { ScopedTimer t(p, T_CONV2_WGRAD, pend[0].b, side); rc2 = launch_wgrad_batched(host.data(), dev_w2 + pend[np - 1].id, np, seed, 27, PRO_BNRELU, side); }
+    { ScopedTimer t(p, T_CONV2_WGRAD, b, stream); rc2 = launch_wgrad_batched(host_w2 + id0, dev_w2 + id0, np, seed, 27, PRO_BNRELU, stream); }
+    if (rc2) return rc2;
+    // conv1: runs [i, j) of equal channel-group width (monotonic in the layer index), last layers first; a run of one layer takes
+    // the unbatched kernel
+    for (int j = id0 + np; j > id0;) {
+      int i = j - 1;
+      while (i > id0 && wgrad1_channel_width(host_w1[i - 1].Cin, p.Vb[b]) == wgrad1_channel_width(host_w1[j - 1].Cin, p.Vb[b])) --i;
+      {
+        ScopedTimer t(p, T_CONV1_WGRAD, b, stream);
+        rc2 = j - i > 1 ? launch_wgrad_batched(host_w1 + i, dev_w1 + i, j - i, seed, 1, PRO_BNRELU, stream)
+                        : launch_wgrad1(host_w1[i], PRO_BNRELU, stream);
+      }
       if (rc2) return rc2;
-      for (int i = 0; i < np;) {       // conv1: runs of equal channel-group width (monotonic in the layer index)
-        int j = i + 1;
-        const long vb = (long)pend[i].w1.D * pend[i].w1.H * pend[i].w1.W;
-        while (j < np && wgrad1_channel_width(pend[j].w1.Cin, vb) == wgrad1_channel_width(pend[i].w1.Cin, vb)) ++j;
-        if (j - i > 1) {
-          for (int k = i; k < j; ++k) host[j - 1 - k] = pend[k].w1;
-          ScopedTimer t(p, T_CONV1_WGRAD, pend[i].b, side2);
-          rc2 = launch_wgrad_batched(host.data(), dev_w1 + pend[j - 1].id, j - i, seed, 1, PRO_BNRELU, side2);
-        } else {
-          ScopedTimer t(p, T_CONV1_WGRAD, pend[i].b, side2);
-          rc2 = launch_wgrad(pend[i].w1, 1, PRO_BNRELU, side2);
-        }
-        if (rc2) return rc2;
-        i = j;
-      }
-    } else {
-      for (const PendingW& q : pend) {
-        { ScopedTimer t(p, T_CONV2_WGRAD, q.b, side); rc2 = launch_wgrad(q.w2, 27, PRO_BNRELU, side); }
-        if (rc2) return rc2;
-      }
-      for (const PendingW& q : pend) {
-        { ScopedTimer t(p, T_CONV1_WGRAD, q.b, side2); rc2 = launch_wgrad(q.w1, 1, PRO_BNRELU, side2); }
-        if (rc2) return rc2;
-      }
+      j = i;
     }
-    pend.clear();
     return 0;
   };
   auto sptr = [&](int b, int off) { return statptr(ws, p.o_s_x[b], p.ctot_b[b], off, p.nrep_b[b]); };
@@ -773,10 +713,6 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       a.pf_ptr = params + lo.c1; a.pf_bytes = (unsigned)(sizeof(float) * p.mid * lo.cin);
       { ScopedTimer t(p, T_CONV2_DGRAD, b, stream); rc = launch_fprop(a, 27, PRO_GRAD, EPI_MASK_STORE, stream); }
       if (rc) return rc;
-      WgradArgs w2, w1;
-      layer_wgrad_args(p, params, run, ws, b, l, layer_id, seed, w2, w1);
-      w2.trace = (p.trace_base && p.trace_seq < p.trace_slots) ? p.trace_base + (size_t)(p.trace_seq++) * 64 * 16 : nullptr;   // developer aid
-      w1.trace = (p.trace_base && p.trace_seq < p.trace_slots) ? p.trace_base + (size_t)(p.trace_seq++) * 64 * 16 : nullptr;
       // BN-backward of T1 (single consumer norm2): S1 = dbeta2, S2 = dgamma2, scaled by gamma2
       BnBwd g1;
       g1.st = statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]);
@@ -803,21 +739,8 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       else if (l > 0) { d.pf_ptr = fptr(ws, p.o_pk_c2b[b][l - 1]); d.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27); }
       { ScopedTimer t(p, T_CONV1_DGRAD, b, stream); rc = launch_fprop(d, 1, PRO_GRAD, EPI_MASK_ACCUM, stream); }
       if (rc) return rc;
-      // both weight gradients of this layer can run from here on (its G slice was final before conv2 dgrad, dZ2 and
-      // dgamma2/dbeta2 since conv2 dgrad): queue them for the side streams
-      PendingW pw;
-      pw.w2 = w2; pw.w1 = w1; pw.b = b; pw.id = layer_id;
-      pend.push_back(pw);
-      if (l == 0 && (rc = flush())) return rc;
     }
-    if (two) {
-      // Every gradient of this block (its layers, and the transition / norm5 that consumed it) is final once the side streams
-      // drain: reduce its slabs there (HBM-bound) while the chain moves on to the next block / the stem (MFMA-bound).
-      if ((rc = order(stream, side))) return rc;
-      if (side2 != side && (rc = order(side2, side))) return rc;
-      if ((rc = launch_finalize(reinterpret_cast<const GradJob*>(ws + p.o_jobs_grad) + p.gj_begin[b], p.gj_begin[b + 1] - p.gj_begin[b],
-                                p.gj_max[b], grad_params, accumulate, side))) return rc;
-    }
+    if ((rc = block_wgrads(b, layer_id))) return rc;     // layer_id: the block's first layer
     if (b > 0) {
       const int pb = b - 1;
       const TransOff& t = p.trans[pb];
@@ -832,7 +755,7 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       w.gr = concat_grad(b, 0);
       w.x = fptr(ws, p.o_ap[pb]); w.x_ns = (long)t.cin * p.Vb[b]; w.x_coff = 0;
       w.slab = fptr(ws, p.o_sl_tr[pb]); w.slab_stride = (long)t.cout * t.cin; w.nsplit = p.ns_tr[pb];
-      if ((rc = launch_wgrad(w, 1, PRO_NONE, stream))) return rc;
+      if ((rc = launch_wgrad1(w, PRO_NONE, stream))) return rc;
       // transition conv data gradient -> gradient wrt the pooled activations
       FpropArgs d;
       memset(&d, 0, sizeof(d));
@@ -883,14 +806,8 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
       if (rc) return rc;
     }
   }
-  if ((rc = order(side, stream))) return rc;                // join: every weight-gradient slab is written / reduced
-  if (side2 != side && (rc = order(side2, stream))) return rc;
   const long stem_count = (long)c.init_features * c.in_channels * 343;
   const GradJob* jobs = reinterpret_cast<const GradJob*>(ws + p.o_jobs_grad);
-  if (two) {                                                // the blocks' jobs were reduced on the side stream as they became final
-    if (lo > 0) return 0;
-    return launch_finalize(jobs, 3, stem_count, grad_params, accumulate, stream);
-  }
   // one launch for every job of this call: blocks [lo, hi] (their layers + the transition / norm5 behind them), + the stem when lo == 0
   const int j0 = lo == 0 ? 0 : p.gj_begin[lo], j1 = p.gj_begin[hi + 1];
   long jmax = lo == 0 ? stem_count : 0;

@@ -73,17 +73,12 @@ struct Plan {
   int n_run_jobs = 0, n_pack_jobs = 0, n_grad_jobs = 0; long max_pack = 0, max_grad = 0;
   int gj_begin[MAX_BLOCKS + 1] = {0};   // gradient jobs of block b: [gj_begin[b], gj_begin[b+1])  (jobs 0..2: the stem)
   long gj_max[MAX_BLOCKS] = {0};        // largest job of the block
-  // backward runs the weight-gradient kernels on a second stream beside the data-gradient chain (host objects only)
-  hipStream_t side = nullptr, side2 = nullptr; bool side_tried = false;   // conv2 / conv1 weight-gradient streams
-  std::vector<hipEvent_t> sync_ev; size_t sync_used = 0;
   // optional live timing of one kernel class with HIP events (bench.py roofline leg)
   unsigned timer_mask = 0; int timer_block = -1;   // bit k: class k of TimerKind is timed; block < 0: every block
   std::vector<hipEvent_t> timer_ev;                // start/stop pairs recorded since the last read
   std::vector<int> timer_tag;                      // class of each pair
   size_t timer_used = 0;
   double timer_ms[16 * MAX_BLOCKS] = {0}; long timer_count[16 * MAX_BLOCKS] = {0};   // [class][block]
-  bool single_stream = false;                      // option "single_stream": backward on the caller's stream only (overrides side_streams)
-  int side_streams = 0;                            // option "side_streams": 0 (default), 1 or 2 streams for the weight-gradient kernels
   long params_version = 0, packed_version = 0; const float* packed_params = nullptr; const char* packed_ws = nullptr;   // option "params_version"
   long pack_launches = 0;
   long long* nbt = nullptr; int nbt_count = 0;     // mmnn_densenet_set_batch_counters

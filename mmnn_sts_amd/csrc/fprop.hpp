@@ -388,15 +388,12 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
     }
   };
 
-  // ---- output positions of this lane, and (MASK_STORE) the epilogue's operand: the pre-activation tensor `ex`, whole tile.  In the
-  // single-slice fast path its loads CAN be issued before the MFMAs of the last chunk (XPRE below): every block of a launch
-  // reaches its epilogue at the same time, and the chip-wide burst of these reads is 40k of a block's 290k cycles in block 1's
-  // data gradient (phase trace r02), matrix pipe idle. ----
+  // ---- output positions of this lane, and (MASK_STORE) the epilogue's operand: the pre-activation tensor `ex`, whole tile, loaded
+  // in the epilogue.  (Loading it before the last chunk's MFMAs measured slower: its registers stay live across the chunk) ----
   float* outn = a.out + (long)n * a.out_ns + (long)a.out_coff * V;
   const float* exn = (EPI == EPI_MASK_STORE || EPI == EPI_MASK_ACCUM) ? a.ex + (long)n * a.ex_ns + (long)a.ex_coff * V : nullptr;
   constexpr bool ALL_ROWS = (EPI == EPI_MASK_STORE);
   float xall[ALL_ROWS ? MT : 1][ALL_ROWS ? 16 : 1][NT];
-  bool xall_loaded = false;
   auto load_xall = [&]() {
     if (ALL_ROWS) {
       int vox[NT];      // (recomputed in the epilogue: kept live across the K loop these cost the small-tile kernels their last registers)
@@ -427,13 +424,7 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
           }
         }
     }
-    xall_loaded = true;
   };
-  // r02 RESULT: measured SLOWER on the one kernel it targets (block 1's conv2 data gradient 145 -> 167 us: the 64 loads live
-  // across the last chunk push the kernel from 156 to 256 registers), so it is switched off; the smaller tiles have no registers
-  // to spare either.  Kept as a compile-time switch for a version that holds the operand in LDS instead.
-  constexpr bool XPRE = false && ALL_ROWS && TAPS == 27 && TW > 16 && MT * NT > 1 && !SPEC;
-  const bool xall_early = XPRE && gridDim.z == 1 && kg == 0 && !loader;     // wave-uniform
 
   if (vecx && vecw && (long)KC * V < (1l << 30)) {
     // ===== fast path: 16-byte staging through registers, software-pipelined.  The global loads of chunk k+1 are issued
@@ -641,7 +632,6 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
         __syncthreads();
         if (c0 == c_begin) stamp(9);
         if (c0 + KC < c_end) load_chunk(c0 + KC, stA);
-        else if (XPRE && xall_early) load_xall();
         mfma_chunk();
         __syncthreads();
       }
@@ -1218,7 +1208,7 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
       }
     }
   } else {
-  if (ALL_ROWS && !(XPRE && xall_loaded)) load_xall();
+  if (ALL_ROWS) load_xall();
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     float s0[16], s1[16];

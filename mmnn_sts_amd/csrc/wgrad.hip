@@ -55,7 +55,6 @@ int wgrad_pick_splits(int taps, int N, int D, int H, int W, int M, int Cin, int 
 int wgrad1_channel_width(int Cin, long V) { return 32 * wg1_wc(Cin, V); }
 
 // kernel translation units
-int wgrad3_launch(const WgradArgs& a, int pro_x, hipStream_t s);
 int wgrad3_launch_batched(const WgradArgs* host, const WgradArgs* dev, int count, uint64_t seed, hipStream_t stream);
 int wgrad1_launch(const WgradArgs& a, int pro_x, int wc, hipStream_t s);
 int wgrad1_launch_batched(const WgradArgs* host, const WgradArgs* dev, int count, uint64_t seed, int wc, hipStream_t stream);
@@ -81,17 +80,14 @@ int launch_wgrad_batched(const WgradArgs* host, const WgradArgs* dev, int count,
   return wgrad1_launch_batched(host, dev, count, seed, wg1_wc(f.Cin, (long)f.D * f.H * f.W), stream);
 }
 
-int launch_wgrad(const WgradArgs& a, int taps, int pro_x, hipStream_t stream) {
+int launch_wgrad1(const WgradArgs& a, int pro_x, hipStream_t stream) {
   MMNN_REQUIRE(a.N > 0 && a.D > 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.M > 0, "wgrad: non-positive extent");
   MMNN_REQUIRE((long)a.D * a.H * a.W < (1l << 30), "wgrad: volume too large for 32-bit voxel indices");
-  MMNN_REQUIRE(taps != 27 || (long)33 * a.D * a.H * a.W < (1l << 31), "wgrad: volume too large for 32-bit element offsets of a 32-channel group");
   MMNN_REQUIRE(a.g0 && a.g1 && a.x && a.slab, "wgrad: null operand");
   MMNN_REQUIRE(a.nsplit >= 1 && a.nsplit <= 65535, "wgrad: bad split count %d", a.nsplit);
-  MMNN_REQUIRE(taps == 1 || taps == 27, "wgrad: taps must be 1 or 27");
-  MMNN_REQUIRE(taps != 27 || a.M <= 32, "wgrad: the 3x3x3 kernel handles at most 32 output channels (growth rate), got %d", a.M);
-  MMNN_REQUIRE(a.slab_stride >= (long)taps * a.M * a.Cin, "wgrad: slab stride too small");
+  MMNN_REQUIRE(a.slab_stride >= (long)a.M * a.Cin, "wgrad: slab stride too small");
   MMNN_REQUIRE(pro_x == PRO_BNRELU || pro_x == PRO_NONE, "wgrad: unsupported input prologue %d", pro_x);
-  return taps == 27 ? wgrad3_launch(a, pro_x, stream) : wgrad1_launch(a, pro_x, wg1_wc(a.Cin, (long)a.D * a.H * a.W), stream);
+  return wgrad1_launch(a, pro_x, wg1_wc(a.Cin, (long)a.D * a.H * a.W), stream);
 }
 
 }  // namespace mmnn

@@ -34,7 +34,7 @@ struct WgradArgs {
   unsigned long long* trace;   // developer builds (MMNN_PHASE_TRACE): per-block phase cycle sums; null otherwise
 };
 
-int launch_wgrad(const WgradArgs& a, int taps, int pro_x, hipStream_t stream);
+int launch_wgrad1(const WgradArgs& a, int pro_x, hipStream_t stream);   // one 1x1x1 weight gradient (any M; PRO_BNRELU or PRO_NONE)
 // `count` layers of identical extent (N, D, H, W), M and prologue in one launch.  host: the arguments (validated here);
 // dev_table: the same `count` entries in device memory (already uploaded); seed: this step's dropout seed (overrides drop.seed).
 // For taps == 1 every entry must select the same channel-group width (wgrad1_channel_width(Cin, V)).
@@ -440,14 +440,10 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
   }
 }
 
-template <int PRO_X, int TD, int TH, int TW>
-__global__ void __launch_bounds__(512) wgrad3_kernel(const WgradArgs a) {
-  wgrad3_body<PRO_X, TD, TH, TW>(a, blockIdx.x, blockIdx.y);
-}
-
 // Several layers in ONE launch (blockIdx.z = layer): the late dense blocks' weight gradients are a few dozen blocks per layer
 // each, far too few for 256 CUs, and independent of one another once the data-gradient chain has passed their layers.  The
-// argument table lives in device memory and is step-invariant; the per-step dropout seed arrives as a kernel argument.
+// argument table lives in device memory and is step-invariant; the per-step dropout seed arrives as a kernel argument.  Every
+// conv2 weight gradient goes through this kernel (a one-layer block is a batch of one).
 template <int PRO_X, int TD, int TH, int TW>
 __global__ void __launch_bounds__(512) wgrad3_batched_kernel(const WgradArgs* __restrict__ table, const uint64_t seed, const int nsplit,
                                                              const int cgroups, const int ngroups) {
@@ -725,27 +721,9 @@ __global__ void __launch_bounds__(WC * 64) wgrad1_kernel(const WgradArgs a) {
 
 // several layers in one launch (blockIdx.z = layer; every layer of a batch has M <= 128): see wgrad3_batched_kernel
 template <int PRO_X, int WC>
-__global__ void __launch_bounds__(WC * 64) wgrad1_batched_kernel(const WgradArgs* __restrict__ table, const uint64_t seed, const int count,
-                                                                 const int nsplit, const int members) {
-  int z, split, cg;
-  if (members > 0) {
-    // XCD-aware order (1-D grid, see wgrad3_batched_kernel): all (layer, channel group) blocks of ONE voxel split go to one XCD back to
-    // back.  They read the same voxel range: the channel groups of a layer share its 128-row dOut operand, and the layers share the
-    // concat buffer's channels -- one HBM read per XCD instead of one per block.
-    const int lin = blockIdx.x, x = lin & 7, j = lin >> 3;
-    split = x + 8 * (j / members);
-    if (split >= nsplit) return;
-    int m = j % members;
-    z = 0; cg = 0;
-    for (int i = 0; i < count; ++i) {                  // member m -> (layer, channel group): a few dozen layers at most
-      const int n = (table[i].Cin + 32 * WC - 1) / (32 * WC);
-      if (m < n) { z = i; cg = m; break; }
-      m -= n;
-    }
-  } else {
-    z = blockIdx.z; split = blockIdx.x; cg = blockIdx.y;
-  }
-  WgradArgs a = table[z];
+__global__ void __launch_bounds__(WC * 64) wgrad1_batched_kernel(const WgradArgs* __restrict__ table, const uint64_t seed) {
+  const int split = blockIdx.x, cg = blockIdx.y;
+  WgradArgs a = table[blockIdx.z];
   if (split >= a.nsplit || cg * (32 * WC) >= a.Cin) return;
   a.drop.seed = seed;
   wgrad1_body<PRO_X, WC>(a, split, cg * (32 * WC), 0);

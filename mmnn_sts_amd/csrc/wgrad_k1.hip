@@ -1,6 +1,4 @@
 // 1x1x1 weight-gradient kernels: instantiations + launches (see wgrad_k3.hip).
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "wgrad.hpp"
@@ -34,23 +32,10 @@ static int launch1_batched(const WgradArgs* host, const WgradArgs* dev, int coun
     MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     conf = true;
   }
-  int gx = 1, gy = 1, members = 0;
-  bool uniform = true;
-  for (int i = 0; i < count; ++i) {
-    gx = std::max(gx, host[i].nsplit); gy = std::max(gy, cdiv(host[i].Cin, 32 * WC));
-    members += cdiv(host[i].Cin, 32 * WC);
-    uniform = uniform && host[i].nsplit == host[0].nsplit;
-  }
-  // r03 A/B (profiles/r03_ab_experiments.txt): the XCD-aware order measured 2-3 % SLOWER here (block 1: 285 vs 278 us) -- unlike the 3x3x3
-  // kernel the blocks of one split do not stage the same tiles in lockstep (their channel counts differ), so it stays off: MMNN_WG1_XCD=1
-  static const bool remap = [] { const char* e = getenv("MMNN_WG1_XCD"); return e && e[0] == '1'; }();
-  if (uniform && members > 1 && remap) {
-    const long blocks = 8l * members * ((gx + 7) / 8);
-    MMNN_REQUIRE(blocks < (1l << 31), "wgrad batch: grid out of range");
-    MMNN_LAUNCH(kern, dim3((unsigned)blocks), dim3(C::NTHREADS), smem, stream, dev, seed, count, gx, members);
-  } else {
-    MMNN_LAUNCH(kern, dim3(gx, gy, count), dim3(C::NTHREADS), smem, stream, dev, seed, count, gx, 0);
-  }
+  int gx = 1, gy = 1;
+  for (int i = 0; i < count; ++i) { gx = std::max(gx, host[i].nsplit); gy = std::max(gy, cdiv(host[i].Cin, 32 * WC)); }
+  // (an XCD-aware block order, as in the 3x3x3 kernel, measured 2-3 % slower here: DESIGN §4)
+  MMNN_LAUNCH(kern, dim3(gx, gy, count), dim3(C::NTHREADS), smem, stream, dev, seed);
   MMNN_HIP(hipGetLastError());
   return 0;
 }

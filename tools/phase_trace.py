@@ -17,7 +17,6 @@ x = torch.randn(n, 2, s, s, s, device="cuda")
 cot = torch.randn(nb.out_shape, device="cuda")
 L = _lib.lib()
 _lib.check(L.mmnn_densenet_set_option(nb.plan, b"single_stream", 1), "opt")
-os.environ.setdefault("MMNN_NO_WGRAD_BATCH", "1")        # per-layer weight-gradient launches carry the trace pointer
 for _ in range(3):
     nb.forward(flat, run, x, True, seed=1); nb.backward(flat, x, cot, seed=1)
 torch.cuda.synchronize()
