@@ -239,6 +239,33 @@ int mmnn_sgd_step_multi(const mmnn_tensor_ref* refs, int32_t n, float* momentum_
 /* scatter == 0: flat[flat_offset + i] = grad[i] (gather the small gradients into ONE all-reduce bucket); scatter != 0: the way back */
 int mmnn_multi_copy(const mmnn_tensor_ref* refs, int32_t n, float* flat, int32_t scatter, void* stream);
 
+/* ---- learning-rate range test (upstream utils/find_lr.py: torch-lr-finder's LRFinder.range_test with nn.CrossEntropyLoss) --------
+ * nn.CrossEntropyLoss(ignore_index, reduction) over logits [n][c] (1 <= c <= 1024).  target_kind 0: int64 class indices [n] (rows equal
+ * to ignore_index are left out; the mean divides by the rows kept, NaN if none); 1: fp32 class probabilities [n][c] (the mean divides
+ * by n).  An index outside [0, c) gives a NaN row (loss and gradient) instead of a fault.  reduction 0 none (loss [n]), 1 sum, 2 mean
+ * (loss [1]).  dlogits_saved [n][c] (may be NULL): softmax * sum(y) - y, divided by the mean's divisor.  Deterministic: one block,
+ * rows reduced in a fixed order.  Backward: dlogits = dlogits_saved * dloss, dloss a device pointer to 1 float (sum / mean) or n
+ * (none). */
+int mmnn_cross_entropy(int32_t n, int32_t c, const float* logits, const void* target, int32_t target_kind, int64_t ignore_index,
+                       int32_t reduction, float* loss, float* dlogits_saved, void* stream);
+int mmnn_cross_entropy_backward(int32_t n, int32_t c, int32_t reduction, const float* dlogits_saved, const float* dloss, float* dlogits,
+                                void* stream);
+/* The sweep's state (mmnn_lr_range_state_bytes(num_iter) bytes, 8-byte aligned): float total @0, int32 live @4, stop_iter @8 (-1: no
+ * stop), iters_done @12, num_iter @16; double best @24, prev @32, hist[num_iter] @40.  accumulate: total = (first ? 0 : total) +
+ * loss[0] / steps_or_1 in fp32.  update(iter): raw = (double)total; iter 0: best = s = raw; else s = smooth_f * raw +
+ * one_minus_smooth_f * prev (raw when smooth_f == 0), best = min(best, s); hist[iter] = s; s > diverge_th * best stops the sweep
+ * (live = 0, stop_iter = iter).  Once stopped, accumulate and update change nothing. */
+int64_t mmnn_lr_range_state_bytes(int32_t num_iter);
+int mmnn_lr_range_init(void* state, int32_t num_iter, void* stream);
+int mmnn_lr_range_accumulate(void* state, const float* loss, float steps_or_1, int32_t first, void* stream);
+int mmnn_lr_range_update(void* state, int32_t iter, double smooth_f, double one_minus_smooth_f, double diverge_th, void* stream);
+/* mmnn_sgd_step / mmnn_sgd_step_multi with the learning rate read from device memory (*lr) and a device switch: *live == 0 leaves
+ * params and momentum untouched.  Same per-element code, so a given lr gives bit-identical results. */
+int mmnn_sgd_step_dev(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr, const int32_t* live, float momentum,
+                      float weight_decay, int32_t nesterov, int32_t first_step, void* stream);
+int mmnn_sgd_step_multi_dev(const mmnn_tensor_ref* refs, int32_t n, float* momentum_buf, const float* lr, const int32_t* live, float momentum,
+                            float weight_decay, int32_t nesterov, void* stream);
+
 /* ---- Grad-CAM of the fusion model on the last Conv3d of the image backbone: MultiModalGradCAM.forward after its model forward
  * (utils/utils.py:293-344), batch size 1 (:334).  Per class, in order: d out[0,cls] / d act in closed form (fused head -> feature_layer ->
  * average pool -> ReLU mask -> eval-mode norm5 scale, restricted to the captured layer = the LAST `growth` channels of the concat),

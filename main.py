@@ -402,12 +402,46 @@ def inference_survival(model, ds, args, device):
     return p
 
 
+class SyntheticImagePatients(SyntheticPatients):
+    """Synthetic image patients addressed by uid (0 .. n-1) with three event flags each: the shape of the image classification
+    dataset upstream's find_lr trains its 3-class DenseNet121 on (utils/find_lr.py:25,96-100)."""
+
+    def __init__(self, n, in_channels, size, seed, classes=3):
+        super().__init__(n, in_channels, size, 0, False, True, seed)
+        g = torch.Generator().manual_seed(seed + 1)
+        self.events = (torch.rand((n, classes), generator=g) < 0.6).long()
+        self.uids = list(range(n))
+
+
+def run_lr_finder(a, cfg, seed):
+    """`--lr_finder` (upstream main.py:1009-1010 -> utils/find_lr.py): the range test of a fresh 3-class MONAI-schema DenseNet121 on
+    synthetic patients, then lr_finder.csv (lr,loss per recorded iteration), lr_finder.png and the suggested lr."""
+    from mmnn_sts_amd.utils.find_lr import find_lr
+    if not torch.cuda.is_available():
+        raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
+    torch.cuda.set_device(0)
+    inch = int(cfg["ImageModel"]["in_channels"])
+    ds = SyntheticImagePatients(max(2, a.synthetic_patients), inch, a.synthetic_size, 1000)
+    a.seed, a.in_channels = seed, inch
+    os.makedirs(a.output_path, exist_ok=True)
+    finder, suggestion = find_lr(a, ds)
+    with open(os.path.join(a.output_path, "lr_finder.csv"), "w") as f:
+        f.write("lr,loss\n")
+        for lr, loss in zip(finder.history["lr"], finder.history["loss"]):
+            f.write(f"{lr!r},{loss!r}\n")
+    if suggestion is not None:
+        logger.info("Suggested LR: %.2E", suggestion)
+    else:
+        logger.info("Suggested LR: none (too few points)")
+    return finder
+
+
 def build_arg_parser():
     ap = argparse.ArgumentParser()
     for flag, h in (("preop", "clinical features available pre-operation"), ("postop", "pre + post operation clinical features"),
                     ("radiomics", "radiomic features (not implemented upstream either)"), ("images", "image data"),
                     ("classification", "binary classification"), ("survival", "time-to-event model"), ("segmentation", "unsupported"),
-                    ("lr_finder", "unsupported tooling"), ("no_gradcam", "disable Grad-CAM for inference"), ("inference", "inference"),
+                    ("lr_finder", "learning-rate range test (with --images --classification): lr_finder.csv / .png, suggested lr"), ("no_gradcam", "disable Grad-CAM for inference"), ("inference", "inference"),
                     ("split", "create a new dataset split"), ("blend", "gradient blending"), ("bootstrap", "bootstrap evaluation (with --inference --survival)")):
         ap.add_argument(f"--{flag}", action="store_true", help=h)
     for twin in ("use_images", "use_preop", "use_postop", "classification_task", "inference_task", "survival_task", "use_blend"):
@@ -441,8 +475,13 @@ def main(argv=None):
     a.blend = a.blend or str_to_bool(a.use_blend)
     assert not all([a.classification, a.survival, a.segmentation]), 'Can only specify one of --classification , --survival , or --segmentation'
     assert any([a.classification, a.survival, a.segmentation]), 'Must specify one of --classification , --survival , or --segmentation'
-    if a.segmentation or a.lr_finder or a.radiomics:
-        raise SystemExit("--segmentation / --lr_finder / --radiomics are outside the MI355X fusion path (SURVEY 2)")
+    if a.segmentation or a.radiomics:
+        raise SystemExit("--segmentation / --radiomics are outside the MI355X fusion path (SURVEY 2)")
+    if a.lr_finder and not (a.images and a.classification and not (a.preop or a.postop)):
+        raise SystemExit("--lr_finder runs upstream's find_lr on an image classification dataset: it needs --images --classification "
+                         "and no clinical flags (--preop / --postop)")
+    if a.lr_finder and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--lr_finder is single-process (as upstream's find_lr); run it without torch.distributed.run")
     if a.bootstrap and not (a.inference and a.survival):
         raise SystemExit("--bootstrap resamples the evaluation of `--inference --survival` (main.py:767-887); it has no meaning for training runs")
     if a.transforms and not a.images:
@@ -459,6 +498,8 @@ def main(argv=None):
     a.momentum, a.weight_decay = float(hp.get("momentum", 0.9)), float(hp.get("weight_decay", 1e-4))
     a.class_frequencies = list(hp.get("class_frequencies", [0.4] * NUM_CLASSES))     # CLASS_FREQUENCIES is undefined upstream (Q1)
     torch.manual_seed(int(hp.get("seed", 42)))
+    if a.lr_finder:
+        return run_lr_finder(a, cfg, int(hp.get("seed", 42)))
     a.train_tf = a.val_tf = None
     if a.transforms:
         from mmnn_sts_amd.transforms import train_transforms, val_transforms

@@ -35,6 +35,10 @@ class MlpDesc(Structure):
 
 
 MULTI_MAX = 64
+CE_TARGET_INDEX, CE_TARGET_PROB = 0, 1
+CE_REDUCTIONS = {"none": 0, "sum": 1, "mean": 2}
+# byte offsets inside the lr range-test state (include/mmnn_sts.h, mmnn_lr_range_*)
+LRS_LIVE, LRS_STOP_ITER, LRS_ITERS_DONE, LRS_BEST, LRS_HIST = 4, 8, 12, 24, 40
 DT_F64, DT_F32, DT_I64, DT_I32, DT_U8 = 0, 1, 2, 3, 4
 
 
@@ -140,6 +144,13 @@ def lib():
         "mmnn_sgd_step": [V, V, V, c_int64, F, F, F, I, I, V],
         "mmnn_sgd_step_multi": [POINTER(TensorRef), I, V, F, F, F, I, V],
         "mmnn_multi_copy": [POINTER(TensorRef), I, V, I, V],
+        "mmnn_sgd_step_dev": [V, V, V, c_int64, V, V, F, F, I, I, V],
+        "mmnn_sgd_step_multi_dev": [POINTER(TensorRef), I, V, V, V, F, F, I, V],
+        "mmnn_cross_entropy": [I, I, V, V, I, c_int64, I, V, V, V],
+        "mmnn_cross_entropy_backward": [I, I, I, V, V, V, V],
+        "mmnn_lr_range_init": [V, I, V],
+        "mmnn_lr_range_accumulate": [V, V, F, I, V],
+        "mmnn_lr_range_update": [V, I, ctypes.c_double, ctypes.c_double, ctypes.c_double, V],
         "mmnn_gradcam": [POINTER(GradcamDesc), V, V, V, V, V, V, V, V, V, V, V],
         "mmnn_gradcam_unimodal": [POINTER(GradcamUnimodalDesc), POINTER(GradcamHead), V, V, V, V, V, V, c_int64, V],
         "mmnn_bce_logits": [c_int64, I, V, V, V, V, V, V],
@@ -170,6 +181,8 @@ def lib():
     L.mmnn_transform_workspace_bytes.argtypes = [POINTER(TransformDesc)]
     L.mmnn_transform_volumes.restype = c_int32
     L.mmnn_transform_volumes.argtypes = [POINTER(TransformDesc), POINTER(TransformParams), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    L.mmnn_lr_range_state_bytes.restype = c_int64
+    L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64
     L.mmnn_mlp_saved_floats.argtypes = [POINTER(MlpDesc)]
     _lib = L

@@ -352,31 +352,48 @@ int launch_finalize(const GradJob* jobs_dev, int njobs, long max_count, float* g
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) sgd_kernel(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first) {
+// one element of the update: d = g + wd*p; b = first ? d : mom*b + d; p -= lr * (nesterov ? d + mom*b : b).  Shared by the host-lr
+// kernels and the device-lr ones (sweeps whose lr lives in a device table), so a given lr gives bit-identical results.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& b, float lr, float mom, float wd, int nesterov, bool first) {
+  float d = fmaf(wd, p, g);
+  const float m = first ? d : fmaf(mom, b, d);
+  b = m;
+  d = nesterov ? fmaf(mom, m, d) : m;
+  p = fmaf(-lr, d, p);
+}
+
+__device__ __forceinline__ void sgd_body(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first) {
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
     if (i + 3 < n && ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0)) {
       f32x4 pv = *reinterpret_cast<f32x4*>(p + i), gv = *reinterpret_cast<const f32x4*>(g + i);
       f32x4 bv = first ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<f32x4*>(buf + i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float d = fmaf(wd, pv[e], gv[e]);
-        const float b = first ? d : fmaf(mom, bv[e], d);
-        bv[e] = b;
-        d = nesterov ? fmaf(mom, b, d) : b;
-        pv[e] = fmaf(-lr, d, pv[e]);
+        float pe = pv[e], be = bv[e];
+        sgd_elem(pe, gv[e], be, lr, mom, wd, nesterov, first);
+        pv[e] = pe; bv[e] = be;
       }
       *reinterpret_cast<f32x4*>(p + i) = pv;
       *reinterpret_cast<f32x4*>(buf + i) = bv;
     } else {
       for (long j = i; j < n && j < i + 4; ++j) {
-        float d = fmaf(wd, p[j], g[j]);
-        const float b = first ? d : fmaf(mom, buf[j], d);
-        buf[j] = b;
-        d = nesterov ? fmaf(mom, b, d) : b;
-        p[j] = fmaf(-lr, d, p[j]);
+        float pe = p[j], be = first ? 0.f : buf[j];
+        sgd_elem(pe, g[j], be, lr, mom, wd, nesterov, first);
+        p[j] = pe; buf[j] = be;
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(256) sgd_kernel(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first) {
+  sgd_body(p, g, buf, n, lr, mom, wd, nesterov, first);
+}
+
+// lr read from device memory; *live == 0 leaves params and momentum untouched (lr = 0 would not: 0 * inf = NaN)
+__global__ void __launch_bounds__(256) sgd_dev_kernel(float* p, const float* g, float* buf, long n, const float* lr, const int* live, float mom,
+                                                      float wd, int nesterov, int first) {
+  if (*live == 0) return;
+  sgd_body(p, g, buf, n, *lr, mom, wd, nesterov, first);
 }
 
 int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay, int nesterov, int first_step,
@@ -389,6 +406,16 @@ int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom
   return 0;
 }
 
+int launch_sgd_dev(float* p, const float* g, float* buf, long n, const float* lr, const int* live, float momentum, float weight_decay,
+                   int nesterov, int first_step, hipStream_t stream) {
+  MMNN_REQUIRE(p && g && buf && n > 0 && lr && live, "sgd_dev: bad arguments");
+  int gx = cdiv(n, 1024);
+  if (gx > 2048) gx = 2048;
+  MMNN_LAUNCH(sgd_dev_kernel, dim3(gx), dim3(256), 0, stream, p, g, buf, n, lr, live, momentum, weight_decay, nesterov, first_step);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- the same update over a LIST of small tensors (the ~30 parameter tensors outside the backbone) in one launch: the table travels
 // as a kernel argument (no upload), blockIdx.y = tensor -------------------------------------------------------------------------------
 struct MultiTable {
@@ -396,32 +423,60 @@ struct MultiTable {
   float* p[MMNN_MULTI_MAX]; const float* g[MMNN_MULTI_MAX]; long count[MMNN_MULTI_MAX]; long off[MMNN_MULTI_MAX]; int first[MMNN_MULTI_MAX];
 };
 
-__global__ void __launch_bounds__(256) sgd_multi_kernel(const MultiTable t, float* buf, float lr, float mom, float wd, int nesterov) {
+__device__ __forceinline__ void sgd_multi_body(const MultiTable& t, float* buf, float lr, float mom, float wd, int nesterov) {
   const int k = blockIdx.y;
   float* p = t.p[k]; const float* g = t.g[k]; float* b = buf + t.off[k];
   const bool first = t.first[k] != 0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.count[k]; i += (long)gridDim.x * 256) {
-    float d = fmaf(wd, p[i], g[i]);
-    const float m = first ? d : fmaf(mom, b[i], d);
-    b[i] = m;
-    d = nesterov ? fmaf(mom, m, d) : m;
-    p[i] = fmaf(-lr, d, p[i]);
+    float pe = p[i], be = first ? 0.f : b[i];
+    sgd_elem(pe, g[i], be, lr, mom, wd, nesterov, first);
+    b[i] = be; p[i] = pe;
   }
 }
 
-int launch_sgd_multi(const mmnn_tensor_ref* refs, int n, float* buf, float lr, float momentum, float weight_decay, int nesterov, hipStream_t stream) {
-  MMNN_REQUIRE(refs && buf && n >= 1 && n <= MMNN_MULTI_MAX, "sgd_multi: 1..%d tensors per call, got %d", MMNN_MULTI_MAX, n);
-  MultiTable t;
+__global__ void __launch_bounds__(256) sgd_multi_kernel(const MultiTable t, float* buf, float lr, float mom, float wd, int nesterov) {
+  sgd_multi_body(t, buf, lr, mom, wd, nesterov);
+}
+
+__global__ void __launch_bounds__(256) sgd_multi_dev_kernel(const MultiTable t, float* buf, const float* lr, const int* live, float mom, float wd,
+                                                            int nesterov) {
+  if (*live == 0) return;
+  sgd_multi_body(t, buf, *lr, mom, wd, nesterov);
+}
+
+static int fill_multi_table(const mmnn_tensor_ref* refs, int n, MultiTable& t, long& most) {
+  MMNN_REQUIRE(refs && n >= 1 && n <= MMNN_MULTI_MAX, "sgd_multi: 1..%d tensors per call, got %d", MMNN_MULTI_MAX, n);
   t.n = n;
-  long most = 0;
+  most = 0;
   for (int i = 0; i < n; ++i) {
     MMNN_REQUIRE(refs[i].param && refs[i].grad && refs[i].count > 0 && refs[i].flat_offset >= 0, "sgd_multi: bad tensor %d", i);
     t.p[i] = refs[i].param; t.g[i] = refs[i].grad; t.count[i] = refs[i].count; t.off[i] = refs[i].flat_offset; t.first[i] = refs[i].first_step;
     most = std::max(most, (long)refs[i].count);
   }
+  return 0;
+}
+
+int launch_sgd_multi(const mmnn_tensor_ref* refs, int n, float* buf, float lr, float momentum, float weight_decay, int nesterov, hipStream_t stream) {
+  MMNN_REQUIRE(buf, "sgd_multi: null momentum buffer");
+  MultiTable t;
+  long most;
+  if (int st = fill_multi_table(refs, n, t, most)) return st;
   int gx = cdiv(most, 256);
   if (gx > 64) gx = 64;
   MMNN_LAUNCH(sgd_multi_kernel, dim3(gx, n), dim3(256), 0, stream, t, buf, lr, momentum, weight_decay, nesterov);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_sgd_multi_dev(const mmnn_tensor_ref* refs, int n, float* buf, const float* lr, const int* live, float momentum, float weight_decay,
+                         int nesterov, hipStream_t stream) {
+  MMNN_REQUIRE(buf && lr && live, "sgd_multi_dev: null momentum buffer, lr or live flag");
+  MultiTable t;
+  long most;
+  if (int st = fill_multi_table(refs, n, t, most)) return st;
+  int gx = cdiv(most, 256);
+  if (gx > 64) gx = 64;
+  MMNN_LAUNCH(sgd_multi_dev_kernel, dim3(gx, n), dim3(256), 0, stream, t, buf, lr, live, momentum, weight_decay, nesterov);
   MMNN_HIP(hipGetLastError());
   return 0;
 }

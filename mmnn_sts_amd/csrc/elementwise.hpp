@@ -89,6 +89,11 @@ int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom
 
 // the same update / a flat gather-scatter over a list of small tensors, one launch each (table passed as a kernel argument)
 int launch_sgd_multi(const mmnn_tensor_ref* refs, int n, float* buf, float lr, float momentum, float weight_decay, int nesterov, hipStream_t stream);
+// the same two updates with the learning rate read from device memory and a device on/off flag (*live == 0: nothing is written)
+int launch_sgd_dev(float* p, const float* g, float* buf, long n, const float* lr, const int* live, float momentum, float weight_decay,
+                   int nesterov, int first_step, hipStream_t stream);
+int launch_sgd_multi_dev(const mmnn_tensor_ref* refs, int n, float* buf, const float* lr, const int* live, float momentum, float weight_decay,
+                         int nesterov, hipStream_t stream);
 int launch_multi_copy(const mmnn_tensor_ref* refs, int n, float* flat, int scatter, hipStream_t stream);
 
 }  // namespace mmnn

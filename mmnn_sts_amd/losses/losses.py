@@ -40,3 +40,27 @@ class BCEWithLogitsLoss(torch.nn.Module):
             raise ValueError(f"Target size ({target.shape}) must be the same as input size ({input.shape})")
         loss = ops.BceLogits.apply(input, target.to(input.dtype), self.pos_weight)
         return loss if self.reduction == 'none' else (loss.sum() if self.reduction == 'sum' else loss.mean())
+
+
+class CrossEntropyLoss(torch.nn.Module):
+    """`nn.CrossEntropyLoss(ignore_index=..., reduction=...)` as upstream's utils/find_lr.py builds it, on the MI355X: the loss and
+    its gradient come from one HIP kernel (`mmnn_cross_entropy`).  Targets are int64 class indices (N,) or floating class
+    probabilities (N, C).  An index outside [0, C) that is not `ignore_index` gives NaN for its row instead of raising (raising
+    would need a host round trip).  Class weights and label smoothing are not provided."""
+
+    def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None, reduction: str = 'mean',
+                 label_smoothing: float = 0.0):
+        super().__init__()
+        if weight is not None:
+            raise ValueError("CrossEntropyLoss: class weights are not supported by the native kernel")
+        if label_smoothing != 0.0:
+            raise ValueError("CrossEntropyLoss: label smoothing is not supported by the native kernel")
+        if size_average is not None or reduce is not None:
+            raise ValueError("CrossEntropyLoss: the deprecated size_average / reduce arguments are not supported; use reduction")
+        if reduction not in ('none', 'sum', 'mean'):
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+
+    def forward(self, input, target):
+        return ops.CrossEntropy.apply(input, target, self.ignore_index, self.reduction)

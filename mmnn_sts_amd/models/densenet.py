@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from .. import _lib, ops
 
-__all__ = ["DenseNet", "DenseNet121", "TinyDensenet"]
+__all__ = ["DenseNet", "DenseNet121", "TinyDensenet", "MonaiDenseNet", "densenet121"]
 
 
 class _DenseLayer(nn.Module):
@@ -449,3 +449,65 @@ class TinyDensenet(DenseNet):
         super().__init__(init_features=init_features, growth_rate=growth_rate, block_config=block_config, **kwargs)
         if pretrained:
             raise NotImplementedError("Parameter `spatial_dims` is > 2 ; PyTorch Hub provides no pretrained 3-D DenseNet")
+
+
+class _MonaiClassLayers(nn.Sequential):
+    """MONAI's DenseNet head: relu -> AdaptiveAvgPool3d(1) -> flatten -> out: Linear, one fused op (dropout 0)."""
+
+    def __init__(self, in_channels: int, out_channels: int):
+        super().__init__(OrderedDict([
+            ("relu", nn.ReLU(inplace=True)), ("pool", nn.AdaptiveAvgPool3d(1)), ("flatten", nn.Flatten(1)),
+            ("out", nn.Linear(in_channels, out_channels)),
+        ]))
+
+    def forward(self, h: torch.Tensor) -> torch.Tensor:
+        return ops.GapLinear.apply(h, self.out.weight, self.out.bias, 0.0, self.training)
+
+
+class MonaiDenseNet(nn.Module):
+    """`monai.networks.nets.DenseNet` as upstream's utils/find_lr.py builds it (3-D, batch norm, ReLU, no feature layer), in MONAI's
+    state_dict schema: `features.conv0.weight`, `features.denseblock1.denselayer1.layers.norm1.weight`, ..., `features.norm5.*`,
+    `class_layers.out.{weight,bias}` -- the DenseNet backbone keys above with `backbone.` renamed to `features.`."""
+
+    def __init__(self, spatial_dims: int, in_channels: int, out_channels: int, init_features: int = 64, growth_rate: int = 32,
+                 block_config: Sequence[int] = (6, 12, 24, 16), bn_size: int = 4, act: Union[str, tuple] = ("relu", {"inplace": True}),
+                 norm: Union[str, tuple] = "batch", dropout_prob: float = 0.0) -> None:
+        super().__init__()
+        if spatial_dims != 3:
+            raise NotImplementedError("mmnn_sts_amd implements the 3-D DenseNet only (spatial_dims=3)")
+        if (act if isinstance(act, str) else act[0]).lower() != "relu" or (norm if isinstance(norm, str) else norm[0]).lower() != "batch":
+            raise NotImplementedError("mmnn_sts_amd kernels fuse ReLU + batch norm; other act/norm choices are not available")
+        if not (1 <= int(in_channels) <= 4):
+            raise ValueError(f"mmnn_sts_amd: in_channels must be 1..4 (the stem kernel's input tile), got {in_channels}")
+        if not (1 <= int(init_features) <= 64) or not (1 <= int(growth_rate) <= 32):
+            raise ValueError(f"mmnn_sts_amd: init_features <= 64 and growth_rate <= 32 (one MFMA row tile each), got {init_features} / {growth_rate}")
+        if not (1 <= len(block_config) <= 8) or any(int(n) < 1 for n in block_config) or int(bn_size) < 1 or not (0.0 <= float(dropout_prob) < 1.0):
+            raise ValueError(f"mmnn_sts_amd: bad block_config / bn_size / dropout_prob: {block_config} / {bn_size} / {dropout_prob}")
+        self.features = _Backbone(in_channels, init_features, growth_rate, block_config, bn_size, dropout_prob)
+        self.class_layers = _MonaiClassLayers(self.features.out_channels, out_channels)
+        for m in self.modules():      # monai/networks/nets/densenet.py: the same initialisation as the reference DenseNet
+            if isinstance(m, nn.Conv3d):
+                nn.init.kaiming_normal_(m.weight)
+            elif isinstance(m, nn.BatchNorm3d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.Linear):
+                nn.init.constant_(m.bias, 0)
+
+    @property
+    def in_channels(self) -> int:
+        return self.features.cfg["in_channels"]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.class_layers(self.features(x))
+
+
+def densenet121(pretrained: bool = False, progress: bool = True, **kwargs) -> MonaiDenseNet:
+    """`monai.networks.nets.densenet121(spatial_dims=3, in_channels=..., out_channels=...)`: init_features 64, growth 32,
+    block_config (6, 12, 24, 16) unless given."""
+    if pretrained:
+        raise NotImplementedError("Parameter `spatial_dims` is > 2 ; PyTorch Hub provides no pretrained 3-D DenseNet")
+    kwargs.setdefault("init_features", 64)
+    kwargs.setdefault("growth_rate", 32)
+    kwargs.setdefault("block_config", (6, 12, 24, 16))
+    return MonaiDenseNet(**kwargs)

@@ -292,6 +292,50 @@ class BceLogits(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# softmax cross entropy  (nn.CrossEntropyLoss of upstream's utils/find_lr.py)
+# ----------------------------------------------------------------------------------------------------------------------
+class CrossEntropy(torch.autograd.Function):
+    """nn.functional.cross_entropy(logits (N, C), target, ignore_index, reduction) without weights or label smoothing.  `target`:
+    int64 class indices (N,) or floating class probabilities (N, C).  One HIP launch computes the loss and the gradient it saves."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index: int, reduction: str):
+        _need_cuda(logits, target)
+        z = _f32c(logits)
+        if z.dim() != 2:
+            raise ValueError(f"cross_entropy: expected (N, C) logits, got {tuple(z.shape)}")
+        n, c = z.shape
+        if target.is_floating_point():
+            if tuple(target.shape) != (n, c):
+                raise ValueError(f"cross_entropy: probability targets must be {(n, c)}, got {tuple(target.shape)}")
+            t, kind = _f32c(target), _lib.CE_TARGET_PROB
+        else:
+            if tuple(target.shape) != (n,):
+                raise ValueError(f"cross_entropy: index targets must be ({n},), got {tuple(target.shape)}")
+            t, kind = target.to(torch.int64).contiguous(), _lib.CE_TARGET_INDEX
+        red = _lib.CE_REDUCTIONS[reduction]
+        loss = torch.empty((n,) if red == 0 else (), device=z.device, dtype=torch.float32)
+        saved = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        _lib.check(_lib.lib().mmnn_cross_entropy(n, c, z.data_ptr(), t.data_ptr(), kind, int(ignore_index), red, loss.data_ptr(),
+                                                 saved.data_ptr() if saved is not None else None, _stream()), "cross_entropy")
+        ctx.save_for_backward(saved)
+        ctx.red = red
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (saved,) = ctx.saved_tensors
+        if saved is None:
+            return None, None, None, None
+        n, c = saved.shape
+        dl = _f32c(dloss)
+        dz = torch.empty_like(saved)
+        _lib.check(_lib.lib().mmnn_cross_entropy_backward(n, c, ctx.red, saved.data_ptr(), dl.data_ptr(), dz.data_ptr(), _stream()),
+                   "cross_entropy_backward")
+        return dz, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # 3-D ResNet-18 variant  (models/resnet.py:5-227): direct convolution, BN [+ residual] [+ ReLU] [+ dropout], pooled sigmoid head
 # ----------------------------------------------------------------------------------------------------------------------
 def _triple(v):

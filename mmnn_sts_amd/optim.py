@@ -33,8 +33,23 @@ class FusedSGD(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._step(float(self.param_groups[0]["lr"]), None, None)
+        return None
+
+    @torch.no_grad()
+    def step_device_lr(self, lr: torch.Tensor, live: torch.Tensor):
+        """`step()` with the learning rate read from device memory (`lr`: one float32, e.g. a view into a table of the sweep's rates)
+        and a device switch (`live`: one int32; 0 leaves parameters and momentum untouched).  No host read of either: a caller can
+        enqueue many steps ahead of the GPU (utils/find_lr.py).  The group's `lr` is not used or changed."""
+        for t, dt in ((lr, torch.float32), (live, torch.int32)):
+            if not t.is_cuda or t.dtype != dt or t.numel() != 1:
+                raise ValueError(f"step_device_lr: expected a 1-element {dt} CUDA tensor, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        self._step(None, lr.data_ptr(), live.data_ptr())
+        return None
+
+    def _step(self, lr, lr_ptr, live_ptr):
         g = self.param_groups[0]
-        lr, mom, wd, nes = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), int(bool(g["nesterov"]))
+        mom, wd, nes = float(g["momentum"]), float(g["weight_decay"]), int(bool(g["nesterov"]))
         st = torch.cuda.current_stream().cuda_stream
         L = _lib.lib()
         for bb in self._backbones:
@@ -44,8 +59,12 @@ class FusedSGD(torch.optim.Optimizer):
             first = id(bb) not in self._bufs or self._bufs[id(bb)].data_ptr() == 0 or self._bufs[id(bb)].numel() != flat.numel()
             if first:
                 self._bufs[id(bb)] = torch.empty_like(flat)
-            _lib.check(L.mmnn_sgd_step(flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr, mom, wd,
-                                       nes, int(first), st), "sgd_step")
+            if lr_ptr is None:
+                _lib.check(L.mmnn_sgd_step(flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr, mom, wd,
+                                           nes, int(first), st), "sgd_step")
+            else:
+                _lib.check(L.mmnn_sgd_step_dev(flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr_ptr, live_ptr,
+                                               mom, wd, nes, int(first), st), "sgd_step_dev")
             bb.mark_params_changed()          # written through the raw pointer: invisible to autograd's version counters
         live = [(i, p) for i, p in enumerate(self._rest) if p.grad is not None]
         if live:
@@ -62,9 +81,29 @@ class FusedSGD(torch.optim.Optimizer):
                         raise RuntimeError("FusedSGD expects contiguous float32 parameters and gradients")
                     r.param, r.grad, r.count, r.flat_offset = p.data_ptr(), gr.data_ptr(), p.numel(), self._rest_off[i]
                     r.first_step = int(i not in self._rest_started)      # mom == 0: the buffer is written but never read back
-                _lib.check(L.mmnn_sgd_step_multi(refs, len(chunk), self._rest_buf.data_ptr(), lr, mom, wd, nes, st), "sgd_step_multi")
+                if lr_ptr is None:
+                    _lib.check(L.mmnn_sgd_step_multi(refs, len(chunk), self._rest_buf.data_ptr(), lr, mom, wd, nes, st), "sgd_step_multi")
+                else:
+                    _lib.check(L.mmnn_sgd_step_multi_dev(refs, len(chunk), self._rest_buf.data_ptr(), lr_ptr, live_ptr, mom, wd, nes, st),
+                               "sgd_step_multi_dev")
             self._rest_started.update(i for i, _ in live)
-        return None
+
+    def snapshot_state(self):
+        """Copy of everything a step reads or writes besides the parameters: momentum buffers (device clones), which buffers have
+        started, and the param-group values.  `restore_state(snap)` puts it back (utils/find_lr.py: LRFinder.reset)."""
+        return {
+            "bufs": {k: v.clone() for k, v in self._bufs.items()},
+            "rest_buf": None if self._rest_buf is None else self._rest_buf.clone(),
+            "rest_started": set(self._rest_started),
+            "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+        }
+
+    def restore_state(self, snap) -> None:
+        self._bufs = {k: v.clone() for k, v in snap["bufs"].items()}
+        self._rest_buf = None if snap["rest_buf"] is None else snap["rest_buf"].clone()
+        self._rest_started = set(snap["rest_started"])
+        for g, saved in zip(self.param_groups, snap["param_groups"]):
+            g.update(saved)
 
     def zero_grad(self, set_to_none: bool = True):
         """Tail gradients are set to None.  The backbone's `.grad` views stay attached to the flat gradient buffer and are marked
