@@ -876,6 +876,8 @@ long plan_ws_offset(const Plan& p, const char* name, int i, int j) {
   if (s == "#x3_bytes") return (long)p.x3_bytes;
   if (s == "pk_conv0") return (long)p.o_pk_conv0;
   if (s == "#pack_launches") return p.pack_launches;      // counter, not an offset (tests)
+  if (s == "#ns_c2" && okl(i, j)) return p.ns_c2[i][j];   // voxel splits of the layer's weight-gradient launches (tests)
+  if (s == "#ns_c1" && okl(i, j)) return p.ns_c1[i][j];
   return -1;
 }
 

@@ -79,11 +79,59 @@ class NativeBackbone:
                                                  grad.data_ptr(), int(accumulate), seed, st), "densenet_backward")
         return grad
 
+    def backward_range(self, flat, x, grad_out, hi, lo, accumulate=False, seed=0, grad=None):
+        """Blocks hi .. lo of the backward (the data-parallel schedule: walk from the last block down to 0 in several calls)."""
+        if grad is None:
+            grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+        st = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.mmnn_densenet_backward_range(self.plan, flat.data_ptr(), x.data_ptr(), self.ws.data_ptr(), grad_out.data_ptr(),
+                                                       grad.data_ptr(), int(accumulate), seed, hi, lo, st), "densenet_backward_range")
+        return grad
+
+    def set_option(self, name, value):
+        _lib.check(self.L.mmnn_densenet_set_option(self.plan, name.encode(), value), "set_option")
+
+    def query(self, name, i=0, j=0):
+        """`#name` introspection counters of mmnn_densenet_ws_offset (not offsets)."""
+        v = self.L.mmnn_densenet_ws_offset(self.plan, name.encode(), i, j)
+        assert v >= 0, name
+        return v
+
+    def block_dims(self):
+        """(D, H, W) of every dense block."""
+        d = [(s - 1) // 2 + 1 for s in self.in_dhw]
+        d = [(s - 1) // 2 + 1 for s in d]
+        out = []
+        for _ in self.cfg.block_config:
+            out.append(tuple(d))
+            d = [s // 2 for s in d]
+        return out
+
+    def device_drop_masks(self):
+        """{"b{b}l{l}": (n, growth) bool, True = the layer's channel of that sample has a non-zero element in the concat buffer} of the
+        last forward: the channel-dropout decisions as the device took them."""
+        cfg, n = self.cfg, self.out_shape[0]
+        alive = {}
+        c = cfg.init_features
+        for b, (nl, dims) in enumerate(zip(cfg.block_config, self.block_dims())):
+            ctot = c + nl * cfg.growth_rate
+            xb = self.region("x", (n, ctot, int(np.prod(dims))), b)
+            for l in range(nl):
+                alive[f"b{b + 1}l{l + 1}"] = (xb[:, c:c + cfg.growth_rate] != 0).any(dim=2).cpu()
+                c += cfg.growth_rate
+            c //= 2
+        return alive
+
     def region(self, name, shape, i=0, j=0, dtype=torch.float32):
         off = self.L.mmnn_densenet_ws_offset(self.plan, name.encode(), i, j)
         assert off >= 0, name
         n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
         return self.ws[off:off + n].view(dtype).view(shape)
+
+    def pool_taps(self):
+        """Winning tap (kd*9 + kh*3 + kw) of every window of the stem's max-pool in the last training forward, (n, C0, D, H, W) uint8."""
+        d = self.block_dims()[0]
+        return self.region("idx", (self.out_shape[0], self.cfg.init_features, *d), dtype=torch.uint8).cpu()
 
     def relu_masks(self, flat):
         """All ReLU branch decisions of the last training forward, keyed like oracle.restatement.densenet_backbone."""

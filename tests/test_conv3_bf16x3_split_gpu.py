@@ -15,9 +15,9 @@ pytestmark = pytest.mark.gpu
 CASES = [((24, 40, 66), 2), ((16, 24, 130), 2), ((64, 64, 128), 1)]
 
 
-def _setup(dhw, n, seed_name):
+def _setup(dhw, n, seed_name, dropout=0.0):
     cfg = R.DenseNetCfg(in_channels=2, block_config=(2, 2))
-    nb = NativeBackbone(cfg, n, *dhw)
+    nb = NativeBackbone(cfg, n, *dhw, dropout=dropout)
     sch = nb.schema
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.synth_state_dict(sch, seed_name).items()}
     flat, run = nb.flatten(sd)
@@ -121,6 +121,47 @@ def test_dgrad_planes_and_repeatability(dhw, n):
     s = hi + mi + lo
     assert float(s.abs().max()) > 0
     _check_split(hi, mi, lo, s)
+
+
+@pytest.mark.parametrize("dhw,n", CASES[:2])
+def test_dgrad_planes_with_dropout(dhw, n):
+    """p = 0.2: the split pass folds the layer's dropout scale into the batch-norm backward coefficients (conv3_split_bnbwd_kernel, code
+    of its own).  The planes of a dropped (n, c) channel are exact zeros, every kept channel has a non-zero element, and hi + mid + lo is
+    scale * (p G + q X + r) rebuilt in fp64 from the gradient / activation regions and the fp64 statistics (st_x: sums of X and X^2,
+    s_x: sums of G and G * xhat; NREP = 8 replica rows of `ctot` channels each, unused rows zero)."""
+    from tests._util import channel_drop_mask
+    seed, p = 0xD1B54A32D192ED03, 0.2
+    cfg, nb, flat, run, x = _setup(dhw, n, "c3drop.", dropout=p)
+    if nb.L.mmnn_densenet_ws_offset(nb.plan, b"x3", 0, 0) < 0:
+        pytest.skip("three-piece bf16 kernels switched off (MMNN_BF16X3=0)")
+    cot = torch.from_numpy(synth.uniform("c3drop.cot", nb.out_shape)).cuda()
+    nb.forward(flat, run, x, training=True, seed=seed)
+    nb.backward(flat, x, cot, seed=seed)
+    torch.cuda.synchronize()
+    D, H, W = _block1_dims(dhw)
+    V = D * H * W
+    gr, c0 = cfg.growth_rate, cfg.init_features
+    ctot = c0 + cfg.block_config[0] * gr
+    hi, mi, lo = (t.cpu() for t in _pieces(nb, n, gr, V))          # the last wide data gradient of the backward: block 1, layer 1 (id 0)
+    mask = torch.from_numpy(channel_drop_mask(seed, 0, n, gr, p)).double()
+    assert bool((mask == 0).any()) and bool((mask != 0).any())
+    alive = ((hi != 0) | (mi != 0) | (lo != 0)).any(dim=2)
+    assert torch.equal(alive, mask != 0)
+    G = nb.region("g", (n, ctot, V), 0).double().cpu()[:, c0:c0 + gr]
+    X = nb.region("x", (n, ctot, V), 0).double().cpu()[:, c0:c0 + gr]
+    st = nb.region("st_x", (2, 8, ctot), 0, dtype=torch.float64).cpu().sum(1)[:, c0:c0 + gr]
+    sg = nb.region("s_x", (2, 8, ctot), 0, dtype=torch.float64).cpu().sum(1)[:, c0:c0 + gr]
+    assert torch.isfinite(st).all() and torch.isfinite(sg).all()
+    cnt = float(n * V)
+    mean = st[0] / cnt
+    rstd = 1.0 / torch.sqrt((st[1] / cnt - mean * mean).clamp_min(0) + 1e-5)
+    m1, m2 = sg[0] / cnt, sg[1] / cnt
+    # the statistics are the device's own; pin them to the data they were taken of before using them
+    assert float((mean - X.mean(dim=(0, 2))).abs().max()) <= 1e-6 * float(X.abs().max())
+    pc, qc, rc = rstd, -rstd * rstd * m2, rstd * rstd * m2 * mean - rstd * m1
+    ref = mask[:, :, None] * (pc[None, :, None] * G + qc[None, :, None] * X + rc[None, :, None])
+    print("planes against the fp64 rebuild: max abs err / max", float((hi + mi + lo - ref).abs().max() / ref.abs().max()))
+    _check_split(hi, mi, lo, ref)
 
 
 def test_training_step_on_split_operands_matches_oracle():

@@ -255,6 +255,74 @@ def test_baseline_config3_fusion_gradients_fp64(s):
     assert _compare_all_grads(mm.named_parameters(), sd) == 394   # 398 tensors - the 4 that never get a gradient
 
 
+def test_baseline_config3_fusion_gradients_fp64_dropout(monkeypatch):
+    """The blended training step with NOTHING zeroed, as main.py and bench.py run it: DenseNet121 with Dropout3d 0.2 in every dense
+    layer, element dropout 0.2 on the image features, Dropout1d 0.2 in the clinical MLP.  The stream ids are recorded in call order
+    (backbone, image features, the MLP's two stacks), the restated masks of all of them (tests/_util.py) and the device's ReLU branches
+    are imposed on the fp64 oracle: risk scores and loss at 1e-4, all 394 gradients at the tolerance of the dropout-free test.
+    N = 4 at 64^3; torch.manual_seed is chosen on the CPU (tests/_dropout_cases.py: FUSION_TORCH_SEED, kept true by
+    tests/test_dropout_cpu.py) such that the MLP's batch norm over the live rows is well conditioned."""
+    from mmnn_sts_amd import _lib, ops
+    from mmnn_sts_amd.losses.GradientBlender import GradientBlender
+    from mmnn_sts_amd.losses.losses import CoxPH
+    from mmnn_sts_amd.utils.utils import surv_criterion
+    from tests import _dropout_cases as D
+    from tests._util import backbone_drop_masks, feat_drop_mask_ref
+    n, s, p = 4, 64, 0.2
+    mm = _fusion(True, dropout=p)
+    mm.train()
+    assert sum(1 for m in mm.modules() if m.__class__.__name__.startswith("Dropout") and m.p == p) == 58 + 1 + 6
+    monkeypatch.setattr(ops, "_seed_counter", [0])
+    torch.manual_seed(D.FUSION_TORCH_SEED)
+    drawn, orig = [], ops.next_seed
+    monkeypatch.setattr(ops, "next_seed", lambda: drawn.append(orig()) or drawn[-1])
+    feats = {}
+    hooks = [mm.image_model.register_forward_hook(lambda m, i, o: feats.__setitem__("image", o.detach().cpu())),
+             mm.clinical_model.register_forward_hook(lambda m, i, o: feats.__setitem__("clinical", o.detach().cpu()))]
+    x = {"image": image_in(n, 2, s).to(DEV), "clinical": clin_in(n).to(DEV)}
+    ev, du = labels(n)
+    out = mm(x)
+    for h in hooks:
+        h.remove()
+    gb = GradientBlender(CoxPH, survival=True, surv_criterion=surv_criterion)
+    loss, _ = gb.computeLoss(out, ev.to(DEV), du.to(DEV))
+    loss.backward()
+    monkeypatch.setattr(ops, "next_seed", orig)
+    assert drawn == D.fusion_seeds(D.FUSION_TORCH_SEED)
+    cfg = R.DenseNetCfg()
+    case = D.fusion_mlp_case(D.FUSION_TORCH_SEED, n, p)
+    drop_masks = backbone_drop_masks(cfg, drawn[0], n, p)
+    feat_mask = torch.from_numpy(feat_drop_mask_ref(drawn[1], n, 12, p)).double()
+    mlp_masks = case.masks()
+    # the masks as the device took them, where its outputs show them: dropped image features, dead MLP rows
+    assert torch.equal(feats["image"] == 0, feat_mask == 0) and bool((feat_mask == 0).any())
+    assert bool((feats["clinical"].abs().sum(dim=1) == 0)[mlp_masks[5] == 0].all()) and D.well_formed(case)
+    assert all(bool((m == 0).any()) and bool((m != 0).any()) for m in drop_masks.values())
+    bb = mm.image_model.model.backbone
+    masks = _device_relu_masks(bb, x["image"], cfg)
+    ent = bb._plans[(tuple(x["image"].shape), x["image"].device.index)]
+    off = _lib.lib().mmnn_densenet_ws_offset(ent["plan"], b"idx", 0, 0)
+    pool = ent["ws"][off:off + n * cfg.init_features * (s // 4) ** 3].view(torch.uint8).view(n, cfg.init_features, s // 4, s // 4, s // 4).cpu()
+    sch = R.multimodal_schema(cfg, N_CLIN, 2, 12)
+    sd = {k: (v.double().requires_grad_("running" not in k) if v.is_floating_point() else v) for k, v in synth_sd(sch, "fusion.").items()}
+    taps = {}
+    o64 = R.multimodal_forward(sd, image_in(n, 2, s).double(), clin_in(n).double(), cfg, True, True, mlp_dropout=p, relu_masks=masks,
+                               taps=taps, pool_taps=pool,       # the stem's max-pool winners too: see tests/test_backbone_gpu.py::_run_case
+                               drop_masks=drop_masks, feat_drop_mask=feat_mask, mlp_drop_masks=mlp_masks,
+                               mlp_relu_masks={5: feats["clinical"] > 0})
+    b64 = R.Blender()
+    l64, _ = b64.compute_loss(o64, ev, du)
+    b64.weights = b64.weights.double()
+    l64, _ = b64.compute_loss(o64, ev, du)
+    l64.backward()
+    assert float(taps["pool_gap"].max()) <= 1e-4 * float(taps["stem"].detach().abs().max())
+    eo, el = rel_err(out.detach().cpu().numpy(), o64.detach().numpy()), abs(loss.item() - l64.item()) / abs(l64.item())
+    print("seeds", [hex(v) for v in drawn], "risk scores rel err", eo, "loss rel err", el)
+    assert eo < 1e-4
+    assert el < 1e-4
+    assert _compare_all_grads(mm.named_parameters(), sd) == 394
+
+
 @pytest.mark.parametrize("s", [64, 128, 256])
 def test_baseline_config5_gradcam_golden(s):
     """BASELINE configs[4] (`--inference --images --preop --survival`): Grad-CAM on one patient, up to the BASELINE extent

@@ -244,3 +244,94 @@ def test_cox_blend_typed_operands_and_backward_scale():
     ref2 = preds.double().requires_grad_(True)
     sum(R.pycox_cox_ph_loss(ref2[1][:, c], ev[:, c].double(), du[:, c].double()) for c in range(2)).backward()
     assert rel_err(p.grad.cpu().numpy(), ref2.grad.numpy()) < 2e-5
+
+
+# ---- dropout on: the tail ops against fp64 with the restated masks imposed (tests/_util.py) ---------------------------------------------
+def _record_seeds(monkeypatch, fixed=None):
+    """ops.next_seed() wrapped: records every seed the ops draw, in call order; with `fixed`, hands out those seeds instead."""
+    from mmnn_sts_amd import ops
+    drawn, orig = [], ops.next_seed
+    it = iter(fixed) if fixed is not None else None
+
+    def wrapper():
+        drawn.append(next(it) if it is not None else orig())
+        return drawn[-1]
+
+    monkeypatch.setattr(ops, "next_seed", wrapper)
+    return drawn
+
+
+# n * f crosses 1024 (sample field of the packed index) and 2^20 (layer field), besides a shape that stays inside the channel field.
+# The 2^20 shape is near-square on purpose: dh sums over f and dw / db over n in one fp32 chain each, and a chain of 600000 terms
+# ((2, 8, (1,1,1), 600000): dh off by 1.9e-5, the other three by 1.5e-7) is beyond the 1e-5 of this comparison with or without dropout.
+@pytest.mark.parametrize("n,c,dhw,f", [(3, 40, (2, 3, 5), 12), (130, 8, (1, 1, 1), 12), (1100, 8, (1, 1, 1), 1000)])
+def test_gap_linear_dropout_vs_torch(n, c, dhw, f, monkeypatch):
+    from mmnn_sts_amd import ops
+    from tests._util import feat_drop_mask_ref
+    torch.manual_seed(n)                       # next_seed() derives from it: full 64-bit stream ids
+    drawn = _record_seeds(monkeypatch)
+    h = torch.from_numpy(synth.uniform("gapd/h", (n, c) + dhw)).requires_grad_(True)
+    w = torch.from_numpy(synth.uniform("gapd/w", (f, c), 0.2)).requires_grad_(True)
+    b = torch.from_numpy(synth.uniform("gapd/b", (f,), 0.1)).requires_grad_(True)
+    cot = torch.from_numpy(synth.uniform("gapd/cot", (n, f)))
+    hg, wg, bg = (t.detach().to(DEV).requires_grad_(True) for t in (h, w, b))
+    out = ops.GapLinear.apply(hg, wg, bg, 0.2, True)
+    (out * cot.to(DEV)).sum().backward()
+    assert len(drawn) == 1
+    mask = feat_drop_mask_ref(drawn[0], n, f, 0.2)
+    assert (mask == 0).any() and (mask != 0).any()
+    assert np.array_equal(out.detach().cpu().numpy() == 0, mask == 0)          # the device's own decisions, element by element
+    plain = torch.nn.functional.linear(torch.relu(h.double()).mean(dim=(2, 3, 4)), w.double(), b.double())
+    ref = plain * torch.from_numpy(mask).double()
+    (ref * cot.double()).sum().backward()
+    errs = [rel_err(out.detach().cpu().numpy(), ref.detach().numpy())]
+    errs += [rel_err(got.cpu().numpy(), want.numpy()) for got, want in ((hg.grad, h.grad), (wg.grad, w.grad), (bg.grad, b.grad))]
+    print("seed", hex(drawn[0]), "rel errors out / dh / dw / db", errs)
+    assert max(errs) < 1e-5, errs
+    # eval mode: no mask, whatever p
+    out_e = ops.GapLinear.apply(hg.detach(), wg.detach(), bg.detach(), 0.2, False)
+    assert rel_err(out_e.cpu().numpy(), plain.detach().numpy()) < 1e-5
+
+
+def _mlp_case_id(case):
+    return f"n{case.n}-p{case.p}"
+
+
+def _mlp_cases():
+    from tests._dropout_cases import CASES
+    return CASES
+
+
+@pytest.mark.parametrize("case", _mlp_cases(), ids=_mlp_case_id)
+def test_mlp_row_dropout_vs_fp64(case, monkeypatch):
+    """Both stacks of the MLP (first_layer_id 0: relu -> drop in layer 0, drop -> relu after; first_layer_id 5) with Dropout1d on:
+    features, running statistics, dx and every parameter gradient against oracle.restatement.mlp_features in fp64 with the restated row
+    masks.  The seeds of the N <= 4 cases are chosen on the CPU (tests/_dropout_cases.py, kept true by tests/test_dropout_cpu.py)."""
+    from mmnn_sts_amd.models.mlp import MLP
+    from tests import _dropout_cases as D
+    from tests._util import N_CLIN, clin_in, synth_sd
+    drawn = _record_seeds(monkeypatch, fixed=[case.seed0, case.seed1])
+    m = MLP(N_CLIN, 2, 12, dropout_prob=case.p)
+    m.load_state_dict(synth_sd(D.SCHEMA, "mlp."), strict=True)
+    m = m.to(DEV).train()
+    x = clin_in(case.n).to(DEV).requires_grad_(True)
+    hb = m.backbone(x)
+    f = m.features(hb)
+    cot = torch.from_numpy(synth.uniform("mlp/drop/cot", tuple(f.shape))).to(DEV)
+    (f * cot).sum().backward()
+    assert drawn == [case.seed0, case.seed1]
+    masks = case.masks()
+    assert D.well_formed(case)                                                   # a dropped row somewhere, a kept row in every layer
+    for t, mk in ((hb, masks[4]), (f, masks[5])):
+        dead = (t.detach().abs().sum(dim=1) == 0).cpu()
+        assert bool(dead[mk == 0].all())                                         # dropped rows are all-zero rows
+    # ReLU branches of the two layers whose outputs leave the kernels are taken from the device (a dropped row is zero either way)
+    relu = {4: (hb.detach() > 0).cpu(), 5: (f.detach() > 0).cpu()}
+    ref = D.oracle(case, torch.float64, relu_masks=relu)
+    params = dict(m.named_parameters())
+    sd = m.state_dict()
+    got = (f.detach().cpu(), x.grad.cpu(), {k: params[k].grad.cpu() for k in D.PARAM_KEYS}, {k: sd[k].cpu() for k in D.RUN_KEYS})
+    worst = D.worst_ratio(got, ref)
+    print(case, "worst err / tolerance:", worst)
+    assert worst[0] < 1.0, worst
+    assert params["output_head.dense6.weight"].grad is None

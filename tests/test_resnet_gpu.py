@@ -92,3 +92,104 @@ def test_direct_conv_matches_torch_reference():
         assert rel_err(yg.detach().cpu().numpy(), y.detach().numpy()) < 2e-5, (xs, k)
         assert rel_err(xg.grad.cpu().numpy(), x.grad.numpy()) < 2e-5, (xs, k)
         assert rel_err(wg.grad.cpu().numpy(), w.grad.numpy()) < 2e-5, (xs, k)
+
+
+# ---- element dropout on (csrc/resnet.hip: elem_drop_scale; the backward recomputes the scale from the flat index) ---------------------
+def _record_seeds(monkeypatch):
+    from mmnn_sts_amd import ops
+    drawn, orig = [], ops.next_seed
+
+    def wrapper():
+        drawn.append(orig())
+        return drawn[-1]
+
+    monkeypatch.setattr(ops, "next_seed", wrapper)
+    return drawn
+
+
+@pytest.mark.parametrize("residual", [False, True])
+@pytest.mark.parametrize("relu", [False, True])
+def test_bn_act_dropout_vs_torch(residual, relu, monkeypatch):
+    """BatchNormAct3d at drop_p = 0.5, n * c * v = 1050 (not a multiple of the 256-thread blocks): out, running statistics, dx,
+    dresidual, dgamma, dbeta against torch fp64 with the restated element mask imposed."""
+    from mmnn_sts_amd import ops
+    from tests._util import resnet_elem_mask_ref
+    torch.manual_seed(7)
+    drawn = _record_seeds(monkeypatch)
+    shape, c = (2, 5, 3, 5, 7), 5
+    x = torch.from_numpy(synth.uniform("bnd/x", shape)).double().requires_grad_(True)
+    res = torch.from_numpy(synth.uniform("bnd/r", shape)).double().requires_grad_(True) if residual else None
+    gamma = torch.from_numpy(1.0 + 0.5 * synth.uniform("bnd/g", (c,))).double().requires_grad_(True)
+    beta = torch.from_numpy(synth.uniform("bnd/b", (c,), 0.3)).double().requires_grad_(True)
+    cot = torch.from_numpy(synth.uniform("bnd/c", shape))
+    dev = lambda t: t.detach().float().to(DEV).requires_grad_(True) if t is not None else None
+    xg, rg, gg, bg = dev(x), dev(res), dev(gamma), dev(beta)
+    rm, rv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
+    out = ops.BatchNormAct3d.apply(xg, gg, bg, rm, rv, rg, 0.1, 1e-5, True, relu, 0.5)
+    (out * cot.to(DEV)).sum().backward()
+    assert len(drawn) == 1 and drawn[0] >= 0
+    mask = resnet_elem_mask_ref(drawn[0], x.numel(), 0.5).reshape(shape)
+    assert (mask == 0).any() and (mask == 2).any()
+    rm64, rv64 = torch.zeros(c, dtype=torch.float64), torch.ones(c, dtype=torch.float64)
+    y = torch.nn.functional.batch_norm(x, rm64, rv64, gamma, beta, True, 0.1, 1e-5)
+    if residual:
+        y = y + res
+    if relu:
+        y = torch.relu(y)
+    assert np.array_equal((out.detach().cpu().numpy() == 0) | (y.detach().numpy() == 0), (mask == 0) | (y.detach().numpy() == 0))
+    ref = y * torch.from_numpy(mask).double()
+    (ref * cot.double()).sum().backward()
+    pairs = [("out", out.detach(), ref.detach()), ("running_mean", rm, rm64), ("running_var", rv, rv64), ("dx", xg.grad, x.grad),
+             ("dgamma", gg.grad, gamma.grad), ("dbeta", bg.grad, beta.grad)]
+    if residual:
+        pairs.append(("dresidual", rg.grad, res.grad))
+    errs = {k: rel_err(a.cpu().numpy(), b.numpy()) for k, a, b in pairs}
+    print("seed", hex(drawn[0]), errs)
+    assert max(errs.values()) < 2e-5, errs
+
+
+def test_r3d18_dropout_train_step_fp64(monkeypatch):
+    """r3d_18 end to end at dropout 0.5 (after every stage, fused into the stage's last BN + residual + ReLU): output and all 65
+    gradients against the fp64 oracle with the restated element masks imposed, at the tolerances of the dropout-free test above."""
+    from mmnn_sts_amd.models import resnet as resnet_mod
+    from tests._util import resnet_elem_mask_ref
+    torch.manual_seed(3)
+    drawn = _record_seeds(monkeypatch)
+    stage = []
+    orig_bn = resnet_mod._bn
+
+    def bn(x, bnm, relu, residual=None, drop_p=0.0):
+        out = orig_bn(x, bnm, relu, residual=residual, drop_p=drop_p)
+        if drop_p > 0:
+            stage.append((drawn[-1], tuple(out.shape)))
+        return out
+
+    monkeypatch.setattr(resnet_mod, "_bn", bn)
+    m = _model(dropout=0.5).train()
+    shape = (3, 1, 9, 40, 52)
+    x = torch.from_numpy(synth.uniform("r3d/x/b", shape))
+    y = m(x.to(DEV))
+    cot = torch.from_numpy(synth.uniform("r3d/cot/b", tuple(y.shape)))
+    (y * cot.to(DEV)).sum().backward()
+    assert len(stage) == 4 and len({s for s, _ in stage}) == 4
+    masks = {f"layer{i + 1}": torch.from_numpy(resnet_elem_mask_ref(s, int(np.prod(shp)), 0.5).reshape(shp)).double() for i, (s, shp) in enumerate(stage)}
+    sd = {k: (v.double().requires_grad_("running" not in k) if v.is_floating_point() else v) for k, v in synth_sd(R.resnet18_schema(2), "r3d.").items()}
+    y64 = R.resnet18_forward(sd, x.double(), True, 0.5, drop_masks=masks)
+    (y64 * cot.double()).sum().backward()
+    eo = rel_err(y.detach().cpu().numpy(), y64.detach().numpy())
+    gl2 = float(torch.sqrt(sum((v.grad ** 2).sum() for v in sd.values() if v.is_floating_point() and v.grad is not None)))
+    bad, worst = [], (0.0, "")
+    for k, p in m.named_parameters():
+        ref = sd[k].grad
+        err = float((p.grad.double().cpu() - ref).norm())
+        tol = 2e-3 * float(ref.norm()) + 2e-5 * gl2
+        worst = max(worst, (err / tol, k))
+        if err > tol:
+            bad.append((k, err, float(ref.norm())))
+    print("output rel err", eo, "worst gradient err/tol", worst)
+    assert eo < 1e-4
+    assert not bad, (len(bad), gl2, bad[:6])
+    sd_dev = m.state_dict()
+    for k in sd:
+        if "running" in k:
+            assert rel_err(sd_dev[k].cpu().numpy(), sd[k].detach().numpy()) < 1e-4, k
