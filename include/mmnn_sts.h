@@ -372,6 +372,30 @@ int64_t mmnn_transform_workspace_bytes(const mmnn_transform_desc* d);
 int mmnn_transform_volumes(const mmnn_transform_desc* d, const mmnn_transform_params* per_sample, const float* in, float* out, void* ws,
                            int64_t ws_bytes, void* stream);
 
+/* ---- scan ingest: what upstream's NIfTI datasets do per patient and modality (data/ImageDatasets.py:431-470, :599-637) -- image * mask,
+ * removal of every all-zero slice along each axis, Resize((64,64,64)) (area) -- from the file's voxels in their on-disk type to one
+ * 64^3 fp32 channel plane (csrc/ingest.hip).  With v(x,y,z) = (slope raw + inter) (mslope mraw + minter), formed in fp64 with a rounded
+ * multiply and a rounded add: slice i of an axis is kept when any of its voxels has !(v == 0) (NaN counts as non-zero); the plane is
+ * the adaptive average pooling of the compacted volume to 64^3, window sums in fp64, one rounding to fp32.  Tensor axes D, H, W are the
+ * array axes x, y, z; the raw buffers are read as stored (x fastest).  A slope of 0, NaN or +-inf means "no scaling" (inter ignored
+ * too); a non-finite inter counts as 0.  When the mask leaves nothing (an extent of 0) the plane is written as zeros.
+ * Four launches (one of them a memset), no host synchronisation, no floating-point atomics: repeated calls are bit-identical. */
+#define MMNN_INGEST_SIZE   64     /* output extent per axis */
+#define MMNN_INGEST_MAX_X  2048   /* largest x extent (one fp64 column sum per x and wave lives in LDS) */
+typedef struct {
+  int32_t x, y, z;                /* NIfTI dim[1..3] */
+  int32_t scan_type, mask_type;   /* NIfTI datatype codes: 2 uint8, 4 int16, 8 int32, 16 float32, 64 float64, 256 int8, 512 uint16, 768 uint32 */
+  float scan_slope, scan_inter;   /* scl_slope / scl_inter of the scan's header */
+  float mask_slope, mask_inter;   /* ... of the mask's header */
+} mmnn_ingest_desc;
+/* bytes of device scratch for a scan of x * y * z voxels (occupancy flags, kept-index lists, extents); -1 on a bad extent.  Needs no GPU. */
+int64_t mmnn_ingest_workspace_bytes(int32_t x, int32_t y, int32_t z);
+/* scan, mask: device buffers of x*y*z voxels of the given types, aligned to their element size; out_plane: 64^3 floats (a channel of an
+ * (N, C, 64, 64, 64) tensor; nothing else is written); extents: 3 int32 on the device = kept slices along x, y, z, valid once the
+ * stream has run the call. */
+int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* mask, float* out_plane, int32_t* extents, void* ws,
+                       void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

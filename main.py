@@ -14,7 +14,9 @@ optimizer step per batch, F1 per epoch, best model by mean validation F1 saved a
 Deviations from the reference, all listed in SURVEY Appendix A: the published script cannot be imported (Q1) -- its third assert
 is dropped and CLASS_FREQUENCIES comes from the config; the validation loop moves `val_images` (Q10); the blender lives on the
 loss device (Q4); logging syncs once per epoch, not per micro-batch; `--preop` alone builds the standalone MLP (Q12).
-Datasets (NIfTI / DICOM / S3) are host I/O outside the path: without `--data_loc` synthetic patients are used; the tabular-only
+Datasets: `--image_loc DIR --key_loc key.csv --data_loc clinical.csv` (or the config's `Data:` section) trains on / evaluates local NIfTI
+patient directories -- the files' raw voxels are masked, cropped of empty slices and resized to 64^3 on the device
+(mmnn_sts_amd/data/ingest.py); DICOM / S3 stay outside the path.  Without an image location synthetic patients are used; the tabular-only
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -202,6 +204,55 @@ def to_device(x, device):
     return {k: v.to(device) for k, v in x.items()} if isinstance(x, dict) else x.to(device)
 
 
+def batch_collate(args):
+    """The loader's collate function: the NIfTI datasets' device ingest when `--image_loc` selected them, else `collate`."""
+    return getattr(args, "ingest_collate", None) or collate
+
+
+def report_empty_masks(args):
+    """`--image_loc`: patients whose mask left nothing of a scan (the ingest wrote zeros for them; upstream crashes there) are named once
+    and the run ends non-zero.  Reads the extents of every batch collated since the last call: call it where the epoch has synchronised."""
+    ingest = getattr(args, "ingest_collate", None)
+    empty = ingest.take_empty() if ingest is not None else []
+    if empty:
+        logger.error("empty mask: nothing of the scan is left after masking for patient uid(s) %s", ", ".join(str(u) for u in empty))
+        raise SystemExit(f"empty mask for patient uid(s) {empty}: fix or remove these patients")
+
+
+def split_uids(uids, args, seed):
+    """(train, val) uids: `--train_uid_location` / `--val_uid_location` when both files exist, else a seeded 80 / 20 split of the sorted uids."""
+    from mmnn_sts_amd.utils.utils import loadUIDs
+    if os.path.exists(args.train_uid_location) and os.path.exists(args.val_uid_location):
+        return loadUIDs(args.train_uid_location), loadUIDs(args.val_uid_location)
+    uids = sorted(uids)
+    order = np.random.default_rng(seed).permutation(len(uids))
+    n_val = min(max(1, round(0.2 * len(uids))), len(uids) - 1)
+    return sorted(uids[i] for i in order[n_val:]), sorted(uids[i] for i in order[:n_val])
+
+
+def nifti_datasets(parser, args, device, seed, rank, world):
+    """`--image_loc`: upstream's datasets (parser.getDatasets) over the local patient tree, cut into the train and validation uids; the
+    loaders' collate function becomes the device ingest."""
+    from mmnn_sts_amd.data.ImageDatasets import ImageDatasetByUIDs
+    from mmnn_sts_amd.data.ingest import IngestCollate
+    full = parser.getDatasets(args, parser.getImagePath())
+    train_uids, val_uids = split_uids(full.uids, args, seed)
+    args.ingest_collate = IngestCollate(device)
+    return ImageDatasetByUIDs(full, train_uids[rank::world]), ImageDatasetByUIDs(full, val_uids)
+
+
+def export_patient_nifti(args, uid, image, att, preds):
+    """Upstream's per-patient folder (main.py:829-845): attention_maps/_patient_<uid>/{t1image,t2image,att_map}.nii.gz + preds.txt."""
+    from mmnn_sts_amd.data import nifti
+    d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
+    os.makedirs(d, exist_ok=True)
+    for c, name in zip(range(image.shape[0]), ("t1image", "t2image")):
+        nifti.write(os.path.join(d, name + ".nii.gz"), image[c].cpu().numpy().astype(np.float32))
+    nifti.write(os.path.join(d, "att_map.nii.gz"), att.cpu().numpy().astype(np.float32))
+    with open(os.path.join(d, "preds.txt"), "w") as f:
+        f.write("".join(f"{float(v)!r}\n" for v in preds.reshape(-1)))
+
+
 def apply_transforms(x, tf):
     """`--transforms`: upstream's train / val transforms (main.py:64-92) on the device batch -- the image itself for image-only runs,
     x['image'] for multimodal ones.  None: no transforms."""
@@ -214,8 +265,8 @@ def apply_transforms(x, tf):
 
 # ---- survival (main.py:385-601) ----------------------------------------------------------------------------------------------
 def train_survival(model, train_ds, val_ds, args, device, rank, world):
-    loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, collate_fn=collate, drop_last=len(train_ds) > args.batch_size)
-    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, collate_fn=collate, drop_last=len(val_ds) > args.batch_size)
+    loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, collate_fn=batch_collate(args), drop_last=len(train_ds) > args.batch_size)
+    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, collate_fn=batch_collate(args), drop_last=len(val_ds) > args.batch_size)
     model = model.to(device)
     D.broadcast_parameters(model)
     for m in model.modules():                 # this loop only changes weights through FusedSGD: repack them once per optimizer step,
@@ -278,6 +329,7 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
                 os.makedirs(args.output_path, exist_ok=True)
                 torch.save(model.state_dict(), os.path.join(args.output_path, 'best_surv_model.pth'))
                 logger.info('saved new best metric model')
+        report_empty_masks(args)
         if args.blend and blender_update_due(epoch, args.blend_update_interval):
             # every rank evaluates the same epoch-level losses: its own training patients are gathered from all ranks (the
             # validation set is identical on every rank), so one global weight vector results, as on a single GPU
@@ -296,8 +348,8 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
     GradientBlender's classification branch (:156,:210,:264,:311-314).  With `world` > 1 every rank trains on its own patients:
     identical initial weights, gradients SUM-all-reduced before every optimizer step, checkpoints written by rank 0 only."""
     bs = max(2, args.batch_size)
-    loader = torch.utils.data.DataLoader(train_ds, batch_size=bs, shuffle=True, collate_fn=collate, drop_last=len(train_ds) > bs)
-    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=bs, shuffle=False, collate_fn=collate)
+    loader = torch.utils.data.DataLoader(train_ds, batch_size=bs, shuffle=True, collate_fn=batch_collate(args), drop_last=len(train_ds) > bs)
+    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=bs, shuffle=False, collate_fn=batch_collate(args))
     model = model.to(device)
     D.broadcast_parameters(model)
     freqs = torch.tensor(args.class_frequencies, dtype=torch.float32)
@@ -360,6 +412,7 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
         if rank == 0:
             logger.info(f"epoch {epoch + 1}/{args.epochs} average loss: {float(epoch_loss) / len(train_ds):.4f} train f1 {train_f1:.4f} "
                         f"validation loss {test_loss / len(val_ds):.4f} current f1: {mean_f1:.4f} best f1: {best_metric:.4f} at epoch: {best_epoch}")
+        report_empty_masks(args)
         if args.blend and blender_update_due(epoch, args.blend_update_interval):
             # as in the survival loop: the training patients of all ranks (the validation set is the same everywhere) -> one weight vector
             blender.updateWeights(gather_rows(torch.cat(train_preds, dim=1), 1, world), gather_rows(torch.cat(train_gt).float(), 0, world),
@@ -372,8 +425,8 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
 
 
 def inference_survival(model, ds, args, device):
-    """main.py:750-887: batch-1 loop, Grad-CAM maps (saved as .npy; NIfTI export needs nibabel, host I/O) of fusion and image-only
-    models (main.py:1013-1014: add_gradcam(model, multimodal=...)), C-index."""
+    """main.py:750-887: batch-1 loop, Grad-CAM maps (saved as .npy; with `--image_loc` also upstream's per-patient NIfTI folder) of
+    fusion and image-only models (main.py:1013-1014: add_gradcam(model, multimodal=...)), C-index."""
     model = model.to(device).eval()
     if args.bootstrap:
         args.no_gradcam = True                       # main.py:774-777: no attention maps, no prediction dump while bootstrapping
@@ -381,7 +434,7 @@ def inference_survival(model, ds, args, device):
     preds, evs, dus = [], [], []
     os.makedirs(os.path.join(args.output_path, "attention_maps"), exist_ok=True)
     for i in range(len(ds)):
-        x, ev, du = collate([ds[i]])
+        x, ev, du = batch_collate(args)([ds[i]])
         x = apply_transforms(to_device(x, device), getattr(args, "val_tf", None))
         with torch.no_grad():
             if cam is not None:
@@ -389,10 +442,13 @@ def inference_survival(model, ds, args, device):
                 # fusion: the list of per-class maps, the first saved; image-only: (1, 1, D, H, W), the sample's map saved
                 att = maps[0] if args.multimodal else maps[0, 0]
                 np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_att_map.npy"), att.cpu().numpy())
+                if getattr(args, "ingest_collate", None) is not None:
+                    export_patient_nifti(args, ds.uids[i], (x["image"] if args.multimodal else x)[0], att, p)
             else:
                 p = model(x)
         preds.append(p.cpu()); evs.append(ev); dus.append(du)
     p, e, d = torch.cat(preds).numpy(), torch.cat(evs).numpy(), torch.cat(dus).numpy()
+    report_empty_masks(args)
     if args.bootstrap:
         means, stds, used = bootstrap_c_indices(p, e, d)
         logger.info('Mean c indices: {}'.format(means))
@@ -486,11 +542,23 @@ def main(argv=None):
         raise SystemExit("--bootstrap resamples the evaluation of `--inference --survival` (main.py:767-887); it has no meaning for training runs")
     if a.transforms and not a.images:
         raise SystemExit("--transforms acts on image volumes: it needs --images")
-    if a.image_loc:
-        raise SystemExit("image loaders (NIfTI / DICOM / S3) are host I/O outside this path; run without --image_loc for synthetic volumes")
 
     parser = Parser(a.config)
     cfg = parser.parseConfig()
+    data_cfg = parser.applyDataFlags(a)
+    use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images)
+    if use_nifti:
+        if not a.images:
+            raise SystemExit("--image_loc points at NIfTI patient directories: it needs --images")
+        missing = [k for k in ("key_loc", "data_loc") if not data_cfg.get(k)]
+        if missing:
+            raise SystemExit("--image_loc needs " + " and ".join(f"--{k}" for k in missing) + " (the patient key csv with the columns "
+                             "'Anon MRN', 'MRN'; the clinical csv with uid, predictors, event{i}, duration{i})")
+        if a.lr_finder:
+            raise SystemExit("--lr_finder runs on synthetic patients: run it without --image_loc")
+        n_mod = 2 if cfg["ImageModel"]["modality"].lower().startswith("t1t2") else 1
+        if int(cfg["ImageModel"]["in_channels"]) != n_mod:
+            raise SystemExit(f"ImageModel modality {cfg['ImageModel']['modality']} yields {n_mod} channel(s) per patient, in_channels is {cfg['ImageModel']['in_channels']}")
     hp = cfg.get("Hyperparameters", {})
     a.multimodal = a.images and (a.preop or a.postop)
     a.blend = a.blend and a.multimodal
@@ -526,8 +594,12 @@ def main(argv=None):
         val_csv = write_synthetic_csv(os.path.join(a.output_path, f"synthetic_val_rank{rank}.csv"), n_val, predictors, 7)
         eval_csv = a.data_loc or val_csv        # --inference --data_loc x.csv evaluates THAT file
         mk = lambda n, seed: ClinicalCsvDataset(train_csv if seed >= 1000 else (eval_csv if seed == 99 else val_csv), predictors)
+    elif use_nifti:
+        seed = int(hp.get("seed", 42))
+        nifti_train, nifti_val = nifti_datasets(parser, a, device, seed, rank, world)
+        mk = lambda n, s: nifti_train if s >= 1000 else nifti_val
     elif a.data_loc:
-        raise SystemExit("clinical csv + image loaders are host I/O outside this path; run without --data_loc for synthetic patients")
+        raise SystemExit("clinical csv + image loaders need --image_loc (NIfTI patient directories) and --key_loc; run without --data_loc for synthetic patients")
     if a.inference:
         inference_survival(model, mk(max(2, a.synthetic_patients // 4), 99), a, device)
     elif a.survival:

@@ -93,6 +93,12 @@ class TransformParams(Structure):
                 ("sharp2_k", (c_float * TF_MAX_TAPS) * 3)]
 
 
+class IngestDesc(Structure):
+    """mmnn_ingest_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("scan_type", c_int32), ("mask_type", c_int32), ("scan_slope", c_float),
+                ("scan_inter", c_float), ("mask_slope", c_float), ("mask_inter", c_float)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -181,6 +187,10 @@ def lib():
     L.mmnn_transform_workspace_bytes.argtypes = [POINTER(TransformDesc)]
     L.mmnn_transform_volumes.restype = c_int32
     L.mmnn_transform_volumes.argtypes = [POINTER(TransformDesc), POINTER(TransformParams), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    L.mmnn_ingest_workspace_bytes.restype = c_int64
+    L.mmnn_ingest_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.mmnn_ingest_volume.restype = c_int32
+    L.mmnn_ingest_volume.argtypes = [POINTER(IngestDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

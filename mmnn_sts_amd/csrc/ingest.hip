@@ -1,0 +1,296 @@
+// Scan ingest: one raw NIfTI scan and its mask -> one 64^3 fp32 channel plane, as upstream's image datasets prepare it per patient and
+// modality (data/ImageDatasets.py:431-470, :599-637): image * mask, every all-zero slice dropped along each axis, area resize to 64^3.
+// The contract is the comment above mmnn_ingest_volume in include/mmnn_sts.h.  Neither a float copy nor a cropped copy of the volume
+// is ever written: the scan and the mask are read in their on-disk types, twice (the second time only inside the kept region).
+//
+//   memset                the occupancy flags of the three axes
+//   ingest_flags_kernel   pass A, over the whole scan and mask: flag_x[x] / flag_y[y] / flag_z[z] = 1 where a voxel with !(v == 0) lies.
+//                         Lanes along x, each a fixed group of x columns whose flags it keeps in registers over all its rows; a wave
+//                         covers one row segment at a time, so the y and z flags are reduced with one ballot and written by one lane.
+//                         Every writer writes the constant 1: ordinary stores, no atomics.
+//   ingest_scan_kernel    pass B, one workgroup: exclusive scans of the flags -> kept-index lists and the extents M.
+//   ingest_area_kernel    pass C: a wave per output (b, c) = (y window, z window).  Lanes along the kept x indices sum v over the rows of
+//                         the window in fp64 (registers), leave one column sum per kept x in LDS, and then lane a adds the columns of
+//                         x window a, divides by the window's voxel count and rounds once to fp32.
+// v is formed identically in passes A and C (`ingest_value`): a rounded multiply and a rounded add, never an FMA -- whether a voxel is
+// exactly zero decides which slices survive.
+#include "../../include/mmnn_sts.h"
+#include "area.hpp"
+#include "common.hpp"
+
+#include <cmath>
+
+namespace mmnn {
+
+constexpr int IG_S = MMNN_INGEST_SIZE;
+constexpr int IG_WAVES = 4;                 // waves per block in passes A and C
+constexpr int IG_TPB = 64 * IG_WAVES;
+constexpr int IG_SCAN_TPB = 256;
+
+struct IgScale {
+  double slope, inter;
+  int on;                                   // 0: the raw value is the value
+};
+
+struct IgArgs {
+  const void* scan; const void* mask;
+  int X, Y, Z;
+  int stype, mtype;                         // NIfTI datatype codes
+  IgScale ss, ms;
+  unsigned* flag_x; unsigned* flag_y; unsigned* flag_z;     // [X], [Y], [Z]
+  int* kept_x; int* kept_y; int* kept_z;                    // kept indices in ascending order, the first M[axis] entries valid
+  int* M;                                                   // [3]
+  int* extents;                                             // the caller's copy of M
+  float* out;
+};
+
+template <typename T, int VEC>
+struct alignas(sizeof(T) * VEC) IgVec { T e[VEC]; };
+
+template <typename T, int VEC>
+__device__ __forceinline__ void ig_load_t(const void* base, long idx, double (&out)[VEC]) {
+  const IgVec<T, VEC> v = *reinterpret_cast<const IgVec<T, VEC>*>(static_cast<const T*>(base) + idx);
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) out[k] = (double)v.e[k];
+}
+
+// VEC consecutive voxels starting at element `idx` (a multiple of VEC when VEC > 1), widened to fp64 (exact for every supported type).
+// The type code is the same in every lane: a uniform branch.
+template <int VEC>
+__device__ __forceinline__ void ig_load(const void* base, int code, long idx, double (&out)[VEC]) {
+  switch (code) {
+    case 2:   ig_load_t<uint8_t, VEC>(base, idx, out); break;
+    case 4:   ig_load_t<int16_t, VEC>(base, idx, out); break;
+    case 8:   ig_load_t<int32_t, VEC>(base, idx, out); break;
+    case 16:  ig_load_t<float, VEC>(base, idx, out); break;
+    case 64:  ig_load_t<double, VEC>(base, idx, out); break;
+    case 256: ig_load_t<int8_t, VEC>(base, idx, out); break;
+    case 512: ig_load_t<uint16_t, VEC>(base, idx, out); break;
+    default:  ig_load_t<uint32_t, VEC>(base, idx, out); break;   // 768 (the host admits no other code)
+  }
+}
+
+// raw * slope + inter as numpy evaluates it: two roundings
+__device__ __forceinline__ double ig_scaled(double raw, const IgScale& s) {
+  return s.on ? __dadd_rn(__dmul_rn(raw, s.slope), s.inter) : raw;
+}
+__device__ __forceinline__ double ingest_value(double sraw, double mraw, const IgScale& ss, const IgScale& ms) {
+  return __dmul_rn(ig_scaled(sraw, ss), ig_scaled(mraw, ms));
+}
+
+// ---- pass A ------------------------------------------------------------------------------------------------------------------
+// grid (x groups of 64 * VEC columns, row blocks); block (64, IG_WAVES): threadIdx.y picks the row, a wave = one row segment
+template <int VEC>
+__global__ void __launch_bounds__(IG_TPB) ingest_flags_kernel(const IgArgs a) {
+  const int x0 = (blockIdx.x * 64 + threadIdx.x) * VEC;
+  const bool in_x = x0 < a.X;                       // VEC > 1 only when X % VEC == 0: a group is inside or outside as a whole
+  const int R = a.Y * a.Z;
+  bool nzx[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) nzx[k] = false;
+  for (int r = blockIdx.y * IG_WAVES + threadIdx.y; r < R; r += gridDim.y * IG_WAVES) {
+    bool any = false;
+    if (in_x) {
+      const long idx = (long)r * a.X + x0;
+      double s[VEC], m[VEC];
+      ig_load<VEC>(a.scan, a.stype, idx, s);
+      ig_load<VEC>(a.mask, a.mtype, idx, m);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const bool nz = !(ingest_value(s[k], m[k], a.ss, a.ms) == 0.0);
+        nzx[k] |= nz;
+        any |= nz;
+      }
+    }
+    if (__ballot(any) != 0ull && threadIdx.x == 0) {   // r = y + Y z is the same in the whole wave
+      a.flag_y[r % a.Y] = 1u;
+      a.flag_z[r / a.Y] = 1u;
+    }
+  }
+  if (in_x) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+      if (nzx[k]) a.flag_x[x0 + k] = 1u;
+  }
+}
+
+// ---- pass B ------------------------------------------------------------------------------------------------------------------
+// one block: kept[pos] = i for every i with flag[i] != 0, pos = number of flagged indices below i; returns the count (in every thread)
+__device__ int ig_compact(const unsigned* flag, int n, int* kept, int* lds) {
+  int base = 0;
+  for (int c0 = 0; c0 < n; c0 += IG_SCAN_TPB) {
+    const int i = c0 + threadIdx.x;
+    const int f = (i < n && flag[i] != 0u) ? 1 : 0;
+    __syncthreads();
+    lds[threadIdx.x] = f;
+    __syncthreads();
+    // inclusive Hillis-Steele scan of IG_SCAN_TPB entries
+    for (int o = 1; o < IG_SCAN_TPB; o <<= 1) {
+      const int add = (int)threadIdx.x >= o ? lds[threadIdx.x - o] : 0;
+      __syncthreads();
+      lds[threadIdx.x] += add;
+      __syncthreads();
+    }
+    const int incl = lds[threadIdx.x];
+    if (f) kept[base + incl - 1] = i;
+    base += lds[IG_SCAN_TPB - 1];
+  }
+  return base;
+}
+
+__global__ void __launch_bounds__(IG_SCAN_TPB) ingest_scan_kernel(const IgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char ig_smem[];
+  int* lds = reinterpret_cast<int*>(ig_smem);
+  const int mx = ig_compact(a.flag_x, a.X, a.kept_x, lds);
+  const int my = ig_compact(a.flag_y, a.Y, a.kept_y, lds);
+  const int mz = ig_compact(a.flag_z, a.Z, a.kept_z, lds);
+  if (threadIdx.x == 0) {
+    a.M[0] = mx; a.M[1] = my; a.M[2] = mz;
+    a.extents[0] = mx; a.extents[1] = my; a.extents[2] = mz;
+  }
+}
+
+// ---- pass C ------------------------------------------------------------------------------------------------------------------
+// grid (IG_S / IG_WAVES, IG_S): blockIdx.y = b (y window), wave w of block blockIdx.x = c (z window).  Dynamic LDS: IG_WAVES * X doubles.
+__global__ void __launch_bounds__(IG_TPB) ingest_area_kernel(const IgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char ig_smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double* col = reinterpret_cast<double*>(ig_smem) + (long)wave * a.X;
+  const int b = blockIdx.y, c = blockIdx.x * IG_WAVES + wave;
+  const int mx = a.M[0], my = a.M[1], mz = a.M[2];
+  float* dst = a.out + ((long)lane * IG_S + b) * IG_S + c;      // lane = a (x window)
+  if (mx == 0 || my == 0 || mz == 0) {                          // the mask misses the scan: zeros (the extents tell the caller)
+    *dst = 0.f;
+    return;
+  }
+  int yb, ye, zb, ze;
+  area_window(b, my, IG_S, 0, yb, ye);
+  area_window(c, mz, IG_S, 0, zb, ze);
+  for (int j = lane; j < mx; j += 64) {
+    const long x = a.kept_x[j];
+    double acc = 0.0;
+    for (int zi = zb; zi < ze; ++zi) {
+      const long zrow = (long)a.kept_z[zi] * a.Y;
+#pragma unroll 4
+      for (int yi = yb; yi < ye; ++yi) {
+        const long idx = (zrow + a.kept_y[yi]) * a.X + x;
+        double s[1], m[1];
+        ig_load<1>(a.scan, a.stype, idx, s);
+        ig_load<1>(a.mask, a.mtype, idx, m);
+        acc += ingest_value(s[0], m[0], a.ss, a.ms);
+      }
+    }
+    col[j] = acc;
+  }
+  __syncthreads();     // (every wave of the block runs the same trip counts: mx, my, mz are block-uniform)
+  int xb, xe;
+  area_window(lane, mx, IG_S, 0, xb, xe);
+  double sum = 0.0;
+  for (int j = xb; j < xe; ++j) sum += col[j];
+  const double count = (double)(xe - xb) * (double)(ye - yb) * (double)(ze - zb);
+  *dst = (float)(sum / count);
+}
+
+namespace {
+
+size_t ig_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct IgLayout {
+  size_t flags, kept, m, total;     // flags: X + Y + Z words (one memset); kept: X + Y + Z ints; m: the extents
+};
+
+IgLayout ig_layout(int x, int y, int z) {
+  const size_t n = (size_t)x + (size_t)y + (size_t)z;
+  IgLayout L;
+  size_t off = 0;
+  L.flags = off; off += ig_align(n * sizeof(unsigned));
+  L.kept = off; off += ig_align(n * sizeof(int));
+  L.m = off; off += ig_align(4 * sizeof(int));
+  L.total = off;
+  return L;
+}
+
+int ig_type_size(int code) {
+  switch (code) {
+    case 2: case 256: return 1;
+    case 4: case 512: return 2;
+    case 8: case 16: case 768: return 4;
+    case 64: return 8;
+    default: return 0;
+  }
+}
+
+// nibabel's reading of scl_slope / scl_inter: a slope of 0, NaN or +-inf switches scaling off; a non-finite inter is 0.  The header's
+// float32 values are widened to fp64 before they meet a voxel.
+IgScale ig_scale(float slope, float inter) {
+  IgScale s{1.0, 0.0, 0};
+  if (slope == 0.f || !std::isfinite(slope)) return s;
+  s.slope = (double)slope;
+  s.inter = std::isfinite(inter) ? (double)inter : 0.0;
+  s.on = !(s.slope == 1.0 && s.inter == 0.0);
+  return s;
+}
+
+int ig_validate_extent(int x, int y, int z) {
+  MMNN_REQUIRE(x >= 1 && y >= 1 && z >= 1, "ingest: non-positive extent %d x %d x %d", x, y, z);
+  MMNN_REQUIRE(x <= MMNN_INGEST_MAX_X, "ingest: x extent %d above %d", x, MMNN_INGEST_MAX_X);
+  MMNN_REQUIRE((long)y * z < (1l << 31) && (long)x + y + z < (1l << 30), "ingest: extent %d x %d x %d too large", x, y, z);
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace mmnn
+
+using namespace mmnn;
+
+extern "C" {
+
+int64_t mmnn_ingest_workspace_bytes(int32_t x, int32_t y, int32_t z) {
+  if (ig_validate_extent(x, y, z) != 0) return -1;
+  return (int64_t)ig_layout(x, y, z).total;
+}
+
+int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* mask, float* out_plane, int32_t* extents, void* ws,
+                       void* stream_) {
+  MMNN_REQUIRE(d, "ingest: null descriptor");
+  if (ig_validate_extent(d->x, d->y, d->z) != 0) return 1;
+  const int ssz = ig_type_size(d->scan_type), msz = ig_type_size(d->mask_type);
+  MMNN_REQUIRE(ssz != 0, "ingest: unsupported scan datatype code %d (2, 4, 8, 16, 64, 256, 512, 768 are)", d->scan_type);
+  MMNN_REQUIRE(msz != 0, "ingest: unsupported mask datatype code %d (2, 4, 8, 16, 64, 256, 512, 768 are)", d->mask_type);
+  MMNN_REQUIRE(scan && mask && out_plane && extents && ws, "ingest: null argument");
+  MMNN_REQUIRE((uintptr_t)scan % ssz == 0 && (uintptr_t)mask % msz == 0, "ingest: scan / mask buffer not aligned to its element size");
+  MMNN_REQUIRE((uintptr_t)ws % 256 == 0 && (uintptr_t)out_plane % 4 == 0 && (uintptr_t)extents % 4 == 0, "ingest: misaligned workspace / output");
+  const hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const IgLayout L = ig_layout(d->x, d->y, d->z);
+  char* wsb = static_cast<char*>(ws);
+  IgArgs a{};
+  a.scan = scan; a.mask = mask;
+  a.X = d->x; a.Y = d->y; a.Z = d->z;
+  a.stype = d->scan_type; a.mtype = d->mask_type;
+  a.ss = ig_scale(d->scan_slope, d->scan_inter);
+  a.ms = ig_scale(d->mask_slope, d->mask_inter);
+  a.flag_x = reinterpret_cast<unsigned*>(wsb + L.flags); a.flag_y = a.flag_x + d->x; a.flag_z = a.flag_y + d->y;
+  a.kept_x = reinterpret_cast<int*>(wsb + L.kept); a.kept_y = a.kept_x + d->x; a.kept_z = a.kept_y + d->y;
+  a.M = reinterpret_cast<int*>(wsb + L.m);
+  a.extents = extents;
+  a.out = out_plane;
+
+  MMNN_HIP(hipMemsetAsync(wsb + L.flags, 0, ((size_t)d->x + d->y + d->z) * sizeof(unsigned), stream));
+  // pass A: 4 voxels per lane when every row starts on a 4-voxel boundary of both buffers
+  const int R = d->y * d->z;
+  const bool vec4 = d->x % 4 == 0 && (uintptr_t)scan % (4 * ssz) == 0 && (uintptr_t)mask % (4 * msz) == 0;
+  const int vec = vec4 ? 4 : 1;
+  const int gx = cdiv(d->x, 64 * vec);
+  int gy = cdiv(R, IG_WAVES);
+  const int cap = cdiv(2048, gx);
+  if (gy > cap) gy = cap;
+  if (vec4) MMNN_LAUNCH(ingest_flags_kernel<4>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a);
+  else MMNN_LAUNCH(ingest_flags_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a);
+  MMNN_LAUNCH(ingest_scan_kernel, dim3(1), dim3(IG_SCAN_TPB), IG_SCAN_TPB * sizeof(int), stream, a);
+  MMNN_LAUNCH(ingest_area_kernel, dim3(IG_S / IG_WAVES, IG_S), dim3(IG_TPB), (size_t)IG_WAVES * d->x * sizeof(double), stream, a);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 //
 // Samples travel in groups of TF_G per launch: every per-sample parameter is a kernel argument (no host-to-device copy, no sync).
 #include "../../include/mmnn_sts.h"
+#include "area.hpp"
 #include "common.hpp"
 
 #include <math.h>
@@ -198,12 +199,7 @@ __global__ void __launch_bounds__(TF_TPB) tf_rotate_kernel(const TfRotArgs a) {
   store_partial(a.part_out, s, olo, ohi);
 }
 
-// window of intermediate index j (extent m) over a source axis of extent n: adaptive_avg_pool's [floor(j n / m), ceil((j + 1) n / m))
-__device__ __forceinline__ void area_window(int o, int n, int m, int off, int& b, int& e) {
-  const int j = min(max(o + off, 0), m - 1);
-  b = (j * n) / m;
-  e = ((j + 1) * n + m - 1) / m;
-}
+// (the window rule of the area resize, `area_window`, is csrc/area.hpp: the scan ingest uses the same one)
 
 __global__ void __launch_bounds__(TF_TPB) tf_area_kernel(const TfAreaArgs a) {
   const int s = blockIdx.y;

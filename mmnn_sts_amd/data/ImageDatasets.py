@@ -1,0 +1,172 @@
+"""Upstream's local-disk NIfTI datasets (data/ImageDatasets.py:26-56, 310-377, 422-470, 520-640) with their class names and constructor
+arguments.  The directory contract is upstream's: one directory per patient under `patient_directory`; in it, the file whose name starts
+with `scan` is the image and the other one the mask; the anonymised id is the first two `-`-separated fields of the directory name
+(:426); `patient_key` is a csv with the columns `Anon MRN` and `MRN` that maps it to the uid.  Labels come from this project's clinical
+csv (`ClinicalDatasets.LabelTable`), joined on `uid`.
+
+`__getitem__` yields a `RawPatient` -- the files' voxels in their on-disk type, unmasked and uncropped -- in place of upstream's float
+volume: masking, empty-slice removal, the 64^3 area resize and the T1 / T2 stacking happen on the device in the collate function
+(`mmnn_sts_amd.data.ingest.IngestCollate`), and upstream's train / validation transforms act on the collated batch (`--transforms`).
+`transforms`, `slices` are accepted for signature parity; a per-item transform cannot run on raw voxels and is refused.
+"""
+import csv
+import os
+
+import torch
+
+from ..exceptions.exceptions import ConfigurationError
+from . import nifti
+from .ClinicalDatasets import LabelTable
+from .ingest import RawPatient
+
+RADIOMICS_UID = 'MRN'
+ANON_ID = 'Anon MRN'
+
+
+def anon_id_of(directory_name):
+    return '-'.join(directory_name.split('-')[:2])
+
+
+def _read_key(path):
+    with open(path, newline='') as f:
+        rows = list(csv.DictReader(f))
+    if not rows or ANON_ID not in rows[0] or RADIOMICS_UID not in rows[0]:
+        raise ConfigurationError(f"patient key {path} needs the columns '{ANON_ID}' and '{RADIOMICS_UID}'")
+    return {r[ANON_ID].strip(): int(float(r[RADIOMICS_UID])) for r in rows}
+
+
+class ImageDataset(torch.utils.data.Dataset):
+    def __init__(self, patient_directory, patient_key):
+        self.patient_directory = str(patient_directory)
+        self.patients = sorted(x for x in os.listdir(self.patient_directory)
+                               if not x.startswith('.') and os.path.isdir(os.path.join(self.patient_directory, x)))
+        self.patient_key = _read_key(patient_key)
+        self.multimodal_identifier = 'image'
+        self.transforms = None
+        for p in self.patients:
+            if anon_id_of(p) not in self.patient_key:
+                raise ConfigurationError(f"patient directory {p} ({anon_id_of(p)}) has no row in the patient key {patient_key}")
+            self._files(p)
+
+    def _uid_of(self, patient):
+        return self.patient_key[anon_id_of(patient)]
+
+    @property
+    def uids(self):
+        return [self._uid_of(p) for p in self.patients]
+
+    def __len__(self):
+        return len(self.patients)
+
+    def _files(self, patient):
+        d = os.path.join(self.patient_directory, patient)
+        files = sorted(f for f in os.listdir(d) if not f.startswith('.'))
+        scans = [f for f in files if f.startswith('scan')]
+        masks = [f for f in files if not f.startswith('scan')]
+        if len(scans) != 1:
+            raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {len(scans)} files named scan* in {d}, one expected")
+        if len(masks) != 1:
+            raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {'no mask' if not masks else 'several candidate masks'} beside {scans[0]} in {d}")
+        return os.path.join(d, scans[0]), os.path.join(d, masks[0])
+
+    def _load(self, patient):
+        scan_path, mask_path = self._files(patient)
+        scan, mask = nifti.read(scan_path), nifti.read(mask_path)
+        if scan.shape != mask.shape or len(scan.shape) != 3:
+            raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): scan extent {scan.shape}, mask extent {mask.shape}")
+        return scan, mask
+
+    def _index_of_uid(self, uid):
+        for i, p in enumerate(self.patients):
+            if self._uid_of(p) == int(uid):
+                return i
+        raise ConfigurationError(f"patient uid {uid} not found under {self.patient_directory}")
+
+    def getDataByUID(self, uid):
+        return self.__getitem__(self._index_of_uid(uid))
+
+
+class _LabelledNifti(ImageDataset):
+    survival = False
+
+    def __init__(self, patient_directory, clinical_data, patient_key, slices=False, transforms=None):
+        super().__init__(patient_directory, patient_key)
+        if slices:
+            raise ConfigurationError("slices=True (2-D slices of a volume) is outside the MI355X path")
+        if transforms is not None:
+            raise ConfigurationError("per-item transforms cannot run on raw voxels: pass --transforms (they act on the collated device batch)")
+        self.labels = LabelTable(clinical_data)
+        for p in self.patients:
+            if self._uid_of(p) not in self.labels.row:
+                raise ConfigurationError(f"patient {p} (uid {self._uid_of(p)}) has no row in the clinical csv {clinical_data}")
+
+    def _volumes(self, patient):
+        return [self._load(patient)]
+
+    def __getitem__(self, index):
+        patient = self.patients[index]
+        uid = self._uid_of(patient)
+        raw = RawPatient(uid, self._volumes(patient))
+        if self.survival:
+            return raw, self.labels.events(uid), self.labels.durations(uid)
+        return raw, self.labels.events(uid)
+
+
+class NiftiImageDataset(_LabelledNifti):
+    """data/ImageDatasets.py:327-377: (image, label)."""
+
+
+class NiftiSurvivalDataset(_LabelledNifti):
+    """data/ImageDatasets.py:422-470: (image, events, durations)."""
+    survival = True
+
+
+class _T1T2(_LabelledNifti):
+    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None):
+        cls = NiftiSurvivalDataset if self.survival else NiftiImageDataset
+        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None)
+        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None)
+        super().__init__(t1_directory, clinical_data, patient_key, slices, transforms)
+        self.t1_patients, self.t2_patients = self.t1_dataset.patients, self.t2_dataset.patients
+        # patients common to both trees, by anonymised id; kept as the T1 directory names
+        in_t2 = {anon_id_of(p): p for p in self.t2_patients}
+        self.patients = [p for p in self.t1_patients if anon_id_of(p) in in_t2]
+        self._t2_of = {p: in_t2[anon_id_of(p)] for p in self.patients}
+
+    def _volumes(self, patient):
+        return [self.t1_dataset._load(patient), self.t2_dataset._load(self._t2_of[patient])]
+
+
+class T1T2ImageDataset(_T1T2):
+    """data/ImageDatasets.py:520-576: both modalities of the patients present in both trees, stacked along the channel axis."""
+
+
+class T1T2SurvivalDataset(_T1T2):
+    """data/ImageDatasets.py:578-640."""
+    survival = True
+
+
+class ImageDatasetByUIDs(torch.utils.data.Dataset):
+    """data/ImageDatasets.py:310-325: the sub-dataset of `dataset` that can only reach the given uids."""
+
+    def __init__(self, dataset, uids, seed=42, train_percent=0.8, transforms=None):
+        self.dataset = dataset
+        self.set_uids = [int(u) for u in uids]
+        self.multimodal_identifier = getattr(dataset, 'multimodal_identifier', 'image')
+        known = set(dataset.uids)
+        missing = [u for u in self.set_uids if u not in known]
+        if missing:
+            raise ConfigurationError(f"uids {missing[:8]} are not in the dataset")
+
+    @property
+    def uids(self):
+        return self.set_uids
+
+    def getDataByUID(self, uid):
+        return self.dataset.getDataByUID(uid)
+
+    def __getitem__(self, index):
+        return self.dataset.getDataByUID(self.set_uids[index])
+
+    def __len__(self):
+        return len(self.set_uids)

@@ -3,12 +3,19 @@
 `Parser(config).parseConfig()` reads the same YAML schema (config.yaml); `getModel(args)` builds the native DenseNet121 /
 TinyDensenet and wraps it into `MultiModalModel` for `--images --preop|--postop` exactly like parser/parser.py:105-182.
 Fixes: `--preop` alone yields the standalone clinical MLP; the predictor list may be given as an
-integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  Dataset construction (parser.py:43-97) is host I/O outside
-the path; main.py substitutes synthetic patients when no data location is configured.
+integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  `getImagePath()` / `getDatasets(args, image_path)` (parser.py:43-97,
+184-198) build the local-disk NIfTI datasets from the `Data:` section (`image_loc`, `t1_path`, `t2_path`, `data_loc`, `key_loc`; the
+command-line flags override it); S3, DICOM and radiomics datasets stay outside the path, and main.py substitutes synthetic patients when
+no image location is configured.
 """
+import os
+
 import yaml
 
 from ..exceptions.exceptions import ConfigurationError, InitializationError
+from ..data.ClinicalDatasets import ClinicalDataset
+from ..data.ImageDatasets import NiftiImageDataset, NiftiSurvivalDataset, T1T2ImageDataset, T1T2SurvivalDataset
+from ..data.MultiModalDatasets import MultiModalDataset, MultiModalSurvivalDataset
 from ..models.densenet import DenseNet121, TinyDensenet
 from ..models.mlp import MLP
 from ..models.multimodal import MultiModalModel
@@ -47,6 +54,54 @@ class Parser:
         if getattr(args, 'postop', False):
             p += list(cm.get('POST_OP_PREDICTORS', []))
         return p
+
+    def applyDataFlags(self, args):
+        """The `Data:` section with --image_loc / --data_loc / --key_loc laid over it (t1_path / t2_path default to 't1' / 't2')."""
+        data = dict(self.config.get('Data') or {})
+        for k in ('image_loc', 'data_loc', 'key_loc'):
+            if getattr(args, k, None):
+                data[k] = getattr(args, k)
+        data.setdefault('t1_path', 't1')
+        data.setdefault('t2_path', 't2')
+        self.config['Data'] = data
+        return data
+
+    def _data(self, key):
+        value = (self.config.get('Data') or {}).get(key)
+        if not value:
+            raise ConfigurationError('Data.{0} is not configured (config `Data: {0}:` or --{0})'.format(key))
+        return value
+
+    def getImagePath(self):
+        """parser/parser.py:184-198: the modality's directory under image_loc; a (t1, t2) tuple for 't1t2'."""
+        modality = self.config['ImageModel']['modality'].lower()
+        if modality.startswith('t1t2'):
+            return (os.path.join(self._data('image_loc'), self._data('t1_path')), os.path.join(self._data('image_loc'), self._data('t2_path')))
+        if modality.startswith('t1'):
+            return os.path.join(self._data('image_loc'), self._data('t1_path'))
+        if modality.startswith('t2'):
+            return os.path.join(self._data('image_loc'), self._data('t2_path'))
+        raise ConfigurationError("ImageModel modality {!r} is none of 't1', 't2', 't1t2'".format(self.config['ImageModel']['modality']))
+
+    def getDatasets(self, args, image_path=None):
+        """parser/parser.py:43-97 for the local-disk cases: the clinical dataset (with --preop / --postop), the NIfTI image dataset of
+        the modality (with --images), and their MultiModal(Survival)Dataset when both are asked for."""
+        if not (args.classification or args.survival):
+            raise ConfigurationError('getDatasets needs --survival or --classification to pick the dataset classes')
+        datasets = []
+        if getattr(args, 'preop', False) or getattr(args, 'postop', False):
+            datasets.append(ClinicalDataset(self._data('data_loc'), self.predictors(args), classification=args.classification, survival=args.survival))
+        if args.images:
+            both = isinstance(image_path, tuple)
+            if args.survival:
+                cls = T1T2SurvivalDataset if both else NiftiSurvivalDataset
+            else:
+                cls = T1T2ImageDataset if both else NiftiImageDataset
+            paths = image_path if both else (image_path,)
+            datasets.append(cls(*paths, self._data('data_loc'), self._data('key_loc')))
+        if len(datasets) == 1:
+            return datasets[0]
+        return MultiModalSurvivalDataset(datasets) if args.survival else MultiModalDataset(datasets)
 
     def getModel(self, args):
         if self.config is None:
