@@ -136,7 +136,9 @@ typedef struct {
 } mmnn_mlp_params;
 int64_t mmnn_mlp_saved_floats(const mmnn_mlp_desc* d);      /* size of `saved` */
 int mmnn_mlp_forward(const mmnn_mlp_desc* d, const mmnn_mlp_params* p, const float* x, float* out, float* saved, void* stream);
-/* scratch: 2 * n * max(dim) floats; dx may be NULL */
+/* scratch: 2 * n * max(dim) floats; dx may be NULL.  The BatchNorm adjoint follows d->training, which must be the flag of the forward
+   that wrote `saved`: 1 -- batch statistics, dz = gamma rstd (g - mean_n g - xhat mean_n(g xhat)); 0 -- running statistics, constants
+   of the pass, dz = gamma rstd g.  Either way dgamma = sum_n g xhat, dbeta = sum_n g (xhat and rstd as the forward saved them). */
 int mmnn_mlp_backward(const mmnn_mlp_desc* d, const mmnn_mlp_params* p, const float* x, const float* saved, const float* dy,
                       float* dx, float* scratch, int32_t accumulate, void* stream);
 

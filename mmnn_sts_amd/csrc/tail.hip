@@ -192,7 +192,8 @@ __global__ void __launch_bounds__(256) mlp_bwd_kernel(const MlpArgs a) {
       a.dbeta[i][o] = (a.accumulate ? a.dbeta[i][o] : 0.f) + (float)s0;
       a.dgamma[i][o] = (a.accumulate ? a.dgamma[i][o] : 0.f) + (float)s1;
       const float k = a.gamma[i][o] * rstd[o];
-      const float m0 = (float)(s0 / a.N), m1 = (float)(s1 / a.N);
+      // batch statistics: dz = k (g - mean g - xhat mean(g xhat)); running statistics (eval) are constants of the pass: dz = k g
+      const float m0 = a.training ? (float)(s0 / a.N) : 0.f, m1 = a.training ? (float)(s1 / a.N) : 0.f;
       float sb = 0.f;
       for (int n = 0; n < a.N; ++n) {
         const float v = k * (g[n * O + o] - m0 - xhat[n * O + o] * m1);
@@ -440,16 +441,19 @@ __global__ void __launch_bounds__(256) linear_bwd_kernel(int N, int D, int O, co
 // ='none') as the classification trainer builds it (main.py:147-153), for `criterion` (utils/utils.py:20-22) and
 // GradientBlender.computeLossClassification (losses/GradientBlender.py:150-179).
 //   l = pw_c * y * softplus(-x) + (1 - y) * softplus(x),   dl/dx = (1 - y) * sigmoid(x) - pw_c * y * sigmoid(-x)
+// with e = exp(-|x|): sigmoid(|x|) = 1 / (1 + e), sigmoid(-|x|) = e / (1 + e) -- both to fp32 rounding (1 - sigmoid(x) would leave
+// sigmoid(-x) with an absolute error of 6e-8 however small it is)
 // =====================================================================================================================
 __global__ void __launch_bounds__(256) bce_logits_kernel(long total, int C, const float* x, const float* y, const float* pw, float* loss,
                                                           float* dldx) {
   for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const float xv = x[e], yv = y[e], w = pw ? pw[e % C] : 1.f;
-    const float ax = fabsf(xv), l1p = log1pf(expf(-ax));          // stable softplus: softplus(t) = max(t, 0) + log1p(exp(-|t|))
+    const float ex = expf(-fabsf(xv)), l1p = log1pf(ex);          // stable softplus: softplus(t) = max(t, 0) + log1p(exp(-|t|))
     const float sp_pos = fmaxf(xv, 0.f) + l1p, sp_neg = fmaxf(-xv, 0.f) + l1p;
-    const float sg = 1.f / (1.f + expf(-xv));
+    const float s_big = 1.f / (1.f + ex), s_small = ex * s_big;
+    const float sg = xv >= 0.f ? s_big : s_small, sg_neg = xv >= 0.f ? s_small : s_big;
     loss[e] = w * yv * sp_neg + (1.f - yv) * sp_pos;
-    if (dldx) dldx[e] = (1.f - yv) * sg - w * yv * (1.f - sg);
+    if (dldx) dldx[e] = (1.f - yv) * sg - w * yv * sg_neg;
   }
 }
 
