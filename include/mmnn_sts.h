@@ -398,6 +398,32 @@ int64_t mmnn_ingest_workspace_bytes(int32_t x, int32_t y, int32_t z);
 int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* mask, float* out_plane, int32_t* extents, void* ws,
                        void* stream);
 
+/* ---- a mask drawn on another grid -> the scan's grid: what upstream's DICOM datasets do before masking (data/ImageDatasets.py:145-152,
+ * :246-257) -- `sitk.Resample(mask, image)` with its defaults (identity transform, linear interpolator, default pixel value 0), then the
+ * rebinarisation `mask > 128` -- as one byte per scan voxel (csrc/ingest.hip).  T = index_map takes a scan voxel index to a continuous
+ * mask index: inverse(mask affine) * (scan affine), formed by the caller in fp64.  For scan voxel (i, j, k), all in fp64:
+ *   coordinates    c_r = T[r][0] i + T[r][1] j + T[r][2] k + T[r][3], r = 0..2.
+ *   outside test   the byte is 0 unless -0.5 <= c_r < m_r - 0.5 on all three axes (ITK's buffer test on a continuous index).
+ *   interpolation  f_r = floor(c_r), w_r = c_r - f_r; the eight neighbour indices f_r, f_r + 1 are clamped to [0, m_r - 1]; m is the
+ *                  trilinear blend (weights 1 - w_r, w_r) of the scaled mask voxels slope raw + inter (the "no scaling" rules of the
+ *                  ingest above: a slope of 0, NaN or +-inf switches scaling off, a non-finite inter counts as 0).
+ *   binarisation   the byte is 1 when m > threshold, else 0.  A NaN mask voxel therefore gives 0 over its whole neighbourhood -- unlike
+ *                  the same-grid ingest above, where a NaN mask voxel counts as non-zero and keeps its slices.
+ * Differences from SimpleITK: sitk.Resample casts the interpolated value to the mask's integer pixel type before upstream compares it
+ * with 128; here the fp64 value is compared.  `out` holds x*y*z bytes, x fastest, and every byte is written (nothing else is).  One
+ * launch, no atomics, no host synchronisation: repeated calls are bit-identical.  The ingest then runs on (scan, out) with mask_type 2,
+ * slope 1, inter 0.  Refused (status 1): a non-positive extent, x*y*z or mx*my*mz >= 2^31, an unknown type code, a non-finite
+ * index_map entry or threshold, a mask buffer not aligned to its element size. */
+typedef struct {
+  int32_t x, y, z;                /* scan grid = output grid, NIfTI dim[1..3] */
+  int32_t mx, my, mz;             /* mask grid */
+  int32_t mask_type;              /* NIfTI datatype code, same set as mmnn_ingest_desc */
+  float mask_slope, mask_inter;   /* scl_slope / scl_inter of the mask's header */
+  double index_map[12];           /* rows of the 3x4 matrix T */
+  double threshold;
+} mmnn_resample_mask_desc;
+int mmnn_resample_mask(const mmnn_resample_mask_desc* d, const void* mask, uint8_t* out, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

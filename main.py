@@ -237,7 +237,7 @@ def nifti_datasets(parser, args, device, seed, rank, world):
     from mmnn_sts_amd.data.ingest import IngestCollate
     full = parser.getDatasets(args, parser.getImagePath())
     train_uids, val_uids = split_uids(full.uids, args, seed)
-    args.ingest_collate = IngestCollate(device)
+    args.ingest_collate = IngestCollate(device, *parser.maskResample())
     return ImageDatasetByUIDs(full, train_uids[rank::world]), ImageDatasetByUIDs(full, val_uids)
 
 

@@ -99,6 +99,12 @@ class IngestDesc(Structure):
                 ("scan_inter", c_float), ("mask_slope", c_float), ("mask_inter", c_float)]
 
 
+class ResampleMaskDesc(Structure):
+    """mmnn_resample_mask_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("mx", c_int32), ("my", c_int32), ("mz", c_int32), ("mask_type", c_int32),
+                ("mask_slope", c_float), ("mask_inter", c_float), ("index_map", ctypes.c_double * 12), ("threshold", ctypes.c_double)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -191,6 +197,8 @@ def lib():
     L.mmnn_ingest_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.mmnn_ingest_volume.restype = c_int32
     L.mmnn_ingest_volume.argtypes = [POINTER(IngestDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_resample_mask.restype = c_int32
+    L.mmnn_resample_mask.argtypes = [POINTER(ResampleMaskDesc), c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

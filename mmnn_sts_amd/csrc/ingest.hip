@@ -14,6 +14,9 @@
 //                         x window a, divides by the window's voxel count and rounds once to fp32.
 // v is formed identically in passes A and C (`ingest_value`): a rounded multiply and a rounded add, never an FMA -- whether a voxel is
 // exactly zero decides which slices survive.
+//
+//   resample_mask_kernel  mmnn_resample_mask, a call of its own ahead of the three passes when the mask was drawn on another grid:
+//                         sitk.Resample(mask, image) with its defaults, then upstream's rebinarisation, to one byte per scan voxel.
 #include "../../include/mmnn_sts.h"
 #include "area.hpp"
 #include "common.hpp"
@@ -191,6 +194,103 @@ __global__ void __launch_bounds__(IG_TPB) ingest_area_kernel(const IgArgs a) {
   *dst = (float)(sum / count);
 }
 
+// ---- mask resample -------------------------------------------------------------------------------------------------------------
+// A mask drawn on another grid -> bytes on the scan's grid (the contract is the comment above mmnn_resample_mask in the header).
+// grid and block as pass A: lanes along x, VEC output voxels per lane, a wave = one row segment; the (j, k) part of the three mask
+// coordinates is formed once per row.  The mask is small and each of its voxels is gathered by up to 8 * (spacing ratio)^3 scan voxels:
+// plain cached loads.  Every output byte is written, with ordinary vector stores (one dword per lane when VEC = 4).
+struct RsArgs {
+  const void* mask;
+  uint8_t* out;
+  int X, Y, Z;                              // scan grid = output grid
+  int MX, MY, MZ;                           // mask grid
+  IgScale ms;
+  double T[12];                             // rows of the 3x4 scan-index -> mask-index matrix
+  double thr;
+};
+
+// SCALED: whether the mask's slope / inter apply (the same in every lane; a template parameter so that the unscaled kernel carries
+// neither the multiply-add nor the select)
+template <typename T, bool SCALED>
+__device__ __forceinline__ double rs_value(const T* m, unsigned idx, const IgScale& s) {
+  const double raw = (double)m[idx];
+  return SCALED ? __dadd_rn(__dmul_rn(raw, s.slope), s.inter) : raw;
+}
+
+template <typename T, bool SCALED>
+__device__ __forceinline__ uint8_t rs_voxel(const RsArgs& a, double cx, double cy, double cz) {
+  // ITK's buffer test on the continuous index (a NaN or infinite coordinate fails it)
+  const bool inside = cx >= -0.5 && cx < (double)a.MX - 0.5 && cy >= -0.5 && cy < (double)a.MY - 0.5 && cz >= -0.5 && cz < (double)a.MZ - 0.5;
+  if (!inside) return 0;
+  const double fx = floor(cx), fy = floor(cy), fz = floor(cz);
+  const double wx = cx - fx, wy = cy - fy, wz = cz - fz;
+  // neighbour indices clamped to the grid: inside, floor(c_r) lies in [-1, m_r - 1], so one bound each is left to apply.  Every
+  // element index is below mx * my * mz < 2^31, so 32-bit arithmetic holds it, and the four rows of the 2 x 2 x 2 neighbourhood
+  // differ from the first by 0 or one row (MX) and by 0 or one slice (MX * MY)
+  const int gx = (int)fx, gy = (int)fy, gz = (int)fz;
+  const int x0 = max(gx, 0), x1 = min(gx + 1, a.MX - 1);
+  const int y0 = max(gy, 0), y1 = min(gy + 1, a.MY - 1);
+  const int z0 = max(gz, 0), z1 = min(gz + 1, a.MZ - 1);
+  const unsigned row = (unsigned)(z0 * a.MY + y0) * (unsigned)a.MX;
+  const unsigned dy = y1 != y0 ? (unsigned)a.MX : 0u, dz = z1 != z0 ? (unsigned)a.MX * (unsigned)a.MY : 0u;
+  const unsigned rows[2][2] = {{row, row + dy}, {row + dz, row + dz + dy}};
+  const double ux[2] = {1.0 - wx, wx}, uy[2] = {1.0 - wy, wy}, uz[2] = {1.0 - wz, wz};
+  const T* m = static_cast<const T*>(a.mask);
+  // the eight-term blend, summed along x first: sum over (y, z) of uy uz (ux0 v0 + ux1 v1)
+  double acc = 0.0;
+#pragma unroll
+  for (int kz = 0; kz < 2; ++kz)
+#pragma unroll
+    for (int ky = 0; ky < 2; ++ky) {
+      const double v0 = rs_value<T, SCALED>(m, rows[kz][ky] + (unsigned)x0, a.ms), v1 = rs_value<T, SCALED>(m, rows[kz][ky] + (unsigned)x1, a.ms);
+      acc += uy[ky] * uz[kz] * (ux[0] * v0 + ux[1] * v1);
+    }
+  return acc > a.thr ? 1 : 0;               // a NaN blend compares false: 0
+}
+
+template <typename T, int VEC, bool SCALED>
+__device__ __forceinline__ void rs_rows(const RsArgs& a) {
+  const int x0 = (blockIdx.x * 64 + threadIdx.x) * VEC;
+  if (x0 >= a.X) return;                    // VEC > 1 only when X % VEC == 0: a group is inside or outside as a whole
+  const int R = a.Y * a.Z;
+  for (int r = blockIdx.y * IG_WAVES + threadIdx.y; r < R; r += gridDim.y * IG_WAVES) {
+    const double j = (double)(r % a.Y), k = (double)(r / a.Y);
+    const double bx = a.T[1] * j + a.T[2] * k + a.T[3];
+    const double by = a.T[5] * j + a.T[6] * k + a.T[7];
+    const double bz = a.T[9] * j + a.T[10] * k + a.T[11];
+    uint8_t b[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const double i = (double)(x0 + v);
+      b[v] = rs_voxel<T, SCALED>(a, a.T[0] * i + bx, a.T[4] * i + by, a.T[8] * i + bz);
+    }
+    uint8_t* dst = a.out + (long)r * a.X + x0;
+    if constexpr (VEC == 4) *reinterpret_cast<uint32_t*>(dst) = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+    else *dst = b[0];
+  }
+}
+
+template <int VEC, bool SCALED>
+__device__ __forceinline__ void rs_dispatch(const RsArgs& a, int code) {
+  switch (code) {
+    case 2:   rs_rows<uint8_t, VEC, SCALED>(a); break;
+    case 4:   rs_rows<int16_t, VEC, SCALED>(a); break;
+    case 8:   rs_rows<int32_t, VEC, SCALED>(a); break;
+    case 16:  rs_rows<float, VEC, SCALED>(a); break;
+    case 64:  rs_rows<double, VEC, SCALED>(a); break;
+    case 256: rs_rows<int8_t, VEC, SCALED>(a); break;
+    case 512: rs_rows<uint16_t, VEC, SCALED>(a); break;
+    default:  rs_rows<uint32_t, VEC, SCALED>(a); break;   // 768 (the host admits no other code)
+  }
+}
+
+// the type code and the scaling switch are the same in every lane: two uniform branches per kernel, none per voxel
+template <int VEC>
+__global__ void __launch_bounds__(IG_TPB) resample_mask_kernel(const RsArgs a, const int code) {
+  if (a.ms.on) rs_dispatch<VEC, true>(a, code);
+  else rs_dispatch<VEC, false>(a, code);
+}
+
 namespace {
 
 size_t ig_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -289,6 +389,38 @@ int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* 
   else MMNN_LAUNCH(ingest_flags_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a);
   MMNN_LAUNCH(ingest_scan_kernel, dim3(1), dim3(IG_SCAN_TPB), IG_SCAN_TPB * sizeof(int), stream, a);
   MMNN_LAUNCH(ingest_area_kernel, dim3(IG_S / IG_WAVES, IG_S), dim3(IG_TPB), (size_t)IG_WAVES * d->x * sizeof(double), stream, a);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
+int mmnn_resample_mask(const mmnn_resample_mask_desc* d, const void* mask, uint8_t* out, void* stream_) {
+  MMNN_REQUIRE(d, "resample_mask: null descriptor");
+  MMNN_REQUIRE(d->x >= 1 && d->y >= 1 && d->z >= 1, "resample_mask: non-positive scan extent %d x %d x %d", d->x, d->y, d->z);
+  MMNN_REQUIRE(d->mx >= 1 && d->my >= 1 && d->mz >= 1, "resample_mask: non-positive mask extent %d x %d x %d", d->mx, d->my, d->mz);
+  MMNN_REQUIRE((double)d->x * d->y * d->z < 2147483648.0, "resample_mask: scan extent %d x %d x %d holds 2^31 voxels or more", d->x, d->y, d->z);
+  MMNN_REQUIRE((double)d->mx * d->my * d->mz < 2147483648.0, "resample_mask: mask extent %d x %d x %d holds 2^31 voxels or more", d->mx, d->my, d->mz);
+  const int msz = ig_type_size(d->mask_type);
+  MMNN_REQUIRE(msz != 0, "resample_mask: unsupported mask datatype code %d (2, 4, 8, 16, 64, 256, 512, 768 are)", d->mask_type);
+  for (int i = 0; i < 12; ++i) MMNN_REQUIRE(std::isfinite(d->index_map[i]), "resample_mask: index_map[%d] is not finite", i);
+  MMNN_REQUIRE(std::isfinite(d->threshold), "resample_mask: the threshold is not finite");
+  MMNN_REQUIRE(mask && out, "resample_mask: null argument");
+  MMNN_REQUIRE((uintptr_t)mask % msz == 0, "resample_mask: mask buffer not aligned to its element size");
+  const hipStream_t stream = static_cast<hipStream_t>(stream_);
+  RsArgs a{};
+  a.mask = mask; a.out = out;
+  a.X = d->x; a.Y = d->y; a.Z = d->z;
+  a.MX = d->mx; a.MY = d->my; a.MZ = d->mz;
+  a.ms = ig_scale(d->mask_slope, d->mask_inter);
+  for (int i = 0; i < 12; ++i) a.T[i] = d->index_map[i];
+  a.thr = d->threshold;
+  // 4 voxels per lane and one dword store when every output row starts on a 4-byte boundary
+  const bool vec4 = d->x % 4 == 0 && (uintptr_t)out % 4 == 0;
+  const int gx = cdiv(d->x, 64 * (vec4 ? 4 : 1));
+  int gy = cdiv((long)d->y * d->z, IG_WAVES);
+  const int cap = cdiv(2048, gx);
+  if (gy > cap) gy = cap;
+  if (vec4) MMNN_LAUNCH(resample_mask_kernel<4>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a, d->mask_type);
+  else MMNN_LAUNCH(resample_mask_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a, d->mask_type);
   MMNN_HIP(hipGetLastError());
   return 0;
 }

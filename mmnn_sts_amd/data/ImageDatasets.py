@@ -8,8 +8,13 @@ csv (`ClinicalDatasets.LabelTable`), joined on `uid`.
 volume: masking, empty-slice removal, the 64^3 area resize and the T1 / T2 stacking happen on the device in the collate function
 (`mmnn_sts_amd.data.ingest.IngestCollate`), and upstream's train / validation transforms act on the collated batch (`--transforms`).
 `transforms`, `slices` are accepted for signature parity; a per-item transform cannot run on raw voxels and is refused.
+
+A mask whose extents differ from its scan's (drawn on another series, resliced, cropped to the tumour's bounding box) is accepted when
+both files carry a qform / sform: the collate function resamples it into the scan's grid on the device, as upstream's DICOM datasets do
+with `sitk.Resample(mask, image)` (:145-152).  `mask_resample` is the `Data:` key of that name: 'auto' (the default), 'geometry', 'never'.
 """
 import csv
+import logging
 import os
 
 import torch
@@ -17,8 +22,9 @@ import torch
 from ..exceptions.exceptions import ConfigurationError
 from . import nifti
 from .ClinicalDatasets import LabelTable
-from .ingest import RawPatient
+from .ingest import MASK_RESAMPLE_MODES, RawPatient
 
+logger = logging.getLogger(__name__)
 RADIOMICS_UID = 'MRN'
 ANON_ID = 'Anon MRN'
 
@@ -36,7 +42,10 @@ def _read_key(path):
 
 
 class ImageDataset(torch.utils.data.Dataset):
-    def __init__(self, patient_directory, patient_key):
+    def __init__(self, patient_directory, patient_key, mask_resample='auto', log_grids=True):
+        if mask_resample not in MASK_RESAMPLE_MODES:
+            raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
+        self.mask_resample = mask_resample
         self.patient_directory = str(patient_directory)
         self.patients = sorted(x for x in os.listdir(self.patient_directory)
                                if not x.startswith('.') and os.path.isdir(os.path.join(self.patient_directory, x)))
@@ -47,6 +56,11 @@ class ImageDataset(torch.utils.data.Dataset):
             if anon_id_of(p) not in self.patient_key:
                 raise ConfigurationError(f"patient directory {p} ({anon_id_of(p)}) has no row in the patient key {patient_key}")
             self._files(p)
+        # the headers alone: a mask on another grid needs both geometries, and is refused here rather than in the first epoch
+        self.other_grid = [p for p in self.patients if self._check_grids(p, *(nifti.read_geometry(f) + (f,) for f in self._files(p)))]
+        if log_grids and self.other_grid:
+            logger.info("%d of %d patients under %s have a mask on another grid than the scan's: it is resampled into the scan's grid on the device",
+                        len(self.other_grid), len(self.patients), self.patient_directory)
 
     def _uid_of(self, patient):
         return self.patient_key[anon_id_of(patient)]
@@ -72,9 +86,24 @@ class ImageDataset(torch.utils.data.Dataset):
     def _load(self, patient):
         scan_path, mask_path = self._files(patient)
         scan, mask = nifti.read(scan_path), nifti.read(mask_path)
-        if scan.shape != mask.shape or len(scan.shape) != 3:
-            raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): scan extent {scan.shape}, mask extent {mask.shape}")
+        self._check_grids(patient, (scan.shape, scan.affine, scan_path), (mask.shape, mask.affine, mask_path))
         return scan, mask
+
+    def _check_grids(self, patient, scan, mask):
+        """scan, mask: (extents, affine or None, path).  True when the mask's extents differ from the scan's and can be resampled."""
+        (sshape, saff, _), (mshape, maff, _) = scan, mask
+        what = f"patient {patient} (uid {self._uid_of(patient)}): scan extent {tuple(sshape)}, mask extent {tuple(mshape)}"
+        if len(sshape) != 3 or len(mshape) != 3:
+            raise ConfigurationError(what)
+        if tuple(sshape) == tuple(mshape):
+            return False
+        if self.mask_resample == 'never':
+            raise ConfigurationError(what + " (Data.mask_resample is 'never')")
+        if saff is None and maff is None:
+            raise ConfigurationError(what + " and neither file has a qform/sform to resample by")
+        if saff is None or maff is None:
+            raise ConfigurationError(what + f" and {scan[2] if saff is None else mask[2]} has no qform/sform to resample by")
+        return True
 
     def _index_of_uid(self, uid):
         for i, p in enumerate(self.patients):
@@ -89,8 +118,8 @@ class ImageDataset(torch.utils.data.Dataset):
 class _LabelledNifti(ImageDataset):
     survival = False
 
-    def __init__(self, patient_directory, clinical_data, patient_key, slices=False, transforms=None):
-        super().__init__(patient_directory, patient_key)
+    def __init__(self, patient_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', log_grids=True):
+        super().__init__(patient_directory, patient_key, mask_resample, log_grids)
         if slices:
             raise ConfigurationError("slices=True (2-D slices of a volume) is outside the MI355X path")
         if transforms is not None:
@@ -122,11 +151,11 @@ class NiftiSurvivalDataset(_LabelledNifti):
 
 
 class _T1T2(_LabelledNifti):
-    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None):
+    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto'):
         cls = NiftiSurvivalDataset if self.survival else NiftiImageDataset
-        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None)
-        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None)
-        super().__init__(t1_directory, clinical_data, patient_key, slices, transforms)
+        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None, mask_resample)
+        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None, mask_resample)
+        super().__init__(t1_directory, clinical_data, patient_key, slices, transforms, mask_resample, log_grids=False)   # (t1 has reported)
         self.t1_patients, self.t2_patients = self.t1_dataset.patients, self.t2_dataset.patients
         # patients common to both trees, by anonymised id; kept as the T1 directory names
         in_t2 = {anon_id_of(p): p for p in self.t2_patients}

@@ -5,9 +5,15 @@ every all-zero slice dropped along each axis, Resize((64,64,64)), T1 / T2 stacke
 the file's voxels in their on-disk type.  The host only uploads bytes (pinned, non-blocking) and enqueues; it never waits.
 
     upload(volume, device)                          host volume (NiftiImage or ndarray) -> DeviceVolume
-    ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane
+    resample_mask(mask, scan_shape, index_map)      a mask drawn on another grid -> uint8 bytes on the scan's grid (mmnn_resample_mask)
+    ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
     collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
     IngestCollate(device)                           the DataLoader collate_fn of the NIfTI datasets
+
+A mask on another grid (a T2 contour used on the T1 scan, a resliced export, a mask cropped to the tumour's bounding box) is what
+upstream's DICOM datasets pass through `sitk.Resample(mask, image)` and `> 128` (data/ImageDatasets.py:145-152, :246-257); here the
+host forms one 3x4 matrix from the two headers (`nifti.index_map`) and the device does the rest.  `Data: mask_resample` selects when:
+'auto' (only when the extents differ), 'geometry' (also when equal extents sit elsewhere in space), 'never'.
 """
 import ctypes
 from dataclasses import dataclass
@@ -17,9 +23,13 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..exceptions.exceptions import ConfigurationError
+from . import nifti
 from .nifti import NiftiImage
 
 SIZE = 64                                    # MMNN_INGEST_SIZE
+MASK_RESAMPLE_MODES = ("auto", "geometry", "never")
+GEOMETRY_TOLERANCE = 1e-3                    # voxels: 'geometry' resamples when a corner of the scan grid maps further from itself
 TYPE_CODES = {np.dtype("uint8"): 2, np.dtype("int16"): 4, np.dtype("int32"): 8, np.dtype("float32"): 16, np.dtype("float64"): 64,
               np.dtype("int8"): 256, np.dtype("uint16"): 512, np.dtype("uint32"): 768}
 
@@ -27,12 +37,13 @@ TYPE_CODES = {np.dtype("uint8"): 2, np.dtype("int16"): 4, np.dtype("int32"): 8, 
 @dataclass
 class DeviceVolume:
     """A scan's voxels on the device as the file holds them: `data` is a flat uint8 tensor of x*y*z elements of NIfTI type `datatype`,
-    x fastest."""
+    x fastest.  `affine`: the file's voxel index -> mm matrix when it has one."""
     data: torch.Tensor
     shape: Tuple[int, int, int]
     datatype: int
     slope: float = 1.0
     inter: float = 0.0
+    affine: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -55,14 +66,15 @@ def upload(volume, device, slope: float = 1.0, inter: float = 0.0) -> DeviceVolu
     """Host -> device, in the on-disk type.  `volume`: a NiftiImage (its slope / inter are used) or an (x, y, z) ndarray."""
     if isinstance(volume, DeviceVolume):
         return volume
+    affine = None
     if isinstance(volume, NiftiImage):
-        raw, slope, inter = volume.raw, volume.slope, volume.inter
+        raw, slope, inter, affine = volume.raw, volume.slope, volume.inter, volume.affine
     else:
         raw = np.asarray(volume)
     if not raw.dtype.isnative:
         raw = raw.astype(raw.dtype.newbyteorder("="))
     host = torch.from_numpy(_host_bytes(raw)).pin_memory()
-    return DeviceVolume(host.to(device, non_blocking=True), tuple(int(s) for s in raw.shape), TYPE_CODES[raw.dtype], float(slope), float(inter))
+    return DeviceVolume(host.to(device, non_blocking=True), tuple(int(s) for s in raw.shape), TYPE_CODES[raw.dtype], float(slope), float(inter), affine)
 
 
 def workspace_bytes(x: int, y: int, z: int) -> int:
@@ -72,16 +84,77 @@ def workspace_bytes(x: int, y: int, z: int) -> int:
     return int(n)
 
 
-def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+def resample_mask(mask, scan_shape, index_map, threshold: float = 0.5, out: Optional[torch.Tensor] = None) -> DeviceVolume:
+    """Enqueue `mmnn_resample_mask` on the current stream: the mask, drawn on a grid of its own, as uint8 0 / 1 on the scan's grid
+    (trilinear blend of the scaled mask voxels in fp64, 1 where it exceeds `threshold`, 0 outside the mask's grid).  `index_map`:
+    (3, 4), scan voxel index -> continuous mask index (`nifti.index_map`).  `mask`: DeviceVolume, or a host volume (uploaded to
+    `out`'s device, else the current one); `out`: a contiguous uint8 CUDA tensor of x*y*z elements to write, allocated when None."""
+    x, y, z = (int(v) for v in scan_shape)
+    t = np.ascontiguousarray(np.asarray(index_map, dtype=np.float64))
+    if t.shape != (3, 4):
+        raise ValueError(f"resample_mask: index_map must be (3, 4), got {t.shape}")
+    if not isinstance(mask, DeviceVolume):
+        mask = upload(mask, out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    dev = mask.data.device
+    if min(x, y, z) >= 1:
+        if out is None:
+            out = torch.empty(x * y * z, dtype=torch.uint8, device=dev)
+        elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x * y * z):
+            raise ValueError(f"resample_mask: out must be {x * y * z} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    mx, my, mz = mask.shape
+    desc = _lib.ResampleMaskDesc(x, y, z, mx, my, mz, mask.datatype, mask.slope, mask.inter, (ctypes.c_double * 12)(*t.reshape(-1)), float(threshold))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mmnn_resample_mask(ctypes.byref(desc), mask.data.data_ptr(), out.data_ptr() if out is not None else None, stream),
+                   "mmnn_resample_mask")
+    return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0)
+
+
+def moved(scan_shape, index_map, tolerance: float = GEOMETRY_TOLERANCE) -> bool:
+    """Whether a corner of the scan grid maps more than `tolerance` voxels away from itself under `index_map` (equal extents that do
+    not sit on the same grid in space)."""
+    t = np.asarray(index_map, dtype=np.float64)
+    for corner in np.ndindex(2, 2, 2):
+        p = np.array([c * (n - 1) for c, n in zip(corner, scan_shape)], dtype=np.float64)
+        if np.linalg.norm(t[:, :3] @ p + t[:, 3] - p) > tolerance:
+            return True
+    return False
+
+
+def mask_index_map(scan, mask, mode: str = "auto"):
+    """The index map to resample `mask` by under `Data: mask_resample` = `mode`, or None for the voxelwise path.  `scan`, `mask`:
+    anything with `.shape` and `.affine`.  Raises ConfigurationError where `mode` or the missing geometry forbids a needed resample."""
+    if mode not in MASK_RESAMPLE_MODES:
+        raise ConfigurationError(f"mask_resample {mode!r} is none of {MASK_RESAMPLE_MODES}")
+    same = tuple(scan.shape) == tuple(mask.shape)
+    if same:
+        if mode != "geometry" or scan.affine is None or mask.affine is None:
+            return None
+        t = nifti.index_map(scan, mask)
+        return t if moved(scan.shape, t) else None
+    if mode == "never":
+        raise ConfigurationError(f"scan extent {tuple(scan.shape)} differs from the mask's {tuple(mask.shape)} and mask_resample is 'never'")
+    return nifti.index_map(scan, mask)
+
+
+def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                  index_map=None, threshold: float = 0.5) -> torch.Tensor:
     """Enqueue the ingest of one volume on the current stream: `out_plane` (a contiguous (64,64,64) fp32 CUDA view, e.g. batch[n, c]) receives
     the masked, compacted, area-resized scan; returns `extents` (3 x int32 on the device: kept slices along x, y, z), readable after
-    the next synchronisation.  `scan` / `mask`: DeviceVolume, NiftiImage or ndarray (host volumes are uploaded first)."""
+    the next synchronisation.  `scan` / `mask`: DeviceVolume, NiftiImage or ndarray (host volumes are uploaded first).  When the
+    extents differ, or an `index_map` is given, the mask is first resampled into the scan's grid (`resample_mask`, binarised at
+    `threshold`); without `index_map` the map comes from the two volumes' affines, and differing extents without them are refused.
+    Equal extents without `index_map` are the voxelwise path."""
     if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and tuple(out_plane.shape) == (SIZE,) * 3):
         raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, got {tuple(out_plane.shape)} {out_plane.dtype} on {out_plane.device}")
     dev = out_plane.device
     scan, mask = upload(scan, dev), upload(mask, dev)
-    if scan.shape != mask.shape:
-        raise ValueError(f"ingest: scan extent {scan.shape} differs from the mask's {mask.shape}")
+    if index_map is None and scan.shape != mask.shape:
+        if scan.affine is None or mask.affine is None:
+            raise ValueError(f"ingest: scan extent {scan.shape} differs from the mask's {mask.shape}")
+        index_map = nifti.index_map(scan, mask)
+    if index_map is not None:
+        mask = resample_mask(mask, scan.shape, index_map, threshold)
     if extents is None:
         extents = torch.empty(3, dtype=torch.int32, device=dev)
     if not (extents.is_cuda and extents.dtype == torch.int32 and extents.is_contiguous() and extents.numel() == 3):
@@ -100,19 +173,22 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     return extents
 
 
-def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device) -> Tuple[torch.Tensor, torch.Tensor]:
+def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
+                    mask_threshold: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
     """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
-    issued before the first kernel, so the copies of one volume run beside the passes of the one before it."""
+    issued before the first kernel, so the copies of one volume run beside the passes of the one before it.  A mask on another grid
+    than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`."""
     n, c = len(patients), len(patients[0])
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
     device = torch.device(device)
     up = [[(upload(s, device), upload(m, device)) for s, m in p] for p in patients]
+    maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     batch = torch.empty((n, c, SIZE, SIZE, SIZE), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)
     for i in range(n):
         for j in range(c):
-            ingest_volume(up[i][j][0], up[i][j][1], batch[i, j], extents[i, j])
+            ingest_volume(up[i][j][0], up[i][j][1], batch[i, j], extents[i, j], index_map=maps[i][j], threshold=mask_threshold)
     return batch, extents
 
 
@@ -120,10 +196,13 @@ class IngestCollate:
     """collate_fn of the NIfTI datasets: items are (x, events, durations) or (x, labels) with x a RawPatient or
     {'image': RawPatient, 'clinical': tensor}; returns (x, events, durations) (durations None for classification items) with the image
     batch on `device`.  The extents of every batch are kept in `pending` until `take_empty()` reads them: call it where the epoch
-    synchronises anyway, never per batch."""
+    synchronises anyway, never per batch.  `mask_resample` / `mask_threshold`: the `Data:` keys of the same names (see `collate_volumes`)."""
 
-    def __init__(self, device):
+    def __init__(self, device, mask_resample: str = "auto", mask_threshold: float = 0.5):
+        if mask_resample not in MASK_RESAMPLE_MODES:
+            raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         self.device = torch.device(device)
+        self.mask_resample, self.mask_threshold = mask_resample, float(mask_threshold)
         self.pending: List[Tuple[List[int], torch.Tensor]] = []
 
     def __call__(self, items):
@@ -131,7 +210,7 @@ class IngestCollate:
         targets = [torch.stack([torch.as_tensor(it[k]) for it in items]) for k in range(1, len(items[0]))]
         multimodal = isinstance(xs[0], dict)
         raws = [x["image"] for x in xs] if multimodal else xs
-        batch, extents = collate_volumes([r.volumes for r in raws], self.device)
+        batch, extents = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold)
         self.pending.append(([r.uid for r in raws], extents))
         x = {"image": batch, "clinical": torch.stack([x["clinical"] for x in xs]).float()} if multimodal else batch
         return (x, targets[0], targets[1] if len(targets) > 1 else None)

@@ -8,8 +8,11 @@ tool and a first run of `main.py --image_loc` before it is pointed at patients.
     <root>/train_uids.txt, <root>/val_uids.txt                        one uid per line
 
 Extents are ragged (drawn per patient and shared by its modalities); every mask has at least one interior empty slice along each axis.
+With `mask_grid="own"` every mask is written on a grid of its own -- other extents, coarser spacing, a small rotation and an offset
+against the scan, whose affine is not the identity either -- as a contour drawn on another series arrives; the datasets then resample
+it into the scan's grid on the device.
 
-    python -m mmnn_sts_amd.data.synth_nifti /tmp/syn --patients 8
+    python -m mmnn_sts_amd.data.synth_nifti /tmp/syn --patients 8 [--mask_grid own]
 """
 import argparse
 import os
@@ -44,11 +47,47 @@ def synth_scan(shape, rng):
     return (100.0 + ramp + rng.integers(0, 400, shape)).astype(np.int16)
 
 
+def _rot_z(angle):
+    c, s = np.cos(angle), np.sin(angle)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def _affine(linear, offset):
+    a = np.eye(4)
+    a[:3, :3], a[:3, 3] = linear, offset
+    return a
+
+
+def own_grid(mask, rng):
+    """(mask on a grid of its own, scan affine, mask affine): the scan grid gets 0.9 x 0.9 x 3 mm voxels, a small rotation and an offset;
+    the mask grid is coarser by 1.15-1.45 per axis, rotated a little further about the volume's centre, and its extents differ from
+    the scan's on every axis.  The mask's voxels are the scan-grid mask at the nearest scan voxel (0 outside)."""
+    shape = np.asarray(mask.shape)
+    scan_affine = _affine(_rot_z(rng.uniform(-0.08, 0.08)) @ np.diag([0.9, 0.9, 3.0]), rng.uniform(-80.0, 80.0, 3))
+    factor = rng.uniform(1.15, 1.45, 3)
+    own = np.ceil(shape / factor).astype(int) + 1
+    own += own == shape
+    # mask index -> scan index: about the two centres, a rotation in the (x, y) plane and the coarser spacing
+    lin = _rot_z(rng.uniform(-0.06, 0.06)) @ np.diag(factor)
+    to_scan = _affine(lin, (shape - 1) / 2.0 + rng.uniform(-0.4, 0.4, 3) - lin @ ((own - 1) / 2.0))
+    idx = np.stack(np.meshgrid(*[np.arange(n, dtype=np.float64) for n in own], indexing="ij"), axis=-1)
+    at = np.rint(idx @ to_scan[:3, :3].T + to_scan[:3, 3]).astype(int)
+    inside = ((at >= 0) & (at < shape)).all(axis=-1)
+    at = np.clip(at, 0, shape - 1)
+    out = np.where(inside, mask[at[..., 0], at[..., 1], at[..., 2]], 0).astype(mask.dtype)
+    return out, scan_affine, scan_affine @ to_scan
+
+
 def write_tree(root, n_patients=6, seed=0, predictors=None, extent=((24, 40), (24, 40), (10, 20)), modalities=("t1", "t2"),
-               empty_mask_uids=(), val_fraction=0.34, gz=True):
-    """Write the tree; returns {'image_loc', 't1_path', 't2_path', 'key_loc', 'data_loc', 'train_uids', 'val_uids', 'uids'}."""
+               empty_mask_uids=(), val_fraction=0.34, gz=True, mask_grid="same"):
+    """Write the tree; returns {'image_loc', 't1_path', 't2_path', 'key_loc', 'data_loc', 'train_uids', 'val_uids', 'uids'}.
+    `mask_grid`: 'same' (mask and scan share one grid and the identity affine) or 'own' (see `own_grid`; its draws come from a
+    generator of their own, so scans, masks on the scan grid and labels are those of 'same')."""
+    if mask_grid not in ("same", "own"):
+        raise ValueError(f"mask_grid {mask_grid!r} is neither 'same' nor 'own'")
     root = str(root)
     rng = np.random.default_rng(seed)
+    grid_rng = np.random.default_rng([int(seed), 1])
     predictors = [f"predictor{i}" for i in range(32)] if predictors is None else list(predictors)
     uids = [1000 + 7 * i for i in range(n_patients)]
     image_loc = os.path.join(root, "images")
@@ -61,8 +100,11 @@ def write_tree(root, n_patients=6, seed=0, predictors=None, extent=((24, 40), (2
             mask = ellipsoid_mask(shape, rng)
             if uid in empty_mask_uids:
                 mask[:] = 0
-            nifti.write(os.path.join(d, f"scan_{mod}{ext}"), synth_scan(shape, rng), SCAN_SLOPE, SCAN_INTER)
-            nifti.write(os.path.join(d, f"mask{ext}"), mask)
+            scan_affine = mask_affine = None
+            if mask_grid == "own":
+                mask, scan_affine, mask_affine = own_grid(mask, grid_rng)
+            nifti.write(os.path.join(d, f"scan_{mod}{ext}"), synth_scan(shape, rng), SCAN_SLOPE, SCAN_INTER, affine=scan_affine)
+            nifti.write(os.path.join(d, f"mask{ext}"), mask, affine=mask_affine)
     key = os.path.join(root, "key.csv")
     with open(key, "w") as f:
         f.write("Anon MRN,MRN\n")
@@ -91,6 +133,7 @@ if __name__ == "__main__":
     ap.add_argument("root")
     ap.add_argument("--patients", type=int, default=6)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--mask_grid", choices=("same", "own"), default="same", help="own: every mask on a grid of its own, to be resampled")
     a = ap.parse_args()
-    for k, v in write_tree(a.root, a.patients, a.seed).items():
+    for k, v in write_tree(a.root, a.patients, a.seed, mask_grid=a.mask_grid).items():
         print(f"{k}: {v}")

@@ -5,7 +5,7 @@ TinyDensenet and wraps it into `MultiModalModel` for `--images --preop|--postop`
 Fixes: `--preop` alone yields the standalone clinical MLP; the predictor list may be given as an
 integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  `getImagePath()` / `getDatasets(args, image_path)` (parser.py:43-97,
 184-198) build the local-disk NIfTI datasets from the `Data:` section (`image_loc`, `t1_path`, `t2_path`, `data_loc`, `key_loc`; the
-command-line flags override it); S3, DICOM and radiomics datasets stay outside the path, and main.py substitutes synthetic patients when
+command-line flags override it; `mask_resample`, `mask_threshold` say what happens to a mask drawn on another grid than its scan's); S3, DICOM and radiomics datasets stay outside the path, and main.py substitutes synthetic patients when
 no image location is configured.
 """
 import os
@@ -72,6 +72,25 @@ class Parser:
             raise ConfigurationError('Data.{0} is not configured (config `Data: {0}:` or --{0})'.format(key))
         return value
 
+    def maskResample(self):
+        """(`Data: mask_resample`, `Data: mask_threshold`), defaults ('auto', 0.5).  'auto': a mask whose extents differ from its scan's
+        is resampled into the scan's grid on the device (both files need a qform / sform), equal extents are multiplied voxelwise;
+        'geometry': also resampled when equal extents sit elsewhere in space (a corner of the scan grid maps more than 1e-3 voxel away
+        from itself); 'never': differing extents are refused.  The threshold binarises the interpolated mask: 0.5 for 0/1 masks, 128
+        (upstream's value) for 0/255 masks."""
+        from ..data.ingest import MASK_RESAMPLE_MODES
+        data = self.config.get('Data') or {}
+        mode = str(data.get('mask_resample', 'auto')).lower()
+        if mode not in MASK_RESAMPLE_MODES:
+            raise ConfigurationError('Data.mask_resample {!r} is none of {}'.format(data.get('mask_resample'), ', '.join(MASK_RESAMPLE_MODES)))
+        try:
+            threshold = float(data.get('mask_threshold', 0.5))
+        except (TypeError, ValueError):
+            threshold = float('nan')
+        if threshold != threshold or threshold in (float('inf'), float('-inf')):
+            raise ConfigurationError('Data.mask_threshold {!r} is not a finite number'.format(data.get('mask_threshold')))
+        return mode, threshold
+
     def getImagePath(self):
         """parser/parser.py:184-198: the modality's directory under image_loc; a (t1, t2) tuple for 't1t2'."""
         modality = self.config['ImageModel']['modality'].lower()
@@ -98,7 +117,7 @@ class Parser:
             else:
                 cls = T1T2ImageDataset if both else NiftiImageDataset
             paths = image_path if both else (image_path,)
-            datasets.append(cls(*paths, self._data('data_loc'), self._data('key_loc')))
+            datasets.append(cls(*paths, self._data('data_loc'), self._data('key_loc'), mask_resample=self.maskResample()[0]))
         if len(datasets) == 1:
             return datasets[0]
         return MultiModalSurvivalDataset(datasets) if args.survival else MultiModalDataset(datasets)

@@ -1,0 +1,219 @@
+"""The device mask resample (`mmnn_resample_mask`, csrc/ingest.hip; `ingest.resample_mask`) against the fp64 restatement of its contract
+in tests/_resample_ref.py, alone and through `ingest_volume`, the collate function and `main.py --image_loc` on a tree whose masks sit on
+grids of their own.
+
+Exactness rule: the device bytes equal the restatement's at EVERY voxel.  The comparison is discontinuous (a threshold, an inside test),
+so each test first asserts on the restatement alone that no blend lies within 1e-9 max(1, |threshold|) of the threshold, no coordinate
+within 1e-9 of -0.5 or m_r - 0.5, and that the result is neither empty nor full (`_resample_ref.assert_comparable`).  The bound is
+derived: an fp64 trilinear blend of values <= V errs by <~ 2e-15 V and a coordinate by <~ 1e-13 voxel at these extents, four orders of
+magnitude below it.  Through the ingest the existing bound holds: extents exactly equal, the plane within 2 * 2^-24 * max|v|."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from mmnn_sts_amd.data import ingest, nifti, synth_nifti
+from tests import _ingest_ref as R
+from tests import _resample_ref as G
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda:0"
+GUARD = 256
+PATTERN = 0xA5
+SENTINEL = 1.0e30
+
+
+def _device_bytes(mask, scan_shape, T, threshold=0.5, slope=1.0, inter=0.0, lead=GUARD):
+    """The kernel's bytes as an (x, y, z) array; the output sits inside a larger buffer whose other bytes must keep their pattern."""
+    n = int(np.prod(scan_shape))
+    buf = torch.full((lead + n + GUARD,), PATTERN, dtype=torch.uint8, device=DEV)
+    vol = ingest.resample_mask(ingest.upload(mask, DEV, slope, inter), scan_shape, T, threshold, out=buf[lead:lead + n])
+    torch.cuda.synchronize()
+    assert vol.shape == tuple(scan_shape) and vol.datatype == 2 and (vol.slope, vol.inter) == (1.0, 0.0) and vol.data.data_ptr() == buf.data_ptr() + lead
+    b = buf.cpu().numpy()
+    assert (b[:lead] == PATTERN).all() and (b[lead + n:] == PATTERN).all(), "bytes outside `out` were written"
+    return b[lead:lead + n].reshape(scan_shape, order="F")
+
+
+def _check(name, mask, threshold=0.5, slope=1.0, inter=0.0, label=None):
+    scan_shape, mask_shape, _, _, T = G.case(name)
+    want, m, c = G.resample_ref(mask, scan_shape, T, threshold, slope, inter)
+    G.assert_comparable(want, m, c, mask_shape, threshold, label or f"case {name}")
+    got = _device_bytes(mask, scan_shape, T, threshold, slope, inter)
+    bad = np.argwhere(got != want)
+    assert bad.shape[0] == 0, f"{bad.shape[0]} voxels differ, the first at {tuple(bad[0])}: device {got[tuple(bad[0])]}, blend {m[tuple(bad[0])]!r}"
+    return got, want, m
+
+
+@pytest.mark.parametrize("name", sorted(G.CASES))
+def test_bytes_equal_the_restatement(name):
+    got, _, _ = _check(name, G.ellipsoid(G.CASES[name][1], 40))
+    assert set(np.unique(got)) == {0, 1}
+
+
+def test_int16_0_255_mask_at_128():
+    _check("A", G.ellipsoid(G.CASES["A"][1], 40, dtype="i2", value=255), threshold=128.0, label="case A, int16 0/255 at 128")
+
+
+def test_float32_mask_with_its_own_slope():
+    _check("A", G.ellipsoid(G.CASES["A"][1], 40, dtype="f4", value=2), slope=0.5, inter=0.0, label="case A, float32 0/2, slope 0.5")
+
+
+def test_nan_voxel_clears_its_neighbourhood():
+    mask = G.ellipsoid(G.CASES["A"][1], 40, holes=0.0, dtype="f4")
+    _, before, _ = _check("A", mask, label="case A, float32 without holes")
+    at = (6, 8, 5)
+    assert mask[at] == 1.0 and mask[5:8, 7:10, 4:7].all()                                   # well inside the ellipsoid
+    mask[at] = np.nan
+    _, after, m = _check("A", mask, label="case A, one NaN voxel")
+    lost = (before == 1) & (after == 0)
+    assert np.array_equal(lost, np.isnan(m) & (before == 1)) and lost.sum() > 0             # every voxel that gathers the NaN comes out 0
+    assert not ((before == 0) & (after == 1)).any()
+
+
+def test_pure_crop_pastes_the_mask():
+    scan_shape, _, SA, _, _ = G.case("A")
+    mask_shape, off = (9, 8, 7), (4, 3, 2)
+    MA = SA.copy()
+    MA[:3, 3] = (SA @ np.array([*off, 1.0]))[:3]
+    T = G.index_map(SA, MA)
+    mask = G.ellipsoid(mask_shape, 41)
+    want = np.zeros(scan_shape, dtype=np.uint8)
+    want[off[0]:off[0] + 9, off[1]:off[1] + 8, off[2]:off[2] + 7] = mask
+    ref, m, c = G.resample_ref(mask, scan_shape, T)
+    G.assert_comparable(ref, m, c, mask_shape, 0.5, "pure crop")
+    assert np.array_equal(ref, want)
+    assert np.array_equal(_device_bytes(mask, scan_shape, T), want)
+
+
+def test_a_mask_that_misses_the_scan_gives_zeros():
+    scan_shape, mask_shape, SA, MA, _ = G.case("A")
+    far = MA.copy()
+    far[:3, 3] += (500.0, -300.0, 200.0)
+    T = G.index_map(SA, far)
+    mask = G.ellipsoid(mask_shape, 40)
+    ref, m, c = G.resample_ref(mask, scan_shape, T)
+    assert not ref.any() and np.isnan(m).all()
+    assert not _device_bytes(mask, scan_shape, T).any()
+    plane = torch.full((64, 64, 64), SENTINEL, device=DEV)
+    rng = np.random.default_rng(50)
+    ext = ingest.ingest_volume(R.random_scan(rng, scan_shape, 4), mask, plane, index_map=T)
+    torch.cuda.synchronize()
+    assert ext.cpu().tolist() == [0, 0, 0] and not plane.cpu().numpy().any()
+
+
+def test_two_calls_are_bit_identical_and_only_out_is_written():
+    for name, lead in (("A", GUARD), ("A", GUARD + 1), ("E", GUARD), ("E", GUARD + 3)):      # dword stores, then byte stores (x % 4, alignment)
+        scan_shape, mask_shape, _, _, T = G.case(name)
+        mask = G.ellipsoid(mask_shape, 40)
+        first = _device_bytes(mask, scan_shape, T, lead=lead)
+        assert np.array_equal(first, _device_bytes(mask, scan_shape, T, lead=lead))
+        assert np.array_equal(first, G.resample_ref(mask, scan_shape, T)[0])
+    with pytest.raises(ValueError):
+        ingest.resample_mask(ingest.upload(mask, DEV), scan_shape, T, out=torch.empty(7, dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError):
+        ingest.resample_mask(ingest.upload(mask, DEV), scan_shape, np.eye(4))
+    with pytest.raises(ValueError, match="not finite"):
+        ingest.resample_mask(ingest.upload(mask, DEV), scan_shape, T * np.inf)
+
+
+@pytest.mark.parametrize("name", ["A", "E"])
+def test_ingest_volume_resamples_then_ingests(name):
+    scan_shape, mask_shape, _, _, T = G.case(name)
+    rng = np.random.default_rng(60)
+    scan, mask = R.random_scan(rng, scan_shape, 4), G.ellipsoid(mask_shape, 40)
+    restated, m, c = G.resample_ref(mask, scan_shape, T)
+    G.assert_comparable(restated, m, c, mask_shape, 0.5, f"case {name}")
+    ref, ext_ref, v = R.ingest_ref(scan, restated, (0.5, 3.0))
+    batch = torch.full((2, 2, 64, 64, 64), SENTINEL, device=DEV)
+    ext = ingest.ingest_volume(ingest.upload(scan, DEV, 0.5, 3.0), ingest.upload(mask, DEV), batch[1, 0], index_map=T)
+    torch.cuda.synchronize()
+    b = batch.cpu()
+    err, tol = float(np.abs(b[1, 0].double().numpy() - ref).max()), R.tolerance(v)
+    print(f"case {name}: extents {ext.cpu().tolist()} (ref {ext_ref}), max error {err:.3e}, bound {tol:.3e}")
+    assert tuple(ext.cpu().tolist()) == ext_ref and min(ext_ref) > 0
+    assert err <= tol
+    assert (b[0] == SENTINEL).all() and (b[1, 1] == SENTINEL).all() and not (b[1, 0] == SENTINEL).any()
+    with pytest.raises(ValueError, match="extent"):                                         # no map given and none to be formed
+        ingest.ingest_volume(ingest.upload(scan, DEV), ingest.upload(mask, DEV), batch[0, 0])
+
+
+def test_collate_on_an_own_grid_tree_equals_the_single_volume_results(tmp_path):
+    from mmnn_sts_amd.data.ImageDatasets import T1T2SurvivalDataset
+    tree = synth_nifti.write_tree(tmp_path, n_patients=2, seed=22, mask_grid="own")
+    ds = T1T2SurvivalDataset(os.path.join(tree["image_loc"], "t1"), os.path.join(tree["image_loc"], "t2"), tree["data_loc"], tree["key_loc"])
+    coll = ingest.IngestCollate(DEV)
+    x, ev, du = coll([ds[0], ds[1]])
+    assert x.shape == (2, 2, 64, 64, 64) and x.dtype == torch.float32 and x.is_cuda
+    _, ext = coll.pending[0]
+    for n in range(2):
+        for ch, (scan, mask) in enumerate(ds[n][0].volumes):
+            assert scan.shape != mask.shape
+            single = torch.empty((64, 64, 64), device=DEV)
+            e = ingest.ingest_volume(scan, mask, single)                                    # the map comes from the two affines
+            assert torch.equal(single, x[n, ch]) and torch.equal(e, ext[n, ch])              # bit for bit
+            T = G.index_map(G.parse_affine(G.file_bytes(scan.path)), G.parse_affine(G.file_bytes(mask.path)))
+            restated, m, c = G.resample_ref(mask.raw, scan.shape, T)
+            G.assert_comparable(restated, m, c, mask.shape, 0.5, f"patient {n}, channel {ch}")
+            ref, e_ref, v = R.ingest_ref(scan.raw, restated, (scan.slope, scan.inter))
+            assert tuple(e.tolist()) == e_ref and min(e_ref) > 0
+            assert np.abs(single.cpu().double().numpy() - ref).max() <= R.tolerance(v)
+    assert coll.take_empty() == []
+    with pytest.raises(Exception, match="never"):
+        ingest.IngestCollate(DEV, mask_resample="never")([ds[0], ds[1]])
+
+
+def test_geometry_mode_resamples_an_equal_extent_pair():
+    scan_shape, _, SA, _, _ = G.case("A")
+    MA = SA.copy()
+    MA[:3, 3] = (SA @ np.array([1.3, -0.7, 0.4, 1.0]))[:3]                                  # the same grid, shifted by a fraction of a voxel
+    rng = np.random.default_rng(70)
+    scan = nifti.NiftiImage(R.random_scan(rng, scan_shape, 4), 4, 0.5, 3.0, "scan.nii", SA)
+    mask = nifti.NiftiImage(G.ellipsoid(scan_shape, 42), 2, 1.0, 0.0, "mask.nii", MA)
+    auto, ext_auto = ingest.collate_volumes([[(scan, mask)]], DEV)
+    geom, ext_geom = ingest.collate_volumes([[(scan, mask)]], DEV, mask_resample="geometry")
+    torch.cuda.synchronize()
+    ref_auto, e_auto, v = R.ingest_ref(scan.raw, mask.raw, (0.5, 3.0))
+    assert tuple(ext_auto[0, 0].tolist()) == e_auto and np.abs(auto[0, 0].cpu().double().numpy() - ref_auto).max() <= R.tolerance(v)
+    restated, m, c = G.resample_ref(mask.raw, scan_shape, G.index_map(SA, MA))
+    G.assert_comparable(restated, m, c, scan_shape, 0.5, "shifted equal-extent mask")
+    ref, e_ref, v = R.ingest_ref(scan.raw, restated, (0.5, 3.0))
+    assert tuple(ext_geom[0, 0].tolist()) == e_ref and np.abs(geom[0, 0].cpu().double().numpy() - ref).max() <= R.tolerance(v)
+    assert not torch.equal(auto, geom)
+
+
+# ---- main.py --image_loc on masks with grids of their own: fresh processes, one at a time ----------------------------------------------
+def _main(args, out):
+    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return r.stdout + r.stderr
+
+
+def test_cli_trains_and_infers_on_own_grid_masks(tmp_path):
+    import yaml
+    tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=4, seed=34, mask_grid="own")
+    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
+                          "in_channels": 2, "dropout_prob": 0.2},
+           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
+           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
+    (tmp_path / "config.yaml").write_text(yaml.safe_dump(cfg))
+    loc = ["--config", str(tmp_path / "config.yaml"), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+           "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
+    log = _main(["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1", *loc], tmp_path)
+    assert "epoch 1/1" in log and "4 of 4 patients" in log and "another grid" in log
+    log = _main(["--inference", "--images", "--preop", "--survival", "--transforms", "--weights", str(tmp_path / "best_surv_model.pth"), *loc], tmp_path)
+    assert "All C-indexes" in log
+    val_uids = [int(l) for l in open(tree["val_uids"]).read().split()]
+    assert val_uids
+    for uid in val_uids:
+        d = tmp_path / "attention_maps" / f"_patient_{uid}"
+        for name in ("t1image", "t2image", "att_map"):
+            h = R.read_nifti_file(d / f"{name}.nii.gz")
+            assert h["dim"][:4] == (3, 64, 64, 64) and np.isfinite(h["data"]).all()
+        assert R.read_nifti_file(d / "t1image.nii.gz")["data"].any()                        # the resampled mask left something of the scan

@@ -3,13 +3,17 @@
 warm-up and the calls queued back to back behind a spin kernel (device time alone), beside the host's share per volume: gunzip + parse
 of the two .nii.gz files and the pinned upload.
 
-    python tools/ingest_time.py [--steps 50] [--warmup 10] [--case NAME] [--json out.json] [--kernel_stats kernel_stats.csv]
+    python tools/ingest_time.py [--steps 50] [--warmup 10] [--case NAME] [--mask_grid own] [--json out.json] [--kernel_stats kernel_stats.csv]
 
 Cases: 512 x 512 x 48 int16 scan + uint8 mask with a 320 x 310 x 39 box; 256 x 256 x 40 with the mask covering everything.  Bytes are the
 algorithmic HBM traffic computed from the shapes -- pass A reads every scan and mask byte once, pass C reads the kept box once, 1 MB is
 written -- priced against the 6.29 TB/s measured HBM ceiling of the MI355X.  Per-pass times come from a rocprofv3 run of this tool on
 ONE case (`rocprofv3 --kernel-trace --stats -- python tools/ingest_time.py --case NAME`); pass its kernel_stats.csv back with
-`--kernel_stats` to have each pass's time and its share of the byte floor added to the JSON."""
+`--kernel_stats` to have each pass's time and its share of the byte floor added to the JSON.
+
+`--mask_grid own` draws the same box on a mask grid of 3/4 the scan's extents per axis (384 x 384 x 36 for 512 x 512 x 48; the outer
+faces of the two grids coincide, so the resampled box is within a voxel of the same-grid one) and runs `mmnn_resample_mask` ahead of the three passes; its bytes are the mask read
+once plus x*y*z written."""
 import argparse
 import csv
 import json
@@ -29,7 +33,7 @@ CASES = {
     "512x512x48_box320x310x39": ((512, 512, 48), ((96, 101, 4), (416, 411, 43))),
     "256x256x40_full": ((256, 256, 40), ((0, 0, 0), (256, 256, 40))),
 }
-PASS_OF_KERNEL = {"ingest_flags_kernel": "pass_a_flags", "ingest_scan_kernel": "pass_b_scan", "ingest_area_kernel": "pass_c_area"}
+PASS_OF_KERNEL = {"resample_mask_kernel": "pass_r_resample", "ingest_flags_kernel": "pass_a_flags", "ingest_scan_kernel": "pass_b_scan", "ingest_area_kernel": "pass_c_area"}
 
 
 def make_volume(shape, box, seed):
@@ -41,10 +45,23 @@ def make_volume(shape, box, seed):
     return np.asfortranarray(scan), np.asfortranarray(mask)
 
 
-def pass_bytes(shape, box):
+def own_grid(shape, box):
+    """(mask extents, the box on the mask grid, index map): a grid of 3/4 the extents whose outer faces coincide with the scan's, so
+    mask index = 0.75 (i + 0.5) - 0.5.  The box is the case's, scaled and rounded down; the caller reads the kept extents it leaves."""
+    own = tuple(-(-3 * n // 4) for n in shape)
+    lo, hi = ([int(np.floor(0.75 * v)) for v in b] for b in box)
+    T = np.zeros((3, 4))
+    T[:, :3], T[:, 3] = np.diag([0.75] * 3), 0.75 * 0.5 - 0.5
+    return own, (tuple(lo), tuple(hi)), T
+
+
+def pass_bytes(shape, box, own=None):
     voxels = int(np.prod(shape))
     kept = int(np.prod([b - a for a, b in zip(*box)]))
-    return {"pass_a_flags": voxels * 3, "pass_c_area": kept * 3 + 4 * 64 ** 3, "pass_b_scan": 8 * sum(shape)}
+    pb = {"pass_a_flags": voxels * 3, "pass_c_area": kept * 3 + 4 * 64 ** 3, "pass_b_scan": 8 * sum(shape)}
+    if own is not None:
+        pb["pass_r_resample"] = int(np.prod(own)) + voxels
+    return pb
 
 
 def host_times(scan, mask, repeats=3):
@@ -83,33 +100,51 @@ def queued_us(fn, steps):
     return a.elapsed_time(b) * 1e3 / steps
 
 
-def time_case(name, steps, warmup):
+def time_case(name, steps, warmup, mask_grid="same"):
     shape, box = CASES[name]
     host = [make_volume(shape, box, s) for s in range(4)]
+    own = None
+    if mask_grid == "own":
+        own, own_box, T = own_grid(shape, box)
+        host = [(s, make_volume(own, own_box, 0)[1]) for s, _ in host]
+        resampled = torch.empty(int(np.prod(shape)), dtype=torch.uint8, device="cuda")
     vols = [(ingest.upload(s, "cuda", 0.25, -12.5), ingest.upload(m, "cuda")) for s, m in host]
     batch = torch.empty((2, 2, 64, 64, 64), device="cuda")
     ext = torch.empty((2, 2, 3), dtype=torch.int32, device="cuda")
     ws = torch.empty(ingest.workspace_bytes(*shape), dtype=torch.uint8, device="cuda")
 
+    def volume(i):
+        s, m = vols[i]
+        if own is not None:       # (one buffer for the resampled mask: the four volumes run in stream order)
+            m = ingest.resample_mask(m, shape, T, 0.5, out=resampled)
+        ingest.ingest_volume(s, m, batch[i // 2, i % 2], ext[i // 2, i % 2], ws)
+
     def one():
-        ingest.ingest_volume(vols[0][0], vols[0][1], batch[0, 0], ext[0, 0], ws)
+        volume(0)
 
     def four():
-        for i, (s, m) in enumerate(vols):
-            ingest.ingest_volume(s, m, batch[i // 2, i % 2], ext[i // 2, i % 2], ws)
+        for i in range(4):
+            volume(i)
 
     for _ in range(warmup):
         four()
     torch.cuda.synchronize()
-    want = [b - a for a, b in zip(*box)]
-    assert ext.cpu().reshape(-1, 3).tolist() == [want] * 4, ext
+    got = ext.cpu().reshape(-1, 3).tolist()
+    if own is None:
+        assert got == [[b - a for a, b in zip(*box)]] * 4, ext
+    else:                         # the kept box in scan voxels, for the byte count of pass C
+        assert got == [got[0]] * 4 and min(got[0]) > 0, ext
+        box = ((0, 0, 0), tuple(got[0]))
     vol_us, batch_us = queued_us(one, steps), queued_us(four, steps)
-    pb = pass_bytes(shape, box)
+    pb = pass_bytes(shape, box, own)
     total = sum(pb.values())
     floor_us = total / (HBM_TBS * 1e12) * 1e6
     res = {"device_us_per_volume": round(vol_us, 1), "device_us_per_batch": round(batch_us, 1), "MB_per_volume": round(total / 1e6, 2),
            "hbm_floor_us_per_volume": round(floor_us, 2), "TBps": round(total / (vol_us * 1e-6) / 1e12, 3),
-           "share_of_hbm_ceiling": round(total / (vol_us * 1e-6) / 1e12 / HBM_TBS, 3), "pass_MB": {k: round(v / 1e6, 3) for k, v in pb.items()}}
+           "share_of_hbm_ceiling": round(total / (vol_us * 1e-6) / 1e12 / HBM_TBS, 3), "pass_MB": {k: round(v / 1e6, 3) for k, v in pb.items()}, "pass_bytes": pb}
+    if own is not None:
+        res["mask_grid"] = list(own)
+        res["resample_us_per_volume"] = round(queued_us(lambda: ingest.resample_mask(vols[0][1], shape, T, 0.5, out=resampled), steps), 1)
     res["host_per_volume"] = host_times(*host[0])
     return res
 
@@ -124,7 +159,7 @@ def add_kernel_stats(res, path):
                 tot[name] = (ns + float(r["TotalDurationNs"]), calls + int(r["Calls"]))
     out = {name: ns / calls / 1e3 for name, (ns, calls) in tot.items()}
     for name, us in out.items():
-        b = res["pass_MB"][name] * 1e6
+        b = res["pass_bytes"][name]
         res.setdefault("pass_us", {})[name] = round(us, 2)
         res.setdefault("pass_share_of_hbm_ceiling", {})[name] = round(b / (us * 1e-6) / 1e12 / HBM_TBS, 3)
 
@@ -134,16 +169,18 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--case", type=str, default=None, choices=sorted(CASES))
+    ap.add_argument("--mask_grid", type=str, default="same", choices=("same", "own"), help="own: the mask on a grid of 3/4 the extents, resampled first")
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--kernel_stats", type=str, default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     res = {}
     for name in ([a.case] if a.case else list(CASES)):
-        res[name] = time_case(name, a.steps, a.warmup)
+        key = name if a.mask_grid == "same" else name + "_mask_grid_own"
+        res[key] = time_case(name, a.steps, a.warmup, a.mask_grid)
         if a.kernel_stats and a.case:
-            add_kernel_stats(res[name], a.kernel_stats)
-        print(json.dumps({"case": name, **res[name]}), flush=True)
+            add_kernel_stats(res[key], a.kernel_stats)
+        print(json.dumps({"case": key, **res[key]}), flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
