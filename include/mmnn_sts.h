@@ -394,7 +394,8 @@ typedef struct {
 int64_t mmnn_ingest_workspace_bytes(int32_t x, int32_t y, int32_t z);
 /* scan, mask: device buffers of x*y*z voxels of the given types, aligned to their element size; out_plane: 64^3 floats (a channel of an
  * (N, C, 64, 64, 64) tensor; nothing else is written); extents: 3 int32 on the device = kept slices along x, y, z, valid once the
- * stream has run the call. */
+ * stream has run the call.  ws: once the stream has run the call it holds the kept-index lists and extents of this scan, and stays
+ * valid as the `ingest_ws` of mmnn_maps_to_scan (below) until it is reused for another ingest. */
 int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* mask, float* out_plane, int32_t* extents, void* ws,
                        void* stream);
 
@@ -423,6 +424,31 @@ typedef struct {
   double threshold;
 } mmnn_resample_mask_desc;
 int mmnn_resample_mask(const mmnn_resample_mask_desc* d, const void* mask, uint8_t* out, void* stream);
+
+/* ---- the way back: 64^3 model-space maps (Grad-CAM attention maps) -> fp32 volumes on the scan's voxel grid, so that they overlay the
+ * scan once written with its affine (csrc/ingest.hip).  The kept slices are the ingest's own: `ingest_ws` is the workspace a completed
+ * mmnn_ingest_volume call for this scan left behind; it is read, never written, and neither the scan nor the mask is read again (so a
+ * resampled-mask ingest is inverted by the slices it kept).  With S = 64 and M_r the extent kept along axis r:
+ *   dropped voxels a scan voxel whose x, y or z index is not in the kept list of its axis gets exactly 0.0f.
+ *   coordinate     otherwise p_r is the rank of its index in the kept list, 0 <= p_r < M_r, and per axis, in fp64:
+ *                  s = max((p + 0.5) S / M - 0.5, 0), i0 = min(floor(s), S - 1), i1 = min(i0 + 1, S - 1), w = s - i0.
+ *   value          the trilinear blend of the eight map entries (weights 1 - w, w per axis), formed in fp64 and rounded once to fp32:
+ *                  F.interpolate(map, size=(Mx, My, Mz), mode='trilinear', align_corners=False) scattered to the kept positions, the
+ *                  convention of the Grad-CAM up-sampling (mmnn_gradcam).
+ *   empty mask     an extent of 0 gives an all-zero `out`.
+ * maps: [n_maps][64][64][64] fp32, tensor axes D, H, W = array axes x, y, z as the ingest writes its plane; out: [n_maps][z][y][x]
+ * fp32, x fastest (NIfTI order); every element of it is written and nothing else is.  Two launches (the per-axis tap table, then the
+ * pass), no atomics, no host synchronisation: repeated calls are bit-identical.  Refused (status 1): a non-positive extent,
+ * x > MMNN_INGEST_MAX_X, x*y*z >= 2^31, n_maps outside 1..MMNN_MAPS_TO_SCAN_MAX_MAPS, a null pointer, a workspace not aligned to 256
+ * bytes, maps / out not aligned to 4. */
+#define MMNN_MAPS_TO_SCAN_MAX_MAPS 16
+typedef struct {
+  int32_t x, y, z;                /* the scan's grid = the output grid, NIfTI dim[1..3] */
+  int32_t n_maps;                 /* 1..MMNN_MAPS_TO_SCAN_MAX_MAPS */
+} mmnn_maps_to_scan_desc;
+/* bytes of device scratch (the tap tables of the three axes); -1 on a bad extent.  Needs no GPU. */
+int64_t mmnn_maps_to_scan_workspace_bytes(int32_t x, int32_t y, int32_t z);
+int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, const float* maps, float* out, void* ws, void* stream);
 
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */

@@ -16,7 +16,8 @@ is dropped and CLASS_FREQUENCIES comes from the config; the validation loop move
 loss device (Q4); logging syncs once per epoch, not per micro-batch; `--preop` alone builds the standalone MLP (Q12).
 Datasets: `--image_loc DIR --key_loc key.csv --data_loc clinical.csv` (or the config's `Data:` section) trains on / evaluates local NIfTI
 patient directories -- the files' raw voxels are masked, cropped of empty slices and resized to 64^3 on the device
-(mmnn_sts_amd/data/ingest.py); DICOM / S3 stay outside the path.  Without an image location synthetic patients are used; the tabular-only
+(mmnn_sts_amd/data/ingest.py); DICOM / S3 stay outside the path.  `--inference --image_loc DIR --scan_space` also writes every class's
+attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).  Without an image location synthetic patients are used; the tabular-only
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -237,7 +238,7 @@ def nifti_datasets(parser, args, device, seed, rank, world):
     from mmnn_sts_amd.data.ingest import IngestCollate
     full = parser.getDatasets(args, parser.getImagePath())
     train_uids, val_uids = split_uids(full.uids, args, seed)
-    args.ingest_collate = IngestCollate(device, *parser.maskResample())
+    args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False))
     return ImageDatasetByUIDs(full, train_uids[rank::world]), ImageDatasetByUIDs(full, val_uids)
 
 
@@ -251,6 +252,22 @@ def export_patient_nifti(args, uid, image, att, preds):
     nifti.write(os.path.join(d, "att_map.nii.gz"), att.cpu().numpy().astype(np.float32))
     with open(os.path.join(d, "preds.txt"), "w") as f:
         f.write("".join(f"{float(v)!r}\n" for v in preds.reshape(-1)))
+
+
+def export_scan_space_maps(args, uid, maps, volumes):
+    """`--scan_space`: every class's attention map on the voxel grid of every scan of the patient, into the patient's folder as
+    att_map_class{k}_on_{t1,t2}.nii.gz (att_map_class{k}_on_scan.nii.gz for a single modality), written with the scan's affine so that a
+    viewer lays it over the scan.  `maps`: (classes, 64, 64, 64) on the device, in the model's space; `volumes`: the patient's
+    `KeptVolume` per modality.  The ingest's own kept slices are inverted on the device (`maps_to_scan`); dropped slices are 0."""
+    from mmnn_sts_amd.data import nifti
+    from mmnn_sts_amd.data.ingest import maps_to_scan
+    d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
+    os.makedirs(d, exist_ok=True)
+    names = ("t1", "t2") if len(volumes) == 2 else ("scan",)
+    for name, vol in zip(names, volumes):
+        on_scan = maps_to_scan(maps, vol.shape, vol.workspace).cpu().numpy()           # (classes, z, y, x)
+        for k in range(on_scan.shape[0]):
+            nifti.write(os.path.join(d, f"att_map_class{k}_on_{name}.nii.gz"), on_scan[k].transpose(2, 1, 0), affine=vol.affine)
 
 
 def apply_transforms(x, tf):
@@ -444,6 +461,13 @@ def inference_survival(model, ds, args, device):
                 np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_att_map.npy"), att.cpu().numpy())
                 if getattr(args, "ingest_collate", None) is not None:
                     export_patient_nifti(args, ds.uids[i], (x["image"] if args.multimodal else x)[0], att, p)
+                if getattr(args, "scan_space", False):
+                    # the maps live in the space of the ingest's 64^3 planes: `--transforms` puts only the validation transforms
+                    # between the two, and those are spatially the identity at 64^3 (intensity stages and a Resize to the size the
+                    # planes already have), so the map needs no further correction.  Fusion: one map per class; image-only: the
+                    # sample's one map, class 0
+                    stack = torch.stack(list(maps)) if args.multimodal else maps[0]
+                    export_scan_space_maps(args, ds.uids[i], stack.contiguous(), args.ingest_collate.last_volumes[0])
             else:
                 p = model(x)
         preds.append(p.cpu()); evs.append(ev); dus.append(du)
@@ -514,6 +538,9 @@ def build_arg_parser():
     ap.add_argument("--blend_update_interval", type=int, default=5)
     ap.add_argument("--transforms", action="store_true",
                     help="run upstream's train_transforms / val_transforms on every image batch on the device (resizes to 64^3)")
+    ap.add_argument("--scan_space", action="store_true",
+                    help="with --inference --image_loc and Grad-CAM on: also write every class's attention map on each scan's own voxel "
+                         "grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz)")
     # synthetic-data knobs (no counterpart upstream)
     ap.add_argument("--synthetic_patients", type=int, default=16)
     ap.add_argument("--synthetic_size", type=int, default=64)
@@ -559,6 +586,9 @@ def main(argv=None):
         n_mod = 2 if cfg["ImageModel"]["modality"].lower().startswith("t1t2") else 1
         if int(cfg["ImageModel"]["in_channels"]) != n_mod:
             raise SystemExit(f"ImageModel modality {cfg['ImageModel']['modality']} yields {n_mod} channel(s) per patient, in_channels is {cfg['ImageModel']['in_channels']}")
+    if a.scan_space and not (a.inference and use_nifti and a.images and not a.no_gradcam and not a.bootstrap):
+        raise SystemExit("--scan_space lays the Grad-CAM attention maps over the patients' scans: it needs --inference, --image_loc (NIfTI "
+                         "patient directories) and Grad-CAM on (--images, neither --no_gradcam nor --bootstrap)")
     hp = cfg.get("Hyperparameters", {})
     a.multimodal = a.images and (a.preop or a.postop)
     a.blend = a.blend and a.multimodal

@@ -105,6 +105,14 @@ class ResampleMaskDesc(Structure):
                 ("mask_slope", c_float), ("mask_inter", c_float), ("index_map", ctypes.c_double * 12), ("threshold", ctypes.c_double)]
 
 
+MAPS_TO_SCAN_MAX_MAPS = 16
+
+
+class MapsToScanDesc(Structure):
+    """mmnn_maps_to_scan_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_maps", c_int32)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -199,6 +207,10 @@ def lib():
     L.mmnn_ingest_volume.argtypes = [POINTER(IngestDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_resample_mask.restype = c_int32
     L.mmnn_resample_mask.argtypes = [POINTER(ResampleMaskDesc), c_void_p, c_void_p, c_void_p]
+    L.mmnn_maps_to_scan_workspace_bytes.restype = c_int64
+    L.mmnn_maps_to_scan_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.mmnn_maps_to_scan.restype = c_int32
+    L.mmnn_maps_to_scan.argtypes = [POINTER(MapsToScanDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

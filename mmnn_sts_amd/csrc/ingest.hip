@@ -17,6 +17,8 @@
 //
 //   resample_mask_kernel  mmnn_resample_mask, a call of its own ahead of the three passes when the mask was drawn on another grid:
 //                         sitk.Resample(mask, image) with its defaults, then upstream's rebinarisation, to one byte per scan voxel.
+//   maps_taps_kernel, maps_to_scan_kernel   mmnn_maps_to_scan, the inverse path: 64^3 maps of the model back onto the scan's grid,
+//                         by the kept-index lists that pass B left in the workspace.
 #include "../../include/mmnn_sts.h"
 #include "area.hpp"
 #include "common.hpp"
@@ -291,6 +293,115 @@ __global__ void __launch_bounds__(IG_TPB) resample_mask_kernel(const RsArgs a, c
   else rs_dispatch<VEC, false>(a, code);
 }
 
+// ---- maps to scan ----------------------------------------------------------------------------------------------------------------
+// The way back: 64^3 model-space maps -> fp32 volumes on the scan's grid (the contract is the comment above mmnn_maps_to_scan in the
+// header).  The kept slices are the ingest's own: the kept-index lists and extents its pass B left in its workspace are read, never the
+// scan or the mask.
+//   maps_taps_kernel      one entry per scan index of each axis: the two map indices and the weight of its linear tap, or "dropped".
+//                         The rank of an index is found by bisection of its axis' ascending kept list, so a thread writes its own
+//                         entry only and every entry is written.
+//   maps_to_scan_kernel   grid and block as pass A.  A wave owns a row (y, z); its lanes keep the x taps of their MS_XCH * VEC output
+//                         voxels in registers over all rows.  Per row lane l loads the four (y tap, z tap) entries of map x index l
+//                         -- the map's fastest axis is z, the output's is x, so a gather per output voxel would touch eight cache
+//                         lines where this touches two per lane and row -- and blends them with the row's y and z weights into a
+//                         64-entry fp64 line in LDS, one line per map; then every lane lerps its voxels along x from the line.
+//                         Dropped rows and dropped x indices are stored as zeros: every element of `out` is written.
+struct MsTap {
+  int i0, i1;                               // i0 < 0: the index is not in the kept list
+  double w;
+};
+
+struct MsArgs {
+  const int* kept_x; const int* kept_y; const int* kept_z;  // the ingest's workspace
+  const int* M;
+  MsTap* tx; MsTap* ty; MsTap* tz;                          // [X], [Y], [Z]
+  const float* maps; float* out;
+  int X, Y, Z, n_maps;
+};
+
+constexpr int MS_XCH = 2;                   // x chunks of 64 * VEC voxels per block: 512 voxels of a row when VEC = 4
+
+__device__ __forceinline__ MsTap ms_tap(const int* kept, int m, int n, int i) {
+  MsTap t{-1, -1, 0.0};
+  m = min(max(m, 0), n);
+  int lo = 0, hi = m;                       // the first position whose kept index is not below i
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (kept[mid] < i) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo < m && kept[lo] == i) {
+    const double s = fmax(((double)lo + 0.5) * (double)IG_S / (double)m - 0.5, 0.0);
+    t.i0 = min((int)floor(s), IG_S - 1);
+    t.i1 = min(t.i0 + 1, IG_S - 1);
+    t.w = s - (double)t.i0;
+  }
+  return t;
+}
+
+__global__ void __launch_bounds__(IG_SCAN_TPB) maps_taps_kernel(const MsArgs a) {
+  const int i = blockIdx.x * IG_SCAN_TPB + threadIdx.x;
+  if (i < a.X) a.tx[i] = ms_tap(a.kept_x, a.M[0], a.X, i);
+  else if (i < a.X + a.Y) a.ty[i - a.X] = ms_tap(a.kept_y, a.M[1], a.Y, i - a.X);
+  else if (i < a.X + a.Y + a.Z) a.tz[i - a.X - a.Y] = ms_tap(a.kept_z, a.M[2], a.Z, i - a.X - a.Y);
+}
+
+// grid (x groups of MS_XCH * 64 * VEC columns, row blocks); block (64, IG_WAVES).  Dynamic LDS: IG_WAVES * n_maps * 64 doubles.
+template <int VEC>
+__global__ void __launch_bounds__(IG_TPB) maps_to_scan_kernel(const MsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char ig_smem[];
+  const int lane = threadIdx.x, wave = threadIdx.y;
+  double* line = reinterpret_cast<double*>(ig_smem) + wave * a.n_maps * IG_S;
+  MsTap t[MS_XCH][VEC];
+  int x0[MS_XCH];
+#pragma unroll
+  for (int c = 0; c < MS_XCH; ++c) {
+    x0[c] = ((blockIdx.x * MS_XCH + c) * 64 + lane) * VEC;   // VEC > 1 only when X % VEC == 0: a group is inside or outside as a whole
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) t[c][k] = x0[c] < a.X ? a.tx[x0[c] + k] : MsTap{-1, -1, 0.0};
+  }
+  const long R = (long)a.Y * a.Z, V = R * a.X;
+  // the trip count is the same in every wave of the block (the barriers): a wave past the last row only waits
+  for (long r0 = (long)blockIdx.y * IG_WAVES; r0 < R; r0 += (long)gridDim.y * IG_WAVES) {
+    const long r = r0 + wave;                         // r = y + Y z
+    bool live = false;
+    if (r < R) {
+      const MsTap ty = a.ty[r % a.Y], tz = a.tz[r / a.Y];
+      live = ty.i0 >= 0 && tz.i0 >= 0;
+      if (live) {
+        const float* p0 = a.maps + ((long)lane * IG_S + ty.i0) * IG_S;
+        const float* p1 = a.maps + ((long)lane * IG_S + ty.i1) * IG_S;
+        for (int m = 0; m < a.n_maps; ++m) {
+          const long mo = (long)m * IG_S * IG_S * IG_S;
+          const double v00 = (double)p0[mo + tz.i0], v01 = (double)p0[mo + tz.i1];
+          const double v10 = (double)p1[mo + tz.i0], v11 = (double)p1[mo + tz.i1];
+          line[m * IG_S + lane] = (1.0 - ty.w) * ((1.0 - tz.w) * v00 + tz.w * v01) + ty.w * ((1.0 - tz.w) * v10 + tz.w * v11);
+        }
+      }
+    }
+    __syncthreads();
+    if (r < R) {
+      for (int m = 0; m < a.n_maps; ++m) {
+        float* dst = a.out + (long)m * V + r * a.X;
+        const double* ln = line + m * IG_S;
+#pragma unroll
+        for (int c = 0; c < MS_XCH; ++c) {
+          if (x0[c] >= a.X) continue;
+          IgVec<float, VEC> o;
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            const MsTap& q = t[c][k];
+            const double v = (1.0 - q.w) * ln[max(q.i0, 0)] + q.w * ln[max(q.i1, 0)];
+            o.e[k] = (live && q.i0 >= 0) ? (float)v : 0.f;
+          }
+          *reinterpret_cast<IgVec<float, VEC>*>(dst + x0[c]) = o;
+        }
+      }
+    }
+    __syncthreads();                                  // the lines are rewritten by the next row
+  }
+}
+
 namespace {
 
 size_t ig_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -335,6 +446,12 @@ int ig_validate_extent(int x, int y, int z) {
   MMNN_REQUIRE(x >= 1 && y >= 1 && z >= 1, "ingest: non-positive extent %d x %d x %d", x, y, z);
   MMNN_REQUIRE(x <= MMNN_INGEST_MAX_X, "ingest: x extent %d above %d", x, MMNN_INGEST_MAX_X);
   MMNN_REQUIRE((long)y * z < (1l << 31) && (long)x + y + z < (1l << 30), "ingest: extent %d x %d x %d too large", x, y, z);
+  return 0;
+}
+
+int ms_validate_extent(int x, int y, int z) {
+  if (ig_validate_extent(x, y, z) != 0) return 1;
+  MMNN_REQUIRE((double)x * y * z < 2147483648.0, "maps_to_scan: scan extent %d x %d x %d holds 2^31 voxels or more", x, y, z);
   return 0;
 }
 
@@ -421,6 +538,41 @@ int mmnn_resample_mask(const mmnn_resample_mask_desc* d, const void* mask, uint8
   if (gy > cap) gy = cap;
   if (vec4) MMNN_LAUNCH(resample_mask_kernel<4>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a, d->mask_type);
   else MMNN_LAUNCH(resample_mask_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a, d->mask_type);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
+
+int64_t mmnn_maps_to_scan_workspace_bytes(int32_t x, int32_t y, int32_t z) {
+  if (ms_validate_extent(x, y, z) != 0) return -1;
+  return (int64_t)ig_align(((size_t)x + (size_t)y + (size_t)z) * sizeof(MsTap));
+}
+
+int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, const float* maps, float* out, void* ws, void* stream_) {
+  MMNN_REQUIRE(d, "maps_to_scan: null descriptor");
+  if (ms_validate_extent(d->x, d->y, d->z) != 0) return 1;
+  MMNN_REQUIRE(d->n_maps >= 1 && d->n_maps <= MMNN_MAPS_TO_SCAN_MAX_MAPS, "maps_to_scan: n_maps %d outside 1..%d", d->n_maps, MMNN_MAPS_TO_SCAN_MAX_MAPS);
+  MMNN_REQUIRE(ingest_ws && maps && out && ws, "maps_to_scan: null argument");
+  MMNN_REQUIRE((uintptr_t)ingest_ws % 256 == 0 && (uintptr_t)ws % 256 == 0 && (uintptr_t)maps % 4 == 0 && (uintptr_t)out % 4 == 0,
+               "maps_to_scan: misaligned workspace / maps / output");
+  const hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const IgLayout L = ig_layout(d->x, d->y, d->z);
+  const char* iws = static_cast<const char*>(ingest_ws);
+  MsArgs a{};
+  a.kept_x = reinterpret_cast<const int*>(iws + L.kept); a.kept_y = a.kept_x + d->x; a.kept_z = a.kept_y + d->y;
+  a.M = reinterpret_cast<const int*>(iws + L.m);
+  a.tx = static_cast<MsTap*>(ws); a.ty = a.tx + d->x; a.tz = a.ty + d->y;
+  a.maps = maps; a.out = out;
+  a.X = d->x; a.Y = d->y; a.Z = d->z; a.n_maps = d->n_maps;
+  MMNN_LAUNCH(maps_taps_kernel, dim3(cdiv((long)d->x + d->y + d->z, IG_SCAN_TPB)), dim3(IG_SCAN_TPB), 0, stream, a);
+  // 4 voxels per lane and 16-byte stores when every output row starts on a 16-byte boundary
+  const bool vec4 = d->x % 4 == 0 && (uintptr_t)out % 16 == 0;
+  const int gx = cdiv(d->x, MS_XCH * 64 * (vec4 ? 4 : 1));
+  int gy = cdiv((long)d->y * d->z, IG_WAVES);
+  const int cap = cdiv(2048, gx);
+  if (gy > cap) gy = cap;
+  const size_t lds = (size_t)IG_WAVES * d->n_maps * IG_S * sizeof(double);
+  if (vec4) MMNN_LAUNCH(maps_to_scan_kernel<4>, dim3(gx, gy), dim3(64, IG_WAVES), lds, stream, a);
+  else MMNN_LAUNCH(maps_to_scan_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), lds, stream, a);
   MMNN_HIP(hipGetLastError());
   return 0;
 }

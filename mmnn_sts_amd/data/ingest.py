@@ -9,6 +9,7 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
     collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
     IngestCollate(device)                           the DataLoader collate_fn of the NIfTI datasets
+    maps_to_scan(maps, scan_shape, ingest_workspace)   the way back: 64^3 model-space maps -> fp32 volumes on the scan's grid (mmnn_maps_to_scan)
 
 A mask on another grid (a T2 contour used on the T1 scan, a resliced export, a mask cropped to the tumour's bounding box) is what
 upstream's DICOM datasets pass through `sitk.Resample(mask, image)` and `> 128` (data/ImageDatasets.py:145-152, :246-257); here the
@@ -43,6 +44,15 @@ class DeviceVolume:
     datatype: int
     slope: float = 1.0
     inter: float = 0.0
+    affine: Optional[np.ndarray] = None
+
+
+@dataclass
+class KeptVolume:
+    """What `keep_workspaces` retains of one ingested volume: the ingest's workspace (its kept-index lists and extents, which
+    `maps_to_scan` reads), the scan's extents and its affine (None: the file has no geometry)."""
+    workspace: torch.Tensor
+    shape: Tuple[int, int, int]
     affine: Optional[np.ndarray] = None
 
 
@@ -173,11 +183,63 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     return extents
 
 
+def maps_to_scan_workspace_bytes(x: int, y: int, z: int) -> int:
+    n = _lib.lib().mmnn_maps_to_scan_workspace_bytes(int(x), int(y), int(z))
+    if n < 0:
+        raise ValueError("mmnn_maps_to_scan_workspace_bytes: " + _lib.last_error())
+    return int(n)
+
+
+def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Enqueue `mmnn_maps_to_scan` on the current stream: `maps` ((n_maps, 64, 64, 64) fp32 in model space, axes x, y, z as the ingest
+    writes its plane) -> (n_maps, z, y, x) fp32 on the scan's voxel grid (x fastest, NIfTI order; `.permute(0, 3, 2, 1)` is the (x, y, z)
+    array of a volume).  Kept voxels hold the trilinear up-sampling of the map to the kept extents, every voxel of a slice the ingest
+    dropped is exactly 0.  `ingest_workspace`: the `workspace` tensor a completed `ingest_volume` of this scan used, not reused since.
+    `out`: a contiguous (n_maps, z, y, x) fp32 tensor on the maps' device to write, allocated when None; `workspace`: scratch of
+    `maps_to_scan_workspace_bytes` bytes, allocated when None."""
+    shape = tuple(scan_shape)
+    if len(shape) != 3 or any(int(v) != v or int(v) < 1 for v in shape):
+        raise ValueError(f"maps_to_scan: scan_shape must be three positive extents (x, y, z), got {scan_shape!r}")
+    x, y, z = (int(v) for v in shape)
+    if not isinstance(maps, torch.Tensor) or maps.ndim != 4 or tuple(maps.shape[1:]) != (SIZE,) * 3 or not 1 <= maps.shape[0] <= _lib.MAPS_TO_SCAN_MAX_MAPS:
+        raise ValueError(f"maps_to_scan: maps must be (n, {SIZE}, {SIZE}, {SIZE}) with n in 1..{_lib.MAPS_TO_SCAN_MAX_MAPS}, got {tuple(getattr(maps, 'shape', ()))}")
+    if maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError(f"maps_to_scan: maps must be contiguous fp32, got {maps.dtype}{'' if maps.is_contiguous() else ' (not contiguous)'}")
+    if not isinstance(ingest_workspace, torch.Tensor) or ingest_workspace.dtype != torch.uint8 or not ingest_workspace.is_contiguous():
+        raise ValueError("maps_to_scan: ingest_workspace must be the contiguous uint8 workspace tensor of the scan's ingest")
+    if not maps.is_cuda:
+        raise ValueError(f"maps_to_scan: maps must be on the GPU, got {maps.device}")
+    dev = maps.device
+    if ingest_workspace.device != dev:
+        raise ValueError(f"maps_to_scan: ingest_workspace is on {ingest_workspace.device}, the maps on {dev}")
+    n = int(maps.shape[0])
+    if out is None:
+        out = torch.empty((n, z, y, x), dtype=torch.float32, device=dev)
+    elif not (out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, z, y, x)):
+        raise ValueError(f"maps_to_scan: out must be a contiguous ({n}, {z}, {y}, {x}) fp32 tensor on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    if ingest_workspace.numel() < workspace_bytes(x, y, z):
+        raise ValueError(f"maps_to_scan: ingest_workspace of {ingest_workspace.numel()} bytes, an ingest of {x} x {y} x {z} leaves {workspace_bytes(x, y, z)}")
+    nbytes = maps_to_scan_workspace_bytes(x, y, z)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif not (workspace.device == dev and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= nbytes):
+        raise ValueError(f"maps_to_scan: workspace must be {nbytes} contiguous bytes on {dev}")
+    desc = _lib.MapsToScanDesc(x, y, z, n)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mmnn_maps_to_scan(ctypes.byref(desc), ingest_workspace.data_ptr(), maps.data_ptr(), out.data_ptr(),
+                                                workspace.data_ptr(), stream), "mmnn_maps_to_scan")
+    return out
+
+
 def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
-                    mask_threshold: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+                    mask_threshold: float = 0.5, keep_workspaces: bool = False):
     """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
     issued before the first kernel, so the copies of one volume run beside the passes of the one before it.  A mask on another grid
-    than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`."""
+    than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`.
+    With `keep_workspaces` every volume is ingested with a workspace of its own and a third value is returned: volumes[n][c], the
+    `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan."""
     n, c = len(patients), len(patients[0])
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
@@ -186,31 +248,43 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     batch = torch.empty((n, c, SIZE, SIZE, SIZE), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)
+    kept = []
     for i in range(n):
+        kept.append([])
         for j in range(c):
-            ingest_volume(up[i][j][0], up[i][j][1], batch[i, j], extents[i, j], index_map=maps[i][j], threshold=mask_threshold)
-    return batch, extents
+            ws = torch.empty(workspace_bytes(*up[i][j][0].shape), dtype=torch.uint8, device=device) if keep_workspaces else None
+            ingest_volume(up[i][j][0], up[i][j][1], batch[i, j], extents[i, j], ws, index_map=maps[i][j], threshold=mask_threshold)
+            if keep_workspaces:
+                kept[i].append(KeptVolume(ws, up[i][j][0].shape, up[i][j][0].affine))
+    return (batch, extents, kept) if keep_workspaces else (batch, extents)
 
 
 class IngestCollate:
     """collate_fn of the NIfTI datasets: items are (x, events, durations) or (x, labels) with x a RawPatient or
     {'image': RawPatient, 'clinical': tensor}; returns (x, events, durations) (durations None for classification items) with the image
     batch on `device`.  The extents of every batch are kept in `pending` until `take_empty()` reads them: call it where the epoch
-    synchronises anyway, never per batch.  `mask_resample` / `mask_threshold`: the `Data:` keys of the same names (see `collate_volumes`)."""
+    synchronises anyway, never per batch.  `mask_resample` / `mask_threshold`: the `Data:` keys of the same names (see `collate_volumes`).
+    `keep_workspaces` (off: nothing is retained, as training wants it): `last_volumes[n][c]` holds the `KeptVolume` of every (patient,
+    modality) of the LAST batch, for `maps_to_scan`."""
 
-    def __init__(self, device, mask_resample: str = "auto", mask_threshold: float = 0.5):
+    def __init__(self, device, mask_resample: str = "auto", mask_threshold: float = 0.5, keep_workspaces: bool = False):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         self.device = torch.device(device)
         self.mask_resample, self.mask_threshold = mask_resample, float(mask_threshold)
         self.pending: List[Tuple[List[int], torch.Tensor]] = []
+        self.keep_workspaces = bool(keep_workspaces)
+        self.last_volumes: List[List[KeptVolume]] = []
 
     def __call__(self, items):
         xs = [it[0] for it in items]
         targets = [torch.stack([torch.as_tensor(it[k]) for it in items]) for k in range(1, len(items[0]))]
         multimodal = isinstance(xs[0], dict)
         raws = [x["image"] for x in xs] if multimodal else xs
-        batch, extents = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold)
+        batch, extents, *kept = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold,
+                                                keep_workspaces=self.keep_workspaces)
+        if kept:
+            self.last_volumes = kept[0]
         self.pending.append(([r.uid for r in raws], extents))
         x = {"image": batch, "clinical": torch.stack([x["clinical"] for x in xs]).float()} if multimodal else batch
         return (x, targets[0], targets[1] if len(targets) > 1 else None)

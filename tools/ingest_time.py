@@ -4,6 +4,7 @@ warm-up and the calls queued back to back behind a spin kernel (device time alon
 of the two .nii.gz files and the pinned upload.
 
     python tools/ingest_time.py [--steps 50] [--warmup 10] [--case NAME] [--mask_grid own] [--json out.json] [--kernel_stats kernel_stats.csv]
+    python tools/ingest_time.py --maps_to_scan [--json out.json]      # the inverse path alone (`--json` adds its rows to the file's)
 
 Cases: 512 x 512 x 48 int16 scan + uint8 mask with a 320 x 310 x 39 box; 256 x 256 x 40 with the mask covering everything.  Bytes are the
 algorithmic HBM traffic computed from the shapes -- pass A reads every scan and mask byte once, pass C reads the kept box once, 1 MB is
@@ -13,7 +14,11 @@ ONE case (`rocprofv3 --kernel-trace --stats -- python tools/ingest_time.py --cas
 
 `--mask_grid own` draws the same box on a mask grid of 3/4 the scan's extents per axis (384 x 384 x 36 for 512 x 512 x 48; the outer
 faces of the two grids coincide, so the resampled box is within a voxel of the same-grid one) and runs `mmnn_resample_mask` ahead of the three passes; its bytes are the mask read
-once plus x*y*z written."""
+once plus x*y*z written.
+
+`--maps_to_scan` times the way back (`ingest.maps_to_scan`, 64^3 maps -> fp32 volumes on the scan's grid) on the first case's scan, with 1
+map and with 2, from the workspace one ingest left behind.  Its floor is the bytes WRITTEN (n_maps * x*y*z * 4; the 1 MB map per volume
+and the tap tables are read from cache) over the same 6.29 TB/s."""
 import argparse
 import csv
 import json
@@ -149,6 +154,29 @@ def time_case(name, steps, warmup, mask_grid="same"):
     return res
 
 
+def time_maps_to_scan(steps, warmup, name="512x512x48_box320x310x39"):
+    shape, box = CASES[name]
+    scan, mask = make_volume(shape, box, 0)
+    ws = torch.empty(ingest.workspace_bytes(*shape), dtype=torch.uint8, device="cuda")
+    ext = ingest.ingest_volume(ingest.upload(scan, "cuda", 0.25, -12.5), ingest.upload(mask, "cuda"), torch.empty((64, 64, 64), device="cuda"), workspace=ws)
+    assert ext.cpu().tolist() == [b - a for a, b in zip(*box)], ext
+    scratch = torch.empty(ingest.maps_to_scan_workspace_bytes(*shape), dtype=torch.uint8, device="cuda")
+    res = {"scan": list(shape), "kept": ext.cpu().tolist()}
+    for n in (1, 2):
+        maps = torch.rand((n, 64, 64, 64), device="cuda")
+        out = torch.empty((n, *shape[::-1]), device="cuda")
+        fn = lambda: ingest.maps_to_scan(maps, shape, ws, out=out, workspace=scratch)
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        us = queued_us(fn, steps)
+        written = n * int(np.prod(shape)) * 4
+        floor_us = written / (HBM_TBS * 1e12) * 1e6
+        res[f"n_maps_{n}"] = {"device_us_per_call": round(us, 1), "MB_written": round(written / 1e6, 2), "hbm_floor_us": round(floor_us, 2),
+                              "TBps": round(written / (us * 1e-6) / 1e12, 3), "share_of_hbm_ceiling": round(floor_us / us, 3)}
+    return res
+
+
 def add_kernel_stats(res, path):
     """Per-pass mean time from a rocprofv3 kernel_stats.csv of a ONE-case run, and its share of that pass's byte floor."""
     tot = {}
@@ -170,12 +198,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--case", type=str, default=None, choices=sorted(CASES))
     ap.add_argument("--mask_grid", type=str, default="same", choices=("same", "own"), help="own: the mask on a grid of 3/4 the extents, resampled first")
+    ap.add_argument("--maps_to_scan", action="store_true", help="time the inverse path (maps_to_scan, 1 and 2 maps) instead of the ingest cases")
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--kernel_stats", type=str, default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     res = {}
-    for name in ([a.case] if a.case else list(CASES)):
+    if a.maps_to_scan:
+        res["maps_to_scan_512x512x48"] = time_maps_to_scan(a.steps, a.warmup)
+        print(json.dumps({"case": "maps_to_scan_512x512x48", **res["maps_to_scan_512x512x48"]}), flush=True)
+        if a.json and os.path.exists(a.json):       # its rows join the ingest's
+            res = {**json.load(open(a.json)), **res}
+    for name in ([] if a.maps_to_scan else [a.case] if a.case else list(CASES)):
         key = name if a.mask_grid == "same" else name + "_mask_grid_own"
         res[key] = time_case(name, a.steps, a.warmup, a.mask_grid)
         if a.kernel_stats and a.case:
