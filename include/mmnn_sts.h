@@ -450,6 +450,31 @@ typedef struct {
 int64_t mmnn_maps_to_scan_workspace_bytes(int32_t x, int32_t y, int32_t z);
 int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, const float* maps, float* out, void* ws, void* stream);
 
+/* ---- DICOM slice decode: the PixelData bytes of an uncompressed single-frame series, sorted by position -> the raw voxel volume that
+ * mmnn_ingest_volume / mmnn_resample_mask take (csrc/dicom.hip).  `pixels` holds the z slices back to back, x (the column) fastest,
+ * little-endian words of bits_allocated bits.  Per voxel:
+ *   stored value   u = (word >> (high_bit + 1 - bits_stored)) & (2^bits_stored - 1): whatever sits in the unused bits is dropped.
+ *   signedness     v = u, or, for is_signed (PixelRepresentation 1), u sign-extended from bit bits_stored - 1.
+ *   integer output out_type is the NIfTI code of the (bits_allocated, is_signed) integer type -- 8: 2 / 256, 16: 512 / 4, 32: 768 / 8
+ *                  (unsigned / signed) -- and v is stored in that type; slice_scale must be NULL.  A series whose slices share one
+ *                  RescaleSlope / RescaleIntercept is decoded this way and the pair handed to the ingest like a NIfTI scl_slope.
+ *   float64 output out_type 64: slice k stores (double)v * slice_scale[2k] + slice_scale[2k + 1], a rounded multiply and a rounded add,
+ *                  never an FMA (the ingest's rule).  slice_scale: device pointer to [z][2] doubles (RescaleSlope, RescaleIntercept).
+ * `out` holds x*y*z elements, x fastest; every element of it is written and nothing else is.  One launch, no atomics, no host
+ * synchronisation: repeated calls are bit-identical.  Refused (status 1) before any launch: a null pointer, a non-positive extent,
+ * x*y*z >= 2^31, bits_allocated outside {8, 16, 32}, bits_stored outside 1..bits_allocated, high_bit outside bits_stored-1..
+ * bits_allocated-1, is_signed outside {0, 1}, an out_type that is neither 64 nor the integer type above, slice_scale inconsistent with
+ * out_type, pixels / out not aligned to their element size, overlapping pixels and out. */
+typedef struct {
+  int32_t x, y, z;                /* Columns, Rows, slices */
+  int32_t bits_allocated;         /* 8, 16, 32 */
+  int32_t bits_stored;            /* 1..bits_allocated */
+  int32_t high_bit;               /* bits_stored-1 .. bits_allocated-1 */
+  int32_t is_signed;              /* PixelRepresentation */
+  int32_t out_type;               /* NIfTI code of the (bits_allocated, is_signed) integer type, or 64 = float64 */
+} mmnn_decode_slices_desc;
+int mmnn_decode_slices(const mmnn_decode_slices_desc* d, const void* pixels, const double* slice_scale, void* out, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

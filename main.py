@@ -14,9 +14,11 @@ optimizer step per batch, F1 per epoch, best model by mean validation F1 saved a
 Deviations from the reference, all listed in SURVEY Appendix A: the published script cannot be imported (Q1) -- its third assert
 is dropped and CLASS_FREQUENCIES comes from the config; the validation loop moves `val_images` (Q10); the blender lives on the
 loss device (Q4); logging syncs once per epoch, not per micro-batch; `--preop` alone builds the standalone MLP (Q12).
-Datasets: `--image_loc DIR --key_loc key.csv --data_loc clinical.csv` (or the config's `Data:` section) trains on / evaluates local NIfTI
-patient directories -- the files' raw voxels are masked, cropped of empty slices and resized to 64^3 on the device
-(mmnn_sts_amd/data/ingest.py); DICOM / S3 stay outside the path.  `--inference --image_loc DIR --scan_space` also writes every class's
+Datasets: `--image_loc DIR --key_loc key.csv --data_loc clinical.csv` (or the config's `Data:` section) trains on / evaluates local
+patient directories, NIfTI files or uncompressed single-frame DICOM series (`patient/image/<series>/*.dcm`, `patient/mask/<series>/*.dcm`;
+the layout is detected per tree, `Data: format` forces one) -- the files' raw voxels are masked, cropped of empty slices and resized to
+64^3 on the device, DICOM slices are decoded there first (mmnn_sts_amd/data/ingest.py, dicom.py); compressed or multi-frame DICOM and S3
+stay outside the path.  `--inference --image_loc DIR --scan_space` also writes every class's
 attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).  Without an image location synthetic patients are used; the tabular-only
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).

@@ -113,6 +113,12 @@ class MapsToScanDesc(Structure):
     _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_maps", c_int32)]
 
 
+class DecodeSlicesDesc(Structure):
+    """mmnn_decode_slices_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("bits_allocated", c_int32), ("bits_stored", c_int32), ("high_bit", c_int32),
+                ("is_signed", c_int32), ("out_type", c_int32)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -211,6 +217,8 @@ def lib():
     L.mmnn_maps_to_scan_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.mmnn_maps_to_scan.restype = c_int32
     L.mmnn_maps_to_scan.argtypes = [POINTER(MapsToScanDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_decode_slices.restype = c_int32
+    L.mmnn_decode_slices.argtypes = [POINTER(DecodeSlicesDesc), c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

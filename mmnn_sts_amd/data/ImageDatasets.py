@@ -1,8 +1,17 @@
-"""Upstream's local-disk NIfTI datasets (data/ImageDatasets.py:26-56, 310-377, 422-470, 520-640) with their class names and constructor
-arguments.  The directory contract is upstream's: one directory per patient under `patient_directory`; in it, the file whose name starts
-with `scan` is the image and the other one the mask; the anonymised id is the first two `-`-separated fields of the directory name
-(:426); `patient_key` is a csv with the columns `Anon MRN` and `MRN` that maps it to the uid.  Labels come from this project's clinical
-csv (`ClinicalDatasets.LabelTable`), joined on `uid`.
+"""Upstream's local-disk image datasets (data/ImageDatasets.py:26-56, 196-292, 310-377, 422-470, 520-640) with their class names and
+constructor arguments.  The directory contract is upstream's: one directory per patient under `patient_directory`, in one of two layouts,
+detected per tree (`Data: format: auto | nifti | dicom` forces one; a tree that mixes them is refused):
+
+    NIfTI   the file whose name starts with `scan` is the image and the other one the mask; the anonymised id is the first two
+            `-`-separated fields of the directory name (:426)
+    DICOM   the sub-directories `image` and `mask` each hold one series, `<series>/*.dcm` or the files themselves (:26-56); the
+            anonymised id is the directory name when the key has it (data/utils.py:8-14), else as for NIfTI.  Uncompressed
+            single-frame series only (`mmnn_sts_amd.data.dicom`); the mask is a DICOM image series too (SEG / RTSTRUCT and a NIfTI
+            mask beside a DICOM scan are outside the path), always resampled into the scan's grid and binarised at 128 by default
+
+`patient_key` is a csv with the columns `Anon MRN` and `MRN` that maps the anonymised id to the uid.  Labels come from this project's
+clinical csv (`ClinicalDatasets.LabelTable`), joined on `uid`.  `ImageClassificationDataset` / `ImageSurvivalDataset` are upstream's
+names of the DICOM-layout classes; unlike upstream's, the survival one masks like its classification twin.
 
 `__getitem__` yields a `RawPatient` -- the files' voxels in their on-disk type, unmasked and uncropped -- in place of upstream's float
 volume: masking, empty-slice removal, the 64^3 area resize and the T1 / T2 stacking happen on the device in the collate function
@@ -20,13 +29,14 @@ import os
 import torch
 
 from ..exceptions.exceptions import ConfigurationError
-from . import nifti
+from . import dicom, nifti
 from .ClinicalDatasets import LabelTable
 from .ingest import MASK_RESAMPLE_MODES, RawPatient
 
 logger = logging.getLogger(__name__)
 RADIOMICS_UID = 'MRN'
 ANON_ID = 'Anon MRN'
+FORMATS = ('auto', 'nifti', 'dicom')
 
 
 def anon_id_of(directory_name):
@@ -41,10 +51,28 @@ def _read_key(path):
     return {r[ANON_ID].strip(): int(float(r[RADIOMICS_UID])) for r in rows}
 
 
+def layout_of(patient_path):
+    """'dicom' (the sub-directories `image` and `mask`), 'nifti' (a file named scan*) or None for one patient directory."""
+    entries = [e for e in os.listdir(patient_path) if not e.startswith('.')]
+    is_dicom = all(os.path.isdir(os.path.join(patient_path, d)) for d in ('image', 'mask'))
+    is_nifti = any(e.startswith('scan') and os.path.isfile(os.path.join(patient_path, e)) for e in entries)
+    if is_dicom and is_nifti:
+        raise ConfigurationError(f"{patient_path} holds both the DICOM layout (image/, mask/) and a NIfTI scan*: one format per tree")
+    if os.path.isdir(os.path.join(patient_path, 'image')) and not is_dicom:
+        raise ConfigurationError(f"{patient_path}: image/ without a mask/ series directory beside it (a NIfTI mask beside a DICOM scan, DICOM SEG "
+                                 "and RTSTRUCT are outside the path)")
+    return 'dicom' if is_dicom else ('nifti' if is_nifti else None)
+
+
 class ImageDataset(torch.utils.data.Dataset):
-    def __init__(self, patient_directory, patient_key, mask_resample='auto', log_grids=True):
+    format = 'auto'             # the layout a class is bound to; the constructor's `format` overrides it
+
+    def __init__(self, patient_directory, patient_key, mask_resample='auto', log_grids=True, format=None):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
+        format = str(self.format if format is None else format).lower()
+        if format not in FORMATS:
+            raise ConfigurationError(f"format {format!r} is none of {FORMATS}")
         self.mask_resample = mask_resample
         self.patient_directory = str(patient_directory)
         self.patients = sorted(x for x in os.listdir(self.patient_directory)
@@ -52,18 +80,45 @@ class ImageDataset(torch.utils.data.Dataset):
         self.patient_key = _read_key(patient_key)
         self.multimodal_identifier = 'image'
         self.transforms = None
+        self.layout = self._detect_layout() if format == 'auto' else format
         for p in self.patients:
-            if anon_id_of(p) not in self.patient_key:
-                raise ConfigurationError(f"patient directory {p} ({anon_id_of(p)}) has no row in the patient key {patient_key}")
+            if self._anon(p) not in self.patient_key:
+                raise ConfigurationError(f"patient directory {p} ({self._anon(p)}) has no row in the patient key {patient_key}")
             self._files(p)
         # the headers alone: a mask on another grid needs both geometries, and is refused here rather than in the first epoch
-        self.other_grid = [p for p in self.patients if self._check_grids(p, *(nifti.read_geometry(f) + (f,) for f in self._files(p)))]
+        self.other_grid = [p for p in self.patients if self._check_grids(p, *(self._geometry(f) + (f,) for f in self._files(p)))]
         if log_grids and self.other_grid:
             logger.info("%d of %d patients under %s have a mask on another grid than the scan's: it is resampled into the scan's grid on the device",
                         len(self.other_grid), len(self.patients), self.patient_directory)
 
+    def _detect_layout(self):
+        """The one layout of the tree; a tree that mixes the two (or a patient directory that is neither) is refused."""
+        found = {}
+        for p in self.patients:
+            found.setdefault(layout_of(os.path.join(self.patient_directory, p)), p)
+        if None in found:
+            raise ConfigurationError(f"patient directory {os.path.join(self.patient_directory, found[None])} holds neither a NIfTI scan* file "
+                                     "nor the DICOM sub-directories image/ and mask/")
+        if len(found) > 1:
+            raise ConfigurationError(f"{self.patient_directory} mixes the two layouts: {found['nifti']} is NIfTI, {found['dicom']} is DICOM; "
+                                     "one format per tree (Data.format forces one)")
+        return next(iter(found), 'nifti')
+
+    def _anon(self, patient):
+        """The anonymised id of a patient directory: for DICOM the name itself when the key has it (upstream data/utils.py:8-14)."""
+        if self.layout == 'dicom' and patient in self.patient_key:
+            return patient
+        return anon_id_of(patient)
+
     def _uid_of(self, patient):
-        return self.patient_key[anon_id_of(patient)]
+        return self.patient_key[self._anon(patient)]
+
+    def _geometry(self, path):
+        """(extents, affine or None) from the headers alone."""
+        if self.layout == 'dicom':
+            series = dicom.read_series(path, header_only=True)
+            return series.shape, series.affine
+        return nifti.read_geometry(path)
 
     @property
     def uids(self):
@@ -74,6 +129,12 @@ class ImageDataset(torch.utils.data.Dataset):
 
     def _files(self, patient):
         d = os.path.join(self.patient_directory, patient)
+        if self.layout == 'dicom':
+            for sub in ('image', 'mask'):
+                if not os.path.isdir(os.path.join(d, sub)):
+                    raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): no {sub}/ series directory in {d} (the DICOM layout; "
+                                             "a NIfTI mask beside a DICOM scan is outside the path)")
+            return os.path.join(d, 'image'), os.path.join(d, 'mask')
         files = sorted(f for f in os.listdir(d) if not f.startswith('.'))
         scans = [f for f in files if f.startswith('scan')]
         masks = [f for f in files if not f.startswith('scan')]
@@ -85,7 +146,8 @@ class ImageDataset(torch.utils.data.Dataset):
 
     def _load(self, patient):
         scan_path, mask_path = self._files(patient)
-        scan, mask = nifti.read(scan_path), nifti.read(mask_path)
+        read = dicom.read_series if self.layout == 'dicom' else nifti.read
+        scan, mask = read(scan_path), read(mask_path)
         self._check_grids(patient, (scan.shape, scan.affine, scan_path), (mask.shape, mask.affine, mask_path))
         return scan, mask
 
@@ -99,10 +161,11 @@ class ImageDataset(torch.utils.data.Dataset):
             return False
         if self.mask_resample == 'never':
             raise ConfigurationError(what + " (Data.mask_resample is 'never')")
+        geometry = "position / orientation" if self.layout == 'dicom' else "qform/sform"
         if saff is None and maff is None:
-            raise ConfigurationError(what + " and neither file has a qform/sform to resample by")
+            raise ConfigurationError(what + f" and neither file has a {geometry} to resample by")
         if saff is None or maff is None:
-            raise ConfigurationError(what + f" and {scan[2] if saff is None else mask[2]} has no qform/sform to resample by")
+            raise ConfigurationError(what + f" and {scan[2] if saff is None else mask[2]} has no {geometry} to resample by")
         return True
 
     def _index_of_uid(self, uid):
@@ -118,8 +181,9 @@ class ImageDataset(torch.utils.data.Dataset):
 class _LabelledNifti(ImageDataset):
     survival = False
 
-    def __init__(self, patient_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', log_grids=True):
-        super().__init__(patient_directory, patient_key, mask_resample, log_grids)
+    def __init__(self, patient_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', log_grids=True,
+                 format=None):
+        super().__init__(patient_directory, patient_key, mask_resample, log_grids, format)
         if slices:
             raise ConfigurationError("slices=True (2-D slices of a volume) is outside the MI355X path")
         if transforms is not None:
@@ -150,17 +214,32 @@ class NiftiSurvivalDataset(_LabelledNifti):
     survival = True
 
 
+class ImageClassificationDataset(_LabelledNifti):
+    """data/ImageDatasets.py:224-292: (image, label) from the DICOM layout."""
+    format = 'dicom'
+
+
+class ImageSurvivalDataset(_LabelledNifti):
+    """data/ImageDatasets.py:196-222: (image, events, durations) from the DICOM layout; masked like its classification twin (upstream
+    returns the unmasked image there)."""
+    format = 'dicom'
+    survival = True
+
+
 class _T1T2(_LabelledNifti):
-    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto'):
+    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', format=None):
         cls = NiftiSurvivalDataset if self.survival else NiftiImageDataset
-        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None, mask_resample)
-        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None, mask_resample)
-        super().__init__(t1_directory, clinical_data, patient_key, slices, transforms, mask_resample, log_grids=False)   # (t1 has reported)
+        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None, mask_resample, format=format)
+        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None, mask_resample, format=format)
+        if self.t1_dataset.layout != self.t2_dataset.layout:
+            raise ConfigurationError(f"{t1_directory} is a {self.t1_dataset.layout} tree and {t2_directory} a {self.t2_dataset.layout} one: one format for both")
+        super().__init__(t1_directory, clinical_data, patient_key, slices, transforms, mask_resample, log_grids=False,
+                         format=self.t1_dataset.layout)   # (t1 has reported)
         self.t1_patients, self.t2_patients = self.t1_dataset.patients, self.t2_dataset.patients
         # patients common to both trees, by anonymised id; kept as the T1 directory names
-        in_t2 = {anon_id_of(p): p for p in self.t2_patients}
-        self.patients = [p for p in self.t1_patients if anon_id_of(p) in in_t2]
-        self._t2_of = {p: in_t2[anon_id_of(p)] for p in self.patients}
+        in_t2 = {self.t2_dataset._anon(p): p for p in self.t2_patients}
+        self.patients = [p for p in self.t1_patients if self._anon(p) in in_t2]
+        self._t2_of = {p: in_t2[self._anon(p)] for p in self.patients}
 
     def _volumes(self, patient):
         return [self.t1_dataset._load(patient), self.t2_dataset._load(self._t2_of[patient])]

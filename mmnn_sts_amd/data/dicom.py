@@ -1,0 +1,399 @@
+"""A minimal DICOM reader for uncompressed single-frame series (numpy, mmap and struct only; pydicom / GDCM / SimpleITK are not
+dependencies): a directory of slice files -> the raw voxel bytes, the per-slice rescale pairs and the voxel-index -> mm matrix that the
+device ingest takes (`mmnn_sts_amd.data.ingest.decode_series`).  The host opens files, parses headers and copies bytes; it never touches
+a voxel value -- unpacking the stored bits, sign extension and per-slice rescaling run on the device (`mmnn_decode_slices`).
+
+Pinned to the published standard's element layout (PS3.5 / PS3.10): the 128-byte preamble and `DICM`; the file meta group (0002,xxxx),
+always explicit VR little endian; then the data set in the VR mode TransferSyntaxUID (0002,0010) names.  An explicit-VR element is
+tag (2 + 2 bytes), VR (2 characters) and a 2-byte length, or -- for OB OD OF OL OV OW SQ SV UC UN UR UT UV -- 2 reserved bytes and a 4-byte
+length; an implicit-VR element is tag and a 4-byte length.  A length of FFFFFFFF is "undefined": the value is a sequence of items
+(FFFE,E000), each of defined or undefined length, closed by (FFFE,E00D) / (FFFE,E0DD).  Parity with GDCM / SimpleITK (what upstream's
+`loadImage` / `loadMask` read through, data/utils.py:16-37) is unpinned: neither is installed where this was written.  What it is
+pinned to instead is that layout and the NIfTI twin: `synth_dicom.from_nifti_tree` turns a NIfTI tree into a DICOM one, and the two
+must give the same device batch bit for bit.
+
+Accepted: implicit VR little endian (1.2.840.10008.1.2) and explicit VR little endian (1.2.840.10008.1.2.1), SamplesPerPixel 1, one
+frame per file, BitsAllocated 8 / 16 / 32.  Refused, with the file named: big endian, deflated, every encapsulated (compressed) syntax,
+multi-frame and enhanced objects, colour, float / double pixel data.  DICOM SEG and RTSTRUCT masks are outside the path.
+
+`read_series(directory)` sorts the slices by position along the normal of ImageOrientationPatient -- file names and InstanceNumber play
+no part -- and forms the affine in RAS, the convention of `NiftiImage.affine`, so `nifti.index_map`, `KeptVolume.affine` and the
+`--scan_space` writer work on a series as they do on a NIfTI file.  Voxel index (i, j, k) is (column, row, slice).
+"""
+import logging
+import mmap
+import os
+import struct
+from dataclasses import dataclass, field
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from ..exceptions.exceptions import ConfigurationError
+
+logger = logging.getLogger(__name__)
+
+IMPLICIT_LE = "1.2.840.10008.1.2"
+EXPLICIT_LE = "1.2.840.10008.1.2.1"
+_REFUSED_SYNTAX = {"1.2.840.10008.1.2.2": "explicit VR big endian", "1.2.840.10008.1.2.1.99": "deflated explicit VR little endian",
+                   "1.2.840.10008.1.2.5": "RLE lossless (an encapsulated, compressed syntax)"}
+LONG_VRS = frozenset(("OB", "OD", "OF", "OL", "OV", "OW", "SQ", "SV", "UC", "UN", "UR", "UT", "UV"))
+UNDEFINED = 0xFFFFFFFF
+ITEM, ITEM_END, SEQUENCE_END = (0xFFFE, 0xE000), (0xFFFE, 0xE00D), (0xFFFE, 0xE0DD)
+PIXEL_DATA, FLOAT_PIXEL_DATA, DOUBLE_PIXEL_DATA = (0x7FE0, 0x0010), (0x7FE0, 0x0008), (0x7FE0, 0x0009)
+MAX_DEPTH = 32                               # nesting of undefined-length sequences followed before the file is called malformed
+
+# tag -> (field, VR); the VR is what an implicit-VR file does not say
+KEPT = {
+    (0x0008, 0x0016): ("sop_class_uid", "UI"), (0x0018, 0x0050): ("slice_thickness", "DS"), (0x0018, 0x0088): ("spacing_between_slices", "DS"),
+    (0x0020, 0x000E): ("series_uid", "UI"), (0x0020, 0x0013): ("instance_number", "IS"), (0x0020, 0x0032): ("position", "DS"),
+    (0x0020, 0x0037): ("orientation", "DS"), (0x0028, 0x0002): ("samples_per_pixel", "US"), (0x0028, 0x0008): ("number_of_frames", "IS"),
+    (0x0028, 0x0010): ("rows", "US"), (0x0028, 0x0011): ("columns", "US"), (0x0028, 0x0030): ("pixel_spacing", "DS"),
+    (0x0028, 0x0100): ("bits_allocated", "US"), (0x0028, 0x0101): ("bits_stored", "US"), (0x0028, 0x0102): ("high_bit", "US"),
+    (0x0028, 0x0103): ("pixel_representation", "US"), (0x0028, 0x1052): ("inter", "DS"), (0x0028, 0x1053): ("slope", "DS"),
+}
+_ARITY = {"position": 3, "orientation": 6, "pixel_spacing": 2}
+
+
+class NotDicomError(ConfigurationError):
+    """The file has no `DICM` magic (read_series skips such files)."""
+
+
+@dataclass
+class DicomFile:
+    """The kept elements of one file.  Absent elements are None, except slope / inter (1 / 0)."""
+    path: str
+    transfer_syntax: str
+    rows: Optional[int] = None
+    columns: Optional[int] = None
+    samples_per_pixel: Optional[int] = None
+    bits_allocated: Optional[int] = None
+    bits_stored: Optional[int] = None
+    high_bit: Optional[int] = None
+    pixel_representation: Optional[int] = None
+    slope: float = 1.0
+    inter: float = 0.0
+    pixel_spacing: Optional[Tuple[float, float]] = None
+    position: Optional[Tuple[float, float, float]] = None
+    orientation: Optional[Tuple[float, ...]] = None
+    slice_thickness: Optional[float] = None
+    spacing_between_slices: Optional[float] = None
+    series_uid: Optional[str] = None
+    instance_number: Optional[float] = None
+    number_of_frames: Optional[float] = None
+    sop_class_uid: Optional[str] = None
+    pixel_offset: Optional[int] = None       # byte offset of the PixelData value in the file; None: the file has no PixelData
+    pixel_length: Optional[int] = None       # its declared length
+    frame: Optional[np.ndarray] = None       # uint8 view of the rows * columns * bits_allocated / 8 voxel bytes (None with header_only)
+
+    @property
+    def has_image(self):
+        return self.rows is not None and self.columns is not None and self.pixel_offset is not None
+
+
+def _refuse(path, reason):
+    raise ConfigurationError(f"{path}: {reason}")
+
+
+def _need(buf, off, count, path):
+    if off + count > len(buf):
+        _refuse(path, f"malformed: an element header at byte {off} runs past the end of the file ({len(buf)} bytes)")
+
+
+def _element(buf, off, explicit, path):
+    """(tag, VR or None, length, offset of the value) of the element at `off`.  Item tags carry no VR in either mode."""
+    _need(buf, off, 8, path)
+    tag = struct.unpack_from("<HH", buf, off)
+    if not explicit or tag[0] == 0xFFFE:
+        return tag, None, struct.unpack_from("<I", buf, off + 4)[0], off + 8
+    vr = bytes(buf[off + 4:off + 6]).decode("latin-1")
+    if vr in LONG_VRS:
+        _need(buf, off, 12, path)
+        return tag, vr, struct.unpack_from("<I", buf, off + 8)[0], off + 12
+    return tag, vr, struct.unpack_from("<H", buf, off + 6)[0], off + 8
+
+
+def _skip_sequence(buf, off, explicit, path, depth=0):
+    """`off`: the first item of a sequence of undefined length; returns the offset behind its delimiter (FFFE,E0DD)."""
+    if depth > MAX_DEPTH:
+        _refuse(path, f"malformed: sequences nested deeper than {MAX_DEPTH}")
+    while True:
+        tag, _, length, voff = _element(buf, off, explicit, path)
+        if tag == SEQUENCE_END:
+            return voff
+        if tag != ITEM:
+            _refuse(path, f"malformed: ({tag[0]:04X},{tag[1]:04X}) at byte {off} where an item of a sequence was expected")
+        off = voff + length if length != UNDEFINED else _skip_item(buf, voff, explicit, path, depth)
+
+
+def _skip_item(buf, off, explicit, path, depth):
+    """`off`: the first element of an item of undefined length; returns the offset behind its delimiter (FFFE,E00D)."""
+    while True:
+        tag, vr, length, voff = _element(buf, off, explicit, path)
+        if tag == ITEM_END:
+            return voff
+        if length == UNDEFINED:              # a nested sequence; the content of an undefined-length UN is implicit VR (PS3.5 6.2.2)
+            off = _skip_sequence(buf, voff, explicit and vr != "UN", path, depth + 1)
+        else:
+            off = voff + length
+
+
+def _numbers(raw):
+    """A DS / IS value: split on the backslash, stripped of spaces and NULs, as Python floats (an empty value: no numbers)."""
+    return [float(p) for p in (q.strip(" \0") for q in raw.decode("latin-1").split("\\")) if p]
+
+
+def _value(buf, name, vr, voff, length, path):
+    raw = bytes(buf[voff:voff + length])
+    try:
+        if vr == "US":
+            return struct.unpack_from("<H", raw, 0)[0] if length >= 2 else None
+        if vr == "UI":
+            return raw.decode("latin-1").strip(" \0") or None
+        v = _numbers(raw)
+    except (ValueError, struct.error):
+        _refuse(path, f"malformed: {name} holds {raw[:32]!r}")
+    if name in _ARITY:
+        if not v:
+            return None
+        if len(v) != _ARITY[name]:
+            _refuse(path, f"malformed: {name} holds {len(v)} values, {_ARITY[name]} expected")
+        return tuple(v)
+    return v[0] if v else None
+
+
+def _transfer_syntax(buf, path):
+    """(TransferSyntaxUID, offset of the data set): the file meta group is explicit VR little endian whatever follows it."""
+    if len(buf) < 132 or bytes(buf[128:132]) != b"DICM":
+        raise NotDicomError(f"{path}: missing magic: no 'DICM' behind a 128-byte preamble (not a DICOM part-10 file)")
+    off, syntax = 132, None
+    while off + 8 <= len(buf) and struct.unpack_from("<H", buf, off)[0] == 0x0002:
+        tag, vr, length, voff = _element(buf, off, True, path)
+        if length == UNDEFINED:
+            _refuse(path, "malformed: an element of undefined length in the file meta group")
+        if tag == (0x0002, 0x0010):
+            syntax = bytes(buf[voff:voff + length]).decode("latin-1").strip(" \0")
+        off = voff + length
+    if not syntax:
+        _refuse(path, "no TransferSyntaxUID (0002,0010) in the file meta group")
+    return syntax, off
+
+
+def _check_syntax(syntax, path):
+    if syntax in (IMPLICIT_LE, EXPLICIT_LE):
+        return syntax == EXPLICIT_LE
+    if syntax in _REFUSED_SYNTAX:
+        _refuse(path, f"transfer syntax {syntax} ({_REFUSED_SYNTAX[syntax]}) is outside the path: only uncompressed little endian files are read")
+    if syntax.startswith("1.2.840.10008.1.2.4."):
+        _refuse(path, f"transfer syntax {syntax} is encapsulated (compressed: JPEG / JPEG-LS / JPEG 2000 / MPEG / HEVC), which is outside the "
+                      "path: decompress the series first")
+    _refuse(path, f"transfer syntax {syntax} is not supported: only {IMPLICIT_LE} and {EXPLICIT_LE} are read")
+
+
+def _validate(f: DicomFile, size: int):
+    """The refusals of a file that holds an image."""
+    path = f.path
+    if f.samples_per_pixel is not None and f.samples_per_pixel != 1:
+        _refuse(path, f"SamplesPerPixel {f.samples_per_pixel}: colour images are outside the path (1 expected)")
+    if f.number_of_frames is not None and f.number_of_frames > 1:
+        _refuse(path, f"NumberOfFrames {f.number_of_frames:g}: multi-frame and enhanced DICOM objects are outside the path (one frame per file)")
+    if f.rows < 1 or f.columns < 1:
+        _refuse(path, f"Rows {f.rows}, Columns {f.columns}")
+    if f.bits_allocated not in (8, 16, 32):
+        _refuse(path, f"BitsAllocated {f.bits_allocated} is none of 8, 16, 32")
+    if f.bits_stored is None:
+        f.bits_stored = f.bits_allocated
+    if not 1 <= f.bits_stored <= f.bits_allocated:
+        _refuse(path, f"BitsStored {f.bits_stored} outside 1..{f.bits_allocated} (BitsAllocated)")
+    if f.high_bit is None:
+        f.high_bit = f.bits_stored - 1
+    if not f.bits_stored - 1 <= f.high_bit <= f.bits_allocated - 1:
+        _refuse(path, f"HighBit {f.high_bit} outside {f.bits_stored - 1}..{f.bits_allocated - 1} (BitsStored - 1 .. BitsAllocated - 1)")
+    if f.pixel_representation not in (0, 1):
+        _refuse(path, f"PixelRepresentation {f.pixel_representation} is neither 0 nor 1")
+    if f.pixel_length == UNDEFINED:
+        _refuse(path, "PixelData of undefined length (encapsulated, i.e. compressed, frames) is outside the path")
+    need = f.rows * f.columns * f.bits_allocated // 8
+    have = min(f.pixel_length, size - f.pixel_offset)
+    if have < need:
+        _refuse(path, f"truncated: {have} bytes of PixelData, {need} expected for {f.rows} x {f.columns} x {f.bits_allocated} bits")
+    return need
+
+
+def read_file(path, header_only=False) -> DicomFile:
+    """Parse one file up to PixelData (7FE0,0010).  `frame` is a zero-copy uint8 view of the file's voxel bytes (the file stays mapped
+    while the view lives); with `header_only` no voxel byte is read and `frame` stays None."""
+    path = str(path)
+    size = os.path.getsize(path)
+    if size < 132:
+        raise NotDicomError(f"{path}: missing magic: {size} bytes, shorter than a preamble (not a DICOM part-10 file)")
+    with open(path, "rb") as fh:
+        buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+    try:
+        syntax, off = _transfer_syntax(buf, path)
+        explicit = _check_syntax(syntax, path)
+        f = DicomFile(path, syntax)
+        while off < size:
+            tag, vr, length, voff = _element(buf, off, explicit, path)
+            if tag in (FLOAT_PIXEL_DATA, DOUBLE_PIXEL_DATA):
+                _refuse(path, f"{'float' if tag == FLOAT_PIXEL_DATA else 'double float'} pixel data ({tag[0]:04X},{tag[1]:04X}) is outside the path: "
+                              "only integer PixelData (7FE0,0010) is read")
+            if tag == PIXEL_DATA:
+                f.pixel_offset, f.pixel_length = voff, length
+                break
+            if tag > PIXEL_DATA:
+                break
+            if tag[0] == 0xFFFE:
+                _refuse(path, f"malformed: item tag ({tag[0]:04X},{tag[1]:04X}) at byte {off} outside a sequence")
+            if length == UNDEFINED:
+                off = _skip_sequence(buf, voff, explicit and vr != "UN", path)
+                continue
+            if voff + length > size:
+                _refuse(path, f"malformed: element ({tag[0]:04X},{tag[1]:04X}) at byte {off} declares {length} bytes, {size - voff} are left")
+            if tag in KEPT:
+                name, kvr = KEPT[tag]
+                v = _value(buf, name, kvr, voff, length, path)
+                if v is not None:
+                    setattr(f, name, v)
+            off = voff + length
+        if f.has_image:
+            need = _validate(f, size)
+            if not header_only:
+                f.frame = np.frombuffer(buf, dtype=np.uint8, count=need, offset=f.pixel_offset)
+    except Exception:
+        buf.close()
+        raise
+    if f.frame is None:
+        buf.close()
+    return f
+
+
+@dataclass
+class DicomSeries:
+    """A sorted series: what `ingest.decode_series` uploads.  `shape`: (Columns, Rows, slices) = the extents along voxel index (i, j, k);
+    `affine`: 4x4 float64 voxel index -> mm in RAS, or None (a single slice without geometry); `slopes`, `inters`: RescaleSlope /
+    RescaleIntercept per sorted slice; `frames`: per sorted slice a uint8 view of that file's PixelData bytes (empty with header_only)."""
+    shape: Tuple[int, int, int]
+    affine: Optional[np.ndarray]
+    path: str
+    bits_allocated: int
+    bits_stored: int
+    high_bit: int
+    signed: bool
+    slopes: List[float]
+    inters: List[float]
+    frames: List[np.ndarray] = field(default_factory=list)
+    files: List[str] = field(default_factory=list)       # the slices' paths in sorted order
+
+    def uniform_scale(self):
+        """(slope, inter) when every slice carries the same pair bit for bit, else None."""
+        pairs = {(struct.pack("<d", s), struct.pack("<d", i)) for s, i in zip(self.slopes, self.inters)}
+        return (float(self.slopes[0]), float(self.inters[0])) if len(pairs) == 1 else None
+
+
+def series_directory(directory):
+    """`directory` itself when it holds regular files, else its single sub-directory (upstream takes `os.listdir(...)[0]`)."""
+    directory = str(directory)
+    if not os.path.isdir(directory):
+        raise ConfigurationError(f"{directory}: not a directory, so no DICOM series can be read from it")
+    entries = sorted(e for e in os.listdir(directory) if not e.startswith("."))
+    if any(os.path.isfile(os.path.join(directory, e)) for e in entries):
+        return directory
+    dirs = [e for e in entries if os.path.isdir(os.path.join(directory, e))]
+    if len(dirs) > 1:
+        raise ConfigurationError(f"{directory}: {len(dirs)} sub-directories ({', '.join(dirs[:4])}{', ...' if len(dirs) > 4 else ''}) and no files: "
+                                 "one series directory is expected")
+    if not dirs:
+        raise ConfigurationError(f"{directory}: no DICOM files")
+    inner = os.path.join(directory, dirs[0])
+    if not any(os.path.isfile(os.path.join(inner, e)) for e in os.listdir(inner) if not e.startswith(".")):
+        raise ConfigurationError(f"{inner}: no DICOM files")
+    return inner
+
+
+def _geometry(slices, directory):
+    """(slices sorted along the normal, LPS 4x4 matrix or None)."""
+    z = len(slices)
+    missing = [(s, n) for s in slices for n in ("position", "orientation", "pixel_spacing") if getattr(s, n) is None]
+    if missing:
+        if z > 1:
+            s, n = missing[0]
+            names = {"position": "ImagePositionPatient", "orientation": "ImageOrientationPatient", "pixel_spacing": "PixelSpacing"}
+            _refuse(s.path, f"no {names[n]} in a series of {z} slices: without geometry neither the slice order nor a resampling map exists")
+        return slices, None
+    first = slices[0]
+    ori = np.asarray(first.orientation, dtype=np.float64)
+    for s in slices[1:]:
+        if np.abs(np.asarray(s.orientation, dtype=np.float64) - ori).max() > 1e-4:
+            raise ConfigurationError(f"{directory}: {first.path} and {s.path} differ in ImageOrientationPatient ({first.orientation} and {s.orientation})")
+    r, c = ori[:3], ori[3:]
+    n = np.cross(r, c)
+    if not np.isfinite(ori).all() or np.linalg.norm(n) < 1e-6:
+        _refuse(first.path, f"ImageOrientationPatient {first.orientation} spans no plane")
+    along = [float(n @ np.asarray(s.position, dtype=np.float64)) for s in slices]
+    order = sorted(range(z), key=lambda i: along[i])
+    slices = [slices[i] for i in order]
+    along = [along[i] for i in order]
+    gaps = np.diff(along)
+    for i, g in enumerate(gaps):
+        if g < 1e-6:
+            raise ConfigurationError(f"{directory}: duplicate position: {slices[i].path} and {slices[i + 1].path} lie {g:.3g} mm apart along the slice normal")
+    if z > 2 and np.abs(gaps - gaps.mean()).max() > 0.01 * gaps.mean():
+        logger.warning("%s: non-uniform slice spacing (gaps between %.6g and %.6g mm, mean %.6g): the volume is read as if the slices were "
+                       "evenly spaced between the first and the last", directory, gaps.min(), gaps.max(), gaps.mean())
+    first, last = slices[0], slices[-1]
+    p0 = np.asarray(first.position, dtype=np.float64)
+    m = np.eye(4, dtype=np.float64)
+    m[:3, 0] = r * first.pixel_spacing[1]
+    m[:3, 1] = c * first.pixel_spacing[0]
+    if z > 1:
+        m[:3, 2] = (np.asarray(last.position, dtype=np.float64) - p0) / (z - 1)
+    else:
+        step = first.spacing_between_slices or first.slice_thickness or 1.0
+        m[:3, 2] = n * step
+    m[:3, 3] = p0
+    return slices, m
+
+
+def read_series(directory, header_only=False) -> DicomSeries:
+    """The series under `directory` (see `series_directory`), sorted by position.  Files without the magic or without Rows / PixelData
+    (a DICOMDIR, a report) are skipped; of several SeriesInstanceUIDs the first in sorted order is read."""
+    d = series_directory(directory)
+    slices, skipped = [], 0
+    for name in sorted(os.listdir(d)):
+        p = os.path.join(d, name)
+        if name.startswith(".") or not os.path.isfile(p):
+            continue
+        try:
+            f = read_file(p, header_only)
+        except NotDicomError:
+            skipped += 1
+            continue
+        if not f.has_image:
+            skipped += 1
+            continue
+        slices.append(f)
+    if skipped:
+        logger.info("%s: %d file(s) without the DICM magic or without an image skipped", d, skipped)
+    if not slices:
+        raise ConfigurationError(f"{d}: no DICOM image files ({skipped} file(s) without the DICM magic or without Rows / PixelData skipped)")
+    uids = sorted({s.series_uid or "" for s in slices})
+    if len(uids) > 1:
+        logger.warning("%s: %d SeriesInstanceUIDs; %s is read, ignored: %s", d, len(uids), uids[0], ", ".join(uids[1:]))
+        slices = [s for s in slices if (s.series_uid or "") == uids[0]]
+    first = slices[0]
+    for s in slices[1:]:
+        for name, what in (("rows", "Rows"), ("columns", "Columns"), ("bits_allocated", "BitsAllocated"), ("bits_stored", "BitsStored"),
+                           ("high_bit", "HighBit"), ("pixel_representation", "PixelRepresentation")):
+            if getattr(s, name) != getattr(first, name):
+                raise ConfigurationError(f"{d}: {first.path} and {s.path} differ in {what} ({getattr(first, name)} and {getattr(s, name)})")
+    slices, lps = _geometry(slices, d)
+    affine = None
+    if lps is not None:
+        affine = lps.copy()
+        affine[:2, :] *= -1.0                # LPS -> RAS: the convention of NiftiImage.affine
+        affine += 0.0                        # (no negative zeros)
+    first = slices[0]
+    return DicomSeries((int(first.columns), int(first.rows), len(slices)), affine, d, int(first.bits_allocated), int(first.bits_stored),
+                       int(first.high_bit), bool(first.pixel_representation), [float(s.slope) for s in slices], [float(s.inter) for s in slices],
+                       [] if header_only else [s.frame for s in slices], [s.path for s in slices])

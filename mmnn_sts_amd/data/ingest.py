@@ -4,7 +4,8 @@ What upstream's NIfTI datasets do per patient and modality in `__getitem__` (dat
 every all-zero slice dropped along each axis, Resize((64,64,64)), T1 / T2 stacked along the channel axis) runs here on the device, from
 the file's voxels in their on-disk type.  The host only uploads bytes (pinned, non-blocking) and enqueues; it never waits.
 
-    upload(volume, device)                          host volume (NiftiImage or ndarray) -> DeviceVolume
+    upload(volume, device)                          host volume (NiftiImage, DicomSeries or ndarray) -> DeviceVolume
+    decode_series(series, device)                   a sorted DICOM series -> DeviceVolume: the slices' bytes decoded on device (mmnn_decode_slices)
     resample_mask(mask, scan_shape, index_map)      a mask drawn on another grid -> uint8 bytes on the scan's grid (mmnn_resample_mask)
     ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
     collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
@@ -15,6 +16,11 @@ A mask on another grid (a T2 contour used on the T1 scan, a resliced export, a m
 upstream's DICOM datasets pass through `sitk.Resample(mask, image)` and `> 128` (data/ImageDatasets.py:145-152, :246-257); here the
 host forms one 3x4 matrix from the two headers (`nifti.index_map`) and the device does the rest.  `Data: mask_resample` selects when:
 'auto' (only when the extents differ), 'geometry' (also when equal extents sit elsewhere in space), 'never'.
+
+A DICOM series (`dicom.read_series`) takes one more step in front: its slices' PixelData bytes are uploaded as the files hold them and
+`mmnn_decode_slices` unpacks the stored bits, extends the sign and, where the slices differ in RescaleSlope / RescaleIntercept, rescales
+per slice.  A DICOM (scan, mask) pair always passes through `resample_mask` -- upstream always runs `sitk.Resample(mask, image)` and
+`mask > 128` on that path -- with the identity map when the two series share one grid, and its default threshold is 128.
 """
 import ctypes
 from dataclasses import dataclass
@@ -26,11 +32,14 @@ import torch
 from .. import _lib
 from ..exceptions.exceptions import ConfigurationError
 from . import nifti
+from .dicom import DicomSeries
 from .nifti import NiftiImage
 
 SIZE = 64                                    # MMNN_INGEST_SIZE
 MASK_RESAMPLE_MODES = ("auto", "geometry", "never")
 GEOMETRY_TOLERANCE = 1e-3                    # voxels: 'geometry' resamples when a corner of the scan grid maps further from itself
+NIFTI_MASK_THRESHOLD, DICOM_MASK_THRESHOLD = 0.5, 128.0          # defaults of `Data: mask_threshold` (upstream: `mask > 128`)
+IDENTITY_MAP = np.eye(4, dtype=np.float64)[:3]
 TYPE_CODES = {np.dtype("uint8"): 2, np.dtype("int16"): 4, np.dtype("int32"): 8, np.dtype("float32"): 16, np.dtype("float64"): 64,
               np.dtype("int8"): 256, np.dtype("uint16"): 512, np.dtype("uint32"): 768}
 
@@ -38,13 +47,15 @@ TYPE_CODES = {np.dtype("uint8"): 2, np.dtype("int16"): 4, np.dtype("int32"): 8, 
 @dataclass
 class DeviceVolume:
     """A scan's voxels on the device as the file holds them: `data` is a flat uint8 tensor of x*y*z elements of NIfTI type `datatype`,
-    x fastest.  `affine`: the file's voxel index -> mm matrix when it has one."""
+    x fastest.  `affine`: the file's voxel index -> mm matrix when it has one.  `from_dicom`: decoded from a DICOM series (its mask
+    is always resampled, and binarised at 128 by default)."""
     data: torch.Tensor
     shape: Tuple[int, int, int]
     datatype: int
     slope: float = 1.0
     inter: float = 0.0
     affine: Optional[np.ndarray] = None
+    from_dicom: bool = False
 
 
 @dataclass
@@ -58,9 +69,10 @@ class KeptVolume:
 
 @dataclass
 class RawPatient:
-    """What a NIfTI dataset's `__getitem__` yields in place of a float volume: per modality the (scan, mask) pair, still raw."""
+    """What an image dataset's `__getitem__` yields in place of a float volume: per modality the (scan, mask) pair, still raw (two
+    NiftiImages, or two DicomSeries)."""
     uid: int
-    volumes: List[Tuple[NiftiImage, NiftiImage]]
+    volumes: List[Tuple[object, object]]
 
 
 def _host_bytes(raw: np.ndarray) -> np.ndarray:
@@ -73,9 +85,12 @@ def _host_bytes(raw: np.ndarray) -> np.ndarray:
 
 
 def upload(volume, device, slope: float = 1.0, inter: float = 0.0) -> DeviceVolume:
-    """Host -> device, in the on-disk type.  `volume`: a NiftiImage (its slope / inter are used) or an (x, y, z) ndarray."""
+    """Host -> device, in the on-disk type.  `volume`: a NiftiImage (its slope / inter are used), a DicomSeries (`decode_series`) or
+    an (x, y, z) ndarray."""
     if isinstance(volume, DeviceVolume):
         return volume
+    if isinstance(volume, DicomSeries):
+        return decode_series(volume, device)
     affine = None
     if isinstance(volume, NiftiImage):
         raw, slope, inter, affine = volume.raw, volume.slope, volume.inter, volume.affine
@@ -85,6 +100,45 @@ def upload(volume, device, slope: float = 1.0, inter: float = 0.0) -> DeviceVolu
         raw = raw.astype(raw.dtype.newbyteorder("="))
     host = torch.from_numpy(_host_bytes(raw)).pin_memory()
     return DeviceVolume(host.to(device, non_blocking=True), tuple(int(s) for s in raw.shape), TYPE_CODES[raw.dtype], float(slope), float(inter), affine)
+
+
+def _integer_code(bits_allocated: int, signed: bool) -> int:
+    return TYPE_CODES[np.dtype(f"{'i' if signed else 'u'}{bits_allocated // 8}")]
+
+
+def decode_series(series: DicomSeries, device) -> DeviceVolume:
+    """A sorted DICOM series -> its voxels on the device, (Columns, Rows, slices) with the column fastest.  One pinned staging buffer
+    (the per-slice scale table when it is needed, then the slices' bytes in sorted order), one non-blocking copy and one
+    `mmnn_decode_slices` on the current stream; the host copies bytes and touches no voxel value.  When every slice carries the same
+    RescaleSlope / RescaleIntercept and the ingest's descriptor holds that pair exactly (it carries float32, as a NIfTI header does),
+    the volume keeps the integer type of (BitsAllocated, PixelRepresentation) and the pair goes into `slope` / `inter`, which the
+    ingest applies in fp64 like a NIfTI scl_slope; otherwise the kernel rescales per slice and the volume is float64, slope 1, inter 0."""
+    if not series.frames:
+        raise ValueError(f"decode_series: {series.path} was read with header_only: it holds no voxel bytes")
+    device = torch.device(device)
+    x, y, z = (int(v) for v in series.shape)
+    frame_bytes = x * y * (series.bits_allocated // 8)
+    if len(series.frames) != z or any(f.dtype != np.uint8 or f.size != frame_bytes for f in series.frames):
+        raise ValueError(f"decode_series: {series.path}: {z} slices of {frame_bytes} bytes expected")
+    scale = series.uniform_scale()
+    integer = scale is not None and all(float(np.float32(v)) == v for v in scale)
+    table_bytes = 0 if integer else z * 16
+    stage = torch.empty(table_bytes + z * frame_bytes, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    if not integer:
+        host[:z * 16].view(np.float64)[:] = np.asarray([v for pair in zip(series.slopes, series.inters) for v in pair], dtype=np.float64)
+    for k, frame in enumerate(series.frames):
+        host[table_bytes + k * frame_bytes:table_bytes + (k + 1) * frame_bytes] = frame
+    code = _integer_code(series.bits_allocated, series.signed) if integer else TYPE_CODES[np.dtype("float64")]
+    desc = _lib.DecodeSlicesDesc(x, y, z, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed), code)
+    with torch.cuda.device(device):
+        staged = stage.to(device, non_blocking=True)
+        out = torch.empty(x * y * z * (series.bits_allocated // 8 if integer else 8), dtype=torch.uint8, device=device)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mmnn_decode_slices(ctypes.byref(desc), staged.data_ptr() + table_bytes, None if integer else staged.data_ptr(),
+                                                 out.data_ptr(), stream), "mmnn_decode_slices")
+    slope, inter = scale if integer else (1.0, 0.0)
+    return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
 
 
 def workspace_bytes(x: int, y: int, z: int) -> int:
@@ -137,6 +191,8 @@ def mask_index_map(scan, mask, mode: str = "auto"):
     if mode not in MASK_RESAMPLE_MODES:
         raise ConfigurationError(f"mask_resample {mode!r} is none of {MASK_RESAMPLE_MODES}")
     same = tuple(scan.shape) == tuple(mask.shape)
+    if is_dicom(scan) or is_dicom(mask):
+        return _dicom_index_map(scan, mask, mode, same)
     if same:
         if mode != "geometry" or scan.affine is None or mask.affine is None:
             return None
@@ -147,18 +203,49 @@ def mask_index_map(scan, mask, mode: str = "auto"):
     return nifti.index_map(scan, mask)
 
 
+def is_dicom(volume) -> bool:
+    return isinstance(volume, DicomSeries) or bool(getattr(volume, "from_dicom", False))
+
+
+def default_threshold(scan) -> float:
+    """The `mask_threshold` a pair is binarised at when none is configured: 128 behind a DICOM scan (upstream's `mask > 128`), else 0.5."""
+    return DICOM_MASK_THRESHOLD if is_dicom(scan) else NIFTI_MASK_THRESHOLD
+
+
+def _dicom_index_map(scan, mask, mode, same):
+    """A DICOM pair is always resampled: by the two geometries, by the identity when they are one grid bit for bit, or -- a series
+    without geometry (a single slice without position) -- by the identity when the extents agree."""
+    if not (is_dicom(scan) and is_dicom(mask)):
+        raise ConfigurationError("a NIfTI mask beside a DICOM scan (or the reverse) is outside the path: both come from one format")
+    what = f"scan extent {tuple(scan.shape)} ({getattr(scan, 'path', '') or 'scan'}), mask extent {tuple(mask.shape)} ({getattr(mask, 'path', '') or 'mask'})"
+    if not same and mode == "never":
+        raise ConfigurationError(what + ": they differ and mask_resample is 'never'")
+    if scan.affine is None or mask.affine is None:
+        if not same:
+            raise ConfigurationError(what + ": they differ and a series has no geometry to resample by")
+        return IDENTITY_MAP
+    if same and np.array_equal(np.asarray(scan.affine), np.asarray(mask.affine)):
+        return IDENTITY_MAP
+    return nifti.index_map(scan, mask)
+
+
 def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
-                  index_map=None, threshold: float = 0.5) -> torch.Tensor:
+                  index_map=None, threshold: Optional[float] = None) -> torch.Tensor:
     """Enqueue the ingest of one volume on the current stream: `out_plane` (a contiguous (64,64,64) fp32 CUDA view, e.g. batch[n, c]) receives
     the masked, compacted, area-resized scan; returns `extents` (3 x int32 on the device: kept slices along x, y, z), readable after
     the next synchronisation.  `scan` / `mask`: DeviceVolume, NiftiImage or ndarray (host volumes are uploaded first).  When the
     extents differ, or an `index_map` is given, the mask is first resampled into the scan's grid (`resample_mask`, binarised at
     `threshold`); without `index_map` the map comes from the two volumes' affines, and differing extents without them are refused.
-    Equal extents without `index_map` are the voxelwise path."""
+    Equal extents without `index_map` are the voxelwise path -- except for a DICOM pair, which is always resampled.  `threshold`
+    None: 0.5, or 128 behind a DICOM scan."""
     if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and tuple(out_plane.shape) == (SIZE,) * 3):
         raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, got {tuple(out_plane.shape)} {out_plane.dtype} on {out_plane.device}")
     dev = out_plane.device
     scan, mask = upload(scan, dev), upload(mask, dev)
+    if threshold is None:
+        threshold = default_threshold(scan)
+    if index_map is None and (is_dicom(scan) or is_dicom(mask)):
+        index_map = mask_index_map(scan, mask)
     if index_map is None and scan.shape != mask.shape:
         if scan.affine is None or mask.affine is None:
             raise ValueError(f"ingest: scan extent {scan.shape} differs from the mask's {mask.shape}")
@@ -234,10 +321,11 @@ def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor,
 
 
 def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
-                    mask_threshold: float = 0.5, keep_workspaces: bool = False):
+                    mask_threshold: Optional[float] = None, keep_workspaces: bool = False):
     """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
     issued before the first kernel, so the copies of one volume run beside the passes of the one before it.  A mask on another grid
-    than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`.
+    than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`
+    (None: 0.5; 128 for a DICOM pair, which is always resampled).
     With `keep_workspaces` every volume is ingested with a workspace of its own and a third value is returned: volumes[n][c], the
     `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan."""
     n, c = len(patients), len(patients[0])
@@ -260,18 +348,18 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
 
 
 class IngestCollate:
-    """collate_fn of the NIfTI datasets: items are (x, events, durations) or (x, labels) with x a RawPatient or
+    """collate_fn of the NIfTI and DICOM datasets: items are (x, events, durations) or (x, labels) with x a RawPatient or
     {'image': RawPatient, 'clinical': tensor}; returns (x, events, durations) (durations None for classification items) with the image
     batch on `device`.  The extents of every batch are kept in `pending` until `take_empty()` reads them: call it where the epoch
     synchronises anyway, never per batch.  `mask_resample` / `mask_threshold`: the `Data:` keys of the same names (see `collate_volumes`).
     `keep_workspaces` (off: nothing is retained, as training wants it): `last_volumes[n][c]` holds the `KeptVolume` of every (patient,
     modality) of the LAST batch, for `maps_to_scan`."""
 
-    def __init__(self, device, mask_resample: str = "auto", mask_threshold: float = 0.5, keep_workspaces: bool = False):
+    def __init__(self, device, mask_resample: str = "auto", mask_threshold: Optional[float] = 0.5, keep_workspaces: bool = False):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         self.device = torch.device(device)
-        self.mask_resample, self.mask_threshold = mask_resample, float(mask_threshold)
+        self.mask_resample, self.mask_threshold = mask_resample, (None if mask_threshold is None else float(mask_threshold))
         self.pending: List[Tuple[List[int], torch.Tensor]] = []
         self.keep_workspaces = bool(keep_workspaces)
         self.last_volumes: List[List[KeptVolume]] = []

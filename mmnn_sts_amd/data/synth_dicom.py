@@ -1,0 +1,208 @@
+"""A minimal DICOM writer and the DICOM twin of a `synth_nifti.write_tree` tree, for the tests, the timing tool and a first run of
+`main.py --image_loc` on the DICOM layout (`mmnn_sts_amd.data.ImageDatasets`).  A test and demo aid, like `synth_nifti`: it writes what
+`mmnn_sts_amd.data.dicom` reads (uncompressed, one frame per file, explicit VR little endian, or implicit on request) and nothing else.
+
+    <root>/images/t1/SYN-0007-t1-a/image/series_1/0003.dcm ...     one file per slice, names in a seeded random order
+    <root>/images/t1/SYN-0007-t1-a/mask/series_1/0011.dcm ...      the mask as an 8-bit image series, 0 / 255
+    <root>/key.csv, clinical.csv, train_uids.txt, val_uids.txt     copied from the NIfTI tree
+
+    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR
+
+The twin holds the same voxels -- slice k, row j, column i is the NIfTI voxel (i, j, k) -- and the same geometry: ImagePositionPatient,
+ImageOrientationPatient and PixelSpacing are the NIfTI affine's columns in LPS (a sheared or left-handed affine has no such form and is
+refused).  Decimal strings hold at most 16 characters, as the standard says, so the geometry agrees with the NIfTI header's to about
+1e-10 relative, not bit for bit.
+"""
+import argparse
+import os
+import shutil
+import struct
+
+import numpy as np
+
+from ..exceptions.exceptions import ConfigurationError
+from . import nifti
+from .dicom import EXPLICIT_LE, IMPLICIT_LE, LONG_VRS
+
+MR_IMAGE_STORAGE = "1.2.840.10008.5.1.4.1.1.4"
+UID_ROOT = "1.2.3.4.5"                       # not a registered root: synthetic files only
+
+
+def ds(value) -> str:
+    """A decimal string of at most 16 characters: the shortest repr when it fits, else the most significant digits that do."""
+    value = float(value)
+    text = repr(value)
+    if text.endswith(".0"):
+        text = text[:-2]
+    digits = 17
+    while len(text) > 16 and digits > 1:
+        digits -= 1
+        text = f"{value:.{digits}g}"
+    return text
+
+
+def _element(group, elem, vr, value: bytes, explicit: bool) -> bytes:
+    if len(value) % 2:
+        value += b"\0" if vr in ("UI", "OB", "OW", "UN") else b" "
+    if not explicit:
+        return struct.pack("<HHI", group, elem, len(value)) + value
+    if vr in LONG_VRS:
+        return struct.pack("<HH2sHI", group, elem, vr.encode(), 0, len(value)) + value
+    return struct.pack("<HH2sH", group, elem, vr.encode(), len(value)) + value
+
+
+def _text(values) -> bytes:
+    return "\\".join(values if isinstance(values, (list, tuple)) else [values]).encode("ascii")
+
+
+def file_bytes(pixels, bits_stored=None, high_bit=None, position=None, orientation=None, pixel_spacing=None, slope=None, inter=None,
+               series_uid=UID_ROOT + ".1", instance_number=1, explicit=True, slice_thickness=None, spacing_between_slices=None,
+               sop_instance_uid=UID_ROOT + ".1.1") -> bytes:
+    """One slice as a part-10 file.  `pixels`: a (Rows, Columns) array of uint8 / int8 / uint16 / int16 / uint32 / int32, written as
+    it is (the caller has placed the stored bits); geometry and rescale elements are left out when None."""
+    a = np.ascontiguousarray(pixels)
+    if a.ndim != 2 or a.dtype.kind not in "iu" or a.dtype.itemsize not in (1, 2, 4):
+        raise ConfigurationError(f"a slice is a 2-D array of 8, 16 or 32-bit integers, got {a.dtype} {a.shape}")
+    bits = a.dtype.itemsize * 8
+    bits_stored = bits if bits_stored is None else int(bits_stored)
+    high_bit = bits_stored - 1 if high_bit is None else int(high_bit)
+    us = lambda v: struct.pack("<H", v)
+    syntax = EXPLICIT_LE if explicit else IMPLICIT_LE
+    meta = b"".join([_element(0x0002, 0x0001, "OB", b"\0\1", True), _element(0x0002, 0x0002, "UI", _text(MR_IMAGE_STORAGE), True),
+                     _element(0x0002, 0x0003, "UI", _text(sop_instance_uid), True), _element(0x0002, 0x0010, "UI", _text(syntax), True),
+                     _element(0x0002, 0x0012, "UI", _text(UID_ROOT + ".0"), True)])
+    meta = _element(0x0002, 0x0000, "UL", struct.pack("<I", len(meta)), True) + meta
+    e = []
+    add = lambda g, el, vr, v: e.append(_element(g, el, vr, v, explicit))
+    add(0x0008, 0x0016, "UI", _text(MR_IMAGE_STORAGE))
+    add(0x0008, 0x0018, "UI", _text(sop_instance_uid))
+    add(0x0008, 0x0060, "CS", b"MR")
+    if slice_thickness is not None:
+        add(0x0018, 0x0050, "DS", _text(ds(slice_thickness)))
+    if spacing_between_slices is not None:
+        add(0x0018, 0x0088, "DS", _text(ds(spacing_between_slices)))
+    add(0x0020, 0x000E, "UI", _text(series_uid))
+    add(0x0020, 0x0013, "IS", _text(str(int(instance_number))))
+    if position is not None:
+        add(0x0020, 0x0032, "DS", _text([ds(v) for v in position]))
+    if orientation is not None:
+        add(0x0020, 0x0037, "DS", _text([ds(v) for v in orientation]))
+    add(0x0028, 0x0002, "US", us(1))
+    add(0x0028, 0x0004, "CS", b"MONOCHROME2")
+    add(0x0028, 0x0010, "US", us(a.shape[0]))
+    add(0x0028, 0x0011, "US", us(a.shape[1]))
+    if pixel_spacing is not None:
+        add(0x0028, 0x0030, "DS", _text([ds(v) for v in pixel_spacing]))
+    add(0x0028, 0x0100, "US", us(bits))
+    add(0x0028, 0x0101, "US", us(bits_stored))
+    add(0x0028, 0x0102, "US", us(high_bit))
+    add(0x0028, 0x0103, "US", us(1 if a.dtype.kind == "i" else 0))
+    if inter is not None:
+        add(0x0028, 0x1052, "DS", _text(ds(inter)))
+    if slope is not None:
+        add(0x0028, 0x1053, "DS", _text(ds(slope)))
+    add(0x7FE0, 0x0010, "OB" if bits == 8 else "OW", a.astype(a.dtype.newbyteorder("<")).tobytes())
+    return b"\0" * 128 + b"DICM" + meta + b"".join(e)
+
+
+def lps_geometry(affine, what=""):
+    """(orientation (6), pixel_spacing (2), first position (3), slice step (3)) of a RAS voxel-index -> mm matrix whose axes are
+    (column, row, slice).  Refused: axes that are not orthogonal (shear) or not right-handed along the slice normal."""
+    a = np.eye(4) if affine is None else np.asarray(affine, dtype=np.float64)
+    lps = np.diag([-1.0, -1.0, 1.0, 1.0]) @ a
+    c0, c1, c2, t = lps[:3, 0], lps[:3, 1], lps[:3, 2], lps[:3, 3]
+    s0, s1, s2 = (float(np.linalg.norm(v)) for v in (c0, c1, c2))
+    if min(s0, s1, s2) <= 0.0:
+        raise ConfigurationError(f"{what}: the affine has a zero column")
+    r, c = c0 / s0, c1 / s1
+    n = np.cross(r, c)
+    if abs(float(r @ c)) > 1e-6 or np.linalg.norm(c2 - (n @ c2) * n) > 1e-6 * s2 or float(n @ c2) <= 0.0:
+        raise ConfigurationError(f"{what}: a sheared or left-handed affine has no ImageOrientationPatient / ImagePositionPatient form")
+    return tuple(r) + tuple(c), (s1, s0), t, c2
+
+
+def _stored(volume, bits_stored, rng):
+    """`volume` with its values in the low `bits_stored` bits and seeded garbage in the unused high bits of every word."""
+    bits = volume.dtype.itemsize * 8
+    if bits_stored is None or bits_stored == bits:
+        return volume
+    lo, hi = (-(1 << (bits_stored - 1)), (1 << (bits_stored - 1)) - 1) if volume.dtype.kind == "i" else (0, (1 << bits_stored) - 1)
+    if volume.min() < lo or volume.max() > hi:
+        raise ConfigurationError(f"the voxels span {volume.min()}..{volume.max()}: they do not fit {bits_stored} stored bits")
+    unsigned = np.dtype(f"u{volume.dtype.itemsize}")
+    word = volume.view(unsigned) & unsigned.type((1 << bits_stored) - 1)
+    garbage = rng.integers(0, 1 << (bits - bits_stored), volume.shape, dtype=np.uint64).astype(unsigned) << unsigned.type(bits_stored)
+    return (word | garbage).view(volume.dtype)
+
+
+def write_series(directory, volume, affine=None, slope=None, inter=None, series_uid=UID_ROOT + ".1", shuffle_names=True, seed=0,
+                 bits_stored=None, per_slice_scale=False, explicit=True):
+    """Write the (x, y, z) integer `volume` as z slice files under `directory`.  `per_slice_scale`: slice k carries its own pair,
+    slope (1 + (k % 4) / 8) and inter - 3.5 k, so that the series has no shared scale."""
+    volume = np.asarray(volume)
+    if volume.ndim != 3:
+        raise ConfigurationError(f"a volume has three axes, got {volume.shape}")
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng([int(seed), 7])
+    orientation, spacing, first, step = lps_geometry(affine, directory)
+    z = volume.shape[2]
+    names = rng.permutation(z) if shuffle_names else np.arange(z)
+    numbers = rng.permutation(z) if shuffle_names else np.arange(z)
+    words = _stored(volume, bits_stored, rng)
+    for k in range(z):
+        s, i = slope, inter
+        if per_slice_scale:
+            s, i = (1.0 if slope is None else slope) * (1.0 + (k % 4) / 8.0), (0.0 if inter is None else inter) - 3.5 * k
+        data = file_bytes(words[:, :, k].T, bits_stored, None, first + k * step, orientation, spacing, s, i, series_uid, int(numbers[k]) + 1,
+                          explicit, float(np.linalg.norm(step)), float(np.linalg.norm(step)), f"{series_uid}.{k + 1}")
+        with open(os.path.join(directory, f"{int(names[k]):04d}.dcm"), "wb") as f:
+            f.write(data)
+    return directory
+
+
+def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, seed=0, bits_stored=None, per_slice_scale=False):
+    """The DICOM twin of a `synth_nifti.write_tree` tree; returns the same dictionary of locations.  Scans keep their type, slope and
+    inter (as RescaleSlope / RescaleIntercept); non-zero mask voxels become `mask_value` (None: the mask's values are kept) in an 8-bit
+    unsigned series.  `bits_stored`, `per_slice_scale`: of the scans (see `write_series`)."""
+    nifti_root, dicom_root = str(nifti_root), str(dicom_root)
+    src = os.path.join(nifti_root, "images")
+    if not os.path.isdir(src):
+        raise ConfigurationError(f"{nifti_root}: no images/ directory (a synth_nifti.write_tree tree is expected)")
+    os.makedirs(dicom_root, exist_ok=True)
+    out = {"image_loc": os.path.join(dicom_root, "images"), "t1_path": "t1", "t2_path": "t2"}
+    for key, name in (("key_loc", "key.csv"), ("data_loc", "clinical.csv"), ("train_uids", "train_uids.txt"), ("val_uids", "val_uids.txt")):
+        if os.path.exists(os.path.join(nifti_root, name)):
+            shutil.copyfile(os.path.join(nifti_root, name), os.path.join(dicom_root, name))
+            out[key] = os.path.join(dicom_root, name)
+    count = 0
+    for mod in sorted(os.listdir(src)):
+        for patient in sorted(os.listdir(os.path.join(src, mod))):
+            d = os.path.join(src, mod, patient)
+            files = sorted(f for f in os.listdir(d) if not f.startswith("."))
+            scans, masks = [f for f in files if f.startswith("scan")], [f for f in files if not f.startswith("scan")]
+            if len(scans) != 1 or len(masks) != 1:
+                raise ConfigurationError(f"{d}: one scan* file and one mask are expected")
+            scan, mask = nifti.read(os.path.join(d, scans[0])), nifti.read(os.path.join(d, masks[0]))
+            if scan.raw.dtype.kind not in "iu" or mask.raw.dtype.kind not in "iu":
+                raise ConfigurationError(f"{d}: integer voxels are expected, got {scan.raw.dtype} and {mask.raw.dtype}")
+            count += 1
+            target = os.path.join(out["image_loc"], mod, patient)
+            scaling = scan.scaling() or (None, None)
+            write_series(os.path.join(target, "image", "series_1"), scan.raw, scan.affine, scaling[0], scaling[1], f"{UID_ROOT}.{count}.1",
+                         shuffle_names, seed + 2 * count, bits_stored, per_slice_scale)
+            m = mask.raw if mask_value is None else np.where(mask.raw != 0, mask_value, 0)
+            write_series(os.path.join(target, "mask", "series_1"), m.astype(np.uint8), mask.affine, None, None, f"{UID_ROOT}.{count}.2",
+                         shuffle_names, seed + 2 * count + 1)
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("nifti_dir", help="a synth_nifti.write_tree tree")
+    ap.add_argument("dicom_dir")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--bits_stored", type=int, default=None)
+    ap.add_argument("--per_slice_scale", action="store_true")
+    a = ap.parse_args()
+    for k, v in from_nifti_tree(a.nifti_dir, a.dicom_dir, seed=a.seed, bits_stored=a.bits_stored, per_slice_scale=a.per_slice_scale).items():
+        print(f"{k}: {v}")

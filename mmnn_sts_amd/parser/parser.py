@@ -4,9 +4,11 @@
 TinyDensenet and wraps it into `MultiModalModel` for `--images --preop|--postop` exactly like parser/parser.py:105-182.
 Fixes: `--preop` alone yields the standalone clinical MLP; the predictor list may be given as an
 integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  `getImagePath()` / `getDatasets(args, image_path)` (parser.py:43-97,
-184-198) build the local-disk NIfTI datasets from the `Data:` section (`image_loc`, `t1_path`, `t2_path`, `data_loc`, `key_loc`; the
-command-line flags override it; `mask_resample`, `mask_threshold` say what happens to a mask drawn on another grid than its scan's); S3, DICOM and radiomics datasets stay outside the path, and main.py substitutes synthetic patients when
-no image location is configured.
+184-198) build the local-disk image datasets from the `Data:` section (`image_loc`, `t1_path`, `t2_path`, `data_loc`, `key_loc`; the
+command-line flags override it; `format: auto | nifti | dicom` names the patient directories' layout, detected per tree by default;
+`mask_resample`, `mask_threshold` say what happens to a mask drawn on another grid than its scan's -- a DICOM mask is always resampled,
+and binarised at 128 unless `mask_threshold` is set).  DICOM means uncompressed single-frame series (`mmnn_sts_amd.data.dicom`); S3 and
+radiomics datasets stay outside the path, and main.py substitutes synthetic patients when no image location is configured.
 """
 import os
 
@@ -73,23 +75,33 @@ class Parser:
         return value
 
     def maskResample(self):
-        """(`Data: mask_resample`, `Data: mask_threshold`), defaults ('auto', 0.5).  'auto': a mask whose extents differ from its scan's
+        """(`Data: mask_resample`, `Data: mask_threshold`), defaults ('auto', 0.5); the threshold's default is 128 (upstream's
+        `mask > 128`) once `getDatasets` has found the image tree to be in the DICOM layout.  'auto': a mask whose extents differ from its scan's
         is resampled into the scan's grid on the device (both files need a qform / sform), equal extents are multiplied voxelwise;
         'geometry': also resampled when equal extents sit elsewhere in space (a corner of the scan grid maps more than 1e-3 voxel away
         from itself); 'never': differing extents are refused.  The threshold binarises the interpolated mask: 0.5 for 0/1 masks, 128
         (upstream's value) for 0/255 masks."""
-        from ..data.ingest import MASK_RESAMPLE_MODES
+        from ..data.ingest import DICOM_MASK_THRESHOLD, MASK_RESAMPLE_MODES, NIFTI_MASK_THRESHOLD
         data = self.config.get('Data') or {}
         mode = str(data.get('mask_resample', 'auto')).lower()
         if mode not in MASK_RESAMPLE_MODES:
             raise ConfigurationError('Data.mask_resample {!r} is none of {}'.format(data.get('mask_resample'), ', '.join(MASK_RESAMPLE_MODES)))
         try:
-            threshold = float(data.get('mask_threshold', 0.5))
+            default = DICOM_MASK_THRESHOLD if getattr(self, 'image_layout', 'nifti') == 'dicom' else NIFTI_MASK_THRESHOLD
+            threshold = float(default if data.get('mask_threshold') is None else data['mask_threshold'])
         except (TypeError, ValueError):
             threshold = float('nan')
         if threshold != threshold or threshold in (float('inf'), float('-inf')):
             raise ConfigurationError('Data.mask_threshold {!r} is not a finite number'.format(data.get('mask_threshold')))
         return mode, threshold
+
+    def dataFormat(self):
+        """`Data: format`: 'auto' (the default: the layout is detected per tree), 'nifti' or 'dicom'."""
+        from ..data.ImageDatasets import FORMATS
+        value = str((self.config.get('Data') or {}).get('format') or 'auto').lower()
+        if value not in FORMATS:
+            raise ConfigurationError('Data.format {!r} is none of {}'.format((self.config.get('Data') or {}).get('format'), ', '.join(FORMATS)))
+        return value
 
     def getImagePath(self):
         """parser/parser.py:184-198: the modality's directory under image_loc; a (t1, t2) tuple for 't1t2'."""
@@ -103,8 +115,8 @@ class Parser:
         raise ConfigurationError("ImageModel modality {!r} is none of 't1', 't2', 't1t2'".format(self.config['ImageModel']['modality']))
 
     def getDatasets(self, args, image_path=None):
-        """parser/parser.py:43-97 for the local-disk cases: the clinical dataset (with --preop / --postop), the NIfTI image dataset of
-        the modality (with --images), and their MultiModal(Survival)Dataset when both are asked for."""
+        """parser/parser.py:43-97 for the local-disk cases: the clinical dataset (with --preop / --postop), the image dataset of
+        the modality (with --images; NIfTI or DICOM layout, see `Data: format`), and their MultiModal(Survival)Dataset when both are asked for."""
         if not (args.classification or args.survival):
             raise ConfigurationError('getDatasets needs --survival or --classification to pick the dataset classes')
         datasets = []
@@ -117,7 +129,9 @@ class Parser:
             else:
                 cls = T1T2ImageDataset if both else NiftiImageDataset
             paths = image_path if both else (image_path,)
-            datasets.append(cls(*paths, self._data('data_loc'), self._data('key_loc'), mask_resample=self.maskResample()[0]))
+            datasets.append(cls(*paths, self._data('data_loc'), self._data('key_loc'), mask_resample=self.maskResample()[0],
+                                format=self.dataFormat()))
+            self.image_layout = datasets[-1].layout
         if len(datasets) == 1:
             return datasets[0]
         return MultiModalSurvivalDataset(datasets) if args.survival else MultiModalDataset(datasets)
