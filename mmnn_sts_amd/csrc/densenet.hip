@@ -17,6 +17,7 @@ constexpr size_t KZ_PART_BYTES = (size_t)512 * 4 * 1024 * sizeof(float);
 constexpr unsigned KZ_CNT_ENTRIES = 4096;
 
 namespace {
+struct Panel { const float* p; unsigned bytes; };   // a weight panel in device memory
 struct Carver {
   size_t cur = 0;
   size_t take(size_t bytes) {
@@ -25,7 +26,24 @@ struct Carver {
     return o;
   }
 };
+// Everything the backward of dense layer (b, l) binds (layer_bind).  The data gradients (plan_backward_range) and the weight gradients
+// (layer_wgrad_args) both take it from here: the operand of a data gradient IS the g0 / g1 / gr of the same convolution's weight gradient.
+struct LayerBind {
+  BnFwd bn1, bn2;          // norm1 / norm2 on batch statistics
+  BnBwd gr_new, gr_t1;     // BN-backward of the layer's own concat channels (gammas folded into G) / of T1 (single consumer norm2)
+  StatPtr dg1, dg2, s_x;   // dgamma/dbeta sums of norm1 / norm2; S1 / S2 of the concat buffer
+  View x, g;               // concat buffer and its gradient from channel 0: what norm1 / conv1 see
+  View x_new, g_new;       // the same from the layer's own channels on: what conv2 wrote
+  View t1, dz2;            // conv1 output; gradient wrt the norm2 output (ReLU mask applied)
+};
 }  // namespace
+
+// Floats of one weight tensor: conv1 [mid][cin], conv2 [growth][mid][27], transition conv [cout][cin].  The raw weights, their packed
+// fp32 panel and one weight-gradient slab all have this size; the pre-split bf16 conv2 panel holds three 2-byte pieces of every weight.
+static long conv1_elems(const Plan& p, int cin) { return (long)p.mid * cin; }
+static long conv2_elems(const Plan& p) { return (long)p.cfg.growth * p.mid * 27; }
+static long trans_elems(const TransOff& t) { return (long)t.cout * t.cin; }
+static size_t conv2_split_bytes(const Plan& p) { return (size_t)3 * conv2_elems(p) * sizeof(uint16_t); }
 
 int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
   MMNN_REQUIRE(cfg.nblocks >= 1 && cfg.nblocks <= MAX_BLOCKS, "plan: 1..%d dense blocks supported, got %d", MAX_BLOCKS, cfg.nblocks);
@@ -67,9 +85,9 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
       LayerOff lo;
       lo.cin = ci;
       bn(ci, lo.n1w, lo.n1b, lo.r1m, lo.r1v);
-      lo.c1 = po; po += (long)p.mid * ci;
+      lo.c1 = po; po += conv1_elems(p, ci);
       bn(p.mid, lo.n2w, lo.n2b, lo.r2m, lo.r2v);
-      lo.c2 = po; po += (long)cfg.growth * p.mid * 27;
+      lo.c2 = po; po += conv2_elems(p);
       p.layers[b].push_back(lo);
       ci += cfg.growth;
     }
@@ -77,7 +95,7 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
       TransOff t;
       t.cin = ci; t.cout = ci / 2;
       bn(ci, t.nw, t.nb, t.rm, t.rv);
-      t.cw = po; po += (long)t.cout * ci;
+      t.cw = po; po += trans_elems(t);
       p.trans.push_back(t);
     } else {
       bn(ci, p.p_n5w, p.p_n5b, p.r_n5m, p.r_n5v);
@@ -148,15 +166,14 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
     const bool f3 = conv3_fwd_bf16x3_eligible(f), b3 = conv3_dgrad_bf16x3_eligible(g);
     if (f3) p.x3_bytes = std::max(p.x3_bytes, conv3_bf16x3_plane_bytes(f));
     if (b3) p.x3_bytes = std::max(p.x3_bytes, conv3_bf16x3_plane_bytes(g));
-    const size_t split_panel = (size_t)3 * cfg.growth * p.mid * 27 * sizeof(uint16_t);
     for (int l = 0; l < cfg.block_layers[b]; ++l) {
-      p.o_pk_c1[b].push_back(cv.take((size_t)p.mid * p.layers[b][l].cin * F));
-      p.o_pk_c2f[b].push_back(cv.take((size_t)cfg.growth * p.mid * 27 * F));
-      p.o_pk_c2b[b].push_back(cv.take((size_t)cfg.growth * p.mid * 27 * F));
-      p.o_pk_c2f3[b].push_back(f3 ? cv.take(split_panel) : 0);
-      p.o_pk_c2b3[b].push_back(b3 ? cv.take(split_panel) : 0);
+      p.o_pk_c1[b].push_back(cv.take(conv1_elems(p, p.layers[b][l].cin) * F));
+      p.o_pk_c2f[b].push_back(cv.take(conv2_elems(p) * F));
+      p.o_pk_c2b[b].push_back(cv.take(conv2_elems(p) * F));
+      p.o_pk_c2f3[b].push_back(f3 ? cv.take(conv2_split_bytes(p)) : 0);
+      p.o_pk_c2b3[b].push_back(b3 ? cv.take(conv2_split_bytes(p)) : 0);
     }
-    if (b != nb - 1) p.o_pk_tr.push_back(cv.take((size_t)p.trans[b].cin * p.trans[b].cout * F));
+    if (b != nb - 1) p.o_pk_tr.push_back(cv.take(trans_elems(p.trans[b]) * F));
   }
   p.o_x3 = p.x3_bytes ? cv.take(p.x3_bytes) : 0;
   // weight-gradient slabs
@@ -180,19 +197,19 @@ int plan_build(Plan& p, const NetCfg& cfg, int N, int D, int H, int W) {
       const int s1 = wgrad_pick_splits(1, N, p.Db[b], p.Hb[b], p.Wb[b], p.mid, ci, pairs);
       const int s2 = wgrad_pick_splits(27, N, p.Db[b], p.Hb[b], p.Wb[b], cfg.growth, p.mid, cfg.block_layers[b]);
       p.ns_c1[b].push_back(s1); p.ns_c2[b].push_back(s2);
-      p.o_sl_c1[b].push_back(cv.take((size_t)s1 * p.mid * ci * F));
-      p.o_sl_c2[b].push_back(cv.take((size_t)s2 * 27 * cfg.growth * p.mid * F));
+      p.o_sl_c1[b].push_back(cv.take(s1 * conv1_elems(p, ci) * F));
+      p.o_sl_c2[b].push_back(cv.take(s2 * conv2_elems(p) * F));
     }
     if (b != nb - 1) {
       const int s = wgrad_pick_splits(1, N, p.Db[b + 1], p.Hb[b + 1], p.Wb[b + 1], p.trans[b].cout, p.trans[b].cin);
       p.ns_tr.push_back(s);
-      p.o_sl_tr.push_back(cv.take((size_t)s * p.trans[b].cout * p.trans[b].cin * F));
+      p.o_sl_tr.push_back(cv.take(s * trans_elems(p.trans[b]) * F));
     }
   }
   // dZ2 (gradient wrt the norm2 output) of every layer has its own buffer: the block's batched conv1 weight gradient reads every
   // layer's dZ2 after the data-gradient chain has passed them all.
   for (int b = 0; b < nb; ++b) p.o_dz2[b] = cv.take((size_t)cfg.block_layers[b] * N * p.mid * p.Vb[b] * F);
-  // cross-block K-split scratch: <= 256 blocks x one 32x32 (or 4 x 32x32) partial tile each, + per-tile counters
+  // cross-block K-split scratch: <= 512 blocks x (up to 4) 32x32 partial tiles, + per-tile counters
   p.o_kz_part = cv.take(KZ_PART_BYTES);
   p.o_kz_cnt = cv.take(KZ_CNT_ENTRIES * sizeof(unsigned));
   // job tables
@@ -222,39 +239,117 @@ void plan_free(Plan& p) {
   p.timer_ev.clear();
 }
 
-static StatPtr statptr(char* ws, size_t o, int C, int off, int nrep = NREP) {
-  StatPtr s;
-  s.sum = reinterpret_cast<double*>(ws + o);
-  s.sq = s.sum + (long)NREP * C;
-  s.stride = C;
-  s.off = off;
-  s.nrep = nrep;
-  s.pad_ = 0;
+// ---- the batch-norm sites (densenet.hpp: NormSite) -----------------------------------------------------------------------
+// a site on dense block b's concat buffer: channels [0, C) of the block's statistics row
+static NormSite concat_site(const Plan& p, int b, int C, long w, long bb, long rm, long rv, size_t o_dg) {
+  return {p.o_st_x[b], p.o_s_x[b], o_dg, p.ctot_b[b], 0, C, p.nrep_b[b], w, bb, rm, rv, (double)p.N * p.Vb[b]};
+}
+static NormSite norm0(const Plan& p) {   // on the stem convolution's output: its statistics always use NREP replicas
+  const int C = p.cfg.init_features;
+  return {p.o_st_conv0, p.o_dg_n0, p.o_dg_n0, C, 0, C, NREP, p.p_n0w, p.p_n0b, p.r_n0m, p.r_n0v, (double)p.N * p.D0 * p.H0 * p.W0};
+}
+static NormSite norm1(const Plan& p, int b, int l) {
+  const LayerOff& lo = p.layers[b][l];
+  return concat_site(p, b, lo.cin, lo.n1w, lo.n1b, lo.r1m, lo.r1v, p.o_dg_n1[b][l]);
+}
+static NormSite norm2(const Plan& p, int b, int l) {   // on T1, the layer's conv1 output
+  const LayerOff& lo = p.layers[b][l];
+  return {p.o_st_t1[b][l], p.o_dg_n2[b][l], p.o_dg_n2[b][l], p.mid, 0, p.mid, p.nrep_b[b], lo.n2w, lo.n2b, lo.r2m, lo.r2v, (double)p.N * p.Vb[b]};
+}
+static NormSite transition(const Plan& p, int b) {
+  const TransOff& t = p.trans[b];
+  return concat_site(p, b, t.cin, t.nw, t.nb, t.rm, t.rv, p.o_dg_tr[b]);
+}
+static NormSite norm5(const Plan& p) {
+  const int b = p.cfg.nblocks - 1;
+  return concat_site(p, b, p.ctot_b[b], p.p_n5w, p.p_n5b, p.r_n5m, p.r_n5v, p.o_dg_n5);
+}
+
+static StatPtr statptr(char* ws, size_t o, int C, int off, int nrep) {
+  StatPtr s; memset(&s, 0, sizeof(s));
+  s.sum = reinterpret_cast<double*>(ws + o); s.sq = s.sum + (long)NREP * C;
+  s.stride = C; s.off = off; s.nrep = nrep;
   return s;
 }
+// What the kernels read and write at a site.  `first` moves the window along the row: the concat channels behind the ones the site sees.
+// The producer of the tensor passes `training`: an eval forward accumulates no statistics (null sum).
+static StatPtr stats(char* ws, const NormSite& s, int first = 0, int training = 1) {
+  StatPtr st = statptr(ws, s.o_st, s.stride, s.off + first, s.nrep);
+  if (!training) st.sum = nullptr;
+  return st;
+}
+static StatPtr sums(char* ws, const NormSite& s, int first = 0) { return statptr(ws, s.o_s, s.stride, s.off + first, s.nrep); }     // S1 / S2
+static StatPtr dgsums(char* ws, const NormSite& s) { return statptr(ws, s.o_dg, s.C, 0, s.nrep); }      // .sum = dbeta, .sq = dgamma
+static BnFwd bnfwd(const Plan& p, char* ws, const float* params, float* run, const NormSite& s, int training) {
+  BnFwd f; memset(&f, 0, sizeof(f));
+  f.st = stats(ws, s);
+  f.rmean = run + s.rm; f.rvar = run + s.rv; f.gamma = params + s.w; f.beta = params + s.b;
+  f.inv_count = 1.0 / s.count; f.eps = p.cfg.eps; f.training = training;
+  return f;
+}
+static BnBwd bnbwd(const Plan& p, char* ws, const float* params, const NormSite& s, int first = 0) {   // of the tensor's channels [first, ...)
+  BnBwd g; memset(&g, 0, sizeof(g));
+  g.st = stats(ws, s, first); g.s = sums(ws, s, first);
+  g.gamma = s.o_s == s.o_dg ? params + s.w : nullptr;   // single consumer: scaled by its gamma here; concat: already folded into G
+  g.inv_count = 1.0 / s.count; g.eps = p.cfg.eps;
+  return g;
+}
+
+// ---- tensor views (densenet.hpp: View) and where they go in the argument structs --------------------------------------------
 static float* fptr(char* ws, size_t o) { return reinterpret_cast<float*>(ws + o); }
+static View concat(const Plan& p, char* ws, int b, int coff = 0) { return {fptr(ws, p.o_x[b]), (long)p.ctot_b[b] * p.Vb[b], coff}; }
+static View concat_grad(const Plan& p, char* ws, int b, int coff = 0) { return {fptr(ws, p.o_g[b]), (long)p.ctot_b[b] * p.Vb[b], coff}; }
+static View t1(const Plan& p, char* ws, int b, int l) { return {fptr(ws, p.o_t1[b][l]), (long)p.mid * p.Vb[b], 0}; }
+static View dz2(const Plan& p, char* ws, int b, int l) { return {fptr(ws, p.o_dz2[b]) + (long)l * p.N * p.mid * p.Vb[b], (long)p.mid * p.Vb[b], 0}; }
+// block b's transition input on block b + 1's grid (normalised, pooled), and the gradient wrt it (one buffer for every transition)
+static View pooled(const Plan& p, char* ws, int b) { return {fptr(ws, p.o_ap[b]), (long)p.ctot_b[b] * p.Vb[b + 1], 0}; }
+static View pooled_grad(const Plan& p, char* ws, int b) { return {fptr(ws, p.o_dap), (long)p.ctot_b[b] * p.Vb[b + 1], 0}; }
+
+static void set_in0(FpropArgs& a, View v) { a.in0 = v.p; a.in0_ns = v.ns; a.in0_coff = v.coff; }
+static void set_in1(FpropArgs& a, View v) { a.in1 = v.p; a.in1_ns = v.ns; a.in1_coff = v.coff; }
+static void set_out(FpropArgs& a, View v) { a.out = v.p; a.out_ns = v.ns; a.out_coff = v.coff; }
+static void set_ex(FpropArgs& a, View v) { a.ex = v.p; a.ex_ns = v.ns; a.ex_coff = v.coff; }
+static void set_g0(WgradArgs& a, View v) { a.g0 = v.p; a.g0_ns = v.ns; a.g0_coff = v.coff; }
+static void set_g1(WgradArgs& a, View v) { a.g1 = v.p; a.g1_ns = v.ns; a.g1_coff = v.coff; }
+static void set_x(WgradArgs& a, View v) { a.x = v.p; a.x_ns = v.ns; a.x_coff = v.coff; }
+
+// ---- weight panels: each is the `w` / `w3` of its own launch and the prefetch hint (FpropArgs::pf_ptr) of the launch before it -------
+static Panel conv1_panel(const Plan& p, char* ws, int b, int l) { return {fptr(ws, p.o_pk_c1[b][l]), (unsigned)(sizeof(float) * conv1_elems(p, p.layers[b][l].cin))}; }
+static Panel trans_panel(const Plan& p, char* ws, int b) { return {fptr(ws, p.o_pk_tr[b]), (unsigned)(sizeof(float) * trans_elems(p.trans[b]))}; }
+// conv1 as the parameters hold it, [m][c]: what its data gradient reads
+static Panel conv1_weights(const Plan& p, const float* params, int b, int l) { return {params + p.layers[b][l].c1, (unsigned)(sizeof(float) * conv1_elems(p, p.layers[b][l].cin))}; }
+// conv2 of the forward (pack kinds 1 / 5) or of the data gradient (kinds 2 / 6).  A layer on the three-piece bf16 kernels has a pre-split
+// panel beside the fp32 one, and its launch reads that one; `fp32` asks for the fp32 panel whatever the kernel.
+static Panel conv2_panel(const Plan& p, char* ws, int b, int l, bool bwd, bool fp32 = false) {
+  const size_t o3 = (bwd ? p.o_pk_c2b3 : p.o_pk_c2f3)[b][l];
+  if (o3 && !fp32) return {fptr(ws, o3), (unsigned)conv2_split_bytes(p)};
+  return {fptr(ws, (bwd ? p.o_pk_c2b : p.o_pk_c2f)[b][l]), (unsigned)(sizeof(float) * conv2_elems(p))};
+}
+static void set_conv2_weights(FpropArgs& a, const Plan& p, char* ws, int b, int l, bool bwd) {
+  const Panel w = conv2_panel(p, ws, b, l, bwd, true), w3 = conv2_panel(p, ws, b, l, bwd);
+  a.w = w.p;
+  if (w3.p != w.p) { a.w3 = w3.p; a.x3 = ws + p.o_x3; a.x3_bytes = p.x3_bytes; }
+}
+static void prefetch(FpropArgs& a, Panel w) { a.pf_ptr = w.p; a.pf_bytes = w.bytes; }
 
 // developer aid: every convolution launch gets its own 64 x 16 slot of the phase-trace buffer (null when tracing is off or the slots ran out)
 static unsigned long long* trace_slot(const Plan& p) {
   return (p.trace_base && p.trace_seq < p.trace_slots) ? p.trace_base + (size_t)(p.trace_seq++) * 64 * 16 : nullptr;
 }
 
-// capacities travel with the arguments: no process-global state
-static void set_kz(FpropArgs& a, const Plan& p, char* ws) {
+// Arguments of a convolution launch over dense block b's extent: zeroed, then the extent, the block's replica count, the K-split
+// scratch (capacities travel with the arguments: no process-global state) and the launch's trace slot.
+static FpropArgs block_args(const Plan& p, char* ws, int b) {
+  FpropArgs a; memset(&a, 0, sizeof(a));
+  a.N = p.N; a.D = p.Db[b]; a.H = p.Hb[b]; a.W = p.Wb[b]; a.nrep = p.nrep_b[b];
   a.kz_part = p.no_kz ? nullptr : fptr(ws, p.o_kz_part); a.kz_cnt = reinterpret_cast<unsigned*>(ws + p.o_kz_cnt);
   a.kz_part_bytes = KZ_PART_BYTES; a.kz_cnt_entries = KZ_CNT_ENTRIES;
   a.trace = trace_slot(p);
+  return a;
 }
-
-static BnFwd bnfwd(const Plan& p, StatPtr st, const float* params, float* run, long w, long b, long rm, long rv, double count, int training) {
-  BnFwd f;
-  f.st = st;
-  f.rmean = run + rm; f.rvar = run + rv;
-  f.gamma = params + w; f.beta = params + b;
-  f.inv_count = 1.0 / count;
-  f.eps = p.cfg.eps;
-  f.training = training;
-  return f;
+static void wgrad_shape(WgradArgs& w, const Plan& p, int b) {   // zeroed in place: the tables that hold them are compared bytewise
+  memset(&w, 0, sizeof(w));
+  w.N = p.N; w.D = p.Db[b]; w.H = p.Hb[b]; w.W = p.Wb[b];
 }
 
 // (re)build the device job tables when the buffers they point into change
@@ -269,60 +364,53 @@ static bool build_tables(Plan& p, const float* params, float* run, char* ws) {
   const int nb = c.nblocks;
   int ir = 0, ip = 0, ig = 0;
   p.max_pack = 0; p.max_grad = 0;
-  auto run_job = [&](size_t o, int C, int off, int n, long rm, long rv, double count) {
-    StatPtr s = statptr(ws, o, C, off);
-    RunStatJob j; j.sum = s.sum; j.sq = s.sq; j.stride = C; j.off = off; j.C = n; j.rmean = run ? run + rm : nullptr; j.rvar = run ? run + rv : nullptr; j.count = count;
-    rj[ir++] = j;
-  };
   auto pack_job = [&](long src, size_t dst, int kind, int M, int C, long count) {
-    PackJob j; j.src = params + src; j.dst = fptr(ws, dst); j.kind = kind; j.M = M; j.C = C; j.count = count;
-    pj[ip++] = j; p.max_pack = std::max(p.max_pack, count);
+    PackJob& j = pj[ip++]; memset(&j, 0, sizeof(j));
+    j.src = params + src; j.dst = fptr(ws, dst); j.kind = kind; j.M = M; j.C = C; j.count = count;
+    p.max_pack = std::max(p.max_pack, count);
   };
-  auto grad_slab = [&](int kind, size_t o, long stride, int ns, int M, int C, long dst, long count) {
-    GradJob j; j.kind = kind; j.src = ws + o; j.stride = stride; j.nsplit = ns; j.off = 0; j.M = M; j.C = C; j.dst_off = dst; j.count = count;
-    gj[ig++] = j; p.max_grad = std::max(p.max_grad, count);
+  auto grad_job = [&](int kind, const void* src, long stride, int ns, int M, int C, long dst, long count) {
+    GradJob& j = gj[ig++]; memset(&j, 0, sizeof(j));
+    j.kind = kind; j.src = src; j.stride = stride; j.nsplit = ns; j.M = M; j.C = C; j.dst_off = dst; j.count = count;
+    p.max_grad = std::max(p.max_grad, count);
   };
-  auto grad_bn = [&](size_t o, int C, long dw, long db) {   // pair block: [dbeta replicas][dgamma replicas]
-    StatPtr s = statptr(ws, o, C, 0);
-    GradJob j; j.kind = 3; j.stride = C; j.nsplit = 0; j.off = 0; j.M = 0; j.C = C; j.count = C;
-    j.src = s.sq; j.dst_off = dw; gj[ig++] = j;     // dgamma
-    j.src = s.sum; j.dst_off = db; gj[ig++] = j;    // dbeta
-    p.max_grad = std::max(p.max_grad, (long)C);
+  auto grad_slab = [&](int kind, size_t o, int ns, int M, int C, long dst, long count) {   // partial slabs of `count` floats each (stem: padded)
+    grad_job(kind, ws + o, kind == 2 ? (long)C * M * 352 : count, ns, M, C, dst, count);
   };
-  const double cnt0 = (double)p.N * p.D0 * p.H0 * p.W0;
-  run_job(p.o_st_conv0, c.init_features, 0, c.init_features, p.r_n0m, p.r_n0v, cnt0);
+  auto site_jobs = [&](const NormSite& s) {   // running statistics of a site, and its dgamma / dbeta out of the pair block
+    const StatPtr st = stats(ws, s), dg = dgsums(ws, s);
+    RunStatJob& j = rj[ir++]; memset(&j, 0, sizeof(j));
+    j.sum = st.sum; j.sq = st.sq; j.stride = s.stride; j.off = s.off; j.C = s.C;
+    j.rmean = run ? run + s.rm : nullptr; j.rvar = run ? run + s.rv : nullptr; j.count = s.count;
+    grad_job(3, dg.sq, s.C, 0, 0, s.C, s.w, s.C);
+    grad_job(3, dg.sum, s.C, 0, 0, s.C, s.b, s.C);
+  };
   pack_job(p.p_conv0, p.o_pk_conv0, (c.in_channels % 2 == 0) ? 3 : 4, c.init_features, c.in_channels, (long)7 * stem_krows(c.in_channels) * 64);
-  grad_slab(2, p.o_sl_conv0, (long)c.in_channels * c.init_features * 352, p.ns_conv0, c.init_features, c.in_channels, p.p_conv0,
-            (long)c.init_features * c.in_channels * 343);
-  grad_bn(p.o_dg_n0, c.init_features, p.p_n0w, p.p_n0b);
+  grad_slab(2, p.o_sl_conv0, p.ns_conv0, c.init_features, c.in_channels, p.p_conv0, (long)c.init_features * c.in_channels * 343);
+  site_jobs(norm0(p));
   for (int b = 0; b < nb; ++b) {
-    const double cnt = (double)p.N * p.Vb[b];
     p.gj_begin[b] = ig;
     const long max_before = p.max_grad;
     p.max_grad = 0;
     for (int l = 0; l < c.block_layers[b]; ++l) {
       const LayerOff& lo = p.layers[b][l];
-      run_job(p.o_st_x[b], p.ctot_b[b], 0, lo.cin, lo.r1m, lo.r1v, cnt);
-      run_job(p.o_st_t1[b][l], p.mid, 0, p.mid, lo.r2m, lo.r2v, cnt);
-      pack_job(lo.c1, p.o_pk_c1[b][l], 0, p.mid, lo.cin, (long)p.mid * lo.cin);
-      pack_job(lo.c2, p.o_pk_c2f[b][l], 1, c.growth, p.mid, (long)c.growth * p.mid * 27);
-      pack_job(lo.c2, p.o_pk_c2b[b][l], 2, c.growth, p.mid, (long)c.growth * p.mid * 27);
+      pack_job(lo.c1, p.o_pk_c1[b][l], 0, p.mid, lo.cin, conv1_elems(p, lo.cin));
+      pack_job(lo.c2, p.o_pk_c2f[b][l], 1, c.growth, p.mid, conv2_elems(p));
+      pack_job(lo.c2, p.o_pk_c2b[b][l], 2, c.growth, p.mid, conv2_elems(p));
       if (p.o_pk_c2f3[b][l]) pack_job(lo.c2, p.o_pk_c2f3[b][l], 5, c.growth, p.mid, (long)27 * (p.mid / 8) * c.growth);
       if (p.o_pk_c2b3[b][l]) pack_job(lo.c2, p.o_pk_c2b3[b][l], 6, c.growth, p.mid, (long)27 * (c.growth / 8) * p.mid);
-      grad_bn(p.o_dg_n1[b][l], lo.cin, lo.n1w, lo.n1b);
-      grad_slab(0, p.o_sl_c1[b][l], (long)p.mid * lo.cin, p.ns_c1[b][l], p.mid, lo.cin, lo.c1, (long)p.mid * lo.cin);
-      grad_bn(p.o_dg_n2[b][l], p.mid, lo.n2w, lo.n2b);
-      grad_slab(1, p.o_sl_c2[b][l], (long)27 * c.growth * p.mid, p.ns_c2[b][l], c.growth, p.mid, lo.c2, (long)c.growth * p.mid * 27);
+      site_jobs(norm1(p, b, l));
+      grad_slab(0, p.o_sl_c1[b][l], p.ns_c1[b][l], p.mid, lo.cin, lo.c1, conv1_elems(p, lo.cin));
+      site_jobs(norm2(p, b, l));
+      grad_slab(1, p.o_sl_c2[b][l], p.ns_c2[b][l], c.growth, p.mid, lo.c2, conv2_elems(p));
     }
     if (b != nb - 1) {
       const TransOff& t = p.trans[b];
-      run_job(p.o_st_x[b], p.ctot_b[b], 0, t.cin, t.rm, t.rv, cnt);
-      pack_job(t.cw, p.o_pk_tr[b], 0, t.cout, t.cin, (long)t.cout * t.cin);
-      grad_bn(p.o_dg_tr[b], t.cin, t.nw, t.nb);
-      grad_slab(0, p.o_sl_tr[b], (long)t.cout * t.cin, p.ns_tr[b], t.cout, t.cin, t.cw, (long)t.cout * t.cin);
+      pack_job(t.cw, p.o_pk_tr[b], 0, t.cout, t.cin, trans_elems(t));
+      site_jobs(transition(p, b));
+      grad_slab(0, p.o_sl_tr[b], p.ns_tr[b], t.cout, t.cin, t.cw, trans_elems(t));
     } else {
-      run_job(p.o_st_x[b], p.ctot_b[b], 0, p.ctot_b[b], p.r_n5m, p.r_n5v, cnt);
-      grad_bn(p.o_dg_n5, p.ctot_b[b], p.p_n5w, p.p_n5b);
+      site_jobs(norm5(p));
     }
     p.gj_max[b] = p.max_grad;
     p.max_grad = std::max(p.max_grad, max_before);
@@ -394,11 +482,9 @@ int plan_set_option(Plan& p, const char* name, long value) {
   set_error("set_option: unknown option '%s'", s.c_str());
   return 1;
 }
-
 static DropCfg dropcfg(const Plan& p, uint64_t seed, int layer, int training) {
-  DropCfg d;
-  d.seed = seed; d.layer = layer;
-  d.p = training ? p.cfg.dropout_p : 0.f;
+  DropCfg d; memset(&d, 0, sizeof(d));
+  d.seed = seed; d.layer = layer; d.p = training ? p.cfg.dropout_p : 0.f;
   return d;
 }
 
@@ -434,94 +520,76 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
     ++p.pack_launches;
   }
 
-  const double cnt0 = (double)N * p.D0 * p.H0 * p.W0;
   {  // stem
-    StemConvArgs a;
+    const NormSite n0 = norm0(p);
+    StemConvArgs a; memset(&a, 0, sizeof(a));
     a.N = N; a.Cin = c.in_channels; a.D = p.D; a.H = p.H; a.W = p.W; a.Do = p.D0; a.Ho = p.H0; a.Wo = p.W0; a.M = c.init_features;
     a.x = x; a.wp = fptr(ws, p.o_pk_conv0); a.out = fptr(ws, p.o_conv0);
-    a.st_out = statptr(ws, p.o_st_conv0, c.init_features, 0);
-    if (!training) a.st_out.sum = nullptr;
+    a.st_out = stats(ws, n0, 0, training);
     { ScopedTimer t(p, T_STEM_CONV, -1, stream); rc = launch_stem_conv(a, stream); }
     if (rc) return rc;
-    StemPoolArgs q;
+    const View X = concat(p, ws, 0);
+    StemPoolArgs q; memset(&q, 0, sizeof(q));
     q.N = N; q.C = c.init_features; q.Di = p.D0; q.Hi = p.H0; q.Wi = p.W0; q.Do = p.Db[0]; q.Ho = p.Hb[0]; q.Wo = p.Wb[0];
     q.x = fptr(ws, p.o_conv0);
-    q.bn = bnfwd(p, statptr(ws, p.o_st_conv0, c.init_features, 0), params, run, p.p_n0w, p.p_n0b, p.r_n0m, p.r_n0v, cnt0, training);
-    q.out = fptr(ws, p.o_x[0]); q.out_ns = (long)p.ctot_b[0] * p.Vb[0];
+    q.bn = bnfwd(p, ws, params, run, n0, training);
+    q.out = X.p; q.out_ns = X.ns;
     q.idx = reinterpret_cast<unsigned char*>(ws + p.o_idx);
-    q.st_out = statptr(ws, p.o_st_x[0], p.ctot_b[0], 0, p.nrep_b[0]);
-    if (!training) q.st_out.sum = nullptr;
+    q.st_out = stats(ws, norm1(p, 0, 0), 0, training);
     if ((rc = launch_stem_pool(q, stream))) return rc;
   }
   int layer_id = 0;
   for (int b = 0; b < nb; ++b) {
-    const double cnt = (double)N * p.Vb[b];
-    const long xns = (long)p.ctot_b[b] * p.Vb[b];
+    const View X = concat(p, ws, b);
     for (int l = 0; l < c.block_layers[b]; ++l, ++layer_id) {
-      const LayerOff& lo = p.layers[b][l];
-      FpropArgs a;
-      memset(&a, 0, sizeof(a));
-      set_kz(a, p, ws);
-      a.N = N; a.D = p.Db[b]; a.H = p.Hb[b]; a.W = p.Wb[b];
+      const NormSite n1 = norm1(p, b, l), n2 = norm2(p, b, l);
       // conv1: ReLU(BN(concat)) -> T1
-      a.Cin = lo.cin; a.M = p.mid; a.nrep = p.nrep_b[b];
-      a.in0 = fptr(ws, p.o_x[b]); a.in0_ns = xns; a.in0_coff = 0;
-      a.bn_in = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, lo.n1w, lo.n1b, lo.r1m, lo.r1v, cnt, training);
-      a.w = fptr(ws, p.o_pk_c1[b][l]); a.w_ld = p.mid;
-      a.out = fptr(ws, p.o_t1[b][l]); a.out_ns = (long)p.mid * p.Vb[b]; a.out_coff = 0;
-      a.st_out = statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]);
-      if (!training) a.st_out.sum = nullptr;
-      if (p.o_pk_c2f3[b][l]) { a.pf_ptr = fptr(ws, p.o_pk_c2f3[b][l]); a.pf_bytes = (unsigned)(3 * sizeof(uint16_t) * c.growth * p.mid * 27); }
-      else { a.pf_ptr = fptr(ws, p.o_pk_c2f[b][l]); a.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27); }
+      FpropArgs a = block_args(p, ws, b);
+      a.Cin = n1.C; a.M = p.mid;
+      set_in0(a, X);
+      a.bn_in = bnfwd(p, ws, params, run, n1, training);
+      a.w = conv1_panel(p, ws, b, l).p; a.w_ld = p.mid;
+      set_out(a, t1(p, ws, b, l));
+      a.st_out = stats(ws, n2, 0, training);
+      prefetch(a, conv2_panel(p, ws, b, l, false));
       { ScopedTimer t(p, T_CONV1_FWD, b, stream); rc = launch_fprop(a, 1, PRO_BNRELU, EPI_STORE_STATS, stream); }
       if (rc) return rc;
       // conv2: ReLU(BN(T1)) -> growth new channels of the concat buffer (+ channel dropout)
-      FpropArgs e;
-      memset(&e, 0, sizeof(e));
-      set_kz(e, p, ws);
-      e.N = N; e.D = p.Db[b]; e.H = p.Hb[b]; e.W = p.Wb[b];
-      e.Cin = p.mid; e.M = c.growth; e.nrep = p.nrep_b[b];
-      e.in0 = fptr(ws, p.o_t1[b][l]); e.in0_ns = (long)p.mid * p.Vb[b]; e.in0_coff = 0;
-      e.bn_in = bnfwd(p, statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]), params, run, lo.n2w, lo.n2b, lo.r2m, lo.r2v, cnt, training);
-      e.w = fptr(ws, p.o_pk_c2f[b][l]); e.w_ld = c.growth;
-      if (p.o_pk_c2f3[b][l]) { e.w3 = ws + p.o_pk_c2f3[b][l]; e.x3 = ws + p.o_x3; e.x3_bytes = p.x3_bytes; }
-      e.out = fptr(ws, p.o_x[b]); e.out_ns = xns; e.out_coff = lo.cin;
+      FpropArgs e = block_args(p, ws, b);
+      e.Cin = p.mid; e.M = c.growth;
+      set_in0(e, t1(p, ws, b, l));
+      e.bn_in = bnfwd(p, ws, params, run, n2, training);
+      set_conv2_weights(e, p, ws, b, l, false); e.w_ld = c.growth;
+      set_out(e, concat(p, ws, b, n1.C));
       e.drop_out = dropcfg(p, seed, layer_id, training);
-      e.st_out = statptr(ws, p.o_st_x[b], p.ctot_b[b], lo.cin, p.nrep_b[b]);
-      if (!training) e.st_out.sum = nullptr;
-      if (l + 1 < c.block_layers[b]) {
-        e.pf_ptr = fptr(ws, p.o_pk_c1[b][l + 1]); e.pf_bytes = (unsigned)(sizeof(float) * p.mid * p.layers[b][l + 1].cin);
-      } else if (b != nb - 1) {
-        e.pf_ptr = fptr(ws, p.o_pk_tr[b]); e.pf_bytes = (unsigned)(sizeof(float) * p.trans[b].cin * p.trans[b].cout);
-      }
+      e.st_out = stats(ws, n1, n1.C, training);
+      if (l + 1 < c.block_layers[b]) prefetch(e, conv1_panel(p, ws, b, l + 1));
+      else if (b != nb - 1) prefetch(e, trans_panel(p, ws, b));
       { ScopedTimer t(p, T_CONV2_FWD, b, stream); rc = launch_fprop(e, 27, PRO_BNRELU, EPI_STORE_STATS, stream); }
       if (rc) return rc;
     }
     if (b != nb - 1) {
-      const TransOff& t = p.trans[b];
-      PoolFwdArgs q;
-      q.N = N; q.C = t.cin; q.D = p.Db[b]; q.H = p.Hb[b]; q.W = p.Wb[b];
-      q.x = fptr(ws, p.o_x[b]); q.x_ns = xns;
-      q.bn = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, t.nw, t.nb, t.rm, t.rv, cnt, training);
-      q.out = fptr(ws, p.o_ap[b]);
+      const NormSite tr = transition(p, b);
+      PoolFwdArgs q; memset(&q, 0, sizeof(q));
+      q.N = N; q.C = tr.C; q.D = p.Db[b]; q.H = p.Hb[b]; q.W = p.Wb[b];
+      q.x = X.p; q.x_ns = X.ns;
+      q.bn = bnfwd(p, ws, params, run, tr, training);
+      q.out = pooled(p, ws, b).p;
       if ((rc = launch_bnrelu_avgpool(q, stream))) return rc;
-      FpropArgs a;
-      memset(&a, 0, sizeof(a));
-      set_kz(a, p, ws);
-      a.N = N; a.D = p.Db[b + 1]; a.H = p.Hb[b + 1]; a.W = p.Wb[b + 1];
-      a.Cin = t.cin; a.M = t.cout; a.nrep = p.nrep_b[b + 1];
-      a.in0 = fptr(ws, p.o_ap[b]); a.in0_ns = (long)t.cin * p.Vb[b + 1]; a.in0_coff = 0;
-      a.w = fptr(ws, p.o_pk_tr[b]); a.w_ld = t.cout;
-      a.out = fptr(ws, p.o_x[b + 1]); a.out_ns = (long)p.ctot_b[b + 1] * p.Vb[b + 1]; a.out_coff = 0;
-      a.st_out = statptr(ws, p.o_st_x[b + 1], p.ctot_b[b + 1], 0, p.nrep_b[b + 1]);
-      if (!training) a.st_out.sum = nullptr;
-      a.pf_ptr = fptr(ws, p.o_pk_c1[b + 1][0]); a.pf_bytes = (unsigned)(sizeof(float) * p.mid * p.layers[b + 1][0].cin);
+      FpropArgs a = block_args(p, ws, b + 1);
+      a.Cin = p.trans[b].cin; a.M = p.trans[b].cout;
+      set_in0(a, pooled(p, ws, b));
+      a.w = trans_panel(p, ws, b).p; a.w_ld = a.M;
+      set_out(a, concat(p, ws, b + 1));
+      a.st_out = stats(ws, norm1(p, b + 1, 0), 0, training);
+      prefetch(a, conv1_panel(p, ws, b + 1, 0));
       if ((rc = launch_fprop(a, 1, PRO_NONE, EPI_STORE_STATS, stream))) return rc;
     } else {
-      BnApplyArgs q;
-      q.N = N; q.C = p.ctot_b[b]; q.V = p.Vb[b];
-      q.x = fptr(ws, p.o_x[b]); q.x_ns = xns;
-      q.bn = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, p.p_n5w, p.p_n5b, p.r_n5m, p.r_n5v, cnt, training);
+      const NormSite n5 = norm5(p);
+      BnApplyArgs q; memset(&q, 0, sizeof(q));
+      q.N = N; q.C = n5.C; q.V = p.Vb[b];
+      q.x = X.p; q.x_ns = X.ns;
+      q.bn = bnfwd(p, ws, params, run, n5, training);
       q.out = out;
       if ((rc = launch_bn_apply(q, stream))) return rc;
     }
@@ -533,41 +601,46 @@ int plan_forward(Plan& p, const float* params, float* run, const float* x, char*
   return 0;
 }
 
+static LayerBind layer_bind(const Plan& p, const float* params, float* run, char* ws, int b, int l) {
+  const NormSite n1 = norm1(p, b, l), n2 = norm2(p, b, l);
+  LayerBind L; memset(&L, 0, sizeof(L));
+  L.bn1 = bnfwd(p, ws, params, run, n1, 1); L.bn2 = bnfwd(p, ws, params, run, n2, 1);
+  L.gr_new = bnbwd(p, ws, params, n1, n1.C); L.gr_t1 = bnbwd(p, ws, params, n2);
+  L.dg1 = dgsums(ws, n1); L.dg2 = dgsums(ws, n2); L.s_x = sums(ws, n1);
+  L.x = concat(p, ws, b); L.g = concat_grad(p, ws, b);
+  L.x_new = concat(p, ws, b, n1.C); L.g_new = concat_grad(p, ws, b, n1.C);
+  L.t1 = t1(p, ws, b, l); L.dz2 = dz2(p, ws, b, l);
+  return L;
+}
+
 // Arguments of the two weight-gradient launches of dense layer (b, l): conv2 (3x3x3, `w2`) and conv1 (1x1x1, `w1`).  The dropout
 // seed is left 0: the batched kernels take the step's as an argument.
-static void layer_wgrad_args(const Plan& p, const float* params, float* run, char* ws, int b, int l, int layer_id, WgradArgs& w2, WgradArgs& w1) {
-  const NetCfg& c = p.cfg;
-  const int N = p.N;
-  const double cnt = (double)N * p.Vb[b];
-  const long xns = (long)p.ctot_b[b] * p.Vb[b], tns = (long)p.mid * p.Vb[b];
-  const LayerOff& lo = p.layers[b][l];
-  const BnFwd bn1 = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, lo.n1w, lo.n1b, lo.r1m, lo.r1v, cnt, 1);
-  const BnFwd bn2 = bnfwd(p, statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]), params, run, lo.n2w, lo.n2b, lo.r2m, lo.r2v, cnt, 1);
-  const StatPtr dg2 = statptr(ws, p.o_dg_n2[b][l], p.mid, 0, p.nrep_b[b]);
-  float* dz2 = fptr(ws, p.o_dz2[b]) + (long)l * N * tns;
-  memset(&w2, 0, sizeof(w2));
-  w2.N = N; w2.D = p.Db[b]; w2.H = p.Hb[b]; w2.W = p.Wb[b];
-  w2.M = c.growth; w2.Cin = p.mid;
-  w2.g0 = fptr(ws, p.o_g[b]); w2.g0_ns = xns; w2.g0_coff = lo.cin;
-  w2.g1 = fptr(ws, p.o_x[b]); w2.g1_ns = xns; w2.g1_coff = lo.cin;
-  w2.gr.st = statptr(ws, p.o_st_x[b], p.ctot_b[b], lo.cin, p.nrep_b[b]);       // BN-backward of the layer's concat slice (gammas folded into G)
-  w2.gr.s = statptr(ws, p.o_s_x[b], p.ctot_b[b], lo.cin, p.nrep_b[b]);
-  w2.gr.gamma = nullptr; w2.gr.inv_count = 1.0 / cnt; w2.gr.eps = c.eps;
-  w2.drop.layer = layer_id; w2.drop.p = c.dropout_p;
-  w2.x = fptr(ws, p.o_t1[b][l]); w2.x_ns = tns; w2.x_coff = 0;
-  w2.bn = bn2;
-  w2.slab = fptr(ws, p.o_sl_c2[b][l]); w2.slab_stride = (long)27 * c.growth * p.mid; w2.nsplit = p.ns_c2[b][l];
-  memset(&w1, 0, sizeof(w1));
-  w1.N = N; w1.D = p.Db[b]; w1.H = p.Hb[b]; w1.W = p.Wb[b];
-  w1.M = p.mid; w1.Cin = lo.cin;
-  w1.g0 = dz2; w1.g0_ns = tns; w1.g0_coff = 0;
-  w1.g1 = fptr(ws, p.o_t1[b][l]); w1.g1_ns = tns; w1.g1_coff = 0;
-  w1.gr.st = statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]);             // BN-backward of T1 (single consumer norm2): S1 = dbeta2, S2 = dgamma2
-  w1.gr.s = dg2;
-  w1.gr.gamma = params + lo.n2w; w1.gr.inv_count = 1.0 / cnt; w1.gr.eps = c.eps;
-  w1.x = fptr(ws, p.o_x[b]); w1.x_ns = xns; w1.x_coff = 0;
-  w1.bn = bn1;
-  w1.slab = fptr(ws, p.o_sl_c1[b][l]); w1.slab_stride = (long)p.mid * lo.cin; w1.nsplit = p.ns_c1[b][l];
+static void layer_wgrad_args(const Plan& p, const LayerBind& L, char* ws, int b, int l, int layer_id, WgradArgs& w2, WgradArgs& w1) {
+  const int cin = p.layers[b][l].cin;
+  wgrad_shape(w2, p, b);
+  w2.M = p.cfg.growth; w2.Cin = p.mid;
+  set_g0(w2, L.g_new); set_g1(w2, L.x_new); w2.gr = L.gr_new;
+  w2.drop.layer = layer_id; w2.drop.p = p.cfg.dropout_p;
+  set_x(w2, L.t1); w2.bn = L.bn2;
+  w2.slab = fptr(ws, p.o_sl_c2[b][l]); w2.slab_stride = conv2_elems(p); w2.nsplit = p.ns_c2[b][l];
+  wgrad_shape(w1, p, b);
+  w1.M = p.mid; w1.Cin = cin;
+  set_g0(w1, L.dz2); set_g1(w1, L.t1); w1.gr = L.gr_t1;
+  set_x(w1, L.x); w1.bn = L.bn1;
+  w1.slab = fptr(ws, p.o_sl_c1[b][l]); w1.slab_stride = conv1_elems(p, cin); w1.nsplit = p.ns_c1[b][l];
+}
+
+// first contribution to block b's G from the consumer at the end of the block: norm5 (mode 0) or the transition (mode 1, un-pool + ReLU)
+static ConsumerBwdArgs consumer_bwd_args(const Plan& p, const float* params, float* run, char* ws, const NormSite& s, int b, int mode, const float* dy) {
+  const View X = concat(p, ws, b), G = concat_grad(p, ws, b);
+  const StatPtr dg = dgsums(ws, s);
+  ConsumerBwdArgs a; memset(&a, 0, sizeof(a));
+  a.N = p.N; a.C = s.C; a.D = p.Db[b]; a.H = p.Hb[b]; a.W = p.Wb[b]; a.mode = mode; a.nrep = s.nrep;
+  a.dy = dy; a.x = X.p; a.x_ns = X.ns;
+  a.bn = bnfwd(p, ws, params, run, s, 1);
+  a.g = G.p; a.g_ns = G.ns; a.dbeta = dg.sum; a.dgamma = dg.sq;
+  a.s_acc = sums(ws, s);
+  return a;
 }
 
 int plan_backward(Plan& p, const float* params, const float* x, char* ws, const float* grad_out, float* grad_params, int accumulate,
@@ -578,9 +651,9 @@ int plan_backward(Plan& p, const float* params, const float* x, char* ws, const 
 int plan_block_param_range(const Plan& p, int block, long* begin, long* end) {
   const int nb = p.cfg.nblocks;
   MMNN_REQUIRE(block >= -1 && block < nb && begin && end, "block_param_range: block %d out of range [-1, %d)", block, nb);
-  if (block < 0) { *begin = 0; *end = p.layers[0][0].n1w; return 0; }          // stem: conv0, norm0
-  *begin = p.layers[block][0].n1w;                                              // the block's layers, then its transition / norm5
-  *end = (block + 1 < nb) ? p.layers[block + 1][0].n1w : p.n_params;
+  if (block < 0) { *begin = 0; *end = norm1(p, 0, 0).w; return 0; }             // stem: conv0, norm0
+  *begin = norm1(p, block, 0).w;                                                // the block's layers, then its transition / norm5
+  *end = (block + 1 < nb) ? norm1(p, block + 1, 0).w : p.n_params;
   return 0;
 }
 
@@ -618,7 +691,7 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
     int id = 0;
     for (int b = 0; b < nb; ++b)
       for (int l = 0; l < c.block_layers[b]; ++l, ++id) {
-        layer_wgrad_args(p, params, run, ws, b, l, id, tab[id], tab[p.n_layers + id]);
+        layer_wgrad_args(p, layer_bind(p, params, run, ws, b, l), ws, b, l, id, tab[id], tab[p.n_layers + id]);
         tab[id].trace = trace_slot(p);
         tab[p.n_layers + id].trace = trace_slot(p);
       }
@@ -656,151 +729,79 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
     }
     return 0;
   };
-  auto sptr = [&](int b, int off) { return statptr(ws, p.o_s_x[b], p.ctot_b[b], off, p.nrep_b[b]); };
-  auto concat_grad = [&](int b, int off) {   // BN-backward of concat channels [off, ...) of block b (gammas folded into G)
-    BnBwd g;
-    g.st = statptr(ws, p.o_st_x[b], p.ctot_b[b], off, p.nrep_b[b]);
-    g.s = sptr(b, off);
-    g.gamma = nullptr;
-    g.inv_count = 1.0 / ((double)N * p.Vb[b]);
-    g.eps = c.eps;
-    return g;
-  };
-  if (first_call) {  // norm5: first contribution to the last block's G
-    const int b = nb - 1;
-    ConsumerBwdArgs a;
-    a.N = N; a.C = p.ctot_b[b]; a.D = p.Db[b]; a.H = p.Hb[b]; a.W = p.Wb[b]; a.mode = 0; a.nrep = p.nrep_b[b];
-    a.dy = grad_out;
-    a.x = fptr(ws, p.o_x[b]); a.x_ns = (long)p.ctot_b[b] * p.Vb[b];
-    a.bn = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, p.p_n5w, p.p_n5b, p.r_n5m, p.r_n5v, (double)N * p.Vb[b], 1);
-    a.g = fptr(ws, p.o_g[b]); a.g_ns = a.x_ns;
-    StatPtr dg = statptr(ws, p.o_dg_n5, p.ctot_b[b], 0, p.nrep_b[b]);
-    a.dbeta = dg.sum; a.dgamma = dg.sq;
-    a.s_acc = sptr(b, 0);
-    if ((rc = launch_consumer_bwd(a, stream))) return rc;
-  }
+  // norm5: first contribution to the last block's G
+  if (first_call && (rc = launch_consumer_bwd(consumer_bwd_args(p, params, run, ws, norm5(p), nb - 1, 0, grad_out), stream))) return rc;
   int layer_id = 0;
   for (int b = 0; b <= hi; ++b) layer_id += c.block_layers[b];
   for (int b = hi; b >= lo; --b) {
-    const double cnt = (double)N * p.Vb[b];
-    const long xns = (long)p.ctot_b[b] * p.Vb[b];
-    const long tns = (long)p.mid * p.Vb[b];
     for (int l = c.block_layers[b] - 1; l >= 0; --l) {
       --layer_id;
-      const LayerOff& lo = p.layers[b][l];
-      const BnFwd bn1 = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, lo.n1w, lo.n1b, lo.r1m, lo.r1v, cnt, 1);
-      const BnFwd bn2 = bnfwd(p, statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]), params, run, lo.n2w, lo.n2b, lo.r2m, lo.r2v, cnt, 1);
-      const StatPtr dg2 = statptr(ws, p.o_dg_n2[b][l], p.mid, 0, p.nrep_b[b]);
-      const StatPtr dg1 = statptr(ws, p.o_dg_n1[b][l], lo.cin, 0, p.nrep_b[b]);
-      const DropCfg drop = dropcfg(p, seed, layer_id, 1);
+      const LayerBind L = layer_bind(p, params, run, ws, b, l);
+      const int cin = p.layers[b][l].cin;
       // conv2 data gradient -> dZ2 (ReLU mask of norm2 applied) + dgamma2/dbeta2
-      FpropArgs a;
-      memset(&a, 0, sizeof(a));
-      set_kz(a, p, ws);
-      a.N = N; a.D = p.Db[b]; a.H = p.Hb[b]; a.W = p.Wb[b];
-      a.Cin = c.growth; a.M = p.mid; a.nrep = p.nrep_b[b];
-      a.in0 = fptr(ws, p.o_g[b]); a.in0_ns = xns; a.in0_coff = lo.cin;
-      a.in1 = fptr(ws, p.o_x[b]); a.in1_ns = xns; a.in1_coff = lo.cin;
-      a.gr_in = concat_grad(b, lo.cin);
-      a.drop_in = drop;
-      a.w = fptr(ws, p.o_pk_c2b[b][l]); a.w_ld = p.mid;
-      if (p.o_pk_c2b3[b][l]) { a.w3 = ws + p.o_pk_c2b3[b][l]; a.x3 = ws + p.o_x3; a.x3_bytes = p.x3_bytes; }
-      float* dz2 = fptr(ws, p.o_dz2[b]) + (long)l * N * tns;
-      a.out = dz2; a.out_ns = tns; a.out_coff = 0;
-      a.ex = fptr(ws, p.o_t1[b][l]); a.ex_ns = tns; a.ex_coff = 0;
-      a.ebn = bn2;
-      a.dbeta = dg2.sum; a.dgamma = dg2.sq;
-      a.pf_ptr = params + lo.c1; a.pf_bytes = (unsigned)(sizeof(float) * p.mid * lo.cin);
+      FpropArgs a = block_args(p, ws, b);
+      a.Cin = c.growth; a.M = p.mid;
+      set_in0(a, L.g_new); set_in1(a, L.x_new); a.gr_in = L.gr_new;
+      a.drop_in = dropcfg(p, seed, layer_id, 1);
+      set_conv2_weights(a, p, ws, b, l, true); a.w_ld = p.mid;
+      set_out(a, L.dz2); set_ex(a, L.t1); a.ebn = L.bn2;
+      a.dbeta = L.dg2.sum; a.dgamma = L.dg2.sq;
+      prefetch(a, conv1_weights(p, params, b, l));
       { ScopedTimer t(p, T_CONV2_DGRAD, b, stream); rc = launch_fprop(a, 27, PRO_GRAD, EPI_MASK_STORE, stream); }
       if (rc) return rc;
-      // BN-backward of T1 (single consumer norm2): S1 = dbeta2, S2 = dgamma2, scaled by gamma2
-      BnBwd g1;
-      g1.st = statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]);
-      g1.s = dg2;
-      g1.gamma = params + lo.n2w;
-      g1.inv_count = 1.0 / cnt;
-      g1.eps = c.eps;
       // conv1 data gradient -> G[0:cin) += gamma1 * mask * (...), dgamma1/dbeta1, S1/S2
-      FpropArgs d;
-      memset(&d, 0, sizeof(d));
-      set_kz(d, p, ws);
-      d.N = N; d.D = p.Db[b]; d.H = p.Hb[b]; d.W = p.Wb[b];
-      d.Cin = p.mid; d.M = lo.cin; d.nrep = p.nrep_b[b];
-      d.in0 = dz2; d.in0_ns = tns; d.in0_coff = 0;
-      d.in1 = fptr(ws, p.o_t1[b][l]); d.in1_ns = tns; d.in1_coff = 0;
-      d.gr_in = g1;
-      d.w = params + lo.c1; d.w_ld = lo.cin;
-      d.out = fptr(ws, p.o_g[b]); d.out_ns = xns; d.out_coff = 0;
-      d.ex = fptr(ws, p.o_x[b]); d.ex_ns = xns; d.ex_coff = 0;
-      d.ebn = bn1;
-      d.dbeta = dg1.sum; d.dgamma = dg1.sq;
-      d.s_acc = sptr(b, 0);
-      if (l > 0 && p.o_pk_c2b3[b][l - 1]) { d.pf_ptr = fptr(ws, p.o_pk_c2b3[b][l - 1]); d.pf_bytes = (unsigned)(3 * sizeof(uint16_t) * c.growth * p.mid * 27); }
-      else if (l > 0) { d.pf_ptr = fptr(ws, p.o_pk_c2b[b][l - 1]); d.pf_bytes = (unsigned)(sizeof(float) * c.growth * p.mid * 27); }
+      FpropArgs d = block_args(p, ws, b);
+      d.Cin = p.mid; d.M = cin;
+      set_in0(d, L.dz2); set_in1(d, L.t1); d.gr_in = L.gr_t1;
+      d.w = conv1_weights(p, params, b, l).p; d.w_ld = cin;
+      set_out(d, L.g); set_ex(d, L.x); d.ebn = L.bn1;
+      d.dbeta = L.dg1.sum; d.dgamma = L.dg1.sq;
+      d.s_acc = L.s_x;
+      if (l > 0) prefetch(d, conv2_panel(p, ws, b, l - 1, true));
       { ScopedTimer t(p, T_CONV1_DGRAD, b, stream); rc = launch_fprop(d, 1, PRO_GRAD, EPI_MASK_ACCUM, stream); }
       if (rc) return rc;
     }
     if ((rc = block_wgrads(b, layer_id))) return rc;     // layer_id: the block's first layer
+    const View X = concat(p, ws, b), G = concat_grad(p, ws, b);
+    const BnBwd gr = bnbwd(p, ws, params, norm1(p, b, 0));   // BN-backward of the whole concat buffer (gammas folded into G)
     if (b > 0) {
       const int pb = b - 1;
       const TransOff& t = p.trans[pb];
-      const long pxns = (long)p.ctot_b[pb] * p.Vb[pb];
       // transition conv weight gradient (input = pooled activations)
       WgradArgs w;
-      memset(&w, 0, sizeof(w));
-      w.N = N; w.D = p.Db[b]; w.H = p.Hb[b]; w.W = p.Wb[b];
+      wgrad_shape(w, p, b);
       w.M = t.cout; w.Cin = t.cin;
-      w.g0 = fptr(ws, p.o_g[b]); w.g0_ns = xns; w.g0_coff = 0;
-      w.g1 = fptr(ws, p.o_x[b]); w.g1_ns = xns; w.g1_coff = 0;
-      w.gr = concat_grad(b, 0);
-      w.x = fptr(ws, p.o_ap[pb]); w.x_ns = (long)t.cin * p.Vb[b]; w.x_coff = 0;
-      w.slab = fptr(ws, p.o_sl_tr[pb]); w.slab_stride = (long)t.cout * t.cin; w.nsplit = p.ns_tr[pb];
+      set_g0(w, G); set_g1(w, X); w.gr = gr;
+      set_x(w, pooled(p, ws, pb));
+      w.slab = fptr(ws, p.o_sl_tr[pb]); w.slab_stride = trans_elems(t); w.nsplit = p.ns_tr[pb];
       if ((rc = launch_wgrad1(w, PRO_NONE, stream))) return rc;
       // transition conv data gradient -> gradient wrt the pooled activations
-      FpropArgs d;
-      memset(&d, 0, sizeof(d));
-      set_kz(d, p, ws);
-      d.N = N; d.D = p.Db[b]; d.H = p.Hb[b]; d.W = p.Wb[b];
+      FpropArgs d = block_args(p, ws, b);
+      d.nrep = 0;   // (as it always was: the plain store epilogue accumulates no statistics)
       d.Cin = t.cout; d.M = t.cin;
-      d.in0 = w.g0; d.in0_ns = xns; d.in0_coff = 0;
-      d.in1 = w.g1; d.in1_ns = xns; d.in1_coff = 0;
-      d.gr_in = w.gr;
+      set_in0(d, G); set_in1(d, X); d.gr_in = gr;
       d.w = params + t.cw; d.w_ld = t.cin;
-      d.out = fptr(ws, p.o_dap); d.out_ns = (long)t.cin * p.Vb[b]; d.out_coff = 0;
+      set_out(d, pooled_grad(p, ws, pb));
       if ((rc = launch_fprop(d, 1, PRO_GRAD, EPI_STORE, stream))) return rc;
       // un-pool + ReLU + BN of the transition: first contribution to the previous block's G
-      ConsumerBwdArgs q;
-      q.N = N; q.C = t.cin; q.D = p.Db[pb]; q.H = p.Hb[pb]; q.W = p.Wb[pb]; q.mode = 1; q.nrep = p.nrep_b[pb];
-      q.dy = fptr(ws, p.o_dap);
-      q.x = fptr(ws, p.o_x[pb]); q.x_ns = pxns;
-      q.bn = bnfwd(p, statptr(ws, p.o_st_x[pb], p.ctot_b[pb], 0, p.nrep_b[pb]), params, run, t.nw, t.nb, t.rm, t.rv, (double)N * p.Vb[pb], 1);
-      q.g = fptr(ws, p.o_g[pb]); q.g_ns = pxns;
-      StatPtr dg = statptr(ws, p.o_dg_tr[pb], t.cin, 0, p.nrep_b[pb]);
-      q.dbeta = dg.sum; q.dgamma = dg.sq;
-      q.s_acc = sptr(pb, 0);
-      if ((rc = launch_consumer_bwd(q, stream))) return rc;
+      if ((rc = launch_consumer_bwd(consumer_bwd_args(p, params, run, ws, transition(p, pb), pb, 1, pooled_grad(p, ws, pb).p), stream))) return rc;
     } else {
-      const double cnt0 = (double)N * p.D0 * p.H0 * p.W0;
-      StemPoolBwdArgs q;
+      const NormSite n0 = norm0(p);
+      const StatPtr dg = dgsums(ws, n0);
+      StemPoolBwdArgs q; memset(&q, 0, sizeof(q));
       q.N = N; q.C = c.init_features; q.Di = p.D0; q.Hi = p.H0; q.Wi = p.W0; q.Do = p.Db[0]; q.Ho = p.Hb[0]; q.Wo = p.Wb[0];
       q.x = fptr(ws, p.o_conv0);
-      q.bn = bnfwd(p, statptr(ws, p.o_st_conv0, c.init_features, 0), params, run, p.p_n0w, p.p_n0b, p.r_n0m, p.r_n0v, cnt0, 1);
-      q.g = fptr(ws, p.o_g[0]); q.g_ns = xns;
-      q.xp = fptr(ws, p.o_x[0]); q.xp_ns = xns;
-      q.gr = concat_grad(0, 0);
+      q.bn = bnfwd(p, ws, params, run, n0, 1);
+      q.g = G.p; q.g_ns = G.ns; q.xp = X.p; q.xp_ns = X.ns;
+      q.gr = gr;
       q.idx = reinterpret_cast<const unsigned char*>(ws + p.o_idx);
       q.dz = fptr(ws, p.o_dz0);
-      StatPtr dg = statptr(ws, p.o_dg_n0, c.init_features, 0);
       q.dbeta = dg.sum; q.dgamma = dg.sq;
       if ((rc = launch_stem_pool_bwd(q, stream))) return rc;
-      StemWgradArgs w;
+      StemWgradArgs w; memset(&w, 0, sizeof(w));
       w.N = N; w.Cin = c.in_channels; w.D = p.D; w.H = p.H; w.W = p.W; w.Do = p.D0; w.Ho = p.H0; w.Wo = p.W0; w.M = c.init_features;
       w.x = x; w.dz = fptr(ws, p.o_dz0); w.y = fptr(ws, p.o_conv0);
-      w.gr.st = statptr(ws, p.o_st_conv0, c.init_features, 0);
-      w.gr.s = dg;
-      w.gr.gamma = params + p.p_n0w;
-      w.gr.inv_count = 1.0 / cnt0;
-      w.gr.eps = c.eps;
+      w.gr = bnbwd(p, ws, params, n0);   // BN-backward of the conv output (single consumer norm0)
       w.slab = fptr(ws, p.o_sl_conv0); w.slab_stride = (long)c.in_channels * c.init_features * 352; w.nsplit = p.ns_conv0;
       { ScopedTimer t(p, T_STEM_WGRAD, -1, stream); rc = launch_stem_wgrad(w, stream); }
       if (rc) return rc;
@@ -818,34 +819,15 @@ int plan_backward_range(Plan& p, const float* params, const float* x, char* ws, 
 int plan_relu_mask(Plan& p, const float* params, char* ws, int kind, int b, int l, unsigned char* out, hipStream_t stream) {
   MMNN_REQUIRE(p.tab_ws == ws && p.tab_params == params, "relu_mask: must follow a training forward on the same buffers");
   const NetCfg& c = p.cfg;
-  float* run = p.tab_run;
-  MaskArgs a;
-  a.out = out; a.N = p.N;
-  if (kind == 0) {
-    a.C = c.init_features; a.V = p.D0 * p.H0 * p.W0;
-    a.x = fptr(ws, p.o_conv0); a.x_ns = (long)a.C * a.V;
-    a.bn = bnfwd(p, statptr(ws, p.o_st_conv0, c.init_features, 0), params, run, p.p_n0w, p.p_n0b, p.r_n0m, p.r_n0v, (double)p.N * a.V, 1);
-    return launch_relu_mask(a, stream);
-  }
-  MMNN_REQUIRE(b >= 0 && b < c.nblocks, "relu_mask: bad block %d", b);
-  const double cnt = (double)p.N * p.Vb[b];
-  a.V = p.Vb[b];
-  if (kind == 3) {
-    MMNN_REQUIRE(b < c.nblocks - 1, "relu_mask: block %d has no transition", b);
-    const TransOff& t = p.trans[b];
-    a.C = t.cin; a.x = fptr(ws, p.o_x[b]); a.x_ns = (long)p.ctot_b[b] * p.Vb[b];
-    a.bn = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, t.nw, t.nb, t.rm, t.rv, cnt, 1);
-    return launch_relu_mask(a, stream);
-  }
-  MMNN_REQUIRE(l >= 0 && l < c.block_layers[b] && (kind == 1 || kind == 2), "relu_mask: bad site (%d,%d,%d)", kind, b, l);
-  const LayerOff& lo = p.layers[b][l];
-  if (kind == 1) {
-    a.C = lo.cin; a.x = fptr(ws, p.o_x[b]); a.x_ns = (long)p.ctot_b[b] * p.Vb[b];
-    a.bn = bnfwd(p, statptr(ws, p.o_st_x[b], p.ctot_b[b], 0, p.nrep_b[b]), params, run, lo.n1w, lo.n1b, lo.r1m, lo.r1v, cnt, 1);
-  } else {
-    a.C = p.mid; a.x = fptr(ws, p.o_t1[b][l]); a.x_ns = (long)p.mid * p.Vb[b];
-    a.bn = bnfwd(p, statptr(ws, p.o_st_t1[b][l], p.mid, 0, p.nrep_b[b]), params, run, lo.n2w, lo.n2b, lo.r2m, lo.r2v, cnt, 1);
-  }
+  MMNN_REQUIRE(kind == 0 || (b >= 0 && b < c.nblocks), "relu_mask: bad block %d", b);
+  MMNN_REQUIRE(kind != 3 || b < c.nblocks - 1, "relu_mask: block %d has no transition", b);
+  MMNN_REQUIRE(kind == 0 || kind == 3 || (l >= 0 && l < c.block_layers[b] && (kind == 1 || kind == 2)), "relu_mask: bad site (%d,%d,%d)", kind, b, l);
+  const NormSite s = kind == 0 ? norm0(p) : kind == 1 ? norm1(p, b, l) : kind == 2 ? norm2(p, b, l) : transition(p, b);
+  const int V = kind == 0 ? p.D0 * p.H0 * p.W0 : p.Vb[b];
+  const View X = kind == 0 ? View{fptr(ws, p.o_conv0), (long)s.C * V, 0} : kind == 2 ? t1(p, ws, b, l) : concat(p, ws, b);
+  MaskArgs a; memset(&a, 0, sizeof(a));
+  a.out = out; a.N = p.N; a.C = s.C; a.V = V; a.x = X.p; a.x_ns = X.ns;
+  a.bn = bnfwd(p, ws, params, p.tab_run, s, 1);
   return launch_relu_mask(a, stream);
 }
 

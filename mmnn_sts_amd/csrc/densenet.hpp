@@ -24,6 +24,19 @@ struct LayerOff {          // offsets (floats) into the flat parameter / running
 };
 struct TransOff { long nw, nb, cw; long rm, rv; int cin, cout; };
 
+// One batch-norm site -- norm0, a layer's norm1 / norm2, a transition norm, norm5 -- described ONCE (densenet.hip: norm0 .. norm5): forward,
+// data gradients, weight gradients, ReLU masks and the running-stat / finalise jobs all derive what they bind from it.
+struct NormSite {
+  size_t o_st;               // batch statistics of the normalised tensor: workspace row [2][NREP][stride]
+  size_t o_s;                // its backward sums S1 / S2, same row shape.  A tensor with this single consumer (norm0, norm2) has S1 = dbeta,
+                             // S2 = dgamma (o_s == o_dg); a concat row collects every consumer's, their gammas folded into G
+  size_t o_dg;               // dgamma/dbeta pair block of the site, [2][NREP][C]
+  int stride, off, C, nrep;  // row stride, first channel, channels the site sees, replicas in use
+  long w, b, rm, rv;         // gamma / beta in the parameter buffer, running mean / var in the running-stat buffer
+  double count;              // elements per channel, N * V
+};
+struct View { float* p; long ns; int coff; };   // a tensor as the kernels address it: p[n * ns + (coff + c) * V + voxel]
+
 struct Plan {
   NetCfg cfg;
   int N, D, H, W;

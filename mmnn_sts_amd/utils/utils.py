@@ -184,7 +184,7 @@ class GradCAM(nn.Module):
         g = bb.cfg["growth_rate"]
         sp = tuple(h.shape[2:])
         v = h[0, 0].numel()
-        # the last dense block's concat buffer is [N][c_total][v] (csrc/densenet.hip: o_x, sample stride c_total * v); its last `g`
+        # the last dense block's concat buffer is [N][c_total][v] (csrc/densenet.hip: the `concat` view, sample stride c_total * v); its last `g`
         # channels are the output of the last conv2 (dropout is the identity in eval)
         off = L.mmnn_densenet_ws_offset(ent["plan"], b"x", len(bb.cfg["block_config"]) - 1, 0)
         if off < 0:
