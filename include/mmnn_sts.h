@@ -475,6 +475,33 @@ typedef struct {
 } mmnn_decode_slices_desc;
 int mmnn_decode_slices(const mmnn_decode_slices_desc* d, const void* pixels, const double* slice_scale, void* out, void* stream);
 
+/* ---- RTSTRUCT contours -> a mask on the scan's grid: the planar polygons of one ROI of an RT Structure Set, already mapped by the host
+ * into the scan's continuous voxel index space (a voxel centre sits at the integer index) and assigned to slices, filled into one byte
+ * per scan voxel (csrc/rtstruct.hip).  `points`: n_points pairs (px, py) in fp64; `contours`: n_contours pairs (first point, point
+ * count), sorted by slice; `slice_first`: z + 1 entries, the contours of slice k are [slice_first[k], slice_first[k + 1]).  Each contour
+ * is closed from its last point back to its first.  Voxel (i, j, k) is 1 if and only if an odd number of edges of slice k count for it
+ * (the even-odd rule), else 0.  Edge (x0, y0) -> (x1, y1) counts for the voxel when both hold, in fp64:
+ *   row test       (y0 <= j && j < y1) || (y1 <= j && j < y0): half open, so a vertex on a row counts once and a horizontal edge never.
+ *   side test      i < x0 + (j - y0) * (x1 - x0) / (y1 - y0), every operation rounded on its own (a subtraction, a multiply, a division
+ *                  and an addition in that order, never an FMA); a comparison with NaN is false.
+ * Contours may leave the grid on any side (they are clipped by construction), may have any orientation and may repeat points; the
+ * result does not depend on the order of the contours or of their edges.  `out` holds x*y*z bytes, x fastest -- a mask of NIfTI type 2
+ * for mmnn_ingest_volume, slope 1, inter 0 -- and every byte of it is written by the kernel (a slice without contours as zeros, no
+ * separate memset); nothing else is.  A contour record that does not lie inside `points`, and a slice range that does not lie inside
+ * `contours`, is ignored.  One launch, no atomics on global memory, no host synchronisation: repeated calls are bit-identical.  There
+ * is no cap on the points of a slice: its edges pass through LDS in chunks of MMNN_RASTERIZE_CHUNK_EDGES.  n_contours == 0 is legal
+ * (an all-zero mask; points and contours may then be null).  Refused (status 1) before any launch: a null descriptor, a non-positive
+ * extent, x > MMNN_INGEST_MAX_X, a negative n_contours or n_points, a null slice_first / out, null points / contours with
+ * n_contours > 0, a pointer not aligned to its element size. */
+#define MMNN_RASTERIZE_CHUNK_EDGES 1024
+typedef struct {
+  int32_t x, y, z;                /* the scan's grid = the output grid, NIfTI dim[1..3] */
+  int32_t n_contours;
+  int64_t n_points;
+} mmnn_rasterize_desc;
+int mmnn_rasterize_contours(const mmnn_rasterize_desc* d, const double* points, const int32_t* contours, const int32_t* slice_first,
+                            uint8_t* out, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

@@ -119,6 +119,14 @@ class DecodeSlicesDesc(Structure):
                 ("is_signed", c_int32), ("out_type", c_int32)]
 
 
+RASTERIZE_CHUNK_EDGES = 1024                 # MMNN_RASTERIZE_CHUNK_EDGES
+
+
+class RasterizeDesc(Structure):
+    """mmnn_rasterize_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_contours", c_int32), ("n_points", c_int64)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -219,6 +227,8 @@ def lib():
     L.mmnn_maps_to_scan.argtypes = [POINTER(MapsToScanDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_decode_slices.restype = c_int32
     L.mmnn_decode_slices.argtypes = [POINTER(DecodeSlicesDesc), c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_rasterize_contours.restype = c_int32
+    L.mmnn_rasterize_contours.argtypes = [POINTER(RasterizeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

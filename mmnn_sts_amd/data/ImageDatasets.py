@@ -6,8 +6,11 @@ detected per tree (`Data: format: auto | nifti | dicom` forces one; a tree that 
             `-`-separated fields of the directory name (:426)
     DICOM   the sub-directories `image` and `mask` each hold one series, `<series>/*.dcm` or the files themselves (:26-56); the
             anonymised id is the directory name when the key has it (data/utils.py:8-14), else as for NIfTI.  Uncompressed
-            single-frame series only (`mmnn_sts_amd.data.dicom`); the mask is a DICOM image series too (SEG / RTSTRUCT and a NIfTI
-            mask beside a DICOM scan are outside the path), always resampled into the scan's grid and binarised at 128 by default
+            single-frame series only (`mmnn_sts_amd.data.dicom`); the mask is a DICOM image series too, always resampled into the
+            scan's grid and binarised at 128 by default -- or one RT Structure Set file (`mmnn_sts_amd.data.rtstruct`): `mask/` (or
+            its single sub-directory) then holds no image file and exactly one RTSTRUCT file, whose ROI `mask_roi` (`Data: mask_roi`;
+            None: its only ROI) is rasterised onto the scan's own grid on the device and takes neither resample nor threshold.
+            DICOM SEG and a NIfTI mask beside a DICOM scan are outside the path
 
 `patient_key` is a csv with the columns `Anon MRN` and `MRN` that maps the anonymised id to the uid.  Labels come from this project's
 clinical csv (`ClinicalDatasets.LabelTable`), joined on `uid`.  `ImageClassificationDataset` / `ImageSurvivalDataset` are upstream's
@@ -29,7 +32,7 @@ import os
 import torch
 
 from ..exceptions.exceptions import ConfigurationError
-from . import dicom, nifti
+from . import dicom, nifti, rtstruct
 from .ClinicalDatasets import LabelTable
 from .ingest import MASK_RESAMPLE_MODES, RawPatient
 
@@ -59,21 +62,54 @@ def layout_of(patient_path):
     if is_dicom and is_nifti:
         raise ConfigurationError(f"{patient_path} holds both the DICOM layout (image/, mask/) and a NIfTI scan*: one format per tree")
     if os.path.isdir(os.path.join(patient_path, 'image')) and not is_dicom:
-        raise ConfigurationError(f"{patient_path}: image/ without a mask/ series directory beside it (a NIfTI mask beside a DICOM scan, DICOM SEG "
-                                 "and RTSTRUCT are outside the path)")
+        raise ConfigurationError(f"{patient_path}: image/ without a mask/ directory beside it (a NIfTI mask beside a DICOM scan and DICOM SEG "
+                                 "are outside the path; an RTSTRUCT file belongs into mask/)")
     return 'dicom' if is_dicom else ('nifti' if is_nifti else None)
+
+
+def rtstruct_in(mask_directory):
+    """The path of the RT Structure Set file when `mask_directory` (or its single sub-directory) holds no DICOM image file and exactly
+    one RTSTRUCT file; None when it holds no RTSTRUCT file (an image series, or nothing this path reads).  Refused: several RTSTRUCT
+    files, an RTSTRUCT file beside image files."""
+    try:
+        d = dicom.series_directory(mask_directory)
+    except ConfigurationError:
+        return None                          # (read_series reports what is wrong with the directory)
+    found, images = [], 0
+    for name in sorted(os.listdir(d)):
+        p = os.path.join(d, name)
+        if name.startswith('.') or not os.path.isfile(p):
+            continue
+        try:
+            f = dicom.read_file(p, header_only=True)
+        except dicom.NotDicomError:
+            continue
+        if f.sop_class_uid == rtstruct.RT_STRUCTURE_SET_STORAGE:
+            found.append(p)
+        elif f.has_image:
+            images += 1
+    if not found:
+        return None
+    if len(found) > 1:
+        raise ConfigurationError(f"{d}: {len(found)} RTSTRUCT files ({', '.join(os.path.basename(p) for p in found[:4])}): one structure set per mask/ is expected")
+    if images:
+        raise ConfigurationError(f"{d}: an RTSTRUCT file ({os.path.basename(found[0])}) beside {images} DICOM image file(s): mask/ holds either "
+                                 "one image series or one structure set")
+    return found[0]
 
 
 class ImageDataset(torch.utils.data.Dataset):
     format = 'auto'             # the layout a class is bound to; the constructor's `format` overrides it
 
-    def __init__(self, patient_directory, patient_key, mask_resample='auto', log_grids=True, format=None):
+    def __init__(self, patient_directory, patient_key, mask_resample='auto', log_grids=True, format=None, mask_roi=None):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         format = str(self.format if format is None else format).lower()
         if format not in FORMATS:
             raise ConfigurationError(f"format {format!r} is none of {FORMATS}")
         self.mask_resample = mask_resample
+        self.mask_roi = mask_roi
+        self._rtstruct = {}                  # mask directory -> the RTSTRUCT file in it, or None (an image series)
         self.patient_directory = str(patient_directory)
         self.patients = sorted(x for x in os.listdir(self.patient_directory)
                                if not x.startswith('.') and os.path.isdir(os.path.join(self.patient_directory, x)))
@@ -114,11 +150,23 @@ class ImageDataset(torch.utils.data.Dataset):
         return self.patient_key[self._anon(patient)]
 
     def _geometry(self, path):
-        """(extents, affine or None) from the headers alone."""
+        """(extents, affine or None) from the headers alone.  An RTSTRUCT mask has no grid of its own: (None, None), once its ROI
+        names have been read and `mask_roi` resolved against them (a bad name fails here, at construction)."""
+        if self.layout == 'dicom' and self._rtstruct_of(path):
+            rtstruct.resolve(rtstruct.read(self._rtstruct_of(path), header_only=True), self.mask_roi)
+            return None, None
         if self.layout == 'dicom':
             series = dicom.read_series(path, header_only=True)
             return series.shape, series.affine
         return nifti.read_geometry(path)
+
+    def _rtstruct_of(self, directory):
+        """The RTSTRUCT file of a mask/ directory, or None; image/ directories always hold a series."""
+        if os.path.basename(directory) != 'mask':
+            return None
+        if directory not in self._rtstruct:
+            self._rtstruct[directory] = rtstruct_in(directory)
+        return self._rtstruct[directory]
 
     @property
     def uids(self):
@@ -147,13 +195,22 @@ class ImageDataset(torch.utils.data.Dataset):
     def _load(self, patient):
         scan_path, mask_path = self._files(patient)
         read = dicom.read_series if self.layout == 'dicom' else nifti.read
+        if self.layout == 'dicom' and self._rtstruct_of(mask_path):
+            # the contours are born on the scan's grid: the collate function rasterises them there (no resample, no threshold)
+            return read(scan_path), rtstruct.select(rtstruct.read(self._rtstruct_of(mask_path)), self.mask_roi)
         scan, mask = read(scan_path), read(mask_path)
         self._check_grids(patient, (scan.shape, scan.affine, scan_path), (mask.shape, mask.affine, mask_path))
         return scan, mask
 
     def _check_grids(self, patient, scan, mask):
-        """scan, mask: (extents, affine or None, path).  True when the mask's extents differ from the scan's and can be resampled."""
+        """scan, mask: (extents, affine or None, path).  True when the mask's extents differ from the scan's and can be resampled.
+        An RTSTRUCT mask (extents None) is on the scan's grid by construction; its scan needs a geometry to place the contours by."""
         (sshape, saff, _), (mshape, maff, _) = scan, mask
+        if mshape is None:
+            if saff is None:
+                raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {scan[2]} has no position / orientation to place the "
+                                         f"contours of {self._rtstruct_of(mask[2])} by")
+            return False
         what = f"patient {patient} (uid {self._uid_of(patient)}): scan extent {tuple(sshape)}, mask extent {tuple(mshape)}"
         if len(sshape) != 3 or len(mshape) != 3:
             raise ConfigurationError(what)
@@ -182,8 +239,8 @@ class _LabelledNifti(ImageDataset):
     survival = False
 
     def __init__(self, patient_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', log_grids=True,
-                 format=None):
-        super().__init__(patient_directory, patient_key, mask_resample, log_grids, format)
+                 format=None, mask_roi=None):
+        super().__init__(patient_directory, patient_key, mask_resample, log_grids, format, mask_roi)
         if slices:
             raise ConfigurationError("slices=True (2-D slices of a volume) is outside the MI355X path")
         if transforms is not None:
@@ -227,14 +284,15 @@ class ImageSurvivalDataset(_LabelledNifti):
 
 
 class _T1T2(_LabelledNifti):
-    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', format=None):
+    def __init__(self, t1_directory, t2_directory, clinical_data, patient_key, slices=False, transforms=None, mask_resample='auto', format=None,
+                 mask_roi=None):
         cls = NiftiSurvivalDataset if self.survival else NiftiImageDataset
-        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None, mask_resample, format=format)
-        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None, mask_resample, format=format)
+        self.t1_dataset = cls(t1_directory, clinical_data, patient_key, slices, None, mask_resample, format=format, mask_roi=mask_roi)
+        self.t2_dataset = cls(t2_directory, clinical_data, patient_key, slices, None, mask_resample, format=format, mask_roi=mask_roi)
         if self.t1_dataset.layout != self.t2_dataset.layout:
             raise ConfigurationError(f"{t1_directory} is a {self.t1_dataset.layout} tree and {t2_directory} a {self.t2_dataset.layout} one: one format for both")
         super().__init__(t1_directory, clinical_data, patient_key, slices, transforms, mask_resample, log_grids=False,
-                         format=self.t1_dataset.layout)   # (t1 has reported)
+                         format=self.t1_dataset.layout, mask_roi=mask_roi)   # (t1 has reported)
         self.t1_patients, self.t2_patients = self.t1_dataset.patients, self.t2_dataset.patients
         # patients common to both trees, by anonymised id; kept as the T1 directory names
         in_t2 = {self.t2_dataset._anon(p): p for p in self.t2_patients}

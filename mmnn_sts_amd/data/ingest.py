@@ -6,6 +6,7 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
 
     upload(volume, device)                          host volume (NiftiImage, DicomSeries or ndarray) -> DeviceVolume
     decode_series(series, device)                   a sorted DICOM series -> DeviceVolume: the slices' bytes decoded on device (mmnn_decode_slices)
+    rasterize_contours(contours, scan, device)      the contours of an RTSTRUCT ROI -> uint8 0 / 1 on the scan's grid (mmnn_rasterize_contours)
     resample_mask(mask, scan_shape, index_map)      a mask drawn on another grid -> uint8 bytes on the scan's grid (mmnn_resample_mask)
     ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
     collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
@@ -21,6 +22,10 @@ A DICOM series (`dicom.read_series`) takes one more step in front: its slices' P
 `mmnn_decode_slices` unpacks the stored bits, extends the sign and, where the slices differ in RescaleSlope / RescaleIntercept, rescales
 per slice.  A DICOM (scan, mask) pair always passes through `resample_mask` -- upstream always runs `sitk.Resample(mask, image)` and
 `mask > 128` on that path -- with the identity map when the two series share one grid, and its default threshold is 128.
+
+A mask that is an RT Structure Set (`rtstruct.read` -> `ContourSet`) beside a DICOM scan is born on the scan's grid: the host maps the
+contour points into the scan's voxel index space (`rtstruct.to_scan_index`), `mmnn_rasterize_contours` fills them by the even-odd rule
+into 0 / 1 bytes, and the pair takes the voxelwise path -- no resample, no threshold.
 """
 import ctypes
 from dataclasses import dataclass
@@ -31,9 +36,10 @@ import torch
 
 from .. import _lib
 from ..exceptions.exceptions import ConfigurationError
-from . import nifti
+from . import nifti, rtstruct
 from .dicom import DicomSeries
 from .nifti import NiftiImage
+from .rtstruct import ContourSet
 
 SIZE = 64                                    # MMNN_INGEST_SIZE
 MASK_RESAMPLE_MODES = ("auto", "geometry", "never")
@@ -70,7 +76,7 @@ class KeptVolume:
 @dataclass
 class RawPatient:
     """What an image dataset's `__getitem__` yields in place of a float volume: per modality the (scan, mask) pair, still raw (two
-    NiftiImages, or two DicomSeries)."""
+    NiftiImages, two DicomSeries, or a DicomSeries and the ContourSet of its RTSTRUCT mask)."""
     uid: int
     volumes: List[Tuple[object, object]]
 
@@ -141,6 +147,66 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
     return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
 
 
+@dataclass
+class StagedContours:
+    """The three arrays of `rtstruct.to_scan_index` in one device buffer: a contour mask between its upload and its rasterisation
+    (`collate_volumes` issues every upload of a batch before its first kernel)."""
+    staged: torch.Tensor
+    at_records: int                          # byte offsets of the contour records and of slice_first behind the points
+    at_slices: int
+    n_contours: int
+    n_points: int
+    slices: int
+
+
+def stage_contours(contours, scan, device, roi=None) -> StagedContours:
+    """Upload a contour mask for the grid of `scan` (anything with `.shape` and `.affine`): one pinned staging buffer for the three
+    arrays and one non-blocking copy.  `contours`: a ContourSet (`roi` names the ROI to take; None: its only one), placed on the
+    scan's grid by `rtstruct.to_scan_index`, or the (points, contours, slice_first) arrays themselves."""
+    if isinstance(contours, ContourSet):
+        if not is_dicom(scan):
+            raise ConfigurationError(f"an RTSTRUCT mask ({contours.path}) beside a NIfTI scan is outside the path: both come from one format")
+        contours = rtstruct.to_scan_index(rtstruct.select(contours, roi), scan.shape, scan.affine)
+    points, records, slice_first = (np.ascontiguousarray(a, dtype=t) for a, t in zip(contours[:3], (np.float64, np.int32, np.int32)))
+    if points.ndim != 2 or points.shape[1] != 2 or records.ndim != 2 or records.shape[1] != 2 or slice_first.ndim != 1 or slice_first.size < 2:
+        raise ValueError(f"rasterize_contours: points (P, 2), contours (C, 2) and slice_first (z + 1,) expected, got {points.shape}, {records.shape}, {slice_first.shape}")
+    at_records = points.nbytes               # (a multiple of 16: every array starts aligned to its element size)
+    at_slices = at_records + records.nbytes
+    stage = torch.empty(at_slices + slice_first.nbytes, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    host[:at_records] = points.reshape(-1).view(np.uint8)
+    host[at_records:at_slices] = records.reshape(-1).view(np.uint8)
+    host[at_slices:] = slice_first.view(np.uint8)
+    return StagedContours(stage.to(torch.device(device), non_blocking=True), at_records, at_slices, len(records), len(points), slice_first.size - 1)
+
+
+def rasterize_contours(contours, scan, device=None, roi=None, out: Optional[torch.Tensor] = None) -> DeviceVolume:
+    """The contours of one ROI -> uint8 0 / 1 on the grid of `scan` (anything with `.shape` and `.affine`: a DicomSeries, a
+    DeviceVolume), by the even-odd rule of `mmnn_rasterize_contours`.  `contours`: what `stage_contours` takes, or its result.  One
+    pinned staging buffer, one non-blocking copy and one launch on the current stream.  `device`: None is `out`'s, else the current
+    one.  `out`: a contiguous uint8 CUDA tensor of x*y*z elements to write, allocated when None.  The result is a mask of type 2,
+    slope 1, inter 0 with the scan's affine -- on the scan's grid by construction, so it is neither resampled nor thresholded."""
+    x, y, z = (int(v) for v in scan.shape)
+    if not isinstance(contours, StagedContours):
+        if device is None:
+            device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+        contours = stage_contours(contours, scan, device, roi)
+    dev = contours.staged.device
+    if contours.slices != z:
+        raise ValueError(f"rasterize_contours: slice_first has {contours.slices + 1} entries, a scan of {z} slices needs {z + 1}")
+    if out is None:
+        out = torch.empty(x * y * z, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x * y * z):
+        raise ValueError(f"rasterize_contours: out must be {x * y * z} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    desc = _lib.RasterizeDesc(x, y, z, contours.n_contours, contours.n_points)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        p = contours.staged.data_ptr()
+        _lib.check(_lib.lib().mmnn_rasterize_contours(ctypes.byref(desc), p, p + contours.at_records, p + contours.at_slices, out.data_ptr(), stream),
+                   "mmnn_rasterize_contours")
+    return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, getattr(scan, "affine", None))
+
+
 def workspace_bytes(x: int, y: int, z: int) -> int:
     n = _lib.lib().mmnn_ingest_workspace_bytes(int(x), int(y), int(z))
     if n < 0:
@@ -190,6 +256,10 @@ def mask_index_map(scan, mask, mode: str = "auto"):
     anything with `.shape` and `.affine`.  Raises ConfigurationError where `mode` or the missing geometry forbids a needed resample."""
     if mode not in MASK_RESAMPLE_MODES:
         raise ConfigurationError(f"mask_resample {mode!r} is none of {MASK_RESAMPLE_MODES}")
+    if isinstance(mask, (ContourSet, StagedContours)):           # rasterised onto the scan's own grid: nothing to resample
+        if not is_dicom(scan):
+            raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
+        return None
     same = tuple(scan.shape) == tuple(mask.shape)
     if is_dicom(scan) or is_dicom(mask):
         return _dicom_index_map(scan, mask, mode, same)
@@ -237,14 +307,24 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     extents differ, or an `index_map` is given, the mask is first resampled into the scan's grid (`resample_mask`, binarised at
     `threshold`); without `index_map` the map comes from the two volumes' affines, and differing extents without them are refused.
     Equal extents without `index_map` are the voxelwise path -- except for a DICOM pair, which is always resampled.  `threshold`
-    None: 0.5, or 128 behind a DICOM scan."""
+    None: 0.5, or 128 behind a DICOM scan.  A `mask` that is a ContourSet (or `stage_contours`' result) beside a DICOM scan is
+    rasterised onto the scan's grid first (`rasterize_contours`) and takes the voxelwise path: no resample, no threshold."""
     if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and tuple(out_plane.shape) == (SIZE,) * 3):
         raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, got {tuple(out_plane.shape)} {out_plane.dtype} on {out_plane.device}")
     dev = out_plane.device
-    scan, mask = upload(scan, dev), upload(mask, dev)
+    scan = upload(scan, dev)
+    drawn = isinstance(mask, (ContourSet, StagedContours))
+    if drawn:
+        if index_map is not None:
+            raise ValueError("ingest: a contour mask is rasterised onto the scan's own grid; it takes no index_map")
+        if not is_dicom(scan):
+            raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
+        mask = rasterize_contours(mask, scan, dev)
+    else:
+        mask = upload(mask, dev)
     if threshold is None:
         threshold = default_threshold(scan)
-    if index_map is None and (is_dicom(scan) or is_dicom(mask)):
+    if index_map is None and not drawn and (is_dicom(scan) or is_dicom(mask)):
         index_map = mask_index_map(scan, mask)
     if index_map is None and scan.shape != mask.shape:
         if scan.affine is None or mask.affine is None:
@@ -325,14 +405,15 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
     issued before the first kernel, so the copies of one volume run beside the passes of the one before it.  A mask on another grid
     than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`
-    (None: 0.5; 128 for a DICOM pair, which is always resampled).
+    (None: 0.5; 128 for a DICOM pair, which is always resampled).  A ContourSet as the mask of a DICOM scan (an RTSTRUCT file) is
+    placed on that scan's grid by the host, uploaded with the others and rasterised there; it takes neither resample nor threshold.
     With `keep_workspaces` every volume is ingested with a workspace of its own and a third value is returned: volumes[n][c], the
     `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan."""
     n, c = len(patients), len(patients[0])
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
     device = torch.device(device)
-    up = [[(upload(s, device), upload(m, device)) for s, m in p] for p in patients]
+    up = [[(upload(s, device), stage_contours(m, s, device) if isinstance(m, ContourSet) else upload(m, device)) for s, m in p] for p in patients]
     maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     batch = torch.empty((n, c, SIZE, SIZE, SIZE), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)

@@ -4,9 +4,10 @@
 
     <root>/images/t1/SYN-0007-t1-a/image/series_1/0003.dcm ...     one file per slice, names in a seeded random order
     <root>/images/t1/SYN-0007-t1-a/mask/series_1/0011.dcm ...      the mask as an 8-bit image series, 0 / 255
+    <root>/images/t1/SYN-0007-t1-a/mask/rtstruct.dcm               with mask_format="rtstruct": the mask as one RT Structure Set file
     <root>/key.csv, clinical.csv, train_uids.txt, val_uids.txt     copied from the NIfTI tree
 
-    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR
+    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct]
 
 The twin holds the same voxels -- slice k, row j, column i is the NIfTI voxel (i, j, k) -- and the same geometry: ImagePositionPatient,
 ImageOrientationPatient and PixelSpacing are the NIfTI affine's columns in LPS (a sheared or left-handed affine has no such form and is
@@ -25,6 +26,8 @@ from . import nifti
 from .dicom import EXPLICIT_LE, IMPLICIT_LE, LONG_VRS
 
 MR_IMAGE_STORAGE = "1.2.840.10008.5.1.4.1.1.4"
+RT_STRUCTURE_SET_STORAGE = "1.2.840.10008.5.1.4.1.1.481.3"
+MASK_FORMATS = ("series", "rtstruct")
 UID_ROOT = "1.2.3.4.5"                       # not a registered root: synthetic files only
 
 
@@ -160,10 +163,97 @@ def write_series(directory, volume, affine=None, slope=None, inter=None, series_
     return directory
 
 
-def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, seed=0, bits_stored=None, per_slice_scale=False):
+def _sequence(group, elem, items, explicit, undefined):
+    """A sequence element: `items` are the encoded data sets of its items; `undefined`: sequence and items of undefined length, closed
+    by their delimiters."""
+    if undefined:
+        body = b"".join(struct.pack("<HHI", 0xFFFE, 0xE000, 0xFFFFFFFF) + it + struct.pack("<HHI", 0xFFFE, 0xE00D, 0) for it in items)
+        body += struct.pack("<HHI", 0xFFFE, 0xE0DD, 0)
+        head = struct.pack("<HH2sHI", group, elem, b"SQ", 0, 0xFFFFFFFF) if explicit else struct.pack("<HHI", group, elem, 0xFFFFFFFF)
+        return head + body
+    return _element(group, elem, "SQ", b"".join(struct.pack("<HHI", 0xFFFE, 0xE000, len(it)) + it for it in items), explicit)
+
+
+def rtstruct_bytes(rois, explicit=True, undefined_lengths=False, frame_uid=UID_ROOT + ".9", sop_instance_uid=UID_ROOT + ".8.1") -> bytes:
+    """An RT Structure Set as a part-10 file.  `rois`: [(name, [(geometric type, (n, 3) points in LPS mm), ...]), ...]; a contour may
+    carry a third entry, the NumberOfContourPoints to declare in place of n.  Coordinates are written with `ds()`.  A ContourData
+    value too long for the 16-bit length of an explicit-VR DS element is written as UN with a 32-bit length (PS3.5 6.2.2)."""
+    def el(g, e, vr, v):
+        if explicit and vr not in LONG_VRS and len(v) > 0xFFFE:
+            vr = "UN"
+        return _element(g, e, vr, v, explicit)
+
+    syntax = EXPLICIT_LE if explicit else IMPLICIT_LE
+    meta = b"".join([_element(0x0002, 0x0001, "OB", b"\0\1", True), _element(0x0002, 0x0002, "UI", _text(RT_STRUCTURE_SET_STORAGE), True),
+                     _element(0x0002, 0x0003, "UI", _text(sop_instance_uid), True), _element(0x0002, 0x0010, "UI", _text(syntax), True),
+                     _element(0x0002, 0x0012, "UI", _text(UID_ROOT + ".0"), True)])
+    meta = _element(0x0002, 0x0000, "UL", struct.pack("<I", len(meta)), True) + meta
+    described, drawn = [], []
+    for number, (name, contours) in enumerate(rois, 1):
+        described.append(el(0x3006, 0x0022, "IS", _text(str(number))) + el(0x3006, 0x0024, "UI", _text(frame_uid)) + el(0x3006, 0x0026, "LO", _text(name)))
+        items = []
+        for kind, points, *declared in contours:
+            points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+            count = declared[0] if declared else len(points)
+            items.append(el(0x3006, 0x0042, "CS", _text(kind)) + el(0x3006, 0x0046, "IS", _text(str(int(count))))
+                         + el(0x3006, 0x0050, "DS", _text([ds(v) for v in points.reshape(-1)])))
+        drawn.append(el(0x3006, 0x002A, "IS", _text(["255", "0", "0"])) + _sequence(0x3006, 0x0040, items, explicit, undefined_lengths)
+                     + el(0x3006, 0x0084, "IS", _text(str(number))))
+    e = [el(0x0008, 0x0016, "UI", _text(RT_STRUCTURE_SET_STORAGE)), el(0x0008, 0x0018, "UI", _text(sop_instance_uid)), el(0x0008, 0x0060, "CS", b"RTSTRUCT"),
+         el(0x3006, 0x0002, "SH", b"SYNTHETIC"), _sequence(0x3006, 0x0020, described, explicit, undefined_lengths),
+         _sequence(0x3006, 0x0039, drawn, explicit, undefined_lengths)]
+    return b"\0" * 128 + b"DICM" + meta + b"".join(e)
+
+
+def run_rectangles(mask, affine):
+    """A binary (x, y, z) mask as closed planar contours in LPS mm: one rectangle per run of set voxels in each row, with its corners
+    at (i0 - 1/2, j - 1/2) ... (i1 + 1/2, j + 1/2) in voxel index coordinates, mapped through the RAS `affine`.  (A test device: a
+    contouring workstation draws one polygon around a region, not one per run.)"""
+    mask = np.asarray(mask) != 0
+    if mask.ndim != 3:
+        raise ConfigurationError(f"a mask has three axes, got {mask.shape}")
+    a = np.eye(4) if affine is None else np.asarray(affine, dtype=np.float64)
+    edge = np.diff(np.pad(mask, ((1, 1), (0, 0), (0, 0))).astype(np.int8), axis=0)       # (x + 1, y, z): +1 where a run starts, -1 behind its end
+    i0, j0, k0 = np.nonzero(edge == 1)
+    order = np.lexsort((i0, j0, k0))
+    i0, j0, k0 = i0[order], j0[order], k0[order]
+    i1, j1, k1 = np.nonzero(edge == -1)
+    order = np.lexsort((i1, j1, k1))
+    i1 = i1[order]                                                                       # (the runs of a row pair up in order)
+    lo, hi, top, bottom, k = i0 - 0.5, i1 - 0.5, j0 - 0.5, j0 + 0.5, k0.astype(np.float64)
+    corners = np.stack([np.stack([lo, top, k], 1), np.stack([hi, top, k], 1), np.stack([hi, bottom, k], 1), np.stack([lo, bottom, k], 1)], 1)   # (runs, 4, 3)
+    ras = corners @ a[:3, :3].T + a[:3, 3]
+    lps = ras * np.array([-1.0, -1.0, 1.0])
+    return [("CLOSED_PLANAR", p) for p in lps]
+
+
+def write_rtstruct(path, mask, affine, roi_name="GTV", extra_rois=(), explicit=True, undefined_lengths=False):
+    """Write the binary (x, y, z) `mask` as an RT Structure Set whose ROI `roi_name` holds one rectangle contour per run of set voxels
+    (`run_rectangles`).  `extra_rois`: further ROIs written in front of and behind it alternately -- a name (a decoy: one rectangle
+    around the whole first slice) or a (name, mask) pair."""
+    rois = [(roi_name, run_rectangles(mask, affine))]
+    for n, extra in enumerate(extra_rois):
+        if isinstance(extra, str):
+            decoy = np.zeros(np.asarray(mask).shape, dtype=np.uint8)
+            decoy[:, :, 0] = 1
+            extra = (extra, decoy)
+        roi = (extra[0], run_rectangles(extra[1], affine))
+        rois = [roi] + rois if n % 2 == 0 else rois + [roi]
+    os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(rtstruct_bytes(rois, explicit, undefined_lengths))
+    return str(path)
+
+
+def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, seed=0, bits_stored=None, per_slice_scale=False,
+                    mask_format="series", roi_name="GTV", extra_rois=()):
     """The DICOM twin of a `synth_nifti.write_tree` tree; returns the same dictionary of locations.  Scans keep their type, slope and
     inter (as RescaleSlope / RescaleIntercept); non-zero mask voxels become `mask_value` (None: the mask's values are kept) in an 8-bit
-    unsigned series.  `bits_stored`, `per_slice_scale`: of the scans (see `write_series`)."""
+    unsigned series.  `bits_stored`, `per_slice_scale`: of the scans (see `write_series`).  `mask_format` 'rtstruct': the mask directory
+    holds one RT Structure Set file instead (`write_rtstruct` of the non-zero mask voxels on the scan's geometry, ROI `roi_name`,
+    with `extra_rois`); the mask must then share the scan's extents."""
+    if mask_format not in MASK_FORMATS:
+        raise ConfigurationError(f"mask_format {mask_format!r} is none of {MASK_FORMATS}")
     nifti_root, dicom_root = str(nifti_root), str(dicom_root)
     src = os.path.join(nifti_root, "images")
     if not os.path.isdir(src):
@@ -190,6 +280,11 @@ def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, 
             scaling = scan.scaling() or (None, None)
             write_series(os.path.join(target, "image", "series_1"), scan.raw, scan.affine, scaling[0], scaling[1], f"{UID_ROOT}.{count}.1",
                          shuffle_names, seed + 2 * count, bits_stored, per_slice_scale)
+            if mask_format == "rtstruct":
+                if mask.raw.shape != scan.raw.shape:
+                    raise ConfigurationError(f"{d}: an RTSTRUCT twin is drawn on the scan's grid; the mask's extents {mask.raw.shape} differ from {scan.raw.shape}")
+                write_rtstruct(os.path.join(target, "mask", "rtstruct.dcm"), mask.raw, scan.affine, roi_name, extra_rois)
+                continue
             m = mask.raw if mask_value is None else np.where(mask.raw != 0, mask_value, 0)
             write_series(os.path.join(target, "mask", "series_1"), m.astype(np.uint8), mask.affine, None, None, f"{UID_ROOT}.{count}.2",
                          shuffle_names, seed + 2 * count + 1)
@@ -203,6 +298,8 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--bits_stored", type=int, default=None)
     ap.add_argument("--per_slice_scale", action="store_true")
+    ap.add_argument("--mask_format", choices=MASK_FORMATS, default="series", help="the masks as 8-bit image series or as RT Structure Set files")
     a = ap.parse_args()
-    for k, v in from_nifti_tree(a.nifti_dir, a.dicom_dir, seed=a.seed, bits_stored=a.bits_stored, per_slice_scale=a.per_slice_scale).items():
+    for k, v in from_nifti_tree(a.nifti_dir, a.dicom_dir, seed=a.seed, bits_stored=a.bits_stored, per_slice_scale=a.per_slice_scale,
+                                mask_format=a.mask_format).items():
         print(f"{k}: {v}")

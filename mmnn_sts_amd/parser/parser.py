@@ -7,7 +7,8 @@ integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  `getImagePat
 184-198) build the local-disk image datasets from the `Data:` section (`image_loc`, `t1_path`, `t2_path`, `data_loc`, `key_loc`; the
 command-line flags override it; `format: auto | nifti | dicom` names the patient directories' layout, detected per tree by default;
 `mask_resample`, `mask_threshold` say what happens to a mask drawn on another grid than its scan's -- a DICOM mask is always resampled,
-and binarised at 128 unless `mask_threshold` is set).  DICOM means uncompressed single-frame series (`mmnn_sts_amd.data.dicom`); S3 and
+and binarised at 128 unless `mask_threshold` is set; `mask_roi` names the region of interest to take from an RTSTRUCT mask, which is
+rasterised onto its scan's grid and takes neither resample nor threshold).  DICOM means uncompressed single-frame series (`mmnn_sts_amd.data.dicom`); S3 and
 radiomics datasets stay outside the path, and main.py substitutes synthetic patients when no image location is configured.
 """
 import os
@@ -95,6 +96,16 @@ class Parser:
             raise ConfigurationError('Data.mask_threshold {!r} is not a finite number'.format(data.get('mask_threshold')))
         return mode, threshold
 
+    def maskRoi(self):
+        """`Data: mask_roi`: the ROIName to take from a mask that is an RT Structure Set (exact, case-insensitive), or None (the default:
+        the file's only ROI).  The datasets resolve it against every patient's file when they are built."""
+        value = (self.config.get('Data') or {}).get('mask_roi')
+        if value is None:
+            return None
+        if not isinstance(value, str) or not value.strip():
+            raise ConfigurationError('Data.mask_roi {!r} is not a ROI name (a non-empty string)'.format(value))
+        return value.strip()
+
     def dataFormat(self):
         """`Data: format`: 'auto' (the default: the layout is detected per tree), 'nifti' or 'dicom'."""
         from ..data.ImageDatasets import FORMATS
@@ -130,7 +141,7 @@ class Parser:
                 cls = T1T2ImageDataset if both else NiftiImageDataset
             paths = image_path if both else (image_path,)
             datasets.append(cls(*paths, self._data('data_loc'), self._data('key_loc'), mask_resample=self.maskResample()[0],
-                                format=self.dataFormat()))
+                                format=self.dataFormat(), mask_roi=self.maskRoi()))
             self.image_layout = datasets[-1].layout
         if len(datasets) == 1:
             return datasets[0]
