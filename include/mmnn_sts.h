@@ -502,6 +502,31 @@ typedef struct {
 int mmnn_rasterize_contours(const mmnn_rasterize_desc* d, const double* points, const int32_t* contours, const int32_t* slice_first,
                             uint8_t* out, void* stream);
 
+/* ---- DICOM SEG frames -> a byte mask: the PixelData value of a BINARY Segmentation object (PS3.3 C.8.20, one bit per pixel, PS3.5 bit
+ * order) unpacked into one byte per voxel of an x * y * z grid (csrc/seg.hip).  `bits` holds the value as the file holds it: pixel
+ * p = j*x + i of frame f is bit number (int64)f*x*y + p of the stream, and bit b of the stream is bit b & 7 of byte b >> 3, counted from
+ * the least significant.  The frames follow each other WITHOUT byte alignment; the stream holds ceil(n_frames*x*y / 8) bytes, and the
+ * padding bits behind the last frame are never read as pixels.  `refs`: n_refs frame indices; `slice_first`: z + 1 entries, the frames
+ * of output slice k are refs[slice_first[k] .. slice_first[k + 1]) (the layout mmnn_rasterize_contours uses for its contours).  Voxel
+ * (i, j, k) of `out` is `one` if a frame f listed for slice k, with 0 <= f < n_frames, has its bit set, else 0: several frames on one
+ * slice are OR-ed, a frame may be listed for several slices, frames need no order, and frames that no slice lists (another segment's)
+ * are not read.  A frame index outside 0..n_frames-1 is ignored; so is a slice range that does not lie inside `refs` (not
+ * 0 <= first <= last <= n_refs), as a whole.  `out` holds x*y*z bytes, x fastest -- a mask of NIfTI type 2 for mmnn_ingest_volume
+ * (one = 1) or mmnn_resample_mask (one = 255) -- and every byte of it is written by the kernel (a slice without frames as zeros, no
+ * separate memset); nothing else is.  `bits` and `out` may have any byte alignment; the stream is read in aligned 32-bit words, so the
+ * 4-byte cells around its first and last byte are read whole.  One launch, no atomics on global memory, no host synchronisation:
+ * repeated calls are bit-identical.  n_refs == 0 is legal (an all-zero mask; bits and refs may then be null).  Refused (status 1)
+ * before any launch: a null descriptor, a non-positive extent, x*y*z >= 2^31, a negative n_frames or n_refs, `one` outside 1..255, a
+ * null slice_first / out, null bits / refs with n_refs > 0, refs / slice_first not aligned to 4 bytes, overlapping bits and out. */
+typedef struct {
+  int32_t x, y, z;                /* output grid: Columns, Rows, slices */
+  int32_t n_frames;               /* frames held by `bits` */
+  int32_t n_refs;                 /* entries of `refs` */
+  int32_t one;                    /* byte written for a set voxel, 1..255 */
+} mmnn_unpack_frames_desc;
+int mmnn_unpack_frames(const mmnn_unpack_frames_desc* d, const uint8_t* bits, const int32_t* refs, const int32_t* slice_first, uint8_t* out,
+                       void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

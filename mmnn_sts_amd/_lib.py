@@ -127,6 +127,11 @@ class RasterizeDesc(Structure):
     _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_contours", c_int32), ("n_points", c_int64)]
 
 
+class UnpackFramesDesc(Structure):
+    """mmnn_unpack_frames_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_frames", c_int32), ("n_refs", c_int32), ("one", c_int32)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -229,6 +234,8 @@ def lib():
     L.mmnn_decode_slices.argtypes = [POINTER(DecodeSlicesDesc), c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_rasterize_contours.restype = c_int32
     L.mmnn_rasterize_contours.argtypes = [POINTER(RasterizeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_unpack_frames.restype = c_int32
+    L.mmnn_unpack_frames.argtypes = [POINTER(UnpackFramesDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

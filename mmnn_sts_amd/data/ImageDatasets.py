@@ -9,8 +9,11 @@ detected per tree (`Data: format: auto | nifti | dicom` forces one; a tree that 
             single-frame series only (`mmnn_sts_amd.data.dicom`); the mask is a DICOM image series too, always resampled into the
             scan's grid and binarised at 128 by default -- or one RT Structure Set file (`mmnn_sts_amd.data.rtstruct`): `mask/` (or
             its single sub-directory) then holds no image file and exactly one RTSTRUCT file, whose ROI `mask_roi` (`Data: mask_roi`;
-            None: its only ROI) is rasterised onto the scan's own grid on the device and takes neither resample nor threshold.
-            DICOM SEG and a NIfTI mask beside a DICOM scan are outside the path
+            None: its only ROI) is rasterised onto the scan's own grid on the device and takes neither resample nor threshold --
+            or one DICOM Segmentation file (`mmnn_sts_amd.data.seg`, BINARY only), detected by its SOP class: the frames of the
+            segment `mask_roi` names by its SegmentLabel are unpacked on the device, straight onto the scan's grid when they lie
+            on its slice planes, else onto the segmentation's own grid and then resampled like a mask series.  A NIfTI mask beside a
+            DICOM scan, enhanced multi-frame scans, FRACTIONAL / LABELMAP SEG and compressed syntaxes are outside the path
 
 `patient_key` is a csv with the columns `Anon MRN` and `MRN` that maps the anonymised id to the uid.  Labels come from this project's
 clinical csv (`ClinicalDatasets.LabelTable`), joined on `uid`.  `ImageClassificationDataset` / `ImageSurvivalDataset` are upstream's
@@ -32,7 +35,7 @@ import os
 import torch
 
 from ..exceptions.exceptions import ConfigurationError
-from . import dicom, nifti, rtstruct
+from . import dicom, nifti, rtstruct, seg
 from .ClinicalDatasets import LabelTable
 from .ingest import MASK_RESAMPLE_MODES, RawPatient
 
@@ -62,8 +65,8 @@ def layout_of(patient_path):
     if is_dicom and is_nifti:
         raise ConfigurationError(f"{patient_path} holds both the DICOM layout (image/, mask/) and a NIfTI scan*: one format per tree")
     if os.path.isdir(os.path.join(patient_path, 'image')) and not is_dicom:
-        raise ConfigurationError(f"{patient_path}: image/ without a mask/ directory beside it (a NIfTI mask beside a DICOM scan and DICOM SEG "
-                                 "are outside the path; an RTSTRUCT file belongs into mask/)")
+        raise ConfigurationError(f"{patient_path}: image/ without a mask/ directory beside it (a NIfTI mask beside a DICOM scan is outside "
+                                 "the path; an RTSTRUCT or DICOM SEG file belongs into mask/)")
     return 'dicom' if is_dicom else ('nifti' if is_nifti else None)
 
 
@@ -98,6 +101,40 @@ def rtstruct_in(mask_directory):
     return found[0]
 
 
+def seg_in(mask_directory):
+    """The path of the DICOM Segmentation file when `mask_directory` (or its single sub-directory) holds exactly one and neither an
+    image file nor an RTSTRUCT file; None when it holds no SEG file.  Files are told apart by SOPClassUID alone (`seg.sop_class_of`):
+    a SEG file never reaches `dicom.read_file`, which refuses multi-frame objects.  Refused: several SEG files, a SEG file beside image
+    files or beside an RTSTRUCT file."""
+    try:
+        d = dicom.series_directory(mask_directory)
+    except ConfigurationError:
+        return None                          # (read_series reports what is wrong with the directory)
+    found, others = [], []
+    for name in sorted(os.listdir(d)):
+        p = os.path.join(d, name)
+        if name.startswith('.') or not os.path.isfile(p):
+            continue
+        try:
+            sop = seg.sop_class_of(p)
+        except dicom.NotDicomError:
+            continue
+        (found if sop == seg.SEGMENTATION_STORAGE else others).append((p, sop))
+    if not found:
+        return None
+    if len(found) > 1:
+        raise ConfigurationError(f"{d}: {len(found)} DICOM SEG files ({', '.join(os.path.basename(p) for p, _ in found[:4])}): one segmentation per mask/ is expected")
+    structure_sets = [p for p, sop in others if sop == rtstruct.RT_STRUCTURE_SET_STORAGE]
+    if structure_sets:
+        raise ConfigurationError(f"{d}: a DICOM SEG file ({os.path.basename(found[0][0])}) beside an RTSTRUCT file ({os.path.basename(structure_sets[0])}): "
+                                 "mask/ holds one image series, one structure set or one segmentation")
+    images = sum(1 for p, _ in others if dicom.read_file(p, header_only=True).has_image)
+    if images:
+        raise ConfigurationError(f"{d}: a DICOM SEG file ({os.path.basename(found[0][0])}) beside {images} DICOM image file(s): mask/ holds one "
+                                 "image series, one structure set or one segmentation")
+    return found[0][0]
+
+
 class ImageDataset(torch.utils.data.Dataset):
     format = 'auto'             # the layout a class is bound to; the constructor's `format` overrides it
 
@@ -110,6 +147,7 @@ class ImageDataset(torch.utils.data.Dataset):
         self.mask_resample = mask_resample
         self.mask_roi = mask_roi
         self._rtstruct = {}                  # mask directory -> the RTSTRUCT file in it, or None (an image series)
+        self._seg = {}                       # mask directory -> the DICOM SEG file in it, or None
         self.patient_directory = str(patient_directory)
         self.patients = sorted(x for x in os.listdir(self.patient_directory)
                                if not x.startswith('.') and os.path.isdir(os.path.join(self.patient_directory, x)))
@@ -151,7 +189,11 @@ class ImageDataset(torch.utils.data.Dataset):
 
     def _geometry(self, path):
         """(extents, affine or None) from the headers alone.  An RTSTRUCT mask has no grid of its own: (None, None), once its ROI
-        names have been read and `mask_roi` resolved against them (a bad name fails here, at construction)."""
+        names have been read and `mask_roi` resolved against them (a bad name fails here, at construction).  So has a SEG mask
+        until it is placed against its scan (`_check_grids`); its segment labels are resolved here as well."""
+        if self.layout == 'dicom' and self._seg_of(path):
+            seg.resolve(seg.read(self._seg_of(path), header_only=True), self.mask_roi)
+            return None, None
         if self.layout == 'dicom' and self._rtstruct_of(path):
             rtstruct.resolve(rtstruct.read(self._rtstruct_of(path), header_only=True), self.mask_roi)
             return None, None
@@ -162,11 +204,19 @@ class ImageDataset(torch.utils.data.Dataset):
 
     def _rtstruct_of(self, directory):
         """The RTSTRUCT file of a mask/ directory, or None; image/ directories always hold a series."""
-        if os.path.basename(directory) != 'mask':
+        if os.path.basename(directory) != 'mask' or self._seg_of(directory):
             return None
         if directory not in self._rtstruct:
             self._rtstruct[directory] = rtstruct_in(directory)
         return self._rtstruct[directory]
+
+    def _seg_of(self, directory):
+        """The DICOM SEG file of a mask/ directory, or None."""
+        if os.path.basename(directory) != 'mask':
+            return None
+        if directory not in self._seg:
+            self._seg[directory] = seg_in(directory)
+        return self._seg[directory]
 
     @property
     def uids(self):
@@ -195,6 +245,9 @@ class ImageDataset(torch.utils.data.Dataset):
     def _load(self, patient):
         scan_path, mask_path = self._files(patient)
         read = dicom.read_series if self.layout == 'dicom' else nifti.read
+        if self.layout == 'dicom' and self._seg_of(mask_path):
+            # the collate function places the frames against the scan and unpacks them on the device
+            return read(scan_path), seg.select(seg.read(self._seg_of(mask_path)), self.mask_roi)
         if self.layout == 'dicom' and self._rtstruct_of(mask_path):
             # the contours are born on the scan's grid: the collate function rasterises them there (no resample, no threshold)
             return read(scan_path), rtstruct.select(rtstruct.read(self._rtstruct_of(mask_path)), self.mask_roi)
@@ -204,8 +257,19 @@ class ImageDataset(torch.utils.data.Dataset):
 
     def _check_grids(self, patient, scan, mask):
         """scan, mask: (extents, affine or None, path).  True when the mask's extents differ from the scan's and can be resampled.
-        An RTSTRUCT mask (extents None) is on the scan's grid by construction; its scan needs a geometry to place the contours by."""
+        An RTSTRUCT mask (extents None) is on the scan's grid by construction; its scan needs a geometry to place the contours by.
+        A SEG mask (extents None as well) is placed here from its header: True when its frames form a grid of their own."""
         (sshape, saff, _), (mshape, maff, _) = scan, mask
+        if mshape is None and self._seg_of(mask[2]):
+            path = self._seg_of(mask[2])
+            if saff is None:
+                raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {scan[2]} has no position / orientation to place the "
+                                         f"frames of {path} by")
+            place = seg.to_scan(seg.select(seg.read(path, header_only=True), self.mask_roi), sshape, saff)
+            if not place.on_scan and self.mask_resample == 'never':
+                raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): scan extent {tuple(sshape)}, SEG extent {tuple(place.shape)}: "
+                                         f"{path} is on a grid of its own (Data.mask_resample is 'never')")
+            return not place.on_scan
         if mshape is None:
             if saff is None:
                 raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {scan[2]} has no position / orientation to place the "

@@ -15,8 +15,8 @@ must give the same device batch bit for bit.
 Accepted: implicit VR little endian (1.2.840.10008.1.2) and explicit VR little endian (1.2.840.10008.1.2.1), SamplesPerPixel 1, one
 frame per file, BitsAllocated 8 / 16 / 32.  Refused, with the file named: big endian, deflated, every encapsulated (compressed) syntax,
 multi-frame and enhanced objects, colour, float / double pixel data.  A mask may also be an RT Structure Set: that file is read by
-`rtstruct.py`, which shares this module's element decoding and descends into the sequences that `read_file` skips.  DICOM SEG stays
-outside the path.
+`rtstruct.py`, or a BINARY DICOM Segmentation object, read by `seg.py`; both share this module's element decoding and descend into the
+sequences that `read_file` skips.  `read_file` itself keeps refusing every multi-frame file.
 
 `read_series(directory)` sorts the slices by position along the normal of ImageOrientationPatient -- file names and InstanceNumber play
 no part -- and forms the affine in RAS, the convention of `NiftiImage.affine`, so `nifti.index_map`, `KeptVolume.affine` and the

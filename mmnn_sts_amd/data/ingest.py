@@ -7,6 +7,8 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     upload(volume, device)                          host volume (NiftiImage, DicomSeries or ndarray) -> DeviceVolume
     decode_series(series, device)                   a sorted DICOM series -> DeviceVolume: the slices' bytes decoded on device (mmnn_decode_slices)
     rasterize_contours(contours, scan, device)      the contours of an RTSTRUCT ROI -> uint8 0 / 1 on the scan's grid (mmnn_rasterize_contours)
+    unpack_frames(frames, scan, device)             the frames of a DICOM SEG segment -> uint8 0 / 1 on the scan's grid, or 0 / 255 on the
+                                                    segmentation's own (mmnn_unpack_frames)
     resample_mask(mask, scan_shape, index_map)      a mask drawn on another grid -> uint8 bytes on the scan's grid (mmnn_resample_mask)
     ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
     collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
@@ -26,6 +28,12 @@ per slice.  A DICOM (scan, mask) pair always passes through `resample_mask` -- u
 A mask that is an RT Structure Set (`rtstruct.read` -> `ContourSet`) beside a DICOM scan is born on the scan's grid: the host maps the
 contour points into the scan's voxel index space (`rtstruct.to_scan_index`), `mmnn_rasterize_contours` fills them by the even-odd rule
 into 0 / 1 bytes, and the pair takes the voxelwise path -- no resample, no threshold.
+
+A mask that is a DICOM Segmentation object (`seg.read` -> `FrameSet`) beside a DICOM scan: the host places the frames of the selected
+segment against the scan (`seg.to_scan`) and `mmnn_unpack_frames` unpacks the bit-packed PixelData, uploaded as the file holds it.
+Frames on the scan's slice planes are written as 0 / 1 straight onto the scan's grid and take the voxelwise path like an RTSTRUCT
+mask; a segmentation on a grid of its own is unpacked as 0 / 255 onto its own stack and then takes the path of a DICOM mask series
+(`resample_mask` by `nifti.index_map`, binarised at `mask_threshold` or 128).
 """
 import ctypes
 from dataclasses import dataclass
@@ -36,10 +44,11 @@ import torch
 
 from .. import _lib
 from ..exceptions.exceptions import ConfigurationError
-from . import nifti, rtstruct
+from . import nifti, rtstruct, seg
 from .dicom import DicomSeries
 from .nifti import NiftiImage
 from .rtstruct import ContourSet
+from .seg import FrameSet
 
 SIZE = 64                                    # MMNN_INGEST_SIZE
 MASK_RESAMPLE_MODES = ("auto", "geometry", "never")
@@ -76,7 +85,7 @@ class KeptVolume:
 @dataclass
 class RawPatient:
     """What an image dataset's `__getitem__` yields in place of a float volume: per modality the (scan, mask) pair, still raw (two
-    NiftiImages, two DicomSeries, or a DicomSeries and the ContourSet of its RTSTRUCT mask)."""
+    NiftiImages, two DicomSeries, or a DicomSeries and the ContourSet of its RTSTRUCT mask or the FrameSet of its SEG mask)."""
     uid: int
     volumes: List[Tuple[object, object]]
 
@@ -97,6 +106,8 @@ def upload(volume, device, slope: float = 1.0, inter: float = 0.0) -> DeviceVolu
         return volume
     if isinstance(volume, DicomSeries):
         return decode_series(volume, device)
+    if isinstance(volume, FrameSet):
+        raise ValueError(f"ingest: a SEG mask ({volume.path}) is placed against its scan: upload it with stage_frames(frames, scan, device)")
     affine = None
     if isinstance(volume, NiftiImage):
         raw, slope, inter, affine = volume.raw, volume.slope, volume.inter, volume.affine
@@ -207,6 +218,79 @@ def rasterize_contours(contours, scan, device=None, roi=None, out: Optional[torc
     return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, getattr(scan, "affine", None))
 
 
+@dataclass
+class StagedFrames:
+    """The bit stream of a SEG file and the two arrays of `seg.to_scan` in one device buffer: a SEG mask between its upload and its
+    unpacking.  `shape`, `affine`: the grid it is unpacked onto -- the scan's (`on_scan`) or the segmentation's own."""
+    staged: torch.Tensor
+    at_slices: int                           # byte offsets of slice_first and of the bit stream behind refs
+    at_bits: int
+    n_frames: int
+    n_refs: int
+    shape: Tuple[int, int, int]
+    affine: Optional[np.ndarray]
+    one: int
+    on_scan: bool
+    path: str = ""
+    from_dicom: bool = True
+
+
+def stage_frames(frames, scan, device, roi=None) -> StagedFrames:
+    """Upload a SEG mask for `scan` (anything with `.shape` and `.affine`): one pinned staging buffer (refs, slice_first, then the
+    PixelData bytes as the file holds them) and one non-blocking copy.  `frames`: a FrameSet (`roi` names the segment to take; None:
+    its only one), placed by `seg.to_scan`, or the arrays themselves, (bits, n_frames, refs, slice_first[, one]), for the scan's grid."""
+    if isinstance(frames, FrameSet):
+        if not is_dicom(scan):
+            raise ConfigurationError(f"a DICOM SEG mask ({frames.path}) beside a NIfTI scan is outside the path: both come from one format")
+        if frames.header_only or frames.frame is None:
+            raise ValueError(f"unpack_frames: {frames.path} was read with header_only: it holds no PixelData")
+        place = seg.to_scan(seg.select(frames, roi), scan.shape, scan.affine)
+        bits, n_frames, refs, slice_first, one = frames.frame, frames.n_frames, place.refs, place.slice_first, place.one
+        shape, affine, on_scan, path = place.shape, place.affine, place.on_scan, frames.path
+    else:
+        bits, n_frames, refs, slice_first, *rest = frames
+        one, shape, affine, on_scan, path = (int(rest[0]) if rest else 1), tuple(int(v) for v in scan.shape), getattr(scan, "affine", None), True, ""
+    bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+    refs, slice_first = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (refs, slice_first))
+    need = (int(n_frames) * shape[0] * shape[1] + 7) // 8
+    if slice_first.size != shape[2] + 1 or bits.size < need:
+        raise ValueError(f"unpack_frames: slice_first of {shape[2] + 1} entries and {need} bytes of frames expected, got {slice_first.size} and {bits.size}")
+    at_slices = refs.nbytes
+    at_bits = at_slices + slice_first.nbytes
+    stage = torch.empty(at_bits + need, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    host[:at_slices] = refs.view(np.uint8)
+    host[at_slices:at_bits] = slice_first.view(np.uint8)
+    host[at_bits:] = bits[:need]
+    return StagedFrames(stage.to(torch.device(device), non_blocking=True), at_slices, at_bits, int(n_frames), int(refs.size), tuple(shape), affine,
+                        int(one), bool(on_scan), path)
+
+
+def unpack_frames(frames, scan, device=None, roi=None, out: Optional[torch.Tensor] = None) -> DeviceVolume:
+    """The frames of one SEG segment -> a uint8 mask (`mmnn_unpack_frames`): 0 / 1 on the grid of `scan` (anything with `.shape` and
+    `.affine`) when they lie on it, else 0 / 255 on the segmentation's own stack, marked `from_dicom` so that it is resampled and
+    binarised like a DICOM mask series.  `frames`: what `stage_frames` takes, or its result.  One pinned staging buffer, one
+    non-blocking copy and one launch on the current stream.  `device`: None is `out`'s, else the current one.  `out`: a contiguous
+    uint8 CUDA tensor of the grid's x*y*z elements to write, allocated when None."""
+    if not isinstance(frames, StagedFrames):
+        if device is None:
+            device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+        frames = stage_frames(frames, scan, device, roi)
+    dev = frames.staged.device
+    x, y, z = frames.shape
+    if out is None:
+        out = torch.empty(x * y * z, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x * y * z):
+        raise ValueError(f"unpack_frames: out must be {x * y * z} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    desc = _lib.UnpackFramesDesc(x, y, z, frames.n_frames, frames.n_refs, frames.one)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        p = frames.staged.data_ptr()
+        _lib.check(_lib.lib().mmnn_unpack_frames(ctypes.byref(desc), p + frames.at_bits, p, p + frames.at_slices, out.data_ptr(), stream),
+                   "mmnn_unpack_frames")
+    return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, frames.affine, from_dicom=not frames.on_scan)
+
+
 def workspace_bytes(x: int, y: int, z: int) -> int:
     n = _lib.lib().mmnn_ingest_workspace_bytes(int(x), int(y), int(z))
     if n < 0:
@@ -260,6 +344,19 @@ def mask_index_map(scan, mask, mode: str = "auto"):
         if not is_dicom(scan):
             raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
         return None
+    if isinstance(mask, FrameSet):
+        if not is_dicom(scan):
+            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
+        mask = seg.to_scan(mask, scan.shape, scan.affine)
+    if isinstance(mask, (StagedFrames, seg.Placement)):
+        if not is_dicom(scan):
+            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
+        if mask.on_scan:                     # unpacked onto the scan's own grid: nothing to resample
+            return None
+        if mode == "never":
+            raise ConfigurationError(f"scan extent {tuple(scan.shape)} ({getattr(scan, 'path', '') or 'scan'}), SEG extent {tuple(mask.shape)} "
+                                     f"({mask.path or 'mask'}): the segmentation is on a grid of its own and mask_resample is 'never'")
+        return nifti.index_map(scan, mask)
     same = tuple(scan.shape) == tuple(mask.shape)
     if is_dicom(scan) or is_dicom(mask):
         return _dicom_index_map(scan, mask, mode, same)
@@ -308,13 +405,22 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     `threshold`); without `index_map` the map comes from the two volumes' affines, and differing extents without them are refused.
     Equal extents without `index_map` are the voxelwise path -- except for a DICOM pair, which is always resampled.  `threshold`
     None: 0.5, or 128 behind a DICOM scan.  A `mask` that is a ContourSet (or `stage_contours`' result) beside a DICOM scan is
-    rasterised onto the scan's grid first (`rasterize_contours`) and takes the voxelwise path: no resample, no threshold."""
+    rasterised onto the scan's grid first (`rasterize_contours`) and takes the voxelwise path: no resample, no threshold.  A `mask`
+    that is a FrameSet (or `stage_frames`' result) beside a DICOM scan is unpacked first (`unpack_frames`): onto the scan's grid, and
+    then voxelwise like a contour mask, or onto a grid of its own, and then resampled and binarised like a DICOM mask series."""
     if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and tuple(out_plane.shape) == (SIZE,) * 3):
         raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, got {tuple(out_plane.shape)} {out_plane.dtype} on {out_plane.device}")
     dev = out_plane.device
     scan = upload(scan, dev)
     drawn = isinstance(mask, (ContourSet, StagedContours))
-    if drawn:
+    if isinstance(mask, (FrameSet, StagedFrames)):
+        if not is_dicom(scan):
+            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
+        mask = unpack_frames(mask, scan, dev)
+        drawn = not mask.from_dicom          # on the scan's grid: the voxelwise path; on its own: a DICOM mask volume like a series'
+        if drawn and index_map is not None:
+            raise ValueError("ingest: a SEG mask on the scan's own grid takes no index_map")
+    elif drawn:
         if index_map is not None:
             raise ValueError("ingest: a contour mask is rasterised onto the scan's own grid; it takes no index_map")
         if not is_dicom(scan):
@@ -400,6 +506,14 @@ def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor,
     return out
 
 
+def _upload_mask(scan, mask, device):
+    if isinstance(mask, ContourSet):
+        return stage_contours(mask, scan, device)
+    if isinstance(mask, FrameSet):
+        return stage_frames(mask, scan, device)
+    return upload(mask, device)
+
+
 def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
                     mask_threshold: Optional[float] = None, keep_workspaces: bool = False):
     """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
@@ -407,13 +521,14 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`
     (None: 0.5; 128 for a DICOM pair, which is always resampled).  A ContourSet as the mask of a DICOM scan (an RTSTRUCT file) is
     placed on that scan's grid by the host, uploaded with the others and rasterised there; it takes neither resample nor threshold.
+    A FrameSet (a DICOM SEG file) is placed by the host, uploaded with the others and unpacked on the device (see `unpack_frames`).
     With `keep_workspaces` every volume is ingested with a workspace of its own and a third value is returned: volumes[n][c], the
     `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan."""
     n, c = len(patients), len(patients[0])
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
     device = torch.device(device)
-    up = [[(upload(s, device), stage_contours(m, s, device) if isinstance(m, ContourSet) else upload(m, device)) for s, m in p] for p in patients]
+    up = [[(upload(s, device), _upload_mask(s, m, device)) for s, m in p] for p in patients]
     maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     batch = torch.empty((n, c, SIZE, SIZE, SIZE), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)

@@ -13,7 +13,7 @@ skips and this walk descends into:
 in explicit or implicit VR little endian, with sequences and items of defined or undefined length; in implicit VR the sequences to enter
 are recognised by tag.  ContourData is a DS string of x\\y\\z triplets in patient millimetres, LPS.  Only CLOSED_PLANAR contours are kept;
 the others are counted.  The refusals of `dicom.py` hold: compressed, big endian and deflated syntaxes, truncated elements, nesting
-beyond `MAX_DEPTH`.  DICOM SEG is another object and stays outside the path.
+beyond `MAX_DEPTH`.  DICOM SEG is another object: `read` refuses it; `seg.py` reads it.
 
     read(path, header_only=False)                 -> ContourSet: ROI names in file order and, per ROI, its (n, 3) float64 contours
     select(contour_set, roi)                      -> the ContourSet of one ROI (name match exact, case-insensitive; None: the only one)

@@ -5,9 +5,10 @@
     <root>/images/t1/SYN-0007-t1-a/image/series_1/0003.dcm ...     one file per slice, names in a seeded random order
     <root>/images/t1/SYN-0007-t1-a/mask/series_1/0011.dcm ...      the mask as an 8-bit image series, 0 / 255
     <root>/images/t1/SYN-0007-t1-a/mask/rtstruct.dcm               with mask_format="rtstruct": the mask as one RT Structure Set file
+    <root>/images/t1/SYN-0007-t1-a/mask/seg.dcm                    with mask_format="seg": the mask as one BINARY Segmentation object
     <root>/key.csv, clinical.csv, train_uids.txt, val_uids.txt     copied from the NIfTI tree
 
-    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct]
+    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct | seg]
 
 The twin holds the same voxels -- slice k, row j, column i is the NIfTI voxel (i, j, k) -- and the same geometry: ImagePositionPatient,
 ImageOrientationPatient and PixelSpacing are the NIfTI affine's columns in LPS (a sheared or left-handed affine has no such form and is
@@ -27,7 +28,8 @@ from .dicom import EXPLICIT_LE, IMPLICIT_LE, LONG_VRS
 
 MR_IMAGE_STORAGE = "1.2.840.10008.5.1.4.1.1.4"
 RT_STRUCTURE_SET_STORAGE = "1.2.840.10008.5.1.4.1.1.481.3"
-MASK_FORMATS = ("series", "rtstruct")
+SEGMENTATION_STORAGE = "1.2.840.10008.5.1.4.1.1.66.4"
+MASK_FORMATS = ("series", "rtstruct", "seg")
 UID_ROOT = "1.2.3.4.5"                       # not a registered root: synthetic files only
 
 
@@ -245,13 +247,97 @@ def write_rtstruct(path, mask, affine, roi_name="GTV", extra_rois=(), explicit=T
     return str(path)
 
 
+def seg_bytes(rows, columns, segments, frames, pixel_data, orientation=None, pixel_spacing=None, step=None, explicit=True,
+              undefined_lengths=False, per_frame_orientation=False, segmentation_type="BINARY", bits_allocated=1,
+              sop_class=SEGMENTATION_STORAGE, number_of_frames=None, sop_instance_uid=UID_ROOT + ".7.1") -> bytes:
+    """A Segmentation object as a part-10 file.  `segments`: [(SegmentNumber, SegmentLabel), ...]; `frames`: [(ReferencedSegmentNumber,
+    ImagePositionPatient), ...] in the order of the frames in `pixel_data`, the PixelData value (bit-packed by the caller).
+    `orientation` (6), `pixel_spacing` (2) and `step` (SliceThickness and SpacingBetweenSlices) go into the shared functional group,
+    or, with `per_frame_orientation`, into every per-frame item; None leaves them out.  `number_of_frames`: the NumberOfFrames to
+    declare in place of len(frames)."""
+    el = lambda g, e, vr, v: _element(g, e, vr, v, explicit)
+    seq = lambda g, e, items: _sequence(g, e, items, explicit, undefined_lengths)
+    us = lambda v: struct.pack("<H", v)
+    syntax = EXPLICIT_LE if explicit else IMPLICIT_LE
+    meta = b"".join([_element(0x0002, 0x0001, "OB", b"\0\1", True), _element(0x0002, 0x0002, "UI", _text(sop_class), True),
+                     _element(0x0002, 0x0003, "UI", _text(sop_instance_uid), True), _element(0x0002, 0x0010, "UI", _text(syntax), True),
+                     _element(0x0002, 0x0012, "UI", _text(UID_ROOT + ".0"), True)])
+    meta = _element(0x0002, 0x0000, "UL", struct.pack("<I", len(meta)), True) + meta
+    measures = b""
+    if step is not None:
+        measures += el(0x0018, 0x0050, "DS", _text(ds(step))) + el(0x0018, 0x0088, "DS", _text(ds(step)))
+    if pixel_spacing is not None:
+        measures += el(0x0028, 0x0030, "DS", _text([ds(v) for v in pixel_spacing]))
+    placed = b""                             # the functional groups that sit in the shared item or in every per-frame item, in tag order
+    if orientation is not None:
+        placed += seq(0x0020, 0x9116, [el(0x0020, 0x0037, "DS", _text([ds(v) for v in orientation]))])
+    if measures:
+        placed += seq(0x0028, 0x9110, [measures])
+    per_frame = []
+    for number, position in frames:
+        item = seq(0x0020, 0x9113, [el(0x0020, 0x0032, "DS", _text([ds(v) for v in position]))])
+        if per_frame_orientation:
+            item += placed
+        per_frame.append(item + seq(0x0062, 0x000A, [el(0x0062, 0x000B, "US", us(int(number)))]))
+    described = [el(0x0062, 0x0004, "US", us(int(number))) + el(0x0062, 0x0005, "LO", _text(label)) + el(0x0062, 0x0008, "CS", b"MANUAL")
+                 for number, label in segments]
+    e = [el(0x0008, 0x0016, "UI", _text(sop_class)), el(0x0008, 0x0018, "UI", _text(sop_instance_uid)), el(0x0008, 0x0060, "CS", b"SEG"),
+         el(0x0028, 0x0002, "US", us(1)), el(0x0028, 0x0004, "CS", b"MONOCHROME2"),
+         el(0x0028, 0x0008, "IS", _text(str(len(frames) if number_of_frames is None else int(number_of_frames)))),
+         el(0x0028, 0x0010, "US", us(rows)), el(0x0028, 0x0011, "US", us(columns)), el(0x0028, 0x0100, "US", us(bits_allocated)),
+         el(0x0028, 0x0101, "US", us(bits_allocated)), el(0x0028, 0x0102, "US", us(bits_allocated - 1)), el(0x0028, 0x0103, "US", us(0)),
+         el(0x0062, 0x0001, "CS", _text(segmentation_type)), seq(0x0062, 0x0002, described),
+         seq(0x5200, 0x9229, [b"" if per_frame_orientation else placed]), seq(0x5200, 0x9230, per_frame),
+         el(0x7FE0, 0x0010, "OB", bytes(pixel_data))]
+    return b"\0" * 128 + b"DICM" + meta + b"".join(e)
+
+
+def write_seg(path, mask, affine, label="GTV", extra_segments=(), explicit=True, undefined_lengths=False, shuffle_frames=True,
+              per_frame_orientation=False, seed=0):
+    """Write the binary (x, y, z) `mask`, on the grid of the RAS `affine`, as a BINARY Segmentation object whose segment `label` holds
+    one frame per NON-EMPTY slice.  `extra_segments`: further segments -- a label (a decoy: the whole first slice) or a (label, mask)
+    pair -- numbered in front of and behind it alternately, their frames interleaved with its own.  The frames are written in a
+    seeded random order (`shuffle_frames`) and bit-packed back to back, least significant bit first, without byte alignment; the
+    value is padded to even length, and the pad bits behind the last frame and the pad byte hold seeded garbage."""
+    mask = np.asarray(mask) != 0
+    if mask.ndim != 3:
+        raise ConfigurationError(f"a mask has three axes, got {mask.shape}")
+    x, y, z = mask.shape
+    orientation, spacing, first, step = lps_geometry(affine, str(path))
+    segments = [(label, mask)]
+    for n, extra in enumerate(extra_segments):
+        if isinstance(extra, str):
+            decoy = np.zeros(mask.shape, dtype=bool)
+            decoy[:, :, 0] = True
+            extra = (extra, decoy)
+        segment = (extra[0], np.asarray(extra[1]) != 0)
+        segments = [segment] + segments if n % 2 == 0 else segments + [segment]
+    frames = [(number, k) for number, (_, m) in enumerate(segments, 1) for k in range(z) if m[:, :, k].any()]
+    rng = np.random.default_rng([int(seed), 11])
+    if shuffle_frames:
+        frames = [frames[i] for i in rng.permutation(len(frames))]
+    bits = np.concatenate([segments[number - 1][1][:, :, k].T.reshape(-1) for number, k in frames]) if frames else np.zeros(0, dtype=bool)
+    pad = -bits.size % 8
+    packed = np.packbits(np.concatenate([bits, rng.integers(0, 2, pad).astype(bool)]), bitorder="little")
+    if packed.size % 2:
+        packed = np.concatenate([packed, rng.integers(0, 256, 1).astype(np.uint8)])
+    data = seg_bytes(y, x, [(number, name) for number, (name, _) in enumerate(segments, 1)], [(number, first + k * step) for number, k in frames],
+                     packed.tobytes(), orientation, spacing, float(np.linalg.norm(step)), explicit, undefined_lengths, per_frame_orientation)
+    os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(data)
+    return str(path)
+
+
 def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, seed=0, bits_stored=None, per_slice_scale=False,
                     mask_format="series", roi_name="GTV", extra_rois=()):
     """The DICOM twin of a `synth_nifti.write_tree` tree; returns the same dictionary of locations.  Scans keep their type, slope and
     inter (as RescaleSlope / RescaleIntercept); non-zero mask voxels become `mask_value` (None: the mask's values are kept) in an 8-bit
     unsigned series.  `bits_stored`, `per_slice_scale`: of the scans (see `write_series`).  `mask_format` 'rtstruct': the mask directory
     holds one RT Structure Set file instead (`write_rtstruct` of the non-zero mask voxels on the scan's geometry, ROI `roi_name`,
-    with `extra_rois`); the mask must then share the scan's extents."""
+    with `extra_rois`); the mask must then share the scan's extents.  `mask_format` 'seg': one BINARY Segmentation object
+    instead (`write_seg` of the non-zero mask voxels, segment `roi_name`, with `extra_rois` as further segments), written on the
+    mask's own grid when that is another than its scan's."""
     if mask_format not in MASK_FORMATS:
         raise ConfigurationError(f"mask_format {mask_format!r} is none of {MASK_FORMATS}")
     nifti_root, dicom_root = str(nifti_root), str(dicom_root)
@@ -285,6 +371,10 @@ def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, 
                     raise ConfigurationError(f"{d}: an RTSTRUCT twin is drawn on the scan's grid; the mask's extents {mask.raw.shape} differ from {scan.raw.shape}")
                 write_rtstruct(os.path.join(target, "mask", "rtstruct.dcm"), mask.raw, scan.affine, roi_name, extra_rois)
                 continue
+            if mask_format == "seg":
+                write_seg(os.path.join(target, "mask", "seg.dcm"), mask.raw, mask.affine, roi_name, extra_rois, shuffle_frames=shuffle_names,
+                          seed=seed + 2 * count + 1)
+                continue
             m = mask.raw if mask_value is None else np.where(mask.raw != 0, mask_value, 0)
             write_series(os.path.join(target, "mask", "series_1"), m.astype(np.uint8), mask.affine, None, None, f"{UID_ROOT}.{count}.2",
                          shuffle_names, seed + 2 * count + 1)
@@ -298,7 +388,7 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--bits_stored", type=int, default=None)
     ap.add_argument("--per_slice_scale", action="store_true")
-    ap.add_argument("--mask_format", choices=MASK_FORMATS, default="series", help="the masks as 8-bit image series or as RT Structure Set files")
+    ap.add_argument("--mask_format", choices=MASK_FORMATS, default="series", help="the masks as 8-bit image series, as RT Structure Set files or as BINARY Segmentation objects")
     a = ap.parse_args()
     for k, v in from_nifti_tree(a.nifti_dir, a.dicom_dir, seed=a.seed, bits_stored=a.bits_stored, per_slice_scale=a.per_slice_scale,
                                 mask_format=a.mask_format).items():

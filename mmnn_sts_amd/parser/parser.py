@@ -8,7 +8,8 @@ integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  `getImagePat
 command-line flags override it; `format: auto | nifti | dicom` names the patient directories' layout, detected per tree by default;
 `mask_resample`, `mask_threshold` say what happens to a mask drawn on another grid than its scan's -- a DICOM mask is always resampled,
 and binarised at 128 unless `mask_threshold` is set; `mask_roi` names the region of interest to take from an RTSTRUCT mask, which is
-rasterised onto its scan's grid and takes neither resample nor threshold).  DICOM means uncompressed single-frame series (`mmnn_sts_amd.data.dicom`); S3 and
+rasterised onto its scan's grid and takes neither resample nor threshold, or the segment to take, by its SegmentLabel, from a DICOM SEG
+mask, which is unpacked onto its scan's grid when its frames lie on it and else resampled like a mask series).  DICOM means uncompressed single-frame series (`mmnn_sts_amd.data.dicom`); S3 and
 radiomics datasets stay outside the path, and main.py substitutes synthetic patients when no image location is configured.
 """
 import os
@@ -97,8 +98,8 @@ class Parser:
         return mode, threshold
 
     def maskRoi(self):
-        """`Data: mask_roi`: the ROIName to take from a mask that is an RT Structure Set (exact, case-insensitive), or None (the default:
-        the file's only ROI).  The datasets resolve it against every patient's file when they are built."""
+        """`Data: mask_roi`: the ROIName to take from a mask that is an RT Structure Set, or the SegmentLabel to take from one that is a
+        DICOM SEG file (exact, case-insensitive), or None (the default: the file's only ROI / segment).  The datasets resolve it against every patient's file when they are built."""
         value = (self.config.get('Data') or {}).get('mask_roi')
         if value is None:
             return None
