@@ -527,6 +527,45 @@ typedef struct {
 int mmnn_unpack_frames(const mmnn_unpack_frames_desc* d, const uint8_t* bits, const int32_t* refs, const int32_t* slice_first, uint8_t* out,
                        void* stream);
 
+/* ---- occlusion sensitivity: blank a box of the input, run the model, record how far each output moved; slide the box over the volume
+ * and average the moves over the boxes that cover a voxel (csrc/occlusion.hip).  The library builds the occluded batches and assembles
+ * the map; the forwards in between are the caller's.
+ *   window grid    along an axis of length L with window w and stride s, 1 <= s <= w <= L: n = ceil((L - w) / s) + 1 windows, window i
+ *                  starts at o_i = min(i * s, L - w).  The last window is clamped to the edge, so every voxel is covered by at least one
+ *                  window, and the windows that cover a voxel form a contiguous index range lo..hi.  Windows are numbered d-major:
+ *                  index = (a * n_h + b) * n_w + c; Wn = n_d * n_h * n_w.  s > w would leave holes and is refused.
+ * mmnn_occlusion_window_count returns Wn and fills the per-axis counts n_out[3] (d, h, w order; may be null); -1 on a bad descriptor.
+ * Needs no GPU.
+ * mmnn_occlude_windows: x is (c, d, h, w) fp32, `fill` c floats on the device, out (count, c, d, h, w).  Sample b is a copy of x in
+ * which every voxel inside window min(first + b, Wn - 1) is replaced by fill[channel], in all channels; values are copied as bit patterns
+ * (NaN payloads and -0.0 survive).  The clamp pads a last short batch with repeats of the last window, so the shape the model sees never
+ * changes.  Every element of `out` is written and nothing else is.  One launch, no atomics, no host synchronisation.  16-byte loads and
+ * stores when w % 4 == 0 and x and out are aligned to 16 bytes, dwords otherwise.
+ * mmnn_occlusion_map: `base` is k floats (the model's outputs on the unoccluded input), `scores` (Wn, k), out (k, d, h, w).  For class j
+ * and voxel v, out = (float)( sum((double)base[j] - (double)scores[win][j]) / count ) over the `count` windows that cover v, added in
+ * fp64 in ascending (a, b, c) order starting from 0.0, divided in fp64 and rounded to fp32 once: positive where hiding the voxel
+ * lowers the output.  One launch, no atomics: repeated calls are bit-identical, and (the library is built without FMA contraction) equal
+ * the same statement in numpy.
+ * mmnn_channel_means: x is (c, n) fp32, out c floats: each channel's mean, summed in fp64 in a fixed order that depends on n only (two
+ * stages: MMNN_CHANNEL_MEANS_PARTS partial sums per channel in `ws`, then their sum), divided by n in fp64 and rounded once.  No atomics:
+ * repeated calls are bit-identical.  ws: c * MMNN_CHANNEL_MEANS_PARTS doubles of device scratch.
+ * Refused (status 1; the count returns -1) before any launch, with mmnn_last_error() naming the field: a null pointer or descriptor, a
+ * non-positive extent, c*d*h*w*count >= 2^31 (for the map d*h*w*k and Wn*k), win outside 1..L, stride outside 1..win, first outside
+ * 0..Wn-1, count < 1, k outside 1..MMNN_OCCLUSION_MAX_OUTPUTS, a float pointer not aligned to 4 bytes or a workspace not aligned to 8,
+ * x and out overlapping (for the map: out overlapping scores or base). */
+#define MMNN_OCCLUSION_MAX_OUTPUTS 16
+#define MMNN_CHANNEL_MEANS_PARTS 64
+typedef struct {
+  int32_t c, d, h, w;             /* the model's input, one sample */
+  int32_t win[3];                 /* window per axis, d, h, w order: 1..extent */
+  int32_t stride[3];              /* stride per axis, d, h, w order: 1..win */
+} mmnn_occlusion_desc;
+int64_t mmnn_occlusion_window_count(const mmnn_occlusion_desc* d, int32_t n_out[3]);
+int mmnn_occlude_windows(const mmnn_occlusion_desc* d, const float* x, const float* fill, int32_t first, int32_t count, float* out,
+                         void* stream);
+int mmnn_occlusion_map(const mmnn_occlusion_desc* d, int32_t k, const float* base, const float* scores, float* out, void* stream);
+int mmnn_channel_means(const float* x, int32_t c, int64_t n, float* out, void* ws, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

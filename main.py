@@ -19,7 +19,9 @@ patient directories, NIfTI files or uncompressed single-frame DICOM series (`pat
 the layout is detected per tree, `Data: format` forces one) -- the files' raw voxels are masked, cropped of empty slices and resized to
 64^3 on the device, DICOM slices are decoded there first (mmnn_sts_amd/data/ingest.py, dicom.py); compressed or multi-frame DICOM and S3
 stay outside the path.  `--inference --image_loc DIR --scan_space` also writes every class's
-attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).  Without an image location synthetic patients are used; the tabular-only
+attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).
+`--inference --images --occlusion` writes occlusion sensitivity maps (patient{i}_occ_map.npy: (K, D, H, W) signed deltas at the resolution of
+`--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -41,7 +43,7 @@ from mmnn_sts_amd.losses.GradientBlender import GradientBlender  # noqa: E402
 from mmnn_sts_amd.losses.losses import BCEWithLogitsLoss, CoxPH  # noqa: E402
 from mmnn_sts_amd.optim import FusedSGD  # noqa: E402
 from mmnn_sts_amd.parser.parser import Parser  # noqa: E402
-from mmnn_sts_amd.utils.utils import add_gradcam, criterion, loadWeights, surv_criterion  # noqa: E402
+from mmnn_sts_amd.utils.utils import add_gradcam, add_occlusion, criterion, loadWeights, surv_criterion  # noqa: E402
 
 logging.basicConfig(level=logging.INFO, format="%(message)s")
 logger = logging.getLogger("mmnn_sts_amd")
@@ -256,9 +258,20 @@ def export_patient_nifti(args, uid, image, att, preds):
         f.write("".join(f"{float(v)!r}\n" for v in preds.reshape(-1)))
 
 
-def export_scan_space_maps(args, uid, maps, volumes):
+def export_occlusion_nifti(args, uid, maps):
+    """`--occlusion --image_loc`: occ_map_class{k}.nii.gz per output in upstream's per-patient folder, beside att_map.nii.gz."""
+    from mmnn_sts_amd.data import nifti
+    d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
+    os.makedirs(d, exist_ok=True)
+    maps = maps.cpu().numpy().astype(np.float32)
+    for k in range(maps.shape[0]):
+        nifti.write(os.path.join(d, f"occ_map_class{k}.nii.gz"), maps[k])
+
+
+def export_scan_space_maps(args, uid, maps, volumes, prefix="att_map"):
     """`--scan_space`: every class's attention map on the voxel grid of every scan of the patient, into the patient's folder as
-    att_map_class{k}_on_{t1,t2}.nii.gz (att_map_class{k}_on_scan.nii.gz for a single modality), written with the scan's affine so that a
+    att_map_class{k}_on_{t1,t2}.nii.gz (att_map_class{k}_on_scan.nii.gz for a single modality; `prefix` replaces "att_map": the
+    occlusion maps are written as occ_map_class{k}_on_*), written with the scan's affine so that a
     viewer lays it over the scan.  `maps`: (classes, 64, 64, 64) on the device, in the model's space; `volumes`: the patient's
     `KeptVolume` per modality.  The ingest's own kept slices are inverted on the device (`maps_to_scan`); dropped slices are 0."""
     from mmnn_sts_amd.data import nifti
@@ -269,7 +282,7 @@ def export_scan_space_maps(args, uid, maps, volumes):
     for name, vol in zip(names, volumes):
         on_scan = maps_to_scan(maps, vol.shape, vol.workspace).cpu().numpy()           # (classes, z, y, x)
         for k in range(on_scan.shape[0]):
-            nifti.write(os.path.join(d, f"att_map_class{k}_on_{name}.nii.gz"), on_scan[k].transpose(2, 1, 0), affine=vol.affine)
+            nifti.write(os.path.join(d, f"{prefix}_class{k}_on_{name}.nii.gz"), on_scan[k].transpose(2, 1, 0), affine=vol.affine)
 
 
 def apply_transforms(x, tf):
@@ -450,6 +463,10 @@ def inference_survival(model, ds, args, device):
     if args.bootstrap:
         args.no_gradcam = True                       # main.py:774-777: no attention maps, no prediction dump while bootstrapping
     cam = add_gradcam(model, multimodal=args.multimodal) if (args.images and not args.no_gradcam) else None
+    occ = None
+    if getattr(args, "occlusion", False):
+        occ = add_occlusion(model, multimodal=args.multimodal, window=args.occlusion_window, stride=args.occlusion_stride,
+                            batch=args.occlusion_batch)
     preds, evs, dus = [], [], []
     os.makedirs(os.path.join(args.output_path, "attention_maps"), exist_ok=True)
     for i in range(len(ds)):
@@ -470,8 +487,18 @@ def inference_survival(model, ds, args, device):
                     # sample's one map, class 0
                     stack = torch.stack(list(maps)) if args.multimodal else maps[0]
                     export_scan_space_maps(args, ds.uids[i], stack.contiguous(), args.ingest_collate.last_volumes[0])
-            else:
+            elif occ is None:
                 p = model(x)
+            if occ is not None:
+                # the occluded inputs are built from what the model sees: the batch after the validation transforms
+                outs, occ_maps = occ(x)
+                if cam is None:
+                    p = outs
+                np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_occ_map.npy"), occ_maps.cpu().numpy())
+                if getattr(args, "ingest_collate", None) is not None:
+                    export_occlusion_nifti(args, ds.uids[i], occ_maps)
+                if getattr(args, "scan_space", False):
+                    export_scan_space_maps(args, ds.uids[i], occ_maps, args.ingest_collate.last_volumes[0], prefix="occ_map")
         preds.append(p.cpu()); evs.append(ev); dus.append(du)
     p, e, d = torch.cat(preds).numpy(), torch.cat(evs).numpy(), torch.cat(dus).numpy()
     report_empty_masks(args)
@@ -543,6 +570,12 @@ def build_arg_parser():
     ap.add_argument("--scan_space", action="store_true",
                     help="with --inference --image_loc and Grad-CAM on: also write every class's attention map on each scan's own voxel "
                          "grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz)")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="with --inference --images: occlusion sensitivity maps per patient (attention_maps/patient{i}_occ_map.npy, "
+                         "(K, D, H, W) signed deltas; with --image_loc occ_map_class{k}.nii.gz, with --scan_space also on the scans' grids)")
+    ap.add_argument("--occlusion_window", type=int, default=16, help="edge of the occluded box in voxels")
+    ap.add_argument("--occlusion_stride", type=int, default=8, help="step of the box, 1..window")
+    ap.add_argument("--occlusion_batch", type=int, default=8, help="occluded samples per forward")
     # synthetic-data knobs (no counterpart upstream)
     ap.add_argument("--synthetic_patients", type=int, default=16)
     ap.add_argument("--synthetic_size", type=int, default=64)
@@ -569,6 +602,15 @@ def main(argv=None):
         raise SystemExit("--lr_finder is single-process (as upstream's find_lr); run it without torch.distributed.run")
     if a.bootstrap and not (a.inference and a.survival):
         raise SystemExit("--bootstrap resamples the evaluation of `--inference --survival` (main.py:767-887); it has no meaning for training runs")
+    if a.occlusion:
+        missing = [f for f, on in (("--inference", a.inference), ("--images", a.images)) if not on]
+        if missing:
+            raise SystemExit("--occlusion writes occlusion sensitivity maps of the image input at inference: it needs " + " and ".join(missing))
+        if a.bootstrap:
+            raise SystemExit("--occlusion excludes --bootstrap (bootstrapping writes no maps, main.py:774-777)")
+        if not (1 <= a.occlusion_stride <= a.occlusion_window) or a.occlusion_batch < 1:
+            raise SystemExit(f"--occlusion needs 1 <= --occlusion_stride ({a.occlusion_stride}) <= --occlusion_window ({a.occlusion_window}) "
+                             f"and --occlusion_batch ({a.occlusion_batch}) >= 1")
     if a.transforms and not a.images:
         raise SystemExit("--transforms acts on image volumes: it needs --images")
 

@@ -132,6 +132,15 @@ class UnpackFramesDesc(Structure):
     _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_frames", c_int32), ("n_refs", c_int32), ("one", c_int32)]
 
 
+OCCLUSION_MAX_OUTPUTS = 16                   # MMNN_OCCLUSION_MAX_OUTPUTS
+CHANNEL_MEANS_PARTS = 64                     # MMNN_CHANNEL_MEANS_PARTS
+
+
+class OcclusionDesc(Structure):
+    """mmnn_occlusion_desc (include/mmnn_sts.h)."""
+    _fields_ = [("c", c_int32), ("d", c_int32), ("h", c_int32), ("w", c_int32), ("win", c_int32 * 3), ("stride", c_int32 * 3)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -236,6 +245,14 @@ def lib():
     L.mmnn_rasterize_contours.argtypes = [POINTER(RasterizeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_unpack_frames.restype = c_int32
     L.mmnn_unpack_frames.argtypes = [POINTER(UnpackFramesDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_occlusion_window_count.restype = c_int64
+    L.mmnn_occlusion_window_count.argtypes = [POINTER(OcclusionDesc), POINTER(c_int32)]
+    L.mmnn_occlude_windows.restype = c_int32
+    L.mmnn_occlude_windows.argtypes = [POINTER(OcclusionDesc), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]
+    L.mmnn_occlusion_map.restype = c_int32
+    L.mmnn_occlusion_map.argtypes = [POINTER(OcclusionDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_channel_means.restype = c_int32
+    L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64
     L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
     L.mmnn_mlp_saved_floats.restype = c_int64

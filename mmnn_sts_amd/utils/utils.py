@@ -273,6 +273,125 @@ def add_gradcam(model, output_dir='attention_maps', multimodal=False):
     return GradCAM(model)
 
 
+def _occlusion_triple(name, v):
+    """An int or a 3-sequence of ints >= 1 -> (d, h, w)."""
+    t = tuple(v) if isinstance(v, (tuple, list)) else (v,) * 3
+    if len(t) != 3 or any(isinstance(e, bool) or not isinstance(e, int) or e < 1 for e in t):
+        raise ValueError(f"OcclusionSensitivity: {name} must be a positive int or three of them (d, h, w), got {v!r}")
+    return t
+
+
+class OcclusionSensitivity(nn.Module):
+    """Occlusion sensitivity maps: a `window` box of the input is replaced by `fill`, the model run, and the move of every output
+    recorded; the box slides over the volume with `stride` and each voxel gets the mean move over the boxes that cover it.  The window
+    grid, the fp64 summation order and the padding of the last batch are the contract above `mmnn_occlusion_window_count` in
+    include/mmnn_sts.h (the last window of an axis is clamped to the edge, so every voxel is covered).
+
+    `window`, `stride`: an int or (d, h, w), 1 <= stride <= window; `batch`: occluded samples per forward; `fill`: "mean" (the
+    per-channel mean of the input it is given, computed on the device) or a float.  `occ(x)` takes a batch-1 input -- a (1, C, D, H, W)
+    tensor or, with `multimodal`, the fusion model's {"image", "clinical"} dict, whose clinical row is repeated per occluded sample
+    while only the image is occluded -- and returns `(outputs, maps)`: `outputs` is what `model.eval()(x)` returns, `maps` a
+    (K, D, H, W) fp32 device tensor of RAW SIGNED deltas, one map per output: positive where hiding the region lowers that output.
+    They are not min-max normalised: the sign and the scale are the information.
+
+    Only the model's eval-mode forward is used, on its existing HIP path and under `torch.no_grad()`, so the supported models are
+    exactly those whose own `eval()` forward supports a batch of `batch` samples (the fusion model with blend off, the image-only
+    DenseNets, r3d_18); the model must return an (N, K) fp32 tensor with K <= 16.  The occluded batches (`mmnn_occlude_windows`), the
+    fill (`mmnn_channel_means`) and the map (`mmnn_occlusion_map`) are HIP kernels (csrc/occlusion.hip); torch allocates and copies
+    rows into the score table and does no arithmetic.  Parity with MONAI's OcclusionSensitivity is unpinned.
+    """
+
+    def __init__(self, model, window=16, stride=8, batch=8, fill="mean", multimodal=False):
+        super().__init__()
+        self.window = _occlusion_triple("window", window)
+        self.stride = _occlusion_triple("stride", stride)
+        for r, (w, s) in enumerate(zip(self.window, self.stride)):
+            if s > w:
+                raise ValueError(f"OcclusionSensitivity: stride {s} exceeds window {w} on axis {r}: voxels between the windows would never be hidden")
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise ValueError(f"OcclusionSensitivity: batch must be a positive int, got {batch!r}")
+        if fill != "mean":
+            if isinstance(fill, (bool, str)) or not isinstance(fill, (int, float)) or fill != fill or fill in (float("inf"), float("-inf")):
+                raise ValueError(f"OcclusionSensitivity: fill must be 'mean' or a finite float, got {fill!r}")
+            fill = float(fill)
+        self.model = model
+        self.batch = batch
+        self.fill = fill
+        self.multimodal = bool(multimodal)
+
+    def _check_input(self, x):
+        if self.multimodal:
+            if not (isinstance(x, dict) and "image" in x and "clinical" in x):
+                raise ValueError("OcclusionSensitivity(multimodal=True) expects the fusion model's {'image', 'clinical'} dict")
+            if getattr(self.model, "blend", False):
+                raise ValueError("OcclusionSensitivity expects blend=False (an (N, K) output), as main.py's inference path uses it")
+            image = x["image"]
+        else:
+            image = x
+        if not (torch.is_tensor(image) and image.dim() == 5 and image.shape[0] == 1):
+            raise ValueError(f"OcclusionSensitivity takes one patient at a time: a (1, C, D, H, W) image, got "
+                             f"{tuple(image.shape) if torch.is_tensor(image) else type(image).__name__}")
+        if not image.is_cuda:
+            raise RuntimeError("mmnn_sts_amd: occlusion sensitivity runs on the MI355X only (no CPU path); move model and input to cuda")
+        extent = tuple(int(t) for t in image.shape[2:])
+        if any(w > e for w, e in zip(self.window, extent)):
+            raise ValueError(f"OcclusionSensitivity: window {self.window} is larger than the input extent {extent}")
+        return image.contiguous().float()
+
+    def forward(self, x):
+        import ctypes
+        image = self._check_input(x)
+        m = self.model
+        modes = [(mod, mod.training) for mod in m.modules()]
+        m.eval()
+        try:
+            with torch.no_grad():
+                L = _lib.lib()
+                stream = torch.cuda.current_stream().cuda_stream
+                dev = image.device
+                c, (d, h, w) = int(image.shape[1]), (int(t) for t in image.shape[2:])
+                desc = _lib.OcclusionDesc(c, d, h, w, (ctypes.c_int32 * 3)(*self.window), (ctypes.c_int32 * 3)(*self.stride))
+                wn = L.mmnn_occlusion_window_count(ctypes.byref(desc), None)
+                if wn < 0:
+                    raise ValueError(f"OcclusionSensitivity: {_lib.last_error()}")
+                outputs = m(dict(x, image=image) if self.multimodal else image)
+                if not (outputs.dim() == 2 and outputs.shape[0] == 1 and outputs.dtype == torch.float32
+                        and 1 <= outputs.shape[1] <= _lib.OCCLUSION_MAX_OUTPUTS):
+                    raise ValueError(f"OcclusionSensitivity: the model must return a (1, K) float32 tensor with K <= "
+                                     f"{_lib.OCCLUSION_MAX_OUTPUTS} for one patient, got {tuple(outputs.shape)} {outputs.dtype}")
+                base = outputs.contiguous()
+                k = int(base.shape[1])
+                if self.fill == "mean":
+                    fill = torch.empty(c, device=dev, dtype=torch.float32)
+                    ws = torch.empty(c * _lib.CHANNEL_MEANS_PARTS, device=dev, dtype=torch.float64)
+                    _lib.check(L.mmnn_channel_means(image.data_ptr(), c, d * h * w, fill.data_ptr(), ws.data_ptr(), stream), "channel_means")
+                else:
+                    fill = torch.full((c,), self.fill, device=dev, dtype=torch.float32)
+                scores = torch.empty((wn, k), device=dev, dtype=torch.float32)
+                occluded = torch.empty((self.batch, c, d, h, w), device=dev, dtype=torch.float32)
+                clinical = x["clinical"].expand(self.batch, -1).contiguous() if self.multimodal else None
+                for first in range(0, wn, self.batch):
+                    _lib.check(L.mmnn_occlude_windows(ctypes.byref(desc), image.data_ptr(), fill.data_ptr(), first, self.batch,
+                                                      occluded.data_ptr(), stream), "occlude_windows")
+                    out = m({"image": occluded, "clinical": clinical} if self.multimodal else occluded)
+                    rows = min(self.batch, wn - first)                  # the padded tail of the last batch repeats the last window
+                    scores[first:first + rows].copy_(out[:rows])
+                maps = torch.empty((k, d, h, w), device=dev, dtype=torch.float32)
+                _lib.check(L.mmnn_occlusion_map(ctypes.byref(desc), k, base.data_ptr(), scores.data_ptr(), maps.data_ptr(), stream),
+                           "occlusion_map")
+                self.scores = scores
+        finally:
+            for mod, mode in modes:
+                mod.training = mode
+        return outputs, maps
+
+
+def add_occlusion(model, multimodal=False, **kw):
+    """The twin of `add_gradcam`: an `OcclusionSensitivity` over the fusion model (multimodal) or an image-only one; `kw` are its
+    window / stride / batch / fill."""
+    return OcclusionSensitivity(model, multimodal=multimodal, **kw)
+
+
 class Normalize:
     """utils/utils.py:348-355: (x - mean * max(x)) / (std * max(x)), max over the whole sample (all channels); the sign of max(x) is
     kept.  A stage of mmnn_sts_amd.transforms.Compose; called on its own it runs as a one-stage pipeline on the device."""
