@@ -566,6 +566,58 @@ int mmnn_occlude_windows(const mmnn_occlusion_desc* d, const float* x, const flo
 int mmnn_occlusion_map(const mmnn_occlusion_desc* d, int32_t k, const float* base, const float* scores, float* out, void* stream);
 int mmnn_channel_means(const float* x, int32_t c, int64_t n, float* out, void* ws, void* stream);
 
+/* ---- radiomic features of one (scan, mask) pair: first order, the intensity histogram, exact order statistics and the 13 grey-level
+ * co-occurrence matrices with 23 features (csrc/radiomics.hip).  Scan and mask hold x*y*z elements, x fastest, in NIfTI types scan_type /
+ * mask_type (the codes of mmnn_ingest_desc); a voxel's value is raw * slope + inter in fp64, two roundings, and a slope of 0 or a
+ * non-finite slope switches the scaling off, as in the ingest.  The ROI is the voxels whose scaled mask value is not 0.  Everything is
+ * in voxel index space: distance 1, no resampling.
+ *   discretisation  low = floor(min / bw) * bw;  bin(v) = floor((v - low) / bw) + 1 in fp64, held at 1 from below;  Ng = bin(max).
+ *   hist            [max_bins] counts of bin - 1.           glcm  [13][max_bins][max_bins]: direction d (offsets (dz, dy, dx) with the first
+ *                   non-zero component positive, in lexicographic order: (0,0,1), (0,1,-1), (0,1,0), (0,1,1), (1,-1,-1), ... (1,1,1)), then
+ *                   [a - 1][b - 1]: for every ROI voxel with bin a whose neighbour at the offset lies in the volume and in the ROI with bin
+ *                   b, one count at [a][b] and one at [b][a].  Both buffers are the accumulation targets; the call zeroes them first.
+ *   result          the block below.  order[2i], order[2i + 1]: the values of rank floor(h), ceil(h), h = (n - 1) * p / 100, for
+ *                   p = 10, 25, 50, 75, 90, bitwise the elements of the sorted ROI values (-0.0 counts and is returned as +0.0).
+ *                   firstorder: Energy, Minimum, Maximum, Range, Mean, Variance, Skewness, Kurtosis, MeanAbsoluteDeviation,
+ *                   RootMeanSquared, 10Percentile, 90Percentile, Median, InterquartileRange, RobustMeanAbsoluteDeviation, Entropy,
+ *                   Uniformity (PyRadiomics' definitions, shift 0; RobustMeanAbsoluteDeviation is NaN when no value lies in [p10, p90]).
+ *                   glcm: Autocorrelation, JointAverage, ClusterProminence, ClusterShade, ClusterTendency, Contrast, Correlation,
+ *                   DifferenceAverage, DifferenceEntropy, DifferenceVariance, JointEnergy, JointEntropy, Imc1, Imc2, Idm, Idmn, Id, Idn,
+ *                   InverseVariance, MaximumProbability, SumAverage, SumEntropy, SumSquares: per direction, averaged over the directions
+ *                   whose matrix is not empty, NaN when all are.
+ *   flags           overflow (Ng > max_bins; n_bins still holds Ng), nonfinite (a NaN / Inf value in the ROI), empty (n = 0).  With a flag
+ *                   set every fp64 entry of the result is NaN, hist and glcm are zero, and n, the bounding box and the moments are still
+ *                   valid (lo = hi = 0 when empty).
+ * The integers are accumulated exactly (uint32 / uint64 atomics, in LDS where the matrix fits); every fp64 sum runs over a partition and
+ * in an order that depend on the extents only, without floating-point atomics: repeated calls are bit-identical.  No host wait.
+ * ws: mmnn_radiomics_workspace_bytes bytes, aligned to 256.  Refused (status 1; the size returns -1) before any launch: a null pointer, a
+ * non-positive extent, x*y*z >= 2^31, max_bins outside 1..MMNN_RADIOMICS_MAX_BINS, an unsupported type code, a bin_width that is not
+ * finite and positive, a buffer not aligned to its element size. */
+#define MMNN_RADIOMICS_DIRECTIONS 13
+#define MMNN_RADIOMICS_FIRSTORDER 17
+#define MMNN_RADIOMICS_GLCM 23
+#define MMNN_RADIOMICS_MAX_BINS 1024
+typedef struct {
+  int32_t x, y, z;
+  int32_t scan_type, mask_type;   /* NIfTI datatype codes */
+  double scan_slope, scan_inter, mask_slope, mask_inter;
+  double bin_width;
+  int32_t max_bins;
+} mmnn_radiomics_desc;
+typedef struct {
+  int64_t n;
+  int64_t lo[3], hi[3];           /* bounding box of the ROI, inclusive, x y z */
+  int64_t moments[9];             /* sums over the ROI of x, y, z, xx, yy, zz, xy, xz, yz */
+  int64_t n_bins;                 /* Ng */
+  int64_t overflow, nonfinite, empty;
+  double order[10];
+  double firstorder[MMNN_RADIOMICS_FIRSTORDER];
+  double glcm[MMNN_RADIOMICS_GLCM];
+} mmnn_radiomics_result;
+int64_t mmnn_radiomics_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t max_bins);
+int mmnn_radiomics(const mmnn_radiomics_desc* d, const void* scan, const void* mask, mmnn_radiomics_result* result, uint32_t* hist,
+                   uint32_t* glcm, void* ws, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

@@ -23,6 +23,9 @@ attention map back on each scan's own voxel grid, with the scan's affine (att_ma
 `--inference --images --occlusion` writes occlusion sensitivity maps (patient{i}_occ_map.npy: (K, D, H, W) signed deltas at the resolution of
 `--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
+`--radiomics` trains on radiomic features: the csv of `--rad_loc` (column MRN, then the features), or, without it, the table extracted
+on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py); alone it is
+the standalone MLP over the radiomic columns, with `--images` the fusion model, with `--preop` / `--postop` too the clinical columns first.
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
 """
@@ -242,8 +245,91 @@ def nifti_datasets(parser, args, device, seed, rank, world):
     from mmnn_sts_amd.data.ingest import IngestCollate
     full = parser.getDatasets(args, parser.getImagePath())
     train_uids, val_uids = split_uids(full.uids, args, seed)
+    if getattr(args, "radiomics", False):
+        scale_radiomics(parser, args, train_uids, rank)
     args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False))
     return ImageDatasetByUIDs(full, train_uids[rank::world]), ImageDatasetByUIDs(full, val_uids)
+
+
+def check_radiomics_flags(a, data_cfg):
+    """`--radiomics`: the csv of `--rad_loc` / `Data: rad_loc`, or an image tree to extract it from; the clinical csv holds the targets."""
+    if not data_cfg.get("rad_loc") and not data_cfg.get("image_loc"):
+        raise SystemExit("--radiomics needs --rad_loc (a csv of radiomic features with the column MRN) or --image_loc (patient directories "
+                         "to extract the features from)")
+    if not data_cfg.get("rad_loc") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--radiomics without --rad_loc extracts the features in a single process: run the extraction once "
+                         "(python -m mmnn_sts_amd.radiomics) and pass its csv as --rad_loc")
+    missing = [k for k in (("data_loc",) if data_cfg.get("rad_loc") else ("data_loc", "key_loc")) if not data_cfg.get(k)]
+    if missing:
+        raise SystemExit("--radiomics needs " + " and ".join(f"--{k}" for k in missing) + " (the clinical csv with uid, event{i}, duration{i}"
+                         + ("" if data_cfg.get("rad_loc") else "; the patient key csv with the columns 'Anon MRN', 'MRN'") + ")")
+    if a.images and not data_cfg.get("image_loc"):
+        raise SystemExit("--radiomics with --images pairs each patient's features with their scans: it needs --image_loc")
+    if a.lr_finder:
+        raise SystemExit("--lr_finder runs on synthetic image patients: run it without --radiomics")
+
+
+def extract_radiomics_if_needed(parser, args):
+    """`--radiomics` without `--rad_loc`: every patient (and modality) of the image tree -> <output_path>/radiomics_features.csv on the
+    device, which then is the run's `rad_loc`."""
+    data = parser.config["Data"]
+    if data.get("rad_loc"):
+        return
+    from mmnn_sts_amd import radiomics
+    from mmnn_sts_amd.data.ImageDatasets import ImageDataset
+    if not torch.cuda.is_available():
+        raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
+    rc = parser.radiomicsConfig()
+    paths = parser.getImagePath()
+    paths = paths if isinstance(paths, tuple) else (paths,)
+    prefixes = ("t1_", "t2_") if len(paths) == 2 else ("",)
+    rows = None
+    for path, px in zip(paths, prefixes):
+        ds = ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
+        threshold = (parser.config.get("Data") or {}).get("mask_threshold")
+        part = radiomics.extract_tree(ds, torch.device("cuda", 0), None, rc["bin_width"], rc["max_bins"],
+                                      None if threshold is None else float(threshold), prefixes=(px,))
+        if rows is None:
+            rows = part
+        else:
+            by = {r["MRN"]: r for r in part}
+            rows = [dict(r, **{k: v for k, v in by[r["MRN"]].items() if k != "MRN"}) for r in rows if r["MRN"] in by]
+    os.makedirs(args.output_path, exist_ok=True)
+    out = os.path.join(args.output_path, "radiomics_features.csv")
+    radiomics.write_csv(out, rows)
+    logger.info("radiomic features of %d patients -> %s", len(rows), out)
+    data["rad_loc"] = out
+
+
+def scale_radiomics(parser, args, train_uids, rank):
+    """`Radiomics: standardize`: z-score the radiomic columns with the training uids' mean / std, written to
+    <output_path>/radiomics_scaler.csv; `--inference` reads that file back."""
+    from mmnn_sts_amd.data.RadiomicsDatasets import SCALER_FILE
+    if not parser.radiomicsConfig()["standardize"]:
+        return
+    ds, path = parser.radiomics_dataset, os.path.join(args.output_path, SCALER_FILE)
+    if args.inference:
+        if not os.path.exists(path):
+            raise SystemExit(f"--inference --radiomics reads the scaler the training run wrote: {path} is missing (same --output_path, or "
+                             "`Radiomics: standardize: false`)")
+        ds.load_scaler(path)
+        return
+    ds.fit_scaler(train_uids)
+    if rank == 0:
+        os.makedirs(args.output_path, exist_ok=True)
+        ds.save_scaler(path)
+
+
+def radiomics_datasets(parser, args, seed, rank, world):
+    """`--radiomics` without `--images`: the predictor table (radiomic columns, behind the clinical ones with --preop / --postop) cut
+    into the train and validation uids."""
+    from mmnn_sts_amd.data.RadiomicsDatasets import TableByUIDs
+    full = parser.getDatasets(args)
+    train_uids, val_uids = split_uids(full.uids, args, seed)
+    known = set(full.uids)
+    train_uids, val_uids = [u for u in train_uids if u in known], [u for u in val_uids if u in known]
+    scale_radiomics(parser, args, train_uids, rank)
+    return TableByUIDs(full, train_uids[rank::world]), TableByUIDs(full, val_uids)
 
 
 def export_patient_nifti(args, uid, image, att, preds):
@@ -548,7 +634,7 @@ def run_lr_finder(a, cfg, seed):
 def build_arg_parser():
     ap = argparse.ArgumentParser()
     for flag, h in (("preop", "clinical features available pre-operation"), ("postop", "pre + post operation clinical features"),
-                    ("radiomics", "radiomic features (not implemented upstream either)"), ("images", "image data"),
+                    ("radiomics", "radiomic features: the csv of --rad_loc, or extracted on the device from --image_loc"), ("images", "image data"),
                     ("classification", "binary classification"), ("survival", "time-to-event model"), ("segmentation", "unsupported"),
                     ("lr_finder", "learning-rate range test (with --images --classification): lr_finder.csv / .png, suggested lr"), ("no_gradcam", "disable Grad-CAM for inference"), ("inference", "inference"),
                     ("split", "create a new dataset split"), ("blend", "gradient blending"), ("bootstrap", "bootstrap evaluation (with --inference --survival)")):
@@ -593,8 +679,8 @@ def main(argv=None):
     a.blend = a.blend or str_to_bool(a.use_blend)
     assert not all([a.classification, a.survival, a.segmentation]), 'Can only specify one of --classification , --survival , or --segmentation'
     assert any([a.classification, a.survival, a.segmentation]), 'Must specify one of --classification , --survival , or --segmentation'
-    if a.segmentation or a.radiomics:
-        raise SystemExit("--segmentation / --radiomics are outside the MI355X fusion path (SURVEY 2)")
+    if a.segmentation:
+        raise SystemExit("--segmentation is outside the MI355X fusion path (SURVEY 2)")
     if a.lr_finder and not (a.images and a.classification and not (a.preop or a.postop)):
         raise SystemExit("--lr_finder runs upstream's find_lr on an image classification dataset: it needs --images --classification "
                          "and no clinical flags (--preop / --postop)")
@@ -617,7 +703,10 @@ def main(argv=None):
     parser = Parser(a.config)
     cfg = parser.parseConfig()
     data_cfg = parser.applyDataFlags(a)
-    use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images)
+    if a.radiomics:
+        check_radiomics_flags(a, data_cfg)
+    # (--radiomics without --images reads --image_loc only to extract its features from)
+    use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images) and (a.images or not a.radiomics)
     if use_nifti:
         if not a.images:
             raise SystemExit("--image_loc points at NIfTI patient directories: it needs --images")
@@ -634,7 +723,7 @@ def main(argv=None):
         raise SystemExit("--scan_space lays the Grad-CAM attention maps over the patients' scans: it needs --inference, --image_loc (NIfTI "
                          "patient directories) and Grad-CAM on (--images, neither --no_gradcam nor --bootstrap)")
     hp = cfg.get("Hyperparameters", {})
-    a.multimodal = a.images and (a.preop or a.postop)
+    a.multimodal = a.images and (a.preop or a.postop or a.radiomics)
     a.blend = a.blend and a.multimodal
     a.batch_size = int(hp.get("train_batch_size", 2)) if a.config else 2
     a.momentum, a.weight_decay = float(hp.get("momentum", 0.9)), float(hp.get("weight_decay", 1e-4))
@@ -646,6 +735,8 @@ def main(argv=None):
     if a.transforms:
         from mmnn_sts_amd.transforms import train_transforms, val_transforms
         a.train_tf, a.val_tf = train_transforms, val_transforms
+    if a.radiomics:
+        extract_radiomics_if_needed(parser, a)
     model = parser.getModel(a)
     if a.multimodal:
         model.blend = a.blend
@@ -660,7 +751,10 @@ def main(argv=None):
     predictors = parser.predictors(a)
     inch = cfg["ImageModel"]["in_channels"]
     mk = lambda n, seed: SyntheticPatients(n, inch, a.synthetic_size, len(predictors), a.multimodal, a.images, seed)
-    if not a.images:
+    if a.radiomics and not a.images:
+        rad_train, rad_val = radiomics_datasets(parser, a, int(hp.get("seed", 42)), rank, world)
+        mk = lambda n, s: rad_train if s >= 1000 else rad_val
+    elif not a.images:
         # tabular-only: patients travel through a csv, as upstream's clinical datasets do
         os.makedirs(a.output_path, exist_ok=True)
         n_train, n_val = max(4, a.synthetic_patients), max(4, a.synthetic_patients // 4)

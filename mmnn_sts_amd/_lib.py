@@ -141,6 +141,17 @@ class OcclusionDesc(Structure):
     _fields_ = [("c", c_int32), ("d", c_int32), ("h", c_int32), ("w", c_int32), ("win", c_int32 * 3), ("stride", c_int32 * 3)]
 
 
+RADIOMICS_DIRECTIONS, RADIOMICS_FIRSTORDER, RADIOMICS_GLCM, RADIOMICS_MAX_BINS = 13, 17, 23, 1024
+RADIOMICS_RESULT_INT64, RADIOMICS_RESULT_BYTES = 20, (20 + 10 + 17 + 23) * 8      # mmnn_radiomics_result: 20 int64, then 50 doubles
+
+
+class RadiomicsDesc(Structure):
+    """mmnn_radiomics_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("scan_type", c_int32), ("mask_type", c_int32),
+                ("scan_slope", ctypes.c_double), ("scan_inter", ctypes.c_double), ("mask_slope", ctypes.c_double),
+                ("mask_inter", ctypes.c_double), ("bin_width", ctypes.c_double), ("max_bins", c_int32)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -251,6 +262,10 @@ def lib():
     L.mmnn_occlude_windows.argtypes = [POINTER(OcclusionDesc), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]
     L.mmnn_occlusion_map.restype = c_int32
     L.mmnn_occlusion_map.argtypes = [POINTER(OcclusionDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_radiomics_workspace_bytes.restype = c_int64
+    L.mmnn_radiomics_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.mmnn_radiomics.restype = c_int32
+    L.mmnn_radiomics.argtypes = [POINTER(RadiomicsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_channel_means.restype = c_int32
     L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64

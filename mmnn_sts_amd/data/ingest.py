@@ -10,6 +10,7 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     unpack_frames(frames, scan, device)             the frames of a DICOM SEG segment -> uint8 0 / 1 on the scan's grid, or 0 / 255 on the
                                                     segmentation's own (mmnn_unpack_frames)
     resample_mask(mask, scan_shape, index_map)      a mask drawn on another grid -> uint8 bytes on the scan's grid (mmnn_resample_mask)
+    prepare_pair(scan, mask, device)                upload, rasterise / unpack / resample the mask: the pair on one grid, on the device
     ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
     collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
     IngestCollate(device)                           the DataLoader collate_fn of the NIfTI datasets
@@ -396,6 +397,40 @@ def _dicom_index_map(scan, mask, mode, same):
     return nifti.index_map(scan, mask)
 
 
+def prepare_pair(scan, mask, dev, index_map=None, threshold: Optional[float] = None, what: str = "ingest"):
+    """The front that every consumer of a (scan, mask) pair shares (`ingest_volume`, `radiomics.extract`): upload what is still on the
+    host, rasterise an RTSTRUCT mask, unpack a SEG mask, resample a mask drawn on another grid (binarised at `threshold`; None: 0.5, or
+    128 behind a DICOM scan).  Returns (scan, mask), two DeviceVolumes on one grid.  The rules are `ingest_volume`'s."""
+    scan = upload(scan, dev)
+    drawn = isinstance(mask, (ContourSet, StagedContours))
+    if isinstance(mask, (FrameSet, StagedFrames)):
+        if not is_dicom(scan):
+            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
+        mask = unpack_frames(mask, scan, dev)
+        drawn = not mask.from_dicom          # on the scan's grid: the voxelwise path; on its own: a DICOM mask volume like a series'
+        if drawn and index_map is not None:
+            raise ValueError(f"{what}: a SEG mask on the scan's own grid takes no index_map")
+    elif drawn:
+        if index_map is not None:
+            raise ValueError(f"{what}: a contour mask is rasterised onto the scan's own grid; it takes no index_map")
+        if not is_dicom(scan):
+            raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
+        mask = rasterize_contours(mask, scan, dev)
+    else:
+        mask = upload(mask, dev)
+    if threshold is None:
+        threshold = default_threshold(scan)
+    if index_map is None and not drawn and (is_dicom(scan) or is_dicom(mask)):
+        index_map = mask_index_map(scan, mask)
+    if index_map is None and scan.shape != mask.shape:
+        if scan.affine is None or mask.affine is None:
+            raise ValueError(f"{what}: scan extent {scan.shape} differs from the mask's {mask.shape}")
+        index_map = nifti.index_map(scan, mask)
+    if index_map is not None:
+        mask = resample_mask(mask, scan.shape, index_map, threshold)
+    return scan, mask
+
+
 def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                   index_map=None, threshold: Optional[float] = None) -> torch.Tensor:
     """Enqueue the ingest of one volume on the current stream: `out_plane` (a contiguous (64,64,64) fp32 CUDA view, e.g. batch[n, c]) receives
@@ -411,33 +446,7 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and tuple(out_plane.shape) == (SIZE,) * 3):
         raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, got {tuple(out_plane.shape)} {out_plane.dtype} on {out_plane.device}")
     dev = out_plane.device
-    scan = upload(scan, dev)
-    drawn = isinstance(mask, (ContourSet, StagedContours))
-    if isinstance(mask, (FrameSet, StagedFrames)):
-        if not is_dicom(scan):
-            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
-        mask = unpack_frames(mask, scan, dev)
-        drawn = not mask.from_dicom          # on the scan's grid: the voxelwise path; on its own: a DICOM mask volume like a series'
-        if drawn and index_map is not None:
-            raise ValueError("ingest: a SEG mask on the scan's own grid takes no index_map")
-    elif drawn:
-        if index_map is not None:
-            raise ValueError("ingest: a contour mask is rasterised onto the scan's own grid; it takes no index_map")
-        if not is_dicom(scan):
-            raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
-        mask = rasterize_contours(mask, scan, dev)
-    else:
-        mask = upload(mask, dev)
-    if threshold is None:
-        threshold = default_threshold(scan)
-    if index_map is None and not drawn and (is_dicom(scan) or is_dicom(mask)):
-        index_map = mask_index_map(scan, mask)
-    if index_map is None and scan.shape != mask.shape:
-        if scan.affine is None or mask.affine is None:
-            raise ValueError(f"ingest: scan extent {scan.shape} differs from the mask's {mask.shape}")
-        index_map = nifti.index_map(scan, mask)
-    if index_map is not None:
-        mask = resample_mask(mask, scan.shape, index_map, threshold)
+    scan, mask = prepare_pair(scan, mask, dev, index_map, threshold)
     if extents is None:
         extents = torch.empty(3, dtype=torch.int32, device=dev)
     if not (extents.is_cuda and extents.dtype == torch.int32 and extents.is_contiguous() and extents.numel() == 3):

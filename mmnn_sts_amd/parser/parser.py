@@ -10,7 +10,7 @@ command-line flags override it; `format: auto | nifti | dicom` names the patient
 and binarised at 128 unless `mask_threshold` is set; `mask_roi` names the region of interest to take from an RTSTRUCT mask, which is
 rasterised onto its scan's grid and takes neither resample nor threshold, or the segment to take, by its SegmentLabel, from a DICOM SEG
 mask, which is unpacked onto its scan's grid when its frames lie on it and else resampled like a mask series).  DICOM means uncompressed single-frame series (`mmnn_sts_amd.data.dicom`); S3 and
-radiomics datasets stay outside the path, and main.py substitutes synthetic patients when no image location is configured.
+segmentation datasets stay outside the path, and main.py substitutes synthetic patients when no image location is configured.
 """
 import os
 
@@ -50,7 +50,7 @@ class Parser:
             raise ConfigurationError('T1T2 ImageModel modality requires 2 input channels - current number of in_channels: {}'.format(im['in_channels']))
         return self.config
 
-    def predictors(self, args):
+    def clinicalPredictors(self, args):
         cm = self.config['ClinicalModel']
         if 'NUM_PREDICTORS' in cm:
             return [f"predictor{i}" for i in range(int(cm['NUM_PREDICTORS']))]
@@ -59,10 +59,41 @@ class Parser:
             p += list(cm.get('POST_OP_PREDICTORS', []))
         return p
 
+    def predictors(self, args):
+        """The columns of the tabular input: the clinical predictors; with --radiomics the feature columns of the radiomics csv -- alone,
+        or behind the clinical ones when --preop / --postop is given too."""
+        if not getattr(args, 'radiomics', False):
+            return self.clinicalPredictors(args)
+        clinical = self.clinicalPredictors(args) if (getattr(args, 'preop', False) or getattr(args, 'postop', False)) else []
+        return clinical + self.radiomicsColumns()
+
+    def radiomicsConfig(self):
+        """`Radiomics: bin_width` (25), `max_bins` (256), `standardize` (true)."""
+        rad = self.config.get('Radiomics') or {}
+        try:
+            out = {'bin_width': float(rad.get('bin_width', 25.0)), 'max_bins': int(rad.get('max_bins', 256)), 'standardize': bool(rad.get('standardize', True))}
+        except (TypeError, ValueError):
+            raise ConfigurationError('Radiomics.bin_width / max_bins {!r} / {!r} are not numbers'.format(rad.get('bin_width'), rad.get('max_bins')))
+        if not (out['bin_width'] > 0.0 and out['bin_width'] < float('inf')) or not 1 <= out['max_bins'] <= 1024:
+            raise ConfigurationError('Radiomics.bin_width must be positive and finite and max_bins within 1..1024, got {} and {}'.format(out['bin_width'], out['max_bins']))
+        return out
+
+    def _radiomicsExcluded(self):
+        rm = self.config.get('RadiomicsModel') or {}
+        return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])
+
+    def radiomicsColumns(self):
+        """The feature columns of `Data: rad_loc`, from its header alone."""
+        from ..data.RadiomicsDatasets import feature_columns
+        with open(self._data('rad_loc')) as f:
+            header = [c.strip() for c in f.readline().strip().split(',')]
+        exclude, label = self._radiomicsExcluded()
+        return feature_columns(header, exclude + label)
+
     def applyDataFlags(self, args):
         """The `Data:` section with --image_loc / --data_loc / --key_loc laid over it (t1_path / t2_path default to 't1' / 't2')."""
         data = dict(self.config.get('Data') or {})
-        for k in ('image_loc', 'data_loc', 'key_loc'):
+        for k in ('image_loc', 'data_loc', 'key_loc', 'rad_loc'):
             if getattr(args, k, None):
                 data[k] = getattr(args, k)
         data.setdefault('t1_path', 't1')
@@ -133,7 +164,14 @@ class Parser:
             raise ConfigurationError('getDatasets needs --survival or --classification to pick the dataset classes')
         datasets = []
         if getattr(args, 'preop', False) or getattr(args, 'postop', False):
-            datasets.append(ClinicalDataset(self._data('data_loc'), self.predictors(args), classification=args.classification, survival=args.survival))
+            datasets.append(ClinicalDataset(self._data('data_loc'), self.clinicalPredictors(args), classification=args.classification, survival=args.survival))
+        if getattr(args, 'radiomics', False):
+            from ..data.RadiomicsDatasets import JoinedTableDataset, RadiomicsClassificationDataset, RadiomicsSurvivalDataset
+            cls = RadiomicsSurvivalDataset if args.survival else RadiomicsClassificationDataset
+            self.radiomics_dataset = cls(self._data('rad_loc'), self._data('data_loc'), *self._radiomicsExcluded())
+            datasets.append(self.radiomics_dataset)
+            if len(datasets) == 2:       # clinical and radiomic columns of one patient are one predictor table, clinical first
+                datasets = [JoinedTableDataset(datasets)]
         if args.images:
             both = isinstance(image_path, tuple)
             if args.survival:
@@ -153,7 +191,7 @@ class Parser:
             raise InitializationError('Attempted to load model prior to parsing config parameters, config must be parsed prior to loading model')
         im = self.config['ImageModel']
         name = im['name'].lower()
-        clinical = getattr(args, 'preop', False) or getattr(args, 'postop', False)
+        clinical = getattr(args, 'preop', False) or getattr(args, 'postop', False) or getattr(args, 'radiomics', False)
         if not args.images and clinical:
             return MLP(len(self.predictors(args)), im['num_classes'], im['feature_layers'])
         kw = dict(spatial_dims=im['spatial_dims'], in_channels=im['in_channels'], out_channels=im['num_classes'],
