@@ -10,7 +10,8 @@ detected per tree (`Data: format: auto | nifti | dicom` forces one; a tree that 
             scan's grid and binarised at 128 by default -- or one RT Structure Set file (`mmnn_sts_amd.data.rtstruct`): `mask/` (or
             its single sub-directory) then holds no image file and exactly one RTSTRUCT file, whose ROI `mask_roi` (`Data: mask_roi`;
             None: its only ROI) is rasterised onto the scan's own grid on the device and takes neither resample nor threshold --
-            or one DICOM Segmentation file (`mmnn_sts_amd.data.seg`, BINARY only), detected by its SOP class: the frames of the
+            or one DICOM Segmentation file (`mmnn_sts_amd.data.seg`, BINARY only); one scan of `mask/` tells the three apart by
+            SOP class (`mask_source`).  The frames of the
             segment `mask_roi` names by its SegmentLabel are unpacked on the device, straight onto the scan's grid when they lie
             on its slice planes, else onto the segmentation's own grid and then resampled like a mask series.  A NIfTI mask beside a
             DICOM scan, enhanced multi-frame scans, FRACTIONAL / LABELMAP SEG and compressed syntaxes are outside the path
@@ -70,69 +71,59 @@ def layout_of(patient_path):
     return 'dicom' if is_dicom else ('nifti' if is_nifti else None)
 
 
-def rtstruct_in(mask_directory):
-    """The path of the RT Structure Set file when `mask_directory` (or its single sub-directory) holds no DICOM image file and exactly
-    one RTSTRUCT file; None when it holds no RTSTRUCT file (an image series, or nothing this path reads).  Refused: several RTSTRUCT
-    files, an RTSTRUCT file beside image files."""
+def mask_source(mask_directory):
+    """What `mask_directory` (or its single sub-directory) holds, from one scan of it: ('series', the directory), ('rtstruct', the RT
+    Structure Set file) or ('seg', the DICOM Segmentation file).  Dot files and files without the magic are skipped; the others are
+    told apart by SOPClassUID alone (`seg.sop_class_of`), so a SEG file never reaches `dicom.read_file`, which refuses multi-frame
+    objects.  Refused: several RTSTRUCT or several SEG files, a SEG file beside an RTSTRUCT file, either beside image files.  A
+    directory with neither is a series, whatever else is wrong with it: `dicom.read_series` reports that."""
     try:
         d = dicom.series_directory(mask_directory)
     except ConfigurationError:
-        return None                          # (read_series reports what is wrong with the directory)
-    found, images = [], 0
+        return 'series', str(mask_directory)
+    found = {seg.SEGMENTATION_STORAGE: [], rtstruct.RT_STRUCTURE_SET_STORAGE: []}
+    others = []
     for name in sorted(os.listdir(d)):
         p = os.path.join(d, name)
         if name.startswith('.') or not os.path.isfile(p):
             continue
         try:
-            f = dicom.read_file(p, header_only=True)
+            found.get(seg.sop_class_of(p), others).append(p)
         except dicom.NotDicomError:
             continue
-        if f.sop_class_uid == rtstruct.RT_STRUCTURE_SET_STORAGE:
-            found.append(p)
-        elif f.has_image:
-            images += 1
-    if not found:
-        return None
-    if len(found) > 1:
-        raise ConfigurationError(f"{d}: {len(found)} RTSTRUCT files ({', '.join(os.path.basename(p) for p in found[:4])}): one structure set per mask/ is expected")
+    segs, sets = (found[k] for k in (seg.SEGMENTATION_STORAGE, rtstruct.RT_STRUCTURE_SET_STORAGE))
+    if not segs and not sets:
+        return 'series', str(mask_directory)
+    if len(segs) > 1:
+        raise ConfigurationError(f"{d}: {len(segs)} DICOM SEG files ({', '.join(os.path.basename(p) for p in segs[:4])}): one segmentation per mask/ is expected")
+    if segs and sets:
+        raise ConfigurationError(f"{d}: a DICOM SEG file ({os.path.basename(segs[0])}) beside an RTSTRUCT file ({os.path.basename(sets[0])}): "
+                                 "mask/ holds one image series, one structure set or one segmentation")
+    if len(sets) > 1:
+        raise ConfigurationError(f"{d}: {len(sets)} RTSTRUCT files ({', '.join(os.path.basename(p) for p in sets[:4])}): one structure set per mask/ is expected")
+    images = sum(1 for p in others if dicom.read_file(p, header_only=True).has_image)
+    if images and segs:
+        raise ConfigurationError(f"{d}: a DICOM SEG file ({os.path.basename(segs[0])}) beside {images} DICOM image file(s): mask/ holds one "
+                                 "image series, one structure set or one segmentation")
     if images:
-        raise ConfigurationError(f"{d}: an RTSTRUCT file ({os.path.basename(found[0])}) beside {images} DICOM image file(s): mask/ holds either "
+        raise ConfigurationError(f"{d}: an RTSTRUCT file ({os.path.basename(sets[0])}) beside {images} DICOM image file(s): mask/ holds either "
                                  "one image series or one structure set")
-    return found[0]
+    return ('seg', segs[0]) if segs else ('rtstruct', sets[0])
+
+
+def rtstruct_in(mask_directory):
+    """The path of the RT Structure Set file when `mask_source` finds one, else None."""
+    kind, path = mask_source(mask_directory)
+    return path if kind == 'rtstruct' else None
 
 
 def seg_in(mask_directory):
-    """The path of the DICOM Segmentation file when `mask_directory` (or its single sub-directory) holds exactly one and neither an
-    image file nor an RTSTRUCT file; None when it holds no SEG file.  Files are told apart by SOPClassUID alone (`seg.sop_class_of`):
-    a SEG file never reaches `dicom.read_file`, which refuses multi-frame objects.  Refused: several SEG files, a SEG file beside image
-    files or beside an RTSTRUCT file."""
-    try:
-        d = dicom.series_directory(mask_directory)
-    except ConfigurationError:
-        return None                          # (read_series reports what is wrong with the directory)
-    found, others = [], []
-    for name in sorted(os.listdir(d)):
-        p = os.path.join(d, name)
-        if name.startswith('.') or not os.path.isfile(p):
-            continue
-        try:
-            sop = seg.sop_class_of(p)
-        except dicom.NotDicomError:
-            continue
-        (found if sop == seg.SEGMENTATION_STORAGE else others).append((p, sop))
-    if not found:
-        return None
-    if len(found) > 1:
-        raise ConfigurationError(f"{d}: {len(found)} DICOM SEG files ({', '.join(os.path.basename(p) for p, _ in found[:4])}): one segmentation per mask/ is expected")
-    structure_sets = [p for p, sop in others if sop == rtstruct.RT_STRUCTURE_SET_STORAGE]
-    if structure_sets:
-        raise ConfigurationError(f"{d}: a DICOM SEG file ({os.path.basename(found[0][0])}) beside an RTSTRUCT file ({os.path.basename(structure_sets[0])}): "
-                                 "mask/ holds one image series, one structure set or one segmentation")
-    images = sum(1 for p, _ in others if dicom.read_file(p, header_only=True).has_image)
-    if images:
-        raise ConfigurationError(f"{d}: a DICOM SEG file ({os.path.basename(found[0][0])}) beside {images} DICOM image file(s): mask/ holds one "
-                                 "image series, one structure set or one segmentation")
-    return found[0][0]
+    """The path of the DICOM Segmentation file when `mask_source` finds one, else None."""
+    kind, path = mask_source(mask_directory)
+    return path if kind == 'seg' else None
+
+
+READERS = {'rtstruct': rtstruct, 'seg': seg}         # the kinds of `mask_source` that are one file, placed against the scan
 
 
 class ImageDataset(torch.utils.data.Dataset):
@@ -146,8 +137,7 @@ class ImageDataset(torch.utils.data.Dataset):
             raise ConfigurationError(f"format {format!r} is none of {FORMATS}")
         self.mask_resample = mask_resample
         self.mask_roi = mask_roi
-        self._rtstruct = {}                  # mask directory -> the RTSTRUCT file in it, or None (an image series)
-        self._seg = {}                       # mask directory -> the DICOM SEG file in it, or None
+        self._sources = {}                   # mask directory -> what `mask_source` found in it: (kind, path)
         self.patient_directory = str(patient_directory)
         self.patients = sorted(x for x in os.listdir(self.patient_directory)
                                if not x.startswith('.') and os.path.isdir(os.path.join(self.patient_directory, x)))
@@ -191,32 +181,23 @@ class ImageDataset(torch.utils.data.Dataset):
         """(extents, affine or None) from the headers alone.  An RTSTRUCT mask has no grid of its own: (None, None), once its ROI
         names have been read and `mask_roi` resolved against them (a bad name fails here, at construction).  So has a SEG mask
         until it is placed against its scan (`_check_grids`); its segment labels are resolved here as well."""
-        if self.layout == 'dicom' and self._seg_of(path):
-            seg.resolve(seg.read(self._seg_of(path), header_only=True), self.mask_roi)
-            return None, None
-        if self.layout == 'dicom' and self._rtstruct_of(path):
-            rtstruct.resolve(rtstruct.read(self._rtstruct_of(path), header_only=True), self.mask_roi)
+        kind, file = self._source(path)
+        if kind in READERS:
+            READERS[kind].resolve(READERS[kind].read(file, header_only=True), self.mask_roi)
             return None, None
         if self.layout == 'dicom':
             series = dicom.read_series(path, header_only=True)
             return series.shape, series.affine
         return nifti.read_geometry(path)
 
-    def _rtstruct_of(self, directory):
-        """The RTSTRUCT file of a mask/ directory, or None; image/ directories always hold a series."""
-        if os.path.basename(directory) != 'mask' or self._seg_of(directory):
-            return None
-        if directory not in self._rtstruct:
-            self._rtstruct[directory] = rtstruct_in(directory)
-        return self._rtstruct[directory]
-
-    def _seg_of(self, directory):
-        """The DICOM SEG file of a mask/ directory, or None."""
-        if os.path.basename(directory) != 'mask':
-            return None
-        if directory not in self._seg:
-            self._seg[directory] = seg_in(directory)
-        return self._seg[directory]
+    def _source(self, path):
+        """(kind, path) of a scan or mask: what `mask_source` finds in a mask/ directory of the DICOM layout, looked at once; image/
+        directories and NIfTI files are always ('series', path)."""
+        if self.layout != 'dicom' or os.path.basename(path) != 'mask':
+            return 'series', path
+        if path not in self._sources:
+            self._sources[path] = mask_source(path)
+        return self._sources[path]
 
     @property
     def uids(self):
@@ -245,12 +226,11 @@ class ImageDataset(torch.utils.data.Dataset):
     def _load(self, patient):
         scan_path, mask_path = self._files(patient)
         read = dicom.read_series if self.layout == 'dicom' else nifti.read
-        if self.layout == 'dicom' and self._seg_of(mask_path):
-            # the collate function places the frames against the scan and unpacks them on the device
-            return read(scan_path), seg.select(seg.read(self._seg_of(mask_path)), self.mask_roi)
-        if self.layout == 'dicom' and self._rtstruct_of(mask_path):
-            # the contours are born on the scan's grid: the collate function rasterises them there (no resample, no threshold)
-            return read(scan_path), rtstruct.select(rtstruct.read(self._rtstruct_of(mask_path)), self.mask_roi)
+        kind, file = self._source(mask_path)
+        if kind in READERS:
+            # the collate function places the frames of a SEG mask against the scan and unpacks them on the device; contours are born
+            # on the scan's grid and rasterised there (no resample, no threshold)
+            return read(scan_path), READERS[kind].select(READERS[kind].read(file), self.mask_roi)
         scan, mask = read(scan_path), read(mask_path)
         self._check_grids(patient, (scan.shape, scan.affine, scan_path), (mask.shape, mask.affine, mask_path))
         return scan, mask
@@ -260,20 +240,17 @@ class ImageDataset(torch.utils.data.Dataset):
         An RTSTRUCT mask (extents None) is on the scan's grid by construction; its scan needs a geometry to place the contours by.
         A SEG mask (extents None as well) is placed here from its header: True when its frames form a grid of their own."""
         (sshape, saff, _), (mshape, maff, _) = scan, mask
-        if mshape is None and self._seg_of(mask[2]):
-            path = self._seg_of(mask[2])
-            if saff is None:
-                raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {scan[2]} has no position / orientation to place the "
-                                         f"frames of {path} by")
+        kind, path = self._source(mask[2])
+        if kind in READERS and saff is None:
+            raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {scan[2]} has no position / orientation to place the "
+                                     f"{'frames' if kind == 'seg' else 'contours'} of {path} by")
+        if kind == 'seg':
             place = seg.to_scan(seg.select(seg.read(path, header_only=True), self.mask_roi), sshape, saff)
             if not place.on_scan and self.mask_resample == 'never':
                 raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): scan extent {tuple(sshape)}, SEG extent {tuple(place.shape)}: "
                                          f"{path} is on a grid of its own (Data.mask_resample is 'never')")
             return not place.on_scan
-        if mshape is None:
-            if saff is None:
-                raise ConfigurationError(f"patient {patient} (uid {self._uid_of(patient)}): {scan[2]} has no position / orientation to place the "
-                                         f"contours of {self._rtstruct_of(mask[2])} by")
+        if kind == 'rtstruct':
             return False
         what = f"patient {patient} (uid {self._uid_of(patient)}): scan extent {tuple(sshape)}, mask extent {tuple(mshape)}"
         if len(sshape) != 3 or len(mshape) != 3:

@@ -15,8 +15,10 @@ must give the same device batch bit for bit.
 Accepted: implicit VR little endian (1.2.840.10008.1.2) and explicit VR little endian (1.2.840.10008.1.2.1), SamplesPerPixel 1, one
 frame per file, BitsAllocated 8 / 16 / 32.  Refused, with the file named: big endian, deflated, every encapsulated (compressed) syntax,
 multi-frame and enhanced objects, colour, float / double pixel data.  A mask may also be an RT Structure Set: that file is read by
-`rtstruct.py`, or a BINARY DICOM Segmentation object, read by `seg.py`; both share this module's element decoding and descend into the
-sequences that `read_file` skips.  `read_file` itself keeps refusing every multi-frame file.
+`rtstruct.py`, or a BINARY DICOM Segmentation object, read by `seg.py`.  What the three readers share lives here once: `part10` (the
+one place a file is mapped), `walk` (the nested data-set walk that descends into the sequences `read_file` skips), the value helpers
+`_text` / `_integer` / `_floats`, `match_name` behind both `resolve`s and `lps_to_ras`.  `read_file` itself keeps refusing every
+multi-frame file.
 
 `read_series(directory)` sorts the slices by position along the normal of ImageOrientationPatient -- file names and InstanceNumber play
 no part -- and forms the affine in RAS, the convention of `NiftiImage.affine`, so `nifti.index_map`, `KeptVolume.affine` and the
@@ -26,7 +28,9 @@ import logging
 import mmap
 import os
 import struct
+from contextlib import contextmanager
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -164,6 +168,143 @@ def _value(buf, name, vr, voff, length, path):
     return v[0] if v else None
 
 
+def _text(buf, value):
+    voff, length = value
+    return bytes(buf[voff:voff + length]).decode("latin-1").strip(" \0")
+
+
+def _integer(buf, value, what, path, vr="IS"):
+    """The integer of an element found by `walk`: a binary US, else a decimal string (IS, DS)."""
+    voff, length = value
+    if vr == "US":
+        if length < 2:
+            _refuse(path, f"malformed: {what} is empty")
+        return struct.unpack_from("<H", buf, voff)[0]
+    text = _text(buf, value)
+    try:
+        return int(float(text))
+    except ValueError:
+        _refuse(path, f"malformed: {what} holds {text[:32]!r}")
+
+
+def _floats(buf, value, what, count, path):
+    """The finite numbers of a DS element found by `walk`, `count` of them (None: any number)."""
+    voff, length = value
+    raw = bytes(buf[voff:voff + length])
+    try:
+        v = _numbers(raw)
+    except ValueError:
+        _refuse(path, f"malformed: {what} holds {raw[:32]!r}")
+    if count is not None and len(v) != count:
+        _refuse(path, f"malformed: {what} holds {len(v)} values, {count} expected")
+    if not np.isfinite(v).all():
+        _refuse(path, f"malformed: {what} holds a non-finite number")
+    return v
+
+
+def walk(buf, off, end, explicit, path, kept, entered, depth=0, stop_after=None, pixel_data=False):
+    """The elements of one data set (the file's, or an item's) from `off`: {tag: (value offset, length)} for the tags in `kept` and
+    {tag: [item, ...]} for the sequences in `entered`, which it descends into (in implicit VR they are recognised by tag).  `end`:
+    where the data set ends, or None for an item of undefined length (closed by its delimiter).  Where the file's own data set stops:
+    behind tag `stop_after`, or, with `pixel_data`, at PixelData, whose (value offset, declared length) is recorded without looking
+    at the value.  Returns (elements, offset behind the data set)."""
+    if depth > MAX_DEPTH:
+        _refuse(path, f"malformed: sequences nested deeper than {MAX_DEPTH}")
+    found = {}
+    while end is None or off < end:
+        tag, vr, length, voff = _element(buf, off, explicit, path)
+        if tag == ITEM_END and end is None:
+            return found, voff
+        if tag[0] == 0xFFFE:
+            _refuse(path, f"malformed: item tag ({tag[0]:04X},{tag[1]:04X}) at byte {off} outside a sequence")
+        if stop_after is not None and tag > stop_after:
+            break
+        if pixel_data and tag >= PIXEL_DATA:
+            if tag == PIXEL_DATA:
+                found[tag] = (voff, length)
+            break
+        inner_explicit = explicit and vr != "UN"      # the content of a UN element of undefined length is implicit VR (PS3.5 6.2.2)
+        if tag in entered and (vr in (None, "SQ") or (vr == "UN" and length == UNDEFINED)):
+            found[tag], off = _items(buf, voff, length, inner_explicit, path, kept, entered, depth + 1)
+            continue
+        if length == UNDEFINED:
+            off = _skip_sequence(buf, voff, inner_explicit, path, depth)
+            continue
+        limit = len(buf) if end is None else end
+        if voff + length > limit:
+            _refuse(path, f"malformed: element ({tag[0]:04X},{tag[1]:04X}) at byte {off} declares {length} bytes, {limit - voff} are left")
+        if tag in kept:
+            found[tag] = (voff, length)
+        off = voff + length
+    return found, off
+
+
+def _items(buf, off, length, explicit, path, kept, entered, depth):
+    """The items of a sequence whose value starts at `off`: ([elements of each item], offset behind the sequence)."""
+    end = None if length == UNDEFINED else off + length
+    if end is not None and end > len(buf):
+        _refuse(path, f"malformed: a sequence at byte {off} declares {length} bytes, {len(buf) - off} are left")
+    items = []
+    while end is None or off < end:
+        tag, _, ilen, voff = _element(buf, off, explicit, path)
+        if tag == SEQUENCE_END and end is None:
+            return items, voff
+        if tag != ITEM:
+            _refuse(path, f"malformed: ({tag[0]:04X},{tag[1]:04X}) at byte {off} where an item of a sequence was expected")
+        if ilen == UNDEFINED:
+            found, off = walk(buf, voff, None, explicit, path, kept, entered, depth)
+        else:
+            limit = len(buf) if end is None else end
+            if voff + ilen > limit:
+                _refuse(path, f"malformed: an item at byte {off} declares {ilen} bytes, {limit - voff} are left")
+            found, off = walk(buf, voff, voff + ilen, explicit, path, kept, entered, depth)
+        items.append(found)
+    return items, off
+
+
+def match_name(path, names, roi, noun, verb):
+    """The index into `names` of the one that `roi` (`Data: mask_roi`) names: exact and case-insensitive; None takes the only one.
+    `noun`, `verb`: what the file calls them ("ROI" / "named", "segment" / "labelled")."""
+    listed = ", ".join(repr(n) for n in names)
+    if roi is None:
+        if len(names) == 1:
+            return 0
+        raise ConfigurationError(f"{path} holds {len(names)} {noun}s ({listed}): name one with Data.mask_roi")
+    hits = [i for i, n in enumerate(names) if n.lower() == str(roi).lower()]
+    if not hits:
+        raise ConfigurationError(f"{path} has no {noun} {verb} {roi!r}; its {noun}s are {listed}")
+    if len(hits) > 1:
+        raise ConfigurationError(f"{path} has {len(hits)} {noun}s {verb} {roi!r} ({listed})")
+    return hits[0]
+
+
+def lps_to_ras(lps):
+    """A voxel index -> mm matrix in DICOM's LPS as one in RAS, the convention of `NiftiImage.affine`."""
+    affine = lps.copy()
+    affine[:2, :] *= -1.0
+    affine += 0.0                            # (no negative zeros)
+    return affine
+
+
+@contextmanager
+def part10(path):
+    """Map a part-10 file: yields `f` with `buf` (the mapping), `path`, `size`, `syntax` (TransferSyntaxUID) and `off` (where the data
+    set starts).  NotDicomError for a file too short for a preamble or without the magic.  The mapping is closed on the way out unless
+    the caller set `f.keep`, as it must when it hands on a zero-copy view of PixelData: the file then stays mapped while the view lives."""
+    path = str(path)
+    size = os.path.getsize(path)
+    if size < 132:
+        raise NotDicomError(f"{path}: missing magic: {size} bytes, shorter than a preamble (not a DICOM part-10 file)")
+    with open(path, "rb") as fh:
+        f = SimpleNamespace(buf=mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ), path=path, size=size, keep=False)
+    try:
+        f.syntax, f.off = _transfer_syntax(f.buf, path)
+        yield f
+    finally:
+        if not f.keep:
+            f.buf.close()
+
+
 def _transfer_syntax(buf, path):
     """(TransferSyntaxUID, offset of the data set): the file meta group is explicit VR little endian whatever follows it."""
     if len(buf) < 132 or bytes(buf[128:132]) != b"DICM":
@@ -225,16 +366,10 @@ def _validate(f: DicomFile, size: int):
 def read_file(path, header_only=False) -> DicomFile:
     """Parse one file up to PixelData (7FE0,0010).  `frame` is a zero-copy uint8 view of the file's voxel bytes (the file stays mapped
     while the view lives); with `header_only` no voxel byte is read and `frame` stays None."""
-    path = str(path)
-    size = os.path.getsize(path)
-    if size < 132:
-        raise NotDicomError(f"{path}: missing magic: {size} bytes, shorter than a preamble (not a DICOM part-10 file)")
-    with open(path, "rb") as fh:
-        buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-    try:
-        syntax, off = _transfer_syntax(buf, path)
-        explicit = _check_syntax(syntax, path)
-        f = DicomFile(path, syntax)
+    with part10(path) as p:
+        path, buf, size, off = p.path, p.buf, p.size, p.off
+        explicit = _check_syntax(p.syntax, path)
+        f = DicomFile(path, p.syntax)
         while off < size:
             tag, vr, length, voff = _element(buf, off, explicit, path)
             if tag in (FLOAT_PIXEL_DATA, DOUBLE_PIXEL_DATA):
@@ -262,11 +397,7 @@ def read_file(path, header_only=False) -> DicomFile:
             need = _validate(f, size)
             if not header_only:
                 f.frame = np.frombuffer(buf, dtype=np.uint8, count=need, offset=f.pixel_offset)
-    except Exception:
-        buf.close()
-        raise
-    if f.frame is None:
-        buf.close()
+                p.keep = True
     return f
 
 
@@ -390,11 +521,7 @@ def read_series(directory, header_only=False) -> DicomSeries:
             if getattr(s, name) != getattr(first, name):
                 raise ConfigurationError(f"{d}: {first.path} and {s.path} differ in {what} ({getattr(first, name)} and {getattr(s, name)})")
     slices, lps = _geometry(slices, d)
-    affine = None
-    if lps is not None:
-        affine = lps.copy()
-        affine[:2, :] *= -1.0                # LPS -> RAS: the convention of NiftiImage.affine
-        affine += 0.0                        # (no negative zeros)
+    affine = None if lps is None else lps_to_ras(lps)
     first = slices[0]
     return DicomSeries((int(first.columns), int(first.rows), len(slices)), affine, d, int(first.bits_allocated), int(first.bits_stored),
                        int(first.high_bit), bool(first.pixel_representation), [float(s.slope) for s in slices], [float(s.inter) for s in slices],

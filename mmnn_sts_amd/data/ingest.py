@@ -5,6 +5,7 @@ every all-zero slice dropped along each axis, Resize((64,64,64)), T1 / T2 stacke
 the file's voxels in their on-disk type.  The host only uploads bytes (pinned, non-blocking) and enqueues; it never waits.
 
     upload(volume, device)                          host volume (NiftiImage, DicomSeries or ndarray) -> DeviceVolume
+    stage_mask(scan, mask, device)                  host mask of any source -> DeviceVolume, or Staged{Contours,Frames} that wait for their kernel
     decode_series(series, device)                   a sorted DICOM series -> DeviceVolume: the slices' bytes decoded on device (mmnn_decode_slices)
     rasterize_contours(contours, scan, device)      the contours of an RTSTRUCT ROI -> uint8 0 / 1 on the scan's grid (mmnn_rasterize_contours)
     unpack_frames(frames, scan, device)             the frames of a DICOM SEG segment -> uint8 0 / 1 on the scan's grid, or 0 / 255 on the
@@ -159,16 +160,43 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
     return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
 
 
+def _default_device(out):                    # where a call that names no device works
+    return out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _mask_out(out, n, dev, who):
+    """`out`, checked to be what `who` can write `n` mask voxels to on `dev`; a new tensor when None."""
+    if out is not None and not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n):
+        raise ValueError(f"{who}: out must be {n} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    return torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
+
+
 @dataclass
 class StagedContours:
     """The three arrays of `rtstruct.to_scan_index` in one device buffer: a contour mask between its upload and its rasterisation
-    (`collate_volumes` issues every upload of a batch before its first kernel)."""
+    (`collate_volumes` issues every upload first).  Like `StagedFrames` it says whether it is `on_scan` and runs its kernel in `to_volume`."""
     staged: torch.Tensor
     at_records: int                          # byte offsets of the contour records and of slice_first behind the points
     at_slices: int
     n_contours: int
     n_points: int
     slices: int
+    on_scan = True                           # contours are born on the scan's grid
+    no_index_map = "a contour mask is rasterised onto the scan's own grid; it takes no index_map"
+
+    def to_volume(self, scan, out: Optional[torch.Tensor] = None) -> DeviceVolume:
+        x, y, z = (int(v) for v in scan.shape)
+        dev = self.staged.device
+        if self.slices != z:
+            raise ValueError(f"rasterize_contours: slice_first has {self.slices + 1} entries, a scan of {z} slices needs {z + 1}")
+        out = _mask_out(out, x * y * z, dev, "rasterize_contours")
+        desc = _lib.RasterizeDesc(x, y, z, self.n_contours, self.n_points)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            p = self.staged.data_ptr()
+            _lib.check(_lib.lib().mmnn_rasterize_contours(ctypes.byref(desc), p, p + self.at_records, p + self.at_slices, out.data_ptr(), stream),
+                       "mmnn_rasterize_contours")
+        return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, getattr(scan, "affine", None))
 
 
 def stage_contours(contours, scan, device, roi=None) -> StagedContours:
@@ -176,8 +204,7 @@ def stage_contours(contours, scan, device, roi=None) -> StagedContours:
     arrays and one non-blocking copy.  `contours`: a ContourSet (`roi` names the ROI to take; None: its only one), placed on the
     scan's grid by `rtstruct.to_scan_index`, or the (points, contours, slice_first) arrays themselves."""
     if isinstance(contours, ContourSet):
-        if not is_dicom(scan):
-            raise ConfigurationError(f"an RTSTRUCT mask ({contours.path}) beside a NIfTI scan is outside the path: both come from one format")
+        _placed(scan, contours, named=True)
         contours = rtstruct.to_scan_index(rtstruct.select(contours, roi), scan.shape, scan.affine)
     points, records, slice_first = (np.ascontiguousarray(a, dtype=t) for a, t in zip(contours[:3], (np.float64, np.int32, np.int32)))
     if points.ndim != 2 or points.shape[1] != 2 or records.ndim != 2 or records.shape[1] != 2 or slice_first.ndim != 1 or slice_first.size < 2:
@@ -198,25 +225,9 @@ def rasterize_contours(contours, scan, device=None, roi=None, out: Optional[torc
     pinned staging buffer, one non-blocking copy and one launch on the current stream.  `device`: None is `out`'s, else the current
     one.  `out`: a contiguous uint8 CUDA tensor of x*y*z elements to write, allocated when None.  The result is a mask of type 2,
     slope 1, inter 0 with the scan's affine -- on the scan's grid by construction, so it is neither resampled nor thresholded."""
-    x, y, z = (int(v) for v in scan.shape)
     if not isinstance(contours, StagedContours):
-        if device is None:
-            device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
-        contours = stage_contours(contours, scan, device, roi)
-    dev = contours.staged.device
-    if contours.slices != z:
-        raise ValueError(f"rasterize_contours: slice_first has {contours.slices + 1} entries, a scan of {z} slices needs {z + 1}")
-    if out is None:
-        out = torch.empty(x * y * z, dtype=torch.uint8, device=dev)
-    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x * y * z):
-        raise ValueError(f"rasterize_contours: out must be {x * y * z} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-    desc = _lib.RasterizeDesc(x, y, z, contours.n_contours, contours.n_points)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        p = contours.staged.data_ptr()
-        _lib.check(_lib.lib().mmnn_rasterize_contours(ctypes.byref(desc), p, p + contours.at_records, p + contours.at_slices, out.data_ptr(), stream),
-                   "mmnn_rasterize_contours")
-    return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, getattr(scan, "affine", None))
+        contours = stage_contours(contours, scan, _default_device(out) if device is None else device, roi)
+    return contours.to_volume(scan, out)
 
 
 @dataclass
@@ -234,6 +245,19 @@ class StagedFrames:
     on_scan: bool
     path: str = ""
     from_dicom: bool = True
+    no_index_map = "a SEG mask on the scan's own grid takes no index_map"
+
+    def to_volume(self, scan=None, out: Optional[torch.Tensor] = None) -> DeviceVolume:
+        dev = self.staged.device
+        x, y, z = self.shape
+        out = _mask_out(out, x * y * z, dev, "unpack_frames")
+        desc = _lib.UnpackFramesDesc(x, y, z, self.n_frames, self.n_refs, self.one)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            p = self.staged.data_ptr()
+            _lib.check(_lib.lib().mmnn_unpack_frames(ctypes.byref(desc), p + self.at_bits, p, p + self.at_slices, out.data_ptr(), stream),
+                       "mmnn_unpack_frames")
+        return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, self.affine, from_dicom=not self.on_scan)
 
 
 def stage_frames(frames, scan, device, roi=None) -> StagedFrames:
@@ -241,8 +265,7 @@ def stage_frames(frames, scan, device, roi=None) -> StagedFrames:
     PixelData bytes as the file holds them) and one non-blocking copy.  `frames`: a FrameSet (`roi` names the segment to take; None:
     its only one), placed by `seg.to_scan`, or the arrays themselves, (bits, n_frames, refs, slice_first[, one]), for the scan's grid."""
     if isinstance(frames, FrameSet):
-        if not is_dicom(scan):
-            raise ConfigurationError(f"a DICOM SEG mask ({frames.path}) beside a NIfTI scan is outside the path: both come from one format")
+        _placed(scan, frames, named=True)
         if frames.header_only or frames.frame is None:
             raise ValueError(f"unpack_frames: {frames.path} was read with header_only: it holds no PixelData")
         place = seg.to_scan(seg.select(frames, roi), scan.shape, scan.affine)
@@ -274,22 +297,17 @@ def unpack_frames(frames, scan, device=None, roi=None, out: Optional[torch.Tenso
     non-blocking copy and one launch on the current stream.  `device`: None is `out`'s, else the current one.  `out`: a contiguous
     uint8 CUDA tensor of the grid's x*y*z elements to write, allocated when None."""
     if not isinstance(frames, StagedFrames):
-        if device is None:
-            device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
-        frames = stage_frames(frames, scan, device, roi)
-    dev = frames.staged.device
-    x, y, z = frames.shape
-    if out is None:
-        out = torch.empty(x * y * z, dtype=torch.uint8, device=dev)
-    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x * y * z):
-        raise ValueError(f"unpack_frames: out must be {x * y * z} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-    desc = _lib.UnpackFramesDesc(x, y, z, frames.n_frames, frames.n_refs, frames.one)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        p = frames.staged.data_ptr()
-        _lib.check(_lib.lib().mmnn_unpack_frames(ctypes.byref(desc), p + frames.at_bits, p, p + frames.at_slices, out.data_ptr(), stream),
-                   "mmnn_unpack_frames")
-    return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, frames.affine, from_dicom=not frames.on_scan)
+        frames = stage_frames(frames, scan, _default_device(out) if device is None else device, roi)
+    return frames.to_volume(scan, out)
+
+
+def stage_mask(scan, mask, device):
+    """A mask of any source beside `scan` on the device: contours and frames staged (`to_volume` runs their kernel), a volume uploaded."""
+    if isinstance(mask, ContourSet):
+        return stage_contours(mask, scan, device)
+    if isinstance(mask, FrameSet):
+        return stage_frames(mask, scan, device)
+    return mask if isinstance(mask, (StagedContours, StagedFrames)) else upload(mask, device)
 
 
 def workspace_bytes(x: int, y: int, z: int) -> int:
@@ -309,13 +327,10 @@ def resample_mask(mask, scan_shape, index_map, threshold: float = 0.5, out: Opti
     if t.shape != (3, 4):
         raise ValueError(f"resample_mask: index_map must be (3, 4), got {t.shape}")
     if not isinstance(mask, DeviceVolume):
-        mask = upload(mask, out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+        mask = upload(mask, _default_device(out))
     dev = mask.data.device
     if min(x, y, z) >= 1:
-        if out is None:
-            out = torch.empty(x * y * z, dtype=torch.uint8, device=dev)
-        elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x * y * z):
-            raise ValueError(f"resample_mask: out must be {x * y * z} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        out = _mask_out(out, x * y * z, dev, "resample_mask")
     mx, my, mz = mask.shape
     desc = _lib.ResampleMaskDesc(x, y, z, mx, my, mz, mask.datatype, mask.slope, mask.inter, (ctypes.c_double * 12)(*t.reshape(-1)), float(threshold))
     with torch.cuda.device(dev):
@@ -341,18 +356,10 @@ def mask_index_map(scan, mask, mode: str = "auto"):
     anything with `.shape` and `.affine`.  Raises ConfigurationError where `mode` or the missing geometry forbids a needed resample."""
     if mode not in MASK_RESAMPLE_MODES:
         raise ConfigurationError(f"mask_resample {mode!r} is none of {MASK_RESAMPLE_MODES}")
-    if isinstance(mask, (ContourSet, StagedContours)):           # rasterised onto the scan's own grid: nothing to resample
-        if not is_dicom(scan):
-            raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
-        return None
-    if isinstance(mask, FrameSet):
-        if not is_dicom(scan):
-            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
-        mask = seg.to_scan(mask, scan.shape, scan.affine)
-    if isinstance(mask, (StagedFrames, seg.Placement)):
-        if not is_dicom(scan):
-            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
-        if mask.on_scan:                     # unpacked onto the scan's own grid: nothing to resample
+    if _placed(scan, mask):
+        if isinstance(mask, FrameSet):       # still on the host: placed here as `stage_frames` will place it
+            mask = seg.to_scan(mask, scan.shape, scan.affine)
+        if getattr(mask, "on_scan", True):   # rasterised or unpacked onto the scan's own grid (a ContourSet always is): nothing to resample
             return None
         if mode == "never":
             raise ConfigurationError(f"scan extent {tuple(scan.shape)} ({getattr(scan, 'path', '') or 'scan'}), SEG extent {tuple(mask.shape)} "
@@ -369,6 +376,16 @@ def mask_index_map(scan, mask, mode: str = "auto"):
     if mode == "never":
         raise ConfigurationError(f"scan extent {tuple(scan.shape)} differs from the mask's {tuple(mask.shape)} and mask_resample is 'never'")
     return nifti.index_map(scan, mask)
+
+
+def _placed(scan, mask, named=False) -> bool:
+    """Whether `mask` is contours or frames, placed against its scan's geometry, rather than a volume with a grid of its own.  Beside
+    a scan that is no DICOM series they are refused here (`named`: with their file)."""
+    rs, sg = "an RTSTRUCT mask", "a DICOM SEG mask"
+    what = {ContourSet: rs, StagedContours: rs, FrameSet: sg, StagedFrames: sg, seg.Placement: sg}.get(type(mask))
+    if what and not is_dicom(scan):
+        raise ConfigurationError(f"{what}{f' ({mask.path})' if named else ''} beside a NIfTI scan is outside the path: both come from one format")
+    return what is not None
 
 
 def is_dicom(volume) -> bool:
@@ -402,22 +419,13 @@ def prepare_pair(scan, mask, dev, index_map=None, threshold: Optional[float] = N
     host, rasterise an RTSTRUCT mask, unpack a SEG mask, resample a mask drawn on another grid (binarised at `threshold`; None: 0.5, or
     128 behind a DICOM scan).  Returns (scan, mask), two DeviceVolumes on one grid.  The rules are `ingest_volume`'s."""
     scan = upload(scan, dev)
-    drawn = isinstance(mask, (ContourSet, StagedContours))
-    if isinstance(mask, (FrameSet, StagedFrames)):
-        if not is_dicom(scan):
-            raise ConfigurationError("a DICOM SEG mask beside a NIfTI scan is outside the path: both come from one format")
-        mask = unpack_frames(mask, scan, dev)
-        drawn = not mask.from_dicom          # on the scan's grid: the voxelwise path; on its own: a DICOM mask volume like a series'
+    drawn = _placed(scan, mask)
+    mask = stage_mask(scan, mask, dev)
+    if drawn:
+        drawn = mask.on_scan                 # on the scan's grid: the voxelwise path; on its own: a DICOM mask volume like a series'
         if drawn and index_map is not None:
-            raise ValueError(f"{what}: a SEG mask on the scan's own grid takes no index_map")
-    elif drawn:
-        if index_map is not None:
-            raise ValueError(f"{what}: a contour mask is rasterised onto the scan's own grid; it takes no index_map")
-        if not is_dicom(scan):
-            raise ConfigurationError("an RTSTRUCT mask beside a NIfTI scan is outside the path: both come from one format")
-        mask = rasterize_contours(mask, scan, dev)
-    else:
-        mask = upload(mask, dev)
+            raise ValueError(f"{what}: {mask.no_index_map}")
+        mask = mask.to_volume(scan)
     if threshold is None:
         threshold = default_threshold(scan)
     if index_map is None and not drawn and (is_dicom(scan) or is_dicom(mask)):
@@ -515,14 +523,6 @@ def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor,
     return out
 
 
-def _upload_mask(scan, mask, device):
-    if isinstance(mask, ContourSet):
-        return stage_contours(mask, scan, device)
-    if isinstance(mask, FrameSet):
-        return stage_frames(mask, scan, device)
-    return upload(mask, device)
-
-
 def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
                     mask_threshold: Optional[float] = None, keep_workspaces: bool = False):
     """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
@@ -537,7 +537,7 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
     device = torch.device(device)
-    up = [[(upload(s, device), _upload_mask(s, m, device)) for s, m in p] for p in patients]
+    up = [[(upload(s, device), stage_mask(s, m, device)) for s, m in p] for p in patients]
     maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     batch = torch.empty((n, c, SIZE, SIZE, SIZE), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)

@@ -1,10 +1,10 @@
-"""A minimal RT Structure Set reader (numpy, mmap and struct only, like `dicom.py`, whose element decoding it reuses): the planar contours
+"""A minimal RT Structure Set reader (numpy only, on `dicom.py`'s file opener, nested data-set walk and value helpers): the planar contours
 of the regions of interest a contouring workstation exports, and their mapping onto a scan's voxel grid for the device rasteriser
 (`mmnn_sts_amd.data.ingest.rasterize_contours`, `mmnn_rasterize_contours`).  The host parses the file and moves the contour points into
 the scan's index space; it fills no voxel.
 
 An RTSTRUCT file is a part-10 file of SOP class 1.2.840.10008.5.1.4.1.1.481.3 whose data set nests sequences, which `dicom.read_file`
-skips and this walk descends into:
+skips and `dicom.walk` descends into (`ENTERED`, keeping the elements in `KEPT`):
 
     StructureSetROISequence (3006,0020)   per ROI: ROINumber (3006,0022), ReferencedFrameOfReferenceUID (3006,0024), ROIName (3006,0026)
     ROIContourSequence (3006,0039)        per ROI: ReferencedROINumber (3006,0084) and ContourSequence (3006,0040), per contour:
@@ -24,15 +24,13 @@ pinned to the standard's element layout, to the even-odd rule stated above `mmnn
 twin (`synth_dicom.from_nifti_tree(..., mask_format="rtstruct")` must give the same device batch as the NIfTI tree, bit for bit).
 """
 import logging
-import mmap
-import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 import numpy as np
 
 from ..exceptions.exceptions import ConfigurationError
-from .dicom import ITEM, ITEM_END, MAX_DEPTH, SEQUENCE_END, UNDEFINED, NotDicomError, _check_syntax, _element, _refuse, _skip_sequence, _transfer_syntax
+from .dicom import _check_syntax, _integer, _refuse, _text, match_name, part10, walk
 
 logger = logging.getLogger(__name__)
 
@@ -61,72 +59,6 @@ class ContourSet:
     header_only: bool = False
 
 
-def _text(buf, value):
-    voff, length = value
-    return bytes(buf[voff:voff + length]).decode("latin-1").strip(" \0")
-
-
-def _integer(buf, value, what, path):
-    text = _text(buf, value)
-    try:
-        return int(float(text))
-    except ValueError:
-        _refuse(path, f"malformed: {what} holds {text[:32]!r}")
-
-
-def _data_set(buf, off, end, explicit, path, depth, stop_after=None):
-    """The elements of one data set (the file's, or an item's) from `off`: {tag: (value offset, length)} for the KEPT tags and
-    {tag: [item, ...]} for the ENTERED sequences.  `end`: where it ends, or None for an item of undefined length (closed by its
-    delimiter).  Returns (elements, offset behind the data set)."""
-    if depth > MAX_DEPTH:
-        _refuse(path, f"malformed: sequences nested deeper than {MAX_DEPTH}")
-    found = {}
-    while end is None or off < end:
-        tag, vr, length, voff = _element(buf, off, explicit, path)
-        if tag == ITEM_END and end is None:
-            return found, voff
-        if tag[0] == 0xFFFE:
-            _refuse(path, f"malformed: item tag ({tag[0]:04X},{tag[1]:04X}) at byte {off} outside a sequence")
-        if stop_after is not None and tag > stop_after:
-            break
-        inner_explicit = explicit and vr != "UN"      # the content of a UN element of undefined length is implicit VR (PS3.5 6.2.2)
-        if tag in ENTERED and (vr in (None, "SQ") or (vr == "UN" and length == UNDEFINED)):
-            found[tag], off = _items(buf, voff, length, inner_explicit, path, depth + 1)
-            continue
-        if length == UNDEFINED:
-            off = _skip_sequence(buf, voff, inner_explicit, path, depth)
-            continue
-        if voff + length > (len(buf) if end is None else end):
-            _refuse(path, f"malformed: element ({tag[0]:04X},{tag[1]:04X}) at byte {off} declares {length} bytes, "
-                          f"{(len(buf) if end is None else end) - voff} are left")
-        if tag in KEPT:
-            found[tag] = (voff, length)
-        off = voff + length
-    return found, off
-
-
-def _items(buf, off, length, explicit, path, depth):
-    """The items of a sequence whose value starts at `off`: ([elements of each item], offset behind the sequence)."""
-    end = None if length == UNDEFINED else off + length
-    if end is not None and end > len(buf):
-        _refuse(path, f"malformed: a sequence at byte {off} declares {length} bytes, {len(buf) - off} are left")
-    items = []
-    while end is None or off < end:
-        tag, _, ilen, voff = _element(buf, off, explicit, path)
-        if tag == SEQUENCE_END and end is None:
-            return items, voff
-        if tag != ITEM:
-            _refuse(path, f"malformed: ({tag[0]:04X},{tag[1]:04X}) at byte {off} where an item of a sequence was expected")
-        if ilen == UNDEFINED:
-            found, off = _data_set(buf, voff, None, explicit, path, depth)
-        else:
-            if voff + ilen > (len(buf) if end is None else end):
-                _refuse(path, f"malformed: an item at byte {off} declares {ilen} bytes, {(len(buf) if end is None else end) - voff} are left")
-            found, off = _data_set(buf, voff, voff + ilen, explicit, path, depth)
-        items.append(found)
-    return items, off
-
-
 def _contour(buf, item, path, roi_name, index):
     """(points or None, reason it was dropped or None) of one item of a ContourSequence."""
     kind = _text(buf, item[CONTOUR_GEOMETRIC_TYPE]).upper() if CONTOUR_GEOMETRIC_TYPE in item else ""
@@ -153,16 +85,10 @@ def _contour(buf, item, path, roi_name, index):
 
 def read(path, header_only=False) -> ContourSet:
     """Parse an RTSTRUCT file.  With `header_only` the walk stops behind StructureSetROISequence: the ROI names alone."""
-    path = str(path)
-    size = os.path.getsize(path)
-    if size < 132:
-        raise NotDicomError(f"{path}: missing magic: {size} bytes, shorter than a preamble (not a DICOM part-10 file)")
-    with open(path, "rb") as fh:
-        buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-    try:
-        syntax, off = _transfer_syntax(buf, path)
-        explicit = _check_syntax(syntax, path)
-        top, _ = _data_set(buf, off, size, explicit, path, 0, STRUCTURE_SET_ROI_SEQUENCE if header_only else None)
+    with part10(path) as f:
+        path, buf = f.path, f.buf
+        explicit = _check_syntax(f.syntax, path)
+        top, _ = walk(buf, f.off, f.size, explicit, path, KEPT, ENTERED, stop_after=STRUCTURE_SET_ROI_SEQUENCE if header_only else None)
         sop = _text(buf, top[SOP_CLASS_UID]) if SOP_CLASS_UID in top else None
         if sop != RT_STRUCTURE_SET_STORAGE:
             _refuse(path, f"SOPClassUID {sop} is not RT Structure Set Storage ({RT_STRUCTURE_SET_STORAGE})"
@@ -196,27 +122,11 @@ def read(path, header_only=False) -> ContourSet:
                 else:
                     cs.contours[r].append(points)
         return cs
-    finally:
-        buf.close()
-
-
-def _listed(names):
-    return ", ".join(repr(n) for n in names)
 
 
 def resolve(contour_set: ContourSet, roi) -> int:
     """The index of the ROI that `roi` (`Data: mask_roi`) names: exact and case-insensitive; None takes the only ROI."""
-    names = contour_set.names
-    if roi is None:
-        if len(names) == 1:
-            return 0
-        raise ConfigurationError(f"{contour_set.path} holds {len(names)} ROIs ({_listed(names)}): name one with Data.mask_roi")
-    hits = [i for i, n in enumerate(names) if n.lower() == str(roi).lower()]
-    if not hits:
-        raise ConfigurationError(f"{contour_set.path} has no ROI named {roi!r}; its ROIs are {_listed(names)}")
-    if len(hits) > 1:
-        raise ConfigurationError(f"{contour_set.path} has {len(hits)} ROIs named {roi!r} ({_listed(names)})")
-    return hits[0]
+    return match_name(contour_set.path, contour_set.names, roi, "ROI", "named")
 
 
 def select(contour_set: ContourSet, roi=None) -> ContourSet:

@@ -1,6 +1,6 @@
-"""A minimal DICOM Segmentation (SEG) reader (numpy, mmap and struct only, like `dicom.py`, whose element decoding it reuses, as
-`rtstruct.py` does): the bit-packed frames of a BINARY segmentation, which segment and which plane each of them belongs to, and their
-placement against a scan's voxel grid for the device unpacker (`mmnn_sts_amd.data.ingest.unpack_frames`, `mmnn_unpack_frames`).  The
+"""A minimal DICOM Segmentation (SEG) reader (numpy and struct only, on `dicom.py`'s file opener, nested data-set walk and value
+helpers, as `rtstruct.py` is): the bit-packed frames of a BINARY segmentation, which segment and which plane each of them belongs to,
+and their placement against a scan's voxel grid for the device unpacker (`mmnn_sts_amd.data.ingest.unpack_frames`, `mmnn_unpack_frames`).  The
 host parses the file and places planes; it never looks at a bit of PixelData.
 
 A SEG file is a part-10 file of SOP class 1.2.840.10008.5.1.4.1.1.66.4 (PS3.3 A.51, C.8.20), an enhanced multi-frame object:
@@ -33,8 +33,6 @@ multi-frame *scans*, FRACTIONAL and LABELMAP SEG and compressed syntaxes stay ou
 """
 import dataclasses
 import logging
-import mmap
-import os
 import struct
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -42,8 +40,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from ..exceptions.exceptions import ConfigurationError
-from .dicom import (ITEM, ITEM_END, MAX_DEPTH, PIXEL_DATA, SEQUENCE_END, UNDEFINED, NotDicomError, _check_syntax, _element, _numbers, _refuse,
-                    _skip_sequence, _transfer_syntax)
+from .dicom import (PIXEL_DATA, UNDEFINED, _check_syntax, _element, _floats, _integer, _refuse, _skip_sequence, _text, lps_to_ras, match_name,
+                    part10, walk)
 
 logger = logging.getLogger(__name__)
 
@@ -106,105 +104,11 @@ class Placement:
     from_dicom: bool = True
 
 
-def _text(buf, value):
-    voff, length = value
-    return bytes(buf[voff:voff + length]).decode("latin-1").strip(" \0")
-
-
-def _floats(buf, value, what, count, path):
-    voff, length = value
-    raw = bytes(buf[voff:voff + length])
-    try:
-        v = _numbers(raw)
-    except ValueError:
-        _refuse(path, f"malformed: {what} holds {raw[:32]!r}")
-    if count is not None and len(v) != count:
-        _refuse(path, f"malformed: {what} holds {len(v)} values, {count} expected")
-    if not np.isfinite(v).all():
-        _refuse(path, f"malformed: {what} holds a non-finite number")
-    return v
-
-
-def _integer(buf, value, what, path, vr):
-    voff, length = value
-    if vr == "US":
-        if length < 2:
-            _refuse(path, f"malformed: {what} is empty")
-        return struct.unpack_from("<H", buf, voff)[0]
-    text = _text(buf, value)
-    try:
-        return int(float(text))
-    except ValueError:
-        _refuse(path, f"malformed: {what} holds {text[:32]!r}")
-
-
-def _data_set(buf, off, end, explicit, path, depth, top=False):
-    """The elements of one data set (the file's, or an item's) from `off`: {tag: (value offset, length)} for the KEPT tags and
-    {tag: [item, ...]} for the ENTERED sequences.  `end`: where it ends, or None for an item of undefined length.  At the top level
-    the walk stops at PixelData, whose (value offset, declared length) it records without looking at the value."""
-    if depth > MAX_DEPTH:
-        _refuse(path, f"malformed: sequences nested deeper than {MAX_DEPTH}")
-    found = {}
-    while end is None or off < end:
-        tag, vr, length, voff = _element(buf, off, explicit, path)
-        if tag == ITEM_END and end is None:
-            return found, voff
-        if tag[0] == 0xFFFE:
-            _refuse(path, f"malformed: item tag ({tag[0]:04X},{tag[1]:04X}) at byte {off} outside a sequence")
-        if top and tag >= PIXEL_DATA:
-            if tag == PIXEL_DATA:
-                found[tag] = (voff, length)
-            break
-        inner_explicit = explicit and vr != "UN"      # the content of a UN element of undefined length is implicit VR (PS3.5 6.2.2)
-        if tag in ENTERED and (vr in (None, "SQ") or (vr == "UN" and length == UNDEFINED)):
-            found[tag], off = _items(buf, voff, length, inner_explicit, path, depth + 1)
-            continue
-        if length == UNDEFINED:
-            off = _skip_sequence(buf, voff, inner_explicit, path, depth)
-            continue
-        limit = len(buf) if end is None else end
-        if voff + length > limit:
-            _refuse(path, f"malformed: element ({tag[0]:04X},{tag[1]:04X}) at byte {off} declares {length} bytes, {limit - voff} are left")
-        if tag in KEPT:
-            found[tag] = (voff, length)
-        off = voff + length
-    return found, off
-
-
-def _items(buf, off, length, explicit, path, depth):
-    """The items of a sequence whose value starts at `off`: ([elements of each item], offset behind the sequence)."""
-    end = None if length == UNDEFINED else off + length
-    if end is not None and end > len(buf):
-        _refuse(path, f"malformed: a sequence at byte {off} declares {length} bytes, {len(buf) - off} are left")
-    items = []
-    while end is None or off < end:
-        tag, _, ilen, voff = _element(buf, off, explicit, path)
-        if tag == SEQUENCE_END and end is None:
-            return items, voff
-        if tag != ITEM:
-            _refuse(path, f"malformed: ({tag[0]:04X},{tag[1]:04X}) at byte {off} where an item of a sequence was expected")
-        if ilen == UNDEFINED:
-            found, off = _data_set(buf, voff, None, explicit, path, depth)
-        else:
-            limit = len(buf) if end is None else end
-            if voff + ilen > limit:
-                _refuse(path, f"malformed: an item at byte {off} declares {ilen} bytes, {limit - voff} are left")
-            found, off = _data_set(buf, voff, voff + ilen, explicit, path, depth)
-        items.append(found)
-    return items, off
-
-
 def sop_class_of(path) -> Optional[str]:
     """SOPClassUID (0008,0016) of a part-10 file from its first elements alone, or None (NotDicomError without the magic).  What the
     datasets tell a SEG file from an image or an RTSTRUCT file by, before any reader validates it."""
-    path = str(path)
-    size = os.path.getsize(path)
-    if size < 132:
-        raise NotDicomError(f"{path}: missing magic: {size} bytes, shorter than a preamble (not a DICOM part-10 file)")
-    with open(path, "rb") as fh:
-        buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-    try:
-        syntax, off = _transfer_syntax(buf, path)
+    with part10(path) as f:
+        path, buf, size, syntax, off = f.path, f.buf, f.size, f.syntax, f.off
         explicit = syntax != "1.2.840.10008.1.2"      # (every syntax but implicit VR little endian is explicit; only the tag order matters here)
         if syntax == "1.2.840.10008.1.2.2":           # big endian: the data set cannot be walked little endian; the meta group names the class too
             return _media_storage_class(buf, path)
@@ -219,8 +123,6 @@ def sop_class_of(path) -> Optional[str]:
             else:
                 off = voff + length
         return _media_storage_class(buf, path)
-    finally:
-        buf.close()
 
 
 def _media_storage_class(buf, path):
@@ -246,20 +148,13 @@ def _group(buf, item, tag, inner, what, count, path):
 
 def read(path, header_only=False) -> FrameSet:
     """Parse a SEG file.  With `header_only` the walk stops in front of PixelData: `frame` stays None and its length is not checked."""
-    path = str(path)
-    size = os.path.getsize(path)
-    if size < 132:
-        raise NotDicomError(f"{path}: missing magic: {size} bytes, shorter than a preamble (not a DICOM part-10 file)")
-    with open(path, "rb") as fh:
-        buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-    keep = False
-    try:
-        syntax, off = _transfer_syntax(buf, path)
+    with part10(path) as part:
+        path, buf, size, syntax = part.path, part.buf, part.size, part.syntax
         if syntax == "1.2.840.10008.1.2.5":
             _refuse(path, f"transfer syntax {syntax} (RLE lossless, an encapsulated, compressed syntax) is outside the path: only uncompressed "
                           "little endian files are read; decompress the file first")
         explicit = _check_syntax(syntax, path)
-        top, _ = _data_set(buf, off, size, explicit, path, 0, top=True)
+        top, _ = walk(buf, part.off, size, explicit, path, KEPT, ENTERED, pixel_data=True)
         sop = _text(buf, top[SOP_CLASS_UID]) if SOP_CLASS_UID in top else None
         if sop != SEGMENTATION_STORAGE:
             _refuse(path, f"SOPClassUID {sop} is not Segmentation Storage ({SEGMENTATION_STORAGE})")
@@ -334,30 +229,13 @@ def read(path, header_only=False) -> FrameSet:
         if have < need:
             _refuse(path, f"truncated: {have} bytes of PixelData, {need} expected for {n_frames} frames of {rows} x {columns} bits")
         fs.frame = np.frombuffer(buf, dtype=np.uint8, count=need, offset=voff)
-        keep = True
+        part.keep = True
         return fs
-    finally:
-        if not keep:
-            buf.close()
-
-
-def _listed(names):
-    return ", ".join(repr(n) for n in names)
 
 
 def resolve(frame_set: FrameSet, roi) -> int:
     """The index of the segment that `roi` (`Data: mask_roi`) names: SegmentLabel, exact and case-insensitive; None takes the only one."""
-    names = frame_set.names
-    if roi is None:
-        if len(names) == 1:
-            return 0
-        raise ConfigurationError(f"{frame_set.path} holds {len(names)} segments ({_listed(names)}): name one with Data.mask_roi")
-    hits = [i for i, n in enumerate(names) if n.lower() == str(roi).lower()]
-    if not hits:
-        raise ConfigurationError(f"{frame_set.path} has no segment labelled {roi!r}; its segments are {_listed(names)}")
-    if len(hits) > 1:
-        raise ConfigurationError(f"{frame_set.path} has {len(hits)} segments labelled {roi!r} ({_listed(names)})")
-    return hits[0]
+    return match_name(frame_set.path, frame_set.names, roi, "segment", "labelled")
 
 
 def select(frame_set: FrameSet, roi=None) -> FrameSet:
@@ -367,13 +245,6 @@ def select(frame_set: FrameSet, roi=None) -> FrameSet:
     if len(frame_set.names) == 1:
         return frame_set
     return dataclasses.replace(frame_set, names=[frame_set.names[i]], segment_of=np.where(frame_set.segment_of == i, 0, -1).astype(np.int32))
-
-
-def _lps_to_ras(lps):
-    affine = lps.copy()
-    affine[:2, :] *= -1.0                    # LPS -> RAS, as dicom.read_series forms a series' affine
-    affine += 0.0                            # (no negative zeros)
-    return affine
 
 
 def _on_scan(fs, chosen, shape, m):
@@ -479,4 +350,4 @@ def to_scan(frames: FrameSet, scan_shape, scan_affine) -> Placement:
     lps = np.eye(4, dtype=np.float64)
     lps[:3, 0], lps[:3, 1], lps[:3, 2], lps[:3, 3] = r * spacing[1], c * spacing[0], v, p0 - v        # (slice 0 is the empty one below the first)
     refs, slice_first = _arrays(index.astype(np.int64) + 1, chosen, top + 3)
-    return Placement((int(fs.columns), int(fs.rows), top + 3), _lps_to_ras(lps), refs, slice_first, 255, False, 0, path)
+    return Placement((int(fs.columns), int(fs.rows), top + 3), lps_to_ras(lps), refs, slice_first, 255, False, 0, path)

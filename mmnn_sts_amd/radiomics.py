@@ -178,7 +178,7 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
     for b0 in range(0, len(patients), max(1, int(batch))):
         chunk = patients[b0:b0 + max(1, int(batch))]
         raws = [_volumes_of(dataset, p) for p in chunk]
-        up = [[(ingest.upload(s, dev), ingest._upload_mask(s, m, dev)) for s, m in vols] for vols in raws]
+        up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
         res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold) for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]

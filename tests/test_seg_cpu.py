@@ -324,6 +324,50 @@ def test_mask_directories_that_mix_are_refused(tree, tmp_path):
     assert rtstruct_in(os.path.join(patient, "image")) is None
 
 
+def test_one_scan_of_a_mask_directory_classifies_it_and_refuses_mixtures(tmp_path, monkeypatch):
+    """The datasets look at a mask/ directory once: every file in it is classified by one `seg.sop_class_of` call per dataset, whatever
+    it turns out to hold, and the refusals that used to hang on the order of two scans come from that one."""
+    from mmnn_sts_amd.data import dicom, rtstruct
+    from mmnn_sts_amd.data.ImageDatasets import ImageSurvivalDataset
+    synth_nifti.write_tree(tmp_path / "nifti", n_patients=1, seed=4, extent=((6, 6), (6, 6), (4, 4)), modalities=("t1",))
+    trees = {f: synth_dicom.from_nifti_tree(tmp_path / "nifti", tmp_path / f, mask_format=f) for f in ("series", "rtstruct", "seg")}
+    calls = {}
+
+    def counted(path, inner=seg.sop_class_of):
+        calls[os.path.realpath(str(path))] = calls.get(os.path.realpath(str(path)), 0) + 1
+        return inner(path)
+
+    monkeypatch.setattr(seg, "sop_class_of", counted)
+
+    def construct(tree):
+        calls.clear()
+        try:
+            return ImageSurvivalDataset(os.path.join(tree["image_loc"], "t1"), tree["data_loc"], tree["key_loc"])
+        finally:
+            patient = os.path.join(tree["image_loc"], "t1", os.listdir(os.path.join(tree["image_loc"], "t1"))[0])
+            inside = [os.path.realpath(os.path.join(d, f)) for d, _, files in os.walk(os.path.join(patient, "mask")) for f in files]
+            assert calls == {p: 1 for p in inside}, calls          # each file of mask/ once, no file of image/ at all
+
+    for name, kind in (("series", dicom.DicomSeries), ("rtstruct", rtstruct.ContourSet), ("seg", seg.FrameSet)):
+        ds = construct(trees[name])
+        scan, mask = ds[0][0].volumes[0]
+        assert isinstance(scan, dicom.DicomSeries) and type(mask) is kind
+        assert max(calls.values()) == 1                           # loading a patient does not look again
+
+    def mask_directory(tree):
+        t1 = os.path.join(tree["image_loc"], "t1")
+        return os.path.join(t1, os.listdir(t1)[0], "mask")
+
+    rs = os.path.join(mask_directory(trees["rtstruct"]), "rtstruct.dcm")
+    shutil.copyfile(rs, os.path.join(mask_directory(trees["seg"]), "rtstruct.dcm"))
+    with pytest.raises(ConfigurationError, match=r"a DICOM SEG file \(seg\.dcm\) beside an RTSTRUCT file \(rtstruct\.dcm\)"):
+        construct(trees["seg"])
+    series = os.path.join(mask_directory(trees["series"]), "series_1")
+    shutil.copyfile(os.path.join(series, sorted(os.listdir(series))[0]), os.path.join(mask_directory(trees["rtstruct"]), "slice.dcm"))
+    with pytest.raises(ConfigurationError, match=r"an RTSTRUCT file \(rtstruct\.dcm\) beside 1 DICOM image file\(s\)"):
+        construct(trees["rtstruct"])
+
+
 def test_a_seg_mask_beside_a_nifti_scan_is_refused(tree):
     from mmnn_sts_amd.data import ingest, nifti
     ds = _dataset(tree, mask_roi="gtv")

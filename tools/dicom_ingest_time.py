@@ -15,46 +15,21 @@ Bytes are the algorithmic HBM traffic computed from the shapes, priced against t
 host's share per volume is reported beside them: parsing the 2 x 48 slice headers and mapping the files, and `decode_series` (the copy
 of the slices into one pinned buffer, the upload and the enqueue) against gunzip + parse + upload of the two .nii.gz files."""
 import argparse
-import ctypes
 import json
 import os
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmnn_sts_amd import _lib  # noqa: E402
 from mmnn_sts_amd.data import dicom, ingest, nifti, synth_dicom  # noqa: E402
+from dicom_timing import best_ms, decode, queued_us  # noqa: E402
 
 HBM_TBS = 6.29
 SHAPE = (512, 512, 48)
 BOX = ((96, 101, 4), (416, 411, 43))
-
-
-def queued_us(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(50_000_000)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / steps
-
-
-def best_ms(fn, repeats=3):
-    out = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        keep = fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t) * 1e3)
-        del keep
-    return round(min(out), 2)
 
 
 def main():
@@ -76,12 +51,12 @@ def main():
         synth_dicom.write_series(os.path.join(d, "mask"), mask * np.uint8(255), affine, seed=2)
         ps = nifti.write(os.path.join(d, "scan.nii.gz"), scan, 0.25, -12.5, affine=affine)
         pm = nifti.write(os.path.join(d, "mask.nii.gz"), mask, affine=affine)
-        host = {"dicom_parse_ms": best_ms(lambda: (dicom.read_series(os.path.join(d, "image")), dicom.read_series(os.path.join(d, "mask")))),
-                "nifti_gunzip_parse_ms": best_ms(lambda: (nifti.read(ps), nifti.read(pm)))}
+        host = {"dicom_parse_ms": best_ms(lambda: (dicom.read_series(os.path.join(d, "image")), dicom.read_series(os.path.join(d, "mask"))), sync=True),
+                "nifti_gunzip_parse_ms": best_ms(lambda: (nifti.read(ps), nifti.read(pm)), sync=True)}
         s_series, m_series = dicom.read_series(os.path.join(d, "image")), dicom.read_series(os.path.join(d, "mask"))
         s_nifti, m_nifti = nifti.read(ps), nifti.read(pm)
-        host["dicom_stage_upload_decode_ms"] = best_ms(lambda: (ingest.upload(s_series, "cuda"), ingest.upload(m_series, "cuda")))
-        host["nifti_upload_ms"] = best_ms(lambda: (ingest.upload(s_nifti, "cuda"), ingest.upload(m_nifti, "cuda")))
+        host["dicom_stage_upload_decode_ms"] = best_ms(lambda: (ingest.upload(s_series, "cuda"), ingest.upload(m_series, "cuda")), sync=True)
+        host["nifti_upload_ms"] = best_ms(lambda: (ingest.upload(s_nifti, "cuda"), ingest.upload(m_nifti, "cuda")), sync=True)
 
         # device: the slices' bytes as `decode_series` stages them, then the calls it makes
         def staged(series):
@@ -96,18 +71,13 @@ def main():
         ws = torch.empty(ingest.workspace_bytes(*SHAPE), dtype=torch.uint8, device="cuda")
         stream = torch.cuda.current_stream().cuda_stream
 
-        def decode(series, pixels, out):
-            desc = _lib.DecodeSlicesDesc(*SHAPE, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed),
-                                         ingest._integer_code(series.bits_allocated, series.signed))
-            _lib.check(_lib.lib().mmnn_decode_slices(ctypes.byref(desc), pixels.data_ptr(), None, out.data_ptr(), stream), "mmnn_decode_slices")
-
         vol_s = ingest.DeviceVolume(out_s, SHAPE, 4, 0.25, -12.5)      # (the decoded scan beside a mask already on its grid)
         vol_m = ingest.DeviceVolume(out_m, SHAPE, 2, 1.0, 0.0, m_series.affine, from_dicom=True)
         nif_s, nif_m = ingest.upload(s_nifti, "cuda"), ingest.upload(m_nifti, "cuda")
 
         def dicom_volume():
-            decode(s_series, pix_s, out_s)
-            decode(m_series, pix_m, out_m)
+            decode(s_series, pix_s, out_s, stream)
+            decode(m_series, pix_m, out_m, stream)
             m = ingest.resample_mask(vol_m, SHAPE, ingest.IDENTITY_MAP, ingest.DICOM_MASK_THRESHOLD, out=resampled)
             ingest.ingest_volume(vol_s, m, plane, ext, ws)
 
@@ -122,7 +92,7 @@ def main():
             nifti_volume()
         torch.cuda.synchronize()
         assert kept_d == ext.cpu().tolist() == [b - a_ for a_, b in zip(*BOX)] and torch.equal(plane_d, plane), (kept_d, ext)
-        decode_us = queued_us(lambda: decode(s_series, pix_s, out_s), a.steps)
+        decode_us = queued_us(lambda: decode(s_series, pix_s, out_s, stream), a.steps)
         dicom_us = queued_us(dicom_volume, a.steps)
         nifti_us = queued_us(nifti_volume, a.steps)
     decode_bytes = voxels * 4                                   # int16 read once, written once

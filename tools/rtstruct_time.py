@@ -21,45 +21,22 @@ The only bound that can be derived is the 12.6 MB the kernel must write, priced 
 share is reported beside them: parsing the file, selecting the ROI and placing its contours on the scan's grid, against parsing the 48
 slice headers of the mask series."""
 import argparse
-import ctypes
 import json
 import os
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmnn_sts_amd import _lib  # noqa: E402
 from mmnn_sts_amd.data import dicom, ingest, rtstruct, synth_dicom  # noqa: E402
+from dicom_timing import best_ms, decode, ingest_passes, queued_us  # noqa: E402
 
 HBM_TBS = 6.29
 SHAPE = (512, 512, 48)
 CENTRE, RADIUS = (262.3, 249.6, 23.4), (163.7, 151.2, 17.8)       # voxels: the ellipsoid meets 36 of the 48 slices
 ROTATING = 24
-
-
-def queued_us(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(50_000_000)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / steps
-
-
-def best_ms(fn, repeats=3):
-    out = []
-    for _ in range(repeats):
-        t = time.perf_counter()
-        keep = fn()
-        out.append((time.perf_counter() - t) * 1e3)
-        del keep
-    return round(min(out), 2)
 
 
 def traced_ellipsoid(affine):
@@ -116,11 +93,6 @@ def main():
         ws = torch.empty(ingest.workspace_bytes(*SHAPE), dtype=torch.uint8, device="cuda")
         turn = [0]
 
-        def decode(series, pixels, out):
-            desc = _lib.DecodeSlicesDesc(*SHAPE, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed),
-                                         ingest._integer_code(series.bits_allocated, series.signed))
-            _lib.check(_lib.lib().mmnn_decode_slices(ctypes.byref(desc), pixels.data_ptr(), None, out.data_ptr(), stream), "mmnn_decode_slices")
-
         def rasterize():
             return ingest.rasterize_contours(staged, vol_s, out=masks[0])
 
@@ -137,7 +109,7 @@ def main():
             m = ingest.rasterize_contours(ingest.stage_contours(arrays, vol_s, "cuda"), vol_s, out=masks[0])
             ingest.ingest_volume(vol_s, m, plane, ext, ws, index_map=None)
 
-        decode(s_series, pix_s, out_s)
+        decode(s_series, pix_s, out_s, stream)
         rasterize()
         torch.cuda.synchronize()
         mask = masks[0].cpu().numpy().reshape(SHAPE, order="F")
@@ -154,24 +126,19 @@ def main():
         drawn = ingest.DeviceVolume(masks[0], SHAPE, 2, 1.0, 0.0, s_series.affine)
 
         def series_mask_path():
-            decode(m_series, pix_m, out_m)
+            decode(m_series, pix_m, out_m, stream)
             m = ingest.resample_mask(vol_m, SHAPE, ingest.IDENTITY_MAP, ingest.DICOM_MASK_THRESHOLD, out=resampled)
             ingest.ingest_volume(vol_s, m, plane, ext, ws, index_map=None)
 
         def bare_ingest():
-            _ingest(vol_s, drawn, plane, ext, ws)
-
-        def _ingest(s, m, plane, ext, ws):
-            desc = _lib.IngestDesc(*SHAPE, s.datatype, m.datatype, s.slope, s.inter, m.slope, m.inter)
-            _lib.check(_lib.lib().mmnn_ingest_volume(ctypes.byref(desc), s.data.data_ptr(), m.data.data_ptr(), plane.data_ptr(), ext.data_ptr(),
-                                                     ws.data_ptr(), stream), "mmnn_ingest_volume")
+            ingest_passes(vol_s, drawn, plane, ext, ws, stream)
 
         def rtstruct_volume():
-            decode(s_series, pix_s, out_s)
+            decode(s_series, pix_s, out_s, stream)
             rtstruct_mask_path()
 
         def series_volume():
-            decode(s_series, pix_s, out_s)
+            decode(s_series, pix_s, out_s, stream)
             series_mask_path()
 
         for _ in range(a.warmup):

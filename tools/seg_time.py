@@ -21,45 +21,22 @@ The bytes the contract moves (the mask written once, the listed frames' bits and
 the 6.29 TB/s measured HBM ceiling.  The host's share is reported beside them: parsing the file, selecting the segment and placing its
 frames against the scan, against parsing the 48 slice headers of the mask series."""
 import argparse
-import ctypes
 import json
 import os
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmnn_sts_amd import _lib  # noqa: E402
 from mmnn_sts_amd.data import dicom, ingest, seg, synth_dicom  # noqa: E402
+from dicom_timing import best_ms, decode, ingest_passes, queued_us  # noqa: E402
 
 HBM_TBS = 6.29
 SHAPE = (512, 512, 48)
 CENTRE, RADIUS = (262.3, 249.6, 23.4), (163.7, 151.2, 10.2)       # voxels: the ellipsoid meets slices 14 .. 33, 20 of the 48
 ROTATING = 24
-
-
-def queued_us(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(50_000_000)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / steps
-
-
-def best_ms(fn, repeats=3):
-    out = []
-    for _ in range(repeats):
-        t = time.perf_counter()
-        keep = fn()
-        out.append((time.perf_counter() - t) * 1e3)
-        del keep
-    return round(min(out), 2)
 
 
 def ellipsoid():
@@ -105,11 +82,6 @@ def main():
         ws = torch.empty(ingest.workspace_bytes(*SHAPE), dtype=torch.uint8, device="cuda")
         turn = [0]
 
-        def decode(series, pixels, out):
-            desc = _lib.DecodeSlicesDesc(*SHAPE, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed),
-                                         ingest._integer_code(series.bits_allocated, series.signed))
-            _lib.check(_lib.lib().mmnn_decode_slices(ctypes.byref(desc), pixels.data_ptr(), None, out.data_ptr(), stream), "mmnn_decode_slices")
-
         def unpack():
             return ingest.unpack_frames(staged, vol_s, out=masks[0])
 
@@ -123,15 +95,13 @@ def main():
             return ingest.unpack_frames(empty, vol_s, out=masks[1])
 
         def _ingest(s, m):
-            desc = _lib.IngestDesc(*SHAPE, s.datatype, m.datatype, s.slope, s.inter, m.slope, m.inter)
-            _lib.check(_lib.lib().mmnn_ingest_volume(ctypes.byref(desc), s.data.data_ptr(), m.data.data_ptr(), plane.data_ptr(), ext.data_ptr(),
-                                                     ws.data_ptr(), stream), "mmnn_ingest_volume")
+            ingest_passes(s, m, plane, ext, ws, stream)
 
         def seg_mask_path():
             m = ingest.unpack_frames(ingest.stage_frames(fs, vol_s, "cuda"), vol_s, out=masks[0])
             _ingest(vol_s, m)
 
-        decode(s_series, pix_s, out_s)
+        decode(s_series, pix_s, out_s, stream)
         unpack()
         torch.cuda.synchronize()
         got = masks[0].cpu().numpy().reshape(SHAPE, order="F")
@@ -148,7 +118,7 @@ def main():
         unpacked = ingest.DeviceVolume(masks[0], SHAPE, 2, 1.0, 0.0, s_series.affine)
 
         def series_mask():
-            decode(m_series, pix_m, out_m)
+            decode(m_series, pix_m, out_m, stream)
             return ingest.resample_mask(vol_m, SHAPE, ingest.IDENTITY_MAP, ingest.DICOM_MASK_THRESHOLD, out=resampled)
 
         def series_mask_path():
