@@ -618,6 +618,61 @@ int64_t mmnn_radiomics_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t 
 int mmnn_radiomics(const mmnn_radiomics_desc* d, const void* scan, const void* mask, mmnn_radiomics_result* result, uint32_t* hist,
                    uint32_t* glcm, void* ws, void* stream);
 
+/* ---- three more texture classes of the same pair: the grey-level run-length matrix (GLRLM), the grey-level dependence matrix (GLDM)
+ * and the neighbouring grey-tone difference matrix (NGTDM) (csrc/radiomics_texture.hip).  The call runs after mmnn_radiomics on the same
+ * stream: `ws` and `result` are the workspace and the device result block that a mmnn_radiomics call with the same descriptor has filled
+ * earlier on `stream`.  The bin volume (uint16, 0 outside the ROI), Ng, n and the flags are read from the workspace ON THE DEVICE: no
+ * host wait, no read-back (`result` is checked like the other pointers and names the call this one belongs to).  Distance 1, the 26
+ * neighbours, alpha = 0, levels i = 1..Ng, lengths / dependences j from 1, eps = 2^-52.  L = max(x, y, z).
+ *   glrlm    [13][max_bins][L] uint32, the directions of mmnn_radiomics in its order.  A run is a maximal set of consecutive voxels along
+ *            the direction that all lie in the volume and in the ROI and share one bin; one count at [d][bin - 1][length - 1].  Every ROI
+ *            voxel is in exactly one run per direction: sum_j j P(i, j) = hist[i].
+ *   gldm     [max_bins][27] uint32: an ROI voxel of bin i counts at [i - 1][k], k the number of its 26 neighbours in the volume and in the
+ *            ROI with the same bin; the dependence is j = k + 1.
+ *   ngtdm_n  [max_bins][27] uint32, ngtdm_s [max_bins][27] uint64: an ROI voxel of bin i with c of its 26 neighbours in the volume and in
+ *            the ROI, their bins summing to B, adds 1 at n[i - 1][c] and |i c - B| at s[i - 1][c].  So n_i = sum_{c=1..26} n[i][c] and
+ *            s_i = sum_{c=1..26} s[i][c] / c, exact up to that division; column 0 (no neighbour) is counted and enters no feature.
+ *   The four tables are the accumulation targets; the call zeroes them first, and they are exact.
+ *   out.glrlm  per direction, averaged over the 13 (none is empty when n > 0).  P(i, j) the count, Nr = sum P, p = P / Nr, pg(i) = sum_j P,
+ *            pr(j) = sum_i P, Np = n, mu_g = sum i pg / Nr, mu_r = sum j pr / Nr:
+ *            ShortRunEmphasis sum pr / j^2 / Nr; LongRunEmphasis sum pr j^2 / Nr; GrayLevelNonUniformity sum pg^2 / Nr;
+ *            GrayLevelNonUniformityNormalized sum pg^2 / Nr^2; RunLengthNonUniformity sum pr^2 / Nr; RunLengthNonUniformityNormalized
+ *            sum pr^2 / Nr^2; RunPercentage Nr / Np; GrayLevelVariance sum (pg / Nr)(i - mu_g)^2; RunVariance sum (pr / Nr)(j - mu_r)^2;
+ *            RunEntropy -sum sum p log2(p + eps); LowGrayLevelRunEmphasis sum pg / i^2 / Nr; HighGrayLevelRunEmphasis sum pg i^2 / Nr;
+ *            ShortRunLowGrayLevelEmphasis sum sum P / (i^2 j^2) / Nr; ShortRunHighGrayLevelEmphasis sum sum P i^2 / j^2 / Nr;
+ *            LongRunLowGrayLevelEmphasis sum sum P j^2 / i^2 / Nr; LongRunHighGrayLevelEmphasis sum sum P i^2 j^2 / Nr.
+ *   out.gldm   one matrix, Nz = sum P = n, pg and pd the marginals, p = P / Nz: SmallDependenceEmphasis sum pd / j^2 / Nz;
+ *            LargeDependenceEmphasis sum pd j^2 / Nz; GrayLevelNonUniformity sum pg^2 / Nz; DependenceNonUniformity sum pd^2 / Nz;
+ *            DependenceNonUniformityNormalized sum pd^2 / Nz^2; GrayLevelVariance; DependenceVariance; DependenceEntropy
+ *            -sum sum p log2(p + eps); LowGrayLevelEmphasis sum pg / i^2 / Nz; HighGrayLevelEmphasis sum pg i^2 / Nz;
+ *            SmallDependenceLowGrayLevelEmphasis sum sum P / (i^2 j^2) / Nz; SmallDependenceHighGrayLevelEmphasis sum sum P i^2 / j^2 / Nz;
+ *            LargeDependenceLowGrayLevelEmphasis sum sum P j^2 / i^2 / Nz; LargeDependenceHighGrayLevelEmphasis sum sum P i^2 j^2 / Nz.
+ *   out.ngtdm  Nvp = sum n_i, p_i = n_i / Nvp, Ngp = #{i: n_i > 0}, double sums over the pairs with n_i > 0 and n_j > 0:
+ *            Coarseness 1 / sum p_i s_i (10^6 when that sum is 0); Contrast [sum sum p_i p_j (i - j)^2 / (Ngp (Ngp - 1))] [sum s_i / Nvp]
+ *            (0 when Ngp = 1); Busyness sum p_i s_i / sum sum |i p_i - j p_j| (0 when the denominator is 0); Complexity
+ *            sum sum |i - j| (p_i s_i + p_j s_j) / (p_i + p_j) / Nvp; Strength sum sum (p_i + p_j)(i - j)^2 / sum s_i (0 when sum s_i = 0).
+ *            All five are NaN when Nvp = 0 (a single voxel, isolated voxels only).
+ *   flags    with overflow, nonfinite or empty set by mmnn_radiomics every fp64 of `out` is NaN and the four tables are zero.
+ * Where the tables live while they are counted: the run-length matrix of a direction in LDS when Ng * L <= 16384 (64 KiB), the three
+ * neighbourhood tables in LDS when Ng <= 128 (54 KiB); uint32 / uint64 atomics on global memory beyond.  Every fp64 sum runs over a
+ * partition and in an order fixed by the extents and Ng alone, without floating-point atomics: repeated calls are bit-identical.
+ * ws2: mmnn_radiomics_texture_workspace_bytes bytes, aligned to 256.  Refused as mmnn_radiomics refuses (status 1; the size returns -1),
+ * before any launch: a null pointer, a bad extent, max_bins, type code or bin_width, a buffer not aligned to its element size.
+ * GLSZM, mesh-based shape features and the GLCM's MCC are not computed. */
+#define MMNN_RADIOMICS_GLRLM 16
+#define MMNN_RADIOMICS_GLDM 14
+#define MMNN_RADIOMICS_NGTDM 5
+#define MMNN_RADIOMICS_NEIGHBOURS 27
+typedef struct {
+  double glrlm[MMNN_RADIOMICS_GLRLM];
+  double gldm[MMNN_RADIOMICS_GLDM];
+  double ngtdm[MMNN_RADIOMICS_NGTDM];
+} mmnn_radiomics_texture_result;
+int64_t mmnn_radiomics_texture_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t max_bins);
+int mmnn_radiomics_texture(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws,
+                           mmnn_radiomics_texture_result* out, uint32_t* glrlm, uint32_t* gldm, uint32_t* ngtdm_n, uint64_t* ngtdm_s,
+                           void* ws2, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

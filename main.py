@@ -24,7 +24,8 @@ attention map back on each scan's own voxel grid, with the scan's affine (att_ma
 `--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
 `--radiomics` trains on radiomic features: the csv of `--rad_loc` (column MRN, then the features), or, without it, the table extracted
-on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py); alone it is
+on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py; the config's
+`Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it); alone it is
 the standalone MLP over the radiomic columns, with `--images` the fusion model, with `--preop` / `--postop` too the clinical columns first.
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -279,7 +280,7 @@ def extract_radiomics_if_needed(parser, args):
     from mmnn_sts_amd.data.ImageDatasets import ImageDataset
     if not torch.cuda.is_available():
         raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
-    rc = parser.radiomicsConfig()
+    rc, classes = parser.radiomicsConfig(), parser.radiomicsClasses()
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
     prefixes = ("t1_", "t2_") if len(paths) == 2 else ("",)
@@ -288,7 +289,7 @@ def extract_radiomics_if_needed(parser, args):
         ds = ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
         threshold = (parser.config.get("Data") or {}).get("mask_threshold")
         part = radiomics.extract_tree(ds, torch.device("cuda", 0), None, rc["bin_width"], rc["max_bins"],
-                                      None if threshold is None else float(threshold), prefixes=(px,))
+                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes)
         if rows is None:
             rows = part
         else:

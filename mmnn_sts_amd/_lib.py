@@ -143,6 +143,8 @@ class OcclusionDesc(Structure):
 
 RADIOMICS_DIRECTIONS, RADIOMICS_FIRSTORDER, RADIOMICS_GLCM, RADIOMICS_MAX_BINS = 13, 17, 23, 1024
 RADIOMICS_RESULT_INT64, RADIOMICS_RESULT_BYTES = 20, (20 + 10 + 17 + 23) * 8      # mmnn_radiomics_result: 20 int64, then 50 doubles
+RADIOMICS_GLRLM, RADIOMICS_GLDM, RADIOMICS_NGTDM, RADIOMICS_NEIGHBOURS = 16, 14, 5, 27
+RADIOMICS_TEXTURE_BYTES = (16 + 14 + 5) * 8                                       # mmnn_radiomics_texture_result: 35 doubles
 
 
 class RadiomicsDesc(Structure):
@@ -266,6 +268,10 @@ def lib():
     L.mmnn_radiomics_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
     L.mmnn_radiomics.restype = c_int32
     L.mmnn_radiomics.argtypes = [POINTER(RadiomicsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_radiomics_texture_workspace_bytes.restype = c_int64
+    L.mmnn_radiomics_texture_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.mmnn_radiomics_texture.restype = c_int32
+    L.mmnn_radiomics_texture.argtypes = [POINTER(RadiomicsDesc)] + [c_void_p] * 9
     L.mmnn_channel_means.restype = c_int32
     L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64

@@ -20,43 +20,12 @@
 // atomics does not show.  Every fp64 sum runs over a partition that depends on the extents only: a lane adds its voxels in ascending
 // order, a wave folds its lanes by the xor butterfly, the four waves of a workgroup and then the RAD_PARTS workgroups are added in index
 // order.  No floating-point atomics anywhere.
-#include "../../include/mmnn_sts.h"
-#include "common.hpp"
 #include "ingest_load.hpp"
+#include "radiomics.hpp"
 
 #include <cmath>
 
 namespace mmnn {
-
-constexpr int RAD_TPB = 256;
-constexpr int RAD_MAX_PARTS = 256;          // workgroups of a voxel pass (the fixed partition of the fp64 sums)
-constexpr int RAD_SLOTS = 24;               // 64-bit partial results per workgroup and pass
-constexpr int RAD_RANKS = 10;
-constexpr int RAD_DIGITS = 65536;           // 16-bit radix digits: four passes over the 64-bit key
-constexpr int RAD_LDS_NG = 128;             // the LDS matrix: RAD_LDS_NG^2 * 4 B = 64 KiB of the CU's 160, two workgroups per CU
-constexpr int RAD_DIRS = MMNN_RADIOMICS_DIRECTIONS;
-constexpr int RAD_GLCM_CHUNKS = 64;         // workgroups per direction in glcm_count_kernel
-constexpr int RAD_NF = MMNN_RADIOMICS_GLCM;
-constexpr int RAD_MAX_BINS = MMNN_RADIOMICS_MAX_BINS;
-constexpr double RAD_EPS = 2.220446049250313e-16;   // 2^-52
-
-__constant__ int rad_dirs[RAD_DIRS][3] = {      // (dz, dy, dx), first non-zero component positive, lexicographic
-    {0, 0, 1}, {0, 1, -1}, {0, 1, 0}, {0, 1, 1}, {1, -1, -1}, {1, -1, 0}, {1, -1, 1}, {1, 0, -1}, {1, 0, 0}, {1, 0, 1}, {1, 1, -1},
-    {1, 1, 0}, {1, 1, 1}};
-
-struct RadState {
-  long long n;
-  int flagged;                              // overflow | nonfinite | empty
-  int n_bins;
-  double low, bw, mean, vmin, vmax, sum, sumsq;
-  double cen[4];                            // sum |d|, d^2, d^3, d^4
-  long long rob_n;
-  double rob_sum, rob_mean, rob_abs;
-  double p10, p90;
-  unsigned long long prefix[RAD_RANKS];
-  unsigned long long rank[RAD_RANKS];       // rank among the values that share the prefix
-  int rep[RAD_RANKS];                       // the first rank with the same prefix: its histogram is the one that is filled
-};
 
 struct RadArgs {
   const void* scan; const void* mask;
@@ -105,7 +74,6 @@ __device__ __forceinline__ void rad_count(unsigned* h, unsigned digit, bool acti
   }
 }
 
-__device__ __forceinline__ double rad_wave_sum(double v) { return wave_sum_d(v); }
 __device__ __forceinline__ long long rad_wave_sum(long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -130,26 +98,6 @@ __device__ __forceinline__ double rad_wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
   return v;
-}
-
-// K sums over the workgroup, the same total in every thread: lanes by the butterfly, then the waves in index order.
-// lds: (RAD_TPB / 64) * K doubles.  Two barriers.
-template <int K>
-__device__ __forceinline__ void rad_block_sum(double (&a)[K], double* lds) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double t = rad_wave_sum(a[k]);
-    if (lane == 0) lds[wave * K + k] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double t = lds[k];
-    for (int w = 1; w < RAD_TPB / 64; ++w) t += lds[w * K + k];
-    a[k] = t;
-  }
-  __syncthreads();
 }
 
 enum { RS_N = 0, RS_LO = 1, RS_HI = 4, RS_MOM = 7, RS_BAD = 16, RS_SUM = 17, RS_SQ = 18, RS_MIN = 19, RS_MAX = 20 };
@@ -524,8 +472,6 @@ __global__ void __launch_bounds__(RAD_TPB) glcm_count_kernel(const RadArgs a) {
 }
 
 // ---- co-occurrence features: one workgroup per direction --------------------------------------------------------------------------
-__device__ __forceinline__ double rad_plogp(double p) { return p * log2(p + RAD_EPS); }
-
 __global__ void __launch_bounds__(RAD_TPB) glcm_features_kernel(const RadArgs a) {
   __shared__ unsigned long long row[RAD_MAX_BINS], plus[2 * RAD_MAX_BINS], minus[RAD_MAX_BINS];
   __shared__ unsigned long long total;
@@ -690,29 +636,6 @@ __global__ void __launch_bounds__(RAD_TPB) rad_final_kernel(const RadArgs a) {
 }
 
 namespace {
-
-size_t rad_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct RadLayout { size_t state, part, rhist, dirf, bins, total; };
-
-RadLayout rad_layout(long n) {
-  RadLayout L;
-  size_t off = 0;
-  L.state = off; off += rad_align(sizeof(RadState));
-  L.part = off; off += rad_align((size_t)RAD_SLOTS * RAD_MAX_PARTS * 8);
-  L.rhist = off; off += rad_align((size_t)RAD_RANKS * RAD_DIGITS * 4);
-  L.dirf = off; off += rad_align((size_t)RAD_DIRS * (RAD_NF + 1) * 8);
-  L.bins = off; off += rad_align((size_t)n * 2);
-  L.total = off;
-  return L;
-}
-
-int rad_validate(int x, int y, int z, int max_bins) {
-  MMNN_REQUIRE(x >= 1 && y >= 1 && z >= 1, "radiomics: non-positive extent %d x %d x %d", x, y, z);
-  MMNN_REQUIRE((double)x * y * z < 2147483648.0, "radiomics: extent %d x %d x %d holds 2^31 voxels or more", x, y, z);
-  MMNN_REQUIRE(max_bins >= 1 && max_bins <= RAD_MAX_BINS, "radiomics: max_bins %d outside 1..%d", max_bins, RAD_MAX_BINS);
-  return 0;
-}
 
 IgScale rad_scale(double slope, double inter) {      // as ig_scale reads a header's pair
   IgScale s{1.0, 0.0, 0};

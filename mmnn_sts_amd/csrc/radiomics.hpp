@@ -1,0 +1,90 @@
+// What csrc/radiomics.hip and csrc/radiomics_texture.hip share: the constants, the 13 directions, the state block that the kernels of
+// `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks and the workgroup sum.
+#pragma once
+#include "../../include/mmnn_sts.h"
+#include "common.hpp"
+
+namespace mmnn {
+
+constexpr int RAD_TPB = 256;
+constexpr int RAD_MAX_PARTS = 256;          // workgroups of a voxel pass (the fixed partition of the fp64 sums)
+constexpr int RAD_SLOTS = 24;               // 64-bit partial results per workgroup and pass
+constexpr int RAD_RANKS = 10;
+constexpr int RAD_DIGITS = 65536;           // 16-bit radix digits: four passes over the 64-bit key
+constexpr int RAD_LDS_NG = 128;             // the LDS matrix: RAD_LDS_NG^2 * 4 B = 64 KiB of the CU's 160, two workgroups per CU
+constexpr int RAD_DIRS = MMNN_RADIOMICS_DIRECTIONS;
+constexpr int RAD_GLCM_CHUNKS = 64;         // workgroups per direction in glcm_count_kernel
+constexpr int RAD_NF = MMNN_RADIOMICS_GLCM;
+constexpr int RAD_MAX_BINS = MMNN_RADIOMICS_MAX_BINS;
+constexpr double RAD_EPS = 2.220446049250313e-16;   // 2^-52
+
+#if defined(__HIPCC__)
+static __constant__ int rad_dirs[RAD_DIRS][3] = {      // (dz, dy, dx), first non-zero component positive, lexicographic
+    {0, 0, 1}, {0, 1, -1}, {0, 1, 0}, {0, 1, 1}, {1, -1, -1}, {1, -1, 0}, {1, -1, 1}, {1, 0, -1}, {1, 0, 0}, {1, 0, 1}, {1, 1, -1},
+    {1, 1, 0}, {1, 1, 1}};
+#endif
+
+struct RadState {
+  long long n;
+  int flagged;                              // overflow | nonfinite | empty
+  int n_bins;
+  double low, bw, mean, vmin, vmax, sum, sumsq;
+  double cen[4];                            // sum |d|, d^2, d^3, d^4
+  long long rob_n;
+  double rob_sum, rob_mean, rob_abs;
+  double p10, p90;
+  unsigned long long prefix[RAD_RANKS];
+  unsigned long long rank[RAD_RANKS];       // rank among the values that share the prefix
+  int rep[RAD_RANKS];                       // the first rank with the same prefix: its histogram is the one that is filled
+};
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ double rad_wave_sum(double v) { return wave_sum_d(v); }
+
+// K sums over the workgroup, the same total in every thread: lanes by the butterfly, then the waves in index order.
+// lds: (RAD_TPB / 64) * K doubles.  Two barriers.
+template <int K>
+__device__ __forceinline__ void rad_block_sum(double (&a)[K], double* lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double t = rad_wave_sum(a[k]);
+    if (lane == 0) lds[wave * K + k] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double t = lds[k];
+    for (int w = 1; w < RAD_TPB / 64; ++w) t += lds[w * K + k];
+    a[k] = t;
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ double rad_plogp(double p) { return p * log2(p + RAD_EPS); }
+#endif
+
+inline size_t rad_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct RadLayout { size_t state, part, rhist, dirf, bins, total; };
+
+inline RadLayout rad_layout(long n) {
+  RadLayout L;
+  size_t off = 0;
+  L.state = off; off += rad_align(sizeof(RadState));
+  L.part = off; off += rad_align((size_t)RAD_SLOTS * RAD_MAX_PARTS * 8);
+  L.rhist = off; off += rad_align((size_t)RAD_RANKS * RAD_DIGITS * 4);
+  L.dirf = off; off += rad_align((size_t)RAD_DIRS * (RAD_NF + 1) * 8);
+  L.bins = off; off += rad_align((size_t)n * 2);
+  L.total = off;
+  return L;
+}
+
+inline int rad_validate(int x, int y, int z, int max_bins) {
+  MMNN_REQUIRE(x >= 1 && y >= 1 && z >= 1, "radiomics: non-positive extent %d x %d x %d", x, y, z);
+  MMNN_REQUIRE((double)x * y * z < 2147483648.0, "radiomics: extent %d x %d x %d holds 2^31 voxels or more", x, y, z);
+  MMNN_REQUIRE(max_bins >= 1 && max_bins <= RAD_MAX_BINS, "radiomics: max_bins %d outside 1..%d", max_bins, RAD_MAX_BINS);
+  return 0;
+}
+
+}  // namespace mmnn

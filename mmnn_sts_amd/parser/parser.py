@@ -78,6 +78,15 @@ class Parser:
             raise ConfigurationError('Radiomics.bin_width must be positive and finite and max_bins within 1..1024, got {} and {}'.format(out['bin_width'], out['max_bins']))
         return out
 
+    def radiomicsClasses(self):
+        """`Radiomics: classes`: the texture classes extracted beside the default columns, a list drawn from glrlm, gldm, ngtdm (empty)."""
+        from ..radiomics import texture_classes
+        rad = self.config.get('Radiomics') or {}
+        classes = rad.get('classes')
+        if classes is not None and not isinstance(classes, (list, tuple, str)):
+            raise ConfigurationError('Radiomics.classes must be a list drawn from glrlm, gldm, ngtdm, got {!r}'.format(classes))
+        return texture_classes(classes)
+
     def _radiomicsExcluded(self):
         rm = self.config.get('RadiomicsModel') or {}
         return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])

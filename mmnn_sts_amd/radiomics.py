@@ -1,15 +1,22 @@
-"""Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip).
+"""Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip) and of
+`mmnn_radiomics_texture` (csrc/radiomics_texture.hip).
 
     extract(scan, mask, device)            enqueue one extraction; the result holds device tensors, nothing is read back
     finish(result, affine)                 one read-back -> {feature name: float}: adds TotalEnergy and the voxel-based shape features
     extract_tree(dataset, device, out)     every patient and modality of an image dataset -> a csv (`MRN`, then the features)
-    python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] --out radiomics.csv
+    feature_names(classes)                 the columns: FEATURE_NAMES, then those of the requested texture classes
+    python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] --out radiomics.csv
 
 Upstream reads such a csv (`Data: rad_loc`, data/RadiomicsDatasets.py) and leaves its extraction to PyRadiomics; here the table is built
 from the very pair the image path ingests, through the same mask routes (NIfTI mask, resampled mask, DICOM mask series, RTSTRUCT, SEG:
 `data.ingest.prepare_pair`).  The 47 columns carry PyRadiomics' names and definitions -- 18 first-order, 6 voxel-based shape, 23 GLCM --
 in voxel index space (distance 1, no resampling, fixed `bin_width`).  Mesh-based shape features (surface area, sphericity, the
 diameters) and the GLCM's MCC are out of scope.  What the numbers are pinned to is the numpy restatement in tests/_radiomics_ref.py.
+
+`classes` (`Radiomics: classes`, `--classes`; empty by default) adds the columns of further texture classes, computed by a second call on
+the same stream from the bin volume the first one left on the device: `glrlm` (16 run-length features), `gldm` (14 dependence features,
+alpha 0) and `ngtdm` (5), 82 columns per modality with all three.  GLSZM, the mesh-based shape features and the GLCM's MCC stay out of
+scope.  These too are pinned to a numpy restatement (tests/_radiomics_texture_ref.py); **parity with PyRadiomics is unpinned**.
 """
 import argparse
 import csv
@@ -37,15 +44,49 @@ SHAPE = ("VoxelVolume", "MajorAxisLength", "MinorAxisLength", "LeastAxisLength",
 GLCM = ("Autocorrelation", "JointAverage", "ClusterProminence", "ClusterShade", "ClusterTendency", "Contrast", "Correlation",
         "DifferenceAverage", "DifferenceEntropy", "DifferenceVariance", "JointEnergy", "JointEntropy", "Imc1", "Imc2", "Idm", "Idmn", "Id",
         "Idn", "InverseVariance", "MaximumProbability", "SumAverage", "SumEntropy", "SumSquares")
+GLRLM = ("ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized", "RunLengthNonUniformity",
+         "RunLengthNonUniformityNormalized", "RunPercentage", "GrayLevelVariance", "RunVariance", "RunEntropy", "LowGrayLevelRunEmphasis",
+         "HighGrayLevelRunEmphasis", "ShortRunLowGrayLevelEmphasis", "ShortRunHighGrayLevelEmphasis", "LongRunLowGrayLevelEmphasis",
+         "LongRunHighGrayLevelEmphasis")
+GLDM = ("SmallDependenceEmphasis", "LargeDependenceEmphasis", "GrayLevelNonUniformity", "DependenceNonUniformity",
+        "DependenceNonUniformityNormalized", "GrayLevelVariance", "DependenceVariance", "DependenceEntropy", "LowGrayLevelEmphasis",
+        "HighGrayLevelEmphasis", "SmallDependenceLowGrayLevelEmphasis", "SmallDependenceHighGrayLevelEmphasis",
+        "LargeDependenceLowGrayLevelEmphasis", "LargeDependenceHighGrayLevelEmphasis")
+NGTDM = ("Coarseness", "Contrast", "Busyness", "Complexity", "Strength")
+TEXTURE_CLASSES = ("glrlm", "gldm", "ngtdm")
+_TEXTURE = {"glrlm": GLRLM, "gldm": GLDM, "ngtdm": NGTDM}
 FEATURE_NAMES = tuple([f"original_firstorder_{n}" for n in FIRSTORDER] + [f"original_shape_{n}" for n in SHAPE]
                       + [f"original_glcm_{n}" for n in GLCM])
 _logged_identity = False
 
 
+def texture_classes(classes) -> tuple:
+    """`classes` (names, a comma-separated string, or 'all') -> the requested texture classes in the fixed order of TEXTURE_CLASSES."""
+    if classes is None:
+        return ()
+    if isinstance(classes, str):
+        classes = [c for c in classes.replace(",", " ").split() if c]
+    names = [str(c).strip().lower() for c in classes]
+    if names == ["all"]:
+        return TEXTURE_CLASSES
+    unknown = [c for c in names if c not in TEXTURE_CLASSES]
+    if unknown:
+        raise ConfigurationError(f"radiomics: unknown texture class {', '.join(repr(c) for c in unknown)}: the valid ones are "
+                                 + ", ".join(TEXTURE_CLASSES))
+    return tuple(c for c in TEXTURE_CLASSES if c in names)
+
+
+def feature_names(classes=()) -> tuple:
+    """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes."""
+    return FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
+
+
 @dataclass
 class RadiomicsResult:
     """One extraction, still on the device.  `block`: the bytes of mmnn_radiomics_result; `hist` (max_bins,) and `glcm`
-    (13, max_bins, max_bins) int32 views of the uint32 counts; `shape`, `affine`: the scan's grid."""
+    (13, max_bins, max_bins) int32 views of the uint32 counts; `shape`, `affine`: the scan's grid.  With texture classes: `texture`, the
+    bytes of mmnn_radiomics_texture_result; `glrlm` (13, max_bins, L), `gldm` and `ngtdm_n` (max_bins, 27) int32 views of the uint32 counts,
+    `ngtdm_s` (max_bins, 27) int64; `classes`, the requested ones (the device computes all three)."""
     block: torch.Tensor
     hist: torch.Tensor
     glcm: torch.Tensor
@@ -54,6 +95,13 @@ class RadiomicsResult:
     affine: Optional[np.ndarray]
     bin_width: float
     max_bins: int
+    texture: Optional[torch.Tensor] = None
+    glrlm: Optional[torch.Tensor] = None
+    gldm: Optional[torch.Tensor] = None
+    ngtdm_n: Optional[torch.Tensor] = None
+    ngtdm_s: Optional[torch.Tensor] = None
+    texture_workspace: Optional[torch.Tensor] = None
+    classes: tuple = ()
 
 
 def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
@@ -64,15 +112,17 @@ def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) ->
 
 
 def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS, index_map=None,
-            threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None) -> RadiomicsResult:
+            threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=()) -> RadiomicsResult:
     """Enqueue the extraction of one (scan, mask) pair on the current stream of `device`.  `scan` / `mask`: whatever `ingest_volume`
     takes (host volumes are uploaded; a contour, SEG or other-grid mask is brought onto the scan's grid first, `index_map` and
-    `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again."""
+    `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again.  `classes`:
+    texture classes of TEXTURE_CLASSES; when not empty `mmnn_radiomics_texture` is enqueued behind the extraction."""
     from .data import ingest
     dev = torch.device(device)
     scan, mask = ingest.prepare_pair(scan, mask, dev, index_map, threshold, what="radiomics")
     x, y, z = scan.shape
     max_bins = int(max_bins)
+    classes = texture_classes(classes)
     nbytes = workspace_bytes(x, y, z, max_bins)
     if buffers is not None and (tuple(buffers.shape) != (x, y, z) or buffers.max_bins != max_bins or buffers.block.device != scan.data.device):
         raise ValueError(f"radiomics: buffers of extent {buffers.shape} / {buffers.max_bins} bins cannot take a scan of {(x, y, z)} / {max_bins}")
@@ -90,7 +140,34 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), block.data_ptr(), hist.data_ptr(),
                                              glcm.data_ptr(), ws.data_ptr(), stream), "mmnn_radiomics")
-    return RadiomicsResult(block, hist, glcm, ws, (x, y, z), scan.affine, float(bin_width), max_bins)
+    out = RadiomicsResult(block, hist, glcm, ws, (x, y, z), scan.affine, float(bin_width), max_bins)
+    if not classes:
+        return out
+    if buffers is not None and buffers.texture is not None:
+        tex, glrlm, gldm, ngn, ngs, ws2 = buffers.texture, buffers.glrlm, buffers.gldm, buffers.ngtdm_n, buffers.ngtdm_s, buffers.texture_workspace
+    else:
+        n2 = _lib.lib().mmnn_radiomics_texture_workspace_bytes(x, y, z, max_bins)
+        if n2 < 0:
+            raise ValueError("mmnn_radiomics_texture_workspace_bytes: " + _lib.last_error())
+        tex = torch.empty(_lib.RADIOMICS_TEXTURE_BYTES, dtype=torch.uint8, device=dev)
+        glrlm = torch.empty((_lib.RADIOMICS_DIRECTIONS, max_bins, max(x, y, z)), dtype=torch.int32, device=dev)
+        gldm = torch.empty((max_bins, _lib.RADIOMICS_NEIGHBOURS), dtype=torch.int32, device=dev)
+        ngn = torch.empty((max_bins, _lib.RADIOMICS_NEIGHBOURS), dtype=torch.int32, device=dev)
+        ngs = torch.empty((max_bins, _lib.RADIOMICS_NEIGHBOURS), dtype=torch.int64, device=dev)
+        ws2 = torch.empty(int(n2), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mmnn_radiomics_texture(ctypes.byref(desc), block.data_ptr(), ws.data_ptr(), tex.data_ptr(), glrlm.data_ptr(),
+                                                     gldm.data_ptr(), ngn.data_ptr(), ngs.data_ptr(), ws2.data_ptr(), stream),
+                   "mmnn_radiomics_texture")
+    out.texture, out.glrlm, out.gldm, out.ngtdm_n, out.ngtdm_s, out.texture_workspace, out.classes = tex, glrlm, gldm, ngn, ngs, ws2, classes
+    return out
+
+
+def unpack_texture(raw: np.ndarray) -> dict:
+    """The bytes of mmnn_radiomics_texture_result -> its fields."""
+    f = np.ascontiguousarray(raw, dtype=np.uint8).view(np.float64)
+    a, b = _lib.RADIOMICS_GLRLM, _lib.RADIOMICS_GLRLM + _lib.RADIOMICS_GLDM
+    return {"glrlm": f[:a].copy(), "gldm": f[a:b].copy(), "ngtdm": f[b:].copy()}
 
 
 def unpack_block(raw: np.ndarray) -> dict:
@@ -123,8 +200,8 @@ def shape_features(n: int, moments, linear) -> Dict[str, float]:
     return out
 
 
-def features_of(fields: dict, affine, what: str = "radiomics") -> Dict[str, float]:
-    """The host half of `finish`, from the unpacked block."""
+def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=()) -> Dict[str, float]:
+    """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block)."""
     global _logged_identity
     if fields["empty"]:
         raise ConfigurationError(f"{what}: the mask selects no voxel of the scan")
@@ -150,16 +227,23 @@ def features_of(fields: dict, affine, what: str = "radiomics") -> Dict[str, floa
         out[f"original_shape_{n}"] = shape[n]
     for n, v in zip(GLCM, fields["glcm"]):
         out[f"original_glcm_{n}"] = float(v)
+    for c in texture_classes(classes):
+        for n, v in zip(_TEXTURE[c], texture[c]):
+            out[f"original_{c}_{n}"] = float(v)
     return out
 
 
 def finish(result: RadiomicsResult, affine="scan", what: str = "radiomics") -> Dict[str, float]:
-    """One read-back of the result block -> {name: float} over FEATURE_NAMES.  `affine`: the scan's voxel index -> mm matrix (4x4 or
+    """One read-back of the result block(s) -> {name: float} over FEATURE_NAMES, then the columns of the result's texture classes.  `affine`: the scan's voxel index -> mm matrix (4x4 or
     its 3x3 linear part as the top-left block), None for the identity; the default takes the scan's own.  A flag raises
     ConfigurationError with the cause."""
     if isinstance(affine, str):
         affine = result.affine
-    return features_of(unpack_block(result.block.cpu().numpy()), affine, what)
+    if not result.classes:
+        return features_of(unpack_block(result.block.cpu().numpy()), affine, what)
+    raw = torch.cat([result.block, result.texture]).cpu().numpy()
+    nb = _lib.RADIOMICS_RESULT_BYTES
+    return features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:]), result.classes)
 
 
 def _volumes_of(dataset, patient):
@@ -167,12 +251,15 @@ def _volumes_of(dataset, patient):
 
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
-                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None) -> List[dict]:
+                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=()) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
-    A dataset of two modalities prefixes its columns `t1_` / `t2_`."""
+    A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
+    blocks come back in the batch's same stacked read-back."""
     from .data import ingest
     dev = torch.device(device)
+    classes = texture_classes(classes)
+    nb = _lib.RADIOMICS_RESULT_BYTES
     rows = []
     patients = list(dataset.patients)
     for b0 in range(0, len(patients), max(1, int(batch))):
@@ -180,16 +267,17 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         raws = [_volumes_of(dataset, p) for p in chunk]
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
-        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold) for (s, m), t in zip(vols, ts)]
+        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes) for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
-        blocks = torch.stack([r.block for rs in res for r in rs]).cpu().numpy()          # the batch's one read-back
+        blocks = torch.stack([torch.cat([r.block, r.texture]) if classes else r.block for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
         k = 0
         for p, rs in zip(chunk, res):
             uid = dataset._uid_of(p)
             pre = prefixes if prefixes is not None else (("",) if len(rs) == 1 else ("t1_", "t2_"))
             row = {"MRN": uid}
             for r, px in zip(rs, pre):
-                feats = features_of(unpack_block(blocks[k]), r.affine, f"patient {p} (uid {uid})")
+                feats = features_of(unpack_block(blocks[k][:nb]), r.affine, f"patient {p} (uid {uid})",
+                                    unpack_texture(blocks[k][nb:]) if classes else None, classes)
                 row.update({px + n: v for n, v in feats.items()})
                 k += 1
             rows.append(row)
@@ -223,11 +311,15 @@ def main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--modality", choices=("t1", "t2", "t1t2"), default="t1t2")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--classes", default=None, help="texture classes beside the 47 default columns: a comma-separated list of glrlm, gldm, "
+                    "ngtdm, or 'all'; overrides the config's `Radiomics: classes`")
     a = ap.parse_args(argv)
     import os
     from .data.ImageDatasets import ImageDataset
     from .parser.parser import Parser
-    config = Parser(a.config).parseConfig()
+    parser = Parser(a.config)
+    config = parser.parseConfig()
+    classes = texture_classes(a.classes) if a.classes is not None else parser.radiomicsClasses()
     data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
@@ -238,7 +330,7 @@ def main(argv=None):
     rows = None
     for ds, px in zip(sets, ("t1_", "t2_") if len(sets) == 2 else ("",)):
         part = extract_tree(ds, a.device, None, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
-                            data.get("mask_threshold"), prefixes=(px,))
+                            data.get("mask_threshold"), prefixes=(px,), classes=classes)
         if rows is None:
             rows = part
         else:
