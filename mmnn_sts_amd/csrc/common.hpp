@@ -1,5 +1,10 @@
 // Shared device/host helpers for the MI355X (gfx950) kernels of the MMNN_STS fusion path.
 //
+// Holds: the host error channel and the launch macro; the batch-norm / dropout descriptors and the device code that turns statistics
+// into coefficients; the hash finaliser and 24-bit uniform of the counter-based random streams; the cross-lane helpers that follow the
+// MFMA tile layout (swz_xor, half_reduce16, acc_row); kernarg_warm; and on the host cdiv and the workspace Carver.  The lane butterfly
+// and the workgroup reductions are in reduce.hpp.
+//
 // Conventions used by every kernel in this directory:
 //  * activations are fp32, channel-major per sample:  buf[n][c][v],  v = (d*H + h)*W + w  (NCDHW as the reference's
 //    collate produces it, utils/utils.py:112-117).  A dense block's concat (models/densenet.py:87-89) is ONE
@@ -11,6 +16,7 @@
 //  * wave = 64 lanes; MFMA = v_mfma_f32_32x32x2_f32 (exact fp32 fma chain, 64 FLOP/clk/SIMD).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace mmnn {
@@ -205,15 +211,21 @@ __device__ __forceinline__ void bn_bwd_finish(const BnBwd& s, BnBwdRaw& r, float
   rr = (float)(g * rstd * rstd * m2 * mean - g * rstd * m1);
 }
 
+// The counter-based random streams (channel dropout here, element dropout in resnet.hip, the noise of transforms.hip) each form a
+// 64-bit counter their own way and share the two steps below: the finaliser of splitmix64, and a uniform in [0, 1) from the top 24 bits.
+__device__ __host__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __host__ __forceinline__ float unit24(uint64_t x) { return (float)(x >> 40) * (1.0f / 16777216.0f); }
+
 // counter-based uniform in [0,1): splitmix64 of (seed, layer, n, c)
 __device__ __host__ __forceinline__ float drop_scale(const DropCfg& d, int n, int c) {
   if (d.p <= 0.f) return 1.f;
   uint64_t x = d.seed + 0x9E3779B97F4A7C15ull * (uint64_t)(((uint64_t)(uint32_t)d.layer << 40) ^ ((uint64_t)(uint32_t)n << 20) ^ (uint64_t)(uint32_t)c);
   x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  float u = (float)(x >> 40) * (1.0f / 16777216.0f);
+  float u = unit24(mix64(x));
   return u < d.p ? 0.f : 1.f / (1.f - d.p);
 }
 
@@ -257,17 +269,6 @@ __device__ __forceinline__ float half_reduce16(const float v[16], int lane) {
 // row of the 32x32 accumulator tile held in register r by a lane of half h (C/D layout of v_mfma_f32_32x32x2_f32)
 __device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Every 64-byte line of the kernel-argument segment in ONE scalar-cache round trip, first thing in a kernel.  The argument
 // structs here are 200-560 bytes; the compiler places each `s_load` next to its first use, every line it touches for the first
 // time is a miss (the segment was written by the host a moment ago: cold in every cache) and the misses come one after the other --
@@ -296,5 +297,17 @@ __device__ __forceinline__ void kernarg_warm() {
 #endif  // __HIPCC__
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Carves a workspace into fields that each start on a multiple of 256 bytes: take(bytes) returns the offset of the next field and moves
+// on to the next multiple of 256 behind it; take(0) returns the offset a field would have and does not move (a field that is absent in
+// this configuration).  `cur` after the last take is the workspace size.
+struct Carver {
+  size_t cur = 0;
+  size_t take(size_t bytes) {
+    const size_t o = cur;
+    cur = (cur + bytes + 255) / 256 * 256;
+    return o;
+  }
+};
 
 }  // namespace mmnn

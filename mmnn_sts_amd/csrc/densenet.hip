@@ -11,21 +11,12 @@
 
 namespace mmnn {
 
-static size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 // cross-block K-split scratch of the plan's workspace: <= 512 blocks x (up to 4) 32x32 partial tiles, + per-tile counters
 constexpr size_t KZ_PART_BYTES = (size_t)512 * 4 * 1024 * sizeof(float);
 constexpr unsigned KZ_CNT_ENTRIES = 4096;
 
 namespace {
 struct Panel { const float* p; unsigned bytes; };   // a weight panel in device memory
-struct Carver {
-  size_t cur = 0;
-  size_t take(size_t bytes) {
-    size_t o = cur;
-    cur = align_up(cur + bytes);
-    return o;
-  }
-};
 // Everything the backward of dense layer (b, l) binds (layer_bind).  The data gradients (plan_backward_range) and the weight gradients
 // (layer_wgrad_args) both take it from here: the operand of a data gradient IS the g0 / g1 / gr of the same convolution's weight gradient.
 struct LayerBind {

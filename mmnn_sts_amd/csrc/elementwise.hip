@@ -1,20 +1,10 @@
 #include "elementwise.hpp"
 #include "bf16x3.hpp"
+#include "reduce.hpp"
 
 #include <algorithm>
 
 namespace mmnn {
-
-// block-wide sum of two floats -> thread 0 (256 threads)
-__device__ __forceinline__ void block_sum2(float& s0, float& s1, float (*red)[4]) {
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; }
-  __syncthreads();
-  s0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  s1 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) bnrelu_avgpool_kernel(const PoolFwdArgs a) {
@@ -87,7 +77,7 @@ int launch_relu_mask(const MaskArgs& a, hipStream_t stream) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) consumer_bwd_kernel(const ConsumerBwdArgs a) {
-  __shared__ float red[2][4];
+  __shared__ float red[4 * 2];
   const int c = blockIdx.y, n = blockIdx.z;
   const int V = a.D * a.H * a.W;
   const int Do = a.D / 2, Ho = a.H / 2, Wo = a.W / 2;
@@ -146,13 +136,14 @@ __global__ void __launch_bounds__(256) consumer_bwd_kernel(const ConsumerBwdArgs
     s0 += z;
     s1 += z * (x - mu) * rs;
   }
-  block_sum2(s0, s1, red);
+  float s[2] = {s0, s1};
+  block_reduce<4>(s, red, Sum{});
   if (threadIdx.x == 0) {
     const int rep = blockIdx.x & ((a.nrep > 0 ? a.nrep : NREP) - 1);
-    atomicAdd(a.dbeta + (long)rep * a.C + c, (double)s0);
-    atomicAdd(a.dgamma + (long)rep * a.C + c, (double)s1);
-    atomicAdd(a.s_acc.sum + (long)rep * a.s_acc.stride + a.s_acc.off + c, (double)gam * s0);
-    atomicAdd(a.s_acc.sq + (long)rep * a.s_acc.stride + a.s_acc.off + c, (double)gam * s1);
+    atomicAdd(a.dbeta + (long)rep * a.C + c, (double)s[0]);
+    atomicAdd(a.dgamma + (long)rep * a.C + c, (double)s[1]);
+    atomicAdd(a.s_acc.sum + (long)rep * a.s_acc.stride + a.s_acc.off + c, (double)gam * s[0]);
+    atomicAdd(a.s_acc.sq + (long)rep * a.s_acc.stride + a.s_acc.off + c, (double)gam * s[1]);
   }
 }
 

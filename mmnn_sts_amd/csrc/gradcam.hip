@@ -20,22 +20,6 @@ struct GradcamArgs {
 constexpr int GC_THREADS = 1024;
 constexpr int GC_MAX_G = 64, GC_MAX_CLASSES = 16;
 
-__device__ __forceinline__ float block_reduce(float val, float* red, bool is_max, bool is_min) {
-  // all 1024 threads call; red: 16 floats of LDS
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float other = __shfl_xor(val, o, 64);
-    val = is_max ? fmaxf(val, other) : (is_min ? fminf(val, other) : val + other);
-  }
-  __syncthreads();
-  if (lane == 0) red[wave] = val;
-  __syncthreads();
-  float r = red[0];
-  for (int k = 1; k < GC_THREADS / 64; ++k) r = is_max ? fmaxf(r, red[k]) : (is_min ? fminf(r, red[k]) : r + red[k]);
-  return r;
-}
-
 __global__ void __launch_bounds__(GC_THREADS) gradcam_heat_kernel(const GradcamArgs a) {
   __shared__ float chan[GC_MAX_CLASSES * GC_MAX_G];   // d out[0,cls] / d act[c][.] where the ReLU passes
   __shared__ float cnt[GC_MAX_G];                      // voxels of channel c where norm5's output is positive
@@ -75,14 +59,14 @@ __global__ void __launch_bounds__(GC_THREADS) gradcam_heat_kernel(const GradcamA
       a.heat[(long)cls * a.v + i] = s;
       lo = fminf(lo, s); hi = fmaxf(hi, s);
     }
-    lo = block_reduce(lo, red, false, true);
+    lo = block_reduce<GC_THREADS / 64>(lo, red, FMin{});
     float top = -3.4e38f;
     for (int i = tid; i < a.v; i += GC_THREADS) {     // heat -= min ; heat /= max(heat)
       const float t = a.heat[(long)cls * a.v + i] - lo;
       a.heat[(long)cls * a.v + i] = t;
       top = fmaxf(top, t);
     }
-    top = block_reduce(top, red, true, false);
+    top = block_reduce<GC_THREADS / 64>(top, red, FMax{});
     for (int i = tid; i < a.v; i += GC_THREADS) a.heat[(long)cls * a.v + i] /= top;
     (void)hi;
   }

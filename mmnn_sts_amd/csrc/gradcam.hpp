@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 

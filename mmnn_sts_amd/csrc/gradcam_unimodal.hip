@@ -97,22 +97,8 @@ __global__ void __launch_bounds__(GCU_THREADS) gcu_count_kernel(const GcuArgs a)
       if (g && v + 64 * e < v1) g[v + 64 * e] = on ? gs : 0.f;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  n = wave_sum(n);
   if (lane == 0) a.part_cnt[((long)b * a.chunks + chunk) * a.C + c] = n;
-}
-
-__device__ __forceinline__ void gcu_block_minmax(float& lo, float& hi, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-  }
-  if (lane == 0) { red[2 * wave] = lo; red[2 * wave + 1] = hi; }
-  __syncthreads();
-  lo = red[0]; hi = red[1];
-  for (int w = 1; w < GCU_THREADS / 64; ++w) { lo = fminf(lo, red[2 * w]); hi = fmaxf(hi, red[2 * w + 1]); }
 }
 
 // thread per voxel: heat = ReLU(sum_c alpha[c] * A[c][v]) with alpha = s * count / V / V (the mean over the voxels of s * mask / V)
@@ -131,18 +117,18 @@ __global__ void __launch_bounds__(GCU_THREADS) gcu_heat_kernel(const GcuArgs a) 
   const int v0 = chunk * GCU_CHUNK, v1 = min(a.V, v0 + GCU_CHUNK);
   const float* x = a.act + (long)b * a.act_ns;
   float* hb = a.heat + (long)b * a.V;
-  float lo = 3.4e38f, hi = -3.4e38f;
+  float mm[2] = {3.4e38f, -3.4e38f};     // min, max
   for (int v = v0 + threadIdx.x; v < v1; v += GCU_THREADS) {
     float m = 0.f;
     for (int c = 0; c < a.C; ++c) m = fmaf(alpha[c], x[(long)c * a.V + v], m);
     m = m > 0.f ? m : 0.f;
     hb[v] = m;
-    lo = fminf(lo, m); hi = fmaxf(hi, m);
+    mm[0] = fminf(mm[0], m); mm[1] = fmaxf(mm[1], m);
   }
-  gcu_block_minmax(lo, hi, red);
+  block_reduce<GCU_THREADS / 64>(mm, red, FMinMax{});
   if (threadIdx.x == 0) {
     float* pm = a.part_mm + ((long)b * a.chunks + chunk) * 2;
-    pm[0] = lo; pm[1] = hi;
+    pm[0] = mm[0]; pm[1] = mm[1];
   }
 }
 
@@ -165,11 +151,11 @@ static GcuLayout gcu_layout(const mmnn_gradcam_unimodal_desc* d) {
   GcuLayout l;
   const long v = (long)d->d * d->h * d->w, n = d->n, c = d->channels;
   l.chunks = (v + GCU_CHUNK - 1) / GCU_CHUNK;
-  auto al = [](long x) { return (x + 255) / 256 * 256; };
-  l.s_off = 0;
-  l.cnt_off = al(4 * n * c);
-  l.mm_off = l.cnt_off + al(4 * n * l.chunks * c);
-  l.bytes = l.mm_off + al(4 * n * l.chunks * 2);
+  Carver cv;
+  l.s_off = (long)cv.take(4 * n * c);
+  l.cnt_off = (long)cv.take(4 * n * l.chunks * c);
+  l.mm_off = (long)cv.take(4 * n * l.chunks * 2);
+  l.bytes = (long)cv.cur;
   return l;
 }
 

@@ -370,8 +370,6 @@ __global__ void __launch_bounds__(IG_TPB) maps_to_scan_kernel(const MsArgs a) {
 
 namespace {
 
-size_t ig_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct IgLayout {
   size_t flags, kept, m, total;     // flags: X + Y + Z words (one memset); kept: X + Y + Z ints; m: the extents
 };
@@ -379,11 +377,11 @@ struct IgLayout {
 IgLayout ig_layout(int x, int y, int z) {
   const size_t n = (size_t)x + (size_t)y + (size_t)z;
   IgLayout L;
-  size_t off = 0;
-  L.flags = off; off += ig_align(n * sizeof(unsigned));
-  L.kept = off; off += ig_align(n * sizeof(int));
-  L.m = off; off += ig_align(4 * sizeof(int));
-  L.total = off;
+  Carver cv;
+  L.flags = cv.take(n * sizeof(unsigned));
+  L.kept = cv.take(n * sizeof(int));
+  L.m = cv.take(4 * sizeof(int));
+  L.total = cv.cur;
   return L;
 }
 
@@ -489,7 +487,9 @@ int mmnn_resample_mask(const mmnn_resample_mask_desc* d, const void* mask, uint8
 
 int64_t mmnn_maps_to_scan_workspace_bytes(int32_t x, int32_t y, int32_t z) {
   if (ms_validate_extent(x, y, z) != 0) return -1;
-  return (int64_t)ig_align(((size_t)x + (size_t)y + (size_t)z) * sizeof(MsTap));
+  Carver cv;
+  cv.take(((size_t)x + (size_t)y + (size_t)z) * sizeof(MsTap));
+  return (int64_t)cv.cur;
 }
 
 int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, const float* maps, float* out, void* ws, void* stream_) {

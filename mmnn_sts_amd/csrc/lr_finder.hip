@@ -7,6 +7,7 @@
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
 #include "elementwise.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 
@@ -17,18 +18,6 @@ namespace mmnn {
 // =====================================================================================================================
 constexpr int CE_THREADS = 256;
 constexpr int CE_WAVES = CE_THREADS / 64;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 struct CeRow {
   double lse;      // log-sum-exp of the row
@@ -43,7 +32,7 @@ __device__ CeRow ce_row(const float* z, const void* target, int kind, long ignor
   CeRow o;
   float m = -INFINITY;
   for (int k = lane; k < c; k += 64) m = fmaxf(m, z[k]);   // fmaxf drops NaN; a NaN logit still poisons the sum below
-  m = wave_max(m);
+  m = wave_reduce(m, FMax{});
   const double md = (double)m;
   double s = 0.0;
   for (int k = lane; k < c; k += 64) s += exp((double)z[k] - md);

@@ -25,6 +25,7 @@
 //                         (n, the constants) only -- not on the alignment, which merely selects 16-byte (VEC = 4) or dword loads.
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 
@@ -140,14 +141,6 @@ __global__ void __launch_bounds__(OM_TPB) occlusion_map_kernel(const OmArgs a) {
   }
 }
 
-// the four waves of a block, in order; valid in thread 0
-__device__ __forceinline__ double block_sum_d(double v, double* lds) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-
 template <int VEC>
 __global__ void __launch_bounds__(CM_TPB) channel_partial_kernel(const float* x, long n, double* partial) {
   __shared__ double lds[CM_TPB / 64];
@@ -165,12 +158,12 @@ __global__ void __launch_bounds__(CM_TPB) channel_partial_kernel(const float* x,
       for (int j = 0; j < m; ++j) acc += (double)xc[i + j];
     }
   }
-  const double t = block_sum_d(acc, lds);
+  const double t = block_reduce<CM_TPB / 64>(acc, lds, Sum{});     // the block's waves in index order
   if (threadIdx.x == 0) partial[(long)blockIdx.y * CM_PARTS + blockIdx.x] = t;
 }
 
 __global__ void __launch_bounds__(64) channel_final_kernel(const double* partial, long n, float* out) {
-  const double t = wave_sum_d(partial[(long)blockIdx.x * CM_PARTS + threadIdx.x]);
+  const double t = wave_sum(partial[(long)blockIdx.x * CM_PARTS + threadIdx.x]);
   if (threadIdx.x == 0) out[blockIdx.x] = (float)(t / (double)n);
 }
 

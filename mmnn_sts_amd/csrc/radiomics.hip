@@ -74,32 +74,6 @@ __device__ __forceinline__ void rad_count(unsigned* h, unsigned digit, bool acti
   }
 }
 
-__device__ __forceinline__ long long rad_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long rad_wave_min(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const long long w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ long long rad_wave_max(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const long long w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ double rad_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ double rad_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-  return v;
-}
-
 enum { RS_N = 0, RS_LO = 1, RS_HI = 4, RS_MOM = 7, RS_BAD = 16, RS_SUM = 17, RS_SQ = 18, RS_MIN = 19, RS_MAX = 20 };
 
 __device__ __forceinline__ unsigned long long rad_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
@@ -199,21 +173,21 @@ __global__ void __launch_bounds__(RAD_TPB) rad_pass_kernel(const RadArgs a) {
   unsigned long long w[RAD_SLOTS];
   int nq = 0;
   if (PHASE == 1) {
-    w[RS_N] = rad_bits(rad_wave_sum(cnt));
-    for (int k = 0; k < 3; ++k) { w[RS_LO + k] = rad_bits(rad_wave_min(lo[k])); w[RS_HI + k] = rad_bits(rad_wave_max(hi[k])); }
-    for (int k = 0; k < 9; ++k) w[RS_MOM + k] = rad_bits(rad_wave_sum(mom[k]));
-    w[RS_BAD] = rad_bits(rad_wave_max(bad));
-    w[RS_SUM] = rad_bits(rad_wave_sum(s[0])); w[RS_SQ] = rad_bits(rad_wave_sum(s[1]));
-    w[RS_MIN] = rad_bits(rad_wave_min(vmin)); w[RS_MAX] = rad_bits(rad_wave_max(vmax));
+    w[RS_N] = rad_bits(wave_sum(cnt));
+    for (int k = 0; k < 3; ++k) { w[RS_LO + k] = rad_bits(wave_reduce(lo[k], Less{})); w[RS_HI + k] = rad_bits(wave_reduce(hi[k], Greater{})); }
+    for (int k = 0; k < 9; ++k) w[RS_MOM + k] = rad_bits(wave_sum(mom[k]));
+    w[RS_BAD] = rad_bits(wave_reduce(bad, Greater{}));
+    w[RS_SUM] = rad_bits(wave_sum(s[0])); w[RS_SQ] = rad_bits(wave_sum(s[1]));
+    w[RS_MIN] = rad_bits(wave_reduce(vmin, Less{})); w[RS_MAX] = rad_bits(wave_reduce(vmax, Greater{}));
     nq = 21;
   } else if (PHASE == 2) {
-    for (int k = 0; k < 4; ++k) w[k] = rad_bits(rad_wave_sum(s[k]));
+    for (int k = 0; k < 4; ++k) w[k] = rad_bits(wave_sum(s[k]));
     nq = 4;
   } else if (PHASE == 5) {
-    w[0] = rad_bits(rad_wave_sum(cnt)); w[1] = rad_bits(rad_wave_sum(s[0]));
+    w[0] = rad_bits(wave_sum(cnt)); w[1] = rad_bits(wave_sum(s[0]));
     nq = 2;
   } else {
-    w[0] = rad_bits(rad_wave_sum(s[0]));
+    w[0] = rad_bits(wave_sum(s[0]));
     nq = 1;
   }
   if (lane == 0)
@@ -510,7 +484,7 @@ __global__ void __launch_bounds__(RAD_TPB) glcm_features_kernel(const RadArgs a)
   // the marginal row sums: mu, then sigma^2 and HX
   double m1[1] = {0.0};
   for (int i = t; i < ng; i += RAD_TPB) m1[0] += (double)(i + 1) * ((double)row[i] / S);
-  rad_block_sum<1>(m1, red);
+  block_reduce<RAD_TPB / 64>(m1, red, Sum{});
   const double mu = m1[0];
   double m2[2] = {0.0, 0.0};
   for (int i = t; i < ng; i += RAD_TPB) {
@@ -518,7 +492,7 @@ __global__ void __launch_bounds__(RAD_TPB) glcm_features_kernel(const RadArgs a)
     m2[0] += di * di * px;
     m2[1] += rad_plogp(px);
   }
-  rad_block_sum<2>(m2, red);
+  block_reduce<RAD_TPB / 64>(m2, red, Sum{});
   const double var = m2[0], HX = -m2[1];
   // the matrix: autocorrelation, joint energy, HXY, HXY1, HXY2
   double m5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -532,7 +506,7 @@ __global__ void __launch_bounds__(RAD_TPB) glcm_features_kernel(const RadArgs a)
     m5[3] += p * lg;
     m5[4] += pp * lg;
   }
-  rad_block_sum<5>(m5, red);
+  block_reduce<RAD_TPB / 64>(m5, red, Sum{});
   const double autoc = m5[0], HXY = -m5[2], HXY1 = -m5[3], HXY2 = -m5[4];
   // p+(k), k = 2..2Ng
   double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -544,7 +518,7 @@ __global__ void __launch_bounds__(RAD_TPB) glcm_features_kernel(const RadArgs a)
     s5[3] += c2 * c * p;
     s5[4] += c2 * c2 * p;
   }
-  rad_block_sum<5>(s5, red);
+  block_reduce<RAD_TPB / 64>(s5, red, Sum{});
   // p-(k), k = 0..Ng-1
   double d8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int q = t; q < ng; q += RAD_TPB) {
@@ -558,14 +532,14 @@ __global__ void __launch_bounds__(RAD_TPB) glcm_features_kernel(const RadArgs a)
     d8[6] += p / (1.0 + k / Ng);
     if (q >= 1) d8[7] += p / (k * k);
   }
-  rad_block_sum<8>(d8, red);
+  block_reduce<RAD_TPB / 64>(d8, red, Sum{});
   const double DA = d8[0];
   double dv[1] = {0.0};
   for (int q = t; q < ng; q += RAD_TPB) {
     const double p = (double)minus[q] / S, c = (double)q - DA;
     dv[0] += c * c * p;
   }
-  rad_block_sum<1>(dv, red);
+  block_reduce<RAD_TPB / 64>(dv, red, Sum{});
   if (t == 0) {
     out[0] = autoc;
     out[1] = mu;
@@ -607,7 +581,7 @@ __global__ void __launch_bounds__(RAD_TPB) rad_final_kernel(const RadArgs a) {
     h2[0] += rad_plogp(p);
     h2[1] += p * p;
   }
-  rad_block_sum<2>(h2, red);
+  block_reduce<RAD_TPB / 64>(h2, red, Sum{});
   if (t == 0) {
     double* f = a.res->firstorder;
     const double m2 = st.cen[1] / n, m3 = st.cen[2] / n, m4 = st.cen[3] / n;

@@ -1,8 +1,10 @@
 // What csrc/radiomics.hip and csrc/radiomics_texture.hip share: the constants, the 13 directions, the state block that the kernels of
-// `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks and the workgroup sum.
+// `mmnn_radiomics` leave in the workspace, the workspace layout and the extent checks.  Their fp64 sums over a workgroup are
+// block_reduce<RAD_TPB / 64>(values, lds, Sum{}) of reduce.hpp: lanes by the butterfly, then the waves in index order.
 #pragma once
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 
@@ -39,44 +41,20 @@ struct RadState {
 };
 
 #if defined(__HIPCC__)
-__device__ __forceinline__ double rad_wave_sum(double v) { return wave_sum_d(v); }
-
-// K sums over the workgroup, the same total in every thread: lanes by the butterfly, then the waves in index order.
-// lds: (RAD_TPB / 64) * K doubles.  Two barriers.
-template <int K>
-__device__ __forceinline__ void rad_block_sum(double (&a)[K], double* lds) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double t = rad_wave_sum(a[k]);
-    if (lane == 0) lds[wave * K + k] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double t = lds[k];
-    for (int w = 1; w < RAD_TPB / 64; ++w) t += lds[w * K + k];
-    a[k] = t;
-  }
-  __syncthreads();
-}
-
 __device__ __forceinline__ double rad_plogp(double p) { return p * log2(p + RAD_EPS); }
 #endif
-
-inline size_t rad_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct RadLayout { size_t state, part, rhist, dirf, bins, total; };
 
 inline RadLayout rad_layout(long n) {
   RadLayout L;
-  size_t off = 0;
-  L.state = off; off += rad_align(sizeof(RadState));
-  L.part = off; off += rad_align((size_t)RAD_SLOTS * RAD_MAX_PARTS * 8);
-  L.rhist = off; off += rad_align((size_t)RAD_RANKS * RAD_DIGITS * 4);
-  L.dirf = off; off += rad_align((size_t)RAD_DIRS * (RAD_NF + 1) * 8);
-  L.bins = off; off += rad_align((size_t)n * 2);
-  L.total = off;
+  Carver cv;
+  L.state = cv.take(sizeof(RadState));
+  L.part = cv.take((size_t)RAD_SLOTS * RAD_MAX_PARTS * 8);
+  L.rhist = cv.take((size_t)RAD_RANKS * RAD_DIGITS * 4);
+  L.dirf = cv.take((size_t)RAD_DIRS * (RAD_NF + 1) * 8);
+  L.bins = cv.take((size_t)n * 2);
+  L.total = cv.cur;
   return L;
 }
 

@@ -19,7 +19,7 @@
 //
 // Determinism.  The four tables are integers, accumulated exactly.  Every fp64 sum runs over a partition fixed by Ng and the extents: a
 // lane adds the rows in ascending order and its columns t, t + 256, ...; a wave folds its lanes by the xor butterfly and the four waves are
-// added in index order (rad_block_sum).  No floating-point atomics.  All index arithmetic is 32-bit (x * y * z < 2^31).
+// added in index order (block_reduce, reduce.hpp).  No floating-point atomics.  All index arithmetic is 32-bit (x * y * z < 2^31).
 #include "ingest_load.hpp"
 #include "radiomics.hpp"
 
@@ -192,7 +192,7 @@ __device__ void tex_matrix_features(const unsigned* P, size_t stride, int ng, in
     a4[2] += r * r;
     a4[3] += jj * (r / Nr);
   }
-  rad_block_sum<4>(a4, red);
+  block_reduce<RAD_TPB / 64>(a4, red, Sum{});
   double b4[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = t; i < ng; i += RAD_TPB) {
     const double g = (double)pg[i], ii = (double)(i + 1);
@@ -201,12 +201,12 @@ __device__ void tex_matrix_features(const unsigned* P, size_t stride, int ng, in
     b4[2] += g * g;
     b4[3] += ii * (g / Nr);
   }
-  rad_block_sum<4>(b4, red);
+  block_reduce<RAD_TPB / 64>(b4, red, Sum{});
   const double mu_r = a4[3], mu_g = b4[3];
   double v2[2] = {0.0, 0.0};
   for (int i = t; i < ng; i += RAD_TPB) { const double c = (double)(i + 1) - mu_g; v2[0] += ((double)pg[i] / Nr) * (c * c); }
   for (int j = t; j < J; j += RAD_TPB) { const double c = (double)(j + 1) - mu_r; v2[1] += ((double)pr[j] / Nr) * (c * c); }
-  rad_block_sum<2>(v2, red);
+  block_reduce<RAD_TPB / 64>(v2, red, Sum{});
   double m5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int i = 0; i < ng; ++i) {
     const double ii = (double)(i + 1) * (double)(i + 1);
@@ -221,7 +221,7 @@ __device__ void tex_matrix_features(const unsigned* P, size_t stride, int ng, in
       m5[4] += cd * (ii * jj);
     }
   }
-  rad_block_sum<5>(m5, red);
+  block_reduce<RAD_TPB / 64>(m5, red, Sum{});
   f[0] = a4[0] / Nr;
   f[1] = a4[1] / Nr;
   f[2] = b4[2] / Nr;
@@ -270,7 +270,7 @@ __device__ void tex_ngtdm_features(const unsigned* n, const unsigned long long* 
     s2[0] += ((double)ni[i] / Nvp) * si[i];
     s2[1] += si[i];
   }
-  rad_block_sum<2>(s2, red);
+  block_reduce<RAD_TPB / 64>(s2, red, Sum{});
   double p4[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = 0; i < ng; ++i) {
     if (ni[i] == 0ull) continue;                                   // (uniform over the workgroup)
@@ -284,7 +284,7 @@ __device__ void tex_ngtdm_features(const unsigned* n, const unsigned long long* 
       p4[3] += (pi + pj) * (dl * dl);
     }
   }
-  rad_block_sum<4>(p4, red);
+  block_reduce<RAD_TPB / 64>(p4, red, Sum{});
   f[0] = s2[0] == 0.0 ? 1.0e6 : 1.0 / s2[0];
   f[1] = *levels == 1u ? 0.0 : (p4[0] / (Ngp * (Ngp - 1.0))) * (s2[1] / Nvp);
   f[2] = p4[1] == 0.0 ? 0.0 : s2[0] / p4[1];
@@ -347,10 +347,10 @@ struct TexLayout { size_t dirf, runs, total; };
 
 TexLayout tex_layout(int L) {
   TexLayout T;
-  size_t off = 0;
-  T.dirf = off; off += rad_align((size_t)RAD_DIRS * RADT_NRL * 8);
-  T.runs = off; off += rad_align(L > RADT_LDS_L ? (size_t)RAD_DIRS * L * 8 : 0);
-  T.total = off;
+  Carver cv;
+  T.dirf = cv.take((size_t)RAD_DIRS * RADT_NRL * 8);
+  T.runs = cv.take(L > RADT_LDS_L ? (size_t)RAD_DIRS * L * 8 : 0);
+  T.total = cv.cur;
   return T;
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 
@@ -16,16 +17,10 @@ struct ConvGeom {
   int kd, kh, kw, sd, sh, sw, pd, ph, pw;
 };
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 // element-wise dropout keep-scale of element `idx` (nn.Dropout semantics, models/resnet.py:128,163-169)
 __device__ __forceinline__ float elem_drop_scale(uint64_t seed, long idx, float p) {
   if (p <= 0.f) return 1.f;
-  const float u = (float)(mix64(seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(idx + 1))) >> 40) * (1.0f / 16777216.0f);
+  const float u = unit24(mix64((seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(idx + 1))) + 0x9E3779B97F4A7C15ull));
   return u < p ? 0.f : 1.f / (1.f - p);
 }
 
@@ -167,7 +162,7 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(int N, int C, long V, con
     const float t = p[v];
     s += t; q = fmaf(t, t, q);
   }
-  const double sd = wave_sum_d((double)s), qd = wave_sum_d((double)q);
+  const double sd = wave_sum((double)s), qd = wave_sum((double)q);
   if ((threadIdx.x & 63) == 0) { atomicAdd(sums + c, sd); atomicAdd(sums + C + c, qd); }
 }
 // save[0][c] = mean, save[1][c] = rstd; running statistics updated with the UNBIASED variance (torch.nn.BatchNorm3d)
@@ -220,7 +215,7 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(int N, int C, long V
     const float d = bn_dz(dout, out, base + v, relu, drop_p, seed);
     s += d; q = fmaf(d, (x[base + v] - mean) * rstd, q);
   }
-  const double sd = wave_sum_d((double)s), qd = wave_sum_d((double)q);
+  const double sd = wave_sum((double)s), qd = wave_sum((double)q);
   if ((threadIdx.x & 63) == 0) { atomicAdd(sums + c, sd); atomicAdd(sums + C + c, qd); }
 }
 // pass 2: dx = gamma * rstd * (dz - S1/n - xhat * S2/n) (training) or gamma * rstd * dz (eval);  dres = dz;  dgamma = S2, dbeta = S1

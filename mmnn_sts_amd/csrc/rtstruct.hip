@@ -20,6 +20,8 @@
 //                     Contour records that point outside `points` and slice ranges outside `contours` are ignored, not followed.
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "mask_bytes.hpp"
+#include "reduce.hpp"
 
 #include <cmath>
 
@@ -49,13 +51,10 @@ __device__ __forceinline__ int rc_group_start(const uint8_t* row, int span0, int
   return span0 - (int)((uintptr_t)(row + span0) & 15) + lane * 16;
 }
 
-// four parity bits -> four bytes of 0 / 1 (the four products occupy disjoint bit ranges: no carries)
-__device__ __forceinline__ unsigned rc_spread(unsigned b) { return ((b & 0xFu) * 0x00204081u) & 0x01010101u; }
-
 __global__ void __launch_bounds__(RC_TPB) rasterize_kernel(const RcArgs a) {
   __shared__ double ex0[RC_CHUNK], ey0[RC_CHUNK], ex1[RC_CHUNK], ey1[RC_CHUNK];
   __shared__ double xlist[RC_WAVES][64];
-  __shared__ double ylo[RC_WAVES], yhi[RC_WAVES];
+  __shared__ double yred[2 * RC_WAVES];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   unsigned b = blockIdx.x;
@@ -76,7 +75,7 @@ __global__ void __launch_bounds__(RC_TPB) rasterize_kernel(const RcArgs a) {
   while (true) {
     // ---- stage up to one chunk of edges, contour after contour
     int fill = 0;
-    double lo = INFINITY, hi = -INFINITY;
+    double yr[2] = {INFINITY, -INFINITY};    // min, max of the chunk's y
     while (c < c1 && fill < RC_CHUNK) {
       const long first = a.contours[2 * c];
       int n = a.contours[2 * c + 1];
@@ -88,23 +87,16 @@ __global__ void __launch_bounds__(RC_TPB) rasterize_kernel(const RcArgs a) {
         const long p = first + e, q = first + (e + 1 == n ? 0 : e + 1);
         const double x0 = a.points[2 * p], y0 = a.points[2 * p + 1], x1 = a.points[2 * q], y1 = a.points[2 * q + 1];
         ex0[fill + t] = x0; ey0[fill + t] = y0; ex1[fill + t] = x1; ey1[fill + t] = y1;
-        lo = fmin(lo, fmin(y0, y1));
-        hi = fmax(hi, fmax(y0, y1));
+        yr[0] = fmin(yr[0], fmin(y0, y1));
+        yr[1] = fmax(yr[1], fmax(y0, y1));
       }
       if (take > 0) { fill += take; e0 += take; }
       if (e0 >= n) { ++c; e0 = 0; }
     }
     if (fill == 0) break;
     // ---- the chunk's y range
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo = fmin(lo, __shfl_xor(lo, o, 64));
-      hi = fmax(hi, __shfl_xor(hi, o, 64));
-    }
-    if (lane == 0) { ylo[wave] = lo; yhi[wave] = hi; }
-    __syncthreads();
-    lo = fmin(fmin(ylo[0], ylo[1]), fmin(ylo[2], ylo[3]));
-    hi = fmax(fmax(yhi[0], yhi[1]), fmax(yhi[2], yhi[3]));
+    block_reduce<RC_WAVES>(yr, yred, FMinMax{});     // (its barriers also publish the staged edges)
+    const double lo = yr[0], hi = yr[1];
     // ---- the band's rows against the chunk
 #pragma unroll
     for (int r = 0; r < RC_ROWS; ++r) {
@@ -157,14 +149,7 @@ __global__ void __launch_bounds__(RC_TPB) rasterize_kernel(const RcArgs a) {
     const int i0 = rc_group_start(row, span0, lane);
     const int ib = i0 > span0 ? i0 : span0, ie = i0 + 16 < span1 ? i0 + 16 : span1;
     if (ib >= ie) continue;
-    const unsigned w = bits[r];
-    if (ie - ib == 16) {
-      uint4 v;
-      v.x = rc_spread(w); v.y = rc_spread(w >> 4); v.z = rc_spread(w >> 8); v.w = rc_spread(w >> 12);
-      *reinterpret_cast<uint4*>(row + i0) = v;
-    } else {
-      for (int i = ib; i < ie; ++i) row[i] = (uint8_t)((w >> (i - i0)) & 1u);
-    }
+    store_mask_bits(row + i0, ib - i0, ie - i0, bits[r], 1u);
   }
 }
 

@@ -18,6 +18,7 @@
 //                         No LDS, no atomics.
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "mask_bytes.hpp"
 
 namespace mmnn {
 
@@ -34,9 +35,6 @@ struct UfArgs {
   unsigned lead;                            // out & 15
   unsigned one;                             // 1..255
 };
-
-// four bits -> four bytes of 0 / 1 (the four products occupy disjoint bit ranges: no carries)
-__device__ __forceinline__ unsigned uf_spread(unsigned b) { return ((b & 0xFu) * 0x00204081u) & 0x01010101u; }
 
 // bits [b, b + n) of the stream, 1 <= n <= 16, in the low bits of the result (bit b lowest)
 __device__ __forceinline__ unsigned uf_run(const uint8_t* bits, long b, int n) {
@@ -73,13 +71,7 @@ __global__ void __launch_bounds__(UF_TPB) unpack_frames_kernel(const UfArgs a) {
     ++k;
     p = 0u;
   }
-  if (oe - ob == 16u) {
-    uint4 v;
-    v.x = uf_spread(m) * a.one; v.y = uf_spread(m >> 4) * a.one; v.z = uf_spread(m >> 8) * a.one; v.w = uf_spread(m >> 12) * a.one;
-    *reinterpret_cast<uint4*>(a.out + o0) = v;
-  } else {
-    for (unsigned i = ob; i < oe; ++i) a.out[i] = (uint8_t)(((m >> (i - (unsigned)o0)) & 1u) * a.one);
-  }
+  store_mask_bits(a.out + o0, (int)((long)ob - o0), (int)((long)oe - o0), m, a.one);
 }
 
 }  // namespace mmnn

@@ -1,6 +1,7 @@
 // Stem kernels: conv0 (7x7x7, stride 2) forward on fp32 MFMA, BN+ReLU+max-pool forward/backward, conv0 weight
 // gradient on fp32 MFMA.  Reference: models/densenet.py:199-202 and their autograd adjoints (main.py:469).
 #include "stem.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 

@@ -10,6 +10,7 @@
 
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace mmnn {
 

@@ -18,6 +18,7 @@
 #include "../../include/mmnn_sts.h"
 #include "area.hpp"
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <math.h>
 
@@ -85,41 +86,28 @@ struct TfMinmaxArgs {
 };
 
 // ---- block helpers -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_minmax(float& lo, float& hi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-  }
+// All threads call; every thread returns the block's (min, max).  The LDS of the reduction (TF_MM_LDS floats) is the caller's.
+constexpr int TF_MM_LDS = 2 * (TF_TPB / 64);
+__device__ __forceinline__ void block_minmax(float& lo, float& hi, float* red) {
+  float v[2] = {lo, hi};
+  block_reduce<TF_TPB / 64>(v, red, FMinMax{});
+  lo = v[0]; hi = v[1];
 }
 
-// All threads call; every thread returns the block's (min, max).
-__device__ __forceinline__ void block_minmax(float& lo, float& hi) {
-  __shared__ float2 red[TF_TPB / 64];
-  wave_minmax(lo, hi);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wave] = make_float2(lo, hi);
-  __syncthreads();
-  lo = red[0].x; hi = red[0].y;
-#pragma unroll
-  for (int k = 1; k < TF_TPB / 64; ++k) { lo = fminf(lo, red[k].x); hi = fmaxf(hi, red[k].y); }
-}
-
-__device__ __forceinline__ void store_partial(float2* part_out, int s, float lo, float hi) {
-  block_minmax(lo, hi);
+__device__ __forceinline__ void store_partial(float2* part_out, int s, float lo, float hi, float* red) {
+  block_minmax(lo, hi, red);
   if (part_out && threadIdx.x == 0) part_out[s * TF_MAXP + blockIdx.x] = make_float2(lo, hi);
 }
 
 // (min, max) of sample s's input; then, with a pending Normalize / ScaleIntensity, the affine y = A x + B they form and the
 // (min, max) of y.  Normalize: (x - mean M) / (std M), M = max(x) (its sign is kept); ScaleIntensity: (y - min) / (max - min), zeros
 // when max == min.
-__device__ void load_mm(const TfMM& mm, int s, float& lo, float& hi, float& A, float& B) {
+__device__ void load_mm(const TfMM& mm, int s, float& lo, float& hi, float& A, float& B, float* red) {
   A = 1.f; B = 0.f; lo = 0.f; hi = 0.f;
   if (!mm.part) return;
   float l = INFINITY, h = -INFINITY;
   if ((int)threadIdx.x < mm.p) { const float2 v = mm.part[s * TF_MAXP + threadIdx.x]; l = v.x; h = v.y; }
-  block_minmax(l, h);
+  block_minmax(l, h, red);
   lo = l; hi = h;
   if (!mm.norm && !mm.scale) return;
   double a = 1.0, b = 0.0, ylo = l, yhi = h;
@@ -140,6 +128,7 @@ __device__ void load_mm(const TfMM& mm, int s, float& lo, float& hi, float& A, f
 
 // ---- passes ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TF_TPB) tf_minmax_kernel(const TfMinmaxArgs a) {
+  __shared__ float red[TF_MM_LDS];
   const int s = blockIdx.y;
   const float* src = a.src + s * a.stride;
   float lo = INFINITY, hi = -INFINITY;
@@ -154,13 +143,14 @@ __global__ void __launch_bounds__(TF_TPB) tf_minmax_kernel(const TfMinmaxArgs a)
   } else {
     for (int i = blockIdx.x * TF_TPB + threadIdx.x; i < a.count; i += step) { lo = fminf(lo, src[i]); hi = fmaxf(hi, src[i]); }
   }
-  store_partial(a.part_out, s, lo, hi);
+  store_partial(a.part_out, s, lo, hi, red);
 }
 
 __global__ void __launch_bounds__(TF_TPB) tf_rotate_kernel(const TfRotArgs a) {
+  __shared__ float red[TF_MM_LDS];
   const int s = blockIdx.y;
   float lo, hi, A, B;
-  load_mm(a.mm, s, lo, hi, A, B);
+  load_mm(a.mm, s, lo, hi, A, B, red);
   const float* src = a.src + s * a.sstride;
   float* dst = a.dst + s * a.dstride;
   const int HW = a.H * a.W, V = a.D * HW, count = a.C * V;
@@ -196,15 +186,16 @@ __global__ void __launch_bounds__(TF_TPB) tf_rotate_kernel(const TfRotArgs a) {
     dst[e] = val;
     olo = fminf(olo, val); ohi = fmaxf(ohi, val);
   }
-  store_partial(a.part_out, s, olo, ohi);
+  store_partial(a.part_out, s, olo, ohi, red);
 }
 
 // (the window rule of the area resize, `area_window`, is csrc/area.hpp: the scan ingest uses the same one)
 
 __global__ void __launch_bounds__(TF_TPB) tf_area_kernel(const TfAreaArgs a) {
+  __shared__ float red[TF_MM_LDS];
   const int s = blockIdx.y;
   float lo, hi, A, B;
-  load_mm(a.mm, s, lo, hi, A, B);
+  load_mm(a.mm, s, lo, hi, A, B, red);
   const float* src = a.src + s * a.sstride;
   float* dst = a.dst + s * a.dstride;
   const int HW = a.H * a.W, V = a.D * HW;
@@ -231,10 +222,11 @@ __global__ void __launch_bounds__(TF_TPB) tf_area_kernel(const TfAreaArgs a) {
     dst[e] = val;
     olo = fminf(olo, val); ohi = fmaxf(ohi, val);
   }
-  store_partial(a.part_out, s, olo, ohi);
+  store_partial(a.part_out, s, olo, ohi, red);
 }
 
 __global__ void __launch_bounds__(TF_TPB) tf_gauss_kernel(const TfGaussArgs a) {
+  __shared__ float red[TF_MM_LDS];
   const int s = blockIdx.y;
   const float* src = a.src + s * a.stride;
   float* dst = a.dst + s * a.stride;
@@ -262,25 +254,24 @@ __global__ void __launch_bounds__(TF_TPB) tf_gauss_kernel(const TfGaussArgs a) {
     dst[e] = acc;
     olo = fminf(olo, acc); ohi = fmaxf(ohi, acc);
   }
-  if (a.part_out) store_partial(a.part_out, s, olo, ohi);
+  if (a.part_out) store_partial(a.part_out, s, olo, ohi, red);
 }
 
 // counter-based standard normal for (seed, sample, element): splitmix64, then Box-Muller on two 24-bit uniforms
 __device__ __forceinline__ float tf_normal(uint64_t seed, int n, int e) {
   uint64_t x = seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(n + 1));
   x += 0xD1B54A32D192ED03ull * (uint64_t)(uint32_t)e;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x ^= x >> 31;
+  x = mix64(x);
   const float u1 = (float)((x >> 40) + 1) * (1.0f / 16777216.0f);          // (0, 1]
-  const float u2 = (float)((x >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);    // [0, 1)
+  const float u2 = unit24(x << 32);                                         // [0, 1): bits 8..31
   return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
 __global__ void __launch_bounds__(TF_TPB) tf_intensity_kernel(const TfIntArgs a) {
+  __shared__ float red[TF_MM_LDS];
   const int s = blockIdx.y;
   float lo, hi, A, B;
-  load_mm(a.mm, s, lo, hi, A, B);
+  load_mm(a.mm, s, lo, hi, A, B, red);
   const float* src = a.src + s * a.stride;
   float* dst = a.dst + s * a.stride;
   const int f = a.flags[s];
@@ -322,8 +313,6 @@ struct WsLayout {
   size_t part_r, part_s, sp0, sp1, g0, g1, g2, total;
 };
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 WsLayout ws_layout(const mmnn_transform_desc& d) {
   const int g = d.n < TF_G ? d.n : TF_G;
   const size_t vin = (size_t)g * d.c * d.d * d.h * d.w * sizeof(float);
@@ -332,15 +321,15 @@ WsLayout ws_layout(const mmnn_transform_desc& d) {
   const bool spatial = d.stages & (MMNN_TF_ROTATE | MMNN_TF_FLIP | MMNN_TF_ZOOM);
   const int ng = (d.stages & MMNN_TF_SHARPEN) ? 3 : ((d.stages & MMNN_TF_SMOOTH) ? 2 : 0);
   WsLayout L;
-  size_t off = 0;
-  L.part_r = off; off += align256(part);
-  L.part_s = off; off += align256(part);
-  L.sp0 = off; off += spatial ? align256(vin) : 0;
-  L.sp1 = off; off += spatial ? align256(vin) : 0;
-  L.g0 = off; off += ng >= 1 ? align256(vout) : 0;
-  L.g1 = off; off += ng >= 2 ? align256(vout) : 0;
-  L.g2 = off; off += ng >= 3 ? align256(vout) : 0;
-  L.total = off;
+  Carver cv;
+  L.part_r = cv.take(part);
+  L.part_s = cv.take(part);
+  L.sp0 = cv.take(spatial ? vin : 0);
+  L.sp1 = cv.take(spatial ? vin : 0);
+  L.g0 = cv.take(ng >= 1 ? vout : 0);
+  L.g1 = cv.take(ng >= 2 ? vout : 0);
+  L.g2 = cv.take(ng >= 3 ? vout : 0);
+  L.total = cv.cur;
   return L;
 }
 
