@@ -658,7 +658,7 @@ int mmnn_radiomics(const mmnn_radiomics_desc* d, const void* scan, const void* m
  * partition and in an order fixed by the extents and Ng alone, without floating-point atomics: repeated calls are bit-identical.
  * ws2: mmnn_radiomics_texture_workspace_bytes bytes, aligned to 256.  Refused as mmnn_radiomics refuses (status 1; the size returns -1),
  * before any launch: a null pointer, a bad extent, max_bins, type code or bin_width, a buffer not aligned to its element size.
- * GLSZM, mesh-based shape features and the GLCM's MCC are not computed. */
+ * The size-zone matrix is the call below; mesh-based shape features and the GLCM's MCC are not computed. */
 #define MMNN_RADIOMICS_GLRLM 16
 #define MMNN_RADIOMICS_GLDM 14
 #define MMNN_RADIOMICS_NGTDM 5
@@ -672,6 +672,54 @@ int64_t mmnn_radiomics_texture_workspace_bytes(int32_t x, int32_t y, int32_t z, 
 int mmnn_radiomics_texture(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws,
                            mmnn_radiomics_texture_result* out, uint32_t* glrlm, uint32_t* gldm, uint32_t* ngtdm_n, uint64_t* ngtdm_s,
                            void* ws2, void* stream);
+
+/* ---- the grey-level size-zone matrix (GLSZM) of the same pair, from a connected-component labelling on the device
+ * (csrc/radiomics_zones.hip).  The call runs after mmnn_radiomics on the same stream, like mmnn_radiomics_texture: `ws` and `result` are
+ * the workspace and the device result block that a mmnn_radiomics call with the same descriptor has filled earlier on `stream`.  The bin
+ * volume (uint16, 0 outside the ROI), Ng, n and the flags are read from the workspace ON THE DEVICE: no host wait, no read-back.
+ *   zones    a zone is a maximal set of ROI voxels that share one bin and are connected through the 26 neighbours inside the volume
+ *            (PyRadiomics' default in 3-D: the 13 directions at distance 1).  The neighbour test is made on (x, y, z): the last voxel of a
+ *            row or slice never connects to the first of the next.
+ *   labels   [x*y*z] uint32 in the scan's layout: 0 outside the ROI, otherwise 1 + the smallest linear index among the voxels of the
+ *            voxel's zone.  The label is canonical: it does not depend on the order in which the zones were merged.
+ *   sizes    [x*y*z] uint32: the zone's voxel count at its smallest-index voxel, 0 everywhere else.  sum sizes = n.
+ *   levels   [max_bins] uint32: pg(i), the number of zones of bin i + 1.
+ *   The three tables are the accumulation targets; the call zeroes them first, and they are exact.
+ *   out      P(i, j) the number of zones of level i and size j, Nz = sum P, Np = n, pg(i) = sum_j P, ps(j) = sum_i P, p = P / Nz,
+ *            mu_i = sum i pg / Nz, mu_j = sum j ps / Nz = n / Nz, eps = 2^-52.  The six integers, exact (all below 2^62: n < 2^31,
+ *            sum ps^2 <= Nz^2, sum over zones of size^2 <= n^2): nz = Nz; n_keys, the number of distinct (i, j) with P > 0; max_size;
+ *            sum_pg2 = sum_i pg^2; sum_ps2 = sum_j ps^2; sum_j2 = sum over zones of size^2 = sum_j ps j^2.  glszm, in this order:
+ *            SmallAreaEmphasis sum ps / j^2 / Nz; LargeAreaEmphasis sum ps j^2 / Nz; GrayLevelNonUniformity sum pg^2 / Nz;
+ *            GrayLevelNonUniformityNormalized sum pg^2 / Nz^2; SizeZoneNonUniformity sum ps^2 / Nz; SizeZoneNonUniformityNormalized
+ *            sum ps^2 / Nz^2; ZonePercentage Nz / Np; GrayLevelVariance sum (pg / Nz)(i - mu_i)^2; ZoneVariance sum (ps / Nz)(j - mu_j)^2;
+ *            ZoneEntropy -sum sum p log2(p + eps); LowGrayLevelZoneEmphasis sum pg / i^2 / Nz; HighGrayLevelZoneEmphasis sum pg i^2 / Nz;
+ *            SmallAreaLowGrayLevelEmphasis sum sum P / (i^2 j^2) / Nz; SmallAreaHighGrayLevelEmphasis sum sum P i^2 / j^2 / Nz;
+ *            LargeAreaLowGrayLevelEmphasis sum sum P j^2 / i^2 / Nz; LargeAreaHighGrayLevelEmphasis sum sum P i^2 j^2 / Nz.
+ *            One matrix: nothing is averaged over directions, and no feature degenerates while n > 0.
+ *   flags    with overflow, nonfinite or empty set by mmnn_radiomics the 16 doubles are NaN, the six integers and the three tables zero.
+ * How it is built: union-find on a parent array in ws3 (every write is an atomic minimum with a smaller index, so parent[v] <= v always
+ * holds, every walk and retry is bounded and the final root is the zone's smallest index); P never exists densely: the distinct (i, j)
+ * are at most sqrt(2 n Ng) <= sqrt(2 x y z max_bins), and they are counted in an open-addressing table in ws3 of the next power of two
+ * above twice that bound, which therefore never fills; a second table keyed by j holds ps.  Both live in global memory at every Ng.
+ * The integers are accumulated exactly (uint32 / uint64 atomic add, minimum and maximum); every fp64 sum runs over the distinct keys in a
+ * partition and an order fixed by the extents, Ng and the exact integer tables alone, without floating-point atomics: repeated calls are
+ * bit-identical.  ws3: mmnn_radiomics_zones_workspace_bytes bytes, aligned to 256.  Refused as mmnn_radiomics_texture refuses (status 1;
+ * the size returns -1), before any launch: a null pointer, a bad extent, max_bins, type code or bin_width, a buffer not aligned to its
+ * element size.  Zones per slice (2-D), other distances, mesh-based shape features and the GLCM's MCC are not computed. */
+#define MMNN_RADIOMICS_GLSZM 16
+typedef struct {
+  int64_t nz;        /* number of zones = sum P */
+  int64_t n_keys;    /* number of distinct (level, size) pairs */
+  int64_t max_size;  /* largest zone */
+  int64_t sum_pg2;   /* sum_i pg(i)^2 */
+  int64_t sum_ps2;   /* sum_j ps(j)^2 */
+  int64_t sum_j2;    /* sum over zones of size^2 */
+  double glszm[MMNN_RADIOMICS_GLSZM];
+} mmnn_radiomics_zones_result;
+int64_t mmnn_radiomics_zones_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t max_bins);
+int mmnn_radiomics_zones(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws,
+                         mmnn_radiomics_zones_result* out, uint32_t* labels, uint32_t* sizes, uint32_t* levels,
+                         void* ws3, void* stream);
 
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */

@@ -280,7 +280,7 @@ def extract_radiomics_if_needed(parser, args):
     from mmnn_sts_amd.data.ImageDatasets import ImageDataset
     if not torch.cuda.is_available():
         raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
-    rc, classes = parser.radiomicsConfig(), parser.radiomicsClasses()
+    rc, classes, glszm = parser.radiomicsConfig(), parser.radiomicsClasses(), parser.radiomicsZones()
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
     prefixes = ("t1_", "t2_") if len(paths) == 2 else ("",)
@@ -289,7 +289,7 @@ def extract_radiomics_if_needed(parser, args):
         ds = ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
         threshold = (parser.config.get("Data") or {}).get("mask_threshold")
         part = radiomics.extract_tree(ds, torch.device("cuda", 0), None, rc["bin_width"], rc["max_bins"],
-                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes)
+                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes, glszm=glszm)
         if rows is None:
             rows = part
         else:

@@ -145,6 +145,8 @@ RADIOMICS_DIRECTIONS, RADIOMICS_FIRSTORDER, RADIOMICS_GLCM, RADIOMICS_MAX_BINS =
 RADIOMICS_RESULT_INT64, RADIOMICS_RESULT_BYTES = 20, (20 + 10 + 17 + 23) * 8      # mmnn_radiomics_result: 20 int64, then 50 doubles
 RADIOMICS_GLRLM, RADIOMICS_GLDM, RADIOMICS_NGTDM, RADIOMICS_NEIGHBOURS = 16, 14, 5, 27
 RADIOMICS_TEXTURE_BYTES = (16 + 14 + 5) * 8                                       # mmnn_radiomics_texture_result: 35 doubles
+RADIOMICS_GLSZM = 16
+RADIOMICS_ZONES_BYTES = (6 + 16) * 8                                              # mmnn_radiomics_zones_result: 6 int64, then 16 doubles
 
 
 class RadiomicsDesc(Structure):
@@ -272,6 +274,10 @@ def lib():
     L.mmnn_radiomics_texture_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
     L.mmnn_radiomics_texture.restype = c_int32
     L.mmnn_radiomics_texture.argtypes = [POINTER(RadiomicsDesc)] + [c_void_p] * 9
+    L.mmnn_radiomics_zones_workspace_bytes.restype = c_int64
+    L.mmnn_radiomics_zones_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.mmnn_radiomics_zones.restype = c_int32
+    L.mmnn_radiomics_zones.argtypes = [POINTER(RadiomicsDesc)] + [c_void_p] * 8
     L.mmnn_channel_means.restype = c_int32
     L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64

@@ -61,19 +61,6 @@ __device__ __forceinline__ int rad_bin(double v, double low, double bw) {
   return b < 1.0 ? 1 : (b > 65535.0 ? 65535 : (int)b);
 }
 
-// One count per active lane into h[digit].  Called by whole waves; a wave whose active lanes agree sends one add of their number.
-__device__ __forceinline__ void rad_count(unsigned* h, unsigned digit, bool active) {
-  const unsigned long long m = __ballot(active);
-  if (m == 0ull) return;
-  const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-  const unsigned d0 = (unsigned)__shfl((int)digit, leader, 64);
-  if (__ballot(active && digit != d0) == 0ull) {
-    if (lane == leader) atomicAdd(&h[d0], (unsigned)__popcll(m));
-  } else if (active) {
-    atomicAdd(&h[digit], 1u);
-  }
-}
-
 enum { RS_N = 0, RS_LO = 1, RS_HI = 4, RS_MOM = 7, RS_BAD = 16, RS_SUM = 17, RS_SQ = 18, RS_MIN = 19, RS_MAX = 20 };
 
 __device__ __forceinline__ unsigned long long rad_bits(double v) { return (unsigned long long)__double_as_longlong(v); }

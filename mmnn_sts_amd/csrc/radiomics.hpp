@@ -1,6 +1,7 @@
-// What csrc/radiomics.hip and csrc/radiomics_texture.hip share: the constants, the 13 directions, the state block that the kernels of
-// `mmnn_radiomics` leave in the workspace, the workspace layout and the extent checks.  Their fp64 sums over a workgroup are
-// block_reduce<RAD_TPB / 64>(values, lds, Sum{}) of reduce.hpp: lanes by the butterfly, then the waves in index order.
+// What csrc/radiomics.hip, csrc/radiomics_texture.hip and csrc/radiomics_zones.hip share: the constants, the 13 directions, the state
+// block that the kernels of `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks and the wave-folded count.
+// Their fp64 sums over a workgroup are block_reduce<RAD_TPB / 64>(values, lds, Sum{}) of reduce.hpp: lanes by the butterfly, then the
+// waves in index order.
 #pragma once
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
@@ -42,6 +43,19 @@ struct RadState {
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ double rad_plogp(double p) { return p * log2(p + RAD_EPS); }
+
+// One count per active lane into h[digit].  Called by whole waves; a wave whose active lanes agree sends one add of their number.
+__device__ __forceinline__ void rad_count(unsigned* h, unsigned digit, bool active) {
+  const unsigned long long m = __ballot(active);
+  if (m == 0ull) return;
+  const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
+  const unsigned d0 = (unsigned)__shfl((int)digit, leader, 64);
+  if (__ballot(active && digit != d0) == 0ull) {
+    if (lane == leader) atomicAdd(&h[d0], (unsigned)__popcll(m));
+  } else if (active) {
+    atomicAdd(&h[digit], 1u);
+  }
+}
 #endif
 
 struct RadLayout { size_t state, part, rhist, dirf, bins, total; };

@@ -87,6 +87,14 @@ class Parser:
             raise ConfigurationError('Radiomics.classes must be a list drawn from glrlm, gldm, ngtdm, got {!r}'.format(classes))
         return texture_classes(classes)
 
+    def radiomicsZones(self):
+        """`Radiomics: glszm`: whether the 16 size-zone (GLSZM) columns are extracted behind the other classes (false)."""
+        rad = self.config.get('Radiomics') or {}
+        glszm = rad.get('glszm', False)
+        if not isinstance(glszm, bool):
+            raise ConfigurationError('Radiomics.glszm must be true or false, got {!r}'.format(glszm))
+        return glszm
+
     def _radiomicsExcluded(self):
         rm = self.config.get('RadiomicsModel') or {}
         return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])

@@ -1,11 +1,12 @@
-"""Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip) and of
-`mmnn_radiomics_texture` (csrc/radiomics_texture.hip).
+"""Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip), of
+`mmnn_radiomics_texture` (csrc/radiomics_texture.hip) and of `mmnn_radiomics_zones` (csrc/radiomics_zones.hip).
 
     extract(scan, mask, device)            enqueue one extraction; the result holds device tensors, nothing is read back
     finish(result, affine)                 one read-back -> {feature name: float}: adds TotalEnergy and the voxel-based shape features
     extract_tree(dataset, device, out)     every patient and modality of an image dataset -> a csv (`MRN`, then the features)
-    feature_names(classes)                 the columns: FEATURE_NAMES, then those of the requested texture classes
-    python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] --out radiomics.csv
+    feature_names(classes, glszm)          the columns: FEATURE_NAMES, then those of the requested texture classes, then the size-zone ones
+    python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] [--glszm]
+                                     --out radiomics.csv
 
 Upstream reads such a csv (`Data: rad_loc`, data/RadiomicsDatasets.py) and leaves its extraction to PyRadiomics; here the table is built
 from the very pair the image path ingests, through the same mask routes (NIfTI mask, resampled mask, DICOM mask series, RTSTRUCT, SEG:
@@ -15,8 +16,14 @@ diameters) and the GLCM's MCC are out of scope.  What the numbers are pinned to 
 
 `classes` (`Radiomics: classes`, `--classes`; empty by default) adds the columns of further texture classes, computed by a second call on
 the same stream from the bin volume the first one left on the device: `glrlm` (16 run-length features), `gldm` (14 dependence features,
-alpha 0) and `ngtdm` (5), 82 columns per modality with all three.  GLSZM, the mesh-based shape features and the GLCM's MCC stay out of
-scope.  These too are pinned to a numpy restatement (tests/_radiomics_texture_ref.py); **parity with PyRadiomics is unpinned**.
+alpha 0) and `ngtdm` (5), 82 columns per modality with all three.  These too are pinned to a numpy restatement
+(tests/_radiomics_texture_ref.py); **parity with PyRadiomics is unpinned**.
+
+`glszm` (`Radiomics: glszm`, `--glszm`; off by default) is a switch of its own beside `classes`: a third call on the same stream labels
+the 26-connected zones of equal bin on the device and appends the 16 size-zone features (`original_glszm_*`) behind the other classes: 63
+columns per modality alone, 98 with all three classes.  They are pinned to the numpy / scipy restatement in
+tests/_radiomics_zones_ref.py; **parity with PyRadiomics is unpinned** here too.  The mesh-based shape features and the GLCM's MCC stay out
+of scope.
 """
 import argparse
 import csv
@@ -53,6 +60,10 @@ GLDM = ("SmallDependenceEmphasis", "LargeDependenceEmphasis", "GrayLevelNonUnifo
         "HighGrayLevelEmphasis", "SmallDependenceLowGrayLevelEmphasis", "SmallDependenceHighGrayLevelEmphasis",
         "LargeDependenceLowGrayLevelEmphasis", "LargeDependenceHighGrayLevelEmphasis")
 NGTDM = ("Coarseness", "Contrast", "Busyness", "Complexity", "Strength")
+GLSZM = ("SmallAreaEmphasis", "LargeAreaEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized", "SizeZoneNonUniformity",
+         "SizeZoneNonUniformityNormalized", "ZonePercentage", "GrayLevelVariance", "ZoneVariance", "ZoneEntropy", "LowGrayLevelZoneEmphasis",
+         "HighGrayLevelZoneEmphasis", "SmallAreaLowGrayLevelEmphasis", "SmallAreaHighGrayLevelEmphasis", "LargeAreaLowGrayLevelEmphasis",
+         "LargeAreaHighGrayLevelEmphasis")
 TEXTURE_CLASSES = ("glrlm", "gldm", "ngtdm")
 _TEXTURE = {"glrlm": GLRLM, "gldm": GLDM, "ngtdm": NGTDM}
 FEATURE_NAMES = tuple([f"original_firstorder_{n}" for n in FIRSTORDER] + [f"original_shape_{n}" for n in SHAPE]
@@ -72,13 +83,16 @@ def texture_classes(classes) -> tuple:
     unknown = [c for c in names if c not in TEXTURE_CLASSES]
     if unknown:
         raise ConfigurationError(f"radiomics: unknown texture class {', '.join(repr(c) for c in unknown)}: the valid ones are "
-                                 + ", ".join(TEXTURE_CLASSES))
+                                 + ", ".join(TEXTURE_CLASSES) + (" (the size-zone features have a switch of their own: `Radiomics: glszm: true`, "
+                                                                 "`--glszm`)" if "glszm" in unknown else ""))
     return tuple(c for c in TEXTURE_CLASSES if c in names)
 
 
-def feature_names(classes=()) -> tuple:
-    """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes."""
-    return FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
+def feature_names(classes=(), glszm=False) -> tuple:
+    """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes, then with `glszm`
+    `original_glszm_*`."""
+    return (FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
+            + (tuple(f"original_glszm_{n}" for n in GLSZM) if glszm else ()))
 
 
 @dataclass
@@ -86,7 +100,8 @@ class RadiomicsResult:
     """One extraction, still on the device.  `block`: the bytes of mmnn_radiomics_result; `hist` (max_bins,) and `glcm`
     (13, max_bins, max_bins) int32 views of the uint32 counts; `shape`, `affine`: the scan's grid.  With texture classes: `texture`, the
     bytes of mmnn_radiomics_texture_result; `glrlm` (13, max_bins, L), `gldm` and `ngtdm_n` (max_bins, 27) int32 views of the uint32 counts,
-    `ngtdm_s` (max_bins, 27) int64; `classes`, the requested ones (the device computes all three)."""
+    `ngtdm_s` (max_bins, 27) int64; `classes`, the requested ones (the device computes all three).  With `glszm`: `zones`, the bytes of
+    mmnn_radiomics_zones_result; `labels` and `sizes` (x * y * z,) and `levels` (max_bins,) int32 views of the uint32 tables."""
     block: torch.Tensor
     hist: torch.Tensor
     glcm: torch.Tensor
@@ -102,6 +117,12 @@ class RadiomicsResult:
     ngtdm_s: Optional[torch.Tensor] = None
     texture_workspace: Optional[torch.Tensor] = None
     classes: tuple = ()
+    zones: Optional[torch.Tensor] = None
+    labels: Optional[torch.Tensor] = None
+    sizes: Optional[torch.Tensor] = None
+    levels: Optional[torch.Tensor] = None
+    zones_workspace: Optional[torch.Tensor] = None
+    glszm: bool = False
 
 
 def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
@@ -112,11 +133,12 @@ def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) ->
 
 
 def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS, index_map=None,
-            threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=()) -> RadiomicsResult:
+            threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=(), glszm: bool = False) -> RadiomicsResult:
     """Enqueue the extraction of one (scan, mask) pair on the current stream of `device`.  `scan` / `mask`: whatever `ingest_volume`
     takes (host volumes are uploaded; a contour, SEG or other-grid mask is brought onto the scan's grid first, `index_map` and
     `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again.  `classes`:
-    texture classes of TEXTURE_CLASSES; when not empty `mmnn_radiomics_texture` is enqueued behind the extraction."""
+    texture classes of TEXTURE_CLASSES; when not empty `mmnn_radiomics_texture` is enqueued behind the extraction.  `glszm`: enqueue
+    `mmnn_radiomics_zones` behind them."""
     from .data import ingest
     dev = torch.device(device)
     scan, mask = ingest.prepare_pair(scan, mask, dev, index_map, threshold, what="radiomics")
@@ -141,8 +163,15 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
         _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), block.data_ptr(), hist.data_ptr(),
                                              glcm.data_ptr(), ws.data_ptr(), stream), "mmnn_radiomics")
     out = RadiomicsResult(block, hist, glcm, ws, (x, y, z), scan.affine, float(bin_width), max_bins)
-    if not classes:
-        return out
+    if classes:
+        _enqueue_texture(out, desc, dev, stream, buffers, classes)
+    if glszm:
+        _enqueue_zones(out, desc, dev, stream, buffers)
+    return out
+
+
+def _enqueue_texture(out: RadiomicsResult, desc, dev, stream, buffers, classes) -> None:
+    (x, y, z), max_bins, block, ws = out.shape, out.max_bins, out.block, out.workspace
     if buffers is not None and buffers.texture is not None:
         tex, glrlm, gldm, ngn, ngs, ws2 = buffers.texture, buffers.glrlm, buffers.gldm, buffers.ngtdm_n, buffers.ngtdm_s, buffers.texture_workspace
     else:
@@ -160,7 +189,26 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
                                                      gldm.data_ptr(), ngn.data_ptr(), ngs.data_ptr(), ws2.data_ptr(), stream),
                    "mmnn_radiomics_texture")
     out.texture, out.glrlm, out.gldm, out.ngtdm_n, out.ngtdm_s, out.texture_workspace, out.classes = tex, glrlm, gldm, ngn, ngs, ws2, classes
-    return out
+
+
+def _enqueue_zones(out: RadiomicsResult, desc, dev, stream, buffers) -> None:
+    (x, y, z), max_bins = out.shape, out.max_bins
+    if buffers is not None and buffers.zones is not None:
+        zones, labels, sizes, levels, ws3 = buffers.zones, buffers.labels, buffers.sizes, buffers.levels, buffers.zones_workspace
+    else:
+        n3 = _lib.lib().mmnn_radiomics_zones_workspace_bytes(x, y, z, max_bins)
+        if n3 < 0:
+            raise ValueError("mmnn_radiomics_zones_workspace_bytes: " + _lib.last_error())
+        zones = torch.empty(_lib.RADIOMICS_ZONES_BYTES, dtype=torch.uint8, device=dev)
+        labels = torch.empty(x * y * z, dtype=torch.int32, device=dev)
+        sizes = torch.empty(x * y * z, dtype=torch.int32, device=dev)
+        levels = torch.empty(max_bins, dtype=torch.int32, device=dev)
+        ws3 = torch.empty(int(n3), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mmnn_radiomics_zones(ctypes.byref(desc), out.block.data_ptr(), out.workspace.data_ptr(), zones.data_ptr(),
+                                                   labels.data_ptr(), sizes.data_ptr(), levels.data_ptr(), ws3.data_ptr(), stream),
+                   "mmnn_radiomics_zones")
+    out.zones, out.labels, out.sizes, out.levels, out.zones_workspace, out.glszm = zones, labels, sizes, levels, ws3, True
 
 
 def unpack_texture(raw: np.ndarray) -> dict:
@@ -168,6 +216,15 @@ def unpack_texture(raw: np.ndarray) -> dict:
     f = np.ascontiguousarray(raw, dtype=np.uint8).view(np.float64)
     a, b = _lib.RADIOMICS_GLRLM, _lib.RADIOMICS_GLRLM + _lib.RADIOMICS_GLDM
     return {"glrlm": f[:a].copy(), "gldm": f[a:b].copy(), "ngtdm": f[b:].copy()}
+
+
+def unpack_zones(raw: np.ndarray) -> dict:
+    """The bytes of mmnn_radiomics_zones_result -> its fields."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    i, f = raw[:48].view(np.int64), raw[48:].view(np.float64)
+    out = {k: int(v) for k, v in zip(("nz", "n_keys", "max_size", "sum_pg2", "sum_ps2", "sum_j2"), i)}
+    out["glszm"] = f.copy()
+    return out
 
 
 def unpack_block(raw: np.ndarray) -> dict:
@@ -200,8 +257,9 @@ def shape_features(n: int, moments, linear) -> Dict[str, float]:
     return out
 
 
-def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=()) -> Dict[str, float]:
-    """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block)."""
+def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=(), zones: Optional[dict] = None) -> Dict[str, float]:
+    """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block; with `zones`, the unpacked
+    size-zone block)."""
     global _logged_identity
     if fields["empty"]:
         raise ConfigurationError(f"{what}: the mask selects no voxel of the scan")
@@ -230,20 +288,33 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
     for c in texture_classes(classes):
         for n, v in zip(_TEXTURE[c], texture[c]):
             out[f"original_{c}_{n}"] = float(v)
+    if zones is not None:
+        for n, v in zip(GLSZM, zones["glszm"]):
+            out[f"original_glszm_{n}"] = float(v)
     return out
 
 
+def _stacked(r: RadiomicsResult) -> torch.Tensor:
+    """The result blocks of one extraction behind each other: what one read-back brings to the host."""
+    parts = [r.block] + ([r.texture] if r.classes else []) + ([r.zones] if r.glszm else [])
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def _features_of_stacked(raw: np.ndarray, r: RadiomicsResult, affine, what: str) -> Dict[str, float]:
+    nb = _lib.RADIOMICS_RESULT_BYTES
+    nt = nb + (_lib.RADIOMICS_TEXTURE_BYTES if r.classes else 0)
+    return features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:nt]) if r.classes else None, r.classes,
+                       unpack_zones(raw[nt:nt + _lib.RADIOMICS_ZONES_BYTES]) if r.glszm else None)
+
+
 def finish(result: RadiomicsResult, affine="scan", what: str = "radiomics") -> Dict[str, float]:
-    """One read-back of the result block(s) -> {name: float} over FEATURE_NAMES, then the columns of the result's texture classes.  `affine`: the scan's voxel index -> mm matrix (4x4 or
+    """One read-back of the result block(s) -> {name: float} over FEATURE_NAMES, then the columns of the result's texture classes and, with
+    `glszm`, the size-zone ones.  `affine`: the scan's voxel index -> mm matrix (4x4 or
     its 3x3 linear part as the top-left block), None for the identity; the default takes the scan's own.  A flag raises
     ConfigurationError with the cause."""
     if isinstance(affine, str):
         affine = result.affine
-    if not result.classes:
-        return features_of(unpack_block(result.block.cpu().numpy()), affine, what)
-    raw = torch.cat([result.block, result.texture]).cpu().numpy()
-    nb = _lib.RADIOMICS_RESULT_BYTES
-    return features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:]), result.classes)
+    return _features_of_stacked(_stacked(result).cpu().numpy(), result, affine, what)
 
 
 def _volumes_of(dataset, patient):
@@ -251,15 +322,14 @@ def _volumes_of(dataset, patient):
 
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
-                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=()) -> List[dict]:
+                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
     A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
-    blocks come back in the batch's same stacked read-back."""
+    blocks, and with `glszm` the size-zone blocks, come back in the batch's same stacked read-back."""
     from .data import ingest
     dev = torch.device(device)
     classes = texture_classes(classes)
-    nb = _lib.RADIOMICS_RESULT_BYTES
     rows = []
     patients = list(dataset.patients)
     for b0 in range(0, len(patients), max(1, int(batch))):
@@ -267,17 +337,16 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         raws = [_volumes_of(dataset, p) for p in chunk]
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
-        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes) for (s, m), t in zip(vols, ts)]
+        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm) for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
-        blocks = torch.stack([torch.cat([r.block, r.texture]) if classes else r.block for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
+        blocks = torch.stack([_stacked(r) for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
         k = 0
         for p, rs in zip(chunk, res):
             uid = dataset._uid_of(p)
             pre = prefixes if prefixes is not None else (("",) if len(rs) == 1 else ("t1_", "t2_"))
             row = {"MRN": uid}
             for r, px in zip(rs, pre):
-                feats = features_of(unpack_block(blocks[k][:nb]), r.affine, f"patient {p} (uid {uid})",
-                                    unpack_texture(blocks[k][nb:]) if classes else None, classes)
+                feats = _features_of_stacked(blocks[k], r, r.affine, f"patient {p} (uid {uid})")
                 row.update({px + n: v for n, v in feats.items()})
                 k += 1
             rows.append(row)
@@ -313,6 +382,8 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--classes", default=None, help="texture classes beside the 47 default columns: a comma-separated list of glrlm, gldm, "
                     "ngtdm, or 'all'; overrides the config's `Radiomics: classes`")
+    ap.add_argument("--glszm", action="store_true", help="append the 16 size-zone (GLSZM) columns; also switched on by the config's "
+                    "`Radiomics: glszm: true`")
     a = ap.parse_args(argv)
     import os
     from .data.ImageDatasets import ImageDataset
@@ -320,6 +391,7 @@ def main(argv=None):
     parser = Parser(a.config)
     config = parser.parseConfig()
     classes = texture_classes(a.classes) if a.classes is not None else parser.radiomicsClasses()
+    glszm = a.glszm or parser.radiomicsZones()
     data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
@@ -330,7 +402,7 @@ def main(argv=None):
     rows = None
     for ds, px in zip(sets, ("t1_", "t2_") if len(sets) == 2 else ("",)):
         part = extract_tree(ds, a.device, None, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
-                            data.get("mask_threshold"), prefixes=(px,), classes=classes)
+                            data.get("mask_threshold"), prefixes=(px,), classes=classes, glszm=glszm)
         if rows is None:
             rows = part
         else:
