@@ -658,7 +658,7 @@ int mmnn_radiomics(const mmnn_radiomics_desc* d, const void* scan, const void* m
  * partition and in an order fixed by the extents and Ng alone, without floating-point atomics: repeated calls are bit-identical.
  * ws2: mmnn_radiomics_texture_workspace_bytes bytes, aligned to 256.  Refused as mmnn_radiomics refuses (status 1; the size returns -1),
  * before any launch: a null pointer, a bad extent, max_bins, type code or bin_width, a buffer not aligned to its element size.
- * The size-zone matrix is the call below; mesh-based shape features and the GLCM's MCC are not computed. */
+ * The size-zone matrix and the mesh-based shape features are the calls below; the GLCM's MCC is not computed. */
 #define MMNN_RADIOMICS_GLRLM 16
 #define MMNN_RADIOMICS_GLDM 14
 #define MMNN_RADIOMICS_NGTDM 5
@@ -705,7 +705,8 @@ int mmnn_radiomics_texture(const mmnn_radiomics_desc* d, const mmnn_radiomics_re
  * partition and an order fixed by the extents, Ng and the exact integer tables alone, without floating-point atomics: repeated calls are
  * bit-identical.  ws3: mmnn_radiomics_zones_workspace_bytes bytes, aligned to 256.  Refused as mmnn_radiomics_texture refuses (status 1;
  * the size returns -1), before any launch: a null pointer, a bad extent, max_bins, type code or bin_width, a buffer not aligned to its
- * element size.  Zones per slice (2-D), other distances, mesh-based shape features and the GLCM's MCC are not computed. */
+ * element size.  Zones per slice (2-D), other distances and the GLCM's MCC are not computed; the mesh-based shape features are the
+ * call below. */
 #define MMNN_RADIOMICS_GLSZM 16
 typedef struct {
   int64_t nz;        /* number of zones = sum P */
@@ -720,6 +721,65 @@ int64_t mmnn_radiomics_zones_workspace_bytes(int32_t x, int32_t y, int32_t z, in
 int mmnn_radiomics_zones(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws,
                          mmnn_radiomics_zones_result* out, uint32_t* labels, uint32_t* sizes, uint32_t* levels,
                          void* ws3, void* stream);
+
+/* ---- the surface mesh of the same ROI and what the eight mesh-based shape features need from it (csrc/radiomics_mesh.hip).  The call
+ * runs after mmnn_radiomics on the same stream, like the two above: `ws` and `result` are the workspace and the device result block that
+ * a mmnn_radiomics call with the same descriptor has filled earlier on `stream`.  The bin volume (uint16, 0 outside the ROI), the flags and
+ * the ROI's bounding box are read ON THE DEVICE: no host wait, no read-back, and no triangle is ever stored.
+ *   mesh     The ROI (bin != 0) is padded with one layer of empty voxels on every side, in thought only: a corner outside the volume
+ *            reads as empty and nothing is allocated for it.  A cell is a 2 x 2 x 2 block of corners with origin o in -1 .. extent - 1
+ *            per axis; corner k of a cell is o + (k & 1, k >> 1 & 1, k >> 2 & 1) in (x, y, z), and bit k of the cell's configuration
+ *            says whether that corner is in the ROI.  Coordinates are DOUBLED voxel indices (voxel i at 2 i).
+ *            vertices: every cell edge whose two corners differ carries one vertex at its midpoint, an integer triple.  Edge
+ *            4 a + p + 2 q runs along axis a (x 0, y 1, z 2) at the position (p, q) of the two other axes in ascending order.
+ *            segments: on each of the six faces the four corners are visited counter-clockwise as seen from outside the cell; every
+ *            maximal run of set corners is cut off by one directed segment from the crossing where the run starts to the crossing
+ *            where it ends (two diagonally opposite set corners get two segments that separate them).
+ *            loops: every vertex ends one segment and starts another, so the segments form disjoint closed loops.
+ *            triangles: a loop is rotated to start at its lowest-numbered edge v0 and cut into the fan (v0, v_i, v_i+1); a cell's loops
+ *            are taken in the order of their lowest edge.  At most 5 triangles per cell.
+ *            orientation: as directed above the normals (b - a) x (c - a) point out of the ROI; the signed volume is positive.
+ *            A face's segments depend on that face's four corners alone, so neighbouring cells agree and the mesh is closed: every
+ *            directed edge occurs as often as its reverse (an undirected edge can be used more than twice, where two sheets touch).
+ *            The table is generated from this rule (tools/gen_mesh_table.py -> csrc/mesh_table.hpp); mmnn_radiomics_mesh_table returns
+ *            the copy the library was built with, on the host: tri [256][16] (edge numbers, -1 behind the last triangle, the triangle
+ *            count in [15]), l48 [256] and nsum [256][3] (below).
+ *   cfg      [256] uint64: the number of cells per configuration, all (x + 1)(y + 1)(z + 1) cells counted.  The accumulation target;
+ *            the call zeroes it first.  Exact.
+ *   out      n_vertices; n_triangles = sum_c cfg[c] T_c; volume48 = sum over the triangles of a . (b x c) in doubled coordinates
+ *            = 48 x the mesh volume in voxels.  All exact.  With l48[c] = sum a . (b x c) and nsum[c] = sum (b - a) x (c - a) over the
+ *            triangles of configuration c in coordinates relative to the cell, a cell at origin o adds l48[c] + 2 o . nsum[c]; o is
+ *            taken relative to the ROI's bounding box (the mesh is closed, so the sum does not depend on the origin) and the sum runs
+ *            modulo 2^64, which cannot touch a value of at most 48 n.
+ *            area = sum_c cfg[c] A_c in index order c = 0 .. 255, A_c = sum over the triangles of c in table order of |cof(L) n| / 8,
+ *            n = (b - a) x (c - a) the integer normal, cof(L) the cofactor matrix of `linear` ((L a) x (L b) = cof(L) (a x b)), each
+ *            row applied as (C0 nx + C1 ny) + C2 nz, the norm as sqrt((w0^2 + w1^2) + w2^2).  In the squared units of `linear`.
+ *            q[4]: squared diameters in doubled units.  Every vertex v is mapped to t_r = (L[r][0] vx + L[r][1] vy) + L[r][2] vz; a pair
+ *            scores q = ((dt0)^2 + (dt1)^2) + (dt2)^2.  q[0] is the largest q over all unordered vertex pairs, self-pairs included (so a
+ *            class with no other pair gives 0, never NaN); q[1], q[2], q[3] over the pairs whose integer z, y and x coordinate agrees:
+ *            Maximum2DDiameterSlice, Column and Row in the (x, y, z) order of the scan's array -- Slice holds z fixed, Column y, Row x.
+ *            (PyRadiomics names its axes after its own array order; that naming is not checked here.)  A diameter is sqrt(q) / 2.
+ *            The four are maxima, the file is built without contraction: they are bit-identical to the restatement's and from call
+ *            to call, although the order of the vertex list in ws4 is not fixed.
+ *            (Specified while every t_r is finite: a `linear` so large that L v overflows is the caller's error.)
+ *   flags    with overflow, nonfinite or empty set by mmnn_radiomics the five doubles are NaN, the three integers and cfg zero.
+ * linear: 9 doubles ON THE HOST, row-major, the 3 x 3 linear part of the voxel index -> mm affine; read during the call.
+ * Integers by uint32 / uint64 atomic add and maximum (the maxima on the bit patterns of non-negative doubles); no floating-point atomics.
+ * ws4: mmnn_radiomics_mesh_workspace_bytes bytes, aligned to 256: the vertex list, three uint32 per vertex for 3 (x + 1)(y + 1)(z + 1)
+ * vertices, the most a volume can have.  Refused as mmnn_radiomics_zones refuses (status 1; the size returns -1), before any launch: a
+ * null pointer, a bad extent, max_bins, type code or bin_width, a buffer not aligned to its element size; and a null or non-finite
+ * `linear`.  Pruning the pair search to hull-extreme vertices is not done.  The GLCM's MCC is not computed. */
+typedef struct {
+  int64_t n_vertices;
+  int64_t n_triangles;
+  int64_t volume48;  /* 48 x the mesh volume in voxels */
+  double area;       /* in the squared units of `linear` */
+  double q[4];       /* squared diameters, doubled units: all pairs, z fixed (Slice), y fixed (Column), x fixed (Row) */
+} mmnn_radiomics_mesh_result;
+int64_t mmnn_radiomics_mesh_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t max_bins);
+int mmnn_radiomics_mesh(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws, const double* linear,
+                        mmnn_radiomics_mesh_result* out, uint64_t* cfg, void* ws4, void* stream);
+int mmnn_radiomics_mesh_table(int8_t* tri, int32_t* l48, int32_t* nsum);
 
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */

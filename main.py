@@ -25,7 +25,8 @@ attention map back on each scan's own voxel grid, with the scan's affine (att_ma
 config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
 `--radiomics` trains on radiomic features: the csv of `--rad_loc` (column MRN, then the features), or, without it, the table extracted
 on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py; the config's
-`Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it); alone it is
+`Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it, `--mesh_shape` / `Radiomics: mesh_shape: true` the
+eight mesh-based shape columns); alone it is
 the standalone MLP over the radiomic columns, with `--images` the fusion model, with `--preop` / `--postop` too the clinical columns first.
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -281,6 +282,7 @@ def extract_radiomics_if_needed(parser, args):
     if not torch.cuda.is_available():
         raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
     rc, classes, glszm = parser.radiomicsConfig(), parser.radiomicsClasses(), parser.radiomicsZones()
+    mesh = getattr(args, "mesh_shape", False) or parser.radiomicsMesh()
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
     prefixes = ("t1_", "t2_") if len(paths) == 2 else ("",)
@@ -289,7 +291,7 @@ def extract_radiomics_if_needed(parser, args):
         ds = ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
         threshold = (parser.config.get("Data") or {}).get("mask_threshold")
         part = radiomics.extract_tree(ds, torch.device("cuda", 0), None, rc["bin_width"], rc["max_bins"],
-                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes, glszm=glszm)
+                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh)
         if rows is None:
             rows = part
         else:
@@ -660,6 +662,9 @@ def build_arg_parser():
     ap.add_argument("--occlusion", action="store_true",
                     help="with --inference --images: occlusion sensitivity maps per patient (attention_maps/patient{i}_occ_map.npy, "
                          "(K, D, H, W) signed deltas; with --image_loc occ_map_class{k}.nii.gz, with --scan_space also on the scans' grids)")
+    ap.add_argument("--mesh_shape", action="store_true",
+                    help="with --radiomics and no --rad_loc: append the 8 mesh-based shape columns (mesh volume, surface area, sphericity, "
+                         "the diameters) to the extracted table; also switched on by the config's `Radiomics: mesh_shape: true`")
     ap.add_argument("--occlusion_window", type=int, default=16, help="edge of the occluded box in voxels")
     ap.add_argument("--occlusion_stride", type=int, default=8, help="step of the box, 1..window")
     ap.add_argument("--occlusion_batch", type=int, default=8, help="occluded samples per forward")

@@ -147,6 +147,8 @@ RADIOMICS_GLRLM, RADIOMICS_GLDM, RADIOMICS_NGTDM, RADIOMICS_NEIGHBOURS = 16, 14,
 RADIOMICS_TEXTURE_BYTES = (16 + 14 + 5) * 8                                       # mmnn_radiomics_texture_result: 35 doubles
 RADIOMICS_GLSZM = 16
 RADIOMICS_ZONES_BYTES = (6 + 16) * 8                                              # mmnn_radiomics_zones_result: 6 int64, then 16 doubles
+RADIOMICS_MESH_BYTES = (3 + 1 + 4) * 8                                            # mmnn_radiomics_mesh_result: 3 int64, then 5 doubles
+RADIOMICS_MESH_CONFIGS, RADIOMICS_MESH_TRI_ROW = 256, 16
 
 
 class RadiomicsDesc(Structure):
@@ -278,6 +280,12 @@ def lib():
     L.mmnn_radiomics_zones_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
     L.mmnn_radiomics_zones.restype = c_int32
     L.mmnn_radiomics_zones.argtypes = [POINTER(RadiomicsDesc)] + [c_void_p] * 8
+    L.mmnn_radiomics_mesh_workspace_bytes.restype = c_int64
+    L.mmnn_radiomics_mesh_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.mmnn_radiomics_mesh.restype = c_int32
+    L.mmnn_radiomics_mesh.argtypes = [POINTER(RadiomicsDesc), c_void_p, c_void_p, POINTER(ctypes.c_double)] + [c_void_p] * 4
+    L.mmnn_radiomics_mesh_table.restype = c_int32
+    L.mmnn_radiomics_mesh_table.argtypes = [c_void_p, c_void_p, c_void_p]
     L.mmnn_channel_means.restype = c_int32
     L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64

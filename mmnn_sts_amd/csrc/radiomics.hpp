@@ -1,4 +1,4 @@
-// What csrc/radiomics.hip, csrc/radiomics_texture.hip and csrc/radiomics_zones.hip share: the constants, the 13 directions, the state
+// What csrc/radiomics.hip, csrc/radiomics_texture.hip, csrc/radiomics_zones.hip and csrc/radiomics_mesh.hip share: the constants, the 13 directions, the state
 // block that the kernels of `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks and the wave-folded count.
 // Their fp64 sums over a workgroup are block_reduce<RAD_TPB / 64>(values, lds, Sum{}) of reduce.hpp: lanes by the butterfly, then the
 // waves in index order.

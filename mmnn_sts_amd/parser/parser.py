@@ -95,6 +95,14 @@ class Parser:
             raise ConfigurationError('Radiomics.glszm must be true or false, got {!r}'.format(glszm))
         return glszm
 
+    def radiomicsMesh(self):
+        """`Radiomics: mesh_shape`: whether the 8 mesh-based shape columns are extracted behind all the others (false)."""
+        rad = self.config.get('Radiomics') or {}
+        mesh = rad.get('mesh_shape', False)
+        if not isinstance(mesh, bool):
+            raise ConfigurationError('Radiomics.mesh_shape must be true or false, got {!r}'.format(mesh))
+        return mesh
+
     def _radiomicsExcluded(self):
         rm = self.config.get('RadiomicsModel') or {}
         return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])

@@ -1,18 +1,21 @@
 """Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip), of
-`mmnn_radiomics_texture` (csrc/radiomics_texture.hip) and of `mmnn_radiomics_zones` (csrc/radiomics_zones.hip).
+`mmnn_radiomics_texture` (csrc/radiomics_texture.hip), of `mmnn_radiomics_zones` (csrc/radiomics_zones.hip) and of `mmnn_radiomics_mesh`
+(csrc/radiomics_mesh.hip).
 
     extract(scan, mask, device)            enqueue one extraction; the result holds device tensors, nothing is read back
     finish(result, affine)                 one read-back -> {feature name: float}: adds TotalEnergy and the voxel-based shape features
     extract_tree(dataset, device, out)     every patient and modality of an image dataset -> a csv (`MRN`, then the features)
-    feature_names(classes, glszm)          the columns: FEATURE_NAMES, then those of the requested texture classes, then the size-zone ones
+    feature_names(classes, glszm, mesh)    the columns: FEATURE_NAMES, then those of the requested texture classes, then the size-zone ones,
+                                           then the mesh-based shape ones
     python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] [--glszm]
-                                     --out radiomics.csv
+                                     [--mesh_shape] --out radiomics.csv
 
 Upstream reads such a csv (`Data: rad_loc`, data/RadiomicsDatasets.py) and leaves its extraction to PyRadiomics; here the table is built
 from the very pair the image path ingests, through the same mask routes (NIfTI mask, resampled mask, DICOM mask series, RTSTRUCT, SEG:
 `data.ingest.prepare_pair`).  The 47 columns carry PyRadiomics' names and definitions -- 18 first-order, 6 voxel-based shape, 23 GLCM --
-in voxel index space (distance 1, no resampling, fixed `bin_width`).  Mesh-based shape features (surface area, sphericity, the
-diameters) and the GLCM's MCC are out of scope.  What the numbers are pinned to is the numpy restatement in tests/_radiomics_ref.py.
+in voxel index space (distance 1, no resampling, fixed `bin_width`).  The mesh-based shape features (surface area, sphericity, the
+diameters) are behind the switch `mesh_shape` below; the GLCM's MCC is out of scope.  What the numbers are pinned to is the numpy
+restatement in tests/_radiomics_ref.py.
 
 `classes` (`Radiomics: classes`, `--classes`; empty by default) adds the columns of further texture classes, computed by a second call on
 the same stream from the bin volume the first one left on the device: `glrlm` (16 run-length features), `gldm` (14 dependence features,
@@ -22,8 +25,16 @@ alpha 0) and `ngtdm` (5), 82 columns per modality with all three.  These too are
 `glszm` (`Radiomics: glszm`, `--glszm`; off by default) is a switch of its own beside `classes`: a third call on the same stream labels
 the 26-connected zones of equal bin on the device and appends the 16 size-zone features (`original_glszm_*`) behind the other classes: 63
 columns per modality alone, 98 with all three classes.  They are pinned to the numpy / scipy restatement in
-tests/_radiomics_zones_ref.py; **parity with PyRadiomics is unpinned** here too.  The mesh-based shape features and the GLCM's MCC stay out
-of scope.
+tests/_radiomics_zones_ref.py; **parity with PyRadiomics is unpinned** here too.
+
+`mesh` (`Radiomics: mesh_shape`, `--mesh_shape`; off by default) is a fourth call on the same stream: it walks the cells of the ROI's
+surface mesh on the device (a triangle table generated from a stated rule, tools/gen_mesh_table.py) and returns the exact integer volume,
+the surface area under the scan's 3 x 3 linear part and four squared diameters from a pass over all vertex pairs; `finish` derives the
+eight columns `original_shape_MeshVolume` ... `original_shape_Maximum2DDiameterRow`, which follow all the others: 55 columns per
+modality with the switch alone, 106 with all classes and `glszm`.  Slice, Column and Row hold the z, y and x index of the scan's array
+fixed.  They are pinned to the numpy restatement in tests/_radiomics_mesh_ref.py; **parity with PyRadiomics is unpinned**: its table may
+triangulate some configurations differently, and it scales by the spacing alone where this uses the full linear part.  The GLCM's MCC
+stays out of scope.
 """
 import argparse
 import csv
@@ -64,6 +75,8 @@ GLSZM = ("SmallAreaEmphasis", "LargeAreaEmphasis", "GrayLevelNonUniformity", "Gr
          "SizeZoneNonUniformityNormalized", "ZonePercentage", "GrayLevelVariance", "ZoneVariance", "ZoneEntropy", "LowGrayLevelZoneEmphasis",
          "HighGrayLevelZoneEmphasis", "SmallAreaLowGrayLevelEmphasis", "SmallAreaHighGrayLevelEmphasis", "LargeAreaLowGrayLevelEmphasis",
          "LargeAreaHighGrayLevelEmphasis")
+MESH_SHAPE = ("MeshVolume", "SurfaceArea", "SurfaceVolumeRatio", "Sphericity", "Maximum3DDiameter", "Maximum2DDiameterSlice",
+              "Maximum2DDiameterColumn", "Maximum2DDiameterRow")
 TEXTURE_CLASSES = ("glrlm", "gldm", "ngtdm")
 _TEXTURE = {"glrlm": GLRLM, "gldm": GLDM, "ngtdm": NGTDM}
 FEATURE_NAMES = tuple([f"original_firstorder_{n}" for n in FIRSTORDER] + [f"original_shape_{n}" for n in SHAPE]
@@ -88,11 +101,12 @@ def texture_classes(classes) -> tuple:
     return tuple(c for c in TEXTURE_CLASSES if c in names)
 
 
-def feature_names(classes=(), glszm=False) -> tuple:
+def feature_names(classes=(), glszm=False, mesh=False) -> tuple:
     """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes, then with `glszm`
-    `original_glszm_*`."""
+    `original_glszm_*`, then with `mesh` the eight mesh-based `original_shape_*`."""
     return (FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
-            + (tuple(f"original_glszm_{n}" for n in GLSZM) if glszm else ()))
+            + (tuple(f"original_glszm_{n}" for n in GLSZM) if glszm else ())
+            + (tuple(f"original_shape_{n}" for n in MESH_SHAPE) if mesh else ()))
 
 
 @dataclass
@@ -101,7 +115,9 @@ class RadiomicsResult:
     (13, max_bins, max_bins) int32 views of the uint32 counts; `shape`, `affine`: the scan's grid.  With texture classes: `texture`, the
     bytes of mmnn_radiomics_texture_result; `glrlm` (13, max_bins, L), `gldm` and `ngtdm_n` (max_bins, 27) int32 views of the uint32 counts,
     `ngtdm_s` (max_bins, 27) int64; `classes`, the requested ones (the device computes all three).  With `glszm`: `zones`, the bytes of
-    mmnn_radiomics_zones_result; `labels` and `sizes` (x * y * z,) and `levels` (max_bins,) int32 views of the uint32 tables."""
+    mmnn_radiomics_zones_result; `labels` and `sizes` (x * y * z,) and `levels` (max_bins,) int32 views of the uint32 tables.  With `mesh`:
+    `mesh`, the bytes of mmnn_radiomics_mesh_result; `mesh_cfg` (256,) int64, the cells per configuration; `linear`, the 3 x 3 linear part
+    that was enqueued with the call (the scan's, the identity without an affine)."""
     block: torch.Tensor
     hist: torch.Tensor
     glcm: torch.Tensor
@@ -123,6 +139,11 @@ class RadiomicsResult:
     levels: Optional[torch.Tensor] = None
     zones_workspace: Optional[torch.Tensor] = None
     glszm: bool = False
+    mesh: Optional[torch.Tensor] = None
+    mesh_cfg: Optional[torch.Tensor] = None
+    mesh_workspace: Optional[torch.Tensor] = None
+    linear: Optional[np.ndarray] = None
+    mesh_shape: bool = False
 
 
 def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
@@ -133,12 +154,14 @@ def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) ->
 
 
 def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS, index_map=None,
-            threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=(), glszm: bool = False) -> RadiomicsResult:
+            threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=(), glszm: bool = False,
+            mesh: bool = False) -> RadiomicsResult:
     """Enqueue the extraction of one (scan, mask) pair on the current stream of `device`.  `scan` / `mask`: whatever `ingest_volume`
     takes (host volumes are uploaded; a contour, SEG or other-grid mask is brought onto the scan's grid first, `index_map` and
     `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again.  `classes`:
     texture classes of TEXTURE_CLASSES; when not empty `mmnn_radiomics_texture` is enqueued behind the extraction.  `glszm`: enqueue
-    `mmnn_radiomics_zones` behind them."""
+    `mmnn_radiomics_zones` behind them.  `mesh`: enqueue `mmnn_radiomics_mesh` behind those, with the linear part of the scan's affine (the
+    identity without one), which the result remembers."""
     from .data import ingest
     dev = torch.device(device)
     scan, mask = ingest.prepare_pair(scan, mask, dev, index_map, threshold, what="radiomics")
@@ -167,6 +190,8 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
         _enqueue_texture(out, desc, dev, stream, buffers, classes)
     if glszm:
         _enqueue_zones(out, desc, dev, stream, buffers)
+    if mesh:
+        _enqueue_mesh(out, desc, dev, stream, buffers)
     return out
 
 
@@ -209,6 +234,59 @@ def _enqueue_zones(out: RadiomicsResult, desc, dev, stream, buffers) -> None:
                                                    labels.data_ptr(), sizes.data_ptr(), levels.data_ptr(), ws3.data_ptr(), stream),
                    "mmnn_radiomics_zones")
     out.zones, out.labels, out.sizes, out.levels, out.zones_workspace, out.glszm = zones, labels, sizes, levels, ws3, True
+
+
+def _linear_of(affine) -> np.ndarray:
+    """The 3 x 3 linear part of a voxel index -> mm matrix (4 x 4, or 3 x 3 as it is); the identity for None."""
+    return np.eye(3) if affine is None else np.ascontiguousarray(np.asarray(affine, dtype=np.float64)[:3, :3])
+
+
+def _enqueue_mesh(out: RadiomicsResult, desc, dev, stream, buffers) -> None:
+    x, y, z = out.shape
+    if buffers is not None and buffers.mesh is not None:
+        block, cfg, ws4 = buffers.mesh, buffers.mesh_cfg, buffers.mesh_workspace
+    else:
+        n4 = _lib.lib().mmnn_radiomics_mesh_workspace_bytes(x, y, z, out.max_bins)
+        if n4 < 0:
+            raise ValueError("mmnn_radiomics_mesh_workspace_bytes: " + _lib.last_error())
+        block = torch.empty(_lib.RADIOMICS_MESH_BYTES, dtype=torch.uint8, device=dev)
+        cfg = torch.empty(_lib.RADIOMICS_MESH_CONFIGS, dtype=torch.int64, device=dev)
+        ws4 = torch.empty(int(n4), dtype=torch.uint8, device=dev)
+    linear = _linear_of(out.affine)
+    flat = (ctypes.c_double * 9)(*linear.ravel().tolist())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mmnn_radiomics_mesh(ctypes.byref(desc), out.block.data_ptr(), out.workspace.data_ptr(), flat, block.data_ptr(),
+                                                  cfg.data_ptr(), ws4.data_ptr(), stream), "mmnn_radiomics_mesh")
+    out.mesh, out.mesh_cfg, out.mesh_workspace, out.linear, out.mesh_shape = block, cfg, ws4, linear, True
+
+
+def mesh_table() -> dict:
+    """The triangle table the library was built with (host only, no device): `tri` (256, 16) int8, `l48` (256,), `nsum` (256, 3) int32."""
+    tri = np.zeros((_lib.RADIOMICS_MESH_CONFIGS, _lib.RADIOMICS_MESH_TRI_ROW), dtype=np.int8)
+    l48, nsum = np.zeros(_lib.RADIOMICS_MESH_CONFIGS, dtype=np.int32), np.zeros((_lib.RADIOMICS_MESH_CONFIGS, 3), dtype=np.int32)
+    _lib.check(_lib.lib().mmnn_radiomics_mesh_table(tri.ctypes.data, l48.ctypes.data, nsum.ctypes.data), "mmnn_radiomics_mesh_table")
+    return {"tri": tri, "l48": l48, "nsum": nsum}
+
+
+def unpack_mesh(raw: np.ndarray) -> dict:
+    """The bytes of mmnn_radiomics_mesh_result -> its fields."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    i, f = raw[:24].view(np.int64), raw[24:].view(np.float64)
+    out = {k: int(v) for k, v in zip(("n_vertices", "n_triangles", "volume48"), i)}
+    out["area"], out["q"] = float(f[0]), f[1:5].copy()
+    return out
+
+
+def mesh_features(mesh: dict, linear) -> Dict[str, float]:
+    """The eight mesh-based shape features from the device's block: MeshVolume = volume48 / 48 |det L|, SurfaceArea as returned,
+    SurfaceVolumeRatio = A / V, Sphericity = (36 pi V^2)^(1/3) / A, each diameter sqrt(q) / 2."""
+    V = mesh["volume48"] / 48.0 * abs(float(np.linalg.det(np.asarray(linear, dtype=np.float64).reshape(3, 3))))
+    A = mesh["area"]
+    out = {"MeshVolume": V, "SurfaceArea": A, "SurfaceVolumeRatio": A / V if V > 0.0 else float("nan"),
+           "Sphericity": (36.0 * math.pi * V * V) ** (1.0 / 3.0) / A if A > 0.0 else float("nan")}
+    for n, q in zip(MESH_SHAPE[4:], mesh["q"]):
+        out[n] = math.sqrt(float(q)) / 2.0
+    return out
 
 
 def unpack_texture(raw: np.ndarray) -> dict:
@@ -257,9 +335,10 @@ def shape_features(n: int, moments, linear) -> Dict[str, float]:
     return out
 
 
-def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=(), zones: Optional[dict] = None) -> Dict[str, float]:
+def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=(), zones: Optional[dict] = None,
+                mesh: Optional[dict] = None) -> Dict[str, float]:
     """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block; with `zones`, the unpacked
-    size-zone block)."""
+    size-zone block; with `mesh`, the unpacked mesh block, whose area and diameters were computed under the linear part of `affine`)."""
     global _logged_identity
     if fields["empty"]:
         raise ConfigurationError(f"{what}: the mask selects no voxel of the scan")
@@ -291,25 +370,33 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
     if zones is not None:
         for n, v in zip(GLSZM, zones["glszm"]):
             out[f"original_glszm_{n}"] = float(v)
+    if mesh is not None:
+        for n, v in mesh_features(mesh, linear).items():
+            out[f"original_shape_{n}"] = v
     return out
 
 
 def _stacked(r: RadiomicsResult) -> torch.Tensor:
     """The result blocks of one extraction behind each other: what one read-back brings to the host."""
-    parts = [r.block] + ([r.texture] if r.classes else []) + ([r.zones] if r.glszm else [])
+    parts = [r.block] + ([r.texture] if r.classes else []) + ([r.zones] if r.glszm else []) + ([r.mesh] if r.mesh_shape else [])
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
 def _features_of_stacked(raw: np.ndarray, r: RadiomicsResult, affine, what: str) -> Dict[str, float]:
     nb = _lib.RADIOMICS_RESULT_BYTES
     nt = nb + (_lib.RADIOMICS_TEXTURE_BYTES if r.classes else 0)
+    nz = nt + (_lib.RADIOMICS_ZONES_BYTES if r.glszm else 0)
+    if r.mesh_shape and not np.array_equal(_linear_of(affine), r.linear):
+        raise ValueError(f"{what}: the mesh-based shape features were enqueued under the linear part {r.linear.tolist()}; `finish` cannot "
+                         f"apply another one ({_linear_of(affine).tolist()}): extract with the affine that is meant")
     return features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:nt]) if r.classes else None, r.classes,
-                       unpack_zones(raw[nt:nt + _lib.RADIOMICS_ZONES_BYTES]) if r.glszm else None)
+                       unpack_zones(raw[nt:nz]) if r.glszm else None, unpack_mesh(raw[nz:nz + _lib.RADIOMICS_MESH_BYTES]) if r.mesh_shape else None)
 
 
 def finish(result: RadiomicsResult, affine="scan", what: str = "radiomics") -> Dict[str, float]:
-    """One read-back of the result block(s) -> {name: float} over FEATURE_NAMES, then the columns of the result's texture classes and, with
-    `glszm`, the size-zone ones.  `affine`: the scan's voxel index -> mm matrix (4x4 or
+    """One read-back of the result block(s) -> {name: float} over FEATURE_NAMES, then the columns of the result's texture classes, with
+    `glszm` the size-zone ones and with `mesh` the mesh-based shape ones (ValueError when `affine` is passed and its linear part is not the
+    one the mesh call was enqueued with).  `affine`: the scan's voxel index -> mm matrix (4x4 or
     its 3x3 linear part as the top-left block), None for the identity; the default takes the scan's own.  A flag raises
     ConfigurationError with the cause."""
     if isinstance(affine, str):
@@ -322,11 +409,12 @@ def _volumes_of(dataset, patient):
 
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
-                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False) -> List[dict]:
+                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False,
+                 mesh: bool = False) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
     A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
-    blocks, and with `glszm` the size-zone blocks, come back in the batch's same stacked read-back."""
+    blocks, with `glszm` the size-zone blocks and with `mesh` the mesh blocks, come back in the batch's same stacked read-back."""
     from .data import ingest
     dev = torch.device(device)
     classes = texture_classes(classes)
@@ -337,7 +425,8 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         raws = [_volumes_of(dataset, p) for p in chunk]
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
-        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm) for (s, m), t in zip(vols, ts)]
+        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm, mesh=mesh)
+                for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
         blocks = torch.stack([_stacked(r) for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
         k = 0
@@ -384,6 +473,8 @@ def main(argv=None):
                     "ngtdm, or 'all'; overrides the config's `Radiomics: classes`")
     ap.add_argument("--glszm", action="store_true", help="append the 16 size-zone (GLSZM) columns; also switched on by the config's "
                     "`Radiomics: glszm: true`")
+    ap.add_argument("--mesh_shape", action="store_true", help="append the 8 mesh-based shape columns (volume, surface area, sphericity, the "
+                    "diameters); also switched on by the config's `Radiomics: mesh_shape: true`")
     a = ap.parse_args(argv)
     import os
     from .data.ImageDatasets import ImageDataset
@@ -392,6 +483,7 @@ def main(argv=None):
     config = parser.parseConfig()
     classes = texture_classes(a.classes) if a.classes is not None else parser.radiomicsClasses()
     glszm = a.glszm or parser.radiomicsZones()
+    mesh = a.mesh_shape or parser.radiomicsMesh()
     data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
@@ -402,7 +494,7 @@ def main(argv=None):
     rows = None
     for ds, px in zip(sets, ("t1_", "t2_") if len(sets) == 2 else ("",)):
         part = extract_tree(ds, a.device, None, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
-                            data.get("mask_threshold"), prefixes=(px,), classes=classes, glszm=glszm)
+                            data.get("mask_threshold"), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh)
         if rows is None:
             rows = part
         else:
