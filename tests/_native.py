@@ -88,6 +88,47 @@ class NativeBackbone:
                                                        grad.data_ptr(), int(accumulate), seed, hi, lo, st), "densenet_backward_range")
         return grad
 
+    def block_channels(self):
+        """Channels of every dense block's concat buffer."""
+        out, c = [], self.cfg.init_features
+        for nl in self.cfg.block_config:
+            c += nl * self.cfg.growth_rate
+            out.append(c)
+            c //= 2
+        return out
+
+    def forward_taps(self):
+        """Copies of the forward regions no other helper reads: {("t1", b, l): conv1 output, ("ap", b): pooled transition activations}."""
+        n, mid = self.out_shape[0], self.cfg.bn_size * self.cfg.growth_rate
+        dims, ctot, out = self.block_dims(), self.block_channels(), {}
+        for b, nl in enumerate(self.cfg.block_config):
+            for l in range(nl):
+                out[("t1", b, l)] = self.region("t1", (n, mid, *dims[b]), b, l).clone()
+            if b + 1 < len(dims):
+                out[("ap", b)] = self.region("ap", (n, ctot[b], *dims[b + 1]), b).clone()
+        return out
+
+    def backward_walk(self, flat, x, grad_out, seed=0):
+        """The backward as one backward_range(b, b) call per dense block, from the last block down to 0.  After each call the regions that
+        call completed are copied: ("g", b), ("dz2", b, l), ("s_x", b) (fp64 (2, C): S1, S2 with the replicas summed), ("dap", b - 1) -- the
+        gradient wrt the pooled activations of the transition in front of block b, one buffer for all transitions -- and ("dz0",) after
+        block 0.  Copies taken between the calls do not depend on which regions a later call reuses.  Returns (gradient buffer, copies)."""
+        n, mid = self.out_shape[0], self.cfg.bn_size * self.cfg.growth_rate
+        dims, ctot, snap = self.block_dims(), self.block_channels(), {}
+        grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+        for b in reversed(range(len(dims))):
+            self.backward_range(flat, x, grad_out, b, b, seed=seed, grad=grad)
+            snap[("g", b)] = self.region("g", (n, ctot[b], *dims[b]), b).clone()
+            for l in range(self.cfg.block_config[b]):
+                snap[("dz2", b, l)] = self.region("dz2", (n, mid, *dims[b]), b, l).clone()
+            snap[("s_x", b)] = self.region("s_x", (2, 8, ctot[b]), b, dtype=torch.float64).sum(1)
+            if b > 0:
+                snap[("dap", b - 1)] = self.region("dap", (n, ctot[b - 1], *dims[b]), dtype=torch.float32).clone()
+            else:
+                d0 = [(s - 1) // 2 + 1 for s in self.in_dhw]
+                snap[("dz0",)] = self.region("dz0", (n, self.cfg.init_features, *d0)).clone()
+        return grad, snap
+
     def set_option(self, name, value):
         _lib.check(self.L.mmnn_densenet_set_option(self.plan, name.encode(), value), "set_option")
 
