@@ -781,6 +781,37 @@ int mmnn_radiomics_mesh(const mmnn_radiomics_desc* d, const mmnn_radiomics_resul
                         mmnn_radiomics_mesh_result* out, uint64_t* cfg, void* ws4, void* stream);
 int mmnn_radiomics_mesh_table(int8_t* tri, int32_t* l48, int32_t* nsum);
 
+/* ---- the Laplacian-of-Gaussian image type of the radiomics path: a separable 3-D FIR with spacing-dependent taps, fp64 accumulation and
+ * edge replication (csrc/radiomics_filter.hip).  `scan` holds x*y*z elements, x fastest, in NIfTI type scan_type; a voxel's value v is
+ * raw * scan_slope + scan_inter in fp64, the type codes and the rule exactly those of mmnn_radiomics_desc (a slope of 0 switches the
+ * scaling off).  `out` is [z][y][x] float32, x fastest, every element written: it is a scan of type 16 with slope 0 for mmnn_radiomics.
+ *   taps     a device buffer of fp64: for each axis a = x, y, z in turn g_a[2 r_a + 1] (the smoothing taps) and then h_a[2 r_a + 1] (the
+ *            second-derivative taps), r_a = radius[a].  The caller computes them; the library never calls exp.
+ *   weight   w_x, w_y, w_z: what each axis' second derivative is multiplied by (sigma^2 / spacing_a^2 for the scale-normalised mm
+ *            Laplacian).
+ *   arithmetic  all fp64, product then sum with no contraction; every sum runs over the taps t = -r .. +r in ascending order, starting
+ *            from +0.0, and a source index outside the volume is clamped to it (edge replication):
+ *              x pass   A0 = sum g_x[t] v(x + t)                       A2 = sum h_x[t] v(x + t)
+ *              y pass   B0 = sum g_y[t] A0(y + t)                      C  = (sum g_y[t] A2(y + t)) w_x + (sum h_y[t] A0(y + t)) w_y
+ *              z pass   out = (float)( sum g_z[t] C(z + t) + (sum h_z[t] B0(z + t)) w_z )
+ *            The intermediates are fp64 and the result is rounded to fp32 once.  A non-finite voxel propagates to every output within
+ *            its radii.  A radius may exceed the extent of its axis.
+ * One lane per output and no atomics: repeated calls are bit-identical, and so is a restatement that follows the order above.  No host
+ * wait.  ws: mmnn_log_filter_workspace_bytes bytes, aligned to 256: the four fp64 intermediates.  Refused (status 1; the size returns -1)
+ * before any launch: a null pointer, a non-positive extent, x*y*z >= 2^31, an unsupported type code, a radius outside
+ * 1..MMNN_LOG_FILTER_MAX_RADIUS, a non-finite weight, a scan not aligned to its element size, taps not aligned to 8, out not to 4, ws
+ * not to 256.  The largest radius is what the y / z tile with its two halos takes of the LDS: 62.8 KiB of a CU's 160. */
+#define MMNN_LOG_FILTER_MAX_RADIUS 88
+typedef struct {
+  int32_t x, y, z;
+  int32_t scan_type;              /* NIfTI datatype code */
+  double scan_slope, scan_inter;
+  int32_t radius[3];              /* x, y, z */
+  double weight[3];               /* x, y, z */
+} mmnn_log_filter_desc;
+int64_t mmnn_log_filter_workspace_bytes(int32_t x, int32_t y, int32_t z);
+int mmnn_log_filter(const mmnn_log_filter_desc* d, const void* scan, const double* taps, float* out, void* ws, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

@@ -26,7 +26,8 @@ config reads them back from a csv it writes first (the "synthetic 32-feature x 6
 `--radiomics` trains on radiomic features: the csv of `--rad_loc` (column MRN, then the features), or, without it, the table extracted
 on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py; the config's
 `Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it, `--mesh_shape` / `Radiomics: mesh_shape: true` the
-eight mesh-based shape columns); alone it is
+eight mesh-based shape columns, `--log_sigma 1,3` / `Radiomics: log: {sigma: [1.0, 3.0]}` the `log-sigma-<sigma>-mm-3D_*` columns of the
+scan filtered by a Laplacian of Gaussian at those scales in mm); alone it is
 the standalone MLP over the radiomic columns, with `--images` the fusion model, with `--preop` / `--postop` too the clinical columns first.
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -283,6 +284,7 @@ def extract_radiomics_if_needed(parser, args):
         raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
     rc, classes, glszm = parser.radiomicsConfig(), parser.radiomicsClasses(), parser.radiomicsZones()
     mesh = getattr(args, "mesh_shape", False) or parser.radiomicsMesh()
+    log = parser.radiomicsLog(getattr(args, "log_sigma", None), getattr(args, "log_bin_width", None))
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
     prefixes = ("t1_", "t2_") if len(paths) == 2 else ("",)
@@ -291,7 +293,8 @@ def extract_radiomics_if_needed(parser, args):
         ds = ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
         threshold = (parser.config.get("Data") or {}).get("mask_threshold")
         part = radiomics.extract_tree(ds, torch.device("cuda", 0), None, rc["bin_width"], rc["max_bins"],
-                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh)
+                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh,
+                                      log_sigma=log["sigma"], log_bin_width=log["bin_width"])
         if rows is None:
             rows = part
         else:
@@ -665,6 +668,11 @@ def build_arg_parser():
     ap.add_argument("--mesh_shape", action="store_true",
                     help="with --radiomics and no --rad_loc: append the 8 mesh-based shape columns (mesh volume, surface area, sphericity, "
                          "the diameters) to the extracted table; also switched on by the config's `Radiomics: mesh_shape: true`")
+    ap.add_argument("--log_sigma", type=str, default=None,
+                    help="with --radiomics and no --rad_loc: Laplacian-of-Gaussian scales in mm, comma-separated (1,3): append the "
+                         "log-sigma-<sigma>-mm-3D_* columns of the filtered scans; overrides the config's `Radiomics: log: sigma`")
+    ap.add_argument("--log_bin_width", type=float, default=None,
+                    help="bin width of the filtered images; overrides `Radiomics: log: bin_width` (default: `Radiomics: bin_width`)")
     ap.add_argument("--occlusion_window", type=int, default=16, help="edge of the occluded box in voxels")
     ap.add_argument("--occlusion_stride", type=int, default=8, help="step of the box, 1..window")
     ap.add_argument("--occlusion_batch", type=int, default=8, help="occluded samples per forward")

@@ -158,6 +158,15 @@ class RadiomicsDesc(Structure):
                 ("mask_inter", ctypes.c_double), ("bin_width", ctypes.c_double), ("max_bins", c_int32)]
 
 
+LOG_FILTER_MAX_RADIUS = 88                   # MMNN_LOG_FILTER_MAX_RADIUS
+
+
+class LogFilterDesc(Structure):
+    """mmnn_log_filter_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("scan_type", c_int32), ("scan_slope", ctypes.c_double),
+                ("scan_inter", ctypes.c_double), ("radius", c_int32 * 3), ("weight", ctypes.c_double * 3)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -286,6 +295,10 @@ def lib():
     L.mmnn_radiomics_mesh.argtypes = [POINTER(RadiomicsDesc), c_void_p, c_void_p, POINTER(ctypes.c_double)] + [c_void_p] * 4
     L.mmnn_radiomics_mesh_table.restype = c_int32
     L.mmnn_radiomics_mesh_table.argtypes = [c_void_p, c_void_p, c_void_p]
+    L.mmnn_log_filter_workspace_bytes.restype = c_int64
+    L.mmnn_log_filter_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.mmnn_log_filter.restype = c_int32
+    L.mmnn_log_filter.argtypes = [POINTER(LogFilterDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_channel_means.restype = c_int32
     L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64

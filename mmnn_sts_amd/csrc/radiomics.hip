@@ -598,15 +598,6 @@ __global__ void __launch_bounds__(RAD_TPB) rad_final_kernel(const RadArgs a) {
 
 namespace {
 
-IgScale rad_scale(double slope, double inter) {      // as ig_scale reads a header's pair
-  IgScale s{1.0, 0.0, 0};
-  if (slope == 0.0 || !std::isfinite(slope)) return s;
-  s.slope = slope;
-  s.inter = std::isfinite(inter) ? inter : 0.0;
-  s.on = !(s.slope == 1.0 && s.inter == 0.0);
-  return s;
-}
-
 template <int PHASE>
 void rad_launch_pass(const RadArgs& a, bool vec4, hipStream_t stream) {
   const auto pass = vec4 ? rad_pass_kernel<PHASE, 4> : rad_pass_kernel<PHASE, 1>;

@@ -1,11 +1,15 @@
 // What csrc/radiomics.hip, csrc/radiomics_texture.hip, csrc/radiomics_zones.hip and csrc/radiomics_mesh.hip share: the constants, the 13 directions, the state
-// block that the kernels of `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks and the wave-folded count.
+// block that the kernels of `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks, the wave-folded count and (with
+// csrc/radiomics_filter.hip) the descriptor's slope / inter rule.
 // Their fp64 sums over a workgroup are block_reduce<RAD_TPB / 64>(values, lds, Sum{}) of reduce.hpp: lanes by the butterfly, then the
 // waves in index order.
 #pragma once
 #include "../../include/mmnn_sts.h"
 #include "common.hpp"
+#include "ingest_load.hpp"
 #include "reduce.hpp"
+
+#include <cmath>
 
 namespace mmnn {
 
@@ -70,6 +74,16 @@ inline RadLayout rad_layout(long n) {
   L.bins = cv.take((size_t)n * 2);
   L.total = cv.cur;
   return L;
+}
+
+// The fp64 slope / inter pair of a descriptor, as ig_scale reads a header's pair.
+inline IgScale rad_scale(double slope, double inter) {
+  IgScale s{1.0, 0.0, 0};
+  if (slope == 0.0 || !std::isfinite(slope)) return s;
+  s.slope = slope;
+  s.inter = std::isfinite(inter) ? inter : 0.0;
+  s.on = !(s.slope == 1.0 && s.inter == 0.0);
+  return s;
 }
 
 inline int rad_validate(int x, int y, int z, int max_bins) {

@@ -103,6 +103,25 @@ class Parser:
             raise ConfigurationError('Radiomics.mesh_shape must be true or false, got {!r}'.format(mesh))
         return mesh
 
+    def radiomicsLog(self, sigma=None, bin_width=None):
+        """`Radiomics: log: {sigma: [1.0, 3.0], bin_width: 25}`: the Laplacian-of-Gaussian image type -> {'sigma': the scales in mm,
+        de-duplicated and ascending (empty: no filtered image), 'bin_width': the filtered images' bin width (`Radiomics: bin_width` when
+        not given)}.  `sigma` / `bin_width`: a command line's values, which go before the config's."""
+        from ..radiomics import log_sigmas
+        log = (self.config.get('Radiomics') or {}).get('log')
+        valid = 'Radiomics.log must be a mapping of `sigma` (a list of positive finite numbers, in mm) and optionally `bin_width` (a positive finite number)'
+        if log is None:
+            log = {}
+        if not isinstance(log, dict) or set(log) - {'sigma', 'bin_width'}:
+            raise ConfigurationError('{}, got {!r}'.format(valid, log))
+        if 'sigma' in log and not isinstance(log['sigma'], (list, tuple)):
+            raise ConfigurationError('{}, got sigma {!r}'.format(valid, log['sigma']))
+        sigmas = log_sigmas(sigma if sigma is not None else log.get('sigma'))
+        bw = bin_width if bin_width is not None else log.get('bin_width', self.radiomicsConfig()['bin_width'])
+        if isinstance(bw, bool) or not isinstance(bw, (int, float)) or not (bw > 0.0 and bw < float('inf')):
+            raise ConfigurationError('{}, got bin_width {!r}'.format(valid, bw))
+        return {'sigma': sigmas, 'bin_width': float(bw)}
+
     def _radiomicsExcluded(self):
         rm = self.config.get('RadiomicsModel') or {}
         return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])

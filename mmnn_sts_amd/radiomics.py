@@ -1,14 +1,16 @@
 """Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip), of
-`mmnn_radiomics_texture` (csrc/radiomics_texture.hip), of `mmnn_radiomics_zones` (csrc/radiomics_zones.hip) and of `mmnn_radiomics_mesh`
-(csrc/radiomics_mesh.hip).
+`mmnn_radiomics_texture` (csrc/radiomics_texture.hip), of `mmnn_radiomics_zones` (csrc/radiomics_zones.hip), of `mmnn_radiomics_mesh`
+(csrc/radiomics_mesh.hip) and of `mmnn_log_filter` (csrc/radiomics_filter.hip).
 
     extract(scan, mask, device)            enqueue one extraction; the result holds device tensors, nothing is read back
     finish(result, affine)                 one read-back -> {feature name: float}: adds TotalEnergy and the voxel-based shape features
     extract_tree(dataset, device, out)     every patient and modality of an image dataset -> a csv (`MRN`, then the features)
-    feature_names(classes, glszm, mesh)    the columns: FEATURE_NAMES, then those of the requested texture classes, then the size-zone ones,
-                                           then the mesh-based shape ones
+    feature_names(classes, glszm, mesh, log_sigma)  the columns: FEATURE_NAMES, then those of the requested texture classes, then the
+                                           size-zone ones, then the mesh-based shape ones, then those of the filtered images
+    log_taps(sigma_mm, spacing)            the radii, taps and weights of one Laplacian-of-Gaussian scale (numpy fp64, host only)
+    log_filter(scan, sigma_mm, device)     enqueue the filter; the float32 volume stays on the device
     python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] [--glszm]
-                                     [--mesh_shape] --out radiomics.csv
+                                     [--mesh_shape] [--log_sigma 1,3 [--log_bin_width B]] --out radiomics.csv
 
 Upstream reads such a csv (`Data: rad_loc`, data/RadiomicsDatasets.py) and leaves its extraction to PyRadiomics; here the table is built
 from the very pair the image path ingests, through the same mask routes (NIfTI mask, resampled mask, DICOM mask series, RTSTRUCT, SEG:
@@ -35,6 +37,15 @@ modality with the switch alone, 106 with all classes and `glszm`.  Slice, Column
 fixed.  They are pinned to the numpy restatement in tests/_radiomics_mesh_ref.py; **parity with PyRadiomics is unpinned**: its table may
 triangulate some configurations differently, and it scales by the spacing alone where this uses the full linear part.  The GLCM's MCC
 stays out of scope.
+
+`log_sigma` (`Radiomics: log: {sigma: [1.0, 3.0], bin_width: 25}`, `--log_sigma 1,3`; empty by default) adds a second image type: for
+every sigma (in mm, ascending) the scan is filtered on the device by a Laplacian of Gaussian at that physical scale (`log_filter`: the
+taps follow the scan's voxel spacing, the column norms of its affine's linear part) and the same extraction calls -- first order and GLCM,
+the requested texture classes and `glszm`, never the shape classes -- run on the filtered volume under the same device mask, binned at
+`log_bin_width` (the original image's `bin_width` when not given).  Their columns `log-sigma-<sigma>-mm-3D_*` (sigma 3 is written `3-0`)
+follow every `original_*` one: 41 per sigma by default, 92 with all classes and `glszm`.  The filter is pinned to the numpy restatement
+in tests/_radiomics_log_ref.py, bit for bit, and that one to scipy's `gaussian_filter`; **parity with PyRadiomics is unpinned**: its LoG
+is ITK's recursive (IIR) Gaussian, this one a sampled FIR truncated at 4 sigma.
 """
 import argparse
 import csv
@@ -42,7 +53,7 @@ import ctypes
 import logging
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -81,7 +92,9 @@ TEXTURE_CLASSES = ("glrlm", "gldm", "ngtdm")
 _TEXTURE = {"glrlm": GLRLM, "gldm": GLDM, "ngtdm": NGTDM}
 FEATURE_NAMES = tuple([f"original_firstorder_{n}" for n in FIRSTORDER] + [f"original_shape_{n}" for n in SHAPE]
                       + [f"original_glcm_{n}" for n in GLCM])
+LOG_TRUNCATE = 4.0
 _logged_identity = False
+_logged_unit_spacing = False
 
 
 def texture_classes(classes) -> tuple:
@@ -101,12 +114,46 @@ def texture_classes(classes) -> tuple:
     return tuple(c for c in TEXTURE_CLASSES if c in names)
 
 
-def feature_names(classes=(), glszm=False, mesh=False) -> tuple:
+def log_sigmas(sigma) -> tuple:
+    """`sigma` (numbers, a comma-separated string, one number or None) -> the scales in mm, de-duplicated and ascending."""
+    if sigma is None:
+        return ()
+    if isinstance(sigma, str):
+        sigma = [v for v in sigma.replace(",", " ").split() if v]
+    elif isinstance(sigma, (int, float)) and not isinstance(sigma, bool):
+        sigma = [sigma]
+    if not isinstance(sigma, (list, tuple)):
+        raise ConfigurationError(f"radiomics: log sigma must be a list of positive finite numbers (mm), got {sigma!r}")
+    out = set()
+    for v in sigma:
+        try:
+            f = math.nan if isinstance(v, bool) else float(v)
+        except (TypeError, ValueError):
+            f = math.nan
+        if not (f > 0.0 and f < math.inf):
+            raise ConfigurationError(f"radiomics: log sigma {v!r} is not a positive finite number (mm)")
+        out.add(f)
+    return tuple(sorted(out))
+
+
+def log_image_type(sigma) -> str:
+    """PyRadiomics' name of the LoG image type at `sigma` mm: 3 -> `log-sigma-3-0-mm-3D`, 1.5 -> `log-sigma-1-5-mm-3D`."""
+    return "log-sigma-" + str(float(sigma)).replace(".", "-") + "-mm-3D"
+
+
+def feature_names(classes=(), glszm=False, mesh=False, log_sigma=()) -> tuple:
     """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes, then with `glszm`
-    `original_glszm_*`, then with `mesh` the eight mesh-based `original_shape_*`."""
-    return (FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
-            + (tuple(f"original_glszm_{n}" for n in GLSZM) if glszm else ())
-            + (tuple(f"original_shape_{n}" for n in MESH_SHAPE) if mesh else ()))
+    `original_glszm_*`, then with `mesh` the eight mesh-based `original_shape_*`; then for every sigma of `log_sigma`, ascending,
+    `log-sigma-<sigma>-mm-3D_firstorder_*`, `_glcm_*`, the requested classes and with `glszm` `_glszm_*` (never the shape classes)."""
+    names = (FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
+             + (tuple(f"original_glszm_{n}" for n in GLSZM) if glszm else ())
+             + (tuple(f"original_shape_{n}" for n in MESH_SHAPE) if mesh else ()))
+    for s in log_sigmas(log_sigma):
+        im = log_image_type(s)
+        names += (tuple(f"{im}_firstorder_{n}" for n in FIRSTORDER) + tuple(f"{im}_glcm_{n}" for n in GLCM)
+                  + tuple(f"{im}_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
+                  + (tuple(f"{im}_glszm_{n}" for n in GLSZM) if glszm else ()))
+    return names
 
 
 @dataclass
@@ -117,7 +164,10 @@ class RadiomicsResult:
     `ngtdm_s` (max_bins, 27) int64; `classes`, the requested ones (the device computes all three).  With `glszm`: `zones`, the bytes of
     mmnn_radiomics_zones_result; `labels` and `sizes` (x * y * z,) and `levels` (max_bins,) int32 views of the uint32 tables.  With `mesh`:
     `mesh`, the bytes of mmnn_radiomics_mesh_result; `mesh_cfg` (256,) int64, the cells per configuration; `linear`, the 3 x 3 linear part
-    that was enqueued with the call (the scan's, the identity without an affine)."""
+    that was enqueued with the call (the scan's, the identity without an affine).  With `log_sigma`: `log`, a tuple of (sigma, the
+    RadiomicsResult of the image filtered at sigma); such a result has `image` set to its image type, `bin_width` the filtered images'
+    and `filtered`, the DeviceVolume `log_filter` returned (float32, on the scan's grid), beside `filter_taps`, the taps on the device;
+    `filter_workspace`, which the scales of one extraction share, is on the original image's result."""
     block: torch.Tensor
     hist: torch.Tensor
     glcm: torch.Tensor
@@ -144,6 +194,11 @@ class RadiomicsResult:
     mesh_workspace: Optional[torch.Tensor] = None
     linear: Optional[np.ndarray] = None
     mesh_shape: bool = False
+    image: str = "original"
+    log: tuple = ()
+    filtered: Optional[object] = None
+    filter_taps: Optional[torch.Tensor] = None
+    filter_workspace: Optional[torch.Tensor] = None
 
 
 def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
@@ -153,21 +208,134 @@ def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) ->
     return int(n)
 
 
+def spacing_of(affine) -> Tuple[float, float, float]:
+    """The voxel spacing in mm along x, y, z: the column norms of the affine's linear part; (1, 1, 1) without an affine."""
+    global _logged_unit_spacing
+    if affine is None:
+        if not _logged_unit_spacing:
+            logger.info("radiomics: a scan without an affine: the LoG scales are in voxels (spacing 1, 1, 1)")
+            _logged_unit_spacing = True
+        return (1.0, 1.0, 1.0)
+    return tuple(float(v) for v in np.sqrt((_linear_of(affine) ** 2).sum(axis=0)))
+
+
+def log_taps(sigma_mm: float, spacing=(1.0, 1.0, 1.0)):
+    """The sampled Laplacian-of-Gaussian kernel of scale `sigma_mm` on a grid of voxel `spacing` (x, y, z, in mm), separated per axis:
+    -> (radius[3], taps, weight[3]), numpy fp64.  Per axis a, with s_a its spacing:
+        sigma_a = sigma / s_a                       the scale in voxels
+        r_a = int(4 sigma_a + 0.5)                  the truncation at 4 sigma, rounded to the nearest sample
+        k = -r_a .. r_a;  g = exp(-k^2 / (2 sigma_a^2));  g /= g.sum()                 the smoothing taps, which sum to 1
+        d = (k^2 / sigma_a^4 - 1 / sigma_a^2) g                                        the sampled second derivative
+        h = d - g d.sum()                           so that h sums to 0 and a constant image filters to 0 (the sampled d alone leaves a
+                                                    bias of 6 % of the image mean at sigma_a = 0.6)
+        w_a = sigma^2 / s_a^2                       ITK's normalise-across-scale (sigma^2) together with the mm Laplacian (1 / s_a^2)
+    `taps` is g_x, h_x, g_y, h_y, g_z, h_z behind each other, as `mmnn_log_filter` reads them: the filtered image is
+    sum_a w_a (h_a along a, g along the two other axes).  An axis whose r_a would be 0 or above the library's largest radius raises
+    ConfigurationError."""
+    sigma = float(sigma_mm)
+    if not (sigma > 0.0 and sigma < math.inf):
+        raise ConfigurationError(f"radiomics: log sigma {sigma_mm!r} is not a positive finite number (mm)")
+    radius, taps, weight = [], [], []
+    for axis, s in zip("xyz", spacing):
+        s = float(s)
+        if not (s > 0.0 and s < math.inf):
+            raise ConfigurationError(f"radiomics: log sigma {sigma} mm: the {axis} axis has spacing {s} mm, which is not positive and finite")
+        sv = sigma / s
+        r = int(LOG_TRUNCATE * sv + 0.5)
+        if not 1 <= r <= _lib.LOG_FILTER_MAX_RADIUS:
+            raise ConfigurationError(f"radiomics: log sigma {sigma} mm on the {axis} axis (spacing {s} mm) is {sv:.4g} voxels, a kernel radius "
+                                     f"of {r}: the filter takes radii 1..{_lib.LOG_FILTER_MAX_RADIUS} (sigma between 0.125 and "
+                                     f"{(_lib.LOG_FILTER_MAX_RADIUS + 0.5) / LOG_TRUNCATE:.5g} voxels on every axis)")
+        k = np.arange(-r, r + 1, dtype=np.float64)
+        g = np.exp(-(k * k) / (2.0 * sv * sv))
+        g /= g.sum()
+        d = ((k * k) / sv ** 4 - 1.0 / (sv * sv)) * g
+        h = d - g * d.sum()
+        radius.append(r)
+        taps += [g, h]
+        weight.append(sigma * sigma / (s * s))
+    return np.array(radius, dtype=np.int32), np.concatenate(taps), np.array(weight, dtype=np.float64)
+
+
+def log_filter(scan, sigma_mm: float, device, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+               taps: Optional[torch.Tensor] = None):
+    """Enqueue `mmnn_log_filter` on the current stream of `device`: `scan` (whatever `ingest.upload` takes) filtered by the Laplacian of
+    Gaussian of `sigma_mm` under `log_taps`' rule, with the spacing of the scan's affine.  Returns a DeviceVolume of float32 (NIfTI code
+    16) with slope 0 (no scaling) and the scan's affine, which `extract` and the ingest take like any scan.  `out`: a contiguous float32
+    tensor of x * y * z elements on the device to write; `workspace`: at least `mmnn_log_filter_workspace_bytes` bytes of uint8; `taps`: a
+    float64 device tensor of the taps' length to upload them into.  Each is allocated when None."""
+    from .data import ingest
+    return _enqueue_log_filter(ingest.upload(scan, torch.device(device)), sigma_mm, out, workspace, taps)[0]
+
+
+def _enqueue_log_filter(scan, sigma_mm, out, workspace, taps):
+    """`log_filter` on an uploaded scan -> (the filtered DeviceVolume, the workspace, the taps on the device)."""
+    from .data import ingest
+    dev = scan.data.device
+    x, y, z = scan.shape
+    radius, host_taps, weight = log_taps(sigma_mm, spacing_of(scan.affine))
+    nbytes = _lib.lib().mmnn_log_filter_workspace_bytes(x, y, z)
+    if nbytes < 0:
+        raise ValueError("mmnn_log_filter_workspace_bytes: " + _lib.last_error())
+    if out is None:
+        out = torch.empty(x * y * z, dtype=torch.float32, device=dev)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x * y * z and out.device == dev):
+        raise ValueError(f"log_filter: out must be {x * y * z} contiguous float32 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    if workspace is None:
+        workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f"log_filter: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, {nbytes} needed on {dev}")
+    if taps is None:
+        taps = torch.empty(host_taps.size, dtype=torch.float64, device=dev)
+    if not (taps.dtype == torch.float64 and taps.is_contiguous() and taps.numel() == host_taps.size and taps.device == dev):
+        raise ValueError(f"log_filter: taps must be {host_taps.size} contiguous float64 on {dev}")
+    taps.copy_(torch.from_numpy(host_taps))
+    desc = _lib.LogFilterDesc(x, y, z, scan.datatype, float(scan.slope), float(scan.inter), (ctypes.c_int32 * 3)(*radius.tolist()),
+                              (ctypes.c_double * 3)(*weight.tolist()))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mmnn_log_filter(ctypes.byref(desc), scan.data.data_ptr(), taps.data_ptr(), out.data_ptr(), workspace.data_ptr(),
+                                              stream), "mmnn_log_filter")
+    return ingest.DeviceVolume(out.view(torch.uint8), (x, y, z), 16, 0.0, 0.0, scan.affine), workspace, taps
+
+
 def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS, index_map=None,
             threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=(), glszm: bool = False,
-            mesh: bool = False) -> RadiomicsResult:
+            mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None) -> RadiomicsResult:
     """Enqueue the extraction of one (scan, mask) pair on the current stream of `device`.  `scan` / `mask`: whatever `ingest_volume`
     takes (host volumes are uploaded; a contour, SEG or other-grid mask is brought onto the scan's grid first, `index_map` and
     `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again.  `classes`:
     texture classes of TEXTURE_CLASSES; when not empty `mmnn_radiomics_texture` is enqueued behind the extraction.  `glszm`: enqueue
     `mmnn_radiomics_zones` behind them.  `mesh`: enqueue `mmnn_radiomics_mesh` behind those, with the linear part of the scan's affine (the
-    identity without one), which the result remembers."""
+    identity without one), which the result remembers.  `log_sigma`: LoG scales in mm; behind the original image's calls, for each sigma
+    ascending, `log_filter` and then the same calls but the mesh one on the filtered volume, under the same prepared mask and binned at
+    `log_bin_width` (None: `bin_width`); the results are `RadiomicsResult.log`.  `buffers` must then come from an extraction with the
+    same scales."""
     from .data import ingest
     dev = torch.device(device)
     scan, mask = ingest.prepare_pair(scan, mask, dev, index_map, threshold, what="radiomics")
+    classes, sigmas = texture_classes(classes), log_sigmas(log_sigma)
+    if buffers is not None and tuple(s for s, _ in buffers.log) != sigmas:
+        raise ValueError(f"radiomics: buffers of the LoG scales {tuple(s for s, _ in buffers.log)} cannot take an extraction at {sigmas}")
+    out = _extract_image(scan, mask, bin_width, max_bins, buffers, classes, glszm, mesh)
+    if sigmas:
+        out.filter_workspace = None if buffers is None else buffers.filter_workspace
+        subs = []
+        for i, s in enumerate(sigmas):
+            old = None if buffers is None else buffers.log[i][1]
+            vol, out.filter_workspace, taps = _enqueue_log_filter(scan, s, None if old is None else old.filtered.data.view(torch.float32),
+                                                                  out.filter_workspace, None if old is None else old.filter_taps)
+            sub = _extract_image(vol, mask, bin_width if log_bin_width is None else log_bin_width, max_bins, old, classes, glszm, False)
+            sub.image, sub.filtered, sub.filter_taps = log_image_type(s), vol, taps
+            subs.append((s, sub))
+        out.log = tuple(subs)
+    return out
+
+
+def _extract_image(scan, mask, bin_width, max_bins, buffers, classes, glszm, mesh) -> RadiomicsResult:
+    """The calls of one image (the original scan or a filtered volume) under the prepared device mask."""
     x, y, z = scan.shape
     max_bins = int(max_bins)
-    classes = texture_classes(classes)
     nbytes = workspace_bytes(x, y, z, max_bins)
     if buffers is not None and (tuple(buffers.shape) != (x, y, z) or buffers.max_bins != max_bins or buffers.block.device != scan.data.device):
         raise ValueError(f"radiomics: buffers of extent {buffers.shape} / {buffers.max_bins} bins cannot take a scan of {(x, y, z)} / {max_bins}")
@@ -336,17 +504,21 @@ def shape_features(n: int, moments, linear) -> Dict[str, float]:
 
 
 def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=(), zones: Optional[dict] = None,
-                mesh: Optional[dict] = None) -> Dict[str, float]:
+                mesh: Optional[dict] = None, image: str = "original") -> Dict[str, float]:
     """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block; with `zones`, the unpacked
-    size-zone block; with `mesh`, the unpacked mesh block, whose area and diameters were computed under the linear part of `affine`)."""
+    size-zone block; with `mesh`, the unpacked mesh block, whose area and diameters were computed under the linear part of `affine`).
+    `image`: the image type that prefixes the columns; a filtered one has no shape columns and is named in what a flag raises."""
     global _logged_identity
+    if image != "original":
+        what = f"{what}, image type {image}"
     if fields["empty"]:
         raise ConfigurationError(f"{what}: the mask selects no voxel of the scan")
     if fields["nonfinite"]:
         raise ConfigurationError(f"{what}: a NaN or infinite voxel value lies inside the mask")
     if fields["overflow"]:
         raise ConfigurationError(f"{what}: the values inside the mask span {fields['n_bins']} bins, more than max_bins: choose a larger "
-                                 "bin_width (Radiomics: bin_width) or more bins (Radiomics: max_bins)")
+                                 + ("bin_width (Radiomics: bin_width)" if image == "original" else
+                                    "log.bin_width (Radiomics: log: bin_width, --log_bin_width)") + " or more bins (Radiomics: max_bins)")
     if affine is None:
         if not _logged_identity:
             logger.info("radiomics: a scan without an affine: shape features in voxel units (the identity)")
@@ -356,20 +528,21 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
         linear = np.asarray(affine, dtype=np.float64)[:3, :3]
     out = {}
     fo = dict(zip(DEVICE_FIRSTORDER, (float(v) for v in fields["firstorder"])))
-    shape = shape_features(fields["n"], fields["moments"], linear)
     fo["TotalEnergy"] = fo["Energy"] * abs(float(np.linalg.det(linear)))
     for n in FIRSTORDER:
-        out[f"original_firstorder_{n}"] = fo[n]
-    for n in SHAPE:
-        out[f"original_shape_{n}"] = shape[n]
+        out[f"{image}_firstorder_{n}"] = fo[n]
+    if image == "original":
+        shape = shape_features(fields["n"], fields["moments"], linear)
+        for n in SHAPE:
+            out[f"original_shape_{n}"] = shape[n]
     for n, v in zip(GLCM, fields["glcm"]):
-        out[f"original_glcm_{n}"] = float(v)
+        out[f"{image}_glcm_{n}"] = float(v)
     for c in texture_classes(classes):
         for n, v in zip(_TEXTURE[c], texture[c]):
-            out[f"original_{c}_{n}"] = float(v)
+            out[f"{image}_{c}_{n}"] = float(v)
     if zones is not None:
         for n, v in zip(GLSZM, zones["glszm"]):
-            out[f"original_glszm_{n}"] = float(v)
+            out[f"{image}_glszm_{n}"] = float(v)
     if mesh is not None:
         for n, v in mesh_features(mesh, linear).items():
             out[f"original_shape_{n}"] = v
@@ -378,7 +551,9 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
 
 def _stacked(r: RadiomicsResult) -> torch.Tensor:
     """The result blocks of one extraction behind each other: what one read-back brings to the host."""
-    parts = [r.block] + ([r.texture] if r.classes else []) + ([r.zones] if r.glszm else []) + ([r.mesh] if r.mesh_shape else [])
+    parts = []
+    for q in (r,) + tuple(sub for _, sub in r.log):
+        parts += [q.block] + ([q.texture] if q.classes else []) + ([q.zones] if q.glszm else []) + ([q.mesh] if q.mesh_shape else [])
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
@@ -389,16 +564,22 @@ def _features_of_stacked(raw: np.ndarray, r: RadiomicsResult, affine, what: str)
     if r.mesh_shape and not np.array_equal(_linear_of(affine), r.linear):
         raise ValueError(f"{what}: the mesh-based shape features were enqueued under the linear part {r.linear.tolist()}; `finish` cannot "
                          f"apply another one ({_linear_of(affine).tolist()}): extract with the affine that is meant")
-    return features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:nt]) if r.classes else None, r.classes,
-                       unpack_zones(raw[nt:nz]) if r.glszm else None, unpack_mesh(raw[nz:nz + _lib.RADIOMICS_MESH_BYTES]) if r.mesh_shape else None)
+    nm = nz + (_lib.RADIOMICS_MESH_BYTES if r.mesh_shape else 0)
+    out = features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:nt]) if r.classes else None, r.classes,
+                      unpack_zones(raw[nt:nz]) if r.glszm else None, unpack_mesh(raw[nz:nm]) if r.mesh_shape else None, r.image)
+    for _, sub in r.log:                                                                # the filtered images' blocks follow, sigma ascending
+        raw = raw[nm:]
+        nm = nb + (_lib.RADIOMICS_TEXTURE_BYTES if sub.classes else 0) + (_lib.RADIOMICS_ZONES_BYTES if sub.glszm else 0)
+        out.update(_features_of_stacked(raw[:nm], sub, affine, what))
+    return out
 
 
 def finish(result: RadiomicsResult, affine="scan", what: str = "radiomics") -> Dict[str, float]:
     """One read-back of the result block(s) -> {name: float} over FEATURE_NAMES, then the columns of the result's texture classes, with
     `glszm` the size-zone ones and with `mesh` the mesh-based shape ones (ValueError when `affine` is passed and its linear part is not the
-    one the mesh call was enqueued with).  `affine`: the scan's voxel index -> mm matrix (4x4 or
-    its 3x3 linear part as the top-left block), None for the identity; the default takes the scan's own.  A flag raises
-    ConfigurationError with the cause."""
+    one the mesh call was enqueued with), then the columns of the result's filtered images.  `affine`: the scan's voxel index -> mm
+    matrix (4x4 or its 3x3 linear part as the top-left block), None for the identity; the default takes the scan's own.  A flag raises
+    ConfigurationError with the cause, and names the image type when a filtered image set it."""
     if isinstance(affine, str):
         affine = result.affine
     return _features_of_stacked(_stacked(result).cpu().numpy(), result, affine, what)
@@ -410,14 +591,15 @@ def _volumes_of(dataset, patient):
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
                  mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False,
-                 mesh: bool = False) -> List[dict]:
+                 mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
     A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
-    blocks, with `glszm` the size-zone blocks and with `mesh` the mesh blocks, come back in the batch's same stacked read-back."""
+    blocks, with `glszm` the size-zone blocks, with `mesh` the mesh blocks and with `log_sigma` the filtered images' blocks, come back in
+    the batch's same stacked read-back."""
     from .data import ingest
     dev = torch.device(device)
-    classes = texture_classes(classes)
+    classes, log_sigma = texture_classes(classes), log_sigmas(log_sigma)
     rows = []
     patients = list(dataset.patients)
     for b0 in range(0, len(patients), max(1, int(batch))):
@@ -425,7 +607,8 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         raws = [_volumes_of(dataset, p) for p in chunk]
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
-        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm, mesh=mesh)
+        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm, mesh=mesh,
+                        log_sigma=log_sigma, log_bin_width=log_bin_width)
                 for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
         blocks = torch.stack([_stacked(r) for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
@@ -475,6 +658,10 @@ def main(argv=None):
                     "`Radiomics: glszm: true`")
     ap.add_argument("--mesh_shape", action="store_true", help="append the 8 mesh-based shape columns (volume, surface area, sphericity, the "
                     "diameters); also switched on by the config's `Radiomics: mesh_shape: true`")
+    ap.add_argument("--log_sigma", default=None, help="Laplacian-of-Gaussian scales in mm, comma-separated (1,3): appends the "
+                    "log-sigma-<sigma>-mm-3D_* columns of every scale; overrides the config's `Radiomics: log: sigma`")
+    ap.add_argument("--log_bin_width", type=float, default=None, help="bin width of the filtered images; overrides the config's "
+                    "`Radiomics: log: bin_width` (default: the original image's bin width)")
     a = ap.parse_args(argv)
     import os
     from .data.ImageDatasets import ImageDataset
@@ -484,6 +671,7 @@ def main(argv=None):
     classes = texture_classes(a.classes) if a.classes is not None else parser.radiomicsClasses()
     glszm = a.glszm or parser.radiomicsZones()
     mesh = a.mesh_shape or parser.radiomicsMesh()
+    log = parser.radiomicsLog(a.log_sigma, a.log_bin_width)
     data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
@@ -494,7 +682,8 @@ def main(argv=None):
     rows = None
     for ds, px in zip(sets, ("t1_", "t2_") if len(sets) == 2 else ("",)):
         part = extract_tree(ds, a.device, None, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
-                            data.get("mask_threshold"), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh)
+                            data.get("mask_threshold"), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh, log_sigma=log["sigma"],
+                            log_bin_width=log["bin_width"])
         if rows is None:
             rows = part
         else:
