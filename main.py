@@ -287,19 +287,12 @@ def extract_radiomics_if_needed(parser, args):
     log = parser.radiomicsLog(getattr(args, "log_sigma", None), getattr(args, "log_bin_width", None))
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
-    prefixes = ("t1_", "t2_") if len(paths) == 2 else ("",)
-    rows = None
-    for path, px in zip(paths, prefixes):
-        ds = ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
-        threshold = (parser.config.get("Data") or {}).get("mask_threshold")
-        part = radiomics.extract_tree(ds, torch.device("cuda", 0), None, rc["bin_width"], rc["max_bins"],
-                                      None if threshold is None else float(threshold), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh,
-                                      log_sigma=log["sigma"], log_bin_width=log["bin_width"])
-        if rows is None:
-            rows = part
-        else:
-            by = {r["MRN"]: r for r in part}
-            rows = [dict(r, **{k: v for k, v in by[r["MRN"]].items() if k != "MRN"}) for r in rows if r["MRN"] in by]
+    sets = [ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
+            for path in paths]
+    threshold = (parser.config.get("Data") or {}).get("mask_threshold")
+    rows = radiomics.extract_modalities(sets, torch.device("cuda", 0), rc["bin_width"], rc["max_bins"],
+                                        None if threshold is None else float(threshold), classes=classes, glszm=glszm, mesh=mesh,
+                                        log_sigma=log["sigma"], log_bin_width=log["bin_width"])
     os.makedirs(args.output_path, exist_ok=True)
     out = os.path.join(args.output_path, "radiomics_features.csv")
     radiomics.write_csv(out, rows)

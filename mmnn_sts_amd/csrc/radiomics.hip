@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(RAD_TPB) rad_step_kernel(const RadArgs a) {
       for (int k = 0; k < 9; ++k) r->moments[k] = (long long)fold[RS_MOM + k];
       r->n_bins = s.n_bins;
       r->overflow = overflow; r->nonfinite = nonfinite; r->empty = empty;
-      const double nan = __longlong_as_double(0x7ff8000000000000ll);
+      const double nan = rad_nan();
       for (int k = 0; k < RAD_RANKS; ++k) r->order[k] = nan;
       for (int k = 0; k < MMNN_RADIOMICS_FIRSTORDER; ++k) r->firstorder[k] = nan;
       for (int k = 0; k < RAD_NF; ++k) r->glcm[k] = nan;

@@ -1,6 +1,7 @@
 // What csrc/radiomics.hip, csrc/radiomics_texture.hip, csrc/radiomics_zones.hip and csrc/radiomics_mesh.hip share: the constants, the 13 directions, the state
-// block that the kernels of `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks, the wave-folded count and (with
-// csrc/radiomics_filter.hip) the descriptor's slope / inter rule.
+// block that the kernels of `mmnn_radiomics` leave in the workspace, the workspace layout, the extent checks, the prologue of the follow-on
+// calls (their descriptor checks and what they read of the first call), the wave-folded count and (with csrc/radiomics_filter.hip) the
+// descriptor's slope / inter rule.
 // Their fp64 sums over a workgroup are block_reduce<RAD_TPB / 64>(values, lds, Sum{}) of reduce.hpp: lanes by the butterfly, then the
 // waves in index order.
 #pragma once
@@ -48,6 +49,17 @@ struct RadState {
 #if defined(__HIPCC__)
 __device__ __forceinline__ double rad_plogp(double p) { return p * log2(p + RAD_EPS); }
 
+// The quiet NaN that fills a result block when a flag is set or a matrix is empty.
+__device__ __forceinline__ double rad_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// A flat voxel index (x fastest) -> (x, y, z) by two 32-bit divisions; XY = X * Y (x * y * z < 2^31).
+__device__ __forceinline__ void rad_split(unsigned idx, unsigned X, unsigned XY, int& x, int& y, int& z) {
+  const unsigned zq = idx / XY, r = idx - zq * XY, yq = r / X;
+  x = (int)(r - yq * X);
+  y = (int)yq;
+  z = (int)zq;
+}
+
 // One count per active lane into h[digit].  Called by whole waves; a wave whose active lanes agree sends one add of their number.
 __device__ __forceinline__ void rad_count(unsigned* h, unsigned digit, bool active) {
   const unsigned long long m = __ballot(active);
@@ -91,6 +103,32 @@ inline int rad_validate(int x, int y, int z, int max_bins) {
   MMNN_REQUIRE((double)x * y * z < 2147483648.0, "radiomics: extent %d x %d x %d holds 2^31 voxels or more", x, y, z);
   MMNN_REQUIRE(max_bins >= 1 && max_bins <= RAD_MAX_BINS, "radiomics: max_bins %d outside 1..%d", max_bins, RAD_MAX_BINS);
   return 0;
+}
+
+// What a follow-on call (texture, zones, mesh) requires of the descriptor the first call ran under; `who` prefixes the message.
+inline int rad_validate_follow(const char* who, const mmnn_radiomics_desc* d) {
+  MMNN_REQUIRE(d, "%s: null descriptor", who);
+  if (rad_validate(d->x, d->y, d->z, d->max_bins) != 0) return 1;
+  MMNN_REQUIRE(ig_type_size(d->scan_type) != 0, "%s: unsupported scan datatype code %d", who, d->scan_type);
+  MMNN_REQUIRE(ig_type_size(d->mask_type) != 0, "%s: unsupported mask datatype code %d", who, d->mask_type);
+  MMNN_REQUIRE(std::isfinite(d->bin_width) && d->bin_width > 0.0, "%s: bin_width must be finite and positive", who);
+  return 0;
+}
+
+// What every follow-on call reads of the first one: the bin volume (0 outside the ROI) and the state block in its workspace, the extents.
+struct RadFollow {
+  const uint16_t* bins;                     // [Z][Y][X]
+  const RadState* st;
+  int X, Y, Z;
+  unsigned N;                               // X * Y * Z
+};
+
+inline RadFollow rad_follow(const mmnn_radiomics_desc* d, const void* ws) {
+  const long n = (long)d->x * d->y * d->z;
+  const RadLayout R = rad_layout(n);
+  const char* wsb = static_cast<const char*>(ws);
+  return RadFollow{reinterpret_cast<const uint16_t*>(wsb + R.bins), reinterpret_cast<const RadState*>(wsb + R.state), d->x, d->y, d->z,
+                   (unsigned)n};
 }
 
 }  // namespace mmnn

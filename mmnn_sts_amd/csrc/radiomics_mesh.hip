@@ -35,11 +35,8 @@ constexpr int MS_ACC = 8;
 static_assert(MS_TILE == RAD_TPB, "one staged vertex and one configuration per lane");
 enum { MA_NV = 0, MA_ORIGIN = 1, MA_Q = 2 };  // acc: vertex cursor, sum (o - lo) . N, then the bit patterns of the four maxima
 
-struct MeshArgs {
-  const uint16_t* bins;                     // [Z][Y][X]
-  const RadState* st;
+struct MeshArgs : RadFollow {
   const mmnn_radiomics_result* res;         // the first call's block: lo[3]
-  int X, Y, Z;
   unsigned long long cells;                 // (X + 1)(Y + 1)(Z + 1)
   unsigned long long* cfg;                  // [256], caller-owned
   unsigned long long* acc;                  // [MS_ACC]
@@ -167,10 +164,9 @@ __global__ void __launch_bounds__(RAD_TPB) mesh_final_kernel(const MeshArgs a) {
   const int t = threadIdx.x;
   if (a.st->flagged) {                                                  // cfg was zeroed by the memset
     if (t == 0) {
-      const double nan = __longlong_as_double(0x7ff8000000000000ll);
       a.out->n_vertices = 0; a.out->n_triangles = 0; a.out->volume48 = 0;
-      a.out->area = nan;
-      for (int k = 0; k < 4; ++k) a.out->q[k] = nan;
+      a.out->area = rad_nan();
+      for (int k = 0; k < 4; ++k) a.out->q[k] = rad_nan();
     }
     return;
   }
@@ -236,26 +232,18 @@ int mmnn_radiomics_mesh_table(int8_t* tri, int32_t* l48, int32_t* nsum) {
 
 int mmnn_radiomics_mesh(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws, const double* linear,
                         mmnn_radiomics_mesh_result* out, uint64_t* cfg, void* ws4, void* stream_) {
-  MMNN_REQUIRE(d, "radiomics_mesh: null descriptor");
-  if (rad_validate(d->x, d->y, d->z, d->max_bins) != 0) return 1;
-  MMNN_REQUIRE(ig_type_size(d->scan_type) != 0, "radiomics_mesh: unsupported scan datatype code %d", d->scan_type);
-  MMNN_REQUIRE(ig_type_size(d->mask_type) != 0, "radiomics_mesh: unsupported mask datatype code %d", d->mask_type);
-  MMNN_REQUIRE(std::isfinite(d->bin_width) && d->bin_width > 0.0, "radiomics_mesh: bin_width must be finite and positive");
+  if (rad_validate_follow("radiomics_mesh", d) != 0) return 1;
   MMNN_REQUIRE(result && ws && linear && out && cfg && ws4, "radiomics_mesh: null argument");
   for (int k = 0; k < 9; ++k) MMNN_REQUIRE(std::isfinite(linear[k]), "radiomics_mesh: linear[%d] is not finite", k);
   MMNN_REQUIRE((uintptr_t)ws % 256 == 0 && (uintptr_t)ws4 % 256 == 0 && (uintptr_t)result % 8 == 0 && (uintptr_t)out % 8 == 0 &&
                    (uintptr_t)cfg % 8 == 0,
                "radiomics_mesh: misaligned workspace / result / table");
   const hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const RadLayout R = rad_layout((long)d->x * d->y * d->z);
   const MeshLayout M = mesh_layout(d->x, d->y, d->z);
-  const char* wsb = static_cast<const char*>(ws);
   char* w4 = static_cast<char*>(ws4);
   MeshArgs a{};
-  a.bins = reinterpret_cast<const uint16_t*>(wsb + R.bins);
-  a.st = reinterpret_cast<const RadState*>(wsb + R.state);
+  static_cast<RadFollow&>(a) = rad_follow(d, ws);
   a.res = result;
-  a.X = d->x; a.Y = d->y; a.Z = d->z;
   a.cells = M.cells;
   a.cfg = reinterpret_cast<unsigned long long*>(cfg);
   a.acc = reinterpret_cast<unsigned long long*>(w4 + M.acc);

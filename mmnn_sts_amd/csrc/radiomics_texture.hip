@@ -35,11 +35,8 @@ constexpr int RADT_NBHD_CHUNKS = 1024;      // workgroups of the neighbourhood s
 constexpr int RADT_LDS_L = 4096;            // run-length marginal in LDS up to this L, in the second workspace beyond
 constexpr int RADT_NRL = MMNN_RADIOMICS_GLRLM, RADT_NDM = MMNN_RADIOMICS_GLDM, RADT_NGT = MMNN_RADIOMICS_NGTDM;
 
-struct TexArgs {
-  const uint16_t* bins;                     // [N]
-  const RadState* st;
-  int X, Y, Z, L;
-  unsigned N;
+struct TexArgs : RadFollow {
+  int L;
   int max_bins;
   unsigned* glrlm; unsigned* gldm; unsigned* ngn;
   unsigned long long* ngs;
@@ -67,8 +64,8 @@ __global__ void __launch_bounds__(RAD_TPB) glrlm_count_kernel(const TexArgs a) {
   for (unsigned idx = blockIdx.x * RAD_TPB + threadIdx.x; idx < a.N; idx += stride) {
     const unsigned b = a.bins[idx];
     if (b == 0u || b > (unsigned)ng) continue;
-    const unsigned zq = idx / XY, r = idx - zq * XY, yq = r / X;
-    const int x = (int)(r - yq * X), y = (int)yq, z = (int)zq;
+    int x, y, z;
+    rad_split(idx, X, XY, x, y, z);
     const int px = x - dx, py = y - dy, pz = z - dz;                    // (dz >= 0: pz < Z)
     if (px >= 0 && px < a.X && py >= 0 && py < a.Y && pz >= 0 && a.bins[idx - off] == b) continue;      // inside a run, not its start
     int len = 1, nx = x + dx, ny = y + dy, nz = z + dz;
@@ -107,8 +104,8 @@ __global__ void __launch_bounds__(RAD_TPB) nbhd_count_kernel(const TexArgs a) {
   for (unsigned idx = blockIdx.x * RAD_TPB + threadIdx.x; idx < a.N; idx += stride) {
     const unsigned b = a.bins[idx];
     if (b == 0u || b > (unsigned)ng) continue;
-    const unsigned zq = idx / XY, r = idx - zq * XY, yq = r / X;
-    const int x = (int)(r - yq * X), y = (int)yq, z = (int)zq;
+    int x, y, z;
+    rad_split(idx, X, XY, x, y, z);
     unsigned c = 0, same = 0, B = 0;
 #pragma unroll
     for (int ez = -1; ez <= 1; ++ez) {
@@ -179,8 +176,7 @@ __device__ void tex_matrix_features(const unsigned* P, size_t stride, int ng, in
   if (own) atomicAdd(total, own);
   __syncthreads();
   if (*total == 0ull) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    for (int k = 0; k < 16; ++k) f[k] = nan;
+    for (int k = 0; k < 16; ++k) f[k] = rad_nan();
     return;
   }
   const double Nr = (double)*total;
@@ -259,8 +255,7 @@ __device__ void tex_ngtdm_features(const unsigned* n, const unsigned long long* 
   }
   __syncthreads();
   if (*total == 0ull) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    for (int k = 0; k < 5; ++k) f[k] = nan;
+    for (int k = 0; k < 5; ++k) f[k] = rad_nan();
     return;
   }
   const double Nvp = (double)*total, Ngp = (double)*levels;
@@ -328,10 +323,9 @@ __global__ void __launch_bounds__(RAD_TPB) tex_features_kernel(const TexArgs a) 
 __global__ void __launch_bounds__(64) tex_final_kernel(const TexArgs a) {
   const int t = threadIdx.x;
   if (a.st->flagged) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    if (t < RADT_NRL) a.out->glrlm[t] = nan;
-    if (t < RADT_NDM) a.out->gldm[t] = nan;
-    if (t < RADT_NGT) a.out->ngtdm[t] = nan;
+    if (t < RADT_NRL) a.out->glrlm[t] = rad_nan();
+    if (t < RADT_NDM) a.out->gldm[t] = rad_nan();
+    if (t < RADT_NGT) a.out->ngtdm[t] = rad_nan();
     return;
   }
   if (t < RADT_NRL) {
@@ -372,27 +366,19 @@ int64_t mmnn_radiomics_texture_workspace_bytes(int32_t x, int32_t y, int32_t z, 
 int mmnn_radiomics_texture(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws,
                            mmnn_radiomics_texture_result* out, uint32_t* glrlm, uint32_t* gldm, uint32_t* ngtdm_n, uint64_t* ngtdm_s,
                            void* ws2, void* stream_) {
-  MMNN_REQUIRE(d, "radiomics_texture: null descriptor");
-  if (rad_validate(d->x, d->y, d->z, d->max_bins) != 0) return 1;
-  MMNN_REQUIRE(ig_type_size(d->scan_type) != 0, "radiomics_texture: unsupported scan datatype code %d", d->scan_type);
-  MMNN_REQUIRE(ig_type_size(d->mask_type) != 0, "radiomics_texture: unsupported mask datatype code %d", d->mask_type);
-  MMNN_REQUIRE(std::isfinite(d->bin_width) && d->bin_width > 0.0, "radiomics_texture: bin_width must be finite and positive");
+  if (rad_validate_follow("radiomics_texture", d) != 0) return 1;
   MMNN_REQUIRE(result && ws && out && glrlm && gldm && ngtdm_n && ngtdm_s && ws2, "radiomics_texture: null argument");
   MMNN_REQUIRE((uintptr_t)ws % 256 == 0 && (uintptr_t)ws2 % 256 == 0 && (uintptr_t)result % 8 == 0 && (uintptr_t)out % 8 == 0 &&
                    (uintptr_t)glrlm % 4 == 0 && (uintptr_t)gldm % 4 == 0 && (uintptr_t)ngtdm_n % 4 == 0 && (uintptr_t)ngtdm_s % 8 == 0,
                "radiomics_texture: misaligned workspace / result / table");
   const hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const long n = (long)d->x * d->y * d->z;
-  const RadLayout R = rad_layout(n);
   const int L = tex_longest(d->x, d->y, d->z);
   const TexLayout T = tex_layout(L);
-  const char* wsb = static_cast<const char*>(ws);
   char* ws2b = static_cast<char*>(ws2);
   TexArgs a{};
-  a.bins = reinterpret_cast<const uint16_t*>(wsb + R.bins);
-  a.st = reinterpret_cast<const RadState*>(wsb + R.state);
-  a.X = d->x; a.Y = d->y; a.Z = d->z; a.L = L;
-  a.N = (unsigned)n;
+  static_cast<RadFollow&>(a) = rad_follow(d, ws);
+  const long n = (long)a.N;
+  a.L = L;
   a.max_bins = d->max_bins;
   a.glrlm = glrlm; a.gldm = gldm; a.ngn = ngtdm_n;
   a.ngs = reinterpret_cast<unsigned long long*>(ngtdm_s);

@@ -44,11 +44,7 @@ static_assert(RAD_TPB >= RAD_MAX_PARTS, "zones_final_kernel holds one workgroup 
 enum { ZA_NZ = 0, ZA_J2 = 1, ZA_PS2 = 2, ZA_KEYS = 3, ZA_MAX = 4 };
 enum { ZS_SAE = 0, ZS_ZV = 1, ZS_ENT = 2, ZS_SALG = 3, ZS_SAHG = 4, ZS_LALG = 5, ZS_LAHG = 6 };
 
-struct ZoneArgs {
-  const uint16_t* bins;                     // [N]
-  const RadState* st;
-  int X, Y, Z;
-  unsigned N;
+struct ZoneArgs : RadFollow {
   int max_bins, parts;
   uint32_t* labels; uint32_t* sizes; uint32_t* levels;
   uint32_t* parent;                         // [N]
@@ -75,8 +71,8 @@ __global__ void __launch_bounds__(RAD_TPB) zones_link_kernel(const ZoneArgs a) {
   for (unsigned idx = blockIdx.x * RAD_TPB + threadIdx.x; idx < a.N; idx += stride) {
     const unsigned b = a.bins[idx];
     if (b == 0u || b > ng) continue;
-    const unsigned zq = idx / XY, r = idx - zq * XY, yq = r / X;
-    const int x = (int)(r - yq * X), y = (int)yq, z = (int)zq;
+    int x, y, z;
+    rad_split(idx, X, XY, x, y, z);
     bool linked = false;
     for (int d = 0; d < RAD_DIRS; ++d) {
       const int dz = rad_dirs[d][0], dy = rad_dirs[d][1], dx = rad_dirs[d][2];
@@ -242,7 +238,7 @@ __global__ void __launch_bounds__(RAD_TPB) zones_final_kernel(const ZoneArgs a) 
   long long* oi = reinterpret_cast<long long*>(a.out);                  // nz, n_keys, max_size, sum_pg2, sum_ps2, sum_j2
   if (a.st->flagged) {
     if (t < 6) oi[t] = 0;
-    if (t < ZN_NF) a.out->glszm[t] = __longlong_as_double(0x7ff8000000000000ll);
+    if (t < ZN_NF) a.out->glszm[t] = rad_nan();
     return;
   }
   const int ng = a.st->n_bins;
@@ -339,26 +335,17 @@ int64_t mmnn_radiomics_zones_workspace_bytes(int32_t x, int32_t y, int32_t z, in
 int mmnn_radiomics_zones(const mmnn_radiomics_desc* d, const mmnn_radiomics_result* result, const void* ws,
                          mmnn_radiomics_zones_result* out, uint32_t* labels, uint32_t* sizes, uint32_t* levels, void* ws3,
                          void* stream_) {
-  MMNN_REQUIRE(d, "radiomics_zones: null descriptor");
-  if (rad_validate(d->x, d->y, d->z, d->max_bins) != 0) return 1;
-  MMNN_REQUIRE(ig_type_size(d->scan_type) != 0, "radiomics_zones: unsupported scan datatype code %d", d->scan_type);
-  MMNN_REQUIRE(ig_type_size(d->mask_type) != 0, "radiomics_zones: unsupported mask datatype code %d", d->mask_type);
-  MMNN_REQUIRE(std::isfinite(d->bin_width) && d->bin_width > 0.0, "radiomics_zones: bin_width must be finite and positive");
+  if (rad_validate_follow("radiomics_zones", d) != 0) return 1;
   MMNN_REQUIRE(result && ws && out && labels && sizes && levels && ws3, "radiomics_zones: null argument");
   MMNN_REQUIRE((uintptr_t)ws % 256 == 0 && (uintptr_t)ws3 % 256 == 0 && (uintptr_t)result % 8 == 0 && (uintptr_t)out % 8 == 0 &&
                    (uintptr_t)labels % 4 == 0 && (uintptr_t)sizes % 4 == 0 && (uintptr_t)levels % 4 == 0,
                "radiomics_zones: misaligned workspace / result / table");
   const hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const long n = (long)d->x * d->y * d->z;
-  const RadLayout R = rad_layout(n);
-  const ZoneLayout Z = zone_layout(n, d->max_bins);
-  const char* wsb = static_cast<const char*>(ws);
-  char* w3 = static_cast<char*>(ws3);
   ZoneArgs a{};
-  a.bins = reinterpret_cast<const uint16_t*>(wsb + R.bins);
-  a.st = reinterpret_cast<const RadState*>(wsb + R.state);
-  a.X = d->x; a.Y = d->y; a.Z = d->z;
-  a.N = (unsigned)n;
+  static_cast<RadFollow&>(a) = rad_follow(d, ws);
+  const long n = (long)a.N;
+  const ZoneLayout Z = zone_layout(n, d->max_bins);
+  char* w3 = static_cast<char*>(ws3);
   a.max_bins = d->max_bins;
   a.labels = labels; a.sizes = sizes; a.levels = levels;
   a.parent = reinterpret_cast<uint32_t*>(w3 + Z.parent);

@@ -46,6 +46,11 @@ the requested texture classes and `glszm`, never the shape classes -- run on the
 follow every `original_*` one: 41 per sigma by default, 92 with all classes and `glszm`.  The filter is pinned to the numpy restatement
 in tests/_radiomics_log_ref.py, bit for bit, and that one to scipy's `gaussian_filter`; **parity with PyRadiomics is unpinned**: its LoG
 is ITK's recursive (IIR) Gaussian, this one a sampled FIR truncated at 4 sigma.
+
+STAGES states each call once -- its C symbol, buffers, switch, unpacking and columns -- and `extract`, `finish`, `feature_names` and
+`features_of` all read it; `enqueue(result, stage, desc, stream)` makes one call into the buffers a result already has.  One read-back
+brings every result block to the host, stacked per image (the original, then each filtered one, sigma ascending): the first call's block,
+then, of the calls that ran, the texture block, the size-zone block and the mesh block.
 """
 import argparse
 import csv
@@ -90,8 +95,6 @@ MESH_SHAPE = ("MeshVolume", "SurfaceArea", "SurfaceVolumeRatio", "Sphericity", "
               "Maximum2DDiameterColumn", "Maximum2DDiameterRow")
 TEXTURE_CLASSES = ("glrlm", "gldm", "ngtdm")
 _TEXTURE = {"glrlm": GLRLM, "gldm": GLDM, "ngtdm": NGTDM}
-FEATURE_NAMES = tuple([f"original_firstorder_{n}" for n in FIRSTORDER] + [f"original_shape_{n}" for n in SHAPE]
-                      + [f"original_glcm_{n}" for n in GLCM])
 LOG_TRUNCATE = 4.0
 _logged_identity = False
 _logged_unit_spacing = False
@@ -145,14 +148,10 @@ def feature_names(classes=(), glszm=False, mesh=False, log_sigma=()) -> tuple:
     """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes, then with `glszm`
     `original_glszm_*`, then with `mesh` the eight mesh-based `original_shape_*`; then for every sigma of `log_sigma`, ascending,
     `log-sigma-<sigma>-mm-3D_firstorder_*`, `_glcm_*`, the requested classes and with `glszm` `_glszm_*` (never the shape classes)."""
-    names = (FEATURE_NAMES + tuple(f"original_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
-             + (tuple(f"original_glszm_{n}" for n in GLSZM) if glszm else ())
-             + (tuple(f"original_shape_{n}" for n in MESH_SHAPE) if mesh else ()))
-    for s in log_sigmas(log_sigma):
-        im = log_image_type(s)
-        names += (tuple(f"{im}_firstorder_{n}" for n in FIRSTORDER) + tuple(f"{im}_glcm_{n}" for n in GLCM)
-                  + tuple(f"{im}_{c}_{n}" for c in texture_classes(classes) for n in _TEXTURE[c])
-                  + (tuple(f"{im}_glszm_{n}" for n in GLSZM) if glszm else ()))
+    classes, names = texture_classes(classes), ()
+    for im in ("original",) + tuple(log_image_type(s) for s in log_sigmas(log_sigma)):
+        on = {"classes": classes, "glszm": glszm, "mesh_shape": mesh and im == "original"}
+        names += tuple(n for st in STAGES if st.flag is None or on[st.flag] for n in st.names(im, classes))
     return names
 
 
@@ -201,11 +200,16 @@ class RadiomicsResult:
     filter_workspace: Optional[torch.Tensor] = None
 
 
-def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
-    n = _lib.lib().mmnn_radiomics_workspace_bytes(int(x), int(y), int(z), int(max_bins))
+def _bytes_or_raise(symbol: str, *extents) -> int:
+    """A `*_workspace_bytes` function of the library at these extents; its -1 raises with the library's message."""
+    n = getattr(_lib.lib(), symbol)(*(int(v) for v in extents))
     if n < 0:
-        raise ValueError("mmnn_radiomics_workspace_bytes: " + _lib.last_error())
+        raise ValueError(f"{symbol}: " + _lib.last_error())
     return int(n)
+
+
+def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
+    return _bytes_or_raise("mmnn_radiomics_workspace_bytes", x, y, z, max_bins)
 
 
 def spacing_of(affine) -> Tuple[float, float, float]:
@@ -274,9 +278,7 @@ def _enqueue_log_filter(scan, sigma_mm, out, workspace, taps):
     dev = scan.data.device
     x, y, z = scan.shape
     radius, host_taps, weight = log_taps(sigma_mm, spacing_of(scan.affine))
-    nbytes = _lib.lib().mmnn_log_filter_workspace_bytes(x, y, z)
-    if nbytes < 0:
-        raise ValueError("mmnn_log_filter_workspace_bytes: " + _lib.last_error())
+    nbytes = _bytes_or_raise("mmnn_log_filter_workspace_bytes", x, y, z)
     if out is None:
         out = torch.empty(x * y * z, dtype=torch.float32, device=dev)
     if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x * y * z and out.device == dev):
@@ -336,96 +338,50 @@ def _extract_image(scan, mask, bin_width, max_bins, buffers, classes, glszm, mes
     """The calls of one image (the original scan or a filtered volume) under the prepared device mask."""
     x, y, z = scan.shape
     max_bins = int(max_bins)
-    nbytes = workspace_bytes(x, y, z, max_bins)
     if buffers is not None and (tuple(buffers.shape) != (x, y, z) or buffers.max_bins != max_bins or buffers.block.device != scan.data.device):
         raise ValueError(f"radiomics: buffers of extent {buffers.shape} / {buffers.max_bins} bins cannot take a scan of {(x, y, z)} / {max_bins}")
-    dev = scan.data.device
-    if buffers is None:
-        block = torch.empty(_lib.RADIOMICS_RESULT_BYTES, dtype=torch.uint8, device=dev)
-        hist = torch.empty(max_bins, dtype=torch.int32, device=dev)
-        glcm = torch.empty((_lib.RADIOMICS_DIRECTIONS, max_bins, max_bins), dtype=torch.int32, device=dev)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    else:
-        block, hist, glcm, ws = buffers.block, buffers.hist, buffers.glcm, buffers.workspace
     desc = _lib.RadiomicsDesc(x, y, z, scan.datatype, mask.datatype, float(scan.slope), float(scan.inter), float(mask.slope), float(mask.inter),
                               float(bin_width), max_bins)
-    with torch.cuda.device(dev):
+    out = RadiomicsResult(None, None, None, None, (x, y, z), scan.affine, float(bin_width), max_bins)
+    with torch.cuda.device(scan.data.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), block.data_ptr(), hist.data_ptr(),
-                                             glcm.data_ptr(), ws.data_ptr(), stream), "mmnn_radiomics")
-    out = RadiomicsResult(block, hist, glcm, ws, (x, y, z), scan.affine, float(bin_width), max_bins)
-    if classes:
-        _enqueue_texture(out, desc, dev, stream, buffers, classes)
-    if glszm:
-        _enqueue_zones(out, desc, dev, stream, buffers)
-    if mesh:
-        _enqueue_mesh(out, desc, dev, stream, buffers)
+        for st, on in zip(STAGES, (True, classes, glszm, mesh)):
+            if on:
+                _enqueue_stage(out, st, desc, stream, buffers, scan.data, mask.data)
+                if st.flag is not None:
+                    setattr(out, st.flag, classes if st.flag == "classes" else True)
     return out
 
 
-def _enqueue_texture(out: RadiomicsResult, desc, dev, stream, buffers, classes) -> None:
-    (x, y, z), max_bins, block, ws = out.shape, out.max_bins, out.block, out.workspace
-    if buffers is not None and buffers.texture is not None:
-        tex, glrlm, gldm, ngn, ngs, ws2 = buffers.texture, buffers.glrlm, buffers.gldm, buffers.ngtdm_n, buffers.ngtdm_s, buffers.texture_workspace
+def _enqueue_stage(out: RadiomicsResult, st, desc, stream, buffers, scan, mask) -> None:
+    """Give `out` the buffers of stage `st`, those of `buffers` when it has them and new ones otherwise, and enqueue the stage."""
+    if buffers is not None and getattr(buffers, st.block) is not None:
+        for a in st.attrs:
+            setattr(out, a, getattr(buffers, a))
     else:
-        n2 = _lib.lib().mmnn_radiomics_texture_workspace_bytes(x, y, z, max_bins)
-        if n2 < 0:
-            raise ValueError("mmnn_radiomics_texture_workspace_bytes: " + _lib.last_error())
-        tex = torch.empty(_lib.RADIOMICS_TEXTURE_BYTES, dtype=torch.uint8, device=dev)
-        glrlm = torch.empty((_lib.RADIOMICS_DIRECTIONS, max_bins, max(x, y, z)), dtype=torch.int32, device=dev)
-        gldm = torch.empty((max_bins, _lib.RADIOMICS_NEIGHBOURS), dtype=torch.int32, device=dev)
-        ngn = torch.empty((max_bins, _lib.RADIOMICS_NEIGHBOURS), dtype=torch.int32, device=dev)
-        ngs = torch.empty((max_bins, _lib.RADIOMICS_NEIGHBOURS), dtype=torch.int64, device=dev)
-        ws2 = torch.empty(int(n2), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mmnn_radiomics_texture(ctypes.byref(desc), block.data_ptr(), ws.data_ptr(), tex.data_ptr(), glrlm.data_ptr(),
-                                                     gldm.data_ptr(), ngn.data_ptr(), ngs.data_ptr(), ws2.data_ptr(), stream),
-                   "mmnn_radiomics_texture")
-    out.texture, out.glrlm, out.gldm, out.ngtdm_n, out.ngtdm_s, out.texture_workspace, out.classes = tex, glrlm, gldm, ngn, ngs, ws2, classes
+        (x, y, z), dev = out.shape, scan.device
+        nbytes = _bytes_or_raise(st.symbol + "_workspace_bytes", x, y, z, out.max_bins)
+        setattr(out, st.block, torch.empty(st.nbytes, dtype=torch.uint8, device=dev))
+        for a, shape, dtype in st.tables:
+            setattr(out, a, torch.empty(shape(x, y, z, out.max_bins), dtype=dtype, device=dev))
+        setattr(out, st.workspace, torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    if st.name == "mesh":
+        out.linear = _linear_of(out.affine)
+    enqueue(out, st.name, desc, stream, scan.data_ptr(), mask.data_ptr())
 
 
-def _enqueue_zones(out: RadiomicsResult, desc, dev, stream, buffers) -> None:
-    (x, y, z), max_bins = out.shape, out.max_bins
-    if buffers is not None and buffers.zones is not None:
-        zones, labels, sizes, levels, ws3 = buffers.zones, buffers.labels, buffers.sizes, buffers.levels, buffers.zones_workspace
-    else:
-        n3 = _lib.lib().mmnn_radiomics_zones_workspace_bytes(x, y, z, max_bins)
-        if n3 < 0:
-            raise ValueError("mmnn_radiomics_zones_workspace_bytes: " + _lib.last_error())
-        zones = torch.empty(_lib.RADIOMICS_ZONES_BYTES, dtype=torch.uint8, device=dev)
-        labels = torch.empty(x * y * z, dtype=torch.int32, device=dev)
-        sizes = torch.empty(x * y * z, dtype=torch.int32, device=dev)
-        levels = torch.empty(max_bins, dtype=torch.int32, device=dev)
-        ws3 = torch.empty(int(n3), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mmnn_radiomics_zones(ctypes.byref(desc), out.block.data_ptr(), out.workspace.data_ptr(), zones.data_ptr(),
-                                                   labels.data_ptr(), sizes.data_ptr(), levels.data_ptr(), ws3.data_ptr(), stream),
-                   "mmnn_radiomics_zones")
-    out.zones, out.labels, out.sizes, out.levels, out.zones_workspace, out.glszm = zones, labels, sizes, levels, ws3, True
+def enqueue(r: RadiomicsResult, stage: str, desc, stream, scan: Optional[int] = None, mask: Optional[int] = None) -> None:
+    """Enqueue the call of one stage of STAGES (`first`, `texture`, `zones`, `mesh`) into the buffers `r` already has, under the
+    descriptor `desc` on `stream` (the current device's): nothing is prepared or allocated.  `scan` / `mask`: the device addresses the
+    first call reads; the follow-on calls read `r.block` and `r.workspace`, the mesh one `r.linear` too."""
+    st = _STAGE[stage]
+    lead = (scan, mask) if st.flag is None else (r.block.data_ptr(), r.workspace.data_ptr()) + st.extra(r)
+    _lib.check(getattr(_lib.lib(), st.symbol)(ctypes.byref(desc), *lead, *(getattr(r, a).data_ptr() for a in st.attrs), stream), st.symbol)
 
 
 def _linear_of(affine) -> np.ndarray:
     """The 3 x 3 linear part of a voxel index -> mm matrix (4 x 4, or 3 x 3 as it is); the identity for None."""
     return np.eye(3) if affine is None else np.ascontiguousarray(np.asarray(affine, dtype=np.float64)[:3, :3])
-
-
-def _enqueue_mesh(out: RadiomicsResult, desc, dev, stream, buffers) -> None:
-    x, y, z = out.shape
-    if buffers is not None and buffers.mesh is not None:
-        block, cfg, ws4 = buffers.mesh, buffers.mesh_cfg, buffers.mesh_workspace
-    else:
-        n4 = _lib.lib().mmnn_radiomics_mesh_workspace_bytes(x, y, z, out.max_bins)
-        if n4 < 0:
-            raise ValueError("mmnn_radiomics_mesh_workspace_bytes: " + _lib.last_error())
-        block = torch.empty(_lib.RADIOMICS_MESH_BYTES, dtype=torch.uint8, device=dev)
-        cfg = torch.empty(_lib.RADIOMICS_MESH_CONFIGS, dtype=torch.int64, device=dev)
-        ws4 = torch.empty(int(n4), dtype=torch.uint8, device=dev)
-    linear = _linear_of(out.affine)
-    flat = (ctypes.c_double * 9)(*linear.ravel().tolist())
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mmnn_radiomics_mesh(ctypes.byref(desc), out.block.data_ptr(), out.workspace.data_ptr(), flat, block.data_ptr(),
-                                                  cfg.data_ptr(), ws4.data_ptr(), stream), "mmnn_radiomics_mesh")
-    out.mesh, out.mesh_cfg, out.mesh_workspace, out.linear, out.mesh_shape = block, cfg, ws4, linear, True
 
 
 def mesh_table() -> dict:
@@ -503,6 +459,71 @@ def shape_features(n: int, moments, linear) -> Dict[str, float]:
     return out
 
 
+@dataclass(frozen=True)
+class Stage:
+    """One call of an extraction, stated once.  `symbol`: the C function (its workspace size is `<symbol>_workspace_bytes`); `block`: the
+    RadiomicsResult attribute of its result block of `nbytes` bytes; `tables`: its caller-owned tables as (attribute, shape from x, y, z,
+    max_bins, dtype); `workspace`: the attribute of its workspace; `flag`: the attribute in which a result records that the call ran (None:
+    the first call, which always runs); `unpack`: the block's bytes -> its fields; `names(image, classes)`: its columns in order, and
+    `values(fields, classes, linear, image)` their values; `extra(result)`: arguments between the first call's workspace and the block."""
+    name: str
+    symbol: str
+    block: str
+    nbytes: int
+    tables: tuple
+    workspace: str
+    flag: Optional[str]
+    unpack: object
+    names: object
+    values: object
+    extra: object = lambda r: ()
+
+    @property
+    def attrs(self) -> tuple:
+        """The attributes of the buffers in the order of the C arguments: block, tables, workspace."""
+        return (self.block,) + tuple(t[0] for t in self.tables) + (self.workspace,)
+
+
+def _first_names(image, classes=()):
+    return (tuple(f"{image}_firstorder_{n}" for n in FIRSTORDER) + (tuple(f"original_shape_{n}" for n in SHAPE) if image == "original" else ())
+            + tuple(f"{image}_glcm_{n}" for n in GLCM))
+
+
+def _first_values(f, classes, linear, image):
+    fo = [float(v) for v in f["firstorder"]]
+    shape = shape_features(f["n"], f["moments"], linear) if image == "original" else None
+    return (fo + [fo[DEVICE_FIRSTORDER.index("Energy")] * abs(float(np.linalg.det(linear)))] + ([shape[n] for n in SHAPE] if shape else [])
+            + [float(v) for v in f["glcm"]])
+
+
+_NBHD = lambda x, y, z, mb: (mb, _lib.RADIOMICS_NEIGHBOURS)
+_VOXELS = lambda x, y, z, mb: (x * y * z,)
+STAGES = (
+    Stage("first", "mmnn_radiomics", "block", _lib.RADIOMICS_RESULT_BYTES,
+          (("hist", lambda x, y, z, mb: (mb,), torch.int32), ("glcm", lambda x, y, z, mb: (_lib.RADIOMICS_DIRECTIONS, mb, mb), torch.int32)),
+          "workspace", None, unpack_block, _first_names, _first_values),
+    Stage("texture", "mmnn_radiomics_texture", "texture", _lib.RADIOMICS_TEXTURE_BYTES,
+          (("glrlm", lambda x, y, z, mb: (_lib.RADIOMICS_DIRECTIONS, mb, max(x, y, z)), torch.int32), ("gldm", _NBHD, torch.int32),
+           ("ngtdm_n", _NBHD, torch.int32), ("ngtdm_s", _NBHD, torch.int64)),
+          "texture_workspace", "classes", unpack_texture,
+          lambda image, classes: tuple(f"{image}_{c}_{n}" for c in classes for n in _TEXTURE[c]),
+          lambda f, classes, linear, image: [float(v) for c in classes for v in f[c]]),
+    Stage("zones", "mmnn_radiomics_zones", "zones", _lib.RADIOMICS_ZONES_BYTES,
+          (("labels", _VOXELS, torch.int32), ("sizes", _VOXELS, torch.int32), ("levels", lambda x, y, z, mb: (mb,), torch.int32)),
+          "zones_workspace", "glszm", unpack_zones,
+          lambda image, classes: tuple(f"{image}_glszm_{n}" for n in GLSZM),
+          lambda f, classes, linear, image: [float(v) for v in f["glszm"]]),
+    Stage("mesh", "mmnn_radiomics_mesh", "mesh", _lib.RADIOMICS_MESH_BYTES,
+          (("mesh_cfg", lambda x, y, z, mb: (_lib.RADIOMICS_MESH_CONFIGS,), torch.int64),),
+          "mesh_workspace", "mesh_shape", unpack_mesh,
+          lambda image, classes: tuple(f"original_shape_{n}" for n in MESH_SHAPE),
+          lambda f, classes, linear, image: [mesh_features(f, linear)[n] for n in MESH_SHAPE],
+          lambda r: ((ctypes.c_double * 9)(*r.linear.ravel().tolist()),)),
+)
+_STAGE = {st.name: st for st in STAGES}
+FEATURE_NAMES = _first_names("original")
+
+
 def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=(), zones: Optional[dict] = None,
                 mesh: Optional[dict] = None, image: str = "original") -> Dict[str, float]:
     """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block; with `zones`, the unpacked
@@ -526,51 +547,39 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
         linear = np.eye(3)
     else:
         linear = np.asarray(affine, dtype=np.float64)[:3, :3]
-    out = {}
-    fo = dict(zip(DEVICE_FIRSTORDER, (float(v) for v in fields["firstorder"])))
-    fo["TotalEnergy"] = fo["Energy"] * abs(float(np.linalg.det(linear)))
-    for n in FIRSTORDER:
-        out[f"{image}_firstorder_{n}"] = fo[n]
-    if image == "original":
-        shape = shape_features(fields["n"], fields["moments"], linear)
-        for n in SHAPE:
-            out[f"original_shape_{n}"] = shape[n]
-    for n, v in zip(GLCM, fields["glcm"]):
-        out[f"{image}_glcm_{n}"] = float(v)
-    for c in texture_classes(classes):
-        for n, v in zip(_TEXTURE[c], texture[c]):
-            out[f"{image}_{c}_{n}"] = float(v)
-    if zones is not None:
-        for n, v in zip(GLSZM, zones["glszm"]):
-            out[f"{image}_glszm_{n}"] = float(v)
-    if mesh is not None:
-        for n, v in mesh_features(mesh, linear).items():
-            out[f"original_shape_{n}"] = v
+    classes, out = texture_classes(classes), {}
+    for st, f in zip(STAGES, (fields, texture, zones, mesh)):
+        if f is not None:
+            out.update(zip(st.names(image, classes), st.values(f, classes, linear, image)))
     return out
+
+
+def _stage_blocks(r: RadiomicsResult):
+    """(the RadiomicsResult of an image, stage, that stage's block) in the order of the stacked read-back: per image -- `r`, then its
+    filtered ones, sigma ascending -- the first call's block, then those of the follow-on calls that ran."""
+    for q in (r,) + tuple(sub for _, sub in r.log):
+        for st in STAGES:
+            if st.flag is None or getattr(q, st.flag):
+                yield q, st, getattr(q, st.block)
 
 
 def _stacked(r: RadiomicsResult) -> torch.Tensor:
     """The result blocks of one extraction behind each other: what one read-back brings to the host."""
-    parts = []
-    for q in (r,) + tuple(sub for _, sub in r.log):
-        parts += [q.block] + ([q.texture] if q.classes else []) + ([q.zones] if q.glszm else []) + ([q.mesh] if q.mesh_shape else [])
+    parts = [block for _, _, block in _stage_blocks(r)]
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
 def _features_of_stacked(raw: np.ndarray, r: RadiomicsResult, affine, what: str) -> Dict[str, float]:
-    nb = _lib.RADIOMICS_RESULT_BYTES
-    nt = nb + (_lib.RADIOMICS_TEXTURE_BYTES if r.classes else 0)
-    nz = nt + (_lib.RADIOMICS_ZONES_BYTES if r.glszm else 0)
     if r.mesh_shape and not np.array_equal(_linear_of(affine), r.linear):
         raise ValueError(f"{what}: the mesh-based shape features were enqueued under the linear part {r.linear.tolist()}; `finish` cannot "
                          f"apply another one ({_linear_of(affine).tolist()}): extract with the affine that is meant")
-    nm = nz + (_lib.RADIOMICS_MESH_BYTES if r.mesh_shape else 0)
-    out = features_of(unpack_block(raw[:nb]), affine, what, unpack_texture(raw[nb:nt]) if r.classes else None, r.classes,
-                      unpack_zones(raw[nt:nz]) if r.glszm else None, unpack_mesh(raw[nz:nm]) if r.mesh_shape else None, r.image)
-    for _, sub in r.log:                                                                # the filtered images' blocks follow, sigma ascending
-        raw = raw[nm:]
-        nm = nb + (_lib.RADIOMICS_TEXTURE_BYTES if sub.classes else 0) + (_lib.RADIOMICS_ZONES_BYTES if sub.glszm else 0)
-        out.update(_features_of_stacked(raw[:nm], sub, affine, what))
+    unpacked, off = {}, 0
+    for q, st, _ in _stage_blocks(r):
+        unpacked.setdefault(id(q), (q, {}))[1][st.name] = st.unpack(raw[off:off + st.nbytes])
+        off += st.nbytes
+    out = {}
+    for q, f in unpacked.values():
+        out.update(features_of(f.pop("first"), affine, what, classes=q.classes, image=q.image, **f))
     return out
 
 
@@ -627,6 +636,21 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
     return rows
 
 
+def extract_modalities(datasets, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
+                       mask_threshold: Optional[float] = None, **switches) -> List[dict]:
+    """`extract_tree` (with its `switches`) over one image dataset per modality: the columns of two modalities are prefixed `t1_` /
+    `t2_` and their rows merged on `MRN`, in the first one's order, keeping the patients both have."""
+    rows = None
+    for ds, px in zip(datasets, ("t1_", "t2_") if len(datasets) == 2 else ("",)):
+        part = extract_tree(ds, device, None, bin_width, max_bins, mask_threshold, prefixes=(px,), **switches)
+        if rows is None:
+            rows = part
+        else:
+            by = {r["MRN"]: r for r in part}
+            rows = [dict(r, **{k: v for k, v in by[r["MRN"]].items() if k != "MRN"}) for r in rows if r["MRN"] in by]
+    return rows
+
+
 def write_csv(path, rows: List[dict]) -> None:
     cols = list(rows[0].keys()) if rows else ["MRN"] + list(FEATURE_NAMES)
     with open(path, "w", newline="") as f:
@@ -679,16 +703,9 @@ def main(argv=None):
         raise SystemExit(f"no modality directory under {a.image_loc}")
     sets = [ImageDataset(d, a.key_loc, str(data.get("mask_resample", "auto")).lower(), format=data.get("format"), mask_roi=data.get("mask_roi"))
             for d in dirs]
-    rows = None
-    for ds, px in zip(sets, ("t1_", "t2_") if len(sets) == 2 else ("",)):
-        part = extract_tree(ds, a.device, None, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
-                            data.get("mask_threshold"), prefixes=(px,), classes=classes, glszm=glszm, mesh=mesh, log_sigma=log["sigma"],
-                            log_bin_width=log["bin_width"])
-        if rows is None:
-            rows = part
-        else:
-            by = {r["MRN"]: r for r in part}
-            rows = [dict(r, **{k: v for k, v in by[r["MRN"]].items() if k != "MRN"}) for r in rows if r["MRN"] in by]
+    rows = extract_modalities(sets, a.device, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
+                              data.get("mask_threshold"), classes=classes, glszm=glszm, mesh=mesh, log_sigma=log["sigma"],
+                              log_bin_width=log["bin_width"])
     write_csv(a.out, rows)
     print(f"{len(rows)} patients, {len(rows[0]) - 1 if rows else 0} features -> {a.out}")
 

@@ -267,3 +267,52 @@ def test_main_refusals(tmp_path, monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     with pytest.raises(SystemExit, match=r"single process.*--rad_loc"):
         main.main(["--radiomics", "--survival", "--image_loc", str(tmp_path), "--data_loc", "c.csv", "--key_loc", "k.csv"])
+
+
+def test_stacked_layout_of_every_switch_combination():
+    """The one read-back's layout, from the module docstring and the `_lib.RADIOMICS_*` sizes: per image (the original, then each LoG
+    scale ascending) the result block, then the texture block if any class was asked for, the size-zone block, the mesh block (original
+    only).  Word k of the buffer holds the double k, so a device-computed column must hold the index of the word it is read from."""
+    from itertools import combinations, product
+    from mmnn_sts_amd import _lib
+    L = _lib
+    first = L.RADIOMICS_RESULT_INT64 + len(radiomics.ORDER_RANKS)
+    assert (first + L.RADIOMICS_FIRSTORDER + L.RADIOMICS_GLCM) * 8 == L.RADIOMICS_RESULT_BYTES
+    tex_off = {"glrlm": 0, "gldm": L.RADIOMICS_GLRLM, "ngtdm": L.RADIOMICS_GLRLM + L.RADIOMICS_GLDM}
+    tex_names = {"glrlm": radiomics.GLRLM, "gldm": radiomics.GLDM, "ngtdm": radiomics.NGTDM}
+    subsets = [c for k in range(4) for c in combinations(radiomics.TEXTURE_CLASSES, k)]
+    combos = list(product(subsets, (False, True), (False, True), ((), (1.0,), (1.0, 3.0))))
+    assert len(combos) == 96
+    for classes, glszm, mesh, sigmas in combos:
+        expect, words, starts = {}, 0, []
+        for image in ("original",) + tuple(radiomics.log_image_type(s) for s in sigmas):
+            starts.append(words)
+            for j, n in enumerate(radiomics.DEVICE_FIRSTORDER):
+                expect[f"{image}_firstorder_{n}"] = words + first + j
+            for j, n in enumerate(radiomics.GLCM):
+                expect[f"{image}_glcm_{n}"] = words + first + L.RADIOMICS_FIRSTORDER + j
+            words += L.RADIOMICS_RESULT_BYTES // 8
+            if classes:
+                for c in classes:
+                    for j, n in enumerate(tex_names[c]):
+                        expect[f"{image}_{c}_{n}"] = words + tex_off[c] + j
+                words += L.RADIOMICS_TEXTURE_BYTES // 8
+            if glszm:
+                for j, n in enumerate(radiomics.GLSZM):
+                    expect[f"{image}_glszm_{n}"] = words + (L.RADIOMICS_ZONES_BYTES // 8 - L.RADIOMICS_GLSZM) + j
+                words += L.RADIOMICS_ZONES_BYTES // 8
+            if mesh and image == "original":
+                words += L.RADIOMICS_MESH_BYTES // 8
+        buf = np.arange(words, dtype=np.float64)
+        for s in starts:                  # n = 8; lo, hi; the index sums of the block (0..1)^3; n_bins; the three flags clear
+            buf[s:s + L.RADIOMICS_RESULT_INT64].view(np.int64)[:] = [8, 0, 0, 0, 1, 1, 1, 4, 4, 4, 4, 4, 4, 2, 2, 2, 2, 0, 0, 0]
+
+        def result(image, with_mesh):
+            return radiomics.RadiomicsResult(None, None, None, None, (2, 2, 2), None, 25.0, 256, classes=classes, glszm=glszm,
+                                             mesh_shape=with_mesh, linear=np.eye(3) if with_mesh else None, image=image)
+        r = result("original", mesh)
+        r.log = tuple((s, result(radiomics.log_image_type(s), False)) for s in sigmas)
+        got = radiomics._features_of_stacked(buf.view(np.uint8), r, None, "layout")
+        assert tuple(got) == radiomics.feature_names(classes, glszm, mesh, sigmas), (classes, glszm, mesh, sigmas)
+        assert {k: got[k] for k in expect} == {k: float(v) for k, v in expect.items()}, (classes, glszm, mesh, sigmas)
+        assert len(got) - len(expect) == (1 + len(sigmas)) + len(radiomics.SHAPE) + (len(radiomics.MESH_SHAPE) if mesh else 0)

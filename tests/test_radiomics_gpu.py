@@ -8,8 +8,6 @@ stay within MEASURED against the mpmath evaluation for every case, so no case go
 import ctypes
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,12 +17,9 @@ from mmnn_sts_amd import _lib, radiomics
 from mmnn_sts_amd.data import ingest, synth_dicom, synth_nifti
 from tests import _radiomics_ref as R
 from tests._radiomics_cases import BOUND, CASES, MEASURED
+from tests._radiomics_harness import DEV, ROOT, cut, first_call, mlp_at_width, process, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-GUARD = 256
-PATTERN = 0xA5
 _REF = {}
 
 
@@ -39,45 +34,14 @@ def _ref(name):
     return _REF[name]
 
 
-def _device_bytes(arr, lead):
-    """(holder, pointer): the array's bytes, x fastest, `lead` bytes past a 256-byte boundary."""
-    host = ingest._host_bytes(np.ascontiguousarray(arr))
-    buf = torch.zeros(lead + host.size + 64, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
-    buf[lead:lead + host.size] = torch.from_numpy(host.copy()).to(DEV)
-    return buf, buf.data_ptr() + lead
-
-
 def _run(name):
     """One call through the C-ABI itself: result block, hist and glcm sit between guard bytes inside one buffer; returns
     (fields, hist, glcm) on the host."""
-    c = CASES[name]
-    x, y, z = c["scan"].shape
-    mb = c["max_bins"]
-    sizes = [_lib.RADIOMICS_RESULT_BYTES, mb * 4, 13 * mb * mb * 4]
-    offs, off = [], GUARD
-    for s in sizes:
-        offs.append(off)
-        off += (s + GUARD + 255) // 256 * 256
-    buf = torch.full((off,), PATTERN, dtype=torch.uint8, device=DEV)
-    sbuf, sp = _device_bytes(c["scan"], c["scan_lead"])
-    mbuf, mp = _device_bytes(c["mask"], c["mask_lead"])
-    ws = torch.full((radiomics.workspace_bytes(x, y, z, mb),), 0xFF, dtype=torch.uint8, device=DEV)
-    desc = _lib.RadiomicsDesc(x, y, z, ingest.TYPE_CODES[c["scan"].dtype], ingest.TYPE_CODES[c["mask"].dtype], *c["scan_scale"], *c["mask_scale"],
-                              c["bin_width"], mb)
-    p = buf.data_ptr()
-    _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), sp, mp, p + offs[0], p + offs[1], p + offs[2], ws.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream), "mmnn_radiomics")
+    mb = CASES[name]["max_bins"]
+    _, _, buf, offs, sizes = first_call(CASES[name], guard=True)
     torch.cuda.synchronize()
-    b = buf.cpu().numpy()
-    keep = np.ones(off, dtype=bool)
-    for o, s in zip(offs, sizes):
-        keep[o:o + s] = False
-    assert (b[keep] == PATTERN).all(), f"{name}: bytes outside result / hist / glcm were written"
-    fields = radiomics.unpack_block(b[offs[0]:offs[0] + sizes[0]])
-    hist = b[offs[1]:offs[1] + sizes[1]].view(np.uint32).astype(np.int64)
-    glcm = b[offs[2]:offs[2] + sizes[2]].view(np.uint32).astype(np.int64).reshape(13, mb, mb)
-    return fields, hist, glcm, b[offs[0]:offs[0] + sizes[0]].copy()
+    block, hist, glcm = cut(buf, offs, sizes, f"{name}: bytes outside result / hist / glcm were written")
+    return radiomics.unpack_block(block), hist.view(np.uint32).astype(np.int64), glcm.view(np.uint32).astype(np.int64).reshape(13, mb, mb), block
 
 
 def _same_bits(a, b):
@@ -161,39 +125,10 @@ def test_refusals():
 MLP_STREAM = {47: 0, 94: 0, 126: 0}
 
 
-def mlp_case(width, n=4):
-    from oracle import restatement as OR
-    from tests._util import synth_sd
-    from tests import test_tail_ops_gpu as T
-    sd = synth_sd(OR.mlp_schema(width, 2, 12), f"radmlp{width}.")
-    return sd, T._u(f"rad/mlp/x/{width}/{MLP_STREAM[width]}", (n, width)), T._u(f"rad/mlp/cot/{width}", (n, 12))
-
-
 @pytest.mark.parametrize("width", [47, 94, 126])
 def test_mlp_at_radiomic_width_vs_fp64(width):
-    """MLP(width) forward and backward at N = 4, training mode, against the fp64 torch restatement (oracle.restatement.mlp_features for the
-    features; its layer-by-layer twin in tests/test_tail_ops_gpu.py for the gradients), at the bar that file holds width 32 to."""
-    from mmnn_sts_amd.models.mlp import MLP
-    from oracle import restatement as OR
-    from tests import test_tail_ops_gpu as T
-    sd, x, cot = mlp_case(width)
-    ref, leaves, pres = T.mlp_ref(sd, x, True)
-    T._assert_off_branch(pres, f"mlp width {width}")
-    assert torch.allclose(ref.detach(), OR.mlp_features({k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}, x.double(), True, 0.0).detach(),
-                          rtol=1e-12, atol=1e-14)
-    (ref * cot.double()).sum().backward()
-    m = MLP(width, 2, 12, dropout_prob=0.0)
-    m.load_state_dict(sd, strict=True)
-    m = m.to(DEV).train()
-    xg = x.to(DEV).requires_grad_(True)
-    f = m.features(m.backbone(xg))
-    (f * cot.to(DEV)).sum().backward()
-    params = dict(m.named_parameters())
-    errs = {"features": T.rel_err(f.detach().cpu().numpy(), ref.detach().numpy()), "dx": T.rel_err(xg.grad.cpu().numpy(), leaves["x"].grad.numpy())}
-    for k in T.MLP_PARAM_KEYS:
-        errs[k] = T.mlp_grad_err(k, params[k].grad, leaves, True)
-    assert len(errs) == 26
-    T._check(errs, T.BAR)
+    """tests/_radiomics_harness.py: mlp_at_width, at the three widths of the default table."""
+    mlp_at_width(width, MLP_STREAM[width])
 
 
 # ---- extract through every mask route ------------------------------------------------------------------------------------------------------
@@ -270,28 +205,10 @@ def test_finish_raises_with_the_cause():
 
 
 # ---- the command lines: one fresh process each -----------------------------------------------------------------------------------------------
-def _process(argv, cwd):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, *argv], cwd=str(cwd), env=env, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def _tiny_config(tmp_path, modality="t1t2", in_channels=2):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": modality, "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": in_channels, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    path = tmp_path / "config.yaml"
-    path.write_text(yaml.safe_dump(cfg))
-    return str(path)
-
-
 def test_cli_extraction_tool_writes_the_rows_of_finish(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=4, seed=11)
     out = tmp_path / "radiomics.csv"
-    _process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--out", str(out)], tmp_path)
+    process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--out", str(out)], tmp_path)
     cols, rows = radiomics.read_csv(out)
     assert cols == ["MRN"] + [p + n for p in ("t1_", "t2_") for n in radiomics.FEATURE_NAMES] and len(rows) == 4
     from mmnn_sts_amd.data.ImageDatasets import ImageDataset
@@ -306,19 +223,19 @@ def test_cli_extraction_tool_writes_the_rows_of_finish(tmp_path):
 
 def test_cli_trains_on_extracted_features_then_infers_with_images(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=12, val_fraction=0.34)
-    loc = ["--config", _tiny_config(tmp_path), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    loc = ["--config", tiny_config(tmp_path), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
     out = tmp_path / "run"
     out.mkdir()
     main = os.path.join(ROOT, "main.py")
-    log = _process([main, "--output_path", str(out), "--radiomics", "--survival", "--image_loc", tree["image_loc"], "--epochs", "1", *loc], out)
+    log = process([main, "--output_path", str(out), "--radiomics", "--survival", "--image_loc", tree["image_loc"], "--epochs", "1", *loc], out)
     assert "epoch 1/1" in log
     for name in ("radiomics_features.csv", "radiomics_scaler.csv", "best_surv_model.pth"):
         assert (out / name).exists(), name
     out2 = tmp_path / "run2"
     out2.mkdir()
     rad = ["--rad_loc", str(out / "radiomics_features.csv"), "--image_loc", tree["image_loc"]]
-    _process([main, "--output_path", str(out2), "--radiomics", "--images", "--survival", "--epochs", "1", *rad, *loc], out2)
-    log = _process([main, "--output_path", str(out2), "--inference", "--radiomics", "--images", "--survival", "--weights",
+    process([main, "--output_path", str(out2), "--radiomics", "--images", "--survival", "--epochs", "1", *rad, *loc], out2)
+    log = process([main, "--output_path", str(out2), "--inference", "--radiomics", "--images", "--survival", "--weights",
                     str(out2 / "best_surv_model.pth"), *rad, *loc], out2)
     assert "All C-indexes" in log

@@ -8,8 +8,6 @@ their exactness rules, unchanged."""
 import ctypes
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -23,25 +21,14 @@ from tests import _radiomics_ref as R
 from tests import _radiomics_texture_ref as T
 from tests import _radiomics_zones_ref as Z
 from tests._radiomics_cases import BOUND, _case
+from tests._radiomics_harness import (DEV, GUARD, PATTERN, ROOT, device_bytes, leave_the_dropout_stream_where_it_was, mlp_at_width,  # noqa: F401
+                                      process, tiny_config)
 from tests._radiomics_log_cases import FEATURE_CASES, FILTER_CASES, MLP_STREAM, TILE_COLUMNS, TILE_LINE, TILE_ROWS, TILE_X, affine_of
 from tests._radiomics_texture_cases import BOUND as TEXTURE_BOUND
 from tests._radiomics_zones_cases import BOUND as ZONES_BOUND
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-GUARD = 256
-PATTERN = 0xA5
 _REF = {}
-
-
-@pytest.fixture(autouse=True)
-def _leave_the_dropout_stream_where_it_was():
-    """As in tests/test_radiomics_texture_gpu.py: the fused MLP draws from the process's one seed counter; put it back."""
-    from mmnn_sts_amd import ops
-    before = ops._seed_counter[0]
-    yield
-    ops._seed_counter[0] = before
 
 
 def _ref(name):
@@ -54,22 +41,13 @@ def _ref(name):
     return _REF[name]
 
 
-def _device_bytes(arr, lead):
-    """(holder, pointer): the array's bytes, x fastest, `lead` bytes past a 256-byte boundary."""
-    host = ingest._host_bytes(np.ascontiguousarray(arr))
-    buf = torch.zeros(lead + host.size + 64, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
-    buf[lead:lead + host.size] = torch.from_numpy(host.copy()).to(DEV)
-    return buf, buf.data_ptr() + lead
-
-
 def _call(scan, radius, taps, weight, scale=(1.0, 0.0), lead=0, expect=0, null=None, scan_type=None):
     """One call through the C-ABI itself: `out` sits between guard bytes in a buffer filled with a pattern, the workspace starts from
     0xFF.  Returns (status, out as float32 (x, y, z) or None when nothing may have been written)."""
     x, y, z = scan.shape
     n = x * y * z
     buf = torch.full((GUARD + (n * 4 + 255) // 256 * 256 + GUARD,), PATTERN, dtype=torch.uint8, device=DEV)
-    sbuf, sp = _device_bytes(scan, lead)
+    sbuf, sp = device_bytes(scan, lead)
     nbytes = _lib.lib().mmnn_log_filter_workspace_bytes(x, y, z)
     assert nbytes >= 4 * 8 * n
     ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=DEV)
@@ -266,56 +244,16 @@ def test_a_flag_on_a_filtered_image_names_the_image_type():
 def test_mlp_at_log_width_vs_fp64(width):
     """MLP(width) forward and backward at N = 4, training mode, against the fp64 torch restatement, at the bar tests/test_tail_ops_gpu.py
     holds width 32 to: 47 + 41 columns of one modality with one scale, 176 of two."""
-    from mmnn_sts_amd.models.mlp import MLP
-    from oracle import restatement as OR
-    from tests import test_tail_ops_gpu as TT
-    from tests._util import synth_sd
-    sd = synth_sd(OR.mlp_schema(width, 2, 12), f"radmlp{width}.")
-    x, cot = TT._u(f"rad/mlp/x/{width}/{MLP_STREAM[width]}", (4, width)), TT._u(f"rad/mlp/cot/{width}", (4, 12))
-    ref, leaves, pres = TT.mlp_ref(sd, x, True)
-    TT._assert_off_branch(pres, f"mlp width {width}")
-    assert torch.allclose(ref.detach(), OR.mlp_features({k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}, x.double(), True, 0.0).detach(),
-                          rtol=1e-12, atol=1e-14)
-    (ref * cot.double()).sum().backward()
-    m = MLP(width, 2, 12, dropout_prob=0.0)
-    m.load_state_dict(sd, strict=True)
-    m = m.to(DEV).train()
-    xg = x.to(DEV).requires_grad_(True)
-    f = m.features(m.backbone(xg))
-    (f * cot.to(DEV)).sum().backward()
-    params = dict(m.named_parameters())
-    errs = {"features": TT.rel_err(f.detach().cpu().numpy(), ref.detach().numpy()), "dx": TT.rel_err(xg.grad.cpu().numpy(), leaves["x"].grad.numpy())}
-    for k in TT.MLP_PARAM_KEYS:
-        errs[k] = TT.mlp_grad_err(k, params[k].grad, leaves, True)
-    assert len(errs) == 26
-    TT._check(errs, TT.BAR)
+    mlp_at_width(width, MLP_STREAM[width])
 
 
 # ---- the command lines: one fresh process each -----------------------------------------------------------------------------------------------
-def _process(argv, cwd):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, *argv], cwd=str(cwd), env=env, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def _tiny_config(tmp_path):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    path = tmp_path / "config.yaml"
-    path.write_text(yaml.safe_dump(cfg))
-    return str(path)
-
-
 def test_cli_extraction_tool_with_log_sigma_writes_the_rows_of_finish(tmp_path):
     from mmnn_sts_amd.data.ImageDatasets import ImageDataset
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=3, seed=11)
     names = radiomics.feature_names(log_sigma=(1, 3))
     out = tmp_path / "radiomics.csv"
-    log = _process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--log_sigma", "1,3", "--out", str(out)],
+    log = process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--log_sigma", "1,3", "--out", str(out)],
                    tmp_path)
     assert "258 features" in log
     cols, rows = radiomics.read_csv(out)
@@ -333,18 +271,18 @@ def test_cli_extraction_tool_with_log_sigma_writes_the_rows_of_finish(tmp_path):
 
 def test_cli_trains_on_the_log_table_then_infers_with_the_saved_scaler(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=12, val_fraction=0.34)
-    loc = ["--config", _tiny_config(tmp_path), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    loc = ["--config", tiny_config(tmp_path), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
     out = tmp_path / "run"
     out.mkdir()
     main = os.path.join(ROOT, "main.py")
-    log = _process([main, "--output_path", str(out), "--radiomics", "--survival", "--image_loc", tree["image_loc"], "--log_sigma", "1,3",
+    log = process([main, "--output_path", str(out), "--radiomics", "--survival", "--image_loc", tree["image_loc"], "--log_sigma", "1,3",
                     "--epochs", "1", *loc], out)
     assert "epoch 1/1" in log
     for name in ("radiomics_features.csv", "radiomics_scaler.csv", "best_surv_model.pth"):
         assert (out / name).exists(), name
     cols, rows = radiomics.read_csv(out / "radiomics_features.csv")
     assert len(cols) == 1 + 2 * (47 + 2 * 41) and cols[-1] == "t2_log-sigma-3-0-mm-3D_glcm_SumSquares" and len(rows) == 6
-    log = _process([main, "--output_path", str(out), "--inference", "--radiomics", "--survival", "--weights", str(out / "best_surv_model.pth"),
+    log = process([main, "--output_path", str(out), "--inference", "--radiomics", "--survival", "--weights", str(out / "best_surv_model.pth"),
                     "--rad_loc", str(out / "radiomics_features.csv"), *loc], out)
     assert "All C-indexes" in log

@@ -8,8 +8,6 @@ import ctypes
 import dataclasses
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,24 +17,12 @@ from mmnn_sts_amd import _lib, radiomics
 from mmnn_sts_amd.data import ingest, synth_nifti
 from tests import _radiomics_mesh_ref as M
 from tests import _radiomics_ref as R
+from tests._radiomics_harness import (DEV, GOOD_DESC, GUARD, ROOT, cut, first_call, follow_call, leave_the_dropout_stream_where_it_was,  # noqa: F401
+                                      mlp_at_width, process, refusal_walk, tiny_config)
 from tests._radiomics_mesh_cases import BOUND, FLAGGED, MESH_CASES, MLP_STREAM, OBLIQUE, U
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-GUARD = 256
-PATTERN = 0xA5
 _REF = {}
-
-
-@pytest.fixture(autouse=True)
-def _leave_the_dropout_stream_where_it_was():
-    """As in tests/test_radiomics_texture_gpu.py: the fused MLP draws from the process-wide seed counter in every forward; tests later in
-    the suite were tuned on the masks they get, so the tests of this file put the counter back."""
-    from mmnn_sts_amd import ops
-    before = ops._seed_counter[0]
-    yield
-    ops._seed_counter[0] = before
 
 
 def _ref(name):
@@ -47,52 +33,18 @@ def _ref(name):
     return _REF[name]
 
 
-def _device_bytes(arr, lead):
-    """(holder, pointer): the array's bytes, x fastest, `lead` bytes past a 256-byte boundary."""
-    host = ingest._host_bytes(np.ascontiguousarray(arr))
-    buf = torch.zeros(lead + host.size + 64, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
-    buf[lead:lead + host.size] = torch.from_numpy(host.copy()).to(DEV)
-    return buf, buf.data_ptr() + lead
-
-
 def _run(name):
     """mmnn_radiomics, then mmnn_radiomics_mesh through the C-ABI itself: the result block and cfg sit between guard bytes inside one
     buffer filled with a pattern; both workspaces start from 0xFF.  Returns dict(block, cfg (bytes), fields (of the first call))."""
     c = MESH_CASES[name]
-    x, y, z = c["scan"].shape
-    mb = c["max_bins"]
     sizes = [_lib.RADIOMICS_MESH_BYTES, _lib.RADIOMICS_MESH_CONFIGS * 8]
-    offs, off = [], GUARD
-    for s in sizes:
-        offs.append(off)
-        off += (s + GUARD + 255) // 256 * 256
-    buf = torch.full((off,), PATTERN, dtype=torch.uint8, device=DEV)
-    first = torch.full((_lib.RADIOMICS_RESULT_BYTES + mb * 4 + 13 * mb * mb * 4,), PATTERN, dtype=torch.uint8, device=DEV)
-    sbuf, sp = _device_bytes(c["scan"], c["scan_lead"])
-    mbuf, mp = _device_bytes(c["mask"], c["mask_lead"])
-    ws = torch.full((radiomics.workspace_bytes(x, y, z, mb),), 0xFF, dtype=torch.uint8, device=DEV)
-    n4 = _lib.lib().mmnn_radiomics_mesh_workspace_bytes(x, y, z, mb)
-    assert n4 > 0
-    ws4 = torch.full((n4 + GUARD,), 0xFF, dtype=torch.uint8, device=DEV)
-    desc = _lib.RadiomicsDesc(x, y, z, ingest.TYPE_CODES[c["scan"].dtype], ingest.TYPE_CODES[c["mask"].dtype], *c["scan_scale"], *c["mask_scale"],
-                              c["bin_width"], mb)
-    lin = (ctypes.c_double * 9)(*(np.eye(3) if c["L"] is None else c["L"]).ravel().tolist())
-    stream = torch.cuda.current_stream().cuda_stream
-    f, p = first.data_ptr(), buf.data_ptr()
-    nb = _lib.RADIOMICS_RESULT_BYTES
-    _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), sp, mp, f, f + nb, f + nb + mb * 4, ws.data_ptr(), stream), "mmnn_radiomics")
-    _lib.check(_lib.lib().mmnn_radiomics_mesh(ctypes.byref(desc), f, ws.data_ptr(), lin, p + offs[0], p + offs[1], ws4.data_ptr(), stream),
-               "mmnn_radiomics_mesh")
+    r, desc, first, _, _ = first_call(c)
+    r.linear = np.eye(3) if c["L"] is None else c["L"]
+    buf, offs, ws4, n4 = follow_call(r, desc, "mesh", sizes, behind=GUARD)
     torch.cuda.synchronize()
-    b = buf.cpu().numpy()
-    keep = np.ones(off, dtype=bool)
-    for o, s in zip(offs, sizes):
-        keep[o:o + s] = False
-    assert (b[keep] == PATTERN).all(), f"{name}: bytes outside the mesh block and cfg were written"
+    block, cfg = cut(buf, offs, sizes, f"{name}: bytes outside the mesh block and cfg were written")
     assert (ws4[n4:] == 0xFF).all(), f"{name}: bytes behind the mesh workspace were written"
-    return {"block": b[offs[0]:offs[0] + sizes[0]].copy(), "cfg": b[offs[1]:offs[1] + sizes[1]].copy(),
-            "fields": radiomics.unpack_block(first[:nb].cpu().numpy())}
+    return {"block": block, "cfg": cfg, "fields": radiomics.unpack_block(first[:_lib.RADIOMICS_RESULT_BYTES].cpu().numpy())}
 
 
 @pytest.mark.parametrize("name", list(MESH_CASES))
@@ -123,21 +75,13 @@ def test_refusals_write_nothing():
     L = _lib.lib()
     t = torch.zeros(1 << 17, dtype=torch.uint8, device=DEV)
     p = t.data_ptr()
-    good = dict(x=4, y=4, z=4, scan_type=4, mask_type=2, scan_slope=1.0, scan_inter=0.0, mask_slope=1.0, mask_inter=0.0, bin_width=25.0, max_bins=16)
     lin = (ctypes.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
     ptrs = [p, p + 65536, p + 1024, p + 2048, p + 32768]          # result, ws, out, cfg, ws4
     call = lambda desc, q, linear=lin: L.mmnn_radiomics_mesh(desc, q[0], q[1], linear, q[2], q[3], q[4], None)
-    desc = ctypes.byref(_lib.RadiomicsDesc(**good))
-    for bad in (dict(bin_width=0.0), dict(scan_type=3), dict(x=0), dict(max_bins=0)):
-        assert call(ctypes.byref(_lib.RadiomicsDesc(**dict(good, **bad))), ptrs) == 1 and _lib.last_error(), bad
+    desc = ctypes.byref(_lib.RadiomicsDesc(**GOOD_DESC))
     assert call(desc, ptrs, None) == 1 and "null" in _lib.last_error()
     assert call(desc, ptrs, (ctypes.c_double * 9)(1, 0, 0, 0, float("nan"), 0, 0, 0, 1)) == 1 and "linear[4]" in _lib.last_error()
-    for k in range(len(ptrs)):
-        assert call(desc, [None if q == k else v for q, v in enumerate(ptrs)]) == 1 and "null" in _lib.last_error(), k
-    for k, step in ((0, 4), (1, 64), (2, 4), (3, 4), (4, 64)):
-        assert call(desc, [v + step if q == k else v for q, v in enumerate(ptrs)]) == 1 and "misaligned" in _lib.last_error(), k
-    torch.cuda.synchronize()
-    assert not t.any()                                     # refused before any launch: nothing was written
+    refusal_walk(call, ptrs, ((0, 4), (1, 64), (2, 4), (3, 4), (4, 64)), (dict(bin_width=0.0), dict(scan_type=3), dict(x=0), dict(max_bins=0)), t)
 
 
 def _on_grid(arr, affine, slope=1.0, inter=0.0):
@@ -206,49 +150,10 @@ def test_extract_passes_the_scans_linear_part():
 def test_mlp_at_mesh_width_vs_fp64(width):
     """MLP(width) forward and backward at N = 4, training mode, against the fp64 torch restatement, at the bar tests/test_tail_ops_gpu.py
     holds width 32 to: 106 columns of one modality with every switch on, 244 = 32 clinical columns + 2 x 106."""
-    from mmnn_sts_amd.models.mlp import MLP
-    from oracle import restatement as OR
-    from tests import test_tail_ops_gpu as TT
-    from tests._util import synth_sd
-    sd = synth_sd(OR.mlp_schema(width, 2, 12), f"radmlp{width}.")
-    x, cot = TT._u(f"rad/mlp/x/{width}/{MLP_STREAM[width]}", (4, width)), TT._u(f"rad/mlp/cot/{width}", (4, 12))
-    ref, leaves, pres = TT.mlp_ref(sd, x, True)
-    TT._assert_off_branch(pres, f"mlp width {width}")
-    (ref * cot.double()).sum().backward()
-    m = MLP(width, 2, 12, dropout_prob=0.0)
-    m.load_state_dict(sd, strict=True)
-    m = m.to(DEV).train()
-    xg = x.to(DEV).requires_grad_(True)
-    f = m.features(m.backbone(xg))
-    (f * cot.to(DEV)).sum().backward()
-    params = dict(m.named_parameters())
-    errs = {"features": TT.rel_err(f.detach().cpu().numpy(), ref.detach().numpy()), "dx": TT.rel_err(xg.grad.cpu().numpy(), leaves["x"].grad.numpy())}
-    for k in TT.MLP_PARAM_KEYS:
-        errs[k] = TT.mlp_grad_err(k, params[k].grad, leaves, True)
-    assert len(errs) == 26
-    TT._check(errs, TT.BAR)
+    mlp_at_width(width, MLP_STREAM[width])
 
 
 # ---- through the Python layer and the command lines ------------------------------------------------------------------------------------------
-def _process(argv, cwd):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, *argv], cwd=str(cwd), env=env, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def _tiny_config(tmp_path):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]},
-           "Radiomics": {"classes": list(radiomics.TEXTURE_CLASSES), "glszm": True, "mesh_shape": True}}
-    path = tmp_path / "config.yaml"
-    path.write_text(yaml.safe_dump(cfg))
-    return str(path)
-
-
 def test_extract_tree_and_the_extraction_tool_write_the_eight_columns_last(tmp_path):
     from mmnn_sts_amd.data.ImageDatasets import ImageDataset
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=3, seed=15)
@@ -275,7 +180,7 @@ def test_extract_tree_and_the_extraction_tool_write_the_eight_columns_last(tmp_p
     # the command line, every switch on
     wide = radiomics.feature_names("all", True, True)
     out2 = tmp_path / "radiomics.csv"
-    log = _process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--classes", "all", "--glszm",
+    log = process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--classes", "all", "--glszm",
                     "--mesh_shape", "--out", str(out2)], tmp_path)
     assert "212 features" in log
     cols, rows = radiomics.read_csv(out2)
@@ -285,16 +190,16 @@ def test_extract_tree_and_the_extraction_tool_write_the_eight_columns_last(tmp_p
 
 def test_cli_trains_the_fusion_model_with_mesh_shape_then_infers(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=16, val_fraction=0.34)
-    loc = ["--config", _tiny_config(tmp_path), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    loc = ["--config", tiny_config(tmp_path, {"classes": list(radiomics.TEXTURE_CLASSES), "glszm": True, "mesh_shape": True}), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"], "--image_loc", tree["image_loc"]]
     out = tmp_path / "run"
     out.mkdir()
     main = os.path.join(ROOT, "main.py")
-    log = _process([main, "--output_path", str(out), "--radiomics", "--images", "--survival", "--epochs", "1", *loc], out)
+    log = process([main, "--output_path", str(out), "--radiomics", "--images", "--survival", "--epochs", "1", *loc], out)
     assert "epoch 1/1" in log
     cols, rows = radiomics.read_csv(out / "radiomics_features.csv")
     assert len(cols) == 1 + 2 * 106 and cols[-1] == "t2_original_shape_Maximum2DDiameterRow" and len(rows) == 6
     assert cols[106] == "t1_original_shape_Maximum2DDiameterRow" and os.path.exists(out / "radiomics_scaler.csv")
-    log = _process([main, "--output_path", str(out), "--inference", "--radiomics", "--images", "--survival", "--weights",
+    log = process([main, "--output_path", str(out), "--inference", "--radiomics", "--images", "--survival", "--weights",
                     str(out / "best_surv_model.pth"), "--rad_loc", str(out / "radiomics_features.csv"), *loc], out)
     assert "All C-indexes" in log

@@ -4,38 +4,22 @@
 The four integer tables (run-length, dependence, NGTDM counts and sums) are compared with array equality.  The 35 fp64 features are held to
 tests/_radiomics_texture_cases.py: BOUND relative to the scale the restatement returns beside each value, against the mpmath evaluation of
 the same tables; NaN patterns and the NGTDM's special values (10^6, 0) are exact."""
-import ctypes
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from mmnn_sts_amd import _lib, radiomics
-from mmnn_sts_amd.data import ingest, synth_nifti
+from mmnn_sts_amd.data import synth_nifti
 from tests import _radiomics_texture_ref as T
+from tests._radiomics_harness import (DEV, ROOT, cut, first_call, follow_call, leave_the_dropout_stream_where_it_was, mlp_at_width,  # noqa: F401
+                                      process, refusal_walk, tiny_config)
 from tests._radiomics_texture_cases import BOUND, FLAGGED, MLP_STREAM, TEXTURE_CASES
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-GUARD = 256
-PATTERN = 0xA5
 _REF = {}
-
-
-@pytest.fixture(autouse=True)
-def _leave_the_dropout_stream_where_it_was():
-    """`ops.next_seed` numbers the dropout streams of the process with one counter, and the fused MLP draws from it in every forward,
-    dropout or not.  Tests later in the suite restate the masks of the seeds they draw and hold fp32 gradients to tight bars, so which
-    masks they get is part of what they were tuned on: the tests of this file put the counter back."""
-    from mmnn_sts_amd import ops
-    before = ops._seed_counter[0]
-    yield
-    ops._seed_counter[0] = before
 
 
 def _ref(name):
@@ -47,53 +31,21 @@ def _ref(name):
     return _REF[name]
 
 
-def _device_bytes(arr, lead):
-    """(holder, pointer): the array's bytes, x fastest, `lead` bytes past a 256-byte boundary."""
-    host = ingest._host_bytes(np.ascontiguousarray(arr))
-    buf = torch.zeros(lead + host.size + 64, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 256 == 0
-    buf[lead:lead + host.size] = torch.from_numpy(host.copy()).to(DEV)
-    return buf, buf.data_ptr() + lead
-
-
 def _run(name):
     """mmnn_radiomics, then mmnn_radiomics_texture through the C-ABI itself: the texture block and the four tables sit between guard
     bytes inside one buffer filled with a pattern.  Returns dict(block (bytes of the texture block), glrlm, gldm, ngtdm_n, ngtdm_s (int64),
     fields (of the first call), first (the first call's result block, hist and glcm, as bytes))."""
     c = TEXTURE_CASES[name]
-    x, y, z = c["scan"].shape
-    mb, L = c["max_bins"], max(x, y, z)
+    mb, L = c["max_bins"], max(c["scan"].shape)
     sizes = [_lib.RADIOMICS_TEXTURE_BYTES, 13 * mb * L * 4, mb * 27 * 4, mb * 27 * 4, mb * 27 * 8]
-    offs, off = [], GUARD
-    for s in sizes:
-        offs.append(off)
-        off += (s + GUARD + 255) // 256 * 256
-    buf = torch.full((off,), PATTERN, dtype=torch.uint8, device=DEV)
-    first = torch.full((_lib.RADIOMICS_RESULT_BYTES + mb * 4 + 13 * mb * mb * 4,), PATTERN, dtype=torch.uint8, device=DEV)
-    sbuf, sp = _device_bytes(c["scan"], c["scan_lead"])
-    mbuf, mp = _device_bytes(c["mask"], c["mask_lead"])
-    ws = torch.full((radiomics.workspace_bytes(x, y, z, mb),), 0xFF, dtype=torch.uint8, device=DEV)
-    n2 = _lib.lib().mmnn_radiomics_texture_workspace_bytes(x, y, z, mb)
-    assert n2 > 0
-    ws2 = torch.full((n2,), 0xFF, dtype=torch.uint8, device=DEV)
-    desc = _lib.RadiomicsDesc(x, y, z, ingest.TYPE_CODES[c["scan"].dtype], ingest.TYPE_CODES[c["mask"].dtype], *c["scan_scale"], *c["mask_scale"],
-                              c["bin_width"], mb)
-    stream = torch.cuda.current_stream().cuda_stream
-    f, p = first.data_ptr(), buf.data_ptr()
-    nb = _lib.RADIOMICS_RESULT_BYTES
-    _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), sp, mp, f, f + nb, f + nb + mb * 4, ws.data_ptr(), stream), "mmnn_radiomics")
-    _lib.check(_lib.lib().mmnn_radiomics_texture(ctypes.byref(desc), f, ws.data_ptr(), p + offs[0], p + offs[1], p + offs[2], p + offs[3],
-                                                 p + offs[4], ws2.data_ptr(), stream), "mmnn_radiomics_texture")
+    r, desc, first, _, _ = first_call(c)
+    buf, offs, _, _ = follow_call(r, desc, "texture", sizes)
     torch.cuda.synchronize()
-    b = buf.cpu().numpy()
-    keep = np.ones(off, dtype=bool)
-    for o, s in zip(offs, sizes):
-        keep[o:o + s] = False
-    assert (b[keep] == PATTERN).all(), f"{name}: bytes outside the texture block and the tables were written"
-    cut = [b[o:o + s].copy() for o, s in zip(offs, sizes)]
-    return {"block": cut[0], "glrlm": cut[1].view(np.uint32).astype(np.int64).reshape(13, mb, L),
-            "gldm": cut[2].view(np.uint32).astype(np.int64).reshape(mb, 27), "ngtdm_n": cut[3].view(np.uint32).astype(np.int64).reshape(mb, 27),
-            "ngtdm_s": cut[4].view(np.uint64).astype(np.int64).reshape(mb, 27), "fields": radiomics.unpack_block(first[:nb].cpu().numpy()), "first": first.cpu().numpy()}
+    got = cut(buf, offs, sizes, f"{name}: bytes outside the texture block and the tables were written")
+    return {"block": got[0], "glrlm": got[1].view(np.uint32).astype(np.int64).reshape(13, mb, L),
+            "gldm": got[2].view(np.uint32).astype(np.int64).reshape(mb, 27), "ngtdm_n": got[3].view(np.uint32).astype(np.int64).reshape(mb, 27),
+            "ngtdm_s": got[4].view(np.uint64).astype(np.int64).reshape(mb, 27),
+            "fields": radiomics.unpack_block(first[:_lib.RADIOMICS_RESULT_BYTES].cpu().numpy()), "first": first.cpu().numpy()}
 
 
 @pytest.mark.parametrize("name", list(TEXTURE_CASES))
@@ -139,20 +91,11 @@ def test_refusals():
     assert L.mmnn_radiomics_texture_workspace_bytes(2048, 2048, 512, 256) == -1          # 2^31 voxels
     t = torch.zeros(1 << 17, dtype=torch.uint8, device=DEV)
     p = t.data_ptr()
-    good = dict(x=4, y=4, z=4, scan_type=4, mask_type=2, scan_slope=1.0, scan_inter=0.0, mask_slope=1.0, mask_inter=0.0, bin_width=25.0, max_bins=16)
     ptrs = [p, p + 65536, p + 1024, p + 2048, p + 8192, p + 12288, p + 16384, p + 32768]      # result, ws, out, glrlm, gldm, n, s, ws2
-    for bad in (dict(bin_width=0.0), dict(bin_width=float("nan")), dict(scan_type=3), dict(mask_type=1), dict(x=0), dict(max_bins=0),
-                dict(max_bins=_lib.RADIOMICS_MAX_BINS + 1)):
-        desc = _lib.RadiomicsDesc(**dict(good, **bad))
-        assert L.mmnn_radiomics_texture(ctypes.byref(desc), *ptrs, None) == 1, bad
-    desc = _lib.RadiomicsDesc(**good)
-    assert L.mmnn_radiomics_texture(None, *ptrs, None) == 1
-    for k in range(len(ptrs)):
-        assert L.mmnn_radiomics_texture(ctypes.byref(desc), *[None if q == k else v for q, v in enumerate(ptrs)], None) == 1, k      # null
-    for k, step in ((0, 4), (1, 64), (2, 4), (3, 2), (4, 2), (5, 2), (6, 4), (7, 64)):
-        assert L.mmnn_radiomics_texture(ctypes.byref(desc), *[v + step if q == k else v for q, v in enumerate(ptrs)], None) == 1, k   # misaligned
-    torch.cuda.synchronize()
-    assert not t.any()                                     # refused before any launch: nothing was written
+    refusal_walk(lambda desc, q: L.mmnn_radiomics_texture(desc, *q, None), ptrs,
+                 ((0, 4), (1, 64), (2, 4), (3, 2), (4, 2), (5, 2), (6, 4), (7, 64)),
+                 (dict(bin_width=0.0), dict(bin_width=float("nan")), dict(scan_type=3), dict(mask_type=1), dict(x=0), dict(max_bins=0),
+                  dict(max_bins=_lib.RADIOMICS_MAX_BINS + 1)), t)
 
 
 def test_without_classes_the_extraction_is_what_it_was():
@@ -181,67 +124,20 @@ def test_without_classes_the_extraction_is_what_it_was():
 # input stream per width: tests/_radiomics_texture_cases.py: MLP_STREAM states the rule
 
 
-def mlp_case(width, n=4):
-    from oracle import restatement as OR
-    from tests._util import synth_sd
-    from tests import test_tail_ops_gpu as TT
-    sd = synth_sd(OR.mlp_schema(width, 2, 12), f"radmlp{width}.")
-    return sd, TT._u(f"rad/mlp/x/{width}/{MLP_STREAM[width]}", (n, width)), TT._u(f"rad/mlp/cot/{width}", (n, 12))
-
-
 @pytest.mark.parametrize("width", [82, 164, 196])
 def test_mlp_at_texture_width_vs_fp64(width):
-    """MLP(width) forward and backward at N = 4, training mode, against the fp64 torch restatement, at the bar tests/test_tail_ops_gpu.py
-    holds width 32 to: 82 columns of one modality with all classes, 164 of two, 196 with the 32 clinical columns in front."""
-    from mmnn_sts_amd.models.mlp import MLP
-    from oracle import restatement as OR
-    from tests import test_tail_ops_gpu as TT
-    sd, x, cot = mlp_case(width)
-    ref, leaves, pres = TT.mlp_ref(sd, x, True)
-    TT._assert_off_branch(pres, f"mlp width {width}")
-    assert torch.allclose(ref.detach(), OR.mlp_features({k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}, x.double(), True, 0.0).detach(),
-                          rtol=1e-12, atol=1e-14)
-    (ref * cot.double()).sum().backward()
-    m = MLP(width, 2, 12, dropout_prob=0.0)
-    m.load_state_dict(sd, strict=True)
-    m = m.to(DEV).train()
-    xg = x.to(DEV).requires_grad_(True)
-    f = m.features(m.backbone(xg))
-    (f * cot.to(DEV)).sum().backward()
-    params = dict(m.named_parameters())
-    errs = {"features": TT.rel_err(f.detach().cpu().numpy(), ref.detach().numpy()), "dx": TT.rel_err(xg.grad.cpu().numpy(), leaves["x"].grad.numpy())}
-    for k in TT.MLP_PARAM_KEYS:
-        errs[k] = TT.mlp_grad_err(k, params[k].grad, leaves, True)
-    assert len(errs) == 26
-    TT._check(errs, TT.BAR)
+    """tests/_radiomics_harness.py: mlp_at_width: 82 columns of one modality with all classes, 164 of two, 196 with the 32 clinical columns
+    in front."""
+    mlp_at_width(width, MLP_STREAM[width])
 
 
 # ---- through the Python layer and the command lines ------------------------------------------------------------------------------------------
-def _process(argv, cwd):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, *argv], cwd=str(cwd), env=env, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def _tiny_config(tmp_path, classes):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]},
-           "Radiomics": {"classes": list(classes)}}
-    path = tmp_path / "config.yaml"
-    path.write_text(yaml.safe_dump(cfg))
-    return str(path)
-
-
 def test_cli_extraction_tool_with_all_classes_writes_the_rows_of_finish(tmp_path):
     from mmnn_sts_amd.data.ImageDatasets import ImageDataset
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=3, seed=11)
     names = radiomics.feature_names(radiomics.TEXTURE_CLASSES)
     out = tmp_path / "radiomics.csv"
-    log = _process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--classes", "all", "--out", str(out)],
+    log = process(["-m", "mmnn_sts_amd.radiomics", "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--classes", "all", "--out", str(out)],
                    tmp_path)
     assert "164 features" in log
     cols, rows = radiomics.read_csv(out)
@@ -262,15 +158,15 @@ def test_cli_extraction_tool_with_all_classes_writes_the_rows_of_finish(tmp_path
 
 def test_cli_trains_the_fusion_model_on_the_wider_table_then_infers(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=12, val_fraction=0.34)
-    loc = ["--config", _tiny_config(tmp_path, radiomics.TEXTURE_CLASSES), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    loc = ["--config", tiny_config(tmp_path, {"classes": list(radiomics.TEXTURE_CLASSES)}), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"], "--image_loc", tree["image_loc"]]
     out = tmp_path / "run"
     out.mkdir()
     main = os.path.join(ROOT, "main.py")
-    log = _process([main, "--output_path", str(out), "--radiomics", "--images", "--survival", "--epochs", "1", *loc], out)
+    log = process([main, "--output_path", str(out), "--radiomics", "--images", "--survival", "--epochs", "1", *loc], out)
     assert "epoch 1/1" in log
     cols, rows = radiomics.read_csv(out / "radiomics_features.csv")
     assert len(cols) == 1 + 2 * 82 and cols[-1] == "t2_original_ngtdm_Strength" and len(rows) == 6
-    log = _process([main, "--output_path", str(out), "--inference", "--radiomics", "--images", "--survival", "--weights",
+    log = process([main, "--output_path", str(out), "--inference", "--radiomics", "--images", "--survival", "--weights",
                     str(out / "best_surv_model.pth"), "--rad_loc", str(out / "radiomics_features.csv"), *loc], out)
     assert "All C-indexes" in log

@@ -29,7 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mmnn_sts_amd import _lib, radiomics  # noqa: E402
 from mmnn_sts_amd.data import ingest  # noqa: E402
-from tools.radiomics_time import BIN_WIDTH, MAX_BINS, ROTATING, SHAPE, ellipsoid, queued_us  # noqa: E402
+from tools.radiomics_time import BIN_WIDTH, MAX_BINS, ROTATING, SHAPE, copy_tbs, ellipsoid, kernel_split, queued_us  # noqa: E402
 
 SPACING = (0.8, 0.8, 5.0)
 SIGMAS = (1.0, 3.0, 5.0)
@@ -54,13 +54,9 @@ def main():
     n = int(np.prod(SHAPE))
     stream = torch.cuda.current_stream().cuda_stream
     L = _lib.lib()
-    src, dst = torch.empty(COPY_BYTES, dtype=torch.uint8, device=dev), torch.empty(COPY_BYTES, dtype=torch.uint8, device=dev)
-    for _ in range(a.warmup):
-        dst.copy_(src)
-    copy_us = float(np.median([queued_us(lambda: dst.copy_(src), a.steps) for _ in range(a.repeats)]))
-    copy_tbs = 2 * COPY_BYTES / (copy_us * 1e-6) / 1e12
-    del src, dst
-    floor_us = (scan.nbytes + n * 4) / (copy_tbs * 1e12) * 1e6
+    tbs = float(np.median([copy_tbs(a.steps) for _ in range(a.repeats)]))
+    copy_us = 2 * COPY_BYTES / (tbs * 1e12) * 1e6
+    floor_us = (scan.nbytes + n * 4) / (tbs * 1e12) * 1e6
     ws = [torch.empty(L.mmnn_log_filter_workspace_bytes(*SHAPE), dtype=torch.uint8, device=dev) for _ in range(ROTATING)]
     per_sigma = {}
     for sigma in SIGMAS:
@@ -88,9 +84,7 @@ def main():
 
         def both(k):
             filt(k)
-            r = sets[k]
-            _lib.check(L.mmnn_radiomics(ctypes.byref(rdesc), outs[k].data_ptr(), m.data.data_ptr(), r.block.data_ptr(), r.hist.data_ptr(),
-                                        r.glcm.data_ptr(), r.workspace.data_ptr(), stream), "mmnn_radiomics")
+            radiomics.enqueue(sets[k], "first", rdesc, stream, outs[k].data_ptr(), m.data.data_ptr())
 
         def rotate(fn):
             def step():
@@ -108,26 +102,12 @@ def main():
         spread = {name: [round(min(q[name] for q in runs), 1), round(max(q[name] for q in runs), 1)] for name, _ in named}
         torch.cuda.synchronize()
         assert all(torch.equal(outs[0], o) for o in outs[1:]) and all(torch.equal(sets[0].block, r.block) for r in sets[1:]), "two calls differ"
-        try:
-            from torch.profiler import ProfilerActivity, profile
-            calls = 3
-            with profile(activities=[ProfilerActivity.CUDA]) as prof:
-                for _ in range(calls):
-                    filt(0)
-                torch.cuda.synchronize()
-            kernels = {}
-            for ev in prof.key_averages():
-                t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
-                if t:
-                    kernels[ev.key[:80]] = round(t / calls, 1)
-            kernels = dict(sorted(kernels.items(), key=lambda kv: -kv[1]))
-        except Exception as e:                                   # the split is an aid; the totals above stand without it
-            kernels = {"unavailable": repr(e)[:200]}
+        kernels = kernel_split(lambda: filt(0))
         per_sigma[str(sigma)] = {"radius": radius.tolist(), "bin_width": bw, "n_bins": fields["n_bins"], **times, "min_max_over_repeats": spread,
                                  "filter_over_floor": round(times["filter_us"] / floor_us, 1), "kernels_us": kernels}
         del sets, outs, first, f32
     res = {"shape": list(SHAPE), "spacing_mm": list(SPACING), "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "buffer_sets": ROTATING,
-           "copy_MB": COPY_BYTES >> 20, "copy_us": round(copy_us, 1), "copy_TBs": round(copy_tbs, 2),
+           "copy_MB": COPY_BYTES >> 20, "copy_us": round(copy_us, 1), "copy_TBs": round(tbs, 2),
            "contract_MB": round((scan.nbytes + n * 4) / 1e6, 2), "contract_floor_us": round(floor_us, 1),
            "moved_MB": round((scan.nbytes + n * (16 + 16 + 16 + 16) + n * 4) / 1e6, 1), "workspace_MB": round(ws[0].numel() / 1e6, 1),
            "max_radius": _lib.LOG_FILTER_MAX_RADIUS, "sigma_mm": per_sigma}

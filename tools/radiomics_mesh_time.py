@@ -16,7 +16,6 @@ Device times are HIP events after warm-up with the calls queued back to back beh
                            fp64 vector rate of the chip, 256 CUs x 4 SIMDs x 16 lanes per clock at the clock given by --mhz
 No target was set in advance: the capability is new."""
 import argparse
-import ctypes
 import dataclasses
 import json
 import os
@@ -26,9 +25,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmnn_sts_amd import _lib, radiomics  # noqa: E402
+from mmnn_sts_amd import radiomics  # noqa: E402
 from mmnn_sts_amd.data import ingest  # noqa: E402
-from tools.radiomics_time import BIN_WIDTH, MAX_BINS, SHAPE, ellipsoid, queued_us  # noqa: E402
+from tools.radiomics_time import BIN_WIDTH, MAX_BINS, SHAPE, ellipsoid, enqueuer, kernel_split, queued_us  # noqa: E402
 
 LINEAR = np.diag([0.78, 0.78, 5.0])
 FP64_OPS_PER_SCORE = 8
@@ -60,25 +59,14 @@ def main():
     del again
     mesh = radiomics.unpack_mesh(r.mesh.cpu().numpy())
     feats = radiomics.finish(r)
-    desc = _lib.RadiomicsDesc(*SHAPE, s.datatype, m.datatype, s.slope, s.inter, m.slope, m.inter, BIN_WIDTH, MAX_BINS)
-    lin = (ctypes.c_double * 9)(*LINEAR.ravel().tolist())
-    stream = torch.cuda.current_stream().cuda_stream
-    L = _lib.lib()
+    assert np.array_equal(r.linear, LINEAR)                # what the mesh call is enqueued under
+    call = enqueuer(s, m)
 
     def three():
-        _lib.check(L.mmnn_radiomics(ctypes.byref(desc), s.data.data_ptr(), m.data.data_ptr(), r.block.data_ptr(), r.hist.data_ptr(),
-                                    r.glcm.data_ptr(), r.workspace.data_ptr(), stream), "mmnn_radiomics")
-        _lib.check(L.mmnn_radiomics_texture(ctypes.byref(desc), r.block.data_ptr(), r.workspace.data_ptr(), r.texture.data_ptr(),
-                                            r.glrlm.data_ptr(), r.gldm.data_ptr(), r.ngtdm_n.data_ptr(), r.ngtdm_s.data_ptr(),
-                                            r.texture_workspace.data_ptr(), stream), "mmnn_radiomics_texture")
-        _lib.check(L.mmnn_radiomics_zones(ctypes.byref(desc), r.block.data_ptr(), r.workspace.data_ptr(), r.zones.data_ptr(),
-                                          r.labels.data_ptr(), r.sizes.data_ptr(), r.levels.data_ptr(), r.zones_workspace.data_ptr(),
-                                          stream), "mmnn_radiomics_zones")
+        call(r, "first", "texture", "zones")
 
     def four():
-        three()
-        _lib.check(L.mmnn_radiomics_mesh(ctypes.byref(desc), r.block.data_ptr(), r.workspace.data_ptr(), lin, r.mesh.data_ptr(),
-                                         r.mesh_cfg.data_ptr(), r.mesh_workspace.data_ptr(), stream), "mmnn_radiomics_mesh")
+        call(r, "first", "texture", "zones", "mesh")
 
     named = (("extract_three_us", three), ("extract_four_us", four))
     for _, fn in named:
@@ -87,21 +75,7 @@ def main():
     runs = [{name: queued_us(fn, a.steps) for name, fn in named} for _ in range(a.repeats)]          # the variants alternate inside a repeat
     times = {name: round(float(np.median([q[name] for q in runs])), 1) for name, _ in named}
     spread = {name: [round(min(q[name] for q in runs), 1), round(max(q[name] for q in runs), 1)] for name, _ in named}
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        calls = 3
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            for _ in range(calls):
-                four()
-            torch.cuda.synchronize()
-        kernels = {}
-        for ev in prof.key_averages():
-            t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
-            if t:
-                kernels[ev.key[:80]] = round(t / calls, 1)
-        kernels = dict(sorted(kernels.items(), key=lambda kv: -kv[1]))
-    except Exception as e:                                   # the split is an aid; the totals above stand without it
-        kernels = {"unavailable": repr(e)[:200]}
+    kernels = kernel_split(four)
     mesh_kernels = {k: v for k, v in kernels.items() if "mesh_" in k}
     V = mesh["n_vertices"]
     T = (V + 255) // 256

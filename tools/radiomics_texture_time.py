@@ -15,7 +15,6 @@ against two yardsticks taken in the same run:
     numpy_restatement_ms   tests/_radiomics_texture_ref.py: the four tables and the 35 features from the same bin volume, on the host
 No target was set in advance: the capability is new."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -25,21 +24,11 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmnn_sts_amd import _lib, radiomics  # noqa: E402
+from mmnn_sts_amd import radiomics  # noqa: E402
 from mmnn_sts_amd.data import ingest  # noqa: E402
-from tools.radiomics_time import BIN_WIDTH, MAX_BINS, ROTATING, SHAPE, ellipsoid, queued_us  # noqa: E402
+from tools.radiomics_time import BIN_WIDTH, MAX_BINS, ROTATING, SHAPE, copy_tbs, ellipsoid, enqueuer, kernel_split, queued_us  # noqa: E402
 
 SWEEPS = 13 + 1
-
-
-def copy_tbs(steps):
-    """Device-to-device copy rate, read + written bytes per second, in TB/s."""
-    src = torch.empty(256 << 20, dtype=torch.uint8, device="cuda")
-    dst = torch.empty_like(src)
-    for _ in range(3):
-        dst.copy_(src)
-    us = queued_us(lambda: dst.copy_(src), steps)
-    return 2 * src.numel() / (us * 1e-6) / 1e12
 
 
 def main():
@@ -62,19 +51,14 @@ def main():
     assert not (fields["empty"] or fields["nonfinite"] or fields["overflow"]), fields
     for r in sets[1:]:
         assert all(torch.equal(getattr(sets[0], k), getattr(r, k)) for k in ("block", "texture", "glrlm", "gldm", "ngtdm_n", "ngtdm_s")), "two calls differ"
-    desc = _lib.RadiomicsDesc(*SHAPE, s.datatype, m.datatype, s.slope, s.inter, m.slope, m.inter, BIN_WIDTH, MAX_BINS)
-    stream = torch.cuda.current_stream().cuda_stream
+    call = enqueuer(s, m)
     turn = [0]
 
     def first(r):
-        _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), s.data.data_ptr(), m.data.data_ptr(), r.block.data_ptr(), r.hist.data_ptr(),
-                                             r.glcm.data_ptr(), r.workspace.data_ptr(), stream), "mmnn_radiomics")
+        call(r, "first")
 
     def both(r):
-        first(r)
-        _lib.check(_lib.lib().mmnn_radiomics_texture(ctypes.byref(desc), r.block.data_ptr(), r.workspace.data_ptr(), r.texture.data_ptr(),
-                                                     r.glrlm.data_ptr(), r.gldm.data_ptr(), r.ngtdm_n.data_ptr(), r.ngtdm_s.data_ptr(),
-                                                     r.texture_workspace.data_ptr(), stream), "mmnn_radiomics_texture")
+        call(r, "first", "texture")
 
     def rotate(fn):
         def go():
@@ -91,22 +75,7 @@ def main():
     times = {name: round(float(np.median([r[name] for r in runs])), 1) for name, _ in named}
     spread = {name: [round(min(r[name] for r in runs), 1), round(max(r[name] for r in runs), 1)] for name, _ in named}
     tbs = float(np.median([copy_tbs(a.steps) for _ in range(a.repeats)]))
-    kernels = None
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        calls = 3
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            for _ in range(calls):
-                both(sets[0])
-            torch.cuda.synchronize()
-        kernels = {}
-        for ev in prof.key_averages():
-            t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
-            if t:
-                kernels[ev.key[:80]] = round(t / calls, 1)
-        kernels = dict(sorted(kernels.items(), key=lambda kv: -kv[1]))
-    except Exception as e:                                   # the split is an aid; the totals above stand without it
-        kernels = {"unavailable": repr(e)[:200]}
+    kernels = kernel_split(lambda: both(sets[0]))
     host_ms = None
     if not a.no_host:
         from tests import _radiomics_ref as R

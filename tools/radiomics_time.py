@@ -14,7 +14,6 @@ against two yardsticks taken in the same run:
     numpy_restatement_ms   tests/_radiomics_ref.py: restate() of the same volume on the host
 No target was set in advance and the capability is new, so there is no parent-commit figure."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -45,6 +44,45 @@ def queued_us(fn, steps):
     return a.elapsed_time(b) * 1e3 / steps
 
 
+def copy_tbs(steps):
+    """Device-to-device copy rate, read + written bytes per second, in TB/s."""
+    src = torch.empty(256 << 20, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    for _ in range(3):
+        dst.copy_(src)
+    us = queued_us(lambda: dst.copy_(src), steps)
+    return 2 * src.numel() / (us * 1e-6) / 1e12
+
+
+def kernel_split(fn, calls=3):
+    """The per-kernel split of `fn` (torch.profiler, device time per kernel name in us, averaged over `calls` calls), longest first."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(calls):
+                fn()
+            torch.cuda.synchronize()
+        kernels = {}
+        for ev in prof.key_averages():
+            t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+            if t:
+                kernels[ev.key[:80]] = round(t / calls, 1)
+        return dict(sorted(kernels.items(), key=lambda kv: -kv[1]))
+    except Exception as e:                                   # the split is an aid; the totals stand without it
+        return {"unavailable": repr(e)[:200]}
+
+
+def enqueuer(s, m, bin_width=BIN_WIDTH):
+    """call(result, *stages): the calls of `radiomics.STAGES` named, on the uploaded scan `s` and mask `m`, into the result's buffers."""
+    desc = _lib.RadiomicsDesc(*SHAPE, s.datatype, m.datatype, s.slope, s.inter, m.slope, m.inter, bin_width, MAX_BINS)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(r, *stages):
+        for st in stages:
+            radiomics.enqueue(r, st, desc, stream, s.data.data_ptr(), m.data.data_ptr())
+    return call
+
+
 def ellipsoid():
     g = np.meshgrid(*[np.arange(n, dtype=np.float32) for n in SHAPE], indexing="ij", sparse=True)
     return (sum(((v - c) / r) ** 2 for v, c, r in zip(g, CENTRE, RADIUS)) <= 1.0).astype(np.uint8)
@@ -69,20 +107,15 @@ def main():
     fields = radiomics.unpack_block(sets[0].block.cpu().numpy())
     assert not (fields["empty"] or fields["nonfinite"] or fields["overflow"]), fields
     assert all(torch.equal(sets[0].block, r.block) and torch.equal(sets[0].glcm, r.glcm) for r in sets[1:]), "two calls differ"
-    desc = _lib.RadiomicsDesc(*SHAPE, s.datatype, m.datatype, s.slope, s.inter, m.slope, m.inter, BIN_WIDTH, MAX_BINS)
-    stream = torch.cuda.current_stream().cuda_stream
+    call = enqueuer(s, m)
     turn = [0]
 
-    def call(r):
-        _lib.check(_lib.lib().mmnn_radiomics(ctypes.byref(desc), s.data.data_ptr(), m.data.data_ptr(), r.block.data_ptr(), r.hist.data_ptr(),
-                                             r.glcm.data_ptr(), r.workspace.data_ptr(), stream), "mmnn_radiomics")
-
     def reused():
-        call(sets[0])
+        call(sets[0], "first")
 
     def rotating():
         turn[0] = (turn[0] + 1) % ROTATING
-        call(sets[turn[0]])
+        call(sets[turn[0]], "first")
 
     named = (("extract_us", reused), ("extract_rotating_us", rotating))
     for _, fn in named:
@@ -91,22 +124,7 @@ def main():
     runs = [{name: queued_us(fn, a.steps) for name, fn in named} for _ in range(a.repeats)]
     times = {name: round(float(np.median([r[name] for r in runs])), 1) for name, _ in named}
     spread = {name: [round(min(r[name] for r in runs), 1), round(max(r[name] for r in runs), 1)] for name, _ in named}
-    kernels = None
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        calls = 3
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            for _ in range(calls):
-                reused()
-            torch.cuda.synchronize()
-        kernels = {}
-        for ev in prof.key_averages():
-            t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
-            if t:
-                kernels[ev.key[:80]] = round(t / calls, 1)
-        kernels = dict(sorted(kernels.items(), key=lambda kv: -kv[1]))
-    except Exception as e:                                   # the split is an aid; the totals above stand without it
-        kernels = {"unavailable": repr(e)[:200]}
+    kernels = kernel_split(reused)
     host_ms = None
     if not a.no_host:
         from tests import _radiomics_ref as R
