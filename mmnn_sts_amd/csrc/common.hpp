@@ -1,9 +1,9 @@
 // Shared device/host helpers for the MI355X (gfx950) kernels of the MMNN_STS fusion path.
 //
-// Holds: the host error channel and the launch macro; the batch-norm / dropout descriptors and the device code that turns statistics
-// into coefficients; the hash finaliser and 24-bit uniform of the counter-based random streams; the cross-lane helpers that follow the
-// MFMA tile layout (swz_xor, half_reduce16, acc_row); kernarg_warm; and on the host cdiv and the workspace Carver.  The lane butterfly
-// and the workgroup reductions are in reduce.hpp.
+// Holds: the host error channel, the launch macro and the per-device dynamic-LDS opt-in; the batch-norm / dropout descriptors and the
+// device code that turns statistics into coefficients; the hash finaliser and 24-bit uniform of the counter-based random streams; the
+// cross-lane helpers that follow the MFMA tile layout (swz_xor, half_reduce16, half_sum2, acc_row); kernarg_warm; and on the host cdiv
+// and the workspace Carver.  The lane butterfly and the workgroup reductions are in reduce.hpp.
 //
 // Conventions used by every kernel in this directory:
 //  * activations are fp32, channel-major per sample:  buf[n][c][v],  v = (d*H + h)*W + w  (NCDHW as the reference's
@@ -54,6 +54,25 @@ void debug_poison_lds(hipStream_t stream);
     ::mmnn::debug_poison_lds(stream);                                \
     hipLaunchKernelGGL(kern, grid, block, smem, stream, __VA_ARGS__); \
   } while (0)
+
+// Allow kernel KERN `bytes` of dynamic LDS on the calling thread's current device.  hipFuncSetAttribute is per device and not free:
+// each kernel (the template gives it a table of its own) remembers the largest request of each device and asks the runtime only past it.
+constexpr int MAX_DEVICES = 32;
+inline int current_device_slot() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+  return dev % MAX_DEVICES;
+}
+template <auto KERN>
+int allow_dynamic_lds(size_t bytes) {
+  static size_t allowed[MAX_DEVICES] = {0};
+  size_t& cur = allowed[current_device_slot()];
+  if (bytes > cur) {
+    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    cur = bytes;
+  }
+  return 0;
+}
 
 // ---- descriptors ----------------------------------------------------------------------------------------------------
 // Statistics of a tensor's channels: sum[r*stride + off + c], sq[...] for replica r.
@@ -264,6 +283,15 @@ __device__ __forceinline__ float half_reduce16(const float v[16], int lane) {
     w1 = keep + swz_xor<2>(send);
   }
   return w1 + swz_xor<1>(w1);
+}
+
+// Sum a pair of per-lane values over the 32 lanes of a wave half, the two butterflies interleaved; every lane ends with both totals.
+__device__ __forceinline__ void half_sum2(float& a, float& b) {
+  a += swz_xor<16>(a); b += swz_xor<16>(b);
+  a += swz_xor<8>(a);  b += swz_xor<8>(b);
+  a += swz_xor<4>(a);  b += swz_xor<4>(b);
+  a += swz_xor<2>(a);  b += swz_xor<2>(b);
+  a += swz_xor<1>(a);  b += swz_xor<1>(b);
 }
 
 // row of the 32x32 accumulator tile held in register r by a lane of half h (C/D layout of v_mfma_f32_32x32x2_f32)

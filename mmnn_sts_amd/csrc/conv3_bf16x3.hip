@@ -26,36 +26,30 @@
 
 namespace mmnn {
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 namespace c3b {
-constexpr int KC = 16, NT = 7, MAXC = 256;
-// Tile geometry: TD x TH x TW voxels = ROWS rows of 32 voxels (voxel v = 32 row + column: w = v % TW, h = (v / TW) % TH, d = v / (TW TH)).
-//   <2, 4, 32>: 256 voxels, extents wider than 16 (one workgroup per CU at 2 x 32^3).
-template <int TD, int TH, int TW>
-struct Geo {
-  static constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2, HV = HD * HH * HW, ROWS = TD * TH * TW / 32;
-  static constexpr int ITEMS = (2 * HV + 255) / 256;
-  static constexpr size_t OPER_BYTES = (size_t)2 * 6 * HV * 16;                            // two buffers of [3][2][HV] 16-byte entries
-  static constexpr size_t SMEM = OPER_BYTES + sizeof(float) * (2 * 4 * 32 + 32);          // + statistics scratch, dropout scales
-  static_assert(TD * TH * TW % 32 == 0 && (TW == 32 || TW == 16), "rows of 32 voxels");
-  static_assert(ITEMS <= NT, "one staging item per tap slot");
-  static_assert(4 * ROWS * 16 * 64 * sizeof(float) <= OPER_BYTES, "the partial tiles are summed in the operand buffers");
-  static_assert(SMEM <= 160 * 1024, "LDS");
-};
-
-__device__ __forceinline__ bf16x8_t as_bf16x8(uint4 v) { return __builtin_bit_cast(bf16x8_t, v); }
+constexpr int KC = BF16X3_KC, NT = 7, MAXC = 256;
+// The one tile of both kernels: 2 x 4 x 32 = 256 voxels, extents wider than 16 (one workgroup per CU at 2 x 32^3).
+using G = HaloTile<2, 4, 32>;
+constexpr size_t FWD_SMEM = G::OPER_BYTES + sizeof(float) * (2 * 4 * 32 + 32);            // + statistics scratch, dropout scales
+constexpr size_t DGRAD_SMEM = G::OPER_BYTES + sizeof(float) * 512;                        // + the mask's norm2 coefficients
+static_assert(G::ITEMS <= NT, "forward: one staging item per tap slot");
+static_assert(FWD_SMEM <= 160 * 1024 && DGRAD_SMEM <= 160 * 1024, "LDS");
 }  // namespace c3b
 
 // ----------------------------------------------------------------------------------------------------------------
-// Split passes: one thread per (voxel, group of 8 channels), 16-byte entries [piece][n][c / 8][v].  A workgroup is 256 voxels of one channel
+// Split passes: one thread per (voxel, group of 8 channels), one plane entry each (bf16x3.hpp).  A workgroup is 256 voxels of one channel
 // group of one sample; its 8 coefficients go through LDS while its operand loads are in flight.
 // ----------------------------------------------------------------------------------------------------------------
+// shared end of both passes: the thread's eight values -> its plane entry of each piece
+__device__ __forceinline__ void split_store(const FpropArgs& a, int n, int c8, int v, const float (&f)[8]) {
+  const int C8 = a.Cin / 8, V = a.D * a.H * a.W;
+  store_pieces(reinterpret_cast<uint4*>(a.x3) + plane_entry(n, c8, v, C8, V), plane_piece_stride(a.N, C8, V), f);
+}
+
 // forward operand: ReLU(BN(T1)) of all Cin channels -- exactly fmaxf(fmaf(a_c, x, b_c), 0) with bn_fwd_coef, then split3
 __global__ void __launch_bounds__(256) conv3_split_bnrelu_kernel(const FpropArgs a) {
   __shared__ float cf[2][8];
-  const int c8 = blockIdx.y, n = blockIdx.z, C8 = a.Cin / 8, V = a.D * a.H * a.W;
+  const int c8 = blockIdx.y, n = blockIdx.z, V = a.D * a.H * a.W;
   const int v = blockIdx.x * 256 + threadIdx.x;
   const float* __restrict__ x = a.in0 + (long)n * a.in0_ns + (long)(a.in0_coff + 8 * c8) * V;
   float xv[8];
@@ -70,17 +64,13 @@ __global__ void __launch_bounds__(256) conv3_split_bnrelu_kernel(const FpropArgs
   if (v >= V) return;
 #pragma unroll
   for (int e = 0; e < 8; ++e) xv[e] = fmaxf(fmaf(cf[0][e], xv[e], cf[1][e]), 0.f);
-  uint4 hi, mid, lo;
-  split3x8(xv, hi, mid, lo);
-  const long ps = (long)a.N * C8 * V;
-  uint4* __restrict__ dst = reinterpret_cast<uint4*>(a.x3) + ((long)n * C8 + c8) * V + v;
-  dst[0] = hi; dst[ps] = mid; dst[2 * ps] = lo;
+  split_store(a, n, c8, v, xv);
 }
 
 // data-gradient operand of the layer's 32 output channels: f = fmaf(p_c s, G, fmaf(q_c s, X, r_c s)), bn_bwd_coef(gr_in), s = drop_scale(drop_in)
 __global__ void __launch_bounds__(256) conv3_split_bnbwd_kernel(const FpropArgs a) {
   __shared__ float cf[3][8];
-  const int c8 = blockIdx.y, n = blockIdx.z, C8 = a.Cin / 8, V = a.D * a.H * a.W;
+  const int c8 = blockIdx.y, n = blockIdx.z, V = a.D * a.H * a.W;
   const int v = blockIdx.x * 256 + threadIdx.x;
   const float* __restrict__ gn = a.in0 + (long)n * a.in0_ns + (long)(a.in0_coff + 8 * c8) * V;
   const float* __restrict__ xn = a.in1 + (long)n * a.in1_ns + (long)(a.in1_coff + 8 * c8) * V;
@@ -101,11 +91,7 @@ __global__ void __launch_bounds__(256) conv3_split_bnbwd_kernel(const FpropArgs 
   if (v >= V) return;
 #pragma unroll
   for (int e = 0; e < 8; ++e) gv[e] = fmaf(cf[0][e], gv[e], fmaf(cf[1][e], xv[e], cf[2][e]));
-  uint4 hi, mid, lo;
-  split3x8(gv, hi, mid, lo);
-  const long ps = (long)a.N * C8 * V;
-  uint4* __restrict__ dst = reinterpret_cast<uint4*>(a.x3) + ((long)n * C8 + c8) * V + v;
-  dst[0] = hi; dst[ps] = mid; dst[2 * ps] = lo;
+  split_store(a, n, c8, v, gv);
 }
 
 static int launch_split(bool bwd, const FpropArgs& a, hipStream_t stream) {
@@ -120,25 +106,16 @@ static int launch_split(bool bwd, const FpropArgs& a, hipStream_t stream) {
 // ----------------------------------------------------------------------------------------------------------------
 // conv2 forward on the pre-split planes (a.x3) and weight panel (a.w3, pack kind 5: [piece][tap][Cin / 8][32])
 // ----------------------------------------------------------------------------------------------------------------
-template <int TD, int TH, int TW>
 __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a) {
   using namespace c3b;
-  using G = Geo<TD, TH, TW>;
-  constexpr int HH = G::HH, HW = G::HW, HV = G::HV, ROWS = G::ROWS, ITEMS = G::ITEMS;
-  constexpr size_t OPER_BYTES = G::OPER_BYTES;
+  constexpr int ROWS = G::ROWS, ITEMS = G::ITEMS;
   extern __shared__ uint4 xs128[];                          // [2][3][2][HV]
-  float* const sred = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + OPER_BYTES);   // [2][4][32]
+  float* const sred = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + G::OPER_BYTES);   // [2][4][32]
   float* const dsc = sred + 2 * 4 * 32;                     // [32] dropout scale of the output channels
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int D = a.D, H = a.H, W = a.W, V = D * H * W, C8 = a.Cin / 8, nchunk = a.Cin / KC;
-  const int twn = (W + TW - 1) / TW, thn = (H + TH - 1) / TH, tdn = (D + TD - 1) / TD;
-  int b = blockIdx.x;
-  const int w0 = (b % twn) * TW; b /= twn;
-  const int h0 = (b % thn) * TH; b /= thn;
-  const int d0 = (b % tdn) * TD;
-  const int n = b / tdn;
-  const long ps = (long)a.N * C8 * V;                       // entries per piece plane
-  const uint4* __restrict__ xin = reinterpret_cast<const uint4*>(a.x3) + (long)n * C8 * V;
+  const G tile(blockIdx.x, D, H, W);
+  const int n = tile.n;
   const uint4* __restrict__ wp = reinterpret_cast<const uint4*>(a.w3);
   if (tid < 32) dsc[tid] = drop_scale(a.drop_out, n, tid);
   f32x16_t acc[ROWS];
@@ -146,55 +123,26 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
   for (int t = 0; t < ROWS; ++t)
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-  // staging item = (channel half g, halo voxel hv), g the slow index: a wave's 64 lanes copy 64 consecutive halo entries of one plane
-  uint4 xr[ITEMS][3];
-  auto item_pos = [&](int it, int& g, int& hv, int& o) -> bool {
-    const int item = tid + it * 256;
-    g = item >= HV;
-    hv = item - g * HV;
-    const int hd = hv / (HH * HW), hh = (hv / HW) % HH, hw = hv % HW;
-    const int d = d0 + hd - 1, h = h0 + hh - 1, w = w0 + hw - 1;
-    o = (d * H + h) * W + w;
-    return item < 2 * HV && (unsigned)d < (unsigned)D && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-  };
-  auto issue = [&](int ch) {
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      int g, hv, o;
-      const bool ok = item_pos(it, g, hv, o);
-      const uint4* src = xin + (long)(2 * ch + g) * V + o;
-#pragma unroll
-      for (int p = 0; p < 3; ++p) xr[it][p] = ok ? src[p * ps] : make_uint4(0u, 0u, 0u, 0u);   // zero padding AFTER BN + ReLU
-    }
-  };
-  auto commit_item = [&](int it, int buf) {
-    int g, hv, o;
-    item_pos(it, g, hv, o);
-    if (tid + it * 256 >= 2 * HV) return;
-    uint4* dst = xs128 + buf * (6 * HV);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) dst[(p * 2 + g) * HV + hv] = xr[it][p];
-  };
+  const HaloStage<G> stage(tile, reinterpret_cast<const uint4*>(a.x3), a.N, C8, tid, D, H, W);   // zero padding AFTER BN + ReLU
+  HaloStage<G>::Regs xr;
   // weights: lane = (row m, channel half); ring slot ti holds the three pieces of tap wv + 4 ti of the chunk ahead
   bf16x8_t wr[NT][3];
   auto load_w = [&](int ti, int ch) {
     const int tap = wv + 4 * ti;
     if (tap < 27 && ch < nchunk) {
-      const int c8 = 2 * ch + (lane >> 5);
 #pragma unroll
-      for (int p = 0; p < 3; ++p) wr[ti][p] = as_bf16x8(wp[((long)(p * 27 + tap) * C8 + c8) * 32 + (lane & 31)]);
+      for (int p = 0; p < 3; ++p) wr[ti][p] = as_bf16x8(wp[panel_entry(p, tap, 2 * ch + (lane >> 5), lane & 31, C8, 32)]);
     }
   };
 #pragma unroll
   for (int ti = 0; ti < NT; ++ti) load_w(ti, 0);
-  issue(0);
-#pragma unroll
-  for (int it = 0; it < ITEMS; ++it) commit_item(it, 0);
+  stage.issue(xr, 0);
+  stage.commit(xr, xs128);
   __syncthreads();
   for (int ch = 0; ch < nchunk; ++ch) {
     const int cur = ch & 1;
     const bool more = ch + 1 < nchunk;
-    if (more) issue(ch + 1);
+    if (more) stage.issue(xr, ch + 1);
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti) {
       const int tap = wv + 4 * ti;
@@ -206,26 +154,19 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
         load_w(ti, ch + 1);
 #pragma unroll
         for (int t = 0; t < ROWS; ++t) {
-          const int v = t * 32 + (lane & 31);
-          const int hv = ((v / (TW * TH) + td) * HH + ((v / TW) % TH + th)) * HW + (v % TW + tw);
+          const int hv = G::tap_hv(t, lane & 31, td, th, tw);
           bf16x8_t bb[3];
 #pragma unroll
-          for (int p = 0; p < 3; ++p) bb[p] = as_bf16x8(xs128[cur * (6 * HV) + (p * 2 + (lane >> 5)) * HV + hv]);
-          // smallest products first: their sum is formed before it meets the large one
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[1], bb[1], acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[2], acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[2], bb[0], acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[1], acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[1], bb[0], acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[0], acc[t], 0, 0, 0);
+          for (int p = 0; p < 3; ++p) bb[p] = as_bf16x8(xs128[cur * G::BUF + G::lds_entry(p, lane >> 5, hv)]);
+          mfma_bf16x3(acc[t], aw, bb);
         }
       }
-      if (more && ti < ITEMS) commit_item(ti, cur ^ 1);
+      if (more && ti < ITEMS) stage.commit_item(xr, ti, xs128 + (cur ^ 1) * G::BUF);   // one item between the MFMAs of each tap
     }
     __syncthreads();
   }
   // sum the four waves' partial tiles (fixed order) through LDS; wave wv finishes rows wv, wv + 4, ... of the tile.
-  // register q of lane l: output channel 8 * (q / 4) + 4 * (l / 32) + q % 4, voxel column l % 32
+  // register q of lane l: output channel acc_row(q, l / 32), voxel column l % 32
   float* red = reinterpret_cast<float*>(xs128);            // [wave][row][q][lane]
 #pragma unroll
   for (int t = 0; t < ROWS; ++t)
@@ -241,16 +182,14 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
   for (int tt = 0; tt < (ROWS + 3) / 4; ++tt) {
     const int t = wv + 4 * tt;
     if (t >= ROWS) break;
-    const int v = t * 32 + (lane & 31);
-    const int d = d0 + v / (TW * TH), h = h0 + (v / TW) % TH, w = w0 + v % TW;
-    const bool ok = d < D && h < H && w < W;
-    const int o = (d * H + h) * W + w;
+    int o;
+    const bool ok = tile.row_pos(t, lane & 31, D, H, W, o);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       float val = 0.f;
 #pragma unroll
       for (int w2 = 0; w2 < 4; ++w2) val += red[((w2 * ROWS + t) * 16 + q) * 64 + lane];
-      const int m = 8 * (q / 4) + 4 * (lane >> 5) + q % 4;
+      const int m = acc_row(q, lane >> 5);
       val *= dsc[m];
       if (ok) {
         outn[(long)m * V + o] = val;
@@ -263,13 +202,9 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       float t0 = s0[q], t1 = s1[q];
-      t0 += swz_xor<16>(t0); t1 += swz_xor<16>(t1);
-      t0 += swz_xor<8>(t0);  t1 += swz_xor<8>(t1);
-      t0 += swz_xor<4>(t0);  t1 += swz_xor<4>(t1);
-      t0 += swz_xor<2>(t0);  t1 += swz_xor<2>(t1);
-      t0 += swz_xor<1>(t0);  t1 += swz_xor<1>(t1);
+      half_sum2(t0, t1);
       if ((lane & 31) == 0) {
-        const int m = 8 * (q / 4) + 4 * (lane >> 5) + q % 4;
+        const int m = acc_row(q, lane >> 5);
         sred[wv * 32 + m] = t0;
         sred[4 * 32 + wv * 32 + m] = t1;
       }
@@ -298,73 +233,35 @@ __global__ void __launch_bounds__(256) conv3_fwd_bf16x3_kernel(const FpropArgs a
 // ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs a) {
   using namespace c3b;
-  using G = Geo<2, 4, 32>;
-  constexpr int TH = 4, TW = 32, HH = G::HH, HW = G::HW, HV = G::HV, ROWS = G::ROWS, ITEMS = G::ITEMS, PF = 3, C8 = 4;
+  constexpr int ROWS = G::ROWS, PF = 3, C8 = 4;
   extern __shared__ uint4 xs128[];                          // [2 chunks][3][2][HV]
   float* const ecoef = reinterpret_cast<float*>(reinterpret_cast<char*>(xs128) + G::OPER_BYTES);   // [4][128]: a_m, b_m, mean_m, rstd_m of norm2
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int D = a.D, H = a.H, W = a.W, V = D * H * W;
-  const int twn = (W + TW - 1) / TW, thn = (H + TH - 1) / TH, tdn = (D + 1) / 2;
-  int b = blockIdx.x;
-  const int w0 = (b % twn) * TW; b /= twn;
-  const int h0 = (b % thn) * TH; b /= thn;
-  const int d0 = (b % tdn) * 2;
-  const int n = b / tdn;
-  const long ps = (long)a.N * C8 * V;
-  const uint4* __restrict__ xin = reinterpret_cast<const uint4*>(a.x3) + (long)n * C8 * V;
+  const G tile(blockIdx.x, D, H, W);
+  const int n = tile.n;
   const uint4* __restrict__ wp = reinterpret_cast<const uint4*>(a.w3);
-  uint4 xr[ITEMS][3];
-  auto item_pos = [&](int it, int& g, int& hv, int& o) -> bool {
-    const int item = tid + it * 256;
-    g = item >= HV;
-    hv = item - g * HV;
-    const int hd = hv / (HH * HW), hh = (hv / HW) % HH, hw = hv % HW;
-    const int d = d0 + hd - 1, h = h0 + hh - 1, w = w0 + hw - 1;
-    o = (d * H + h) * W + w;
-    return item < 2 * HV && (unsigned)d < (unsigned)D && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-  };
-  auto issue = [&](int ch) {
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      int g, hv, o;
-      const bool ok = item_pos(it, g, hv, o);
-      const uint4* src = xin + (long)(2 * ch + g) * V + o;
-#pragma unroll
-      for (int p = 0; p < 3; ++p) xr[it][p] = ok ? src[p * ps] : make_uint4(0u, 0u, 0u, 0u);
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      int g, hv, o;
-      item_pos(it, g, hv, o);
-      if (tid + it * 256 < 2 * HV) {
-        uint4* dst = xs128 + buf * (6 * HV);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) dst[(p * 2 + g) * HV + hv] = xr[it][p];
-      }
-    }
-  };
+  const HaloStage<G> stage(tile, reinterpret_cast<const uint4*>(a.x3), a.N, C8, tid, D, H, W);
+  HaloStage<G>::Regs xr;
   // weights: lane = (row m of this wave's tile, channel half); ring slot tap % PF
   bf16x8_t wr[PF][3];
   auto load_w = [&](int slot, int tap, int ch) {
     if (ch < 2) {
-      const int c8 = 2 * ch + (lane >> 5);
 #pragma unroll
-      for (int p = 0; p < 3; ++p) wr[slot][p] = as_bf16x8(wp[((long)(p * 27 + tap) * C8 + c8) * 128 + wv * 32 + (lane & 31)]);
+      for (int p = 0; p < 3; ++p) wr[slot][p] = as_bf16x8(wp[panel_entry(p, tap, 2 * ch + (lane >> 5), wv * 32 + (lane & 31), C8, 128)]);
     }
   };
 #pragma unroll
   for (int t = 0; t < PF; ++t) load_w(t, t, 0);
-  issue(0);
+  stage.issue(xr, 0);
   if (tid >= 128) {                                         // the statistics loads travel beside the operand loads
     const int m = tid - 128;
     float ea, eb, mu, rs;
     bn_fwd_coef(a.ebn, m, ea, eb, mu, rs);
     ecoef[m] = ea; ecoef[128 + m] = eb; ecoef[256 + m] = mu; ecoef[384 + m] = rs;
   }
-  commit(0);
-  issue(1);
+  stage.commit(xr, xs128);
+  stage.issue(xr, 1);
   __syncthreads();
   f32x16_t acc[ROWS];
 #pragma unroll
@@ -382,60 +279,50 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
       if (tq < 8) load_w(tw, tap + PF, ch); else load_w(tw, tw, ch + 1);
 #pragma unroll
       for (int t = 0; t < ROWS; ++t) {
-        const int hv = ((t / TH + td) * HH + (t % TH + th)) * HW + ((lane & 31) + tw);
+        const int hv = G::tap_hv(t, lane & 31, td, th, tw);
         bf16x8_t bb[3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) bb[p] = as_bf16x8(xs128[ch * (6 * HV) + (p * 2 + (lane >> 5)) * HV + hv]);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[1], bb[1], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[2], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[2], bb[0], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[1], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[1], bb[0], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[0], bb[0], acc[t], 0, 0, 0);
+        for (int p = 0; p < 3; ++p) bb[p] = as_bf16x8(xs128[ch * G::BUF + G::lds_entry(p, lane >> 5, hv)]);
+        mfma_bf16x3(acc[t], aw, bb);
       }
     }
   };
   pair(0, 0);
-  commit(1);                                                // chunk 1 -> its own buffer: nobody reads it before this barrier
+  stage.commit(xr, xs128 + G::BUF);                             // chunk 1 -> its own buffer: nobody reads it before this barrier
   __syncthreads();
 #pragma unroll 1
   for (int tq = 1; tq < 9; ++tq) pair(0, tq);
 #pragma unroll 1
   for (int tq = 0; tq < 9; ++tq) pair(1, tq);
-  // epilogue: register q of lane l = output row 32 wv + 8 (q / 4) + 4 (l / 32) + q % 4, voxel column l % 32 of row t
+  // epilogue: register q of lane l = output row 32 wv + acc_row(q, l / 32), voxel column l % 32 of row t
   const float* __restrict__ exn = a.ex + (long)n * a.ex_ns + (long)a.ex_coff * V;
   float* __restrict__ outn = a.out + (long)n * a.out_ns + (long)a.out_coff * V;
   float s0[16], s1[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) { s0[q] = 0.f; s1[q] = 0.f; }
-  auto row_pos = [&](int t, int& o) -> bool {
-    const int d = d0 + t / TH, h = h0 + t % TH, w = w0 + (lane & 31);
-    o = (d * H + h) * W + w;
-    return d < D && h < H && w < W;
-  };
   float xn[16];
   {
     int o;
-    const bool ok = row_pos(0, o);
+    const bool ok = tile.row_pos(0, lane & 31, D, H, W, o);
 #pragma unroll
-    for (int q = 0; q < 16; ++q) xn[q] = ok ? exn[(long)(wv * 32 + 8 * (q / 4) + 4 * (lane >> 5) + q % 4) * V + o] : 0.f;
+    for (int q = 0; q < 16; ++q) xn[q] = ok ? exn[(long)(wv * 32 + acc_row(q, lane >> 5)) * V + o] : 0.f;
   }
 #pragma unroll
   for (int t = 0; t < ROWS; ++t) {
     int o;
-    const bool ok = row_pos(t, o);
+    const bool ok = tile.row_pos(t, lane & 31, D, H, W, o);
     float xe[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) xe[q] = xn[q];
     if (t + 1 < ROWS) {                                     // the next row's mask operand is in flight while this row is masked and stored
       int o2;
-      const bool ok2 = row_pos(t + 1, o2);
+      const bool ok2 = tile.row_pos(t + 1, lane & 31, D, H, W, o2);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) xn[q] = ok2 ? exn[(long)(wv * 32 + 8 * (q / 4) + 4 * (lane >> 5) + q % 4) * V + o2] : 0.f;
+      for (int q = 0; q < 16; ++q) xn[q] = ok2 ? exn[(long)(wv * 32 + acc_row(q, lane >> 5)) * V + o2] : 0.f;
     }
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int m = wv * 32 + 8 * (q / 4) + 4 * (lane >> 5) + q % 4;
+      const int m = wv * 32 + acc_row(q, lane >> 5);
       if (ok) {
         const float pre = fmaf(ecoef[m], xe[q], ecoef[128 + m]);
         const float z = pre > 0.f ? acc[t][q] : 0.f;
@@ -450,13 +337,9 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     float t0 = s0[q], t1 = s1[q];
-    t0 += swz_xor<16>(t0); t1 += swz_xor<16>(t1);
-    t0 += swz_xor<8>(t0);  t1 += swz_xor<8>(t1);
-    t0 += swz_xor<4>(t0);  t1 += swz_xor<4>(t1);
-    t0 += swz_xor<2>(t0);  t1 += swz_xor<2>(t1);
-    t0 += swz_xor<1>(t0);  t1 += swz_xor<1>(t1);
+    half_sum2(t0, t1);
     if ((lane & 31) == 0) {
-      const int m = wv * 32 + 8 * (q / 4) + 4 * (lane >> 5) + q % 4;
+      const int m = wv * 32 + acc_row(q, lane >> 5);
       atomicAdd(a.dbeta + (long)rep * a.M + m, (double)t0);
       atomicAdd(a.dgamma + (long)rep * a.M + m, (double)t1);
     }
@@ -464,7 +347,22 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
 }
 
 // operand planes of one launch: three pieces x N x Cin / 8 x V entries of 16 bytes (the forward's Cin = 128, the data gradient's Cin = 32)
-size_t conv3_bf16x3_plane_bytes(const FpropArgs& a) { return (size_t)3 * a.N * (a.Cin / 8) * a.D * a.H * a.W * 16; }
+size_t conv3_bf16x3_plane_bytes(const FpropArgs& a) { return (size_t)3 * plane_piece_stride(a.N, a.Cin / 8, a.D * a.H * a.W) * 16; }
+
+// What both launches share once their own checks have passed: the checks on the planes, the offsets and the grid (`who` names the launch in
+// the messages, `chans` = channels of its widest tensor), the LDS opt-in, the split pass and the kernel, one workgroup per tile.
+template <auto KERN>
+static int launch_tiles(const char* who, bool bwd, int chans, size_t smem, const FpropArgs& a, hipStream_t stream) {
+  MMNN_REQUIRE(a.w3 && a.x3 && a.x3_bytes >= conv3_bf16x3_plane_bytes(a), "%s: pre-split weights or plane scratch missing", who);
+  MMNN_REQUIRE((long)(chans + 1) * a.D * a.H * a.W < (1l << 31), "%s: volume too large for 32-bit element offsets", who);
+  const long tiles = c3b::G::count(a.N, a.D, a.H, a.W);
+  MMNN_REQUIRE(tiles > 0 && tiles < (1l << 31), "%s: grid out of range", who);
+  if (int rc = allow_dynamic_lds<KERN>(smem)) return rc;
+  if (int rc = launch_split(bwd, a, stream)) return rc;
+  MMNN_LAUNCH(KERN, dim3((unsigned)tiles), dim3(256), smem, stream, a);
+  MMNN_HIP(hipGetLastError());
+  return 0;
+}
 
 bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a) {
   static const int mode = [] { const char* e = getenv("MMNN_BF16X3_DGRAD"); return e ? atoi(e) : 1; }();
@@ -473,25 +371,9 @@ bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a) {
 }
 
 int launch_conv3_dgrad_bf16x3(const FpropArgs& a, hipStream_t stream) {
-  using G = c3b::Geo<2, 4, 32>;
-  constexpr size_t SMEM = G::OPER_BYTES + sizeof(float) * 512;
-  static_assert(SMEM <= 160 * 1024, "LDS");
   MMNN_REQUIRE(conv3_dgrad_bf16x3_eligible(a), "conv3 dgrad bf16x3: shape not handled (M=%d, Cin=%d, W=%d)", a.M, a.Cin, a.W);
   MMNN_REQUIRE(a.in1 && a.ex && a.dgamma && a.dbeta, "conv3 dgrad bf16x3: operands missing");
-  MMNN_REQUIRE(a.w3 && a.x3 && a.x3_bytes >= conv3_bf16x3_plane_bytes(a), "conv3 dgrad bf16x3: pre-split weights or plane scratch missing");
-  MMNN_REQUIRE((long)(a.M + 1) * a.D * a.H * a.W < (1l << 31), "conv3 dgrad bf16x3: volume too large for 32-bit element offsets");
-  const long tiles = (long)a.N * cdiv(a.D, 2) * cdiv(a.H, 4) * cdiv(a.W, 32);
-  MMNN_REQUIRE(tiles > 0 && tiles < (1l << 31), "conv3 dgrad bf16x3: grid out of range");
-  static bool configured[MAX_DEVICES] = {false};
-  bool& conf = configured[current_device_slot()];
-  if (!conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_dgrad_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-    conf = true;
-  }
-  if (int rc = launch_split(true, a, stream)) return rc;
-  MMNN_LAUNCH(conv3_dgrad_bf16x3_kernel, dim3((unsigned)tiles), dim3(256), SMEM, stream, a);
-  MMNN_HIP(hipGetLastError());
-  return 0;
+  return launch_tiles<conv3_dgrad_bf16x3_kernel>("conv3 dgrad bf16x3", true, a.M, c3b::DGRAD_SMEM, a, stream);
 }
 
 // Shapes this kernel takes (everything else stays on fprop_kernel): 32 output channels, input channels in chunks of 16, rows wider than
@@ -504,23 +386,9 @@ bool conv3_fwd_bf16x3_eligible(const FpropArgs& a) {
 }
 
 int launch_conv3_fwd_bf16x3(const FpropArgs& a, hipStream_t stream) {
-  using G = c3b::Geo<2, 4, 32>;
   MMNN_REQUIRE(conv3_fwd_bf16x3_eligible(a), "conv3 bf16x3: shape not handled (M=%d, Cin=%d, W=%d)", a.M, a.Cin, a.W);
   MMNN_REQUIRE(a.drop_in.p <= 0.f, "conv3 bf16x3: no input dropout on this path");
-  MMNN_REQUIRE(a.w3 && a.x3 && a.x3_bytes >= conv3_bf16x3_plane_bytes(a), "conv3 bf16x3: pre-split weights or plane scratch missing");
-  MMNN_REQUIRE((long)(a.Cin + 1) * a.D * a.H * a.W < (1l << 31), "conv3 bf16x3: volume too large for 32-bit element offsets");
-  const long tiles = (long)a.N * cdiv(a.D, 2) * cdiv(a.H, 4) * cdiv(a.W, 32);
-  MMNN_REQUIRE(tiles > 0 && tiles < (1l << 31), "conv3 bf16x3: grid out of range");
-  static bool configured[MAX_DEVICES] = {false};
-  bool& conf = configured[current_device_slot()];
-  if (!conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_fwd_bf16x3_kernel<2, 4, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM));
-    conf = true;
-  }
-  if (int rc = launch_split(false, a, stream)) return rc;
-  MMNN_LAUNCH((conv3_fwd_bf16x3_kernel<2, 4, 32>), dim3((unsigned)tiles), dim3(256), G::SMEM, stream, a);
-  MMNN_HIP(hipGetLastError());
-  return 0;
+  return launch_tiles<conv3_fwd_bf16x3_kernel>("conv3 bf16x3", false, a.Cin, c3b::FWD_SMEM, a, stream);
 }
 
 }  // namespace mmnn

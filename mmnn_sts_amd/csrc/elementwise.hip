@@ -220,22 +220,17 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackJob* jobs) {
     uint4* dst = reinterpret_cast<uint4*>(j.dst);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < j.count; i += (long)gridDim.x * 256) {
       float v[8];
+      int t, k8, row;
       if (j.kind == 5) {                    // [t][c/8][m] of w[m][c][t]
-        const int m = (int)(i % j.M);
-        const long k = i / j.M;
-        const int c8 = (int)(k % (j.C / 8)), t = (int)(k / (j.C / 8));
+        panel_pos(i, j.C / 8, j.M, t, k8, row);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = j.src[((long)m * j.C + 8 * c8 + e) * 27 + t];
+        for (int e = 0; e < 8; ++e) v[e] = j.src[((long)row * j.C + 8 * k8 + e) * 27 + t];
       } else {                              // [t][m/8][c] of w[m][c][26-t]
-        const int c = (int)(i % j.C);
-        const long k = i / j.C;
-        const int m8 = (int)(k % (j.M / 8)), t = (int)(k / (j.M / 8));
+        panel_pos(i, j.M / 8, j.C, t, k8, row);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = j.src[((long)(8 * m8 + e) * j.C + c) * 27 + 26 - t];
+        for (int e = 0; e < 8; ++e) v[e] = j.src[((long)(8 * k8 + e) * j.C + row) * 27 + 26 - t];
       }
-      uint4 hi, mid, lo;
-      split3x8(v, hi, mid, lo);
-      dst[i] = hi; dst[j.count + i] = mid; dst[2 * j.count + i] = lo;
+      store_pieces(dst + i, j.count, v);    // i = panel_entry(0, t, k8, row, ...), j.count = entries per piece
     }
     return;
   }

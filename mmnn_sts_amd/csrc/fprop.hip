@@ -6,12 +6,6 @@
 
 namespace mmnn {
 
-int current_device_slot() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-  return dev % MAX_DEVICES;
-}
-
 // defined (explicitly instantiated) in fprop_inst_*.hip, one translation unit per combination
 template <int TAPS, int PRO, int EPI>
 int dispatch(const FpropArgs& a, hipStream_t s);

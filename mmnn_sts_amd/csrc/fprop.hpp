@@ -79,8 +79,6 @@ int launch_fprop(const FpropArgs& a, int taps, int pro, int epi, hipStream_t str
 bool conv3_fwd_bf16x3_eligible(const FpropArgs& a);
 bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a);
 size_t conv3_bf16x3_plane_bytes(const FpropArgs& a);
-int current_device_slot();   // index of the calling thread's current HIP device, for per-device caches of kernel attributes
-constexpr int MAX_DEVICES = 32;
 
 #if defined(__HIPCC__)
 

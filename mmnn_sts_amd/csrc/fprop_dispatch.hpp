@@ -13,15 +13,10 @@ static int launch_cfg(const FpropArgs& a_in, hipStream_t stream) {
   FpropArgs a = a_in;
   constexpr bool KZ_OK = (MT * NT == 1) || (TAPS == 27 && TW <= 16);   // only the small-extent tiles are ever short of blocks
   using C = FpropCfg<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
-  auto kern = fprop_kernel<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
+  constexpr auto kern = fprop_kernel<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
   const size_t smem = C::smem_bytes(a.Cin);
   MMNN_REQUIRE(smem <= 160 * 1024, "fprop: %zu bytes of LDS needed (Cin=%d) exceeds 160 KiB", smem, a.Cin);
-  static size_t configured[MAX_DEVICES] = {0};   // hipFuncSetAttribute is per device: remember the largest request of each
-  size_t& conf = configured[current_device_slot()];
-  if (smem > conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    conf = smem;
-  }
+  if (int rc = allow_dynamic_lds<kern>(smem)) return rc;
   long tiles;
   if (TAPS == 27) tiles = (long)a.N * cdiv(a.D, TD) * cdiv(a.H, TH) * cdiv(a.W, TW);
   else tiles = (long)a.N * cdiv((long)a.D * a.H * a.W, C::V_B);

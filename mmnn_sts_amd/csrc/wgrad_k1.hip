@@ -8,14 +8,9 @@ namespace mmnn {
 template <int PRO_X, int WC>
 static int launch1(const WgradArgs& a, hipStream_t stream) {
   using C = Wg1Cfg<WC>;
-  auto kern = wgrad1_kernel<PRO_X, WC>;
+  constexpr auto kern = wgrad1_kernel<PRO_X, WC>;
   const size_t smem = C::smem_bytes();
-  static bool configured[MAX_DEVICES] = {false};   // per device
-  bool& conf = configured[current_device_slot()];
-  if (!conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    conf = true;
-  }
+  if (int rc = allow_dynamic_lds<kern>(smem)) return rc;
   MMNN_LAUNCH(kern, dim3(a.nsplit, cdiv(a.Cin, 32 * WC), cdiv(a.M, 128)), dim3(C::NTHREADS), smem, stream, a);
   MMNN_HIP(hipGetLastError());
   return 0;
@@ -24,14 +19,9 @@ static int launch1(const WgradArgs& a, hipStream_t stream) {
 template <int PRO_X, int WC>
 static int launch1_batched(const WgradArgs* host, const WgradArgs* dev, int count, uint64_t seed, hipStream_t stream) {
   using C = Wg1Cfg<WC>;
-  auto kern = wgrad1_batched_kernel<PRO_X, WC>;
+  constexpr auto kern = wgrad1_batched_kernel<PRO_X, WC>;
   const size_t smem = C::smem_bytes();
-  static bool configured[MAX_DEVICES] = {false};   // per device
-  bool& conf = configured[current_device_slot()];
-  if (!conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    conf = true;
-  }
+  if (int rc = allow_dynamic_lds<kern>(smem)) return rc;
   int gx = 1, gy = 1;
   for (int i = 0; i < count; ++i) { gx = std::max(gx, host[i].nsplit); gy = std::max(gy, cdiv(host[i].Cin, 32 * WC)); }
   // (an XCD-aware block order, as in the 3x3x3 kernel, measured 2-3 % slower here: DESIGN §4)

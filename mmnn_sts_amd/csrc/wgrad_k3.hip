@@ -9,14 +9,9 @@ namespace mmnn {
 template <int PRO_X, int TD, int TH, int TW>
 static int launch3_batched(const WgradArgs* host, const WgradArgs* dev, int count, uint64_t seed, hipStream_t stream) {
   using C = Wg3Cfg<TD, TH, TW>;
-  auto kern = wgrad3_batched_kernel<PRO_X, TD, TH, TW>;
+  constexpr auto kern = wgrad3_batched_kernel<PRO_X, TD, TH, TW>;
   const size_t smem = C::smem_bytes();
-  static bool configured[MAX_DEVICES] = {false};   // per device
-  bool& conf = configured[current_device_slot()];
-  if (!conf) {
-    MMNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    conf = true;
-  }
+  if (int rc = allow_dynamic_lds<kern>(smem)) return rc;
   int gx = 1, gy = 1;
   bool uniform = true;
   for (int i = 0; i < count; ++i) {
