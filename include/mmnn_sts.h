@@ -812,6 +812,96 @@ typedef struct {
 int64_t mmnn_log_filter_workspace_bytes(int32_t x, int32_t y, int32_t z);
 int mmnn_log_filter(const mmnn_log_filter_desc* d, const void* scan, const double* taps, float* out, void* ws, void* stream);
 
+/* ---- the two optional pre-steps of the radiomics path, in PyRadiomics' order: normalise the scan's intensities, then resample the
+ * (scan, mask) pair to a stated voxel spacing (csrc/radiomics_resample.hip).  Each returns a new scan of type 16 with slope 0 (and the
+ * second a byte mask) that mmnn_radiomics, its follow-on calls and mmnn_log_filter take like any other.  **Parity with PyRadiomics is
+ * unpinned**: no test compares with it; its B-spline is ITK's, and it crops the resampled grid to the ROI's bounding
+ * box plus padding, where this resamples the whole scan.
+ *
+ * mmnn_normalize_scan.  `scan` holds x*y*z elements, x fastest, in NIfTI type scan_type; a voxel's value v is raw * scan_slope +
+ * scan_inter in fp64 under the rule of mmnn_radiomics_desc (a slope of 0 switches the scaling off).  The statistics are those of the
+ * WHOLE scan (n = x*y*z), not of an ROI, as PyRadiomics takes them:
+ *   mean = (sum v) / n;   sd = sqrt(sum (v - mean)^2 / (n - 1)), a second pass over the scan with the first one's mean.  (The n - 1
+ *   divisor is believed to be what ITK's statistics filter uses; that belief is unpinned.)
+ *   out = (float)(((v - mean) / sd) * scale), one rounding to fp32; with outliers = k > 0 the fp64 value is clamped to
+ *   [-k scale, +k scale] before that rounding (a NaN stays a NaN).  `out` is [z][y][x] float32, every element written.
+ *   result (on the device, nothing is read back): n, mean, sd, and nonfinite = 1 when any voxel is NaN or infinite.
+ * A non-finite voxel makes mean or sd NaN and with them EVERY output; so does a scan of one voxel (0 / 0) and a constant scan whose sums
+ * are exact (sd = 0, 0 / 0: integer types; a constant whose fp64 mean rounds leaves a tiny non-zero sd and finite, meaningless outputs,
+ * which nothing detects).  mmnn_radiomics then finds non-finite values inside the mask and sets its nonfinite flag.
+ * The two fp64 sums: workgroup p of P = min(256, ceil(n / 256)) adds the voxels p 256 + t + k P 256 (lane t, k ascending) per lane,
+ * folds the workgroup by block_reduce (csrc/reduce.hpp: the lanes of each wave by the xor butterfly, then the waves in index order), and
+ * the P partial sums, part p in lane p, are folded by one more block_reduce: a partition and an order fixed by the extents alone, no floating-point atomics, repeated calls are bit-identical.  No host wait.
+ * ws: mmnn_normalize_scan_workspace_bytes bytes, aligned to 256.  Refused (status 1, nothing written; the size returns -1) before any
+ * launch: a null pointer, a non-positive extent, x*y*z >= 2^31, an unsupported type code, a scale that is not finite and positive, an
+ * outliers that is negative or not finite, a scan not aligned to its element size, out not to 4, result not to 8, ws not to 256. */
+typedef struct {
+  int32_t x, y, z;
+  int32_t scan_type;              /* NIfTI datatype code */
+  double scan_slope, scan_inter;
+  double scale;                   /* what the z-score is multiplied by */
+  double outliers;                /* 0: no clamp; k > 0: clamp to [-k scale, +k scale] */
+} mmnn_normalize_desc;
+typedef struct {
+  int64_t n;
+  double mean, sd;
+  int64_t nonfinite;
+} mmnn_normalize_result;
+int64_t mmnn_normalize_scan_workspace_bytes(int32_t x, int32_t y, int32_t z);
+int mmnn_normalize_scan(const mmnn_normalize_desc* d, const void* scan, float* out, mmnn_normalize_result* result, void* ws, void* stream);
+
+/* mmnn_resample_pair.  `scan` and `mask` hold x*y*z elements each, as above; `out` is [mz][my][mx] float32 and `out_mask` [mz][my][mx]
+ * bytes, every element of both written.  The caller decides the output grid and states it in per-axis tables; the library calls
+ * neither floor on a coordinate nor any power.
+ *   tables   mx + my + mz entries of mmnn_resample_entry (56 bytes each, no padding): those of the x axis, then y, then z.  Entry j of
+ *            an axis of source extent n whose output sample j sits at the continuous source index c: with f = floor(c), t = c - f,
+ *              i[k]     mirror(f - 1 + k), k = 0..3: the whole-sample symmetric reflection, period 2 n - 2 (0 when n = 1)
+ *              w[k]     the cubic B-spline weights (1-t)^3/6, 2/3 - t^2 (2-t)/2, 2/3 - (1-t)^2 (1+t)/2, t^3/6
+ *              nearest  clamp(floor(c + 0.5), 0, n - 1): where the mask is read
+ *              inside   0 when c < -0.5 or c >= n - 0.5 (ITK's buffer test), otherwise 1
+ *            `tables` is the copy on the device, which the kernels read; `tables_host` the same bytes on the host, read during the call
+ *            to refuse an index outside its axis before anything is launched.
+ *   prefilter  the scan becomes cubic B-spline coefficients in fp64, one volume in ws, by the recursion below along every line of x,
+ *            then of y, then of z; an axis of extent 1 is left as it is.  z = pole (sqrt(3) - 2), pole_gain = z / (z^2 - 1), gain = 6,
+ *            pole_power[k] = z^k, k = 0 .. H - 1, H = MMNN_RESAMPLE_HORIZON: all from the descriptor.  |z|^40 = 1.3e-23 is below fp64
+ *            resolution, so one horizon serves every axis length.  Every product is rounded before its sum, no contraction:
+ *              s[k]     = gain v[k]
+ *              c+[0]    = sum_{k = 0 .. H-1, ascending from +0.0} pole_power[k] s[mirror(k)]
+ *              c+[k]    = s[k] + z c+[k-1]                         k = 1 .. n-1
+ *              c-[n-1]  = pole_gain (c+[n-1] + z c+[n-2])
+ *              c-[k]    = z (c-[k+1] - c+[k])                      k = n-2 .. 0
+ *   evaluation  out[jx, jy, jz] = (float)( sum_kz wz[jz][kz] ( sum_ky wy[jy][ky] ( sum_kx wx[jx][kx]
+ *            coef[ix[jx][kx], iy[jy][ky], iz[jz][kz]] ) ) ), each sum over k = 0..3 ascending from +0.0, product then sum; computed as
+ *            three passes x, y, z over fp64 intermediates in ws (the inner sums depend on (jx, y, z) and (jx, jy, z) alone: the same
+ *            bits as the nested form).  Where any axis is outside, out is 0.0f (ITK's default pixel value).
+ *   mask     out_mask is 1 where all three axes are inside and the mask voxel at the three nearest indices, raw * mask_slope +
+ *            mask_inter, is not 0 (a NaN counts as not 0: the ROI rule of mmnn_radiomics); otherwise 0.
+ * A non-finite scan voxel propagates through the recursion: it reaches the whole of its x line, then every y line that crosses that,
+ * then every z line -- in practice the whole volume.  One lane per output, no atomics: repeated calls are bit-identical, and so is a
+ * restatement that follows the order above.  No host wait.  ws: mmnn_resample_pair_workspace_bytes bytes, aligned to 256: the
+ * coefficients and the two intermediates, 8 (x y z + mx y z + mx my z) bytes.  Refused (status 1, nothing written; the size returns -1)
+ * before any launch: a null pointer, a non-positive extent on either grid, 2^31 elements or more on either grid or in an intermediate,
+ * an unsupported type code, a non-finite prefilter constant, a scan or mask not aligned to its element size, tables not to 8, out not to
+ * 4, ws not to 256, a table index outside its source axis, a non-finite weight. */
+#define MMNN_RESAMPLE_HORIZON 40
+typedef struct {
+  double w[4];
+  int32_t i[4];
+  int32_t nearest;
+  int32_t inside;
+} mmnn_resample_entry;
+typedef struct {
+  int32_t x, y, z;                /* the source grid */
+  int32_t mx, my, mz;             /* the output grid */
+  int32_t scan_type, mask_type;   /* NIfTI datatype codes */
+  double scan_slope, scan_inter, mask_slope, mask_inter;
+  double pole, pole_gain, gain;
+  double pole_power[MMNN_RESAMPLE_HORIZON];
+} mmnn_resample_desc;
+int64_t mmnn_resample_pair_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t mx, int32_t my, int32_t mz);
+int mmnn_resample_pair(const mmnn_resample_desc* d, const void* scan, const void* mask, const mmnn_resample_entry* tables_host,
+                       const mmnn_resample_entry* tables, float* out, uint8_t* out_mask, void* ws, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

@@ -27,7 +27,9 @@ config reads them back from a csv it writes first (the "synthetic 32-feature x 6
 on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py; the config's
 `Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it, `--mesh_shape` / `Radiomics: mesh_shape: true` the
 eight mesh-based shape columns, `--log_sigma 1,3` / `Radiomics: log: {sigma: [1.0, 3.0]}` the `log-sigma-<sigma>-mm-3D_*` columns of the
-scan filtered by a Laplacian of Gaussian at those scales in mm); alone it is
+scan filtered by a Laplacian of Gaussian at those scales in mm; `--normalize` / `Radiomics: normalize` z-scores each scan first and
+`--resample_spacing 1,1,1` / `Radiomics: resample: {spacing: [1, 1, 1]}` brings scan and mask onto that spacing, both on the device and
+without a change of the columns); alone it is
 the standalone MLP over the radiomic columns, with `--images` the fusion model, with `--preop` / `--postop` too the clinical columns first.
 There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
 With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
@@ -285,6 +287,9 @@ def extract_radiomics_if_needed(parser, args):
     rc, classes, glszm = parser.radiomicsConfig(), parser.radiomicsClasses(), parser.radiomicsZones()
     mesh = getattr(args, "mesh_shape", False) or parser.radiomicsMesh()
     log = parser.radiomicsLog(getattr(args, "log_sigma", None), getattr(args, "log_bin_width", None))
+    normalize = parser.radiomicsNormalize(getattr(args, "normalize", False), getattr(args, "normalize_scale", None),
+                                          getattr(args, "normalize_outliers", None))
+    resample = parser.radiomicsResample(getattr(args, "resample_spacing", None))
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
     sets = [ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
@@ -292,7 +297,7 @@ def extract_radiomics_if_needed(parser, args):
     threshold = (parser.config.get("Data") or {}).get("mask_threshold")
     rows = radiomics.extract_modalities(sets, torch.device("cuda", 0), rc["bin_width"], rc["max_bins"],
                                         None if threshold is None else float(threshold), classes=classes, glszm=glszm, mesh=mesh,
-                                        log_sigma=log["sigma"], log_bin_width=log["bin_width"])
+                                        log_sigma=log["sigma"], log_bin_width=log["bin_width"], normalize=normalize, resample=resample)
     os.makedirs(args.output_path, exist_ok=True)
     out = os.path.join(args.output_path, "radiomics_features.csv")
     radiomics.write_csv(out, rows)
@@ -666,6 +671,8 @@ def build_arg_parser():
                          "log-sigma-<sigma>-mm-3D_* columns of the filtered scans; overrides the config's `Radiomics: log: sigma`")
     ap.add_argument("--log_bin_width", type=float, default=None,
                     help="bin width of the filtered images; overrides `Radiomics: log: bin_width` (default: `Radiomics: bin_width`)")
+    from mmnn_sts_amd.radiomics import add_pre_step_arguments
+    add_pre_step_arguments(ap)
     ap.add_argument("--occlusion_window", type=int, default=16, help="edge of the occluded box in voxels")
     ap.add_argument("--occlusion_stride", type=int, default=8, help="step of the box, 1..window")
     ap.add_argument("--occlusion_batch", type=int, default=8, help="occluded samples per forward")

@@ -167,6 +167,29 @@ class LogFilterDesc(Structure):
                 ("scan_inter", ctypes.c_double), ("radius", c_int32 * 3), ("weight", ctypes.c_double * 3)]
 
 
+RESAMPLE_HORIZON = 40                        # MMNN_RESAMPLE_HORIZON
+NORMALIZE_RESULT_BYTES = 32                  # mmnn_normalize_result: int64 n, double mean, sd, int64 nonfinite
+
+
+class NormalizeDesc(Structure):
+    """mmnn_normalize_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("scan_type", c_int32), ("scan_slope", ctypes.c_double),
+                ("scan_inter", ctypes.c_double), ("scale", ctypes.c_double), ("outliers", ctypes.c_double)]
+
+
+class ResampleEntry(Structure):
+    """mmnn_resample_entry (include/mmnn_sts.h): 56 bytes."""
+    _fields_ = [("w", ctypes.c_double * 4), ("i", c_int32 * 4), ("nearest", c_int32), ("inside", c_int32)]
+
+
+class ResampleDesc(Structure):
+    """mmnn_resample_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("mx", c_int32), ("my", c_int32), ("mz", c_int32), ("scan_type", c_int32),
+                ("mask_type", c_int32), ("scan_slope", ctypes.c_double), ("scan_inter", ctypes.c_double), ("mask_slope", ctypes.c_double),
+                ("mask_inter", ctypes.c_double), ("pole", ctypes.c_double), ("pole_gain", ctypes.c_double), ("gain", ctypes.c_double),
+                ("pole_power", ctypes.c_double * RESAMPLE_HORIZON)]
+
+
 def lib():
     """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
     global _lib
@@ -299,6 +322,14 @@ def lib():
     L.mmnn_log_filter_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.mmnn_log_filter.restype = c_int32
     L.mmnn_log_filter.argtypes = [POINTER(LogFilterDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_normalize_scan_workspace_bytes.restype = c_int64
+    L.mmnn_normalize_scan_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.mmnn_normalize_scan.restype = c_int32
+    L.mmnn_normalize_scan.argtypes = [POINTER(NormalizeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_resample_pair_workspace_bytes.restype = c_int64
+    L.mmnn_resample_pair_workspace_bytes.argtypes = [c_int32] * 6
+    L.mmnn_resample_pair.restype = c_int32
+    L.mmnn_resample_pair.argtypes = [POINTER(ResampleDesc)] + [c_void_p] * 8
     L.mmnn_channel_means.restype = c_int32
     L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.mmnn_lr_range_state_bytes.restype = c_int64

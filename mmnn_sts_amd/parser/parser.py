@@ -122,6 +122,36 @@ class Parser:
             raise ConfigurationError('{}, got bin_width {!r}'.format(valid, bw))
         return {'sigma': sigmas, 'bin_width': float(bw)}
 
+    def radiomicsNormalize(self, flag=False, scale=None, outliers=None):
+        """`Radiomics: normalize: true | {scale: 100, outliers: 3}`: the whole-scan intensity normalisation ahead of the extraction ->
+        None (off, the default) or (scale, outliers).  `flag` / `scale` / `outliers`: a command line's values, which go before the
+        config's; any of them switches the step on.  The default scale is 100, not PyRadiomics' 1, because of the default bin width 25."""
+        from ..radiomics import normalize_settings
+        norm = (self.config.get('Radiomics') or {}).get('normalize')
+        if norm is not None and not isinstance(norm, (bool, dict)):
+            raise ConfigurationError('Radiomics.normalize must be true / false or a mapping of `scale` and `outliers`, got {!r}'.format(norm))
+        settings = dict(norm) if isinstance(norm, dict) else {}
+        if scale is not None:
+            settings['scale'] = scale
+        if outliers is not None:
+            settings['outliers'] = outliers
+        on = bool(flag) or scale is not None or outliers is not None or isinstance(norm, dict) or norm is True
+        return normalize_settings(settings) if on else None
+
+    def radiomicsResample(self, spacing=None):
+        """`Radiomics: resample: {spacing: [1, 1, 1]}` (or one number): the voxel spacing in mm scan and mask are resampled to ahead of
+        the extraction -> None (off, the default) or the three spacings; 0 keeps an axis.  `spacing`: a command line's value, which goes
+        before the config's."""
+        from ..radiomics import resample_spacing
+        res = (self.config.get('Radiomics') or {}).get('resample')
+        if spacing is not None:
+            return resample_spacing(spacing)
+        if res is not None and not isinstance(res, dict):
+            raise ConfigurationError('Radiomics.resample must be a mapping of `spacing` (one number or three, in mm), got {!r}'.format(res))
+        if isinstance(res, dict) and isinstance(res.get('spacing'), str):
+            raise ConfigurationError('Radiomics.resample.spacing must be one number or a list of three (mm), got {!r}'.format(res['spacing']))
+        return resample_spacing(res)
+
     def _radiomicsExcluded(self):
         rm = self.config.get('RadiomicsModel') or {}
         return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])

@@ -1,6 +1,7 @@
 """Radiomic features of a (scan, mask) pair, extracted on the device: binding of `mmnn_radiomics` (csrc/radiomics.hip), of
 `mmnn_radiomics_texture` (csrc/radiomics_texture.hip), of `mmnn_radiomics_zones` (csrc/radiomics_zones.hip), of `mmnn_radiomics_mesh`
-(csrc/radiomics_mesh.hip) and of `mmnn_log_filter` (csrc/radiomics_filter.hip).
+(csrc/radiomics_mesh.hip), of `mmnn_log_filter` (csrc/radiomics_filter.hip) and of `mmnn_normalize_scan` and `mmnn_resample_pair`
+(csrc/radiomics_resample.hip).
 
     extract(scan, mask, device)            enqueue one extraction; the result holds device tensors, nothing is read back
     finish(result, affine)                 one read-back -> {feature name: float}: adds TotalEnergy and the voxel-based shape features
@@ -9,8 +10,12 @@
                                            size-zone ones, then the mesh-based shape ones, then those of the filtered images
     log_taps(sigma_mm, spacing)            the radii, taps and weights of one Laplacian-of-Gaussian scale (numpy fp64, host only)
     log_filter(scan, sigma_mm, device)     enqueue the filter; the float32 volume stays on the device
+    normalize_scan(scan, device, scale, outliers)   enqueue the whole-scan z-score; the float32 volume stays on the device
+    resample_grid(shape, affine, spacing)  the output grid of a resampling (numpy fp64, host only); resample_tables(...) its per-axis tables
+    resample_pair(scan, mask, device, spacing)      enqueue the resampling -> (float32 scan with the new affine, uint8 mask)
     python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] [--glszm]
-                                     [--mesh_shape] [--log_sigma 1,3 [--log_bin_width B]] --out radiomics.csv
+                                     [--mesh_shape] [--log_sigma 1,3 [--log_bin_width B]] [--normalize [--normalize_scale S]
+                                     [--normalize_outliers K]] [--resample_spacing 1,1,1] --out radiomics.csv
 
 Upstream reads such a csv (`Data: rad_loc`, data/RadiomicsDatasets.py) and leaves its extraction to PyRadiomics; here the table is built
 from the very pair the image path ingests, through the same mask routes (NIfTI mask, resampled mask, DICOM mask series, RTSTRUCT, SEG:
@@ -47,6 +52,18 @@ follow every `original_*` one: 41 per sigma by default, 92 with all classes and 
 in tests/_radiomics_log_ref.py, bit for bit, and that one to scipy's `gaussian_filter`; **parity with PyRadiomics is unpinned**: its LoG
 is ITK's recursive (IIR) Gaussian, this one a sampled FIR truncated at 4 sigma.
 
+`normalize` and `resample` (`Radiomics: normalize: true | {scale: 100, outliers: 3}`, `--normalize`; `Radiomics: resample: {spacing:
+[1, 1, 1]}`, `--resample_spacing 1,1,1`; both off by default) are two pre-steps in PyRadiomics' order.  They are settings, not image
+types: no column is added or renamed, only the values change, and with both off nothing changes at all.  `normalize` replaces the scan
+by (v - mean) / sd * scale with the mean and sd of the WHOLE scan (`normalize_scan`; `outliers: k` clamps to +-k scale).  The default
+scale is 100, not PyRadiomics' 1: with the default `bin_width` of 25 a scale of 1 would put every voxel into one bin.  `resample` brings
+scan and mask onto a grid of the stated spacing in mm (`resample_pair`: cubic B-spline for the scan, nearest neighbour for the mask;
+an entry of 0 keeps that axis; the corner of the first voxel is kept), so that "distance 1" of the texture classes, the LoG taps, the
+shape moments and the mesh all see the new grid and its affine.  Without them every texture feature is computed in voxel index space on
+the scanner's own grid and in its own intensity units.  Both are pinned to the numpy restatement in tests/_radiomics_resample_ref.py,
+bit for bit, and that one to scipy's `spline_filter` / `map_coordinates`; **parity with PyRadiomics is unpinned**: it is not installed
+here, its B-spline is ITK's, and it crops the resampled grid to the ROI's bounding box plus padding where this resamples the whole scan.
+
 STAGES states each call once -- its C symbol, buffers, switch, unpacking and columns -- and `extract`, `finish`, `feature_names` and
 `features_of` all read it; `enqueue(result, stage, desc, stream)` makes one call into the buffers a result already has.  One read-back
 brings every result block to the host, stacked per image (the original, then each filtered one, sigma ascending): the first call's block,
@@ -58,7 +75,7 @@ import ctypes
 import logging
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -96,6 +113,8 @@ MESH_SHAPE = ("MeshVolume", "SurfaceArea", "SurfaceVolumeRatio", "Sphericity", "
 TEXTURE_CLASSES = ("glrlm", "gldm", "ngtdm")
 _TEXTURE = {"glrlm": GLRLM, "gldm": GLDM, "ngtdm": NGTDM}
 LOG_TRUNCATE = 4.0
+DEFAULT_NORMALIZE_SCALE = 100.0
+RESAMPLE_ENTRY = np.dtype([("w", "<f8", (4,)), ("i", "<i4", (4,)), ("nearest", "<i4"), ("inside", "<i4")])   # mmnn_resample_entry
 _logged_identity = False
 _logged_unit_spacing = False
 
@@ -166,7 +185,11 @@ class RadiomicsResult:
     that was enqueued with the call (the scan's, the identity without an affine).  With `log_sigma`: `log`, a tuple of (sigma, the
     RadiomicsResult of the image filtered at sigma); such a result has `image` set to its image type, `bin_width` the filtered images'
     and `filtered`, the DeviceVolume `log_filter` returned (float32, on the scan's grid), beside `filter_taps`, the taps on the device;
-    `filter_workspace`, which the scales of one extraction share, is on the original image's result."""
+    `filter_workspace`, which the scales of one extraction share, is on the original image's result.  With the pre-steps: `normalize`,
+    the (scale, outliers) in force, `normalized`, the DeviceVolume `normalize_scan` returned, and `normalize_block`, the bytes of
+    mmnn_normalize_result; `resample`, the requested spacing, `resampled`, the (scan, mask) DeviceVolumes `resample_pair` returned (None
+    when every ratio is 1 and the step was skipped), and `resample_tables`, the tables on the device; `pre_workspace`, which the two
+    steps share; `source_shape`, the extents before the pre-steps.  `shape` and `affine` are then the resampled grid's."""
     block: torch.Tensor
     hist: torch.Tensor
     glcm: torch.Tensor
@@ -198,6 +221,14 @@ class RadiomicsResult:
     filtered: Optional[object] = None
     filter_taps: Optional[torch.Tensor] = None
     filter_workspace: Optional[torch.Tensor] = None
+    normalize: Optional[tuple] = None
+    normalized: Optional[object] = None
+    normalize_block: Optional[torch.Tensor] = None
+    resample: Optional[tuple] = None
+    resampled: Optional[tuple] = None
+    resample_tables: Optional[torch.Tensor] = None
+    pre_workspace: Optional[torch.Tensor] = None
+    source_shape: Optional[tuple] = None
 
 
 def _bytes_or_raise(symbol: str, *extents) -> int:
@@ -301,9 +332,263 @@ def _enqueue_log_filter(scan, sigma_mm, out, workspace, taps):
     return ingest.DeviceVolume(out.view(torch.uint8), (x, y, z), 16, 0.0, 0.0, scan.affine), workspace, taps
 
 
+def normalize_settings(normalize) -> Optional[Tuple[float, float]]:
+    """`normalize` (None / False, True, a mapping of `scale` and `outliers`, or the pair) -> None or (scale, outliers): the scale is 100
+    and outliers 0 (no clamp) when not given."""
+    if normalize is None or normalize is False:
+        return None
+    if normalize is True:
+        normalize = {}
+    if isinstance(normalize, (list, tuple)) and len(normalize) == 2:
+        normalize = {"scale": normalize[0], "outliers": normalize[1]}
+    valid = ("radiomics: normalize must be true / false or a mapping of `scale` (a positive finite number, default 100) and `outliers` "
+             "(a finite number >= 0; 0: no clamp)")
+    if not isinstance(normalize, dict) or set(normalize) - {"scale", "outliers"}:
+        raise ConfigurationError(f"{valid}, got {normalize!r}")
+    out = []
+    for key, default in (("scale", DEFAULT_NORMALIZE_SCALE), ("outliers", 0.0)):
+        v = normalize.get(key)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0.0 or (key == "scale" and v == 0.0):
+            raise ConfigurationError(f"{valid}, got {key} {v!r}")
+        out.append(float(v))
+    return tuple(out)
+
+
+def resample_spacing(resample) -> Optional[Tuple[float, float, float]]:
+    """`resample` (None, one number, three numbers, a comma-separated string, or a mapping of `spacing`) -> None or the requested
+    spacing along x, y, z in mm; an entry of 0 keeps that axis."""
+    if resample is None or resample is False:
+        return None
+    valid = "radiomics: resample spacing must be one number or three (mm, finite, >= 0; 0 keeps that axis)"
+    if isinstance(resample, dict):
+        if set(resample) != {"spacing"}:
+            raise ConfigurationError(f"radiomics: resample must be a mapping of `spacing` alone, got {resample!r}")
+        resample = resample["spacing"]
+    if isinstance(resample, str):
+        resample = [v for v in resample.replace(",", " ").split() if v]
+    elif isinstance(resample, (int, float)) and not isinstance(resample, bool):
+        resample = [resample]
+    if not isinstance(resample, (list, tuple, np.ndarray)) or len(resample) not in (1, 3):
+        raise ConfigurationError(f"{valid}, got spacing {resample!r}")
+    out = []
+    for v in resample:
+        try:
+            f = math.nan if isinstance(v, bool) else float(v)
+        except (TypeError, ValueError):
+            f = math.nan
+        if not (math.isfinite(f) and f >= 0.0):
+            raise ConfigurationError(f"{valid}, got spacing {v!r}")
+        out.append(f)
+    return tuple(out * 3) if len(out) == 1 else tuple(out)
+
+
+class ResampleGrid(NamedTuple):
+    """`resample_grid`'s result: `shape`, the output extents; `ratio`, r_a = requested / present spacing per axis; `affine`, the output
+    grid's voxel index -> mm matrix; `skip`: every ratio is 1, nothing is to be done."""
+    shape: Tuple[int, int, int]
+    ratio: np.ndarray
+    affine: np.ndarray
+    skip: bool
+
+
+def resample_grid(shape, affine, spacing) -> ResampleGrid:
+    """The grid a scan of extents `shape` and voxel index -> mm matrix `affine` (None: the identity) is resampled onto at the requested
+    `spacing` (one number or three, mm; 0 keeps that axis).  numpy fp64, host only.  Per axis a, with n_a the extent, s_a the present
+    spacing (`spacing_of`), q_a the requested one and r_a = q_a / s_a:
+        m_a = max(1, ceil(n_a s_a / q_a - 2^-20))        the output extent
+        c_a(j) = (j + 0.5) r_a - 0.5                     the old continuous index of new voxel j: the corner of the first voxel is kept
+        A' = A with column a scaled by r_a, translation t + L (0.5 r - 0.5)
+    A new voxel is outside (scan 0.0, mask 0) when c_a < -0.5 or c_a >= n_a - 0.5 on any axis, which happens on the last plane of an
+    axis when m_a r_a - n_a > 0.5 r_a.  This is the whole scan's grid, not the ROI's bounding box."""
+    q = resample_spacing(spacing)
+    if q is None:
+        raise ConfigurationError(f"radiomics: resample spacing must be given, got {spacing!r}")
+    n = np.array([int(v) for v in shape], dtype=np.float64)
+    s = np.array(spacing_of(affine), dtype=np.float64)
+    if not (np.isfinite(s).all() and (s > 0.0).all()):
+        raise ConfigurationError(f"radiomics: resample spacing {q}: the scan's own spacing {tuple(s)} is not positive and finite")
+    q = np.where(np.array(q) == 0.0, s, np.array(q, dtype=np.float64))
+    r = q / s
+    m = np.maximum(1.0, np.ceil(n * s / q - 2.0 ** -20))
+    # the output grid and the two intermediates of `mmnn_resample_pair` ([z][y][mx] and [z][my][mx]) must each stay below 2^31 elements
+    if max(float(np.prod(m)), float(m[0] * n[1] * n[2]), float(m[0] * m[1] * n[2])) >= 2.0 ** 31:
+        raise ConfigurationError(f"radiomics: resample spacing {tuple(q)} mm turns the scan of {tuple(int(v) for v in n)} voxels at "
+                                 f"{tuple(s)} mm into {tuple(int(v) for v in m)}: 2^31 voxels or more in the output or in an intermediate "
+                                 "of the separable passes")
+    A = np.eye(4) if affine is None else np.array(affine, dtype=np.float64)
+    if A.shape == (3, 3):
+        A = np.block([[A, np.zeros((3, 1))], [np.zeros((1, 3)), np.ones((1, 1))]])
+    out = A.copy()
+    out[:3, :3] = A[:3, :3] * r[None, :]
+    out[:3, 3] = A[:3, 3] + A[:3, :3] @ (0.5 * r - 0.5)
+    return ResampleGrid(tuple(int(v) for v in m), r, out, bool((r == 1.0).all()))
+
+
+def resample_tables(shape, grid: ResampleGrid) -> np.ndarray:
+    """The per-axis tables of `mmnn_resample_pair` for a scan of extents `shape` and the grid of `resample_grid`: a structured array
+    (RESAMPLE_ENTRY, 56 bytes per entry) of the x axis' entries, then y's, then z's.  Entry j of an axis of extent n: c = (j + 0.5) r -
+    0.5, f = floor(c), t = c - f; `i`: mirror(f - 1 + k), k = 0..3, whole-sample symmetric with period 2 n - 2 (0 for n = 1); `w`: the
+    cubic B-spline weights (1-t)^3/6, 2/3 - t^2 (2-t)/2, 2/3 - (1-t)^2 (1+t)/2, t^3/6; `nearest`: clamp(floor(c + 0.5), 0, n - 1);
+    `inside`: not (c < -0.5 or c >= n - 0.5)."""
+    parts = []
+    for n, m, r in zip(shape, grid.shape, grid.ratio):
+        n = int(n)
+        c = (np.arange(m, dtype=np.float64) + 0.5) * float(r) - 0.5
+        f = np.floor(c)
+        t, u = c - f, 1.0 - (c - f)
+        e = np.zeros(m, dtype=RESAMPLE_ENTRY)
+        i = f.astype(np.int64)[:, None] - 1 + np.arange(4)[None, :]
+        if n == 1:
+            i[:] = 0
+        else:
+            i = np.mod(i, 2 * n - 2)
+            i = np.where(i < n, i, 2 * n - 2 - i)
+        e["i"] = i
+        e["w"] = np.stack([u * u * u / 6.0, 2.0 / 3.0 - t * t * (2.0 - t) / 2.0, 2.0 / 3.0 - u * u * (1.0 + t) / 2.0, t * t * t / 6.0], axis=1)
+        e["nearest"] = np.clip(np.floor(c + 0.5), 0, n - 1).astype(np.int64)
+        e["inside"] = ~((c < -0.5) | (c >= n - 0.5))
+        parts.append(e)
+    return np.concatenate(parts)
+
+
+def resample_constants() -> dict:
+    """What the prefilter's recursion takes from the descriptor: the pole z = sqrt(3) - 2, z / (z^2 - 1), the gain 6 and z^k for k below
+    the horizon."""
+    z = math.sqrt(3.0) - 2.0
+    return {"pole": z, "pole_gain": z / (z * z - 1.0), "gain": 6.0, "pole_power": np.array([z ** k for k in range(_lib.RESAMPLE_HORIZON)])}
+
+
+def normalize_scan(scan, device, scale: float = DEFAULT_NORMALIZE_SCALE, outliers: float = 0.0, out: Optional[torch.Tensor] = None,
+                   block: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Enqueue `mmnn_normalize_scan` on the current stream of `device`: `scan` (whatever `ingest.upload` takes) becomes
+    (v - mean) / sd * scale with the mean and the sd (divisor n - 1) of the whole scan, clamped to +-outliers * scale when `outliers` > 0.
+    Returns (a DeviceVolume of float32 (NIfTI code 16) with slope 0 and the scan's affine, the device's result block -- n, mean, sd,
+    nonfinite: `unpack_normalize` -- which stays there).  `out`: x * y * z contiguous float32 on the device; `block`:
+    NORMALIZE_RESULT_BYTES of uint8; `workspace`: at least `mmnn_normalize_scan_workspace_bytes` of uint8.  Each is allocated when None."""
+    from .data import ingest
+    settings = normalize_settings({"scale": scale, "outliers": outliers})
+    return _enqueue_normalize(ingest.upload(scan, torch.device(device)), settings, out, block, workspace)[:2]
+
+
+def unpack_normalize(raw: np.ndarray) -> dict:
+    """The bytes of mmnn_normalize_result -> its fields."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    return {"n": int(raw[:8].view(np.int64)[0]), "mean": float(raw[8:16].view(np.float64)[0]), "sd": float(raw[16:24].view(np.float64)[0]),
+            "nonfinite": bool(raw[24:32].view(np.int64)[0])}
+
+
+def _device_buffer(out, n, dev, what, dtype=torch.float32):
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=dev)
+    if not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and out.numel() == n and out.device == dev):
+        raise ValueError(f"{what}: out must be {n} contiguous {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}: the "
+                         "extents differ from those the buffers were made for")
+    return out
+
+
+def _workspace(workspace, nbytes, dev, what):
+    if workspace is None:
+        workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f"{what}: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, {nbytes} needed on {dev}")
+    return workspace
+
+
+def _enqueue_normalize(scan, settings, out, block, workspace):
+    """`normalize_scan` on an uploaded scan -> (the normalised DeviceVolume, the result block, the workspace)."""
+    from .data import ingest
+    dev = scan.data.device
+    x, y, z = scan.shape
+    nbytes = _bytes_or_raise("mmnn_normalize_scan_workspace_bytes", x, y, z)
+    out = _device_buffer(out, x * y * z, dev, "normalize_scan")
+    block = _device_buffer(block, _lib.NORMALIZE_RESULT_BYTES, dev, "normalize_scan (result block)", torch.uint8)
+    workspace = _workspace(workspace, nbytes, dev, "normalize_scan")
+    desc = _lib.NormalizeDesc(x, y, z, scan.datatype, float(scan.slope), float(scan.inter), settings[0], settings[1])
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mmnn_normalize_scan(ctypes.byref(desc), scan.data.data_ptr(), out.data_ptr(), block.data_ptr(), workspace.data_ptr(),
+                                                  stream), "mmnn_normalize_scan")
+    return ingest.DeviceVolume(out.view(torch.uint8), (x, y, z), 16, 0.0, 0.0, scan.affine), block, workspace
+
+
+def resample_workspace_bytes(shape, out_shape) -> int:
+    return _bytes_or_raise("mmnn_resample_pair_workspace_bytes", *shape, *out_shape)
+
+
+def resample_pair(scan, mask, device, spacing, index_map=None, threshold: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                  out_mask: Optional[torch.Tensor] = None, tables: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Enqueue `mmnn_resample_pair` on the current stream of `device`: the pair (whatever `ingest.prepare_pair` takes) is brought onto
+    the grid `resample_grid` gives for `spacing`, the scan by cubic B-spline interpolation, the mask by nearest neighbour.  Returns two
+    DeviceVolumes with the new affine: float32 (NIfTI code 16, slope 0) and uint8 (0 / 1).  When every ratio is 1 the prepared pair is
+    returned as it is.  `out` / `out_mask`: contiguous float32 / uint8 tensors of the output's voxel count; `tables`: uint8 of 56 bytes
+    per entry to upload the tables into; `workspace`: at least `resample_workspace_bytes` of uint8.  Each is allocated when None."""
+    from .data import ingest
+    scan, mask = ingest.prepare_pair(scan, mask, torch.device(device), index_map, threshold, what="radiomics")
+    grid = resample_grid(scan.shape, scan.affine, spacing)
+    if grid.skip:
+        return scan, mask
+    return _enqueue_resample(scan, mask, grid, out, out_mask, tables, workspace)[:2]
+
+
+def _enqueue_resample(scan, mask, grid, out, out_mask, tables, workspace):
+    """`resample_pair` on a prepared pair -> (the scan's DeviceVolume, the mask's, the tables on the device, the workspace)."""
+    from .data import ingest
+    dev = scan.data.device
+    (x, y, z), (mx, my, mz) = scan.shape, grid.shape
+    host = resample_tables(scan.shape, grid)
+    nbytes = resample_workspace_bytes(scan.shape, grid.shape)
+    out = _device_buffer(out, mx * my * mz, dev, "resample_pair")
+    out_mask = _device_buffer(out_mask, mx * my * mz, dev, "resample_pair (mask)", torch.uint8)
+    tables = _device_buffer(tables, host.nbytes, dev, "resample_pair (tables)", torch.uint8)
+    workspace = _workspace(workspace, nbytes, dev, "resample_pair")
+    tables.copy_(torch.from_numpy(host.view(np.uint8)))
+    k = resample_constants()
+    desc = _lib.ResampleDesc(x, y, z, mx, my, mz, scan.datatype, mask.datatype, float(scan.slope), float(scan.inter), float(mask.slope),
+                             float(mask.inter), k["pole"], k["pole_gain"], k["gain"], (ctypes.c_double * _lib.RESAMPLE_HORIZON)(*k["pole_power"].tolist()))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mmnn_resample_pair(ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), host.ctypes.data, tables.data_ptr(),
+                                                 out.data_ptr(), out_mask.data_ptr(), workspace.data_ptr(), stream), "mmnn_resample_pair")
+    return (ingest.DeviceVolume(out.view(torch.uint8), grid.shape, 16, 0.0, 0.0, grid.affine),
+            ingest.DeviceVolume(out_mask, grid.shape, 2, 1.0, 0.0, grid.affine), tables, workspace)
+
+
+def _pre_steps(scan, mask, norm, spacing, buffers):
+    """The pre-steps of one extraction on the prepared pair, in PyRadiomics' order: normalise, then resample.  Returns the pair the calls
+    are to see and what the result records of the steps: {RadiomicsResult attribute: value}, empty with both off."""
+    old = None if buffers is None else (buffers.normalize, buffers.resample, buffers.source_shape)
+    if old is not None and old != (norm, spacing, tuple(scan.shape) if norm or spacing else None):
+        raise ValueError(f"radiomics: buffers of the pre-steps normalize {old[0]}, resample {old[1]} on a scan of {old[2]} cannot take an "
+                         f"extraction with normalize {norm}, resample {spacing} on a scan of {tuple(scan.shape)}")
+    if not (norm or spacing):
+        return scan, mask, {}
+    rec = {"normalize": norm, "resample": spacing, "source_shape": tuple(scan.shape)}
+    grid = None if spacing is None else resample_grid(scan.shape, scan.affine, spacing)
+    grid = None if grid is None or grid.skip else grid
+    if buffers is not None:
+        ws = buffers.pre_workspace
+    else:
+        need = max(_bytes_or_raise("mmnn_normalize_scan_workspace_bytes", *scan.shape) if norm else 0,
+                   resample_workspace_bytes(scan.shape, grid.shape) if grid is not None else 0)
+        ws = torch.empty(need, dtype=torch.uint8, device=scan.data.device) if need else None
+    rec["pre_workspace"] = ws
+    if norm:
+        prev = None if buffers is None else buffers.normalized.data.view(torch.float32)
+        scan, rec["normalize_block"], _ = _enqueue_normalize(scan, norm, prev, None if buffers is None else buffers.normalize_block, ws)
+        rec["normalized"] = scan
+    if grid is not None:
+        if buffers is not None and buffers.resampled is None:
+            raise ValueError(f"radiomics: buffers of a skipped resampling (every ratio 1) cannot take one onto {grid.shape}")
+        prev = (None, None, None) if buffers is None else (buffers.resampled[0].data.view(torch.float32), buffers.resampled[1].data, buffers.resample_tables)
+        scan, mask, rec["resample_tables"], _ = _enqueue_resample(scan, mask, grid, *prev, ws)
+        rec["resampled"] = (scan, mask)
+    return scan, mask, rec
+
+
 def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS, index_map=None,
             threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=(), glszm: bool = False,
-            mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None) -> RadiomicsResult:
+            mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None) -> RadiomicsResult:
     """Enqueue the extraction of one (scan, mask) pair on the current stream of `device`.  `scan` / `mask`: whatever `ingest_volume`
     takes (host volumes are uploaded; a contour, SEG or other-grid mask is brought onto the scan's grid first, `index_map` and
     `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again.  `classes`:
@@ -312,14 +597,19 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
     identity without one), which the result remembers.  `log_sigma`: LoG scales in mm; behind the original image's calls, for each sigma
     ascending, `log_filter` and then the same calls but the mesh one on the filtered volume, under the same prepared mask and binned at
     `log_bin_width` (None: `bin_width`); the results are `RadiomicsResult.log`.  `buffers` must then come from an extraction with the
-    same scales."""
+    same scales.  `normalize` (`normalize_settings`) and `resample` (`resample_spacing`): the pre-steps, enqueued in this order behind
+    `ingest.prepare_pair` and ahead of every call, which then see the new pair and its affine; `buffers` must come from an extraction with
+    the same settings on the same extents.  With both None nothing is enqueued or allocated for them."""
     from .data import ingest
     dev = torch.device(device)
     scan, mask = ingest.prepare_pair(scan, mask, dev, index_map, threshold, what="radiomics")
     classes, sigmas = texture_classes(classes), log_sigmas(log_sigma)
     if buffers is not None and tuple(s for s, _ in buffers.log) != sigmas:
         raise ValueError(f"radiomics: buffers of the LoG scales {tuple(s for s, _ in buffers.log)} cannot take an extraction at {sigmas}")
+    scan, mask, pre = _pre_steps(scan, mask, normalize_settings(normalize), resample_spacing(resample), buffers)
     out = _extract_image(scan, mask, bin_width, max_bins, buffers, classes, glszm, mesh)
+    for k, v in pre.items():
+        setattr(out, k, v)
     if sigmas:
         out.filter_workspace = None if buffers is None else buffers.filter_workspace
         subs = []
@@ -525,17 +815,20 @@ FEATURE_NAMES = _first_names("original")
 
 
 def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional[dict] = None, classes=(), zones: Optional[dict] = None,
-                mesh: Optional[dict] = None, image: str = "original") -> Dict[str, float]:
+                mesh: Optional[dict] = None, image: str = "original", normalized: bool = False) -> Dict[str, float]:
     """The host half of `finish`, from the unpacked block (and, with `classes`, the unpacked texture block; with `zones`, the unpacked
     size-zone block; with `mesh`, the unpacked mesh block, whose area and diameters were computed under the linear part of `affine`).
-    `image`: the image type that prefixes the columns; a filtered one has no shape columns and is named in what a flag raises."""
+    `image`: the image type that prefixes the columns; a filtered one has no shape columns and is named in what a flag raises.
+    `normalized`: the scan went through `normalize`, which the non-finite flag's message then names."""
     global _logged_identity
     if image != "original":
         what = f"{what}, image type {image}"
     if fields["empty"]:
         raise ConfigurationError(f"{what}: the mask selects no voxel of the scan")
     if fields["nonfinite"]:
-        raise ConfigurationError(f"{what}: a NaN or infinite voxel value lies inside the mask")
+        raise ConfigurationError(f"{what}: a NaN or infinite voxel value lies inside the mask" + (
+            " (with `normalize` on -- Radiomics: normalize, --normalize -- a NaN or infinite voxel anywhere in the scan, or a constant scan "
+            "of an integer type, makes every normalised value NaN)" if normalized else ""))
     if fields["overflow"]:
         raise ConfigurationError(f"{what}: the values inside the mask span {fields['n_bins']} bins, more than max_bins: choose a larger "
                                  + ("bin_width (Radiomics: bin_width)" if image == "original" else
@@ -579,7 +872,7 @@ def _features_of_stacked(raw: np.ndarray, r: RadiomicsResult, affine, what: str)
         off += st.nbytes
     out = {}
     for q, f in unpacked.values():
-        out.update(features_of(f.pop("first"), affine, what, classes=q.classes, image=q.image, **f))
+        out.update(features_of(f.pop("first"), affine, what, classes=q.classes, image=q.image, normalized=r.normalize is not None, **f))
     return out
 
 
@@ -600,12 +893,12 @@ def _volumes_of(dataset, patient):
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
                  mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False,
-                 mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None) -> List[dict]:
+                 mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
     A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
     blocks, with `glszm` the size-zone blocks, with `mesh` the mesh blocks and with `log_sigma` the filtered images' blocks, come back in
-    the batch's same stacked read-back."""
+    the batch's same stacked read-back.  `normalize` / `resample`: the pre-steps of `extract`; they add nothing to the read-back."""
     from .data import ingest
     dev = torch.device(device)
     classes, log_sigma = texture_classes(classes), log_sigmas(log_sigma)
@@ -617,7 +910,7 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
         res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm, mesh=mesh,
-                        log_sigma=log_sigma, log_bin_width=log_bin_width)
+                        log_sigma=log_sigma, log_bin_width=log_bin_width, normalize=normalize, resample=resample)
                 for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
         blocks = torch.stack([_stacked(r) for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
@@ -668,7 +961,19 @@ def read_csv(path):
         return cols, [r for r in rd if r]
 
 
-def main(argv=None):
+def add_pre_step_arguments(ap) -> None:
+    """The command-line switches of the two pre-steps, which main.py and this module's tool share."""
+    ap.add_argument("--normalize", action="store_true", help="with --radiomics and no --rad_loc: z-score the whole scan before the extraction "
+                    "((v - mean) / sd * scale); also switched on by the config's `Radiomics: normalize`, or by either of the two values below")
+    ap.add_argument("--normalize_scale", type=float, default=None, help="what the z-score is multiplied by; overrides `Radiomics: normalize: "
+                    "scale` (default 100: with the default bin width of 25 PyRadiomics' scale of 1 would put every voxel into one bin)")
+    ap.add_argument("--normalize_outliers", type=float, default=None, help="clamp the normalised values to +-K scale; overrides `Radiomics: "
+                    "normalize: outliers` (default 0: no clamp)")
+    ap.add_argument("--resample_spacing", type=str, default=None, help="resample scan and mask to this voxel spacing in mm before the "
+                    "extraction, one number or three comma-separated (1,1,1; 0 keeps an axis); overrides `Radiomics: resample: spacing`")
+
+
+def build_arg_parser():
     ap = argparse.ArgumentParser(description="Extract radiomic features of every patient of an image tree on the device.")
     ap.add_argument("--image_loc", required=True)
     ap.add_argument("--key_loc", required=True)
@@ -686,7 +991,12 @@ def main(argv=None):
                     "log-sigma-<sigma>-mm-3D_* columns of every scale; overrides the config's `Radiomics: log: sigma`")
     ap.add_argument("--log_bin_width", type=float, default=None, help="bin width of the filtered images; overrides the config's "
                     "`Radiomics: log: bin_width` (default: the original image's bin width)")
-    a = ap.parse_args(argv)
+    add_pre_step_arguments(ap)
+    return ap
+
+
+def main(argv=None):
+    a = build_arg_parser().parse_args(argv)
     import os
     from .data.ImageDatasets import ImageDataset
     from .parser.parser import Parser
@@ -696,6 +1006,8 @@ def main(argv=None):
     glszm = a.glszm or parser.radiomicsZones()
     mesh = a.mesh_shape or parser.radiomicsMesh()
     log = parser.radiomicsLog(a.log_sigma, a.log_bin_width)
+    normalize = parser.radiomicsNormalize(a.normalize, a.normalize_scale, a.normalize_outliers)
+    resample = parser.radiomicsResample(a.resample_spacing)
     data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
@@ -705,7 +1017,7 @@ def main(argv=None):
             for d in dirs]
     rows = extract_modalities(sets, a.device, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
                               data.get("mask_threshold"), classes=classes, glszm=glszm, mesh=mesh, log_sigma=log["sigma"],
-                              log_bin_width=log["bin_width"])
+                              log_bin_width=log["bin_width"], normalize=normalize, resample=resample)
     write_csv(a.out, rows)
     print(f"{len(rows)} patients, {len(rows[0]) - 1 if rows else 0} features -> {a.out}")
 
