@@ -90,13 +90,18 @@ int mmnn_densenet_read_timer_class(void* plan, int32_t kernel_class, int32_t blo
  * for the cross-workgroup hand-off).  "single_stream" (any value): accepted and ignored -- the backward always runs on the caller's
  * stream (it once selected between that and side streams for the weight gradients).  "params_version" (any non-zero
  * number the caller changes whenever it changed a parameter; 0 = unknown, the default): the forward re-packs the weights only
- * when the version, the parameter buffer or the workspace differs from the last packed one. */
+ * when the version, the parameter buffer or the workspace differs from the last packed one.  "conv1_dgrad_resident" (0 / 1 / 2, default 1):
+ * which dense-layer conv1 data gradients run on the resident-operand kernel (csrc/conv1_dgrad.hip) instead of the general convolution
+ * template -- 0 none, 1 the launches where it measured faster (bottleneck width 128, voxel count a multiple of 4, at least 512 voxels per
+ * sample in at most 512 tiles of 64 voxels per batch), 2 every launch the kernel can run (tests, measurements). */
 int mmnn_densenet_set_option(void* plan, const char* name, int64_t value);
 /* nn.BatchNorm3d.num_batches_tracked of every BN of the backbone (module order, int64 [runstat_count / 2 channels ... one per BN]): when set
  * (non-NULL device pointer to `bn_count` int64 values), every training forward adds 1 to each of them in its running-statistics kernel;
  * NULL (the default) leaves the counters to the caller. */
 int mmnn_densenet_set_batch_counters(void* plan, int64_t* num_batches_tracked, int32_t bn_count);
-/* byte offset of a named workspace region (tests / GradCAM): "x","g","t1","conv0","st_x",... ; -1 if unknown */
+/* byte offset of a named workspace region (tests / GradCAM): "x","g","t1","conv0","st_x",... ; -1 if unknown.  Names that start with '#'
+ * are counters, not offsets: e.g. "#conv1_dgrad_resident" with i = dense block returns how many layers of that block take the
+ * resident-operand conv1 data gradient under the current "conv1_dgrad_resident" option. */
 int64_t mmnn_densenet_ws_offset(const void* plan, const char* name, int32_t i, int32_t j);
 
 /* ---- DenseNet.features: ReLU -> AdaptiveAvgPool3d(1) -> flatten -> Linear -> Dropout (models/densenet.py:234-247) ---- */

@@ -335,6 +335,7 @@ static FpropArgs block_args(const Plan& p, char* ws, int b) {
   a.N = p.N; a.D = p.Db[b]; a.H = p.Hb[b]; a.W = p.Wb[b]; a.nrep = p.nrep_b[b];
   a.kz_part = p.no_kz ? nullptr : fptr(ws, p.o_kz_part); a.kz_cnt = reinterpret_cast<unsigned*>(ws + p.o_kz_cnt);
   a.kz_part_bytes = KZ_PART_BYTES; a.kz_cnt_entries = KZ_CNT_ENTRIES;
+  a.conv1_dgrad_resident = p.conv1_dgrad_resident;
   a.trace = trace_slot(p);
   return a;
 }
@@ -470,6 +471,11 @@ int plan_set_option(Plan& p, const char* name, long value) {
   if (s == "trace_slots") { p.trace_slots = (int)value; return 0; }
   if (s == "params_version") { p.params_version = value; return 0; }
   if (s == "no_kz") { p.no_kz = value != 0; return 0; }
+  if (s == "conv1_dgrad_resident") {
+    MMNN_REQUIRE(value >= 0 && value <= 2, "set_option: conv1_dgrad_resident is 0, 1 or 2");
+    p.conv1_dgrad_resident = (int)value;
+    return 0;
+  }
   set_error("set_option: unknown option '%s'", s.c_str());
   return 1;
 }
@@ -851,6 +857,12 @@ long plan_ws_offset(const Plan& p, const char* name, int i, int j) {
   if (s == "#pack_launches") return p.pack_launches;      // counter, not an offset (tests)
   if (s == "#ns_c2" && okl(i, j)) return p.ns_c2[i][j];   // voxel splits of the layer's weight-gradient launches (tests)
   if (s == "#ns_c1" && okl(i, j)) return p.ns_c1[i][j];
+  if (s == "#conv1_dgrad_resident" && okb(i)) {   // layers of block i whose conv1 data gradient takes the resident-operand kernel (tests)
+    long cnt = 0;
+    for (int l = 0; l < p.cfg.block_layers[i]; ++l)
+      cnt += conv1_dgrad_resident_shape_ok(p.conv1_dgrad_resident, p.N, p.Vb[i], p.mid, p.layers[i][l].cin, p.layers[i][l].cin) ? 1 : 0;
+    return cnt;
+  }
   return -1;
 }
 

@@ -95,6 +95,7 @@ struct Plan {
   long params_version = 0, packed_version = 0; const float* packed_params = nullptr; const char* packed_ws = nullptr;   // option "params_version"
   long pack_launches = 0;
   long long* nbt = nullptr; int nbt_count = 0;     // mmnn_densenet_set_batch_counters
+  int conv1_dgrad_resident = 1;                    // option "conv1_dgrad_resident": FpropArgs::conv1_dgrad_resident of every conv1 data gradient
   bool no_kz = false;                              // option "no_kz": no cross-workgroup K-split (tests)
   int bwd_next = -1;                               // plan_backward_range: the block the next partial call must start at
   unsigned long long* trace_base = nullptr; mutable int trace_seq = 0; int trace_slots = 0;   // developer aid: per-launch phase stamps

@@ -31,6 +31,11 @@ int launch_fprop(const FpropArgs& a, int taps, int pro, int epi, hipStream_t str
   MMNN_REQUIRE((epi != EPI_MASK_STORE && epi != EPI_MASK_ACCUM) || (a.ex && a.dgamma && a.dbeta), "fprop: mask epilogue operands missing");
   if (taps == 27 && pro == PRO_BNRELU && epi == EPI_STORE_STATS && conv3_fwd_bf16x3_eligible(a)) return launch_conv3_fwd_bf16x3(a, stream);
   if (taps == 27 && pro == PRO_GRAD && epi == EPI_MASK_STORE && conv3_dgrad_bf16x3_eligible(a)) return launch_conv3_dgrad_bf16x3(a, stream);
+  // conv1 data gradient with the normalised operand tile resident in LDS (conv1_dgrad.hip): Cin = 128, V and M multiples of 4, 16-byte
+  // aligned tensors, and -- plan option "conv1_dgrad_resident" = 1, the default -- only the launches where it measured faster than the
+  // tile table below: 512 <= V and at most 512 voxel tiles of 64, i.e. the 8^3 and 16^3 blocks of the 2 x 128^3 step (11.9 -> 9.3 and
+  // 23.2 -> 18.6 us per launch), not 4^3 (7.0 -> 8.7 us) and not 32^3 (60.5 -> 67.4 us).  The numbers per layer: conv1_dgrad_resident_shape_ok.
+  if (taps == 1 && pro == PRO_GRAD && epi == EPI_MASK_ACCUM && conv1_dgrad_resident_eligible(a)) return launch_conv1_dgrad_resident(a, stream);
 #define MMNN_CASE(T, P, E) \
   if (taps == T && pro == P && epi == E) return dispatch<T, P, E>(a, stream);
   MMNN_CASE(1, PRO_BNRELU, EPI_STORE_STATS)    // dense-layer conv1 forward

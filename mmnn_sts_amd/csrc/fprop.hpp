@@ -54,6 +54,7 @@ struct FpropArgs {
   double* dgamma; double* dbeta;                 // [NREP][M]
   StatPtr s_acc;
   int nrep;                                      // replicas this launch's epilogue spreads its fp64 atomics over (0: NREP); see StatPtr::nrep
+  int conv1_dgrad_resident;                      // plan option of the same name (conv1_dgrad.hip): 0 never, 1 where it measured faster, 2 wherever it can run
   // cross-block K-split (gridDim.z slices of the channel axis): partial tiles + per-tile arrival counters (zero on entry)
   float* kz_part; unsigned* kz_cnt;
   size_t kz_part_bytes; unsigned kz_cnt_entries;   // capacity of kz_part / kz_cnt as provided by the caller (the split is skipped when it would not fit)
@@ -79,6 +80,10 @@ int launch_fprop(const FpropArgs& a, int taps, int pro, int epi, hipStream_t str
 bool conv3_fwd_bf16x3_eligible(const FpropArgs& a);
 bool conv3_dgrad_bf16x3_eligible(const FpropArgs& a);
 size_t conv3_bf16x3_plane_bytes(const FpropArgs& a);
+// conv1_dgrad.hip: the dense-layer conv1 data gradient (1x1x1, PRO_GRAD, EPI_MASK_ACCUM) with the normalised operand tile resident in LDS
+bool conv1_dgrad_resident_shape_ok(int mode, int N, long V, int Cin, int M, int w_ld);
+bool conv1_dgrad_resident_eligible(const FpropArgs& a);
+int launch_conv1_dgrad_resident(const FpropArgs& a, hipStream_t stream);
 
 #if defined(__HIPCC__)
 
