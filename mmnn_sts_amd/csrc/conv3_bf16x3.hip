@@ -324,9 +324,9 @@ __global__ void __launch_bounds__(256) conv3_dgrad_bf16x3_kernel(const FpropArgs
     for (int q = 0; q < 16; ++q) {
       const int m = wv * 32 + acc_row(q, lane >> 5);
       if (ok) {
-        const float pre = fmaf(ecoef[m], xe[q], ecoef[128 + m]);
-        const float z = pre > 0.f ? acc[t][q] : 0.f;
-        const float xh = (xe[q] - ecoef[256 + m]) * ecoef[384 + m];
+        const EpiRow<128> e{ecoef + m};
+        float z, xh;
+        mask_elem(e.a(), e.b(), e.mean(), e.rstd(), xe[q], acc[t][q], z, xh);
         outn[(long)m * V + o] = z;
         s0[q] += z;
         s1[q] += z * xh;

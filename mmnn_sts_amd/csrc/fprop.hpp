@@ -18,22 +18,6 @@
 
 namespace mmnn {
 
-// Cross-workgroup K-split hand-off (fprop_kernel, "cross-block K-split").  0: the fence-free form measured valid on gfx950 / ROCm 7.2
-// (MI355X_MICROARCH.md, inter-workgroup visibility, table row "ONE lane of each storing workgroup ... an agent-scope atomic add / the
-// workgroup whose add came last"): partial tiles leave with write-through `sc1` stores, every storing wave drains `vmcnt(0)`, a workgroup
-// barrier, ONE lane's agent-scope ticket; the last arriver reads them with `sc1` loads behind a workgroup barrier.  That is a property of
-// this chip's cache policy, not of the HIP memory model, so it is the default ONLY for gfx950; any other target -- or -DMMNN_KZ_FENCED=1
-// (`MMNN_KZ_FENCED=1 python -m mmnn_sts_amd.build` builds libmmnn_sts_fenced.so) -- gets the portable form: plain stores, an agent-scope
-// RELEASE fence before the ticket, an agent-scope ACQUIRE fence in every reading wave after it.  tests/test_kz_handoff_gpu.py stresses
-// whichever library is loaded; tests/test_host_cpu.py::test_kz_handoff_isa checks that the emitted gfx950 code really carries `sc1`.
-#if !defined(MMNN_KZ_FENCED)
-#if defined(__gfx950__) || !defined(__HIP_DEVICE_COMPILE__)
-#define MMNN_KZ_FENCED 0
-#else
-#define MMNN_KZ_FENCED 1
-#endif
-#endif
-
 enum Pro { PRO_NONE = 0, PRO_BNRELU = 1, PRO_GRAD = 2 };
 enum Epi { EPI_STORE = 0, EPI_STORE_STATS = 1, EPI_MASK_STORE = 2, EPI_MASK_ACCUM = 3 };
 
@@ -85,6 +69,11 @@ bool conv1_dgrad_resident_shape_ok(int mode, int N, long V, int Cin, int M, int 
 bool conv1_dgrad_resident_eligible(const FpropArgs& a);
 int launch_conv1_dgrad_resident(const FpropArgs& a, hipStream_t stream);
 
+}  // namespace mmnn
+
+#include "conv_tile.hpp"   // the building blocks of the kernels below and of their siblings (they take FpropArgs)
+
+namespace mmnn {
 #if defined(__HIPCC__)
 
 template <int TAPS, int PRO, int EPI, int WM, int WN, int KS, int MT, int NT, int KC, int TD, int TH, int TW, bool SPEC = false>
@@ -162,6 +151,352 @@ __device__ __forceinline__ float half_reduce_n(const float (&v)[R], int lane) {
   t += swz_xor<1>(t);
   return t;
 }
+
+// ---- the tails of fprop_kernel: what happens to a workgroup's accumulators after the K loop, as the stages the kernel calls.  The
+// members are what every tail needs of the kernel's state: the extents of the launch (by value: a bound read through the argument
+// struct inside a condition keeps the compiler from flattening it), the tile (rows from m0, voxels from `at`), this lane's place in it
+// (wave (wm, wn) of K-split group kg), the sample's output / mask-operand tensors, and the LDS areas: the per-row epilogue coefficients,
+// the per-wave row sums ([WN][M_B] each, one writer per slot) and the staging area, free after the last barrier of the K loop. ----
+template <int TAPS, int PRO, int EPI, int WM, int WN, int KS, int MT, int NT, int KC, int TD, int TH, int TW, bool SPEC>
+struct FpropTail {
+  using C = FpropCfg<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
+  static constexpr int M_B = C::M_B, RP = 16 / KS, NSLOT = WM * WN * MT * NT;      // RP: accumulator rows per K-split wave group
+  static constexpr bool MASK = (EPI == EPI_MASK_STORE || EPI == EPI_MASK_ACCUM);
+  int D, H, W, V, M;
+  TileAt at;
+  int m0, wm, wn, kg, half, l31, lane;
+  float* outn;
+  const float* exn;
+  float* ecoef; float* red0; float* red1; float* Xs;
+  bool want_sums;
+  __device__ __forceinline__ int slot() const { return (wm * WN + wn) * MT * NT; }      // this wave's first accumulator tile
+  __device__ __forceinline__ bool voxel(int idx, int& vox) const { return tile_voxel<TAPS, TD, TH, TW>(at, D, H, W, V, idx, vox); }
+
+  // ================= distributed tail of the small tiles (r03).  One accumulator tile per wave, the K axis split over KS wave
+  // groups.  The r02 tail funnelled everything through the group-0 waves: they summed (KS - 1) x 16 rows from LDS, published 16 rows,
+  // summed the K-split slices and ran the whole epilogue while seven of eight waves waited (phase trace: 1.3k + 3.4k + 2.2k + 3.7k
+  // cycles of a 23k-cycle 8^3 launch).  Here every group keeps 16 / KS rows of its tile from the in-block reduction through the
+  // cross-workgroup hand-off to the stores; sums are taken in the same order as before (group order, then slice order). =======
+  // In-block reduction: my[q] = row kg * RP + q of the wave's tile, summed over the KS groups in group order.
+  __device__ __forceinline__ void dist_reduce(const f32x16& acc, float (&my)[RP]) const {
+    float* rbuf = Xs;
+    const int slot = this->slot();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rbuf[((kg * NSLOT + slot) * 16 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < RP; ++q) {
+      float s = rbuf[((0 * NSLOT + slot) * 16 + kg * RP + q) * 64 + lane];
+#pragma unroll
+      for (int g = 1; g < KS; ++g) s += rbuf[((g * NSLOT + slot) * 16 + kg * RP + q) * 64 + lane];
+      my[q] = s;
+    }
+  }
+
+  // Epilogue of this wave's rows: register q holds row acc_row(kg * RP + q, half) of tile (wm, wn), voxel l31.
+  __device__ __forceinline__ void dist_epilogue(const float (&my)[RP]) const {
+    int vox;
+    const bool vok = voxel(wn * 32 + l31, vox);
+    int ml[RP]; bool ok[RP]; unsigned off[RP];
+    float xe[MASK ? RP : 1], go[(EPI == EPI_MASK_ACCUM) ? RP : 1];
+#pragma unroll
+    for (int q = 0; q < RP; ++q) {
+      ml[q] = wm * 32 + acc_row(kg * RP + q, half);
+      ok[q] = vok && (m0 + ml[q]) < M;
+      off[q] = ok[q] ? (unsigned)(m0 + ml[q]) * (unsigned)V + (unsigned)vox : 0u;     // unconditional loads (clamped), before any store (aliasing)
+      if (MASK) xe[MASK ? q : 0] = exn[off[q]];
+      if (EPI == EPI_MASK_ACCUM) go[(EPI == EPI_MASK_ACCUM) ? q : 0] = outn[off[q]];
+    }
+    float s0[RP], s1[RP];
+#pragma unroll
+    for (int q = 0; q < RP; ++q) {
+      const EpiRow<M_B> e{ecoef + ml[q]};
+      float val = my[q], t0 = 0.f, t1 = 0.f;
+      if (EPI == EPI_STORE) {
+        if (ok[q]) outn[off[q]] = val;
+      } else if (EPI == EPI_STORE_STATS) {
+        val *= e.dropscale();
+        if (ok[q]) { outn[off[q]] = val; t0 = val; t1 = val * val; }
+      } else {
+        if (ok[q]) {
+          float z, xh;
+          mask_elem(e.a(), e.b(), e.mean(), e.rstd(), xe[MASK ? q : 0], val, z, xh);
+          t0 = z; t1 = z * xh;
+          if (EPI == EPI_MASK_STORE) outn[off[q]] = z;
+          else outn[off[q]] = go[(EPI == EPI_MASK_ACCUM) ? q : 0] + e.gamma() * z;
+        }
+      }
+      s0[q] = t0; s1[q] = t1;
+    }
+    if (want_sums) {
+      const float r0 = half_reduce_n<RP>(s0, lane), r1 = half_reduce_n<RP>(s1, lane);
+      constexpr int SH = (RP == 8) ? 2 : (RP == 4 ? 3 : 4);      // lanes l31 >> SH share a total: the first of each group writes it
+      if ((l31 & ((1 << SH) - 1)) == 0) {
+        const int mrow = wm * 32 + acc_row(kg * RP + (l31 >> SH), half);
+        red0[wn * M_B + mrow] = r0;
+        red1[wn * M_B + mrow] = r1;
+      }
+    }
+  }
+
+  // ================= cross-group reduction of the accumulators (in-block K-split): group 0 adds its partners' tiles in group order =====
+  __device__ __forceinline__ void group_reduce(bool loader, f32x16 (&acc)[MT][NT]) const {
+    float* rbuf = Xs;   // staging buffers are free after the last barrier
+    const int slot = this->slot();
+    if (kg > 0 && !loader) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) rbuf[(((kg - 1) * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane] = acc[i][j][r];
+    }
+    __syncthreads();
+    if (kg == 0 && !loader) {
+#pragma unroll
+      for (int g = 1; g < KS; ++g)
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] += rbuf[(((g - 1) * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane];
+    }
+  }
+
+  // The last arriver of the cross-block K-split: the group-0 waves' accumulators <- the sum of all kz slices, in slice order from zero
+  // (bit-reproducible).
+  __device__ __forceinline__ void kz_collect(const float* part, int kz, bool loader, f32x16 (&acc)[MT][NT]) const {
+    const int slot = this->slot();
+    if constexpr (KS > 1) {
+      // Every wave group takes 16 / KS accumulator rows of each tile and has ALL slices' loads in flight at once (slices past kz
+      // re-read the last one and add an exact zero): one memory round trip instead of kz / 2 dependent ones by the group-0 waves
+      // alone (phase "kz sum": 3.7k of a 27k-cycle launch at kz = 8).  Summed in slice order as before -- same bits -- and handed to
+      // the epilogue waves through the staging area, which is free since the barriers above.
+      float* xbuf = Xs;
+      if (!loader) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+            float sacc[RP];
+            kz_sum_slices<RP>(part, NSLOT, slot + i * NT + j, kg * RP, lane, kz, sacc);
+#pragma unroll
+            for (int q = 0; q < RP; ++q) xbuf[((slot + i * NT + j) * 16 + kg * RP + q) * 64 + lane] = sacc[q];
+          }
+      }
+      __syncthreads();
+      if (kg == 0 && !loader) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = xbuf[((slot + i * NT + j) * 16 + r) * 64 + lane];
+      }
+    } else {
+      if (kg == 0 && !loader) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            // kz is 2, 4 or 8: two slices' loads are in flight together (one memory round trip per pair), summed in slice order
+            for (int z = 0; z < kz; z += 2) {
+              float p0[16], p1[16];
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                p0[r] = kz_load(part + (((long)z * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane);
+                p1[r] = kz_load(part + (((long)(z + 1) * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane);
+              }
+#pragma unroll
+              for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] + p0[r]) + p1[r];
+            }
+          }
+      }
+    }
+  }
+
+  // ================= epilogues of the group-0 waves =================
+  // The mask epilogues read one (ex) or two (ex, out) tensors per element.  Their loads are issued BEFORE the stores: `out` may
+  // alias `ex` as far as the compiler knows, so a load placed after a store is never hoisted above it and every accumulator row
+  // would pay a full memory round trip of its own (phase trace r02: 34 us of a 126 us block in block 1's data gradient).  One
+  // tensor (MASK_STORE): the whole tile's loads go out together; two tensors (MASK_ACCUM): one 32-row slab at a time (register
+  // budget: the big tiles of block 1 must stay at two waves per SIMD).  Element offsets are 32-bit (host check: M * V < 2^31),
+  // so an address costs one register beside the uniform base pointer.
+  // Wide form (big tiles, 16-byte aligned tensors): an MFMA accumulator holds ONE voxel per lane and row, so the direct form below
+  // moves 4 bytes per lane and instruction -- 128..192 memory instructions per thread, and the address coalescer, not HBM, bounds
+  // the epilogue (phase trace r02: 33k of a block's 85k cycles in block 1's conv1 data gradient, 40k of 290k in conv2's).  Each
+  // 32 x 32 accumulator tile is therefore transposed through LDS (wave-private, the staging buffers are free) so that a lane holds
+  // 4 consecutive voxels of 4 rows: every global access becomes a dwordx4 -- a quarter of the memory instructions.
+  __device__ __forceinline__ void epilogue_wide(const f32x16 (&acc)[MT][NT]) const {
+    float* tb = Xs + (wm * WN + wn) * (32 * C::TSTRIDE);
+    const int q4 = 4 * (lane & 7), rl = lane >> 3;            // this lane's voxel quad and first row within a tile
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      f32x4 vt[NT][4], xq[MASK ? NT : 1][4], gq[(EPI == EPI_MASK_ACCUM) ? NT : 1][4];
+      unsigned off[NT][4];
+      bool okq[NT][4];
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        // voxel quad of this lane in tile j
+        int vq;
+        const bool vk = voxel((wn * NT + j) * 32 + q4, vq);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();        // the previous tile's reads precede these writes (LDS executes a wave's accesses in order)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tb[acc_row(r, half) * C::TSTRIDE + l31] = acc[i][j][r];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int ml = wm * MT * 32 + i * 32 + rl + 8 * k;
+          vt[j][k] = *reinterpret_cast<const f32x4*>(tb + (rl + 8 * k) * C::TSTRIDE + q4);
+          okq[j][k] = vk && (m0 + ml) < M;
+          off[j][k] = okq[j][k] ? (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vq : 0u;      // unconditional loads (clamped)
+        }
+      }
+      // all loads of the slab before its stores (see the note on aliasing above)
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (MASK) xq[MASK ? j : 0][k] = *reinterpret_cast<const f32x4*>(exn + off[j][k]);
+          if (EPI == EPI_MASK_ACCUM) gq[(EPI == EPI_MASK_ACCUM) ? j : 0][k] = *reinterpret_cast<const f32x4*>(outn + off[j][k]);
+        }
+      float s0[4], s1[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int ml = wm * MT * 32 + i * 32 + rl + 8 * k;
+        const EpiRow<M_B> e{ecoef + ml};
+        const float ea = e.a(), eb = e.b(), mu = e.mean(), rs = e.rstd(), gm = e.gamma(), ds = e.dropscale();
+        float t0 = 0.f, t1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          if (okq[j][k]) {
+            f32x4 o;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              if (MASK) {
+                float z, xh;
+                mask_elem(ea, eb, mu, rs, xq[MASK ? j : 0][k][c], vt[j][k][c], z, xh);
+                t0 += z;
+                t1 += z * xh;
+                o[c] = (EPI == EPI_MASK_STORE) ? z : gq[(EPI == EPI_MASK_ACCUM) ? j : 0][k][c] + gm * z;
+              } else {     // EPI_STORE_STATS: channel dropout scale, sums for the consumer's batch statistics
+                const float val = vt[j][k][c] * ds;
+                t0 += val;
+                t1 += val * val;
+                o[c] = val;
+              }
+            }
+            *reinterpret_cast<f32x4*>(outn + off[j][k]) = o;
+          }
+        }
+        s0[k] = t0; s1[k] = t1;
+      }
+      if (want_sums) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float r0 = s0[k], r1 = s1[k];
+          quad_row_sum(r0, r1);
+          if ((lane & 7) == 0) {
+            const int ml = wm * MT * 32 + i * 32 + rl + 8 * k;
+            red0[wn * M_B + ml] = r0;
+            red1[wn * M_B + ml] = r1;
+          }
+        }
+      }
+    }
+  }
+
+  // Direct form: a lane stores the one voxel per row that its accumulator registers hold.  EPI_MASK_STORE: the epilogue's operand, the
+  // pre-activation tensor `ex`, is loaded for the whole tile at once.  (Loading it before the last chunk's MFMAs measured slower: its
+  // registers stay live across the chunk)
+  __device__ __forceinline__ void epilogue_direct(const f32x16 (&acc)[MT][NT]) const {
+    constexpr bool ALL_ROWS = (EPI == EPI_MASK_STORE);
+    int vox[NT];      // (computed here, not ahead of the K loop: kept live across it these cost the small-tile kernels their last registers)
+    bool vok[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) vok[j] = voxel((wn * NT + j) * 32 + l31, vox[j]);
+    float xall[ALL_ROWS ? MT : 1][ALL_ROWS ? 16 : 1][NT];
+    if (ALL_ROWS) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int ml = wm * MT * 32 + i * 32 + acc_row(q, half);
+          const bool mok = (m0 + ml) < M;
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+            const unsigned o = (mok && vok[j]) ? (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vox[j] : 0u;   // unconditional loads (clamped)
+            xall[ALL_ROWS ? i : 0][ALL_ROWS ? q : 0][j] = exn[o];
+          }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      float s0[16], s1[16];
+      float xe[(MASK && !ALL_ROWS) ? 16 : 1][NT], go[(EPI == EPI_MASK_ACCUM) ? 16 : 1][NT];
+      if (MASK && !ALL_ROWS) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int ml = wm * MT * 32 + i * 32 + acc_row(q, half);
+          const bool mok = (m0 + ml) < M;
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+            const unsigned o = (mok && vok[j]) ? (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vox[j] : 0u;
+            xe[(MASK && !ALL_ROWS) ? q : 0][j] = exn[o];
+            if (EPI == EPI_MASK_ACCUM) go[(EPI == EPI_MASK_ACCUM) ? q : 0][j] = outn[o];
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ml = wm * MT * 32 + i * 32 + acc_row(r, half);
+        const EpiRow<M_B> e{ecoef + ml};
+        const bool mok = (m0 + ml) < M;
+        float t0 = 0.f, t1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          const bool ok = mok && vok[j];
+          const unsigned o = (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vox[j];
+          float val = acc[i][j][r];
+          if (EPI == EPI_STORE) {
+            if (ok) outn[o] = val;
+          } else if (EPI == EPI_STORE_STATS) {
+            val *= e.dropscale();
+            if (ok) {
+              outn[o] = val;
+              t0 += val;
+              t1 += val * val;
+            }
+          } else {
+            if (ok) {
+              float z, xh;
+              mask_elem(e.a(), e.b(), e.mean(), e.rstd(), ALL_ROWS ? xall[ALL_ROWS ? i : 0][ALL_ROWS ? r : 0][j] : xe[(MASK && !ALL_ROWS) ? r : 0][j], val, z, xh);
+              t0 += z;
+              t1 += z * xh;
+              if (EPI == EPI_MASK_STORE) outn[o] = z;
+              else outn[o] = go[(EPI == EPI_MASK_ACCUM) ? r : 0][j] + e.gamma() * z;
+            }
+          }
+        }
+        s0[r] = t0;
+        s1[r] = t1;
+      }
+      if (want_sums) {
+        const float r0 = half_reduce16(s0, lane), r1 = half_reduce16(s1, lane);
+        if ((lane & 1) == 0) {
+          const int ml = wm * MT * 32 + i * 32 + acc_row((l31 >> 1) & 15, half);
+          red0[wn * M_B + ml] = r0;
+          red1[wn * M_B + ml] = r1;
+        }
+      }
+    }
+  }
+};
 
 template <int TAPS, int PRO, int EPI, int WM, int WN, int KS, int MT, int NT, int KC, int TD, int TH, int TW, bool SPEC = false>
 __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel(const FpropArgs a) {
@@ -259,35 +594,20 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
     if (MASK_E && (tid & ~63) < M_B) bn_fwd_issue(a.ebn, pm, raw_e);
   }
   stamp(14);
+  // one channel's prologue coefficients, one row's epilogue coefficients (`fast`: from the statistics issued above)
+  auto pro_row = [&](int c, bool fast) {
+    if (PRO == PRO_BNRELU) pro_coef(coef, cpad, c, c < a.Cin, fast, a.bn_in, raw_in);
+    if (PRO == PRO_GRAD) pro_coef(coef, cpad, c, c < a.Cin, fast, a.gr_in, raw_gr, drop_scale(a.drop_in, n, c));
+  };
+  auto epi_row = [&](int m, bool fast) {
+    const EpiRow<M_B> e{ecoef + m};
+    const bool valid = m0 + m < a.M;
+    e.fill(fast, a.ebn, raw_e, m0 + m, MASK_E && valid);
+    e.put_dropscale((EPI == EPI_STORE_STATS && valid) ? drop_scale(a.drop_out, n, m0 + m) : 1.f);
+  };
   auto prologue_fast = [&]() {
-    const int c = c_begin + tid;
-    if (c < c_hi) {
-      if (PRO == PRO_BNRELU) {
-        float ca = 0.f, cb = 0.f, mu, rs;
-        bn_fwd_finish(a.bn_in, raw_in, ca, cb, mu, rs);
-        const bool ok = c < a.Cin;
-        coef[c] = ok ? ca : 0.f; coef[cpad + c] = ok ? cb : 0.f;
-      } else if (PRO == PRO_GRAD) {
-        float p = 0.f, q = 0.f, r = 0.f;
-        bn_bwd_finish(a.gr_in, raw_gr, p, q, r);
-        const bool ok = c < a.Cin;
-        const float sc = drop_scale(a.drop_in, n, c);
-        coef[c] = ok ? p * sc : 0.f; coef[cpad + c] = ok ? q * sc : 0.f; coef[2 * cpad + c] = ok ? r * sc : 0.f;
-      }
-    }
-    if (tid < M_B) {
-      const int m = tid;
-      float ea = 0.f, eb = 0.f, mu = 0.f, rs = 0.f, g = 0.f, ds = 1.f;
-      if (m0 + m < a.M) {
-        if (MASK_E) {
-          bn_fwd_finish(a.ebn, raw_e, ea, eb, mu, rs);
-          g = raw_e.g;
-        }
-        if (EPI == EPI_STORE_STATS) ds = drop_scale(a.drop_out, n, m0 + m);
-      }
-      ecoef[m] = ea; ecoef[M_B + m] = eb; ecoef[2 * M_B + m] = mu; ecoef[3 * M_B + m] = rs;
-      ecoef[4 * M_B + m] = g; ecoef[5 * M_B + m] = ds;
-    }
+    if (c_begin + tid < c_hi) pro_row(c_begin + tid, true);
+    if (tid < M_B) epi_row(tid, true);
     __syncthreads();
   };
 
@@ -296,35 +616,8 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
   // the chunk is written to LDS, so the two latencies overlap instead of adding up -- the small-extent layers are a chain of
   // such latencies and little else. ----
   auto prologue = [&]() {
-    if (PRO == PRO_BNRELU) {
-      for (int c = c_begin + tid; c < min(cpad, c_begin + ((c_end - c_begin + KC - 1) / KC) * KC); c += NTHREADS) {
-        float ca = 0.f, cb = 0.f, mu, rs;
-        if (c < a.Cin) bn_fwd_coef(a.bn_in, c, ca, cb, mu, rs);
-        coef[c] = ca; coef[cpad + c] = cb;
-      }
-    } else if (PRO == PRO_GRAD) {
-      for (int c = c_begin + tid; c < min(cpad, c_begin + ((c_end - c_begin + KC - 1) / KC) * KC); c += NTHREADS) {
-        float p = 0.f, q = 0.f, r = 0.f;
-        if (c < a.Cin) {
-          bn_bwd_coef(a.gr_in, c, p, q, r);
-          const float s = drop_scale(a.drop_in, n, c);
-          p *= s; q *= s; r *= s;
-        }
-        coef[c] = p; coef[cpad + c] = q; coef[2 * cpad + c] = r;
-      }
-    }
-    for (int m = tid; m < M_B; m += NTHREADS) {
-      float ea = 0.f, eb = 0.f, mu = 0.f, rs = 0.f, g = 0.f, ds = 1.f;
-      if (m0 + m < a.M) {
-        if (EPI == EPI_MASK_STORE || EPI == EPI_MASK_ACCUM) {
-          bn_fwd_coef(a.ebn, m0 + m, ea, eb, mu, rs);
-          g = a.ebn.gamma[m0 + m];
-        }
-        if (EPI == EPI_STORE_STATS) ds = drop_scale(a.drop_out, n, m0 + m);
-      }
-      ecoef[m] = ea; ecoef[M_B + m] = eb; ecoef[2 * M_B + m] = mu; ecoef[3 * M_B + m] = rs;
-      ecoef[4 * M_B + m] = g; ecoef[5 * M_B + m] = ds;
-    }
+    for (int c = c_begin + tid; c < c_hi; c += NTHREADS) pro_row(c, false);
+    for (int m = tid; m < M_B; m += NTHREADS) epi_row(m, false);
     __syncthreads();
   };
 
@@ -339,15 +632,7 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
 
   int pos[NT];
 #pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int t = (wn * NT + j) * 32 + l31;
-    if (TAPS == 27) {
-      const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
-      pos[j] = (dz * HS + hy) * RS + wx + 3;
-    } else {
-      pos[j] = t;
-    }
-  }
+  for (int j = 0; j < NT; ++j) pos[j] = tile_lds_pos<TAPS, TH, TW, HS, RS>((wn * NT + j) * 32 + l31);
 
   const float* in0n = a.in0 + (long)n * a.in0_ns + (long)a.in0_coff * V;
   const float* in1n = (PRO == PRO_GRAD) ? a.in1 + (long)n * a.in1_ns + (long)a.in1_coff * V : nullptr;
@@ -391,43 +676,9 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
     }
   };
 
-  // ---- output positions of this lane, and (MASK_STORE) the epilogue's operand: the pre-activation tensor `ex`, whole tile, loaded
-  // in the epilogue.  (Loading it before the last chunk's MFMAs measured slower: its registers stay live across the chunk) ----
+  // ---- this sample's output tensor and the mask epilogues' operand, the pre-activation tensor `ex` ----
   float* outn = a.out + (long)n * a.out_ns + (long)a.out_coff * V;
   const float* exn = (EPI == EPI_MASK_STORE || EPI == EPI_MASK_ACCUM) ? a.ex + (long)n * a.ex_ns + (long)a.ex_coff * V : nullptr;
-  constexpr bool ALL_ROWS = (EPI == EPI_MASK_STORE);
-  float xall[ALL_ROWS ? MT : 1][ALL_ROWS ? 16 : 1][NT];
-  auto load_xall = [&]() {
-    if (ALL_ROWS) {
-      int vox[NT];      // (recomputed in the epilogue: kept live across the K loop these cost the small-tile kernels their last registers)
-      bool vok[NT];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int t = (wn * NT + j) * 32 + l31;
-        if (TAPS == 27) {
-          const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
-          const int d = d0 + dz, h = h0 + hy, w = w0 + wx;
-          vok[j] = d < a.D && h < a.H && w < a.W;
-          vox[j] = (d * a.H + h) * a.W + w;
-        } else {
-          vox[j] = v0_ + t;
-          vok[j] = vox[j] < V;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int ml = wm * MT * 32 + i * 32 + acc_row(q, half);
-          const bool mok = (m0 + ml) < a.M;
-#pragma unroll
-          for (int j = 0; j < NT; ++j) {
-            const unsigned o = (mok && vok[j]) ? (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vox[j] : 0u;   // unconditional loads (clamped)
-            xall[ALL_ROWS ? i : 0][ALL_ROWS ? q : 0][j] = exn[o];
-          }
-        }
-    }
-  };
 
   if (vecx && vecw && (long)KC * V < (1l << 30)) {
     // ===== fast path: 16-byte staging through registers, software-pipelined.  The global loads of chunk k+1 are issued
@@ -593,18 +844,9 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
     // big tiles of block 1 amortise the prologue over a long K loop and cannot afford the registers (staging registers live
     // across the fp64 coefficient math: 116 -> 188 VGPRs, one register short of losing the second wave per SIMD).
     if (!EARLY) prologue();
-    // One dword per 128-byte line of the NEXT launch's weights, at most two lines per thread, addresses clamped instead of guarded
-    // and the values consumed only at the very end of the kernel: nothing ever waits for these loads.  Issued after the first
-    // chunk's loads and the coefficient loads (memory returns in order: a cold weight line ahead of them would hold them back).
-    auto prefetch_next_weights = [&]() {
-      const unsigned lines = a.pf_bytes >> 7;
-      if (a.pf_ptr == nullptr || lines == 0) return;
-      const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);      // dispatch order: XCD = lin & 7
-      const unsigned per_xcd = (gridDim.x * gridDim.y * gridDim.z + 7u) >> 3;
-      const unsigned ln0 = (lin >> 3) * NTHREADS + tid, ln1 = ln0 + per_xcd * NTHREADS;
-      pf_sink = a.pf_ptr[(size_t)min(ln0, lines - 1) * 32];
-      pf_sink2 = a.pf_ptr[(size_t)min(ln1, lines - 1) * 32];
-    };
+    // the NEXT launch's weights: after the first chunk's loads and the coefficient loads (prefetch_weight_lines)
+    const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), nblocks = gridDim.x * gridDim.y * gridDim.z;
+    auto prefetch_next_weights = [&]() { prefetch_weight_lines(a, lin, nblocks, NTHREADS, tid, pf_sink, pf_sink2); };
     if (SPEC) {
       // loader waves fill buffer (k+1)&1 while compute waves consume buffer k&1; one barrier per chunk
       if (loader && c_begin < c_end) load_first(stA);
@@ -793,513 +1035,63 @@ __global__ void __launch_bounds__(WM* WN* KS * 64 * (SPEC ? 2 : 1)) fprop_kernel
   }
 
   stamp(3);
+  // ---- after the K loop: in-block reduction, cross-workgroup hand-off, epilogue, flush (the tails above) ----
   float* red0 = ecoef + 6 * M_B;            // [WN][M_B] partial sums, one writer per slot (no LDS atomics: reproducible)
   float* red1 = red0 + WN * M_B;
   const bool want_sums = (EPI == EPI_STORE_STATS) ? (a.st_out.sum != nullptr) : (EPI != EPI_STORE);
+  using Tail = FpropTail<TAPS, PRO, EPI, WM, WN, KS, MT, NT, KC, TD, TH, TW, SPEC>;
+  const Tail tail{a.D, a.H, a.W, V, a.M, TileAt{d0, h0, w0, v0_}, m0, wm, wn, kg, half, l31, lane, outn, exn, ecoef, red0, red1, Xs, want_sums};
+  // cross-block K-split (kz > 1): this tile's partial accumulator tiles in a.kz_part, its arrival counter, the ticket's word of LDS
+  constexpr int NSLOT = Tail::NSLOT, RP = Tail::RP;
+  const int slot = tail.slot();
+  const long tile_id = blockIdx.x + (long)gridDim.x * blockIdx.y;
+  float* part = a.kz_part + (tile_id * kz) * NSLOT * 1024;
+  auto kz_last = [&]() { return kz_arrive(a.kz_cnt + tile_id, kz, reinterpret_cast<unsigned*>(ecoef + C::ECOEF * M_B), tid, [&]() { stamp(5); }); };
   if constexpr (C::DIST) {
-    // ================= distributed tail of the small tiles (r03).  One accumulator tile per wave, the K axis split over KS wave
-    // groups.  The r02 tail funnelled everything through the group-0 waves: they summed (KS - 1) x 16 rows from LDS, published 16 rows,
-    // summed the K-split slices and ran the whole epilogue while seven of eight waves waited (phase trace: 1.3k + 3.4k + 2.2k + 3.7k
-    // cycles of a 23k-cycle 8^3 launch).  Here every group keeps 16 / KS rows of its tile from the in-block reduction through the
-    // cross-workgroup hand-off to the stores; sums are taken in the same order as before (group order, then slice order). =======
-    constexpr int RP = 16 / KS, NSLOT = WM * WN;
-    constexpr bool MASK = (EPI == EPI_MASK_STORE || EPI == EPI_MASK_ACCUM);
-    float* rbuf = Xs;                                   // staging buffers are free after the last barrier
-    const int slot = wm * WN + wn;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) rbuf[((kg * NSLOT + slot) * 16 + r) * 64 + lane] = acc[0][0][r];
-    __syncthreads();
     float my[RP];
-#pragma unroll
-    for (int q = 0; q < RP; ++q) {
-      float t = rbuf[((0 * NSLOT + slot) * 16 + kg * RP + q) * 64 + lane];
-#pragma unroll
-      for (int g = 1; g < KS; ++g) t += rbuf[((g * NSLOT + slot) * 16 + kg * RP + q) * 64 + lane];
-      my[q] = t;
-    }
+    tail.dist_reduce(acc[0][0], my);
     stamp(4);
     if (kz > 1) {
-      // cross-workgroup K-split, as in the general tail below (write-through partials, drained, ticket; the last arriver reads
-      // with sc1 loads) -- but every wave publishes and sums its own rows
-      const long tile_id = blockIdx.x + (long)gridDim.x * blockIdx.y;
-      float* part = a.kz_part + (tile_id * kz) * NSLOT * 1024;
-#pragma unroll
-      for (int q = 0; q < RP; ++q) {
-        float* dst = part + (((long)blockIdx.z * NSLOT + slot) * 16 + kg * RP + q) * 64 + lane;
-#if MMNN_KZ_FENCED
-        *dst = my[q];
-#else
-        __hip_atomic_store(dst, my[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // global_store_dword ... sc1
-#endif
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave drains its stores before the barrier
-      __syncthreads();
-      unsigned* ticket = reinterpret_cast<unsigned*>(ecoef + C::ECOEF * M_B);
-      if (tid == 0) {
-#if MMNN_KZ_FENCED
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // cumulative over the barrier: publishes the whole workgroup's stores
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        *ticket = __hip_atomic_fetch_add(a.kz_cnt + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      stamp(5);
-      const unsigned arrived = *ticket;
-      if (arrived != (unsigned)(kz - 1)) return;            // not the last slice of this tile: done
-      if (tid == 0) __hip_atomic_store(a.kz_cnt + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-#if MMNN_KZ_FENCED
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-      constexpr int ZB = (RP <= 4) ? 8 : 4;               // slices in flight: at most 32 loads per lane
-#pragma unroll
-      for (int q = 0; q < RP; ++q) my[q] = 0.f;
-      for (int z0 = 0; z0 < kz; z0 += ZB) {
-        float pz[ZB][RP];
-#pragma unroll
-        for (int z = 0; z < ZB; ++z) {
-          const int zc = min(z0 + z, kz - 1);
-#pragma unroll
-          for (int q = 0; q < RP; ++q) {
-            const float* sp = part + (((long)zc * NSLOT + slot) * 16 + kg * RP + q) * 64 + lane;
-#if MMNN_KZ_FENCED
-            pz[z][q] = *sp;
-#else
-            pz[z][q] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);            // global_load_dword ... sc1
-#endif
-          }
-        }
-#pragma unroll
-        for (int z = 0; z < ZB; ++z)
-#pragma unroll
-          for (int q = 0; q < RP; ++q) my[q] += (z0 + z < kz) ? pz[z][q] : 0.f;
-      }
+      // as in the general tail below, but every wave publishes and sums its own rows
+      kz_publish_rows<RP>(part, NSLOT, slot, kg * RP, lane, blockIdx.z, my);
+      if (!kz_last()) return;                               // not the last slice of this tile: done
+      kz_sum_slices<RP>(part, NSLOT, slot, kg * RP, lane, kz, my);
     }
     stamp(6);
-    // ---- epilogue of this wave's rows: register q holds row acc_row(kg * RP + q, half) of tile (wm, wn), voxel l31 ----
-    int vox; bool vok;
-    {
-      const int t = wn * 32 + l31;
-      if (TAPS == 27) {
-        const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
-        const int d = d0 + dz, h = h0 + hy, w = w0 + wx;
-        vok = d < a.D && h < a.H && w < a.W;
-        vox = (d * a.H + h) * a.W + w;
-      } else {
-        vox = v0_ + t;
-        vok = vox < V;
-      }
-    }
-    int ml[RP]; bool ok[RP]; unsigned off[RP];
-    float xe[MASK ? RP : 1], go[(EPI == EPI_MASK_ACCUM) ? RP : 1];
-#pragma unroll
-    for (int q = 0; q < RP; ++q) {
-      ml[q] = wm * 32 + acc_row(kg * RP + q, half);
-      ok[q] = vok && (m0 + ml[q]) < a.M;
-      off[q] = ok[q] ? (unsigned)(m0 + ml[q]) * (unsigned)V + (unsigned)vox : 0u;     // unconditional loads (clamped), before any store (aliasing)
-      if (MASK) xe[MASK ? q : 0] = exn[off[q]];
-      if (EPI == EPI_MASK_ACCUM) go[(EPI == EPI_MASK_ACCUM) ? q : 0] = outn[off[q]];
-    }
-    float s0[RP], s1[RP];
-#pragma unroll
-    for (int q = 0; q < RP; ++q) {
-      float val = my[q], t0 = 0.f, t1 = 0.f;
-      if (EPI == EPI_STORE) {
-        if (ok[q]) outn[off[q]] = val;
-      } else if (EPI == EPI_STORE_STATS) {
-        val *= ecoef[5 * M_B + ml[q]];
-        if (ok[q]) { outn[off[q]] = val; t0 = val; t1 = val * val; }
-      } else {
-        if (ok[q]) {
-          const float x = xe[MASK ? q : 0];
-          const float pre = fmaf(ecoef[ml[q]], x, ecoef[M_B + ml[q]]);
-          const float z = pre > 0.f ? val : 0.f;
-          const float xh = (x - ecoef[2 * M_B + ml[q]]) * ecoef[3 * M_B + ml[q]];
-          t0 = z; t1 = z * xh;
-          if (EPI == EPI_MASK_STORE) outn[off[q]] = z;
-          else outn[off[q]] = go[(EPI == EPI_MASK_ACCUM) ? q : 0] + ecoef[4 * M_B + ml[q]] * z;
-        }
-      }
-      s0[q] = t0; s1[q] = t1;
-    }
-    if (want_sums) {
-      const float r0 = half_reduce_n<RP>(s0, lane), r1 = half_reduce_n<RP>(s1, lane);
-      constexpr int SH = (RP == 8) ? 2 : (RP == 4 ? 3 : 4);      // lanes l31 >> SH share a total: the first of each group writes it
-      if ((l31 & ((1 << SH) - 1)) == 0) {
-        const int mrow = wm * 32 + acc_row(kg * RP + (l31 >> SH), half);
-        red0[wn * M_B + mrow] = r0;
-        red1[wn * M_B + mrow] = r1;
-      }
-    }
+    tail.dist_epilogue(my);
   } else {
-  // ================= cross-group reduction of the accumulators (K-split) =================
-  if (KS > 1) {
-    float* rbuf = Xs;   // staging buffers are free after the last barrier
-    const int slot = (wm * WN + wn) * MT * NT;
-    if (kg > 0 && !loader) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) rbuf[(((kg - 1) * WM * WN * MT * NT + slot + i * NT + j) * 16 + r) * 64 + lane] = acc[i][j][r];
-    }
-    __syncthreads();
-    if (kg == 0 && !loader) {
-#pragma unroll
-      for (int g = 1; g < KS; ++g)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] += rbuf[(((g - 1) * WM * WN * MT * NT + slot + i * NT + j) * 16 + r) * 64 + lane];
-    }
-  }
-
-  stamp(4);
-  // ================= cross-block K-split: publish the partial tile; the LAST arriving slice sums all slices (in slice
-  // order: bit-reproducible) and runs the epilogue.  No spinning.  Hand-off without fences (MI355X_MICROARCH.md, inter-workgroup
-  // visibility, "valid forms"): every partial is written with write-through (`sc1`) stores, drained with vmcnt(0) before the
-  // workgroup's agent-scope ticket; the last arriver reads the partials with `sc1` loads, which bypass its own XCD's L2.  An
-  // agent-scope release fence instead writes back the XCD's whole dirty L2 -- 3-6 us per kernel in the phase trace, as long as
-  // the K loop of the 8^3 / 4^3 layers itself. =======
-  if (kz > 1) {
-    constexpr int NSLOT = WM * WN * MT * NT;
-    const long tile_id = blockIdx.x + (long)gridDim.x * blockIdx.y;
-    float* part = a.kz_part + (tile_id * kz) * NSLOT * 1024;
-    const int slot = (wm * WN + wn) * MT * NT;
-    if (kg == 0 && !loader) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float* dst = part + (((long)blockIdx.z * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane;
-#if MMNN_KZ_FENCED
-            *dst = acc[i][j][r];
-#else
-            __hip_atomic_store(dst, acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // global_store_dword ... sc1
-#endif
-          }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave drains its stores before the barrier
-    __syncthreads();
-    unsigned* ticket = reinterpret_cast<unsigned*>(ecoef + C::ECOEF * M_B);
-    if (tid == 0) {
-#if MMNN_KZ_FENCED
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // cumulative over the barrier: publishes the whole workgroup's stores
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the compiler may drop the wait after buffer_wbl2: MI355X_MICROARCH.md, compiler hazard)
-#endif
-      *ticket = __hip_atomic_fetch_add(a.kz_cnt + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    stamp(5);
-    const unsigned arrived = *ticket;
-    if (arrived != (unsigned)(kz - 1)) return;            // not the last slice of this tile: done
-    // Ready for the next launch: nobody else touches this tile's counter any more in THIS launch (all kz slices have arrived), and the
-    // kernel boundary orders the store before the next launch's first add.
-    if (tid == 0) __hip_atomic_store(a.kz_cnt + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if MMNN_KZ_FENCED
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // every reading wave: drops this CU's stale L1 lines of the partial tiles
-#endif
-    if constexpr (KS > 1) {
-      // Every wave group takes 16 / KS accumulator rows of each tile and has ALL slices' loads in flight at once (slices past kz
-      // re-read the last one and add an exact zero): one memory round trip instead of kz / 2 dependent ones by the group-0 waves
-      // alone (phase "kz sum": 3.7k of a 27k-cycle launch at kz = 8).  Summed in slice order as before -- same bits -- and handed to
-      // the epilogue waves through the staging area, which is free since the barriers above.
-      constexpr int RP = 16 / KS;                       // rows per wave group
-      constexpr int ZB = (RP <= 4) ? 8 : 4;             // slices in flight: at most 32 loads per lane
-      float* xbuf = Xs;
-      if (!loader) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) {
-            float sacc[RP];
-#pragma unroll
-            for (int q = 0; q < RP; ++q) sacc[q] = 0.f;
-            for (int z0 = 0; z0 < kz; z0 += ZB) {
-              float pz[ZB][RP];
-#pragma unroll
-              for (int z = 0; z < ZB; ++z) {
-                const int zc = min(z0 + z, kz - 1);
-#pragma unroll
-                for (int q = 0; q < RP; ++q) {
-                  const float* sp = part + (((long)zc * NSLOT + slot + i * NT + j) * 16 + kg * RP + q) * 64 + lane;
-#if MMNN_KZ_FENCED
-                  pz[z][q] = *sp;
-#else
-                  pz[z][q] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);            // global_load_dword ... sc1
-#endif
-                }
-              }
-#pragma unroll
-              for (int z = 0; z < ZB; ++z)
-#pragma unroll
-                for (int q = 0; q < RP; ++q) sacc[q] += (z0 + z < kz) ? pz[z][q] : 0.f;
-            }
-#pragma unroll
-            for (int q = 0; q < RP; ++q) xbuf[((slot + i * NT + j) * 16 + kg * RP + q) * 64 + lane] = sacc[q];
-          }
-      }
-      __syncthreads();
+    if constexpr (KS > 1) tail.group_reduce(loader, acc);
+    stamp(4);
+    if (kz > 1) {
+      // publish the partial tile; the LAST arriving slice sums all slices (in slice order: bit-reproducible) and runs the epilogue
       if (kg == 0 && !loader) {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-          for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = xbuf[((slot + i * NT + j) * 16 + r) * 64 + lane];
+          for (int j = 0; j < NT; ++j) kz_publish_rows<16>(part, NSLOT, slot + i * NT + j, 0, lane, blockIdx.z, acc[i][j]);
       }
-    } else {
+      if (!kz_last()) return;                               // not the last slice of this tile: done
+      tail.kz_collect(part, kz, loader, acc);
+    }
+    stamp(6);
+    // the wide epilogue reuses the staging area: with an in-block K-split the group-0 waves were still reading their partners'
+    // accumulators (kz == 1) or the summed slices (kz > 1) from it
+    if (C::WIDE && KS > 1) __syncthreads();
     if (kg == 0 && !loader) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-          // kz is 2, 4 or 8: two slices' loads are in flight together (one memory round trip per pair), summed in slice order
-          for (int z = 0; z < kz; z += 2) {
-            float p0[16], p1[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float* s0 = part + (((long)z * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane;
-              const float* s1 = part + (((long)(z + 1) * NSLOT + slot + i * NT + j) * 16 + r) * 64 + lane;
-#if MMNN_KZ_FENCED
-              p0[r] = *s0; p1[r] = *s1;
-#else
-              p0[r] = __hip_atomic_load(s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);              // global_load_dword ... sc1
-              p1[r] = __hip_atomic_load(s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] + p0[r]) + p1[r];
-          }
-        }
+      const bool wide_ok = C::WIDE && (V & 3) == 0 && ((TAPS == 27) ? ((a.W & 3) == 0) : true) && ((((uintptr_t)outn | (uintptr_t)exn) & 15) == 0);
+      if (C::WIDE && wide_ok) tail.epilogue_wide(acc);
+      else tail.epilogue_direct(acc);
     }
-    }
-  }
-
-  stamp(6);
-  // the wide epilogue reuses the staging area: with an in-block K-split the group-0 waves were still reading their partners'
-  // accumulators (kz == 1) or the summed slices (kz > 1) from it
-  if (C::WIDE && KS > 1) __syncthreads();
-  // ================= epilogue =================
-
-  int vox[NT];
-  bool vok[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int t = (wn * NT + j) * 32 + l31;
-    if (TAPS == 27) {
-      const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
-      const int d = d0 + dz, h = h0 + hy, w = w0 + wx;
-      vok[j] = d < a.D && h < a.H && w < a.W;
-      vox[j] = (d * a.H + h) * a.W + w;
-    } else {
-      vox[j] = v0_ + t;
-      vok[j] = vox[j] < V;
-    }
-  }
-
-  if (kg == 0 && !loader) {
-  // The mask epilogues read one (ex) or two (ex, out) tensors per element.  Their loads are issued BEFORE the stores: `out` may
-  // alias `ex` as far as the compiler knows, so a load placed after a store is never hoisted above it and every accumulator row
-  // would pay a full memory round trip of its own (phase trace r02: 34 us of a 126 us block in block 1's data gradient).  One
-  // tensor (MASK_STORE): the whole tile's loads go out together; two tensors (MASK_ACCUM): one 32-row slab at a time (register
-  // budget: the big tiles of block 1 must stay at two waves per SIMD).  Element offsets are 32-bit (host check: M * V < 2^31),
-  // so an address costs one register beside the uniform base pointer.
-  constexpr bool MASK = (EPI == EPI_MASK_STORE || EPI == EPI_MASK_ACCUM);
-  // Wide form (big tiles, 16-byte aligned tensors): an MFMA accumulator holds ONE voxel per lane and row, so the direct form below
-  // moves 4 bytes per lane and instruction -- 128..192 memory instructions per thread, and the address coalescer, not HBM, bounds
-  // the epilogue (phase trace r02: 33k of a block's 85k cycles in block 1's conv1 data gradient, 40k of 290k in conv2's).  Each
-  // 32 x 32 accumulator tile is therefore transposed through LDS (wave-private, the staging buffers are free) so that a lane holds
-  // 4 consecutive voxels of 4 rows: every global access becomes a dwordx4 -- a quarter of the memory instructions.
-  const bool wide_ok = C::WIDE && (V & 3) == 0 && ((TAPS == 27) ? ((a.W & 3) == 0) : true) && ((((uintptr_t)outn | (uintptr_t)exn) & 15) == 0);
-  if (C::WIDE && wide_ok) {
-    float* tb = Xs + (wm * WN + wn) * (32 * C::TSTRIDE);
-    const int q4 = 4 * (lane & 7), rl = lane >> 3;            // this lane's voxel quad and first row within a tile
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      f32x4 vt[NT][4], xq[MASK ? NT : 1][4], gq[(EPI == EPI_MASK_ACCUM) ? NT : 1][4];
-      unsigned off[NT][4];
-      bool okq[NT][4];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        // voxel quad of this lane in tile j
-        const int t = (wn * NT + j) * 32 + q4;
-        int vq; bool vk;
-        if (TAPS == 27) {
-          const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
-          const int d = d0 + dz, h = h0 + hy, w = w0 + wx;
-          vk = d < a.D && h < a.H && w < a.W;
-          vq = (d * a.H + h) * a.W + w;
-        } else {
-          vq = v0_ + t;
-          vk = vq < V;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();        // the previous tile's reads precede these writes (LDS executes a wave's accesses in order)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tb[acc_row(r, half) * C::TSTRIDE + l31] = acc[i][j][r];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int ml = wm * MT * 32 + i * 32 + rl + 8 * k;
-          vt[j][k] = *reinterpret_cast<const f32x4*>(tb + (rl + 8 * k) * C::TSTRIDE + q4);
-          okq[j][k] = vk && (m0 + ml) < a.M;
-          off[j][k] = okq[j][k] ? (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vq : 0u;      // unconditional loads (clamped)
-        }
-      }
-      // all loads of the slab before its stores (see the note on aliasing below)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (MASK) xq[MASK ? j : 0][k] = *reinterpret_cast<const f32x4*>(exn + off[j][k]);
-          if (EPI == EPI_MASK_ACCUM) gq[(EPI == EPI_MASK_ACCUM) ? j : 0][k] = *reinterpret_cast<const f32x4*>(outn + off[j][k]);
-        }
-      float s0[4], s1[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int ml = wm * MT * 32 + i * 32 + rl + 8 * k;
-        const float ea = ecoef[ml], eb = ecoef[M_B + ml], mu = ecoef[2 * M_B + ml], rs = ecoef[3 * M_B + ml], gm = ecoef[4 * M_B + ml];
-        const float ds = ecoef[5 * M_B + ml];
-        float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          if (okq[j][k]) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (MASK) {
-                const float x = xq[MASK ? j : 0][k][e];
-                const float pre = fmaf(ea, x, eb);
-                const float z = pre > 0.f ? vt[j][k][e] : 0.f;
-                const float xh = (x - mu) * rs;
-                t0 += z;
-                t1 += z * xh;
-                o[e] = (EPI == EPI_MASK_STORE) ? z : gq[(EPI == EPI_MASK_ACCUM) ? j : 0][k][e] + gm * z;
-              } else {     // EPI_STORE_STATS: channel dropout scale, sums for the consumer's batch statistics
-                const float val = vt[j][k][e] * ds;
-                t0 += val;
-                t1 += val * val;
-                o[e] = val;
-              }
-            }
-            *reinterpret_cast<f32x4*>(outn + off[j][k]) = o;
-          }
-        }
-        s0[k] = t0; s1[k] = t1;
-      }
-      if (want_sums) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float r0 = s0[k], r1 = s1[k];
-          r0 += swz_xor<1>(r0); r1 += swz_xor<1>(r1);
-          r0 += swz_xor<2>(r0); r1 += swz_xor<2>(r1);
-          r0 += swz_xor<4>(r0); r1 += swz_xor<4>(r1);
-          if ((lane & 7) == 0) {
-            const int ml = wm * MT * 32 + i * 32 + rl + 8 * k;
-            red0[wn * M_B + ml] = r0;
-            red1[wn * M_B + ml] = r1;
-          }
-        }
-      }
-    }
-  } else {
-  if (ALL_ROWS) load_xall();
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    float s0[16], s1[16];
-    float xe[(MASK && !ALL_ROWS) ? 16 : 1][NT], go[(EPI == EPI_MASK_ACCUM) ? 16 : 1][NT];
-    if (MASK && !ALL_ROWS) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int ml = wm * MT * 32 + i * 32 + acc_row(q, half);
-        const bool mok = (m0 + ml) < a.M;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const unsigned o = (mok && vok[j]) ? (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vox[j] : 0u;
-          xe[(MASK && !ALL_ROWS) ? q : 0][j] = exn[o];
-          if (EPI == EPI_MASK_ACCUM) go[(EPI == EPI_MASK_ACCUM) ? q : 0][j] = outn[o];
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int ml = wm * MT * 32 + i * 32 + acc_row(r, half);
-      const bool mok = (m0 + ml) < a.M;
-      float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const bool ok = mok && vok[j];
-        const unsigned o = (unsigned)(m0 + ml) * (unsigned)V + (unsigned)vox[j];
-        float val = acc[i][j][r];
-        if (EPI == EPI_STORE) {
-          if (ok) outn[o] = val;
-        } else if (EPI == EPI_STORE_STATS) {
-          val *= ecoef[5 * M_B + ml];
-          if (ok) {
-            outn[o] = val;
-            t0 += val;
-            t1 += val * val;
-          }
-        } else {
-          if (ok) {
-            const float x = ALL_ROWS ? xall[ALL_ROWS ? i : 0][ALL_ROWS ? r : 0][j] : xe[(MASK && !ALL_ROWS) ? r : 0][j];
-            const float pre = fmaf(ecoef[ml], x, ecoef[M_B + ml]);
-            const float z = pre > 0.f ? val : 0.f;
-            const float xh = (x - ecoef[2 * M_B + ml]) * ecoef[3 * M_B + ml];
-            t0 += z;
-            t1 += z * xh;
-            if (EPI == EPI_MASK_STORE) outn[o] = z;
-            else outn[o] = go[(EPI == EPI_MASK_ACCUM) ? r : 0][j] + ecoef[4 * M_B + ml] * z;
-          }
-        }
-      }
-      s0[r] = t0;
-      s1[r] = t1;
-    }
-    if (want_sums) {
-      const float r0 = half_reduce16(s0, lane);
-      const float r1 = half_reduce16(s1, lane);
-      if ((lane & 1) == 0) {
-        const int ml = wm * MT * 32 + i * 32 + acc_row((l31 >> 1) & 15, half);
-        red0[wn * M_B + ml] = r0;
-        red1[wn * M_B + ml] = r1;
-      }
-    }
-  }
-  }
-  }
   }
   stamp(7);
   if (want_sums) {
     __syncthreads();
     for (int m = tid; m < M_B; m += NTHREADS) {
       if (m0 + m >= a.M) continue;
-      double v0d = 0.0, v1d = 0.0;
-#pragma unroll
-      for (int j = 0; j < WN; ++j) { v0d += (double)red0[j * M_B + m]; v1d += (double)red1[j * M_B + m]; }
-      if (EPI == EPI_STORE_STATS) {
-        atomicAdd(a.st_out.sum + (long)rep * a.st_out.stride + a.st_out.off + m0 + m, v0d);
-        atomicAdd(a.st_out.sq + (long)rep * a.st_out.stride + a.st_out.off + m0 + m, v1d);
-      } else {
-        atomicAdd(a.dbeta + (long)rep * a.M + m0 + m, v0d);
-        atomicAdd(a.dgamma + (long)rep * a.M + m0 + m, v1d);
-        if (EPI == EPI_MASK_ACCUM) {
-          const double g = (double)ecoef[4 * M_B + m];
-          atomicAdd(a.s_acc.sum + (long)rep * a.s_acc.stride + a.s_acc.off + m0 + m, g * v0d);
-          atomicAdd(a.s_acc.sq + (long)rep * a.s_acc.stride + a.s_acc.off + m0 + m, g * v1d);
-        }
-      }
+      flush_row_sums<EPI, WN>(a, rep, m0 + m, red0 + m, red1 + m, M_B, EpiRow<M_B>{ecoef + m}.gamma());
     }
   }
-  if (pf_sink + pf_sink2 == 1.2345678e-33f) a.out[0] = pf_sink;     // never true in practice: the prefetched values are not used
+  prefetch_sink(a, pf_sink, pf_sink2);
   stamp(8);
   if (tracing) {
     a.trace[10] = ((unsigned long long)TAPS << 48) | ((unsigned long long)PRO << 40) | ((unsigned long long)EPI << 32) | ((unsigned long long)a.M << 16) | (unsigned long long)a.Cin;
