@@ -2,8 +2,26 @@
 // gradient on fp32 MFMA.  Reference: models/densenet.py:199-202 and their autograd adjoints (main.py:469).
 #include "stem.hpp"
 #include "reduce.hpp"
+#include "wgrad_tile.hpp"   // tile walk, k-step loop, prologue element, slab store: shared with the dense-layer weight gradients
 
 namespace mmnn {
+
+// Two per-channel sums of a workgroup leave as fp64 atomics on replica blockIdx.x & (NREP - 1): v0 onto s0[rep * stride + c], v1 onto s1[..].
+__device__ __forceinline__ void stat_atomics(double* s0, double* s1, long stride, int c, double v0, double v1) {
+  const int rep = blockIdx.x & (NREP - 1);
+  atomicAdd(s0 + rep * stride + c, v0);
+  atomicAdd(s1 + rep * stride + c, v1);
+}
+// Tail of the pool kernels (256 threads): each thread's two partial sums -> wave_sum -> red[k][wave] -> thread 0 adds the four waves' values
+// in fp64, left to right from wave 0 -> stat_atomics.  Every thread of the block calls it (one barrier inside).
+__device__ __forceinline__ void pool_flush_sums(float s0, float s1, float (&red)[2][4], double* d0, double* d1, long stride, int c) {
+  s0 = wave_sum(s0); s1 = wave_sum(s1);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    stat_atomics(d0, d1, stride, c, (double)red[0][0] + red[0][1] + red[0][2] + red[0][3], (double)red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+}
 
 // =====================================================================================================================
 // conv0 forward.  Implicit GEMM: i = output channel (2 tiles of 32), j = 32 consecutive output voxels along W,
@@ -32,13 +50,8 @@ __global__ void __launch_bounds__(256, 2) stem_conv_kernel(const StemConvArgs a)
   float* red = smem;                          // [4 waves][2][64] per-wave partial sums: reuses buffer 0 after the last kd slice
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
   const int Vi = a.D * a.H * a.W, Vo = a.Do * a.Ho * a.Wo;
-  int b = blockIdx.x;
-  const int nw = (a.Wo + SC_TW - 1) / SC_TW, nh = (a.Ho + SC_TH - 1) / SC_TH, nd = (a.Do + SC_TD - 1) / SC_TD;
-  const int wo0 = (b % nw) * SC_TW; b /= nw;
-  const int ho0 = (b % nh) * SC_TH; b /= nh;
-  const int do0 = (b % nd) * SC_TD; b /= nd;
-  const int n = b;
-  const int rep = blockIdx.x & (NREP - 1);
+  int n, do0, ho0, wo0;
+  TileGrid<SC_TD, SC_TH, SC_TW>(a.Do, a.Ho, a.Wo).origin(blockIdx.x, n, do0, ho0, wo0);
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -64,8 +77,7 @@ __global__ void __launch_bounds__(256, 2) stem_conv_kernel(const StemConvArgs a)
   // a clamped address: uniform control flow keeps all loads of a slice in flight together).
   // 70 columns per row: the odd-Cin path pairs taps (kw, kw+1) across lane halves, so its zero-weight pad tap kw = 7 reads parity-1
   // entry l31 + 3 <= 34; that entry must hold a finite value (0 * garbage-NaN would poison the tile). ----
-  typedef const __attribute__((address_space(1))) float* gcf;
-  auto ldg = [](gcf base, unsigned byte_off) { return *(gcf)((const __attribute__((address_space(1))) char*)base + byte_off); };
+  const Ldg ldg;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
   const int wa = 2 * wo0 + lane - 3, wb_ = wa + 64;
   const bool oka = (unsigned)wa < (unsigned)a.W, okb = lane < 6 && (unsigned)wb_ < (unsigned)a.W;
@@ -228,8 +240,7 @@ __global__ void __launch_bounds__(256, 2) stem_conv_kernel(const StemConvArgs a)
     if (tid < a.M) {
       double v0 = 0.0, v1 = 0.0;
       for (int j = 0; j < 4; ++j) { v0 += (double)red[j * 128 + tid]; v1 += (double)red[j * 128 + 64 + tid]; }
-      atomicAdd(a.st_out.sum + (long)rep * a.st_out.stride + a.st_out.off + tid, v0);
-      atomicAdd(a.st_out.sq + (long)rep * a.st_out.stride + a.st_out.off + tid, v1);
+      stat_atomics(a.st_out.sum + a.st_out.off, a.st_out.sq + a.st_out.off, a.st_out.stride, tid, v0, v1);
     }
   }
 }
@@ -287,17 +298,7 @@ __global__ void __launch_bounds__(256) stem_pool_kernel(const StemPoolArgs a) {
     a.idx[((long)n * a.C + c) * Vo + p] = (unsigned char)bi;
     s0 = best; s1 = best * best;
   }
-  if (a.st_out.sum) {
-    s0 = wave_sum(s0); s1 = wave_sum(s1);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int rep = blockIdx.x & (NREP - 1);
-      atomicAdd(a.st_out.sum + (long)rep * a.st_out.stride + a.st_out.off + c, (double)red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-      atomicAdd(a.st_out.sq + (long)rep * a.st_out.stride + a.st_out.off + c, (double)red[1][0] + red[1][1] + red[1][2] + red[1][3]);
-    }
-  }
+  if (a.st_out.sum) pool_flush_sums(s0, s1, red, a.st_out.sum + a.st_out.off, a.st_out.sq + a.st_out.off, a.st_out.stride, c);
 }
 
 // LDS-tiled version: one block = (n, c, 4 x 4 pooled rows, full width).  The 9 x 9 conv-output rows those windows cover are
@@ -364,17 +365,7 @@ __global__ void __launch_bounds__(256) stem_pool_tiled_kernel(const StemPoolArgs
     a.idx[((long)n * a.C + c) * Vo + p] = (unsigned char)bi;
     s0 += best; s1 += best * best;
   }
-  if (a.st_out.sum) {
-    s0 = wave_sum(s0); s1 = wave_sum(s1);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int rep = blockIdx.x & (NREP - 1);
-      atomicAdd(a.st_out.sum + (long)rep * a.st_out.stride + a.st_out.off + c, (double)red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-      atomicAdd(a.st_out.sq + (long)rep * a.st_out.stride + a.st_out.off + c, (double)red[1][0] + red[1][1] + red[1][2] + red[1][3]);
-    }
-  }
+  if (a.st_out.sum) pool_flush_sums(s0, s1, red, a.st_out.sum + a.st_out.off, a.st_out.sq + a.st_out.off, a.st_out.stride, c);
 }
 
 int launch_stem_pool(const StemPoolArgs& a, hipStream_t stream) {
@@ -482,15 +473,7 @@ __global__ void __launch_bounds__(256) stem_pool_bwd_kernel(const StemPoolBwdArg
       s0 += z; s1 += z * (x - mu) * rs;
     }
   }
-  s0 = wave_sum(s0); s1 = wave_sum(s1);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int rep = blockIdx.x & (NREP - 1);
-    atomicAdd(a.dbeta + (long)rep * a.C + c, (double)red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-    atomicAdd(a.dgamma + (long)rep * a.C + c, (double)red[1][0] + red[1][1] + red[1][2] + red[1][3]);
-  }
+  pool_flush_sums(s0, s1, red, a.dbeta, a.dgamma, a.C, c);
 }
 
 int launch_stem_pool_bwd(const StemPoolBwdArgs& a, hipStream_t stream) {
@@ -529,24 +512,17 @@ __global__ void __launch_bounds__(SW_THREADS) stem_wgrad_kernel(const StemWgradA
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
   const int Vi = a.D * a.H * a.W, Vo = a.Do * a.Ho * a.Wo;
   const int split = blockIdx.x, c = blockIdx.y;
-  const int nw = (a.Wo + SW_TW - 1) / SW_TW, nh = (a.Ho + SW_TH - 1) / SW_TH, nd = (a.Do + SW_TD - 1) / SW_TD;
-  const int ntiles = a.N * nw * nh * nd;
-  const int t_begin = (int)((long)ntiles * split / a.nsplit), t_end = (int)((long)ntiles * (split + 1) / a.nsplit);
-  if (tid < 64) {
-    float p = 0.f, q = 0.f, r = 0.f;
-    if (tid < a.M) bn_bwd_coef(a.gr, tid, p, q, r);
-    gcoef[tid] = p; gcoef[64 + tid] = q; gcoef[128 + tid] = r;
-  }
+  const TileGrid<SW_TD, SW_TH, SW_TW> grid(a.Do, a.Ho, a.Wo);
+  const int nw = grid.nw, nh = grid.nh, nd = grid.nd;
+  int t_begin, t_end;
+  split_range(a.N * grid.per_sample(), split, a.nsplit, t_begin, t_end);
+  if (tid < 64) pro_coef_row(gcoef, 64, tid, tid, tid < a.M, a.gr);      // no dropout in front of conv0: the unscaled rows are the final ones
   const int tap = wave * 32 + l31;                       // >= 343: padding lanes (results discarded)
   const int tkd = tap / 49, tkh = (tap / 7) % 7, tkw = tap % 7;
   const int tapoff = (tap < 343) ? tkd * SW_PS + tkh * SW_RS + tkw : 0;
   const float* xl = Xs + tapoff + half * (2 * SW_PS);    // voxel s+32 is one output depth slice further
   const float* yl = Ys + l31 * SW_YS + 32 * half;
-  f32x16 acc[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  f32x16 acc[2] = {};
 
   // ---- staging.  The (unconditional) global loads of tile t+1 are issued one barrier ahead of their LDS stores.  Everything a
   // thread needs to know about its items is worked out ONCE: with 11 waves a CU the vector ALU is shared with the matrix pipe, and
@@ -554,13 +530,12 @@ __global__ void __launch_bounds__(SW_THREADS) stem_wgrad_kernel(const StemWgradA
   // tile and wave = 7.6 per MFMA) held the kernel at 92 cycles per MFMA instead of 64 (tools/microbench/mfma_valu_overlap.hip:
   // 8 vector instructions per MFMA = 92).  Now: per-item LDS offset and 32-bit byte offset from a per-tile uniform base
   // (`global_load_dword v, v_off, s[base]`), validity = two compares against per-tile scalars, tile origin advanced by carries. ----
-  typedef const __attribute__((address_space(1))) float* gcf;
-  auto ldg = [](gcf base, unsigned byte_off) { return *(gcf)((const __attribute__((address_space(1))) char*)base + byte_off); };
   constexpr int XT = 19 * 37;                      // threads staging the input halo: 19 of its 81 (plane, row) pairs x 37 columns a pass
   constexpr int X_IT = 5, Y_IT = 6;                // 81 / 19 passes;  64 x 64 gradient values / 704 threads
   static_assert(X_IT * 19 >= SW_PLANES * SW_ROWS && Y_IT * SW_THREADS >= 64 * 64 && SW_THREADS >= XT, "staging passes");
   constexpr int X_DUMMY = SW_XN - 1, Y_DUMMY = 64 * SW_YS - 1;   // padding words: where items that do not exist write their zero
   static_assert(X_DUMMY > (SW_PLANES - 1) * SW_PS + (SW_ROWS - 1) * SW_RS + 36, "dummy word inside the used halo");
+  const Ldg ldg;
   const int xci = tid % 37, xrow0 = tid / 37;
   int x_pl[X_IT], x_r[X_IT], x_dst[X_IT];
   unsigned x_rel[X_IT];
@@ -588,14 +563,8 @@ __global__ void __launch_bounds__(SW_THREADS) stem_wgrad_kernel(const StemWgradA
   }
   float xr[X_IT], y0[Y_IT], y1[Y_IT];
   unsigned okx = 0, oky = 0;
-  int ln, ld0, lh0, lw0;                            // origin of the NEXT tile to load
-  {
-    int b = t_begin;
-    lw0 = (b % nw) * SW_TW; b /= nw;
-    lh0 = (b % nh) * SW_TH; b /= nh;
-    ld0 = (b % nd) * SW_TD; b /= nd;
-    ln = b;
-  }
+  int ln, ld0, lh0, lw0;                            // origin of the NEXT tile to load: decoded once, then advanced by carries (no divisions per tile)
+  grid.origin(t_begin, ln, ld0, lh0, lw0);
   auto load_tile = [&]() {
     const int dbase = 2 * ld0 - 3, hbase = 2 * lh0 - 3, wbase = 2 * lw0 - 3;
     gcf xb = (gcf)(a.x + ((long)ln * a.Cin + c) * Vi + ((long)dbase * a.H + hbase) * a.W + wbase);
@@ -629,35 +598,17 @@ __global__ void __launch_bounds__(SW_THREADS) stem_wgrad_kernel(const StemWgradA
 #pragma unroll
     for (int i = 0; i < Y_IT; ++i) {
       const int m = min(wave + 11 * i, 63);
-      ys[y_dst[i]] = ((oky >> i) & 1u) ? fmaf(gcoef[m], y0[i], fmaf(gcoef[64 + m], y1[i], gcoef[128 + m])) : 0.f;
+      ys[y_dst[i]] = ((oky >> i) & 1u) ? pro_apply<PRO_GRAD>(gcoef, 64, m, y0[i], y1[i]) : 0.f;
     }
   };
-  // k-steps [S0, S0 + 16) of a tile x 2 output-channel tiles; operand reads one step ahead of the MFMAs
+  // mfma_ksteps over k-steps [S0, S0 + 16) of a tile: A = the two 32-row tiles of dOut, B = this wave's 32 taps
   auto mfma_half = [&](int buf, int S0) {
     const float* xb = xl + buf * SW_XN;
     const float* yb = yl + buf * (64 * SW_YS);
-    auto rd = [&](int s, float (&av)[2], float& bv) {
-      bv = xb[(2 * (s / SW_TW)) * SW_RS + 2 * (s % SW_TW)];      // s < 32: dz = 0, hy = s/16, wx = s%16
-      av[0] = yb[s];
-      av[1] = yb[32 * SW_YS + s];
-    };
-    auto mm = [&](const float (&av)[2], float bv) {
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv, acc[1], 0, 0, 0);
-    };
-    float a0[2], a1[2], b0, b1;
-    rd(S0, a0, b0);
-#pragma unroll
-    for (int s = 0; s < 16; s += 2) {
-      rd(S0 + s + 1, a1, b1);
-      __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-      mm(a0, b0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      if (s + 2 < 16) rd(S0 + s + 2, a0, b0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-      mm(a1, b1);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    }
+    mfma_ksteps<16, 2, 1>(
+        acc, [&](int s, float (&av)[2]) { av[0] = yb[S0 + s]; av[1] = yb[32 * SW_YS + S0 + s]; },
+        [&](int s, float (&bv)[1]) { bv[0] = xb[(2 * ((S0 + s) / SW_TW)) * SW_RS + 2 * ((S0 + s) % SW_TW)]; },      // s < 32: dz = 0, hy = s/16, wx = s%16
+        NoFiller{});
   };
   __syncthreads();                                   // gcoef visible
   if (t_begin < t_end) {
@@ -674,14 +625,9 @@ __global__ void __launch_bounds__(SW_THREADS) stem_wgrad_kernel(const StemWgradA
     __syncthreads();
     if (tile + 2 < t_end) load_tile();
   }
-  float* out = a.slab + (long)split * a.slab_stride + (long)c * a.M * 352;
+  float* out = a.slab + (long)split * a.slab_stride + (long)c * a.M * 352 + tap;      // slab[split][c][m][352 taps]
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = t * 32 + acc_row(r, half);
-      if (m < a.M) out[(long)m * 352 + tap] = acc[t][r];
-    }
+  for (int t = 0; t < 2; ++t) store_acc_tile(acc[t], out, 352, t * 32, a.M, half, true);
 }
 
 int stem_wgrad_pick_splits(int N, int Do, int Ho, int Wo, int Cin) {

@@ -14,7 +14,7 @@
 #include <type_traits>
 
 #include "common.hpp"
-#include "fprop.hpp"
+#include "wgrad_tile.hpp"   // the blocks both bodies below are built from, each with its summing order
 
 namespace mmnn {
 
@@ -48,12 +48,6 @@ int wgrad_pick_splits(int taps, int N, int D, int H, int W, int M, int Cin, int 
 #define MMNN_TRACE_TID 0     // thread whose phase stamps a trace build records (developer builds only; 320 = a 4-tap wave of wgrad3)
 #endif
 
-// Pointers read from a device-resident argument table (the batched kernels) are "generic" to the compiler, and every access
-// through them becomes a FLAT instruction -- which counts on the LDS counter (lgkmcnt) as well as on vmcnt, so a wait for an LDS
-// operand inside the MFMA loop also waits for the global loads in flight.  The tile loops therefore load through pointers that
-// are explicitly in the global address space (kernel arguments passed by value get this automatically).
-#define MMNN_GLOBAL __attribute__((address_space(1)))
-
 // ----------------------------------------------------------------------------------------------------------------
 // (r02: a loader / compute wave specialisation of this kernel -- waves 0-3 stage tile t+1 into a second LDS buffer and take one tap,
 // waves 4-7 take 6,6,6,5 taps, one barrier per tile -- measured 10 % SLOWER at 32^3 (1000 vs 905 us for block 1's six layers), 13 %
@@ -74,42 +68,21 @@ struct Wg3Cfg {
   static size_t smem_bytes() { return sizeof(float) * (2 * STAGE + 3 * 32 + 2 * 32 + 3 * 32); }   // two tiles: see wgrad3_body
 };
 
-// MFMA over one staged 64-voxel tile for NTP taps: 32 k-steps; the operand reads of step s+1 are issued before the MFMAs of
-// step s (two register sets).  Accumulators are passed by reference so that they stay in registers in both instantiations.
-// filler(s) is called once per k-step, between the MFMA groups: the caller's staging work for the NEXT tile (BN+ReLU, LDS writes into
-// the other buffer, global loads of the tile after) issues in the shadow of this wave's own MFMAs -- the matrix pipe is busy 64 cycles
-// per instruction, an in-order wave has nothing else to issue meanwhile.
+// mfma_ksteps over one staged 64-voxel tile: A = the wave's 32 dOut rows, B = the input box seen through each of NTP taps.  Step s reads
+// voxel s of the tile; lanes 32-63 get voxel s + 32 through the offset of their pointers.
 template <int NTP, int TD, int TH, int TW, class F>
 __device__ __forceinline__ void wg3_mfma(f32x16 (&acc)[4], const float* yl, const float* x0, const float* x1, const float* x2, const float* x3, F&& filler) {
   constexpr int RS = Wg3Cfg<TD, TH, TW>::RS, HS = Wg3Cfg<TD, TH, TW>::HS;
-  float a0, a1, b0[4], b1[4];
-  auto rd = [&](int s, float& av, float (&bv)[4]) {
-    const int wx = s % TW, hy = (s / TW) % TH, dz = s / (TW * TH);
-    const int p0 = (dz * HS + hy) * RS + wx;
-    av = yl[s];
-    bv[0] = x0[p0]; bv[1] = x1[p0]; bv[2] = x2[p0];
-    if (NTP == 4) bv[3] = x3[p0];
-  };
-  auto mm = [&](float av, const float (&bv)[4]) {
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[0], acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[1], acc[1], 0, 0, 0);
-    acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[2], acc[2], 0, 0, 0);
-    if (NTP == 4) acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[3], acc[3], 0, 0, 0);
-  };
-  rd(0, a0, b0);
-#pragma unroll
-  for (int s = 0; s < 32; s += 2) {
-    rd(s + 1, a1, b1);
-    __builtin_amdgcn_sched_group_barrier(0x100, NTP + 1, 0);
-    mm(a0, b0);
-    __builtin_amdgcn_sched_group_barrier(0x008, NTP, 0);
-    filler(s);
-    if (s + 2 < 32) rd(s + 2, a0, b0);
-    __builtin_amdgcn_sched_group_barrier(0x100, NTP + 1, 0);
-    mm(a1, b1);
-    __builtin_amdgcn_sched_group_barrier(0x008, NTP, 0);
-    filler(s + 1);
-  }
+  mfma_ksteps<32, 1, NTP>(
+      acc, [&](int s, float (&av)[1]) { av[0] = yl[s]; },
+      [&](int s, float (&bv)[NTP]) {
+        int wx, hy, dz;
+        tile_local<TH, TW>(s, wx, hy, dz);
+        const int p0 = (dz * HS + hy) * RS + wx;
+        bv[0] = x0[p0]; bv[1] = x1[p0]; bv[2] = x2[p0];
+        if constexpr (NTP == 4) bv[3] = x3[p0];
+      },
+      filler);
 }
 
 template <int PRO_X, int TD, int TH, int TW>
@@ -125,21 +98,16 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
   const int V = a.D * a.H * a.W;
   const int c0 = cg * 32;
-  const int nw = (a.W + TW - 1) / TW, nh = (a.H + TH - 1) / TH, nd = (a.D + TD - 1) / TD;
-  const int tiles_per_n = nw * nh * nd;
-  const int ntiles = a.N * tiles_per_n;
-  const int t_begin = (int)((long)ntiles * split / a.nsplit), t_end = (int)((long)ntiles * (split + 1) / a.nsplit);
+  const TileGrid<TD, TH, TW> grid(a.D, a.H, a.W);
+  int t_begin, t_end;
+  split_range(a.N * grid.per_sample(), split, a.nsplit, t_begin, t_end);
 
   // BN coefficients of both operands (one memory round trip over the fp64 statistics).  In the fast path they are computed
   // AFTER the first tile's loads were issued, so the two latencies overlap.
   auto coefficients = [&]() {
     if (tid < 32) {
-      float ca = 0.f, cb = 0.f, mu, rs;
-      if (PRO_X == PRO_BNRELU && c0 + tid < a.Cin) bn_fwd_coef(a.bn, c0 + tid, ca, cb, mu, rs);
-      xcoef[tid] = ca; xcoef[32 + tid] = cb;
-      float p = 0.f, q = 0.f, r = 0.f;
-      if (tid < a.M) bn_bwd_coef(a.gr, tid, p, q, r);
-      gbase[tid] = p; gbase[32 + tid] = q; gbase[64 + tid] = r;
+      pro_coef_row(xcoef, 32, tid, c0 + tid, PRO_X == PRO_BNRELU && c0 + tid < a.Cin, a.bn);
+      pro_coef_row(gbase, 32, tid, tid, tid < a.M, a.gr);
     }
   };
   const int tap0 = (wave < 5) ? wave * 3 : 15 + (wave - 5) * 4;       // first tap of this wave
@@ -156,25 +124,10 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
   }
   const float* yl = Ys + l31 * YS + 32 * half;
 
-  f32x16 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  // ---- MFMA over one staged tile: 32 k-steps (2 voxels each) x 3 taps; operand reads of step s+1 issued before the
-  // MFMAs of step s (two register sets) ----
+  f32x16 acc[4] = {};      // the chains start from zero and run over all of the block's tiles
   auto mfma_tile = [&](int boff, auto&& filler) {   // wave-uniform choice of the tap count; boff: float offset of the tile buffer
     if (ntap == 4) wg3_mfma<4, TD, TH, TW>(acc, yl + boff, xb[0] + boff, xb[1] + boff, xb[2] + boff, xb[3] + boff, filler);
     else wg3_mfma<3, TD, TH, TW>(acc, yl + boff, xb[0] + boff, xb[1] + boff, xb[2] + boff, xb[2] + boff, filler);
-  };
-  auto no_filler = [](int) {};
-  auto tile_origin = [&](int tile, int& n, int& d0, int& h0, int& w0) {
-    int b = tile;
-    w0 = (b % nw) * TW; b /= nw;
-    h0 = (b % nh) * TH; b /= nh;
-    d0 = (b % nd) * TD; b /= nd;
-    n = b;
   };
   const bool vec = ((a.W & 3) == 0) && ((TW & 3) == 0) && ((((uintptr_t)a.x | (uintptr_t)a.g0 | (uintptr_t)a.g1) & 15) == 0) && ((V & 3) == 0);
 
@@ -215,17 +168,18 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
 #pragma unroll
     for (int i = 0; i < Y_IT; ++i) {
       const int it = tid + i * NTHREADS, m = it >> 4, t = 4 * (it & 15);
-      const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
+      int wx, hy, dz;
+      tile_local<TH, TW>(t, wx, hy, dz);
       const bool ok = (it < Y_ITEMS) && m < a.M;
       y_s[i] = m * V + (dz * a.H + hy) * a.W + wx;
       y_k[i] = ok ? (m | (dz << 8) | (hy << 16) | (wx << 24)) : -1;
     }
     auto load_tile = [&](int tile) {
       int n, d0, h0, w0;
-      tile_origin(tile, n, d0, h0, w0);
-      const MMNN_GLOBAL float* xn = (const MMNN_GLOBAL float*)a.x + (long)n * a.x_ns + (long)(a.x_coff + c0) * V;
-      const MMNN_GLOBAL float* g0n = (const MMNN_GLOBAL float*)a.g0 + (long)n * a.g0_ns + (long)a.g0_coff * V;
-      const MMNN_GLOBAL float* g1n = (const MMNN_GLOBAL float*)a.g1 + (long)n * a.g1_ns + (long)a.g1_coff * V;
+      grid.origin(tile, n, d0, h0, w0);
+      const gcf xn = (gcf)a.x + (long)n * a.x_ns + (long)(a.x_coff + c0) * V;
+      const gcf g0n = (gcf)a.g0 + (long)n * a.g0_ns + (long)a.g0_coff * V;
+      const gcf g1n = (gcf)a.g1 + (long)n * a.g1_ns + (long)a.g1_coff * V;
       const int xbase = ((d0 - 1) * a.H + (h0 - 1)) * a.W + w0;      // tile origin of the halo box (may be negative: only used when in range)
       const int ybase = (d0 * a.H + h0) * a.W + w0;
       okv = okh = oky = 0;
@@ -274,10 +228,7 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
       if (u == 0) {
         if (ld_n != st_n) {   // dropout scale depends on the sample (wave-uniform, at most once per block and sample)
 #pragma unroll
-          for (int i = 0; i < Y_IT; ++i) {
-            const float sc = drop_scale(a.drop, ld_n, y_k[i] & 31);
-            y_p[i] = yb_p[i] * sc; y_q[i] = yb_q[i] * sc; y_r[i] = yb_r[i] * sc;
-          }
+          for (int i = 0; i < Y_IT; ++i) rescale_row(drop_scale(a.drop, ld_n, y_k[i] & 31), yb_p[i], yb_q[i], yb_r[i], y_p[i], y_q[i], y_r[i]);
           st_n = ld_n;
         }
         return;
@@ -288,18 +239,12 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
         if (i == u && tid + i * NTHREADS < XV_ITEMS) {
           const bool ok = (okv >> i) & 1u;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float o = (PRO_X == PRO_BNRELU) ? fmaxf(fmaf(xv_a[i], xv[i][e], xv_b[i]), 0.f) : xv[i][e];
-            X[xv_l[i] + e] = ok ? o : 0.f;
-          }
+          for (int e = 0; e < 4; ++e) X[xv_l[i] + e] = ok ? pro_elem<PRO_X>(xv_a[i], xv_b[i], 0.f, xv[i][e], 0.f) : 0.f;
         }
       }
 #pragma unroll
       for (int i = 0; i < XH_IT; ++i) {
-        if (XV_IT + i == u && tid + i * NTHREADS < XH_ITEMS) {
-          const float o = (PRO_X == PRO_BNRELU) ? fmaxf(fmaf(xh_a[i], xh[i], xh_b[i]), 0.f) : xh[i];
-          X[xh_l[i]] = ((okh >> i) & 1u) ? o : 0.f;
-        }
+        if (XV_IT + i == u && tid + i * NTHREADS < XH_ITEMS) X[xh_l[i]] = ((okh >> i) & 1u) ? pro_elem<PRO_X>(xh_a[i], xh_b[i], 0.f, xh[i], 0.f) : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < Y_IT; ++i) {
@@ -308,25 +253,20 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
           const int m = it >> 4, t = 4 * (it & 15);
           const bool ok = (oky >> i) & 1u;
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            Y[m * YS + t + e] = ok ? fmaf(y_p[i], y0[i][e], fmaf(y_q[i], y1[i][e], y_r[i])) : 0.f;
+          for (int e = 0; e < 4; ++e) Y[m * YS + t + e] = ok ? pro_elem<PRO_GRAD>(y_p[i], y_q[i], y_r[i], y0[i][e], y1[i][e]) : 0.f;
         }
       }
     };
-#if defined(MMNN_PHASE_TRACE)
-    const bool tracing = a.trace != nullptr && tid == MMNN_TRACE_TID && split < 16 && cg == 0;
-    unsigned long long tr[6] = {0, 0, 0, 0, 0, 0}, tprev = tracing ? __builtin_amdgcn_s_memtime() : 0;
-    auto lap = [&](int k) { if (tracing) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr[k] += t - tprev; tprev = t; } };
-#else
-    auto lap = [&](int) {};
-#endif
+    PhaseTrace pt(a.trace != nullptr && tid == MMNN_TRACE_TID && split < 16 && cg == 0);
     // Software pipeline over the block's tiles, two LDS buffers: while the MFMAs of tile t run out of buffer t&1, the same waves
     // write tile t+1 (already in registers) into the other buffer and then issue the global loads of tile t+2 -- all of it between
     // their own MFMAs.  One barrier per tile.  (r02 phase trace of the former store / barrier / MFMA / barrier sequence: 5.6k of a
     // tile's 19.9k cycles had the matrix pipe idle, both waves of each SIMD staging in lockstep.)
+    // (the sample of a tile is decoded BEFORE its load_tile, in the caller: decoded afterwards, or only inside load_tile, the same
+    // arithmetic lands elsewhere among the MFMAs of the 32-wide tiles: conv2_wgrad at 32^3 / 16^3 measured about 1 % slower, profiles/r08_wgrad_blocks_ab.txt)
     if (t_begin < t_end) {
       int n, d0, h0, w0;
-      tile_origin(t_begin, n, d0, h0, w0);
+      grid.origin(t_begin, n, d0, h0, w0);
       load_tile(t_begin); ld_n = n;
     }
     coefficients();
@@ -337,12 +277,12 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
       for (int u = 0; u < NUNITS; ++u) store_unit(u, Xs, Ys);
       if (t_begin + 1 < t_end) {
         int n, d0, h0, w0;
-        tile_origin(t_begin + 1, n, d0, h0, w0);
+        grid.origin(t_begin + 1, n, d0, h0, w0);
         load_tile(t_begin + 1); ld_n = n;
       }
     }
     __syncthreads();
-    lap(0);
+    pt.lap(0);
     constexpr int LOAD_AT = NUNITS + 1;      // k-step after which the registers are free again
     static_assert(LOAD_AT < 32, "staging pieces must fit the k-steps of a tile");
     for (int tile = t_begin; tile < t_end; ++tile) {
@@ -352,41 +292,28 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
       if (tile + 1 < t_end) {
         const int nxt = min(tile + 2, t_end - 1);     // the last tile is loaded twice (never stored the second time)
         int n2, d2, h2, w2;
-        tile_origin(nxt, n2, d2, h2, w2);
+        grid.origin(nxt, n2, d2, h2, w2);
         mfma_tile(cur * C::STAGE, [&](int s) {
           if (s < NUNITS) store_unit(s, Xn, Yn);
           if (s == LOAD_AT) { load_tile(nxt); ld_n = n2; }
         });
       } else {
-        mfma_tile(cur * C::STAGE, no_filler);
+        mfma_tile(cur * C::STAGE, NoFiller{});
       }
-      lap(4);
+      pt.lap(4);
       __syncthreads();
-      lap(5);
+      pt.lap(5);
     }
-#if defined(MMNN_PHASE_TRACE)
-    if (tracing) {
-      for (int k = 0; k < 6; ++k) a.trace[split * 16 + k] = tr[k];
-      a.trace[split * 16 + 6] = (unsigned long long)(t_end - t_begin);
-      a.trace[10] = (27ull << 48) | (9ull << 40) | ((unsigned long long)a.M << 16) | (unsigned long long)a.Cin;
-      a.trace[11] = ((unsigned long long)gridDim.x << 32) | ((unsigned long long)gridDim.y << 16) | gridDim.z;
-    }
-#endif
+    pt.finish(a.trace, split, 27, a.M, a.Cin, t_end - t_begin);
   } else {
   coefficients();
   int cur_n = -1;
   for (int tile = t_begin; tile < t_end; ++tile) {
-    int b = tile;
-    const int w0 = (b % nw) * TW; b /= nw;
-    const int h0 = (b % nh) * TH; b /= nh;
-    const int d0 = (b % nd) * TD; b /= nd;
-    const int n = b;
+    int n, d0, h0, w0;
+    grid.origin(tile, n, d0, h0, w0);
     if (n != cur_n) {   // dropout scale depends on the sample: refresh the dOut coefficients
       __syncthreads();
-      if (tid < 32) {
-        const float s = drop_scale(a.drop, n, tid);
-        gcoef[tid] = gbase[tid] * s; gcoef[32 + tid] = gbase[32 + tid] * s; gcoef[64 + tid] = gbase[64 + tid] * s;
-      }
+      rescale_rows(gbase, gcoef, 32, 0, n, a.drop, tid, NTHREADS);
       cur_n = n;
       __syncthreads();
     }
@@ -406,38 +333,30 @@ __device__ __forceinline__ void wgrad3_body(const WgradArgs& a, const int split,
       // unconditional load from a clamped address (a load under a divergent branch costs one memory round trip EACH)
       const bool ok = c0 + cl < a.Cin && (unsigned)d < (unsigned)a.D && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W;
       const float x = xn[ok ? (long)cl * V + ((long)d * a.H + h) * a.W + w : 0];
-      const float o = (PRO_X == PRO_BNRELU) ? fmaxf(fmaf(xcoef[cl], x, xcoef[32 + cl]), 0.f) : x;
-      Xs[cl * XS + (dz * HS + hy) * RS + q] = ok ? o : 0.f;
+      Xs[cl * XS + (dz * HS + hy) * RS + q] = ok ? pro_apply<PRO_X>(xcoef, 32, cl, x, 0.f) : 0.f;
     }
     // ---- stage dOut for the tile's 64 voxels ----
 #pragma unroll 4
     for (int it = tid; it < 32 * 64; it += NTHREADS) {
       const int t = it & 63, m = it >> 6;
-      const int wx = t % TW, hy = (t / TW) % TH, dz = t / (TW * TH);
+      int wx, hy, dz;
+      tile_local<TH, TW>(t, wx, hy, dz);
       const int d = d0 + dz, h = h0 + hy, w = w0 + wx;
       const bool ok = m < a.M && d < a.D && h < a.H && w < a.W;
       const long g = ok ? (long)m * V + ((long)d * a.H + h) * a.W + w : 0;
-      const float o = fmaf(gcoef[m], g0n[g], fmaf(gcoef[32 + m], g1n[g], gcoef[64 + m]));
+      const float o = pro_apply<PRO_GRAD>(gcoef, 32, m, g0n[g], g1n[g]);
       Ys[m * YS + t] = ok ? o : 0.f;
     }
     __syncthreads();
-    mfma_tile(0, no_filler);
+    mfma_tile(0, NoFiller{});
     __syncthreads();
   }
   }
   // ---- partial result: slab[split][tap][m][c] ----
-  float* out = a.slab + (long)split * a.slab_stride;
+  float* out = a.slab + (long)split * a.slab_stride + c0 + l31;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int tap = tap0 + j;
-    if (j < ntap) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = acc_row(r, half);
-        if (m < a.M && c0 + l31 < a.Cin) out[((long)tap * a.M + m) * a.Cin + c0 + l31] = acc[j][r];
-      }
-    }
-  }
+  for (int j = 0; j < 4; ++j)
+    if (j < ntap) store_acc_tile(acc[j], out + (long)(tap0 + j) * a.M * a.Cin, a.Cin, 0, a.M, half, c0 + l31 < a.Cin);
 }
 
 // Several layers in ONE launch (blockIdx.z = layer): the late dense blocks' weight gradients are a few dozen blocks per layer
@@ -490,55 +409,28 @@ __device__ __forceinline__ void wgrad1_body(const WgradArgs& a, const int split,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
   const int V = a.D * a.H * a.W;
   const int chunks_per_n = (V + VK - 1) / VK;
-  const int nchunks = a.N * chunks_per_n;
-  const int k_begin = (int)((long)nchunks * split / a.nsplit), k_end = (int)((long)nchunks * (split + 1) / a.nsplit);
+  int k_begin, k_end;
+  split_range(a.N * chunks_per_n, split, a.nsplit, k_begin, k_end);
 
   auto coefficients = [&]() {   // see wgrad3_body: computed after the first chunk's loads were issued (fast path)
-    for (int c = tid; c < CB; c += NTHREADS) {
-      float ca = 0.f, cb = 0.f, mu, rs;
-      if (PRO_X == PRO_BNRELU && c0 + c < a.Cin) bn_fwd_coef(a.bn, c0 + c, ca, cb, mu, rs);
-      xcoef[c] = ca; xcoef[CB + c] = cb;
-    }
-    for (int m = tid; m < 128; m += NTHREADS) {
-      float p = 0.f, q = 0.f, r = 0.f;
-      if (m0 + m < a.M) bn_bwd_coef(a.gr, m0 + m, p, q, r);
-      gbase[m] = p; gbase[128 + m] = q; gbase[256 + m] = r;
-    }
+    for (int c = tid; c < CB; c += NTHREADS) pro_coef_row(xcoef, CB, c, c0 + c, PRO_X == PRO_BNRELU && c0 + c < a.Cin, a.bn);
+    for (int m = tid; m < 128; m += NTHREADS) pro_coef_row(gbase, 128, m, m0 + m, m0 + m < a.M, a.gr);
   };
-  f32x16 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  f32x16 acc[4] = {};      // the chains start from zero and run over all of the block's tiles
   const float* al = As + l31 * S + 32 * half;
   const float* bl = Bs + (wave * 32 + l31) * S + 32 * half;
   const bool wave_has_channels = c0 + wave * 32 < a.Cin;
   const bool vec = (V & 3) == 0 && ((((uintptr_t)a.x | (uintptr_t)a.g0 | (uintptr_t)a.g1) & 15) == 0);
 
-  // ---- MFMA over one staged chunk of 64 voxels: 32 k-steps x 4 output-channel tiles, operand reads one step ahead ----
+  // mfma_ksteps over one staged chunk of 64 voxels: A = the four 32-row tiles of dOut, B = this wave's 32 input channels
   auto mfma_chunk = [&]() {
-    auto rd = [&](int s, float (&av)[4], float& bv) {
-      bv = bl[s];
+    mfma_ksteps<32, 4, 1>(
+        acc,
+        [&](int s, float (&av)[4]) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t) av[t] = al[t * 32 * S + s];
-    };
-    auto mm = [&](const float (&av)[4], float bv) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv, acc[t], 0, 0, 0);
-    };
-    float a0[4], a1[4], b0, b1;
-    rd(0, a0, b0);
-#pragma unroll
-    for (int s = 0; s < 32; s += 2) {
-      rd(s + 1, a1, b1);
-      __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-      mm(a0, b0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      if (s + 2 < 32) rd(s + 2, a0, b0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-      mm(a1, b1);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    }
+          for (int t = 0; t < 4; ++t) av[t] = al[t * 32 * S + s];
+        },
+        [&](int s, float (&bv)[1]) { bv[0] = bl[s]; }, NoFiller{});
   };
 
   if (vec) {
@@ -549,9 +441,9 @@ __device__ __forceinline__ void wgrad1_body(const WgradArgs& a, const int split,
     unsigned oka = 0, okb = 0;
     auto load_chunk = [&](int ch) {
       const int n = ch / chunks_per_n, v0 = (ch % chunks_per_n) * VK;
-      const MMNN_GLOBAL float* xn = (const MMNN_GLOBAL float*)a.x + (long)n * a.x_ns + (long)(a.x_coff + c0) * V;      // (see MMNN_GLOBAL)
-      const MMNN_GLOBAL float* g0n = (const MMNN_GLOBAL float*)a.g0 + (long)n * a.g0_ns + (long)(a.g0_coff + m0) * V;
-      const MMNN_GLOBAL float* g1n = (const MMNN_GLOBAL float*)a.g1 + (long)n * a.g1_ns + (long)(a.g1_coff + m0) * V;
+      const gcf xn = (gcf)a.x + (long)n * a.x_ns + (long)(a.x_coff + c0) * V;      // (see MMNN_GLOBAL)
+      const gcf g0n = (gcf)a.g0 + (long)n * a.g0_ns + (long)(a.g0_coff + m0) * V;
+      const gcf g1n = (gcf)a.g1 + (long)n * a.g1_ns + (long)(a.g1_coff + m0) * V;
       oka = okb = 0;
 #pragma unroll
       for (int i = 0; i < A_IT; ++i) {
@@ -582,8 +474,7 @@ __device__ __forceinline__ void wgrad1_body(const WgradArgs& a, const int split,
           const int q = it % (VK / 4), m = it / (VK / 4);
           const bool ok = (oka >> i) & 1u;
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            As[m * S + 4 * q + e] = ok ? fmaf(gcoef[m], ga[i][e], fmaf(gcoef[128 + m], gb[i][e], gcoef[256 + m])) : 0.f;
+          for (int e = 0; e < 4; ++e) As[m * S + 4 * q + e] = ok ? pro_apply<PRO_GRAD>(gcoef, 128, m, ga[i][e], gb[i][e]) : 0.f;
         }
       }
 #pragma unroll
@@ -593,51 +484,34 @@ __device__ __forceinline__ void wgrad1_body(const WgradArgs& a, const int split,
           const int q = it % (VK / 4), c = it / (VK / 4);
           const bool ok = (okb >> i) & 1u;
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            Bs[c * S + 4 * q + e] = ok ? ((PRO_X == PRO_BNRELU) ? fmaxf(fmaf(xcoef[c], xb[i][e], xcoef[CB + c]), 0.f) : xb[i][e]) : 0.f;
+          for (int e = 0; e < 4; ++e) Bs[c * S + 4 * q + e] = ok ? pro_apply<PRO_X>(xcoef, CB, c, xb[i][e], 0.f) : 0.f;
         }
       }
     };
     int cur_n = -1;
-#if defined(MMNN_PHASE_TRACE)
-    const bool tracing = a.trace != nullptr && tid == 0 && split < 16 && c0 == 0 && m0 == 0;
-    unsigned long long tr[6] = {0, 0, 0, 0, 0, 0}, tprev = tracing ? __builtin_amdgcn_s_memtime() : 0;
-    auto lap = [&](int k) { if (tracing) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr[k] += t - tprev; tprev = t; } };
-#else
-    auto lap = [&](int) {};
-#endif
+    PhaseTrace pt(a.trace != nullptr && tid == 0 && split < 16 && c0 == 0 && m0 == 0);
     if (k_begin < k_end) load_chunk(k_begin);
     coefficients();
-    lap(0);
+    pt.lap(0);
     for (int ch = k_begin; ch < k_end; ++ch) {
       const int n = ch / chunks_per_n;
-      if (n != cur_n) {
-        for (int m = tid; m < 128; m += NTHREADS) {
-          const float sc = drop_scale(a.drop, n, m0 + m);
-          gcoef[m] = gbase[m] * sc; gcoef[128 + m] = gbase[128 + m] * sc; gcoef[256 + m] = gbase[256 + m] * sc;
-        }
+      if (n != cur_n) {   // (the barrier in front: the one that ends the previous chunk, or none needed before the first)
+        rescale_rows(gbase, gcoef, 128, m0, n, a.drop, tid, NTHREADS);
         cur_n = n;
         __syncthreads();
       }
       store_chunk();
-      lap(1);
+      pt.lap(1);
       __syncthreads();
-      lap(2);
+      pt.lap(2);
       if (ch + 1 < k_end) load_chunk(ch + 1);
-      lap(3);
+      pt.lap(3);
       if (wave_has_channels) mfma_chunk();   // waves whose 32 channels lie beyond Cin only help staging (Cin = 64 / 96 with WC = 4)
-      lap(4);
+      pt.lap(4);
       __syncthreads();
-      lap(5);
+      pt.lap(5);
     }
-#if defined(MMNN_PHASE_TRACE)
-    if (tracing) {
-      for (int k = 0; k < 6; ++k) a.trace[split * 16 + k] = tr[k];
-      a.trace[split * 16 + 6] = (unsigned long long)(k_end - k_begin);
-      a.trace[10] = (1ull << 48) | (9ull << 40) | ((unsigned long long)a.M << 16) | (unsigned long long)a.Cin;
-      a.trace[11] = ((unsigned long long)gridDim.x << 32) | ((unsigned long long)gridDim.y << 16) | gridDim.z;
-    }
-#endif
+    pt.finish(a.trace, split, 1, a.M, a.Cin, k_end - k_begin);
   } else {
   coefficients();
   int cur_n = -1;
@@ -646,72 +520,39 @@ __device__ __forceinline__ void wgrad1_body(const WgradArgs& a, const int split,
     const int v0 = (ch % chunks_per_n) * VK;
     if (n != cur_n) {
       __syncthreads();
-      for (int m = tid; m < 128; m += NTHREADS) {
-        const float s = drop_scale(a.drop, n, m0 + m);
-        gcoef[m] = gbase[m] * s; gcoef[128 + m] = gbase[128 + m] * s; gcoef[256 + m] = gbase[256 + m] * s;
-      }
+      rescale_rows(gbase, gcoef, 128, m0, n, a.drop, tid, NTHREADS);
       cur_n = n;
       __syncthreads();
     }
     const float* xn = a.x + (long)n * a.x_ns + (long)(a.x_coff + c0) * V;
     const float* g0n = a.g0 + (long)n * a.g0_ns + (long)(a.g0_coff + m0) * V;
     const float* g1n = a.g1 + (long)n * a.g1_ns + (long)(a.g1_coff + m0) * V;
-    if (vec) {
-#pragma unroll 4
-      for (int it = tid; it < 128 * (VK / 4); it += NTHREADS) {
-        const int q = it % (VK / 4), m = it / (VK / 4);
-        const int v = v0 + 4 * q;
-        const bool ok = m0 + m < a.M && v < V;
-        const long go = ok ? (long)m * V + v : 0;
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(g0n + go);
-        const f32x4 g1 = *reinterpret_cast<const f32x4*>(g1n + go);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) As[m * S + 4 * q + e] = ok ? fmaf(gcoef[m], g0[e], fmaf(gcoef[128 + m], g1[e], gcoef[256 + m])) : 0.f;
-      }
-#pragma unroll 4
-      for (int it = tid; it < CB * (VK / 4); it += NTHREADS) {
-        const int q = it % (VK / 4), c = it / (VK / 4);
-        const int v = v0 + 4 * q;
-        const bool ok = c0 + c < a.Cin && v < V;
-        const f32x4 x = *reinterpret_cast<const f32x4*>(xn + (ok ? (long)c * V + v : 0));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Bs[c * S + 4 * q + e] = ok ? ((PRO_X == PRO_BNRELU) ? fmaxf(fmaf(xcoef[c], x[e], xcoef[CB + c]), 0.f) : x[e]) : 0.f;
-      }
-    } else {
 #pragma unroll 2
-      for (int it = tid; it < 128 * VK; it += NTHREADS) {
-        const int q = it % VK, m = it / VK;
-        const int v = v0 + q;
-        float o = 0.f;
-        if (m0 + m < a.M && v < V) o = fmaf(gcoef[m], g0n[(long)m * V + v], fmaf(gcoef[128 + m], g1n[(long)m * V + v], gcoef[256 + m]));
-        As[m * S + q] = o;
-      }
+    for (int it = tid; it < 128 * VK; it += NTHREADS) {
+      const int q = it % VK, m = it / VK;
+      const int v = v0 + q;
+      float o = 0.f;
+      if (m0 + m < a.M && v < V) o = pro_apply<PRO_GRAD>(gcoef, 128, m, g0n[(long)m * V + v], g1n[(long)m * V + v]);
+      As[m * S + q] = o;
+    }
 #pragma unroll 2
-      for (int it = tid; it < CB * VK; it += NTHREADS) {
-        const int q = it % VK, c = it / VK;
-        const int v = v0 + q;
-        float o = 0.f;
-        if (c0 + c < a.Cin && v < V) {
-          const float x = xn[(long)c * V + v];
-          o = (PRO_X == PRO_BNRELU) ? fmaxf(fmaf(xcoef[c], x, xcoef[CB + c]), 0.f) : x;
-        }
-        Bs[c * S + q] = o;
-      }
+    for (int it = tid; it < CB * VK; it += NTHREADS) {
+      const int q = it % VK, c = it / VK;
+      const int v = v0 + q;
+      float o = 0.f;
+      if (c0 + c < a.Cin && v < V) o = pro_apply<PRO_X>(xcoef, CB, c, xn[(long)c * V + v], 0.f);
+      Bs[c * S + q] = o;
     }
     __syncthreads();
     if (wave_has_channels) mfma_chunk();
     __syncthreads();
   }
   }
-  float* out = a.slab + (long)split * a.slab_stride;
+  // ---- partial result: slab[split][m][c] ----
   const int c = c0 + wave * 32 + l31;
+  float* out = a.slab + (long)split * a.slab_stride + c;
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + t * 32 + acc_row(r, half);
-      if (m < a.M && c < a.Cin) out[(long)m * a.Cin + c] = acc[t][r];
-    }
+  for (int t = 0; t < 4; ++t) store_acc_tile(acc[t], out, a.Cin, m0 + t * 32, a.M, half, c < a.Cin);
 }
 
 template <int PRO_X, int WC>
