@@ -387,7 +387,8 @@ int mmnn_transform_volumes(const mmnn_transform_desc* d, const mmnn_transform_pa
  * array axes x, y, z; the raw buffers are read as stored (x fastest).  A slope of 0, NaN or +-inf means "no scaling" (inter ignored
  * too); a non-finite inter counts as 0.  When the mask leaves nothing (an extent of 0) the plane is written as zeros.
  * Four launches (one of them a memset), no host synchronisation, no floating-point atomics: repeated calls are bit-identical. */
-#define MMNN_INGEST_SIZE   64     /* output extent per axis */
+#define MMNN_INGEST_SIZE      64   /* output extent per axis where the caller names none (upstream's Resize target) */
+#define MMNN_INGEST_MAX_SIZE  128  /* largest output extent of the _sized calls (16 maps of 128^3 fill a workgroup's 64 KiB of LDS on the way back) */
 #define MMNN_INGEST_MAX_X  2048   /* largest x extent (one fp64 column sum per x and wave lives in LDS) */
 typedef struct {
   int32_t x, y, z;                /* NIfTI dim[1..3] */
@@ -403,6 +404,13 @@ int64_t mmnn_ingest_workspace_bytes(int32_t x, int32_t y, int32_t z);
  * valid as the `ingest_ws` of mmnn_maps_to_scan (below) until it is reused for another ingest. */
 int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* mask, float* out_plane, int32_t* extents, void* ws,
                        void* stream);
+/* The same ingest with the output extent `size` per axis in place of 64: out_plane is size^3 floats (a channel of an
+ * (N, C, size, size, size) tensor), the plane is the adaptive average pooling of the compacted volume to size^3, and everything else --
+ * the kept slices, `extents`, what `ws` holds afterwards, the launches, the bit-identical repeats -- is as above;
+ * mmnn_ingest_volume(d, ...) is mmnn_ingest_volume_sized(d, MMNN_INGEST_SIZE, ...).  The workspace does not depend on `size`.
+ * Refused (status 1, mmnn_last_error): what mmnn_ingest_volume refuses, and a size outside 1..MMNN_INGEST_MAX_SIZE. */
+int mmnn_ingest_volume_sized(const mmnn_ingest_desc* d, int32_t size, const void* scan, const void* mask, float* out_plane,
+                             int32_t* extents, void* ws, void* stream);
 
 /* ---- a mask drawn on another grid -> the scan's grid: what upstream's DICOM datasets do before masking (data/ImageDatasets.py:145-152,
  * :246-257) -- `sitk.Resample(mask, image)` with its defaults (identity transform, linear interpolator, default pixel value 0), then the
@@ -454,6 +462,12 @@ typedef struct {
 /* bytes of device scratch (the tap tables of the three axes); -1 on a bad extent.  Needs no GPU. */
 int64_t mmnn_maps_to_scan_workspace_bytes(int32_t x, int32_t y, int32_t z);
 int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, const float* maps, float* out, void* ws, void* stream);
+/* The same way back for maps of extent `size` per axis: maps is [n_maps][size][size][size] fp32 and S = size in the coordinate rule
+ * above; out, the workspace, the launches and the refusals are as above, and mmnn_maps_to_scan(d, ...) is
+ * mmnn_maps_to_scan_sized(d, MMNN_INGEST_SIZE, ...).  `ingest_ws` holds the scan's kept slices and nothing of the extent its ingest
+ * resized them to, so `size` need not be that ingest's.  Also refused (status 1): a size outside 1..MMNN_INGEST_MAX_SIZE. */
+int mmnn_maps_to_scan_sized(const mmnn_maps_to_scan_desc* d, int32_t size, const void* ingest_ws, const float* maps, float* out, void* ws,
+                            void* stream);
 
 /* ---- DICOM slice decode: the PixelData bytes of an uncompressed single-frame series, sorted by position -> the raw voxel volume that
  * mmnn_ingest_volume / mmnn_resample_mask take (csrc/dicom.hip).  `pixels` holds the z slices back to back, x (the column) fastest,

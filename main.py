@@ -17,8 +17,11 @@ loss device (Q4); logging syncs once per epoch, not per micro-batch; `--preop` a
 Datasets: `--image_loc DIR --key_loc key.csv --data_loc clinical.csv` (or the config's `Data:` section) trains on / evaluates local
 patient directories, NIfTI files or uncompressed single-frame DICOM series (`patient/image/<series>/*.dcm`, `patient/mask/<series>/*.dcm`;
 the layout is detected per tree, `Data: format` forces one) -- the files' raw voxels are masked, cropped of empty slices and resized to
-64^3 on the device, DICOM slices are decoded there first (mmnn_sts_amd/data/ingest.py, dicom.py); compressed or multi-frame DICOM and S3
-stay outside the path.  `--inference --image_loc DIR --scan_space` also writes every class's
+S^3 on the device, DICOM slices are decoded there first (mmnn_sts_amd/data/ingest.py, dicom.py); compressed or multi-frame DICOM and S3
+stay outside the path.  S is 64, upstream's Resize target, unless `--image_size S` (or the config's `Data: size: S`; the flag goes before
+it) names another extent in 1..128 that the model admits: the ingest, the `--transforms` Resize, the attention and occlusion maps and
+their exports then all work at S^3, and without `--image_loc` the synthetic patients are S^3 too.  End to end this is covered at 64 and
+at 128 only.  `--inference --image_loc DIR --scan_space` also writes every class's
 attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).
 `--inference --images --occlusion` writes occlusion sensitivity maps (patient{i}_occ_map.npy: (K, D, H, W) signed deltas at the resolution of
 `--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
@@ -50,6 +53,7 @@ from mmnn_sts_amd.data.constants import CLASSIFICATION_THRESHOLD, NUM_BOOTSTRAP_
 from mmnn_sts_amd.losses.GradientBlender import GradientBlender  # noqa: E402
 from mmnn_sts_amd.losses.losses import BCEWithLogitsLoss, CoxPH  # noqa: E402
 from mmnn_sts_amd.optim import FusedSGD  # noqa: E402
+from mmnn_sts_amd.exceptions.exceptions import ConfigurationError  # noqa: E402
 from mmnn_sts_amd.parser.parser import Parser  # noqa: E402
 from mmnn_sts_amd.utils.utils import add_gradcam, add_occlusion, criterion, loadWeights, surv_criterion  # noqa: E402
 
@@ -247,12 +251,13 @@ def nifti_datasets(parser, args, device, seed, rank, world):
     """`--image_loc`: upstream's datasets (parser.getDatasets) over the local patient tree, cut into the train and validation uids; the
     loaders' collate function becomes the device ingest."""
     from mmnn_sts_amd.data.ImageDatasets import ImageDatasetByUIDs
-    from mmnn_sts_amd.data.ingest import IngestCollate
+    from mmnn_sts_amd.data.ingest import SIZE, IngestCollate
     full = parser.getDatasets(args, parser.getImagePath())
     train_uids, val_uids = split_uids(full.uids, args, seed)
     if getattr(args, "radiomics", False):
         scale_radiomics(parser, args, train_uids, rank)
-    args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False))
+    args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False),
+                                        size=getattr(args, "image_size", None) or SIZE)
     return ImageDatasetByUIDs(full, train_uids[rank::world]), ImageDatasetByUIDs(full, val_uids)
 
 
@@ -337,7 +342,8 @@ def radiomics_datasets(parser, args, seed, rank, world):
 
 
 def export_patient_nifti(args, uid, image, att, preds):
-    """Upstream's per-patient folder (main.py:829-845): attention_maps/_patient_<uid>/{t1image,t2image,att_map}.nii.gz + preds.txt."""
+    """Upstream's per-patient folder (main.py:829-845): attention_maps/_patient_<uid>/{t1image,t2image,att_map}.nii.gz + preds.txt.
+    The volumes are written at the extent they have: S^3 under `--image_size S`."""
     from mmnn_sts_amd.data import nifti
     d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
     os.makedirs(d, exist_ok=True)
@@ -362,7 +368,7 @@ def export_scan_space_maps(args, uid, maps, volumes, prefix="att_map"):
     """`--scan_space`: every class's attention map on the voxel grid of every scan of the patient, into the patient's folder as
     att_map_class{k}_on_{t1,t2}.nii.gz (att_map_class{k}_on_scan.nii.gz for a single modality; `prefix` replaces "att_map": the
     occlusion maps are written as occ_map_class{k}_on_*), written with the scan's affine so that a
-    viewer lays it over the scan.  `maps`: (classes, 64, 64, 64) on the device, in the model's space; `volumes`: the patient's
+    viewer lays it over the scan.  `maps`: (classes, S, S, S) on the device, in the model's space (S: `--image_size`, 64 by default); `volumes`: the patient's
     `KeptVolume` per modality.  The ingest's own kept slices are inverted on the device (`maps_to_scan`); dropped slices are 0."""
     from mmnn_sts_amd.data import nifti
     from mmnn_sts_amd.data.ingest import maps_to_scan
@@ -571,9 +577,9 @@ def inference_survival(model, ds, args, device):
                 if getattr(args, "ingest_collate", None) is not None:
                     export_patient_nifti(args, ds.uids[i], (x["image"] if args.multimodal else x)[0], att, p)
                 if getattr(args, "scan_space", False):
-                    # the maps live in the space of the ingest's 64^3 planes: `--transforms` puts only the validation transforms
-                    # between the two, and those are spatially the identity at 64^3 (intensity stages and a Resize to the size the
-                    # planes already have), so the map needs no further correction.  Fusion: one map per class; image-only: the
+                    # the maps live in the space of the ingest's S^3 planes: `--transforms` puts only the validation transforms
+                    # between the two, and those are spatially the identity at S^3 (intensity stages and a Resize to the size the
+                    # planes already have: both take `--image_size`), so the map needs no further correction.  Fusion: one map per class; image-only: the
                     # sample's one map, class 0
                     stack = torch.stack(list(maps)) if args.multimodal else maps[0]
                     export_scan_space_maps(args, ds.uids[i], stack.contiguous(), args.ingest_collate.last_volumes[0])
@@ -656,7 +662,12 @@ def build_arg_parser():
     ap.add_argument("--config", type=str, default=None)
     ap.add_argument("--blend_update_interval", type=int, default=5)
     ap.add_argument("--transforms", action="store_true",
-                    help="run upstream's train_transforms / val_transforms on every image batch on the device (resizes to 64^3)")
+                    help="run upstream's train_transforms / val_transforms on every image batch on the device (resizes to 64^3, or to "
+                         "the extent of --image_size)")
+    ap.add_argument("--image_size", type=int, default=None,
+                    help="extent S per axis, 1..128, of the volumes the model sees (default 64; overrides the config's `Data: size`): "
+                         "with --image_loc the scans are ingested at S^3, without it the synthetic patients are S^3; --transforms resizes "
+                         "to S^3 and the attention / occlusion maps and their exports are S^3")
     ap.add_argument("--scan_space", action="store_true",
                     help="with --inference --image_loc and Grad-CAM on: also write every class's attention map on each scan's own voxel "
                          "grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz)")
@@ -736,6 +747,18 @@ def main(argv=None):
     if a.scan_space and not (a.inference and use_nifti and a.images and not a.no_gradcam and not a.bootstrap):
         raise SystemExit("--scan_space lays the Grad-CAM attention maps over the patients' scans: it needs --inference, --image_loc (NIfTI "
                          "patient directories) and Grad-CAM on (--images, neither --no_gradcam nor --bootstrap)")
+    # the extent S of the image volumes: named by --image_size / `Data: size`, else 64 for the ingest and the Resize (and
+    # --synthetic_size for synthetic patients, as before)
+    sized = a.image_size is not None or (data_cfg.get("size") is not None)
+    if sized and not a.images:
+        raise SystemExit("--image_size / `Data: size` is the extent of the image volumes: it needs --images")
+    if a.images:
+        try:
+            a.image_size = parser.imageSize(a.image_size)
+        except ConfigurationError as e:
+            raise SystemExit(str(e))
+        if sized and not use_nifti:
+            a.synthetic_size = a.image_size
     hp = cfg.get("Hyperparameters", {})
     a.multimodal = a.images and (a.preop or a.postop or a.radiomics)
     a.blend = a.blend and a.multimodal
@@ -747,8 +770,8 @@ def main(argv=None):
         return run_lr_finder(a, cfg, int(hp.get("seed", 42)))
     a.train_tf = a.val_tf = None
     if a.transforms:
-        from mmnn_sts_amd.transforms import train_transforms, val_transforms
-        a.train_tf, a.val_tf = train_transforms, val_transforms
+        from mmnn_sts_amd.transforms import pipelines
+        a.train_tf, a.val_tf = pipelines(a.image_size)
     if a.radiomics:
         extract_radiomics_if_needed(parser, a)
     model = parser.getModel(a)

@@ -282,12 +282,16 @@ def lib():
     L.mmnn_ingest_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.mmnn_ingest_volume.restype = c_int32
     L.mmnn_ingest_volume.argtypes = [POINTER(IngestDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_ingest_volume_sized.restype = c_int32
+    L.mmnn_ingest_volume_sized.argtypes = [POINTER(IngestDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_resample_mask.restype = c_int32
     L.mmnn_resample_mask.argtypes = [POINTER(ResampleMaskDesc), c_void_p, c_void_p, c_void_p]
     L.mmnn_maps_to_scan_workspace_bytes.restype = c_int64
     L.mmnn_maps_to_scan_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.mmnn_maps_to_scan.restype = c_int32
     L.mmnn_maps_to_scan.argtypes = [POINTER(MapsToScanDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mmnn_maps_to_scan_sized.restype = c_int32
+    L.mmnn_maps_to_scan_sized.argtypes = [POINTER(MapsToScanDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_decode_slices.restype = c_int32
     L.mmnn_decode_slices.argtypes = [POINTER(DecodeSlicesDesc), c_void_p, c_void_p, c_void_p, c_void_p]
     L.mmnn_rasterize_contours.restype = c_int32

@@ -1,5 +1,7 @@
-// Scan ingest: one raw NIfTI scan and its mask -> one 64^3 fp32 channel plane, as upstream's image datasets prepare it per patient and
-// modality (data/ImageDatasets.py:431-470, :599-637): image * mask, every all-zero slice dropped along each axis, area resize to 64^3.
+// Scan ingest: one raw NIfTI scan and its mask -> one S^3 fp32 channel plane, as upstream's image datasets prepare it per patient and
+// modality (data/ImageDatasets.py:431-470, :599-637): image * mask, every all-zero slice dropped along each axis, area resize to S^3.
+// S is a run-time argument of the kernels, 1..MMNN_INGEST_MAX_SIZE, and MMNN_INGEST_SIZE = 64 (upstream's) where the caller names none;
+// no kernel is specialised on it, so an S = 64 call runs the one code every other S runs.
 // The contract is the comment above mmnn_ingest_volume in include/mmnn_sts.h.  Neither a float copy nor a cropped copy of the volume
 // is ever written: the scan and the mask are read in their on-disk types, twice (the second time only inside the kept region).
 //
@@ -10,14 +12,14 @@
 //                         Every writer writes the constant 1: ordinary stores, no atomics.
 //   ingest_scan_kernel    pass B, one workgroup: exclusive scans of the flags -> kept-index lists and the extents M.
 //   ingest_area_kernel    pass C: a wave per output (b, c) = (y window, z window).  Lanes along the kept x indices sum v over the rows of
-//                         the window in fp64 (registers), leave one column sum per kept x in LDS, and then lane a adds the columns of
-//                         x window a, divides by the window's voxel count and rounds once to fp32.
+//                         the window in fp64 (registers), leave one column sum per kept x in LDS, and then a lane adds the columns of
+//                         each of its x windows a = lane, lane + 64, ... < S, divides by the window's voxel count and rounds once to fp32.
 // v is formed identically in passes A and C (`ingest_value`): a rounded multiply and a rounded add, never an FMA -- whether a voxel is
 // exactly zero decides which slices survive.
 //
 //   resample_mask_kernel  mmnn_resample_mask, a call of its own ahead of the three passes when the mask was drawn on another grid:
 //                         sitk.Resample(mask, image) with its defaults, then upstream's rebinarisation, to one byte per scan voxel.
-//   maps_taps_kernel, maps_to_scan_kernel   mmnn_maps_to_scan, the inverse path: 64^3 maps of the model back onto the scan's grid,
+//   maps_taps_kernel, maps_to_scan_kernel   mmnn_maps_to_scan, the inverse path: S^3 maps of the model back onto the scan's grid,
 //                         by the kept-index lists that pass B left in the workspace.
 #include "../../include/mmnn_sts.h"
 #include "area.hpp"
@@ -28,7 +30,6 @@
 
 namespace mmnn {
 
-constexpr int IG_S = MMNN_INGEST_SIZE;
 constexpr int IG_WAVES = 4;                 // waves per block in passes A and C
 constexpr int IG_TPB = 64 * IG_WAVES;
 constexpr int IG_SCAN_TPB = 256;
@@ -42,7 +43,8 @@ struct IgArgs {
   int* kept_x; int* kept_y; int* kept_z;                    // kept indices in ascending order, the first M[axis] entries valid
   int* M;                                                   // [3]
   int* extents;                                             // the caller's copy of M
-  float* out;
+  float* out;                                               // [S][S][S]
+  int S;                                                    // output extent per axis
 };
 
 __device__ __forceinline__ double ingest_value(double sraw, double mraw, const IgScale& ss, const IgScale& ms) {
@@ -122,22 +124,26 @@ __global__ void __launch_bounds__(IG_SCAN_TPB) ingest_scan_kernel(const IgArgs a
 }
 
 // ---- pass C ------------------------------------------------------------------------------------------------------------------
-// grid (IG_S / IG_WAVES, IG_S): blockIdx.y = b (y window), wave w of block blockIdx.x = c (z window).  Dynamic LDS: IG_WAVES * X doubles.
+// grid (cdiv(S, IG_WAVES), S): blockIdx.y = b (y window), wave w of block blockIdx.x = c (z window); a wave with c >= S (the last
+// block when IG_WAVES does not divide S) only takes part in the barrier.  Dynamic LDS: IG_WAVES * X doubles.
 __global__ void __launch_bounds__(IG_TPB) ingest_area_kernel(const IgArgs a) {
   extern __shared__ __attribute__((aligned(16))) char ig_smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double* col = reinterpret_cast<double*>(ig_smem) + (long)wave * a.X;
+  const int S = a.S;
   const int b = blockIdx.y, c = blockIdx.x * IG_WAVES + wave;
+  const bool owns = c < S;                                      // (wave-uniform)
   const int mx = a.M[0], my = a.M[1], mz = a.M[2];
-  float* dst = a.out + ((long)lane * IG_S + b) * IG_S + c;      // lane = a (x window)
+  float* dst = a.out + (long)b * S + c;                         // + xa S S for x window xa
   if (mx == 0 || my == 0 || mz == 0) {                          // the mask misses the scan: zeros (the extents tell the caller)
-    *dst = 0.f;
+    if (owns)
+      for (int xa = lane; xa < S; xa += 64) dst[(long)xa * S * S] = 0.f;
     return;
   }
   int yb, ye, zb, ze;
-  area_window(b, my, IG_S, 0, yb, ye);
-  area_window(c, mz, IG_S, 0, zb, ze);
-  for (int j = lane; j < mx; j += 64) {
+  area_window(b, my, S, 0, yb, ye);
+  area_window(c, mz, S, 0, zb, ze);                             // (clamped to the last window when c >= S; not used then)
+  for (int j = lane; owns && j < mx; j += 64) {
     const long x = a.kept_x[j];
     double acc = 0.0;
     for (int zi = zb; zi < ze; ++zi) {
@@ -153,13 +159,16 @@ __global__ void __launch_bounds__(IG_TPB) ingest_area_kernel(const IgArgs a) {
     }
     col[j] = acc;
   }
-  __syncthreads();     // (every wave of the block runs the same trip counts: mx, my, mz are block-uniform)
-  int xb, xe;
-  area_window(lane, mx, IG_S, 0, xb, xe);
-  double sum = 0.0;
-  for (int j = xb; j < xe; ++j) sum += col[j];
-  const double count = (double)(xe - xb) * (double)(ye - yb) * (double)(ze - zb);
-  *dst = (float)(sum / count);
+  __syncthreads();     // (every wave of the block arrives: mx, my, mz are block-uniform, and nothing above returns once they are non-zero)
+  if (!owns) return;
+  for (int xa = lane; xa < S; xa += 64) {                       // x windows of this lane
+    int xb, xe;
+    area_window(xa, mx, S, 0, xb, xe);
+    double sum = 0.0;
+    for (int j = xb; j < xe; ++j) sum += col[j];
+    const double count = (double)(xe - xb) * (double)(ye - yb) * (double)(ze - zb);
+    dst[(long)xa * S * S] = (float)(sum / count);
+  }
 }
 
 // ---- mask resample -------------------------------------------------------------------------------------------------------------
@@ -260,17 +269,19 @@ __global__ void __launch_bounds__(IG_TPB) resample_mask_kernel(const RsArgs a, c
 }
 
 // ---- maps to scan ----------------------------------------------------------------------------------------------------------------
-// The way back: 64^3 model-space maps -> fp32 volumes on the scan's grid (the contract is the comment above mmnn_maps_to_scan in the
+// The way back: S^3 model-space maps -> fp32 volumes on the scan's grid (the contract is the comment above mmnn_maps_to_scan in the
 // header).  The kept slices are the ingest's own: the kept-index lists and extents its pass B left in its workspace are read, never the
 // scan or the mask.
 //   maps_taps_kernel      one entry per scan index of each axis: the two map indices and the weight of its linear tap, or "dropped".
 //                         The rank of an index is found by bisection of its axis' ascending kept list, so a thread writes its own
 //                         entry only and every entry is written.
 //   maps_to_scan_kernel   grid and block as pass A.  A wave owns a row (y, z); its lanes keep the x taps of their MS_XCH * VEC output
-//                         voxels in registers over all rows.  Per row lane l loads the four (y tap, z tap) entries of map x index l
-//                         -- the map's fastest axis is z, the output's is x, so a gather per output voxel would touch eight cache
-//                         lines where this touches two per lane and row -- and blends them with the row's y and z weights into a
-//                         64-entry fp64 line in LDS, one line per map; then every lane lerps its voxels along x from the line.
+//                         voxels in registers over all rows.  Per row a lane loads the four (y tap, z tap) entries of each of its map
+//                         x indices l = lane, lane + 64, ... < S -- the map's fastest axis is z, the output's is x, so a gather per
+//                         output voxel would touch eight cache lines where this touches two per lane, index and row -- and blends
+//                         them with the row's y and z weights into an S-entry fp64 line in LDS, one line per map; then every lane
+//                         lerps its voxels along x from the line.  LDS: IG_WAVES * n_maps * S doubles, 64 KiB at 16 maps of 128^3 --
+//                         the most a workgroup is given, and what caps S at MMNN_INGEST_MAX_SIZE.
 //                         Dropped rows and dropped x indices are stored as zeros: every element of `out` is written.
 struct MsTap {
   int i0, i1;                               // i0 < 0: the index is not in the kept list
@@ -283,11 +294,12 @@ struct MsArgs {
   MsTap* tx; MsTap* ty; MsTap* tz;                          // [X], [Y], [Z]
   const float* maps; float* out;
   int X, Y, Z, n_maps;
+  int S;                                                    // extent per axis of the maps
 };
 
 constexpr int MS_XCH = 2;                   // x chunks of 64 * VEC voxels per block: 512 voxels of a row when VEC = 4
 
-__device__ __forceinline__ MsTap ms_tap(const int* kept, int m, int n, int i) {
+__device__ __forceinline__ MsTap ms_tap(const int* kept, int m, int n, int i, int S) {
   MsTap t{-1, -1, 0.0};
   m = min(max(m, 0), n);
   int lo = 0, hi = m;                       // the first position whose kept index is not below i
@@ -297,9 +309,9 @@ __device__ __forceinline__ MsTap ms_tap(const int* kept, int m, int n, int i) {
     else hi = mid;
   }
   if (lo < m && kept[lo] == i) {
-    const double s = fmax(((double)lo + 0.5) * (double)IG_S / (double)m - 0.5, 0.0);
-    t.i0 = min((int)floor(s), IG_S - 1);
-    t.i1 = min(t.i0 + 1, IG_S - 1);
+    const double s = fmax(((double)lo + 0.5) * (double)S / (double)m - 0.5, 0.0);
+    t.i0 = min((int)floor(s), S - 1);
+    t.i1 = min(t.i0 + 1, S - 1);
     t.w = s - (double)t.i0;
   }
   return t;
@@ -307,17 +319,19 @@ __device__ __forceinline__ MsTap ms_tap(const int* kept, int m, int n, int i) {
 
 __global__ void __launch_bounds__(IG_SCAN_TPB) maps_taps_kernel(const MsArgs a) {
   const int i = blockIdx.x * IG_SCAN_TPB + threadIdx.x;
-  if (i < a.X) a.tx[i] = ms_tap(a.kept_x, a.M[0], a.X, i);
-  else if (i < a.X + a.Y) a.ty[i - a.X] = ms_tap(a.kept_y, a.M[1], a.Y, i - a.X);
-  else if (i < a.X + a.Y + a.Z) a.tz[i - a.X - a.Y] = ms_tap(a.kept_z, a.M[2], a.Z, i - a.X - a.Y);
+  if (i < a.X) a.tx[i] = ms_tap(a.kept_x, a.M[0], a.X, i, a.S);
+  else if (i < a.X + a.Y) a.ty[i - a.X] = ms_tap(a.kept_y, a.M[1], a.Y, i - a.X, a.S);
+  else if (i < a.X + a.Y + a.Z) a.tz[i - a.X - a.Y] = ms_tap(a.kept_z, a.M[2], a.Z, i - a.X - a.Y, a.S);
 }
 
-// grid (x groups of MS_XCH * 64 * VEC columns, row blocks); block (64, IG_WAVES).  Dynamic LDS: IG_WAVES * n_maps * 64 doubles.
+// grid (x groups of MS_XCH * 64 * VEC columns, row blocks); block (64, IG_WAVES).  Dynamic LDS: IG_WAVES * n_maps * S doubles.
 template <int VEC>
 __global__ void __launch_bounds__(IG_TPB) maps_to_scan_kernel(const MsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char ig_smem[];
   const int lane = threadIdx.x, wave = threadIdx.y;
-  double* line = reinterpret_cast<double*>(ig_smem) + wave * a.n_maps * IG_S;
+  const int S = a.S;
+  const long S2 = (long)S * S, S3 = S2 * S;
+  double* line = reinterpret_cast<double*>(ig_smem) + wave * a.n_maps * S;
   MsTap t[MS_XCH][VEC];
   int x0[MS_XCH];
 #pragma unroll
@@ -335,13 +349,15 @@ __global__ void __launch_bounds__(IG_TPB) maps_to_scan_kernel(const MsArgs a) {
       const MsTap ty = a.ty[r % a.Y], tz = a.tz[r / a.Y];
       live = ty.i0 >= 0 && tz.i0 >= 0;
       if (live) {
-        const float* p0 = a.maps + ((long)lane * IG_S + ty.i0) * IG_S;
-        const float* p1 = a.maps + ((long)lane * IG_S + ty.i1) * IG_S;
-        for (int m = 0; m < a.n_maps; ++m) {
-          const long mo = (long)m * IG_S * IG_S * IG_S;
-          const double v00 = (double)p0[mo + tz.i0], v01 = (double)p0[mo + tz.i1];
-          const double v10 = (double)p1[mo + tz.i0], v11 = (double)p1[mo + tz.i1];
-          line[m * IG_S + lane] = (1.0 - ty.w) * ((1.0 - tz.w) * v00 + tz.w * v01) + ty.w * ((1.0 - tz.w) * v10 + tz.w * v11);
+        for (int l = lane; l < S; l += 64) {          // map x indices of this lane
+          const float* p0 = a.maps + l * S2 + (long)ty.i0 * S;
+          const float* p1 = a.maps + l * S2 + (long)ty.i1 * S;
+          for (int m = 0; m < a.n_maps; ++m) {
+            const long mo = m * S3;
+            const double v00 = (double)p0[mo + tz.i0], v01 = (double)p0[mo + tz.i1];
+            const double v10 = (double)p1[mo + tz.i0], v11 = (double)p1[mo + tz.i1];
+            line[m * S + l] = (1.0 - ty.w) * ((1.0 - tz.w) * v00 + tz.w * v01) + ty.w * ((1.0 - tz.w) * v10 + tz.w * v11);
+          }
         }
       }
     }
@@ -349,7 +365,7 @@ __global__ void __launch_bounds__(IG_TPB) maps_to_scan_kernel(const MsArgs a) {
     if (r < R) {
       for (int m = 0; m < a.n_maps; ++m) {
         float* dst = a.out + (long)m * V + r * a.X;
-        const double* ln = line + m * IG_S;
+        const double* ln = line + m * S;
 #pragma unroll
         for (int c = 0; c < MS_XCH; ++c) {
           if (x0[c] >= a.X) continue;
@@ -392,6 +408,11 @@ int ig_validate_extent(int x, int y, int z) {
   return 0;
 }
 
+int ig_validate_size(int size) {
+  MMNN_REQUIRE(size >= 1 && size <= MMNN_INGEST_MAX_SIZE, "ingest: size %d outside 1..%d", size, MMNN_INGEST_MAX_SIZE);
+  return 0;
+}
+
 int ms_validate_extent(int x, int y, int z) {
   if (ig_validate_extent(x, y, z) != 0) return 1;
   MMNN_REQUIRE((double)x * y * z < 2147483648.0, "maps_to_scan: scan extent %d x %d x %d holds 2^31 voxels or more", x, y, z);
@@ -413,8 +434,13 @@ int64_t mmnn_ingest_workspace_bytes(int32_t x, int32_t y, int32_t z) {
 
 int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* mask, float* out_plane, int32_t* extents, void* ws,
                        void* stream_) {
+  return mmnn_ingest_volume_sized(d, MMNN_INGEST_SIZE, scan, mask, out_plane, extents, ws, stream_);
+}
+
+int mmnn_ingest_volume_sized(const mmnn_ingest_desc* d, int32_t size, const void* scan, const void* mask, float* out_plane,
+                             int32_t* extents, void* ws, void* stream_) {
   MMNN_REQUIRE(d, "ingest: null descriptor");
-  if (ig_validate_extent(d->x, d->y, d->z) != 0) return 1;
+  if (ig_validate_extent(d->x, d->y, d->z) != 0 || ig_validate_size(size) != 0) return 1;
   const int ssz = ig_type_size(d->scan_type), msz = ig_type_size(d->mask_type);
   MMNN_REQUIRE(ssz != 0, "ingest: unsupported scan datatype code %d (2, 4, 8, 16, 64, 256, 512, 768 are)", d->scan_type);
   MMNN_REQUIRE(msz != 0, "ingest: unsupported mask datatype code %d (2, 4, 8, 16, 64, 256, 512, 768 are)", d->mask_type);
@@ -435,6 +461,7 @@ int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* 
   a.M = reinterpret_cast<int*>(wsb + L.m);
   a.extents = extents;
   a.out = out_plane;
+  a.S = size;
 
   MMNN_HIP(hipMemsetAsync(wsb + L.flags, 0, ((size_t)d->x + d->y + d->z) * sizeof(unsigned), stream));
   // pass A: 4 voxels per lane when every row starts on a 4-voxel boundary of both buffers
@@ -448,7 +475,7 @@ int mmnn_ingest_volume(const mmnn_ingest_desc* d, const void* scan, const void* 
   if (vec4) MMNN_LAUNCH(ingest_flags_kernel<4>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a);
   else MMNN_LAUNCH(ingest_flags_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), 0, stream, a);
   MMNN_LAUNCH(ingest_scan_kernel, dim3(1), dim3(IG_SCAN_TPB), IG_SCAN_TPB * sizeof(int), stream, a);
-  MMNN_LAUNCH(ingest_area_kernel, dim3(IG_S / IG_WAVES, IG_S), dim3(IG_TPB), (size_t)IG_WAVES * d->x * sizeof(double), stream, a);
+  MMNN_LAUNCH(ingest_area_kernel, dim3(cdiv(size, IG_WAVES), size), dim3(IG_TPB), (size_t)IG_WAVES * d->x * sizeof(double), stream, a);
   MMNN_HIP(hipGetLastError());
   return 0;
 }
@@ -493,8 +520,14 @@ int64_t mmnn_maps_to_scan_workspace_bytes(int32_t x, int32_t y, int32_t z) {
 }
 
 int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, const float* maps, float* out, void* ws, void* stream_) {
+  return mmnn_maps_to_scan_sized(d, MMNN_INGEST_SIZE, ingest_ws, maps, out, ws, stream_);
+}
+
+int mmnn_maps_to_scan_sized(const mmnn_maps_to_scan_desc* d, int32_t size, const void* ingest_ws, const float* maps, float* out, void* ws,
+                            void* stream_) {
   MMNN_REQUIRE(d, "maps_to_scan: null descriptor");
   if (ms_validate_extent(d->x, d->y, d->z) != 0) return 1;
+  MMNN_REQUIRE(size >= 1 && size <= MMNN_INGEST_MAX_SIZE, "maps_to_scan: size %d outside 1..%d", size, MMNN_INGEST_MAX_SIZE);
   MMNN_REQUIRE(d->n_maps >= 1 && d->n_maps <= MMNN_MAPS_TO_SCAN_MAX_MAPS, "maps_to_scan: n_maps %d outside 1..%d", d->n_maps, MMNN_MAPS_TO_SCAN_MAX_MAPS);
   MMNN_REQUIRE(ingest_ws && maps && out && ws, "maps_to_scan: null argument");
   MMNN_REQUIRE((uintptr_t)ingest_ws % 256 == 0 && (uintptr_t)ws % 256 == 0 && (uintptr_t)maps % 4 == 0 && (uintptr_t)out % 4 == 0,
@@ -508,6 +541,7 @@ int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, co
   a.tx = static_cast<MsTap*>(ws); a.ty = a.tx + d->x; a.tz = a.ty + d->y;
   a.maps = maps; a.out = out;
   a.X = d->x; a.Y = d->y; a.Z = d->z; a.n_maps = d->n_maps;
+  a.S = size;
   MMNN_LAUNCH(maps_taps_kernel, dim3(cdiv((long)d->x + d->y + d->z, IG_SCAN_TPB)), dim3(IG_SCAN_TPB), 0, stream, a);
   // 4 voxels per lane and 16-byte stores when every output row starts on a 16-byte boundary
   const bool vec4 = d->x % 4 == 0 && (uintptr_t)out % 16 == 0;
@@ -515,7 +549,7 @@ int mmnn_maps_to_scan(const mmnn_maps_to_scan_desc* d, const void* ingest_ws, co
   int gy = cdiv((long)d->y * d->z, IG_WAVES);
   const int cap = cdiv(2048, gx);
   if (gy > cap) gy = cap;
-  const size_t lds = (size_t)IG_WAVES * d->n_maps * IG_S * sizeof(double);
+  const size_t lds = (size_t)IG_WAVES * d->n_maps * size * sizeof(double);      // at most 64 KiB: 16 maps of 128^3
   if (vec4) MMNN_LAUNCH(maps_to_scan_kernel<4>, dim3(gx, gy), dim3(64, IG_WAVES), lds, stream, a);
   else MMNN_LAUNCH(maps_to_scan_kernel<1>, dim3(gx, gy), dim3(64, IG_WAVES), lds, stream, a);
   MMNN_HIP(hipGetLastError());

@@ -21,8 +21,8 @@ clinical csv (`ClinicalDatasets.LabelTable`), joined on `uid`.  `ImageClassifica
 names of the DICOM-layout classes; unlike upstream's, the survival one masks like its classification twin.
 
 `__getitem__` yields a `RawPatient` -- the files' voxels in their on-disk type, unmasked and uncropped -- in place of upstream's float
-volume: masking, empty-slice removal, the 64^3 area resize and the T1 / T2 stacking happen on the device in the collate function
-(`mmnn_sts_amd.data.ingest.IngestCollate`), and upstream's train / validation transforms act on the collated batch (`--transforms`).
+volume: masking, empty-slice removal, the area resize (to 64^3, or to the S^3 of `IngestCollate(size=S)`) and the T1 / T2 stacking happen
+on the device in the collate function (`mmnn_sts_amd.data.ingest.IngestCollate`), and upstream's train / validation transforms act on the collated batch (`--transforms`).
 `transforms`, `slices` are accepted for signature parity; a per-item transform cannot run on raw voxels and is refused.
 
 A mask whose extents differ from its scan's (drawn on another series, resliced, cropped to the tumour's bounding box) is accepted when

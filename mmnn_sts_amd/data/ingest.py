@@ -12,10 +12,13 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
                                                     segmentation's own (mmnn_unpack_frames)
     resample_mask(mask, scan_shape, index_map)      a mask drawn on another grid -> uint8 bytes on the scan's grid (mmnn_resample_mask)
     prepare_pair(scan, mask, device)                upload, rasterise / unpack / resample the mask: the pair on one grid, on the device
-    ingest_volume(scan, mask, out_plane, extents)   one volume -> one 64^3 channel plane (the mask is resampled first when its grid differs)
-    collate_volumes(patients, device)               [[(scan, mask) per modality] per patient] -> (N, C, 64,64,64) fp32, (N, C, 3) int32
-    IngestCollate(device)                           the DataLoader collate_fn of the NIfTI datasets
-    maps_to_scan(maps, scan_shape, ingest_workspace)   the way back: 64^3 model-space maps -> fp32 volumes on the scan's grid (mmnn_maps_to_scan)
+    ingest_volume(scan, mask, out_plane, extents)   one volume -> one S^3 channel plane, S = the plane's extent (the mask is resampled first when its grid differs)
+    collate_volumes(patients, device, size=64)      [[(scan, mask) per modality] per patient] -> (N, C, S,S,S) fp32, (N, C, 3) int32
+    IngestCollate(device, size=64)                  the DataLoader collate_fn of the NIfTI datasets
+    maps_to_scan(maps, scan_shape, ingest_workspace)   the way back: S^3 model-space maps -> fp32 volumes on the scan's grid (mmnn_maps_to_scan_sized)
+
+The output extent S is 64 (`SIZE`, upstream's Resize target) unless a caller chooses another one in 1..128 (`MAX_SIZE`): `ingest_volume`
+reads it off the plane it is given, `maps_to_scan` off the maps, the collate functions take `size=`.
 
 A mask on another grid (a T2 contour used on the T1 scan, a resliced export, a mask cropped to the tumour's bounding box) is what
 upstream's DICOM datasets pass through `sitk.Resample(mask, image)` and `> 128` (data/ImageDatasets.py:145-152, :246-257); here the
@@ -52,7 +55,8 @@ from .nifti import NiftiImage
 from .rtstruct import ContourSet
 from .seg import FrameSet
 
-SIZE = 64                                    # MMNN_INGEST_SIZE
+SIZE = 64                                    # MMNN_INGEST_SIZE: the default output extent per axis
+MAX_SIZE = 128                               # MMNN_INGEST_MAX_SIZE: the largest one
 MASK_RESAMPLE_MODES = ("auto", "geometry", "never")
 GEOMETRY_TOLERANCE = 1e-3                    # voxels: 'geometry' resamples when a corner of the scan grid maps further from itself
 NIFTI_MASK_THRESHOLD, DICOM_MASK_THRESHOLD = 0.5, 128.0          # defaults of `Data: mask_threshold` (upstream: `mask > 128`)
@@ -439,10 +443,17 @@ def prepare_pair(scan, mask, dev, index_map=None, threshold: Optional[float] = N
     return scan, mask
 
 
+def check_size(size, who: str = "ingest") -> int:
+    """`size` as an output extent per axis: an integer in 1..MAX_SIZE, else ValueError."""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 1 <= int(size) <= MAX_SIZE:
+        raise ValueError(f"{who}: the output extent per axis must be an integer in 1..{MAX_SIZE}, got {size!r}")
+    return int(size)
+
+
 def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                   index_map=None, threshold: Optional[float] = None) -> torch.Tensor:
-    """Enqueue the ingest of one volume on the current stream: `out_plane` (a contiguous (64,64,64) fp32 CUDA view, e.g. batch[n, c]) receives
-    the masked, compacted, area-resized scan; returns `extents` (3 x int32 on the device: kept slices along x, y, z), readable after
+    """Enqueue the ingest of one volume on the current stream: `out_plane` (a contiguous (S,S,S) fp32 CUDA view with S in 1..128, e.g. batch[n, c]) receives
+    the masked, compacted scan, area-resized to S^3; returns `extents` (3 x int32 on the device: kept slices along x, y, z), readable after
     the next synchronisation.  `scan` / `mask`: DeviceVolume, NiftiImage or ndarray (host volumes are uploaded first).  When the
     extents differ, or an `index_map` is given, the mask is first resampled into the scan's grid (`resample_mask`, binarised at
     `threshold`); without `index_map` the map comes from the two volumes' affines, and differing extents without them are refused.
@@ -451,8 +462,12 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     rasterised onto the scan's grid first (`rasterize_contours`) and takes the voxelwise path: no resample, no threshold.  A `mask`
     that is a FrameSet (or `stage_frames`' result) beside a DICOM scan is unpacked first (`unpack_frames`): onto the scan's grid, and
     then voxelwise like a contour mask, or onto a grid of its own, and then resampled and binarised like a DICOM mask series."""
-    if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and tuple(out_plane.shape) == (SIZE,) * 3):
-        raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, got {tuple(out_plane.shape)} {out_plane.dtype} on {out_plane.device}")
+    shape = tuple(out_plane.shape)
+    if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and len(shape) == 3
+            and shape == shape[:1] * 3 and 1 <= shape[0] <= MAX_SIZE):
+        raise ValueError(f"ingest: out_plane must be a contiguous ({SIZE},{SIZE},{SIZE}) fp32 CUDA tensor, or (S,S,S) with another S in 1..{MAX_SIZE}, "
+                         f"got {shape} {out_plane.dtype} on {out_plane.device}")
+    size = shape[0]
     dev = out_plane.device
     scan, mask = prepare_pair(scan, mask, dev, index_map, threshold)
     if extents is None:
@@ -468,8 +483,8 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     desc = _lib.IngestDesc(x, y, z, scan.datatype, mask.datatype, scan.slope, scan.inter, mask.slope, mask.inter)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_ingest_volume(ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), out_plane.data_ptr(),
-                                                 extents.data_ptr(), workspace.data_ptr(), stream), "mmnn_ingest_volume")
+        _lib.check(_lib.lib().mmnn_ingest_volume_sized(ctypes.byref(desc), size, scan.data.data_ptr(), mask.data.data_ptr(), out_plane.data_ptr(),
+                                                       extents.data_ptr(), workspace.data_ptr(), stream), "mmnn_ingest_volume_sized")
     return extents
 
 
@@ -482,18 +497,21 @@ def maps_to_scan_workspace_bytes(x: int, y: int, z: int) -> int:
 
 def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor, out: Optional[torch.Tensor] = None,
                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Enqueue `mmnn_maps_to_scan` on the current stream: `maps` ((n_maps, 64, 64, 64) fp32 in model space, axes x, y, z as the ingest
-    writes its plane) -> (n_maps, z, y, x) fp32 on the scan's voxel grid (x fastest, NIfTI order; `.permute(0, 3, 2, 1)` is the (x, y, z)
+    """Enqueue `mmnn_maps_to_scan_sized` on the current stream: `maps` ((n_maps, S, S, S) fp32 in model space with S in 1..128, axes
+    x, y, z as the ingest writes its plane) -> (n_maps, z, y, x) fp32 on the scan's voxel grid (x fastest, NIfTI order; `.permute(0, 3, 2, 1)` is the (x, y, z)
     array of a volume).  Kept voxels hold the trilinear up-sampling of the map to the kept extents, every voxel of a slice the ingest
-    dropped is exactly 0.  `ingest_workspace`: the `workspace` tensor a completed `ingest_volume` of this scan used, not reused since.
+    dropped is exactly 0.  `ingest_workspace`: the `workspace` tensor a completed `ingest_volume` of this scan used, not reused since;
+    it holds the scan's kept slices and nothing of the extent they were resized to, so S is the maps' own and need not equal that ingest's.
     `out`: a contiguous (n_maps, z, y, x) fp32 tensor on the maps' device to write, allocated when None; `workspace`: scratch of
     `maps_to_scan_workspace_bytes` bytes, allocated when None."""
     shape = tuple(scan_shape)
     if len(shape) != 3 or any(int(v) != v or int(v) < 1 for v in shape):
         raise ValueError(f"maps_to_scan: scan_shape must be three positive extents (x, y, z), got {scan_shape!r}")
     x, y, z = (int(v) for v in shape)
-    if not isinstance(maps, torch.Tensor) or maps.ndim != 4 or tuple(maps.shape[1:]) != (SIZE,) * 3 or not 1 <= maps.shape[0] <= _lib.MAPS_TO_SCAN_MAX_MAPS:
-        raise ValueError(f"maps_to_scan: maps must be (n, {SIZE}, {SIZE}, {SIZE}) with n in 1..{_lib.MAPS_TO_SCAN_MAX_MAPS}, got {tuple(getattr(maps, 'shape', ()))}")
+    if (not isinstance(maps, torch.Tensor) or maps.ndim != 4 or tuple(maps.shape[1:]) != tuple(maps.shape[1:2]) * 3
+            or not 1 <= maps.shape[1] <= MAX_SIZE or not 1 <= maps.shape[0] <= _lib.MAPS_TO_SCAN_MAX_MAPS):
+        raise ValueError(f"maps_to_scan: maps must be (n, {SIZE}, {SIZE}, {SIZE}), or (n, S, S, S) with another S in 1..{MAX_SIZE}, with n in "
+                         f"1..{_lib.MAPS_TO_SCAN_MAX_MAPS}, got {tuple(getattr(maps, 'shape', ()))}")
     if maps.dtype != torch.float32 or not maps.is_contiguous():
         raise ValueError(f"maps_to_scan: maps must be contiguous fp32, got {maps.dtype}{'' if maps.is_contiguous() else ' (not contiguous)'}")
     if not isinstance(ingest_workspace, torch.Tensor) or ingest_workspace.dtype != torch.uint8 or not ingest_workspace.is_contiguous():
@@ -518,14 +536,14 @@ def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor,
     desc = _lib.MapsToScanDesc(x, y, z, n)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_maps_to_scan(ctypes.byref(desc), ingest_workspace.data_ptr(), maps.data_ptr(), out.data_ptr(),
-                                                workspace.data_ptr(), stream), "mmnn_maps_to_scan")
+        _lib.check(_lib.lib().mmnn_maps_to_scan_sized(ctypes.byref(desc), int(maps.shape[1]), ingest_workspace.data_ptr(), maps.data_ptr(),
+                                                      out.data_ptr(), workspace.data_ptr(), stream), "mmnn_maps_to_scan_sized")
     return out
 
 
 def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
-                    mask_threshold: Optional[float] = None, keep_workspaces: bool = False):
-    """patients[n][c] = (scan, mask) -> the device batch (N, C, 64, 64, 64) fp32 and the kept extents (N, C, 3) int32.  Every upload is
+                    mask_threshold: Optional[float] = None, keep_workspaces: bool = False, size: int = SIZE):
+    """patients[n][c] = (scan, mask) -> the device batch (N, C, S, S, S) fp32, S = `size` in 1..128, and the kept extents (N, C, 3) int32.  Every upload is
     issued before the first kernel, so the copies of one volume run beside the passes of the one before it.  A mask on another grid
     than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`
     (None: 0.5; 128 for a DICOM pair, which is always resampled).  A ContourSet as the mask of a DICOM scan (an RTSTRUCT file) is
@@ -533,13 +551,14 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     A FrameSet (a DICOM SEG file) is placed by the host, uploaded with the others and unpacked on the device (see `unpack_frames`).
     With `keep_workspaces` every volume is ingested with a workspace of its own and a third value is returned: volumes[n][c], the
     `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan."""
+    size = check_size(size)
     n, c = len(patients), len(patients[0])
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
     device = torch.device(device)
     up = [[(upload(s, device), stage_mask(s, m, device)) for s, m in p] for p in patients]
     maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
-    batch = torch.empty((n, c, SIZE, SIZE, SIZE), dtype=torch.float32, device=device)
+    batch = torch.empty((n, c, size, size, size), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)
     kept = []
     for i in range(n):
@@ -558,15 +577,17 @@ class IngestCollate:
     batch on `device`.  The extents of every batch are kept in `pending` until `take_empty()` reads them: call it where the epoch
     synchronises anyway, never per batch.  `mask_resample` / `mask_threshold`: the `Data:` keys of the same names (see `collate_volumes`).
     `keep_workspaces` (off: nothing is retained, as training wants it): `last_volumes[n][c]` holds the `KeptVolume` of every (patient,
-    modality) of the LAST batch, for `maps_to_scan`."""
+    modality) of the LAST batch, for `maps_to_scan`.  `size`: the extent S per axis of the planes, 1..128 (64)."""
 
-    def __init__(self, device, mask_resample: str = "auto", mask_threshold: Optional[float] = 0.5, keep_workspaces: bool = False):
+    def __init__(self, device, mask_resample: str = "auto", mask_threshold: Optional[float] = 0.5, keep_workspaces: bool = False,
+                 size: int = SIZE):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         self.device = torch.device(device)
         self.mask_resample, self.mask_threshold = mask_resample, (None if mask_threshold is None else float(mask_threshold))
         self.pending: List[Tuple[List[int], torch.Tensor]] = []
         self.keep_workspaces = bool(keep_workspaces)
+        self.size = check_size(size)
         self.last_volumes: List[List[KeptVolume]] = []
 
     def __call__(self, items):
@@ -574,8 +595,9 @@ class IngestCollate:
         targets = [torch.stack([torch.as_tensor(it[k]) for it in items]) for k in range(1, len(items[0]))]
         multimodal = isinstance(xs[0], dict)
         raws = [x["image"] for x in xs] if multimodal else xs
+        sized = {"size": self.size} if self.size != SIZE else {}          # (the default's call is the one it always was)
         batch, extents, *kept = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold,
-                                                keep_workspaces=self.keep_workspaces)
+                                                keep_workspaces=self.keep_workspaces, **sized)
         if kept:
             self.last_volumes = kept[0]
         self.pending.append(([r.uid for r in raws], extents))

@@ -5,7 +5,8 @@ TinyDensenet and wraps it into `MultiModalModel` for `--images --preop|--postop`
 Fixes: `--preop` alone yields the standalone clinical MLP; the predictor list may be given as an
 integer count (`ClinicalModel.NUM_PREDICTORS`) for synthetic data.  `getImagePath()` / `getDatasets(args, image_path)` (parser.py:43-97,
 184-198) build the local-disk image datasets from the `Data:` section (`image_loc`, `t1_path`, `t2_path`, `data_loc`, `key_loc`; the
-command-line flags override it; `format: auto | nifti | dicom` names the patient directories' layout, detected per tree by default;
+command-line flags override it; `size: S`, 1..128, default 64, is the extent per axis the scans are ingested at -- `imageSize`;
+`format: auto | nifti | dicom` names the patient directories' layout, detected per tree by default;
 `mask_resample`, `mask_threshold` say what happens to a mask drawn on another grid than its scan's -- a DICOM mask is always resampled,
 and binarised at 128 unless `mask_threshold` is set; `mask_roi` names the region of interest to take from an RTSTRUCT mask, which is
 rasterised onto its scan's grid and takes neither resample nor threshold, or the segment to take, by its SegmentLabel, from a DICOM SEG
@@ -211,6 +212,33 @@ class Parser:
         if not isinstance(value, str) or not value.strip():
             raise ConfigurationError('Data.mask_roi {!r} is not a ROI name (a non-empty string)'.format(value))
         return value.strip()
+
+    def minImageSize(self):
+        """The smallest cubic input extent at which the native plan (csrc/densenet.hip: plan_build) still leaves the last dense block of
+        the configured DenseNet a voxel: the stem and the pool halve the extent rounding up, every transition halves it rounding down.
+        1 for a model that is no DenseNet (r3d_18 pools adaptively)."""
+        name = self.config['ImageModel']['name'].lower()
+        blocks = 4 if name.startswith('densenet121') else 3 if name.startswith('tinydensenet') else 0
+        if not blocks:
+            return 1
+        size = 1
+        while (((size - 1) // 2) // 2 + 1) >> (blocks - 1) < 1:
+            size += 1
+        return size
+
+    def imageSize(self, flag=None):
+        """`Data: size`: the extent S per axis that the scan ingest, the `--transforms` Resize and the exports work at -> an integer in
+        1..128, default 64 (upstream's Resize((64,64,64))).  `flag`: the command line's `--image_size`, which goes before the config's."""
+        from ..data.ingest import MAX_SIZE, SIZE
+        value = flag if flag is not None else (self.config.get('Data') or {}).get('size', SIZE)
+        where = '--image_size' if flag is not None else 'Data.size'
+        if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= MAX_SIZE:
+            raise ConfigurationError('{} {!r} is not an integer in 1..{}'.format(where, value, MAX_SIZE))
+        lowest = self.minImageSize()
+        if value < lowest:
+            raise ConfigurationError('{} {} is within 1..{} but leaves the last dense block of {} no voxel: its smallest extent is {}'.format(
+                where, value, MAX_SIZE, self.config['ImageModel']['name'], lowest))
+        return value
 
     def dataFormat(self):
         """`Data: format`: 'auto' (the default: the layout is detected per tree), 'nifti' or 'dicom'."""

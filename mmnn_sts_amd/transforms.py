@@ -11,6 +11,10 @@ monai itself is not a dependency).  Work is split in two:
 
 `Compose(x)` is `apply(x, randomize(N))`; a transform called on its own behaves as a one-element Compose.  Inputs are CUDA fp32
 tensors of shape (N, C, D, H, W) or (C, D, H, W); the result is a new tensor.
+
+`pipelines(size)` returns upstream's two pipelines with the Resize target (size,) * 3 -- the one departure from upstream's argument
+values, for runs whose volumes are ingested at another extent than 64 (`--image_size`).  `train_transforms` / `val_transforms` are
+`pipelines(64)`; the public `Resize(spatial_size=...)` still admits upstream's value only.
 """
 import ctypes
 import math
@@ -26,6 +30,7 @@ from .data.constants import IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV
 from .utils.utils import Normalize
 
 SPATIAL_SIZE = (64, 64, 64)      # main.py:60
+MAX_SIZE = 128                   # the largest Resize target of `pipelines` (MMNN_INGEST_MAX_SIZE: what the scan ingest can feed)
 
 # stage bits, in pipeline order (include/mmnn_sts.h: MMNN_TF_*)
 NORMALIZE, SCALE, ROTATE, FLIP, ZOOM, RESIZE, SHIFT, CONTRAST, SMOOTH, SHARPEN, HIST, NOISE = (1 << i for i in range(12))
@@ -187,6 +192,15 @@ class Resize(Transform):
         if mode != "area":
             _reject("Resize", "mode", mode, "area")
         self.spatial_size = size
+
+    @classmethod
+    def _sized(cls, size: int) -> "Resize":
+        """The Resize of `pipelines(size)`: target (size,) * 3 with size in 1..MAX_SIZE.  Not part of the public surface."""
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 1 <= int(size) <= MAX_SIZE:
+            raise ValueError(f"pipelines: size={size!r} is not an integer in 1..{MAX_SIZE}")
+        t = cls()
+        t.spatial_size = (int(size),) * 3
+        return t
 
 
 class RandShiftIntensity(Transform):
@@ -376,29 +390,35 @@ class Compose:
         return self.apply(x, self.randomize(x.shape[0] if x.dim() == 5 else 1))
 
 
-train_transforms = Compose([
-    EnsureChannelFirst(channel_dim=0),
-    Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV),
-    ScaleIntensity(),
-    # spatial
-    RandRotate(range_x=15, prob=0.5, keep_size=True),
-    RandAxisFlip(prob=0.5),
-    RandZoom(min_zoom=0.9, max_zoom=1.1, prob=0.5, keep_size=True),
-    Resize(spatial_size=SPATIAL_SIZE),
-    # intensity
-    RandShiftIntensity(0.1, prob=0.3),
-    RandAdjustContrast(prob=0.3),
-    RandGaussianSmooth(prob=0.2),
-    RandGaussianSharpen(prob=0.2),
-    RandHistogramShift(prob=0.3),
-    RandGaussianNoise(prob=0.3, mean=0, std=0.05),
-    ToTensor(),
-])
+def pipelines(size: int = SPATIAL_SIZE[0]) -> Tuple[Compose, Compose]:
+    """(train, val): upstream's two pipelines (main.py:64-92) with the Resize target (size,) * 3, size in 1..MAX_SIZE.  Every other
+    argument is upstream's, so the stages, their order and the draws of `randomize` do not depend on `size`."""
+    train = Compose([
+        EnsureChannelFirst(channel_dim=0),
+        Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV),
+        ScaleIntensity(),
+        # spatial
+        RandRotate(range_x=15, prob=0.5, keep_size=True),
+        RandAxisFlip(prob=0.5),
+        RandZoom(min_zoom=0.9, max_zoom=1.1, prob=0.5, keep_size=True),
+        Resize._sized(size),
+        # intensity
+        RandShiftIntensity(0.1, prob=0.3),
+        RandAdjustContrast(prob=0.3),
+        RandGaussianSmooth(prob=0.2),
+        RandGaussianSharpen(prob=0.2),
+        RandHistogramShift(prob=0.3),
+        RandGaussianNoise(prob=0.3, mean=0, std=0.05),
+        ToTensor(),
+    ])
+    val = Compose([
+        EnsureChannelFirst(channel_dim=0),
+        Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV),
+        ScaleIntensity(),
+        Resize._sized(size),
+        ToTensor(),
+    ])
+    return train, val
 
-val_transforms = Compose([
-    EnsureChannelFirst(channel_dim=0),
-    Normalize(IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV),
-    ScaleIntensity(),
-    Resize(spatial_size=SPATIAL_SIZE),
-    ToTensor(),
-])
+
+train_transforms, val_transforms = pipelines(SPATIAL_SIZE[0])

@@ -5,6 +5,7 @@ of the two .nii.gz files and the pinned upload.
 
     python tools/ingest_time.py [--steps 50] [--warmup 10] [--case NAME] [--mask_grid own] [--json out.json] [--kernel_stats kernel_stats.csv]
     python tools/ingest_time.py --maps_to_scan [--json out.json]      # the inverse path alone (`--json` adds its rows to the file's)
+    python tools/ingest_time.py --size 64 128 [--json out.json]       # both paths at each output extent S (`--json` adds its rows to the file's)
 
 Cases: 512 x 512 x 48 int16 scan + uint8 mask with a 320 x 310 x 39 box; 256 x 256 x 40 with the mask covering everything.  Bytes are the
 algorithmic HBM traffic computed from the shapes -- pass A reads every scan and mask byte once, pass C reads the kept box once, 1 MB is
@@ -18,7 +19,11 @@ once plus x*y*z written.
 
 `--maps_to_scan` times the way back (`ingest.maps_to_scan`, 64^3 maps -> fp32 volumes on the scan's grid) on the first case's scan, with 1
 map and with 2, from the workspace one ingest left behind.  Its floor is the bytes WRITTEN (n_maps * x*y*z * 4; the 1 MB map per volume
-and the tap tables are read from cache) over the same 6.29 TB/s."""
+and the tap tables are read from cache) over the same 6.29 TB/s.
+
+`--size S [S ...]` (1..128) times, in one run and on the first case (or `--case`), the ingest to S^3 planes and the way back from S^3
+maps at every S named, under the key `sizes_<case>`: {"size_<S>": {"ingest": ..., "maps_to_scan": ...}}.  Without it S is 64 and the
+keys are the ones above."""
 import argparse
 import csv
 import json
@@ -60,10 +65,10 @@ def own_grid(shape, box):
     return own, (tuple(lo), tuple(hi)), T
 
 
-def pass_bytes(shape, box, own=None):
+def pass_bytes(shape, box, own=None, size=ingest.SIZE):
     voxels = int(np.prod(shape))
     kept = int(np.prod([b - a for a, b in zip(*box)]))
-    pb = {"pass_a_flags": voxels * 3, "pass_c_area": kept * 3 + 4 * 64 ** 3, "pass_b_scan": 8 * sum(shape)}
+    pb = {"pass_a_flags": voxels * 3, "pass_c_area": kept * 3 + 4 * size ** 3, "pass_b_scan": 8 * sum(shape)}
     if own is not None:
         pb["pass_r_resample"] = int(np.prod(own)) + voxels
     return pb
@@ -105,7 +110,7 @@ def queued_us(fn, steps):
     return a.elapsed_time(b) * 1e3 / steps
 
 
-def time_case(name, steps, warmup, mask_grid="same"):
+def time_case(name, steps, warmup, mask_grid="same", size=ingest.SIZE):
     shape, box = CASES[name]
     host = [make_volume(shape, box, s) for s in range(4)]
     own = None
@@ -114,7 +119,7 @@ def time_case(name, steps, warmup, mask_grid="same"):
         host = [(s, make_volume(own, own_box, 0)[1]) for s, _ in host]
         resampled = torch.empty(int(np.prod(shape)), dtype=torch.uint8, device="cuda")
     vols = [(ingest.upload(s, "cuda", 0.25, -12.5), ingest.upload(m, "cuda")) for s, m in host]
-    batch = torch.empty((2, 2, 64, 64, 64), device="cuda")
+    batch = torch.empty((2, 2, size, size, size), device="cuda")
     ext = torch.empty((2, 2, 3), dtype=torch.int32, device="cuda")
     ws = torch.empty(ingest.workspace_bytes(*shape), dtype=torch.uint8, device="cuda")
 
@@ -141,7 +146,7 @@ def time_case(name, steps, warmup, mask_grid="same"):
         assert got == [got[0]] * 4 and min(got[0]) > 0, ext
         box = ((0, 0, 0), tuple(got[0]))
     vol_us, batch_us = queued_us(one, steps), queued_us(four, steps)
-    pb = pass_bytes(shape, box, own)
+    pb = pass_bytes(shape, box, own, size)
     total = sum(pb.values())
     floor_us = total / (HBM_TBS * 1e12) * 1e6
     res = {"device_us_per_volume": round(vol_us, 1), "device_us_per_batch": round(batch_us, 1), "MB_per_volume": round(total / 1e6, 2),
@@ -154,16 +159,16 @@ def time_case(name, steps, warmup, mask_grid="same"):
     return res
 
 
-def time_maps_to_scan(steps, warmup, name="512x512x48_box320x310x39"):
+def time_maps_to_scan(steps, warmup, name="512x512x48_box320x310x39", size=ingest.SIZE):
     shape, box = CASES[name]
     scan, mask = make_volume(shape, box, 0)
     ws = torch.empty(ingest.workspace_bytes(*shape), dtype=torch.uint8, device="cuda")
-    ext = ingest.ingest_volume(ingest.upload(scan, "cuda", 0.25, -12.5), ingest.upload(mask, "cuda"), torch.empty((64, 64, 64), device="cuda"), workspace=ws)
+    ext = ingest.ingest_volume(ingest.upload(scan, "cuda", 0.25, -12.5), ingest.upload(mask, "cuda"), torch.empty((size, size, size), device="cuda"), workspace=ws)
     assert ext.cpu().tolist() == [b - a for a, b in zip(*box)], ext
     scratch = torch.empty(ingest.maps_to_scan_workspace_bytes(*shape), dtype=torch.uint8, device="cuda")
     res = {"scan": list(shape), "kept": ext.cpu().tolist()}
     for n in (1, 2):
-        maps = torch.rand((n, 64, 64, 64), device="cuda")
+        maps = torch.rand((n, size, size, size), device="cuda")
         out = torch.empty((n, *shape[::-1]), device="cuda")
         fn = lambda: ingest.maps_to_scan(maps, shape, ws, out=out, workspace=scratch)
         for _ in range(warmup):
@@ -199,17 +204,28 @@ def main():
     ap.add_argument("--case", type=str, default=None, choices=sorted(CASES))
     ap.add_argument("--mask_grid", type=str, default="same", choices=("same", "own"), help="own: the mask on a grid of 3/4 the extents, resampled first")
     ap.add_argument("--maps_to_scan", action="store_true", help="time the inverse path (maps_to_scan, 1 and 2 maps) instead of the ingest cases")
+    ap.add_argument("--size", type=int, nargs="+", default=None, metavar="S",
+                    help="output extents per axis (1..128): time the ingest and the inverse path of one case at each of them instead")
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--kernel_stats", type=str, default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     res = {}
-    if a.maps_to_scan:
+    if a.size:
+        name = a.case or next(iter(CASES))
+        rows = res["sizes_" + name] = {}
+        for size in a.size:
+            rows[f"size_{size}"] = {"ingest": time_case(name, a.steps, a.warmup, a.mask_grid, size),
+                                    "maps_to_scan": time_maps_to_scan(a.steps, a.warmup, name, size)}
+            print(json.dumps({"case": name, "size": size, **rows[f"size_{size}"]}), flush=True)
+        if a.json and os.path.exists(a.json):       # its rows join the file's
+            res = {**json.load(open(a.json)), **res}
+    elif a.maps_to_scan:
         res["maps_to_scan_512x512x48"] = time_maps_to_scan(a.steps, a.warmup)
         print(json.dumps({"case": "maps_to_scan_512x512x48", **res["maps_to_scan_512x512x48"]}), flush=True)
         if a.json and os.path.exists(a.json):       # its rows join the ingest's
             res = {**json.load(open(a.json)), **res}
-    for name in ([] if a.maps_to_scan else [a.case] if a.case else list(CASES)):
+    for name in ([] if a.maps_to_scan or a.size else [a.case] if a.case else list(CASES)):
         key = name if a.mask_grid == "same" else name + "_mask_grid_own"
         res[key] = time_case(name, a.steps, a.warmup, a.mask_grid)
         if a.kernel_stats and a.case:
