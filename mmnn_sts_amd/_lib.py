@@ -4,6 +4,8 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint64, c_void_p
 
+import torch  # before the library: it loads libamdhip64 with the SONAME the extension needs
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMNN_LIB_PATH") or os.path.join(_HERE, "libmmnn_sts.so")   # override: developer builds only
 _lib = None
@@ -190,47 +192,21 @@ class ResampleDesc(Structure):
                 ("pole_power", ctypes.c_double * RESAMPLE_HORIZON)]
 
 
-def lib():
-    """Load the shared library once (torch must be imported first so that its HIP runtime is the one bound)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    import torch  # noqa: F401  (loads libamdhip64 with the SONAME the extension needs)
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} not found: build it with `python -m mmnn_sts_amd.build` (hipcc, gfx950). "
-            "mmnn_sts_amd has no CPU / eager fallback.")
-    L = ctypes.CDLL(LIB_PATH)
-    L.mmnn_version.restype = c_int32
-    L.mmnn_last_error.restype = c_char_p
-    L.mmnn_densenet_plan_create.restype = c_void_p
-    L.mmnn_densenet_plan_create.argtypes = [POINTER(DenseNetConfig), c_int32, c_int32, c_int32, c_int32]
-    L.mmnn_densenet_plan_destroy.restype = None
-    L.mmnn_densenet_plan_destroy.argtypes = [c_void_p]
-    for f in ("mmnn_densenet_param_count", "mmnn_densenet_runstat_count", "mmnn_densenet_workspace_bytes"):
-        getattr(L, f).restype = c_int64
-        getattr(L, f).argtypes = [c_void_p]
-    L.mmnn_densenet_out_shape.restype = c_int32
-    L.mmnn_densenet_out_shape.argtypes = [c_void_p] + [POINTER(c_int32)] * 4
-    L.mmnn_densenet_forward.restype = c_int32
-    L.mmnn_densenet_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_void_p]
-    L.mmnn_densenet_backward.restype = c_int32
-    L.mmnn_densenet_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_void_p]
-    L.mmnn_densenet_backward_range.restype = c_int32
-    L.mmnn_densenet_backward_range.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_int32, c_int32,
-                                               c_void_p]
-    L.mmnn_densenet_block_param_range.restype = c_int32
-    L.mmnn_densenet_block_param_range.argtypes = [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]
-    L.mmnn_densenet_relu_mask.restype = c_int32
-    L.mmnn_densenet_relu_mask.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    L.mmnn_densenet_ws_offset.restype = c_int64
-    L.mmnn_densenet_ws_offset.argtypes = [c_void_p, c_char_p, c_int32, c_int32]
-    V, I, U, F = c_void_p, c_int32, c_uint64, c_float
-    sigs = {
+def _signatures():
+    """Every prototype of include/mmnn_sts.h as {symbol: (restype, argtypes)}, from one table per return type (tests/test_host_cpu.py
+    holds them against the header)."""
+    V, I, U, F, Q, D, S, P = c_void_p, c_int32, c_uint64, c_float, c_int64, ctypes.c_double, c_char_p, POINTER
+    status = {                               # int32 status: 0, or 1 (ValueError) / another (RuntimeError) with mmnn_last_error set
+        "mmnn_densenet_out_shape": [V] + [P(I)] * 4,
+        "mmnn_densenet_forward": [V, V, V, V, V, V, I, U, V],
+        "mmnn_densenet_backward": [V, V, V, V, V, V, I, U, V],
+        "mmnn_densenet_backward_range": [V, V, V, V, V, V, I, U, I, I, V],
+        "mmnn_densenet_block_param_range": [V, I, P(Q), P(Q)],
+        "mmnn_densenet_relu_mask": [V, V, V, I, I, I, V, V],
         "mmnn_gap_linear_forward": [I, I, I, I, V, V, V, V, V, F, U, I, V],
         "mmnn_gap_linear_backward": [I, I, I, I, V, V, V, V, V, V, V, F, U, I, I, V],
-        "mmnn_mlp_forward": [POINTER(MlpDesc), POINTER(MlpParams), V, V, V, V],
-        "mmnn_mlp_backward": [POINTER(MlpDesc), POINTER(MlpParams), V, V, V, V, V, I, V],
+        "mmnn_mlp_forward": [P(MlpDesc), P(MlpParams), V, V, V, V],
+        "mmnn_mlp_backward": [P(MlpDesc), P(MlpParams), V, V, V, V, V, I, V],
         "mmnn_fusion_heads_forward": [I, I, I, I] + [V] * 9 + [V],
         "mmnn_fusion_heads_backward": [I, I, I, I] + [V] * 14 + [I, V],
         "mmnn_linear_forward": [I, I, I, V, V, V, V, V],
@@ -238,108 +214,100 @@ def lib():
         "mmnn_cox_blend_loss": [I, I, I, V, V, V, V, V, V, V, V, V],
         "mmnn_cox_blend_loss_typed": [I, I, I, V, V, I, V, I, V, V, V, V, V, V],
         "mmnn_cox_blend_backward": [I, I, I, V, V, V, V, V, V],
-        "mmnn_sgd_step": [V, V, V, c_int64, F, F, F, I, I, V],
-        "mmnn_sgd_step_multi": [POINTER(TensorRef), I, V, F, F, F, I, V],
-        "mmnn_multi_copy": [POINTER(TensorRef), I, V, I, V],
-        "mmnn_sgd_step_dev": [V, V, V, c_int64, V, V, F, F, I, I, V],
-        "mmnn_sgd_step_multi_dev": [POINTER(TensorRef), I, V, V, V, F, F, I, V],
-        "mmnn_cross_entropy": [I, I, V, V, I, c_int64, I, V, V, V],
+        "mmnn_sgd_step": [V, V, V, Q, F, F, F, I, I, V],
+        "mmnn_sgd_step_multi": [P(TensorRef), I, V, F, F, F, I, V],
+        "mmnn_multi_copy": [P(TensorRef), I, V, I, V],
+        "mmnn_sgd_step_dev": [V, V, V, Q, V, V, F, F, I, I, V],
+        "mmnn_sgd_step_multi_dev": [P(TensorRef), I, V, V, V, F, F, I, V],
+        "mmnn_cross_entropy": [I, I, V, V, I, Q, I, V, V, V],
         "mmnn_cross_entropy_backward": [I, I, I, V, V, V, V],
         "mmnn_lr_range_init": [V, I, V],
         "mmnn_lr_range_accumulate": [V, V, F, I, V],
-        "mmnn_lr_range_update": [V, I, ctypes.c_double, ctypes.c_double, ctypes.c_double, V],
-        "mmnn_gradcam": [POINTER(GradcamDesc), V, V, V, V, V, V, V, V, V, V, V],
-        "mmnn_gradcam_unimodal": [POINTER(GradcamUnimodalDesc), POINTER(GradcamHead), V, V, V, V, V, V, c_int64, V],
-        "mmnn_bce_logits": [c_int64, I, V, V, V, V, V, V],
-        "mmnn_conv3d_out_shape": [POINTER(Conv3dDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
-        "mmnn_conv3d_forward": [POINTER(Conv3dDesc), V, V, V, V],
-        "mmnn_conv3d_backward_data": [POINTER(Conv3dDesc), V, V, V, V],
-        "mmnn_conv3d_backward_weight": [POINTER(Conv3dDesc), V, V, V, V, I, V],
-        "mmnn_bn3d_forward": [I, I, c_int64, V, V, V, V, V, F, F, I, I, V, F, U, V, V, V, V],
-        "mmnn_bn3d_backward": [I, I, c_int64, V, V, V, V, V, I, I, F, U, V, V, V, V, V, V],
-        "mmnn_gap_fc_sigmoid_forward": [I, I, c_int64, I, V, V, V, V, V, V],
-        "mmnn_gap_fc_sigmoid_backward": [I, I, c_int64, I, V, V, V, V, V, V, V, V],
+        "mmnn_lr_range_update": [V, I, D, D, D, V],
+        "mmnn_gradcam": [P(GradcamDesc), V, V, V, V, V, V, V, V, V, V, V],
+        "mmnn_gradcam_unimodal": [P(GradcamUnimodalDesc), P(GradcamHead), V, V, V, V, V, V, Q, V],
+        "mmnn_bce_logits": [Q, I, V, V, V, V, V, V],
+        "mmnn_conv3d_out_shape": [P(Conv3dDesc), P(I), P(I), P(I)],
+        "mmnn_conv3d_forward": [P(Conv3dDesc), V, V, V, V],
+        "mmnn_conv3d_backward_data": [P(Conv3dDesc), V, V, V, V],
+        "mmnn_conv3d_backward_weight": [P(Conv3dDesc), V, V, V, V, I, V],
+        "mmnn_bn3d_forward": [I, I, Q, V, V, V, V, V, F, F, I, I, V, F, U, V, V, V, V],
+        "mmnn_bn3d_backward": [I, I, Q, V, V, V, V, V, I, I, F, U, V, V, V, V, V, V],
+        "mmnn_gap_fc_sigmoid_forward": [I, I, Q, I, V, V, V, V, V, V],
+        "mmnn_gap_fc_sigmoid_backward": [I, I, Q, I, V, V, V, V, V, V, V, V],
         "mmnn_densenet_set_timer": [V, I, I],
-        "mmnn_densenet_read_timer": [V, POINTER(ctypes.c_double), POINTER(c_int64)],
-        "mmnn_densenet_read_timer_class": [V, I, I, POINTER(ctypes.c_double), POINTER(c_int64)],
-        "mmnn_densenet_set_option": [V, c_char_p, c_int64],
+        "mmnn_densenet_read_timer": [V, P(D), P(Q)],
+        "mmnn_densenet_read_timer_class": [V, I, I, P(D), P(Q)],
+        "mmnn_densenet_set_option": [V, S, Q],
         "mmnn_densenet_set_batch_counters": [V, V, I],
-        "mmnn_measure_mfma_clock": [POINTER(ctypes.c_double), V, V],
+        "mmnn_measure_mfma_clock": [P(D), V, V],
+        "mmnn_transform_volumes": [P(TransformDesc), P(TransformParams), V, V, V, Q, V],
+        "mmnn_ingest_volume": [P(IngestDesc), V, V, V, V, V, V],
+        "mmnn_ingest_volume_sized": [P(IngestDesc), I, V, V, V, V, V, V],
+        "mmnn_resample_mask": [P(ResampleMaskDesc), V, V, V],
+        "mmnn_maps_to_scan": [P(MapsToScanDesc), V, V, V, V, V],
+        "mmnn_maps_to_scan_sized": [P(MapsToScanDesc), I, V, V, V, V, V],
+        "mmnn_decode_slices": [P(DecodeSlicesDesc), V, V, V, V],
+        "mmnn_rasterize_contours": [P(RasterizeDesc), V, V, V, V, V],
+        "mmnn_unpack_frames": [P(UnpackFramesDesc), V, V, V, V, V],
+        "mmnn_occlude_windows": [P(OcclusionDesc), V, V, I, I, V, V],
+        "mmnn_occlusion_map": [P(OcclusionDesc), I, V, V, V, V],
+        "mmnn_channel_means": [V, I, Q, V, V, V],
+        "mmnn_radiomics": [P(RadiomicsDesc)] + [V] * 7,
+        "mmnn_radiomics_texture": [P(RadiomicsDesc)] + [V] * 9,
+        "mmnn_radiomics_zones": [P(RadiomicsDesc)] + [V] * 8,
+        "mmnn_radiomics_mesh": [P(RadiomicsDesc), V, V, P(D)] + [V] * 4,
+        "mmnn_radiomics_mesh_table": [V, V, V],
+        "mmnn_log_filter": [P(LogFilterDesc), V, V, V, V, V],
+        "mmnn_normalize_scan": [P(NormalizeDesc), V, V, V, V, V],
+        "mmnn_resample_pair": [P(ResampleDesc)] + [V] * 8,
     }
-    for name, args in sigs.items():
+    counts = {                               # int64 size, count or offset; negative: refused, with mmnn_last_error set
+        "mmnn_densenet_param_count": [V],
+        "mmnn_densenet_runstat_count": [V],
+        "mmnn_densenet_workspace_bytes": [V],
+        "mmnn_densenet_ws_offset": [V, S, I, I],
+        "mmnn_conv3d_wgrad_workspace_bytes": [P(Conv3dDesc)],
+        "mmnn_gradcam_unimodal_workspace_bytes": [P(GradcamUnimodalDesc)],
+        "mmnn_transform_workspace_bytes": [P(TransformDesc)],
+        "mmnn_ingest_workspace_bytes": [I, I, I],
+        "mmnn_maps_to_scan_workspace_bytes": [I, I, I],
+        "mmnn_occlusion_window_count": [P(OcclusionDesc), P(I)],
+        "mmnn_radiomics_workspace_bytes": [I, I, I, I],
+        "mmnn_radiomics_texture_workspace_bytes": [I, I, I, I],
+        "mmnn_radiomics_zones_workspace_bytes": [I, I, I, I],
+        "mmnn_radiomics_mesh_workspace_bytes": [I, I, I, I],
+        "mmnn_log_filter_workspace_bytes": [I, I, I],
+        "mmnn_normalize_scan_workspace_bytes": [I, I, I],
+        "mmnn_resample_pair_workspace_bytes": [I] * 6,
+        "mmnn_lr_range_state_bytes": [I],
+        "mmnn_mlp_saved_floats": [P(MlpDesc)],
+    }
+    sigs = {                                 # neither of the two: (restype, argtypes)
+        "mmnn_version": (I, []),
+        "mmnn_last_error": (S, []),
+        "mmnn_densenet_plan_create": (V, [P(DenseNetConfig), I, I, I, I]),
+        "mmnn_densenet_plan_destroy": (None, [V]),
+    }
+    sigs.update((name, (I, args)) for name, args in status.items())
+    sigs.update((name, (Q, args)) for name, args in counts.items())
+    return sigs
+
+
+def lib():
+    """Load the shared library once (torch is imported first, above, so that its HIP runtime is the one bound)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(
+            f"{LIB_PATH} not found: build it with `python -m mmnn_sts_amd.build` (hipcc, gfx950). "
+            "mmnn_sts_amd has no CPU / eager fallback.")
+    L = ctypes.CDLL(LIB_PATH)
+    for name, (restype, args) in _signatures().items():
         fn = getattr(L, name)
-        fn.restype = c_int32
+        fn.restype = restype
         fn.argtypes = args
-    L.mmnn_conv3d_wgrad_workspace_bytes.restype = c_int64
-    L.mmnn_conv3d_wgrad_workspace_bytes.argtypes = [POINTER(Conv3dDesc)]
-    L.mmnn_gradcam_unimodal_workspace_bytes.restype = c_int64
-    L.mmnn_gradcam_unimodal_workspace_bytes.argtypes = [POINTER(GradcamUnimodalDesc)]
-    L.mmnn_transform_workspace_bytes.restype = c_int64
-    L.mmnn_transform_workspace_bytes.argtypes = [POINTER(TransformDesc)]
-    L.mmnn_transform_volumes.restype = c_int32
-    L.mmnn_transform_volumes.argtypes = [POINTER(TransformDesc), POINTER(TransformParams), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-    L.mmnn_ingest_workspace_bytes.restype = c_int64
-    L.mmnn_ingest_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    L.mmnn_ingest_volume.restype = c_int32
-    L.mmnn_ingest_volume.argtypes = [POINTER(IngestDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_ingest_volume_sized.restype = c_int32
-    L.mmnn_ingest_volume_sized.argtypes = [POINTER(IngestDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_resample_mask.restype = c_int32
-    L.mmnn_resample_mask.argtypes = [POINTER(ResampleMaskDesc), c_void_p, c_void_p, c_void_p]
-    L.mmnn_maps_to_scan_workspace_bytes.restype = c_int64
-    L.mmnn_maps_to_scan_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    L.mmnn_maps_to_scan.restype = c_int32
-    L.mmnn_maps_to_scan.argtypes = [POINTER(MapsToScanDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_maps_to_scan_sized.restype = c_int32
-    L.mmnn_maps_to_scan_sized.argtypes = [POINTER(MapsToScanDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_decode_slices.restype = c_int32
-    L.mmnn_decode_slices.argtypes = [POINTER(DecodeSlicesDesc), c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_rasterize_contours.restype = c_int32
-    L.mmnn_rasterize_contours.argtypes = [POINTER(RasterizeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_unpack_frames.restype = c_int32
-    L.mmnn_unpack_frames.argtypes = [POINTER(UnpackFramesDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_occlusion_window_count.restype = c_int64
-    L.mmnn_occlusion_window_count.argtypes = [POINTER(OcclusionDesc), POINTER(c_int32)]
-    L.mmnn_occlude_windows.restype = c_int32
-    L.mmnn_occlude_windows.argtypes = [POINTER(OcclusionDesc), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]
-    L.mmnn_occlusion_map.restype = c_int32
-    L.mmnn_occlusion_map.argtypes = [POINTER(OcclusionDesc), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_radiomics_workspace_bytes.restype = c_int64
-    L.mmnn_radiomics_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mmnn_radiomics.restype = c_int32
-    L.mmnn_radiomics.argtypes = [POINTER(RadiomicsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_radiomics_texture_workspace_bytes.restype = c_int64
-    L.mmnn_radiomics_texture_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mmnn_radiomics_texture.restype = c_int32
-    L.mmnn_radiomics_texture.argtypes = [POINTER(RadiomicsDesc)] + [c_void_p] * 9
-    L.mmnn_radiomics_zones_workspace_bytes.restype = c_int64
-    L.mmnn_radiomics_zones_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mmnn_radiomics_zones.restype = c_int32
-    L.mmnn_radiomics_zones.argtypes = [POINTER(RadiomicsDesc)] + [c_void_p] * 8
-    L.mmnn_radiomics_mesh_workspace_bytes.restype = c_int64
-    L.mmnn_radiomics_mesh_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mmnn_radiomics_mesh.restype = c_int32
-    L.mmnn_radiomics_mesh.argtypes = [POINTER(RadiomicsDesc), c_void_p, c_void_p, POINTER(ctypes.c_double)] + [c_void_p] * 4
-    L.mmnn_radiomics_mesh_table.restype = c_int32
-    L.mmnn_radiomics_mesh_table.argtypes = [c_void_p, c_void_p, c_void_p]
-    L.mmnn_log_filter_workspace_bytes.restype = c_int64
-    L.mmnn_log_filter_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    L.mmnn_log_filter.restype = c_int32
-    L.mmnn_log_filter.argtypes = [POINTER(LogFilterDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_normalize_scan_workspace_bytes.restype = c_int64
-    L.mmnn_normalize_scan_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    L.mmnn_normalize_scan.restype = c_int32
-    L.mmnn_normalize_scan.argtypes = [POINTER(NormalizeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.mmnn_resample_pair_workspace_bytes.restype = c_int64
-    L.mmnn_resample_pair_workspace_bytes.argtypes = [c_int32] * 6
-    L.mmnn_resample_pair.restype = c_int32
-    L.mmnn_resample_pair.argtypes = [POINTER(ResampleDesc)] + [c_void_p] * 8
-    L.mmnn_channel_means.restype = c_int32
-    L.mmnn_channel_means.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
-    L.mmnn_lr_range_state_bytes.restype = c_int64
-    L.mmnn_lr_range_state_bytes.argtypes = [c_int32]
-    L.mmnn_mlp_saved_floats.restype = c_int64
-    L.mmnn_mlp_saved_floats.argtypes = [POINTER(MlpDesc)]
     _lib = L
     return L
 
@@ -356,3 +324,48 @@ def check(status: int, what: str) -> None:
 
 def last_error() -> str:
     return lib().mmnn_last_error().decode("utf-8", "replace")
+
+
+def call(symbol: str, *args) -> None:
+    """Call a status-returning function; a nonzero status raises through `check` under the symbol's name."""
+    status = getattr(lib(), symbol)(*args)
+    if status:
+        check(status, symbol)
+
+
+def enqueue(symbol: str, *args, device=None) -> None:
+    """`call` with the current stream appended as the last argument: the current device's, or, under a guard, that of `device`."""
+    if device is None:
+        return call(symbol, *args, torch.cuda.current_stream().cuda_stream)
+    with torch.cuda.device(device):
+        call(symbol, *args, torch.cuda.current_stream().cuda_stream)
+
+
+def count(symbol: str, *args) -> int:
+    """Call an int64 size / count / offset function; a negative result raises ValueError with the library's message."""
+    n = getattr(lib(), symbol)(*args)
+    if n < 0:
+        raise ValueError(f"{symbol}: {last_error()}")
+    return int(n)
+
+
+def device_buffer(t, shape_or_count, dtype, device, who: str):
+    """`t`, checked to be what `who` can write on `device`: contiguous, of `dtype`, with exactly that shape (a tuple) or that many
+    elements (an int); a new tensor when None."""
+    if t is None:
+        return torch.empty(shape_or_count, dtype=dtype, device=device)
+    fits = tuple(t.shape) == shape_or_count if isinstance(shape_or_count, tuple) else t.numel() == shape_or_count
+    if not (fits and t.device == device and t.dtype == dtype and t.is_contiguous()):
+        raise ValueError(f"{who}: out must be {shape_or_count} contiguous {dtype} on {device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t
+
+
+def workspace(t, nbytes: int, device, who: str):
+    """`t`, checked to hold at least `nbytes` contiguous bytes on `device`; a new uint8 tensor when None."""
+    if t is None:
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    have = t.numel() * t.element_size()
+    if t.device != device or not t.is_contiguous() or have < nbytes:
+        raise ValueError(f"{who}: workspace of {have} bytes on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}, "
+                         f"{nbytes} needed on {device}")
+    return t

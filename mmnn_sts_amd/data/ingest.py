@@ -154,25 +154,16 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
         host[table_bytes + k * frame_bytes:table_bytes + (k + 1) * frame_bytes] = frame
     code = _integer_code(series.bits_allocated, series.signed) if integer else TYPE_CODES[np.dtype("float64")]
     desc = _lib.DecodeSlicesDesc(x, y, z, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed), code)
-    with torch.cuda.device(device):
-        staged = stage.to(device, non_blocking=True)
-        out = torch.empty(x * y * z * (series.bits_allocated // 8 if integer else 8), dtype=torch.uint8, device=device)
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_decode_slices(ctypes.byref(desc), staged.data_ptr() + table_bytes, None if integer else staged.data_ptr(),
-                                                 out.data_ptr(), stream), "mmnn_decode_slices")
+    staged = stage.to(device, non_blocking=True)
+    out = torch.empty(x * y * z * (series.bits_allocated // 8 if integer else 8), dtype=torch.uint8, device=device)
+    _lib.enqueue("mmnn_decode_slices", ctypes.byref(desc), staged.data_ptr() + table_bytes, None if integer else staged.data_ptr(), out.data_ptr(),
+                 device=device)
     slope, inter = scale if integer else (1.0, 0.0)
     return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
 
 
 def _default_device(out):                    # where a call that names no device works
     return out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _mask_out(out, n, dev, who):
-    """`out`, checked to be what `who` can write `n` mask voxels to on `dev`; a new tensor when None."""
-    if out is not None and not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n):
-        raise ValueError(f"{who}: out must be {n} contiguous uint8 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-    return torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
 
 
 @dataclass
@@ -193,13 +184,10 @@ class StagedContours:
         dev = self.staged.device
         if self.slices != z:
             raise ValueError(f"rasterize_contours: slice_first has {self.slices + 1} entries, a scan of {z} slices needs {z + 1}")
-        out = _mask_out(out, x * y * z, dev, "rasterize_contours")
+        out = _lib.device_buffer(out, x * y * z, torch.uint8, dev, "rasterize_contours")
         desc = _lib.RasterizeDesc(x, y, z, self.n_contours, self.n_points)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            p = self.staged.data_ptr()
-            _lib.check(_lib.lib().mmnn_rasterize_contours(ctypes.byref(desc), p, p + self.at_records, p + self.at_slices, out.data_ptr(), stream),
-                       "mmnn_rasterize_contours")
+        p = self.staged.data_ptr()
+        _lib.enqueue("mmnn_rasterize_contours", ctypes.byref(desc), p, p + self.at_records, p + self.at_slices, out.data_ptr(), device=dev)
         return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, getattr(scan, "affine", None))
 
 
@@ -254,13 +242,10 @@ class StagedFrames:
     def to_volume(self, scan=None, out: Optional[torch.Tensor] = None) -> DeviceVolume:
         dev = self.staged.device
         x, y, z = self.shape
-        out = _mask_out(out, x * y * z, dev, "unpack_frames")
+        out = _lib.device_buffer(out, x * y * z, torch.uint8, dev, "unpack_frames")
         desc = _lib.UnpackFramesDesc(x, y, z, self.n_frames, self.n_refs, self.one)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            p = self.staged.data_ptr()
-            _lib.check(_lib.lib().mmnn_unpack_frames(ctypes.byref(desc), p + self.at_bits, p, p + self.at_slices, out.data_ptr(), stream),
-                       "mmnn_unpack_frames")
+        p = self.staged.data_ptr()
+        _lib.enqueue("mmnn_unpack_frames", ctypes.byref(desc), p + self.at_bits, p, p + self.at_slices, out.data_ptr(), device=dev)
         return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, self.affine, from_dicom=not self.on_scan)
 
 
@@ -315,10 +300,7 @@ def stage_mask(scan, mask, device):
 
 
 def workspace_bytes(x: int, y: int, z: int) -> int:
-    n = _lib.lib().mmnn_ingest_workspace_bytes(int(x), int(y), int(z))
-    if n < 0:
-        raise ValueError("mmnn_ingest_workspace_bytes: " + _lib.last_error())
-    return int(n)
+    return _lib.count("mmnn_ingest_workspace_bytes", int(x), int(y), int(z))
 
 
 def resample_mask(mask, scan_shape, index_map, threshold: float = 0.5, out: Optional[torch.Tensor] = None) -> DeviceVolume:
@@ -334,13 +316,10 @@ def resample_mask(mask, scan_shape, index_map, threshold: float = 0.5, out: Opti
         mask = upload(mask, _default_device(out))
     dev = mask.data.device
     if min(x, y, z) >= 1:
-        out = _mask_out(out, x * y * z, dev, "resample_mask")
+        out = _lib.device_buffer(out, x * y * z, torch.uint8, dev, "resample_mask")
     mx, my, mz = mask.shape
     desc = _lib.ResampleMaskDesc(x, y, z, mx, my, mz, mask.datatype, mask.slope, mask.inter, (ctypes.c_double * 12)(*t.reshape(-1)), float(threshold))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_resample_mask(ctypes.byref(desc), mask.data.data_ptr(), out.data_ptr() if out is not None else None, stream),
-                   "mmnn_resample_mask")
+    _lib.enqueue("mmnn_resample_mask", ctypes.byref(desc), mask.data.data_ptr(), out.data_ptr() if out is not None else None, device=dev)
     return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0)
 
 
@@ -470,29 +449,17 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     size = shape[0]
     dev = out_plane.device
     scan, mask = prepare_pair(scan, mask, dev, index_map, threshold)
-    if extents is None:
-        extents = torch.empty(3, dtype=torch.int32, device=dev)
-    if not (extents.is_cuda and extents.dtype == torch.int32 and extents.is_contiguous() and extents.numel() == 3):
-        raise ValueError("ingest: extents must be 3 contiguous int32 on the device")
+    extents = _lib.device_buffer(extents, 3, torch.int32, dev, "ingest (extents)")
     x, y, z = scan.shape
-    nbytes = workspace_bytes(x, y, z)
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    elif workspace.numel() * workspace.element_size() < nbytes:
-        raise ValueError(f"ingest: workspace of {workspace.numel() * workspace.element_size()} bytes, {nbytes} needed")
+    workspace = _lib.workspace(workspace, workspace_bytes(x, y, z), dev, "ingest")
     desc = _lib.IngestDesc(x, y, z, scan.datatype, mask.datatype, scan.slope, scan.inter, mask.slope, mask.inter)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_ingest_volume_sized(ctypes.byref(desc), size, scan.data.data_ptr(), mask.data.data_ptr(), out_plane.data_ptr(),
-                                                       extents.data_ptr(), workspace.data_ptr(), stream), "mmnn_ingest_volume_sized")
+    _lib.enqueue("mmnn_ingest_volume_sized", ctypes.byref(desc), size, scan.data.data_ptr(), mask.data.data_ptr(), out_plane.data_ptr(),
+                 extents.data_ptr(), workspace.data_ptr(), device=dev)
     return extents
 
 
 def maps_to_scan_workspace_bytes(x: int, y: int, z: int) -> int:
-    n = _lib.lib().mmnn_maps_to_scan_workspace_bytes(int(x), int(y), int(z))
-    if n < 0:
-        raise ValueError("mmnn_maps_to_scan_workspace_bytes: " + _lib.last_error())
-    return int(n)
+    return _lib.count("mmnn_maps_to_scan_workspace_bytes", int(x), int(y), int(z))
 
 
 def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -522,22 +489,13 @@ def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor,
     if ingest_workspace.device != dev:
         raise ValueError(f"maps_to_scan: ingest_workspace is on {ingest_workspace.device}, the maps on {dev}")
     n = int(maps.shape[0])
-    if out is None:
-        out = torch.empty((n, z, y, x), dtype=torch.float32, device=dev)
-    elif not (out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, z, y, x)):
-        raise ValueError(f"maps_to_scan: out must be a contiguous ({n}, {z}, {y}, {x}) fp32 tensor on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    out = _lib.device_buffer(out, (n, z, y, x), torch.float32, dev, "maps_to_scan")
     if ingest_workspace.numel() < workspace_bytes(x, y, z):
         raise ValueError(f"maps_to_scan: ingest_workspace of {ingest_workspace.numel()} bytes, an ingest of {x} x {y} x {z} leaves {workspace_bytes(x, y, z)}")
-    nbytes = maps_to_scan_workspace_bytes(x, y, z)
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    elif not (workspace.device == dev and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= nbytes):
-        raise ValueError(f"maps_to_scan: workspace must be {nbytes} contiguous bytes on {dev}")
+    workspace = _lib.workspace(workspace, maps_to_scan_workspace_bytes(x, y, z), dev, "maps_to_scan")
     desc = _lib.MapsToScanDesc(x, y, z, n)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_maps_to_scan_sized(ctypes.byref(desc), int(maps.shape[1]), ingest_workspace.data_ptr(), maps.data_ptr(),
-                                                      out.data_ptr(), workspace.data_ptr(), stream), "mmnn_maps_to_scan_sized")
+    _lib.enqueue("mmnn_maps_to_scan_sized", ctypes.byref(desc), int(maps.shape[1]), ingest_workspace.data_ptr(), maps.data_ptr(), out.data_ptr(),
+                 workspace.data_ptr(), device=dev)
     return out
 
 

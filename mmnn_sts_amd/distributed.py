@@ -51,14 +51,12 @@ def _small_bucket(small: List[torch.Tensor]):
 
 def _multi_copy(small, flat, offs, scatter: bool) -> None:
     from . import _lib
-    L = _lib.lib()
-    st = torch.cuda.current_stream().cuda_stream
     for lo in range(0, len(small), _lib.MULTI_MAX):
         chunk = small[lo:lo + _lib.MULTI_MAX]
         refs = (_lib.TensorRef * len(chunk))()
         for r, b, o in zip(refs, chunk, offs[lo:lo + _lib.MULTI_MAX]):
             r.param, r.grad, r.count, r.flat_offset, r.first_step = None, b.data_ptr(), b.numel(), o, 0
-        _lib.check(L.mmnn_multi_copy(refs, len(chunk), flat.data_ptr(), int(scatter), st), "multi_copy")
+        _lib.enqueue("mmnn_multi_copy", refs, len(chunk), flat.data_ptr(), int(scatter))
 
 
 def _reduce_small(small: List[torch.Tensor], group) -> None:

@@ -109,14 +109,13 @@ class _Backbone(nn.Sequential):
         """[(begin, end)] of the flat buffers in backward completion order: last block first; the first block's range includes the stem."""
         r = ent.get("ranges")
         if r is None:
-            L = _lib.lib()
             nb = len(self.cfg["block_config"])
             b, e = ctypes.c_int64(), ctypes.c_int64()
             r = []
             for blk in range(nb - 1, -1, -1):
-                _lib.check(L.mmnn_densenet_block_param_range(ent["plan"], blk, ctypes.byref(b), ctypes.byref(e)), "block_param_range")
+                _lib.call("mmnn_densenet_block_param_range", ent["plan"], blk, ctypes.byref(b), ctypes.byref(e))
                 r.append([blk, b.value, e.value])
-            _lib.check(L.mmnn_densenet_block_param_range(ent["plan"], -1, ctypes.byref(b), ctypes.byref(e)), "block_param_range")
+            _lib.call("mmnn_densenet_block_param_range", ent["plan"], -1, ctypes.byref(b), ctypes.byref(e))
             assert e.value == r[-1][1] and b.value == 0
             r[-1][1] = 0                                   # the call for block 0 also finishes the stem
             r = ent["ranges"] = [tuple(t) for t in r]
@@ -230,12 +229,12 @@ class _Backbone(nn.Sequential):
             L.mmnn_densenet_plan_destroy(plan)
             raise RuntimeError("parameter layout mismatch between the Python module tree and the native plan")
         shp = [ctypes.c_int32() for _ in range(4)]
-        _lib.check(L.mmnn_densenet_out_shape(plan, *[ctypes.byref(v) for v in shp]), "out_shape")
+        _lib.call("mmnn_densenet_out_shape", plan, *[ctypes.byref(v) for v in shp])
         ws = torch.empty(L.mmnn_densenet_workspace_bytes(plan), dtype=torch.uint8, device=x.device)
         if os.environ.get("MMNN_POISON_WS") == "1":   # debugging aid: NaN-fill so reads of unwritten workspace words surface
             ws.fill_(255)
         # nn.BatchNorm3d.num_batches_tracked: the training forward's running-statistics kernel adds 1 to each (no torch op per step)
-        _lib.check(L.mmnn_densenet_set_batch_counters(plan, self._flat_nbt.data_ptr(), self._flat_nbt.numel()), "set_batch_counters")
+        _lib.call("mmnn_densenet_set_batch_counters", plan, self._flat_nbt.data_ptr(), self._flat_nbt.numel())
         ent = {"plan": plan, "ws": ws, "out_shape": (n,) + tuple(v.value for v in shp), "nbt_ptr": self._flat_nbt.data_ptr()}
         self._plans[key] = ent
         while len(self._plans) > self._MAX_PLANS:
@@ -280,15 +279,14 @@ class _Backbone(nn.Sequential):
         out = torch.empty(ent["out_shape"], dtype=torch.float32, device=x.device)
         seed = ops.next_seed()
         if ent["nbt_ptr"] != self._flat_nbt.data_ptr():          # re-flattened since the plan was made
-            _lib.check(_lib.lib().mmnn_densenet_set_batch_counters(ent["plan"], self._flat_nbt.data_ptr(), self._flat_nbt.numel()), "set_batch_counters")
+            _lib.call("mmnn_densenet_set_batch_counters", ent["plan"], self._flat_nbt.data_ptr(), self._flat_nbt.numel())
             ent["nbt_ptr"] = self._flat_nbt.data_ptr()
         version = self._params_version() if self.repack_policy == "versioned" else 0
         if version != ent.get("version", 0):
-            _lib.check(_lib.lib().mmnn_densenet_set_option(ent["plan"], b"params_version", version), "set_option")
+            _lib.call("mmnn_densenet_set_option", ent["plan"], b"params_version", version)
             ent["version"] = version
-        _lib.check(_lib.lib().mmnn_densenet_forward(ent["plan"], self._flat.data_ptr(), self._flat_run.data_ptr(), x.data_ptr(),
-                                                    ent["ws"].data_ptr(), out.data_ptr(), int(training), seed,
-                                                    torch.cuda.current_stream().cuda_stream), "mmnn_densenet_forward")
+        _lib.enqueue("mmnn_densenet_forward", ent["plan"], self._flat.data_ptr(), self._flat_run.data_ptr(), x.data_ptr(), ent["ws"].data_ptr(),
+                     out.data_ptr(), int(training), seed)
         object.__setattr__(self, "_fwd_token", self._fwd_token + 1)
         return out, ent, seed, self._fwd_token
 
@@ -308,16 +306,13 @@ class _Backbone(nn.Sequential):
         # stale by FusedSGD.zero_grad() (which keeps the views attached: re-attaching 364 tensors per step costs ~1.5 ms of host time)
         fresh = (not attached) or self._grads_stale
         hook = self._grad_ready_hook
-        st = torch.cuda.current_stream().cuda_stream
         if hook is None:
-            _lib.check(_lib.lib().mmnn_densenet_backward(ent["plan"], self._flat.data_ptr(), x.data_ptr(), ent["ws"].data_ptr(),
-                                                         grad_out.data_ptr(), gflat.data_ptr(), 0 if fresh else 1, seed, st),
-                       "mmnn_densenet_backward")
+            _lib.enqueue("mmnn_densenet_backward", ent["plan"], self._flat.data_ptr(), x.data_ptr(), ent["ws"].data_ptr(), grad_out.data_ptr(),
+                         gflat.data_ptr(), 0 if fresh else 1, seed)
         else:
             for blk, begin, end in self.block_param_ranges(ent):
-                _lib.check(_lib.lib().mmnn_densenet_backward_range(ent["plan"], self._flat.data_ptr(), x.data_ptr(), ent["ws"].data_ptr(),
-                                                                   grad_out.data_ptr(), gflat.data_ptr(), 0 if fresh else 1, seed, blk, blk, st),
-                           "mmnn_densenet_backward_range")
+                _lib.enqueue("mmnn_densenet_backward_range", ent["plan"], self._flat.data_ptr(), x.data_ptr(), ent["ws"].data_ptr(),
+                             grad_out.data_ptr(), gflat.data_ptr(), 0 if fresh else 1, seed, blk, blk)
                 hook(self, begin, end)
         if not attached:   # (re)attach .grad views; afterwards gradients accumulate inside the kernel
             off = 0

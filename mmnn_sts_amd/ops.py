@@ -11,10 +11,6 @@ import torch
 from . import _lib
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _need_cuda(*ts: torch.Tensor) -> None:
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -53,8 +49,8 @@ class GapLinear(torch.autograd.Function):
         pooled = torch.empty((n, c), device=h.device, dtype=torch.float32)
         out = torch.empty((n, f), device=h.device, dtype=torch.float32)
         seed = next_seed()
-        _lib.check(_lib.lib().mmnn_gap_linear_forward(n, c, v, f, h.data_ptr(), weight.data_ptr(), bias.data_ptr(), pooled.data_ptr(),
-                                                      out.data_ptr(), float(p), seed, int(training), _stream()), "gap_linear_forward")
+        _lib.enqueue("mmnn_gap_linear_forward", n, c, v, f, h.data_ptr(), weight.data_ptr(), bias.data_ptr(), pooled.data_ptr(), out.data_ptr(),
+                     float(p), seed, int(training))
         ctx.save_for_backward(h, weight, pooled)
         ctx.meta = (n, c, v, f, float(p), seed, int(training))
         return out
@@ -67,9 +63,8 @@ class GapLinear(torch.autograd.Function):
         dw = torch.empty_like(weight)
         db = torch.empty((f,), device=h.device, dtype=torch.float32)
         dh = torch.empty_like(h)
-        _lib.check(_lib.lib().mmnn_gap_linear_backward(n, c, v, f, h.data_ptr(), weight.data_ptr(), pooled.data_ptr(), dout.data_ptr(),
-                                                       dw.data_ptr(), db.data_ptr(), dh.data_ptr(), p, seed, training, 0, _stream()),
-                   "gap_linear_backward")
+        _lib.enqueue("mmnn_gap_linear_backward", n, c, v, f, h.data_ptr(), weight.data_ptr(), pooled.data_ptr(), dout.data_ptr(), dw.data_ptr(),
+                     db.data_ptr(), dh.data_ptr(), p, seed, training, 0)
         return dh, dw, db, None, None
 
 
@@ -110,11 +105,9 @@ class MlpStack(torch.autograd.Function):
             pp.running_mean[i], pp.running_var[i] = running[2 * i].data_ptr(), running[2 * i + 1].data_ptr()
             if len(cfg) > 6 and cfg[6] is not None:           # nn.BatchNorm1d.num_batches_tracked, +1 per training forward (in the kernel)
                 pp.num_batches_tracked[i] = cfg[6][i].data_ptr()
-        L = _lib.lib()
-        saved = torch.empty((max(1, L.mmnn_mlp_saved_floats(ctypes.byref(desc))),), device=x.device, dtype=torch.float32)
+        saved = torch.empty((max(1, _lib.lib().mmnn_mlp_saved_floats(ctypes.byref(desc))),), device=x.device, dtype=torch.float32)
         out = torch.empty((n, dims_out[-1]), device=x.device, dtype=torch.float32)
-        _lib.check(L.mmnn_mlp_forward(ctypes.byref(desc), ctypes.byref(pp), x.data_ptr(), out.data_ptr(), saved.data_ptr(), _stream()),
-                   "mlp_forward")
+        _lib.enqueue("mmnn_mlp_forward", ctypes.byref(desc), ctypes.byref(pp), x.data_ptr(), out.data_ptr(), saved.data_ptr())
         ctx.save_for_backward(x, saved, *ws)
         ctx.desc_args = (n, dims_in, dims_out, relu_first, p, eps, momentum, seed, training, first_id)
         ctx.running = running
@@ -135,8 +128,8 @@ class MlpStack(torch.autograd.Function):
         dy = _f32c(dy)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         scratch = torch.empty((2 * n * max(dims_in + dims_out),), device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mmnn_mlp_backward(ctypes.byref(desc), ctypes.byref(pp), x.data_ptr(), saved.data_ptr(), dy.data_ptr(),
-                                                dx.data_ptr() if dx is not None else None, scratch.data_ptr(), 0, _stream()), "mlp_backward")
+        _lib.enqueue("mmnn_mlp_backward", ctypes.byref(desc), ctypes.byref(pp), x.data_ptr(), saved.data_ptr(), dy.data_ptr(),
+                     dx.data_ptr() if dx is not None else None, scratch.data_ptr(), 0)
         return (dx, None, None, *grads)
 
 
@@ -151,8 +144,7 @@ class SmallLinear(torch.autograd.Function):
         bias = _f32c(bias) if bias is not None else None
         n, d, o = x.shape[0], x.shape[1], weight.shape[0]
         y = torch.empty((n, o), device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mmnn_linear_forward(n, d, o, x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                  y.data_ptr(), _stream()), "linear_forward")
+        _lib.enqueue("mmnn_linear_forward", n, d, o, x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr())
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y
@@ -165,9 +157,8 @@ class SmallLinear(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(weight)
         db = torch.empty((o,), device=x.device, dtype=torch.float32) if ctx.has_bias else None
-        _lib.check(_lib.lib().mmnn_linear_backward(n, d, o, x.data_ptr(), weight.data_ptr(), dy.data_ptr(),
-                                                   dx.data_ptr() if dx is not None else None, dw.data_ptr(),
-                                                   db.data_ptr() if db is not None else None, 0, _stream()), "linear_backward")
+        _lib.enqueue("mmnn_linear_backward", n, d, o, x.data_ptr(), weight.data_ptr(), dy.data_ptr(), dx.data_ptr() if dx is not None else None,
+                     dw.data_ptr(), db.data_ptr() if db is not None else None, 0)
         return dx, dw, db
 
 
@@ -182,9 +173,8 @@ class FusionHeads(torch.autograd.Function):
         n, f = fi.shape
         c = wf.shape[0]
         out = torch.empty((3, n, c) if blend else (n, c), device=fi.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mmnn_fusion_heads_forward(n, f, c, int(blend), fi.data_ptr(), fc.data_ptr(), wf.data_ptr(), bf.data_ptr(),
-                                                        wi.data_ptr(), bi.data_ptr(), wc.data_ptr(), bc.data_ptr(), out.data_ptr(),
-                                                        _stream()), "fusion_heads_forward")
+        _lib.enqueue("mmnn_fusion_heads_forward", n, f, c, int(blend), fi.data_ptr(), fc.data_ptr(), wf.data_ptr(), bf.data_ptr(), wi.data_ptr(),
+                     bi.data_ptr(), wc.data_ptr(), bc.data_ptr(), out.data_ptr())
         ctx.save_for_backward(fi, fc, wf, wi, wc)
         ctx.meta = (n, f, c, bool(blend))
         return out
@@ -202,10 +192,8 @@ class FusionHeads(torch.autograd.Function):
         dwi, dwc = (torch.empty_like(wi), torch.empty_like(wc)) if blend else (None, None)
         dbi, dbc = (torch.empty((c,), device=dev, dtype=torch.float32), torch.empty((c,), device=dev, dtype=torch.float32)) if blend else (None, None)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(_lib.lib().mmnn_fusion_heads_backward(n, f, c, int(blend), fi.data_ptr(), fc.data_ptr(), wf.data_ptr(), wi.data_ptr(),
-                                                         wc.data_ptr(), dout.data_ptr(), dfi.data_ptr(), dfc.data_ptr(), dwf.data_ptr(),
-                                                         dbf.data_ptr(), ptr(dwi), ptr(dbi), ptr(dwc), ptr(dbc), 0,
-                                                         _stream()), "fusion_heads_backward")
+        _lib.enqueue("mmnn_fusion_heads_backward", n, f, c, int(blend), fi.data_ptr(), fc.data_ptr(), wf.data_ptr(), wi.data_ptr(), wc.data_ptr(),
+                     dout.data_ptr(), dfi.data_ptr(), dfc.data_ptr(), dwf.data_ptr(), dbf.data_ptr(), ptr(dwi), ptr(dbi), ptr(dwc), ptr(dbc), 0)
         return dfi, dfc, dwf, dbf, dwi, dbi, dwc, dbc, None
 
 
@@ -229,9 +217,8 @@ class CoxBlend(torch.autograd.Function):
         out = torch.empty((1 + h,), device=dev, dtype=torch.float32)
         grad = torch.empty_like(preds)
         scratch = torch.empty((4 * n,), device=dev, dtype=torch.float32)
-        _lib.check(_lib.lib().mmnn_cox_blend_loss_typed(h, n, c, preds.data_ptr(), sort_key.data_ptr(), kdt, weight.data_ptr(), wdt,
-                                                        hw.data_ptr() if hw is not None else None, out.data_ptr(), out[1:].data_ptr(),
-                                                        grad.data_ptr(), scratch.data_ptr(), _stream()), "cox_blend_loss")
+        _lib.enqueue("mmnn_cox_blend_loss_typed", h, n, c, preds.data_ptr(), sort_key.data_ptr(), kdt, weight.data_ptr(), wdt,
+                     hw.data_ptr() if hw is not None else None, out.data_ptr(), out[1:].data_ptr(), grad.data_ptr(), scratch.data_ptr())
         ctx.save_for_backward(grad, hw)
         ctx.set_materialize_grads(False)     # unused outputs arrive as None instead of zero tensors (no device sync needed)
         return out[0], out[1:]
@@ -245,9 +232,8 @@ class CoxBlend(torch.autograd.Function):
         g = torch.empty_like(grad)
         dl = _f32c(dloss) if dloss is not None else None
         dh = _f32c(dheads) if dheads is not None else None      # d head_losses[h] / d preds = grad[h] / head_weights[h]
-        _lib.check(_lib.lib().mmnn_cox_blend_backward(h, n, c, grad.data_ptr(), hw.data_ptr() if hw is not None else None,
-                                                      dl.data_ptr() if dl is not None else None, dh.data_ptr() if dh is not None else None,
-                                                      g.data_ptr(), _stream()), "cox_blend_backward")
+        _lib.enqueue("mmnn_cox_blend_backward", h, n, c, grad.data_ptr(), hw.data_ptr() if hw is not None else None,
+                     dl.data_ptr() if dl is not None else None, dh.data_ptr() if dh is not None else None, g.data_ptr())
         return g, None, None, None
 
 
@@ -280,8 +266,8 @@ class BceLogits(torch.autograd.Function):
             raise ValueError(f"pos_weight has {pw.numel()} entries for {c} classes")
         loss = torch.empty_like(x)
         dldx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        _lib.check(_lib.lib().mmnn_bce_logits(x.numel(), c, x.data_ptr(), y.data_ptr(), pw.data_ptr() if pw is not None else None,
-                                              loss.data_ptr(), dldx.data_ptr() if dldx is not None else None, _stream()), "bce_logits")
+        _lib.enqueue("mmnn_bce_logits", x.numel(), c, x.data_ptr(), y.data_ptr(), pw.data_ptr() if pw is not None else None, loss.data_ptr(),
+                     dldx.data_ptr() if dldx is not None else None)
         ctx.save_for_backward(dldx)
         return loss
 
@@ -316,8 +302,8 @@ class CrossEntropy(torch.autograd.Function):
         red = _lib.CE_REDUCTIONS[reduction]
         loss = torch.empty((n,) if red == 0 else (), device=z.device, dtype=torch.float32)
         saved = torch.empty_like(z) if ctx.needs_input_grad[0] else None
-        _lib.check(_lib.lib().mmnn_cross_entropy(n, c, z.data_ptr(), t.data_ptr(), kind, int(ignore_index), red, loss.data_ptr(),
-                                                 saved.data_ptr() if saved is not None else None, _stream()), "cross_entropy")
+        _lib.enqueue("mmnn_cross_entropy", n, c, z.data_ptr(), t.data_ptr(), kind, int(ignore_index), red, loss.data_ptr(),
+                     saved.data_ptr() if saved is not None else None)
         ctx.save_for_backward(saved)
         ctx.red = red
         return loss
@@ -330,8 +316,7 @@ class CrossEntropy(torch.autograd.Function):
         n, c = saved.shape
         dl = _f32c(dloss)
         dz = torch.empty_like(saved)
-        _lib.check(_lib.lib().mmnn_cross_entropy_backward(n, c, ctx.red, saved.data_ptr(), dl.data_ptr(), dz.data_ptr(), _stream()),
-                   "cross_entropy_backward")
+        _lib.enqueue("mmnn_cross_entropy_backward", n, c, ctx.red, saved.data_ptr(), dl.data_ptr(), dz.data_ptr())
         return dz, None, None, None
 
 
@@ -358,11 +343,10 @@ class Conv3dDirect(torch.autograd.Function):
             raise ValueError(f"conv3d: input {tuple(x.shape)} does not match weight {tuple(weight.shape)}")
         stride, padding = _triple(stride), _triple(padding)
         desc = _conv_desc(x.shape, weight.shape[0], tuple(weight.shape[2:]), stride, padding)
-        L = _lib.lib()
         o = [ctypes.c_int32() for _ in range(3)]
-        _lib.check(L.mmnn_conv3d_out_shape(ctypes.byref(desc), *[ctypes.byref(v) for v in o]), "conv3d_out_shape")
+        _lib.call("mmnn_conv3d_out_shape", ctypes.byref(desc), *[ctypes.byref(v) for v in o])
         y = torch.empty((x.shape[0], weight.shape[0], o[0].value, o[1].value, o[2].value), device=x.device, dtype=torch.float32)
-        _lib.check(L.mmnn_conv3d_forward(ctypes.byref(desc), x.data_ptr(), weight.data_ptr(), y.data_ptr(), _stream()), "conv3d_forward")
+        _lib.enqueue("mmnn_conv3d_forward", ctypes.byref(desc), x.data_ptr(), weight.data_ptr(), y.data_ptr())
         ctx.save_for_backward(x, weight)
         ctx.geom = (stride, padding)
         return y
@@ -373,15 +357,13 @@ class Conv3dDirect(torch.autograd.Function):
         stride, padding = ctx.geom
         dy = _f32c(dy)
         desc = _conv_desc(x.shape, weight.shape[0], tuple(weight.shape[2:]), stride, padding)
-        L = _lib.lib()
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(L.mmnn_conv3d_backward_data(ctypes.byref(desc), dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), _stream()), "conv3d_backward_data")
+            _lib.enqueue("mmnn_conv3d_backward_data", ctypes.byref(desc), dy.data_ptr(), weight.data_ptr(), dx.data_ptr())
         dw = torch.empty_like(weight)
-        ws = torch.empty((L.mmnn_conv3d_wgrad_workspace_bytes(ctypes.byref(desc)),), dtype=torch.uint8, device=x.device)
-        _lib.check(L.mmnn_conv3d_backward_weight(ctypes.byref(desc), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), 0, _stream()),
-                   "conv3d_backward_weight")
+        ws = torch.empty((_lib.lib().mmnn_conv3d_wgrad_workspace_bytes(ctypes.byref(desc)),), dtype=torch.uint8, device=x.device)
+        _lib.enqueue("mmnn_conv3d_backward_weight", ctypes.byref(desc), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), 0)
         return dx, dw, None, None
 
 
@@ -401,10 +383,9 @@ class BatchNormAct3d(torch.autograd.Function):
         save = torch.empty((2, c), device=x.device, dtype=torch.float32)
         stat = torch.empty((2, c), device=x.device, dtype=torch.float64)
         seed = next_seed()
-        _lib.check(_lib.lib().mmnn_bn3d_forward(n, c, v, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(),
-                                                running_var.data_ptr(), float(momentum), float(eps), int(training), int(relu),
-                                                res.data_ptr() if res is not None else None, float(drop_p), seed, out.data_ptr(),
-                                                save.data_ptr(), stat.data_ptr(), _stream()), "bn3d_forward")
+        _lib.enqueue("mmnn_bn3d_forward", n, c, v, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
+                     float(momentum), float(eps), int(training), int(relu), res.data_ptr() if res is not None else None, float(drop_p), seed,
+                     out.data_ptr(), save.data_ptr(), stat.data_ptr())
         ctx.save_for_backward(x, out, gamma, save)
         ctx.meta = (int(training), int(relu), float(drop_p), seed, res is not None)
         return out
@@ -421,9 +402,8 @@ class BatchNormAct3d(torch.autograd.Function):
         dg = torch.empty((c,), device=x.device, dtype=torch.float32)
         db = torch.empty((c,), device=x.device, dtype=torch.float32)
         stat = torch.empty((2, c), device=x.device, dtype=torch.float64)
-        _lib.check(_lib.lib().mmnn_bn3d_backward(n, c, v, x.data_ptr(), out.data_ptr(), dout.data_ptr(), gamma.data_ptr(), save.data_ptr(),
-                                                 training, relu, drop_p, seed, dx.data_ptr(), dres.data_ptr() if dres is not None else None,
-                                                 dg.data_ptr(), db.data_ptr(), stat.data_ptr(), _stream()), "bn3d_backward")
+        _lib.enqueue("mmnn_bn3d_backward", n, c, v, x.data_ptr(), out.data_ptr(), dout.data_ptr(), gamma.data_ptr(), save.data_ptr(), training, relu,
+                     drop_p, seed, dx.data_ptr(), dres.data_ptr() if dres is not None else None, dg.data_ptr(), db.data_ptr(), stat.data_ptr())
         return dx, dg, db, None, None, dres, None, None, None, None, None
 
 
@@ -439,8 +419,7 @@ class GapFcSigmoid(torch.autograd.Function):
         o = weight.shape[0]
         pooled = torch.empty((n, c), device=x.device, dtype=torch.float32)
         y = torch.empty((n, o), device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mmnn_gap_fc_sigmoid_forward(n, c, v, o, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), pooled.data_ptr(),
-                                                          y.data_ptr(), _stream()), "gap_fc_sigmoid_forward")
+        _lib.enqueue("mmnn_gap_fc_sigmoid_forward", n, c, v, o, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), pooled.data_ptr(), y.data_ptr())
         ctx.save_for_backward(weight, pooled, y)
         ctx.shape = tuple(x.shape)
         return y
@@ -456,7 +435,6 @@ class GapFcSigmoid(torch.autograd.Function):
         dx = torch.empty(ctx.shape, device=weight.device, dtype=torch.float32)
         dw = torch.empty_like(weight)
         db = torch.empty((weight.shape[0],), device=weight.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mmnn_gap_fc_sigmoid_backward(n, c, v, weight.shape[0], weight.data_ptr(), pooled.data_ptr(), y.data_ptr(),
-                                                           dy.data_ptr(), dw.data_ptr(), db.data_ptr(), dx.data_ptr(), _stream()),
-                   "gap_fc_sigmoid_backward")
+        _lib.enqueue("mmnn_gap_fc_sigmoid_backward", n, c, v, weight.shape[0], weight.data_ptr(), pooled.data_ptr(), y.data_ptr(), dy.data_ptr(),
+                     dw.data_ptr(), db.data_ptr(), dx.data_ptr())
         return dx, dw, db

@@ -50,8 +50,6 @@ class FusedSGD(torch.optim.Optimizer):
     def _step(self, lr, lr_ptr, live_ptr):
         g = self.param_groups[0]
         mom, wd, nes = float(g["momentum"]), float(g["weight_decay"]), int(bool(g["nesterov"]))
-        st = torch.cuda.current_stream().cuda_stream
-        L = _lib.lib()
         for bb in self._backbones:
             flat, grad = bb.flat_parameters, bb.flat_grad
             if grad is None or bb.conv0.weight.grad is None or bb._grads_stale:
@@ -60,11 +58,10 @@ class FusedSGD(torch.optim.Optimizer):
             if first:
                 self._bufs[id(bb)] = torch.empty_like(flat)
             if lr_ptr is None:
-                _lib.check(L.mmnn_sgd_step(flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr, mom, wd,
-                                           nes, int(first), st), "sgd_step")
+                _lib.enqueue("mmnn_sgd_step", flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr, mom, wd, nes, int(first))
             else:
-                _lib.check(L.mmnn_sgd_step_dev(flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr_ptr, live_ptr,
-                                               mom, wd, nes, int(first), st), "sgd_step_dev")
+                _lib.enqueue("mmnn_sgd_step_dev", flat.data_ptr(), grad.data_ptr(), self._bufs[id(bb)].data_ptr(), flat.numel(), lr_ptr, live_ptr,
+                             mom, wd, nes, int(first))
             bb.mark_params_changed()          # written through the raw pointer: invisible to autograd's version counters
         live = [(i, p) for i, p in enumerate(self._rest) if p.grad is not None]
         if live:
@@ -82,10 +79,9 @@ class FusedSGD(torch.optim.Optimizer):
                     r.param, r.grad, r.count, r.flat_offset = p.data_ptr(), gr.data_ptr(), p.numel(), self._rest_off[i]
                     r.first_step = int(i not in self._rest_started)      # mom == 0: the buffer is written but never read back
                 if lr_ptr is None:
-                    _lib.check(L.mmnn_sgd_step_multi(refs, len(chunk), self._rest_buf.data_ptr(), lr, mom, wd, nes, st), "sgd_step_multi")
+                    _lib.enqueue("mmnn_sgd_step_multi", refs, len(chunk), self._rest_buf.data_ptr(), lr, mom, wd, nes)
                 else:
-                    _lib.check(L.mmnn_sgd_step_multi_dev(refs, len(chunk), self._rest_buf.data_ptr(), lr_ptr, live_ptr, mom, wd, nes, st),
-                               "sgd_step_multi_dev")
+                    _lib.enqueue("mmnn_sgd_step_multi_dev", refs, len(chunk), self._rest_buf.data_ptr(), lr_ptr, live_ptr, mom, wd, nes)
             self._rest_started.update(i for i, _ in live)
 
     def snapshot_state(self):

@@ -231,16 +231,8 @@ class RadiomicsResult:
     source_shape: Optional[tuple] = None
 
 
-def _bytes_or_raise(symbol: str, *extents) -> int:
-    """A `*_workspace_bytes` function of the library at these extents; its -1 raises with the library's message."""
-    n = getattr(_lib.lib(), symbol)(*(int(v) for v in extents))
-    if n < 0:
-        raise ValueError(f"{symbol}: " + _lib.last_error())
-    return int(n)
-
-
 def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
-    return _bytes_or_raise("mmnn_radiomics_workspace_bytes", x, y, z, max_bins)
+    return _lib.count("mmnn_radiomics_workspace_bytes", int(x), int(y), int(z), int(max_bins))
 
 
 def spacing_of(affine) -> Tuple[float, float, float]:
@@ -309,26 +301,13 @@ def _enqueue_log_filter(scan, sigma_mm, out, workspace, taps):
     dev = scan.data.device
     x, y, z = scan.shape
     radius, host_taps, weight = log_taps(sigma_mm, spacing_of(scan.affine))
-    nbytes = _bytes_or_raise("mmnn_log_filter_workspace_bytes", x, y, z)
-    if out is None:
-        out = torch.empty(x * y * z, dtype=torch.float32, device=dev)
-    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x * y * z and out.device == dev):
-        raise ValueError(f"log_filter: out must be {x * y * z} contiguous float32 on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}")
-    if workspace is None:
-        workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < nbytes:
-        raise ValueError(f"log_filter: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, {nbytes} needed on {dev}")
-    if taps is None:
-        taps = torch.empty(host_taps.size, dtype=torch.float64, device=dev)
-    if not (taps.dtype == torch.float64 and taps.is_contiguous() and taps.numel() == host_taps.size and taps.device == dev):
-        raise ValueError(f"log_filter: taps must be {host_taps.size} contiguous float64 on {dev}")
+    out = _lib.device_buffer(out, x * y * z, torch.float32, dev, "log_filter")
+    workspace = _lib.workspace(workspace, _lib.count("mmnn_log_filter_workspace_bytes", x, y, z), dev, "log_filter")
+    taps = _lib.device_buffer(taps, host_taps.size, torch.float64, dev, "log_filter (taps)")
     taps.copy_(torch.from_numpy(host_taps))
     desc = _lib.LogFilterDesc(x, y, z, scan.datatype, float(scan.slope), float(scan.inter), (ctypes.c_int32 * 3)(*radius.tolist()),
                               (ctypes.c_double * 3)(*weight.tolist()))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_log_filter(ctypes.byref(desc), scan.data.data_ptr(), taps.data_ptr(), out.data_ptr(), workspace.data_ptr(),
-                                              stream), "mmnn_log_filter")
+    _lib.enqueue("mmnn_log_filter", ctypes.byref(desc), scan.data.data_ptr(), taps.data_ptr(), out.data_ptr(), workspace.data_ptr(), device=dev)
     return ingest.DeviceVolume(out.view(torch.uint8), (x, y, z), 16, 0.0, 0.0, scan.affine), workspace, taps
 
 
@@ -478,42 +457,21 @@ def unpack_normalize(raw: np.ndarray) -> dict:
             "nonfinite": bool(raw[24:32].view(np.int64)[0])}
 
 
-def _device_buffer(out, n, dev, what, dtype=torch.float32):
-    if out is None:
-        out = torch.empty(n, dtype=dtype, device=dev)
-    if not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and out.numel() == n and out.device == dev):
-        raise ValueError(f"{what}: out must be {n} contiguous {dtype} on {dev}, got {tuple(out.shape)} {out.dtype} on {out.device}: the "
-                         "extents differ from those the buffers were made for")
-    return out
-
-
-def _workspace(workspace, nbytes, dev, what):
-    if workspace is None:
-        workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < nbytes:
-        raise ValueError(f"{what}: workspace of {workspace.numel() * workspace.element_size()} bytes on {workspace.device}, {nbytes} needed on {dev}")
-    return workspace
-
-
 def _enqueue_normalize(scan, settings, out, block, workspace):
     """`normalize_scan` on an uploaded scan -> (the normalised DeviceVolume, the result block, the workspace)."""
     from .data import ingest
     dev = scan.data.device
     x, y, z = scan.shape
-    nbytes = _bytes_or_raise("mmnn_normalize_scan_workspace_bytes", x, y, z)
-    out = _device_buffer(out, x * y * z, dev, "normalize_scan")
-    block = _device_buffer(block, _lib.NORMALIZE_RESULT_BYTES, dev, "normalize_scan (result block)", torch.uint8)
-    workspace = _workspace(workspace, nbytes, dev, "normalize_scan")
+    out = _lib.device_buffer(out, x * y * z, torch.float32, dev, "normalize_scan")
+    block = _lib.device_buffer(block, _lib.NORMALIZE_RESULT_BYTES, torch.uint8, dev, "normalize_scan (result block)")
+    workspace = _lib.workspace(workspace, _lib.count("mmnn_normalize_scan_workspace_bytes", x, y, z), dev, "normalize_scan")
     desc = _lib.NormalizeDesc(x, y, z, scan.datatype, float(scan.slope), float(scan.inter), settings[0], settings[1])
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_normalize_scan(ctypes.byref(desc), scan.data.data_ptr(), out.data_ptr(), block.data_ptr(), workspace.data_ptr(),
-                                                  stream), "mmnn_normalize_scan")
+    _lib.enqueue("mmnn_normalize_scan", ctypes.byref(desc), scan.data.data_ptr(), out.data_ptr(), block.data_ptr(), workspace.data_ptr(), device=dev)
     return ingest.DeviceVolume(out.view(torch.uint8), (x, y, z), 16, 0.0, 0.0, scan.affine), block, workspace
 
 
 def resample_workspace_bytes(shape, out_shape) -> int:
-    return _bytes_or_raise("mmnn_resample_pair_workspace_bytes", *shape, *out_shape)
+    return _lib.count("mmnn_resample_pair_workspace_bytes", *(int(v) for v in (*shape, *out_shape)))
 
 
 def resample_pair(scan, mask, device, spacing, index_map=None, threshold: Optional[float] = None, out: Optional[torch.Tensor] = None,
@@ -537,19 +495,16 @@ def _enqueue_resample(scan, mask, grid, out, out_mask, tables, workspace):
     dev = scan.data.device
     (x, y, z), (mx, my, mz) = scan.shape, grid.shape
     host = resample_tables(scan.shape, grid)
-    nbytes = resample_workspace_bytes(scan.shape, grid.shape)
-    out = _device_buffer(out, mx * my * mz, dev, "resample_pair")
-    out_mask = _device_buffer(out_mask, mx * my * mz, dev, "resample_pair (mask)", torch.uint8)
-    tables = _device_buffer(tables, host.nbytes, dev, "resample_pair (tables)", torch.uint8)
-    workspace = _workspace(workspace, nbytes, dev, "resample_pair")
+    out = _lib.device_buffer(out, mx * my * mz, torch.float32, dev, "resample_pair")
+    out_mask = _lib.device_buffer(out_mask, mx * my * mz, torch.uint8, dev, "resample_pair (mask)")
+    tables = _lib.device_buffer(tables, host.nbytes, torch.uint8, dev, "resample_pair (tables)")
+    workspace = _lib.workspace(workspace, resample_workspace_bytes(scan.shape, grid.shape), dev, "resample_pair")
     tables.copy_(torch.from_numpy(host.view(np.uint8)))
     k = resample_constants()
     desc = _lib.ResampleDesc(x, y, z, mx, my, mz, scan.datatype, mask.datatype, float(scan.slope), float(scan.inter), float(mask.slope),
                              float(mask.inter), k["pole"], k["pole_gain"], k["gain"], (ctypes.c_double * _lib.RESAMPLE_HORIZON)(*k["pole_power"].tolist()))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mmnn_resample_pair(ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), host.ctypes.data, tables.data_ptr(),
-                                                 out.data_ptr(), out_mask.data_ptr(), workspace.data_ptr(), stream), "mmnn_resample_pair")
+    _lib.enqueue("mmnn_resample_pair", ctypes.byref(desc), scan.data.data_ptr(), mask.data.data_ptr(), host.ctypes.data, tables.data_ptr(),
+                 out.data_ptr(), out_mask.data_ptr(), workspace.data_ptr(), device=dev)
     return (ingest.DeviceVolume(out.view(torch.uint8), grid.shape, 16, 0.0, 0.0, grid.affine),
             ingest.DeviceVolume(out_mask, grid.shape, 2, 1.0, 0.0, grid.affine), tables, workspace)
 
@@ -569,7 +524,7 @@ def _pre_steps(scan, mask, norm, spacing, buffers):
     if buffers is not None:
         ws = buffers.pre_workspace
     else:
-        need = max(_bytes_or_raise("mmnn_normalize_scan_workspace_bytes", *scan.shape) if norm else 0,
+        need = max(_lib.count("mmnn_normalize_scan_workspace_bytes", *scan.shape) if norm else 0,
                    resample_workspace_bytes(scan.shape, grid.shape) if grid is not None else 0)
         ws = torch.empty(need, dtype=torch.uint8, device=scan.data.device) if need else None
     rec["pre_workspace"] = ws
@@ -633,31 +588,35 @@ def _extract_image(scan, mask, bin_width, max_bins, buffers, classes, glszm, mes
     desc = _lib.RadiomicsDesc(x, y, z, scan.datatype, mask.datatype, float(scan.slope), float(scan.inter), float(mask.slope), float(mask.inter),
                               float(bin_width), max_bins)
     out = RadiomicsResult(None, None, None, None, (x, y, z), scan.affine, float(bin_width), max_bins)
-    with torch.cuda.device(scan.data.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        for st, on in zip(STAGES, (True, classes, glszm, mesh)):
-            if on:
-                _enqueue_stage(out, st, desc, stream, buffers, scan.data, mask.data)
-                if st.flag is not None:
-                    setattr(out, st.flag, classes if st.flag == "classes" else True)
+    for st, on in zip(STAGES, (True, classes, glszm, mesh)):
+        if on:
+            _enqueue_stage(out, st, desc, buffers, scan.data, mask.data)
+            if st.flag is not None:
+                setattr(out, st.flag, classes if st.flag == "classes" else True)
     return out
 
 
-def _enqueue_stage(out: RadiomicsResult, st, desc, stream, buffers, scan, mask) -> None:
+def _enqueue_stage(out: RadiomicsResult, st, desc, buffers, scan, mask) -> None:
     """Give `out` the buffers of stage `st`, those of `buffers` when it has them and new ones otherwise, and enqueue the stage."""
     if buffers is not None and getattr(buffers, st.block) is not None:
         for a in st.attrs:
             setattr(out, a, getattr(buffers, a))
     else:
         (x, y, z), dev = out.shape, scan.device
-        nbytes = _bytes_or_raise(st.symbol + "_workspace_bytes", x, y, z, out.max_bins)
+        nbytes = _lib.count(st.symbol + "_workspace_bytes", x, y, z, out.max_bins)
         setattr(out, st.block, torch.empty(st.nbytes, dtype=torch.uint8, device=dev))
         for a, shape, dtype in st.tables:
             setattr(out, a, torch.empty(shape(x, y, z, out.max_bins), dtype=dtype, device=dev))
         setattr(out, st.workspace, torch.empty(nbytes, dtype=torch.uint8, device=dev))
     if st.name == "mesh":
         out.linear = _linear_of(out.affine)
-    enqueue(out, st.name, desc, stream, scan.data_ptr(), mask.data_ptr())
+    _lib.enqueue(st.symbol, *_stage_args(out, st, desc, scan.data_ptr(), mask.data_ptr()), device=scan.device)
+
+
+def _stage_args(r: RadiomicsResult, st, desc, scan, mask) -> tuple:
+    """The arguments of stage `st`'s call ahead of its stream."""
+    lead = (scan, mask) if st.flag is None else (r.block.data_ptr(), r.workspace.data_ptr()) + st.extra(r)
+    return (ctypes.byref(desc), *lead, *(getattr(r, a).data_ptr() for a in st.attrs))
 
 
 def enqueue(r: RadiomicsResult, stage: str, desc, stream, scan: Optional[int] = None, mask: Optional[int] = None) -> None:
@@ -665,8 +624,7 @@ def enqueue(r: RadiomicsResult, stage: str, desc, stream, scan: Optional[int] = 
     descriptor `desc` on `stream` (the current device's): nothing is prepared or allocated.  `scan` / `mask`: the device addresses the
     first call reads; the follow-on calls read `r.block` and `r.workspace`, the mesh one `r.linear` too."""
     st = _STAGE[stage]
-    lead = (scan, mask) if st.flag is None else (r.block.data_ptr(), r.workspace.data_ptr()) + st.extra(r)
-    _lib.check(getattr(_lib.lib(), st.symbol)(ctypes.byref(desc), *lead, *(getattr(r, a).data_ptr() for a in st.attrs), stream), st.symbol)
+    _lib.call(st.symbol, *_stage_args(r, st, desc, scan, mask), stream)
 
 
 def _linear_of(affine) -> np.ndarray:
@@ -678,7 +636,7 @@ def mesh_table() -> dict:
     """The triangle table the library was built with (host only, no device): `tri` (256, 16) int8, `l48` (256,), `nsum` (256, 3) int32."""
     tri = np.zeros((_lib.RADIOMICS_MESH_CONFIGS, _lib.RADIOMICS_MESH_TRI_ROW), dtype=np.int8)
     l48, nsum = np.zeros(_lib.RADIOMICS_MESH_CONFIGS, dtype=np.int32), np.zeros((_lib.RADIOMICS_MESH_CONFIGS, 3), dtype=np.int32)
-    _lib.check(_lib.lib().mmnn_radiomics_mesh_table(tri.ctypes.data, l48.ctypes.data, nsum.ctypes.data), "mmnn_radiomics_mesh_table")
+    _lib.call("mmnn_radiomics_mesh_table", tri.ctypes.data, l48.ctypes.data, nsum.ctypes.data)
     return {"tri": tri, "l48": l48, "nsum": nsum}
 
 

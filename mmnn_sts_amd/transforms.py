@@ -372,18 +372,12 @@ class Compose:
         recs = (_lib.TransformParams * n)()
         for i, p in enumerate(params):
             self._pack(p, (d, h, w), recs[i])
-        L = _lib.lib()
-        nbytes = L.mmnn_transform_workspace_bytes(ctypes.byref(desc))
-        if nbytes < 0:
-            raise ValueError("mmnn_transform_workspace_bytes: " + _lib.last_error())
+        nbytes = _lib.count("mmnn_transform_workspace_bytes", ctypes.byref(desc))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
         if os.environ.get("MMNN_POISON_WS") == "1":   # debugging aid: NaN-fill so reads of unwritten workspace words surface
             ws.fill_(255)
         out = torch.empty((n, c, od, oh, ow), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(L.mmnn_transform_volumes(ctypes.byref(desc), recs, x.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, stream),
-                       "transform_volumes")
+        _lib.enqueue("mmnn_transform_volumes", ctypes.byref(desc), recs, x.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, device=x.device)
         return out[0] if single else out
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:

@@ -118,11 +118,9 @@ class LRFinder:
         lrs = lr_schedule(base_lr, end_lr, num_iter, step_mode)
         self.history = {"lr": [], "loss": []}
         dev = self.device
-        L = _lib.lib()
-        st = torch.cuda.current_stream(dev).cuda_stream
         table = torch.tensor(lrs, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)   # rounded to fp32 once, as ctypes does
-        state = torch.empty((L.mmnn_lr_range_state_bytes(num_iter),), dtype=torch.uint8, device=dev)
-        _lib.check(L.mmnn_lr_range_init(state.data_ptr(), num_iter, st), "lr_range_init")
+        state = torch.empty((_lib.lib().mmnn_lr_range_state_bytes(num_iter),), dtype=torch.uint8, device=dev)
+        _lib.enqueue("mmnn_lr_range_init", state.data_ptr(), num_iter, device=dev)
         live = state[_lib.LRS_LIVE:_lib.LRS_LIVE + 4].view(torch.int32)
         n_polls = num_iter // poll_every + 1
         words = torch.ones((n_polls,), dtype=torch.int32).pin_memory()
@@ -169,9 +167,9 @@ class LRFinder:
                 if accumulation_steps > 1:
                     loss = loss / accumulation_steps
                 loss.backward()
-                _lib.check(L.mmnn_lr_range_accumulate(state.data_ptr(), loss.detach().data_ptr(), 1.0, int(a == 0), st), "lr_range_accumulate")
+                _lib.enqueue("mmnn_lr_range_accumulate", state.data_ptr(), loss.detach().data_ptr(), 1.0, int(a == 0), device=dev)
             self.optimizer.step_device_lr(table[i:i + 1], live)
-            _lib.check(L.mmnn_lr_range_update(state.data_ptr(), i, float(smooth_f), float(one_minus), float(diverge_th), st), "lr_range_update")
+            _lib.enqueue("mmnn_lr_range_update", state.data_ptr(), i, float(smooth_f), float(one_minus), float(diverge_th), device=dev)
             i += 1
             if i % poll_every == 0:
                 slot = i // poll_every

@@ -111,9 +111,8 @@ class MultiModalGradCAM(nn.Module):
             for t in (h, wfeat, whead, n5.weight, n5.running_var):
                 if not (t.is_contiguous() and t.dtype == torch.float32):
                     raise RuntimeError("MultiModalGradCAM expects contiguous float32 model tensors")
-            _lib.check(L.mmnn_gradcam(ctypes.byref(desc), h.data_ptr(), act_in, whead.data_ptr(), wfeat.data_ptr(), n5.weight.data_ptr(),
-                                      n5.running_var.data_ptr(), act.data_ptr(), grads.data_ptr(), heat.data_ptr(), maps.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream), "gradcam")
+            _lib.enqueue("mmnn_gradcam", ctypes.byref(desc), h.data_ptr(), act_in, whead.data_ptr(), wfeat.data_ptr(), n5.weight.data_ptr(),
+                         n5.running_var.data_ptr(), act.data_ptr(), grads.data_ptr(), heat.data_ptr(), maps.data_ptr())
             assert heat.ndim == 4, 'Batch dimension found in attention map - Must use batch size 1 when computing attention maps'
             att_maps = list(maps.unbind(0))
             self.features, self.grads, self.heat = act, grads, heat
@@ -237,17 +236,15 @@ class GradCAM(nn.Module):
         D, H, W = (int(t) for t in extent)
         dev = act.device
         desc = _lib.GradcamUnimodalDesc(n, c, sp[0], sp[1], sp[2], D, H, W, outputs.shape[1], self._label_code(), act_ns, mask_ns)
-        L = _lib.lib()
-        ws_bytes = L.mmnn_gradcam_unimodal_workspace_bytes(ctypes.byref(desc))
+        ws_bytes = _lib.lib().mmnn_gradcam_unimodal_workspace_bytes(ctypes.byref(desc))
         if ws_bytes < 0:
             raise ValueError(f"GradCAM: bad captured layer {tuple(act.shape)}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         grads = torch.empty((n, c) + sp, device=dev, dtype=torch.float32)
         heat = torch.empty((n, 1) + sp, device=dev, dtype=torch.float32)
         maps = torch.empty((n, 1, D, H, W), device=dev, dtype=torch.float32)
-        _lib.check(L.mmnn_gradcam_unimodal(ctypes.byref(desc), ctypes.byref(head), act.data_ptr(), mask.data_ptr(), grads.data_ptr(),
-                                           heat.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws_bytes,
-                                           torch.cuda.current_stream().cuda_stream), "gradcam_unimodal")
+        _lib.enqueue("mmnn_gradcam_unimodal", ctypes.byref(desc), ctypes.byref(head), act.data_ptr(), mask.data_ptr(), grads.data_ptr(),
+                     heat.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws_bytes)
         self.features, self.grads, self.heat = act, grads, heat
         return maps
 
@@ -346,12 +343,10 @@ class OcclusionSensitivity(nn.Module):
         m.eval()
         try:
             with torch.no_grad():
-                L = _lib.lib()
-                stream = torch.cuda.current_stream().cuda_stream
                 dev = image.device
                 c, (d, h, w) = int(image.shape[1]), (int(t) for t in image.shape[2:])
                 desc = _lib.OcclusionDesc(c, d, h, w, (ctypes.c_int32 * 3)(*self.window), (ctypes.c_int32 * 3)(*self.stride))
-                wn = L.mmnn_occlusion_window_count(ctypes.byref(desc), None)
+                wn = _lib.lib().mmnn_occlusion_window_count(ctypes.byref(desc), None)
                 if wn < 0:
                     raise ValueError(f"OcclusionSensitivity: {_lib.last_error()}")
                 outputs = m(dict(x, image=image) if self.multimodal else image)
@@ -364,21 +359,19 @@ class OcclusionSensitivity(nn.Module):
                 if self.fill == "mean":
                     fill = torch.empty(c, device=dev, dtype=torch.float32)
                     ws = torch.empty(c * _lib.CHANNEL_MEANS_PARTS, device=dev, dtype=torch.float64)
-                    _lib.check(L.mmnn_channel_means(image.data_ptr(), c, d * h * w, fill.data_ptr(), ws.data_ptr(), stream), "channel_means")
+                    _lib.enqueue("mmnn_channel_means", image.data_ptr(), c, d * h * w, fill.data_ptr(), ws.data_ptr())
                 else:
                     fill = torch.full((c,), self.fill, device=dev, dtype=torch.float32)
                 scores = torch.empty((wn, k), device=dev, dtype=torch.float32)
                 occluded = torch.empty((self.batch, c, d, h, w), device=dev, dtype=torch.float32)
                 clinical = x["clinical"].expand(self.batch, -1).contiguous() if self.multimodal else None
                 for first in range(0, wn, self.batch):
-                    _lib.check(L.mmnn_occlude_windows(ctypes.byref(desc), image.data_ptr(), fill.data_ptr(), first, self.batch,
-                                                      occluded.data_ptr(), stream), "occlude_windows")
+                    _lib.enqueue("mmnn_occlude_windows", ctypes.byref(desc), image.data_ptr(), fill.data_ptr(), first, self.batch, occluded.data_ptr())
                     out = m({"image": occluded, "clinical": clinical} if self.multimodal else occluded)
                     rows = min(self.batch, wn - first)                  # the padded tail of the last batch repeats the last window
                     scores[first:first + rows].copy_(out[:rows])
                 maps = torch.empty((k, d, h, w), device=dev, dtype=torch.float32)
-                _lib.check(L.mmnn_occlusion_map(ctypes.byref(desc), k, base.data_ptr(), scores.data_ptr(), maps.data_ptr(), stream),
-                           "occlusion_map")
+                _lib.enqueue("mmnn_occlusion_map", ctypes.byref(desc), k, base.data_ptr(), scores.data_ptr(), maps.data_ptr())
                 self.scores = scores
         finally:
             for mod, mode in modes:

@@ -35,6 +35,98 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.mmnn_version() >= 100
 
 
+_C_SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+              "double": ctypes.c_double}
+
+
+def _is_pointer(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def _parse_header():
+    """include/mmnn_sts.h -> ({MMNN_X: int}, {struct: [(field, C type or 'pointer', [array lengths])]}, {function: (return type, [parameter])}),
+    a parameter being a C scalar type or 'pointer' (`T*`, `T name[3]`)."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mmnn_sts.h")).read(), flags=re.S)
+    macros = {}
+    for name, value in re.findall(r"^#define\s+(MMNN_\w+)[ \t]+(\S.*?)\s*$", hdr, flags=re.M):
+        m = re.fullmatch(r"\(?\s*(-?\d+)(?:\s*<<\s*(\d+))?\s*\)?", value)
+        if m:
+            macros[name] = int(m.group(1)) << int(m.group(2) or 0)
+    structs = {}
+    for body, name in re.findall(r"typedef struct \{(.*?)\}\s*(mmnn_\w+);", hdr, flags=re.S):
+        fields = structs[name] = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            ctype, first = re.fullmatch(r"(?:const\s+)?(\w+\s*\*?)\s*(\w.*)", decl, flags=re.S).groups()
+            for item in (first.split(",")):
+                field, dims = re.fullmatch(r"\s*(\w+)((?:\[\w+\])*)\s*", item).groups()
+                lengths = [int(d) if d.isdigit() else macros[d] for d in re.findall(r"\[(\w+)\]", dims)]
+                fields.append((field, "pointer" if "*" in ctype else ctype.strip(), lengths))
+    protos = {}
+    rest = re.sub(r"^#.*$", "", re.sub(r"typedef struct \{.*?\}\s*mmnn_\w+;", "", hdr, flags=re.S), flags=re.M)
+    for ret, name, params in re.findall(r"([\w \t\*]+?)\s*\b(mmnn_\w+)\s*\(([^)]*)\)\s*;", rest):
+        params = [] if params.strip() == "void" else [
+            "pointer" if ("*" in p or "[" in p) else [w for w in p.split() if w != "const"][0] for p in params.split(",")]
+        protos[name] = (" ".join(ret.replace("const", "").split()), params)
+    return macros, structs, protos
+
+
+def test_binding_agrees_with_the_header(lib):
+    """Every prototype, every mirrored struct and every mirrored constant of include/mmnn_sts.h against mmnn_sts_amd/_lib.py."""
+    from mmnn_sts_amd import _lib
+    macros, structs, protos = _parse_header()
+    returns = {"int": ctypes.c_int32, "int64_t": ctypes.c_int64, "void": None, "void*": ctypes.c_void_p, "char*": ctypes.c_char_p}
+    for name, (ret, params) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.restype is returns[ret.replace(" *", "*")], f"{name}: returns {ret}, bound as {fn.restype}"
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), f"{name}: {len(params)} parameters, bound {fn.argtypes}"
+        for i, (want, got) in enumerate(zip(params, fn.argtypes)):
+            assert _is_pointer(got) if want == "pointer" else got is _C_SCALARS[want], f"{name}: parameter {i} is {want}, bound as {got}"
+    assert len(protos) >= 87
+
+    classes = {k.lower(): v for k, v in vars(_lib).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    checked = 0
+    for name, fields in structs.items():
+        cls = classes.get(name[len("mmnn_"):].replace("_", ""))
+        if cls is None:
+            continue
+        mirrored = []
+        for field, t in cls._fields_:
+            lengths = []
+            while issubclass(t, ctypes.Array):
+                lengths.append(t._length_)
+                t = t._type_
+            mirrored.append((field, "pointer" if _is_pointer(t) else next(k for k, v in _C_SCALARS.items() if v is t and k != "int"), lengths))
+        assert mirrored == fields, f"{name} / {cls.__name__}: {mirrored} != {fields}"
+        checked += 1
+    assert checked >= 22 and checked == len(classes), (checked, sorted(classes))
+
+    same = {k: v for k, v in macros.items() if hasattr(_lib, k[len("MMNN_"):])}
+    for k, v in same.items():
+        assert getattr(_lib, k[len("MMNN_"):]) == v, f"{k} is {v}, _lib has {getattr(_lib, k[len('MMNN_'):])}"
+    assert len(same) >= 25, sorted(same)
+    for const, struct in (("RADIOMICS_RESULT_BYTES", "mmnn_radiomics_result"), ("RADIOMICS_TEXTURE_BYTES", "mmnn_radiomics_texture_result"),
+                          ("RADIOMICS_ZONES_BYTES", "mmnn_radiomics_zones_result"), ("RADIOMICS_MESH_BYTES", "mmnn_radiomics_mesh_result"),
+                          ("NORMALIZE_RESULT_BYTES", "mmnn_normalize_result")):
+        assert all(t in ("int64_t", "uint64_t", "double") for _, t, _ in structs[struct]), struct
+        assert getattr(_lib, const) == 8 * sum(int(np.prod(lengths)) for _, _, lengths in structs[struct]), const
+
+
+def test_buffer_helpers_check_or_allocate():
+    from mmnn_sts_amd import _lib
+    cpu, meta = torch.device("cpu"), torch.device("meta")
+    good = torch.zeros((2, 3))
+    assert _lib.device_buffer(good, 6, torch.float32, cpu, "who") is good and _lib.device_buffer(good, (2, 3), torch.float32, cpu, "who") is good
+    made = _lib.device_buffer(None, (2, 3), torch.int32, cpu, "who")
+    assert tuple(made.shape) == (2, 3) and made.dtype == torch.int32 and _lib.device_buffer(None, 5, torch.uint8, cpu, "who").shape == (5,)
+    for t, need, device in ((good, 5, cpu), (good, (3, 2), cpu), (good.double(), 6, cpu), (torch.zeros((2, 6))[:, ::2], 6, cpu), (good, 6, meta)):
+        with pytest.raises(ValueError, match=r"who: out must be .* contiguous torch.float32 on .*, got \(2, 3\) torch.float"):
+            _lib.device_buffer(t, need, torch.float32, device, "who")
+    assert _lib.workspace(good, 24, cpu, "who") is good and _lib.workspace(None, 7, cpu, "who").shape == (7,)
+    for t, device in ((good, meta), (torch.zeros((2, 6))[:, ::2], cpu), (torch.zeros(5), cpu)):
+        with pytest.raises(ValueError, match=r"who: workspace of \d+ bytes on cpu.*, 24 needed on"):
+            _lib.workspace(t, 24, device, "who")
+
+
 def test_plan_queries_without_gpu(lib):
     from mmnn_sts_amd import _lib
     cfg = _lib.DenseNetConfig(2, 64, 32, 4, 4, (ctypes.c_int32 * 8)(6, 12, 24, 16, 0, 0, 0, 0), 1e-5, 0.1, 0.2)
