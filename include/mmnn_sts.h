@@ -546,6 +546,18 @@ typedef struct {
 int mmnn_unpack_frames(const mmnn_unpack_frames_desc* d, const uint8_t* bits, const int32_t* refs, const int32_t* slice_first, uint8_t* out,
                        void* stream);
 
+/* ---- row gather: a batch assembled from a table of rows that stays on the device (csrc/gather.hip) -- the ingested planes and kept
+ * extents of the patients that the volume cache holds (mmnn_sts_amd/data/cache.py).
+ * out row i = table row slots[i], i < n, copied as bit patterns (NaN payloads and -0.0 survive).  table: n_rows rows of row_bytes
+ * bytes on the device; slots: n int32 ON THE HOST, read and checked before the launch and passed to the kernel by value; out:
+ * n * row_bytes bytes on the device.  Every byte of out is written and nothing else is.  One launch, no atomics, no host
+ * synchronisation.  All byte offsets are 64-bit: n_rows * row_bytes may exceed 2^32.  16-byte loads and stores when row_bytes % 16 == 0
+ * and table and out are aligned to 16 bytes, dwords otherwise.  The same slot may appear several times.
+ * Refused (status 1, mmnn_last_error names the argument) before any launch: a null pointer, n_rows < 1, row_bytes < 4 or not a multiple
+ * of 4, n outside 1..MMNN_GATHER_MAX_ROWS, a slot outside 0..n_rows-1, table or out not aligned to 4 bytes, out overlapping the table. */
+#define MMNN_GATHER_MAX_ROWS 256
+int mmnn_gather_rows(const void* table, int64_t n_rows, int64_t row_bytes, const int32_t* slots, int32_t n, void* out, void* stream);
+
 /* ---- occlusion sensitivity: blank a box of the input, run the model, record how far each output moved; slide the box over the volume
  * and average the moves over the boxes that cover a voxel (csrc/occlusion.hip).  The library builds the occluded batches and assembles
  * the map; the forwards in between are the caller's.

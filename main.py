@@ -21,7 +21,9 @@ S^3 on the device, DICOM slices are decoded there first (mmnn_sts_amd/data/inges
 stay outside the path.  S is 64, upstream's Resize target, unless `--image_size S` (or the config's `Data: size: S`; the flag goes before
 it) names another extent in 1..128 that the model admits: the ingest, the `--transforms` Resize, the attention and occlusion maps and
 their exports then all work at S^3, and without `--image_loc` the synthetic patients are S^3 too.  End to end this is covered at 64 and
-at 128 only.  `--inference --image_loc DIR --scan_space` also writes every class's
+at 128 only.  `--cache_volumes` (`Data: cache: true`; budget `--cache_gb`, 16) ingests each patient once, keeps its S^3 planes on the device
+and assembles every later batch there, so no file is opened after the first epoch (mmnn_sts_amd/data/cache.py); patients beyond the
+budget are read every epoch.  `--inference --image_loc DIR --scan_space` also writes every class's
 attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).
 `--inference --images --occlusion` writes occlusion sensitivity maps (patient{i}_occ_map.npy: (K, D, H, W) signed deltas at the resolution of
 `--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
@@ -256,9 +258,57 @@ def nifti_datasets(parser, args, device, seed, rank, world):
     train_uids, val_uids = split_uids(full.uids, args, seed)
     if getattr(args, "radiomics", False):
         scale_radiomics(parser, args, train_uids, rank)
-    args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False),
-                                        size=getattr(args, "image_size", None) or SIZE)
-    return ImageDatasetByUIDs(full, train_uids[rank::world]), ImageDatasetByUIDs(full, val_uids)
+    size = getattr(args, "image_size", None) or SIZE
+    by_uids, cached = ImageDatasetByUIDs, {}
+    if getattr(args, "cache_volumes", False):
+        # one cache per process: this rank's training shard and the validation set, which every rank evaluates
+        from mmnn_sts_amd.data.cache import CachedByUIDs, VolumeCache, capacity_for
+        channels = int(parser.config["ImageModel"]["in_channels"])
+        args.cache_patients = len(set(train_uids[rank::world]) | set(val_uids))
+        args.volume_cache = VolumeCache(device, channels, size, capacity_for(int(args.cache_gb * 2 ** 30), channels, size, args.cache_patients))
+        by_uids = lambda dataset, uids: CachedByUIDs(dataset, uids, args.volume_cache)
+        cached = {"cache": args.volume_cache}
+        if rank == 0:
+            logger.info("volume cache: room for %d of %d patients (%d x %d^3 fp32 each) in %g GB", args.volume_cache.capacity, args.cache_patients,
+                        channels, size, args.cache_gb)
+    args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False), size=size, **cached)
+    return by_uids(full, train_uids[rank::world]), by_uids(full, val_uids)
+
+
+def check_cache_flags(a, data_cfg, use_nifti):
+    """`--cache_volumes` / `Data: cache` and `--cache_gb` / `Data: cache_gb`: sets a.cache_volumes and a.cache_gb (16 when not named)."""
+    a.cache_volumes = a.cache_volumes or bool(data_cfg.get("cache"))
+    gb = a.cache_gb if a.cache_gb is not None else data_cfg.get("cache_gb")
+    if gb is not None and not a.cache_volumes:
+        raise SystemExit("--cache_gb is the budget of the volume cache: it needs --cache_volumes")
+    if not a.cache_volumes:
+        return
+    if not use_nifti:
+        raise SystemExit("--cache_volumes keeps the ingested scans of patient directories on the device: it needs --image_loc")
+    if a.inference:
+        raise SystemExit("--cache_volumes saves the re-reading of patients in later epochs: --inference reads each patient once, run it without")
+    if a.lr_finder:
+        raise SystemExit("--cache_volumes caches ingested patient scans: --lr_finder runs on synthetic patients, run it without")
+    gb = DEFAULT_CACHE_GB if gb is None else gb
+    if isinstance(gb, bool) or not isinstance(gb, (int, float)) or not 0 < gb < float("inf"):
+        raise SystemExit(f"--cache_gb {gb!r} is not a positive number of GB")
+    a.cache_gb = float(gb)
+
+
+DEFAULT_CACHE_GB = 16.0                      # a setting, not a measurement: about a twentieth of the card's 288 GB
+
+
+def log_volume_cache(args, rank):
+    """`--cache_volumes`: one line per epoch -- what the cache holds, what it served in this epoch, and the files the datasets read in it."""
+    cache = getattr(args, "volume_cache", None)
+    if cache is None:
+        return
+    from mmnn_sts_amd.data.ImageDatasets import ImageDataset
+    hits, misses, overflow = cache.table.take_counters()
+    files, ImageDataset.files_read = ImageDataset.files_read, 0
+    if rank == 0:
+        logger.info("volume cache: %d of %d patients cached, %.1f MB held; this epoch: %d hits, %d misses, %d overflow, %d files read",
+                    cache.table.n_filled, args.cache_patients, cache.bytes_held / 1e6, hits, misses, overflow, files)
 
 
 def check_radiomics_flags(a, data_cfg):
@@ -458,6 +508,7 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
                 torch.save(model.state_dict(), os.path.join(args.output_path, 'best_surv_model.pth'))
                 logger.info('saved new best metric model')
         report_empty_masks(args)
+        log_volume_cache(args, rank)
         if args.blend and blender_update_due(epoch, args.blend_update_interval):
             # every rank evaluates the same epoch-level losses: its own training patients are gathered from all ranks (the
             # validation set is identical on every rank), so one global weight vector results, as on a single GPU
@@ -541,6 +592,7 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
             logger.info(f"epoch {epoch + 1}/{args.epochs} average loss: {float(epoch_loss) / len(train_ds):.4f} train f1 {train_f1:.4f} "
                         f"validation loss {test_loss / len(val_ds):.4f} current f1: {mean_f1:.4f} best f1: {best_metric:.4f} at epoch: {best_epoch}")
         report_empty_masks(args)
+        log_volume_cache(args, rank)
         if args.blend and blender_update_due(epoch, args.blend_update_interval):
             # as in the survival loop: the training patients of all ranks (the validation set is the same everywhere) -> one weight vector
             blender.updateWeights(gather_rows(torch.cat(train_preds, dim=1), 1, world), gather_rows(torch.cat(train_gt).float(), 0, world),
@@ -668,6 +720,11 @@ def build_arg_parser():
                     help="extent S per axis, 1..128, of the volumes the model sees (default 64; overrides the config's `Data: size`): "
                          "with --image_loc the scans are ingested at S^3, without it the synthetic patients are S^3; --transforms resizes "
                          "to S^3 and the attention / occlusion maps and their exports are S^3")
+    ap.add_argument("--cache_volumes", action="store_true",
+                    help="with --image_loc: ingest each patient once and keep its S^3 planes on the device; later epochs assemble their "
+                         "batches there and open no file (also `Data: cache: true`).  Patients beyond --cache_gb are read every epoch")
+    ap.add_argument("--cache_gb", type=float, default=None,
+                    help="budget of --cache_volumes in GB (default 16; overrides the config's `Data: cache_gb`): 2 MB per patient at 2 x 64^3")
     ap.add_argument("--scan_space", action="store_true",
                     help="with --inference --image_loc and Grad-CAM on: also write every class's attention map on each scan's own voxel "
                          "grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz)")
@@ -732,6 +789,7 @@ def main(argv=None):
         check_radiomics_flags(a, data_cfg)
     # (--radiomics without --images reads --image_loc only to extract its features from)
     use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images) and (a.images or not a.radiomics)
+    check_cache_flags(a, data_cfg, use_nifti)
     if use_nifti:
         if not a.images:
             raise SystemExit("--image_loc points at NIfTI patient directories: it needs --images")

@@ -134,6 +134,7 @@ class UnpackFramesDesc(Structure):
     _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("n_frames", c_int32), ("n_refs", c_int32), ("one", c_int32)]
 
 
+GATHER_MAX_ROWS = 256                        # MMNN_GATHER_MAX_ROWS
 OCCLUSION_MAX_OUTPUTS = 16                   # MMNN_OCCLUSION_MAX_OUTPUTS
 CHANNEL_MEANS_PARTS = 64                     # MMNN_CHANNEL_MEANS_PARTS
 
@@ -250,6 +251,7 @@ def _signatures():
         "mmnn_decode_slices": [P(DecodeSlicesDesc), V, V, V, V],
         "mmnn_rasterize_contours": [P(RasterizeDesc), V, V, V, V, V],
         "mmnn_unpack_frames": [P(UnpackFramesDesc), V, V, V, V, V],
+        "mmnn_gather_rows": [V, Q, Q, P(I), I, V, V],
         "mmnn_occlude_windows": [P(OcclusionDesc), V, V, I, I, V, V],
         "mmnn_occlusion_map": [P(OcclusionDesc), I, V, V, V, V],
         "mmnn_channel_means": [V, I, Q, V, V, V],

@@ -123,11 +123,17 @@ def seg_in(mask_directory):
     return path if kind == 'seg' else None
 
 
+def _n_files(volume):
+    """The files a read volume came from: one per slice of a DICOM series, one NIfTI file."""
+    return len(volume.frames) if isinstance(volume, dicom.DicomSeries) else 1
+
+
 READERS = {'rtstruct': rtstruct, 'seg': seg}         # the kinds of `mask_source` that are one file, placed against the scan
 
 
 class ImageDataset(torch.utils.data.Dataset):
     format = 'auto'             # the layout a class is bound to; the constructor's `format` overrides it
+    files_read = 0              # files that `_load` has read in this process, over all datasets (`--cache_volumes` logs and resets it per epoch)
 
     def __init__(self, patient_directory, patient_key, mask_resample='auto', log_grids=True, format=None, mask_roi=None):
         if mask_resample not in MASK_RESAMPLE_MODES:
@@ -230,8 +236,11 @@ class ImageDataset(torch.utils.data.Dataset):
         if kind in READERS:
             # the collate function places the frames of a SEG mask against the scan and unpacks them on the device; contours are born
             # on the scan's grid and rasterised there (no resample, no threshold)
-            return read(scan_path), READERS[kind].select(READERS[kind].read(file), self.mask_roi)
+            scan = read(scan_path)
+            ImageDataset.files_read += _n_files(scan) + 1
+            return scan, READERS[kind].select(READERS[kind].read(file), self.mask_roi)
         scan, mask = read(scan_path), read(mask_path)
+        ImageDataset.files_read += _n_files(scan) + _n_files(mask)
         self._check_grids(patient, (scan.shape, scan.affine, scan_path), (mask.shape, mask.affine, mask_path))
         return scan, mask
 

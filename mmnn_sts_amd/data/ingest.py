@@ -14,7 +14,9 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     prepare_pair(scan, mask, device)                upload, rasterise / unpack / resample the mask: the pair on one grid, on the device
     ingest_volume(scan, mask, out_plane, extents)   one volume -> one S^3 channel plane, S = the plane's extent (the mask is resampled first when its grid differs)
     collate_volumes(patients, device, size=64)      [[(scan, mask) per modality] per patient] -> (N, C, S,S,S) fp32, (N, C, 3) int32
-    IngestCollate(device, size=64)                  the DataLoader collate_fn of the NIfTI datasets
+    ingest_patients(patients, device, into)         the uploads and launches of collate_volumes, into destinations the caller names
+    IngestCollate(device, size=64, cache=None)      the DataLoader collate_fn of the NIfTI datasets; `cache`: a VolumeCache (data/cache.py)
+                                                    that keeps every ingested patient on the device and assembles the batches from it
     maps_to_scan(maps, scan_shape, ingest_workspace)   the way back: S^3 model-space maps -> fp32 volumes on the scan's grid (mmnn_maps_to_scan_sized)
 
 The output extent S is 64 (`SIZE`, upstream's Resize target) unless a caller chooses another one in 1..128 (`MAX_SIZE`): `ingest_volume`
@@ -514,19 +516,27 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     if any(len(p) != c for p in patients):
         raise ValueError("ingest: patients of one batch differ in their number of modalities")
     device = torch.device(device)
-    up = [[(upload(s, device), stage_mask(s, m, device)) for s, m in p] for p in patients]
-    maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     batch = torch.empty((n, c, size, size, size), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)
+    kept = ingest_patients(patients, device, [(batch[i], extents[i]) for i in range(n)], mask_resample, mask_threshold, keep_workspaces)
+    return (batch, extents, kept) if keep_workspaces else (batch, extents)
+
+
+def ingest_patients(patients, device, into, mask_resample: str = "auto", mask_threshold: Optional[float] = None, keep_workspaces: bool = False):
+    """The uploads and launches of `collate_volumes` with the destinations named by the caller: into[n] = (planes (C, S, S, S) fp32,
+    extents (C, 3) int32), two contiguous device views that patient n is ingested into -- a row of a batch, or a row of the volume
+    cache (`mmnn_sts_amd.data.cache`).  Returns the `KeptVolume`s, volumes[n][c] (empty lists without `keep_workspaces`)."""
+    up = [[(upload(s, device), stage_mask(s, m, device)) for s, m in p] for p in patients]
+    maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     kept = []
-    for i in range(n):
+    for i, (planes, extents) in enumerate(into):
         kept.append([])
-        for j in range(c):
+        for j in range(len(up[i])):
             ws = torch.empty(workspace_bytes(*up[i][j][0].shape), dtype=torch.uint8, device=device) if keep_workspaces else None
-            ingest_volume(up[i][j][0], up[i][j][1], batch[i, j], extents[i, j], ws, index_map=maps[i][j], threshold=mask_threshold)
+            ingest_volume(up[i][j][0], up[i][j][1], planes[j], extents[j], ws, index_map=maps[i][j], threshold=mask_threshold)
             if keep_workspaces:
                 kept[i].append(KeptVolume(ws, up[i][j][0].shape, up[i][j][0].affine))
-    return (batch, extents, kept) if keep_workspaces else (batch, extents)
+    return kept
 
 
 class IngestCollate:
@@ -535,10 +545,15 @@ class IngestCollate:
     batch on `device`.  The extents of every batch are kept in `pending` until `take_empty()` reads them: call it where the epoch
     synchronises anyway, never per batch.  `mask_resample` / `mask_threshold`: the `Data:` keys of the same names (see `collate_volumes`).
     `keep_workspaces` (off: nothing is retained, as training wants it): `last_volumes[n][c]` holds the `KeptVolume` of every (patient,
-    modality) of the LAST batch, for `maps_to_scan`.  `size`: the extent S per axis of the planes, 1..128 (64)."""
+    modality) of the LAST batch, for `maps_to_scan`.  `size`: the extent S per axis of the planes, 1..128 (64).
+    `cache` (None: every patient is ingested into every batch it is in): a `VolumeCache` (`mmnn_sts_amd.data.cache`) of this device,
+    size and channel count.  A patient seen for the first time is then ingested straight into its row of the cache -- the same calls
+    with another destination -- and every batch is assembled from the cache's rows by `mmnn_gather_rows` on the same stream, so batch
+    and extents hold the bits they hold without a cache; an item whose image is a `CachedPatient` brings no voxels at all.  A patient
+    that found the cache full is ingested into its row of the batch, as without one."""
 
     def __init__(self, device, mask_resample: str = "auto", mask_threshold: Optional[float] = 0.5, keep_workspaces: bool = False,
-                 size: int = SIZE):
+                 size: int = SIZE, cache=None):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         self.device = torch.device(device)
@@ -547,20 +562,63 @@ class IngestCollate:
         self.keep_workspaces = bool(keep_workspaces)
         self.size = check_size(size)
         self.last_volumes: List[List[KeptVolume]] = []
+        if cache is not None and self.keep_workspaces:
+            raise ConfigurationError("a volume cache keeps no ingest workspaces: keep_workspaces (inference, which reads each patient once) excludes it")
+        held = None if cache is None else cache.planes.device
+        if cache is not None and (cache.size != self.size or held.type != self.device.type or self.device.index not in (None, held.index)):
+            raise ConfigurationError(f"the volume cache holds {cache.size}^3 planes on {cache.planes.device}, the collate makes {self.size}^3 ones on {self.device}")
+        self.cache = cache
 
     def __call__(self, items):
         xs = [it[0] for it in items]
         targets = [torch.stack([torch.as_tensor(it[k]) for it in items]) for k in range(1, len(items[0]))]
         multimodal = isinstance(xs[0], dict)
         raws = [x["image"] for x in xs] if multimodal else xs
-        sized = {"size": self.size} if self.size != SIZE else {}          # (the default's call is the one it always was)
-        batch, extents, *kept = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold,
-                                                keep_workspaces=self.keep_workspaces, **sized)
-        if kept:
-            self.last_volumes = kept[0]
+        if self.cache is not None:
+            batch, extents = self._through_cache(raws)
+        else:
+            sized = {"size": self.size} if self.size != SIZE else {}      # (the default's call is the one it always was)
+            batch, extents, *kept = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold,
+                                                    keep_workspaces=self.keep_workspaces, **sized)
+            if kept:
+                self.last_volumes = kept[0]
         self.pending.append(([r.uid for r in raws], extents))
         x = {"image": batch, "clinical": torch.stack([x["clinical"] for x in xs]).float()} if multimodal else batch
         return (x, targets[0], targets[1] if len(targets) > 1 else None)
+
+    def _through_cache(self, raws):
+        """The batch of `raws` (RawPatient or CachedPatient each) with the cache between the ingest and the batch.  One gather per run of
+        adjacent cached rows: one for a batch without an overflow patient."""
+        cache, n = self.cache, len(raws)
+        batch = torch.empty((n, cache.channels, self.size, self.size, self.size), dtype=torch.float32, device=self.device)
+        extents = torch.empty((n, cache.channels, 3), dtype=torch.int32, device=self.device)
+        slots, cold, into = [None] * n, [], []
+        for i, r in enumerate(raws):
+            if cache.filled(r.uid):
+                slots[i] = cache.table.hit(r.uid)
+                continue
+            volumes = getattr(r, "volumes", None)
+            if volumes is None:
+                raise ValueError(f"ingest: patient uid {r.uid} arrived without voxels and is not in the volume cache")
+            if len(volumes) != cache.channels:
+                raise ValueError(f"ingest: patient uid {r.uid} has {len(volumes)} modalities, the volume cache holds {cache.channels} channels")
+            slots[i] = cache.table.assign(r.uid)
+            cold.append((r.uid, volumes, slots[i]))
+            into.append((batch[i], extents[i]) if slots[i] is None else (cache.planes[slots[i]], cache.extents[slots[i]]))
+        if cold:
+            ingest_patients([v for _, v, _ in cold], self.device, into, self.mask_resample, self.mask_threshold)
+            for uid, _, slot in cold:
+                if slot is not None:
+                    cache.table.mark_filled(uid)
+        i = 0
+        while i < n:
+            j = i
+            while j < n and slots[j] is not None:
+                j += 1
+            if j > i:
+                cache.gather(slots[i:j], batch[i:j], extents[i:j])
+            i = max(j, i + 1)
+        return batch, extents
 
     def take_empty(self) -> List[int]:
         """uids (sorted, each once) of the patients seen since the last call whose mask left nothing of a scan (an extent of 0)."""
