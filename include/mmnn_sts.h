@@ -933,6 +933,47 @@ int64_t mmnn_resample_pair_workspace_bytes(int32_t x, int32_t y, int32_t z, int3
 int mmnn_resample_pair(const mmnn_resample_desc* d, const void* scan, const void* mask, const mmnn_resample_entry* tables_host,
                        const mmnn_resample_entry* tables, float* out, uint8_t* out_mask, void* ws, void* stream);
 
+/* ---- the margin step behind the mask routes: widen a mask by a radius in mm on the scan's grid (csrc/mask_margin.hip).  An exact,
+ * bounded Euclidean distance to the mask under the scan's voxel spacing, thresholded at the radius.  `mask` holds x*y*z elements, x
+ * fastest, in NIfTI type mask_type.
+ *   set voxels   a mask voxel q is set when !(m == 0), m the scaled mask value formed as the ingest forms it: raw * mask_slope +
+ *            mask_inter in fp64, two roundings.  A NaN counts as set.  A slope of 0, NaN or +-inf means no scaling.
+ *   per-axis term  t_a(k) = fl(fl(k s_a) fl(k s_a)) for an index distance k >= 0 along axis a with spacing s_a = spacing[a]: fp64, every
+ *            operation rounded on its own, never an FMA.
+ *   distance  D(p) = min over set q of fl(fl(t_x(|p_x - q_x|) + t_y(|p_y - q_y|)) + t_z(|p_z - q_z|)); +inf for an empty mask.
+ *   radius   R2 = fl(radius radius).
+ *   modes    MMNN_MARGIN_DILATE writes out = 1 where D <= R2, else 0.  MMNN_MARGIN_SHELL writes out = 1 where 0 < D <= R2, else 0: the
+ *            dilated set without the mask itself.
+ *   outputs  `out` is one byte per scan voxel, x fastest; every byte is written and nothing else is.  It is a type-2 mask with slope 1
+ *            and inter 0 for mmnn_ingest_volume and mmnn_radiomics.  An optional `dist2` (fp64, may be null) receives D where D <= R2
+ *            and +inf elsewhere.
+ *   reach    reach_a is the largest k with t_a(k) <= R2; the library computes it on the host from `spacing` and `radius`.  No q farther
+ *            than that along an axis can matter, so the search is bounded.  mmnn_mask_margin_reach is that computation as a host query
+ *            that needs no GPU (status 1 for a null pointer, a spacing or radius that is not finite and > 0, a reach above the cap).
+ * The index axes are taken as orthogonal.  Computed as three passes x, y, z (a rounded addition is monotone, so the minimum commutes with
+ * adding the next axis' term: the same bits as the brute-force minimum above); every loop bound comes from the descriptor, no walk
+ * depends on the data.  Everything is enqueued on the caller's stream; one lane per output, no atomics, no host synchronisation:
+ * repeated calls are bit-identical.  ws: mmnn_mask_margin_workspace_bytes bytes (no GPU needed), aligned to 256: one byte and one fp64
+ * per voxel.  Refused (status 1, nothing written; the size returns -1) before any launch: a null descriptor, mask, out or workspace; a
+ * non-positive extent, or x*y*z >= 2^31; an unknown type code; a spacing or radius that is not finite and > 0; a mode outside the two; a
+ * reach above MMNN_MARGIN_MAX_REACH; `mask` overlapping `out`; a mask not aligned to its element size, dist2 not to 8, ws not to 256.
+ * The cap: 30 mm at 0.4 mm in-plane is 75 voxels; at 128 the y / z tile with its two halos takes 52.1 KiB of the 64 KiB of LDS a launch
+ * gets, and an index distance still fits the byte the x pass stores. */
+#define MMNN_MARGIN_MAX_REACH 128
+#define MMNN_MARGIN_DILATE 0
+#define MMNN_MARGIN_SHELL 1
+typedef struct {
+  int32_t x, y, z;
+  int32_t mask_type;              /* NIfTI datatype code */
+  double mask_slope, mask_inter;
+  double spacing[3];              /* x, y, z, in mm */
+  double radius;                  /* in mm */
+  int32_t mode;                   /* MMNN_MARGIN_DILATE, MMNN_MARGIN_SHELL */
+} mmnn_mask_margin_desc;
+int mmnn_mask_margin_reach(const double spacing[3], double radius, int32_t reach[3]);
+int64_t mmnn_mask_margin_workspace_bytes(int32_t x, int32_t y, int32_t z);
+int mmnn_mask_margin(const mmnn_mask_margin_desc* d, const void* mask, uint8_t* out, double* dist2, void* ws, void* stream);
+
 /* ---- measurement aid (bench.py): MHz the chip sustains under a chip-wide v_mfma_f32_32x32x2_f32 load (one wave per SIMD, every CU), from
  * the known cycle count of an MFMA loop and HIP events around it.  Synchronises the stream.  scratch: >= 1 float of device memory. */
 int mmnn_measure_mfma_clock(double* mhz, float* scratch, void* stream);

@@ -23,7 +23,9 @@ it) names another extent in 1..128 that the model admits: the ingest, the `--tra
 their exports then all work at S^3, and without `--image_loc` the synthetic patients are S^3 too.  End to end this is covered at 64 and
 at 128 only.  `--cache_volumes` (`Data: cache: true`; budget `--cache_gb`, 16) ingests each patient once, keeps its S^3 planes on the device
 and assembles every later batch there, so no file is opened after the first epoch (mmnn_sts_amd/data/cache.py); patients beyond the
-budget are read every epoch.  `--inference --image_loc DIR --scan_space` also writes every class's
+budget are read every epoch.  `--mask_margin_mm r` (`Data: mask_margin_mm: r`) dilates every mask by r mm on the device ahead of the
+ingest (exact Euclidean distance under the scan's voxel spacing, mmnn_sts_amd/data/ingest.py: mask_margin), so the volumes show the tumour
+and the rim around it; the dilated mask is 0 / 1.  `--inference --image_loc DIR --scan_space` also writes every class's
 attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).
 `--inference --images --occlusion` writes occlusion sensitivity maps (patient{i}_occ_map.npy: (K, D, H, W) signed deltas at the resolution of
 `--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
@@ -31,7 +33,8 @@ config reads them back from a csv it writes first (the "synthetic 32-feature x 6
 `--radiomics` trains on radiomic features: the csv of `--rad_loc` (column MRN, then the features), or, without it, the table extracted
 on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py; the config's
 `Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it, `--mesh_shape` / `Radiomics: mesh_shape: true` the
-eight mesh-based shape columns, `--log_sigma 1,3` / `Radiomics: log: {sigma: [1.0, 3.0]}` the `log-sigma-<sigma>-mm-3D_*` columns of the
+eight mesh-based shape columns, `--shell_mm 5,10` / `Radiomics: shell_mm: [5, 10]` the `shell-<r>-mm_*` columns of the tissue within r mm
+around the mask, `--log_sigma 1,3` / `Radiomics: log: {sigma: [1.0, 3.0]}` the `log-sigma-<sigma>-mm-3D_*` columns of the
 scan filtered by a Laplacian of Gaussian at those scales in mm; `--normalize` / `Radiomics: normalize` z-scores each scan first and
 `--resample_spacing 1,1,1` / `Radiomics: resample: {spacing: [1, 1, 1]}` brings scan and mask onto that spacing, both on the device and
 without a change of the columns); alone it is
@@ -271,6 +274,8 @@ def nifti_datasets(parser, args, device, seed, rank, world):
         if rank == 0:
             logger.info("volume cache: room for %d of %d patients (%d x %d^3 fp32 each) in %g GB", args.volume_cache.capacity, args.cache_patients,
                         channels, size, args.cache_gb)
+    if getattr(args, "mask_margin_mm", None) is not None:
+        cached["mask_margin_mm"] = args.mask_margin_mm
     args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False), size=size, **cached)
     return by_uids(full, train_uids[rank::world]), by_uids(full, val_uids)
 
@@ -345,6 +350,7 @@ def extract_radiomics_if_needed(parser, args):
     normalize = parser.radiomicsNormalize(getattr(args, "normalize", False), getattr(args, "normalize_scale", None),
                                           getattr(args, "normalize_outliers", None))
     resample = parser.radiomicsResample(getattr(args, "resample_spacing", None))
+    shells = parser.radiomicsShell(getattr(args, "shell_mm", None))
     paths = parser.getImagePath()
     paths = paths if isinstance(paths, tuple) else (paths,)
     sets = [ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
@@ -352,7 +358,8 @@ def extract_radiomics_if_needed(parser, args):
     threshold = (parser.config.get("Data") or {}).get("mask_threshold")
     rows = radiomics.extract_modalities(sets, torch.device("cuda", 0), rc["bin_width"], rc["max_bins"],
                                         None if threshold is None else float(threshold), classes=classes, glszm=glszm, mesh=mesh,
-                                        log_sigma=log["sigma"], log_bin_width=log["bin_width"], normalize=normalize, resample=resample)
+                                        log_sigma=log["sigma"], log_bin_width=log["bin_width"], normalize=normalize, resample=resample,
+                                        **({"shell_mm": shells} if shells else {}))
     os.makedirs(args.output_path, exist_ok=True)
     out = os.path.join(args.output_path, "radiomics_features.csv")
     radiomics.write_csv(out, rows)
@@ -741,6 +748,12 @@ def build_arg_parser():
                     help="bin width of the filtered images; overrides `Radiomics: log: bin_width` (default: `Radiomics: bin_width`)")
     from mmnn_sts_amd.radiomics import add_pre_step_arguments
     add_pre_step_arguments(ap)
+    ap.add_argument("--shell_mm", type=str, default=None,
+                    help="with --radiomics and no --rad_loc: widths in mm of the peritumoural shells, comma-separated (5,10): append the "
+                         "shell-<r>-mm_* columns of the tissue within r mm around the mask; overrides the config's `Radiomics: shell_mm`")
+    ap.add_argument("--mask_margin_mm", type=float, default=None,
+                    help="with --image_loc: dilate every mask by this many mm on the device ahead of the scan ingest, so the volumes show the "
+                         "tumour and the rim around it; overrides the config's `Data: mask_margin_mm` (the radiomics ROI is not changed)")
     ap.add_argument("--occlusion_window", type=int, default=16, help="edge of the occluded box in voxels")
     ap.add_argument("--occlusion_stride", type=int, default=8, help="step of the box, 1..window")
     ap.add_argument("--occlusion_batch", type=int, default=8, help="occluded samples per forward")
@@ -790,6 +803,17 @@ def main(argv=None):
     # (--radiomics without --images reads --image_loc only to extract its features from)
     use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images) and (a.images or not a.radiomics)
     check_cache_flags(a, data_cfg, use_nifti)
+    try:
+        a.mask_margin_mm = parser.maskMargin(a.mask_margin_mm)
+        shell_flag, a.shell_mm = a.shell_mm is not None, parser.radiomicsShell(a.shell_mm)
+    except ConfigurationError as e:
+        raise SystemExit(str(e))
+    if a.mask_margin_mm is not None and not use_nifti:
+        raise SystemExit("--mask_margin_mm / `Data: mask_margin_mm` widens the masks of patient directories: it needs --image_loc (synthetic "
+                         "patients have no mask)")
+    if shell_flag and not (a.radiomics and not data_cfg.get("rad_loc")):
+        raise SystemExit("--shell_mm adds columns to the table extracted on the device: it needs --radiomics and no "
+                         "--rad_loc")
     if use_nifti:
         if not a.images:
             raise SystemExit("--image_loc points at NIfTI patient directories: it needs --images")

@@ -193,6 +193,16 @@ class ResampleDesc(Structure):
                 ("pole_power", ctypes.c_double * RESAMPLE_HORIZON)]
 
 
+MARGIN_MAX_REACH = 128                       # MMNN_MARGIN_MAX_REACH
+MARGIN_DILATE, MARGIN_SHELL = 0, 1           # MMNN_MARGIN_DILATE, MMNN_MARGIN_SHELL
+
+
+class MaskMarginDesc(Structure):
+    """mmnn_mask_margin_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("mask_type", c_int32), ("mask_slope", ctypes.c_double),
+                ("mask_inter", ctypes.c_double), ("spacing", ctypes.c_double * 3), ("radius", ctypes.c_double), ("mode", c_int32)]
+
+
 def _signatures():
     """Every prototype of include/mmnn_sts.h as {symbol: (restype, argtypes)}, from one table per return type (tests/test_host_cpu.py
     holds them against the header)."""
@@ -263,6 +273,8 @@ def _signatures():
         "mmnn_log_filter": [P(LogFilterDesc), V, V, V, V, V],
         "mmnn_normalize_scan": [P(NormalizeDesc), V, V, V, V, V],
         "mmnn_resample_pair": [P(ResampleDesc)] + [V] * 8,
+        "mmnn_mask_margin_reach": [P(D), D, P(I)],
+        "mmnn_mask_margin": [P(MaskMarginDesc), V, V, V, V, V],
     }
     counts = {                               # int64 size, count or offset; negative: refused, with mmnn_last_error set
         "mmnn_densenet_param_count": [V],
@@ -282,6 +294,7 @@ def _signatures():
         "mmnn_log_filter_workspace_bytes": [I, I, I],
         "mmnn_normalize_scan_workspace_bytes": [I, I, I],
         "mmnn_resample_pair_workspace_bytes": [I] * 6,
+        "mmnn_mask_margin_workspace_bytes": [I, I, I],
         "mmnn_lr_range_state_bytes": [I],
         "mmnn_mlp_saved_floats": [P(MlpDesc)],
     }

@@ -17,6 +17,8 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     ingest_patients(patients, device, into)         the uploads and launches of collate_volumes, into destinations the caller names
     IngestCollate(device, size=64, cache=None)      the DataLoader collate_fn of the NIfTI datasets; `cache`: a VolumeCache (data/cache.py)
                                                     that keeps every ingested patient on the device and assembles the batches from it
+    mask_margin(mask, spacing, radius_mm, mode)     a mask on the scan's grid -> uint8 0 / 1: the mask widened by a margin in mm ('dilate'), or
+                                                    the shell of that width around it ('shell') (mmnn_mask_margin)
     maps_to_scan(maps, scan_shape, ingest_workspace)   the way back: S^3 model-space maps -> fp32 volumes on the scan's grid (mmnn_maps_to_scan_sized)
 
 The output extent S is 64 (`SIZE`, upstream's Resize target) unless a caller chooses another one in 1..128 (`MAX_SIZE`): `ingest_volume`
@@ -424,6 +426,81 @@ def prepare_pair(scan, mask, dev, index_map=None, threshold: Optional[float] = N
     return scan, mask
 
 
+MARGIN_MODES = {"dilate": _lib.MARGIN_DILATE, "shell": _lib.MARGIN_SHELL}
+
+
+def margin_radius(radius_mm, key: str = "mask_margin_mm"):
+    """`radius_mm` as a margin in mm: None stays None (the step is off), otherwise a positive finite number, else ConfigurationError."""
+    if radius_mm is None:
+        return None
+    try:
+        r = float("nan") if isinstance(radius_mm, bool) else float(radius_mm)
+    except (TypeError, ValueError):
+        r = float("nan")
+    if not (r > 0.0 and r < float("inf")):
+        raise ConfigurationError(f"{key} must be a positive finite number of mm, got {radius_mm!r}")
+    return r
+
+
+def margin_reach(spacing, radius_mm) -> Tuple[int, int, int]:
+    """`mmnn_mask_margin_reach`: per axis the largest index distance k with (k s_a)^2 <= radius^2, on the host (no GPU).  ValueError for a
+    spacing or radius that is not finite and > 0 and for a reach above the library's cap (`_lib.MARGIN_MAX_REACH`)."""
+    s = (ctypes.c_double * 3)(*(float(v) for v in spacing))
+    reach = (ctypes.c_int32 * 3)()
+    _lib.call("mmnn_mask_margin_reach", s, float(radius_mm), reach)
+    return tuple(int(v) for v in reach)
+
+
+def mask_margin_workspace_bytes(x: int, y: int, z: int) -> int:
+    return _lib.count("mmnn_mask_margin_workspace_bytes", int(x), int(y), int(z))
+
+
+def mask_margin(mask: DeviceVolume, spacing, radius_mm, mode: str = "dilate", out: Optional[torch.Tensor] = None,
+                dist2: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> DeviceVolume:
+    """Enqueue `mmnn_mask_margin` on the current stream of the mask's device: the mask widened by `radius_mm` under the voxel `spacing`
+    (x, y, z in mm; `radiomics.spacing_of(scan.affine)`, the column norms of the affine's linear part, (1, 1, 1) without an affine).
+    `mode` 'dilate': 1 where the exact Euclidean distance to the nearest set voxel is <= radius_mm (the mask plus its rim); 'shell': 1
+    where it is > 0 and <= radius_mm (the rim alone).  A voxel is set when its scaled value is not 0, as the ingest reads a mask.
+    The distance treats the index axes as orthogonal, which those of a sheared affine are not; shear is not detected.
+    `mask`: a DeviceVolume on the scan's grid (what `prepare_pair` returns).  `out`: a contiguous uint8 tensor of x*y*z elements on its
+    device to write, which must not be the mask's own; `dist2`: None, or x*y*z contiguous float64 that receive the squared distance in
+    mm^2 where it is <= radius^2 and +inf elsewhere; `workspace`: at least `mask_margin_workspace_bytes` of uint8.  `out` and
+    `workspace` are allocated when None.  The result has type 2, slope 1, inter 0 and the mask's affine (on this path the scan's).
+    A radius smaller than every spacing reaches no neighbour -- the dilation would be the mask and the shell empty -- and is refused."""
+    if mode not in MARGIN_MODES:
+        raise ValueError(f"mask_margin: mode {mode!r} is none of {tuple(MARGIN_MODES)}")
+    if not isinstance(mask, DeviceVolume):
+        raise ValueError("mask_margin: the mask must be a DeviceVolume on the scan's grid (see prepare_pair)")
+    spacing = tuple(float(v) for v in spacing)
+    if len(spacing) != 3:
+        raise ValueError(f"mask_margin: spacing must be three numbers (x, y, z in mm), got {spacing!r}")
+    reach = margin_reach(spacing, radius_mm)
+    if reach == (0, 0, 0):
+        raise ValueError(f"mask_margin: a radius of {float(radius_mm)} mm is smaller than every voxel spacing ({spacing[0]}, {spacing[1]}, "
+                         f"{spacing[2]} mm): it reaches no neighbouring voxel, so the dilation is the mask itself and the shell is empty")
+    dev = mask.data.device
+    x, y, z = (int(v) for v in mask.shape)
+    n = x * y * z
+    if min(x, y, z) >= 1:
+        out = _lib.device_buffer(out, n, torch.uint8, dev, "mask_margin")
+        if dist2 is not None:
+            dist2 = _lib.device_buffer(dist2, n, torch.float64, dev, "mask_margin (dist2)")
+        workspace = _lib.workspace(workspace, mask_margin_workspace_bytes(x, y, z), dev, "mask_margin")
+    desc = _lib.MaskMarginDesc(x, y, z, mask.datatype, float(mask.slope), float(mask.inter), (ctypes.c_double * 3)(*spacing), float(radius_mm),
+                               MARGIN_MODES[mode])
+    _lib.enqueue("mmnn_mask_margin", ctypes.byref(desc), mask.data.data_ptr(), None if out is None else out.data_ptr(),
+                 None if dist2 is None else dist2.data_ptr(), None if workspace is None else workspace.data_ptr(), device=dev)
+    return DeviceVolume(out.view(-1), (x, y, z), TYPE_CODES[np.dtype("uint8")], 1.0, 0.0, mask.affine)
+
+
+def widen_mask(scan: DeviceVolume, mask: DeviceVolume, radius_mm, mode: str = "dilate") -> DeviceVolume:
+    """`mask_margin` of a prepared pair's mask under the spacing of the scan's affine; the result carries the scan's affine."""
+    from .. import radiomics
+    out = mask_margin(mask, radiomics.spacing_of(scan.affine), radius_mm, mode)
+    out.affine = scan.affine
+    return out
+
+
 def check_size(size, who: str = "ingest") -> int:
     """`size` as an output extent per axis: an integer in 1..MAX_SIZE, else ValueError."""
     if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 1 <= int(size) <= MAX_SIZE:
@@ -432,7 +509,7 @@ def check_size(size, who: str = "ingest") -> int:
 
 
 def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
-                  index_map=None, threshold: Optional[float] = None) -> torch.Tensor:
+                  index_map=None, threshold: Optional[float] = None, mask_margin_mm: Optional[float] = None) -> torch.Tensor:
     """Enqueue the ingest of one volume on the current stream: `out_plane` (a contiguous (S,S,S) fp32 CUDA view with S in 1..128, e.g. batch[n, c]) receives
     the masked, compacted scan, area-resized to S^3; returns `extents` (3 x int32 on the device: kept slices along x, y, z), readable after
     the next synchronisation.  `scan` / `mask`: DeviceVolume, NiftiImage or ndarray (host volumes are uploaded first).  When the
@@ -442,7 +519,11 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     None: 0.5, or 128 behind a DICOM scan.  A `mask` that is a ContourSet (or `stage_contours`' result) beside a DICOM scan is
     rasterised onto the scan's grid first (`rasterize_contours`) and takes the voxelwise path: no resample, no threshold.  A `mask`
     that is a FrameSet (or `stage_frames`' result) beside a DICOM scan is unpacked first (`unpack_frames`): onto the scan's grid, and
-    then voxelwise like a contour mask, or onto a grid of its own, and then resampled and binarised like a DICOM mask series."""
+    then voxelwise like a contour mask, or onto a grid of its own, and then resampled and binarised like a DICOM mask series.
+    `mask_margin_mm` (None: nothing is launched or allocated for it): behind all of that the mask is replaced by its dilation by that many
+    mm (`mask_margin`, under the spacing of the scan's affine) and the ingest runs unchanged on it: the plane is scan x (1 inside tumour +
+    margin, 0 outside) and the slices the rim touches are kept.  The dilated mask is 0 / 1, so a mask whose set voxels hold another value
+    (255) no longer scales the plane by it."""
     shape = tuple(out_plane.shape)
     if not (out_plane.is_cuda and out_plane.dtype == torch.float32 and out_plane.is_contiguous() and len(shape) == 3
             and shape == shape[:1] * 3 and 1 <= shape[0] <= MAX_SIZE):
@@ -451,6 +532,8 @@ def ingest_volume(scan, mask, out_plane: torch.Tensor, extents: Optional[torch.T
     size = shape[0]
     dev = out_plane.device
     scan, mask = prepare_pair(scan, mask, dev, index_map, threshold)
+    if mask_margin_mm is not None:
+        mask = widen_mask(scan, mask, mask_margin_mm)
     extents = _lib.device_buffer(extents, 3, torch.int32, dev, "ingest (extents)")
     x, y, z = scan.shape
     workspace = _lib.workspace(workspace, workspace_bytes(x, y, z), dev, "ingest")
@@ -502,7 +585,8 @@ def maps_to_scan(maps: torch.Tensor, scan_shape, ingest_workspace: torch.Tensor,
 
 
 def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device, mask_resample: str = "auto",
-                    mask_threshold: Optional[float] = None, keep_workspaces: bool = False, size: int = SIZE):
+                    mask_threshold: Optional[float] = None, keep_workspaces: bool = False, size: int = SIZE,
+                    mask_margin_mm: Optional[float] = None):
     """patients[n][c] = (scan, mask) -> the device batch (N, C, S, S, S) fp32, S = `size` in 1..128, and the kept extents (N, C, 3) int32.  Every upload is
     issued before the first kernel, so the copies of one volume run beside the passes of the one before it.  A mask on another grid
     than its scan's is resampled first, as `mask_resample` ('auto', 'geometry', 'never') says, and binarised at `mask_threshold`
@@ -510,7 +594,9 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     placed on that scan's grid by the host, uploaded with the others and rasterised there; it takes neither resample nor threshold.
     A FrameSet (a DICOM SEG file) is placed by the host, uploaded with the others and unpacked on the device (see `unpack_frames`).
     With `keep_workspaces` every volume is ingested with a workspace of its own and a third value is returned: volumes[n][c], the
-    `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan."""
+    `KeptVolume` (workspace, scan extents, scan affine) that `maps_to_scan` needs to lay a map of the model over that scan.
+    `mask_margin_mm` (`Data: mask_margin_mm`; None: off): every mask is replaced by its dilation by that many mm ahead of the ingest (see
+    `ingest_volume`); the kept lists, and with them the maps `maps_to_scan` lays back, are those of the widened box."""
     size = check_size(size)
     n, c = len(patients), len(patients[0])
     if any(len(p) != c for p in patients):
@@ -518,14 +604,19 @@ def collate_volumes(patients: Sequence[Sequence[Tuple[object, object]]], device,
     device = torch.device(device)
     batch = torch.empty((n, c, size, size, size), dtype=torch.float32, device=device)
     extents = torch.empty((n, c, 3), dtype=torch.int32, device=device)
-    kept = ingest_patients(patients, device, [(batch[i], extents[i]) for i in range(n)], mask_resample, mask_threshold, keep_workspaces)
+    margin = {} if mask_margin_mm is None else {"mask_margin_mm": mask_margin_mm}      # (without one the call is the one it always was)
+    kept = ingest_patients(patients, device, [(batch[i], extents[i]) for i in range(n)], mask_resample, mask_threshold, keep_workspaces, **margin)
     return (batch, extents, kept) if keep_workspaces else (batch, extents)
 
 
-def ingest_patients(patients, device, into, mask_resample: str = "auto", mask_threshold: Optional[float] = None, keep_workspaces: bool = False):
+def ingest_patients(patients, device, into, mask_resample: str = "auto", mask_threshold: Optional[float] = None, keep_workspaces: bool = False,
+                    mask_margin_mm: Optional[float] = None):
     """The uploads and launches of `collate_volumes` with the destinations named by the caller: into[n] = (planes (C, S, S, S) fp32,
     extents (C, 3) int32), two contiguous device views that patient n is ingested into -- a row of a batch, or a row of the volume
-    cache (`mmnn_sts_amd.data.cache`).  Returns the `KeptVolume`s, volumes[n][c] (empty lists without `keep_workspaces`)."""
+    cache (`mmnn_sts_amd.data.cache`).  Returns the `KeptVolume`s, volumes[n][c] (empty lists without `keep_workspaces`).
+    `mask_margin_mm`: as in `collate_volumes`."""
+    mask_margin_mm = margin_radius(mask_margin_mm)
+    margin = {} if mask_margin_mm is None else {"mask_margin_mm": mask_margin_mm}
     up = [[(upload(s, device), stage_mask(s, m, device)) for s, m in p] for p in patients]
     maps = [[mask_index_map(s, m, mask_resample) for s, m in p] for p in up]
     kept = []
@@ -533,7 +624,7 @@ def ingest_patients(patients, device, into, mask_resample: str = "auto", mask_th
         kept.append([])
         for j in range(len(up[i])):
             ws = torch.empty(workspace_bytes(*up[i][j][0].shape), dtype=torch.uint8, device=device) if keep_workspaces else None
-            ingest_volume(up[i][j][0], up[i][j][1], planes[j], extents[j], ws, index_map=maps[i][j], threshold=mask_threshold)
+            ingest_volume(up[i][j][0], up[i][j][1], planes[j], extents[j], ws, index_map=maps[i][j], threshold=mask_threshold, **margin)
             if keep_workspaces:
                 kept[i].append(KeptVolume(ws, up[i][j][0].shape, up[i][j][0].affine))
     return kept
@@ -550,10 +641,12 @@ class IngestCollate:
     size and channel count.  A patient seen for the first time is then ingested straight into its row of the cache -- the same calls
     with another destination -- and every batch is assembled from the cache's rows by `mmnn_gather_rows` on the same stream, so batch
     and extents hold the bits they hold without a cache; an item whose image is a `CachedPatient` brings no voxels at all.  A patient
-    that found the cache full is ingested into its row of the batch, as without one."""
+    that found the cache full is ingested into its row of the batch, as without one.
+    `mask_margin_mm` (`Data: mask_margin_mm`, `--mask_margin_mm`; None: off, and every batch is bit for bit what it is without the
+    key): every mask is dilated by that many mm on the device ahead of its ingest; a cache then stores what that ingest made."""
 
     def __init__(self, device, mask_resample: str = "auto", mask_threshold: Optional[float] = 0.5, keep_workspaces: bool = False,
-                 size: int = SIZE, cache=None):
+                 size: int = SIZE, cache=None, mask_margin_mm: Optional[float] = None):
         if mask_resample not in MASK_RESAMPLE_MODES:
             raise ConfigurationError(f"mask_resample {mask_resample!r} is none of {MASK_RESAMPLE_MODES}")
         self.device = torch.device(device)
@@ -561,6 +654,7 @@ class IngestCollate:
         self.pending: List[Tuple[List[int], torch.Tensor]] = []
         self.keep_workspaces = bool(keep_workspaces)
         self.size = check_size(size)
+        self.mask_margin_mm = margin_radius(mask_margin_mm)
         self.last_volumes: List[List[KeptVolume]] = []
         if cache is not None and self.keep_workspaces:
             raise ConfigurationError("a volume cache keeps no ingest workspaces: keep_workspaces (inference, which reads each patient once) excludes it")
@@ -578,6 +672,8 @@ class IngestCollate:
             batch, extents = self._through_cache(raws)
         else:
             sized = {"size": self.size} if self.size != SIZE else {}      # (the default's call is the one it always was)
+            if self.mask_margin_mm is not None:
+                sized["mask_margin_mm"] = self.mask_margin_mm
             batch, extents, *kept = collate_volumes([r.volumes for r in raws], self.device, self.mask_resample, self.mask_threshold,
                                                     keep_workspaces=self.keep_workspaces, **sized)
             if kept:
@@ -606,7 +702,8 @@ class IngestCollate:
             cold.append((r.uid, volumes, slots[i]))
             into.append((batch[i], extents[i]) if slots[i] is None else (cache.planes[slots[i]], cache.extents[slots[i]]))
         if cold:
-            ingest_patients([v for _, v, _ in cold], self.device, into, self.mask_resample, self.mask_threshold)
+            margin = {} if self.mask_margin_mm is None else {"mask_margin_mm": self.mask_margin_mm}
+            ingest_patients([v for _, v, _ in cold], self.device, into, self.mask_resample, self.mask_threshold, **margin)
             for uid, _, slot in cold:
                 if slot is not None:
                     cache.table.mark_filled(uid)

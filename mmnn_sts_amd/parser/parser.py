@@ -153,6 +153,23 @@ class Parser:
             raise ConfigurationError('Radiomics.resample.spacing must be one number or a list of three (mm), got {!r}'.format(res['spacing']))
         return resample_spacing(res)
 
+    def radiomicsShell(self, shell_mm=None):
+        """`Radiomics: shell_mm: [5, 10]`: the widths in mm of the peritumoural shells whose features follow every `original_*` and
+        `log-*` column -> the widths, de-duplicated and ascending (empty, the default: no shell).  `shell_mm`: a command line's value
+        (`--shell_mm 5,10`), which goes before the config's."""
+        from ..radiomics import shell_widths
+        value = (self.config.get('Radiomics') or {}).get('shell_mm')
+        if shell_mm is None and isinstance(value, str):
+            raise ConfigurationError('Radiomics.shell_mm must be a list of positive finite numbers (mm), got {!r}'.format(value))
+        return shell_widths(shell_mm if shell_mm is not None else value)
+
+    def maskMargin(self, flag=None):
+        """`Data: mask_margin_mm`: the margin in mm every mask is dilated by on the device ahead of the scan ingest -> None (off, the
+        default) or a positive finite number.  `flag`: the command line's `--mask_margin_mm`, which goes before the config's."""
+        from ..data.ingest import margin_radius
+        value = flag if flag is not None else (self.config.get('Data') or {}).get('mask_margin_mm')
+        return margin_radius(value, '--mask_margin_mm' if flag is not None else 'Data.mask_margin_mm')
+
     def _radiomicsExcluded(self):
         rm = self.config.get('RadiomicsModel') or {}
         return list(rm.get('RADIOMICS_EXCLUDE_COLUMNS') or []), list(rm.get('RADIOMICS_LABEL_COLUMNS') or [])

@@ -6,8 +6,9 @@
     extract(scan, mask, device)            enqueue one extraction; the result holds device tensors, nothing is read back
     finish(result, affine)                 one read-back -> {feature name: float}: adds TotalEnergy and the voxel-based shape features
     extract_tree(dataset, device, out)     every patient and modality of an image dataset -> a csv (`MRN`, then the features)
-    feature_names(classes, glszm, mesh, log_sigma)  the columns: FEATURE_NAMES, then those of the requested texture classes, then the
-                                           size-zone ones, then the mesh-based shape ones, then those of the filtered images
+    feature_names(classes, glszm, mesh, log_sigma, shell_mm)  the columns: FEATURE_NAMES, then those of the requested texture classes, then
+                                           the size-zone ones, then the mesh-based shape ones, then those of the filtered images, then
+                                           those of the shells
     log_taps(sigma_mm, spacing)            the radii, taps and weights of one Laplacian-of-Gaussian scale (numpy fp64, host only)
     log_filter(scan, sigma_mm, device)     enqueue the filter; the float32 volume stays on the device
     normalize_scan(scan, device, scale, outliers)   enqueue the whole-scan z-score; the float32 volume stays on the device
@@ -15,7 +16,7 @@
     resample_pair(scan, mask, device, spacing)      enqueue the resampling -> (float32 scan with the new affine, uint8 mask)
     python -m mmnn_sts_amd.radiomics --image_loc DIR --key_loc key.csv [--config c.yaml] [--classes glrlm,gldm,ngtdm | all] [--glszm]
                                      [--mesh_shape] [--log_sigma 1,3 [--log_bin_width B]] [--normalize [--normalize_scale S]
-                                     [--normalize_outliers K]] [--resample_spacing 1,1,1] --out radiomics.csv
+                                     [--normalize_outliers K]] [--resample_spacing 1,1,1] [--shell_mm 5,10] --out radiomics.csv
 
 Upstream reads such a csv (`Data: rad_loc`, data/RadiomicsDatasets.py) and leaves its extraction to PyRadiomics; here the table is built
 from the very pair the image path ingests, through the same mask routes (NIfTI mask, resampled mask, DICOM mask series, RTSTRUCT, SEG:
@@ -64,9 +65,18 @@ the scanner's own grid and in its own intensity units.  Both are pinned to the n
 bit for bit, and that one to scipy's `spline_filter` / `map_coordinates`; **parity with PyRadiomics is unpinned**: it is not installed
 here, its B-spline is ITK's, and it crops the resampled grid to the ROI's bounding box plus padding where this resamples the whole scan.
 
+`shell_mm` (`Radiomics: shell_mm: [5, 10]`, `--shell_mm 5,10`; empty by default) describes the tissue the tumour sits in: for every width r
+(in mm, ascending) `data.ingest.mask_margin` builds on the device the shell of the voxels whose exact Euclidean distance to the mask,
+under the voxel spacing of the grid the extraction sees (behind `normalize` / `resample`), is above 0 and at most r, and the same
+extraction calls -- first order and GLCM, the requested texture classes and `glszm`, never the shape classes or the mesh -- run on the
+unfiltered scan under that shell, binned at `bin_width`.  Their columns `shell-<r>-mm_*` (5 is written `5-0`) follow every `original_*`
+and `log-*` one.  Shells of the LoG volumes are out of scope.  A shell that selects no voxel (the mask fills the scan) raises as an empty
+ROI does.  The mask step is pinned to the numpy restatement in tests/_mask_margin_ref.py, bit for bit, and that one to scipy's
+`distance_transform_edt`.  The distance takes the index axes as orthogonal; a sheared affine is not detected.
+
 STAGES states each call once -- its C symbol, buffers, switch, unpacking and columns -- and `extract`, `finish`, `feature_names` and
 `features_of` all read it; `enqueue(result, stage, desc, stream)` makes one call into the buffers a result already has.  One read-back
-brings every result block to the host, stacked per image (the original, then each filtered one, sigma ascending): the first call's block,
+brings every result block to the host, stacked per image (the original, then each filtered one, sigma ascending, then each shell, width ascending): the first call's block,
 then, of the calls that ran, the texture block, the size-zone block and the mesh block.
 """
 import argparse
@@ -158,17 +168,45 @@ def log_sigmas(sigma) -> tuple:
     return tuple(sorted(out))
 
 
+def shell_widths(shell_mm) -> tuple:
+    """`shell_mm` (numbers, a comma-separated string, one number or None) -> the shell widths in mm, de-duplicated and ascending."""
+    if shell_mm is None:
+        return ()
+    if isinstance(shell_mm, str):
+        shell_mm = [v for v in shell_mm.replace(",", " ").split() if v]
+    elif isinstance(shell_mm, (int, float)) and not isinstance(shell_mm, bool):
+        shell_mm = [shell_mm]
+    if not isinstance(shell_mm, (list, tuple)):
+        raise ConfigurationError(f"radiomics: shell_mm must be a list of positive finite numbers (mm), got {shell_mm!r}")
+    out = set()
+    for v in shell_mm:
+        try:
+            f = math.nan if isinstance(v, bool) else float(v)
+        except (TypeError, ValueError):
+            f = math.nan
+        if not (f > 0.0 and f < math.inf):
+            raise ConfigurationError(f"radiomics: shell width {v!r} is not a positive finite number (mm)")
+        out.add(f)
+    return tuple(sorted(out))
+
+
+def shell_image_type(radius_mm) -> str:
+    """The column prefix of the shell of `radius_mm` mm, written as `log_image_type` writes a sigma: 5 -> `shell-5-0-mm`."""
+    return "shell-" + str(float(radius_mm)).replace(".", "-") + "-mm"
+
+
 def log_image_type(sigma) -> str:
     """PyRadiomics' name of the LoG image type at `sigma` mm: 3 -> `log-sigma-3-0-mm-3D`, 1.5 -> `log-sigma-1-5-mm-3D`."""
     return "log-sigma-" + str(float(sigma)).replace(".", "-") + "-mm-3D"
 
 
-def feature_names(classes=(), glszm=False, mesh=False, log_sigma=()) -> tuple:
+def feature_names(classes=(), glszm=False, mesh=False, log_sigma=(), shell_mm=()) -> tuple:
     """FEATURE_NAMES, then `original_glrlm_*`, `original_gldm_*`, `original_ngtdm_*` of the requested classes, then with `glszm`
     `original_glszm_*`, then with `mesh` the eight mesh-based `original_shape_*`; then for every sigma of `log_sigma`, ascending,
-    `log-sigma-<sigma>-mm-3D_firstorder_*`, `_glcm_*`, the requested classes and with `glszm` `_glszm_*` (never the shape classes)."""
+    `log-sigma-<sigma>-mm-3D_firstorder_*`, `_glcm_*`, the requested classes and with `glszm` `_glszm_*` (never the shape classes);
+    then for every width of `shell_mm`, ascending, the same columns under `shell-<r>-mm_*`."""
     classes, names = texture_classes(classes), ()
-    for im in ("original",) + tuple(log_image_type(s) for s in log_sigmas(log_sigma)):
+    for im in ("original",) + tuple(log_image_type(s) for s in log_sigmas(log_sigma)) + tuple(shell_image_type(r) for r in shell_widths(shell_mm)):
         on = {"classes": classes, "glszm": glszm, "mesh_shape": mesh and im == "original"}
         names += tuple(n for st in STAGES if st.flag is None or on[st.flag] for n in st.names(im, classes))
     return names
@@ -189,7 +227,10 @@ class RadiomicsResult:
     the (scale, outliers) in force, `normalized`, the DeviceVolume `normalize_scan` returned, and `normalize_block`, the bytes of
     mmnn_normalize_result; `resample`, the requested spacing, `resampled`, the (scan, mask) DeviceVolumes `resample_pair` returned (None
     when every ratio is 1 and the step was skipped), and `resample_tables`, the tables on the device; `pre_workspace`, which the two
-    steps share; `source_shape`, the extents before the pre-steps.  `shape` and `affine` are then the resampled grid's."""
+    steps share; `source_shape`, the extents before the pre-steps.  `shape` and `affine` are then the resampled grid's.
+    With `shell_mm`: `shell`, a tuple of (width in mm, the RadiomicsResult of the unfiltered scan under the shell of that width around
+    the mask); such a result has `image` set to its column prefix and `shell_mask`, the DeviceVolume `mask_margin` returned (uint8 0 / 1
+    on the grid the extraction sees); `shell_workspace`, which the shells of one extraction share, is on the original image's result."""
     block: torch.Tensor
     hist: torch.Tensor
     glcm: torch.Tensor
@@ -229,6 +270,9 @@ class RadiomicsResult:
     resample_tables: Optional[torch.Tensor] = None
     pre_workspace: Optional[torch.Tensor] = None
     source_shape: Optional[tuple] = None
+    shell: tuple = ()
+    shell_mask: Optional[object] = None
+    shell_workspace: Optional[torch.Tensor] = None
 
 
 def workspace_bytes(x: int, y: int, z: int, max_bins: int = DEFAULT_MAX_BINS) -> int:
@@ -543,7 +587,8 @@ def _pre_steps(scan, mask, norm, spacing, buffers):
 
 def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS, index_map=None,
             threshold: Optional[float] = None, buffers: Optional[RadiomicsResult] = None, classes=(), glszm: bool = False,
-            mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None) -> RadiomicsResult:
+            mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None,
+            shell_mm=()) -> RadiomicsResult:
     """Enqueue the extraction of one (scan, mask) pair on the current stream of `device`.  `scan` / `mask`: whatever `ingest_volume`
     takes (host volumes are uploaded; a contour, SEG or other-grid mask is brought onto the scan's grid first, `index_map` and
     `threshold` as there).  `buffers`: a former result of the same extents and `max_bins` whose tensors are written again.  `classes`:
@@ -554,11 +599,18 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
     `log_bin_width` (None: `bin_width`); the results are `RadiomicsResult.log`.  `buffers` must then come from an extraction with the
     same scales.  `normalize` (`normalize_settings`) and `resample` (`resample_spacing`): the pre-steps, enqueued in this order behind
     `ingest.prepare_pair` and ahead of every call, which then see the new pair and its affine; `buffers` must come from an extraction with
-    the same settings on the same extents.  With both None nothing is enqueued or allocated for them."""
+    the same settings on the same extents.  With both None nothing is enqueued or allocated for them.  `shell_mm`: shell widths in mm;
+    behind every other call, for each width ascending, `ingest.mask_margin` builds the shell of that width around the mask (mode 'shell':
+    within the width of the mask but not of it) on the grid the calls see -- behind the pre-steps, with that grid's spacing -- and the
+    same calls but the mesh one run on the unfiltered scan under it, binned at `bin_width`; the results are `RadiomicsResult.shell`.  No
+    shell of a filtered volume is taken.  `buffers` must then come from an extraction with the same widths.  Empty: nothing is enqueued
+    or allocated for it."""
     from .data import ingest
     dev = torch.device(device)
     scan, mask = ingest.prepare_pair(scan, mask, dev, index_map, threshold, what="radiomics")
-    classes, sigmas = texture_classes(classes), log_sigmas(log_sigma)
+    classes, sigmas, shells = texture_classes(classes), log_sigmas(log_sigma), shell_widths(shell_mm)
+    if buffers is not None and tuple(r for r, _ in buffers.shell) != shells:
+        raise ValueError(f"radiomics: buffers of the shell widths {tuple(r for r, _ in buffers.shell)} cannot take an extraction at {shells}")
     if buffers is not None and tuple(s for s, _ in buffers.log) != sigmas:
         raise ValueError(f"radiomics: buffers of the LoG scales {tuple(s for s, _ in buffers.log)} cannot take an extraction at {sigmas}")
     scan, mask, pre = _pre_steps(scan, mask, normalize_settings(normalize), resample_spacing(resample), buffers)
@@ -576,6 +628,20 @@ def extract(scan, mask, device, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: 
             sub.image, sub.filtered, sub.filter_taps = log_image_type(s), vol, taps
             subs.append((s, sub))
         out.log = tuple(subs)
+    if shells:
+        out.shell_workspace = None if buffers is None else buffers.shell_workspace
+        if out.shell_workspace is None:
+            out.shell_workspace = torch.empty(ingest.mask_margin_workspace_bytes(*scan.shape), dtype=torch.uint8, device=scan.data.device)
+        subs = []
+        for i, r in enumerate(shells):
+            old = None if buffers is None else buffers.shell[i][1]
+            rim = ingest.mask_margin(mask, spacing_of(scan.affine), r, "shell", None if old is None else old.shell_mask.data,
+                                     workspace=out.shell_workspace)
+            rim.affine = scan.affine
+            sub = _extract_image(scan, rim, bin_width, max_bins, old, classes, glszm, False)
+            sub.image, sub.shell_mask = shell_image_type(r), rim
+            subs.append((r, sub))
+        out.shell = tuple(subs)
     return out
 
 
@@ -789,7 +855,7 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
             "of an integer type, makes every normalised value NaN)" if normalized else ""))
     if fields["overflow"]:
         raise ConfigurationError(f"{what}: the values inside the mask span {fields['n_bins']} bins, more than max_bins: choose a larger "
-                                 + ("bin_width (Radiomics: bin_width)" if image == "original" else
+                                 + ("bin_width (Radiomics: bin_width)" if image == "original" or image.startswith("shell-") else
                                     "log.bin_width (Radiomics: log: bin_width, --log_bin_width)") + " or more bins (Radiomics: max_bins)")
     if affine is None:
         if not _logged_identity:
@@ -807,8 +873,8 @@ def features_of(fields: dict, affine, what: str = "radiomics", texture: Optional
 
 def _stage_blocks(r: RadiomicsResult):
     """(the RadiomicsResult of an image, stage, that stage's block) in the order of the stacked read-back: per image -- `r`, then its
-    filtered ones, sigma ascending -- the first call's block, then those of the follow-on calls that ran."""
-    for q in (r,) + tuple(sub for _, sub in r.log):
+    filtered ones, sigma ascending, then its shells, width ascending -- the first call's block, then those of the follow-on calls that ran."""
+    for q in (r,) + tuple(sub for _, sub in r.log) + tuple(sub for _, sub in r.shell):
         for st in STAGES:
             if st.flag is None or getattr(q, st.flag):
                 yield q, st, getattr(q, st.block)
@@ -851,15 +917,18 @@ def _volumes_of(dataset, patient):
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
                  mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False,
-                 mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None) -> List[dict]:
+                 mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None,
+                 shell_mm=()) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
     A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
     blocks, with `glszm` the size-zone blocks, with `mesh` the mesh blocks and with `log_sigma` the filtered images' blocks, come back in
-    the batch's same stacked read-back.  `normalize` / `resample`: the pre-steps of `extract`; they add nothing to the read-back."""
+    the batch's same stacked read-back.  `normalize` / `resample`: the pre-steps of `extract`; they add nothing to the read-back.
+    `shell_mm`: shell widths in mm, whose columns follow all the others; their blocks come back in the same read-back."""
     from .data import ingest
     dev = torch.device(device)
     classes, log_sigma = texture_classes(classes), log_sigmas(log_sigma)
+    shells = {"shell_mm": shell_widths(shell_mm)} if shell_widths(shell_mm) else {}      # (without one the call is the one it always was)
     rows = []
     patients = list(dataset.patients)
     for b0 in range(0, len(patients), max(1, int(batch))):
@@ -868,7 +937,7 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
         res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm, mesh=mesh,
-                        log_sigma=log_sigma, log_bin_width=log_bin_width, normalize=normalize, resample=resample)
+                        log_sigma=log_sigma, log_bin_width=log_bin_width, normalize=normalize, resample=resample, **shells)
                 for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
         blocks = torch.stack([_stacked(r) for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
@@ -950,6 +1019,9 @@ def build_arg_parser():
     ap.add_argument("--log_bin_width", type=float, default=None, help="bin width of the filtered images; overrides the config's "
                     "`Radiomics: log: bin_width` (default: the original image's bin width)")
     add_pre_step_arguments(ap)
+    ap.add_argument("--shell_mm", default=None, help="widths in mm of the peritumoural shells, comma-separated (5,10): appends the "
+                    "shell-<r>-mm_* columns of the tissue within r mm around the mask (never the shape classes); overrides the config's "
+                    "`Radiomics: shell_mm`")
     return ap
 
 
@@ -966,6 +1038,7 @@ def main(argv=None):
     log = parser.radiomicsLog(a.log_sigma, a.log_bin_width)
     normalize = parser.radiomicsNormalize(a.normalize, a.normalize_scale, a.normalize_outliers)
     resample = parser.radiomicsResample(a.resample_spacing)
+    shells = parser.radiomicsShell(a.shell_mm)
     data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
@@ -975,7 +1048,7 @@ def main(argv=None):
             for d in dirs]
     rows = extract_modalities(sets, a.device, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
                               data.get("mask_threshold"), classes=classes, glszm=glszm, mesh=mesh, log_sigma=log["sigma"],
-                              log_bin_width=log["bin_width"], normalize=normalize, resample=resample)
+                              log_bin_width=log["bin_width"], normalize=normalize, resample=resample, **({"shell_mm": shells} if shells else {}))
     write_csv(a.out, rows)
     print(f"{len(rows)} patients, {len(rows[0]) - 1 if rows else 0} features -> {a.out}")
 
