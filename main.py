@@ -14,38 +14,18 @@ optimizer step per batch, F1 per epoch, best model by mean validation F1 saved a
 Deviations from the reference, all listed in SURVEY Appendix A: the published script cannot be imported (Q1) -- its third assert
 is dropped and CLASS_FREQUENCIES comes from the config; the validation loop moves `val_images` (Q10); the blender lives on the
 loss device (Q4); logging syncs once per epoch, not per micro-batch; `--preop` alone builds the standalone MLP (Q12).
-Datasets: `--image_loc DIR --key_loc key.csv --data_loc clinical.csv` (or the config's `Data:` section) trains on / evaluates local
-patient directories, NIfTI files or uncompressed single-frame DICOM series (`patient/image/<series>/*.dcm`, `patient/mask/<series>/*.dcm`;
-the layout is detected per tree, `Data: format` forces one) -- the files' raw voxels are masked, cropped of empty slices and resized to
-S^3 on the device, DICOM slices are decoded there first (mmnn_sts_amd/data/ingest.py, dicom.py); compressed or multi-frame DICOM and S3
-stay outside the path.  S is 64, upstream's Resize target, unless `--image_size S` (or the config's `Data: size: S`; the flag goes before
-it) names another extent in 1..128 that the model admits: the ingest, the `--transforms` Resize, the attention and occlusion maps and
-their exports then all work at S^3, and without `--image_loc` the synthetic patients are S^3 too.  End to end this is covered at 64 and
-at 128 only.  `--cache_volumes` (`Data: cache: true`; budget `--cache_gb`, 16) ingests each patient once, keeps its S^3 planes on the device
-and assembles every later batch there, so no file is opened after the first epoch (mmnn_sts_amd/data/cache.py); patients beyond the
-budget are read every epoch.  `--mask_margin_mm r` (`Data: mask_margin_mm: r`) dilates every mask by r mm on the device ahead of the
-ingest (exact Euclidean distance under the scan's voxel spacing, mmnn_sts_amd/data/ingest.py: mask_margin), so the volumes show the tumour
-and the rim around it; the dilated mask is 0 / 1.  `--inference --image_loc DIR --scan_space` also writes every class's
-attention map back on each scan's own voxel grid, with the scan's affine (att_map_class{k}_on_{t1,t2,scan}.nii.gz beside att_map.nii.gz).
-`--inference --images --occlusion` writes occlusion sensitivity maps (patient{i}_occ_map.npy: (K, D, H, W) signed deltas at the resolution of
-`--occlusion_stride`; occ_map_class{k}*.nii.gz with `--image_loc` / `--scan_space`), with or without `--no_gradcam`.  Without an image location synthetic patients are used; the tabular-only
-config reads them back from a csv it writes first (the "synthetic 32-feature x 64-patient csv" of BASELINE configs[0]).
-`--radiomics` trains on radiomic features: the csv of `--rad_loc` (column MRN, then the features), or, without it, the table extracted
-on the device from the patients under `--image_loc` into <output_path>/radiomics_features.csv (mmnn_sts_amd/radiomics.py; the config's
-`Radiomics: classes: [glrlm, gldm, ngtdm]` adds those texture classes' columns to it, `--mesh_shape` / `Radiomics: mesh_shape: true` the
-eight mesh-based shape columns, `--shell_mm 5,10` / `Radiomics: shell_mm: [5, 10]` the `shell-<r>-mm_*` columns of the tissue within r mm
-around the mask, `--log_sigma 1,3` / `Radiomics: log: {sigma: [1.0, 3.0]}` the `log-sigma-<sigma>-mm-3D_*` columns of the
-scan filtered by a Laplacian of Gaussian at those scales in mm; `--normalize` / `Radiomics: normalize` z-scores each scan first and
-`--resample_spacing 1,1,1` / `Radiomics: resample: {spacing: [1, 1, 1]}` brings scan and mask onto that spacing, both on the device and
-without a change of the columns); alone it is
-the standalone MLP over the radiomic columns, with `--images` the fusion model, with `--preop` / `--postop` too the clinical columns first.
-There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is upstream's device).
-With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
+What each flag beyond upstream's does is in its help text and in INTEGRATION.md.  `resolve_settings` checks the command line against the
+config once and `build_data_source` picks the datasets: patient directories (`--image_loc`), a radiomics table (`--radiomics`), a clinical
+csv, or synthetic patients.  There is no CPU compute path: every model runs on the MI355X through the HIP library (configs[0]'s "CPU" is
+upstream's device).  With WORLD_SIZE > 1 (torch.distributed.run) patients are sharded over the ranks and gradients SUM-all-reduced (RCCL).
 """
 import argparse
+import contextlib
 import logging
 import os
 import sys
+from dataclasses import dataclass
+from typing import Callable, Optional
 
 import numpy as np
 import torch
@@ -226,19 +206,55 @@ def to_device(x, device):
     return {k: v.to(device) for k, v in x.items()} if isinstance(x, dict) else x.to(device)
 
 
-def batch_collate(args):
-    """The loader's collate function: the NIfTI datasets' device ingest when `--image_loc` selected them, else `collate`."""
-    return getattr(args, "ingest_collate", None) or collate
+NO_DEVICE = "mmnn_sts_amd runs on the MI355X only (no CPU path)"
+DEFAULT_CACHE_GB = 16.0                      # a setting, not a measurement: about a twentieth of the card's 288 GB
+# the synthetic sets: their seeds (every rank draws its own training patients, at TRAIN_SEED + rank) and, for `--synthetic_patients n`,
+# their patient counts
+TRAIN_SEED, VAL_SEED, EVAL_SEED = 1000, 7, 99
 
 
-def report_empty_masks(args):
+def synthetic_counts(n, classification):
+    """(train, validation, evaluation) patients: the classification loop wants 4 of each at least, the survival loop 2 to validate on."""
+    return (max(4, n), max(4, n // 4), max(2, n // 4)) if classification else (n, max(2, n // 4), max(2, n // 4))
+
+
+@dataclass
+class DataSource:
+    """What the loops consume.  `ingest`: the device ingest of patient directories, which then is the loaders' collate function;
+    `cache`: the volume cache behind it, sized for `cache_patients`.  `evaluation` is what `--inference` runs over."""
+    train: Optional[torch.utils.data.Dataset] = None
+    val: Optional[torch.utils.data.Dataset] = None
+    evaluation: Optional[torch.utils.data.Dataset] = None
+    ingest: Optional[Callable] = None
+    train_tf: Optional[Callable] = None
+    val_tf: Optional[Callable] = None
+    cache: Optional[object] = None
+    cache_patients: int = 0
+
+    @property
+    def collate(self):
+        return self.ingest or collate
+
+
+def report_empty_masks(ingest):
     """`--image_loc`: patients whose mask left nothing of a scan (the ingest wrote zeros for them; upstream crashes there) are named once
     and the run ends non-zero.  Reads the extents of every batch collated since the last call: call it where the epoch has synchronised."""
-    ingest = getattr(args, "ingest_collate", None)
     empty = ingest.take_empty() if ingest is not None else []
     if empty:
         logger.error("empty mask: nothing of the scan is left after masking for patient uid(s) %s", ", ".join(str(u) for u in empty))
         raise SystemExit(f"empty mask for patient uid(s) {empty}: fix or remove these patients")
+
+
+def log_volume_cache(data, rank):
+    """`--cache_volumes`: one line per epoch -- what the cache holds, what it served in this epoch, and the files the datasets read in it."""
+    if data.cache is None:
+        return
+    from mmnn_sts_amd.data.ImageDatasets import ImageDataset
+    hits, misses, overflow = data.cache.table.take_counters()
+    files, ImageDataset.files_read = ImageDataset.files_read, 0
+    if rank == 0:
+        logger.info("volume cache: %d of %d patients cached, %.1f MB held; this epoch: %d hits, %d misses, %d overflow, %d files read",
+                    data.cache.table.n_filled, data.cache_patients, data.cache.bytes_held / 1e6, hits, misses, overflow, files)
 
 
 def split_uids(uids, args, seed):
@@ -250,121 +266,6 @@ def split_uids(uids, args, seed):
     order = np.random.default_rng(seed).permutation(len(uids))
     n_val = min(max(1, round(0.2 * len(uids))), len(uids) - 1)
     return sorted(uids[i] for i in order[n_val:]), sorted(uids[i] for i in order[:n_val])
-
-
-def nifti_datasets(parser, args, device, seed, rank, world):
-    """`--image_loc`: upstream's datasets (parser.getDatasets) over the local patient tree, cut into the train and validation uids; the
-    loaders' collate function becomes the device ingest."""
-    from mmnn_sts_amd.data.ImageDatasets import ImageDatasetByUIDs
-    from mmnn_sts_amd.data.ingest import SIZE, IngestCollate
-    full = parser.getDatasets(args, parser.getImagePath())
-    train_uids, val_uids = split_uids(full.uids, args, seed)
-    if getattr(args, "radiomics", False):
-        scale_radiomics(parser, args, train_uids, rank)
-    size = getattr(args, "image_size", None) or SIZE
-    by_uids, cached = ImageDatasetByUIDs, {}
-    if getattr(args, "cache_volumes", False):
-        # one cache per process: this rank's training shard and the validation set, which every rank evaluates
-        from mmnn_sts_amd.data.cache import CachedByUIDs, VolumeCache, capacity_for
-        channels = int(parser.config["ImageModel"]["in_channels"])
-        args.cache_patients = len(set(train_uids[rank::world]) | set(val_uids))
-        args.volume_cache = VolumeCache(device, channels, size, capacity_for(int(args.cache_gb * 2 ** 30), channels, size, args.cache_patients))
-        by_uids = lambda dataset, uids: CachedByUIDs(dataset, uids, args.volume_cache)
-        cached = {"cache": args.volume_cache}
-        if rank == 0:
-            logger.info("volume cache: room for %d of %d patients (%d x %d^3 fp32 each) in %g GB", args.volume_cache.capacity, args.cache_patients,
-                        channels, size, args.cache_gb)
-    if getattr(args, "mask_margin_mm", None) is not None:
-        cached["mask_margin_mm"] = args.mask_margin_mm
-    args.ingest_collate = IngestCollate(device, *parser.maskResample(), keep_workspaces=getattr(args, "scan_space", False), size=size, **cached)
-    return by_uids(full, train_uids[rank::world]), by_uids(full, val_uids)
-
-
-def check_cache_flags(a, data_cfg, use_nifti):
-    """`--cache_volumes` / `Data: cache` and `--cache_gb` / `Data: cache_gb`: sets a.cache_volumes and a.cache_gb (16 when not named)."""
-    a.cache_volumes = a.cache_volumes or bool(data_cfg.get("cache"))
-    gb = a.cache_gb if a.cache_gb is not None else data_cfg.get("cache_gb")
-    if gb is not None and not a.cache_volumes:
-        raise SystemExit("--cache_gb is the budget of the volume cache: it needs --cache_volumes")
-    if not a.cache_volumes:
-        return
-    if not use_nifti:
-        raise SystemExit("--cache_volumes keeps the ingested scans of patient directories on the device: it needs --image_loc")
-    if a.inference:
-        raise SystemExit("--cache_volumes saves the re-reading of patients in later epochs: --inference reads each patient once, run it without")
-    if a.lr_finder:
-        raise SystemExit("--cache_volumes caches ingested patient scans: --lr_finder runs on synthetic patients, run it without")
-    gb = DEFAULT_CACHE_GB if gb is None else gb
-    if isinstance(gb, bool) or not isinstance(gb, (int, float)) or not 0 < gb < float("inf"):
-        raise SystemExit(f"--cache_gb {gb!r} is not a positive number of GB")
-    a.cache_gb = float(gb)
-
-
-DEFAULT_CACHE_GB = 16.0                      # a setting, not a measurement: about a twentieth of the card's 288 GB
-
-
-def log_volume_cache(args, rank):
-    """`--cache_volumes`: one line per epoch -- what the cache holds, what it served in this epoch, and the files the datasets read in it."""
-    cache = getattr(args, "volume_cache", None)
-    if cache is None:
-        return
-    from mmnn_sts_amd.data.ImageDatasets import ImageDataset
-    hits, misses, overflow = cache.table.take_counters()
-    files, ImageDataset.files_read = ImageDataset.files_read, 0
-    if rank == 0:
-        logger.info("volume cache: %d of %d patients cached, %.1f MB held; this epoch: %d hits, %d misses, %d overflow, %d files read",
-                    cache.table.n_filled, args.cache_patients, cache.bytes_held / 1e6, hits, misses, overflow, files)
-
-
-def check_radiomics_flags(a, data_cfg):
-    """`--radiomics`: the csv of `--rad_loc` / `Data: rad_loc`, or an image tree to extract it from; the clinical csv holds the targets."""
-    if not data_cfg.get("rad_loc") and not data_cfg.get("image_loc"):
-        raise SystemExit("--radiomics needs --rad_loc (a csv of radiomic features with the column MRN) or --image_loc (patient directories "
-                         "to extract the features from)")
-    if not data_cfg.get("rad_loc") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("--radiomics without --rad_loc extracts the features in a single process: run the extraction once "
-                         "(python -m mmnn_sts_amd.radiomics) and pass its csv as --rad_loc")
-    missing = [k for k in (("data_loc",) if data_cfg.get("rad_loc") else ("data_loc", "key_loc")) if not data_cfg.get(k)]
-    if missing:
-        raise SystemExit("--radiomics needs " + " and ".join(f"--{k}" for k in missing) + " (the clinical csv with uid, event{i}, duration{i}"
-                         + ("" if data_cfg.get("rad_loc") else "; the patient key csv with the columns 'Anon MRN', 'MRN'") + ")")
-    if a.images and not data_cfg.get("image_loc"):
-        raise SystemExit("--radiomics with --images pairs each patient's features with their scans: it needs --image_loc")
-    if a.lr_finder:
-        raise SystemExit("--lr_finder runs on synthetic image patients: run it without --radiomics")
-
-
-def extract_radiomics_if_needed(parser, args):
-    """`--radiomics` without `--rad_loc`: every patient (and modality) of the image tree -> <output_path>/radiomics_features.csv on the
-    device, which then is the run's `rad_loc`."""
-    data = parser.config["Data"]
-    if data.get("rad_loc"):
-        return
-    from mmnn_sts_amd import radiomics
-    from mmnn_sts_amd.data.ImageDatasets import ImageDataset
-    if not torch.cuda.is_available():
-        raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
-    rc, classes, glszm = parser.radiomicsConfig(), parser.radiomicsClasses(), parser.radiomicsZones()
-    mesh = getattr(args, "mesh_shape", False) or parser.radiomicsMesh()
-    log = parser.radiomicsLog(getattr(args, "log_sigma", None), getattr(args, "log_bin_width", None))
-    normalize = parser.radiomicsNormalize(getattr(args, "normalize", False), getattr(args, "normalize_scale", None),
-                                          getattr(args, "normalize_outliers", None))
-    resample = parser.radiomicsResample(getattr(args, "resample_spacing", None))
-    shells = parser.radiomicsShell(getattr(args, "shell_mm", None))
-    paths = parser.getImagePath()
-    paths = paths if isinstance(paths, tuple) else (paths,)
-    sets = [ImageDataset(path, parser._data("key_loc"), parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi())
-            for path in paths]
-    threshold = (parser.config.get("Data") or {}).get("mask_threshold")
-    rows = radiomics.extract_modalities(sets, torch.device("cuda", 0), rc["bin_width"], rc["max_bins"],
-                                        None if threshold is None else float(threshold), classes=classes, glszm=glszm, mesh=mesh,
-                                        log_sigma=log["sigma"], log_bin_width=log["bin_width"], normalize=normalize, resample=resample,
-                                        **({"shell_mm": shells} if shells else {}))
-    os.makedirs(args.output_path, exist_ok=True)
-    out = os.path.join(args.output_path, "radiomics_features.csv")
-    radiomics.write_csv(out, rows)
-    logger.info("radiomic features of %d patients -> %s", len(rows), out)
-    data["rad_loc"] = out
 
 
 def scale_radiomics(parser, args, train_uids, rank):
@@ -386,23 +287,107 @@ def scale_radiomics(parser, args, train_uids, rank):
         ds.save_scaler(path)
 
 
-def radiomics_datasets(parser, args, seed, rank, world):
-    """`--radiomics` without `--images`: the predictor table (radiomic columns, behind the clinical ones with --preop / --postop) cut
-    into the train and validation uids."""
-    from mmnn_sts_amd.data.RadiomicsDatasets import TableByUIDs
-    full = parser.getDatasets(args)
-    train_uids, val_uids = split_uids(full.uids, args, seed)
-    known = set(full.uids)
-    train_uids, val_uids = [u for u in train_uids if u in known], [u for u in val_uids if u in known]
-    scale_radiomics(parser, args, train_uids, rank)
-    return TableByUIDs(full, train_uids[rank::world]), TableByUIDs(full, val_uids)
+def tree_data_source(data, parser, args, device, rank, world):
+    """`--image_loc`: upstream's datasets (parser.getDatasets) over the local patient tree, cut into the train and validation uids; the
+    loaders' collate function becomes the device ingest, behind a volume cache with `--cache_volumes`."""
+    from mmnn_sts_amd.data.ImageDatasets import ImageDatasetByUIDs
+    full = parser.getDatasets(args, parser.getImagePath())
+    train_uids, val_uids = split_uids(full.uids, args, args.seed)
+    if args.radiomics:
+        scale_radiomics(parser, args, train_uids, rank)
+    by_uids, extras = ImageDatasetByUIDs, {}
+    if args.cache_volumes:
+        # one cache per process: this rank's training shard and the validation set, which every rank evaluates
+        from mmnn_sts_amd.data.cache import CachedByUIDs, VolumeCache, capacity_for
+        data.cache_patients = len(set(train_uids[rank::world]) | set(val_uids))
+        data.cache = VolumeCache(device, args.in_channels, args.image_size,
+                                 capacity_for(int(args.cache_gb * 2 ** 30), args.in_channels, args.image_size, data.cache_patients))
+        by_uids = lambda dataset, uids: CachedByUIDs(dataset, uids, data.cache)
+        extras["cache"] = data.cache
+        if rank == 0:
+            logger.info("volume cache: room for %d of %d patients (%d x %d^3 fp32 each) in %g GB", data.cache.capacity, data.cache_patients,
+                        args.in_channels, args.image_size, args.cache_gb)
+    if args.mask_margin_mm is not None:
+        extras["mask_margin_mm"] = args.mask_margin_mm
+    # `getDatasets` above has left the tree's layout on the parser (`image_layout`), which `maskResample()`'s default threshold depends
+    # on (128 behind DICOM scans): the ingest is built behind it, here and nowhere else
+    from mmnn_sts_amd.data.ingest import IngestCollate
+    data.ingest = IngestCollate(device, *parser.maskResample(), keep_workspaces=args.scan_space, size=args.image_size, **extras)
+    data.train, data.val = by_uids(full, train_uids[rank::world]), by_uids(full, val_uids)
 
 
-def export_patient_nifti(args, uid, image, att, preds):
-    """Upstream's per-patient folder (main.py:829-845): attention_maps/_patient_<uid>/{t1image,t2image,att_map}.nii.gz + preds.txt.
-    The volumes are written at the extent they have: S^3 under `--image_size S`."""
+def build_data_source(args, parser, rank=0, world=1, device=None) -> DataSource:
+    """The datasets of the run, their collate function, the `--transforms` pipelines and the volume cache.  Only patient directories
+    (`--image_loc`) need `device`, for their ingest.  `--inference` evaluates the validation uids of a tree or table, `--data_loc`
+    (else the validation csv) of a clinical csv, and synthetic image patients of their own seed."""
+    data = DataSource()
+    if args.transforms:
+        from mmnn_sts_amd.transforms import pipelines
+        data.train_tf, data.val_tf = pipelines(args.image_size)
+    if args.radiomics and not args.images:
+        # the predictor table (radiomic columns, behind the clinical ones with --preop / --postop) cut into the train and validation uids
+        from mmnn_sts_amd.data.RadiomicsDatasets import TableByUIDs
+        full = parser.getDatasets(args)
+        known = set(full.uids)
+        train_uids, val_uids = ([u for u in uids if u in known] for uids in split_uids(full.uids, args, args.seed))
+        scale_radiomics(parser, args, train_uids, rank)
+        data.train, data.val = TableByUIDs(full, train_uids[rank::world]), TableByUIDs(full, val_uids)
+    elif not args.images:
+        # tabular-only: patients travel through a csv, as upstream's clinical datasets do (at the classification loop's counts)
+        predictors = parser.predictors(args)
+        os.makedirs(args.output_path, exist_ok=True)
+        n_train, n_val, _ = synthetic_counts(args.synthetic_patients, True)
+        train_csv = args.data_loc or write_synthetic_csv(os.path.join(args.output_path, f"synthetic_train_rank{rank}.csv"), n_train, predictors,
+                                                         TRAIN_SEED + rank)
+        val_csv = write_synthetic_csv(os.path.join(args.output_path, f"synthetic_val_rank{rank}.csv"), n_val, predictors, VAL_SEED)
+        data.train, data.val = ClinicalCsvDataset(train_csv, predictors), ClinicalCsvDataset(val_csv, predictors)
+        data.evaluation = ClinicalCsvDataset(args.data_loc or val_csv, predictors)        # --inference --data_loc x.csv evaluates THAT file
+    elif args.use_nifti:
+        tree_data_source(data, parser, args, device, rank, world)
+    elif args.data_loc:
+        raise SystemExit("clinical csv + image loaders need --image_loc (NIfTI patient directories) and --key_loc; run without --data_loc for synthetic patients")
+    else:
+        n_train, n_val, n_eval = synthetic_counts(args.synthetic_patients, args.classification)
+        n_clinical = len(parser.predictors(args))
+        patients = lambda n, seed: SyntheticPatients(n, args.in_channels, args.synthetic_size, n_clinical, args.multimodal, True, seed)
+        if args.inference:
+            data.evaluation = patients(n_eval, EVAL_SEED)
+        else:
+            data.train, data.val = patients(n_train, TRAIN_SEED + rank), patients(n_val, VAL_SEED)
+    if data.evaluation is None:
+        data.evaluation = data.val
+    return data
+
+
+def extract_radiomics_if_needed(parser, args):
+    """`--radiomics` without `--rad_loc`: every patient (and modality) of the image tree -> <output_path>/radiomics_features.csv on the
+    device, which then is the run's `rad_loc`."""
+    data = parser.config["Data"]
+    if data.get("rad_loc"):
+        return
+    from mmnn_sts_amd import radiomics
+    if not torch.cuda.is_available():
+        raise SystemExit(NO_DEVICE)
+    settings = parser.radiomicsExtraction(args)
+    paths = parser.getImagePath()
+    sets = radiomics.tree_datasets(parser, paths if isinstance(paths, tuple) else (paths,), parser._data("key_loc"))
+    rows = radiomics.extract_modalities(sets, torch.device("cuda", 0), **settings)
+    os.makedirs(args.output_path, exist_ok=True)
+    out = os.path.join(args.output_path, "radiomics_features.csv")
+    radiomics.write_csv(out, rows)
+    logger.info("radiomic features of %d patients -> %s", len(rows), out)
+    data["rad_loc"] = out
+
+
+def patient_folder(output_path, uid):
+    """Upstream's per-patient folder (main.py:829-845), which the three exporters below write into."""
+    return os.path.join(output_path, "attention_maps", f"_patient_{uid}")
+
+
+def export_patient_nifti(d, image, att, preds):
+    """Into the patient's folder `d`: {t1image,t2image,att_map}.nii.gz + preds.txt (main.py:829-845).  The volumes are written at the
+    extent they have: S^3 under `--image_size S`."""
     from mmnn_sts_amd.data import nifti
-    d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
     os.makedirs(d, exist_ok=True)
     for c, name in zip(range(image.shape[0]), ("t1image", "t2image")):
         nifti.write(os.path.join(d, name + ".nii.gz"), image[c].cpu().numpy().astype(np.float32))
@@ -411,25 +396,23 @@ def export_patient_nifti(args, uid, image, att, preds):
         f.write("".join(f"{float(v)!r}\n" for v in preds.reshape(-1)))
 
 
-def export_occlusion_nifti(args, uid, maps):
-    """`--occlusion --image_loc`: occ_map_class{k}.nii.gz per output in upstream's per-patient folder, beside att_map.nii.gz."""
+def export_occlusion_nifti(d, maps):
+    """`--occlusion --image_loc`: occ_map_class{k}.nii.gz per output in the patient's folder `d`, beside att_map.nii.gz."""
     from mmnn_sts_amd.data import nifti
-    d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
     os.makedirs(d, exist_ok=True)
     maps = maps.cpu().numpy().astype(np.float32)
     for k in range(maps.shape[0]):
         nifti.write(os.path.join(d, f"occ_map_class{k}.nii.gz"), maps[k])
 
 
-def export_scan_space_maps(args, uid, maps, volumes, prefix="att_map"):
-    """`--scan_space`: every class's attention map on the voxel grid of every scan of the patient, into the patient's folder as
+def export_scan_space_maps(d, maps, volumes, prefix="att_map"):
+    """`--scan_space`: every class's attention map on the voxel grid of every scan of the patient, into the patient's folder `d` as
     att_map_class{k}_on_{t1,t2}.nii.gz (att_map_class{k}_on_scan.nii.gz for a single modality; `prefix` replaces "att_map": the
     occlusion maps are written as occ_map_class{k}_on_*), written with the scan's affine so that a
     viewer lays it over the scan.  `maps`: (classes, S, S, S) on the device, in the model's space (S: `--image_size`, 64 by default); `volumes`: the patient's
     `KeptVolume` per modality.  The ingest's own kept slices are inverted on the device (`maps_to_scan`); dropped slices are 0."""
     from mmnn_sts_amd.data import nifti
     from mmnn_sts_amd.data.ingest import maps_to_scan
-    d = os.path.join(args.output_path, "attention_maps", f"_patient_{uid}")
     os.makedirs(d, exist_ok=True)
     names = ("t1", "t2") if len(volumes) == 2 else ("scan",)
     for name, vol in zip(names, volumes):
@@ -448,10 +431,34 @@ def apply_transforms(x, tf):
     return tf(x)
 
 
+def device_batches(batches, device, tf, targets=2):
+    """Each (input, events, durations) of `batches` with the input on the device and through this phase's transforms `tf`, and the first
+    `targets` of the other two on the device as well (the classification loops read the events alone; inference keeps both on the host)."""
+    for x, ev, du in batches:
+        x = to_device(x, device)
+        if targets >= 1:
+            ev = ev.to(device)
+        if targets >= 2:
+            du = du.to(device)
+        yield apply_transforms(x, tf), ev, du
+
+
+def end_of_epoch(data, rank, blender=None, blender_inputs=None):
+    """Where an epoch has synchronised: the empty masks it met, the cache's line and, when `blender` is given (its update is due), the
+    new head weights from `blender_inputs()`."""
+    report_empty_masks(data.ingest)
+    log_volume_cache(data, rank)
+    if blender is not None:
+        blender.updateWeights(*blender_inputs())
+        if rank == 0:
+            logger.info('Completed updating gradient blender weights - new weights : {}'.format(blender.weights))
+
+
 # ---- survival (main.py:385-601) ----------------------------------------------------------------------------------------------
-def train_survival(model, train_ds, val_ds, args, device, rank, world):
-    loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, collate_fn=batch_collate(args), drop_last=len(train_ds) > args.batch_size)
-    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, collate_fn=batch_collate(args), drop_last=len(val_ds) > args.batch_size)
+def train_survival(model, data, args, device, rank, world):
+    train_ds, val_ds = data.train, data.val
+    loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, collate_fn=data.collate, drop_last=len(train_ds) > args.batch_size)
+    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, collate_fn=data.collate, drop_last=len(val_ds) > args.batch_size)
     model = model.to(device)
     D.broadcast_parameters(model)
     for m in model.modules():                 # this loop only changes weights through FusedSGD: repack them once per optimizer step,
@@ -470,9 +477,7 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
     for epoch in range(args.epochs):
         model.train()
         losses, c_pred, c_ev, c_du = [], [], [], []
-        for i, (x, ev, du) in enumerate(loader):
-            x, ev, du = to_device(x, device), ev.to(device), du.to(device)
-            x = apply_transforms(x, getattr(args, "train_tf", None))
+        for i, (x, ev, du) in enumerate(device_batches(loader, device, data.train_tf)):
             out = model(x)
             loss = blender.computeLoss(out, ev, du)[0] if args.blend else surv_criterion(CoxPH, out, ev, du, device)
             boundary = is_step_boundary(i, len(loader), interval)
@@ -493,9 +498,7 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
         model.eval()
         y_pred, y_ev, y_du, sel = [], [], [], None
         with torch.no_grad():
-            for x, ev, du in val_loader:
-                x, ev, du = to_device(x, device), ev.to(device), du.to(device)
-                x = apply_transforms(x, getattr(args, "val_tf", None))
+            for x, ev, du in device_batches(val_loader, device, data.val_tf):
                 p = model(x)
                 if args.blend:
                     _, sel = blender.computeLoss(p, ev, du)
@@ -514,28 +517,24 @@ def train_survival(model, train_ds, val_ds, args, device, rank, world):
                 os.makedirs(args.output_path, exist_ok=True)
                 torch.save(model.state_dict(), os.path.join(args.output_path, 'best_surv_model.pth'))
                 logger.info('saved new best metric model')
-        report_empty_masks(args)
-        log_volume_cache(args, rank)
-        if args.blend and blender_update_due(epoch, args.blend_update_interval):
-            # every rank evaluates the same epoch-level losses: its own training patients are gathered from all ranks (the
-            # validation set is identical on every rank), so one global weight vector results, as on a single GPU
-            blender.updateWeights(gather_rows(cp, 1, world), gather_rows(ce, 0, world), gather_rows(cd, 0, world), yp, ye, yd)
-            if rank == 0:
-                logger.info('Completed updating gradient blender weights - new weights : {}'.format(blender.weights))
+        # every rank evaluates the same epoch-level losses: its own training patients are gathered from all ranks (the
+        # validation set is identical on every rank), so one global weight vector results, as on a single GPU
+        end_of_epoch(data, rank, blender if args.blend and blender_update_due(epoch, args.blend_update_interval) else None,
+                     lambda: (gather_rows(cp, 1, world), gather_rows(ce, 0, world), gather_rows(cd, 0, world), yp, ye, yd))
     if args.blend and rank == 0:
         blender.saveHistory()
     return model
 
 
 # ---- classification (main.py:125-327) ----------------------------------------------------------------------------------------
-def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1):
+def train_classification(model, data, args, device, rank=0, world=1):
     """Binary classification of the event flags: pos-weighted BCE on logits (:147-153), SGD-Nesterov + OneCycleLR stepped every
     batch (:207-215), F1 per class (:217-233,:289-300), best mean validation F1 -> model.pth (:301-306); with --blend the
     GradientBlender's classification branch (:156,:210,:264,:311-314).  With `world` > 1 every rank trains on its own patients:
     identical initial weights, gradients SUM-all-reduced before every optimizer step, checkpoints written by rank 0 only."""
-    bs = max(2, args.batch_size)
-    loader = torch.utils.data.DataLoader(train_ds, batch_size=bs, shuffle=True, collate_fn=batch_collate(args), drop_last=len(train_ds) > bs)
-    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=bs, shuffle=False, collate_fn=batch_collate(args))
+    train_ds, val_ds, bs = data.train, data.val, max(2, args.batch_size)
+    loader = torch.utils.data.DataLoader(train_ds, batch_size=bs, shuffle=True, collate_fn=data.collate, drop_last=len(train_ds) > bs)
+    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=bs, shuffle=False, collate_fn=data.collate)
     model = model.to(device)
     D.broadcast_parameters(model)
     freqs = torch.tensor(args.class_frequencies, dtype=torch.float32)
@@ -551,9 +550,7 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
         epoch_loss = torch.zeros((), device=device)
         tps = fps = fns = 0
         train_preds, train_gt, val_preds, val_gt = [], [], [], []
-        for x, labels, _ in loader:
-            x, labels = to_device(x, device), labels.to(device)
-            x = apply_transforms(x, getattr(args, "train_tf", None))
+        for x, labels, _ in device_batches(loader, device, data.train_tf, targets=1):
             opt.zero_grad()
             outputs = model(x)
             loss = blender.computeLoss(outputs, labels.float()) if args.blend else criterion(train_loss_function, outputs, labels.float(), device)
@@ -575,9 +572,7 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
         test_loss = 0.0
         y_pred, y = [], []
         with torch.no_grad():
-            for x, labels, _ in val_loader:
-                x, labels = to_device(x, device), labels.to(device)
-                x = apply_transforms(x, getattr(args, "val_tf", None))
+            for x, labels, _ in device_batches(val_loader, device, data.val_tf, targets=1):
                 p = model(x)
                 l = blender.computeLoss(p, labels.float(), no_reduce=True) if args.blend else criterion(loss_function, p, labels.float(), device)
                 test_loss += float(l.sum())
@@ -598,50 +593,44 @@ def train_classification(model, train_ds, val_ds, args, device, rank=0, world=1)
         if rank == 0:
             logger.info(f"epoch {epoch + 1}/{args.epochs} average loss: {float(epoch_loss) / len(train_ds):.4f} train f1 {train_f1:.4f} "
                         f"validation loss {test_loss / len(val_ds):.4f} current f1: {mean_f1:.4f} best f1: {best_metric:.4f} at epoch: {best_epoch}")
-        report_empty_masks(args)
-        log_volume_cache(args, rank)
-        if args.blend and blender_update_due(epoch, args.blend_update_interval):
-            # as in the survival loop: the training patients of all ranks (the validation set is the same everywhere) -> one weight vector
-            blender.updateWeights(gather_rows(torch.cat(train_preds, dim=1), 1, world), gather_rows(torch.cat(train_gt).float(), 0, world),
-                                  torch.cat(val_preds, dim=1), torch.cat(val_gt).float())
-            if rank == 0:
-                logger.info('Completed updating gradient blender weights - new weights : {}'.format(blender.weights))
+        # as in the survival loop: the training patients of all ranks (the validation set is the same everywhere) -> one weight vector
+        end_of_epoch(data, rank, blender if args.blend and blender_update_due(epoch, args.blend_update_interval) else None,
+                     lambda: (gather_rows(torch.cat(train_preds, dim=1), 1, world), gather_rows(torch.cat(train_gt).float(), 0, world),
+                              torch.cat(val_preds, dim=1), torch.cat(val_gt).float()))
     if rank == 0:
         torch.save(model.state_dict(), os.path.join(args.output_path, 'final_model.pth'))
     return model
 
 
-def inference_survival(model, ds, args, device):
+def inference_survival(model, data, args, device):
     """main.py:750-887: batch-1 loop, Grad-CAM maps (saved as .npy; with `--image_loc` also upstream's per-patient NIfTI folder) of
     fusion and image-only models (main.py:1013-1014: add_gradcam(model, multimodal=...)), C-index."""
     model = model.to(device).eval()
-    if args.bootstrap:
-        args.no_gradcam = True                       # main.py:774-777: no attention maps, no prediction dump while bootstrapping
+    ds, on_tree = data.evaluation, data.ingest is not None
     cam = add_gradcam(model, multimodal=args.multimodal) if (args.images and not args.no_gradcam) else None
     occ = None
-    if getattr(args, "occlusion", False):
+    if args.occlusion:
         occ = add_occlusion(model, multimodal=args.multimodal, window=args.occlusion_window, stride=args.occlusion_stride,
                             batch=args.occlusion_batch)
     preds, evs, dus = [], [], []
     os.makedirs(os.path.join(args.output_path, "attention_maps"), exist_ok=True)
-    for i in range(len(ds)):
-        x, ev, du = batch_collate(args)([ds[i]])
-        x = apply_transforms(to_device(x, device), getattr(args, "val_tf", None))
+    for i, (x, ev, du) in enumerate(device_batches((data.collate([ds[j]]) for j in range(len(ds))), device, data.val_tf, targets=0)):
+        folder = patient_folder(args.output_path, ds.uids[i]) if on_tree else None
         with torch.no_grad():
             if cam is not None:
                 p, maps = cam(x)
                 # fusion: the list of per-class maps, the first saved; image-only: (1, 1, D, H, W), the sample's map saved
                 att = maps[0] if args.multimodal else maps[0, 0]
                 np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_att_map.npy"), att.cpu().numpy())
-                if getattr(args, "ingest_collate", None) is not None:
-                    export_patient_nifti(args, ds.uids[i], (x["image"] if args.multimodal else x)[0], att, p)
-                if getattr(args, "scan_space", False):
+                if on_tree:
+                    export_patient_nifti(folder, (x["image"] if args.multimodal else x)[0], att, p)
+                if args.scan_space:
                     # the maps live in the space of the ingest's S^3 planes: `--transforms` puts only the validation transforms
                     # between the two, and those are spatially the identity at S^3 (intensity stages and a Resize to the size the
                     # planes already have: both take `--image_size`), so the map needs no further correction.  Fusion: one map per class; image-only: the
                     # sample's one map, class 0
                     stack = torch.stack(list(maps)) if args.multimodal else maps[0]
-                    export_scan_space_maps(args, ds.uids[i], stack.contiguous(), args.ingest_collate.last_volumes[0])
+                    export_scan_space_maps(folder, stack.contiguous(), data.ingest.last_volumes[0])
             elif occ is None:
                 p = model(x)
             if occ is not None:
@@ -650,13 +639,13 @@ def inference_survival(model, ds, args, device):
                 if cam is None:
                     p = outs
                 np.save(os.path.join(args.output_path, "attention_maps", f"patient{i}_occ_map.npy"), occ_maps.cpu().numpy())
-                if getattr(args, "ingest_collate", None) is not None:
-                    export_occlusion_nifti(args, ds.uids[i], occ_maps)
-                if getattr(args, "scan_space", False):
-                    export_scan_space_maps(args, ds.uids[i], occ_maps, args.ingest_collate.last_volumes[0], prefix="occ_map")
+                if on_tree:
+                    export_occlusion_nifti(folder, occ_maps)
+                if args.scan_space:
+                    export_scan_space_maps(folder, occ_maps, data.ingest.last_volumes[0], prefix="occ_map")
         preds.append(p.cpu()); evs.append(ev); dus.append(du)
     p, e, d = torch.cat(preds).numpy(), torch.cat(evs).numpy(), torch.cat(dus).numpy()
-    report_empty_masks(args)
+    report_empty_masks(data.ingest)
     if args.bootstrap:
         means, stds, used = bootstrap_c_indices(p, e, d)
         logger.info('Mean c indices: {}'.format(means))
@@ -677,18 +666,16 @@ class SyntheticImagePatients(SyntheticPatients):
         self.uids = list(range(n))
 
 
-def run_lr_finder(a, cfg, seed):
+def run_lr_finder(a):
     """`--lr_finder` (upstream main.py:1009-1010 -> utils/find_lr.py): the range test of a fresh 3-class MONAI-schema DenseNet121 on
     synthetic patients, then lr_finder.csv (lr,loss per recorded iteration), lr_finder.png and the suggested lr."""
     from mmnn_sts_amd.utils.find_lr import find_lr
     if not torch.cuda.is_available():
-        raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
+        raise SystemExit(NO_DEVICE)
     torch.cuda.set_device(0)
-    inch = int(cfg["ImageModel"]["in_channels"])
-    ds = SyntheticImagePatients(max(2, a.synthetic_patients), inch, a.synthetic_size, 1000)
-    a.seed, a.in_channels = seed, inch
+    ds = SyntheticImagePatients(max(2, a.synthetic_patients), a.in_channels, a.synthetic_size, TRAIN_SEED)
     os.makedirs(a.output_path, exist_ok=True)
-    finder, suggestion = find_lr(a, ds)
+    finder, suggestion = find_lr(a, ds)                  # (reads a.seed, a.in_channels, a.batch_size, a.output_path)
     with open(os.path.join(a.output_path, "lr_finder.csv"), "w") as f:
         f.write("lr,loss\n")
         for lr, loss in zip(finder.history["lr"], finder.history["loss"]):
@@ -738,19 +725,8 @@ def build_arg_parser():
     ap.add_argument("--occlusion", action="store_true",
                     help="with --inference --images: occlusion sensitivity maps per patient (attention_maps/patient{i}_occ_map.npy, "
                          "(K, D, H, W) signed deltas; with --image_loc occ_map_class{k}.nii.gz, with --scan_space also on the scans' grids)")
-    ap.add_argument("--mesh_shape", action="store_true",
-                    help="with --radiomics and no --rad_loc: append the 8 mesh-based shape columns (mesh volume, surface area, sphericity, "
-                         "the diameters) to the extracted table; also switched on by the config's `Radiomics: mesh_shape: true`")
-    ap.add_argument("--log_sigma", type=str, default=None,
-                    help="with --radiomics and no --rad_loc: Laplacian-of-Gaussian scales in mm, comma-separated (1,3): append the "
-                         "log-sigma-<sigma>-mm-3D_* columns of the filtered scans; overrides the config's `Radiomics: log: sigma`")
-    ap.add_argument("--log_bin_width", type=float, default=None,
-                    help="bin width of the filtered images; overrides `Radiomics: log: bin_width` (default: `Radiomics: bin_width`)")
-    from mmnn_sts_amd.radiomics import add_pre_step_arguments
-    add_pre_step_arguments(ap)
-    ap.add_argument("--shell_mm", type=str, default=None,
-                    help="with --radiomics and no --rad_loc: widths in mm of the peritumoural shells, comma-separated (5,10): append the "
-                         "shell-<r>-mm_* columns of the tissue within r mm around the mask; overrides the config's `Radiomics: shell_mm`")
+    from mmnn_sts_amd.radiomics import add_extraction_arguments
+    add_extraction_arguments(ap, "with --radiomics and no --rad_loc: ")
     ap.add_argument("--mask_margin_mm", type=float, default=None,
                     help="with --image_loc: dilate every mask by this many mm on the device ahead of the scan ingest, so the volumes show the "
                          "tumour and the rim around it; overrides the config's `Data: mask_margin_mm` (the radiomics ROI is not changed)")
@@ -763,8 +739,21 @@ def build_arg_parser():
     return ap
 
 
-def main(argv=None):
-    a = build_arg_parser().parse_args(argv)
+@contextlib.contextmanager
+def configuration_errors_exit():
+    """A setting the config layer refuses ends the command line with its message."""
+    try:
+        yield
+    except ConfigurationError as e:
+        raise SystemExit(str(e))
+
+
+def resolve_settings(a, parser):
+    """Every check of the command line against itself and the config, in the one order that decides which message a user sees, and every
+    setting derived from the two: `a` comes back as the record of the run, which nothing later assigns to.  Beyond the flags it holds
+    `use_nifti` (the run reads patient directories), `multimodal`, `seed`, `in_channels`, `batch_size`, `momentum`, `weight_decay` and
+    `class_frequencies`; `image_size`, `synthetic_size`, `mask_margin_mm`, `cache_volumes`, `cache_gb`, `blend` and `no_gradcam` hold
+    what the run uses.  Reads the config (`parser.parseConfig`) and lays the location flags over its `Data:` section."""
     a.images = a.images or str_to_bool(a.use_images)
     a.classification = a.classification or str_to_bool(a.classification_task)
     a.inference = a.inference or str_to_bool(a.inference_task)
@@ -795,26 +784,52 @@ def main(argv=None):
     if a.transforms and not a.images:
         raise SystemExit("--transforms acts on image volumes: it needs --images")
 
-    parser = Parser(a.config)
     cfg = parser.parseConfig()
     data_cfg = parser.applyDataFlags(a)
-    if a.radiomics:
-        check_radiomics_flags(a, data_cfg)
+    if a.radiomics:             # the csv of --rad_loc / `Data: rad_loc`, or an image tree to extract it from; the clinical csv holds the targets
+        if not data_cfg.get("rad_loc") and not data_cfg.get("image_loc"):
+            raise SystemExit("--radiomics needs --rad_loc (a csv of radiomic features with the column MRN) or --image_loc (patient directories "
+                             "to extract the features from)")
+        if not data_cfg.get("rad_loc") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--radiomics without --rad_loc extracts the features in a single process: run the extraction once "
+                             "(python -m mmnn_sts_amd.radiomics) and pass its csv as --rad_loc")
+        missing = [k for k in (("data_loc",) if data_cfg.get("rad_loc") else ("data_loc", "key_loc")) if not data_cfg.get(k)]
+        if missing:
+            raise SystemExit("--radiomics needs " + " and ".join(f"--{k}" for k in missing) + " (the clinical csv with uid, event{i}, duration{i}"
+                             + ("" if data_cfg.get("rad_loc") else "; the patient key csv with the columns 'Anon MRN', 'MRN'") + ")")
+        if a.images and not data_cfg.get("image_loc"):
+            raise SystemExit("--radiomics with --images pairs each patient's features with their scans: it needs --image_loc")
+        if a.lr_finder:
+            raise SystemExit("--lr_finder runs on synthetic image patients: run it without --radiomics")
     # (--radiomics without --images reads --image_loc only to extract its features from)
-    use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images) and (a.images or not a.radiomics)
-    check_cache_flags(a, data_cfg, use_nifti)
-    try:
+    a.use_nifti = bool(data_cfg.get("image_loc")) and (bool(a.image_loc) or a.images) and (a.images or not a.radiomics)
+    # --cache_volumes / `Data: cache` and its budget --cache_gb / `Data: cache_gb` (16 when not named)
+    a.cache_volumes = a.cache_volumes or bool(data_cfg.get("cache"))
+    gb = a.cache_gb if a.cache_gb is not None else data_cfg.get("cache_gb")
+    if gb is not None and not a.cache_volumes:
+        raise SystemExit("--cache_gb is the budget of the volume cache: it needs --cache_volumes")
+    if a.cache_volumes:
+        if not a.use_nifti:
+            raise SystemExit("--cache_volumes keeps the ingested scans of patient directories on the device: it needs --image_loc")
+        if a.inference:
+            raise SystemExit("--cache_volumes saves the re-reading of patients in later epochs: --inference reads each patient once, run it without")
+        if a.lr_finder:
+            raise SystemExit("--cache_volumes caches ingested patient scans: --lr_finder runs on synthetic patients, run it without")
+        gb = DEFAULT_CACHE_GB if gb is None else gb
+        if isinstance(gb, bool) or not isinstance(gb, (int, float)) or not 0 < gb < float("inf"):
+            raise SystemExit(f"--cache_gb {gb!r} is not a positive number of GB")
+        a.cache_gb = float(gb)
+    with configuration_errors_exit():
         a.mask_margin_mm = parser.maskMargin(a.mask_margin_mm)
-        shell_flag, a.shell_mm = a.shell_mm is not None, parser.radiomicsShell(a.shell_mm)
-    except ConfigurationError as e:
-        raise SystemExit(str(e))
-    if a.mask_margin_mm is not None and not use_nifti:
+        parser.radiomicsShell(a.shell_mm)               # (refused here; `Parser.radiomicsExtraction` resolves the widths for the extraction)
+    if a.mask_margin_mm is not None and not a.use_nifti:
         raise SystemExit("--mask_margin_mm / `Data: mask_margin_mm` widens the masks of patient directories: it needs --image_loc (synthetic "
                          "patients have no mask)")
-    if shell_flag and not (a.radiomics and not data_cfg.get("rad_loc")):
+    if a.shell_mm is not None and not (a.radiomics and not data_cfg.get("rad_loc")):
         raise SystemExit("--shell_mm adds columns to the table extracted on the device: it needs --radiomics and no "
                          "--rad_loc")
-    if use_nifti:
+    a.in_channels = int(cfg["ImageModel"]["in_channels"])
+    if a.use_nifti:
         if not a.images:
             raise SystemExit("--image_loc points at NIfTI patient directories: it needs --images")
         missing = [k for k in ("key_loc", "data_loc") if not data_cfg.get(k)]
@@ -824,9 +839,9 @@ def main(argv=None):
         if a.lr_finder:
             raise SystemExit("--lr_finder runs on synthetic patients: run it without --image_loc")
         n_mod = 2 if cfg["ImageModel"]["modality"].lower().startswith("t1t2") else 1
-        if int(cfg["ImageModel"]["in_channels"]) != n_mod:
+        if a.in_channels != n_mod:
             raise SystemExit(f"ImageModel modality {cfg['ImageModel']['modality']} yields {n_mod} channel(s) per patient, in_channels is {cfg['ImageModel']['in_channels']}")
-    if a.scan_space and not (a.inference and use_nifti and a.images and not a.no_gradcam and not a.bootstrap):
+    if a.scan_space and not (a.inference and a.use_nifti and a.images and not a.no_gradcam and not a.bootstrap):
         raise SystemExit("--scan_space lays the Grad-CAM attention maps over the patients' scans: it needs --inference, --image_loc (NIfTI "
                          "patient directories) and Grad-CAM on (--images, neither --no_gradcam nor --bootstrap)")
     # the extent S of the image volumes: named by --image_size / `Data: size`, else 64 for the ingest and the Resize (and
@@ -835,25 +850,28 @@ def main(argv=None):
     if sized and not a.images:
         raise SystemExit("--image_size / `Data: size` is the extent of the image volumes: it needs --images")
     if a.images:
-        try:
+        with configuration_errors_exit():
             a.image_size = parser.imageSize(a.image_size)
-        except ConfigurationError as e:
-            raise SystemExit(str(e))
-        if sized and not use_nifti:
+        if sized and not a.use_nifti:
             a.synthetic_size = a.image_size
     hp = cfg.get("Hyperparameters", {})
     a.multimodal = a.images and (a.preop or a.postop or a.radiomics)
     a.blend = a.blend and a.multimodal
+    a.no_gradcam = a.no_gradcam or a.bootstrap      # main.py:774-777: no attention maps, no prediction dump while bootstrapping
     a.batch_size = int(hp.get("train_batch_size", 2)) if a.config else 2
     a.momentum, a.weight_decay = float(hp.get("momentum", 0.9)), float(hp.get("weight_decay", 1e-4))
     a.class_frequencies = list(hp.get("class_frequencies", [0.4] * NUM_CLASSES))     # CLASS_FREQUENCIES is undefined upstream (Q1)
-    torch.manual_seed(int(hp.get("seed", 42)))
+    a.seed = int(hp.get("seed", 42))
+    return a
+
+
+def main(argv=None):
+    a = build_arg_parser().parse_args(argv)
+    parser = Parser(a.config)
+    resolve_settings(a, parser)
+    torch.manual_seed(a.seed)
     if a.lr_finder:
-        return run_lr_finder(a, cfg, int(hp.get("seed", 42)))
-    a.train_tf = a.val_tf = None
-    if a.transforms:
-        from mmnn_sts_amd.transforms import pipelines
-        a.train_tf, a.val_tf = pipelines(a.image_size)
+        return run_lr_finder(a)
     if a.radiomics:
         extract_radiomics_if_needed(parser, a)
     model = parser.getModel(a)
@@ -861,38 +879,19 @@ def main(argv=None):
         model.blend = a.blend
     rank, world, local = D.init_from_env(os.environ.get("MMNN_DIST_BACKEND", "nccl"))    # "nccl" = RCCL; gloo only for rehearsals on one card
     if not torch.cuda.is_available():
-        raise SystemExit("mmnn_sts_amd runs on the MI355X only (no CPU path)")
+        raise SystemExit(NO_DEVICE)
     local = local % max(1, torch.cuda.device_count())            # (gloo rehearsals: several ranks share a card)
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     if a.weights:
         model = loadWeights(model, a.weights, "cpu")
-    predictors = parser.predictors(a)
-    inch = cfg["ImageModel"]["in_channels"]
-    mk = lambda n, seed: SyntheticPatients(n, inch, a.synthetic_size, len(predictors), a.multimodal, a.images, seed)
-    if a.radiomics and not a.images:
-        rad_train, rad_val = radiomics_datasets(parser, a, int(hp.get("seed", 42)), rank, world)
-        mk = lambda n, s: rad_train if s >= 1000 else rad_val
-    elif not a.images:
-        # tabular-only: patients travel through a csv, as upstream's clinical datasets do
-        os.makedirs(a.output_path, exist_ok=True)
-        n_train, n_val = max(4, a.synthetic_patients), max(4, a.synthetic_patients // 4)
-        train_csv = a.data_loc or write_synthetic_csv(os.path.join(a.output_path, f"synthetic_train_rank{rank}.csv"), n_train, predictors, 1000 + rank)
-        val_csv = write_synthetic_csv(os.path.join(a.output_path, f"synthetic_val_rank{rank}.csv"), n_val, predictors, 7)
-        eval_csv = a.data_loc or val_csv        # --inference --data_loc x.csv evaluates THAT file
-        mk = lambda n, seed: ClinicalCsvDataset(train_csv if seed >= 1000 else (eval_csv if seed == 99 else val_csv), predictors)
-    elif use_nifti:
-        seed = int(hp.get("seed", 42))
-        nifti_train, nifti_val = nifti_datasets(parser, a, device, seed, rank, world)
-        mk = lambda n, s: nifti_train if s >= 1000 else nifti_val
-    elif a.data_loc:
-        raise SystemExit("clinical csv + image loaders need --image_loc (NIfTI patient directories) and --key_loc; run without --data_loc for synthetic patients")
+    data = build_data_source(a, parser, rank, world, device)
     if a.inference:
-        inference_survival(model, mk(max(2, a.synthetic_patients // 4), 99), a, device)
+        inference_survival(model, data, a, device)
     elif a.survival:
-        train_survival(model, mk(a.synthetic_patients, 1000 + rank), mk(max(2, a.synthetic_patients // 4), 7), a, device, rank, world)
+        train_survival(model, data, a, device, rank, world)
     else:
-        train_classification(model, mk(max(4, a.synthetic_patients), 1000 + rank), mk(max(4, a.synthetic_patients // 4), 7), a, device, rank, world)
+        train_classification(model, data, a, device, rank, world)
     if world > 1:
         torch.distributed.destroy_process_group()
 

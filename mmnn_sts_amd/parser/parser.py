@@ -56,16 +56,16 @@ class Parser:
         if 'NUM_PREDICTORS' in cm:
             return [f"predictor{i}" for i in range(int(cm['NUM_PREDICTORS']))]
         p = list(cm['PRE_OP_PREDICTORS'])
-        if getattr(args, 'postop', False):
+        if args.postop:
             p += list(cm.get('POST_OP_PREDICTORS', []))
         return p
 
     def predictors(self, args):
         """The columns of the tabular input: the clinical predictors; with --radiomics the feature columns of the radiomics csv -- alone,
         or behind the clinical ones when --preop / --postop is given too."""
-        if not getattr(args, 'radiomics', False):
+        if not args.radiomics:
             return self.clinicalPredictors(args)
-        clinical = self.clinicalPredictors(args) if (getattr(args, 'preop', False) or getattr(args, 'postop', False)) else []
+        clinical = self.clinicalPredictors(args) if (args.preop or args.postop) else []
         return clinical + self.radiomicsColumns()
 
     def radiomicsConfig(self):
@@ -162,6 +162,25 @@ class Parser:
         if shell_mm is None and isinstance(value, str):
             raise ConfigurationError('Radiomics.shell_mm must be a list of positive finite numbers (mm), got {!r}'.format(value))
         return shell_widths(shell_mm if shell_mm is not None else value)
+
+    def radiomicsExtraction(self, args):
+        """What the extraction of a radiomics table is run with -> the keyword arguments of `radiomics.extract_modalities` behind its
+        datasets and device: the two bin settings, the mask threshold (`Data: mask_threshold`; None: each scan's default) and the
+        switches of `radiomics.extract`.  `args`: the flags of `radiomics.add_extraction_arguments`, which go before the config's
+        `Radiomics:` section; `classes` / `glszm` are read when the command line has them (the tool's alone)."""
+        from ..radiomics import texture_classes
+        rc = self.radiomicsConfig()
+        classes = texture_classes(args.classes) if getattr(args, 'classes', None) is not None else self.radiomicsClasses()
+        glszm = getattr(args, 'glszm', False) or self.radiomicsZones()
+        mesh = args.mesh_shape or self.radiomicsMesh()
+        log = self.radiomicsLog(args.log_sigma, args.log_bin_width)
+        normalize = self.radiomicsNormalize(args.normalize, args.normalize_scale, args.normalize_outliers)
+        resample = self.radiomicsResample(args.resample_spacing)
+        shells = self.radiomicsShell(args.shell_mm)
+        threshold = (self.config.get('Data') or {}).get('mask_threshold')
+        return dict(bin_width=rc['bin_width'], max_bins=rc['max_bins'], mask_threshold=None if threshold is None else float(threshold),
+                    classes=classes, glszm=glszm, mesh=mesh, log_sigma=log['sigma'], log_bin_width=log['bin_width'], normalize=normalize,
+                    resample=resample, shell_mm=shells)
 
     def maskMargin(self, flag=None):
         """`Data: mask_margin_mm`: the margin in mm every mask is dilated by on the device ahead of the scan ingest -> None (off, the
@@ -282,9 +301,9 @@ class Parser:
         if not (args.classification or args.survival):
             raise ConfigurationError('getDatasets needs --survival or --classification to pick the dataset classes')
         datasets = []
-        if getattr(args, 'preop', False) or getattr(args, 'postop', False):
+        if args.preop or args.postop:
             datasets.append(ClinicalDataset(self._data('data_loc'), self.clinicalPredictors(args), classification=args.classification, survival=args.survival))
-        if getattr(args, 'radiomics', False):
+        if getattr(args, 'radiomics', False):       # (the image tests build their arguments without the field)
             from ..data.RadiomicsDatasets import JoinedTableDataset, RadiomicsClassificationDataset, RadiomicsSurvivalDataset
             cls = RadiomicsSurvivalDataset if args.survival else RadiomicsClassificationDataset
             self.radiomics_dataset = cls(self._data('rad_loc'), self._data('data_loc'), *self._radiomicsExcluded())
@@ -310,7 +329,7 @@ class Parser:
             raise InitializationError('Attempted to load model prior to parsing config parameters, config must be parsed prior to loading model')
         im = self.config['ImageModel']
         name = im['name'].lower()
-        clinical = getattr(args, 'preop', False) or getattr(args, 'postop', False) or getattr(args, 'radiomics', False)
+        clinical = args.preop or args.postop or args.radiomics
         if not args.images and clinical:
             return MLP(len(self.predictors(args)), im['num_classes'], im['feature_layers'])
         kw = dict(spatial_dims=im['spatial_dims'], in_channels=im['in_channels'], out_channels=im['num_classes'],
@@ -327,5 +346,5 @@ class Parser:
             # parser/parser.py:159-160,171-172: only encoders with .backbone / .features can feed the fusion model
             assert name.startswith('tinydensenet') or name.startswith('densenet121'), \
                 "Image models used to build multimodal models must be one of 'tinydensenet' or 'densenet121'"
-            model = MultiModalModel(model, self.predictors(args), im['num_classes'], im['feature_layers'], blend=getattr(args, 'blend', False))
+            model = MultiModalModel(model, self.predictors(args), im['num_classes'], im['feature_layers'], blend=args.blend)
         return model

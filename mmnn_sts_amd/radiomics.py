@@ -916,19 +916,15 @@ def _volumes_of(dataset, patient):
 
 
 def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_WIDTH, max_bins: int = DEFAULT_MAX_BINS,
-                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, classes=(), glszm: bool = False,
-                 mesh: bool = False, log_sigma=(), log_bin_width: Optional[float] = None, normalize=None, resample=None,
-                 shell_mm=()) -> List[dict]:
+                 mask_threshold: Optional[float] = None, batch: int = 8, prefixes=None, **switches) -> List[dict]:
     """Every patient (and modality) of an image dataset (`data.ImageDatasets`) -> rows {'MRN': uid, feature: value}; written as a csv
     to `out_path` when given.  The uploads and kernels of `batch` patients are all enqueued before the first read-back of the batch.
-    A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `classes`: texture classes whose columns follow FEATURE_NAMES; their
-    blocks, with `glszm` the size-zone blocks, with `mesh` the mesh blocks and with `log_sigma` the filtered images' blocks, come back in
-    the batch's same stacked read-back.  `normalize` / `resample`: the pre-steps of `extract`; they add nothing to the read-back.
-    `shell_mm`: shell widths in mm, whose columns follow all the others; their blocks come back in the same read-back."""
+    A dataset of two modalities prefixes its columns `t1_` / `t2_`.  `switches`: those of `extract` (`classes`, `glszm`, `mesh`,
+    `log_sigma`, `log_bin_width`, `normalize`, `resample`, `shell_mm`), handed to it unchanged: the columns of the texture classes follow
+    FEATURE_NAMES, the shells' follow all the others, and every block they add comes back in the batch's same stacked read-back; the
+    pre-steps add nothing to it."""
     from .data import ingest
     dev = torch.device(device)
-    classes, log_sigma = texture_classes(classes), log_sigmas(log_sigma)
-    shells = {"shell_mm": shell_widths(shell_mm)} if shell_widths(shell_mm) else {}      # (without one the call is the one it always was)
     rows = []
     patients = list(dataset.patients)
     for b0 in range(0, len(patients), max(1, int(batch))):
@@ -936,9 +932,7 @@ def extract_tree(dataset, device, out_path=None, bin_width: float = DEFAULT_BIN_
         raws = [_volumes_of(dataset, p) for p in chunk]
         up = [[(ingest.upload(s, dev), ingest.stage_mask(s, m, dev)) for s, m in vols] for vols in raws]
         maps = [[ingest.mask_index_map(s, m, getattr(dataset, "mask_resample", "auto")) for s, m in vols] for vols in up]
-        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, classes=classes, glszm=glszm, mesh=mesh,
-                        log_sigma=log_sigma, log_bin_width=log_bin_width, normalize=normalize, resample=resample, **shells)
-                for (s, m), t in zip(vols, ts)]
+        res = [[extract(s, m, dev, bin_width, max_bins, index_map=t, threshold=mask_threshold, **switches) for (s, m), t in zip(vols, ts)]
                for vols, ts in zip(up, maps)]
         blocks = torch.stack([_stacked(r) for rs in res for r in rs]).cpu().numpy()      # the batch's one read-back
         k = 0
@@ -988,9 +982,16 @@ def read_csv(path):
         return cols, [r for r in rd if r]
 
 
-def add_pre_step_arguments(ap) -> None:
-    """The command-line switches of the two pre-steps, which main.py and this module's tool share."""
-    ap.add_argument("--normalize", action="store_true", help="with --radiomics and no --rad_loc: z-score the whole scan before the extraction "
+def add_extraction_arguments(ap, when: str = "") -> None:
+    """The command-line switches of the extraction that main.py and this module's tool share; `Parser.radiomicsExtraction` resolves them
+    against the config.  `when`: what the command line puts in front of the help texts of the switches that add columns or steps."""
+    ap.add_argument("--mesh_shape", action="store_true", help=when + "append the 8 mesh-based shape columns (mesh volume, surface area, "
+                    "sphericity, the diameters) to the extracted table; also switched on by the config's `Radiomics: mesh_shape: true`")
+    ap.add_argument("--log_sigma", type=str, default=None, help=when + "Laplacian-of-Gaussian scales in mm, comma-separated (1,3): append the "
+                    "log-sigma-<sigma>-mm-3D_* columns of the filtered scans; overrides the config's `Radiomics: log: sigma`")
+    ap.add_argument("--log_bin_width", type=float, default=None, help="bin width of the filtered images; overrides the config's "
+                    "`Radiomics: log: bin_width` (default: `Radiomics: bin_width`)")
+    ap.add_argument("--normalize", action="store_true", help=when + "z-score the whole scan before the extraction "
                     "((v - mean) / sd * scale); also switched on by the config's `Radiomics: normalize`, or by either of the two values below")
     ap.add_argument("--normalize_scale", type=float, default=None, help="what the z-score is multiplied by; overrides `Radiomics: normalize: "
                     "scale` (default 100: with the default bin width of 25 PyRadiomics' scale of 1 would put every voxel into one bin)")
@@ -998,6 +999,15 @@ def add_pre_step_arguments(ap) -> None:
                     "normalize: outliers` (default 0: no clamp)")
     ap.add_argument("--resample_spacing", type=str, default=None, help="resample scan and mask to this voxel spacing in mm before the "
                     "extraction, one number or three comma-separated (1,1,1; 0 keeps an axis); overrides `Radiomics: resample: spacing`")
+    ap.add_argument("--shell_mm", type=str, default=None, help=when + "widths in mm of the peritumoural shells, comma-separated (5,10): append "
+                    "the shell-<r>-mm_* columns of the tissue within r mm around the mask (never the shape classes); overrides the config's "
+                    "`Radiomics: shell_mm`")
+
+
+def tree_datasets(parser, directories, key_loc) -> list:
+    """One image dataset per modality directory, read as the config's `Data:` section says (`mask_resample`, `format`, `mask_roi`)."""
+    from .data.ImageDatasets import ImageDataset
+    return [ImageDataset(d, key_loc, parser.maskResample()[0], format=parser.dataFormat(), mask_roi=parser.maskRoi()) for d in directories]
 
 
 def build_arg_parser():
@@ -1012,43 +1022,22 @@ def build_arg_parser():
                     "ngtdm, or 'all'; overrides the config's `Radiomics: classes`")
     ap.add_argument("--glszm", action="store_true", help="append the 16 size-zone (GLSZM) columns; also switched on by the config's "
                     "`Radiomics: glszm: true`")
-    ap.add_argument("--mesh_shape", action="store_true", help="append the 8 mesh-based shape columns (volume, surface area, sphericity, the "
-                    "diameters); also switched on by the config's `Radiomics: mesh_shape: true`")
-    ap.add_argument("--log_sigma", default=None, help="Laplacian-of-Gaussian scales in mm, comma-separated (1,3): appends the "
-                    "log-sigma-<sigma>-mm-3D_* columns of every scale; overrides the config's `Radiomics: log: sigma`")
-    ap.add_argument("--log_bin_width", type=float, default=None, help="bin width of the filtered images; overrides the config's "
-                    "`Radiomics: log: bin_width` (default: the original image's bin width)")
-    add_pre_step_arguments(ap)
-    ap.add_argument("--shell_mm", default=None, help="widths in mm of the peritumoural shells, comma-separated (5,10): appends the "
-                    "shell-<r>-mm_* columns of the tissue within r mm around the mask (never the shape classes); overrides the config's "
-                    "`Radiomics: shell_mm`")
+    add_extraction_arguments(ap)
     return ap
 
 
 def main(argv=None):
     a = build_arg_parser().parse_args(argv)
     import os
-    from .data.ImageDatasets import ImageDataset
     from .parser.parser import Parser
     parser = Parser(a.config)
-    config = parser.parseConfig()
-    classes = texture_classes(a.classes) if a.classes is not None else parser.radiomicsClasses()
-    glszm = a.glszm or parser.radiomicsZones()
-    mesh = a.mesh_shape or parser.radiomicsMesh()
-    log = parser.radiomicsLog(a.log_sigma, a.log_bin_width)
-    normalize = parser.radiomicsNormalize(a.normalize, a.normalize_scale, a.normalize_outliers)
-    resample = parser.radiomicsResample(a.resample_spacing)
-    shells = parser.radiomicsShell(a.shell_mm)
-    data, rad = dict(config.get("Data") or {}), dict(config.get("Radiomics") or {})
+    data = parser.parseConfig().get("Data") or {}
+    settings = parser.radiomicsExtraction(a)
     dirs = [os.path.join(a.image_loc, data.get(k, d)) for k, d in (("t1_path", "t1"), ("t2_path", "t2"))]
     dirs = [d for d, m in zip(dirs, ("t1", "t2")) if m in a.modality and os.path.isdir(d)]
     if not dirs:
         raise SystemExit(f"no modality directory under {a.image_loc}")
-    sets = [ImageDataset(d, a.key_loc, str(data.get("mask_resample", "auto")).lower(), format=data.get("format"), mask_roi=data.get("mask_roi"))
-            for d in dirs]
-    rows = extract_modalities(sets, a.device, float(rad.get("bin_width", DEFAULT_BIN_WIDTH)), int(rad.get("max_bins", DEFAULT_MAX_BINS)),
-                              data.get("mask_threshold"), classes=classes, glszm=glszm, mesh=mesh, log_sigma=log["sigma"],
-                              log_bin_width=log["bin_width"], normalize=normalize, resample=resample, **({"shell_mm": shells} if shells else {}))
+    rows = extract_modalities(tree_datasets(parser, dirs, a.key_loc), a.device, **settings)
     write_csv(a.out, rows)
     print(f"{len(rows)} patients, {len(rows[0]) - 1 if rows else 0} features -> {a.out}")
 

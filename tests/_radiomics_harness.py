@@ -1,11 +1,9 @@
 """What the five tests/test_radiomics*_gpu.py share: uploads at a byte lead, buffers between guard bytes and the check that nothing
 outside them was written, the first call and a follow-on call through the C-ABI (`radiomics.enqueue`) into such buffers, the walk over
-the refusals of a follow-on call, the MLP at a table's width, the fresh-process runner, the tiny config and the fixture that puts the
+the refusals of a follow-on call, the MLP at a table's width, the fresh-process runner and the fixture that puts the
 dropout seed counter back.  The sizes of the blocks and tables stay spelt out in each test file: they are part of what it checks."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import torch
 
 from mmnn_sts_amd import _lib, radiomics
 from mmnn_sts_amd.data import ingest
+from tests._cli import run_python
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -153,23 +152,5 @@ def mlp_at_width(width, stream):
 
 
 def process(argv, cwd):
-    """A command line in a fresh process -> its output; a status other than 0 fails the test with the end of that output."""
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, *argv], cwd=str(cwd), env=env, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def tiny_config(tmp_path, radiomics_section=None, **image_model):
-    """Writes the smallest config the command lines train on -> its path.  `radiomics_section`: the `Radiomics:` section, if any;
-    `image_model`: overrides of the `ImageModel:` keys."""
-    import yaml
-    cfg = {"ImageModel": dict({"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                               "in_channels": 2, "dropout_prob": 0.2}, **image_model),
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    if radiomics_section is not None:
-        cfg["Radiomics"] = dict(radiomics_section)
-    path = tmp_path / "config.yaml"
-    path.write_text(yaml.safe_dump(cfg))
-    return str(path)
+    """A python command line of the package in a fresh process -> its output (`tests._cli.run_python`, five minutes at the most)."""
+    return run_python(argv, cwd, limit_s=300)

@@ -1,5 +1,6 @@
 """main.py as a fresh process for the BASELINE configs it serves (tiny synthetic sizes): exit code, saved checkpoint reloads
 into a freshly built model with strict=True, attention maps written."""
+import functools
 import os
 import subprocess
 import sys
@@ -8,33 +9,20 @@ import numpy as np
 import pytest
 import torch
 
+from tests._cli import run_main, tiny_config
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def _tiny_config(tmp_path, modality="t1t2", in_channels=2):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": modality, "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": in_channels, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    p = tmp_path / "config.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return str(p)
+_run = functools.partial(run_main, limit_s=900)
+_run_ranks = functools.partial(run_main, limit_s=900, world=2)        # two ranks sharing the one card over gloo
 
 
 def test_config0_preop_classification(tmp_path):
     """BASELINE configs[0]: `--preop --classification`, 32-feature x 64-patient csv -> standalone MLP, pos-weighted BCE."""
     from mmnn_sts_amd.models.mlp import MLP
-    log = _run(["--preop", "--classification", "--epochs", "2", "--synthetic_patients", "64", "--config", _tiny_config(tmp_path)], tmp_path)
+    log = _run(["--preop", "--classification", "--epochs", "2", "--synthetic_patients", "64", "--config", tiny_config(tmp_path)], tmp_path)
     assert "saved new best metric model" in log and "epoch 2/2" in log
     rows = np.loadtxt(tmp_path / "synthetic_train_rank0.csv", delimiter=",", skiprows=1)
     assert rows.shape == (64, 1 + 32 + 4)
@@ -46,7 +34,7 @@ def test_config1_images_survival_t1(tmp_path):
     """BASELINE configs[1]: `--images --survival`, single-channel volumes, unimodal DenseNet."""
     from mmnn_sts_amd.models.densenet import TinyDensenet
     log = _run(["--images", "--survival", "--epochs", "2", "--synthetic_patients", "6", "--synthetic_size", "32",
-                "--config", _tiny_config(tmp_path, "t1", 1)], tmp_path)
+                "--config", tiny_config(tmp_path, "t1", 1)], tmp_path)
     assert "epoch 2/2" in log
     m = TinyDensenet(spatial_dims=3, in_channels=1, out_channels=2, feature_channels=12, dropout_prob=0.2)
     m.load_state_dict(torch.load(tmp_path / "best_surv_model.pth"), strict=True)
@@ -57,7 +45,7 @@ def test_config2_fusion_blend_then_config4_gradcam(tmp_path):
     reload the checkpoint for Grad-CAM inference."""
     from mmnn_sts_amd.models.densenet import TinyDensenet
     from mmnn_sts_amd.models.multimodal import MultiModalModel
-    cfg = _tiny_config(tmp_path)
+    cfg = tiny_config(tmp_path)
     log = _run(["--images", "--preop", "--survival", "--blend", "--blend_update_interval", "2", "--epochs", "2", "--synthetic_patients", "6",
                 "--synthetic_size", "32", "--config", cfg], tmp_path)
     assert "Completed updating gradient blender weights" in log
@@ -118,22 +106,6 @@ def test_bench_plain_run_dumps_outputs(tmp_path):
         np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-3, atol=1e-5, err_msg=k)
 
 
-def _run_ranks(args, out, world=2):
-    """main.py under torch.distributed.run, `world` ranks sharing the one card over gloo (on an 8-GPU node the same command runs over RCCL)."""
-    import socket
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    env = dict(os.environ, MMNN_DIST_BACKEND="gloo", MMNN_POISON_LDS="0", MMNN_POISON_WS="0", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
 def test_two_rank_survival_blend_and_classification(tmp_path):
     """The CLI's data-parallel paths on two ranks: survival + GradientBlender (accumulation windows whose last backward arms the overlapped
     reducer, blender update on gathered predictions, rank 0 saves) and classification (broadcast, all-reduce before every
@@ -141,7 +113,7 @@ def test_two_rank_survival_blend_and_classification(tmp_path):
     from mmnn_sts_amd.models.densenet import TinyDensenet
     from mmnn_sts_amd.models.mlp import MLP
     from mmnn_sts_amd.models.multimodal import MultiModalModel
-    cfg = _tiny_config(tmp_path)
+    cfg = tiny_config(tmp_path)
     a = tmp_path / "surv"; a.mkdir()
     log = _run_ranks(["--images", "--preop", "--survival", "--blend", "--blend_update_interval", "1", "--epochs", "1", "--synthetic_patients", "6",
                       "--synthetic_size", "32", "--config", cfg], a)

@@ -3,10 +3,9 @@ with the output inside a patterned guard buffer; a synth_nifti tree against its 
 byte (derived, not measured: the decode is exact integer work, the shared slope is applied by the same ingest code, and the ingest is
 deterministic); and `main.py` on the twin in fresh processes."""
 import ctypes
+import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,9 +16,9 @@ from mmnn_sts_amd.data import dicom, ingest, nifti, synth_dicom, synth_nifti
 from tests import _dicom_ref as D
 from tests import _ingest_ref as R
 from tests import _resample_ref as G
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 GUARD = 256
 PATTERN = 0xA5
@@ -183,12 +182,7 @@ def test_twin_trees_with_masks_on_their_own_grids(tmp_path):
 
 
 # ---- main.py on the DICOM twin: fresh processes, one at a time ---------------------------------------------------------------------------
-def _main(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_main = functools.partial(run_main, limit_s=600)
 
 
 def _epoch_line(log):
@@ -198,7 +192,6 @@ def _epoch_line(log):
 
 
 def test_cli_trains_and_infers_on_the_dicom_twin(tmp_path):
-    import yaml
     from mmnn_sts_amd.models.densenet import TinyDensenet
     from mmnn_sts_amd.models.multimodal import MultiModalModel
     ntree = synth_nifti.write_tree(tmp_path / "nifti", n_patients=4, seed=35, val_fraction=0.5)
@@ -211,12 +204,8 @@ def test_cli_trains_and_infers_on_the_dicom_twin(tmp_path):
                 img = nifti.read(os.path.join(d, name))
                 nifti.write(os.path.join(d, name), img.raw, img.slope, img.inter, affine=A)
     tree = synth_dicom.from_nifti_tree(tmp_path / "nifti", tmp_path / "dicom", seed=35)
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    (tmp_path / "config.yaml").write_text(yaml.safe_dump(cfg))
-    loc = lambda t: ["--config", str(tmp_path / "config.yaml"), "--image_loc", t["image_loc"], "--key_loc", t["key_loc"], "--data_loc", t["data_loc"],
+    cfg = tiny_config(tmp_path)
+    loc = lambda t: ["--config", cfg, "--image_loc", t["image_loc"], "--key_loc", t["key_loc"], "--data_loc", t["data_loc"],
                      "--train_uid_location", t["train_uids"], "--val_uid_location", t["val_uids"]]
     train = ["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1"]
     out = tmp_path / "dicom_run"

@@ -2,9 +2,8 @@
 INTEGRATION.md ("Grad-CAM of image-only models") -- last Conv3d of the encoder, target = sum / one / argmax of each sample's outputs,
 alpha = voxel mean of d target / d A, ReLU of the weighted channel sum, per-sample min-max (all-equal -> 0), trilinear up-sampling."""
 import copy
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,10 +13,10 @@ import torch.nn.functional as F
 from oracle import restatement as R
 from oracle import synth
 from tests._util import rel_err, synth_sd
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- fp64 references ------------------------------------------------------------------------------------------------------------
@@ -253,29 +252,19 @@ def test_label_out_of_range_is_an_error():
 
 
 # ---- CLI ----------------------------------------------------------------------------------------------------------------------------------
-def _run(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_run = functools.partial(run_main, limit_s=900)
 
 
 def test_cli_inference_images_survival_writes_maps(tmp_path):
     """`--inference --images --survival` of a one-channel TinyDensenet (BASELINE configs[1]'s model) writes one (D, H, W) map per
     patient; `--no_gradcam` writes none."""
-    import yaml
     from mmnn_sts_amd.models.densenet import TinyDensenet
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 1, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    (tmp_path / "config.yaml").write_text(yaml.safe_dump(cfg))
+    cfg = tiny_config(tmp_path, "t1", 1)
     torch.manual_seed(3)
     weights = tmp_path / "model.pth"
     torch.save(TinyDensenet(spatial_dims=3, in_channels=1, out_channels=2, feature_channels=12, dropout_prob=0.2).state_dict(), weights)
     common = ["--inference", "--images", "--survival", "--weights", str(weights), "--synthetic_patients", "8", "--synthetic_size", "32",
-              "--config", str(tmp_path / "config.yaml")]
+              "--config", cfg]
     with_maps = tmp_path / "maps"
     with_maps.mkdir()
     log = _run(common, with_maps)

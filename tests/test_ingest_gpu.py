@@ -4,9 +4,8 @@ function built on it, and `main.py --image_loc` as a fresh process on a syntheti
 Parity bound: the extents are equal EXACTLY; the plane is within 2 * 2^-24 * max|v| absolute (max over the finite voxels of the masked
 volume).  Derivation: v and the window sums are fp64 on both sides, so the only visible error is the final rounding of a mean whose
 magnitude is at most max|v| -- half a unit of 2^-24 max|v|; summation order in fp64 adds ~1e-16 relative; two units are allowed."""
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,9 +13,9 @@ import torch
 
 from mmnn_sts_amd.data import ingest, nifti, synth_nifti
 from tests import _ingest_ref as R
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 SHAPE = (97, 130, 23)
 SENTINEL = 1.0e30          # no plane can hold it: the voxels are below 2^15
@@ -200,24 +199,7 @@ def test_collate_equals_the_single_volume_results_and_feeds_val_transforms(tmp_p
 
 
 # ---- main.py --image_loc, fresh processes, one at a time ---------------------------------------------------------------------------
-def _main(args, out, expect_ok=True):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=900)
-    if expect_ok:
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r
-
-
-def _tiny_config(tmp_path, modality="t1t2", in_channels=2):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": modality, "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": in_channels, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    p = tmp_path / "config.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return str(p)
+_main = functools.partial(run_main, limit_s=900)
 
 
 def _loc(tree):
@@ -229,14 +211,14 @@ def test_cli_fusion_training_then_inference_with_nifti_export(tmp_path):
     from mmnn_sts_amd.models.densenet import TinyDensenet
     from mmnn_sts_amd.models.multimodal import MultiModalModel
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=31)
-    cfg = _tiny_config(tmp_path)
-    r = _main(["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1", "--config", cfg, *_loc(tree)], tmp_path)
-    assert "epoch 1/1" in r.stdout + r.stderr
+    cfg = tiny_config(tmp_path)
+    log = _main(["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1", "--config", cfg, *_loc(tree)], tmp_path)
+    assert "epoch 1/1" in log
     img = TinyDensenet(spatial_dims=3, in_channels=2, out_channels=2, feature_channels=12, dropout_prob=0.2)
     MultiModalModel(img, [f"p{i}" for i in range(32)], 2, 12, blend=True).load_state_dict(torch.load(tmp_path / "best_surv_model.pth"), strict=True)
-    r = _main(["--inference", "--images", "--preop", "--survival", "--transforms", "--weights", str(tmp_path / "best_surv_model.pth"),
-               "--config", cfg, *_loc(tree)], tmp_path)
-    assert "All C-indexes" in r.stdout + r.stderr
+    log = _main(["--inference", "--images", "--preop", "--survival", "--transforms", "--weights", str(tmp_path / "best_surv_model.pth"),
+                 "--config", cfg, *_loc(tree)], tmp_path)
+    assert "All C-indexes" in log
     val_uids = [int(l) for l in open(tree["val_uids"]).read().split()]
     assert len(val_uids) >= 2
     for i, uid in enumerate(val_uids):
@@ -253,14 +235,14 @@ def test_cli_fusion_training_then_inference_with_nifti_export(tmp_path):
 
 def test_cli_unimodal_classification_one_epoch(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=32)
-    r = _main(["--images", "--classification", "--epochs", "1", "--config", _tiny_config(tmp_path, "t1", 1), *_loc(tree)], tmp_path)
-    assert "epoch 1/1" in r.stdout + r.stderr and os.path.exists(tmp_path / "final_model.pth")
+    log = _main(["--images", "--classification", "--epochs", "1", "--config", tiny_config(tmp_path, "t1", 1), *_loc(tree)], tmp_path)
+    assert "epoch 1/1" in log and os.path.exists(tmp_path / "final_model.pth")
 
 
 def test_cli_empty_mask_is_reported_by_uid(tmp_path):
     bad = 1000 + 7 * 2
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=33, empty_mask_uids=(bad,))
-    r = _main(["--images", "--survival", "--epochs", "2", "--config", _tiny_config(tmp_path, "t2", 1), *_loc(tree)], tmp_path, expect_ok=False)
+    r = _main(["--images", "--survival", "--epochs", "2", "--config", tiny_config(tmp_path, "t2", 1), *_loc(tree)], tmp_path, expect_ok=False)
     log = r.stdout + r.stderr
     assert r.returncode != 0, log[-2000:]
     assert f"{bad}" in log and "empty mask" in log

@@ -12,9 +12,8 @@ pass C has waves without a z window, 128 -- two windows per lane, the cap.  The 
 The `ingest_ws` of `maps_to_scan` holds the scan's kept slices and nothing of the S its ingest wrote a plane at, so the maps' S is their
 own: it need not equal the ingest's, and the call has nothing to check it against (`test_maps_size_need_not_be_the_ingests`)."""
 import ctypes
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -26,9 +25,9 @@ from mmnn_sts_amd.data import ingest, synth_nifti
 from tests import _ingest_ref as R
 from tests import _ingest_sized_ref as Z
 from tests import _scan_space_ref as S
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 SHAPE = (97, 130, 23)
 GUARD = 256
@@ -284,18 +283,12 @@ def test_train_pipeline_all_stages_at_128():
 
 
 # ---- main.py --image_size 128, fresh processes, one at a time -------------------------------------------------------------------------------
-def _main(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_main = functools.partial(run_main, limit_s=600)
 
 
 def test_cli_training_then_scan_space_inference_at_128(tmp_path):
-    from tests.test_transforms_gpu import _tiny_config
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=4, seed=41, val_fraction=0.5)      # (every event of this tree is observed)
-    cfg = _tiny_config(tmp_path)
+    cfg = tiny_config(tmp_path)
     loc = ["--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
     log = _main(["--images", "--preop", "--survival", "--blend", "--transforms", "--image_size", "128", "--epochs", "1", "--config", cfg, *loc], tmp_path)

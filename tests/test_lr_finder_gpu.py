@@ -4,16 +4,15 @@ the device-lr SGD against the host-lr kernels (bit for bit), LRFinder.range_test
 absence of host waits inside the sweep, and `main.py --lr_finder` end to end."""
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests._cli import run_main
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = torch.device("cuda:0")
 
 
@@ -444,12 +443,7 @@ def test_range_test_has_no_host_waits(monkeypatch, max_ahead):
 def test_cli_lr_finder(tmp_path):
     """Full DenseNet121, 100 iterations: lr_finder.csv (lr column = the schedule), the logged suggestion, the uid split, the graph."""
     from mmnn_sts_amd.utils.find_lr import lr_schedule, split_uids, suggest_lr
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--images", "--classification", "--lr_finder", "--synthetic_patients", "10",
-                        "--synthetic_size", "64", "--output_path", str(tmp_path)], cwd=str(tmp_path), env=env, capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    log = r.stdout + r.stderr
+    log = run_main(["--images", "--classification", "--lr_finder", "--synthetic_patients", "10", "--synthetic_size", "64"], tmp_path, limit_s=900)
     lines = (tmp_path / "lr_finder.csv").read_text().splitlines()
     assert lines[0] == "lr,loss"
     rows = [tuple(float(v) for v in l.split(",")) for l in lines[1:]]

@@ -17,7 +17,8 @@ from mmnn_sts_amd.data.ImageDatasets import ImageDataset, ImageDatasetByUIDs, T1
 from mmnn_sts_amd.exceptions.exceptions import ConfigurationError
 from tests import _mask_margin_ref as M
 from tests import _scan_space_ref as S
-from tests._radiomics_harness import ROOT, leave_the_dropout_stream_where_it_was, process, tiny_config  # noqa: F401  (the fixture is autouse)
+from tests._radiomics_harness import ROOT, leave_the_dropout_stream_where_it_was, process  # noqa: F401  (the fixture is autouse)
+from tests._cli import tiny_config
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -269,7 +270,7 @@ def test_cli_two_epochs_with_a_margin_and_a_cache_then_scan_space_inference(tree
 
 def test_cli_radiomics_with_shells_two_epochs_and_the_extraction_tool(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=4, seed=12, val_fraction=0.5)
-    cfg = tiny_config(tmp_path, {"shell_mm": [3]})
+    cfg = tiny_config(tmp_path, radiomics={"shell_mm": [3]})
     out = tmp_path / "run"
     out.mkdir()
     main = os.path.join(ROOT, "main.py")

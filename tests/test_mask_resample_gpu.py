@@ -7,9 +7,8 @@ so each test first asserts on the restatement alone that no blend lies within 1e
 within 1e-9 of -0.5 or m_r - 0.5, and that the result is neither empty nor full (`_resample_ref.assert_comparable`).  The bound is
 derived: an fp64 trilinear blend of values <= V errs by <~ 2e-15 V and a coordinate by <~ 1e-13 voxel at these extents, four orders of
 magnitude below it.  Through the ingest the existing bound holds: extents exactly equal, the plane within 2 * 2^-24 * max|v|."""
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,9 +17,9 @@ import torch
 from mmnn_sts_amd.data import ingest, nifti, synth_nifti
 from tests import _ingest_ref as R
 from tests import _resample_ref as G
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 GUARD = 256
 PATTERN = 0xA5
@@ -187,23 +186,13 @@ def test_geometry_mode_resamples_an_equal_extent_pair():
 
 
 # ---- main.py --image_loc on masks with grids of their own: fresh processes, one at a time ----------------------------------------------
-def _main(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_main = functools.partial(run_main, limit_s=600)
 
 
 def test_cli_trains_and_infers_on_own_grid_masks(tmp_path):
-    import yaml
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=4, seed=34, mask_grid="own")
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    (tmp_path / "config.yaml").write_text(yaml.safe_dump(cfg))
-    loc = ["--config", str(tmp_path / "config.yaml"), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    cfg = tiny_config(tmp_path)
+    loc = ["--config", cfg, "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
     log = _main(["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1", *loc], tmp_path)
     assert "epoch 1/1" in log and "4 of 4 patients" in log and "another grid" in log

@@ -4,19 +4,18 @@ array equality (the fp64 order is part of the contract and the library is built 
 two fp32 neighbours of the fp64 mean.  The real models are compared with their own eval() forward run on restated batches of the same
 composition, so that both sides select the same kernels."""
 import ctypes
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from tests import _occlusion_ref as O
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0x7FC0BEEF                      # a NaN pattern no input holds
 GRID_A = ((2, 9, 10, 13), (4, 3, 5), (2, 3, 4))           # odd extents, clamped last windows, w = 13: the dword variant
 GRID_B = ((2, 8, 8, 16), (4, 4, 8), (4, 2, 4))            # w % 4 == 0: the 16-byte variant
@@ -278,29 +277,13 @@ def test_occlusion_sensitivity_on_the_real_models(name):
 
 
 # ---- the CLI, one fresh process each ---------------------------------------------------------------------------------------------------------
-def _tiny_config(tmp_path, modality="t1t2", in_channels=2):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": modality, "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": in_channels, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    p = tmp_path / "config.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return str(p)
-
-
-def _run(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args],
-                       cwd=str(out), env=env, capture_output=True, text=True, timeout=400)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_run = functools.partial(run_main, limit_s=300)
 
 
 @pytest.mark.parametrize("gradcam", [True, False], ids=["gradcam on", "no_gradcam"])
 def test_cli_writes_one_map_per_synthetic_patient(tmp_path, gradcam):
     log = _run(["--inference", "--images", "--survival", "--occlusion", "--synthetic_size", "32", "--synthetic_patients", "4",
-                "--config", _tiny_config(tmp_path, "t1", 1)] + ([] if gradcam else ["--no_gradcam"]), tmp_path)
+                "--config", tiny_config(tmp_path, "t1", 1)] + ([] if gradcam else ["--no_gradcam"]), tmp_path)
     assert "All C-indexes" in log
     written = sorted(p.name for p in (tmp_path / "attention_maps").iterdir())
     patients = 2                                                                         # max(2, synthetic_patients // 4)
@@ -329,7 +312,7 @@ def test_cli_writes_the_maps_on_every_scan(tmp_path):
     weights = tmp_path / "fresh.pth"
     torch.save(MultiModalModel(img_model, [f"predictor{i}" for i in range(32)], 2, 12, blend=False).state_dict(), weights)
     _run(["--inference", "--images", "--preop", "--survival", "--transforms", "--scan_space", "--occlusion", "--weights", str(weights),
-          "--config", _tiny_config(tmp_path), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+          "--config", tiny_config(tmp_path), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
           "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]], tmp_path)
     val_uids = [int(l) for l in open(tree["val_uids"]).read().split()]
     assert len(val_uids) == 2

@@ -17,7 +17,8 @@ from mmnn_sts_amd import _lib, radiomics
 from mmnn_sts_amd.data import ingest, synth_dicom, synth_nifti
 from tests import _radiomics_ref as R
 from tests._radiomics_cases import BOUND, CASES, MEASURED
-from tests._radiomics_harness import DEV, ROOT, cut, first_call, mlp_at_width, process, tiny_config
+from tests._radiomics_harness import DEV, ROOT, cut, first_call, mlp_at_width, process
+from tests._cli import tiny_config
 
 pytestmark = pytest.mark.gpu
 _REF = {}

@@ -22,7 +22,8 @@ from tests import _radiomics_texture_ref as T
 from tests import _radiomics_zones_ref as Z
 from tests._radiomics_cases import BOUND, _case
 from tests._radiomics_harness import (DEV, GUARD, PATTERN, ROOT, device_bytes, leave_the_dropout_stream_where_it_was, mlp_at_width,  # noqa: F401
-                                      process, tiny_config)
+                                      process)
+from tests._cli import tiny_config
 from tests._radiomics_log_cases import FEATURE_CASES, FILTER_CASES, MLP_STREAM, TILE_COLUMNS, TILE_LINE, TILE_ROWS, TILE_X, affine_of
 from tests._radiomics_texture_cases import BOUND as TEXTURE_BOUND
 from tests._radiomics_zones_cases import BOUND as ZONES_BOUND

@@ -225,7 +225,9 @@ def test_binding_constants():
     assert {"mesh", "mesh_cfg", "mesh_workspace", "linear", "mesh_shape"} <= fields
     import inspect
     assert inspect.signature(radiomics.extract).parameters["mesh"].default is False
-    assert inspect.signature(radiomics.extract_tree).parameters["mesh"].default is False
+    # (`extract_tree` states no switch of its own: it hands `**switches` to `extract`, whose default this then is)
+    tree = inspect.signature(radiomics.extract_tree).parameters
+    assert "mesh" not in tree and tree["switches"].kind is inspect.Parameter.VAR_KEYWORD
 
 
 def _parser(tmp_path, rad):

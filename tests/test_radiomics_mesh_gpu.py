@@ -18,7 +18,8 @@ from mmnn_sts_amd.data import ingest, synth_nifti
 from tests import _radiomics_mesh_ref as M
 from tests import _radiomics_ref as R
 from tests._radiomics_harness import (DEV, GOOD_DESC, GUARD, ROOT, cut, first_call, follow_call, leave_the_dropout_stream_where_it_was,  # noqa: F401
-                                      mlp_at_width, process, refusal_walk, tiny_config)
+                                      mlp_at_width, process, refusal_walk)
+from tests._cli import tiny_config
 from tests._radiomics_mesh_cases import BOUND, FLAGGED, MESH_CASES, MLP_STREAM, OBLIQUE, U
 
 pytestmark = pytest.mark.gpu
@@ -190,7 +191,7 @@ def test_extract_tree_and_the_extraction_tool_write_the_eight_columns_last(tmp_p
 
 def test_cli_trains_the_fusion_model_with_mesh_shape_then_infers(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=16, val_fraction=0.34)
-    loc = ["--config", tiny_config(tmp_path, {"classes": list(radiomics.TEXTURE_CLASSES), "glszm": True, "mesh_shape": True}), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    loc = ["--config", tiny_config(tmp_path, radiomics={"classes": list(radiomics.TEXTURE_CLASSES), "glszm": True, "mesh_shape": True}), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"], "--image_loc", tree["image_loc"]]
     out = tmp_path / "run"
     out.mkdir()

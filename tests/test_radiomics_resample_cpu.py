@@ -215,8 +215,10 @@ def test_both_argument_parsers():
 def test_feature_names_do_not_depend_on_the_switches():
     import inspect
     assert "normalize" not in inspect.signature(radiomics.feature_names).parameters and "resample" not in inspect.signature(radiomics.feature_names).parameters
+    tree = inspect.signature(radiomics.extract_tree).parameters      # (no switch of its own: `**switches` go to `extract` unchanged)
     for k in ("normalize", "resample"):
-        assert inspect.signature(radiomics.extract).parameters[k].default is None and inspect.signature(radiomics.extract_tree).parameters[k].default is None
+        assert inspect.signature(radiomics.extract).parameters[k].default is None and k not in tree
+    assert tree["switches"].kind is inspect.Parameter.VAR_KEYWORD
     assert len(radiomics.feature_names()) == 47 and len(radiomics.feature_names("all", True, True, (1.0,))) == 106 + 92
     assert all(n.startswith(("original_", "log-sigma-")) for n in radiomics.feature_names("all", True, True, (1.0,)))
 

@@ -26,7 +26,8 @@ from tests import _radiomics_texture_ref as T
 from tests import _radiomics_zones_ref as Z
 from tests._radiomics_cases import BOUND, _case
 from tests._radiomics_harness import (DEV, GUARD, PATTERN, ROOT, device_bytes, guarded, cut, leave_the_dropout_stream_where_it_was,  # noqa: F401
-                                      process, tiny_config)
+                                      process)
+from tests._cli import tiny_config
 from tests._radiomics_mesh_cases import BOUND as MESH_BOUND
 from tests._radiomics_resample_cases import (BIN_WIDTH, FEATURE_CASES, LINE_BATCH, LINE_TPB, NORM_BATCH, NORM_MAX_PARTS, NORM_TPB, NORM_WRITE_GROUPS,
                                              NORMALIZE_CASES, RESAMPLE_CASES, SCALE, X_CHUNK, X_LINES, Z_RUN, affine_of)

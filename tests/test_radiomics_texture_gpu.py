@@ -15,7 +15,8 @@ from mmnn_sts_amd import _lib, radiomics
 from mmnn_sts_amd.data import synth_nifti
 from tests import _radiomics_texture_ref as T
 from tests._radiomics_harness import (DEV, ROOT, cut, first_call, follow_call, leave_the_dropout_stream_where_it_was, mlp_at_width,  # noqa: F401
-                                      process, refusal_walk, tiny_config)
+                                      process, refusal_walk)
+from tests._cli import tiny_config
 from tests._radiomics_texture_cases import BOUND, FLAGGED, MLP_STREAM, TEXTURE_CASES
 
 pytestmark = pytest.mark.gpu
@@ -158,7 +159,7 @@ def test_cli_extraction_tool_with_all_classes_writes_the_rows_of_finish(tmp_path
 
 def test_cli_trains_the_fusion_model_on_the_wider_table_then_infers(tmp_path):
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=6, seed=12, val_fraction=0.34)
-    loc = ["--config", tiny_config(tmp_path, {"classes": list(radiomics.TEXTURE_CLASSES)}), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    loc = ["--config", tiny_config(tmp_path, radiomics={"classes": list(radiomics.TEXTURE_CLASSES)}), "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"], "--image_loc", tree["image_loc"]]
     out = tmp_path / "run"
     out.mkdir()

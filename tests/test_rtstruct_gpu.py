@@ -7,8 +7,6 @@ and the polygons are chosen (seeds fixed on the CPU) so that no crossing lies wi
 a row -- ten orders of magnitude above an fp64 rounding at these extents -- which each test asserts before it compares every voxel."""
 import math
 import os
-import subprocess
-import sys
 from types import SimpleNamespace
 
 import numpy as np
@@ -19,9 +17,9 @@ from mmnn_sts_amd import _lib
 from mmnn_sts_amd.data import ingest, nifti, synth_dicom, synth_nifti
 from tests import _resample_ref as G
 from tests import _rtstruct_ref as C
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 GUARD = 256
 PATTERN = 0xA5
@@ -201,22 +199,10 @@ def test_twin_tree_with_rtstruct_masks_gives_the_same_batch(tmp_path):
 
 
 def test_cli_trains_one_epoch_on_the_rtstruct_twin(tmp_path):
-    import yaml
     ntree = synth_nifti.write_tree(tmp_path / "nifti", n_patients=4, seed=36, val_fraction=0.5)
     _with_geometry(ntree, 4)
     tree = synth_dicom.from_nifti_tree(tmp_path / "nifti", tmp_path / "dicom", seed=36, mask_format="rtstruct", extra_rois=("Body",))
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]},
-           "Data": {"mask_roi": "GTV"}}
-    (tmp_path / "config.yaml").write_text(yaml.safe_dump(cfg))
-    out = tmp_path / "run"
-    out.mkdir()
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), "--images", "--survival", "--epochs", "1",
-                        "--config", str(tmp_path / "config.yaml"), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"],
-                        "--data_loc", tree["data_loc"], "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]],
-                       cwd=str(out), env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "epoch 1/1" in r.stdout + r.stderr
+    log = run_main(["--images", "--survival", "--epochs", "1", "--config", tiny_config(tmp_path, data={"mask_roi": "GTV"}),
+                    "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+                    "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]], tmp_path / "run", limit_s=600)
+    assert "epoch 1/1" in log

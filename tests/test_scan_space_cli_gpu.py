@@ -2,8 +2,6 @@
 written on the voxel grid of each of the patient's scans, with the scan's geometry, beside the files the inference wrote before.  The
 class-0 file must be the restatement (tests/_scan_space_ref.py) of the patient's 64^3 att_map.nii.gz within 2 * 2^-24 * max|map|."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,20 +11,9 @@ from mmnn_sts_amd.data import nifti, synth_nifti
 from tests import _ingest_ref as R
 from tests import _resample_ref as G
 from tests import _scan_space_ref as S
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _tiny_config(tmp_path):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    p = tmp_path / "config.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return str(p)
 
 
 def test_cli_writes_every_class_on_every_scan(tmp_path):
@@ -47,14 +34,10 @@ def test_cli_writes_every_class_on_every_scan(tmp_path):
     img_model = TinyDensenet(spatial_dims=3, in_channels=2, out_channels=2, feature_channels=12, dropout_prob=0.2)
     weights = tmp_path / "fresh.pth"
     torch.save(MultiModalModel(img_model, [f"predictor{i}" for i in range(32)], 2, 12, blend=False).state_dict(), weights)
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(tmp_path), "--inference", "--images", "--preop", "--survival",
-                        "--transforms", "--scan_space", "--weights", str(weights), "--config", _tiny_config(tmp_path),
-                        "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
-                        "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]],
-                       cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "All C-indexes" in r.stdout + r.stderr
+    log = run_main(["--inference", "--images", "--preop", "--survival", "--transforms", "--scan_space", "--weights", str(weights),
+                    "--config", tiny_config(tmp_path), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+                    "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]], tmp_path, limit_s=600)
+    assert "All C-indexes" in log
     val_uids = [int(l) for l in open(tree["val_uids"]).read().split()]
     assert len(val_uids) == 2
     for i, uid in enumerate(val_uids):

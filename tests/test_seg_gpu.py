@@ -7,9 +7,8 @@ Byte-for-byte is a condition, not a tolerance: unpacking is integer arithmetic. 
 its seed is chosen on the CPU so that, on the restatement alone, no blend lies within 1e-6 * 128 of the threshold and no coordinate
 within 1e-6 of the SEG volume's border under either index map, which the test asserts before it compares the batches."""
 import ctypes
+import functools
 import os
-import subprocess
-import sys
 from types import SimpleNamespace
 
 import numpy as np
@@ -20,9 +19,9 @@ from mmnn_sts_amd import _lib
 from mmnn_sts_amd.data import ingest, nifti, seg, synth_dicom, synth_nifti
 from tests import _resample_ref as G
 from tests import _seg_ref as S
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 GUARD = 256
 PATTERN = 0xA5
@@ -233,29 +232,18 @@ def test_twin_tree_with_seg_masks_on_their_own_grids_gives_the_same_batch(tmp_pa
 
 
 # ---- main.py on the SEG twin: fresh processes, one at a time -------------------------------------------------------------------------------
-def _main(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_main = functools.partial(run_main, limit_s=600)
 
 
 def test_cli_trains_one_epoch_and_infers_in_scan_space_on_the_seg_twin(tmp_path):
-    import yaml
     from mmnn_sts_amd.data import dicom
     from tests import _ingest_ref as R
     from tests.test_rtstruct_gpu import _with_geometry
     ntree = synth_nifti.write_tree(tmp_path / "nifti", n_patients=4, seed=36, val_fraction=0.5)
     _with_geometry(ntree, 4)
     tree = synth_dicom.from_nifti_tree(tmp_path / "nifti", tmp_path / "dicom", seed=36, mask_format="seg", extra_rois=("Body",))
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]},
-           "Data": {"mask_roi": "GTV"}}
-    (tmp_path / "config.yaml").write_text(yaml.safe_dump(cfg))
-    loc = ["--config", str(tmp_path / "config.yaml"), "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
+    cfg = tiny_config(tmp_path, data={"mask_roi": "GTV"})
+    loc = ["--config", cfg, "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
            "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
     out = tmp_path / "run"
     out.mkdir()

@@ -2,10 +2,9 @@
 semantics table: every transform alone with fixed parameters at cubic and ragged extents, the full train / val
 pipelines, per-sample parameters in a batch (including more samples than one launch group holds), the noise stream's statistics
 and determinism, edge cases, and main.py --transforms end to end."""
+import functools
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,9 +14,9 @@ import torch.nn.functional as F
 from mmnn_sts_amd import transforms as T
 from mmnn_sts_amd.data.constants import IMAGE_DATA_MEAN, IMAGE_DATA_STDDEV
 from mmnn_sts_amd.utils.utils import Normalize
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 SHAPES = [(2, 2, 32, 32, 32), (2, 2, 37, 50, 43), (1, 1, 97, 130, 111)]
 
@@ -354,27 +353,11 @@ def test_negative_max_keeps_normalize_sign():
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------------
-def _cli(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
-
-
-def _tiny_config(tmp_path):
-    import yaml
-    cfg = {"ImageModel": {"name": "tinydensenet", "modality": "t1t2", "feature_layers": 12, "num_classes": 2, "spatial_dims": 3,
-                          "in_channels": 2, "dropout_prob": 0.2},
-           "ClinicalModel": {"NUM_PREDICTORS": 32, "PRE_OP_PREDICTORS": [], "POST_OP_PREDICTORS": []},
-           "Hyperparameters": {"momentum": 0.9, "weight_decay": 1e-4, "train_batch_size": 2, "seed": 42, "class_frequencies": [0.4, 0.55]}}
-    p = tmp_path / "config.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return str(p)
+_cli = functools.partial(run_main, limit_s=900)
 
 
 def test_cli_fusion_training_and_inference_with_transforms(tmp_path):
-    cfg = _tiny_config(tmp_path)
+    cfg = tiny_config(tmp_path)
     log = _cli(["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "1", "--synthetic_patients", "4",
                 "--synthetic_size", "48", "--config", cfg], tmp_path)
     line = [l for l in log.splitlines() if "train loss/patient" in l][-1]

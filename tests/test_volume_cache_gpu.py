@@ -3,10 +3,9 @@ carved out of a larger buffer whose sentinel dwords on both sides must survive; 
 uncached collate on the same items, bit for bit, with the file reader disabled in the cached pass; and `main.py --cache_volumes` in fresh
 processes."""
 import ctypes
+import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,9 +16,9 @@ from mmnn_sts_amd.data import cache as C
 from mmnn_sts_amd.data import ingest, nifti, synth_dicom, synth_nifti
 from mmnn_sts_amd.data.ImageDatasets import ImageDataset, ImageDatasetByUIDs, T1T2SurvivalDataset
 from mmnn_sts_amd.exceptions.exceptions import ConfigurationError
+from tests._cli import run_main, tiny_config
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 GUARD = 64                                   # sentinel dwords on each side of `out` (256 bytes: `out` keeps the allocation's alignment)
 SENTINEL = 0x5A5A1234
@@ -251,13 +250,7 @@ def test_keep_workspaces_excludes_a_cache():
 
 
 # ---- main.py ---------------------------------------------------------------------------------------------------------------------------
-def _main(args, out):
-    env = dict(os.environ, MMNN_POISON_LDS="0", MMNN_POISON_WS="0")
-    os.makedirs(out, exist_ok=True)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--output_path", str(out), *args], cwd=str(out), env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout + r.stderr
+_main = functools.partial(run_main, limit_s=600)
 
 
 CACHE_LINE = re.compile(r"volume cache: (\d+) of (\d+) patients cached, ([\d.]+) MB held; this epoch: (\d+) hits, (\d+) misses, (\d+) overflow, "
@@ -267,9 +260,8 @@ CACHE_LINE = re.compile(r"volume cache: (\d+) of (\d+) patients cached, ([\d.]+)
 def test_cli_two_epochs_with_a_cache(tmp_path):
     """Epoch 1 reads every patient's four files (T1 and T2, a scan and a mask each) and hits nothing; epoch 2 reads none.  The
     checkpoint is the uncached run's, tensor for tensor: two uncached runs of this command were identical on the device."""
-    from tests.test_transforms_gpu import _tiny_config
     tree = synth_nifti.write_tree(tmp_path / "tree", n_patients=4, seed=41, val_fraction=0.5)
-    cfg = _tiny_config(tmp_path)
+    cfg = tiny_config(tmp_path)
     args = ["--images", "--preop", "--survival", "--blend", "--transforms", "--epochs", "2", "--config", cfg,
             "--image_loc", tree["image_loc"], "--key_loc", tree["key_loc"], "--data_loc", tree["data_loc"],
             "--train_uid_location", tree["train_uids"], "--val_uid_location", tree["val_uids"]]
