@@ -494,6 +494,40 @@ typedef struct {
 } mmnn_decode_slices_desc;
 int mmnn_decode_slices(const mmnn_decode_slices_desc* d, const void* pixels, const double* slice_scale, void* out, void* stream);
 
+/* ---- DICOM RLE Lossless expansion: the fragments of a sorted single-frame series in transfer syntax 1.2.840.10008.1.2.5 (PS3.5
+ * Annex G, PackBits over byte planes) -> exactly the bytes an uncompressed series would hold, i.e. the `pixels` of mmnn_decode_slices:
+ * little-endian words of bits_allocated bits, x (the column) fastest, the z frames in order (csrc/dicom_rle.hip, csrc/rle_core.hpp).
+ * `payload`: the z fragments back to back as the files hold them (64-byte header included), each start aligned to 16 bytes, payload_bytes
+ * in all.  `segments`: DEVICE memory, [z][B][2] int64, B = bits_allocated / 8: the byte offset into `payload` and the byte length of
+ * segment s of frame k.  The kernel trusts neither number: it clamps the offset into 0..payload_bytes and the length into what is left.
+ *   planes         segment s of a frame holds byte B - 1 - s of every word (the most significant byte plane comes first); a plane has
+ *                  exactly x*y bytes.
+ *   control byte   n in 0..127 copies the next n + 1 bytes; n in 129..255 repeats the next byte 257 - n times; 128 does nothing.
+ *                  Runs may cross row ends (encoders must not do that, decoders must cope).
+ *   a full plane   decoding stops when the plane is full: a run that would overfill it is clipped, and whatever is left in the segment
+ *                  is ignored, the zero byte that pads a segment to even length included.
+ *   a short plane  a run whose bytes (the control byte, then n + 1 literal bytes or the one repeated byte) do not all lie inside the
+ *                  segment is cut: it gives no output, even where clipping would have needed fewer bytes, and it ends the segment.  If
+ *                  a segment ends, or a run is cut, before the plane is full, status[k] of that frame is 1 and the bytes of that plane
+ *                  from there on are written as 0; the frame's other planes and every other frame are unaffected.
+ * status[k] is 0 for a frame whose planes were all filled; every status word and every byte of `pixels` is written.  No read ever leaves
+ * [payload, payload + payload_bytes) and no write ever leaves `pixels`, `status` or `workspace`, whatever the bytes hold.  `workspace`:
+ * mmnn_rle_workspace_bytes bytes (the byte planes before they meet, and their status words); with bits_allocated 8 nothing is kept there.
+ * One launch at 8 bits, two otherwise; no atomics, no host synchronisation: repeated calls are bit-identical.  A segment passes through
+ * LDS in chunks of MMNN_RLE_CHUNK bytes.  Refused (status 1) before any launch: a null pointer, a non-positive extent, x*y*z >= 2^31,
+ * bits_allocated outside {8, 16, 32}, payload_bytes < 1, payload or workspace not aligned to 16 bytes, segments not aligned to 8,
+ * status not to 4, pixels not to its element size, pixels or status overlapping payload. */
+#define MMNN_RLE_CHUNK 4096
+typedef struct {
+  int32_t x, y, z;                /* Columns, Rows, slices */
+  int32_t bits_allocated;         /* 8, 16, 32 */
+  int64_t payload_bytes;
+} mmnn_rle_desc;
+/* bytes of device scratch; grows with every extent and with bits_allocated; -1 on a bad extent or bits_allocated.  Needs no GPU. */
+int64_t mmnn_rle_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bits_allocated);
+int mmnn_rle_expand(const mmnn_rle_desc* d, const void* payload, const int64_t* segments, void* pixels, int32_t* status, void* workspace,
+                    void* stream);
+
 /* ---- RTSTRUCT contours -> a mask on the scan's grid: the planar polygons of one ROI of an RT Structure Set, already mapped by the host
  * into the scan's continuous voxel index space (a voxel centre sits at the integer index) and assigned to slices, filled into one byte
  * per scan voxel (csrc/rtstruct.hip).  `points`: n_points pairs (px, py) in fp64; `contours`: n_contours pairs (first point, point

@@ -121,6 +121,14 @@ class DecodeSlicesDesc(Structure):
                 ("is_signed", c_int32), ("out_type", c_int32)]
 
 
+RLE_CHUNK = 4096                             # MMNN_RLE_CHUNK
+
+
+class RleDesc(Structure):
+    """mmnn_rle_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("bits_allocated", c_int32), ("payload_bytes", c_int64)]
+
+
 RASTERIZE_CHUNK_EDGES = 1024                 # MMNN_RASTERIZE_CHUNK_EDGES
 
 
@@ -259,6 +267,7 @@ def _signatures():
         "mmnn_maps_to_scan": [P(MapsToScanDesc), V, V, V, V, V],
         "mmnn_maps_to_scan_sized": [P(MapsToScanDesc), I, V, V, V, V, V],
         "mmnn_decode_slices": [P(DecodeSlicesDesc), V, V, V, V],
+        "mmnn_rle_expand": [P(RleDesc), V, V, V, V, V, V],
         "mmnn_rasterize_contours": [P(RasterizeDesc), V, V, V, V, V],
         "mmnn_unpack_frames": [P(UnpackFramesDesc), V, V, V, V, V],
         "mmnn_gather_rows": [V, Q, Q, P(I), I, V, V],
@@ -286,6 +295,7 @@ def _signatures():
         "mmnn_transform_workspace_bytes": [P(TransformDesc)],
         "mmnn_ingest_workspace_bytes": [I, I, I],
         "mmnn_maps_to_scan_workspace_bytes": [I, I, I],
+        "mmnn_rle_workspace_bytes": [I, I, I, I],
         "mmnn_occlusion_window_count": [P(OcclusionDesc), P(I)],
         "mmnn_radiomics_workspace_bytes": [I, I, I, I],
         "mmnn_radiomics_texture_workspace_bytes": [I, I, I, I],

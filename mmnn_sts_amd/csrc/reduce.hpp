@@ -78,6 +78,33 @@ __device__ __forceinline__ T block_reduce(T v, T* lds, Op op) {
   block_reduce<WAVES>(a, lds, op);
   return a[0];
 }
+
+// block_exclusive_scan<WAVES>(v, lds, total): every thread of a one-dimensional workgroup of WAVES * 64 threads calls it with one value
+// and the same `lds` of WAVES elements.  It returns the sum of the values of the threads in front of the caller, in thread-index order,
+// and sets `total` to the sum of all of them in every thread.  Integer sums in mind: the lanes fold by the shift-up ladder (offsets
+// 1, 2, ... 32), the waves in wave-index order.  Its two barriers are block_reduce's (1) and (2), with the same consequences.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T* lds, T& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T s = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T t = __shfl_up(s, o, 64);
+    if (lane >= o) s += t;
+  }
+  __syncthreads();   // (1)
+  if (lane == 63) lds[wave] = s;
+  __syncthreads();   // (2)
+  T before = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    const T t = lds[w];
+    if (w < wave) before += t;
+    total += t;
+  }
+  return before + s - v;
+}
 #endif  // __HIPCC__
 
 }  // namespace mmnn

@@ -1,7 +1,8 @@
-"""A minimal DICOM reader for uncompressed single-frame series (numpy, mmap and struct only; pydicom / GDCM / SimpleITK are not
-dependencies): a directory of slice files -> the raw voxel bytes, the per-slice rescale pairs and the voxel-index -> mm matrix that the
-device ingest takes (`mmnn_sts_amd.data.ingest.decode_series`).  The host opens files, parses headers and copies bytes; it never touches
-a voxel value -- unpacking the stored bits, sign extension and per-slice rescaling run on the device (`mmnn_decode_slices`).
+"""A minimal DICOM reader for uncompressed and RLE Lossless single-frame series (numpy, mmap and struct only; pydicom / GDCM /
+SimpleITK are not dependencies): a directory of slice files -> the raw voxel bytes (or the RLE fragments), the per-slice rescale pairs
+and the voxel-index -> mm matrix that the device ingest takes (`mmnn_sts_amd.data.ingest.decode_series`).  The host opens files, parses
+headers and copies bytes; it never touches a voxel value -- expanding the PackBits runs of an RLE series (`mmnn_rle_expand`), unpacking
+the stored bits, sign extension and per-slice rescaling (`mmnn_decode_slices`) run on the device.
 
 Pinned to the published standard's element layout (PS3.5 / PS3.10): the 128-byte preamble and `DICM`; the file meta group (0002,xxxx),
 always explicit VR little endian; then the data set in the VR mode TransferSyntaxUID (0002,0010) names.  An explicit-VR element is
@@ -12,9 +13,14 @@ length; an implicit-VR element is tag and a 4-byte length.  A length of FFFFFFFF
 pinned to instead is that layout and the NIfTI twin: `synth_dicom.from_nifti_tree` turns a NIfTI tree into a DICOM one, and the two
 must give the same device batch bit for bit.
 
-Accepted: implicit VR little endian (1.2.840.10008.1.2) and explicit VR little endian (1.2.840.10008.1.2.1), SamplesPerPixel 1, one
-frame per file, BitsAllocated 8 / 16 / 32.  Refused, with the file named: big endian, deflated, every encapsulated (compressed) syntax,
-multi-frame and enhanced objects, colour, float / double pixel data.  A mask may also be an RT Structure Set: that file is read by
+Accepted: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endian (1.2.840.10008.1.2.1) and RLE Lossless
+(1.2.840.10008.1.2.5, PS3.5 Annex G), SamplesPerPixel 1, one frame per file, BitsAllocated 8 / 16 / 32.  An RLE file's data set is
+explicit VR little endian and its PixelData is encapsulated (PS3.5 A.4): OB of undefined length holding the Basic Offset Table item
+(its content is ignored), one fragment item for the one frame, and the sequence delimiter.  The host reads the fragment's 64-byte
+header -- 16 little-endian uint32: the segment count (BitsAllocated / 8), then 15 offsets from the start of the header -- checks it and
+reads nothing behind it: `encoding` is 'rle', `frame` the whole fragment and `segments` its (offset, length) pairs.  Refused, with the
+file named: big endian, deflated, every other encapsulated (compressed) syntax, multi-frame and enhanced objects, colour, float /
+double pixel data, and a series that mixes uncompressed and RLE files.  A mask may also be an RT Structure Set: that file is read by
 `rtstruct.py`, or a BINARY DICOM Segmentation object, read by `seg.py`.  What the three readers share lives here once: `part10` (the
 one place a file is mapped), `walk` (the nested data-set walk that descends into the sequences `read_file` skips), the value helpers
 `_text` / `_integer` / `_floats`, `match_name` behind both `resolve`s and `lps_to_ras`.  `read_file` itself keeps refusing every
@@ -41,8 +47,10 @@ logger = logging.getLogger(__name__)
 
 IMPLICIT_LE = "1.2.840.10008.1.2"
 EXPLICIT_LE = "1.2.840.10008.1.2.1"
-_REFUSED_SYNTAX = {"1.2.840.10008.1.2.2": "explicit VR big endian", "1.2.840.10008.1.2.1.99": "deflated explicit VR little endian",
-                   "1.2.840.10008.1.2.5": "RLE lossless (an encapsulated, compressed syntax)"}
+RLE_LOSSLESS = "1.2.840.10008.1.2.5"
+NATIVE, RLE = "native", "rle"                # DicomFile.encoding
+RLE_HEADER_BYTES = 64                        # 16 uint32: the segment count and 15 offsets
+_REFUSED_SYNTAX = {"1.2.840.10008.1.2.2": "explicit VR big endian", "1.2.840.10008.1.2.1.99": "deflated explicit VR little endian"}
 LONG_VRS = frozenset(("OB", "OD", "OF", "OL", "OV", "OW", "SQ", "SV", "UC", "UN", "UR", "UT", "UV"))
 UNDEFINED = 0xFFFFFFFF
 ITEM, ITEM_END, SEQUENCE_END = (0xFFFE, 0xE000), (0xFFFE, 0xE00D), (0xFFFE, 0xE0DD)
@@ -90,7 +98,10 @@ class DicomFile:
     sop_class_uid: Optional[str] = None
     pixel_offset: Optional[int] = None       # byte offset of the PixelData value in the file; None: the file has no PixelData
     pixel_length: Optional[int] = None       # its declared length
-    frame: Optional[np.ndarray] = None       # uint8 view of the rows * columns * bits_allocated / 8 voxel bytes (None with header_only)
+    frame: Optional[np.ndarray] = None       # uint8 view of the rows * columns * bits_allocated / 8 voxel bytes, or, 'rle', of the whole
+                                             # fragment, header included (None with header_only)
+    encoding: str = NATIVE                   # NATIVE, or RLE: `frame` holds PackBits segments
+    segments: Optional[np.ndarray] = None    # 'rle': (bits_allocated / 8, 2) int64, byte offset into the fragment and byte length
 
     @property
     def has_image(self):
@@ -323,14 +334,18 @@ def _transfer_syntax(buf, path):
 
 
 def _check_syntax(syntax, path):
+    """(explicit VR?, encoding) of an accepted transfer syntax."""
     if syntax in (IMPLICIT_LE, EXPLICIT_LE):
-        return syntax == EXPLICIT_LE
+        return syntax == EXPLICIT_LE, NATIVE
+    if syntax == RLE_LOSSLESS:
+        return True, RLE
     if syntax in _REFUSED_SYNTAX:
-        _refuse(path, f"transfer syntax {syntax} ({_REFUSED_SYNTAX[syntax]}) is outside the path: only uncompressed little endian files are read")
+        _refuse(path, f"transfer syntax {syntax} ({_REFUSED_SYNTAX[syntax]}) is outside the path: only little endian files, uncompressed or RLE "
+                      "lossless, are read")
     if syntax.startswith("1.2.840.10008.1.2.4."):
         _refuse(path, f"transfer syntax {syntax} is encapsulated (compressed: JPEG / JPEG-LS / JPEG 2000 / MPEG / HEVC), which is outside the "
                       "path: decompress the series first")
-    _refuse(path, f"transfer syntax {syntax} is not supported: only {IMPLICIT_LE} and {EXPLICIT_LE} are read")
+    _refuse(path, f"transfer syntax {syntax} is not supported: only {IMPLICIT_LE}, {EXPLICIT_LE} and {RLE_LOSSLESS} are read")
 
 
 def _validate(f: DicomFile, size: int):
@@ -354,6 +369,11 @@ def _validate(f: DicomFile, size: int):
         _refuse(path, f"HighBit {f.high_bit} outside {f.bits_stored - 1}..{f.bits_allocated - 1} (BitsStored - 1 .. BitsAllocated - 1)")
     if f.pixel_representation not in (0, 1):
         _refuse(path, f"PixelRepresentation {f.pixel_representation} is neither 0 nor 1")
+    if f.encoding == RLE:
+        if f.pixel_length != UNDEFINED:
+            _refuse(path, f"transfer syntax {f.transfer_syntax} (RLE lossless) is compressed and needs encapsulated PixelData of undefined length; "
+                          f"this PixelData declares {f.pixel_length} bytes")
+        return None
     if f.pixel_length == UNDEFINED:
         _refuse(path, "PixelData of undefined length (encapsulated, i.e. compressed, frames) is outside the path")
     need = f.rows * f.columns * f.bits_allocated // 8
@@ -363,13 +383,63 @@ def _validate(f: DicomFile, size: int):
     return need
 
 
+def _rle_fragment(buf, f: DicomFile, size: int):
+    """The one fragment of an RLE file's encapsulated PixelData as (offset in the file, length), its header checked and `f.segments`
+    set.  Nothing behind the 64-byte header is read."""
+    path = f.path
+
+    def item(off, what):
+        if off + 8 > size:
+            _refuse(path, f"malformed: PixelData ends at byte {size} without its sequence delimiter (FFFE,E0DD), where {what} was expected")
+        tag, _, length, voff = _element(buf, off, True, path)
+        if tag == SEQUENCE_END:
+            return None, voff
+        if tag != ITEM:
+            _refuse(path, f"malformed: ({tag[0]:04X},{tag[1]:04X}) at byte {off} inside encapsulated PixelData, where an item (FFFE,E000) was expected")
+        if length == UNDEFINED or voff + length > size:
+            _refuse(path, f"malformed: {what} at byte {off} declares {'an undefined length' if length == UNDEFINED else f'{length} bytes'}, "
+                          f"{size - voff} are left in the file")
+        return (voff, length), voff + length
+
+    table, off = item(f.pixel_offset, "the Basic Offset Table")
+    if table is None:
+        _refuse(path, "malformed: encapsulated PixelData without a Basic Offset Table item")
+    fragments = []
+    while True:
+        fragment, off = item(off, "a fragment or the sequence delimiter")
+        if fragment is None:
+            break
+        fragments.append(fragment)
+    if len(fragments) != 1:
+        _refuse(path, f"{len(fragments)} fragments in PixelData: one frame per file in exactly one fragment is read")
+    at, length = fragments[0]
+    if length % 2:
+        _refuse(path, f"malformed: an RLE fragment of odd length {length}")
+    if length < RLE_HEADER_BYTES:
+        _refuse(path, f"malformed: an RLE fragment of {length} bytes, shorter than its {RLE_HEADER_BYTES}-byte header")
+    count, *offsets = struct.unpack_from("<16I", buf, at)
+    planes = f.bits_allocated // 8
+    if count != planes:
+        _refuse(path, f"the RLE header counts {count} segments, BitsAllocated {f.bits_allocated} needs {planes}")
+    used, spare = offsets[:planes], offsets[planes:]
+    if used[0] != RLE_HEADER_BYTES:
+        _refuse(path, f"malformed: the first RLE segment starts at byte {used[0]} of its fragment, not behind the {RLE_HEADER_BYTES}-byte header")
+    if any(b <= a for a, b in zip(used, used[1:])) or used[-1] > length:
+        _refuse(path, f"malformed: RLE segment offsets {used} do not ascend strictly inside a fragment of {length} bytes")
+    if any(spare):
+        _refuse(path, f"malformed: a non-zero offset behind the {planes} used ones of the RLE header ({spare})")
+    f.segments = np.array([[a, b - a] for a, b in zip(used, used[1:] + [length])], dtype=np.int64)
+    return at, length
+
+
 def read_file(path, header_only=False) -> DicomFile:
-    """Parse one file up to PixelData (7FE0,0010).  `frame` is a zero-copy uint8 view of the file's voxel bytes (the file stays mapped
-    while the view lives); with `header_only` no voxel byte is read and `frame` stays None."""
+    """Parse one file up to PixelData (7FE0,0010).  `frame` is a zero-copy uint8 view of the file's voxel bytes, or of its RLE fragment
+    (the file stays mapped while the view lives); with `header_only` everything is parsed and checked alike, no voxel byte is read and
+    `frame` stays None."""
     with part10(path) as p:
         path, buf, size, off = p.path, p.buf, p.size, p.off
-        explicit = _check_syntax(p.syntax, path)
-        f = DicomFile(path, p.syntax)
+        explicit, encoding = _check_syntax(p.syntax, path)
+        f = DicomFile(path, p.syntax, encoding=encoding)
         while off < size:
             tag, vr, length, voff = _element(buf, off, explicit, path)
             if tag in (FLOAT_PIXEL_DATA, DOUBLE_PIXEL_DATA):
@@ -394,9 +464,11 @@ def read_file(path, header_only=False) -> DicomFile:
                     setattr(f, name, v)
             off = voff + length
         if f.has_image:
-            need = _validate(f, size)
+            need, at = _validate(f, size), f.pixel_offset
+            if encoding == RLE:
+                at, need = _rle_fragment(buf, f, size)
             if not header_only:
-                f.frame = np.frombuffer(buf, dtype=np.uint8, count=need, offset=f.pixel_offset)
+                f.frame = np.frombuffer(buf, dtype=np.uint8, count=need, offset=at)
                 p.keep = True
     return f
 
@@ -405,7 +477,9 @@ def read_file(path, header_only=False) -> DicomFile:
 class DicomSeries:
     """A sorted series: what `ingest.decode_series` uploads.  `shape`: (Columns, Rows, slices) = the extents along voxel index (i, j, k);
     `affine`: 4x4 float64 voxel index -> mm in RAS, or None (a single slice without geometry); `slopes`, `inters`: RescaleSlope /
-    RescaleIntercept per sorted slice; `frames`: per sorted slice a uint8 view of that file's PixelData bytes (empty with header_only)."""
+    RescaleIntercept per sorted slice; `frames`: per sorted slice a uint8 view of that file's PixelData bytes (empty with header_only);
+    `encoding`: NATIVE, or RLE: `frames` are the files' RLE fragments and `segments` holds per sorted slice the (bits_allocated / 8, 2)
+    int64 table of each segment's byte offset into its fragment and byte length."""
     shape: Tuple[int, int, int]
     affine: Optional[np.ndarray]
     path: str
@@ -417,6 +491,8 @@ class DicomSeries:
     inters: List[float]
     frames: List[np.ndarray] = field(default_factory=list)
     files: List[str] = field(default_factory=list)       # the slices' paths in sorted order
+    encoding: str = NATIVE
+    segments: List[np.ndarray] = field(default_factory=list)
 
     def uniform_scale(self):
         """(slope, inter) when every slice carries the same pair bit for bit, else None."""
@@ -520,9 +596,13 @@ def read_series(directory, header_only=False) -> DicomSeries:
                            ("high_bit", "HighBit"), ("pixel_representation", "PixelRepresentation")):
             if getattr(s, name) != getattr(first, name):
                 raise ConfigurationError(f"{d}: {first.path} and {s.path} differ in {what} ({getattr(first, name)} and {getattr(s, name)})")
+        if s.encoding != first.encoding:
+            raise ConfigurationError(f"{d}: {first.path} ({first.transfer_syntax}) and {s.path} ({s.transfer_syntax}) mix uncompressed and RLE "
+                                     "lossless files in one series")
     slices, lps = _geometry(slices, d)
     affine = None if lps is None else lps_to_ras(lps)
     first = slices[0]
     return DicomSeries((int(first.columns), int(first.rows), len(slices)), affine, d, int(first.bits_allocated), int(first.bits_stored),
                        int(first.high_bit), bool(first.pixel_representation), [float(s.slope) for s in slices], [float(s.inter) for s in slices],
-                       [] if header_only else [s.frame for s in slices], [s.path for s in slices])
+                       [] if header_only else [s.frame for s in slices], [s.path for s in slices], first.encoding,
+                       [s.segments for s in slices] if first.encoding == RLE else [])

@@ -7,6 +7,7 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     upload(volume, device)                          host volume (NiftiImage, DicomSeries or ndarray) -> DeviceVolume
     stage_mask(scan, mask, device)                  host mask of any source -> DeviceVolume, or Staged{Contours,Frames} that wait for their kernel
     decode_series(series, device)                   a sorted DICOM series -> DeviceVolume: the slices' bytes decoded on device (mmnn_decode_slices)
+                                                    (an RLE Lossless series: its fragments expanded first, mmnn_rle_expand)
     rasterize_contours(contours, scan, device)      the contours of an RTSTRUCT ROI -> uint8 0 / 1 on the scan's grid (mmnn_rasterize_contours)
     unpack_frames(frames, scan, device)             the frames of a DICOM SEG segment -> uint8 0 / 1 on the scan's grid, or 0 / 255 on the
                                                     segmentation's own (mmnn_unpack_frames)
@@ -31,7 +32,9 @@ host forms one 3x4 matrix from the two headers (`nifti.index_map`) and the devic
 
 A DICOM series (`dicom.read_series`) takes one more step in front: its slices' PixelData bytes are uploaded as the files hold them and
 `mmnn_decode_slices` unpacks the stored bits, extends the sign and, where the slices differ in RescaleSlope / RescaleIntercept, rescales
-per slice.  A DICOM (scan, mask) pair always passes through `resample_mask` -- upstream always runs `sitk.Resample(mask, image)` and
+per slice.  An RLE Lossless series uploads its fragments as the files hold them, `mmnn_rle_expand` turns them into the bytes the uncompressed
+series would hold, and `mmnn_decode_slices` follows unchanged; the z status words are read back once per series, and a slice whose
+segment ended early is refused with its file named.  A DICOM (scan, mask) pair always passes through `resample_mask` -- upstream always runs `sitk.Resample(mask, image)` and
 `mask > 128` on that path -- with the identity map when the two series share one grid, and its default threshold is 128.
 
 A mask that is an RT Structure Set (`rtstruct.read` -> `ContourSet`) beside a DICOM scan is born on the scan's grid: the host maps the
@@ -54,7 +57,7 @@ import torch
 from .. import _lib
 from ..exceptions.exceptions import ConfigurationError
 from . import nifti, rtstruct, seg
-from .dicom import DicomSeries
+from .dicom import RLE, DicomSeries
 from .nifti import NiftiImage
 from .rtstruct import ContourSet
 from .seg import FrameSet
@@ -139,11 +142,16 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
     `mmnn_decode_slices` on the current stream; the host copies bytes and touches no voxel value.  When every slice carries the same
     RescaleSlope / RescaleIntercept and the ingest's descriptor holds that pair exactly (it carries float32, as a NIfTI header does),
     the volume keeps the integer type of (BitsAllocated, PixelRepresentation) and the pair goes into `slope` / `inter`, which the
-    ingest applies in fp64 like a NIfTI scl_slope; otherwise the kernel rescales per slice and the volume is float64, slope 1, inter 0."""
+    ingest applies in fp64 like a NIfTI scl_slope; otherwise the kernel rescales per slice and the volume is float64, slope 1, inter 0.
+    An RLE Lossless series (`series.encoding == 'rle'`) stages its segment table and its fragments in place of the slices' bytes,
+    each fragment on a 16-byte boundary, and `mmnn_rle_expand` runs in front of `mmnn_decode_slices`; the z status words are then read
+    back -- the one wait of this path -- and a slice whose segment ended before its plane was full raises ConfigurationError."""
     if not series.frames:
         raise ValueError(f"decode_series: {series.path} was read with header_only: it holds no voxel bytes")
     device = torch.device(device)
     x, y, z = (int(v) for v in series.shape)
+    if series.encoding == RLE:
+        return _decode_rle_series(series, device, x, y, z)
     frame_bytes = x * y * (series.bits_allocated // 8)
     if len(series.frames) != z or any(f.dtype != np.uint8 or f.size != frame_bytes for f in series.frames):
         raise ValueError(f"decode_series: {series.path}: {z} slices of {frame_bytes} bytes expected")
@@ -162,6 +170,52 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
     out = torch.empty(x * y * z * (series.bits_allocated // 8 if integer else 8), dtype=torch.uint8, device=device)
     _lib.enqueue("mmnn_decode_slices", ctypes.byref(desc), staged.data_ptr() + table_bytes, None if integer else staged.data_ptr(), out.data_ptr(),
                  device=device)
+    slope, inter = scale if integer else (1.0, 0.0)
+    return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
+
+
+def _decode_rle_series(series: DicomSeries, device, x: int, y: int, z: int) -> DeviceVolume:
+    """`decode_series` of an RLE Lossless series.  The pinned buffer: the scale table (when needed), the segment table ([z][B][2] int64:
+    byte offset into the payload, byte length), then the payload, i.e. the fragments in sorted order, each start aligned to 16 bytes."""
+    planes = series.bits_allocated // 8
+    if len(series.frames) != z or len(series.segments) != z or any(f.dtype != np.uint8 for f in series.frames) \
+            or any(np.asarray(t).shape != (planes, 2) for t in series.segments):
+        raise ValueError(f"decode_series: {series.path}: {z} RLE fragments with {planes} segments each expected")
+    scale = series.uniform_scale()
+    integer = scale is not None and all(float(np.float32(v)) == v for v in scale)
+    table_bytes = 0 if integer else z * 16
+    at_payload = table_bytes + z * planes * 16
+    starts = np.zeros(z + 1, dtype=np.int64)
+    np.cumsum([(f.size + 15) // 16 * 16 for f in series.frames], out=starts[1:])
+    payload_bytes = int(starts[-1])
+    stage = torch.empty(at_payload + payload_bytes, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    if not integer:
+        host[:table_bytes].view(np.float64)[:] = np.asarray([v for pair in zip(series.slopes, series.inters) for v in pair], dtype=np.float64)
+    table = host[table_bytes:at_payload].view(np.int64).reshape(z, planes, 2)
+    for k, (frame, segments) in enumerate(zip(series.frames, series.segments)):
+        table[k] = segments
+        table[k, :, 0] += starts[k]
+        at = at_payload + int(starts[k])
+        host[at:at + frame.size] = frame
+        host[at + frame.size:at_payload + int(starts[k + 1])] = 0
+    code = _integer_code(series.bits_allocated, series.signed) if integer else TYPE_CODES[np.dtype("float64")]
+    staged = stage.to(device, non_blocking=True)
+    words = torch.empty(x * y * z * planes, dtype=torch.uint8, device=device)
+    status = torch.empty(z, dtype=torch.int32, device=device)
+    ws = torch.empty(_lib.count("mmnn_rle_workspace_bytes", x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
+    rle = _lib.RleDesc(x, y, z, series.bits_allocated, payload_bytes)
+    _lib.enqueue("mmnn_rle_expand", ctypes.byref(rle), staged.data_ptr() + at_payload, staged.data_ptr() + table_bytes, words.data_ptr(),
+                 status.data_ptr(), ws.data_ptr(), device=device)
+    desc = _lib.DecodeSlicesDesc(x, y, z, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed), code)
+    out = torch.empty(x * y * z * (planes if integer else 8), dtype=torch.uint8, device=device)
+    _lib.enqueue("mmnn_decode_slices", ctypes.byref(desc), words.data_ptr(), None if integer else staged.data_ptr(), out.data_ptr(), device=device)
+    bad = np.flatnonzero(status.cpu().numpy())
+    if bad.size:
+        k = int(bad[0])
+        name = series.files[k] if k < len(series.files) else f"{series.path}: slice {k}"
+        raise ConfigurationError(f"{name}: malformed: an RLE segment ends before its {x} x {y} byte plane is full "
+                                 f"({bad.size} of the {z} slices of {series.path} are short)")
     slope, inter = scale if integer else (1.0, 0.0)
     return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
 

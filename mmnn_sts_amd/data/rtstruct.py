@@ -87,7 +87,7 @@ def read(path, header_only=False) -> ContourSet:
     """Parse an RTSTRUCT file.  With `header_only` the walk stops behind StructureSetROISequence: the ROI names alone."""
     with part10(path) as f:
         path, buf = f.path, f.buf
-        explicit = _check_syntax(f.syntax, path)
+        explicit, _ = _check_syntax(f.syntax, path)
         top, _ = walk(buf, f.off, f.size, explicit, path, KEPT, ENTERED, stop_after=STRUCTURE_SET_ROI_SEQUENCE if header_only else None)
         sop = _text(buf, top[SOP_CLASS_UID]) if SOP_CLASS_UID in top else None
         if sop != RT_STRUCTURE_SET_STORAGE:

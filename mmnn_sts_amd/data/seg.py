@@ -153,7 +153,7 @@ def read(path, header_only=False) -> FrameSet:
         if syntax == "1.2.840.10008.1.2.5":
             _refuse(path, f"transfer syntax {syntax} (RLE lossless, an encapsulated, compressed syntax) is outside the path: only uncompressed "
                           "little endian files are read; decompress the file first")
-        explicit = _check_syntax(syntax, path)
+        explicit, _ = _check_syntax(syntax, path)
         top, _ = walk(buf, part.off, size, explicit, path, KEPT, ENTERED, pixel_data=True)
         sop = _text(buf, top[SOP_CLASS_UID]) if SOP_CLASS_UID in top else None
         if sop != SEGMENTATION_STORAGE:

@@ -1,6 +1,7 @@
 """A minimal DICOM writer and the DICOM twin of a `synth_nifti.write_tree` tree, for the tests, the timing tool and a first run of
 `main.py --image_loc` on the DICOM layout (`mmnn_sts_amd.data.ImageDatasets`).  A test and demo aid, like `synth_nifti`: it writes what
-`mmnn_sts_amd.data.dicom` reads (uncompressed, one frame per file, explicit VR little endian, or implicit on request) and nothing else.
+`mmnn_sts_amd.data.dicom` reads (one frame per file; uncompressed in explicit VR little endian, or implicit on request, or RLE Lossless
+with `transfer_syntax="rle"`) and nothing else.
 
     <root>/images/t1/SYN-0007-t1-a/image/series_1/0003.dcm ...     one file per slice, names in a seeded random order
     <root>/images/t1/SYN-0007-t1-a/mask/series_1/0011.dcm ...      the mask as an 8-bit image series, 0 / 255
@@ -8,7 +9,7 @@
     <root>/images/t1/SYN-0007-t1-a/mask/seg.dcm                    with mask_format="seg": the mask as one BINARY Segmentation object
     <root>/key.csv, clinical.csv, train_uids.txt, val_uids.txt     copied from the NIfTI tree
 
-    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct | seg]
+    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct | seg] [--transfer_syntax rle]
 
 The twin holds the same voxels -- slice k, row j, column i is the NIfTI voxel (i, j, k) -- and the same geometry: ImagePositionPatient,
 ImageOrientationPatient and PixelSpacing are the NIfTI affine's columns in LPS (a sheared or left-handed affine has no such form and is
@@ -24,12 +25,13 @@ import numpy as np
 
 from ..exceptions.exceptions import ConfigurationError
 from . import nifti
-from .dicom import EXPLICIT_LE, IMPLICIT_LE, LONG_VRS
+from .dicom import EXPLICIT_LE, IMPLICIT_LE, LONG_VRS, RLE_LOSSLESS
 
 MR_IMAGE_STORAGE = "1.2.840.10008.5.1.4.1.1.4"
 RT_STRUCTURE_SET_STORAGE = "1.2.840.10008.5.1.4.1.1.481.3"
 SEGMENTATION_STORAGE = "1.2.840.10008.5.1.4.1.1.66.4"
 MASK_FORMATS = ("series", "rtstruct", "seg")
+TRANSFER_SYNTAXES = ("native", "rle")
 UID_ROOT = "1.2.3.4.5"                       # not a registered root: synthetic files only
 
 
@@ -60,19 +62,81 @@ def _text(values) -> bytes:
     return "\\".join(values if isinstance(values, (list, tuple)) else [values]).encode("ascii")
 
 
+def packbits(row) -> bytes:
+    """One row of bytes as PackBits runs (PS3.5 G.3.1): a stretch of 2 or more equal bytes becomes repeat runs (control byte 257 - n,
+    n <= 128, then the byte; a single byte left over becomes a literal of one), the bytes between such stretches literal runs (control
+    byte n - 1, n <= 128, then the n bytes)."""
+    row = np.ascontiguousarray(row, dtype=np.uint8).reshape(-1)
+    n = row.size
+    if n == 0:
+        return b""
+    starts = np.concatenate(([0], np.flatnonzero(row[1:] != row[:-1]) + 1))
+    lengths = np.diff(np.concatenate((starts, [n])))
+    repeats = np.flatnonzero(lengths >= 2)
+    out = bytearray()
+    k, m = 0, len(starts)
+    while k < m:
+        if lengths[k] >= 2:
+            value, left = int(row[starts[k]]), int(lengths[k])
+            while left >= 2:
+                take = min(left, 128)
+                out += bytes((257 - take, value))
+                left -= take
+            if left:
+                out += bytes((0, value))
+            k += 1
+            continue
+        j = np.searchsorted(repeats, k)                                                  # the next stretch of equal bytes
+        j = int(repeats[j]) if j < len(repeats) else m
+        a, b = int(starts[k]), (int(starts[j]) if j < m else n)
+        for at in range(a, b, 128):
+            piece = row[at:min(at + 128, b)]
+            out += bytes((piece.size - 1,)) + piece.tobytes()
+        k = j
+    return bytes(out)
+
+
+def rle_fragment(pixels) -> bytes:
+    """A (Rows, Columns) frame as one RLE fragment (PS3.5 Annex G): the 64-byte header (the segment count and 15 offsets from the start
+    of the header, unused ones zero), then one segment per byte of the word, the most significant byte plane first, every row encoded
+    on its own (`packbits`) and every segment padded with a zero byte to even length."""
+    a = np.ascontiguousarray(pixels)
+    planes = a.astype(a.dtype.newbyteorder("<")).view(np.uint8).reshape(a.shape[0], a.shape[1], a.dtype.itemsize)
+    segments = []
+    for s in range(a.dtype.itemsize):
+        data = b"".join(packbits(row) for row in planes[:, :, a.dtype.itemsize - 1 - s])
+        segments.append(data + b"\0" * (len(data) % 2))
+    offsets, at = [], 64
+    for seg in segments:
+        offsets.append(at)
+        at += len(seg)
+    return struct.pack("<16I", len(segments), *offsets, *([0] * (15 - len(offsets)))) + b"".join(segments)
+
+
+def _encapsulated(fragment: bytes) -> bytes:
+    """PixelData of undefined length (explicit VR): an empty Basic Offset Table, one fragment, the sequence delimiter."""
+    return (struct.pack("<HH2sHI", 0x7FE0, 0x0010, b"OB", 0, 0xFFFFFFFF) + struct.pack("<HHI", 0xFFFE, 0xE000, 0)
+            + struct.pack("<HHI", 0xFFFE, 0xE000, len(fragment)) + fragment + struct.pack("<HHI", 0xFFFE, 0xE0DD, 0))
+
+
 def file_bytes(pixels, bits_stored=None, high_bit=None, position=None, orientation=None, pixel_spacing=None, slope=None, inter=None,
                series_uid=UID_ROOT + ".1", instance_number=1, explicit=True, slice_thickness=None, spacing_between_slices=None,
-               sop_instance_uid=UID_ROOT + ".1.1") -> bytes:
+               sop_instance_uid=UID_ROOT + ".1.1", transfer_syntax="native") -> bytes:
     """One slice as a part-10 file.  `pixels`: a (Rows, Columns) array of uint8 / int8 / uint16 / int16 / uint32 / int32, written as
-    it is (the caller has placed the stored bits); geometry and rescale elements are left out when None."""
+    it is (the caller has placed the stored bits); geometry and rescale elements are left out when None.  `transfer_syntax` 'rle':
+    RLE Lossless, whose data set is explicit VR and whose PixelData is encapsulated (`rle_fragment`)."""
     a = np.ascontiguousarray(pixels)
     if a.ndim != 2 or a.dtype.kind not in "iu" or a.dtype.itemsize not in (1, 2, 4):
         raise ConfigurationError(f"a slice is a 2-D array of 8, 16 or 32-bit integers, got {a.dtype} {a.shape}")
+    if transfer_syntax not in TRANSFER_SYNTAXES:
+        raise ConfigurationError(f"transfer_syntax {transfer_syntax!r} is none of {TRANSFER_SYNTAXES}")
+    if transfer_syntax == "rle" and not explicit:
+        raise ConfigurationError("an RLE Lossless data set is explicit VR little endian: explicit=False cannot be combined with it")
     bits = a.dtype.itemsize * 8
     bits_stored = bits if bits_stored is None else int(bits_stored)
     high_bit = bits_stored - 1 if high_bit is None else int(high_bit)
     us = lambda v: struct.pack("<H", v)
-    syntax = EXPLICIT_LE if explicit else IMPLICIT_LE
+    syntax = RLE_LOSSLESS if transfer_syntax == "rle" else EXPLICIT_LE if explicit else IMPLICIT_LE
     meta = b"".join([_element(0x0002, 0x0001, "OB", b"\0\1", True), _element(0x0002, 0x0002, "UI", _text(MR_IMAGE_STORAGE), True),
                      _element(0x0002, 0x0003, "UI", _text(sop_instance_uid), True), _element(0x0002, 0x0010, "UI", _text(syntax), True),
                      _element(0x0002, 0x0012, "UI", _text(UID_ROOT + ".0"), True)])
@@ -106,7 +170,10 @@ def file_bytes(pixels, bits_stored=None, high_bit=None, position=None, orientati
         add(0x0028, 0x1052, "DS", _text(ds(inter)))
     if slope is not None:
         add(0x0028, 0x1053, "DS", _text(ds(slope)))
-    add(0x7FE0, 0x0010, "OB" if bits == 8 else "OW", a.astype(a.dtype.newbyteorder("<")).tobytes())
+    if transfer_syntax == "rle":
+        e.append(_encapsulated(rle_fragment(a)))
+    else:
+        add(0x7FE0, 0x0010, "OB" if bits == 8 else "OW", a.astype(a.dtype.newbyteorder("<")).tobytes())
     return b"\0" * 128 + b"DICM" + meta + b"".join(e)
 
 
@@ -141,9 +208,10 @@ def _stored(volume, bits_stored, rng):
 
 
 def write_series(directory, volume, affine=None, slope=None, inter=None, series_uid=UID_ROOT + ".1", shuffle_names=True, seed=0,
-                 bits_stored=None, per_slice_scale=False, explicit=True):
+                 bits_stored=None, per_slice_scale=False, explicit=True, transfer_syntax="native"):
     """Write the (x, y, z) integer `volume` as z slice files under `directory`.  `per_slice_scale`: slice k carries its own pair,
-    slope (1 + (k % 4) / 8) and inter - 3.5 k, so that the series has no shared scale."""
+    slope (1 + (k % 4) / 8) and inter - 3.5 k, so that the series has no shared scale.  `transfer_syntax`: 'native' (uncompressed) or
+    'rle' (RLE Lossless)."""
     volume = np.asarray(volume)
     if volume.ndim != 3:
         raise ConfigurationError(f"a volume has three axes, got {volume.shape}")
@@ -159,7 +227,7 @@ def write_series(directory, volume, affine=None, slope=None, inter=None, series_
         if per_slice_scale:
             s, i = (1.0 if slope is None else slope) * (1.0 + (k % 4) / 8.0), (0.0 if inter is None else inter) - 3.5 * k
         data = file_bytes(words[:, :, k].T, bits_stored, None, first + k * step, orientation, spacing, s, i, series_uid, int(numbers[k]) + 1,
-                          explicit, float(np.linalg.norm(step)), float(np.linalg.norm(step)), f"{series_uid}.{k + 1}")
+                          explicit, float(np.linalg.norm(step)), float(np.linalg.norm(step)), f"{series_uid}.{k + 1}", transfer_syntax)
         with open(os.path.join(directory, f"{int(names[k]):04d}.dcm"), "wb") as f:
             f.write(data)
     return directory
@@ -330,14 +398,14 @@ def write_seg(path, mask, affine, label="GTV", extra_segments=(), explicit=True,
 
 
 def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, seed=0, bits_stored=None, per_slice_scale=False,
-                    mask_format="series", roi_name="GTV", extra_rois=()):
+                    mask_format="series", roi_name="GTV", extra_rois=(), transfer_syntax="native"):
     """The DICOM twin of a `synth_nifti.write_tree` tree; returns the same dictionary of locations.  Scans keep their type, slope and
     inter (as RescaleSlope / RescaleIntercept); non-zero mask voxels become `mask_value` (None: the mask's values are kept) in an 8-bit
     unsigned series.  `bits_stored`, `per_slice_scale`: of the scans (see `write_series`).  `mask_format` 'rtstruct': the mask directory
     holds one RT Structure Set file instead (`write_rtstruct` of the non-zero mask voxels on the scan's geometry, ROI `roi_name`,
     with `extra_rois`); the mask must then share the scan's extents.  `mask_format` 'seg': one BINARY Segmentation object
     instead (`write_seg` of the non-zero mask voxels, segment `roi_name`, with `extra_rois` as further segments), written on the
-    mask's own grid when that is another than its scan's."""
+    mask's own grid when that is another than its scan's.  `transfer_syntax`: of the scans and of the masks written as series."""
     if mask_format not in MASK_FORMATS:
         raise ConfigurationError(f"mask_format {mask_format!r} is none of {MASK_FORMATS}")
     nifti_root, dicom_root = str(nifti_root), str(dicom_root)
@@ -365,7 +433,7 @@ def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, 
             target = os.path.join(out["image_loc"], mod, patient)
             scaling = scan.scaling() or (None, None)
             write_series(os.path.join(target, "image", "series_1"), scan.raw, scan.affine, scaling[0], scaling[1], f"{UID_ROOT}.{count}.1",
-                         shuffle_names, seed + 2 * count, bits_stored, per_slice_scale)
+                         shuffle_names, seed + 2 * count, bits_stored, per_slice_scale, transfer_syntax=transfer_syntax)
             if mask_format == "rtstruct":
                 if mask.raw.shape != scan.raw.shape:
                     raise ConfigurationError(f"{d}: an RTSTRUCT twin is drawn on the scan's grid; the mask's extents {mask.raw.shape} differ from {scan.raw.shape}")
@@ -377,7 +445,7 @@ def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, 
                 continue
             m = mask.raw if mask_value is None else np.where(mask.raw != 0, mask_value, 0)
             write_series(os.path.join(target, "mask", "series_1"), m.astype(np.uint8), mask.affine, None, None, f"{UID_ROOT}.{count}.2",
-                         shuffle_names, seed + 2 * count + 1)
+                         shuffle_names, seed + 2 * count + 1, transfer_syntax=transfer_syntax)
     return out
 
 
@@ -389,7 +457,8 @@ if __name__ == "__main__":
     ap.add_argument("--bits_stored", type=int, default=None)
     ap.add_argument("--per_slice_scale", action="store_true")
     ap.add_argument("--mask_format", choices=MASK_FORMATS, default="series", help="the masks as 8-bit image series, as RT Structure Set files or as BINARY Segmentation objects")
+    ap.add_argument("--transfer_syntax", choices=TRANSFER_SYNTAXES, default="native", help="of the scans and of the masks written as series: uncompressed, or RLE Lossless")
     a = ap.parse_args()
     for k, v in from_nifti_tree(a.nifti_dir, a.dicom_dir, seed=a.seed, bits_stored=a.bits_stored, per_slice_scale=a.per_slice_scale,
-                                mask_format=a.mask_format).items():
+                                mask_format=a.mask_format, transfer_syntax=a.transfer_syntax).items():
         print(f"{k}: {v}")

@@ -1,0 +1,195 @@
+"""The RLE Lossless path on the device.  `mmnn_rle_expand` against the numpy restatement of its contract (tests/_dicom_rle_ref.py), bit for
+bit on pixels and status, with every buffer inside a patterned guard buffer; a synth_nifti tree against its uncompressed and its RLE
+DICOM twins through `IngestCollate`, bit for bit (derived, not measured: the expansion is exact byte work and everything behind it is
+the code the uncompressed twin runs); and a series with a truncated segment, refused with its file named.
+
+Every stream here, the malformed ones first of all, passes the stand-alone host check of the decode core under the sanitizers
+(tests/test_dicom_rle_cpu.py::test_decode_core_on_the_host_under_sanitizers takes the same cases from `host_check_cases`)."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from mmnn_sts_amd import _lib
+from mmnn_sts_amd.data import cache as C
+from mmnn_sts_amd.data import dicom, ingest, synth_dicom, synth_nifti
+from mmnn_sts_amd.exceptions.exceptions import ConfigurationError
+from tests import _dicom_rle_ref as R
+from tests.test_dicom_rle_cpu import host_check_cases
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GUARD = 256
+PATTERN = 0xA5
+
+
+def _guarded(content, lead=GUARD):
+    """A device buffer of `content` (uint8 array, or a byte count to leave patterned) between two patterned guards; (buffer, lead, size)."""
+    n = content if isinstance(content, int) else content.size
+    buf = torch.full((lead + n + GUARD,), PATTERN, dtype=torch.uint8, device=DEV)
+    if not isinstance(content, int):
+        buf[lead:lead + n] = torch.from_numpy(np.array(content, dtype=np.uint8)).to(DEV)
+    return buf, lead, n
+
+
+def _expand(fragments, tables, x, y, bits):
+    """The kernel's (pixels (z, y, x), status (z,)).  Payload, segment table, pixels, status and workspace each sit inside a larger
+    buffer: the inputs must come back unchanged, the guards of all five must keep their pattern."""
+    z, B = len(fragments), bits // 8
+    payload, packed = R.pack_payload(fragments, tables)
+    pay = np.frombuffer(payload, dtype=np.uint8)
+    seg = np.ascontiguousarray(packed, dtype="<i8").view(np.uint8).reshape(-1)
+    bufs = {"payload": _guarded(pay), "segments": _guarded(seg), "pixels": _guarded(x * y * z * B), "status": _guarded(4 * z),
+            "workspace": _guarded(_lib.count("mmnn_rle_workspace_bytes", x, y, z, bits))}
+    ptr = {k: b.data_ptr() + lead for k, (b, lead, _) in bufs.items()}
+    desc = _lib.RleDesc(x, y, z, bits, pay.size)
+    _lib.check(_lib.lib().mmnn_rle_expand(ctypes.byref(desc), ptr["payload"], ptr["segments"], ptr["pixels"], ptr["status"], ptr["workspace"],
+                                          torch.cuda.current_stream().cuda_stream), "mmnn_rle_expand")
+    torch.cuda.synchronize()
+    host = {k: b.cpu().numpy() for k, (b, _, _) in bufs.items()}
+    for k, (_, lead, n) in bufs.items():
+        assert (host[k][:lead] == PATTERN).all() and (host[k][lead + n:] == PATTERN).all(), f"bytes outside `{k}` were written"
+    assert np.array_equal(host["payload"][GUARD:GUARD + pay.size], pay) and np.array_equal(host["segments"][GUARD:GUARD + seg.size], seg)
+    inner = lambda k: host[k][bufs[k][1]:bufs[k][1] + bufs[k][2]]
+    return inner("pixels").view(f"<u{B}").reshape(z, y, x), inner("status").view("<i4"), (payload, packed)
+
+
+def _assert_equals_restatement(name, fragments, tables, x, y, bits):
+    pixels, status, (payload, packed) = _expand(fragments, tables, x, y, bits)
+    want_pixels, want_status = R.rle_expand_ref([payload] * len(fragments), list(packed), x, y, bits)
+    assert np.array_equal(status, want_status), f"{name}: status {status.tolist()}, restatement {want_status.tolist()}"
+    bad = np.argwhere(pixels != want_pixels)
+    assert bad.shape[0] == 0, (f"{name}: {bad.shape[0]} words differ, the first at (k, j, i) = {tuple(bad[0])}: device "
+                               f"{int(pixels[tuple(bad[0])]):#x}, restatement {int(want_pixels[tuple(bad[0])]):#x}")
+    return pixels, status
+
+
+@pytest.mark.parametrize("name", sorted(R.volumes()))
+def test_encoded_volumes_expand_to_the_uncompressed_bytes(name):
+    vol = R.volumes()[name]
+    x, y, z = vol.shape
+    bits = vol.dtype.itemsize * 8
+    fragments = [synth_dicom.rle_fragment(vol[:, :, k].T) for k in range(z)]
+    tables = [R.segment_table(f, bits) for f in fragments]
+    pixels, status = _assert_equals_restatement(name, fragments, tables, x, y, bits)
+    assert not status.any() and pixels.tobytes() == vol.astype(vol.dtype.newbyteorder("<")).tobytes(order="F")
+    if name == "256x64x2_i16_noise":            # each segment is longer than its plane and needs several chunks
+        assert all(int(t[:, 1].min()) > x * y > _lib.RLE_CHUNK for t in tables)
+    if name == "64x64x3_i32":
+        assert max(len(f) for f in fragments) > 20 * min(len(f) for f in fragments)
+
+
+@pytest.mark.parametrize("name", sorted(R.hand_streams(_lib.RLE_CHUNK)))
+def test_hand_built_streams(name):
+    x, y, bits, streams = R.hand_streams(_lib.RLE_CHUNK)[name]
+    fragment, table = R.rle_fragment(streams)
+    _, status = _assert_equals_restatement(name, [fragment], [table], x, y, bits)
+    assert not status.any()
+    if "straddles" in name:
+        assert len(streams[0]) > 2 * _lib.RLE_CHUNK
+
+
+def test_two_calls_give_identical_bytes():
+    x, y, bits, streams = R.hand_streams(_lib.RLE_CHUNK)["literal_straddles_50_before"]
+    fragment, table = R.rle_fragment(streams)
+    a, b = (_expand([fragment], [table], x, y, bits) for _ in range(2))
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+
+
+@pytest.mark.parametrize("bits", [8, 16])
+@pytest.mark.parametrize("name", sorted(R.malformed_streams()))
+def test_malformed_segment_fails_its_frame_alone(name, bits):
+    fragments, tables, x, y, _ = R.malformed_frames(name, bits)
+    pixels, status = _assert_equals_restatement(name, fragments, tables, x, y, bits)
+    assert status.tolist() == [0, 1, 0]
+    stream, produced = R.malformed_streams()[name], R.MALFORMED_PRODUCED[name]
+    low = (pixels[1].reshape(-1) & 0xFF).astype(np.uint8)        # the malformed stream is the last segment: the least significant byte plane
+    assert produced < x * y and not low[produced:].any(), "the bad plane's tail is not zero"
+    assert np.array_equal(low[:produced], R.packbits_decode(stream, produced)[0]) and (produced == 0 or low[:produced].any())
+    for k in (0, 2):                            # the sound frames, against their own streams alone
+        alone, ok = R.rle_expand_ref([fragments[k]], [tables[k]], x, y, bits)
+        assert not ok.any() and np.array_equal(pixels[k], alone[0])
+
+
+def test_segment_tables_that_lie_are_clamped():
+    cases = {c[0]: c for c in host_check_cases()}
+    for name in ("offset_far_past_the_payload", "negative_offset", "length_past_the_payload", "negative_length", "offset_at_the_last_byte"):
+        _, x, y, z, bits, fragments, tables = cases[name]
+        _assert_equals_restatement(name, fragments, tables, x, y, bits)
+
+
+# ---- a NIfTI tree, its uncompressed twin and its RLE twin through the collate ------------------------------------------------------------
+def _dataset(tree):
+    from mmnn_sts_amd.data.ImageDatasets import T1T2SurvivalDataset
+    return T1T2SurvivalDataset(os.path.join(tree["image_loc"], "t1"), os.path.join(tree["image_loc"], "t2"), tree["data_loc"], tree["key_loc"])
+
+
+@pytest.fixture(scope="module")
+def trees(tmp_path_factory):
+    root = tmp_path_factory.mktemp("rle_twins")
+    n = synth_nifti.write_tree(root / "nifti", n_patients=2, seed=21)
+    d = synth_dicom.from_nifti_tree(root / "nifti", root / "native", seed=21)
+    r = synth_dicom.from_nifti_tree(root / "nifti", root / "rle", seed=21, transfer_syntax="rle")
+    return n, d, r
+
+
+def test_three_twins_give_the_same_batch(trees):
+    sets = [_dataset(t) for t in trees]
+    assert [s.layout for s in sets] == ["nifti", "dicom", "dicom"] and sets[0].uids == sets[1].uids == sets[2].uids
+    for scan, mask in sets[2][0][0].volumes:    # the scan AND the mask are RLE series
+        assert scan.encoding == mask.encoding == "rle" and mask.bits_allocated == 8 and scan.bits_allocated == 16
+        assert sum(f.size for f in mask.frames) < mask.shape[0] * mask.shape[1] * mask.shape[2] // 4        # a mask compresses to almost nothing
+    assert all(scan.encoding == "native" for scan, _ in sets[1][0][0].volumes)
+    results = []
+    for ds, threshold in zip(sets, (0.5, None, None)):      # a DICOM pair is resampled and binarised at 128 (tests/test_dicom_gpu.py)
+        collate = ingest.IngestCollate(DEV, mask_threshold=threshold)
+        x, ev, du = collate([ds[0], ds[1]])
+        torch.cuda.synchronize()
+        results.append((x, collate.pending[-1][1]))
+    (x_n, e_n), (x_d, e_d), (x_r, e_r) = results
+    assert x_n.shape == (2, 2, 64, 64, 64) and float(x_n.abs().max()) > 0.0 and int(e_n.min()) > 0
+    assert torch.equal(e_n, e_d) and torch.equal(e_d, e_r)
+    assert torch.equal(x_d, x_r), f"{int((x_d != x_r).sum())} elements differ between the uncompressed and the RLE twin"
+    assert torch.equal(x_n, x_r), f"{int((x_n != x_r).sum())} elements differ between the NIfTI tree and the RLE twin"
+
+
+def test_rle_twin_through_the_volume_cache(trees):
+    from mmnn_sts_amd.data.ImageDatasets import ImageDatasetByUIDs
+    native, rle = _dataset(trees[1]), _dataset(trees[2])
+    plain = ingest.IngestCollate(DEV, mask_threshold=None)
+    want, _, _ = plain([native[0], native[1]])
+    want_extents = plain.pending[-1][1]
+    cache = C.VolumeCache(DEV, 2, 64, 2)
+    collate = ingest.IngestCollate(DEV, mask_threshold=None, cache=cache)
+    sub = C.CachedByUIDs(rle, rle.uids, cache)
+    for what in ("filling the cache", "from the cache"):
+        got, _, _ = collate([sub[0], sub[1]])
+        torch.cuda.synchronize()
+        assert torch.equal(got, want) and torch.equal(collate.pending[-1][1], want_extents), what
+    assert isinstance(sub[0][0], C.CachedPatient) and isinstance(ImageDatasetByUIDs(rle, rle.uids)[0][0], ingest.RawPatient)
+
+
+def test_a_truncated_segment_is_refused_with_its_file_named_and_the_next_series_ingests(tmp_path):
+    vol = np.random.default_rng(9).integers(-300, 300, (20, 12, 4)).astype("i2")
+    synth_dicom.write_series(tmp_path / "good", vol, slope=0.5, inter=-3.0, shuffle_names=False, transfer_syntax="rle")
+    synth_dicom.write_series(tmp_path / "bad", vol, slope=0.5, inter=-3.0, shuffle_names=False, transfer_syntax="rle")
+    victim = str(tmp_path / "bad" / "0002.dcm")
+    data = open(victim, "rb").read()
+    head = dicom.read_file(victim, header_only=True)
+    # drop the last 8 bytes of the fragment's last segment: the item grows shorter, the header's offsets stay right, the host finds no fault
+    at = data.rindex(b"\xfe\xff\x00\xe0")
+    length = int.from_bytes(data[at + 4:at + 8], "little")
+    cut = data[:at + 4] + (length - 8).to_bytes(4, "little") + data[at + 8:at + 8 + length - 8] + data[at + 8 + length:]
+    with open(victim, "wb") as f:
+        f.write(cut)
+    series = dicom.read_series(tmp_path / "bad")
+    assert series.encoding == "rle" and int(series.segments[2][-1, 1]) == int(head.segments[-1, 1]) - 8
+    with pytest.raises(ConfigurationError, match="RLE segment ends before") as err:
+        ingest.upload(series, DEV)
+    assert victim in str(err.value)
+    v = ingest.upload(dicom.read_series(tmp_path / "good"), DEV)
+    torch.cuda.synchronize()
+    assert v.from_dicom and v.datatype == 4 and (v.slope, v.inter) == (0.5, -3.0)
+    assert np.array_equal(np.frombuffer(v.data.cpu().numpy().tobytes(), dtype="<i2").reshape(vol.shape, order="F"), vol)
