@@ -528,6 +528,54 @@ int64_t mmnn_rle_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bits_a
 int mmnn_rle_expand(const mmnn_rle_desc* d, const void* payload, const int64_t* segments, void* pixels, int32_t* status, void* workspace,
                     void* stream);
 
+/* ---- DICOM JPEG Lossless decode: the entropy-coded data of a sorted single-frame series in transfer syntax 1.2.840.10008.1.2.4.70
+ * (T.81 Annex H: process 14, selection value 1) or 1.2.840.10008.1.2.4.57 with predictor 1 -> exactly the bytes an uncompressed series
+ * would hold, i.e. the `pixels` of mmnn_decode_slices: little-endian words of bits_allocated bits, x (the column) fastest, the z frames
+ * in order (csrc/dicom_jpegll.hip, csrc/jpegll_core.hpp).  `payload`: the z fragments back to back as the files hold them (marker
+ * segments included), each start aligned to 16 bytes, payload_bytes in all.  `frames`: DEVICE memory, one record per frame: the byte
+ * offset into `payload` and the byte length of what follows the SOS segment, the precision P, and the Huffman table SOS selects as its
+ * 16 BITS counts and up to 17 HUFFVALs (unused ones 0).
+ *   byte stuffing  inside the data FF 00 stands for the byte FF; FF followed by anything else, or FF as the last byte, ends the data
+ *                  there.
+ *   codes          canonical, built from BITS / HUFFVAL as T.81 Annex C builds them; the decoded value SSSS lies in 0..16.
+ *   differences    (T.81 H.1.2.2, F.2.2.1) SSSS 0: 0.  SSSS 1..15: the next SSSS bits are v, most significant first; the difference is
+ *                  v if v >= 2^(SSSS-1), else v - 2^SSSS + 1.  SSSS 16: 32768, and no further bits are read.
+ *   prediction     all modulo 2^16: the first sample of the frame is predicted 2^(P-1), every other sample of the first row from its left
+ *                  neighbour, the first sample of every later row from the sample above it, every other sample from its left neighbour.
+ *                  The stored word is the low bits_allocated bits of prediction + difference.  So the x*y samples are two prefix sums of
+ *                  the differences, one down column 0 and one along each row, and that is how they are computed.
+ *   a full frame   decoding stops after x*y symbols; whatever follows (pad bits, EOI, trailing bytes) is ignored.
+ *   a short frame  a symbol is cut when its code and extra bits do not all lie in front of the end of the data, when its first 16 bits,
+ *                  padded with 1-bits behind the end, match no code, or when its decoded value exceeds 16.  A cut symbol gives no output
+ *                  and ends the frame: status[k] is 1 and the missing differences count as 0.  Every other frame is unaffected.
+ *   trust          nothing in `frames` or `payload` is trusted: offset and length are clamped into the payload, P into 2..16, the BITS
+ *                  counts so that they sum to at most 17, and a HUFFVAL above 16 cuts the symbol that decodes to it.  What a table
+ *                  that the host reader refuses (over-subscribed, repeated values) decodes to is bounded but otherwise unspecified.
+ * status[k] is 0 for a frame that was filled; every status word and every byte of `pixels` is written.  No read ever leaves
+ * [payload, payload + payload_bytes) and no write ever leaves `pixels`, `status` or `workspace`, whatever the bytes hold.  `workspace`:
+ * mmnn_jpegll_workspace_bytes bytes (the differences as 16-bit words, and every row's first sample).  Two launches; no atomics, no host
+ * synchronisation: repeated calls are bit-identical.  A frame's data passes through LDS in chunks of MMNN_JPEGLL_CHUNK bytes as the file
+ * holds them (stuffed zeros included).  Refused (status 1) before any launch: a null pointer, a non-positive extent, x*y*z >= 2^31,
+ * bits_allocated outside {8, 16}, payload_bytes < 1, payload or workspace not aligned to 16 bytes, frames not aligned to 8, status not
+ * to 4, pixels not to its element size, pixels or status overlapping payload. */
+#define MMNN_JPEGLL_CHUNK 1024
+typedef struct {
+  int32_t x, y, z;                /* Columns, Rows, slices */
+  int32_t bits_allocated;         /* 8, 16 */
+  int64_t payload_bytes;
+} mmnn_jpegll_desc;
+typedef struct {
+  int64_t offset, length;         /* of the entropy-coded data, in `payload` */
+  int32_t precision;              /* P of SOF3 */
+  uint8_t bits[16];               /* BITS: the number of codes of each length 1..16 */
+  uint8_t huffval[17];            /* HUFFVAL: the values in code order */
+  uint8_t reserved[3];
+} mmnn_jpegll_frame;              /* 56 bytes */
+/* bytes of device scratch; grows with every extent; -1 on a bad extent or bits_allocated.  Needs no GPU. */
+int64_t mmnn_jpegll_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bits_allocated);
+int mmnn_jpegll_decode(const mmnn_jpegll_desc* d, const void* payload, const mmnn_jpegll_frame* frames, void* pixels, int32_t* status,
+                       void* workspace, void* stream);
+
 /* ---- RTSTRUCT contours -> a mask on the scan's grid: the planar polygons of one ROI of an RT Structure Set, already mapped by the host
  * into the scan's continuous voxel index space (a voxel centre sits at the integer index) and assigned to slices, filled into one byte
  * per scan voxel (csrc/rtstruct.hip).  `points`: n_points pairs (px, py) in fp64; `contours`: n_contours pairs (first point, point

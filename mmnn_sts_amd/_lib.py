@@ -129,6 +129,15 @@ class RleDesc(Structure):
     _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("bits_allocated", c_int32), ("payload_bytes", c_int64)]
 
 
+JPEGLL_CHUNK = 1024                          # MMNN_JPEGLL_CHUNK
+JPEGLL_FRAME_BYTES = 56                      # mmnn_jpegll_frame: int64 offset, length, int32 precision, 16 BITS, 17 HUFFVAL, 3 reserved
+
+
+class JpegllDesc(Structure):
+    """mmnn_jpegll_desc (include/mmnn_sts.h)."""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("z", c_int32), ("bits_allocated", c_int32), ("payload_bytes", c_int64)]
+
+
 RASTERIZE_CHUNK_EDGES = 1024                 # MMNN_RASTERIZE_CHUNK_EDGES
 
 
@@ -268,6 +277,7 @@ def _signatures():
         "mmnn_maps_to_scan_sized": [P(MapsToScanDesc), I, V, V, V, V, V],
         "mmnn_decode_slices": [P(DecodeSlicesDesc), V, V, V, V],
         "mmnn_rle_expand": [P(RleDesc), V, V, V, V, V, V],
+        "mmnn_jpegll_decode": [P(JpegllDesc), V, V, V, V, V, V],
         "mmnn_rasterize_contours": [P(RasterizeDesc), V, V, V, V, V],
         "mmnn_unpack_frames": [P(UnpackFramesDesc), V, V, V, V, V],
         "mmnn_gather_rows": [V, Q, Q, P(I), I, V, V],
@@ -296,6 +306,7 @@ def _signatures():
         "mmnn_ingest_workspace_bytes": [I, I, I],
         "mmnn_maps_to_scan_workspace_bytes": [I, I, I],
         "mmnn_rle_workspace_bytes": [I, I, I, I],
+        "mmnn_jpegll_workspace_bytes": [I, I, I, I],
         "mmnn_occlusion_window_count": [P(OcclusionDesc), P(I)],
         "mmnn_radiomics_workspace_bytes": [I, I, I, I],
         "mmnn_radiomics_texture_workspace_bytes": [I, I, I, I],

@@ -1,8 +1,9 @@
-"""A minimal DICOM reader for uncompressed and RLE Lossless single-frame series (numpy, mmap and struct only; pydicom / GDCM /
-SimpleITK are not dependencies): a directory of slice files -> the raw voxel bytes (or the RLE fragments), the per-slice rescale pairs
-and the voxel-index -> mm matrix that the device ingest takes (`mmnn_sts_amd.data.ingest.decode_series`).  The host opens files, parses
-headers and copies bytes; it never touches a voxel value -- expanding the PackBits runs of an RLE series (`mmnn_rle_expand`), unpacking
-the stored bits, sign extension and per-slice rescaling (`mmnn_decode_slices`) run on the device.
+"""A minimal DICOM reader for uncompressed, RLE Lossless and JPEG Lossless single-frame series (numpy, mmap and struct only; pydicom /
+GDCM / SimpleITK are not dependencies): a directory of slice files -> the raw voxel bytes (or the RLE / JPEG fragments), the per-slice
+rescale pairs and the voxel-index -> mm matrix that the device ingest takes (`mmnn_sts_amd.data.ingest.decode_series`).  The host opens
+files, parses headers and copies bytes; it never touches a voxel value -- expanding the PackBits runs of an RLE series
+(`mmnn_rle_expand`), Huffman decoding and prediction of a JPEG Lossless series (`mmnn_jpegll_decode`), unpacking the stored bits, sign
+extension and per-slice rescaling (`mmnn_decode_slices`) run on the device.
 
 Pinned to the published standard's element layout (PS3.5 / PS3.10): the 128-byte preamble and `DICM`; the file meta group (0002,xxxx),
 always explicit VR little endian; then the data set in the VR mode TransferSyntaxUID (0002,0010) names.  An explicit-VR element is
@@ -18,9 +19,14 @@ Accepted: implicit VR little endian (1.2.840.10008.1.2), explicit VR little endi
 explicit VR little endian and its PixelData is encapsulated (PS3.5 A.4): OB of undefined length holding the Basic Offset Table item
 (its content is ignored), one fragment item for the one frame, and the sequence delimiter.  The host reads the fragment's 64-byte
 header -- 16 little-endian uint32: the segment count (BitsAllocated / 8), then 15 offsets from the start of the header -- checks it and
-reads nothing behind it: `encoding` is 'rle', `frame` the whole fragment and `segments` its (offset, length) pairs.  Refused, with the
-file named: big endian, deflated, every other encapsulated (compressed) syntax, multi-frame and enhanced objects, colour, float /
-double pixel data, and a series that mixes uncompressed and RLE files.  A mask may also be an RT Structure Set: that file is read by
+reads nothing behind it: `encoding` is 'rle', `frame` the whole fragment and `segments` its (offset, length) pairs.  JPEG Lossless,
+Non-Hierarchical, First-Order Prediction (1.2.840.10008.1.2.4.70; T.81 Annex H, process 14 with selection value 1) and its sibling
+1.2.840.10008.1.2.4.57 when its scan header selects predictor 1 are encapsulated alike.  Of that fragment the host reads the marker
+segments in front of the entropy-coded data -- SOI, APPn / COM (skipped), DHT, SOF3, SOS -- and no entropy-coded byte: it does not
+un-stuff and does not look for EOI.  `encoding` is 'jpeg-lossless', `frame` the whole fragment and `jpeg` a `JpegScan`: the precision,
+the Huffman table SOS selects and where the data behind SOS lies.  Refused, with the file named: big endian, deflated, every other
+encapsulated (compressed) syntax -- JPEG baseline / extended, JPEG-LS, JPEG 2000 among them --, predictors 2-7, restart intervals,
+several fragments, multi-frame and enhanced objects, colour, float / double pixel data, and a series that mixes encodings.  A mask may also be an RT Structure Set: that file is read by
 `rtstruct.py`, or a BINARY DICOM Segmentation object, read by `seg.py`.  What the three readers share lives here once: `part10` (the
 one place a file is mapped), `walk` (the nested data-set walk that descends into the sequences `read_file` skips), the value helpers
 `_text` / `_integer` / `_floats`, `match_name` behind both `resolve`s and `lps_to_ras`.  `read_file` itself keeps refusing every
@@ -48,7 +54,9 @@ logger = logging.getLogger(__name__)
 IMPLICIT_LE = "1.2.840.10008.1.2"
 EXPLICIT_LE = "1.2.840.10008.1.2.1"
 RLE_LOSSLESS = "1.2.840.10008.1.2.5"
-NATIVE, RLE = "native", "rle"                # DicomFile.encoding
+JPEG_LOSSLESS, JPEG_LOSSLESS_SV1 = "1.2.840.10008.1.2.4.57", "1.2.840.10008.1.2.4.70"
+NATIVE, RLE, JPEGLL = "native", "rle", "jpeg-lossless"       # DicomFile.encoding
+_ENCODING_NAME = {RLE: "RLE lossless", JPEGLL: "JPEG lossless"}
 RLE_HEADER_BYTES = 64                        # 16 uint32: the segment count and 15 offsets
 _REFUSED_SYNTAX = {"1.2.840.10008.1.2.2": "explicit VR big endian", "1.2.840.10008.1.2.1.99": "deflated explicit VR little endian"}
 LONG_VRS = frozenset(("OB", "OD", "OF", "OL", "OV", "OW", "SQ", "SV", "UC", "UN", "UR", "UT", "UV"))
@@ -71,6 +79,20 @@ _ARITY = {"position": 3, "orientation": 6, "pixel_spacing": 2}
 
 class NotDicomError(ConfigurationError):
     """The file has no `DICM` magic (read_series skips such files)."""
+
+
+@dataclass
+class JpegScan:
+    """What the marker segments of a JPEG Lossless fragment say: `precision` P of SOF3; `lines`, `samples` per line; `bits`, the 16
+    BITS counts of the Huffman table SOS selects, and `huffval`, its values in code order (at most 17, each in 0..16); `offset`,
+    `length`: the bytes behind the SOS segment, relative to the fragment (entropy-coded data, EOI and whatever follows)."""
+    precision: int
+    lines: int
+    samples: int
+    bits: np.ndarray
+    huffval: np.ndarray
+    offset: int
+    length: int
 
 
 @dataclass
@@ -98,10 +120,11 @@ class DicomFile:
     sop_class_uid: Optional[str] = None
     pixel_offset: Optional[int] = None       # byte offset of the PixelData value in the file; None: the file has no PixelData
     pixel_length: Optional[int] = None       # its declared length
-    frame: Optional[np.ndarray] = None       # uint8 view of the rows * columns * bits_allocated / 8 voxel bytes, or, 'rle', of the whole
-                                             # fragment, header included (None with header_only)
-    encoding: str = NATIVE                   # NATIVE, or RLE: `frame` holds PackBits segments
+    frame: Optional[np.ndarray] = None       # uint8 view of the rows * columns * bits_allocated / 8 voxel bytes, or, 'rle' and
+                                             # 'jpeg-lossless', of the whole fragment, header included (None with header_only)
+    encoding: str = NATIVE                   # NATIVE, RLE: `frame` holds PackBits segments, or JPEGLL: a JPEG Lossless stream
     segments: Optional[np.ndarray] = None    # 'rle': (bits_allocated / 8, 2) int64, byte offset into the fragment and byte length
+    jpeg: Optional[JpegScan] = None          # 'jpeg-lossless'
 
     @property
     def has_image(self):
@@ -333,19 +356,24 @@ def _transfer_syntax(buf, path):
     return syntax, off
 
 
-def _check_syntax(syntax, path):
-    """(explicit VR?, encoding) of an accepted transfer syntax."""
+def _check_syntax(syntax, path, jpeg_lossless=False):
+    """(explicit VR?, encoding) of an accepted transfer syntax.  `jpeg_lossless`: the caller reads JPEG Lossless frames (`read_file`
+    does; an RTSTRUCT or SEG file in that syntax stays refused)."""
     if syntax in (IMPLICIT_LE, EXPLICIT_LE):
         return syntax == EXPLICIT_LE, NATIVE
     if syntax == RLE_LOSSLESS:
         return True, RLE
+    if jpeg_lossless and syntax in (JPEG_LOSSLESS, JPEG_LOSSLESS_SV1):
+        return True, JPEGLL
     if syntax in _REFUSED_SYNTAX:
-        _refuse(path, f"transfer syntax {syntax} ({_REFUSED_SYNTAX[syntax]}) is outside the path: only little endian files, uncompressed or RLE "
-                      "lossless, are read")
+        _refuse(path, f"transfer syntax {syntax} ({_REFUSED_SYNTAX[syntax]}) is outside the path: only little endian files, uncompressed, RLE "
+                      "lossless or JPEG lossless, are read")
     if syntax.startswith("1.2.840.10008.1.2.4."):
-        _refuse(path, f"transfer syntax {syntax} is encapsulated (compressed: JPEG / JPEG-LS / JPEG 2000 / MPEG / HEVC), which is outside the "
-                      "path: decompress the series first")
-    _refuse(path, f"transfer syntax {syntax} is not supported: only {IMPLICIT_LE}, {EXPLICIT_LE} and {RLE_LOSSLESS} are read")
+        _refuse(path, f"transfer syntax {syntax} is encapsulated (compressed: JPEG baseline / extended, JPEG-LS, JPEG 2000, MPEG, HEVC; of that "
+                      f"family only JPEG Lossless image series, {JPEG_LOSSLESS_SV1} and {JPEG_LOSSLESS} with predictor 1, are read), which is "
+                      "outside the path: decompress the series first")
+    _refuse(path, f"transfer syntax {syntax} is not supported: only {IMPLICIT_LE}, {EXPLICIT_LE}, {RLE_LOSSLESS}, {JPEG_LOSSLESS_SV1} and "
+                  f"{JPEG_LOSSLESS} are read")
 
 
 def _validate(f: DicomFile, size: int):
@@ -369,10 +397,10 @@ def _validate(f: DicomFile, size: int):
         _refuse(path, f"HighBit {f.high_bit} outside {f.bits_stored - 1}..{f.bits_allocated - 1} (BitsStored - 1 .. BitsAllocated - 1)")
     if f.pixel_representation not in (0, 1):
         _refuse(path, f"PixelRepresentation {f.pixel_representation} is neither 0 nor 1")
-    if f.encoding == RLE:
+    if f.encoding != NATIVE:
         if f.pixel_length != UNDEFINED:
-            _refuse(path, f"transfer syntax {f.transfer_syntax} (RLE lossless) is compressed and needs encapsulated PixelData of undefined length; "
-                          f"this PixelData declares {f.pixel_length} bytes")
+            _refuse(path, f"transfer syntax {f.transfer_syntax} ({_ENCODING_NAME[f.encoding]}) is compressed and needs encapsulated PixelData of "
+                          f"undefined length; this PixelData declares {f.pixel_length} bytes")
         return None
     if f.pixel_length == UNDEFINED:
         _refuse(path, "PixelData of undefined length (encapsulated, i.e. compressed, frames) is outside the path")
@@ -383,9 +411,9 @@ def _validate(f: DicomFile, size: int):
     return need
 
 
-def _rle_fragment(buf, f: DicomFile, size: int):
-    """The one fragment of an RLE file's encapsulated PixelData as (offset in the file, length), its header checked and `f.segments`
-    set.  Nothing behind the 64-byte header is read."""
+def _fragment(buf, f: DicomFile, size: int):
+    """The one fragment of encapsulated PixelData (PS3.5 A.4) as (offset in the file, length): the Basic Offset Table item, whose
+    content is ignored, one fragment item, the sequence delimiter.  No byte of the fragment is read."""
     path = f.path
 
     def item(off, what):
@@ -412,7 +440,14 @@ def _rle_fragment(buf, f: DicomFile, size: int):
         fragments.append(fragment)
     if len(fragments) != 1:
         _refuse(path, f"{len(fragments)} fragments in PixelData: one frame per file in exactly one fragment is read")
-    at, length = fragments[0]
+    return fragments[0]
+
+
+def _rle_fragment(buf, f: DicomFile, size: int):
+    """The one fragment of an RLE file's encapsulated PixelData as (offset in the file, length), its header checked and `f.segments`
+    set.  Nothing behind the 64-byte header is read."""
+    path = f.path
+    at, length = _fragment(buf, f, size)
     if length % 2:
         _refuse(path, f"malformed: an RLE fragment of odd length {length}")
     if length < RLE_HEADER_BYTES:
@@ -432,13 +467,115 @@ def _rle_fragment(buf, f: DicomFile, size: int):
     return at, length
 
 
+def _huffman_tables(buf, off, end, path, tables):
+    """The tables of one DHT segment's body buf[off:end] into `tables`: {identifier: (BITS, HUFFVAL)}, each checked."""
+    while off < end:
+        if off + 17 > end:
+            _refuse(path, "malformed: a Huffman table of the JPEG stream's DHT segment runs past the segment")
+        tc, th = buf[off] >> 4, buf[off] & 15
+        bits = np.frombuffer(buf, dtype=np.uint8, count=16, offset=off + 1).copy()
+        n = int(bits.sum())
+        if tc != 0:
+            _refuse(path, f"the JPEG stream defines a Huffman table of class {tc}: a lossless stream holds tables of class 0 only")
+        if n > 17:
+            _refuse(path, f"malformed: a Huffman table of the JPEG stream counts {n} codes (BITS), a lossless table has at most 17")
+        if off + 17 + n > end:
+            _refuse(path, f"malformed: the {n} values of a Huffman table of the JPEG stream run past its DHT segment")
+        values = np.frombuffer(buf, dtype=np.uint8, count=n, offset=off + 17).copy()
+        if n and int(values.max()) > 16:
+            _refuse(path, f"malformed: a Huffman table of the JPEG stream holds the value {int(values.max())} (HUFFVAL); a lossless category is 0..16")
+        if len(set(values.tolist())) != n:
+            _refuse(path, f"malformed: a Huffman table of the JPEG stream holds repeated values ({values.tolist()})")
+        if sum(int(c) << (16 - l) for l, c in enumerate(bits, 1)) > 1 << 16:
+            _refuse(path, f"malformed: a Huffman table of the JPEG stream is over-subscribed (BITS {bits.tolist()}: Kraft sum above 1)")
+        tables[th] = (bits, values)
+        off += 17 + n
+
+
+def _jpeg_fragment(buf, f: DicomFile, size: int):
+    """The one fragment of a JPEG Lossless file's encapsulated PixelData as (offset in the file, length), the marker segments in front
+    of its entropy-coded data checked and `f.jpeg` set.  Nothing behind the SOS segment is read."""
+    path = f.path
+    if f.bits_allocated == 32:
+        _refuse(path, "BitsAllocated 32 in a JPEG lossless file: a JPEG sample has at most 16 bits")
+    at, length = _fragment(buf, f, size)
+    end = at + length
+    if length < 2 or bytes(buf[at:at + 2]) != b"\xff\xd8":
+        _refuse(path, "malformed: the JPEG fragment does not start with SOI (FFD8)")
+    off, tables, frame = at + 2, {}, None
+    while True:
+        while off + 1 < end and buf[off] == 0xFF and buf[off + 1] == 0xFF:       # fill bytes in front of a marker
+            off += 1
+        if off + 4 > end:
+            _refuse(path, f"malformed: a marker segment at byte {off - at} of the JPEG fragment runs past its {length} bytes (no SOS found)")
+        marker, n = buf[off + 1], struct.unpack_from(">H", buf, off + 2)[0]
+        if buf[off] != 0xFF or marker in (0x00, 0x01, 0xD8, 0xD9) or 0xD0 <= marker <= 0xD7:
+            _refuse(path, f"malformed: {bytes(buf[off:off + 2]).hex().upper()} at byte {off - at} of the JPEG fragment, where a marker segment was expected")
+        name = f"marker segment FF{marker:02X}"
+        if n < 2 or off + 2 + n > end:
+            _refuse(path, f"malformed: the {name} at byte {off - at} of the JPEG fragment declares {n} bytes and runs past the fragment's {length}")
+        body, behind = off + 4, off + 2 + n
+        if marker == 0xC4:
+            _huffman_tables(buf, body, behind, path, tables)
+        elif marker == 0xC3:
+            if n < 8 or n != 8 + 3 * buf[body + 5]:
+                _refuse(path, f"malformed: the SOF3 segment of the JPEG stream is {n} bytes long")
+            precision, lines, samples, components = struct.unpack_from(">BHHB", buf, body)
+            if components != 1:
+                _refuse(path, f"the JPEG frame holds {components} components (Nf): colour is outside the path (1 expected)")
+            frame = (precision, lines, samples, buf[body + 6])
+        elif 0xC0 <= marker <= 0xCF and marker not in (0xC8, 0xCC):
+            _refuse(path, f"the JPEG stream's frame header is SOF{marker - 0xC0} (FF{marker:02X}): only SOF3 (FFC3), lossless Huffman, is read; "
+                          "JPEG baseline / extended / progressive and arithmetic coding are outside the path")
+        elif marker == 0xDD:
+            if n != 4:
+                _refuse(path, f"malformed: the DRI segment of the JPEG stream is {n} bytes long")
+            if struct.unpack_from(">H", buf, body)[0]:
+                _refuse(path, f"the JPEG stream sets a restart interval of {struct.unpack_from('>H', buf, body)[0]} (DRI): restart intervals are outside the path")
+        elif marker == 0xDC:
+            _refuse(path, "the JPEG stream defines its number of lines behind the scan (DNL), which is outside the path")
+        elif marker == 0xDA:
+            break
+        elif not (0xE0 <= marker <= 0xEF or marker == 0xFE):
+            _refuse(path, f"the {name} of the JPEG stream is outside the path: SOI, APPn, COM, DHT, SOF3, DRI 0 and SOS are read")
+        off = behind
+    if frame is None:
+        _refuse(path, "malformed: the JPEG stream's SOS comes without a frame header (SOF3) in front of it")
+    precision, lines, samples, component = frame
+    if n < 6 or n != 6 + 2 * buf[body]:
+        _refuse(path, f"malformed: the SOS segment of the JPEG stream is {n} bytes long")
+    if buf[body] != 1:
+        _refuse(path, f"the JPEG scan holds {buf[body]} components (Ns): 1 expected")
+    selected, table, predictor, _, transform = struct.unpack_from(">BBBBB", buf, body + 1)
+    if selected != component:
+        _refuse(path, f"malformed: the JPEG scan selects component {selected}, the frame defines {component}")
+    if not 1 <= predictor <= 7:
+        _refuse(path, f"malformed: the JPEG scan selects predictor {predictor} (Ss); a lossless scan has 1..7")
+    if predictor != 1:
+        _refuse(path, f"the JPEG scan selects predictor {predictor} (Ss): only predictor 1 (first-order, from the left neighbour) is read; "
+                      "predictors 2-7 are out of scope")
+    if transform & 15:
+        _refuse(path, f"the JPEG scan sets a point transform of {transform & 15} (Al): only 0 is read")
+    if not 2 <= precision <= 16:
+        _refuse(path, f"malformed: JPEG precision {precision} (P) outside 2..16")
+    if precision > f.bits_allocated or precision < f.bits_stored:
+        _refuse(path, f"JPEG precision {precision} (P) outside BitsStored {f.bits_stored} .. BitsAllocated {f.bits_allocated}")
+    if (lines, samples) != (f.rows, f.columns):
+        _refuse(path, f"the JPEG frame is {lines} lines of {samples} samples, Rows and Columns say {f.rows} x {f.columns}")
+    if table >> 4 not in tables:
+        _refuse(path, f"malformed: the JPEG scan selects Huffman table {table >> 4}, for which the stream holds no DHT (it defines {sorted(tables)})")
+    bits, values = tables[table >> 4]
+    f.jpeg = JpegScan(int(precision), int(lines), int(samples), bits, values, behind - at, end - behind)
+    return at, length
+
+
 def read_file(path, header_only=False) -> DicomFile:
-    """Parse one file up to PixelData (7FE0,0010).  `frame` is a zero-copy uint8 view of the file's voxel bytes, or of its RLE fragment
-    (the file stays mapped while the view lives); with `header_only` everything is parsed and checked alike, no voxel byte is read and
+    """Parse one file up to PixelData (7FE0,0010).  `frame` is a zero-copy uint8 view of the file's voxel bytes, or of its RLE or JPEG
+    fragment (the file stays mapped while the view lives); with `header_only` everything is parsed and checked alike, no voxel byte is read and
     `frame` stays None."""
     with part10(path) as p:
         path, buf, size, off = p.path, p.buf, p.size, p.off
-        explicit, encoding = _check_syntax(p.syntax, path)
+        explicit, encoding = _check_syntax(p.syntax, path, jpeg_lossless=True)
         f = DicomFile(path, p.syntax, encoding=encoding)
         while off < size:
             tag, vr, length, voff = _element(buf, off, explicit, path)
@@ -467,6 +604,8 @@ def read_file(path, header_only=False) -> DicomFile:
             need, at = _validate(f, size), f.pixel_offset
             if encoding == RLE:
                 at, need = _rle_fragment(buf, f, size)
+            if encoding == JPEGLL:
+                at, need = _jpeg_fragment(buf, f, size)
             if not header_only:
                 f.frame = np.frombuffer(buf, dtype=np.uint8, count=need, offset=at)
                 p.keep = True
@@ -479,7 +618,8 @@ class DicomSeries:
     `affine`: 4x4 float64 voxel index -> mm in RAS, or None (a single slice without geometry); `slopes`, `inters`: RescaleSlope /
     RescaleIntercept per sorted slice; `frames`: per sorted slice a uint8 view of that file's PixelData bytes (empty with header_only);
     `encoding`: NATIVE, or RLE: `frames` are the files' RLE fragments and `segments` holds per sorted slice the (bits_allocated / 8, 2)
-    int64 table of each segment's byte offset into its fragment and byte length."""
+    int64 table of each segment's byte offset into its fragment and byte length, or JPEGLL: `frames` are the files' JPEG fragments and
+    `jpeg` holds per sorted slice its `JpegScan`."""
     shape: Tuple[int, int, int]
     affine: Optional[np.ndarray]
     path: str
@@ -493,6 +633,7 @@ class DicomSeries:
     files: List[str] = field(default_factory=list)       # the slices' paths in sorted order
     encoding: str = NATIVE
     segments: List[np.ndarray] = field(default_factory=list)
+    jpeg: List[JpegScan] = field(default_factory=list)
 
     def uniform_scale(self):
         """(slope, inter) when every slice carries the same pair bit for bit, else None."""
@@ -597,12 +738,13 @@ def read_series(directory, header_only=False) -> DicomSeries:
             if getattr(s, name) != getattr(first, name):
                 raise ConfigurationError(f"{d}: {first.path} and {s.path} differ in {what} ({getattr(first, name)} and {getattr(s, name)})")
         if s.encoding != first.encoding:
-            raise ConfigurationError(f"{d}: {first.path} ({first.transfer_syntax}) and {s.path} ({s.transfer_syntax}) mix uncompressed and RLE "
-                                     "lossless files in one series")
+            raise ConfigurationError(f"{d}: {first.path} ({first.transfer_syntax}) and {s.path} ({s.transfer_syntax}) mix uncompressed, RLE "
+                                     "lossless and JPEG lossless files in one series")
     slices, lps = _geometry(slices, d)
     affine = None if lps is None else lps_to_ras(lps)
     first = slices[0]
     return DicomSeries((int(first.columns), int(first.rows), len(slices)), affine, d, int(first.bits_allocated), int(first.bits_stored),
                        int(first.high_bit), bool(first.pixel_representation), [float(s.slope) for s in slices], [float(s.inter) for s in slices],
                        [] if header_only else [s.frame for s in slices], [s.path for s in slices], first.encoding,
-                       [s.segments for s in slices] if first.encoding == RLE else [])
+                       [s.segments for s in slices] if first.encoding == RLE else [],
+                       [s.jpeg for s in slices] if first.encoding == JPEGLL else [])

@@ -7,7 +7,8 @@ the file's voxels in their on-disk type.  The host only uploads bytes (pinned, n
     upload(volume, device)                          host volume (NiftiImage, DicomSeries or ndarray) -> DeviceVolume
     stage_mask(scan, mask, device)                  host mask of any source -> DeviceVolume, or Staged{Contours,Frames} that wait for their kernel
     decode_series(series, device)                   a sorted DICOM series -> DeviceVolume: the slices' bytes decoded on device (mmnn_decode_slices)
-                                                    (an RLE Lossless series: its fragments expanded first, mmnn_rle_expand)
+                                                    (an RLE Lossless series: its fragments expanded first, mmnn_rle_expand; a JPEG
+                                                    Lossless series: Huffman-decoded and predicted first, mmnn_jpegll_decode)
     rasterize_contours(contours, scan, device)      the contours of an RTSTRUCT ROI -> uint8 0 / 1 on the scan's grid (mmnn_rasterize_contours)
     unpack_frames(frames, scan, device)             the frames of a DICOM SEG segment -> uint8 0 / 1 on the scan's grid, or 0 / 255 on the
                                                     segmentation's own (mmnn_unpack_frames)
@@ -34,7 +35,8 @@ A DICOM series (`dicom.read_series`) takes one more step in front: its slices' P
 `mmnn_decode_slices` unpacks the stored bits, extends the sign and, where the slices differ in RescaleSlope / RescaleIntercept, rescales
 per slice.  An RLE Lossless series uploads its fragments as the files hold them, `mmnn_rle_expand` turns them into the bytes the uncompressed
 series would hold, and `mmnn_decode_slices` follows unchanged; the z status words are read back once per series, and a slice whose
-segment ended early is refused with its file named.  A DICOM (scan, mask) pair always passes through `resample_mask` -- upstream always runs `sitk.Resample(mask, image)` and
+segment ended early is refused with its file named.  A JPEG Lossless series goes the same way through `mmnn_jpegll_decode`, with a
+record per frame (where its entropy-coded data lies, its precision and its Huffman table) in place of the segment table.  A DICOM (scan, mask) pair always passes through `resample_mask` -- upstream always runs `sitk.Resample(mask, image)` and
 `mask > 128` on that path -- with the identity map when the two series share one grid, and its default threshold is 128.
 
 A mask that is an RT Structure Set (`rtstruct.read` -> `ContourSet`) beside a DICOM scan is born on the scan's grid: the host maps the
@@ -57,7 +59,7 @@ import torch
 from .. import _lib
 from ..exceptions.exceptions import ConfigurationError
 from . import nifti, rtstruct, seg
-from .dicom import RLE, DicomSeries
+from .dicom import JPEGLL, RLE, DicomSeries
 from .nifti import NiftiImage
 from .rtstruct import ContourSet
 from .seg import FrameSet
@@ -145,13 +147,16 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
     ingest applies in fp64 like a NIfTI scl_slope; otherwise the kernel rescales per slice and the volume is float64, slope 1, inter 0.
     An RLE Lossless series (`series.encoding == 'rle'`) stages its segment table and its fragments in place of the slices' bytes,
     each fragment on a 16-byte boundary, and `mmnn_rle_expand` runs in front of `mmnn_decode_slices`; the z status words are then read
-    back -- the one wait of this path -- and a slice whose segment ended before its plane was full raises ConfigurationError."""
+    back -- the one wait of this path -- and a slice whose segment ended before its plane was full raises ConfigurationError.  A JPEG
+    Lossless series (`'jpeg-lossless'`) does the same with `mmnn_jpegll_decode` and a frame record per slice."""
     if not series.frames:
         raise ValueError(f"decode_series: {series.path} was read with header_only: it holds no voxel bytes")
     device = torch.device(device)
     x, y, z = (int(v) for v in series.shape)
     if series.encoding == RLE:
         return _decode_rle_series(series, device, x, y, z)
+    if series.encoding == JPEGLL:
+        return _decode_jpegll_series(series, device, x, y, z)
     frame_bytes = x * y * (series.bits_allocated // 8)
     if len(series.frames) != z or any(f.dtype != np.uint8 or f.size != frame_bytes for f in series.frames):
         raise ValueError(f"decode_series: {series.path}: {z} slices of {frame_bytes} bytes expected")
@@ -174,50 +179,105 @@ def decode_series(series: DicomSeries, device) -> DeviceVolume:
     return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
 
 
-def _decode_rle_series(series: DicomSeries, device, x: int, y: int, z: int) -> DeviceVolume:
-    """`decode_series` of an RLE Lossless series.  The pinned buffer: the scale table (when needed), the segment table ([z][B][2] int64:
-    byte offset into the payload, byte length), then the payload, i.e. the fragments in sorted order, each start aligned to 16 bytes."""
-    planes = series.bits_allocated // 8
-    if len(series.frames) != z or len(series.segments) != z or any(f.dtype != np.uint8 for f in series.frames) \
-            or any(np.asarray(t).shape != (planes, 2) for t in series.segments):
-        raise ValueError(f"decode_series: {series.path}: {z} RLE fragments with {planes} segments each expected")
+@dataclass
+class _StagedFragments:
+    """What the compressed series share in front of their kernel.  The pinned buffer `stage` (`host`: its numpy view): the scale table
+    (when needed), the per-frame records at `at_records`, then the payload at `at_payload`, i.e. the fragments in sorted order, each
+    start (`starts[k]`, relative to the payload) aligned to 16 bytes and the gaps zeroed."""
+    stage: torch.Tensor
+    host: np.ndarray
+    at_records: int
+    at_payload: int
+    starts: np.ndarray
+    payload_bytes: int
+    scale: Optional[Tuple[float, float]]
+    integer: bool
+
+
+def _stage_fragments(series: DicomSeries, z: int, record_bytes: int) -> _StagedFragments:
+    """Stage the fragments of a compressed series; the caller fills the z records of `record_bytes` (a multiple of 8) each."""
     scale = series.uniform_scale()
     integer = scale is not None and all(float(np.float32(v)) == v for v in scale)
-    table_bytes = 0 if integer else z * 16
-    at_payload = table_bytes + z * planes * 16
+    at_records = 0 if integer else z * 16
+    at_payload = (at_records + z * record_bytes + 15) // 16 * 16
     starts = np.zeros(z + 1, dtype=np.int64)
     np.cumsum([(f.size + 15) // 16 * 16 for f in series.frames], out=starts[1:])
-    payload_bytes = int(starts[-1])
-    stage = torch.empty(at_payload + payload_bytes, dtype=torch.uint8, pin_memory=True)
+    stage = torch.empty(at_payload + int(starts[-1]), dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
     if not integer:
-        host[:table_bytes].view(np.float64)[:] = np.asarray([v for pair in zip(series.slopes, series.inters) for v in pair], dtype=np.float64)
-    table = host[table_bytes:at_payload].view(np.int64).reshape(z, planes, 2)
-    for k, (frame, segments) in enumerate(zip(series.frames, series.segments)):
-        table[k] = segments
-        table[k, :, 0] += starts[k]
+        host[:at_records].view(np.float64)[:] = np.asarray([v for pair in zip(series.slopes, series.inters) for v in pair], dtype=np.float64)
+    host[at_records + z * record_bytes:at_payload] = 0
+    for k, frame in enumerate(series.frames):
         at = at_payload + int(starts[k])
         host[at:at + frame.size] = frame
         host[at + frame.size:at_payload + int(starts[k + 1])] = 0
-    code = _integer_code(series.bits_allocated, series.signed) if integer else TYPE_CODES[np.dtype("float64")]
-    staged = stage.to(device, non_blocking=True)
-    words = torch.empty(x * y * z * planes, dtype=torch.uint8, device=device)
-    status = torch.empty(z, dtype=torch.int32, device=device)
-    ws = torch.empty(_lib.count("mmnn_rle_workspace_bytes", x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
-    rle = _lib.RleDesc(x, y, z, series.bits_allocated, payload_bytes)
-    _lib.enqueue("mmnn_rle_expand", ctypes.byref(rle), staged.data_ptr() + at_payload, staged.data_ptr() + table_bytes, words.data_ptr(),
-                 status.data_ptr(), ws.data_ptr(), device=device)
+    return _StagedFragments(stage, host, at_records, at_payload, starts, int(starts[-1]), scale, integer)
+
+
+def _decode_expanded(series: DicomSeries, device, shape, s: _StagedFragments, staged, words, status, fault: str) -> DeviceVolume:
+    """Behind the kernel that turned the staged fragments into `words`, the bytes of the uncompressed series: `mmnn_decode_slices`, then
+    the one read-back of the z status words; a frame whose word is not 0 raises ConfigurationError with its file and `fault`."""
+    x, y, z = shape
+    code = _integer_code(series.bits_allocated, series.signed) if s.integer else TYPE_CODES[np.dtype("float64")]
     desc = _lib.DecodeSlicesDesc(x, y, z, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed), code)
-    out = torch.empty(x * y * z * (planes if integer else 8), dtype=torch.uint8, device=device)
-    _lib.enqueue("mmnn_decode_slices", ctypes.byref(desc), words.data_ptr(), None if integer else staged.data_ptr(), out.data_ptr(), device=device)
+    out = torch.empty(x * y * z * (series.bits_allocated // 8 if s.integer else 8), dtype=torch.uint8, device=device)
+    _lib.enqueue("mmnn_decode_slices", ctypes.byref(desc), words.data_ptr(), None if s.integer else staged.data_ptr(), out.data_ptr(), device=device)
     bad = np.flatnonzero(status.cpu().numpy())
     if bad.size:
         k = int(bad[0])
         name = series.files[k] if k < len(series.files) else f"{series.path}: slice {k}"
-        raise ConfigurationError(f"{name}: malformed: an RLE segment ends before its {x} x {y} byte plane is full "
-                                 f"({bad.size} of the {z} slices of {series.path} are short)")
-    slope, inter = scale if integer else (1.0, 0.0)
+        raise ConfigurationError(f"{name}: malformed: {fault} ({bad.size} of the {z} slices of {series.path} are short)")
+    slope, inter = s.scale if s.integer else (1.0, 0.0)
     return DeviceVolume(out, (x, y, z), code, float(slope), float(inter), series.affine, from_dicom=True)
+
+
+def _decode_rle_series(series: DicomSeries, device, x: int, y: int, z: int) -> DeviceVolume:
+    """`decode_series` of an RLE Lossless series.  The records of the pinned buffer (`_stage_fragments`): the segment table, [z][B][2]
+    int64: byte offset into the payload, byte length."""
+    planes = series.bits_allocated // 8
+    if len(series.frames) != z or len(series.segments) != z or any(f.dtype != np.uint8 for f in series.frames) \
+            or any(np.asarray(t).shape != (planes, 2) for t in series.segments):
+        raise ValueError(f"decode_series: {series.path}: {z} RLE fragments with {planes} segments each expected")
+    s = _stage_fragments(series, z, planes * 16)
+    table = s.host[s.at_records:s.at_records + z * planes * 16].view(np.int64).reshape(z, planes, 2)
+    for k, segments in enumerate(series.segments):
+        table[k] = segments
+        table[k, :, 0] += s.starts[k]
+    staged = s.stage.to(device, non_blocking=True)
+    words = torch.empty(x * y * z * planes, dtype=torch.uint8, device=device)
+    status = torch.empty(z, dtype=torch.int32, device=device)
+    ws = torch.empty(_lib.count("mmnn_rle_workspace_bytes", x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
+    rle = _lib.RleDesc(x, y, z, series.bits_allocated, s.payload_bytes)
+    _lib.enqueue("mmnn_rle_expand", ctypes.byref(rle), staged.data_ptr() + s.at_payload, staged.data_ptr() + s.at_records, words.data_ptr(),
+                 status.data_ptr(), ws.data_ptr(), device=device)
+    return _decode_expanded(series, device, (x, y, z), s, staged, words, status, f"an RLE segment ends before its {x} x {y} byte plane is full")
+
+
+JPEGLL_FRAME = np.dtype([("offset", "<i8"), ("length", "<i8"), ("precision", "<i4"), ("bits", "u1", 16), ("huffval", "u1", 17), ("reserved", "u1", 3)])
+assert JPEGLL_FRAME.itemsize == _lib.JPEGLL_FRAME_BYTES      # mmnn_jpegll_frame
+
+
+def _decode_jpegll_series(series: DicomSeries, device, x: int, y: int, z: int) -> DeviceVolume:
+    """`decode_series` of a JPEG Lossless series.  The records of the pinned buffer (`_stage_fragments`): z `mmnn_jpegll_frame`s -- where the
+    entropy-coded data lies in the payload, the precision and the Huffman table, as `dicom.read_file` took them from the marker segments."""
+    if len(series.frames) != z or len(series.jpeg) != z or any(f.dtype != np.uint8 for f in series.frames):
+        raise ValueError(f"decode_series: {series.path}: {z} JPEG fragments with their scan headers expected")
+    s = _stage_fragments(series, z, JPEGLL_FRAME.itemsize)
+    records = s.host[s.at_records:s.at_records + z * JPEGLL_FRAME.itemsize].view(JPEGLL_FRAME)
+    records[:] = np.zeros((), dtype=JPEGLL_FRAME)
+    for k, scan in enumerate(series.jpeg):
+        records[k]["offset"], records[k]["length"], records[k]["precision"] = int(s.starts[k]) + scan.offset, scan.length, scan.precision
+        records[k]["bits"] = scan.bits
+        records[k]["huffval"][:len(scan.huffval)] = scan.huffval
+    staged = s.stage.to(device, non_blocking=True)
+    words = torch.empty(x * y * z * (series.bits_allocated // 8), dtype=torch.uint8, device=device)
+    status = torch.empty(z, dtype=torch.int32, device=device)
+    ws = torch.empty(_lib.count("mmnn_jpegll_workspace_bytes", x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
+    desc = _lib.JpegllDesc(x, y, z, series.bits_allocated, s.payload_bytes)
+    _lib.enqueue("mmnn_jpegll_decode", ctypes.byref(desc), staged.data_ptr() + s.at_payload, staged.data_ptr() + s.at_records, words.data_ptr(),
+                 status.data_ptr(), ws.data_ptr(), device=device)
+    return _decode_expanded(series, device, (x, y, z), s, staged, words, status,
+                            f"the JPEG stream ends, or holds an invalid code, before its {x} x {y} samples are decoded")
 
 
 def _default_device(out):                    # where a call that names no device works

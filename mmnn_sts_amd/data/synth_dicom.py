@@ -1,7 +1,8 @@
 """A minimal DICOM writer and the DICOM twin of a `synth_nifti.write_tree` tree, for the tests, the timing tool and a first run of
 `main.py --image_loc` on the DICOM layout (`mmnn_sts_amd.data.ImageDatasets`).  A test and demo aid, like `synth_nifti`: it writes what
-`mmnn_sts_amd.data.dicom` reads (one frame per file; uncompressed in explicit VR little endian, or implicit on request, or RLE Lossless
-with `transfer_syntax="rle"`) and nothing else.
+`mmnn_sts_amd.data.dicom` reads (one frame per file; uncompressed in explicit VR little endian, or implicit on request, RLE Lossless
+with `transfer_syntax="rle"`, or JPEG Lossless with first-order prediction, 1.2.840.10008.1.2.4.70, with `transfer_syntax="jpeg-lossless"`)
+and nothing else.
 
     <root>/images/t1/SYN-0007-t1-a/image/series_1/0003.dcm ...     one file per slice, names in a seeded random order
     <root>/images/t1/SYN-0007-t1-a/mask/series_1/0011.dcm ...      the mask as an 8-bit image series, 0 / 255
@@ -9,7 +10,7 @@ with `transfer_syntax="rle"`) and nothing else.
     <root>/images/t1/SYN-0007-t1-a/mask/seg.dcm                    with mask_format="seg": the mask as one BINARY Segmentation object
     <root>/key.csv, clinical.csv, train_uids.txt, val_uids.txt     copied from the NIfTI tree
 
-    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct | seg] [--transfer_syntax rle]
+    python -m mmnn_sts_amd.data.synth_dicom NIFTI_DIR DICOM_DIR [--mask_format rtstruct | seg] [--transfer_syntax rle | jpeg-lossless]
 
 The twin holds the same voxels -- slice k, row j, column i is the NIfTI voxel (i, j, k) -- and the same geometry: ImagePositionPatient,
 ImageOrientationPatient and PixelSpacing are the NIfTI affine's columns in LPS (a sheared or left-handed affine has no such form and is
@@ -25,13 +26,16 @@ import numpy as np
 
 from ..exceptions.exceptions import ConfigurationError
 from . import nifti
-from .dicom import EXPLICIT_LE, IMPLICIT_LE, LONG_VRS, RLE_LOSSLESS
+from .dicom import EXPLICIT_LE, IMPLICIT_LE, JPEG_LOSSLESS_SV1, LONG_VRS, RLE_LOSSLESS
 
 MR_IMAGE_STORAGE = "1.2.840.10008.5.1.4.1.1.4"
 RT_STRUCTURE_SET_STORAGE = "1.2.840.10008.5.1.4.1.1.481.3"
 SEGMENTATION_STORAGE = "1.2.840.10008.5.1.4.1.1.66.4"
 MASK_FORMATS = ("series", "rtstruct", "seg")
-TRANSFER_SYNTAXES = ("native", "rle")
+TRANSFER_SYNTAXES = ("native", "rle", "jpeg-lossless")
+# T.81 Table K.3 (luminance DC) extended by one code per length up to 14 bits, so that it covers the categories 0..16: Kraft sum 1 - 2^-14
+JPEG_DEFAULT_TABLE = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0), tuple(range(17)))
+JPEG_TABLES = ("default", "frame")
 UID_ROOT = "1.2.3.4.5"                       # not a registered root: synthetic files only
 
 
@@ -113,6 +117,112 @@ def rle_fragment(pixels) -> bytes:
     return struct.pack("<16I", len(segments), *offsets, *([0] * (15 - len(offsets)))) + b"".join(segments)
 
 
+def jpeg_categories(pixels, precision):
+    """(SSSS, extra bits) per sample of a (Rows, Columns) frame under predictor 1 (T.81 H.1.2): the first sample is predicted 2^(P-1),
+    the rest of the first row from the left, the first sample of a later row from above, every other sample from the left.  The
+    difference is taken modulo 2^16 into -32767..32768; its category SSSS is 0 for 0, 16 for 32768, else the bit length of its
+    magnitude, and its SSSS extra bits are the difference, or the difference + 2^SSSS - 1 when it is negative (none for 0 and 16)."""
+    a = np.ascontiguousarray(pixels)
+    words = a.view(np.dtype(f"u{a.dtype.itemsize}")).astype(np.int64)
+    predicted = np.empty_like(words)
+    predicted[:, 1:] = words[:, :-1]
+    predicted[1:, 0] = words[:-1, 0]
+    predicted[0, 0] = 1 << (precision - 1)
+    d = ((words - predicted) & 0xFFFF).reshape(-1)
+    d = np.where(d > 32768, d - 65536, d)
+    magnitude = np.abs(d)
+    ssss = np.zeros(d.shape, dtype=np.int64)
+    for s in range(1, 17):
+        ssss[magnitude >= 1 << (s - 1)] = s
+    extra = np.where(d >= 0, d, d + (1 << ssss) - 1)
+    extra[ssss == 16] = 0
+    return ssss, extra
+
+
+def canonical_codes(bits, huffval):
+    """{value: (code, length)} of a BITS / HUFFVAL pair as T.81 Annex C assigns them."""
+    codes, code, k = {}, 0, 0
+    for length, count in enumerate(bits, 1):
+        for _ in range(int(count)):
+            codes[int(huffval[k])] = (code, length)
+            code += 1
+            k += 1
+        code <<= 1
+    return codes
+
+
+def frame_table(ssss):
+    """A Huffman table of a frame's own category counts, the code lengths limited to 16: the lengths of a Huffman tree over the
+    categories that occur (a lone one gets a one-bit code), then, while a length exceeds 16 or the all-ones code is in use (T.81 forbids
+    it: Kraft sum 1), the rarest symbols are pushed down and the sum restored by lengthening the shortest code that can pay for it."""
+    counts = np.bincount(ssss, minlength=17)
+    present = [int(v) for v in np.flatnonzero(counts)]
+    lengths = {v: 0 for v in present}
+    heap = sorted((int(counts[v]), [v]) for v in present)
+    while len(heap) > 1:
+        (ca, a), (cb, b) = heap[0], heap[1]
+        for v in a + b:
+            lengths[v] += 1
+        heap = sorted(heap[2:] + [(ca + cb, a + b)])
+    rare = min(present, key=lambda v: (counts[v], -v))
+    lengths[rare] += 1                         # one code point left over: the all-ones code stays free
+    order = sorted(present, key=lambda v: (lengths[v], -counts[v], v))
+    for v in order:
+        lengths[v] = min(lengths[v], 16)
+    kraft = lambda: sum(1 << (16 - lengths[v]) for v in present)
+    while kraft() > (1 << 16) - 1:             # the clamp over-subscribed the code: lengthen the longest code that is still below 16
+        v = max((v for v in present if lengths[v] < 16), key=lambda v: (lengths[v], -counts[v]))
+        lengths[v] += 1
+    order = sorted(present, key=lambda v: (lengths[v], v))
+    bits = [sum(1 for v in present if lengths[v] == l) for l in range(1, 17)]
+    return tuple(bits), tuple(order)
+
+
+def jpeg_entropy(ssss, extra, table) -> bytes:
+    """The entropy-coded data of a scan: per sample the code of its category, then its extra bits, most significant bit first; the last
+    byte padded with 1-bits; a zero byte stuffed behind every FF."""
+    codes = canonical_codes(*table)
+    code_of, length_of = np.zeros(17, dtype=np.int64), np.zeros(17, dtype=np.int64)
+    for v, (code, length) in codes.items():
+        code_of[v], length_of[v] = code, length
+    if (length_of[ssss] == 0).any():
+        raise ConfigurationError(f"the Huffman table has no code for category {int(ssss[length_of[ssss] == 0][0])}")
+    more = np.where(ssss == 16, 0, ssss)
+    word = (code_of[ssss] << more) | extra
+    width = length_of[ssss] + more
+    start = np.concatenate(([0], np.cumsum(width)))
+    stream = np.ones((int(start[-1]) + 7) // 8 * 8, dtype=np.uint8)
+    for j in range(int(width.max()) if width.size else 0):
+        has = width > j
+        stream[start[:-1][has] + j] = (word[has] >> (width[has] - 1 - j)) & 1
+    data = np.packbits(stream)
+    return np.insert(data, np.flatnonzero(data == 0xFF) + 1, 0).tobytes()
+
+
+def jpeg_lossless_fragment(pixels, bits_stored=None, table="default") -> bytes:
+    """A (Rows, Columns) frame of 8 or 16-bit words as one JPEG Lossless stream (T.81 Annex H, predictor 1): SOI, DHT, SOF3, SOS, the
+    entropy-coded data (`jpeg_entropy`) and EOI.  The precision P is `bits_stored` when no word has a bit set above it, else the
+    word's width.  `table`: 'default' (`JPEG_DEFAULT_TABLE`), 'frame' (`frame_table` of this frame) or a (BITS, HUFFVAL) pair."""
+    a = np.ascontiguousarray(pixels)
+    if a.dtype.itemsize not in (1, 2):
+        raise ConfigurationError(f"JPEG Lossless holds samples of at most 16 bits, got {a.dtype}")
+    width = a.dtype.itemsize * 8
+    words = a.view(np.dtype(f"u{a.dtype.itemsize}"))
+    precision = width if bits_stored is None or int(bits_stored) >= width or int(words.max()) >> int(bits_stored) else max(int(bits_stored), 2)
+    ssss, extra = jpeg_categories(a, precision)
+    if isinstance(table, str):
+        if table not in JPEG_TABLES:
+            raise ConfigurationError(f"jpeg_table {table!r} is none of {JPEG_TABLES}")
+        table = JPEG_DEFAULT_TABLE if table == "default" else frame_table(ssss)
+    bits, huffval = table
+    dht = bytes([0x00]) + bytes(int(v) for v in bits) + bytes(int(v) for v in huffval)
+    sof = struct.pack(">BHHB", precision, a.shape[0], a.shape[1], 1) + bytes([1, 0x11, 0])
+    sos = bytes([1, 1, 0x00, 1, 0, 0])         # one component, table 0; Ss = 1: the predictor; Se = 0; Ah, Al = 0
+    segment = lambda marker, body: bytes([0xFF, marker]) + struct.pack(">H", len(body) + 2) + body
+    data = b"\xff\xd8" + segment(0xC4, dht) + segment(0xC3, sof) + segment(0xDA, sos) + jpeg_entropy(ssss, extra, table) + b"\xff\xd9"
+    return data + b"\0" * (len(data) % 2)
+
+
 def _encapsulated(fragment: bytes) -> bytes:
     """PixelData of undefined length (explicit VR): an empty Basic Offset Table, one fragment, the sequence delimiter."""
     return (struct.pack("<HH2sHI", 0x7FE0, 0x0010, b"OB", 0, 0xFFFFFFFF) + struct.pack("<HHI", 0xFFFE, 0xE000, 0)
@@ -121,22 +231,24 @@ def _encapsulated(fragment: bytes) -> bytes:
 
 def file_bytes(pixels, bits_stored=None, high_bit=None, position=None, orientation=None, pixel_spacing=None, slope=None, inter=None,
                series_uid=UID_ROOT + ".1", instance_number=1, explicit=True, slice_thickness=None, spacing_between_slices=None,
-               sop_instance_uid=UID_ROOT + ".1.1", transfer_syntax="native") -> bytes:
+               sop_instance_uid=UID_ROOT + ".1.1", transfer_syntax="native", jpeg_table="default") -> bytes:
     """One slice as a part-10 file.  `pixels`: a (Rows, Columns) array of uint8 / int8 / uint16 / int16 / uint32 / int32, written as
     it is (the caller has placed the stored bits); geometry and rescale elements are left out when None.  `transfer_syntax` 'rle':
-    RLE Lossless, whose data set is explicit VR and whose PixelData is encapsulated (`rle_fragment`)."""
+    RLE Lossless, whose data set is explicit VR and whose PixelData is encapsulated (`rle_fragment`); 'jpeg-lossless': JPEG Lossless
+    with first-order prediction, encapsulated alike (`jpeg_lossless_fragment` with `jpeg_table`), of 8 or 16-bit words."""
     a = np.ascontiguousarray(pixels)
     if a.ndim != 2 or a.dtype.kind not in "iu" or a.dtype.itemsize not in (1, 2, 4):
         raise ConfigurationError(f"a slice is a 2-D array of 8, 16 or 32-bit integers, got {a.dtype} {a.shape}")
     if transfer_syntax not in TRANSFER_SYNTAXES:
         raise ConfigurationError(f"transfer_syntax {transfer_syntax!r} is none of {TRANSFER_SYNTAXES}")
-    if transfer_syntax == "rle" and not explicit:
-        raise ConfigurationError("an RLE Lossless data set is explicit VR little endian: explicit=False cannot be combined with it")
+    if transfer_syntax != "native" and not explicit:
+        raise ConfigurationError(f"an {'RLE' if transfer_syntax == 'rle' else 'JPEG'} Lossless data set is explicit VR little endian: explicit=False "
+                                 "cannot be combined with it")
     bits = a.dtype.itemsize * 8
     bits_stored = bits if bits_stored is None else int(bits_stored)
     high_bit = bits_stored - 1 if high_bit is None else int(high_bit)
     us = lambda v: struct.pack("<H", v)
-    syntax = RLE_LOSSLESS if transfer_syntax == "rle" else EXPLICIT_LE if explicit else IMPLICIT_LE
+    syntax = {"rle": RLE_LOSSLESS, "jpeg-lossless": JPEG_LOSSLESS_SV1}.get(transfer_syntax, EXPLICIT_LE if explicit else IMPLICIT_LE)
     meta = b"".join([_element(0x0002, 0x0001, "OB", b"\0\1", True), _element(0x0002, 0x0002, "UI", _text(MR_IMAGE_STORAGE), True),
                      _element(0x0002, 0x0003, "UI", _text(sop_instance_uid), True), _element(0x0002, 0x0010, "UI", _text(syntax), True),
                      _element(0x0002, 0x0012, "UI", _text(UID_ROOT + ".0"), True)])
@@ -172,6 +284,8 @@ def file_bytes(pixels, bits_stored=None, high_bit=None, position=None, orientati
         add(0x0028, 0x1053, "DS", _text(ds(slope)))
     if transfer_syntax == "rle":
         e.append(_encapsulated(rle_fragment(a)))
+    elif transfer_syntax == "jpeg-lossless":
+        e.append(_encapsulated(jpeg_lossless_fragment(a, bits_stored, jpeg_table)))
     else:
         add(0x7FE0, 0x0010, "OB" if bits == 8 else "OW", a.astype(a.dtype.newbyteorder("<")).tobytes())
     return b"\0" * 128 + b"DICM" + meta + b"".join(e)
@@ -208,10 +322,10 @@ def _stored(volume, bits_stored, rng):
 
 
 def write_series(directory, volume, affine=None, slope=None, inter=None, series_uid=UID_ROOT + ".1", shuffle_names=True, seed=0,
-                 bits_stored=None, per_slice_scale=False, explicit=True, transfer_syntax="native"):
+                 bits_stored=None, per_slice_scale=False, explicit=True, transfer_syntax="native", jpeg_table="default"):
     """Write the (x, y, z) integer `volume` as z slice files under `directory`.  `per_slice_scale`: slice k carries its own pair,
-    slope (1 + (k % 4) / 8) and inter - 3.5 k, so that the series has no shared scale.  `transfer_syntax`: 'native' (uncompressed) or
-    'rle' (RLE Lossless)."""
+    slope (1 + (k % 4) / 8) and inter - 3.5 k, so that the series has no shared scale.  `transfer_syntax`: 'native' (uncompressed),
+    'rle' (RLE Lossless) or 'jpeg-lossless' (with `jpeg_table`, see `jpeg_lossless_fragment`)."""
     volume = np.asarray(volume)
     if volume.ndim != 3:
         raise ConfigurationError(f"a volume has three axes, got {volume.shape}")
@@ -227,7 +341,7 @@ def write_series(directory, volume, affine=None, slope=None, inter=None, series_
         if per_slice_scale:
             s, i = (1.0 if slope is None else slope) * (1.0 + (k % 4) / 8.0), (0.0 if inter is None else inter) - 3.5 * k
         data = file_bytes(words[:, :, k].T, bits_stored, None, first + k * step, orientation, spacing, s, i, series_uid, int(numbers[k]) + 1,
-                          explicit, float(np.linalg.norm(step)), float(np.linalg.norm(step)), f"{series_uid}.{k + 1}", transfer_syntax)
+                          explicit, float(np.linalg.norm(step)), float(np.linalg.norm(step)), f"{series_uid}.{k + 1}", transfer_syntax, jpeg_table)
         with open(os.path.join(directory, f"{int(names[k]):04d}.dcm"), "wb") as f:
             f.write(data)
     return directory
@@ -398,14 +512,14 @@ def write_seg(path, mask, affine, label="GTV", extra_segments=(), explicit=True,
 
 
 def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, seed=0, bits_stored=None, per_slice_scale=False,
-                    mask_format="series", roi_name="GTV", extra_rois=(), transfer_syntax="native"):
+                    mask_format="series", roi_name="GTV", extra_rois=(), transfer_syntax="native", jpeg_table="default"):
     """The DICOM twin of a `synth_nifti.write_tree` tree; returns the same dictionary of locations.  Scans keep their type, slope and
     inter (as RescaleSlope / RescaleIntercept); non-zero mask voxels become `mask_value` (None: the mask's values are kept) in an 8-bit
     unsigned series.  `bits_stored`, `per_slice_scale`: of the scans (see `write_series`).  `mask_format` 'rtstruct': the mask directory
     holds one RT Structure Set file instead (`write_rtstruct` of the non-zero mask voxels on the scan's geometry, ROI `roi_name`,
     with `extra_rois`); the mask must then share the scan's extents.  `mask_format` 'seg': one BINARY Segmentation object
     instead (`write_seg` of the non-zero mask voxels, segment `roi_name`, with `extra_rois` as further segments), written on the
-    mask's own grid when that is another than its scan's.  `transfer_syntax`: of the scans and of the masks written as series."""
+    mask's own grid when that is another than its scan's.  `transfer_syntax`, `jpeg_table`: of the scans and of the masks written as series."""
     if mask_format not in MASK_FORMATS:
         raise ConfigurationError(f"mask_format {mask_format!r} is none of {MASK_FORMATS}")
     nifti_root, dicom_root = str(nifti_root), str(dicom_root)
@@ -433,7 +547,7 @@ def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, 
             target = os.path.join(out["image_loc"], mod, patient)
             scaling = scan.scaling() or (None, None)
             write_series(os.path.join(target, "image", "series_1"), scan.raw, scan.affine, scaling[0], scaling[1], f"{UID_ROOT}.{count}.1",
-                         shuffle_names, seed + 2 * count, bits_stored, per_slice_scale, transfer_syntax=transfer_syntax)
+                         shuffle_names, seed + 2 * count, bits_stored, per_slice_scale, transfer_syntax=transfer_syntax, jpeg_table=jpeg_table)
             if mask_format == "rtstruct":
                 if mask.raw.shape != scan.raw.shape:
                     raise ConfigurationError(f"{d}: an RTSTRUCT twin is drawn on the scan's grid; the mask's extents {mask.raw.shape} differ from {scan.raw.shape}")
@@ -445,7 +559,7 @@ def from_nifti_tree(nifti_root, dicom_root, mask_value=255, shuffle_names=True, 
                 continue
             m = mask.raw if mask_value is None else np.where(mask.raw != 0, mask_value, 0)
             write_series(os.path.join(target, "mask", "series_1"), m.astype(np.uint8), mask.affine, None, None, f"{UID_ROOT}.{count}.2",
-                         shuffle_names, seed + 2 * count + 1, transfer_syntax=transfer_syntax)
+                         shuffle_names, seed + 2 * count + 1, transfer_syntax=transfer_syntax, jpeg_table=jpeg_table)
     return out
 
 
@@ -457,8 +571,10 @@ if __name__ == "__main__":
     ap.add_argument("--bits_stored", type=int, default=None)
     ap.add_argument("--per_slice_scale", action="store_true")
     ap.add_argument("--mask_format", choices=MASK_FORMATS, default="series", help="the masks as 8-bit image series, as RT Structure Set files or as BINARY Segmentation objects")
-    ap.add_argument("--transfer_syntax", choices=TRANSFER_SYNTAXES, default="native", help="of the scans and of the masks written as series: uncompressed, or RLE Lossless")
+    ap.add_argument("--transfer_syntax", choices=TRANSFER_SYNTAXES, default="native", help="of the scans and of the masks written as series: uncompressed, RLE Lossless, or JPEG Lossless with first-order prediction")
+    ap.add_argument("--jpeg_table", choices=JPEG_TABLES, default="default", help="with --transfer_syntax jpeg-lossless: T.81 Table K.3 extended to 17 categories, "
+                    "or a table from every frame's own category counts")
     a = ap.parse_args()
     for k, v in from_nifti_tree(a.nifti_dir, a.dicom_dir, seed=a.seed, bits_stored=a.bits_stored, per_slice_scale=a.per_slice_scale,
-                                mask_format=a.mask_format, transfer_syntax=a.transfer_syntax).items():
+                                mask_format=a.mask_format, transfer_syntax=a.transfer_syntax, jpeg_table=a.jpeg_table).items():
         print(f"{k}: {v}")
