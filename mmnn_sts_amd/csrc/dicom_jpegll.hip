@@ -2,7 +2,8 @@
 // .57 with predictor 1): the entropy-coded data of a sorted single-frame series -> the bytes an uncompressed series would hold, which
 // mmnn_decode_slices then takes unchanged (the contract is the comment above mmnn_jpegll_decode in include/mmnn_sts.h; what a raw byte
 // and a bit position mean, the clamps and the chunk-to-chunk state are csrc/jpegll_core.hpp, which a host program runs under the
-// sanitizers).
+// sanitizers).  What it shares with csrc/dicom_rle.hip is stated once: the window fill in csrc/stream_window.hpp, the span clamp, the
+// round of pointer doubling and the progress in csrc/stream_core.hpp, the host-side refusals in csrc/stream_args.hpp.
 //
 //   jpegll_symbols_kernel  grid z, block 1024: one workgroup per frame.  The data passes through LDS in windows of JLL_CHUNK + JLL_LOOK raw
 //                          bytes, filled by aligned 16-byte loads (the ragged end of the payload by bytes).  Per window:
@@ -26,6 +27,8 @@
 #include "common.hpp"
 #include "reduce.hpp"
 #include "jpegll_core.hpp"
+#include "stream_args.hpp"
+#include "stream_window.hpp"
 
 namespace mmnn {
 
@@ -55,28 +58,17 @@ __global__ void __launch_bounds__(JL_TPB) jpegll_symbols_kernel(const JpegllArgs
   __shared__ uint32_t scan[JL_WAVES];
   __shared__ JllTable table;
   __shared__ JllChunk chunk;
-  __shared__ JllExit left;
+  __shared__ ChainExit left;
   const int tid = threadIdx.x;
   const long k = blockIdx.x;
   const long plane = (long)a.x * a.y;
   uint16_t* diff = a.diff + k * plane;
   const mmnn_jpegll_frame* fr = a.frames + k;
   if (tid == 0) jll_build(table, fr->bits, fr->huffval);
-  JllState st = jll_begin(jll_clamp(fr->offset, fr->length, a.payload_bytes), plane);   // the same in every thread
+  JllState st = jll_begin(stream_clamp(fr->offset, fr->length, a.payload_bytes), plane);   // the same in every thread
   const uint32_t half = 1u << (jll_precision(fr->precision) - 1);
-  while (jll_more(st)) {
-    if (tid < JLL_WINDOW / 16) {
-      const long g = st.base + 16l * tid;
-      uint4 q = make_uint4(0u, 0u, 0u, 0u);
-      if (g + 16 <= a.payload_bytes) {
-        q = *reinterpret_cast<const uint4*>(a.payload + g);
-      } else if (g < a.payload_bytes) {      // the payload's ragged end
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-        for (int i = 0; i < 16 && g + i < a.payload_bytes; ++i) w[i >> 2] |= (unsigned)a.payload[g + i] << (8 * (i & 3));
-        q = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-      *reinterpret_cast<uint4*>(raw + 16 * tid) = q;
-    }
+  while (stream_more(st)) {
+    window_fill<JLL_WINDOW, JL_TPB>(raw, a.payload, a.payload_bytes, st.base, tid);
     for (int i = tid; i < JLL_UNSTUFFED + 1; i += JL_TPB) u[i] = 0xFF;
 #pragma unroll
     for (int i = 0; i < JL_PER / 4; ++i) reinterpret_cast<uint32_t*>(mark)[i * JL_TPB + tid] = 0u;
@@ -95,18 +87,20 @@ __global__ void __launch_bounds__(JL_TPB) jpegll_symbols_kernel(const JpegllArgs
     __syncthreads();
     const JllChunk c = chunk;
     const bool enters = jll_enters(st.entry, c);
-    // 2. the chain: lanes along the positions (thread t has t, t + 1024, ...), so that neighbouring lanes read neighbouring entries
+    // 2. the chain: the text of chain_resolve<JLL_BITS, JL_TPB, JLL_ROUNDS> (csrc/stream_window.hpp, whose contract holds here), written
+    // out: through the helper the compiler schedules this kernel differently and the smooth scan and the masks decode 1.3 to 1.5 %
+    // slower.  Lanes along the positions (thread t has t, t + 1024, ...): neighbouring lanes read neighbouring entries.
 #pragma unroll
     for (int i = 0; i < JL_PER; ++i) hop[i * JL_TPB + tid] = (uint16_t)jll_successor(table, u, i * JL_TPB + tid, c);
     if (tid == 0) {
-      left = JllExit{st.entry, 1};
+      left = ChainExit{st.entry, 1};
       if (enters) mark[st.entry] = 1;
     }
     __syncthreads();
     for (int r = 0; r < JLL_ROUNDS && enters; ++r) {
       uint16_t on[JL_PER];
 #pragma unroll
-      for (int i = 0; i < JL_PER; ++i) on[i] = jll_hop(hop, mark, i * JL_TPB + tid);
+      for (int i = 0; i < JL_PER; ++i) on[i] = chain_hop<JLL_BITS>(hop, mark, i * JL_TPB + tid);
       __syncthreads();
 #pragma unroll
       for (int i = 0; i < JL_PER; ++i) hop[i * JL_TPB + tid] = on[i];
@@ -134,7 +128,7 @@ __global__ void __launch_bounds__(JL_TPB) jpegll_symbols_kernel(const JpegllArgs
     }
     uint32_t total;
     uint32_t at = block_exclusive_scan<JL_WAVES>(count, scan, total);
-    const uint32_t n = jll_take(st, total);
+    const uint32_t n = stream_take(st, total);
 #pragma unroll
     for (int i = 0; i < JL_PER; ++i)
       if ((have >> i) & 1u) {
@@ -145,7 +139,7 @@ __global__ void __launch_bounds__(JL_TPB) jpegll_symbols_kernel(const JpegllArgs
     jll_advance(st, left, c, n);
     __syncthreads();                         // the next window overwrites raw, u, mark, hop, chunk and left
   }
-  const bool failed = jll_short(st);
+  const bool failed = stream_short(st);
   if (failed)
     for (long o = st.done + tid; o < plane; o += JL_TPB) diff[o] = 0;
   if (tid == 0) a.status[k] = failed ? 1 : 0;
@@ -230,7 +224,7 @@ void jpegll_rows(const uint16_t* diff, const uint16_t* first, int x, int y, int 
   else MMNN_LAUNCH((jpegll_rows_kernel<W, false>), grid, dim3(JR_TPB), 0, stream, diff, first, x, y, z, static_cast<W*>(pixels));
 }
 
-bool jpegll_extent_ok(int x, int y, int z) { return x >= 1 && y >= 1 && z >= 1 && (double)x * y * z < 2147483648.0; }
+constexpr StreamCall JPEGLL_CALL{"jpegll_decode", "frames", 16, "neither 8 nor 16"};
 
 }  // namespace
 
@@ -241,7 +235,7 @@ using namespace mmnn;
 extern "C" {
 
 int64_t mmnn_jpegll_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bits_allocated) {
-  if (!jpegll_extent_ok(x, y, z) || (bits_allocated != 8 && bits_allocated != 16)) {
+  if (!stream_extent_ok(x, y, z) || !stream_depth_ok(JPEGLL_CALL, bits_allocated)) {
     set_error("jpegll_workspace_bytes: extent %d x %d x %d at %d bits", x, y, z, bits_allocated);
     return -1;
   }
@@ -250,24 +244,9 @@ int64_t mmnn_jpegll_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bit
 
 int mmnn_jpegll_decode(const mmnn_jpegll_desc* d, const void* payload, const mmnn_jpegll_frame* frames, void* pixels, int32_t* status,
                        void* workspace, void* stream_) {
-  MMNN_REQUIRE(d, "jpegll_decode: null descriptor");
-  MMNN_REQUIRE(d->x >= 1 && d->y >= 1 && d->z >= 1, "jpegll_decode: non-positive extent %d x %d x %d", d->x, d->y, d->z);
-  MMNN_REQUIRE(jpegll_extent_ok(d->x, d->y, d->z), "jpegll_decode: extent %d x %d x %d holds 2^31 voxels or more", d->x, d->y, d->z);
-  MMNN_REQUIRE(d->bits_allocated == 8 || d->bits_allocated == 16, "jpegll_decode: bits_allocated %d is neither 8 nor 16", d->bits_allocated);
-  MMNN_REQUIRE(d->payload_bytes >= 1, "jpegll_decode: payload_bytes %lld is not positive", (long long)d->payload_bytes);
-  MMNN_REQUIRE(payload && frames && pixels && status && workspace, "jpegll_decode: null argument");
+  if (stream_check_args(JPEGLL_CALL, d, payload, frames, pixels, status, workspace)) return 1;
   const int B = d->bits_allocated / 8;
-  MMNN_REQUIRE((uintptr_t)payload % 16 == 0, "jpegll_decode: payload not aligned to 16 bytes");
-  MMNN_REQUIRE((uintptr_t)frames % 8 == 0, "jpegll_decode: frames not aligned to 8 bytes");
-  MMNN_REQUIRE((uintptr_t)pixels % B == 0, "jpegll_decode: pixels not aligned to its element size");
-  MMNN_REQUIRE((uintptr_t)status % 4 == 0, "jpegll_decode: status not aligned to 4 bytes");
-  MMNN_REQUIRE((uintptr_t)workspace % 16 == 0, "jpegll_decode: workspace not aligned to 16 bytes");
   const long plane = (long)d->x * d->y;
-  const uintptr_t p0 = (uintptr_t)payload, p1 = p0 + (size_t)d->payload_bytes;
-  const uintptr_t o0 = (uintptr_t)pixels, o1 = o0 + (size_t)plane * d->z * B;
-  const uintptr_t s0 = (uintptr_t)status, s1 = s0 + (size_t)d->z * sizeof(int32_t);
-  MMNN_REQUIRE(p1 <= o0 || o1 <= p0, "jpegll_decode: payload and pixels overlap");
-  MMNN_REQUIRE(p1 <= s0 || s1 <= p0, "jpegll_decode: payload and status overlap");
   const hipStream_t stream = static_cast<hipStream_t>(stream_);
   const JpegllWorkspace w = jpegll_carve(plane, d->y, d->z);
   uint8_t* ws = static_cast<uint8_t*>(workspace);

@@ -1,7 +1,9 @@
 // DICOM RLE Lossless (PS3.5 Annex G) expansion: the PackBits segments of a sorted single-frame series -> the bytes an uncompressed
 // series would hold, which mmnn_decode_slices then takes unchanged (the contract is the comment above mmnn_rle_expand in
 // include/mmnn_sts.h; what a control byte means, the clamps and the chunk-to-chunk state are csrc/rle_core.hpp, which a host program
-// runs under the sanitizers).
+// runs under the sanitizers).  What it shares with csrc/dicom_jpegll.hip is stated once: the window fill and the doubling rounds with
+// their barriers in csrc/stream_window.hpp, the span clamp and the progress in csrc/stream_core.hpp, the host-side refusals in
+// csrc/stream_args.hpp.
 //
 //   rle_planes_kernel      grid (z * B), block 1024: one workgroup per (frame, byte plane), B = bits_allocated / 8.  The segment passes
 //                          through LDS in windows of RLE_CHUNK + RLE_LOOK bytes, filled by aligned 16-byte loads (the ragged end of
@@ -26,6 +28,8 @@
 #include "common.hpp"
 #include "reduce.hpp"
 #include "rle_core.hpp"
+#include "stream_args.hpp"
+#include "stream_window.hpp"
 
 namespace mmnn {
 
@@ -51,46 +55,20 @@ __global__ void __launch_bounds__(RL_TPB) rle_planes_kernel(const RleArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t off[RLE_CHUNK];
   __shared__ uint16_t hop[RLE_CHUNK];
   __shared__ uint32_t scan[RL_WAVES];
-  __shared__ RleExit left;
+  __shared__ ChainExit left;
   const int tid = threadIdx.x;
   const long fp = blockIdx.x;
   uint8_t* dst = a.planes + fp * a.stride;
-  RleState st = rle_begin(rle_clamp(a.segments[2 * fp], a.segments[2 * fp + 1], a.payload_bytes), a.plane);   // the same in every thread
-  while (rle_more(st)) {
-    for (int v = tid; v < RLE_WINDOW / 16; v += RL_TPB) {
-      const long g = st.base + 16l * v;
-      uint4 q = make_uint4(0u, 0u, 0u, 0u);
-      if (g + 16 <= a.payload_bytes) {
-        q = *reinterpret_cast<const uint4*>(a.payload + g);
-      } else if (g < a.payload_bytes) {      // the payload's ragged end
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-        for (int i = 0; i < 16 && g + i < a.payload_bytes; ++i) w[i >> 2] |= (unsigned)a.payload[g + i] << (8 * (i & 3));
-        q = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-      *reinterpret_cast<uint4*>(win + 16 * v) = q;
-    }
+  RleState st = rle_begin(stream_clamp(a.segments[2 * fp], a.segments[2 * fp + 1], a.payload_bytes), a.plane);   // the same in every thread
+  while (stream_more(st)) {
+    window_fill<RLE_WINDOW, RL_TPB>(win, a.payload, a.payload_bytes, st.base, tid);
     reinterpret_cast<uint32_t*>(mark)[tid] = 0u;
     __syncthreads();
     const long end = rle_end(st);
-    const bool enters = rle_enters(st.entry, end);
-    // 1. the chain: lanes along the positions (thread t has t, t + 1024, ...), so that neighbouring lanes read neighbouring entries
-#pragma unroll
-    for (int i = 0; i < RL_PER; ++i) hop[i * RL_TPB + tid] = (uint16_t)rle_successor(win, i * RL_TPB + tid, end);
-    if (tid == 0) {
-      left = RleExit{st.entry, 1};
-      if (enters) mark[st.entry] = 1;
-    }
-    __syncthreads();
-    for (int k = 0; k < RLE_ROUNDS && enters; ++k) {
-      uint16_t on[RL_PER];
-#pragma unroll
-      for (int i = 0; i < RL_PER; ++i) on[i] = rle_hop(hop, mark, i * RL_TPB + tid);
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < RL_PER; ++i) hop[i * RL_TPB + tid] = on[i];
-      __syncthreads();
-      if (hop[st.entry] >= RLE_CHUNK) break;   // (the same word in every thread; the next write of hop lies behind the next barrier)
-    }
+    // 1. the chain; `left` has one writer in front of chain_resolve's barriers (thread 0) and one behind them (the chain's last member)
+    if (tid == 0) left = ChainExit{st.entry, 1};
+    chain_resolve<RLE_CHUNK, RL_TPB, RLE_ROUNDS>(hop, mark, st.entry, rle_enters(st.entry, end), tid,
+                                                 [&](int p) { return rle_successor(win, p, end); });
     // the chain's last member in the chunk says where the next window is entered
 #pragma unroll
     for (int i = 0; i < RL_PER; ++i) {
@@ -114,8 +92,8 @@ __global__ void __launch_bounds__(RL_TPB) rle_planes_kernel(const RleArgs a) {
     *reinterpret_cast<uint4*>(off + tid * RL_PER) = q;
     __syncthreads();
     // 3. the expansion
-    const RleExit w = left;
-    const uint32_t n = rle_take(st, total);
+    const ChainExit w = left;
+    const uint32_t n = stream_take(st, total);
     uint8_t* d = dst + st.done;
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(d) & 15);
     const uint32_t cells = (lead + n + 15u) / 16u;
@@ -137,7 +115,7 @@ __global__ void __launch_bounds__(RL_TPB) rle_planes_kernel(const RleArgs a) {
     rle_advance(st, w, n);
     __syncthreads();                         // the next window overwrites win, mark, hop, off and left
   }
-  const bool failed = rle_short(st);
+  const bool failed = stream_short(st);
   if (failed)
     for (long o = st.done + tid; o < st.plane; o += RL_TPB) dst[o] = 0;
   if (tid == 0) a.pstatus[fp] = failed ? 1 : 0;
@@ -196,7 +174,7 @@ void rle_interleave(const uint8_t* planes, long stride, long plane, int z, uint8
   else MMNN_LAUNCH((rle_interleave_kernel<B, 1>), dim3(gx, gy), dim3(IL_TPB), 0, stream, planes, stride, plane, z, pixels, pstatus, status);
 }
 
-bool rle_extent_ok(int x, int y, int z) { return x >= 1 && y >= 1 && z >= 1 && (double)x * y * z < 2147483648.0; }
+constexpr StreamCall RLE_CALL{"rle_expand", "segments", 32, "none of 8, 16, 32"};
 
 }  // namespace
 
@@ -207,7 +185,7 @@ using namespace mmnn;
 extern "C" {
 
 int64_t mmnn_rle_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bits_allocated) {
-  if (!rle_extent_ok(x, y, z) || (bits_allocated != 8 && bits_allocated != 16 && bits_allocated != 32)) {
+  if (!stream_extent_ok(x, y, z) || !stream_depth_ok(RLE_CALL, bits_allocated)) {
     set_error("rle_workspace_bytes: extent %d x %d x %d at %d bits", x, y, z, bits_allocated);
     return -1;
   }
@@ -216,25 +194,9 @@ int64_t mmnn_rle_workspace_bytes(int32_t x, int32_t y, int32_t z, int32_t bits_a
 
 int mmnn_rle_expand(const mmnn_rle_desc* d, const void* payload, const int64_t* segments, void* pixels, int32_t* status, void* workspace,
                     void* stream_) {
-  MMNN_REQUIRE(d, "rle_expand: null descriptor");
-  MMNN_REQUIRE(d->x >= 1 && d->y >= 1 && d->z >= 1, "rle_expand: non-positive extent %d x %d x %d", d->x, d->y, d->z);
-  MMNN_REQUIRE(rle_extent_ok(d->x, d->y, d->z), "rle_expand: extent %d x %d x %d holds 2^31 voxels or more", d->x, d->y, d->z);
-  MMNN_REQUIRE(d->bits_allocated == 8 || d->bits_allocated == 16 || d->bits_allocated == 32, "rle_expand: bits_allocated %d is none of 8, 16, 32",
-               d->bits_allocated);
-  MMNN_REQUIRE(d->payload_bytes >= 1, "rle_expand: payload_bytes %lld is not positive", (long long)d->payload_bytes);
-  MMNN_REQUIRE(payload && segments && pixels && status && workspace, "rle_expand: null argument");
+  if (stream_check_args(RLE_CALL, d, payload, segments, pixels, status, workspace)) return 1;
   const int B = d->bits_allocated / 8;
-  MMNN_REQUIRE((uintptr_t)payload % 16 == 0, "rle_expand: payload not aligned to 16 bytes");
-  MMNN_REQUIRE((uintptr_t)segments % 8 == 0, "rle_expand: segments not aligned to 8 bytes");
-  MMNN_REQUIRE((uintptr_t)pixels % B == 0, "rle_expand: pixels not aligned to its element size");
-  MMNN_REQUIRE((uintptr_t)status % 4 == 0, "rle_expand: status not aligned to 4 bytes");
-  MMNN_REQUIRE((uintptr_t)workspace % 16 == 0, "rle_expand: workspace not aligned to 16 bytes");
   const long plane = (long)d->x * d->y;
-  const uintptr_t p0 = (uintptr_t)payload, p1 = p0 + (size_t)d->payload_bytes;
-  const uintptr_t o0 = (uintptr_t)pixels, o1 = o0 + (size_t)plane * d->z * B;
-  const uintptr_t s0 = (uintptr_t)status, s1 = s0 + (size_t)d->z * sizeof(int32_t);
-  MMNN_REQUIRE(p1 <= o0 || o1 <= p0, "rle_expand: payload and pixels overlap");
-  MMNN_REQUIRE(p1 <= s0 || s1 <= p0, "rle_expand: payload and status overlap");
   const hipStream_t stream = static_cast<hipStream_t>(stream_);
   const RleWorkspace w = rle_carve(plane, d->z, B);
   uint8_t* ws = static_cast<uint8_t*>(workspace);

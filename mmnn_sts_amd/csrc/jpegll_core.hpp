@@ -2,7 +2,9 @@
 // entropy-coded data are stuffed zeros and where a marker ends it, the canonical Huffman table of T.81 Annex C, what the symbol that
 // starts at a bit position means, the successor chain over bit positions that pointer doubling resolves, and the state that carries a
 // frame from chunk to chunk.  Plain C++ over byte arrays with no HIP call: csrc/dicom_jpegll.hip runs it on LDS, and
-// tests/jpegll_core_check.cpp runs it on exact-size heap buffers under the host's sanitizers.
+// tests/jpegll_core_check.cpp runs it on exact-size heap buffers under the host's sanitizers.  The span clamp, the round of pointer
+// doubling, the exit record and the chunk-to-chunk progress are csrc/stream_core.hpp, shared with the RLE core; what is here is JPEG:
+// judging and unstuffing, the Huffman table, the successor and what a symbol is.
 //
 // A frame's data passes through a RAW window of JLL_CHUNK + JLL_LOOK bytes as the file holds them.  The first JLL_JUDGED of them are
 // judged (a byte is judged with its follower in view): kept, a stuffed zero, or the end of the data.  The kept bytes are compacted into
@@ -13,13 +15,7 @@
 // Bit positions are relative to u[0], most significant bit first.  Nothing here reads `raw` at or behind JLL_WINDOW or `u` at or behind
 // JLL_UNSTUFFED, whatever the bytes hold.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define MMNN_JLL_HD __host__ __device__ __forceinline__
-#else
-#define MMNN_JLL_HD inline
-#endif
+#include "stream_core.hpp"
 
 namespace mmnn {
 
@@ -29,20 +25,11 @@ constexpr int JLL_WINDOW = JLL_CHUNK + JLL_LOOK;
 constexpr int JLL_JUDGED = JLL_WINDOW - 1;
 constexpr int JLL_UNSTUFFED = JLL_JUDGED + 8;          // `u`: at most JLL_JUDGED kept bytes, then FF
 constexpr int JLL_BITS = 8 * JLL_CHUNK;      // bit positions of a chunk; as a successor: the chain leaves the chunk
-constexpr int JLL_ROUNDS = 13;
+constexpr int JLL_ROUNDS = 13;               // of chain_hop<JLL_BITS>: a chunk of one-bit symbols
 static_assert((1 << JLL_ROUNDS) >= JLL_BITS && JLL_BITS < 65536, "rounds of pointer doubling over uint16 positions");
 static_assert((JLL_LOOK - 1) / 2 >= 4 && JLL_CHUNK + 4 < JLL_UNSTUFFED, "look-ahead of a symbol");
 
-// A frame record's span of the device table, clamped into [0, payload_bytes): the kernel trusts neither number.
-struct JllSpan { int64_t off, len; };
-MMNN_JLL_HD JllSpan jll_clamp(int64_t off, int64_t len, int64_t payload_bytes) {
-  if (off < 0) off = 0;
-  if (off > payload_bytes) off = payload_bytes;
-  if (len < 0) len = 0;
-  if (len > payload_bytes - off) len = payload_bytes - off;
-  return JllSpan{off, len};
-}
-MMNN_JLL_HD int jll_precision(int p) { return p < 2 ? 2 : p > 16 ? 16 : p; }
+MMNN_STREAM_HD int jll_precision(int p) { return p < 2 ? 2 : p > 16 ? 16 : p; }
 
 // The canonical code of BITS / HUFFVAL (T.81 Annex C) in the form a 16-bit peek w is decoded by: lim[l] is the first code that is
 // NOT of length <= l, left-justified in 16 bits, so the code's length is the smallest l with w < lim[l] (none: w matches no code) and
@@ -53,7 +40,7 @@ struct JllTable {
   int32_t base[17];
   uint8_t val[17];
 };
-MMNN_JLL_HD void jll_build(JllTable& t, const uint8_t* bits, const uint8_t* huffval) {
+MMNN_STREAM_HD void jll_build(JllTable& t, const uint8_t* bits, const uint8_t* huffval) {
   uint32_t code = 0;
   int n = 0;
   t.lim[0] = 0;
@@ -71,33 +58,25 @@ MMNN_JLL_HD void jll_build(JllTable& t, const uint8_t* bits, const uint8_t* huff
 }
 
 // ---- the raw window -> the unstuffed bytes ---------------------------------------------------------------------------------------------
-// One frame from chunk to chunk.  `base`: payload offset of the window's first raw byte, a multiple of 16, so the window is filled by
-// aligned 16-byte loads; the data is payload[lo, hi); `entry`: the bit of `u` where the chain enters; `done`: samples decoded so far.
-struct JllState {
-  int64_t base, lo, hi, done, plane;
-  int entry, spent;
-};
-MMNN_JLL_HD JllState jll_begin(JllSpan s, int64_t plane) {
+// One frame from chunk to chunk: the progress (`entry`: the bit of `u` where the chain enters; `done`: samples decoded so far), and
+// the data, payload[lo, hi).
+struct JllState : StreamProgress { int64_t lo, hi; };
+MMNN_STREAM_HD JllState jll_begin(StreamSpan s, int64_t plane) {
   JllState st;
-  st.base = s.off & ~(int64_t)15;
+  stream_begin(st, s, plane, 0);
   st.lo = s.off;
   st.hi = s.off + s.len;
-  st.done = 0;
-  st.plane = plane;
-  st.entry = 0;
-  st.spent = s.len <= 0;
   return st;
 }
-MMNN_JLL_HD bool jll_more(const JllState& st) { return st.done < st.plane && !st.spent; }
-MMNN_JLL_HD bool jll_in(const JllState& st, int i) { return st.base + i >= st.lo && st.base + i < st.hi; }
+MMNN_STREAM_HD bool jll_in(const JllState& st, int i) { return st.base + i >= st.lo && st.base + i < st.hi; }
 // the payload offset of the raw byte in front of the window, or -1 when the data does not hold it (read by the caller: `prev`)
-MMNN_JLL_HD int64_t jll_prev_at(const JllState& st) { return st.base - 1 >= st.lo && st.base - 1 < st.hi ? st.base - 1 : -1; }
+MMNN_STREAM_HD int64_t jll_prev_at(const JllState& st) { return st.base - 1 >= st.lo && st.base - 1 < st.hi ? st.base - 1 : -1; }
 
 // What raw byte i (i < JLL_JUDGED) is: JLL_KEEP, a byte of the unstuffed data; JLL_END, the data ends in front of it (an FF that no 00
 // follows, or the first byte behind payload[lo, hi)); 0, a stuffed zero, or a byte outside the data.  Only the bytes in front of the
 // first JLL_END count.  `prev`: the raw byte in front of the window, -1 for none.
 constexpr uint32_t JLL_KEEP = 1u, JLL_END = 1u << 16;
-MMNN_JLL_HD uint32_t jll_judge(const uint8_t* raw, const JllState& st, int i, int prev) {
+MMNN_STREAM_HD uint32_t jll_judge(const uint8_t* raw, const JllState& st, int i, int prev) {
   if (!jll_in(st, i)) return st.base + i == st.hi ? JLL_END : 0u;
   const int c = raw[i];
   if (c == 0xFF) return jll_in(st, i + 1) && raw[i + 1] == 0 ? JLL_KEEP : JLL_END;
@@ -113,9 +92,9 @@ MMNN_JLL_HD uint32_t jll_judge(const uint8_t* raw, const JllState& st, int i, in
 struct JllChunk { int n_chunk, n_all, ended, last; };
 // The chunk's own bytes in terms of the exclusive prefix sum of jll_judge over i < JLL_CHUNK: `first_end`, whether an END lies among
 // them, and `kept`, the KEEPs in front of it (without one: all of them).
-MMNN_JLL_HD JllChunk jll_chunk(bool first_end, int kept) { return JllChunk{kept, kept, first_end, first_end}; }
+MMNN_STREAM_HD JllChunk jll_chunk(bool first_end, int kept) { return JllChunk{kept, kept, first_end, first_end}; }
 // The look-ahead, serially (15 bytes), for a chunk whose own bytes hold no END: its kept bytes go behind the chunk's in `u`.
-MMNN_JLL_HD void jll_look(const uint8_t* raw, const JllState& st, uint8_t* u, JllChunk& c) {
+MMNN_STREAM_HD void jll_look(const uint8_t* raw, const JllState& st, uint8_t* u, JllChunk& c) {
   for (int i = JLL_CHUNK; i < JLL_JUDGED; ++i) {
     const uint32_t f = jll_judge(raw, st, i, -1);
     if (f == JLL_END) {
@@ -125,14 +104,14 @@ MMNN_JLL_HD void jll_look(const uint8_t* raw, const JllState& st, uint8_t* u, Jl
     if (f == JLL_KEEP && c.n_all < JLL_UNSTUFFED) u[c.n_all++] = raw[i];
   }
 }
-MMNN_JLL_HD int64_t jll_endbits(const JllChunk& c) { return c.ended ? 8 * (int64_t)c.n_all : (int64_t)1 << 40; }
+MMNN_STREAM_HD int64_t jll_endbits(const JllChunk& c) { return c.ended ? 8 * (int64_t)c.n_all : (int64_t)1 << 40; }
 
 // ---- a symbol --------------------------------------------------------------------------------------------------------------------------
 // The symbol that starts at bit p (p < 8 * n_chunk <= JLL_BITS): `len` bits of code and extra bits, and the difference modulo 2^16.
 // `cut`: its 16 bits (FF-padded behind the data) match no code, its value exceeds 16, or it does not end in front of the data's end:
 // it gives no output and ends the frame.  Reads u[p / 8 .. p / 8 + 4].
 struct JllSym { int len, cut; uint16_t diff; };
-MMNN_JLL_HD JllSym jll_classify(const JllTable& t, const uint8_t* u, int p, int64_t endbits) {
+MMNN_STREAM_HD JllSym jll_classify(const JllTable& t, const uint8_t* u, int p, int64_t endbits) {
   const int b = p >> 3, o = p & 7;
   const uint64_t v = (uint64_t)u[b] << 32 | (uint64_t)u[b + 1] << 24 | (uint64_t)u[b + 2] << 16 | (uint64_t)u[b + 3] << 8 | (uint64_t)u[b + 4];
   const uint32_t w = (uint32_t)(v >> (24 - o)) & 0xFFFFu;
@@ -154,42 +133,19 @@ MMNN_JLL_HD JllSym jll_classify(const JllTable& t, const uint8_t* u, int p, int6
 // The symbols of a frame form a chain: each says where the next one starts.  jll_successor: the bit where the symbol behind the one at p
 // starts (whatever p holds, were a symbol to start there), or JLL_BITS where the chain leaves the chunk: the next one starts in the next
 // window's bytes, or the symbol at p is cut.
-MMNN_JLL_HD int jll_successor(const JllTable& t, const uint8_t* u, int p, const JllChunk& c) {
+MMNN_STREAM_HD int jll_successor(const JllTable& t, const uint8_t* u, int p, const JllChunk& c) {
   if (p >= 8 * c.n_chunk) return JLL_BITS;
   const JllSym s = jll_classify(t, u, p, jll_endbits(c));
   const int j = p + s.len;
   return s.cut || j >= 8 * c.n_chunk ? JLL_BITS : j;
 }
-// One round of pointer doubling for position p, in two phases with a barrier between them and behind them.  Phase one: a marked p marks
-// hop[p], and the value to store is read, hop[hop[p]].  Phase two: hop[p] = that value.  With mark[entry] = 1 and hop = jll_successor
-// before round 0, after round k every chain member up to 2^(k+1) - 1 steps from the entry is marked and hop[p] is 2^(k+1) steps on;
-// marks only ever land on chain members.  JLL_ROUNDS rounds cover a chunk of one-bit symbols; the rounds can stop once hop[entry] has
-// left the chunk.
-MMNN_JLL_HD uint16_t jll_hop(const uint16_t* hop, uint8_t* mark, int p) {
-  const int j = hop[p];
-  if (j >= JLL_BITS) return (uint16_t)JLL_BITS;
-  if (mark[p]) mark[j] = 1;
-  return hop[j];
-}
-MMNN_JLL_HD bool jll_enters(int entry, const JllChunk& c) { return entry >= 0 && entry < 8 * c.n_chunk; }
+MMNN_STREAM_HD bool jll_enters(int entry, const JllChunk& c) { return entry >= 0 && entry < 8 * c.n_chunk; }
 // Where the chain leaves the chunk, from its last member in it (marked, jll_successor == JLL_BITS): `next` is the bit where the next
 // symbol starts, and `spent` says that a symbol was cut or the data ended in this chunk's own bytes: nothing follows.
-struct JllExit { int next, spent; };
-MMNN_JLL_HD JllExit jll_exit(const JllSym& s, int p, const JllChunk& c) { return JllExit{p + s.len, s.cut || c.last}; }
-MMNN_JLL_HD bool jll_leaves(const JllSym& s, int p, const JllChunk& c) { return s.cut || p + s.len >= 8 * c.n_chunk; }
+MMNN_STREAM_HD ChainExit jll_exit(const JllSym& s, int p, const JllChunk& c) { return ChainExit{p + s.len, s.cut || c.last}; }
+MMNN_STREAM_HD bool jll_leaves(const JllSym& s, int p, const JllChunk& c) { return s.cut || p + s.len >= 8 * c.n_chunk; }
 
-// what of the chunk's `total` symbols the frame still takes
-MMNN_JLL_HD uint32_t jll_take(const JllState& st, uint32_t total) {
-  const int64_t room = st.plane - st.done;
-  return (int64_t)total < room ? total : (uint32_t)room;
-}
-MMNN_JLL_HD void jll_advance(JllState& st, JllExit w, const JllChunk& c, uint32_t taken) {
-  st.done += taken;
-  st.spent = w.spent;
-  st.base += JLL_CHUNK;
-  st.entry = w.next - 8 * c.n_chunk;
-}
-// behind the last chunk: the frame is short (status 1, its differences from `done` on are zeros) unless it is full
-MMNN_JLL_HD bool jll_short(const JllState& st) { return st.done < st.plane; }
+// the next window's bit 0 is this one's bit 8 * n_chunk
+MMNN_STREAM_HD void jll_advance(JllState& st, ChainExit w, const JllChunk& c, uint32_t taken) { stream_advance(st, w, taken, JLL_CHUNK, 8 * c.n_chunk); }
 
 }  // namespace mmnn

@@ -214,10 +214,18 @@ def _stage_fragments(series: DicomSeries, z: int, record_bytes: int) -> _StagedF
     return _StagedFragments(stage, host, at_records, at_payload, starts, int(starts[-1]), scale, integer)
 
 
-def _decode_expanded(series: DicomSeries, device, shape, s: _StagedFragments, staged, words, status, fault: str) -> DeviceVolume:
-    """Behind the kernel that turned the staged fragments into `words`, the bytes of the uncompressed series: `mmnn_decode_slices`, then
-    the one read-back of the z status words; a frame whose word is not 0 raises ConfigurationError with its file and `fault`."""
+def _decode_staged(series: DicomSeries, device, shape, s: _StagedFragments, call: str, workspace: str, desc_type, fault: str) -> DeviceVolume:
+    """The staged fragments, their records filled, through `call` (`mmnn_rle_expand` or `mmnn_jpegll_decode`, with the bytes that
+    `workspace`, its `*_workspace_bytes`, asks for) into the bytes of the uncompressed series, then `mmnn_decode_slices` and the one
+    read-back of the z status words; a frame whose word is not 0 raises ConfigurationError with its file and `fault`."""
     x, y, z = shape
+    staged = s.stage.to(device, non_blocking=True)
+    words = torch.empty(x * y * z * (series.bits_allocated // 8), dtype=torch.uint8, device=device)
+    status = torch.empty(z, dtype=torch.int32, device=device)
+    ws = torch.empty(_lib.count(workspace, x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
+    desc = desc_type(x, y, z, series.bits_allocated, s.payload_bytes)
+    _lib.enqueue(call, ctypes.byref(desc), staged.data_ptr() + s.at_payload, staged.data_ptr() + s.at_records, words.data_ptr(),
+                 status.data_ptr(), ws.data_ptr(), device=device)
     code = _integer_code(series.bits_allocated, series.signed) if s.integer else TYPE_CODES[np.dtype("float64")]
     desc = _lib.DecodeSlicesDesc(x, y, z, series.bits_allocated, series.bits_stored, series.high_bit, int(series.signed), code)
     out = torch.empty(x * y * z * (series.bits_allocated // 8 if s.integer else 8), dtype=torch.uint8, device=device)
@@ -243,14 +251,8 @@ def _decode_rle_series(series: DicomSeries, device, x: int, y: int, z: int) -> D
     for k, segments in enumerate(series.segments):
         table[k] = segments
         table[k, :, 0] += s.starts[k]
-    staged = s.stage.to(device, non_blocking=True)
-    words = torch.empty(x * y * z * planes, dtype=torch.uint8, device=device)
-    status = torch.empty(z, dtype=torch.int32, device=device)
-    ws = torch.empty(_lib.count("mmnn_rle_workspace_bytes", x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
-    rle = _lib.RleDesc(x, y, z, series.bits_allocated, s.payload_bytes)
-    _lib.enqueue("mmnn_rle_expand", ctypes.byref(rle), staged.data_ptr() + s.at_payload, staged.data_ptr() + s.at_records, words.data_ptr(),
-                 status.data_ptr(), ws.data_ptr(), device=device)
-    return _decode_expanded(series, device, (x, y, z), s, staged, words, status, f"an RLE segment ends before its {x} x {y} byte plane is full")
+    return _decode_staged(series, device, (x, y, z), s, "mmnn_rle_expand", "mmnn_rle_workspace_bytes", _lib.RleDesc,
+                          f"an RLE segment ends before its {x} x {y} byte plane is full")
 
 
 JPEGLL_FRAME = np.dtype([("offset", "<i8"), ("length", "<i8"), ("precision", "<i4"), ("bits", "u1", 16), ("huffval", "u1", 17), ("reserved", "u1", 3)])
@@ -269,15 +271,8 @@ def _decode_jpegll_series(series: DicomSeries, device, x: int, y: int, z: int) -
         records[k]["offset"], records[k]["length"], records[k]["precision"] = int(s.starts[k]) + scan.offset, scan.length, scan.precision
         records[k]["bits"] = scan.bits
         records[k]["huffval"][:len(scan.huffval)] = scan.huffval
-    staged = s.stage.to(device, non_blocking=True)
-    words = torch.empty(x * y * z * (series.bits_allocated // 8), dtype=torch.uint8, device=device)
-    status = torch.empty(z, dtype=torch.int32, device=device)
-    ws = torch.empty(_lib.count("mmnn_jpegll_workspace_bytes", x, y, z, series.bits_allocated), dtype=torch.uint8, device=device)
-    desc = _lib.JpegllDesc(x, y, z, series.bits_allocated, s.payload_bytes)
-    _lib.enqueue("mmnn_jpegll_decode", ctypes.byref(desc), staged.data_ptr() + s.at_payload, staged.data_ptr() + s.at_records, words.data_ptr(),
-                 status.data_ptr(), ws.data_ptr(), device=device)
-    return _decode_expanded(series, device, (x, y, z), s, staged, words, status,
-                            f"the JPEG stream ends, or holds an invalid code, before its {x} x {y} samples are decoded")
+    return _decode_staged(series, device, (x, y, z), s, "mmnn_jpegll_decode", "mmnn_jpegll_workspace_bytes", _lib.JpegllDesc,
+                          f"the JPEG stream ends, or holds an invalid code, before its {x} x {y} samples are decoded")
 
 
 def _default_device(out):                    # where a call that names no device works

@@ -1,11 +1,13 @@
 """Helpers of the JPEG Lossless tests: the plain restatement of the `mmnn_jpegll_decode` contract (include/mmnn_sts.h) -- byte stuffing,
 the canonical codes of T.81 Annex C decoded bit by bit as Annex F.2.2.3 does, the differences of H.1.2.2 and predictor 1 walked serially
 --, an encoder of its own that writes one bit at a time, the volumes, hand-made streams and hostile streams that the CPU and GPU tests
-share, and the binary fixture that the stand-alone host check of csrc/jpegll_core.hpp reads.  Shares no code with mmnn_sts_amd (neither
-the kernel's core nor synth_dicom's encoder)."""
+share, and the payload as ingest stages it (the fixture of the stand-alone host check is tests/_dicom_stream_harness.py).  Shares no
+code with mmnn_sts_amd (neither the kernel's core nor synth_dicom's encoder)."""
 import struct
 
 import numpy as np
+
+from tests._dicom_stream_harness import align16
 
 K3 = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12)))                 # T.81 Table K.3
 EXTENDED = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0), tuple(range(17)))           # one more code per length up to 14 bits
@@ -147,7 +149,8 @@ def pack_payload(streams):
     content, RECORD array), as ingest stages the fragments."""
     payload, records = bytearray(), []
     for data, precision, table in streams:
-        payload += bytes(-len(payload) % 16) + b"\xff\xd8" + bytes(14)       # (a fragment starts with markers, never with data)
+        align16(payload)
+        payload += b"\xff\xd8" + bytes(14)      # (a fragment starts with markers, never with data)
         records.append(record(len(payload), len(data), precision, table))
         payload += bytes(data)
     return bytes(payload), np.array(records, dtype=RECORD)
@@ -176,9 +179,8 @@ def pack_fragments(fragments):
     pointing behind its stream's SOS and reaching to the fragment's end."""
     payload, records = bytearray(), []
     for fragment in fragments:
-        payload += bytes(-len(payload) % 16)
         at, precision, table = scan_of(fragment)
-        records.append(record(len(payload) + at, len(fragment) - at, precision, table))
+        records.append(record(align16(payload) + at, len(fragment) - at, precision, table))
         payload += bytes(fragment)
     return bytes(payload), np.array(records, dtype=RECORD)
 
@@ -319,28 +321,3 @@ def lying_records():
             "negative_length": (streams, lie(None, -5)), "offset_at_the_last_byte": (streams, lie(lambda r, p: len(p) - 1, 99)),
             "runs_into_the_next_frame": (streams, lie(lambda r, p: int(r[1]["offset"]) + int(r[1]["length"]) - 5, 1 << 40)),
             "length_past_the_payload_from_the_markers": (streams, lie(lambda r, p: int(r[1]["offset"]) - 16, 1 << 40))}
-
-
-# ---- the fixture of the stand-alone host check -------------------------------------------------------------------------------------
-def write_fixture(path, cases):
-    """`cases`: [(x, y, z, bits_allocated, payload, records)].  Little endian: int32 count; per case int32 x, y, z, bits_allocated, int64
-    payload_bytes, the z records of 56 bytes, the payload."""
-    with open(path, "wb") as f:
-        f.write(struct.pack("<i", len(cases)))
-        for x, y, z, bits, payload, records in cases:
-            f.write(struct.pack("<4iq", x, y, z, bits, len(payload)))
-            f.write(np.ascontiguousarray(records, dtype=RECORD).tobytes())
-            f.write(payload)
-
-
-def read_results(data, cases):
-    """The host check's output for `cases`: per case z int32 status words, then the x*y*z words' bytes."""
-    out, at = [], 0
-    for x, y, z, bits, _, _ in cases:
-        status = np.frombuffer(data, dtype="<i4", count=z, offset=at)
-        at += 4 * z
-        n = x * y * z * bits // 8
-        out.append((np.frombuffer(data, dtype=np.uint8, count=n, offset=at).view(f"<u{bits // 8}").reshape(z, y, x), status))
-        at += n
-    assert at == len(data)
-    return out

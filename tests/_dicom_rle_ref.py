@@ -1,10 +1,12 @@
 """Helpers of the RLE Lossless tests: the plain numpy restatement of the `mmnn_rle_expand` contract (include/mmnn_sts.h), a builder of
-fragments from hand-made segment streams, the shapes and the hostile streams that the CPU and GPU tests share, and the binary fixture
-that the stand-alone host check of csrc/rle_core.hpp reads.  Shares no code with mmnn_sts_amd (neither the kernel's core nor
-synth_dicom's encoder)."""
+fragments from hand-made segment streams, the shapes and the hostile streams that the CPU and GPU tests share, and the payload as ingest
+stages it (the fixture of the stand-alone host check is tests/_dicom_stream_harness.py).  Shares no code with mmnn_sts_amd (neither the
+kernel's core nor synth_dicom's encoder)."""
 import struct
 
 import numpy as np
+
+from tests._dicom_stream_harness import align16
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------
@@ -168,38 +170,16 @@ def malformed_frames(name, bits=8):
     return [p[0] for p in pairs], [p[1] for p in pairs], x, y, bits
 
 
-# ---- the fixture of the stand-alone host check -------------------------------------------------------------------------------------
+# ---- the payload as ingest stages it; a record of the host check's fixture (tests/_dicom_stream_harness.py) is one int64 ---------------
+RECORD = np.dtype("<i8")
+
+
 def pack_payload(fragments, tables):
     """(payload with every fragment on a 16-byte boundary, (z, B, 2) table of payload offsets and lengths), as ingest stages them."""
     payload, table = bytearray(), []
     for fragment, t in zip(fragments, tables):
-        payload += bytes(-len(payload) % 16)
         t = np.array(t, dtype=np.int64)
-        t[:, 0] += len(payload)
+        t[:, 0] += align16(payload)
         table.append(t)
         payload += fragment
     return bytes(payload), np.stack(table)
-
-
-def write_fixture(path, cases):
-    """`cases`: [(x, y, z, bits, payload, table)].  Little endian: int32 count; per case int32 x, y, z, bits, int64 payload_bytes, the
-    z * B * 2 int64 of the table, the payload."""
-    with open(path, "wb") as f:
-        f.write(struct.pack("<i", len(cases)))
-        for x, y, z, bits, payload, table in cases:
-            f.write(struct.pack("<4iq", x, y, z, bits, len(payload)))
-            f.write(np.ascontiguousarray(table, dtype="<i8").tobytes())
-            f.write(payload)
-
-
-def read_results(data, cases):
-    """The host check's output for `cases`: per case z int32 status words, then the x*y*z words' bytes."""
-    out, at = [], 0
-    for x, y, z, bits, _, _ in cases:
-        status = np.frombuffer(data, dtype="<i4", count=z, offset=at)
-        at += 4 * z
-        n = x * y * z * bits // 8
-        out.append((np.frombuffer(data, dtype=np.uint8, count=n, offset=at).view(f"<u{bits // 8}").reshape(z, y, x), status))
-        at += n
-    assert at == len(data)
-    return out

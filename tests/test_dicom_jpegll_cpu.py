@@ -3,11 +3,9 @@ restatement (tests/_dicom_jpegll_ref.py), the reader's fields and refusals on JP
 refusals of `mmnn_jpegll_decode`, and the stand-alone host check of the positional core (csrc/jpegll_core.hpp built with the host
 compiler under the address and undefined-behaviour sanitizers), which the hostile streams pass here before
 tests/test_dicom_jpegll_gpu.py hands them to the kernel."""
-import ctypes
 import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,16 +14,11 @@ from mmnn_sts_amd.data import dicom, synth_dicom
 from mmnn_sts_amd.exceptions.exceptions import ConfigurationError
 from tests import _dicom_jpegll_ref as R
 from tests import _dicom_ref as D
+from tests import _dicom_stream_harness as H
+from tests._dicom_stream_harness import DELIMITER, PAY, PIX, STA, WS, item as _item, write as _write
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SV1, P14 = "1.2.840.10008.1.2.4.70", "1.2.840.10008.1.2.4.57"
 BITS = {"u1": (8, 8, 7, 0), "i2": (16, 16, 15, 1), "u2": (16, 16, 15, 0), "i4": (32, 32, 31, 1)}
-
-
-def _write(path, data):
-    with open(path, "wb") as f:
-        f.write(data)
-    return str(path)
 
 
 # ---- typed-in streams ------------------------------------------------------------------------------------------------------------------
@@ -106,11 +99,6 @@ def test_frame_tables_reach_code_lengths_1_and_16():
 
 
 # ---- one file ------------------------------------------------------------------------------------------------------------------------
-def _item(value, tag=(0xFFFE, 0xE000), length=None):
-    return struct.pack("<HHI", tag[0], tag[1], len(value) if length is None else length) + value
-
-
-DELIMITER = _item(b"", (0xFFFE, 0xE0DD))
 SOI, EOI = b"\xff\xd8", b"\xff\xd9"
 
 
@@ -280,44 +268,20 @@ def test_defined_length_pixel_data_and_the_other_jpeg_syntaxes_stay_refused(tmp_
 # ---- mmnn_jpegll_decode refuses bad arguments before any launch (no GPU: the pointers are fake and never dereferenced) -----------------
 @pytest.fixture(scope="module")
 def lib():
-    from mmnn_sts_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    return _lib.lib()
+    return H.built_lib()
 
 
-PAY, FRM, PIX, STA, WS = 0x7F0000100000, 0x7F0000200000, 0x7F0000900000, 0x7F0000080000, 0x7F0001000000     # far apart, 256-byte aligned
-_GOOD = dict(x=8, y=4, z=2, bits_allocated=16, payload_bytes=4096)
-_BAD_CALLS = {
-    "null payload": ({}, (0, FRM, PIX, STA, WS), "null"), "null frames": ({}, (PAY, 0, PIX, STA, WS), "null"),
-    "null pixels": ({}, (PAY, FRM, 0, STA, WS), "null"), "null status": ({}, (PAY, FRM, PIX, 0, WS), "null"),
-    "null workspace": ({}, (PAY, FRM, PIX, STA, 0), "null"),
-    "zero extent": (dict(x=0), (PAY, FRM, PIX, STA, WS), "non-positive extent"), "negative extent": (dict(z=-1), (PAY, FRM, PIX, STA, WS), "non-positive extent"),
-    "2^31 voxels": (dict(x=2048, y=2048, z=512), (PAY, FRM, PIX, STA, WS), "2\\^31"),
-    "bits_allocated 12": (dict(bits_allocated=12), (PAY, FRM, PIX, STA, WS), "bits_allocated"),
-    "bits_allocated 32": (dict(bits_allocated=32), (PAY, FRM, PIX, STA, WS), "bits_allocated"),
-    "bits_allocated 1": (dict(bits_allocated=1), (PAY, FRM, PIX, STA, WS), "bits_allocated"),
-    "no payload bytes": (dict(payload_bytes=0), (PAY, FRM, PIX, STA, WS), "payload_bytes"),
-    "payload misaligned": ({}, (PAY + 8, FRM, PIX, STA, WS), "payload not aligned"), "frames misaligned": ({}, (PAY, FRM + 4, PIX, STA, WS), "frames not aligned"),
-    "pixels misaligned": ({}, (PAY, FRM, PIX + 1, STA, WS), "pixels not aligned"), "status misaligned": ({}, (PAY, FRM, PIX, STA + 2, WS), "status not aligned"),
-    "workspace misaligned": ({}, (PAY, FRM, PIX, STA, WS + 8), "workspace not aligned"),
-    "pixels inside payload": ({}, (PAY, FRM, PAY + 64, STA, WS), "payload and pixels overlap"), "payload inside pixels": ({}, (PIX + 32, FRM, PIX, STA, WS), "payload and pixels overlap"),
-    "status inside payload": ({}, (PAY, FRM, PIX, PAY + 4092, WS), "payload and status overlap"),
-}
+_BAD_CALLS = H.bad_calls("frames", too_deep=32)
 
 
 @pytest.mark.parametrize("name", sorted(_BAD_CALLS))
 def test_jpegll_decode_refuses_before_launching(lib, name):
     from mmnn_sts_amd import _lib
-    fields, pointers, reason = _BAD_CALLS[name]
-    desc = _lib.JpegllDesc(**dict(_GOOD, **fields))
-    assert lib.mmnn_jpegll_decode(ctypes.byref(desc), *(p or None for p in pointers), None) == 1
-    with pytest.raises(ValueError, match=reason):
-        _lib.check(1, "mmnn_jpegll_decode")
+    H.assert_refused(lib, "mmnn_jpegll_decode", _lib.JpegllDesc, *_BAD_CALLS[name])
 
 
 def test_jpegll_decode_refuses_a_null_descriptor(lib):
-    assert lib.mmnn_jpegll_decode(None, PAY, FRM, PIX, STA, WS, None) == 1
+    assert lib.mmnn_jpegll_decode(None, PAY, H.TAB, PIX, STA, WS, None) == 1
 
 
 def test_jpegll_workspace_bytes_is_monotone_and_refuses_bad_extents(lib):
@@ -362,25 +326,10 @@ def host_check_cases():
 
 
 def test_positional_core_on_the_host_under_sanitizers(tmp_path):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "jpegll_core_check")
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                            os.path.join(ROOT, "tests", "jpegll_core_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-4000:]
     cases = host_check_cases()
-    packed = [c[1:] for c in cases]
-    fixture = str(tmp_path / "streams.bin")
-    R.write_fixture(fixture, packed)
-    run = subprocess.run([exe, fixture], capture_output=True, timeout=300)
-    assert run.returncode == 0, run.stderr.decode("utf-8", "replace")[-4000:]
-    results = R.read_results(run.stdout, packed)
-    for (name, x, y, z, bits, payload, records), (pixels, status) in zip(cases, results):
-        want_pixels, want_status = R.decode_ref(payload, records, x, y, bits)
-        assert np.array_equal(status, want_status), f"{name}: status {status.tolist()}, restatement {want_status.tolist()}"
-        bad = np.argwhere(pixels != want_pixels)
-        assert bad.shape[0] == 0, f"{name}: {bad.shape[0]} words differ, the first at (k, j, i) = {tuple(bad[0])}"
+    results = H.run_host_check(tmp_path, "jpegll_core_check", [c[1:] for c in cases], R.RECORD)
+    for (name, x, y, z, bits, payload, records), got in zip(cases, results):
+        _, status = H.assert_equals_restatement(name, got, R.decode_ref(payload, records, x, y, bits), who="host check")
         if name.startswith(("malformed_", "lie_")):
             assert status.tolist() == [0, 1, 0], name
         else:

@@ -5,9 +5,6 @@ it is the code the uncompressed twin runs); and a series with a truncated stream
 
 Every stream here, the malformed ones first of all, passes the stand-alone host check of the positional core under the sanitizers
 (tests/test_dicom_jpegll_cpu.py::test_positional_core_on_the_host_under_sanitizers takes the same cases from `host_check_cases`)."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -17,51 +14,20 @@ from mmnn_sts_amd.data import cache as C
 from mmnn_sts_amd.data import dicom, ingest, synth_dicom, synth_nifti
 from mmnn_sts_amd.exceptions.exceptions import ConfigurationError
 from tests import _dicom_jpegll_ref as R
+from tests import _dicom_stream_harness as H
+from tests._dicom_stream_harness import DEV, dataset as _dataset
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GUARD = 256
-PATTERN = 0xA5
-
-
-def _guarded(content, lead=GUARD):
-    """A device buffer of `content` (uint8 array, or a byte count to leave patterned) between two patterned guards; (buffer, lead, size)."""
-    n = content if isinstance(content, int) else content.size
-    buf = torch.full((lead + n + GUARD,), PATTERN, dtype=torch.uint8, device=DEV)
-    if not isinstance(content, int):
-        buf[lead:lead + n] = torch.from_numpy(np.array(content, dtype=np.uint8)).to(DEV)
-    return buf, lead, n
 
 
 def _decode(payload, records, x, y, bits):
-    """The kernel's (pixels (z, y, x), status (z,)).  Payload, frame records, pixels, status and workspace each sit inside a larger
-    buffer: the inputs must come back unchanged, the guards of all five must keep their pattern."""
-    z, B = len(records), bits // 8
-    pay = np.frombuffer(payload, dtype=np.uint8)
+    """The kernel's (pixels (z, y, x), status (z,)) through `H.guarded_call`."""
     rec = np.ascontiguousarray(records, dtype=R.RECORD).view(np.uint8).reshape(-1)
-    bufs = {"payload": _guarded(pay), "frames": _guarded(rec), "pixels": _guarded(x * y * z * B), "status": _guarded(4 * z),
-            "workspace": _guarded(_lib.count("mmnn_jpegll_workspace_bytes", x, y, z, bits))}
-    ptr = {k: b.data_ptr() + lead for k, (b, lead, _) in bufs.items()}
-    desc = _lib.JpegllDesc(x, y, z, bits, pay.size)
-    _lib.check(_lib.lib().mmnn_jpegll_decode(ctypes.byref(desc), ptr["payload"], ptr["frames"], ptr["pixels"], ptr["status"], ptr["workspace"],
-                                             torch.cuda.current_stream().cuda_stream), "mmnn_jpegll_decode")
-    torch.cuda.synchronize()
-    host = {k: b.cpu().numpy() for k, (b, _, _) in bufs.items()}
-    for k, (_, lead, n) in bufs.items():
-        assert (host[k][:lead] == PATTERN).all() and (host[k][lead + n:] == PATTERN).all(), f"bytes outside `{k}` were written"
-    assert np.array_equal(host["payload"][GUARD:GUARD + pay.size], pay) and np.array_equal(host["frames"][GUARD:GUARD + rec.size], rec)
-    inner = lambda k: host[k][bufs[k][1]:bufs[k][1] + bufs[k][2]]
-    return inner("pixels").view(f"<u{B}").reshape(z, y, x), inner("status").view("<i4")
+    return H.guarded_call("mmnn_jpegll_decode", _lib.JpegllDesc, "frames", rec, payload, x, y, len(records), bits)
 
 
 def _assert_equals_restatement(name, payload, records, x, y, bits):
-    pixels, status = _decode(payload, records, x, y, bits)
-    want_pixels, want_status = R.decode_ref(payload, records, x, y, bits)
-    assert np.array_equal(status, want_status), f"{name}: status {status.tolist()}, restatement {want_status.tolist()}"
-    bad = np.argwhere(pixels != want_pixels)
-    assert bad.shape[0] == 0, (f"{name}: {bad.shape[0]} words differ, the first at (k, j, i) = {tuple(bad[0])}: device "
-                               f"{int(pixels[tuple(bad[0])]):#x}, restatement {int(want_pixels[tuple(bad[0])]):#x}")
-    return pixels, status
+    return H.assert_equals_restatement(name, _decode(payload, records, x, y, bits), R.decode_ref(payload, records, x, y, bits))
 
 
 @pytest.mark.parametrize("table", ["default", "frame"])
@@ -124,11 +90,6 @@ def test_records_that_lie_are_clamped(name):
 
 
 # ---- a NIfTI tree, its uncompressed, RLE and JPEG Lossless twins through the collate ----------------------------------------------------
-def _dataset(tree):
-    from mmnn_sts_amd.data.ImageDatasets import T1T2SurvivalDataset
-    return T1T2SurvivalDataset(os.path.join(tree["image_loc"], "t1"), os.path.join(tree["image_loc"], "t2"), tree["data_loc"], tree["key_loc"])
-
-
 @pytest.fixture(scope="module")
 def trees(tmp_path_factory):
     root = tmp_path_factory.mktemp("jpegll_twins")
